@@ -2,7 +2,7 @@
 """Headline benchmark: MCTS simulations / second, Pendulum-v1, 4096 trees per GPU, n_sims=200, 2x256 ELU MLP
 (BASELINE.json `metric`).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 N = 1  (config C): a "step" is one whole search (4096 trees x 200 simulations = ONE launch of the fused search kernel) over
@@ -21,6 +21,8 @@ N > 1  (config D): one process per GPU (spawned here when the script was not sta
        `extra.search_only` is the same loop without the collectives; rank 0 adds `cpu_baseline` after the timed region.
        Rendezvous and collectives are bounded (--dist-timeout): a rank that never arrives or dies fails the run instead of hanging it.
 Rank 0 prints ONE JSON line.
+--dump-outputs DIR: rank 0 also writes what the timed loop's last step computed as DIR/<name>.npy (see dump_outputs), so that two
+       builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -277,6 +279,22 @@ def time_search(eng, steps, warmup):
     return float(np.median(ms)), float(np.mean(ms))
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: budget of all files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` as path/<name>.npy, float64 kept, everything else as float32 (the counts are exact
+    there).  If the arrays together exceed DUMP_BYTES, each keeps a fixed, seeded sample of its rows (first axis) in proportion."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(a, dtype=np.float64 if np.asarray(a).dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = max(1, int(a.shape[0] * DUMP_BYTES // total))
+            a = a[np.sort(np.random.default_rng(34).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def kernel_name(eng):
     """The kernel(s) the engine's last search ran as, in rocprofv3's spelling (the engine's own account, not a constant here)."""
     return eng.search_info()["kernel_name"]
@@ -450,6 +468,8 @@ def spawn(args):
                      ("--no-cpu-baseline", args.no_cpu_baseline)):
         if on:
             cmd.append(flag)
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     sys.exit(subprocess.call(cmd))
 
 
@@ -475,6 +495,7 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="N = 1: skip the config B / E lines")
     ap.add_argument("--e-trees", type=int, default=1024, help="N > 1: trees per GPU of the config E leg (4x1024 MLP, BASELINE.json configs[4]: 8192 trees over 8 GPUs)")
     ap.add_argument("--e-searches", type=int, default=5, help="N > 1: timed searches of the config E leg (0: skip the leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed loop's last step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.traffic_probe:
@@ -536,6 +557,8 @@ def main():
         eng.sync()
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:   # return_results of the last timed search (every later search advances the engine's search index)
+            dump_outputs(args.dump_outputs, eng.results())
         kmed, kmean = time_search(eng, min(args.steps, 10), 0)   # separate pass: the event reads would serialise the timed loop
         res = eng.results()
         assert (res["counts"].sum(1) == N_SIMS).all()
@@ -637,6 +660,13 @@ def main():
         tlog["on"] = False
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            eng.sync()
+            last = (eng.selfplay_ring()[2] - 1) % (2 * K)         # the ring slot the last timed step wrote
+            out = {"replay_rows": ring.reshape(2 * K * B, RL)[last * B:(last + 1) * B].cpu().numpy()}
+            if verify["gathers"]:
+                out["gathered_rows"] = gathered.cpu().numpy()     # every rank's block of the last all-gather
+            dump_outputs(args.dump_outputs, out)
         barrier()
         t1 = time.perf_counter()
         run(args.steps, False)

@@ -67,7 +67,8 @@ def _run(engine_cls, kw, desc, blob, roots, carry=None, sidx=0, forms=None):
     out = (e.results(), e.dump_tree(), e.root_children(), e.root_eval())
     if forms is not None:
         forms.append(_kernel_form(e))
-        _last_kernel_name["name"] = e.search_info()["kernel_name"]
+        info = e.search_info()
+        _last_kernel_name["name"], _last_kernel_name["team_fallbacks"] = info["kernel_name"], info["team_fallbacks"]
     e.close()
     return out
 
@@ -180,39 +181,47 @@ def test_hip_bit_exact_vs_oracle(native, cfg, variant, monkeypatch):
     launches, and for 2x256 networks the workgroup shapes: eight waves / 16 trees (four of them walking: the default in continuous
     mode), four waves (the general shape) and eight waves / 32 trees (chosen by itself for batches of more 16-tree groups than CUs); in discrete mode one trace per simulation step (the round-3 loop)
     and as many as a tree can run without the network (default: at most five); full 16-tree tiles where small batches of small
-    networks take half-filled ones."""
+    networks take half-filled ones.  Where a variant's path does not exist for the configuration (`moot` says why), its forcing
+    variable must be ignored: the same kernel as an engine created without it, the same records."""
     env, mode, hidden, act, n_sims, extra = cfg
     extra = dict(extra)
     ncomp = extra.pop("_ncomp", 0)
     ln = extra.pop("_ln", False)
+    moot = None
+    forced = {"stream_weights": "AZG_FORCE_STREAM_WEIGHTS", "global_tree": "AZG_FORCE_GLOBAL_TREE", "waves8": "AZG_WAVES", "waves4": "AZG_WAVES",
+              "groups2": "AZG_GROUPS", "trace_cap1": "AZG_TRACE_CAP", "trace_cap64": "AZG_TRACE_CAP", "no_spec": "AZG_NO_SPEC",
+              "tile16": "AZG_TILE_TREES", "persistent": "AZG_FORCE_PERSISTENT", "launches": "AZG_LS_TEAM"}.get(variant)
     if variant == "stream_weights":
         monkeypatch.setenv("AZG_FORCE_STREAM_WEIGHTS", "1")
     if variant == "global_tree":
         monkeypatch.setenv("AZG_FORCE_GLOBAL_TREE", "1")
     if variant in ("waves8", "waves4", "groups2"):
         if hidden != [256, 256] or ln or ncomp or mode != 1:
-            pytest.skip("the 8-wave workgroups exist for 2x256 squashed-Normal networks (continuous mode)")
+            moot = "the 8-wave workgroups exist for 2x256 squashed-Normal networks (continuous mode)"
         monkeypatch.setenv(*(("AZG_WAVES", variant[-1]) if variant.startswith("waves") else ("AZG_GROUPS", "2")))
     if variant in ("trace_cap1", "trace_cap64"):
         if mode != 0 or max(hidden) > 256:
-            pytest.skip("several traces per step: the discrete persistent search kernels")
+            moot = "several traces per step: the discrete persistent search kernels"
         monkeypatch.setenv("AZG_TRACE_CAP", variant[len("trace_cap"):])
     if variant == "no_spec":
         # register-resident one-layer networks with common parameters run kernels specialised at compile time (dispatch.cuh: SPEC);
         # this variant forces the general kernels on the same inputs
         # (SPEC kernels keep their trees in LDS with 8-bit ids: at most 255 records per tree -- n_sims + 2 in continuous mode, the root
         # plus two edges per evaluated node in CartPole's discrete mode; cfg0, the headline shape with its 202 records, is one of them)
+        # -- and so do the team kernels of 1024-wide Pendulum-v1 networks (team_dispatch.cuh: the BASELINE config E shape)
         records = n_sims + 2 if mode == 1 else 1 + 2 * (n_sims + 1)
-        if len(hidden) != 2 or max(hidden) > 256 or ln or ncomp or extra.get("epsilon", 0.0) != 0.0 or records > 255 or env in (3, 5):
-            pytest.skip("no compile-time specialised kernel exists for this configuration")
+        one_launch = not (len(hidden) != 2 or max(hidden) > 256 or ln or ncomp or extra.get("epsilon", 0.0) != 0.0 or records > 255 or env in (3, 5))
+        team = env == 2 and len(hidden) >= 2 and max(hidden) == 1024 and not ln and not ncomp and extra.get("epsilon", 0.0) == 0.0 and records <= 255
+        if not (one_launch or team):
+            moot = "no compile-time specialised kernel exists for this configuration"
         monkeypatch.setenv("AZG_NO_SPEC", "1")
     if variant == "tile16":
         if max(hidden) > 128 or len(hidden) != 2 or ln or ncomp:
-            pytest.skip("half-filled tiles exist for register-resident networks up to 128 wide")
+            moot = "half-filled tiles exist for register-resident networks up to 128 wide"
         monkeypatch.setenv("AZG_TILE_TREES", "16")
     if variant in ("persistent", "launches"):
         if max(hidden) <= 256:
-            pytest.skip("lock-step kernels only exist for hidden widths >= 512")
+            moot = "lock-step kernels only exist for hidden widths >= 512"
         if variant == "persistent":
             monkeypatch.setenv("AZG_FORCE_PERSISTENT", "1")   # wide networks: the one-launch kernel instead of the lock-step path
         else:
@@ -257,6 +266,13 @@ def test_hip_bit_exact_vs_oracle(native, cfg, variant, monkeypatch):
             assert not spec, _last_kernel_name
     if env == 4:   # the point of these configurations: terminal nodes, and traces that ended in an existing one (no new record)
         assert ((a[1]["node_flags"] & 2) != 0).any(1).sum() >= B // 3 and (a[1]["n_records"] < n_sims + 1).sum() >= B // 3
+    if moot:
+        name, fallbacks = _last_kernel_name["name"], _last_kernel_name["team_fallbacks"]
+        monkeypatch.delenv(forced)
+        plain = _run(native.HipEngine, kw, desc, blob, roots, carry, sidx=3, forms=[])
+        _assert_same(a, plain)
+        if fallbacks == _last_kernel_name["team_fallbacks"] == 0:   # (a team kernel that timed out hands over to the per-layer launches)
+            assert _last_kernel_name["name"] == name, (moot, name, _last_kernel_name["name"])
 
 
 def test_deep_discrete_traces(native):
