@@ -100,6 +100,9 @@ SYMBOLS = [
     "selfplay_begin", "selfplay_begin_ex", "selfplay_step", "selfplay_row_len", "selfplay_rows", "selfplay_stats",
     "selfplay_ring", "selfplay_rows_device", "mlp_eval",
 ]
+# entry points a library may lack (the tests' CPU oracle binds SYMBOLS only): bound when present, else the methods that need
+# them raise
+OPTIONAL_SYMBOLS = ["set_population", "set_net_weights"]
 
 
 def bind(lib, prefix):
@@ -141,6 +144,14 @@ def bind(lib, prefix):
     f["selfplay_rows"].argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int32]
     f["selfplay_stats"].argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     f["mlp_eval"].argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    for s in OPTIONAL_SYMBOLS:
+        fn = getattr(lib, prefix + s, None)
+        if fn is not None:
+            f[s] = fn
+    if "set_population" in f:
+        f["set_population"].argtypes = [vp, C.c_int32]
+    if "set_net_weights" in f:
+        f["set_net_weights"].argtypes = [vp, C.c_int32, C.POINTER(AzgMlpDesc), C.POINTER(C.c_float), C.c_size_t]
     return f
 
 
@@ -294,6 +305,29 @@ class Engine:
             return
         desc, blob = policy_blob(policy)
         self.set_weights(desc, blob)
+
+    def _optional(self, name):
+        fn = self._f.get(name)
+        if fn is None:
+            raise NotImplementedError(f"this engine library has no {name} entry point")
+        return fn
+
+    def set_population(self, n_nets):
+        """azg_set_population: trees k*T .. k*T+T-1 (T = n_trees / n_nets) are searched with net k's weights.  Drops every weight
+        when n_nets changes; 1 is the single-network engine."""
+        self._check(self._optional("set_population")(self._h, int(n_nets)))
+        self.n_nets = int(n_nets)
+
+    def set_net_weights(self, net, desc, blob):
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        self._check(self._optional("set_net_weights")(self._h, int(net), C.byref(desc), _ptr(blob, C.c_float), blob.size))
+        if self.mode == MODE_CONTINUOUS:
+            self.n_dist = desc.n_dist
+
+    def set_net_policy(self, net, policy):
+        """Push a torch policy's weights as net ``net`` of the population (host blob: one H2D copy per net)."""
+        desc, blob = policy_blob(policy)
+        self.set_net_weights(net, desc, blob)
 
     def results_resident(self):
         """azg_results_resident: launch return_results into the engine's device buffers; their addresses as a dict of ints."""

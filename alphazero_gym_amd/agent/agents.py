@@ -101,6 +101,10 @@ class DiscreteAgent(Agent):
         """Search, then sample the action from the (temperature-scaled) visit-count or Q distribution (agents.py:257-303).
         Returns (action, state, actions, counts, Qs, V)."""
         self.mcts.search(Env=Env)
+        return self._final_action(deterministic)
+
+    def _final_action(self, deterministic: bool = False):
+        """The final action rule on the last search's results (np.random's global stream)."""
         state, actions, counts, Qs, V = self.mcts.return_results(self.final_selection)
         pi = stable_normalizer(Qs if self.final_selection == "max_value" else counts, self.temperature)
         action = pi.argmax() if deterministic else np.random.choice(len(pi), p=pi)
@@ -142,6 +146,10 @@ class ContinuousAgent(Agent):
     def act(self, Env):
         """Search, then the most visited (or highest-Q) root action, first index on ties (agents.py:492-537)."""
         self.mcts.search(Env=Env)
+        return self._final_action()
+
+    def _final_action(self, deterministic: bool = False):
+        """The final action rule on the last search's results (``random`` / np.random's global streams when epsilon > 0)."""
         state, actions, counts, Qs, V = self.mcts.return_results(self.final_selection)
         values = Qs if self.final_selection == "max_value" else counts
         actions1 = np.atleast_1d(actions)

@@ -235,6 +235,7 @@ int azg_engine_create(const azg_config* cfg, azg_engine** out) {
     e->d_team_cnt = nullptr; e->team_cnt_bytes = 0; e->team_pending = 0; e->team_fallbacks = 0; e->team_search_idx = 0;
     e->kernel_form = -1; e->lds_exit = 0; e->lds_warned = 0; e->last_search_idx = 0; e->ms_kept = 0.0f; e->ms_kept_valid = 0;
     e->carry_max = 0;
+    e->n_nets = 1; e->net_have.assign(1, 0);
     e->h_res_block = nullptr; e->d_res_block = nullptr; e->res_bytes = 0;
     e->d_wblob = nullptr; e->d_wmap = nullptr; e->w_floats = 0; e->dist_nd = -1; e->dist_ncomp = -1;
     e->d_eval = nullptr; e->eval_floats = 0;
@@ -316,6 +317,7 @@ int azg_engine_create(const azg_config* cfg, azg_engine** out) {
         unsigned long long* st;
         CK(dalloc(e, &st, stamp_rows(B) * 16, e->dev_allocs));   // (diagnostic builds: one row of 16 counters per wave)
         e->P.stamps = st;
+        e->stamp_n = stamp_rows(B);
     }
     std::vector<double> sq(e->tab_n);
     for (int n = 0; n < e->tab_n; ++n) sq[n] = std::sqrt((double)(n + 1));
@@ -335,6 +337,7 @@ int azg_engine_create(const azg_config* cfg, azg_engine** out) {
     P.res_actions = e->d_actions; P.res_counts = e->d_counts; P.res_Q = e->d_Q; P.res_vt = e->d_vt; P.res_nch = e->d_nch;
     P.res_child_n = e->d_child_n; P.res_child_state = e->d_child_state; P.res_root_V = e->d_rootV; P.res_root_dist = e->d_rootdist;
     P.res_Kmax = e->Kmax; P.res_v_target = cfg->v_target;
+    P.net_T = cfg->n_trees; P.net_wgs = 1; P.net_wstride = 0;
     *out = e;
     return AZG_OK;
 #undef CK
@@ -491,10 +494,23 @@ __global__ __launch_bounds__(256) void weight_gather_kernel(const unsigned* __re
 
 // Common body of azg_set_weights / azg_set_weights_device: `blob` is a host pointer (on_device false) or a device pointer whose
 // contents are complete (its producer's stream synchronised or otherwise ordered before this call).
-static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* blob, size_t n_floats, bool on_device) {
+// `net`: which net of a population (azg_set_population) the weights are for; 0 for an engine of one net.
+static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* blob, size_t n_floats, bool on_device, int net = 0) {
     if (!e || !d || !blob) return AZG_E_INVALID;
     int HP = 0, ncomp = 0;
     { int rc = check_desc(e, d, n_floats, &HP, &ncomp); if (rc) return rc; }
+    const int NN = e->n_nets;
+    bool others = false;   // another net of the population already has weights: they fix the descriptor
+    for (int k = 0; k < NN; ++k) others = others || (k != net && e->net_have[k]);
+    if (NN > 1) {
+        if (HP >= 512)
+            return fail(e, AZG_E_UNSUPPORTED, "populations: networks wider than 256 (padded) run as team / per-layer searches, which take one "
+                                              "network per engine");
+        if (others && !(e->wmap.valid && e->wmap.HP == HP && same_desc(e->wmap.desc, *d) && d->activation == e->wmap.desc.activation &&
+                        d->num_components == e->wmap.desc.num_components && d->log_std_min == e->wmap.desc.log_std_min &&
+                        d->log_std_max == e->wmap.desc.log_std_max))
+            return fail(e, AZG_E_INVALID, "populations: every net must have the same network descriptor (azg_mlp_desc)");
+    }
     ON_DEVICE(e);
     HIPCHK(e, hipStreamSynchronize(e->stream));
     { int trc = team_check(e); if (trc) return trc; }   // an abandoned team search is redone with the weights it was started with
@@ -508,14 +524,19 @@ static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* b
         build_weight_map(d, HP, m);
         if (e->d_wmap) { (void)hipFree(e->d_wmap); e->d_wmap = nullptr; }   // (uploaded when the device path first needs it)
     }
+    m.desc = *d;
+    // one block of n_out_f floats (a multiple of 64: every tensor starts 256-byte aligned) per net
     const size_t n_out_f = m.src.size();
     if (n_out_f != e->w_floats || !e->d_wblob) {
         if (e->d_wblob) (void)hipFree(e->d_wblob);
         e->d_wblob = nullptr; e->w_floats = 0;
+        for (int k = 0; k < NN; ++k) e->net_have[k] = 0;   // (a new shape: the other nets' blocks no longer exist; NN > 1 cannot get here with any)
         void* q = nullptr;
-        HIPCHK(e, hipMalloc(&q, n_out_f * sizeof(float)));
+        HIPCHK(e, hipMalloc(&q, n_out_f * NN * sizeof(float)));
         e->d_wblob = (float*)q; e->w_floats = n_out_f;
     }
+    float* const wnet = e->d_wblob + (size_t)net * n_out_f;
+    e->net_have[net] = 0;
     if (on_device) {
         if (!e->d_wmap) {
             void* q = nullptr;
@@ -523,7 +544,7 @@ static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* b
             e->d_wmap = (unsigned*)q;
             HIPCHK(e, hipMemcpy(e->d_wmap, m.src.data(), n_out_f * sizeof(unsigned), hipMemcpyHostToDevice));
         }
-        hipLaunchKernelGGL(weight_gather_kernel, dim3((unsigned)((n_out_f + 255) / 256)), dim3(256), 0, e->stream, e->d_wmap, blob, e->d_wblob, n_out_f);
+        hipLaunchKernelGGL(weight_gather_kernel, dim3((unsigned)((n_out_f + 255) / 256)), dim3(256), 0, e->stream, e->d_wmap, blob, wnet, n_out_f);
         HIPCHK(e, hipGetLastError());
         HIPCHK(e, hipStreamSynchronize(e->stream));   // the caller may overwrite its blob as soon as this returns
     } else {
@@ -531,9 +552,11 @@ static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* b
         st.resize(n_out_f);
         const unsigned* src = m.src.data();
         for (size_t i = 0; i < n_out_f; ++i) st[i] = src[i] ? blob[src[i] - 1] : 0.0f;
-        HIPCHK(e, hipMemcpy(e->d_wblob, st.data(), n_out_f * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(e, hipMemcpy(wnet, st.data(), n_out_f * sizeof(float), hipMemcpyHostToDevice));
     }
-    const float* wb = e->d_wblob;
+    e->net_have[net] = 1;
+    e->P.net_wstride = NN > 1 ? n_out_f : 0;
+    const float* wb = e->d_wblob;   // (net 0's tensors; the search kernel adds net_wstride per net)
     e->P.W0u = (const f32x4*)(wb + m.oW0u);
     e->P.b0u = (const f32x4*)(wb + m.ob0u);
     e->P.W0 = wb + m.oW0;
@@ -576,16 +599,57 @@ static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* b
     // LayerNorm and the rare activations live in the weight-streaming kernels only (keeps the register-resident kernels lean)
     if (d->layernorm || (d->activation != AZG_ACT_RELU && d->activation != AZG_ACT_ELU)) e->nreg = 0;
     if (e->opt.force_stream_weights) e->nreg = 0;
-    e->mlp_ready = 1;
+    bool all = true;
+    for (int k = 0; k < NN; ++k) all = all && e->net_have[k];
+    e->mlp_ready = all ? 1 : 0;   // (a population searches once every net has its weights)
     return AZG_OK;
 }
 
+static const char* kPopWeights = "this engine holds a population (azg_set_population > 1): upload each net's weights with azg_set_net_weights";
+
 int azg_set_weights(azg_engine* e, const azg_mlp_desc* d, const float* blob, size_t n_floats) {
+    if (e && e->n_nets > 1) return fail(e, AZG_E_STATE, kPopWeights);
     return set_weights_impl(e, d, blob, n_floats, false);
 }
 
 int azg_set_weights_device(azg_engine* e, const azg_mlp_desc* d, const float* device_blob, size_t n_floats) {
+    if (e && e->n_nets > 1) return fail(e, AZG_E_STATE, kPopWeights);
     return set_weights_impl(e, d, device_blob, n_floats, true);
+}
+
+int azg_set_population(azg_engine* e, int32_t n_nets) {
+    if (!e) return AZG_E_INVALID;
+    if (n_nets < 1 || n_nets > e->cfg.n_trees || e->cfg.n_trees % n_nets != 0)
+        return fail(e, AZG_E_INVALID, "azg_set_population: n_nets must divide n_trees (trees k*T .. k*T+T-1 belong to net k, T = n_trees / n_nets)");
+    if (e->sp_on) return fail(e, AZG_E_UNSUPPORTED, "azg_set_population: device self-play is running on this engine (one network per engine)");
+    if (n_nets == e->n_nets) return AZG_OK;
+    ON_DEVICE(e);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    { int trc = team_check(e); if (trc) return trc; }
+    // the diagnostic stamp buffer has a row per wave of the grid, which padding every net's segment to whole workgroups enlarges
+    // (stamp_rows of the 16-tree padded count covers the 8-, 16- and 32-tree shapes)
+    const size_t rows = stamp_rows((size_t)n_nets * (((size_t)e->cfg.n_trees / n_nets + 15) / 16 * 16));
+    if (rows > e->stamp_n) {
+        unsigned long long* st = nullptr;
+        if (dalloc(e, &st, rows * 16, e->dev_allocs)) return AZG_E_DEVICE;
+        for (size_t i = 0; i < e->dev_allocs.size(); ++i)
+            if (e->dev_allocs[i] == (void*)e->P.stamps) { (void)hipFree(e->dev_allocs[i]); e->dev_allocs.erase(e->dev_allocs.begin() + i); break; }
+        e->P.stamps = st; e->stamp_n = rows;
+    }
+    // every weight goes: the next search needs the weights of every net again
+    if (e->d_wblob) (void)hipFree(e->d_wblob);
+    e->d_wblob = nullptr; e->w_floats = 0;
+    e->n_nets = n_nets;
+    e->net_have.assign(n_nets, 0);
+    e->mlp_ready = 0; e->results_valid = 0; e->redo_ok = 0; e->searched = 0;
+    e->P.net_T = e->cfg.n_trees / n_nets; e->P.net_wstride = 0;
+    return AZG_OK;
+}
+
+int azg_set_net_weights(azg_engine* e, int32_t net, const azg_mlp_desc* d, const float* blob, size_t n_floats) {
+    if (!e) return AZG_E_INVALID;
+    if (net < 0 || net >= e->n_nets) return fail(e, AZG_E_INVALID, "azg_set_net_weights: net index out of range");
+    return set_weights_impl(e, d, blob, n_floats, false, net);
 }
 
 int azg_set_search_index(azg_engine* e, uint32_t idx) { if (!e) return AZG_E_INVALID; e->search_idx = idx; return AZG_OK; }
@@ -638,7 +702,11 @@ int azg_upload_roots(azg_engine* e, const double* roots, const int32_t* carry) {
 
 int azg_search_resident(azg_engine* e) {
     if (!e) return AZG_E_INVALID;
-    if (!e->mlp_ready) return fail(e, AZG_E_STATE, "azg_set_weights has not been called");
+    if (!e->mlp_ready)
+        return fail(e, AZG_E_STATE, e->n_nets > 1 ? "azg_set_net_weights has not been called for every net of the population"
+                                                 : "azg_set_weights has not been called");
+    if (e->n_nets > 1 && use_lockstep(e))   // (set_weights_impl refuses these networks; kept as the guard of the one-launch forms)
+        return fail(e, AZG_E_UNSUPPORTED, "populations run on the one-launch search kernel only");
     ON_DEVICE(e);
     e->P.search_idx = e->search_idx;
     e->last_search_idx = e->search_idx;
@@ -774,6 +842,7 @@ int azg_root_children(azg_engine* e, int32_t* child_n, double* child_state) {
 
 int azg_root_eval(azg_engine* e, float* value, float* dist) {
     if (!e) return AZG_E_INVALID;
+    if (e->n_nets > 1) return fail(e, AZG_E_UNSUPPORTED, "azg_root_eval: not available for populations (azg_set_population > 1)");
     int rc = gather_results(e);
     if (rc) return rc;
     size_t B = e->cfg.n_trees;
@@ -784,6 +853,7 @@ int azg_root_eval(azg_engine* e, float* value, float* dist) {
 
 int azg_mlp_eval(azg_engine* e, const float* obs, size_t n, float* value, float* dist, float* raw) {
     if (!e || !obs) return AZG_E_INVALID;
+    if (e->n_nets > 1) return fail(e, AZG_E_UNSUPPORTED, "azg_mlp_eval: not available for populations (azg_set_population > 1): evaluate each net's policy");
     if (!e->mlp_ready) return fail(e, AZG_E_STATE, "azg_set_weights has not been called");
     if (n == 0) return AZG_OK;
     if (n > (size_t)1 << 24) return fail(e, AZG_E_INVALID, "too many observations in one call");
@@ -920,7 +990,7 @@ int azg_search_info(azg_engine* e, azg_search_report* info) {
 // diagnostic (-DAZG_STAMPS builds): per-wave cycle sums [n_workgroups*4][16]; returns the number of rows
 int azg_debug_stamps(azg_engine* e, unsigned long long* out, size_t max_rows) {
     if (!e || !out) return AZG_E_INVALID;
-    size_t rows = stamp_rows((size_t)e->cfg.n_trees);
+    size_t rows = e->stamp_n;
     if (rows > max_rows) rows = max_rows;
     ON_DEVICE(e);
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -944,6 +1014,7 @@ int azg_selfplay_row_len(const azg_engine* e) { return e ? e->S_obs + 3 * e->Kma
 
 int azg_selfplay_begin_ex(azg_engine* e, const azg_selfplay_config* c) {
     if (!e || !c) return AZG_E_INVALID;
+    if (e->n_nets > 1) return fail(e, AZG_E_UNSUPPORTED, "device self-play is not available for populations (azg_set_population > 1)");
     if (c->struct_size != (int32_t)sizeof(azg_selfplay_config)) return fail(e, AZG_E_INVALID, "azg_selfplay_config size mismatch");
     if (c->max_episode_length < 1 || c->capacity_steps < 1) return fail(e, AZG_E_INVALID, "max_episode_length and capacity_steps must be >= 1");
     if (c->final_selection != AZG_FS_MAX_VISIT && c->final_selection != AZG_FS_MAX_VALUE) return fail(e, AZG_E_INVALID, "unknown final_selection");

@@ -30,7 +30,7 @@ static hipError_t launch_g(azg_engine* e) {
     // allows it, which is worth far more (CartPole, 8192 trees, 2x128: 0.62 ms per search against 0.94 ms)
     constexpr bool CONT = EnvFamily<ENV>::CONT;
     LdsLayout L = lds_layout(e->tab_n, e->cfg.n_sims, HP, NG, act_buffers(NREG), e->R, CONT, TLDS, 1, NT);
-    const long n_wg = (e->cfg.n_trees + NT * NG - 1) / (NT * NG);
+    const long n_wg = azg_padded_trees(e, NT * NG) / (NT * NG);
     const size_t with_state = L.total + (size_t)static_lds;
     const size_t without = lds_layout(e->tab_n, e->cfg.n_sims, HP, NG, act_buffers(NREG), e->R, CONT, TLDS, 0, NT).total + (size_t)static_lds;
     const bool costs_a_neighbour = n_wg > e->n_cus && 2 * without <= 160 * 1024 && 2 * with_state > 160 * 1024;
@@ -41,8 +41,8 @@ static hipError_t launch_g(azg_engine* e) {
         hipError_t rc = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total);
         if (rc != hipSuccess) return rc;
     }
-    const int tpw = NT * NG;
-    dim3 grid((e->cfg.n_trees + tpw - 1) / tpw), block(64 * NW);
+    dim3 grid((unsigned)n_wg), block(64 * NW);
+    e->P.net_wgs = (int)(n_wg / e->n_nets);   // (every net's segment padded to whole workgroups: search_kernel.cuh)
     e->tree_lds = TLDS;
     e->dyn_lds = L.total;
     e->waves = NW; e->groups = NG; e->tile_trees = NT; e->spec = SPEC;
@@ -101,7 +101,7 @@ static hipError_t launch(azg_engine* e) {
     // (Continuous mode only.  The discrete family's 8-wave shapes were measured slower than its 4-wave ones -- CartPole, 8192 trees,
     // 2x256: 1.03 ms against 0.99 ms per search, and they were the only kernels of the family that spilled registers -- and are gone.)
     if constexpr (HP == 256 && NREG == 1 && EnvFamily<ENV>::CONT) {
-        bool two = (e->cfg.n_trees + 15) / 16 > e->n_cus;
+        bool two = azg_padded_trees(e, 16) / 16 > e->n_cus;
         if (e->opt.groups == 2) two = true;
         if (e->opt.groups == 1) two = false;
         // eight waves either way (round 4): 32-tree workgroups when the batch has more groups than CUs, else 16-tree workgroups whose
@@ -119,7 +119,7 @@ static hipError_t launch(azg_engine* e) {
     // (search_kernel.cuh has the measurements: with more trees than that, full tiles win).  AZG_TILE_TREES=16|8 forces a shape (tests).
     if constexpr (HP <= 128 && NREG == 1) {
         if (ts == TS_LDS8 && e->P.ncomp < 2) {
-            int nt = e->cfg.n_trees <= 8L * e->n_cus ? 8 : 16;
+            int nt = azg_padded_trees(e, 8) <= 8L * e->n_cus ? 8 : 16;
             if (e->opt.tile_trees) nt = e->opt.tile_trees;
             if (nt == 8) {
                 hipError_t rc = launch_t<ENV, HP, NREG, TS_LDS8, 4, 1, 8>(e);

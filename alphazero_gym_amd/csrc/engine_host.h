@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "records.h"
+#include "../../include/azgym_population.h"
 
 // diagnostic switches (environment variables, read once when the engine is created): force the other code paths in tests
 struct EngineOptions {
@@ -93,11 +94,21 @@ struct azg_engine {
     int publish_once;        // set by azg_dump_tree around its re-run of the last search
     int published;           // the last search's trees are in global memory (global-tree / lock-step / team forms always are)
     int redo_ok;             // roots, carried counts and weights are still the ones the last search ran on: azg_dump_tree may re-run it
+    int n_nets;              // azg_set_population: the trees split into n_nets nets of n_trees / n_nets trees (1: one network)
+    std::vector<char> net_have;   // net k has weights (azg_set_net_weights); d_wblob holds n_nets blocks of w_floats
+    size_t stamp_n;          // rows of the diagnostic stamp buffer (P.stamps)
     float last_ms;
     uint32_t last_search_idx;   // the search index the last search ran under (azg_dump_tree re-runs it with this one)
     float ms_kept; int ms_kept_valid;   // kernel time of the last search, kept across azg_dump_tree's re-run of it
     std::string err;
 };
+
+// Trees the persistent kernel's grid covers with tpw trees per workgroup: every net's segment padded to whole workgroups (one net: the
+// batch rounded up to tpw).  The launch planning (dispatch.cuh) sizes the grid and picks its shapes from this count.
+static inline long azg_padded_trees(const azg_engine* e, int tpw) {
+    const long T = e->cfg.n_trees / e->n_nets;
+    return (long)e->n_nets * ((T + tpw - 1) / tpw * tpw);
+}
 
 // one search of all trees on e->stream with the kernel variant that fits (dispatch.cuh); hipErrorInvalidValue: no such variant
 hipError_t azg_dispatch_cartpole(azg_engine* e);

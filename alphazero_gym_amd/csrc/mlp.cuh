@@ -101,8 +101,12 @@ __device__ __forceinline__ float ln_reduce(float s, float* buf, int wave, int la
     return ((buf[tree] + buf[16 + tree]) + buf[32 + tree]) + buf[48 + tree];
 }
 
+// a weight tensor of net k of a population: the same tensor of net 0, wofs = k * KParams::net_wstride floats further on
+template <typename T>
+__device__ __forceinline__ const T* net_ptr(const T* p, size_t wofs) { return (const T*)((const float*)p + wofs); }
+
 template <int HP>
-__device__ __forceinline__ void layer_norm_wg(const KParams& P, int layer, f32x4* h, float* s_ln, int wave, int lane) {
+__device__ __forceinline__ void layer_norm_wg(const KParams& P, int layer, f32x4* h, float* s_ln, int wave, int lane, size_t wofs = 0) {
     constexpr int NTW = HP / 64;
     const int H = P.Htrue[layer];
     const int g = lane >> 4;
@@ -125,7 +129,7 @@ __device__ __forceinline__ void layer_norm_wg(const KParams& P, int layer, f32x4
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
         const int u0 = 16 * (wave * NTW + i) + 4 * g;
-        const f32x4 ga = P.lng[layer][(wave * NTW + i) * 64 + lane], be = P.lnb[layer][(wave * NTW + i) * 64 + lane];
+        const f32x4 ga = net_ptr(P.lng[layer], wofs)[(wave * NTW + i) * 64 + lane], be = net_ptr(P.lnb[layer], wofs)[(wave * NTW + i) * 64 + lane];
         h[i].x = u0 + 0 < H ? ((h[i].x - mean) * inv) * ga.x + be.x : 0.0f;
         h[i].y = u0 + 1 < H ? ((h[i].y - mean) * inv) * ga.y + be.y : 0.0f;
         h[i].z = u0 + 2 < H ? ((h[i].z - mean) * inv) * ga.z + be.z : 0.0f;
@@ -153,7 +157,7 @@ __device__ __forceinline__ void mlp_forward(const KParams& P, const WR& wr, cons
 #ifdef AZG_STAMPS
                                             , unsigned long long* st_acc
 #endif
-                                            , int* l0_flag = nullptr, int step = 0) {
+                                            , int* l0_flag = nullptr, int step = 0, size_t wofs = 0) {
     STAMP_M(m0, 4, -1);
     static_assert(!SPLIT || (NW == 8 && NG == 1 && NT == 16 && HP <= 256 && NREG > 0 && !IN8), "split first layer: the eight-wave / 16-tree shape");
     constexpr int NTW = HP / (16 * NW);    // output tiles per wave
@@ -204,8 +208,8 @@ __device__ __forceinline__ void mlp_forward(const KParams& P, const WR& wr, cons
                 if constexpr (IN8) { if (P.in8) a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wr.w0b[i], b2, a0, 0, 0, 0); }
             } else {   // wide layers: first-layer weights are not kept in registers
                 const int nt = wave * NTW + i;
-                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(P.W0[nt * 64 + lane], b, P.b0[nt * 64 + lane], 0, 0, 0);
-                if constexpr (IN8) { if (P.in8) a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(P.W0b[nt * 64 + lane], b2, a0, 0, 0, 0); }
+                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(P.W0[wofs + nt * 64 + lane], b, net_ptr(P.b0, wofs)[nt * 64 + lane], 0, 0, 0);
+                if constexpr (IN8) { if (P.in8) a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(P.W0b[wofs + nt * 64 + lane], b2, a0, 0, 0, 0); }
             }
             if constexpr (NREG == 0) h[g][i] = act4<true>(P.act, a0);   // (weight-streaming kernels: any activation)
             else h[g][i] = a0;
@@ -227,7 +231,7 @@ __device__ __forceinline__ void mlp_forward(const KParams& P, const WR& wr, cons
     }
     }
     // LayerNorm is compiled into the weight-streaming kernels only (the host selects them when layernorm is on)
-    if constexpr (NREG == 0) { if (P.layernorm) layer_norm_wg<HP>(P, 0, h[0], s_ln, wave, lane); }
+    if constexpr (NREG == 0) { if (P.layernorm) layer_norm_wg<HP>(P, 0, h[0], s_ln, wave, lane, wofs); }
     f32x4* buf = actA;
     f32x4* other = actB;
     // hidden->hidden layers held in registers
@@ -303,8 +307,8 @@ __device__ __forceinline__ void mlp_forward(const KParams& P, const WR& wr, cons
 #pragma unroll
             for (int i = 0; i < NTW; ++i) buf[(wave * NTW + i) * 64 + lane] = h[0][i];
             __syncthreads();
-            const f32x4* W = P.Wl[l - 1];
-            const f32x4* bb = P.bl[l - 1];
+            const f32x4* W = net_ptr(P.Wl[l - 1], wofs);
+            const f32x4* bb = net_ptr(P.bl[l - 1], wofs);
             // tiles in groups of at most 4 (wide layers: 16 tiles per wave would not fit the register file)
             constexpr int TG = NTW < 4 ? NTW : 4;
 #pragma unroll
@@ -330,7 +334,7 @@ __device__ __forceinline__ void mlp_forward(const KParams& P, const WR& wr, cons
 #pragma unroll
                 for (int i = 0; i < TG; ++i) h[0][tg + i] = act4<NREG == 0>(P.act, acc[i]);
             }
-            if (P.layernorm) layer_norm_wg<HP>(P, l, h[0], s_ln, wave, lane);
+            if (P.layernorm) layer_norm_wg<HP>(P, l, h[0], s_ln, wave, lane, wofs);
             f32x4* t = buf; buf = other; other = t;
         }
     }
@@ -349,7 +353,7 @@ __device__ __forceinline__ void mlp_forward(const KParams& P, const WR& wr, cons
 #pragma unroll
             for (int sc = 0; sc < NSUB; ++sc) {
                 const int ks = sc * KS + j, ti = ks >> 2, cmp = ks & 3;
-                const f32x4 a = (NREG > 0) ? wr.wh[ti] : P.Whead[(wave * NTW + ti) * 64 + lane];
+                const f32x4 a = (NREG > 0) ? wr.wh[ti] : net_ptr(P.Whead, wofs)[(wave * NTW + ti) * 64 + lane];
 #pragma unroll
                 for (int g = 0; g < NG; ++g) acc[g][sc] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cmp], h[g][ti][cmp], acc[g][sc], 0, 0, 0);
             }

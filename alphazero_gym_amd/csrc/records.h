@@ -121,6 +121,10 @@ struct KParams {
     int publish;                // LDS trees: write them out in the global RecL format after the last trace (azg_dump_tree asks for it;
                                 // the product path's results come from the search kernel's epilogue and need no published tree)
     unsigned long long* stamps; // diagnostic build only (-DAZG_STAMPS): [grid][8] cycle sums per phase
+    // populations (azg_set_population): net k searches trees k*net_T .. k*net_T+net_T-1 in net_wgs workgroups of its own (the last
+    // one padded) with the weights at net_wstride * k floats past the tensors above.  One net: net_T = B, net_wgs = the grid, 0.
+    int net_T, net_wgs;
+    size_t net_wstride;
 };
 
 // ---- state of the lock-step path (lockstep.cuh) between its launches

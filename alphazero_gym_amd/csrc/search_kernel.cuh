@@ -79,6 +79,15 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
 
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
+    // Populations (azg_set_population): trees k*T .. k*T+T-1 are searched with net k's weights.  Each net's tree segment is padded
+    // to whole workgroups (P.net_wgs of them), so a workgroup belongs to one net: wnet.  Its first tree is tree0 (unpadded order),
+    // and only its first n_live columns hold trees; the rest are padding and never walk.  Net k's weights sit k * P.net_wstride
+    // floats after net 0's: wofs.  One net: net_wgs = the grid, T = B, wnet = 0, wofs = 0.
+    const int wnet = (int)blockIdx.x / P.net_wgs;
+    const int wj0 = ((int)blockIdx.x - wnet * P.net_wgs) * TPW;
+    const int tree0 = wnet * P.net_T + wj0;
+    const int n_live = (P.net_T - wj0) < TPW ? (P.net_T - wj0) : TPW;
+    const size_t wofs = (size_t)wnet * P.net_wstride;
     // Two waves per SIMD (NW = 8) leave each wave 256 registers, 128 of them weights: nothing that can be re-derived in a few
     // instructions is carried across the network phase there.  The per-tree context (indices, global base pointers, LDS bases)
     // is rebuilt from the thread index at the top of every tree phase, the loop-carried tree state crosses the network phase
@@ -92,7 +101,7 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
     f32x4* s_actB = act_buffers(NREG) == 2 ? s_actA + NG * (HP / 16 * 64) : s_actA;
     for (int i = tid; i < P.tab_n; i += 64 * NW) s_sqrt[i] = P.sqrt_tab[i];
     if (CONT) for (int i = tid; i < P.n_sims + 2; i += 64 * NW) s_pw[i] = (unsigned short)(P.pw_need[i] < 65535 ? P.pw_need[i] : 65535);
-    if (tid < 16) s_bhead[tid] = P.bhead[tid];
+    if (tid < 16) s_bhead[tid] = P.bhead[wofs + tid];
     if (tid == 0) { s_done = 0; s_l0 = 0; }
 
     // register-resident weights
@@ -104,16 +113,16 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
         if (wave >= NW / 2) {
 #pragma unroll
             for (int i = 0; i < 2 * NTW; ++i) {
-                wr.w0[i] = P.W0[((wave - NW / 2) * 2 * NTW + i) * 64 + lane];
-                wr.b0[i] = P.b0[((wave - NW / 2) * 2 * NTW + i) * 64 + lane];
+                wr.w0[i] = P.W0[wofs + ((wave - NW / 2) * 2 * NTW + i) * 64 + lane];
+                wr.b0[i] = net_ptr(P.b0, wofs)[((wave - NW / 2) * 2 * NTW + i) * 64 + lane];
             }
         }
     } else if constexpr (HP <= 256) {
 #pragma unroll
         for (int i = 0; i < NTW; ++i) {
-            wr.w0[i] = P.W0[(wave * NTW + i) * 64 + lane];
-            if constexpr (IN8) { if (P.in8) wr.w0b[i] = P.W0b[(wave * NTW + i) * 64 + lane]; }
-            wr.b0[i] = P.b0[(wave * NTW + i) * 64 + lane];
+            wr.w0[i] = P.W0[wofs + (wave * NTW + i) * 64 + lane];
+            if constexpr (IN8) { if (P.in8) wr.w0b[i] = P.W0b[wofs + (wave * NTW + i) * 64 + lane]; }
+            wr.b0[i] = net_ptr(P.b0, wofs)[(wave * NTW + i) * 64 + lane];
         }
     }
     if (NREG > 0) {
@@ -122,13 +131,13 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
         for (int l = 0; l < NREG; ++l) {
 #pragma unroll
             for (int i = 0; i < NTW; ++i) {
-                wr.b[l][i] = P.bl[l][(wave * NTW + i) * 64 + lane];
+                wr.b[l][i] = net_ptr(P.bl[l], wofs)[(wave * NTW + i) * 64 + lane];
 #pragma unroll
-                for (int s4 = 0; s4 < S4; ++s4) wr.w[l][i][s4] = P.Wl[l][((wave * NTW + i) * S4 + s4) * 64 + lane];
+                for (int s4 = 0; s4 < S4; ++s4) wr.w[l][i][s4] = net_ptr(P.Wl[l], wofs)[((wave * NTW + i) * S4 + s4) * 64 + lane];
             }
         }
 #pragma unroll
-        for (int i = 0; i < NTW; ++i) wr.wh[i] = P.Whead[(wave * NTW + i) * 64 + lane];
+        for (int i = 0; i < NTW; ++i) wr.wh[i] = net_ptr(P.Whead, wofs)[(wave * NTW + i) * 64 + lane];
     }
 
     // everything a tree phase needs to know about "its" tree, as a function of the thread index
@@ -142,8 +151,8 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
         c.sub = ln & 15;
         c.has_tree = w < NWALK && (ln >> 4) < TPV;
         c.tl = c.has_tree ? w * TPV + (ln >> 4) : 0;   // tree within the workgroup
-        c.tree = blockIdx.x * TPW + c.tl;
-        c.live = c.has_tree && c.tree < P.B;
+        c.tree = tree0 + c.tl;
+        c.live = c.has_tree && c.tl < n_live;
         c.gtree = (unsigned)(P.tree_base + c.tree);
         c.tb = (size_t)(c.live ? c.tree : 0) * P.R;
         c.cold = P.cold + c.tb;
@@ -187,7 +196,6 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
     // (the lean packing below does not carry TreeState::chainR / repeat nor the MULTI loop's per-tree trace counter)
     static_assert(!(LEAN && MULTI), "discrete 8-wave shapes: extend the LEAN packing first");
     int my_sim = -1;                    // the trace whose leaf is pending (-1: the root's evaluation); n_sims: the tree is done
-    const int n_live = (P.B - (int)blockIdx.x * TPW) < TPW ? (P.B - (int)blockIdx.x * TPW) : TPW;
     // (every unfinished tree completes at least one trace per step, so n_sims + 1 steps always suffice: the bound is a guard, the
     // discrete kernels normally leave through s_done long before)
     for (int sim = -1; sim < P.n_sims; ++sim) {
@@ -219,9 +227,9 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
             asm volatile("" : "+v"(pk0), "+v"(pk1), "+v"(pk2), "+v"(pk3));
         }
 #ifdef AZG_STAMPS
-        mlp_forward<HP, NREG, NW, NG, PSTR, WR, NT, IN8, DEFER>(P, wr, s_obsT, s_actA, s_actB, s_parts, s_ln, wave, lane, st_acc, &s_l0, sim + 2);
+        mlp_forward<HP, NREG, NW, NG, PSTR, WR, NT, IN8, DEFER>(P, wr, s_obsT, s_actA, s_actB, s_parts, s_ln, wave, lane, st_acc, &s_l0, sim + 2, wofs);
 #else
-        mlp_forward<HP, NREG, NW, NG, PSTR, WR, NT, IN8, DEFER>(P, wr, s_obsT, s_actA, s_actB, s_parts, s_ln, wave, lane, &s_l0, sim + 2);
+        mlp_forward<HP, NREG, NW, NG, PSTR, WR, NT, IN8, DEFER>(P, wr, s_obsT, s_actA, s_actB, s_parts, s_ln, wave, lane, &s_l0, sim + 2, wofs);
 #endif
         STAMP2(t_c, 1, 2);
         if constexpr (LEAN) {

@@ -2,8 +2,10 @@
 
 ``run_continuous_agent`` / ``run_discrete_agent`` mirror run_continuous.py:15-165 / run_discrete.py:16-146: one game, one
 tree, ``act -> buffer.store -> Env.step -> reset_mcts | mcts_forward`` per step, ``agent.train(buffer)`` per episode.
-``BatchedSelfPlay`` is the scaled-out form the engine is built for: B games per GPU advance in lock step, one search
-launch per environment step, replay rows gathered across ranks, weights broadcast after the optimiser step.
+``run_population`` is the same loop for K seeds at once: every step searches all K agents' trees in one launch
+(AgentPopulation); training stays each agent's own optimiser step.  ``BatchedSelfPlay`` is the scaled-out form the engine is
+built for: B games per GPU advance in lock step, one search launch per environment step, replay rows gathered across ranks,
+weights broadcast after the optimiser step.
 
 Default hyper-parameters are the reference's (config/*.yaml), except that the continuous policy uses
 one squashed-Normal component (num_components: 1) instead of the 2-component GMM.
@@ -18,6 +20,7 @@ import torch
 from . import _capi, distributed as D
 from .agent.agents import ContinuousAgent, DiscreteAgent
 from .agent.buffers import DeviceReplay, ReplayBuffer
+from .agent.population import AgentPopulation
 from .envs import VecCartPole, VecMountainCarContinuous, VecPendulum, make_game
 from .helpers import check_space, stable_normalizer
 from .search.mcts import BatchedMCTS
@@ -123,6 +126,76 @@ def run_discrete_agent(cfg: Optional[dict] = None, log: Optional[Callable[[Dict,
         info["Episode reward"] = R
         if log:
             log(dict(info), ep)
+    return returns
+
+
+def make_agent(kind: str, cfg: dict, Env, tree_id_base: int = 0):
+    """The agent run_continuous_agent / run_discrete_agent build for ``Env`` (cfg: merged defaults), searching tree ``tree_id_base``."""
+    state_dim, _ = check_space(Env.observation_space)
+    action_dim, discrete = check_space(Env.action_space)
+    if kind == "continuous":
+        assert not discrete, "Using continuous agent for a discrete action space!"
+        policy = dict(cfg["policy"], representation_dim=state_dim[0], action_dim=action_dim[0], action_bound=float(Env.action_space.high[0]))
+        return ContinuousAgent(policy_cfg=policy, mcts_cfg=dict(cfg["mcts"], device=cfg["device"], tree_id_base=tree_id_base),
+                               loss_cfg=cfg["loss"], optimizer_cfg=cfg["optimizer"], device=cfg["device"], **cfg["agent"])
+    assert discrete, "Can't use discrete agent for continuous action spaces!"
+    policy = dict(cfg["policy"], representation_dim=state_dim[0], action_dim=1, num_actions=action_dim[0])
+    return DiscreteAgent(policy_cfg=policy, mcts_cfg=dict(cfg["mcts"], device=cfg["device"], num_actions=action_dim[0], tree_id_base=tree_id_base),
+                         loss_cfg=cfg["loss"], optimizer_cfg=cfg["optimizer"], device=cfg["device"], **cfg["agent"])
+
+
+def run_population(kind: str, seeds: List[int], cfg: Optional[dict] = None, log: Optional[Callable[[Dict, int, int], None]] = None,
+                   agents: Optional[List] = None) -> List[List[float]]:
+    """run_continuous.py / run_discrete.py for K seeds at once (kind "continuous" / "discrete"; cfg as for run_*_agent, its
+    ``seed`` replaced by ``seeds``).  Agent k plays its own game (env seeded with seeds[k]) with its own network, buffer,
+    optimiser and np.random / random streams (seeded with seeds[k]); every environment step searches all agents' trees in ONE
+    launch (AgentPopulation; agent k is tree k).  Agents whose episode has ended sit the remaining steps of that episode out.
+    ``agents``: K agents built beforehand (default: built here from cfg).  Returns per seed its episode returns;
+    ``log(info, episode, k)`` gets agent k's training losses and its "Episode reward"."""
+    cfg = _merge(CONTINUOUS_DEFAULTS if kind == "continuous" else DISCRETE_DEFAULTS, cfg)
+    K = len(seeds)
+    envs = []
+    for s in seeds:
+        Env = make_game(cfg["game"])
+        Env.seed(s)
+        envs.append(Env)
+    if agents is None:
+        agents = [make_agent(kind, cfg, envs[k], tree_id_base=k) for k in range(K)]
+    assert len(agents) == K
+    buffers = [ReplayBuffer(**cfg["buffer"]) for _ in range(K)]
+    pop = AgentPopulation(agents, seeds=seeds)
+    returns: List[List[float]] = [[] for _ in range(K)]
+    try:
+        for ep in range(cfg["num_train_episodes"]):
+            R = [0.0] * K
+            for k in range(K):
+                agents[k].reset_mcts(root_state=envs[k].reset())
+            active = [True] * K
+            for t in range(cfg["max_episode_length"]):
+                outs = pop.act([envs[k] if active[k] else None for k in range(K)], deterministic=False)
+                for k in range(K):
+                    if not active[k]:
+                        continue
+                    action, s, actions, counts, Qs, V = outs[k]
+                    buffers[k].store((s, actions, counts, Qs, V))
+                    state, step_reward, terminal, _ = envs[k].step(action)
+                    R[k] += float(np.asarray(step_reward).reshape(-1)[0])
+                    if terminal or t == cfg["max_episode_length"] - 1:
+                        active[k] = False
+                    elif kind == "continuous":
+                        agents[k].reset_mcts(root_state=state)   # the continuous tree cannot be reused
+                    else:
+                        agents[k].mcts_forward(action, state)
+                if not any(active):
+                    break
+            for k in range(K):
+                returns[k].append(R[k])
+                info = pop.train(k, buffers[k])
+                info["Episode reward"] = R[k]
+                if log:
+                    log(dict(info), ep, k)
+    finally:
+        pop.close()
     return returns
 
 

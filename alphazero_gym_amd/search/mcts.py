@@ -6,7 +6,8 @@ attributes the agents poke (``root_node``, ``root_state``, ``n_rollouts``, ``c_u
 weights the engine evaluates on the GPU.  One ``search`` call is ONE kernel launch that runs all ``n_rollouts`` traces.
 
 ``BatchedMCTS`` is the native interface: B independent trees per call (``Env`` may also be a list of environments
-for the two classes above).  There is no CPU fallback; constructing an engine without the HIP library or a GPU raises.
+for the two classes above).  ``PopulationMCTS`` searches the trees of K models, each with its own weights, in one launch.
+There is no CPU fallback; constructing an engine without the HIP library or a GPU raises.
 """
 import warnings
 from typing import Any, List, Optional, Sequence, Tuple
@@ -127,6 +128,63 @@ class BatchedMCTS:
         self.engine.close()
 
 
+class PopulationMCTS:
+    """K models (same network shape, own weights) searched in ONE launch: trees k*T .. k*T+T-1 (T = ``trees_per_model``) use
+    ``models[k]``, with the RNG streams of global trees ``tree_id_base + k*T + j`` -- what K ``BatchedMCTS`` engines with
+    ``tree_id_base + k*T`` compute, one launch and one synchronisation instead of K (azg_set_population).  The search settings
+    (kwargs as in ``BatchedMCTS``) and the search index are shared.  Each model's weights are re-uploaded only when they changed
+    (models train at different times)."""
+
+    def __init__(self, models: Sequence[Any], *, trees_per_model: int = 1, env_id: int, mode: int, n_rollouts: int, c_uct: float,
+                 gamma: float, epsilon: float = 0.0, num_actions: int = 0, c_pw: float = 1.0, kappa: float = 0.5,
+                 V_target_policy: str = "off_policy", action_bound: float = 2.0, seed: int = 34, tree_id_base: int = 0,
+                 device_id: int = 0):
+        from .. import _native   # raises if libazgym_hip.so is missing
+
+        self.models = list(models)
+        if not self.models or trees_per_model < 1:
+            raise ValueError("PopulationMCTS needs at least one model and trees_per_model >= 1")
+        self.n_models = len(self.models)
+        self.trees_per_model = int(trees_per_model)
+        self.n_trees = self.n_models * self.trees_per_model
+        self.engine = _native.HipEngine(env_id=env_id, mode=mode, n_trees=self.n_trees, n_sims=n_rollouts, c_uct=c_uct, gamma=gamma,
+                                        epsilon=epsilon, num_actions=num_actions, c_pw=c_pw, kappa=kappa, v_target=V_target_policy,
+                                        action_bound=action_bound, seed=seed, tree_id_base=tree_id_base, device_id=device_id)
+        self.engine.set_population(self.n_models)
+        self._versions: List[Any] = [None] * self.n_models
+        self.sync_weights()
+
+    def sync_weights(self, force: bool = False) -> None:
+        """Upload the weights of every model that changed since its last upload (net k = models[k])."""
+        for k, m in enumerate(self.models):
+            v = _weights_version(m)
+            if force or v != self._versions[k]:
+                self.engine.set_net_policy(k, m)
+                self._versions[k] = v
+
+    def search(self, root_states: np.ndarray, root_n_carry: Optional[np.ndarray] = None) -> None:
+        """root_states [n_models * trees_per_model, S] (or [n_models, trees_per_model, S]); tree k*T + j belongs to models[k]."""
+        self.sync_weights()
+        roots = np.asarray(root_states, dtype=np.float64).reshape(self.n_trees, -1)
+        carry = None if root_n_carry is None else np.asarray(root_n_carry, dtype=np.int32).reshape(self.n_trees)
+        self.engine.search(roots, carry)
+
+    @property
+    def last_search_info(self) -> dict:
+        """azg_search_info of the last search (see BatchedMCTS.last_search_info)."""
+        return self.engine.search_info()
+
+    def results(self):
+        """return_results of every tree, rows in tree order k*T + j (the shapes of BatchedMCTS.results)."""
+        return self.engine.results()
+
+    def root_children(self):
+        return self.engine.root_children()
+
+    def close(self):
+        self.engine.close()
+
+
 class _Root:
     """What remains of the reference's root Node object on the host: the visit count a reused root carries."""
 
@@ -143,8 +201,9 @@ class MCTS:
     _mode = None
 
     def __init__(self, model, n_rollouts: int, c_uct: float, gamma: float, epsilon: float, device: str, V_target_policy: str,
-                 root_state: np.ndarray, seed: int = 34):
+                 root_state: np.ndarray, seed: int = 34, tree_id_base: int = 0):
         self.device = device
+        self.tree_id_base = tree_id_base   # global id of the (first) tree: keys its RNG streams
         self.root_node = None
         self.root_state = root_state
         self.model = model
@@ -167,14 +226,14 @@ class MCTS:
     def _ensure_engine(self, env_id: int, n_trees: int) -> BatchedMCTS:
         device_id = device_ordinal(self.device)
         key = (env_id, n_trees, self.n_rollouts, self.c_uct, self.gamma, self.epsilon, self.V_target_policy, id(self.model),
-               device_id, tuple(sorted(self._engine_kwargs().items())))
+               device_id, self.tree_id_base, tuple(sorted(self._engine_kwargs().items())))
         if self._batched is None or key != self._key:
             if self._batched is not None:
                 self._batched.close()
             self._batched = BatchedMCTS(self.model, env_id=env_id, mode=self._mode, n_trees=n_trees, n_rollouts=self.n_rollouts,
                                         c_uct=self.c_uct, gamma=self.gamma, epsilon=self.epsilon,
-                                        V_target_policy=self.V_target_policy, seed=self.seed, device_id=device_id,
-                                        **self._engine_kwargs())
+                                        V_target_policy=self.V_target_policy, seed=self.seed, tree_id_base=self.tree_id_base,
+                                        device_id=device_id, **self._engine_kwargs())
             self._key = key
         return self._batched
 
@@ -193,9 +252,14 @@ class MCTS:
         roots = np.stack([s[1] for s in sigs])
         eng = self._ensure_engine(env_id, len(envs))
         eng.search(roots, self._carry(len(envs)))   # raises ValueError on a terminal root (mcts.py:382-383, 599-600)
+        self._adopt(envs, eng.results(), eng.root_children())
+
+    def _adopt(self, envs: Sequence[Any], res: dict, children) -> None:
+        """Take the results of a search of ``envs`` (one tree each) as this object's last search: what search() does once the
+        engine has run (AgentPopulation hands each agent its rows of a population search this way)."""
         self._envs = list(envs)
-        self._res = eng.results()
-        self._children = eng.root_children()
+        self._res = res
+        self._children = children
         carried = 0 if self.root_node is None else self.root_node.n
         self.root_node = _Root(carried + self.n_rollouts, self.root_state)
 
@@ -225,9 +289,9 @@ class MCTSDiscrete(MCTS):
     _mode = _capi.MODE_DISCRETE
 
     def __init__(self, model, num_actions: int, n_rollouts: int, c_uct: float, gamma: float, epsilon: float, V_target_policy: str,
-                 device: str, root_state: np.ndarray, seed: int = 34):
+                 device: str, root_state: np.ndarray, seed: int = 34, tree_id_base: int = 0):
         super().__init__(model=model, n_rollouts=n_rollouts, c_uct=c_uct, gamma=gamma, epsilon=epsilon, device=device,
-                         V_target_policy=V_target_policy, root_state=root_state, seed=seed)
+                         V_target_policy=V_target_policy, root_state=root_state, seed=seed, tree_id_base=tree_id_base)
         self.num_actions = num_actions
 
     def _engine_kwargs(self) -> dict:
@@ -271,9 +335,9 @@ class MCTSContinuous(MCTS):
     _mode = _capi.MODE_CONTINUOUS
 
     def __init__(self, model, n_rollouts: int, c_uct: float, c_pw: float, kappa: float, gamma: float, epsilon: float,
-                 V_target_policy: str, device: str, root_state: np.ndarray, seed: int = 34):
+                 V_target_policy: str, device: str, root_state: np.ndarray, seed: int = 34, tree_id_base: int = 0):
         super().__init__(model=model, n_rollouts=n_rollouts, c_uct=c_uct, gamma=gamma, epsilon=epsilon, device=device,
-                         V_target_policy=V_target_policy, root_state=root_state, seed=seed)
+                         V_target_policy=V_target_policy, root_state=root_state, seed=seed, tree_id_base=tree_id_base)
         self.c_pw = c_pw
         self.kappa = kappa
 
@@ -286,6 +350,10 @@ class MCTSContinuous(MCTS):
     def search(self, Env) -> None:
         self.root_node = None   # initialize_search always builds a fresh root (mcts.py:589-600)
         super().search(Env)
+
+    def _adopt(self, envs, res, children) -> None:
+        self.root_node = None
+        super()._adopt(envs, res, children)
 
     def _row(self, i: int):
         r = self._res

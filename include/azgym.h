@@ -108,6 +108,8 @@ int azg_set_weights(azg_engine* e, const azg_mlp_desc* desc, const float* blob, 
  * called (producer stream synchronised); it may be reused as soon as the call returns.  Same blob, same network as azg_set_weights. */
 int azg_set_weights_device(azg_engine* e, const azg_mlp_desc* desc, const float* device_blob, size_t n_floats);
 
+/* Populations (K nets with weights of their own in one engine): include/azgym_population.h */
+
 /* index mixed into the RNG counter; auto-incremented by azg_search */
 int azg_set_search_index(azg_engine* e, uint32_t idx);
 
