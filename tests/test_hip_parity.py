@@ -98,80 +98,7 @@ def test_hip_matches_reference_goldens(native, name):
         np.testing.assert_array_equal(c1, c2)
 
 
-CONFIGS = [
-    # (env, mode, hidden, act, n_sims, extra)
-    (2, 1, [256, 256], "elu", 200, dict(c_uct=0.05, gamma=1.0)),
-    (2, 1, [256, 256], "elu", 64, dict(c_uct=0.3, gamma=0.97, c_pw=2.5, kappa=0.7, epsilon=0.2, v_target="on_policy")),
-    (1, 1, [128, 128, 128], "elu", 90, dict(c_uct=0.1, gamma=0.99, c_pw=1.0, kappa=0.5)),
-    (2, 1, [64], "relu", 50, dict(c_uct=0.05, gamma=1.0, c_pw=3.0, kappa=0.9)),
-    (2, 1, [100, 60], "elu", 40, dict(c_uct=0.05, gamma=1.0)),
-    (2, 1, [128, 128, 128, 128, 128], "relu", 30, dict(c_uct=0.05, gamma=1.0)),
-    (0, 0, [128, 128], "relu", 100, dict(c_uct=1.5, gamma=1.0, num_actions=2)),
-    (0, 0, [64, 64], "elu", 60, dict(c_uct=20.0, gamma=0.95, epsilon=0.1, num_actions=2, v_target="on_policy")),
-    (0, 0, [256, 256], "relu", 80, dict(c_uct=5.0, gamma=0.99, num_actions=2)),
-    # the other trunk nonlinearities
-    (2, 1, [64, 64], "leakyrelu", 30, dict(c_uct=0.05, gamma=1.0)),
-    (2, 1, [128, 128], "silu", 30, dict(c_uct=0.05, gamma=1.0)),
-    (0, 0, [64, 64], "hardswish", 40, dict(c_uct=4.0, gamma=1.0, num_actions=2)),
-    (0, 0, [64], "relu6", 40, dict(c_uct=4.0, gamma=1.0, num_actions=2)),
-    # LayerNorm trunks (widths that are not multiples of 64 exercise the padded-unit mask)
-    (2, 1, [100, 60], "elu", 30, dict(c_uct=0.05, gamma=1.0, _ln=True)),
-    (2, 1, [256, 256], "relu", 30, dict(c_uct=0.05, gamma=1.0, _ln=True)),
-    (0, 0, [128, 128, 128], "silu", 30, dict(c_uct=4.0, gamma=1.0, num_actions=2, _ln=True)),
-    # Gaussian-mixture policy heads (the reference's default continuous config: 2 components, 3x128 ELU)
-    (2, 1, [128, 128, 128], "elu", 60, dict(c_uct=0.05, gamma=1.0, _ncomp=2)),
-    (1, 1, [64, 64], "elu", 40, dict(c_uct=0.2, gamma=0.95, c_pw=1.5, kappa=0.6, _ncomp=3)),
-    # wide MLPs (BASELINE config E is 4x1024): weights streamed from L2, activation buffers up to 128 KB of LDS
-    (2, 1, [512, 512], "elu", 30, dict(c_uct=0.05, gamma=1.0)),
-    (2, 1, [512, 512, 512], "elu", 20, dict(c_uct=0.05, gamma=1.0, _ncomp=2)),
-    (2, 1, [1024, 1024, 1024, 1024], "elu", 12, dict(c_uct=0.05, gamma=1.0)),
-    (0, 0, [512], "relu", 40, dict(c_uct=3.0, gamma=1.0, num_actions=2)),
-    # trees too large for LDS residency (> 255 records): global-memory tree storage
-    (2, 1, [64, 64], "elu", 300, dict(c_uct=0.05, gamma=1.0)),
-    (0, 0, [64, 64], "relu", 200, dict(c_uct=8.0, gamma=0.98, num_actions=2)),
-    # up to 16 children per node: the LDS child-list pool grows through all its block sizes (4, 8, 16)
-    (2, 1, [256, 256], "relu", 120, dict(c_uct=0.2, gamma=0.98, c_pw=1.4, kappa=0.5)),
-    (1, 1, [64, 64], "elu", 254, dict(c_uct=0.02, gamma=1.0, c_pw=1.0, kappa=0.5)),
-    # three actions (gym MountainCar-v0): the generic-A paths of evaluation, selection, re-scoring; LDS trees of 8- and 9-bit ids,
-    # global trees, a 2x256 network (8-wave variants), a wide one (lock-step path), epsilon-greedy
-    (3, 0, [64, 64], "relu", 60, dict(c_uct=0.8, gamma=0.99, num_actions=3)),
-    (3, 0, [128, 128], "elu", 120, dict(c_uct=2.0, gamma=1.0, num_actions=3, epsilon=0.2, v_target="on_policy")),
-    (3, 0, [256, 256], "relu", 50, dict(c_uct=1.5, gamma=0.97, num_actions=3)),
-    (3, 0, [512, 512], "relu", 25, dict(c_uct=1.5, gamma=1.0, num_actions=3)),
-    (3, 0, [64], "relu", 200, dict(c_uct=3.0, gamma=0.98, num_actions=3, v_target="greedy")),
-    # MCTSContinuous over an env whose episodes END (gym MountainCarContinuous-v0; mcts.py:619-623, 682): terminal nodes in the continuous
-    # descent -- 4-wave LDS kernels, the 8-wave shapes of 2x256 networks (lean walkers), a mixture head, a wide network (team kernel /
-    # per-layer launches / one-launch kernel), trees in global memory (> 255 records), > 16 children per node
-    (4, 1, [64, 64], "elu", 120, dict(c_uct=0.05, gamma=1.0, action_bound=1.0)),
-    (4, 1, [256, 256], "elu", 150, dict(c_uct=0.1, gamma=0.98, epsilon=0.15, v_target="on_policy", action_bound=1.0)),
-    (4, 1, [128, 128, 128], "elu", 60, dict(c_uct=0.05, gamma=1.0, action_bound=1.0, _ncomp=2)),
-    (4, 1, [512, 512], "elu", 30, dict(c_uct=0.05, gamma=1.0, action_bound=1.0)),
-    (4, 1, [64, 64], "relu", 300, dict(c_uct=0.05, gamma=0.99, action_bound=1.0)),
-    (4, 1, [128, 128], "elu", 90, dict(c_uct=0.2, gamma=1.0, c_pw=2.0, kappa=0.6, action_bound=1.0, v_target="greedy")),
-    # six observations (gym Acrobot-v1): two k-steps in the network's first layer, Runge-Kutta dynamics, reward 0 on the terminal step --
-    # LDS trees of 8- and 9-bit ids, global trees, epsilon-greedy, 2x256 and a wide network (one-launch kernel: the team kernels take
-    # at most four inputs), LayerNorm (weight-streaming kernels)
-    (5, 0, [64, 64], "relu", 60, dict(c_uct=1.0, gamma=0.99, num_actions=3)),
-    (5, 0, [128, 128], "elu", 120, dict(c_uct=2.0, gamma=1.0, num_actions=3, epsilon=0.2, v_target="on_policy")),
-    (5, 0, [256, 256], "relu", 50, dict(c_uct=1.5, gamma=0.97, num_actions=3)),
-    (5, 0, [512, 512], "relu", 20, dict(c_uct=1.5, gamma=1.0, num_actions=3)),
-    (5, 0, [64], "relu", 200, dict(c_uct=3.0, gamma=0.98, num_actions=3, v_target="greedy")),
-    (5, 0, [100, 60], "silu", 30, dict(c_uct=2.0, gamma=1.0, num_actions=3, _ln=True)),
-]
-
-
-def upswing_roots(roots):
-    """Acrobot roots on the upswing (the synthetic ones hang at rest, hundreds of steps from the episode's end)."""
-    return np.stack([1.4 + 6.0 * roots[:, 0], 8.0 * roots[:, 1], 3.0 + 20.0 * roots[:, 2], 20.0 * roots[:, 3]], 1)
-
-
-def slope_roots(roots):
-    """MountainCarContinuous roots on the slope below the flag (the synthetic ones rest in the valley, out of the flag's reach)."""
-    u = (roots[:, 0] + 0.6) / 0.2
-    return np.stack([0.25 + 0.199 * u, 0.02 + 0.05 * ((17.0 * u) % 1.0)], 1)
-
-
-@pytest.mark.parametrize("cfg", CONFIGS, ids=[f"cfg{i}" for i in range(len(CONFIGS))])
+@pytest.mark.parametrize("cfg", P.CONFIGS, ids=[f"cfg{i}" for i in range(len(P.CONFIGS))])
 @pytest.mark.parametrize("variant", ["default", "stream_weights", "global_tree", "persistent", "launches", "waves8", "waves4", "groups2",
                                      "trace_cap1", "trace_cap64", "tile16", "no_spec"])
 def test_hip_bit_exact_vs_oracle(native, cfg, variant, monkeypatch):
@@ -183,78 +110,17 @@ def test_hip_bit_exact_vs_oracle(native, cfg, variant, monkeypatch):
     and as many as a tree can run without the network (default: at most five); full 16-tree tiles where small batches of small
     networks take half-filled ones.  Where a variant's path does not exist for the configuration (`moot` says why), its forcing
     variable must be ignored: the same kernel as an engine created without it, the same records."""
-    env, mode, hidden, act, n_sims, extra = cfg
-    extra = dict(extra)
-    ncomp = extra.pop("_ncomp", 0)
-    ln = extra.pop("_ln", False)
-    moot = None
-    forced = {"stream_weights": "AZG_FORCE_STREAM_WEIGHTS", "global_tree": "AZG_FORCE_GLOBAL_TREE", "waves8": "AZG_WAVES", "waves4": "AZG_WAVES",
-              "groups2": "AZG_GROUPS", "trace_cap1": "AZG_TRACE_CAP", "trace_cap64": "AZG_TRACE_CAP", "no_spec": "AZG_NO_SPEC",
-              "tile16": "AZG_TILE_TREES", "persistent": "AZG_FORCE_PERSISTENT", "launches": "AZG_LS_TEAM"}.get(variant)
-    if variant == "stream_weights":
-        monkeypatch.setenv("AZG_FORCE_STREAM_WEIGHTS", "1")
-    if variant == "global_tree":
-        monkeypatch.setenv("AZG_FORCE_GLOBAL_TREE", "1")
-    if variant in ("waves8", "waves4", "groups2"):
-        if hidden != [256, 256] or ln or ncomp or mode != 1:
-            moot = "the 8-wave workgroups exist for 2x256 squashed-Normal networks (continuous mode)"
-        monkeypatch.setenv(*(("AZG_WAVES", variant[-1]) if variant.startswith("waves") else ("AZG_GROUPS", "2")))
-    if variant in ("trace_cap1", "trace_cap64"):
-        if mode != 0 or max(hidden) > 256:
-            moot = "several traces per step: the discrete persistent search kernels"
-        monkeypatch.setenv("AZG_TRACE_CAP", variant[len("trace_cap"):])
-    if variant == "no_spec":
-        # register-resident one-layer networks with common parameters run kernels specialised at compile time (dispatch.cuh: SPEC);
-        # this variant forces the general kernels on the same inputs
-        # (SPEC kernels keep their trees in LDS with 8-bit ids: at most 255 records per tree -- n_sims + 2 in continuous mode, the root
-        # plus two edges per evaluated node in CartPole's discrete mode; cfg0, the headline shape with its 202 records, is one of them)
-        # -- and so do the team kernels of 1024-wide Pendulum-v1 networks (team_dispatch.cuh: the BASELINE config E shape)
-        records = n_sims + 2 if mode == 1 else 1 + 2 * (n_sims + 1)
-        one_launch = not (len(hidden) != 2 or max(hidden) > 256 or ln or ncomp or extra.get("epsilon", 0.0) != 0.0 or records > 255 or env in (3, 5))
-        team = env == 2 and len(hidden) >= 2 and max(hidden) == 1024 and not ln and not ncomp and extra.get("epsilon", 0.0) == 0.0 and records <= 255
-        if not (one_launch or team):
-            moot = "no compile-time specialised kernel exists for this configuration"
-        monkeypatch.setenv("AZG_NO_SPEC", "1")
-    if variant == "tile16":
-        if max(hidden) > 128 or len(hidden) != 2 or ln or ncomp:
-            moot = "half-filled tiles exist for register-resident networks up to 128 wide"
-        monkeypatch.setenv("AZG_TILE_TREES", "16")
-    if variant in ("persistent", "launches"):
-        if max(hidden) <= 256:
-            moot = "lock-step kernels only exist for hidden widths >= 512"
-        if variant == "persistent":
-            monkeypatch.setenv("AZG_FORCE_PERSISTENT", "1")   # wide networks: the one-launch kernel instead of the lock-step path
-        else:
-            monkeypatch.setenv("AZG_LS_TEAM", "0")            # the per-layer launches instead of the persistent team kernel
+    env, mode, hidden, act, n_sims, extra, ncomp, ln = P.split_config(cfg)
+    moot = P.moot(cfg, variant)
+    forced = P.VARIANT_ENV[variant][0] if variant in P.VARIANT_ENV else None
+    if forced:
+        monkeypatch.setenv(*P.VARIANT_ENV[variant])
     B = 37
     kw = dict(env_id=env, mode=mode, n_trees=B, n_sims=n_sims, seed=1234, tree_id_base=77, **extra)
-    in_dim, n_dist = (2 if env == 4 else 3, 3 * ncomp if ncomp else 2) if mode == 1 else {3: (2, 3), 5: (6, 3)}.get(env, (4, 2))
-    desc = _capi.make_desc(in_dim, hidden, n_dist, act, num_components=ncomp, layernorm=ln)
-    blob = O.make_weights(99, in_dim, hidden, n_dist, scale=2.0)
-    if ln:
-        blob = O.add_layernorm(blob, in_dim, hidden, n_dist, 7)
+    desc, blob = P.config_net(cfg, 99)
     o = O.OracleEngine(**kw)
-    roots = o.synthetic_roots()
+    roots = P.config_roots(env, o.synthetic_roots())
     o.close()
-    if env == 0:
-        roots[3] = [2.35, 1.5, 0.0, 0.0]      # terminates quickly
-        roots[5] = [0.0, 0.0, 0.2, 1.0]
-    if env == 3:
-        roots[3] = [0.44, 0.04]               # the flag is two steps away
-        roots[5] = [-1.195, -0.05]            # into the left wall
-    if env == 5:
-        roots = upswing_roots(roots)
-        for i in range(B):
-            if O.env_step(5, roots[i], 1)[2] and (-np.cos(roots[i][0]) - np.cos(roots[i][1] + roots[i][0])) > 1.0:
-                roots[i] = [1.0, 0.0, 0.5, 0.0]           # (already above the line)
-        roots[3] = [1.9, 0.2, 2.0, 1.0]           # every torque swings the tip over the line: terminal children, reward 0
-        roots[5] = [1.373, -0.681, 2.48, 1.698]   # three steps below it
-        roots[7] = [0.05, -0.03, 0.02, 0.01]      # hanging at rest
-    if env == 4:
-        roots = slope_roots(roots)
-        roots[3] = [0.44, 0.03]               # every action reaches the flag: a search of traces that end in terminal nodes
-        roots[5] = [-1.195, -0.05]            # into the left wall
-        roots[7] = [-0.5, 0.0]                # the valley: no terminal node within reach
     carry = (np.arange(B) % 7).astype(np.int32) if mode == 0 else None
     forms = []
     a = _run(native.HipEngine, kw, desc, blob, roots, carry, sidx=3, forms=forms)
@@ -667,9 +533,9 @@ def test_hip_bit_exact_vs_oracle_random_configurations(native, seed):
     roots = o.synthetic_roots()
     o.close()
     if env == 4:
-        roots = slope_roots(roots)
+        roots = P.slope_roots(roots)
     if env == 5:
-        roots = upswing_roots(roots)
+        roots = P.upswing_roots(roots)
         for i in range(B):
             if (-np.cos(roots[i][0]) - np.cos(roots[i][1] + roots[i][0])) > 0.98:
                 roots[i] = [1.0, 0.0, 0.5, 0.0]
