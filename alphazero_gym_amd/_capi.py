@@ -102,7 +102,8 @@ SYMBOLS = [
 ]
 # entry points a library may lack (the tests' CPU oracle binds SYMBOLS only): bound when present, else the methods that need
 # them raise
-OPTIONAL_SYMBOLS = ["set_population", "set_net_weights"]
+OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device",
+                    "population_selfplay_begin"]
 
 
 def bind(lib, prefix):
@@ -152,6 +153,12 @@ def bind(lib, prefix):
         f["set_population"].argtypes = [vp, C.c_int32]
     if "set_net_weights" in f:
         f["set_net_weights"].argtypes = [vp, C.c_int32, C.POINTER(AzgMlpDesc), C.POINTER(C.c_float), C.c_size_t]
+    if "set_net_weights_device" in f:
+        f["set_net_weights_device"].argtypes = [vp, C.c_int32, C.POINTER(AzgMlpDesc), C.c_void_p, C.c_size_t]
+    if "set_population_weights_device" in f:
+        f["set_population_weights_device"].argtypes = [vp, C.POINTER(AzgMlpDesc), C.c_void_p, C.c_size_t, C.c_int32]
+    if "population_selfplay_begin" in f:
+        f["population_selfplay_begin"].argtypes = [vp, C.POINTER(AzgSelfplayConfig)]
     return f
 
 
@@ -329,6 +336,42 @@ class Engine:
         desc, blob = policy_blob(policy)
         self.set_net_weights(net, desc, blob)
 
+    def set_net_weights_device(self, net, desc, device_ptr, n_floats):
+        """azg_set_net_weights_device: net ``net``'s flat float32 blob already lives on the engine's GPU (complete)."""
+        fn = self._optional("set_net_weights_device")
+        self._check(fn(self._h, int(net), C.byref(desc), C.c_void_p(int(device_ptr)), int(n_floats)))
+        if self.mode == MODE_CONTINUOUS:
+            self.n_dist = desc.n_dist
+
+    def set_population_weights_device(self, desc, device_ptr, n_floats_per_net, n_nets):
+        """azg_set_population_weights_device: every net from one device array [n_nets][n_floats_per_net] (complete), one gather
+        launch."""
+        fn = self._optional("set_population_weights_device")
+        self._check(fn(self._h, C.byref(desc), C.c_void_p(int(device_ptr)), int(n_floats_per_net), int(n_nets)))
+        if self.mode == MODE_CONTINUOUS:
+            self.n_dist = desc.n_dist
+
+    def set_population_policies(self, policies):
+        """Push K torch policies as nets 0..K-1 (K = the engine's n_nets).  When every parameter lives on the engine's GPU they are
+        flattened there into one [K, n] tensor, the torch stream is synchronised once and one call gathers them all ("device");
+        otherwise each net is uploaded from a host blob ("host").  Returns which path was taken."""
+        policies = list(policies)
+        self._optional("set_population_weights_device")
+        pars = [p for pol in policies for p in pol.parameters()]
+        dev = self.cfg.device_id
+        if pars and all(p.is_cuda and p.device.index == dev for p in pars):
+            import torch
+            desc, _ = policy_tensors(policies[0])
+            with torch.no_grad():
+                flat = torch.stack([torch.cat([t.detach().reshape(-1).to(torch.float32) for t in policy_tensors(pol)[1]])
+                                    for pol in policies])
+            torch.cuda.current_stream(pars[0].device).synchronize()
+            self.set_population_weights_device(desc, flat.data_ptr(), flat.shape[1], flat.shape[0])
+            return "device"
+        for k, pol in enumerate(policies):
+            self.set_net_policy(k, pol)
+        return "host"
+
     def results_resident(self):
         """azg_results_resident: launch return_results into the engine's device buffers; their addresses as a dict of ints."""
         ptrs = [C.c_void_p() for _ in range(5)]
@@ -427,11 +470,7 @@ class Engine:
 
 
 def _selfplay_methods():
-    def selfplay_begin(self, max_episode_length, deterministic=False, capacity_steps=64, final_selection="max_visit",
-                       temperature=1.0, agent_epsilon=0.0, fifo=False):
-        """Start device-resident self-play: games reset to their fixed-seed initial states (include/azgym.h).
-        final_selection / temperature / agent_epsilon: the agents' final action rule (agents.py:294-301, 524-535);
-        fifo: the ring overwrites its oldest step like ReplayBuffer.store (buffers.py:75-82) instead of refusing when full."""
+    def _selfplay_config(max_episode_length, deterministic, capacity_steps, final_selection, temperature, agent_epsilon, fifo):
         c = AzgSelfplayConfig()
         c.struct_size = C.sizeof(AzgSelfplayConfig)
         c.max_episode_length = int(max_episode_length)
@@ -441,7 +480,23 @@ def _selfplay_methods():
         c.ring_mode = 1 if fifo else 0
         c.temperature = float(temperature)
         c.agent_epsilon = float(agent_epsilon)
+        return c
+
+    def selfplay_begin(self, max_episode_length, deterministic=False, capacity_steps=64, final_selection="max_visit",
+                       temperature=1.0, agent_epsilon=0.0, fifo=False):
+        """Start device-resident self-play: games reset to their fixed-seed initial states (include/azgym.h).
+        final_selection / temperature / agent_epsilon: the agents' final action rule (agents.py:294-301, 524-535);
+        fifo: the ring overwrites its oldest step like ReplayBuffer.store (buffers.py:75-82) instead of refusing when full."""
+        c = _selfplay_config(max_episode_length, deterministic, capacity_steps, final_selection, temperature, agent_epsilon, fifo)
         self._check(self._f["selfplay_begin_ex"](self._h, C.byref(c)))
+        self._sp_cap = int(capacity_steps)
+
+    def population_selfplay_begin(self, max_episode_length, deterministic=False, capacity_steps=64, final_selection="max_visit",
+                                  temperature=1.0, agent_epsilon=0.0, fifo=False):
+        """selfplay_begin for an engine with any number of nets (azg_population_selfplay_begin): net k plays games k*T .. k*T+T-1,
+        and its rows of a step are that block of the step's n_trees rows."""
+        c = _selfplay_config(max_episode_length, deterministic, capacity_steps, final_selection, temperature, agent_epsilon, fifo)
+        self._check(self._optional("population_selfplay_begin")(self._h, C.byref(c)))
         self._sp_cap = int(capacity_steps)
 
     def selfplay_ring(self):
@@ -482,7 +537,7 @@ def _selfplay_methods():
         self._check(self._f["selfplay_stats"](self._h, _ptr(fsum, C.c_double), _ptr(fcnt, C.c_int32), _ptr(state, C.c_double)))
         return fsum, fcnt, state
 
-    for fn in (selfplay_begin, selfplay_ring, selfplay_rows_device, selfplay_step, selfplay_rows, selfplay_clear, selfplay_stats):
+    for fn in (selfplay_begin, population_selfplay_begin, selfplay_ring, selfplay_rows_device, selfplay_step, selfplay_rows, selfplay_clear, selfplay_stats):
         setattr(Engine, fn.__name__, fn)
 
 

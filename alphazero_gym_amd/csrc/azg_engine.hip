@@ -492,16 +492,28 @@ __global__ __launch_bounds__(256) void weight_gather_kernel(const unsigned* __re
     if (i < n) { const unsigned s = src[i]; out[i] = s ? blob[s - 1] : 0.0f; }
 }
 
-// Common body of azg_set_weights / azg_set_weights_device: `blob` is a host pointer (on_device false) or a device pointer whose
-// contents are complete (its producer's stream synchronised or otherwise ordered before this call).
-// `net`: which net of a population (azg_set_population) the weights are for; 0 for an engine of one net.
-static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* blob, size_t n_floats, bool on_device, int net = 0) {
+// The population form: blockIdx.y = net k (of the nets written by one call) gathers blob k (blob + k * blob_stride) through the same
+// map into its block of the engine's weight buffer (out + k * n): every net of a population in one launch.
+__global__ __launch_bounds__(256) void weight_gather_nets_kernel(const unsigned* __restrict__ src, const float* __restrict__ blob,
+                                                                 size_t blob_stride, float* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t k = blockIdx.y;
+    if (i < n) { const unsigned s = src[i]; out[k * n + i] = s ? blob[k * blob_stride + s - 1] : 0.0f; }
+}
+
+// Common body of azg_set_weights / _device and the population uploads: `blob` is a host pointer (on_device false) or a device pointer
+// whose contents are complete (its producer's stream synchronised or otherwise ordered before this call).
+// `net`: which net of a population (azg_set_population) the weights are for; 0 for an engine of one net.  `n_write` nets net ..
+// net + n_write - 1 are written from consecutive blobs of n_floats each (more than one: device blobs only, one gather launch).
+static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* blob, size_t n_floats, bool on_device, int net = 0,
+                            int n_write = 1) {
     if (!e || !d || !blob) return AZG_E_INVALID;
+    if (n_write != 1 && !on_device) return AZG_E_INVALID;
     int HP = 0, ncomp = 0;
     { int rc = check_desc(e, d, n_floats, &HP, &ncomp); if (rc) return rc; }
     const int NN = e->n_nets;
-    bool others = false;   // another net of the population already has weights: they fix the descriptor
-    for (int k = 0; k < NN; ++k) others = others || (k != net && e->net_have[k]);
+    bool others = false;   // a net of the population that keeps its weights already has some: they fix the descriptor
+    for (int k = 0; k < NN; ++k) others = others || ((k < net || k >= net + n_write) && e->net_have[k]);
     if (NN > 1) {
         if (HP >= 512)
             return fail(e, AZG_E_UNSUPPORTED, "populations: networks wider than 256 (padded) run as team / per-layer searches, which take one "
@@ -536,7 +548,7 @@ static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* b
         e->d_wblob = (float*)q; e->w_floats = n_out_f;
     }
     float* const wnet = e->d_wblob + (size_t)net * n_out_f;
-    e->net_have[net] = 0;
+    for (int k = net; k < net + n_write; ++k) e->net_have[k] = 0;
     if (on_device) {
         if (!e->d_wmap) {
             void* q = nullptr;
@@ -544,7 +556,14 @@ static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* b
             e->d_wmap = (unsigned*)q;
             HIPCHK(e, hipMemcpy(e->d_wmap, m.src.data(), n_out_f * sizeof(unsigned), hipMemcpyHostToDevice));
         }
-        hipLaunchKernelGGL(weight_gather_kernel, dim3((unsigned)((n_out_f + 255) / 256)), dim3(256), 0, e->stream, e->d_wmap, blob, wnet, n_out_f);
+        if (n_write == 1)
+            hipLaunchKernelGGL(weight_gather_kernel, dim3((unsigned)((n_out_f + 255) / 256)), dim3(256), 0, e->stream, e->d_wmap, blob, wnet, n_out_f);
+        else
+            for (int k0 = 0; k0 < n_write; k0 += 65535) {   // (grid.y is at most 65535)
+                const int nk = n_write - k0 < 65535 ? n_write - k0 : 65535;
+                hipLaunchKernelGGL(weight_gather_nets_kernel, dim3((unsigned)((n_out_f + 255) / 256), (unsigned)nk), dim3(256), 0, e->stream,
+                                   e->d_wmap, blob + (size_t)k0 * n_floats, n_floats, wnet + (size_t)k0 * n_out_f, n_out_f);
+            }
         HIPCHK(e, hipGetLastError());
         HIPCHK(e, hipStreamSynchronize(e->stream));   // the caller may overwrite its blob as soon as this returns
     } else {
@@ -554,7 +573,7 @@ static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* b
         for (size_t i = 0; i < n_out_f; ++i) st[i] = src[i] ? blob[src[i] - 1] : 0.0f;
         HIPCHK(e, hipMemcpy(wnet, st.data(), n_out_f * sizeof(float), hipMemcpyHostToDevice));
     }
-    e->net_have[net] = 1;
+    for (int k = net; k < net + n_write; ++k) e->net_have[k] = 1;
     e->P.net_wstride = NN > 1 ? n_out_f : 0;
     const float* wb = e->d_wblob;   // (net 0's tensors; the search kernel adds net_wstride per net)
     e->P.W0u = (const f32x4*)(wb + m.oW0u);
@@ -650,6 +669,19 @@ int azg_set_net_weights(azg_engine* e, int32_t net, const azg_mlp_desc* d, const
     if (!e) return AZG_E_INVALID;
     if (net < 0 || net >= e->n_nets) return fail(e, AZG_E_INVALID, "azg_set_net_weights: net index out of range");
     return set_weights_impl(e, d, blob, n_floats, false, net);
+}
+
+int azg_set_net_weights_device(azg_engine* e, int32_t net, const azg_mlp_desc* d, const float* device_blob, size_t n_floats) {
+    if (!e) return AZG_E_INVALID;
+    if (net < 0 || net >= e->n_nets) return fail(e, AZG_E_INVALID, "azg_set_net_weights_device: net index out of range");
+    return set_weights_impl(e, d, device_blob, n_floats, true, net);
+}
+
+int azg_set_population_weights_device(azg_engine* e, const azg_mlp_desc* d, const float* device_blobs, size_t n_floats_per_net, int32_t n_nets) {
+    if (!e) return AZG_E_INVALID;
+    if (n_nets != e->n_nets)
+        return fail(e, AZG_E_INVALID, "azg_set_population_weights_device: n_nets must equal the engine's number of nets (azg_set_population)");
+    return set_weights_impl(e, d, device_blobs, n_floats_per_net, true, 0, n_nets);
 }
 
 int azg_set_search_index(azg_engine* e, uint32_t idx) { if (!e) return AZG_E_INVALID; e->search_idx = idx; return AZG_OK; }
@@ -1012,9 +1044,10 @@ int azg_synthetic_roots(azg_engine* e, double* roots) {
 
 int azg_selfplay_row_len(const azg_engine* e) { return e ? e->S_obs + 3 * e->Kmax + 1 : AZG_E_INVALID; }
 
-int azg_selfplay_begin_ex(azg_engine* e, const azg_selfplay_config* c) {
-    if (!e || !c) return AZG_E_INVALID;
-    if (e->n_nets > 1) return fail(e, AZG_E_UNSUPPORTED, "device self-play is not available for populations (azg_set_population > 1)");
+// Common body of azg_selfplay_begin_ex and azg_population_selfplay_begin.  A population's games are its trees: net k plays games
+// k*T .. k*T+T-1 (global ids tree_id_base + k*T + j), and the self-play kernels work per tree on what the search returned, so the
+// steps, rows, ring and stats are those of an engine of one net.
+static int selfplay_begin_impl(azg_engine* e, const azg_selfplay_config* c) {
     if (c->struct_size != (int32_t)sizeof(azg_selfplay_config)) return fail(e, AZG_E_INVALID, "azg_selfplay_config size mismatch");
     if (c->max_episode_length < 1 || c->capacity_steps < 1) return fail(e, AZG_E_INVALID, "max_episode_length and capacity_steps must be >= 1");
     if (c->final_selection != AZG_FS_MAX_VISIT && c->final_selection != AZG_FS_MAX_VALUE) return fail(e, AZG_E_INVALID, "unknown final_selection");
@@ -1061,6 +1094,18 @@ int azg_selfplay_begin_ex(azg_engine* e, const azg_selfplay_config* c) {
     e->sp_insert = 0; e->sp_total = 0; e->sp_fs = c->final_selection; e->sp_ring = c->ring_mode; e->sp_agent_eps = c->agent_epsilon;
     e->sp_step_idx = 0;
     return AZG_OK;
+}
+
+int azg_selfplay_begin_ex(azg_engine* e, const azg_selfplay_config* c) {
+    if (!e || !c) return AZG_E_INVALID;
+    if (e->n_nets > 1)
+        return fail(e, AZG_E_UNSUPPORTED, "device self-play of a population (azg_set_population > 1) starts with azg_population_selfplay_begin");
+    return selfplay_begin_impl(e, c);
+}
+
+int azg_population_selfplay_begin(azg_engine* e, const azg_selfplay_config* c) {
+    if (!e || !c) return AZG_E_INVALID;
+    return selfplay_begin_impl(e, c);
 }
 
 int azg_selfplay_begin(azg_engine* e, int32_t max_episode_length, int32_t deterministic, int32_t capacity_steps) {

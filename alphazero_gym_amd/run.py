@@ -3,7 +3,8 @@
 ``run_continuous_agent`` / ``run_discrete_agent`` mirror run_continuous.py:15-165 / run_discrete.py:16-146: one game, one
 tree, ``act -> buffer.store -> Env.step -> reset_mcts | mcts_forward`` per step, ``agent.train(buffer)`` per episode.
 ``run_population`` is the same loop for K seeds at once: every step searches all K agents' trees in one launch
-(AgentPopulation); training stays each agent's own optimiser step.  ``BatchedSelfPlay`` is the scaled-out form the engine is
+(AgentPopulation); training stays each agent's own optimiser step.  ``PopulationSelfPlay`` is ``DeviceSelfPlay`` for K policies
+in one engine: K nets' games, searches and replay rows stay on the GPU.  ``BatchedSelfPlay`` is the scaled-out form the engine is
 built for: B games per GPU advance in lock step, one search launch per environment step, replay rows gathered across ranks,
 weights broadcast after the optimiser step.
 
@@ -339,6 +340,125 @@ class DeviceSelfPlay:
     def mean_finished_return(self) -> float:
         fsum, fcnt, _ = self.engine.selfplay_stats()
         return float(fsum.sum() / max(int(fcnt.sum()), 1))
+
+
+class PopulationSelfPlay:
+    """Device self-play for K policies in ONE engine (azg_population_selfplay_begin): ``policies[k]`` plays games k*T .. k*T+T-1
+    (T = ``games_per_net``) with global ids ``tree_id_base + k*T + j``, the games ``DeviceSelfPlay(policies[k], n_games=T, rank=k)``
+    plays, bit for bit, with one search launch and one self-play launch per step for the whole population.  The keywords are
+    ``DeviceSelfPlay``'s and shared by every net (game, search and self-play settings).  Weights are re-uploaded only when some
+    policy changed: with every parameter on the engine's GPU in one gather launch for all nets, otherwise one host upload per
+    changed net (``last_weight_sync``: "device", "host" or None when nothing changed)."""
+
+    def __init__(self, policies, *, game: str, games_per_net: int, n_rollouts: int, c_uct: float, gamma: float = 1.0, epsilon: float = 0.0,
+                 c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
+                 deterministic: bool = False, capacity_steps: int = 64, seed: int = 34, tree_id_base: int = 0, device_id: int = 0,
+                 final_selection: str = "max_visit", temperature: float = 1.0, agent_epsilon: float = 0.0, fifo: bool = False):
+        from . import _native   # raises if libazgym_hip.so is missing
+        from .search.mcts import _weights_version
+
+        self.policies = list(policies)
+        if not self.policies or games_per_net < 1:
+            raise ValueError("PopulationSelfPlay needs at least one policy and games_per_net >= 1")
+        self.n_nets, self.games_per_net = len(self.policies), int(games_per_net)
+        self.n_games = self.n_nets * self.games_per_net
+        p0 = self.policies[0]
+        g = game.lower()
+        self.continuous = g.startswith(("pendulum", "mountaincarcontinuous"))
+        if self.continuous:
+            env_id = (_capi.ENV_MOUNTAINCAR_CONT if g.startswith("mountaincarcontinuous")
+                      else (_capi.ENV_PENDULUM_V0 if game.endswith("v0") else _capi.ENV_PENDULUM_V1))
+            kw = dict(env_id=env_id, mode=_capi.MODE_CONTINUOUS, c_pw=c_pw, kappa=kappa, action_bound=float(p0.action_bound))
+        else:
+            env_id = _capi.ENV_MOUNTAINCAR if g.startswith("mountaincar") else (_capi.ENV_ACROBOT if g.startswith("acrobot") else _capi.ENV_CARTPOLE)
+            kw = dict(env_id=env_id, mode=_capi.MODE_DISCRETE, num_actions=p0.num_actions)
+        self.engine = _native.HipEngine(n_trees=self.n_games, n_sims=n_rollouts, c_uct=c_uct, gamma=gamma, epsilon=epsilon,
+                                        v_target=V_target_policy, seed=seed, tree_id_base=tree_id_base, device_id=device_id, **kw)
+        self.engine.set_population(self.n_nets)
+        self._version_of = _weights_version
+        self._versions: List = [None] * self.n_nets
+        self.last_weight_sync = None
+        self.sync_weights()
+        self.capacity = capacity_steps
+        self.fifo = fifo
+        self._replay = None
+        self.engine.population_selfplay_begin(max_episode_length, deterministic, capacity_steps, final_selection=final_selection,
+                                              temperature=temperature, agent_epsilon=agent_epsilon, fifo=fifo)
+
+    def sync_weights(self, force: bool = False) -> None:
+        """Upload the nets whose policy changed since its last upload (all of them in one launch when they live on the GPU)."""
+        versions = [self._version_of(p) for p in self.policies]
+        changed = [k for k in range(self.n_nets) if force or versions[k] != self._versions[k]]
+        self.last_weight_sync = None
+        if not changed:
+            return
+        dev = self.engine.cfg.device_id
+        if all(p.is_cuda and p.device.index == dev for pol in self.policies for p in pol.parameters()):
+            self.last_weight_sync = self.engine.set_population_policies(self.policies)
+        else:
+            for k in changed:
+                self.engine.set_net_policy(k, self.policies[k])
+            self.last_weight_sync = "host"
+        self._versions = versions
+
+    def play(self, n_steps: int) -> None:
+        """n_steps self-play steps of every game of every net (asynchronous: launches only); rows accumulate in the device ring."""
+        assert self.fifo or n_steps <= self.capacity
+        self.sync_weights()
+        for _ in range(n_steps):
+            self.engine.selfplay_step()
+
+    def _split(self, rows, n_steps: int) -> List[torch.Tensor]:
+        """[n_steps * n_games, row] in step-major order -> net k's [n_steps * T, row] (the order of its DeviceSelfPlay)."""
+        blocks = rows.reshape(n_steps, self.n_nets, self.games_per_net, -1)
+        return [blocks[:, k].reshape(n_steps * self.games_per_net, -1) for k in range(self.n_nets)]
+
+    def collect(self, n_steps: int) -> List[torch.Tensor]:
+        """Play n_steps (<= capacity) and return every net's replay rows since the last clear as host float32 tensors
+        [steps * T, row] (net k's games in DeviceSelfPlay.collect's order); the ring is cleared."""
+        assert n_steps <= self.capacity
+        self.play(n_steps)
+        rows = torch.from_numpy(self.engine.selfplay_rows(clear=True).copy())
+        return [r.clone() for r in self._split(rows, rows.shape[0] // self.n_games)]
+
+    def collect_device(self, n_steps: int) -> List[torch.Tensor]:
+        """Play n_steps and return every net's NEW rows as device tensors [n_steps * T, row] (copies in HBM), as
+        DeviceSelfPlay.collect_device returns them per net: the ring is cleared, unless it runs in FIFO mode."""
+        if self._replay is None:
+            self._replay = DeviceReplay(self.engine, 1)
+        assert n_steps <= self.capacity, "the ring keeps its newest capacity_steps steps: older ones would already be overwritten"
+        if not self.fifo:
+            self.play(n_steps)
+            rows = self._replay.rows()
+            out = [r.clone() for r in self._split(rows, rows.shape[0] // self.n_games)]
+            self.engine.selfplay_clear()
+            return out
+        before = self.engine.selfplay_ring()
+        self.play(n_steps)
+        size, insert, _ = self.engine.selfplay_ring()
+        ring = self._replay.rows().reshape(size, self.n_games, -1)
+        # the n_steps newest slots, oldest first: while filling they are the tail; once full they end just before insert_index
+        if before[0] + n_steps <= self.capacity:
+            new = ring[before[0]:before[0] + n_steps]
+        else:
+            idx = [(insert - n_steps + i) % size for i in range(n_steps)]
+            new = ring[torch.as_tensor(idx, device=ring.device)]
+        return [r.clone() for r in self._split(new, n_steps)]
+
+    def finished_returns(self):
+        """(fsum [K] float64, fcnt [K] int64): the returns and the number of the episodes each net's games finished so far, summed
+        over the net's games in tree order."""
+        fsum, fcnt, _ = self.engine.selfplay_stats()
+        fsum = fsum.reshape(self.n_nets, self.games_per_net)
+        fcnt = fcnt.reshape(self.n_nets, self.games_per_net).astype(np.int64)
+        s, c = np.zeros(self.n_nets), np.zeros(self.n_nets, np.int64)
+        for j in range(self.games_per_net):
+            s += fsum[:, j]
+            c += fcnt[:, j]
+        return s, c
+
+    def close(self) -> None:
+        self.engine.close()
 
 
 def train_on_rows(agent, rows: torch.Tensor, state_dim: int, K: int, batch_size: int = 32, shuffle_seed: int = 0) -> Dict[str, float]:

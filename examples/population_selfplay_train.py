@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Population self-play + training: K seeds' nets trained at once in one engine, the population form of selfplay_train.py.
+Net k's games (--games-per-seed of them, global game ids k*T ...) are played on the device together with every other net's
+(azg_population_selfplay_begin: one search launch and one self-play launch per step for the whole population); each iteration
+downloads the new replay rows, trains every net on its own rows with its own optimiser, one net after another, and re-uploads
+the changed nets (one gather launch for all of them when the nets live on the GPU).
+
+    python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
+
+Seed k sets net k's initial weights (torch.manual_seed), and its own np.random.RandomState picks the training rows and the
+minibatch shuffles.  Prints one JSON line per iteration: per-seed mean return of the episodes finished in it and mean loss, and
+the time spent in self-play, training and weight sync."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from alphazero_gym_amd import run  # noqa: E402
+from selfplay_train import build_agent  # noqa: E402
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--game", default="CartPole-v0")
+    ap.add_argument("--seeds", type=int, nargs="+", default=[0, 1, 2, 3])
+    ap.add_argument("--games-per-seed", type=int, default=64)
+    ap.add_argument("--n-rollouts", type=int, default=32)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--steps-per-iter", type=int, default=20)
+    ap.add_argument("--train-rows", type=int, default=512, help="replay rows sampled per seed and iteration")
+    ap.add_argument("--batch-size", type=int, default=128)
+    ap.add_argument("--hidden", type=int, nargs="+", default=[128, 128])
+    ap.add_argument("--max-episode-length", type=int, default=200)
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--engine-seed", type=int, default=34, help="the engine's RNG seed (shared; games differ by their global ids)")
+    ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
+    return ap.parse_args(argv)
+
+
+def build_population(a):
+    """One agent per seed (its initial weights drawn after torch.manual_seed(seed)) and the self-play engine of them all."""
+    agents = []
+    for s in a.seeds:
+        torch.manual_seed(s)
+        agent, state_dim = build_agent(a.game, a.hidden, a.n_rollouts, a.device, a.lr)
+        agents.append(agent)
+    m = agents[0].mcts
+    sp = run.PopulationSelfPlay([ag.nn for ag in agents], game=a.game, games_per_net=a.games_per_seed, n_rollouts=a.n_rollouts,
+                                c_uct=m.c_uct, gamma=m.gamma, epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0),
+                                kappa=getattr(m, "kappa", 0.5), max_episode_length=a.max_episode_length,
+                                capacity_steps=a.steps_per_iter, seed=a.engine_seed,
+                                device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0)
+    return agents, state_dim, sp
+
+
+def train(a, log=print, on_rows=None):
+    """Runs the loop; returns the per-iteration records.  ``on_rows(it, rows)``, if given, sees every iteration's per-seed rows."""
+    agents, state_dim, sp = build_population(a)
+    K = sp.engine.kmax
+    rngs = [np.random.RandomState(s) for s in a.seeds]
+    on_gpu = a.device.startswith("cuda")
+    fs0, fc0 = np.zeros(len(a.seeds)), np.zeros(len(a.seeds), np.int64)
+    t0 = time.time()
+    history = []
+    for it in range(a.iters):
+        t1 = time.time()
+        rows = sp.collect_device(a.steps_per_iter) if on_gpu else sp.collect(a.steps_per_iter)
+        t2 = time.time()
+        if on_rows is not None:
+            on_rows(it, rows)
+        losses = []
+        for agent, rng, r in zip(agents, rngs, rows):
+            pick = rng.choice(r.shape[0], size=min(a.train_rows, r.shape[0]), replace=False)
+            info = run.train_on_rows(agent, r[torch.from_numpy(pick).to(r.device)], state_dim, K, batch_size=a.batch_size,
+                                     shuffle_seed=int(rng.randint(2 ** 31 - 1)))
+            losses.append(info["loss"] / max(1, len(pick) // a.batch_size))
+        t3 = time.time()
+        sp.sync_weights()
+        t4 = time.time()
+        fs, fc = sp.finished_returns()
+        mean_ret = (fs - fs0) / np.maximum(fc - fc0, 1)
+        history.append({"iter": it, "mean_return": [round(float(x), 2) for x in mean_ret],
+                        "episodes_finished": [int(x) for x in fc - fc0], "loss": [round(float(x), 4) for x in losses],
+                        "selfplay_s": round(t2 - t1, 4), "train_s": round(t3 - t2, 4), "sync_s": round(t4 - t3, 4),
+                        "weight_sync": sp.last_weight_sync,
+                        "env_steps": (it + 1) * a.steps_per_iter * sp.n_games, "elapsed_s": round(time.time() - t0, 2)})
+        if log:
+            log(json.dumps(history[-1]), flush=True)
+        fs0, fc0 = fs, fc
+    sp.close()
+    return history
+
+
+def main():
+    train(parse_args())
+
+
+if __name__ == "__main__":
+    main()

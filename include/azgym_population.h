@@ -6,9 +6,11 @@
  * an engine without nets (seed and search index stay per engine).  Results, root children and tree dumps keep their order and
  * shapes.  Changing n_nets drops every weight; 1 restores the single-network engine.  All nets share the game, azg_config and the
  * network descriptor; they differ in their weights.
- * With n_nets > 1: azg_set_weights / _device return AZG_E_STATE; azg_search* return AZG_E_STATE until every net has weights;
- * networks wider than 256 (padded: the team / per-layer forms), azg_selfplay_begin*, azg_mlp_eval and azg_root_eval return
- * AZG_E_UNSUPPORTED.  The CPU oracle does not export these: the tests hold a K-net engine against K single-net engines. */
+ * With n_nets > 1: azg_set_weights / _device return AZG_E_STATE; azg_search* and azg_selfplay_step return AZG_E_STATE until every
+ * net has weights; networks wider than 256 (padded: the team / per-layer forms), azg_selfplay_begin / _ex (a population starts
+ * self-play with azg_population_selfplay_begin), azg_mlp_eval and azg_root_eval return AZG_E_UNSUPPORTED; azg_set_population
+ * while self-play runs returns AZG_E_UNSUPPORTED.  The CPU oracle does not export these: the tests hold a K-net engine against K
+ * single-net engines. */
 #ifndef AZGYM_POPULATION_H
 #define AZGYM_POPULATION_H
 #include "azgym.h"
@@ -20,6 +22,19 @@ extern "C" {
 int azg_set_population(azg_engine* e, int32_t n_nets);
 /* net k's weights (the azg_set_weights blob, host memory); every net must have the same descriptor */
 int azg_set_net_weights(azg_engine* e, int32_t net, const azg_mlp_desc* desc, const float* blob, size_t n_floats);
+/* the same from a device blob (complete: its producer's stream synchronised); azg_set_weights_device for one net */
+int azg_set_net_weights_device(azg_engine* e, int32_t net, const azg_mlp_desc* desc, const float* device_blob, size_t n_floats);
+/* every net at once from one device array [n_nets][n_floats_per_net] (blob k: net k, azg_set_weights blob order): one gather launch
+ * and one stream synchronisation.  n_nets must equal the engine's (1: azg_set_weights_device).  Every net gets `desc`; the
+ * population checks of azg_set_net_weights apply (HP >= 512: AZG_E_UNSUPPORTED).  NULL pointers or a wrong n_floats_per_net:
+ * AZG_E_INVALID.  On failure no net has weights (nothing half written is searched). */
+int azg_set_population_weights_device(azg_engine* e, const azg_mlp_desc* desc, const float* device_blobs, size_t n_floats_per_net,
+                                      int32_t n_nets);
+/* azg_selfplay_begin_ex for an engine with any n_nets (1: exactly azg_selfplay_begin_ex).  Net k plays games k*T .. k*T+T-1 with
+ * global ids tree_id_base + k*T + j: bit for bit what an engine of T games, tree_id_base + k*T and net k's weights plays.
+ * azg_selfplay_step / _rows / _rows_device / _ring / _stats work unchanged; the ring stays [capacity_steps][n_trees][row_len], so
+ * net k's rows of a step are the block k*T .. k*T+T-1.  azg_set_net_weights* between steps replace nets' weights. */
+int azg_population_selfplay_begin(azg_engine* e, const azg_selfplay_config* cfg);
 
 #ifdef __cplusplus
 }
