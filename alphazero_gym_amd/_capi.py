@@ -286,32 +286,44 @@ class Engine:
         except Exception:
             pass
 
-    def set_weights(self, desc, blob):
-        blob = np.ascontiguousarray(blob, dtype=np.float32)
-        self._check(self._f["set_weights"](self._h, C.byref(desc), _ptr(blob, C.c_float), blob.size))
+    def _weights_set(self, rc, desc):
+        """Check a set_*weights* call; a continuous head's n_dist is then the net's (3 * num_components with a mixture)."""
+        self._check(rc)
         if self.mode == MODE_CONTINUOUS:
             self.n_dist = desc.n_dist
+
+    def set_weights(self, desc, blob):
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        self._weights_set(self._f["set_weights"](self._h, C.byref(desc), _ptr(blob, C.c_float), blob.size), desc)
 
     def set_weights_device(self, desc, device_ptr, n_floats):
         """azg_set_weights_device: the flat float32 blob already lives on the engine's GPU (complete: producer stream synchronised)."""
-        self._check(self._f["set_weights_device"](self._h, C.byref(desc), C.c_void_p(int(device_ptr)), int(n_floats)))
-        if self.mode == MODE_CONTINUOUS:
-            self.n_dist = desc.n_dist
+        self._weights_set(self._f["set_weights_device"](self._h, C.byref(desc), C.c_void_p(int(device_ptr)), int(n_floats)), desc)
+
+    def _flat_on_device(self, policies):
+        """(desc, [K, n] float32 tensor) of K torch policies flattened on the engine's GPU (one torch.cat per policy; the torch stream
+        is synchronised), or None when some parameter lives elsewhere."""
+        pars = [p for pol in policies for p in pol.parameters()]
+        if not pars or not all(p.is_cuda and p.device.index == self.cfg.device_id for p in pars):
+            return None
+        import torch
+        parts = [policy_tensors(pol) for pol in policies]
+        with torch.no_grad():
+            rows = [torch.cat([t.detach().reshape(-1).to(torch.float32) for t in tensors]) for _, tensors in parts]
+        flat = rows[0][None] if len(rows) == 1 else torch.stack(rows)
+        torch.cuda.current_stream(pars[0].device).synchronize()
+        return parts[0][0], flat
 
     def set_policy(self, policy):
-        """Push a torch policy's weights.  Parameters on the engine's GPU are flattened there (one torch.cat into a device
-        buffer) and re-laid-out by the engine's gather kernel: nothing crosses PCIe; CPU parameters take the host path."""
-        par = next(policy.parameters(), None)
-        if par is not None and par.is_cuda and par.device.index == self.cfg.device_id:
-            import torch
-            desc, tensors = policy_tensors(policy)
-            with torch.no_grad():
-                flat = torch.cat([t.detach().reshape(-1).to(torch.float32) for t in tensors])
-            torch.cuda.current_stream(par.device).synchronize()
-            self.set_weights_device(desc, flat.data_ptr(), flat.numel())
-            return
-        desc, blob = policy_blob(policy)
-        self.set_weights(desc, blob)
+        """Push a torch policy's weights.  Parameters on the engine's GPU are flattened there and re-laid-out by the engine's gather
+        kernel: nothing crosses PCIe ("device"); CPU parameters take the host path ("host").  Returns which path was taken."""
+        on_device = self._flat_on_device([policy])
+        if on_device is not None:
+            desc, flat = on_device
+            self.set_weights_device(desc, flat.data_ptr(), flat.shape[1])
+            return "device"
+        self.set_weights(*policy_blob(policy))
+        return "host"
 
     def _optional(self, name):
         fn = self._f.get(name)
@@ -327,9 +339,7 @@ class Engine:
 
     def set_net_weights(self, net, desc, blob):
         blob = np.ascontiguousarray(blob, dtype=np.float32)
-        self._check(self._optional("set_net_weights")(self._h, int(net), C.byref(desc), _ptr(blob, C.c_float), blob.size))
-        if self.mode == MODE_CONTINUOUS:
-            self.n_dist = desc.n_dist
+        self._weights_set(self._optional("set_net_weights")(self._h, int(net), C.byref(desc), _ptr(blob, C.c_float), blob.size), desc)
 
     def set_net_policy(self, net, policy):
         """Push a torch policy's weights as net ``net`` of the population (host blob: one H2D copy per net)."""
@@ -339,17 +349,13 @@ class Engine:
     def set_net_weights_device(self, net, desc, device_ptr, n_floats):
         """azg_set_net_weights_device: net ``net``'s flat float32 blob already lives on the engine's GPU (complete)."""
         fn = self._optional("set_net_weights_device")
-        self._check(fn(self._h, int(net), C.byref(desc), C.c_void_p(int(device_ptr)), int(n_floats)))
-        if self.mode == MODE_CONTINUOUS:
-            self.n_dist = desc.n_dist
+        self._weights_set(fn(self._h, int(net), C.byref(desc), C.c_void_p(int(device_ptr)), int(n_floats)), desc)
 
     def set_population_weights_device(self, desc, device_ptr, n_floats_per_net, n_nets):
         """azg_set_population_weights_device: every net from one device array [n_nets][n_floats_per_net] (complete), one gather
         launch."""
         fn = self._optional("set_population_weights_device")
-        self._check(fn(self._h, C.byref(desc), C.c_void_p(int(device_ptr)), int(n_floats_per_net), int(n_nets)))
-        if self.mode == MODE_CONTINUOUS:
-            self.n_dist = desc.n_dist
+        self._weights_set(fn(self._h, C.byref(desc), C.c_void_p(int(device_ptr)), int(n_floats_per_net), int(n_nets)), desc)
 
     def set_population_policies(self, policies):
         """Push K torch policies as nets 0..K-1 (K = the engine's n_nets).  When every parameter lives on the engine's GPU they are
@@ -357,15 +363,9 @@ class Engine:
         otherwise each net is uploaded from a host blob ("host").  Returns which path was taken."""
         policies = list(policies)
         self._optional("set_population_weights_device")
-        pars = [p for pol in policies for p in pol.parameters()]
-        dev = self.cfg.device_id
-        if pars and all(p.is_cuda and p.device.index == dev for p in pars):
-            import torch
-            desc, _ = policy_tensors(policies[0])
-            with torch.no_grad():
-                flat = torch.stack([torch.cat([t.detach().reshape(-1).to(torch.float32) for t in policy_tensors(pol)[1]])
-                                    for pol in policies])
-            torch.cuda.current_stream(pars[0].device).synchronize()
+        on_device = self._flat_on_device(policies)
+        if on_device is not None:
+            desc, flat = on_device
             self.set_population_weights_device(desc, flat.data_ptr(), flat.shape[1], flat.shape[0])
             return "device"
         for k, pol in enumerate(policies):
@@ -470,7 +470,11 @@ class Engine:
 
 
 def _selfplay_methods():
-    def _selfplay_config(max_episode_length, deterministic, capacity_steps, final_selection, temperature, agent_epsilon, fifo):
+    def selfplay_begin(self, max_episode_length, deterministic=False, capacity_steps=64, final_selection="max_visit",
+                       temperature=1.0, agent_epsilon=0.0, fifo=False, _symbol="selfplay_begin_ex"):
+        """Start device-resident self-play: games reset to their fixed-seed initial states (include/azgym.h).
+        final_selection / temperature / agent_epsilon: the agents' final action rule (agents.py:294-301, 524-535);
+        fifo: the ring overwrites its oldest step like ReplayBuffer.store (buffers.py:75-82) instead of refusing when full."""
         c = AzgSelfplayConfig()
         c.struct_size = C.sizeof(AzgSelfplayConfig)
         c.max_episode_length = int(max_episode_length)
@@ -480,24 +484,13 @@ def _selfplay_methods():
         c.ring_mode = 1 if fifo else 0
         c.temperature = float(temperature)
         c.agent_epsilon = float(agent_epsilon)
-        return c
-
-    def selfplay_begin(self, max_episode_length, deterministic=False, capacity_steps=64, final_selection="max_visit",
-                       temperature=1.0, agent_epsilon=0.0, fifo=False):
-        """Start device-resident self-play: games reset to their fixed-seed initial states (include/azgym.h).
-        final_selection / temperature / agent_epsilon: the agents' final action rule (agents.py:294-301, 524-535);
-        fifo: the ring overwrites its oldest step like ReplayBuffer.store (buffers.py:75-82) instead of refusing when full."""
-        c = _selfplay_config(max_episode_length, deterministic, capacity_steps, final_selection, temperature, agent_epsilon, fifo)
-        self._check(self._f["selfplay_begin_ex"](self._h, C.byref(c)))
+        self._check(self._optional(_symbol)(self._h, C.byref(c)))
         self._sp_cap = int(capacity_steps)
 
-    def population_selfplay_begin(self, max_episode_length, deterministic=False, capacity_steps=64, final_selection="max_visit",
-                                  temperature=1.0, agent_epsilon=0.0, fifo=False):
+    def population_selfplay_begin(self, *args, **kw):
         """selfplay_begin for an engine with any number of nets (azg_population_selfplay_begin): net k plays games k*T .. k*T+T-1,
         and its rows of a step are that block of the step's n_trees rows."""
-        c = _selfplay_config(max_episode_length, deterministic, capacity_steps, final_selection, temperature, agent_epsilon, fifo)
-        self._check(self._optional("population_selfplay_begin")(self._h, C.byref(c)))
-        self._sp_cap = int(capacity_steps)
+        selfplay_begin(self, *args, _symbol="population_selfplay_begin", **kw)
 
     def selfplay_ring(self):
         """(size, insert_index, total) of the replay ring in steps: ReplayBuffer.size / .insert_index (buffers.py:56-82)."""

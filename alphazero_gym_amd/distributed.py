@@ -92,6 +92,6 @@ def broadcast_weights(model: torch.nn.Module, src: int = 0) -> None:
         for p in params:
             n = p.numel()
             # in-place copy INTO the Parameter (not its .data alias): bumps Parameter._version, which is what
-            # BatchedMCTS.sync_weights watches to decide whether the engine needs the new weights
+            # PopulationMCTS.sync_weights (BatchedMCTS, DeviceSelfPlay) watches to decide whether the engine needs the new weights
             p.copy_(flat[off:off + n].view_as(p))
             off += n

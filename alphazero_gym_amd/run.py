@@ -3,10 +3,10 @@
 ``run_continuous_agent`` / ``run_discrete_agent`` mirror run_continuous.py:15-165 / run_discrete.py:16-146: one game, one
 tree, ``act -> buffer.store -> Env.step -> reset_mcts | mcts_forward`` per step, ``agent.train(buffer)`` per episode.
 ``run_population`` is the same loop for K seeds at once: every step searches all K agents' trees in one launch
-(AgentPopulation); training stays each agent's own optimiser step.  ``PopulationSelfPlay`` is ``DeviceSelfPlay`` for K policies
-in one engine: K nets' games, searches and replay rows stay on the GPU.  ``BatchedSelfPlay`` is the scaled-out form the engine is
+(AgentPopulation); training stays each agent's own optimiser step.  ``BatchedSelfPlay`` is the scaled-out form the engine is
 built for: B games per GPU advance in lock step, one search launch per environment step, replay rows gathered across ranks,
-weights broadcast after the optimiser step.
+weights broadcast after the optimiser step.  ``PopulationSelfPlay`` keeps the games, searches and replay rows of K policies on the
+GPU, in one engine; ``DeviceSelfPlay`` is its one-policy form.
 
 Default hyper-parameters are the reference's (config/*.yaml), except that the continuous policy uses
 one squashed-Normal component (num_components: 1) instead of the 2-component GMM.
@@ -24,7 +24,7 @@ from .agent.buffers import DeviceReplay, ReplayBuffer
 from .agent.population import AgentPopulation
 from .envs import VecCartPole, VecMountainCarContinuous, VecPendulum, make_game
 from .helpers import check_space, stable_normalizer
-from .search.mcts import BatchedMCTS
+from .search.mcts import BatchedMCTS, PopulationMCTS
 
 LOSS_TUNED = dict(_target_="alphazero_gym_amd.agent.losses.A0CLossTuned", action_dim=1, alpha_init=1.0, lr=0.001, tau=0.1,
                   policy_coeff=0.1, value_coeff=1.0, reduction="mean", grad_clip=0, device="cpu")
@@ -200,6 +200,15 @@ def run_population(kind: str, seeds: List[int], cfg: Optional[dict] = None, log:
     return returns
 
 
+def _game_engine_kwargs(game: str, policy, c_pw: float = 1.0, kappa: float = 0.5) -> dict:
+    """The engine's env_id, mode and head keywords for ``game`` (make_game's names; ValueError for others) and nets shaped like
+    ``policy``: ``num_actions`` for a discrete game, ``c_pw`` / ``kappa`` / ``action_bound`` for a continuous one."""
+    env_id = make_game(game).azg_env_id
+    if env_id in (_capi.ENV_PENDULUM_V0, _capi.ENV_PENDULUM_V1, _capi.ENV_MOUNTAINCAR_CONT):
+        return dict(env_id=env_id, mode=_capi.MODE_CONTINUOUS, c_pw=c_pw, kappa=kappa, action_bound=float(policy.action_bound))
+    return dict(env_id=env_id, mode=_capi.MODE_DISCRETE, num_actions=policy.num_actions)
+
+
 class BatchedSelfPlay:
     """B games per process in lock step: one search launch per environment step.
     Final action rules are the agents': continuous -> most visited root action (first index on ties),
@@ -209,29 +218,25 @@ class BatchedSelfPlay:
                  c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
                  temperature: float = 1.0, seed: int = 34, rank: int = 0, world: int = 1, device_id: int = 0):
         self.policy = policy
-        self.continuous = game.lower().startswith(("pendulum", "mountaincarcontinuous"))
+        kw = _game_engine_kwargs(game, policy, c_pw, kappa)
+        self.continuous = kw["mode"] == _capi.MODE_CONTINUOUS
         self.n = n_games
         self.max_len = max_episode_length
         self.temperature = temperature
         self.rng = np.random.RandomState(seed + 1000 * rank)
-        base = rank * n_games
-        if self.continuous:
-            if game.lower().startswith("mountaincarcontinuous"):
-                self.env = VecMountainCarContinuous(n_games, seed=seed + rank)
-            else:
-                self.env = VecPendulum(n_games, version=0 if game.endswith("v0") else 1, seed=seed + rank)
-            self.mcts = BatchedMCTS(policy, env_id=self.env.azg_env_id, mode=_capi.MODE_CONTINUOUS, n_trees=n_games, n_rollouts=n_rollouts,
-                                    c_uct=c_uct, gamma=gamma, epsilon=epsilon, c_pw=c_pw, kappa=kappa, V_target_policy=V_target_policy,
-                                    action_bound=float(policy.action_bound), seed=seed, tree_id_base=base, device_id=device_id)
-        else:
-            if not game.lower().startswith("cartpole"):
-                # (this host-stepped loop has vectorised numpy envs for CartPole, Pendulum and MountainCarContinuous only)
-                raise NotImplementedError(f"BatchedSelfPlay steps CartPole, Pendulum and MountainCarContinuous on the host; {game} plays "
-                                          "its own dynamics on the device: use DeviceSelfPlay")
+        env_id = kw["env_id"]
+        if env_id == _capi.ENV_CARTPOLE:
             self.env = VecCartPole(n_games, seed=seed + rank)
-            self.mcts = BatchedMCTS(policy, env_id=_capi.ENV_CARTPOLE, mode=_capi.MODE_DISCRETE, n_trees=n_games, n_rollouts=n_rollouts,
-                                    c_uct=c_uct, gamma=gamma, epsilon=epsilon, num_actions=policy.num_actions,
-                                    V_target_policy=V_target_policy, seed=seed, tree_id_base=base, device_id=device_id)
+        elif env_id == _capi.ENV_MOUNTAINCAR_CONT:
+            self.env = VecMountainCarContinuous(n_games, seed=seed + rank)
+        elif env_id in (_capi.ENV_PENDULUM_V0, _capi.ENV_PENDULUM_V1):
+            self.env = VecPendulum(n_games, version=0 if env_id == _capi.ENV_PENDULUM_V0 else 1, seed=seed + rank)
+        else:
+            # (this host-stepped loop has vectorised numpy envs for CartPole, Pendulum and MountainCarContinuous only)
+            raise NotImplementedError(f"BatchedSelfPlay steps CartPole, Pendulum and MountainCarContinuous on the host; {game} plays "
+                                      "its own dynamics on the device: use DeviceSelfPlay")
+        self.mcts = BatchedMCTS(policy, n_trees=n_games, n_rollouts=n_rollouts, c_uct=c_uct, gamma=gamma, epsilon=epsilon,
+                                V_target_policy=V_target_policy, seed=seed, tree_id_base=rank * n_games, device_id=device_id, **kw)
         self.t = np.zeros(n_games, np.int64)
         self.ep_return = np.zeros(n_games)
         self.finished_returns: List[float] = []
@@ -265,141 +270,48 @@ class BatchedSelfPlay:
         return torch.cat(rows, 0)
 
 
-class DeviceSelfPlay:
-    """The same loop with everything but the optimiser on the GPU (azg_selfplay_* in include/azgym.h): games, final action
-    rule, env step, episode resets and the replay ring live on the device; the host only downloads rows to train on.
-    The agents' final action rules run on the device too: ``final_selection`` "max_visit" / "max_value", discrete
-    ``temperature`` and ``deterministic``, continuous ``agent_epsilon`` (agents.py:294-301, 524-535; include/azgym.h).
-    ``fifo=True`` turns the replay ring into the reference's overwrite-the-oldest buffer (buffers.py:75-82)."""
-
-    def __init__(self, policy, *, game: str, n_games: int, n_rollouts: int, c_uct: float, gamma: float = 1.0, epsilon: float = 0.0,
-                 c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
-                 deterministic: bool = False, capacity_steps: int = 64, seed: int = 34, rank: int = 0, device_id: int = 0,
-                 final_selection: str = "max_visit", temperature: float = 1.0, agent_epsilon: float = 0.0, fifo: bool = False):
-        self.continuous = game.lower().startswith(("pendulum", "mountaincarcontinuous"))
-        if self.continuous:
-            if game.lower().startswith("mountaincarcontinuous"):
-                env_id = _capi.ENV_MOUNTAINCAR_CONT
-            else:
-                env_id = _capi.ENV_PENDULUM_V0 if game.endswith("v0") else _capi.ENV_PENDULUM_V1
-            self.mcts = BatchedMCTS(policy, env_id=env_id, mode=_capi.MODE_CONTINUOUS, n_trees=n_games, n_rollouts=n_rollouts, c_uct=c_uct,
-                                    gamma=gamma, epsilon=epsilon, c_pw=c_pw, kappa=kappa, V_target_policy=V_target_policy,
-                                    action_bound=float(policy.action_bound), seed=seed, tree_id_base=rank * n_games, device_id=device_id)
-        else:
-            g = game.lower()
-            env_id = _capi.ENV_MOUNTAINCAR if g.startswith("mountaincar") else (_capi.ENV_ACROBOT if g.startswith("acrobot") else _capi.ENV_CARTPOLE)
-            self.mcts = BatchedMCTS(policy, env_id=env_id, mode=_capi.MODE_DISCRETE, n_trees=n_games, n_rollouts=n_rollouts,
-                                    c_uct=c_uct, gamma=gamma, epsilon=epsilon, num_actions=policy.num_actions,
-                                    V_target_policy=V_target_policy, seed=seed, tree_id_base=rank * n_games, device_id=device_id)
-        self.engine = self.mcts.engine
-        self.capacity = capacity_steps
-        self.fifo = fifo
-        self.engine.selfplay_begin(max_episode_length, deterministic, capacity_steps, final_selection=final_selection,
-                                   temperature=temperature, agent_epsilon=agent_epsilon, fifo=fifo)
-
-    def play(self, n_steps: int) -> None:
-        """n_steps self-play steps of every game (asynchronous: launches only); rows accumulate in the device ring."""
-        assert self.fifo or n_steps <= self.capacity
-        self.mcts.sync_weights()
-        for _ in range(n_steps):
-            self.engine.selfplay_step()
-
-    def collect(self, n_steps: int) -> torch.Tensor:
-        """Play n_steps (<= capacity) and return this rank's replay rows as a host float32 tensor [n_steps * B, row]."""
-        assert n_steps <= self.capacity
-        self.play(n_steps)
-        return torch.from_numpy(self.engine.selfplay_rows(clear=True).copy())
-
-    def replay(self, batch_size: int, device=None) -> DeviceReplay:
-        """The device ring as a replay buffer with the reference's sampling rules; minibatches are device tensors."""
-        return DeviceReplay(self.engine, batch_size, device=device)
-
-    def collect_device(self, n_steps: int, replay: DeviceReplay) -> torch.Tensor:
-        """Play n_steps and return this rank's NEW rows as a device tensor [n_steps * B, row] (a copy in HBM; the ring is
-        cleared unless it runs in FIFO mode, where it keeps accumulating)."""
-        if not self.fifo:
-            assert n_steps <= self.capacity
-            self.play(n_steps)
-            rows = replay.rows().clone()
-            self.engine.selfplay_clear()
-            return rows
-        assert n_steps <= self.capacity, "the ring keeps its newest capacity_steps steps: older ones would already be overwritten"
-        before = self.engine.selfplay_ring()
-        self.play(n_steps)
-        size, insert, _ = self.engine.selfplay_ring()
-        B = self.engine.n_trees
-        ring = replay.rows().reshape(size, B, -1)
-        # the n_steps newest slots, oldest first: while filling they are the tail; once full they end just before insert_index
-        if before[0] + n_steps <= self.capacity:
-            new = ring[before[0]:before[0] + n_steps]
-        else:
-            idx = [(insert - n_steps + i) % size for i in range(n_steps)]
-            new = ring[torch.as_tensor(idx, device=ring.device)]
-        return new.reshape(n_steps * B, -1).clone()
-
-    def mean_finished_return(self) -> float:
-        fsum, fcnt, _ = self.engine.selfplay_stats()
-        return float(fsum.sum() / max(int(fcnt.sum()), 1))
-
-
 class PopulationSelfPlay:
-    """Device self-play for K policies in ONE engine (azg_population_selfplay_begin): ``policies[k]`` plays games k*T .. k*T+T-1
-    (T = ``games_per_net``) with global ids ``tree_id_base + k*T + j``, the games ``DeviceSelfPlay(policies[k], n_games=T, rank=k)``
-    plays, bit for bit, with one search launch and one self-play launch per step for the whole population.  The keywords are
-    ``DeviceSelfPlay``'s and shared by every net (game, search and self-play settings).  Weights are re-uploaded only when some
-    policy changed: with every parameter on the engine's GPU in one gather launch for all nets, otherwise one host upload per
-    changed net (``last_weight_sync``: "device", "host" or None when nothing changed)."""
+    """Self-play with everything but the optimiser on the GPU (azg_selfplay_* in include/azgym.h), for K policies in ONE engine:
+    games, final action rule, env step, episode resets and the replay ring live on the device; the host only downloads rows to
+    train on.  ``policies[k]`` plays games k*T .. k*T+T-1 (T = ``games_per_net``) with global ids ``tree_id_base + k*T + j``, the
+    games ``DeviceSelfPlay(policies[k], n_games=T, rank=k)`` plays, bit for bit, with one search launch and one self-play launch
+    per step for the whole population.  The game, search and self-play settings are shared by every net.  The agents' final
+    action rules run on the device too: ``final_selection`` "max_visit" / "max_value", discrete ``temperature`` and
+    ``deterministic``, continuous ``agent_epsilon`` (agents.py:294-301, 524-535; include/azgym.h).  ``fifo=True`` turns the
+    replay ring into the reference's overwrite-the-oldest buffer (buffers.py:75-82).  Weights are re-uploaded only when some
+    policy changed (``PopulationMCTS.sync_weights``; ``last_weight_sync``: "device", "host" or None when nothing changed)."""
 
     def __init__(self, policies, *, game: str, games_per_net: int, n_rollouts: int, c_uct: float, gamma: float = 1.0, epsilon: float = 0.0,
                  c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
                  deterministic: bool = False, capacity_steps: int = 64, seed: int = 34, tree_id_base: int = 0, device_id: int = 0,
                  final_selection: str = "max_visit", temperature: float = 1.0, agent_epsilon: float = 0.0, fifo: bool = False):
-        from . import _native   # raises if libazgym_hip.so is missing
-        from .search.mcts import _weights_version
-
-        self.policies = list(policies)
-        if not self.policies or games_per_net < 1:
-            raise ValueError("PopulationSelfPlay needs at least one policy and games_per_net >= 1")
-        self.n_nets, self.games_per_net = len(self.policies), int(games_per_net)
-        self.n_games = self.n_nets * self.games_per_net
-        p0 = self.policies[0]
-        g = game.lower()
-        self.continuous = g.startswith(("pendulum", "mountaincarcontinuous"))
-        if self.continuous:
-            env_id = (_capi.ENV_MOUNTAINCAR_CONT if g.startswith("mountaincarcontinuous")
-                      else (_capi.ENV_PENDULUM_V0 if game.endswith("v0") else _capi.ENV_PENDULUM_V1))
-            kw = dict(env_id=env_id, mode=_capi.MODE_CONTINUOUS, c_pw=c_pw, kappa=kappa, action_bound=float(p0.action_bound))
-        else:
-            env_id = _capi.ENV_MOUNTAINCAR if g.startswith("mountaincar") else (_capi.ENV_ACROBOT if g.startswith("acrobot") else _capi.ENV_CARTPOLE)
-            kw = dict(env_id=env_id, mode=_capi.MODE_DISCRETE, num_actions=p0.num_actions)
-        self.engine = _native.HipEngine(n_trees=self.n_games, n_sims=n_rollouts, c_uct=c_uct, gamma=gamma, epsilon=epsilon,
-                                        v_target=V_target_policy, seed=seed, tree_id_base=tree_id_base, device_id=device_id, **kw)
-        self.engine.set_population(self.n_nets)
-        self._version_of = _weights_version
-        self._versions: List = [None] * self.n_nets
-        self.last_weight_sync = None
-        self.sync_weights()
+        policies = list(policies)
+        if not policies or games_per_net < 1:
+            raise ValueError(f"{type(self).__name__} needs at least one policy and games_per_net >= 1")
+        kw = _game_engine_kwargs(game, policies[0], c_pw, kappa)
+        self.continuous = kw["mode"] == _capi.MODE_CONTINUOUS
+        self.mcts = self._search(policies, games_per_net, n_rollouts=n_rollouts, c_uct=c_uct, gamma=gamma, epsilon=epsilon,
+                                 V_target_policy=V_target_policy, seed=seed, tree_id_base=tree_id_base, device_id=device_id, **kw)
+        self.engine, self.policies = self.mcts.engine, self.mcts.models
+        self.n_nets, self.games_per_net, self.n_games = self.mcts.n_models, self.mcts.trees_per_model, self.mcts.n_trees
         self.capacity = capacity_steps
         self.fifo = fifo
         self._replay = None
-        self.engine.population_selfplay_begin(max_episode_length, deterministic, capacity_steps, final_selection=final_selection,
-                                              temperature=temperature, agent_epsilon=agent_epsilon, fifo=fifo)
+        # (one net: the plain engine's entry point, which the tests' CPU oracle also has)
+        begin = self.engine.selfplay_begin if self.n_nets == 1 else self.engine.population_selfplay_begin
+        begin(max_episode_length, deterministic, capacity_steps, final_selection=final_selection, temperature=temperature,
+              agent_epsilon=agent_epsilon, fifo=fifo)
+
+    @staticmethod
+    def _search(policies, games_per_net: int, **kw) -> PopulationMCTS:
+        return PopulationMCTS(policies, trees_per_model=games_per_net, **kw)
+
+    @property
+    def last_weight_sync(self) -> Optional[str]:
+        return self.mcts.last_weight_sync
 
     def sync_weights(self, force: bool = False) -> None:
-        """Upload the nets whose policy changed since its last upload (all of them in one launch when they live on the GPU)."""
-        versions = [self._version_of(p) for p in self.policies]
-        changed = [k for k in range(self.n_nets) if force or versions[k] != self._versions[k]]
-        self.last_weight_sync = None
-        if not changed:
-            return
-        dev = self.engine.cfg.device_id
-        if all(p.is_cuda and p.device.index == dev for pol in self.policies for p in pol.parameters()):
-            self.last_weight_sync = self.engine.set_population_policies(self.policies)
-        else:
-            for k in changed:
-                self.engine.set_net_policy(k, self.policies[k])
-            self.last_weight_sync = "host"
-        self._versions = versions
+        self.mcts.sync_weights(force)
 
     def play(self, n_steps: int) -> None:
         """n_steps self-play steps of every game of every net (asynchronous: launches only); rows accumulate in the device ring."""
@@ -409,41 +321,44 @@ class PopulationSelfPlay:
             self.engine.selfplay_step()
 
     def _split(self, rows, n_steps: int) -> List[torch.Tensor]:
-        """[n_steps * n_games, row] in step-major order -> net k's [n_steps * T, row] (the order of its DeviceSelfPlay)."""
-        blocks = rows.reshape(n_steps, self.n_nets, self.games_per_net, -1)
-        return [blocks[:, k].reshape(n_steps * self.games_per_net, -1) for k in range(self.n_nets)]
+        """[n_steps * n_games, row] in step-major order -> copies of net k's [n_steps * T, row] (the order of its DeviceSelfPlay)."""
+        blocks = rows.reshape(n_steps, self.n_nets, self.games_per_net, rows.shape[-1])
+        return [blocks[:, k].reshape(n_steps * self.games_per_net, -1).clone() for k in range(self.n_nets)]
 
     def collect(self, n_steps: int) -> List[torch.Tensor]:
         """Play n_steps (<= capacity) and return every net's replay rows since the last clear as host float32 tensors
         [steps * T, row] (net k's games in DeviceSelfPlay.collect's order); the ring is cleared."""
         assert n_steps <= self.capacity
         self.play(n_steps)
-        rows = torch.from_numpy(self.engine.selfplay_rows(clear=True).copy())
-        return [r.clone() for r in self._split(rows, rows.shape[0] // self.n_games)]
+        rows = torch.from_numpy(self.engine.selfplay_rows(clear=True))
+        return self._split(rows, rows.shape[0] // self.n_games)
 
-    def collect_device(self, n_steps: int) -> List[torch.Tensor]:
-        """Play n_steps and return every net's NEW rows as device tensors [n_steps * T, row] (copies in HBM), as
-        DeviceSelfPlay.collect_device returns them per net: the ring is cleared, unless it runs in FIFO mode."""
-        if self._replay is None:
-            self._replay = DeviceReplay(self.engine, 1)
+    def collect_device(self, n_steps: int, replay: Optional[DeviceReplay] = None) -> List[torch.Tensor]:
+        """Play n_steps and return every net's NEW rows as device tensors [n_steps * T, row] (copies in HBM, read through
+        ``replay``, default: a view of this engine's ring): the ring is cleared, unless it runs in FIFO mode, where it keeps
+        accumulating."""
         assert n_steps <= self.capacity, "the ring keeps its newest capacity_steps steps: older ones would already be overwritten"
+        if replay is None:
+            if self._replay is None:
+                self._replay = DeviceReplay(self.engine, 1)
+            replay = self._replay
         if not self.fifo:
             self.play(n_steps)
-            rows = self._replay.rows()
-            out = [r.clone() for r in self._split(rows, rows.shape[0] // self.n_games)]
+            rows = replay.rows()
+            out = self._split(rows, rows.shape[0] // self.n_games)
             self.engine.selfplay_clear()
             return out
         before = self.engine.selfplay_ring()
         self.play(n_steps)
         size, insert, _ = self.engine.selfplay_ring()
-        ring = self._replay.rows().reshape(size, self.n_games, -1)
+        ring = replay.rows().reshape(size, self.n_games, -1)
         # the n_steps newest slots, oldest first: while filling they are the tail; once full they end just before insert_index
         if before[0] + n_steps <= self.capacity:
             new = ring[before[0]:before[0] + n_steps]
         else:
             idx = [(insert - n_steps + i) % size for i in range(n_steps)]
             new = ring[torch.as_tensor(idx, device=ring.device)]
-        return [r.clone() for r in self._split(new, n_steps)]
+        return self._split(new, n_steps)
 
     def finished_returns(self):
         """(fsum [K] float64, fcnt [K] int64): the returns and the number of the episodes each net's games finished so far, summed
@@ -459,6 +374,33 @@ class PopulationSelfPlay:
 
     def close(self) -> None:
         self.engine.close()
+
+
+class DeviceSelfPlay(PopulationSelfPlay):
+    """``PopulationSelfPlay`` of one policy: B games (``n_games``) with global ids ``rank * B + j``; rows come back as one tensor."""
+
+    def __init__(self, policy, *, n_games: int, rank: int = 0, **kwargs):
+        super().__init__([policy], games_per_net=n_games, tree_id_base=rank * n_games, **kwargs)
+
+    @staticmethod
+    def _search(policies, games_per_net: int, **kw) -> BatchedMCTS:
+        return BatchedMCTS(policies[0], n_trees=games_per_net, **kw)   # (.mcts stays the single-net search: .model, ._version)
+
+    def collect(self, n_steps: int) -> torch.Tensor:
+        """Play n_steps (<= capacity) and return this rank's replay rows as a host float32 tensor [n_steps * B, row]."""
+        return super().collect(n_steps)[0]
+
+    def replay(self, batch_size: int, device=None) -> DeviceReplay:
+        """The device ring as a replay buffer with the reference's sampling rules; minibatches are device tensors."""
+        return DeviceReplay(self.engine, batch_size, device=device)
+
+    def collect_device(self, n_steps: int, replay: DeviceReplay) -> torch.Tensor:
+        """Play n_steps and return this rank's NEW rows as a device tensor [n_steps * B, row] (see PopulationSelfPlay.collect_device)."""
+        return super().collect_device(n_steps, replay)[0]
+
+    def mean_finished_return(self) -> float:
+        fsum, fcnt, _ = self.engine.selfplay_stats()
+        return float(fsum.sum() / max(int(fcnt.sum()), 1))
 
 
 def train_on_rows(agent, rows: torch.Tensor, state_dim: int, K: int, batch_size: int = 32, shuffle_seed: int = 0) -> Dict[str, float]:

@@ -76,64 +76,12 @@ def device_ordinal(device) -> int:
     return int(os.environ.get("LOCAL_RANK", "0"))
 
 
-class BatchedMCTS:
-    """B independent trees searched in one launch.  kwargs = the reference's MCTS kwargs + batch geometry."""
-
-    def __init__(self, model, *, env_id: int, mode: int, n_trees: int, n_rollouts: int, c_uct: float, gamma: float,
-                 epsilon: float = 0.0, num_actions: int = 0, c_pw: float = 1.0, kappa: float = 0.5,
-                 V_target_policy: str = "off_policy", action_bound: float = 2.0, seed: int = 34, tree_id_base: int = 0,
-                 device_id: int = 0):
-        from .. import _native   # raises if libazgym_hip.so is missing
-
-        self.model = model
-        self.engine = _native.HipEngine(env_id=env_id, mode=mode, n_trees=n_trees, n_sims=n_rollouts, c_uct=c_uct, gamma=gamma,
-                                        epsilon=epsilon, num_actions=num_actions, c_pw=c_pw, kappa=kappa, v_target=V_target_policy,
-                                        action_bound=action_bound, seed=seed, tree_id_base=tree_id_base, device_id=device_id)
-        self._version = None
-        self._cliff_warned = False
-        self.sync_weights()
-
-    def sync_weights(self, force: bool = False) -> None:
-        """Push the model's weights to the engine when they changed (after every optimiser step)."""
-        v = _weights_version(self.model)
-        if force or v != self._version:
-            self.engine.set_policy(self.model)
-            self._version = v
-
-    def search(self, root_states: np.ndarray, root_n_carry: Optional[np.ndarray] = None) -> None:
-        self.sync_weights()
-        self.engine.search(root_states, root_n_carry)
-        if not self._cliff_warned and hasattr(self.engine, "search_info"):   # (the tests' CPU double of the engine has no kernel forms)
-            info = self.engine.search_info()
-            if info["kernel_form"] == "persistent" and info["tree_storage"] == "global" and info["lds_exit"] != "forced":
-                self._cliff_warned = True
-                warnings.warn(f"the trees of this search do not fit LDS residency ({info['lds_exit']}: {info['max_records']} records per tree, up to "
-                              f"{info['max_children']} children per node): they are kept in global memory -- same results, slower tree walk "
-                              "(BatchedMCTS.last_search_info)", RuntimeWarning, stacklevel=2)
-
-    @property
-    def last_search_info(self) -> dict:
-        """What the last search ran as (azg_search_info): ``kernel_form`` "persistent" / "per_layer" / "team", ``tree_storage`` "lds8" /
-        "lds9" / "global" with ``lds_exit`` saying which residency limit pushed the trees out of LDS, ``spec``, the workgroup shape,
-        ``team_fallbacks``, ``last_ms`` and the kernel's name."""
-        return self.engine.search_info()
-
-    def results(self):
-        return self.engine.results()
-
-    def root_children(self):
-        return self.engine.root_children()
-
-    def close(self):
-        self.engine.close()
-
-
 class PopulationMCTS:
     """K models (same network shape, own weights) searched in ONE launch: trees k*T .. k*T+T-1 (T = ``trees_per_model``) use
     ``models[k]``, with the RNG streams of global trees ``tree_id_base + k*T + j`` -- what K ``BatchedMCTS`` engines with
-    ``tree_id_base + k*T`` compute, one launch and one synchronisation instead of K (azg_set_population).  The search settings
-    (kwargs as in ``BatchedMCTS``) and the search index are shared.  Each model's weights are re-uploaded only when they changed
-    (models train at different times)."""
+    ``tree_id_base + k*T`` compute, one launch and one synchronisation instead of K (azg_set_population).  kwargs = the reference's
+    MCTS kwargs + batch geometry; the search settings and the search index are shared.  Each model's weights are re-uploaded only
+    when they changed (models train at different times).  One model is the plain single-net engine."""
 
     def __init__(self, models: Sequence[Any], *, trees_per_model: int = 1, env_id: int, mode: int, n_rollouts: int, c_uct: float,
                  gamma: float, epsilon: float = 0.0, num_actions: int = 0, c_pw: float = 1.0, kappa: float = 0.5,
@@ -150,32 +98,53 @@ class PopulationMCTS:
         self.engine = _native.HipEngine(env_id=env_id, mode=mode, n_trees=self.n_trees, n_sims=n_rollouts, c_uct=c_uct, gamma=gamma,
                                         epsilon=epsilon, num_actions=num_actions, c_pw=c_pw, kappa=kappa, v_target=V_target_policy,
                                         action_bound=action_bound, seed=seed, tree_id_base=tree_id_base, device_id=device_id)
-        self.engine.set_population(self.n_models)
+        if self.n_models > 1:   # (one model: the plain engine, which the tests' CPU oracle -- no population entry points -- also is)
+            self.engine.set_population(self.n_models)
         self._versions: List[Any] = [None] * self.n_models
+        self._cliff_warned = False
+        self.last_weight_sync: Optional[str] = None
         self.sync_weights()
 
     def sync_weights(self, force: bool = False) -> None:
-        """Upload the weights of every model that changed since its last upload (net k = models[k])."""
-        for k, m in enumerate(self.models):
-            v = _weights_version(m)
-            if force or v != self._versions[k]:
-                self.engine.set_net_policy(k, m)
-                self._versions[k] = v
+        """Upload the weights of every model that changed since its last upload (net k = models[k]; after every optimiser step).
+        ``last_weight_sync`` says how: "device" when every parameter lives on the engine's GPU (flattened there; K > 1: one gather
+        launch for all nets), "host" (K > 1: one host upload per changed net), None when nothing changed."""
+        versions = [_weights_version(m) for m in self.models]
+        changed = [k for k in range(self.n_models) if force or versions[k] != self._versions[k]]
+        self.last_weight_sync = None
+        if not changed:
+            return
+        if self.n_models == 1:
+            self.last_weight_sync = self.engine.set_policy(self.models[0])
+        elif all(p.is_cuda and p.device.index == self.engine.cfg.device_id for m in self.models for p in m.parameters()):
+            self.last_weight_sync = self.engine.set_population_policies(self.models)
+        else:
+            for k in changed:
+                self.engine.set_net_policy(k, self.models[k])
+            self.last_weight_sync = "host"
+        self._versions = versions
 
     def search(self, root_states: np.ndarray, root_n_carry: Optional[np.ndarray] = None) -> None:
-        """root_states [n_models * trees_per_model, S] (or [n_models, trees_per_model, S]); tree k*T + j belongs to models[k]."""
+        """root_states [n_trees, S] (or [n_models, trees_per_model, S]); tree k*T + j belongs to models[k]."""
         self.sync_weights()
-        roots = np.asarray(root_states, dtype=np.float64).reshape(self.n_trees, -1)
-        carry = None if root_n_carry is None else np.asarray(root_n_carry, dtype=np.int32).reshape(self.n_trees)
-        self.engine.search(roots, carry)
+        self.engine.search(root_states, root_n_carry)
+        if not self._cliff_warned and hasattr(self.engine, "search_info"):   # (the tests' CPU double of the engine has no kernel forms)
+            info = self.engine.search_info()
+            if info["kernel_form"] == "persistent" and info["tree_storage"] == "global" and info["lds_exit"] != "forced":
+                self._cliff_warned = True
+                warnings.warn(f"the trees of this search do not fit LDS residency ({info['lds_exit']}: {info['max_records']} records per tree, up to "
+                              f"{info['max_children']} children per node): they are kept in global memory -- same results, slower tree walk "
+                              "(last_search_info)", RuntimeWarning, stacklevel=2)
 
     @property
     def last_search_info(self) -> dict:
-        """azg_search_info of the last search (see BatchedMCTS.last_search_info)."""
+        """What the last search ran as (azg_search_info): ``kernel_form`` "persistent" / "per_layer" / "team", ``tree_storage`` "lds8" /
+        "lds9" / "global" with ``lds_exit`` saying which residency limit pushed the trees out of LDS, ``spec``, the workgroup shape,
+        ``team_fallbacks``, ``last_ms`` and the kernel's name."""
         return self.engine.search_info()
 
     def results(self):
-        """return_results of every tree, rows in tree order k*T + j (the shapes of BatchedMCTS.results)."""
+        """return_results of every tree, rows in tree order k*T + j."""
         return self.engine.results()
 
     def root_children(self):
@@ -183,6 +152,22 @@ class PopulationMCTS:
 
     def close(self):
         self.engine.close()
+
+
+class BatchedMCTS(PopulationMCTS):
+    """B independent trees of one model searched in one launch: a population of one (``PopulationMCTS`` kwargs)."""
+
+    def __init__(self, model, *, n_trees: int, **kwargs):
+        super().__init__([model], trees_per_model=n_trees, **kwargs)
+
+    @property
+    def model(self):
+        return self.models[0]
+
+    @property
+    def _version(self):
+        """The model's weights version (_weights_version) at its last upload."""
+        return self._versions[0]
 
 
 class _Root:

@@ -292,10 +292,10 @@ FACADE = {
 SEEDS = [34, 35, 36]
 
 
-def _agents(kind):
+def _agents(kind, device="cpu"):
     from alphazero_gym_amd import run
     from alphazero_gym_amd.envs import make_game
-    cfg = run._merge(run.CONTINUOUS_DEFAULTS if kind == "continuous" else run.DISCRETE_DEFAULTS, FACADE[kind])
+    cfg = run._merge(run.CONTINUOUS_DEFAULTS if kind == "continuous" else run.DISCRETE_DEFAULTS, dict(FACADE[kind], device=device))
     torch.manual_seed(7)
     return [run.make_agent(kind, cfg, make_game(cfg["game"]), tree_id_base=k) for k in range(len(SEEDS))], cfg
 
@@ -401,6 +401,58 @@ def test_agent_population_equals_standalone_agents(kind, backend, monkeypatch):
             assert torch.equal(p, q), f"agent {k}: {n} after training"
     # the agents did train, and not all alike
     assert not torch.equal(next(pop_agents[0].nn.parameters()), next(pop_agents[1].nn.parameters()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["continuous", "discrete"])
+def test_agent_population_with_nets_on_the_gpu_gathers_them_in_one_upload(kind):
+    """Agents whose nets live on cuda:0: the population uploads every net with one gather ("device"), again after one net changed,
+    and each agent acts bit for bit as it does standalone."""
+    from alphazero_gym_amd.agent.population import AgentPopulation
+    from alphazero_gym_amd.envs import make_game
+    from alphazero_gym_amd.search.mcts import env_signature
+    _hip()
+    pop_agents, cfg = _agents(kind, "cuda:0")
+    ref_agents, _ = _agents(kind, "cuda:0")
+    assert next(pop_agents[0].nn.parameters()).is_cuda
+    K = len(SEEDS)
+    pop_envs, ref_envs = [make_game(cfg["game"]) for _ in range(K)], [make_game(cfg["game"]) for _ in range(K)]
+    for k in range(K):
+        for env, agent in ((pop_envs[k], pop_agents[k]), (ref_envs[k], ref_agents[k])):
+            env.seed(SEEDS[k])
+            agent.reset_mcts(root_state=env.reset())
+    streams = [(np.random.RandomState(s).get_state(), random.Random(s).getstate()) for s in SEEDS]
+    pop = AgentPopulation(pop_agents, seeds=SEEDS)
+    syncs = []
+    for t in range(4):   # (4 steps: no CartPole game ends)
+        if t == 2:       # an optimiser step of agent 1
+            with torch.no_grad():
+                for agent in (pop_agents[1], ref_agents[1]):
+                    for p in agent.nn.parameters():
+                        p.mul_(0.5)
+        outs = pop.act(pop_envs, deterministic=False)
+        syncs.append(pop.mcts.last_weight_sync)
+        for k, agent in enumerate(ref_agents):
+            outer = (np.random.get_state(), random.getstate())
+            np.random.set_state(streams[k][0])
+            random.setstate(streams[k][1])
+            agent.mcts._ensure_engine(env_signature(ref_envs[k])[0], 1).engine.set_search_index(t)
+            want = agent.act(ref_envs[k], deterministic=False) if kind == "discrete" else agent.act(ref_envs[k])
+            streams[k] = (np.random.get_state(), random.getstate())
+            np.random.set_state(outer[0])
+            random.setstate(outer[1])
+            _same(outs[k], want)
+            for env, a in ((pop_envs[k], pop_agents[k]), (ref_envs[k], agent)):
+                state, _, terminal, _ = env.step(want[0])
+                assert not terminal
+                if kind == "continuous":
+                    a.reset_mcts(root_state=state)
+                else:
+                    a.mcts_forward(want[0], state)
+    assert syncs == [None, None, "device", None]   # (the first upload happens when the first act builds the engine)
+    pop.mcts.sync_weights(force=True)
+    assert pop.mcts.last_weight_sync == "device"
+    pop.close()
 
 
 def test_agent_population_rejects_mixed_settings():

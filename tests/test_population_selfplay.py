@@ -472,6 +472,65 @@ def test_population_selfplay_splits_like_single_net_selfplay(fifo, monkeypatch):
     pop.close()
 
 
+class RecordingOracle(O.OracleEngine):
+    """The oracle engine, recording which weight-upload and self-play entry points are called."""
+
+    calls = []
+
+    def __getattribute__(self, name):
+        if name in ("set_policy", "set_net_policy", "set_population", "set_population_policies", "selfplay_begin",
+                    "population_selfplay_begin"):
+            RecordingOracle.calls.append(name)
+        return super().__getattribute__(name)
+
+
+@pytest.mark.parametrize("fifo", [False, True])
+def test_population_selfplay_of_one_policy_is_device_selfplay(fifo, monkeypatch):
+    """A population of one plays on the plain engine (selfplay_begin, set_policy: the CPU oracle has no population entry points), and
+    yields DeviceSelfPlay's rows and stats."""
+    from alphazero_gym_amd import _native, run
+    (net,), T = _cpu_nets(1), 3
+    kw = dict(game="CartPole-v0", n_rollouts=5, c_uct=1.5, epsilon=0.1, max_episode_length=4, capacity_steps=3, fifo=fifo, seed=9)
+    monkeypatch.setattr(_native, "HipEngine", O.OracleEngine)
+    single = run.DeviceSelfPlay(net, n_games=T, rank=2, **kw)
+    assert single.mcts.model is net   # (DeviceSelfPlay.mcts is still the single-net BatchedMCTS)
+    monkeypatch.setattr(_native, "HipEngine", RecordingOracle)
+    RecordingOracle.calls = []
+    pop = run.PopulationSelfPlay([net], games_per_net=T, tree_id_base=2 * T, **kw)
+    assert RecordingOracle.calls == ["set_policy", "selfplay_begin"] and pop.last_weight_sync == "host"
+    for n, extra in ([(2, 0), (3, 0), (1, 4)] if fifo else [(2, 0), (3, 0), (1, 0)]):
+        for sp in (single, pop):
+            sp.play(extra)
+        (got,), want = pop.collect(n), single.collect(n)
+        assert got.shape == want.shape and torch.equal(got, want)
+        fsum, fcnt = pop.finished_returns()
+        f, c, _ = single.engine.selfplay_stats()
+        acc = 0.0
+        for x in f:
+            acc += x
+        assert fsum[0] == acc and fcnt[0] == c.sum()
+    assert fcnt[0] > 0
+    with torch.no_grad():
+        next(net.parameters()).add_(0.1)
+    RecordingOracle.calls = []
+    pop.play(1)
+    assert RecordingOracle.calls == ["set_policy"] and pop.last_weight_sync == "host"
+    single.close()
+    pop.close()
+
+
+def test_selfplay_rejects_an_unknown_game(monkeypatch):
+    """The game names are make_game's: an unknown one raises instead of playing CartPole."""
+    from alphazero_gym_amd import _native, run
+    monkeypatch.setattr(_native, "HipEngine", O.OracleEngine)
+    kw = dict(game="Breakout-v0", n_rollouts=5, c_uct=1.5, capacity_steps=2)
+    with pytest.raises(ValueError):
+        run.DeviceSelfPlay(_cpu_nets(1)[0], n_games=2, **kw)
+    monkeypatch.setattr(_native, "HipEngine", OracleSelfPlayPopulation)
+    with pytest.raises(ValueError):
+        run.PopulationSelfPlay(_cpu_nets(2), games_per_net=2, **kw)
+
+
 def test_population_selfplay_argument_errors(monkeypatch):
     from alphazero_gym_amd import _native, run
     monkeypatch.setattr(_native, "HipEngine", OracleSelfPlayPopulation)
