@@ -2,23 +2,30 @@
 """Headline benchmark: MCTS simulations / second, Pendulum-v1, 4096 trees per GPU, n_sims=200, 2x256 ELU MLP
 (BASELINE.json `metric`).
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints
+the JSON line (`metric`, `value`, `ms_per_step`, ...; N > 1 adds `extra.collectives`, the host-side timings of the timed steps'
+collectives).  Everything else below -- rooflines, kernel-time passes, profiler child passes, other configurations, the CPU
+baseline -- runs only with --full, after the timed region, and goes into the same line.
 
 N = 1  (config C): a "step" is one whole search (4096 trees x 200 simulations = ONE launch of the fused search kernel) over
        synthetic fixed-seed root states already resident in HBM, return_results of every tree included (written into device
-       buffers by the search kernel's epilogue; azg_results_resident hands them out, no copy).  The JSON line also carries `roofline`
-       (fp32 MFMA; `traffic` = HBM bytes per launch from two rocprofv3 --pmc child passes of this run), `roofline_hbm` (the tree walk's
-       algorithmic bytes, counted from the searched trees, against the HBM peak), `cpu_baseline`, and `extra`: configs B and E and C at
-       8192 trees timed the same way (B with its HBM-side block, E with its hardware MFMA-busy share), `mfma_busy` (the hardware's view
-       of roofline.frac), `config_d_1rank` (the N > 1 workload on this one GPU, no collectives) and the PCIe-inclusive rate of config C.
+       buffers by the search kernel's epilogue; azg_results_resident hands them out, no copy).  With --full the JSON line also
+       carries `roofline` (fp32 MFMA; `traffic` = HBM bytes per launch from two rocprofv3 --pmc child passes of this run),
+       `roofline_hbm` (the tree walk's algorithmic bytes, counted from the searched trees, against the HBM peak), `cpu_baseline`,
+       and `extra`: configs B and E and C at 8192 trees timed the same way (B with its HBM-side block, E with its hardware
+       MFMA-busy share), `mfma_busy` (the hardware's view of roofline.frac), `config_d_1rank` (the N > 1 workload on this one GPU,
+       no collectives) and the PCIe-inclusive rate of config C.
        `--config-d` runs the N > 1 loop (below) with one rank: the collectives then go through RCCL with world size 1.
 N > 1  (config D): one process per GPU (spawned here when the script was not started by torch.distributed.run), 4096 self-play
        games per GPU keyed by global game id.  A step is one device-resident self-play step (search + final action + env step +
        replay row) PLUS the all-gather of the step's replay rows over RCCL (HBM to HBM, overlapped with the next step's search)
        and a weight broadcast + engine re-sync (device to device: azg_set_weights_device) every --bcast-every steps: the loop
        shape of run_continuous.py:111-155 scaled out.
-       `extra.search_only` is the same loop without the collectives; rank 0 adds `cpu_baseline` after the timed region.
+       With --full: `extra.search_only` is the same loop without the collectives, `extra.config_e_nrank` the config E leg, and
+       rank 0 adds `roofline` and `cpu_baseline` after the timed region.
        Rendezvous and collectives are bounded (--dist-timeout): a rank that never arrives or dies fails the run instead of hanging it.
 Rank 0 prints ONE JSON line.
 --dump-outputs DIR: rank 0 also writes what the timed loop's last step computed as DIR/<name>.npy (see dump_outputs), so that two
@@ -465,7 +472,7 @@ def spawn(args):
            "--warmup", str(args.warmup), "--trees", str(args.trees), "--bcast-every", str(args.bcast_every), "--gather-every", str(args.gather_every),
            "--backend", args.backend, "--dist-timeout", str(args.dist_timeout), "--e-trees", str(args.e_trees), "--e-searches", str(args.e_searches)]
     for flag, on in (("--same-device", args.same_device), ("--config-d", args.config_d), ("--verify-gather", args.verify_gather),
-                     ("--no-cpu-baseline", args.no_cpu_baseline)):
+                     ("--no-cpu-baseline", args.no_cpu_baseline), ("--full", args.full)):
         if on:
             cmd.append(flag)
     if args.dump_outputs:
@@ -488,14 +495,16 @@ def main():
     ap.add_argument("--verify-gather", action="store_true", help="N > 1 loop: check every gathered block against the rows the previous step wrote (slow)")
     ap.add_argument("--traffic-probe", action="store_true", help="(internal) a few searches for the PMC passes of live_traffic()")
     ap.add_argument("--probe-config", default="C", choices=sorted(PROBE_SHAPES), help="(internal) the shape --traffic-probe runs")
-    ap.add_argument("--no-live-traffic", action="store_true", help="N = 1: take roofline.traffic from the committed profile instead of measuring it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-live-traffic", action="store_true", help="N = 1, --full: take roofline.traffic from the committed profile instead of measuring it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--dist-timeout", type=float, default=300.0, help="N > 1: seconds before a rendezvous / collective that does not complete "
                                                                       "(a dead rank) fails the run")
-    ap.add_argument("--no-extra", action="store_true", help="N = 1: skip the config B / E lines")
-    ap.add_argument("--e-trees", type=int, default=1024, help="N > 1: trees per GPU of the config E leg (4x1024 MLP, BASELINE.json configs[4]: 8192 trees over 8 GPUs)")
-    ap.add_argument("--e-searches", type=int, default=5, help="N > 1: timed searches of the config E leg (0: skip the leg)")
+    ap.add_argument("--no-extra", action="store_true", help="N = 1, --full: skip the config B / E lines")
+    ap.add_argument("--e-trees", type=int, default=1024, help="N > 1, --full: trees per GPU of the config E leg (4x1024 MLP, BASELINE.json configs[4]: 8192 trees over 8 GPUs)")
+    ap.add_argument("--e-searches", type=int, default=5, help="N > 1, --full: timed searches of the config E leg (0: skip the leg)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed loop's last step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure and check everything beyond the headline: rooflines, "
+                                                        "profiler passes, other configurations, the CPU baseline (off: the headline line alone)")
     args = ap.parse_args()
 
     if args.traffic_probe:
@@ -559,32 +568,33 @@ def main():
         elapsed = time.perf_counter() - t0
         if args.dump_outputs:   # return_results of the last timed search (every later search advances the engine's search index)
             dump_outputs(args.dump_outputs, eng.results())
-        kmed, kmean = time_search(eng, min(args.steps, 10), 0)   # separate pass: the event reads would serialise the timed loop
-        res = eng.results()
-        assert (res["counts"].sum(1) == N_SIMS).all()
-        walk_c = tree_walk_bytes_continuous(eng.dump_tree(), N_SIMS, PENDULUM["c_pw"], PENDULUM["kappa"])
-        # the boundary with host buffers (azg_search uploads the roots, azg_results downloads the root statistics over PCIe)
-        roots = eng.synthetic_roots()
-        pc = []
-        for _ in range(5):
-            t1 = time.perf_counter(); eng.search(roots); eng.results(); pc.append(time.perf_counter() - t1)
-        extra["pcie_inclusive"] = {"sims_per_s": B * N_SIMS / float(np.median(pc)), "ms_per_search": float(np.median(pc)) * 1e3,
-                                   "note": "azg_search (host roots in) + azg_results (host root statistics out), median of 5; never `value`"}
-        # the N > 1 workload (config D's self-play step) on this one GPU, no collectives: what the driver's 1 -> N ratio should be
-        # read against (N = 1 times config C = search + return_results; N > 1 times config D = that + final action, env step, replay row)
-        eng.selfplay_begin(200, capacity_steps=8, fifo=True)
-        for _ in range(args.warmup):
-            eng.selfplay_step()
-        eng.sync()
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            eng.selfplay_step()
-        eng.sync()
-        dsp = time.perf_counter() - t1
-        extra["config_d_1rank"] = {"sims_per_s": B * N_SIMS * args.steps / dsp, "ms_per_step": dsp / args.steps * 1e3, "steps": args.steps,
-                                   "note": "config D's step on one GPU (search + final action + env step + replay row on the device, no collectives): "
-                                           "the like-for-like N = 1 leg of the N > 1 lines, whose `value` times this step plus the replay all-gather "
-                                           "and the weight broadcast"}
+        if args.full:
+            kmed, kmean = time_search(eng, min(args.steps, 10), 0)   # separate pass: the event reads would serialise the timed loop
+            res = eng.results()
+            assert (res["counts"].sum(1) == N_SIMS).all()
+            walk_c = tree_walk_bytes_continuous(eng.dump_tree(), N_SIMS, PENDULUM["c_pw"], PENDULUM["kappa"])
+            # the boundary with host buffers (azg_search uploads the roots, azg_results downloads the root statistics over PCIe)
+            roots = eng.synthetic_roots()
+            pc = []
+            for _ in range(5):
+                t1 = time.perf_counter(); eng.search(roots); eng.results(); pc.append(time.perf_counter() - t1)
+            extra["pcie_inclusive"] = {"sims_per_s": B * N_SIMS / float(np.median(pc)), "ms_per_search": float(np.median(pc)) * 1e3,
+                                       "note": "azg_search (host roots in) + azg_results (host root statistics out), median of 5; never `value`"}
+            # the N > 1 workload (config D's self-play step) on this one GPU, no collectives: what the driver's 1 -> N ratio should be
+            # read against (N = 1 times config C = search + return_results; N > 1 times config D = that + final action, env step, replay row)
+            eng.selfplay_begin(200, capacity_steps=8, fifo=True)
+            for _ in range(args.warmup):
+                eng.selfplay_step()
+            eng.sync()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                eng.selfplay_step()
+            eng.sync()
+            dsp = time.perf_counter() - t1
+            extra["config_d_1rank"] = {"sims_per_s": B * N_SIMS * args.steps / dsp, "ms_per_step": dsp / args.steps * 1e3, "steps": args.steps,
+                                       "note": "config D's step on one GPU (search + final action + env step + replay row on the device, no collectives): "
+                                               "the like-for-like N = 1 leg of the N > 1 lines, whose `value` times this step plus the replay all-gather "
+                                               "and the weight broadcast"}
         workload = f"config C: Pendulum-v1 A0C, {B} trees/GPU x {N_SIMS} sims, 2x256 ELU policy/value MLP, c_uct=0.05 c_pw=1 kappa=0.5"
         parallelism = "1 GPU"
     else:
@@ -667,17 +677,18 @@ def main():
             if verify["gathers"]:
                 out["gathered_rows"] = gathered.cpu().numpy()     # every rank's block of the last all-gather
             dump_outputs(args.dump_outputs, out)
-        barrier()
-        t1 = time.perf_counter()
-        run(args.steps, False)
-        barrier()
-        plain = time.perf_counter() - t1
-        if verify["gathers"]:
-            counts = gathered[:, 3 + eng.kmax:3 + 2 * eng.kmax].sum(1)
-            assert bool((counts == N_SIMS).all()), "a gathered replay row does not hold n_sims visits"
-        kmed, kmean = time_search(eng, 5, 0)
-        if dist is not None and args.e_searches > 0:
-            extra["config_e_nrank"] = config_e_leg(args, rank, world, dev, dist, barrier)
+        if args.full:
+            barrier()
+            t1 = time.perf_counter()
+            run(args.steps, False)
+            barrier()
+            plain = time.perf_counter() - t1
+            if verify["gathers"]:
+                counts = gathered[:, 3 + eng.kmax:3 + 2 * eng.kmax].sum(1)
+                assert bool((counts == N_SIMS).all()), "a gathered replay row does not hold n_sims visits"
+            kmed, kmean = time_search(eng, 5, 0)
+            if dist is not None and args.e_searches > 0:
+                extra["config_e_nrank"] = config_e_leg(args, rank, world, dev, dist, barrier)
         workload = (f"config D: Pendulum-v1 A0C self-play, {world * B} games = {B} per GPU x {N_SIMS} sims per move, 2x256 ELU MLP; per step: "
                     f"search + final action + env step + replay row on the device; every {K} steps an all-gather of those steps' "
                     f"{world * K * B} replay rows ({world * K * B * RL * 4 / 1e6:.1f} MB, HBM to HBM, beside the next step's search); a weight "
@@ -699,18 +710,15 @@ def main():
             allr = [torch.zeros_like(mine) for _ in range(world)]
             dist.all_gather(allr, mine)
             per_rank = torch.stack(allr).cpu().numpy()
-        if config_d:
+        if config_d and args.full:
             t = torch.tensor([plain], device="cpu" if args.backend != "nccl" else "cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             plain = float(t.item())
-    kname = kernel_name(eng)
+    kname = kernel_name(eng) if args.full else None
     eng.close()
     if rank == 0:
         sims = world * B * N_SIMS * args.steps
-        achieved = B * N_SIMS * FLOP_PER_SIM / (kmean * 1e-3) / 1e12
         if config_d:
-            extra["search_only"] = {"sims_per_s": sims / plain, "ms_per_step": plain / args.steps * 1e3,
-                                    "note": "the same self-play loop without the all-gather and the weight broadcast"}
             def spread(col):
                 v = per_rank[:, col]
                 v = v[v >= 0]
@@ -724,71 +732,76 @@ def main():
                                                             "all-gather call until its rows are usable, weight broadcast + engine re-sync, one whole "
                                                             "loop iteration (wait for the previous step, collectives, launch of the next step)"},
                                     "weight_sync": "host (gloo functional run)" if on_host else "device to device: RCCL broadcast into HBM + azg_set_weights_device"}
-        elif not args.no_extra:
-            extra["configs"] = [
-                extra_config("C at 8192 trees per GPU (the batch shape of real self-play runs: two 16-tree groups per CU)", PENDULUM, 8192, 200, 3, HIDDEN, 2, "elu",
-                             "search_kernel<2, 256, 1, 1, false, 8, 2, 16, 1>", FLOP_PER_SIM,
-                             "8-wave / 32-tree workgroups: two 16-tree groups share every network phase and walk together, two waves per SIMD (the second one fills the other's LDS / memory waits; MFMA and vector time add up)", dev),
-                extra_config("B: CartPole-v1 discrete, 4096 trees, n_sims=100, 2x128 ReLU", CARTPOLE, 4096, 100, 4, [128, 128], 2, "relu",
-                             B_KERNEL, None,
-                             "tree-walk bound (8-9 levels per trace, about 0.2 evaluations per simulation -- counted from the trees --: the MFMA "
-                             "fraction is small by construction, the HBM-side figure of SURVEY 8d is in roofline_hbm; selections are taken at "
-                             "backup time and stored with the nodes, the descent follows them", dev, hbm=True, live=("B", "search_kernel")),
-                extra_config("E (per GPU): Pendulum-v1, 1024 trees, n_sims=200, 4x1024 ELU", PENDULUM, 1024, 200, 3, [1024] * 4, 2, "elu",
-                             "ls_team_kernel<2, 1024, false, 1, 2, 2, 1, 32>",
-                             mlp_flops(3, [1024] * 4, 3), "persistent team kernel: one launch per search, 32 teams of 16 workgroups (one 64-unit slice of every "
-                             "layer for the team's 32 trees each), hand-offs through global memory; traffic = L2 misses of the cross-XCD "
-                             "activation hand-offs (DESIGN.md section 3), the weights stay L2-resident", dev, live=("E", "ls_team_kernel")),
-                extra_config("E's network at 2048 trees per GPU", PENDULUM, 2048, 200, 3, [1024] * 4, 2, "elu",
-                             "ls_team_kernel<2, 1024, false, 1, 2, 2, 1, 64>",
-                             mlp_flops(3, [1024] * 4, 3), "the team kernel with teams of 64 trees (64 x 64 tiles: a third fewer staged bytes per MFMA than the "
-                             "32-tree teams' 32 x 64), two workgroups per CU, short staging chunks", dev),
-                extra_config("E's network at 3072 trees per GPU", PENDULUM, 3072, 200, 3, [1024] * 4, 2, "elu",
-                             "ls_team_kernel<2, 1024, false, 1, 2, 3, 1, 64>",
-                             mlp_flops(3, [1024] * 4, 3), "64-tree teams, three workgroups per CU: while one waits at a hand-off or walks its trees the "
-                             "other two keep the matrix pipe busy", dev),
-            ]
-        traffic, traffic_note = None, ("not measured in the N > 1 loop (the search kernel is the one of the N = 1 line: same launch, same "
-                                       "traffic; rocprofv3 child passes are not started from inside a running multi-rank job)")
-        if config_d and B == N_TREES:
-            traffic, src = profiled_traffic()
-            traffic_note += f"; value from the committed N = 1 passes ({src})"
-        if not config_d:
-            if not args.no_live_traffic:
-                traffic, why = live_traffic(B)
-                traffic_note = ("measured in this run: two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) over 5 launches of this kernel, "
-                                "2 x FETCH + WRITE") if traffic is not None else f"live PMC passes unavailable ({why})"
-            if traffic is None and B == N_TREES:
-                traffic, src = profiled_traffic()
-                traffic_note += f"; from the committed passes ({src})"
-            if not args.no_live_traffic:
-                busy, why = live_mfma_busy(B)
-                extra["mfma_busy"] = ({"value": busy, "note": "hardware view of roofline.frac: SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs) of the "
-                                                               "search kernel, one more rocprofv3 --pmc child pass of this run (it also counts the first layer's "
-                                                               "and the heads' MFMAs, which the 134 144-FLOP figure leaves out)"}
-                                      if busy is not None else {"value": None, "note": f"not measured ({why})"})
         out = {
             "metric": "MCTS sims/sec (whole node), Pendulum-v1 4096 trees n_sims=200, 1/2/4/8 GPU", "value": sims / elapsed, "unit": "sims/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic",
             "config": {"workload": workload, "trees_per_gpu": B, "n_sims": N_SIMS, "parallelism": parallelism},
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_TFLOPS,
-                         "traffic": traffic, "traffic_note": traffic_note,
-                         "kernel": kname + " (template arguments: ENV 2 = Pendulum, HP = padded hidden width, NREG = hidden->hidden layers held in "
-                                   "registers, tree storage 1 = LDS with 8-bit ids, mixture head, waves per workgroup -- eight, of which the first four walk the trees --, "
-                                   "tree groups per workgroup, trees per group, 1 = compiled for epsilon 0 / lowest-index ties (the general kernel gives the same trees))",
-                         "kernel_ms": kmean, "kernel_ms_median": kmed,
-                         "note": "one launch = one whole search; achieved = trees x sims x 134144 FLOP / mean launch time (HIP events on the "
-                                 "engine stream); policy/value MLP in fp32 MFMA, tree statistics in fp64; traffic = HBM bytes per launch from "
-                                 "rocprofv3 PMC passes (see traffic_note); `value` is wall "
-                                 "time over K steps of search + return_results (written by the same launch's epilogue) with everything resident in HBM, the PCIe-inclusive "
-                                 "rate is extra.pcie_inclusive"},
-            "extra": extra,
         }
-        if not config_d:
+        if args.full:
+            achieved = B * N_SIMS * FLOP_PER_SIM / (kmean * 1e-3) / 1e12
+            if config_d:
+                extra["search_only"] = {"sims_per_s": sims / plain, "ms_per_step": plain / args.steps * 1e3,
+                                        "note": "the same self-play loop without the all-gather and the weight broadcast"}
+            elif not args.no_extra:
+                extra["configs"] = [
+                    extra_config("C at 8192 trees per GPU (the batch shape of real self-play runs: two 16-tree groups per CU)", PENDULUM, 8192, 200, 3, HIDDEN, 2, "elu",
+                                 "search_kernel<2, 256, 1, 1, false, 8, 2, 16, 1>", FLOP_PER_SIM,
+                                 "8-wave / 32-tree workgroups: two 16-tree groups share every network phase and walk together, two waves per SIMD (the second one fills the other's LDS / memory waits; MFMA and vector time add up)", dev),
+                    extra_config("B: CartPole-v1 discrete, 4096 trees, n_sims=100, 2x128 ReLU", CARTPOLE, 4096, 100, 4, [128, 128], 2, "relu",
+                                 B_KERNEL, None,
+                                 "tree-walk bound (8-9 levels per trace, about 0.2 evaluations per simulation -- counted from the trees --: the MFMA "
+                                 "fraction is small by construction, the HBM-side figure of SURVEY 8d is in roofline_hbm; selections are taken at "
+                                 "backup time and stored with the nodes, the descent follows them", dev, hbm=True, live=("B", "search_kernel")),
+                    extra_config("E (per GPU): Pendulum-v1, 1024 trees, n_sims=200, 4x1024 ELU", PENDULUM, 1024, 200, 3, [1024] * 4, 2, "elu",
+                                 "ls_team_kernel<2, 1024, false, 1, 2, 2, 1, 32>",
+                                 mlp_flops(3, [1024] * 4, 3), "persistent team kernel: one launch per search, 32 teams of 16 workgroups (one 64-unit slice of every "
+                                 "layer for the team's 32 trees each), hand-offs through global memory; traffic = L2 misses of the cross-XCD "
+                                 "activation hand-offs (DESIGN.md section 3), the weights stay L2-resident", dev, live=("E", "ls_team_kernel")),
+                    extra_config("E's network at 2048 trees per GPU", PENDULUM, 2048, 200, 3, [1024] * 4, 2, "elu",
+                                 "ls_team_kernel<2, 1024, false, 1, 2, 2, 1, 64>",
+                                 mlp_flops(3, [1024] * 4, 3), "the team kernel with teams of 64 trees (64 x 64 tiles: a third fewer staged bytes per MFMA than the "
+                                 "32-tree teams' 32 x 64), two workgroups per CU, short staging chunks", dev),
+                    extra_config("E's network at 3072 trees per GPU", PENDULUM, 3072, 200, 3, [1024] * 4, 2, "elu",
+                                 "ls_team_kernel<2, 1024, false, 1, 2, 3, 1, 64>",
+                                 mlp_flops(3, [1024] * 4, 3), "64-tree teams, three workgroups per CU: while one waits at a hand-off or walks its trees the "
+                                 "other two keep the matrix pipe busy", dev),
+                ]
+            traffic, traffic_note = None, ("not measured in the N > 1 loop (the search kernel is the one of the N = 1 line: same launch, same "
+                                           "traffic; rocprofv3 child passes are not started from inside a running multi-rank job)")
+            if config_d and B == N_TREES:
+                traffic, src = profiled_traffic()
+                traffic_note += f"; value from the committed N = 1 passes ({src})"
+            if not config_d:
+                if not args.no_live_traffic:
+                    traffic, why = live_traffic(B)
+                    traffic_note = ("measured in this run: two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) over 5 launches of this kernel, "
+                                    "2 x FETCH + WRITE") if traffic is not None else f"live PMC passes unavailable ({why})"
+                if traffic is None and B == N_TREES:
+                    traffic, src = profiled_traffic()
+                    traffic_note += f"; from the committed passes ({src})"
+                if not args.no_live_traffic:
+                    busy, why = live_mfma_busy(B)
+                    extra["mfma_busy"] = ({"value": busy, "note": "hardware view of roofline.frac: SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs) of the "
+                                                                   "search kernel, one more rocprofv3 --pmc child pass of this run (it also counts the first layer's "
+                                                                   "and the heads' MFMAs, which the 134 144-FLOP figure leaves out)"}
+                                          if busy is not None else {"value": None, "note": f"not measured ({why})"})
+            out["roofline"] = {"bound": "mfma", "achieved": achieved, "peak": PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_TFLOPS,
+                               "traffic": traffic, "traffic_note": traffic_note,
+                               "kernel": kname + " (template arguments: ENV 2 = Pendulum, HP = padded hidden width, NREG = hidden->hidden layers held in "
+                                         "registers, tree storage 1 = LDS with 8-bit ids, mixture head, waves per workgroup -- eight, of which the first four walk the trees --, "
+                                         "tree groups per workgroup, trees per group, 1 = compiled for epsilon 0 / lowest-index ties (the general kernel gives the same trees))",
+                               "kernel_ms": kmean, "kernel_ms_median": kmed,
+                               "note": "one launch = one whole search; achieved = trees x sims x 134144 FLOP / mean launch time (HIP events on the "
+                                       "engine stream); policy/value MLP in fp32 MFMA, tree statistics in fp64; traffic = HBM bytes per launch from "
+                                       "rocprofv3 PMC passes (see traffic_note); `value` is wall "
+                                       "time over K steps of search + return_results (written by the same launch's epilogue) with everything resident in HBM, the PCIe-inclusive "
+                                       "rate is extra.pcie_inclusive"}
+        out["extra"] = extra
+        if args.full and not config_d:
             out["roofline_hbm"] = hbm_block(*walk_c, B, N_SIMS, kmean, traffic, traffic_note)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only, after the timed region (the other ranks wait at the final barrier, inside --dist-timeout)
             out["cpu_baseline"] = cpu_baseline(short=config_d)
         print(json.dumps(out), flush=True)

@@ -96,6 +96,21 @@ def test_gpus_must_match_world_size():
     assert p.returncode != 0 and "does not match WORLD_SIZE" in (p.stderr + p.stdout)
 
 
+def test_spawned_ranks_inherit_full(monkeypatch):
+    """`bench.py --gpus N` without a launcher starts torch.distributed.run itself: its ranks run --full exactly when it was asked for."""
+    import bench
+    for var in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(var, raising=False)
+    for extra, want in (([], False), (["--full"], True)):
+        cmds = []
+        monkeypatch.setattr(bench.subprocess, "call", lambda cmd: cmds.append(cmd) or 0)
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2"] + extra)
+        with pytest.raises(SystemExit) as ex:
+            bench.main()
+        assert ex.value.code == 0 and len(cmds) == 1
+        assert ("--full" in cmds[0]) == want, cmds[0]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("ranks", [2, 4])
 def test_multi_rank_loop_on_one_gpu(ranks):
@@ -103,13 +118,13 @@ def test_multi_rank_loop_on_one_gpu(ranks):
     broadcast + engine re-sync) runs with gloo and every rank on GPU 0: N = 2 and 4 -- four tree_id_base offsets, four engines
     on one device, a four-way gather, followed by the config E leg (4x1024 network, every rank its own shard of trees).  (Eight
     ranks would put nine processes on the one GPU, this test's own included: more than a shared device should carry.  The
-    eight-way gather of the same code runs in tests/test_distributed.py over gloo on the CPU.)  The N > 1 line carries the CPU baseline, a
-    note about the traffic figure and every rank's host-side timings of the collectives (min / median / max
-    over the ranks) with the world size each rank saw."""
+    eight-way gather of the same code runs in tests/test_distributed.py over gloo on the CPU.)  With --full the N > 1 line carries the
+    CPU baseline, a note about the traffic figure and every rank's host-side timings of the collectives (min /
+    median / max over the ranks) with the world size each rank saw."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     trees = "512"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "5", "--warmup", "2", "--trees", trees,
-                        "--bcast-every", "2", "--backend", "gloo", "--same-device", "--e-trees", "64", "--e-searches", "2"],
+                        "--bcast-every", "2", "--backend", "gloo", "--same-device", "--e-trees", "64", "--e-searches", "2", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
@@ -171,6 +186,29 @@ def test_gathered_rows_are_the_previous_steps_rows(warmup):
                        "--backend", "gloo", "--same-device", "--verify-gather"])
     c = out["extra"]["collectives"]
     assert c["gathers_verified"] == c["gathers"] >= (warmup + 5 - 1) // 2   # a block of two finished steps per gather, across both runs
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_alone_and_full_adds_the_rest():
+    """A plain `bench.py --gpus 1` run sets up, warms up, times its steps and prints the headline line: no kernel-time pass, no
+    roofline, no other run after the timed steps.  --full adds them (here without the profiler passes, the other configurations
+    and the CPU baseline, whose own switches keep this test short): the rooflines from a kernel-time pass and the searched trees,
+    the PCIe-inclusive rate and config D's step on this one GPU.  The headline fields are the same in both lines."""
+    steps, warmup = 3, 1
+    plain = _bench_json(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)])
+    assert plain["unit"] == "sims/s" and plain["higher_is_better"] is True and plain["dtype"] == "f32"
+    assert plain["n_gpus"] == 1 and plain["steps"] == steps and plain["warmup"] == warmup and "config C" in plain["config"]["workload"]
+    sims = 4096 * 200
+    assert plain["value"] > 0 and abs(plain["value"] * plain["ms_per_step"] * 1e-3 - sims) < 1e-6 * sims
+    assert not {"roofline", "roofline_hbm", "cpu_baseline"} & set(plain) and plain["extra"] == {}
+    full = _bench_json(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-extra", "--no-live-traffic",
+                        "--no-cpu-baseline"])
+    assert set(plain) < set(full) and {"roofline", "roofline_hbm"} <= set(full) and "cpu_baseline" not in full
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "config"):
+        assert full[k] == plain[k], k
+    assert full["roofline"]["kernel_ms"] > 0 and 0 < full["roofline"]["frac"] < 1
+    assert full["roofline"]["kernel"].startswith("search_kernel<2, 256"), full["roofline"]["kernel"]
+    assert {"pcie_inclusive", "config_d_1rank"} <= set(full["extra"]) and "configs" not in full["extra"]
 
 
 @pytest.mark.gpu

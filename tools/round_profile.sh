@@ -32,7 +32,7 @@ fi
 # end-to-end learning on one GPU (examples/selfplay_train.py)
 python3 examples/selfplay_train.py --game CartPole-v0 --games 512 --n-rollouts 32 --iters 80 2>/dev/null | grep "^{" > $OUT/${TAG}_learning_cartpole.jsonl
 python3 examples/selfplay_train.py --game Pendulum-v1 --games 512 --n-rollouts 50 --iters 40 --steps-per-iter 200 --train-rows 16384 --batch-size 128 2>/dev/null | grep "^{" > $OUT/${TAG}_learning_pendulum.jsonl
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 # rocprofv3: kernel stats + PMC passes of the headline command, and of config B (with the HBM passes)
 bash tools/profile_bench.sh $TAG > $OUT/${TAG}_profile_bench.log 2>&1
 bash tools/profile_config_b.sh $TAG > $OUT/${TAG}_profile_b.log 2>&1
