@@ -109,7 +109,7 @@ class AzgSearchInfo(C.Structure):
 
 KERNEL_FORMS = {-1: "none", 0: "persistent", 1: "per_layer", 2: "team"}
 TREE_STORAGE = {0: "global", 1: "lds8", 2: "lds9"}
-LDS_EXIT = {0: "resident", 1: "records", 2: "children", 3: "lds_size", 4: "forced", 5: "not_applicable"}
+LDS_EXIT = {0: "resident", 1: "records", 2: "children", 3: "lds_size", 4: "forced", 5: "not_applicable", 6: "counts"}
 
 
 class HipEngine(_capi.Engine):

@@ -113,6 +113,24 @@ static bool use_lockstep(const azg_engine* e) {
     return e->HP >= 512 && e->n_hidden >= 2 && !e->P.layernorm;
 }
 
+// One search of all trees on e->stream: the kernels of the engine's family (azg_kernel_env) on its path, by network width.
+template <int ENV>
+static hipError_t search_path(azg_engine* e, bool lockstep) {
+    if (lockstep) {
+        if constexpr (ENV == AZG_ENV_ACROBOT) return hipErrorInvalidValue;   // (six network inputs: never lock-step, use_lockstep)
+        else return azg_lockstep_search<ENV>(e);
+    }
+    return e->HP <= 128 ? azg_persistent_search<ENV, false>(e) : azg_persistent_search<ENV, true>(e);
+}
+static hipError_t search_launch(azg_engine* e, bool lockstep) {
+    switch (azg_kernel_env(e->cfg)) {
+        case AZG_ENV_CARTPOLE: return search_path<AZG_ENV_CARTPOLE>(e, lockstep);
+        case AZG_ENV_MOUNTAINCAR_CONT: return search_path<AZG_ENV_MOUNTAINCAR_CONT>(e, lockstep);
+        case AZG_ENV_ACROBOT: return search_path<AZG_ENV_ACROBOT>(e, lockstep);
+        default: return search_path<AZG_ENV_PENDULUM_V1>(e, lockstep);
+    }
+}
+
 // The persistent team kernel leaves instead of hanging when one of its waits times out (its workgroups were not all resident,
 // e.g. another process holds part of the GPU): it raises a word that is read here, after the stream has been synchronised.
 // The search is then run again, with the same search index, as per-layer launches -- which the engine uses from then on.
@@ -229,11 +247,11 @@ int azg_engine_create(const azg_config* cfg, azg_engine** out) {
     { const char* v = getenv("AZG_TILE_TREES"); const int t = v ? atoi(v) : 0; e->opt.tile_trees = (t == 16 || t == 8) ? t : 0; }
     e->opt.ls_team = env_digit("AZG_LS_TEAM", 1);
     e->opt.team_wide = env_digit("AZG_TEAM_WIDE", 1);
-    e->team_kc = 0; e->team_minb = 0; e->team_tt = 32;
     { const char* v = getenv("AZG_TEAM_TT"); e->opt.team_tt = v ? atoi(v) : 0; }
     { const char* v = getenv("AZG_TEAM_SPIN_LIMIT"); e->opt.team_spin_limit = v ? atol(v) : (1L << 23); }
+    e->opt.no_lds_state = getenv("AZG_NO_LDS_STATE") != nullptr;
     e->d_team_cnt = nullptr; e->team_cnt_bytes = 0; e->team_pending = 0; e->team_fallbacks = 0; e->team_search_idx = 0;
-    e->kernel_form = -1; e->lds_exit = 0; e->lds_warned = 0; e->last_search_idx = 0; e->ms_kept = 0.0f; e->ms_kept_valid = 0;
+    e->lds_warned = 0; e->last_search_idx = 0; e->ms_kept = 0.0f; e->ms_kept_valid = 0;
     e->carry_max = 0;
     e->n_nets = 1; e->net_have.assign(1, 0);
     e->h_res_block = nullptr; e->d_res_block = nullptr; e->res_bytes = 0;
@@ -269,11 +287,9 @@ int azg_engine_create(const azg_config* cfg, azg_engine** out) {
     // sqrt(n+1) table: node visit counts reach n_sims (+ the carried root count in discrete mode; beyond 3 n_sims the kernel
     // computes the root's square root in place)
     e->tab_n = cfg->mode == AZG_MODE_CONTINUOUS ? ns + 2 : 4 * ns + 4;
-    e->tree_lds = 0;
-    e->dyn_lds = 0;
     DeviceScope scope(cfg->device_id);
     if (!scope.ok) { delete e; return fail(nullptr, AZG_E_DEVICE, "hipSetDevice failed"); }
-    e->waves = 4; e->groups = 1; e->tile_trees = 16; e->spec = 0; e->n_cus = 256;
+    e->n_cus = 256;
     (void)hipDeviceGetAttribute(&e->n_cus, hipDeviceAttributeMultiprocessorCount, cfg->device_id);
 #define CK(x) do { int _r = (x); if (_r != AZG_OK) { g_create_err = e->err; azg_engine_destroy(e); return _r; } } while (0)
 #define HK(call) do { hipError_t _rc = (call); if (_rc != hipSuccess) { g_create_err = std::string(#call) + ": " + hipGetErrorString(_rc); azg_engine_destroy(e); return AZG_E_DEVICE; } } while (0)
@@ -745,32 +761,30 @@ int azg_search_resident(azg_engine* e) {
     e->ms_kept_valid = 0;
     e->P.publish = (e->publish_always || e->publish_once) ? 1 : 0;
     e->team_search_idx = e->search_idx;
+    e->last = LaunchRecord();
     const bool lockstep = use_lockstep(e);
     if (lockstep) { int prc = ls_prepare(e); if (prc) return prc; }
-    e->launch_timed = 0;
     if (lockstep) HIPCHK(e, hipEventRecord(e->ev0, e->stream));   // (several launches; the one-launch search kernel stamps ev0 / ev1 itself)
-    hipError_t rc;
-    const bool cartpole = e->cfg.mode == AZG_MODE_DISCRETE;   // the discrete family's kernels (CartPole, MountainCar)
-    const bool mcc = e->cfg.env_id == AZG_ENV_MOUNTAINCAR_CONT;   // the continuous family whose episodes end (env.cuh: EnvFamily)
-    if (lockstep) rc = cartpole ? azg_ls_dispatch_cartpole(e) : (mcc ? azg_ls_dispatch_mcc(e) : azg_ls_dispatch_pendulum(e));
-    else if (e->cfg.env_id == AZG_ENV_ACROBOT) rc = azg_dispatch_acrobot(e);
-    else if (cartpole) rc = azg_dispatch_cartpole(e);
-    else if (mcc) rc = azg_dispatch_mcc(e);
-    else rc = e->HP <= 128 ? azg_dispatch_pendulum_small(e) : azg_dispatch_pendulum_large(e);
+    const hipError_t rc = search_launch(e, lockstep);
     if (rc != hipSuccess) return fail(e, AZG_E_DEVICE, std::string("search kernel launch: ") + hipGetErrorString(rc));
-    if (!e->launch_timed) HIPCHK(e, hipEventRecord(e->ev1, e->stream));
+    if (!e->last.timed) HIPCHK(e, hipEventRecord(e->ev1, e->stream));
     e->search_idx += 1;
     e->searched = 1;
-    e->results_valid = e->kernel_form == 0 ? 1 : 0;   // the one-launch search kernel writes return_results in its epilogue
-    e->published = (e->kernel_form != 0 || e->tree_lds == TS_GLOBAL || e->P.publish) ? 1 : 0;
+    const bool persistent = e->last.form == AZG_FORM_PERSISTENT;
+    e->results_valid = persistent ? 1 : 0;   // the one-launch search kernel writes return_results in its epilogue
+    e->published = (!persistent || e->last.tree_lds == TS_GLOBAL || e->P.publish) ? 1 : 0;
     e->redo_ok = 1;
-    if (e->kernel_form == 0 && e->tree_lds == TS_GLOBAL && e->lds_exit != AZG_LDS_EXIT_FORCED && !e->lds_warned) {
+    if (persistent && e->last.tree_lds == TS_GLOBAL && e->last.lds_exit != AZG_LDS_EXIT_FORCED && !e->lds_warned) {
         e->lds_warned = 1;
         static const char* why[] = {"", "more than 511 records per tree (n_sims + 2)", "more than 16 children per node (c_pw / kappa)",
-                                    "the workgroup's LDS plan exceeds the CU's 160 KB", ""};
+                                    "the workgroup's LDS plan exceeds the CU's 160 KB", "", "",
+                                    "the root's visit count (carried + n_sims) overflows the LDS records' counters"};
+        const int x = e->last.lds_exit;
+        const char* reason = x == AZG_LDS_EXIT_RECORDS && e->R <= 511 ? "more than 255 records per tree (n_sims + 2) for this network's kernels"
+                                                                      : (x >= 0 && x < (int)(sizeof(why) / sizeof(why[0])) ? why[x] : "");
         if (!getenv("AZG_QUIET"))
             fprintf(stderr, "azgym: the trees of this search do not fit LDS residency (%s): they are kept in global memory -- same results, "
-                            "slower tree walk (azg_search_info; once per engine)\n", why[e->lds_exit & 3]);
+                            "slower tree walk (azg_search_info; once per engine)\n", reason);
     }
     return AZG_OK;
 }
@@ -978,13 +992,13 @@ int azg_dump_tree(azg_engine* e, int32_t* n_records, int32_t* parent, int32_t* e
 // the kernel(s) of the last search as rocprofv3 names them (template arguments: ENV, HP, NREG, tree storage, mixture head, waves, tree
 // groups, trees per group, compile-time specialisation; team kernel: ..., staging chunk length, workgroups per CU -- see search_kernel.cuh / team.cuh)
 static int kernel_name(const azg_engine* e, char* buf, size_t n) {
-    // (ENV = 0: the CartPole / MountainCar family, 5: Acrobot, 2: both Pendulum versions, 4: MountainCarContinuous)
-    const int env = e->cfg.mode == AZG_MODE_DISCRETE ? (e->cfg.env_id == AZG_ENV_ACROBOT ? 5 : 0) : (e->cfg.env_id == AZG_ENV_MOUNTAINCAR_CONT ? 4 : 2);
-    const char* gmm = (env != 0 && e->P.ncomp >= 2) ? "true" : "false";
-    switch (e->kernel_form) {
-        case 0: return snprintf(buf, n, "search_kernel<%d, %d, %d, %d, %s, %d, %d, %d, %d>", env, e->HP, e->nreg, e->tree_lds, gmm, e->waves, e->groups, e->tile_trees, e->spec);
-        case 1: return snprintf(buf, n, "ls_tree_kernel<%d, ...> + ls_layer0_kernel + ls_hidden_tiled_kernel<%d, ...> per simulation step", env, e->HP);
-        case 2: return snprintf(buf, n, "ls_team_kernel<%d, %d, %s, %d, %d, %d, %d, %d>", env, e->HP, gmm, e->tree_lds, e->team_kc, e->team_minb, e->spec, e->team_tt);
+    const int env = azg_kernel_env(e->cfg);
+    const char* gmm = (env != AZG_ENV_CARTPOLE && e->P.ncomp >= 2) ? "true" : "false";
+    const LaunchRecord& r = e->last;
+    switch (r.form) {
+        case AZG_FORM_PERSISTENT: return snprintf(buf, n, "search_kernel<%d, %d, %d, %d, %s, %d, %d, %d, %d>", env, e->HP, e->nreg, r.tree_lds, gmm, r.waves, r.groups, r.tile_trees, r.spec);
+        case AZG_FORM_PER_LAYER: return snprintf(buf, n, "ls_tree_kernel<%d, ...> + ls_layer0_kernel + ls_hidden_tiled_kernel<%d, ...> per simulation step", env, e->HP);
+        case AZG_FORM_TEAM: return snprintf(buf, n, "ls_team_kernel<%d, %d, %s, %d, %d, %d, %d, %d>", env, e->HP, gmm, r.tree_lds, r.team_kc, r.team_minb, r.spec, r.team_tt);
         default: return snprintf(buf, n, "(no search yet)");
     }
 }
@@ -1001,16 +1015,16 @@ int azg_search_info(azg_engine* e, azg_search_report* info) {
     }
     memset(info, 0, sizeof(*info));
     info->struct_size = (int32_t)sizeof(azg_search_report);
-    info->kernel_form = e->searched ? e->kernel_form : AZG_FORM_NONE;
+    const LaunchRecord& r = e->last;
+    info->kernel_form = e->searched ? r.form : AZG_FORM_NONE;
     info->max_records = e->R; info->max_children = e->Kmax;
     info->team_fallbacks = e->team_fallbacks;
     if (!e->searched) { kernel_name(e, info->kernel_name, sizeof(info->kernel_name)); info->lds_exit = AZG_LDS_RESIDENT; return AZG_OK; }
-    const bool persistent = e->kernel_form == 0;
-    info->tree_storage = persistent ? e->tree_lds : AZG_TREES_GLOBAL;
-    info->lds_exit = !persistent ? AZG_LDS_NOT_APPLICABLE : (e->tree_lds != TS_GLOBAL ? AZG_LDS_RESIDENT : e->lds_exit);
-    info->spec = e->spec;
-    if (persistent) { info->waves = e->waves; info->groups = e->groups; info->tile_trees = e->tile_trees; }
-    if (e->kernel_form == 2) { info->team_trees = e->team_tt; info->team_per_cu = e->team_minb; info->team_parts = e->team_parts; }
+    info->tree_storage = r.form == AZG_FORM_PERSISTENT ? r.tree_lds : AZG_TREES_GLOBAL;   // (the team kernel only stages its trees in LDS)
+    info->lds_exit = r.lds_exit;
+    info->spec = r.spec;
+    info->waves = r.waves; info->groups = r.groups; info->tile_trees = r.tile_trees;
+    if (r.form == AZG_FORM_TEAM) { info->team_trees = r.team_tt; info->team_per_cu = r.team_minb; info->team_parts = r.team_parts; }
     float ms = 0.0f;
     int rc = azg_last_search_ms(e, &ms);
     if (rc) return rc;

@@ -1,9 +1,7 @@
 // dispatch.cuh -- host-side choice and launch of the persistent search kernel variants (included by the dispatch_*.hip
-// translation units, each of which instantiates one family of them).
+// translation units, each of which instantiates azg_persistent_search for one family of them).
 #pragma once
 #include <hip/hip_ext.h>
-#include <atomic>
-#include <cstdlib>
 
 #include "engine_host.h"
 #include "env.cuh"
@@ -16,41 +14,33 @@
 template <int ENV, int HP, int NREG, int TLDS, bool GMM, int NW, int NG, int NT = 16, int SPEC = 0>
 static hipError_t launch_g(azg_engine* e) {
     auto kern = search_kernel<ENV, HP, NREG, TLDS, GMM, NW, NG, NT, SPEC>;
-    static std::atomic<int> static_lds_cache{-1};   // per kernel variant; engines of several host threads may race to fill it
-    int static_lds = static_lds_cache.load(std::memory_order_relaxed);
-    if (static_lds < 0) {
-        hipFuncAttributes fa;
-        hipError_t rc = hipFuncGetAttributes(&fa, (const void*)kern);
-        if (rc != hipSuccess) return rc;
-        static_lds = (int)fa.sharedSizeBytes;
-        static_lds_cache.store(static_lds, std::memory_order_relaxed);
-    }
+    static KernelAttrs attrs;
+    int static_lds = 0;
+    hipError_t rc = attrs.static_bytes((const void*)kern, &static_lds);
+    if (rc != hipSuccess) return rc;
     // discrete LDS trees: the expanded nodes' env states go to LDS too when the CU has room for them -- and when that does not
     // cost a second resident workgroup: a batch with more workgroups than CUs runs two of them side by side on a CU if their LDS
     // allows it, which is worth far more (CartPole, 8192 trees, 2x128: 0.62 ms per search against 0.94 ms)
     constexpr bool CONT = EnvFamily<ENV>::CONT;
-    LdsLayout L = lds_layout(e->tab_n, e->cfg.n_sims, HP, NG, act_buffers(NREG), e->R, CONT, TLDS, 1, NT);
+    const LdsLayout with_state = lds_layout(e->tab_n, e->cfg.n_sims, HP, NG, act_buffers(NREG), e->R, CONT, TLDS, 1, NT);
+    const LdsLayout without = lds_layout(e->tab_n, e->cfg.n_sims, HP, NG, act_buffers(NREG), e->R, CONT, TLDS, 0, NT);
     const long n_wg = azg_padded_trees(e, NT * NG) / (NT * NG);
-    const size_t with_state = L.total + (size_t)static_lds;
-    const size_t without = lds_layout(e->tab_n, e->cfg.n_sims, HP, NG, act_buffers(NREG), e->R, CONT, TLDS, 0, NT).total + (size_t)static_lds;
-    const bool costs_a_neighbour = n_wg > e->n_cus && 2 * without <= 160 * 1024 && 2 * with_state > 160 * 1024;
-    e->P.lds_state = (!CONT && TLDS != TS_GLOBAL && with_state <= 160 * 1024 && !costs_a_neighbour && !getenv("AZG_NO_LDS_STATE")) ? 1 : 0;
-    if (!e->P.lds_state) L = lds_layout(e->tab_n, e->cfg.n_sims, HP, NG, act_buffers(NREG), e->R, CONT, TLDS, 0, NT);
-    if (L.total + (size_t)static_lds > 160 * 1024) return hipErrorInvalidConfiguration;
-    if (L.total > 48 * 1024) {
-        hipError_t rc = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total);
-        if (rc != hipSuccess) return rc;
-    }
+    const size_t room = 160 * 1024 - (size_t)static_lds;   // (the CU's LDS left for the dynamic part)
+    const bool costs_a_neighbour = n_wg > e->n_cus && 2 * (without.total + static_lds) <= 160 * 1024 && 2 * (with_state.total + static_lds) > 160 * 1024;
+    e->P.lds_state = (!CONT && TLDS != TS_GLOBAL && with_state.total <= room && !costs_a_neighbour && !e->opt.no_lds_state) ? 1 : 0;
+    const size_t lds = e->P.lds_state ? with_state.total : without.total;
+    if (lds > room) return hipErrorInvalidConfiguration;
+    rc = attrs.set_dyn_lds(e, (const void*)kern, lds);
+    if (rc != hipSuccess) return rc;
     dim3 grid((unsigned)n_wg), block(64 * NW);
     e->P.net_wgs = (int)(n_wg / e->n_nets);   // (every net's segment padded to whole workgroups: search_kernel.cuh)
-    e->tree_lds = TLDS;
-    e->dyn_lds = L.total;
-    e->waves = NW; e->groups = NG; e->tile_trees = NT; e->spec = SPEC;
-    e->kernel_form = 0;
+    LaunchRecord& r = e->last;
+    r.form = AZG_FORM_PERSISTENT; r.tree_lds = TLDS; r.spec = SPEC;
+    r.waves = NW; r.groups = NG; r.tile_trees = NT;
     // the launch carries its own start / stop events (azg_last_search_ms): stamps of the dispatch packet itself -- event records
     // around it are two more packets in the queue, 7 us per search on a stream of back-to-back searches (measured, config C)
-    hipExtLaunchKernelGGL(kern, grid, block, (unsigned)L.total, e->stream, e->ev0, e->ev1, 0, e->P);
-    e->launch_timed = 1;
+    hipExtLaunchKernelGGL(kern, grid, block, (unsigned)lds, e->stream, e->ev0, e->ev1, 0, e->P);
+    r.timed = 1;
     return hipGetLastError();
 }
 
@@ -82,22 +72,11 @@ static hipError_t launch_t(azg_engine* e) {
 // AZG_WAVES=4|8, AZG_GROUPS=1|2 force a shape (tests).
 template <int ENV, int HP, int NREG>
 static hipError_t launch(azg_engine* e) {
-    const int ns = e->cfg.n_sims;
-    // LDS trees: <= 16 children per node; 8-bit ids / 16-bit counts up to 255 records, 9-bit ids / 11-bit counts up to 511
-    // (node counts: the root's is the largest, carried count + n_sims)
-    int ts = TS_GLOBAL;
-    const long nmax = (long)e->carry_max + ns + 2;
-    e->lds_exit = AZG_LDS_EXIT_CHILDREN;          // (what azg_search_info reports when the trees end up in global memory)
-    if (e->Kp == 16) {
-        e->lds_exit = AZG_LDS_EXIT_RECORDS;
-        if (e->R <= 255 && nmax < 65536) ts = TS_LDS8;
-        else if (e->R <= 511 && nmax < 2048) ts = TS_LDS9;
-        if (ts != TS_GLOBAL) e->lds_exit = AZG_LDS_EXIT_SIZE;   // from here on only the CU's 160 KB can push them out
-    }
     // Trees of 256 .. 511 records stay in LDS (9-bit ids) for the squashed-Normal / discrete heads of networks up to 256 wide; the
     // mixture head's and the wide networks' kernels exist for 8-bit ids and for global trees only (round 6: 32 instantiations fewer)
-    if (ts == TS_LDS9 && (HP >= 512 || e->P.ncomp >= 2)) { ts = TS_GLOBAL; e->lds_exit = AZG_LDS_EXIT_RECORDS; }
-    if (e->opt.force_global_tree) { ts = TS_GLOBAL; e->lds_exit = AZG_LDS_EXIT_FORCED; }
+    const TreeStorage st = azg_tree_storage(e, HP < 512 && e->P.ncomp < 2);
+    const int ts = st.ts;
+    e->last.lds_exit = st.lds_exit;
     // (Continuous mode only.  The discrete family's 8-wave shapes were measured slower than its 4-wave ones -- CartPole, 8192 trees,
     // 2x256: 1.03 ms against 0.99 ms per search, and they were the only kernels of the family that spilled registers -- and are gone.)
     if constexpr (HP == 256 && NREG == 1 && EnvFamily<ENV>::CONT) {
@@ -137,36 +116,22 @@ static hipError_t launch(azg_engine* e) {
             if (rc != hipErrorInvalidConfiguration) return rc;
         }
     }
+    if (ts != TS_GLOBAL) e->last.lds_exit = AZG_LDS_EXIT_SIZE;   // (the LDS variants do not fit the CU's 160 KB)
     return launch_t<ENV, HP, NREG, TS_GLOBAL, 4, 1>(e);
 }
 
-// hidden widths (padded) up to 128
-template <int ENV>
-static hipError_t dispatch_small(azg_engine* e) {
+// hidden widths (padded) 64 and 128, or (WIDE) 256 and up (one or two hidden->hidden layers are kept in registers; deeper trunks
+// stream their weights from L2: any depth)
+template <int ENV, bool WIDE>
+hipError_t azg_persistent_search(azg_engine* e) {
     const int HP = e->HP, NR = e->nreg;
-    // (one or two hidden->hidden layers are kept in registers; deeper trunks stream their weights from L2: any depth)
-    if (HP == 64) {
-        if (NR == 1) return launch<ENV, 64, 1>(e);
-        if (NR == 2) return launch<ENV, 64, 2>(e);
-        return launch<ENV, 64, 0>(e);
-    }
-    if (HP == 128) {
-        if (NR == 1) return launch<ENV, 128, 1>(e);
-        if (NR == 2) return launch<ENV, 128, 2>(e);
-        return launch<ENV, 128, 0>(e);
+    if constexpr (!WIDE) {
+        if (HP == 64) return NR == 1 ? launch<ENV, 64, 1>(e) : NR == 2 ? launch<ENV, 64, 2>(e) : launch<ENV, 64, 0>(e);
+        if (HP == 128) return NR == 1 ? launch<ENV, 128, 1>(e) : NR == 2 ? launch<ENV, 128, 2>(e) : launch<ENV, 128, 0>(e);
+    } else {
+        if (HP == 256) return NR == 1 ? launch<ENV, 256, 1>(e) : launch<ENV, 256, 0>(e);
+        if (HP == 512) return launch<ENV, 512, 0>(e);
+        if (HP == 1024) return launch<ENV, 1024, 0>(e);
     }
     return hipErrorInvalidValue;
 }
-// 256 and wider
-template <int ENV>
-static hipError_t dispatch_large(azg_engine* e) {
-    const int HP = e->HP, NR = e->nreg;
-    if (HP == 256) {
-        if (NR == 1) return launch<ENV, 256, 1>(e);
-        return launch<ENV, 256, 0>(e);
-    }
-    if (HP == 512) return launch<ENV, 512, 0>(e);
-    if (HP == 1024) return launch<ENV, 1024, 0>(e);
-    return hipErrorInvalidValue;
-}
-

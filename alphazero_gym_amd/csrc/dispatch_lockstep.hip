@@ -1,4 +1,4 @@
-// lock-step path for wide networks, both environments
+// lock-step path for wide networks, the CartPole and Pendulum families
 #include "ls_dispatch.cuh"
-hipError_t azg_ls_dispatch_cartpole(azg_engine* e) { return ls_dispatch<AZG_ENV_CARTPOLE>(e); }
-hipError_t azg_ls_dispatch_pendulum(azg_engine* e) { return ls_dispatch<AZG_ENV_PENDULUM_V1>(e); }
+template hipError_t azg_lockstep_search<AZG_ENV_CARTPOLE>(azg_engine*);
+template hipError_t azg_lockstep_search<AZG_ENV_PENDULUM_V1>(azg_engine*);

@@ -1,6 +1,4 @@
 // persistent search kernels, MountainCarContinuous (continuous MCTS whose traces can end in terminal nodes), all hidden widths
 #include "dispatch.cuh"
-hipError_t azg_dispatch_mcc(azg_engine* e) {
-    hipError_t rc = dispatch_small<AZG_ENV_MOUNTAINCAR_CONT>(e);
-    return rc == hipErrorInvalidValue ? dispatch_large<AZG_ENV_MOUNTAINCAR_CONT>(e) : rc;
-}
+template hipError_t azg_persistent_search<AZG_ENV_MOUNTAINCAR_CONT, false>(azg_engine*);
+template hipError_t azg_persistent_search<AZG_ENV_MOUNTAINCAR_CONT, true>(azg_engine*);

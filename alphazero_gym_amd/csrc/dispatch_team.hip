@@ -1,4 +1,4 @@
-// persistent team kernel for wide networks, both environments
+// persistent team kernel for wide networks, the CartPole and Pendulum families
 #include "team_dispatch.cuh"
-hipError_t azg_team_dispatch_cartpole(azg_engine* e) { return team_dispatch<AZG_ENV_CARTPOLE>(e); }
-hipError_t azg_team_dispatch_pendulum(azg_engine* e) { return team_dispatch<AZG_ENV_PENDULUM_V1>(e); }
+template hipError_t azg_team_search<AZG_ENV_CARTPOLE>(azg_engine*);
+template hipError_t azg_team_search<AZG_ENV_PENDULUM_V1>(azg_engine*);

@@ -1,9 +1,10 @@
-// engine_host.h -- the engine object behind the C ABI and the entry points of the kernel translation units.
-// The persistent search kernels are compiled in several translation units (dispatch_*.hip: one family of template
+// engine_host.h -- the engine object behind the C ABI, the host-side rules every kernel form shares, and the entry points of the
+// kernel translation units.  The search kernels are compiled in several translation units (dispatch_*.hip: one family of template
 // instantiations each) so that the library builds in parallel; azg_engine.hip holds the C ABI and the small kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -25,8 +26,19 @@ struct EngineOptions {
                                // then take the per-layer launches)
     int team_tt;               // AZG_TEAM_TT=32 / 64: only teams of that many trees (default 0: 32, and 64 for batches beyond two 32-tree workgroups per CU)
     long team_spin_limit;      // AZG_TEAM_SPIN_LIMIT=n: polls a team hand-off may wait before the launch gives up (tests: 0)
+    int no_lds_state;          // AZG_NO_LDS_STATE set: discrete LDS trees keep the expanded nodes' env states in the cold records only
 };
 #define AZG_MAX_DEVICES 64    // per-device caches of kernel attributes (host side)
+
+// What the last search ran as: azg_search_resident resets it, the launch fills it in, kernel_name / azg_search_info read it
+struct LaunchRecord {
+    int form = AZG_FORM_NONE;                 // AZG_FORM_*: search_kernel, lock-step launches, team kernel
+    int tree_lds = TS_GLOBAL, spec = 0;       // the kernel's tree storage (TS_*, records.h) and SPEC argument
+    int lds_exit = AZG_LDS_NOT_APPLICABLE;    // AZG_LDS_*: why search_kernel's trees were not LDS-resident (azg_tree_storage)
+    int waves = 0, groups = 0, tile_trees = 0;   // search_kernel: waves / tree groups per workgroup, trees per group (16, or 8 / 4)
+    int team_kc = 0, team_minb = 0, team_tt = 0, team_parts = 0;   // team kernel: chunk length, workgroups per CU, trees per team, launches
+    int timed = 0;                            // the launch recorded ev0 / ev1 itself (hipExtLaunchKernelGGL)
+};
 
 // Where every element of the engine's weight buffer comes from, for one network shape (azg_engine.hip: build_weight_map)
 struct WeightMap {
@@ -43,11 +55,8 @@ struct azg_engine {
     int carry_max;           // largest carried root visit count of the uploaded roots
     int S_env, S_obs, Kmax, Kp, R, nd, tab_n;
     int mlp_ready, HP, n_hidden, n_out, act, nreg;
-    int tree_lds;            // tree storage of the last launch: TS_GLOBAL, TS_LDS8, TS_LDS9 (records.h)
-    int waves, groups, n_cus; // waves / tree groups per workgroup of the last launch; compute units of the device
-    int tile_trees;          // trees per group (= per 16-column MFMA tile) of the last launch: 16, or 8 / 4 (half-filled tiles)
-    int spec;                // the last launch ran a compile-time specialised kernel (search_kernel's SPEC argument)
-    size_t dyn_lds;          // dynamic LDS bytes per workgroup
+    int n_cus;               // compute units of the device
+    LaunchRecord last;       // what the last search ran as
     float ls_min, ls_max;
     hipStream_t stream;
     hipEvent_t ev0, ev1;
@@ -78,12 +87,6 @@ struct azg_engine {
     int team_pending;        // a team kernel has been launched since its abort word was last read
     int team_fallbacks;      // searches it gave up on (redone by the per-layer launches)
     uint32_t team_search_idx;
-    int team_tt;             // trees per team of the last team launch (32 or 64)
-    int team_parts;          // launches the last team search was cut into (batches beyond the widest form)
-    int team_kc, team_minb;  // the team kernel form of the last launch (chunk length, workgroups per CU)
-    int launch_timed;        // the last search's launch recorded ev0 / ev1 itself (hipExtLaunchKernelGGL)
-    int kernel_form;         // what the last search ran as: 0 search_kernel, 1 lock-step launches, 2 team kernel
-    int lds_exit;            // AZG_LDS_*: why the last search's trees were not LDS-resident (dispatch.cuh: launch)
     int lds_warned;          // the one stderr line about it has been printed
     LockStep ls;             // lock-step path for wide networks (lockstep.cuh)
     std::vector<void*> ls_allocs;
@@ -110,19 +113,66 @@ static inline long azg_padded_trees(const azg_engine* e, int tpw) {
     return (long)e->n_nets * ((T + tpw - 1) / tpw * tpw);
 }
 
-// one search of all trees on e->stream with the kernel variant that fits (dispatch.cuh); hipErrorInvalidValue: no such variant
-hipError_t azg_dispatch_cartpole(azg_engine* e);
-hipError_t azg_dispatch_pendulum_small(azg_engine* e);   // hidden width (padded) <= 128
-hipError_t azg_dispatch_pendulum_large(azg_engine* e);   // 256 and wider
-hipError_t azg_dispatch_acrobot(azg_engine* e);          // Acrobot-v1 (discrete MCTS, six network inputs), all widths, one-launch kernels only
-hipError_t azg_dispatch_mcc(azg_engine* e);              // MountainCarContinuous (continuous MCTS with terminal nodes), all widths
-hipError_t azg_ls_dispatch_mcc(azg_engine* e);
-hipError_t azg_team_dispatch_mcc(azg_engine* e);
-hipError_t azg_ls_dispatch_cartpole(azg_engine* e);      // lock-step path (lockstep.cuh), buffers prepared by the caller
-hipError_t azg_ls_dispatch_pendulum(azg_engine* e);
-// the same search as ONE persistent launch (team.cuh); hipErrorNotReady: its workgroups cannot all be resident, use the launches
-hipError_t azg_team_dispatch_cartpole(azg_engine* e);
-hipError_t azg_team_dispatch_pendulum(azg_engine* e);
+// The kernels' environment family, their ENV template argument (env.cuh: EnvFamily): 0 CartPole / MountainCar, 5 Acrobot,
+// 4 MountainCarContinuous, 2 both Pendulum versions
+static inline int azg_kernel_env(const azg_config& c) {
+    if (c.mode == AZG_MODE_DISCRETE) return c.env_id == AZG_ENV_ACROBOT ? AZG_ENV_ACROBOT : AZG_ENV_CARTPOLE;
+    return c.env_id == AZG_ENV_MOUNTAINCAR_CONT ? AZG_ENV_MOUNTAINCAR_CONT : AZG_ENV_PENDULUM_V1;
+}
+
+// Where a search's trees live, and why not in LDS.  LDS trees: <= 16 children per node; 8-bit ids / 16-bit counts up to 255 records,
+// 9-bit ids / 11-bit counts up to 511 (the root's count is the largest: carried + n_sims).  lds9: the form has 9-bit-id kernels.
+// (Whether the workgroup's LDS plan fits the CU's 160 KB, AZG_LDS_EXIT_SIZE, is found out by the launch.)
+struct TreeStorage { int ts, lds_exit; };
+static inline TreeStorage azg_tree_storage(const azg_engine* e, bool lds9) {
+    const long nmax = (long)e->carry_max + e->cfg.n_sims + 2;
+    if (e->opt.force_global_tree) return {TS_GLOBAL, AZG_LDS_EXIT_FORCED};
+    if (e->Kp != 16) return {TS_GLOBAL, AZG_LDS_EXIT_CHILDREN};
+    if (e->R <= 255) return nmax < 65536 ? TreeStorage{TS_LDS8, AZG_LDS_RESIDENT} : TreeStorage{TS_GLOBAL, AZG_LDS_EXIT_COUNTS};
+    if (e->R > 511 || !lds9) return {TS_GLOBAL, AZG_LDS_EXIT_RECORDS};
+    return nmax < 2048 ? TreeStorage{TS_LDS9, AZG_LDS_RESIDENT} : TreeStorage{TS_GLOBAL, AZG_LDS_EXIT_COUNTS};
+}
+
+// Host-side attributes of one kernel, a static next to its launch.  Per device (the dynamic-LDS attribute belongs to the device's copy
+// of the kernel) and atomic: engines on several devices or host threads may share a kernel.
+struct KernelAttrs {
+    std::atomic<int> static_lds{-1};
+    std::atomic<size_t> dyn_lds[AZG_MAX_DEVICES] = {};   // dynamic LDS last set on the device (0: never)
+    std::atomic<int> per_cu[AZG_MAX_DEVICES] = {};       // workgroups per CU at that dynamic LDS (0: not asked)
+
+    hipError_t static_bytes(const void* kern, int* bytes) {
+        if ((*bytes = static_lds.load(std::memory_order_relaxed)) >= 0) return hipSuccess;
+        hipFuncAttributes fa;
+        hipError_t rc = hipFuncGetAttributes(&fa, kern);
+        if (rc == hipSuccess) static_lds.store(*bytes = (int)fa.sharedSizeBytes, std::memory_order_relaxed);
+        return rc;
+    }
+    // lets launches on the engine's device take `bytes` of dynamic LDS (hipFuncSetAttribute only when that differs from the last value set)
+    hipError_t set_dyn_lds(const azg_engine* e, const void* kern, size_t bytes) {
+        std::atomic<size_t>& last = dyn_lds[e->cfg.device_id % AZG_MAX_DEVICES];
+        if (last.load(std::memory_order_relaxed) == bytes) return hipSuccess;
+        hipError_t rc = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (rc == hipSuccess) last.store(bytes, std::memory_order_relaxed);
+        return rc;
+    }
+    // set_dyn_lds, then the workgroups of `threads` threads that fit a CU with `bytes` of dynamic LDS each
+    hipError_t occupancy(const azg_engine* e, const void* kern, int threads, size_t bytes, int* blocks) {
+        std::atomic<int>& cached = per_cu[e->cfg.device_id % AZG_MAX_DEVICES];
+        *blocks = cached.load(std::memory_order_relaxed);
+        if (*blocks > 0 && dyn_lds[e->cfg.device_id % AZG_MAX_DEVICES].load(std::memory_order_relaxed) == bytes) return hipSuccess;
+        hipError_t rc = set_dyn_lds(e, kern, bytes);
+        if (rc == hipSuccess) rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, kern, threads, bytes);
+        if (rc == hipSuccess) cached.store(*blocks, std::memory_order_relaxed);
+        return rc;
+    }
+};
+
+// One search of all trees on e->stream with the kernels of family ENV (azg_kernel_env), by path; defined in the headers named, instantiated
+// in the dispatch_*.hip translation units.  hipErrorInvalidValue: no kernel for this width; hipErrorNotReady (team kernel): its workgroups
+// cannot all be resident, use the per-layer launches.
+template <int ENV, bool WIDE> hipError_t azg_persistent_search(azg_engine* e);   // search_kernel, widths up to 128 / 256 and up (dispatch.cuh)
+template <int ENV> hipError_t azg_lockstep_search(azg_engine* e);   // wide networks: the team kernel, else per-layer launches (ls_dispatch.cuh)
+template <int ENV> hipError_t azg_team_search(azg_engine* e);       // (team_dispatch.cuh)
 // the team kernel's forms for more than two 32-tree workgroups per CU (config E's network; team_dispatch.cuh); dry: residency check only
 hipError_t azg_team_wide_forms(azg_engine* e, int g_base, int G, bool dry, bool common, bool t32, bool t64);
 // batched network inference of n observations (device pointers) on e->stream (mlp_eval.cuh)

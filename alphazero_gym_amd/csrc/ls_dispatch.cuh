@@ -1,8 +1,5 @@
-// ls_dispatch.cuh -- host-side launch sequence of the lock-step path (included by dispatch_lockstep.hip).
+// ls_dispatch.cuh -- host-side launch sequence of the lock-step path (included by dispatch_lockstep.hip and dispatch_mcc_wide.hip).
 #pragma once
-#include <atomic>
-#include <cstdlib>
-#include <cstring>
 
 #include "engine_host.h"
 #include "lockstep.cuh"
@@ -23,8 +20,9 @@ static hipError_t ls_enqueue(azg_engine* e, hipStream_t st) {
     // two stages of A (4 tiles) + B (2 groups); the weights-direct tile stages the activations only (and passes the head chain through
     // the first TG * 64 entries)
     const size_t tiled_bytes = LS_LAYER_WD ? (size_t)2 * 2 * LS_LAYER_KC * 64 * 16 : (size_t)2 * (4 + 2) * LS_KC * 64 * 16;
-    hipError_t rc = hipFuncSetAttribute((const void*)tkh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tiled_bytes);
-    if (rc == hipSuccess) rc = hipFuncSetAttribute((const void*)tkl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tiled_bytes);
+    static KernelAttrs tkh_attrs, tkl_attrs;
+    hipError_t rc = tkh_attrs.set_dyn_lds(e, (const void*)tkh, tiled_bytes);
+    if (rc == hipSuccess) rc = tkl_attrs.set_dyn_lds(e, (const void*)tkl, tiled_bytes);
     if (rc != hipSuccess) return rc;
     hipLaunchKernelGGL(tk, dim3(G), dim3(256), tab_bytes, st, e->P, e->ls, -2, 0);
     for (int sim = -1; sim < e->cfg.n_sims; ++sim) {
@@ -41,22 +39,17 @@ static hipError_t ls_enqueue(azg_engine* e, hipStream_t st) {
 template <int ENV, int HP, bool GMM>
 static hipError_t ls_run(azg_engine* e) {
     if (e->opt.ls_team) {
-        hipError_t rc = ENV == AZG_ENV_CARTPOLE ? azg_team_dispatch_cartpole(e)
-                                                : (ENV == AZG_ENV_MOUNTAINCAR_CONT ? azg_team_dispatch_mcc(e) : azg_team_dispatch_pendulum(e));
+        hipError_t rc = azg_team_search<ENV>(e);
         if (rc != hipErrorNotReady) return rc;
     }
-    e->kernel_form = 1;
+    e->last.form = AZG_FORM_PER_LAYER;
     return ls_enqueue<ENV, HP, GMM>(e, e->stream);
 }
 
 template <int ENV>
-static hipError_t ls_dispatch(azg_engine* e) {
-    const bool gmm = EnvFamily<ENV>::CONT && e->P.ncomp >= 2;
-    if (e->HP == 512) {
-        if constexpr (EnvFamily<ENV>::CONT) { if (gmm) return ls_run<ENV, 512, true>(e); }
-        return ls_run<ENV, 512, false>(e);
-    }
-    if constexpr (EnvFamily<ENV>::CONT) { if (gmm) return ls_run<ENV, 1024, true>(e); }
-    return ls_run<ENV, 1024, false>(e);
+hipError_t azg_lockstep_search(azg_engine* e) {
+    constexpr bool CONT = EnvFamily<ENV>::CONT;   // (mixture heads: the continuous family only)
+    const bool gmm = CONT && e->P.ncomp >= 2;
+    if (e->HP == 512) return gmm ? ls_run<ENV, 512, CONT>(e) : ls_run<ENV, 512, false>(e);
+    return gmm ? ls_run<ENV, 1024, CONT>(e) : ls_run<ENV, 1024, false>(e);
 }
-

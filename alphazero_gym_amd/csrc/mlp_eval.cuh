@@ -73,10 +73,9 @@ template <int HP>
 static hipError_t mlp_eval_launch(azg_engine* e, const float* obs, int n, float* value, float* dist, float* raw) {
     auto kern = mlp_eval_kernel<HP>;
     const size_t lds = (size_t)2 * HP * 64;
-    if (lds > 48 * 1024) {
-        hipError_t rc = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (rc != hipSuccess) return rc;
-    }
+    static KernelAttrs attrs;
+    hipError_t rc = attrs.set_dyn_lds(e, (const void*)kern, lds);
+    if (rc != hipSuccess) return rc;
     hipLaunchKernelGGL(kern, dim3((n + 15) / 16), dim3(256), lds, e->stream, e->P, obs, n, e->S_obs, e->nd, value, dist, raw);
     return hipGetLastError();
 }

@@ -1,7 +1,6 @@
-// team_dispatch.cuh -- host-side choice and launch of the persistent team kernel (team.cuh); included by dispatch_team.hip.
+// team_dispatch.cuh -- host-side choice and launch of the persistent team kernel (team.cuh); included by dispatch_team.hip,
+// dispatch_team_wide.hip and dispatch_mcc_wide.hip.
 #pragma once
-#include <atomic>
-#include <cstdlib>
 
 #include "engine_host.h"
 #include "team.cuh"
@@ -30,20 +29,10 @@ static hipError_t team_launch_form(azg_engine* e, bool wider_form_exists, int g_
     const size_t lds = team_tree_off(e->tab_n, e->cfg.n_sims, KC, TGN) + (size_t)TPW * (team_tree_bytes(e->R, CONT, TLDS) + (lds_cold ? team_cold_bytes(e->R) : 0));
     if ((lds + 1024) * MINB > 160 * 1024) return hipErrorNotReady;
     auto kern = ls_team_kernel<ENV, HP, GMM, TLDS, KC, MINB, SPEC, TT>;
-    // (per device: the dynamic-LDS attribute belongs to the device's copy of the kernel)
-    static std::atomic<int> per_cu_caches[AZG_MAX_DEVICES];
-    static std::atomic<size_t> lds_caches[AZG_MAX_DEVICES];
-    std::atomic<int>& per_cu_cache = per_cu_caches[e->cfg.device_id % AZG_MAX_DEVICES];
-    std::atomic<size_t>& lds_cache = lds_caches[e->cfg.device_id % AZG_MAX_DEVICES];
-    int per_cu = per_cu_cache.load(std::memory_order_relaxed);
-    if (per_cu <= 0 || lds != lds_cache.load(std::memory_order_relaxed)) {
-        hipError_t rc = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (rc != hipSuccess) return rc;
-        rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, 256, lds);
-        if (rc != hipSuccess) return rc;
-        per_cu_cache.store(per_cu, std::memory_order_relaxed);
-        lds_cache.store(lds, std::memory_order_relaxed);
-    }
+    static KernelAttrs attrs;
+    int per_cu = 0;
+    hipError_t rc = attrs.occupancy(e, (const void*)kern, 256, lds, &per_cu);
+    if (rc != hipSuccess) return rc;
     // the occupancy query can answer one block per CU too many where the SGPR file is what limits residency; for 256-thread
     // blocks that limit is floor(800 / (ceil(sgpr / 16) * 16 + 16)) >= 6 whatever the kernel's sgpr count (<= 112): answers
     // up to 6 are safe to take as they are (and every wait in the kernel is bounded should this ever be wrong)
@@ -51,7 +40,7 @@ static hipError_t team_launch_form(azg_engine* e, bool wider_form_exists, int g_
     if (wider_form_exists && usable > MINB) usable = MINB;   // (the next form takes the larger batches)
     if (usable < 1 || (long)TQ * NU > (long)usable * e->n_cus) return hipErrorNotReady;
     if (dry) return hipSuccess;   // (residency check only: team_launch asks about every part of a two-part search before it launches the first)
-    hipError_t rc = g_base == 0 ? hipMemsetAsync(e->d_team_cnt, 0, e->team_cnt_bytes, e->stream) : hipSuccess;
+    rc = g_base == 0 ? hipMemsetAsync(e->d_team_cnt, 0, e->team_cnt_bytes, e->stream) : hipSuccess;
     if (rc != hipSuccess) return rc;
     TeamCtl T;
     T.cnt = e->d_team_cnt;
@@ -59,10 +48,9 @@ static hipError_t team_launch_form(azg_engine* e, bool wider_form_exists, int g_
     T.spin_limit = (unsigned)e->opt.team_spin_limit;
     hipLaunchKernelGGL(kern, dim3(TQ * NU), dim3(256), lds, e->stream, e->P, e->ls, T, TQ, g_base);
     e->team_pending = 1;
-    e->kernel_form = 2;
-    e->tree_lds = TLDS;
-    e->dyn_lds = lds;
-    e->team_kc = KC; e->team_minb = MINB; e->spec = SPEC; e->team_tt = TT;
+    LaunchRecord& r = e->last;
+    r.form = AZG_FORM_TEAM; r.tree_lds = TLDS; r.spec = SPEC;
+    r.team_kc = KC; r.team_minb = MINB; r.team_tt = TT;
     return hipGetLastError();
 }
 
@@ -116,7 +104,7 @@ static hipError_t team_launch(azg_engine* e) {
     constexpr bool WIDE = HP == 1024 && !GMM && TLDS == TS_LDS8 && ENV == AZG_ENV_PENDULUM_V1;
     const int G = (e->cfg.n_trees + TREES_PER_WG - 1) / TREES_PER_WG;
     const int G_MAX = 3 * e->n_cus / (HP / 64) * 4;                      // 64-tree teams, three workgroups on every CU
-    e->team_parts = 1;
+    e->last.team_parts = 1;
     if (!WIDE || G <= G_MAX || !e->opt.team_wide || e->opt.team_tt == 32) return team_launch_part<ENV, HP, GMM, TLDS>(e, 0, G);
     const int parts = (G + G_MAX - 1) / G_MAX, per = ((G + parts - 1) / parts + 3) / 4 * 4;   // (whole 64-tree teams)
     if (parts > 2) return hipErrorNotReady;
@@ -126,33 +114,26 @@ static hipError_t team_launch(azg_engine* e) {
     for (int g = 0; g < G && rc == hipSuccess; g += per) rc = team_launch_part<ENV, HP, GMM, TLDS>(e, g, G - g < per ? G - g : per, true);
     if (rc != hipSuccess) return rc;
     for (int g = 0; g < G && rc == hipSuccess; g += per) rc = team_launch_part<ENV, HP, GMM, TLDS>(e, g, G - g < per ? G - g : per);
-    e->team_parts = parts;
+    e->last.team_parts = parts;
     return rc;
 }
 
-// trees in the workgroups' LDS when they fit (same rule as the persistent search kernel's), else in global memory
+// trees in the workgroups' LDS when they fit (azg_tree_storage: the team kernel has 9-bit-id variants for every head), else in global memory
 template <int ENV, int HP, bool GMM>
 static hipError_t team_storage(azg_engine* e) {
-    const long nmax = (long)e->carry_max + e->cfg.n_sims + 2;
+    const int ts = azg_tree_storage(e, true).ts;
     hipError_t rc = hipErrorNotReady;
-    if (e->Kp == 16 && !e->opt.force_global_tree) {
-        if (e->R <= 255 && nmax < 65536) rc = team_launch<ENV, HP, GMM, TS_LDS8>(e);
-        else if (e->R <= 511 && nmax < 2048) rc = team_launch<ENV, HP, GMM, TS_LDS9>(e);
-    }
+    if (ts == TS_LDS8) rc = team_launch<ENV, HP, GMM, TS_LDS8>(e);
+    if (ts == TS_LDS9) rc = team_launch<ENV, HP, GMM, TS_LDS9>(e);
     if (rc == hipErrorNotReady) rc = team_launch<ENV, HP, GMM, TS_GLOBAL>(e);
     return rc;
 }
 
 template <int ENV>
-static hipError_t team_dispatch(azg_engine* e) {
-    const bool gmm = EnvFamily<ENV>::CONT && e->P.ncomp >= 2;
-    if (e->HP == 512) {
-        if constexpr (EnvFamily<ENV>::CONT) { if (gmm) return team_storage<ENV, 512, true>(e); }
-        return team_storage<ENV, 512, false>(e);
-    }
-    if (e->HP == 1024) {
-        if constexpr (EnvFamily<ENV>::CONT) { if (gmm) return team_storage<ENV, 1024, true>(e); }
-        return team_storage<ENV, 1024, false>(e);
-    }
+hipError_t azg_team_search(azg_engine* e) {
+    constexpr bool CONT = EnvFamily<ENV>::CONT;   // (mixture heads: the continuous family only)
+    const bool gmm = CONT && e->P.ncomp >= 2;
+    if (e->HP == 512) return gmm ? team_storage<ENV, 512, CONT>(e) : team_storage<ENV, 512, false>(e);
+    if (e->HP == 1024) return gmm ? team_storage<ENV, 1024, CONT>(e) : team_storage<ENV, 1024, false>(e);
     return hipErrorNotReady;
 }

@@ -176,8 +176,12 @@ enum { AZG_FORM_NONE = -1, AZG_FORM_PERSISTENT = 0 /* one launch = a whole searc
        AZG_FORM_PER_LAYER = 1 /* wide networks: one launch per layer and tree phase of every simulation step */,
        AZG_FORM_TEAM = 2 /* wide networks: one persistent launch, the batch cut into teams of workgroups (ls_team_kernel) */ };
 enum { AZG_TREES_GLOBAL = 0, AZG_TREES_LDS8 = 1 /* <= 255 records, 8-bit ids */, AZG_TREES_LDS9 = 2 /* <= 511 records */ };
-enum { AZG_LDS_RESIDENT = 0, AZG_LDS_EXIT_RECORDS = 1, AZG_LDS_EXIT_CHILDREN = 2, AZG_LDS_EXIT_SIZE = 3, AZG_LDS_EXIT_FORCED = 4 /* AZG_FORCE_GLOBAL_TREE=1 (tests) */,
-       AZG_LDS_NOT_APPLICABLE = 5 /* wide-network forms: the trees live in HBM by design (the team kernel stages its workgroup's two or four trees in LDS) */ };
+enum { AZG_LDS_RESIDENT = 0,
+       AZG_LDS_EXIT_RECORDS = 1 /* more than 511 records per tree; more than 255 for mixture heads and networks >= 512 wide (no 9-bit-id kernels) */,
+       AZG_LDS_EXIT_CHILDREN = 2 /* more than 16 children per node */, AZG_LDS_EXIT_SIZE = 3 /* the workgroup's LDS plan exceeds the CU's 160 KB */,
+       AZG_LDS_EXIT_FORCED = 4 /* AZG_FORCE_GLOBAL_TREE=1 (tests) */,
+       AZG_LDS_NOT_APPLICABLE = 5 /* wide-network forms: the trees live in HBM by design (the team kernel stages its workgroup's two or four trees in LDS) */,
+       AZG_LDS_EXIT_COUNTS = 6 /* the root's visit count (carried + n_sims) overflows the LDS records' counters: 65535 (<= 255 records), 2047 (<= 511) */ };
 typedef struct azg_search_report {
     int32_t struct_size;      /* sizeof(azg_search_report), set by the caller, checked */
     int32_t kernel_form;      /* AZG_FORM_* */

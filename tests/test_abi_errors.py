@@ -139,3 +139,30 @@ def test_search_info_reports_form_and_residency_through_the_abi(capfd, monkeypat
         assert d["team_trees"] == 32 and d["team_parts"] == 1 and d["kernel_name"].startswith("ls_team_kernel<2, 1024")
     e.close()
     assert "LDS residency" not in capfd.readouterr().err
+
+
+@pytest.mark.gpu
+def test_search_info_names_the_residency_limit_that_applied(capfd, monkeypatch):
+    """The two limits besides "more than 511 records": a mixture head has no 9-bit-id kernels, so its trees of 256 .. 511 records leave
+    LDS at 255 records (AZG_LDS_EXIT_RECORDS, and the stderr line says 255); a carried root count of 65536 or more overflows the 8-bit-id
+    records' 16-bit counters (AZG_LDS_EXIT_COUNTS)."""
+    from alphazero_gym_amd import _native
+    monkeypatch.delenv("AZG_QUIET", raising=False)
+    # 300 simulations: 302 records, at most 6 children per node (301^0.3 < 6); 2x256 with three mixture components
+    e = _native.HipEngine(env_id=2, mode=1, n_trees=32, n_sims=300, c_uct=0.05, gamma=1.0, kappa=0.3)
+    e.set_weights(_capi.make_desc(3, [256, 256], 9, "elu", num_components=3), O.make_weights(34, 3, [256, 256], 9))
+    e.search(e.synthetic_roots())
+    assert (e.results()["counts"].sum(1) == 300).all()
+    d = e.search_info()
+    assert d["kernel_form"] == "persistent" and d["tree_storage"] == "global" and d["lds_exit"] == "records" and d["max_records"] == 302
+    e.close()
+    err = capfd.readouterr().err
+    assert "do not fit LDS residency (more than 255 records" in err and "511" not in err
+    # CartPole, 100 simulations (203 records) from roots that carry 70 000 visits
+    e = _native.HipEngine(env_id=0, mode=0, n_trees=32, n_sims=100, c_uct=1.5, gamma=1.0, num_actions=2)
+    e.set_weights(_capi.make_desc(4, [64, 64], 2, "relu"), O.make_weights(34, 4, [64, 64], 2))
+    e.search(e.synthetic_roots(), np.full(32, 70000, dtype=np.int32))
+    d = e.search_info()
+    assert d["kernel_form"] == "persistent" and d["tree_storage"] == "global" and d["lds_exit"] == "counts" and d["max_records"] == 203
+    e.close()
+    assert "do not fit LDS residency (the root's visit count" in capfd.readouterr().err
