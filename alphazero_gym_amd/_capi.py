@@ -103,7 +103,15 @@ SYMBOLS = [
 # entry points a library may lack (the tests' CPU oracle binds SYMBOLS only): bound when present, else the methods that need
 # them raise
 OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device",
-                    "population_selfplay_begin"]
+                    "population_selfplay_begin",
+                    "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
+                    "trainer_backward_step"]
+
+
+class AzgRmsprop(C.Structure):
+    """include/azgym_train.h: azg_rmsprop"""
+    _fields_ = [("struct_size", C.c_int32), ("centered", C.c_int32), ("lr", C.c_double), ("alpha", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("momentum", C.c_double), ("grad_clip", C.c_double)]
 
 
 def bind(lib, prefix):
@@ -159,6 +167,16 @@ def bind(lib, prefix):
         f["set_population_weights_device"].argtypes = [vp, C.POINTER(AzgMlpDesc), C.c_void_p, C.c_size_t, C.c_int32]
     if "population_selfplay_begin" in f:
         f["population_selfplay_begin"].argtypes = [vp, C.POINTER(AzgSelfplayConfig)]
+    if "trainer_create" in f:   # include/azgym_train.h
+        f["trainer_create"].argtypes = [C.c_int32, C.POINTER(AzgMlpDesc), C.c_int32, C.c_int32, C.POINTER(vp)]
+        f["trainer_destroy"].argtypes = [vp]
+        f["trainer_destroy"].restype = None
+        f["trainer_last_error"].argtypes = [vp]
+        f["trainer_last_error"].restype = C.c_char_p
+        f["trainer_param_count"].argtypes = [vp]
+        f["trainer_param_count"].restype = C.c_size_t
+        f["trainer_forward"].argtypes = [vp, vp, vp, C.c_int32, vp]
+        f["trainer_backward_step"].argtypes = [vp, vp, vp, C.c_int32, C.POINTER(AzgRmsprop), vp, vp]
     return f
 
 
@@ -535,6 +553,60 @@ def _selfplay_methods():
 
 
 _selfplay_methods()
+
+
+def rmsprop_opt(lr, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, centered=False, grad_clip=0.0):
+    """azg_rmsprop with torch.optim.RMSprop's keyword names and defaults."""
+    o = AzgRmsprop()
+    o.struct_size = C.sizeof(AzgRmsprop)
+    o.centered = int(bool(centered))
+    o.lr, o.alpha, o.eps, o.weight_decay = float(lr), float(alpha), float(eps), float(weight_decay)
+    o.momentum, o.grad_clip = float(momentum), float(grad_clip)
+    return o
+
+
+class Trainer:
+    """One ``azg_trainer*`` (include/azgym_train.h): forward and backward + RMSprop step of n_nets nets of shape ``desc`` in two
+    launches.  Every array argument is a device address (int) of float32 memory on the trainer's GPU, complete when the call is
+    made; outputs are complete when it returns."""
+
+    def __init__(self, fns, desc, n_nets, max_batch, device_id=0):
+        if "trainer_create" not in fns:
+            raise NotImplementedError("this engine library has no azg_trainer_* entry points")
+        self._f = fns
+        self._h = C.c_void_p()
+        rc = fns["trainer_create"](int(device_id), C.byref(desc) if desc is not None else None, int(n_nets), int(max_batch),
+                                   C.byref(self._h))
+        if rc != 0:
+            raise EngineError(rc, (fns["trainer_last_error"](None) or b"").decode())
+        self.n_nets, self.max_batch, self.device_id = int(n_nets), int(max_batch), int(device_id)
+        self.n_params = int(fns["trainer_param_count"](self._h))
+        self.n_raw = 1 + desc.n_dist
+        self.in_dim = desc.in_dim
+
+    def _check(self, rc):
+        if rc != 0:
+            raise EngineError(rc, (self._f["trainer_last_error"](self._h) or b"").decode())
+
+    def close(self):
+        if self._h:
+            self._f["trainer_destroy"](self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def forward(self, params, obs, n_rows, raw):
+        """azg_trainer_forward: params [n_nets, P], obs [n_nets, n_rows, in_dim] -> raw [n_nets, n_rows, 1 + n_dist]."""
+        self._check(self._f["trainer_forward"](self._h, params or None, obs or None, int(n_rows), raw or None))
+
+    def backward_step(self, params, d_raw, n_rows, opt, square_avg, grads=None):
+        """azg_trainer_backward_step: back from d_raw, RMSprop update of params / square_avg in place; grads (optional) filled."""
+        self._check(self._f["trainer_backward_step"](self._h, params or None, d_raw or None, int(n_rows),
+                                                     C.byref(opt) if opt is not None else None, square_avg or None, grads or None))
 
 
 def pw_table(c_pw, kappa, n):

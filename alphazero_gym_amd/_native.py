@@ -133,6 +133,13 @@ class HipEngine(_capi.Engine):
         return d
 
 
+class HipTrainer(_capi.Trainer):
+    """Population trainer on one MI355X (include/azgym_train.h)."""
+
+    def __init__(self, desc, n_nets, max_batch, device_id=0):
+        super().__init__(fns(), desc, n_nets, max_batch, device_id)
+
+
 def math_selftest(fn_id, x, device_id=0):
     import numpy as np
 

@@ -1,4 +1,5 @@
-"""Training losses (PyTorch autograd; the optimiser step is the one part of the stack that stays in PyTorch-ROCm).
+"""Training losses (PyTorch autograd; for single agents the whole optimiser step stays in PyTorch-ROCm, for populations only these losses do:
+trunk, heads, their backward pass and the RMSprop step of K nets are HIP kernels, agent/population_trainer.py).
 Semantics follow alphazero/agent/losses.py: AlphaZeroLoss 30-151, A0CLoss 154-326, A0CLossTuned 329-500."""
 from typing import Dict, Union
 

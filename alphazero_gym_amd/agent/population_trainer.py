@@ -1,0 +1,359 @@
+"""Population training: one minibatch optimiser step of K agents' nets in two HIP launches (include/azgym_train.h), with no Python
+loop over the nets.
+
+The K policies' parameters live in ONE float32 tensor ``flat[K, P]`` (``bind_flat``; state_dict order, the order of
+``_capi.policy_tensors``) that the trainer's kernels update in place and the search engine's gather reads directly
+(``PopulationMCTS.upload_flat``).  The boundary between HIP and PyTorch is the heads' raw output ``raw[K, B, 1 + n_dist]``:
+trunk, heads, their backward pass and the RMSprop step are kernels; the losses (``population_loss``: ``DiscreteAgent._loss`` /
+``ContinuousAgent._loss`` restated once for a leading K axis, the tuned alpha's Adam step included) stay in PyTorch and give
+``d_raw`` by autograd on those small tensors.  The single-agent path (``Agent.update``) is untouched.
+"""
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from .. import _capi
+from ..network.policies import DiagonalGMMPolicy, DiagonalNormalPolicy, DiscretePolicy
+from .losses import A0CLoss, A0CLossTuned, AlphaZeroLoss
+
+
+def bind_flat(policies: Sequence[Any]) -> Tuple[Any, torch.Tensor]:
+    """(desc, flat[K, P]): one float32 tensor on the policies' device holding every policy's parameters, row k = policy k in
+    ``_capi.policy_tensors`` order (= ``_capi.policy_blob``'s blob).  Every parameter is re-pointed at a view of its row, values
+    preserved, so ``state_dict()``, checkpoints and the agents' own torch optimisers keep working on the same storage."""
+    policies = list(policies)
+    if not policies:
+        raise ValueError("bind_flat needs at least one policy")
+    parts = [_capi.policy_tensors(p) for p in policies]
+    desc, first = parts[0]
+    shapes = [tuple(t.shape) for t in first]
+    device = first[0].device
+    for d_, tensors in parts:
+        if [tuple(t.shape) for t in tensors] != shapes or bytes(d_) != bytes(desc):
+            raise ValueError("bind_flat: every policy must have the same network shape, activation and head settings")
+        if any(t.dtype != torch.float32 or t.device != device for t in tensors):
+            raise ValueError("bind_flat: every parameter must be float32 on one device")
+    flat = torch.empty((len(policies), sum(t.numel() for t in first)), dtype=torch.float32, device=device)
+    with torch.no_grad():
+        for k, (_, tensors) in enumerate(parts):
+            off = 0
+            for t in tensors:
+                row = flat[k, off:off + t.numel()]
+                row.copy_(t.detach().reshape(-1))
+                t.data = row.view_as(t)
+                off += t.numel()
+    return desc, flat
+
+
+def _log_probs_entropy(policy, head, actions):
+    """``policy.get_train_data``'s log-probs and entropy from the distribution head's raw output ``head`` [N, n_dist] and
+    ``actions`` [N, A], N = K * B rows of all nets: policies.py's own lines on a longer batch, so every element and every
+    per-row sum is computed as the single agent computes it."""
+    if isinstance(policy, DiscretePolicy):
+        num_actions = actions.shape[1]
+        pi_hat = torch.distributions.Categorical(logits=head.unsqueeze(dim=1).repeat((1, num_actions, 1)))
+        return pi_hat.log_prob(actions), pi_hat.entropy()
+    if isinstance(policy, DiagonalNormalPolicy):
+        mu, log_std = head.chunk(2, dim=-1)
+        log_std = torch.clamp(log_std, min=policy.log_param_min, max=policy.log_param_max)
+        log_probs = policy._dist(mu, log_std.exp()).log_prob(actions)
+        return log_probs, -log_probs.mean(dim=-1)
+    if isinstance(policy, DiagonalGMMPolicy):
+        C_ = policy.num_components
+        dist_params = head[..., :C_ * 2 * policy.action_dim].reshape(head.shape[0], -1)
+        log_coeff = head[..., -C_:]
+        mu, log_std = dist_params.chunk(2, dim=-1)
+        log_std = torch.clamp(log_std, min=policy.log_param_min, max=policy.log_param_max)
+        A = actions.shape[-1]
+        mu = mu.unsqueeze(dim=1).expand((-1, A, -1))
+        sigma = log_std.exp().unsqueeze(dim=1).expand((-1, A, -1))
+        log_mix = torch.log_softmax(log_coeff, dim=-1).unsqueeze(dim=1).expand((-1, A, -1))
+        comp_lp = policy._component(mu, sigma).log_prob(actions.unsqueeze(-1))
+        log_probs = torch.logsumexp(comp_lp + log_mix, dim=-1)
+        return log_probs, -log_probs.mean(dim=-1)
+    raise ValueError(f"population_loss: {type(policy).__name__} heads are not supported")
+
+
+def _reduce(x, reduction):
+    """Per-net reduction of [K, ...] over everything but K (losses.py: x.mean() / x.sum() of one net's tensor)."""
+    dims = tuple(range(1, x.dim()))
+    return x.mean(dim=dims) if reduction == "mean" else x.sum(dim=dims)
+
+
+def population_terms(policy, loss, raw, actions, counts, values) -> Dict[str, torch.Tensor]:
+    """The losses' summands before any reduction over the batch: "policy" [K, B] (cross-entropy per row, or the A0C policy term
+    sum_i (log pi_i - tau log n_i).detach() * log pi_i per row), "value" [K, B, 1] (squared errors) and, for the A0C losses,
+    "entropy" [K, B] or [K, B, A] and the "log_probs" [K, B, A] they come from.  Element for element what the single agent's code computes (the rows of all nets go through
+    policies.py's and losses.py's own operations as one batch of K * B rows); only the reductions over B that follow see a
+    tensor of another shape."""
+    K, B = raw.shape[0], raw.shape[1]
+    V_hat, head = raw[..., :1], raw[..., 1:]
+    value = F.mse_loss(V_hat, values, reduction="none")
+    if type(loss) is AlphaZeroLoss:
+        if not isinstance(policy, DiscretePolicy):
+            raise ValueError("population_loss: AlphaZeroLoss needs a discrete policy")
+        if loss.reduction not in ("mean", "sum"):
+            raise ValueError("population_loss: reduction must be 'mean' or 'sum'")
+        logits = torch.distributions.Categorical(logits=head.reshape(K * B, -1)).logits
+        target = F.softmax(counts.reshape(K * B, -1), dim=-1).argmax(dim=1)
+        return {"policy": F.cross_entropy(logits, target, reduction="none").reshape(K, B), "value": value}
+    if type(loss) not in (A0CLoss, A0CLossTuned):
+        raise ValueError(f"population_loss: {type(loss).__name__} is not supported")
+    A = actions.shape[-1]
+    log_probs, entropy = _log_probs_entropy(policy, head.reshape(K * B, -1), actions.reshape(K * B, A))
+    counts = counts.reshape(K * B, A)
+    if isinstance(policy, DiscretePolicy):
+        counts = counts + 1   # keeps log(counts) finite (agents.py:364)
+    with torch.no_grad():
+        log_diff = log_probs - loss.tau * torch.log(counts)
+    per_row = torch.einsum("ni, ni -> n", log_diff, log_probs).reshape(K, B)
+    return {"policy": per_row, "value": value, "entropy": entropy.reshape((K, B) + entropy.shape[1:]),
+            "log_probs": log_probs.reshape(K, B, A)}
+
+
+def population_loss(policy, loss, raw, actions, counts, values, log_alpha: Optional[torch.Tensor] = None,
+                    alpha_optimizer: Optional[torch.optim.Optimizer] = None) -> Dict[str, torch.Tensor]:
+    """The K-axis form of ``DiscreteAgent._loss`` / ``ContinuousAgent._loss`` from the heads' raw outputs.
+
+    ``policy`` / ``loss``: one of the K policies / loss objects (all nets share head kind, loss class and hyper-parameters);
+    ``raw`` [K, B, 1 + n_dist] (value head first), ``actions`` / ``counts`` [K, B, A], ``values`` [K, B, 1].  With ``A0CLossTuned``,
+    ``log_alpha`` [K] holds every net's own learned temperature and ``alpha_optimizer`` (one Adam over that tensor: Adam is
+    element-wise, so element k is net k's own Adam) takes the step ``A0CLossTuned.forward`` takes.
+    Returns {key: [K] tensor} with the keys of ``Agent.update``'s dictionary; ``out["loss"].sum().backward()`` gives every net's
+    own ``d loss_k / d raw[k]`` (the nets are independent).  ``per_net`` turns it into K dictionaries of floats."""
+    K = raw.shape[0]
+    terms = population_terms(policy, loss, raw, actions, counts, values)
+    policy_loss = loss.policy_coeff * _reduce(terms["policy"], loss.reduction)
+    value_loss = loss.value_coeff * _reduce(terms["value"], loss.reduction)
+    if type(loss) is AlphaZeroLoss:
+        return {"loss": policy_loss + value_loss, "policy_loss": policy_loss, "value_loss": value_loss}
+    entropy = terms["entropy"]
+    if type(loss) is A0CLoss:
+        entropy_loss = loss.alpha * _reduce(entropy, loss.reduction)
+        return {"loss": policy_loss + entropy_loss + value_loss, "policy_loss": policy_loss, "entropy_loss": entropy_loss,
+                "value_loss": value_loss}
+    if log_alpha is None:
+        raise ValueError("population_loss: A0CLossTuned needs log_alpha [K]")
+    alpha = log_alpha.exp()
+    entropy_loss = alpha.detach() * _reduce(entropy, loss.reduction)
+    total = policy_loss + entropy_loss + value_loss
+    # A0CLossTuned._update_alpha for every net at once
+    gap = (entropy - loss.target_entropy).detach()
+    alpha_loss = (alpha.reshape((K,) + (1,) * (gap.dim() - 1)) * gap).mean(dim=tuple(range(1, gap.dim())))
+    if alpha_optimizer is not None:
+        log_alpha.grad = None
+        alpha_loss.sum().backward()
+        if loss.clip:   # clip_grad_norm_ of a one-element parameter, element by element
+            g = log_alpha.grad
+            g.mul_(torch.clamp(loss.clip / (g.abs() + 1e-6), max=1.0))
+        alpha_optimizer.step()
+    return {"loss": total, "policy_loss": policy_loss, "entropy_loss": entropy_loss, "value_loss": value_loss,
+            "alpha_loss": alpha_loss.detach()}
+
+
+def per_net(losses: Dict[str, torch.Tensor]) -> List[Dict[str, float]]:
+    """{key: [K]} -> K dictionaries of floats (one device-to-host copy)."""
+    keys = list(losses)
+    table = torch.stack([losses[k].detach().to(torch.float32) for k in keys]).cpu().tolist()
+    return [{k: table[i][n] for i, k in enumerate(keys)} for n in range(len(table[0]))]
+
+
+def _loss_settings(loss) -> tuple:
+    if type(loss) is AlphaZeroLoss:
+        return (AlphaZeroLoss, loss.policy_coeff, loss.value_coeff, loss.reduction)
+    if type(loss) is A0CLoss:
+        return (A0CLoss, loss.tau, loss.policy_coeff, float(loss.alpha), loss.value_coeff, loss.reduction)
+    if type(loss) is A0CLossTuned:
+        g = loss.optimizer.param_groups[0]
+        return (A0CLossTuned, loss.tau, loss.policy_coeff, loss.value_coeff, loss.reduction, loss.target_entropy, loss.clip,
+                type(loss.optimizer), g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"], g.get("amsgrad", False))
+    raise ValueError(f"PopulationTrainer: loss {type(loss).__name__} is not supported (AlphaZeroLoss, A0CLoss, A0CLossTuned)")
+
+
+def _rmsprop_settings(opt) -> tuple:
+    if type(opt) is not torch.optim.RMSprop:
+        raise ValueError(f"PopulationTrainer: the nets' optimiser must be torch.optim.RMSprop, not {type(opt).__name__}")
+    if len(opt.param_groups) != 1:
+        raise ValueError("PopulationTrainer: one RMSprop parameter group per agent")
+    g = opt.param_groups[0]
+    if g["momentum"] != 0 or g["centered"] or g.get("maximize", False):
+        raise ValueError("PopulationTrainer: RMSprop with momentum, centered or maximize is not supported")
+    return (g["lr"], g["alpha"], g["eps"], g["weight_decay"])
+
+
+class PopulationTrainer:
+    """The optimiser step of K agents of one shape, all at once.  Raises ``ValueError`` naming the reason when the agents cannot be
+    trained here (the caller then keeps the per-agent ``agent.update`` loop): different network shapes, LayerNorm, gradient
+    clipping, an optimiser other than plain RMSprop, different losses or hyper-parameters, parameters not on a GPU.
+
+    Binds the agents' parameters to ``self.flat`` [K, P] (``bind_flat``) and their RMSprop ``square_avg`` state to
+    ``self.square_avg`` [K, P] (state an agent already has is taken over; the agents' torch optimisers keep working on the same
+    storage).  With ``A0CLossTuned`` the learned temperatures live in ``self.log_alpha`` [K] under one Adam; ``export_alpha()``
+    (called by ``close()``) writes them and their Adam state back into the agents' loss objects, which are stale until then.  After ``update`` hand the weights to the search with
+    ``PopulationMCTS.upload_flat(trainer.desc, trainer.flat)``."""
+
+    def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False):
+        self.agents = list(agents)
+        if not self.agents:
+            raise ValueError("PopulationTrainer needs at least one agent")
+        a0 = self.agents[0]
+        K = len(self.agents)
+        if len({type(a.nn) for a in self.agents}) != 1:
+            raise ValueError("PopulationTrainer: every agent must have the same policy class")
+        if not isinstance(a0.nn, (DiscretePolicy, DiagonalNormalPolicy, DiagonalGMMPolicy)):
+            raise ValueError(f"PopulationTrainer: policy {type(a0.nn).__name__} is not supported")
+        if any(a.nn.layernorm for a in self.agents):
+            raise ValueError("PopulationTrainer: LayerNorm trunks are not trained on the device")
+        if any(a.clip for a in self.agents):
+            raise ValueError("PopulationTrainer: grad_clip != 0 is not supported (a per-net global norm needs a pass of its own)")
+        if len({_rmsprop_settings(a.optimizer) for a in self.agents}) != 1:
+            raise ValueError("PopulationTrainer: every agent must have the same RMSprop settings")
+        if len({_loss_settings(a.loss) for a in self.agents}) != 1:
+            raise ValueError("PopulationTrainer: every agent must have the same loss class and hyper-parameters")
+        descs = [_capi.policy_tensors(a.nn) for a in self.agents]
+        if any([tuple(t.shape) for t in ts] != [tuple(t.shape) for t in descs[0][1]] or bytes(d) != bytes(descs[0][0]) for d, ts in descs):
+            raise ValueError("PopulationTrainer: every agent must have the same network shape, activation and head settings")
+        d0 = descs[0][0]
+        hidden = [d0.hidden[i] for i in range(d0.n_hidden)]
+        if not (1 <= d0.n_hidden <= 3 and all(h % 16 == 0 and 16 <= h <= 256 for h in hidden) and d0.in_dim <= 8 and d0.n_dist <= 16):
+            raise ValueError("PopulationTrainer: supported nets have 1-3 hidden layers of widths 16, 32, ... 256, at most 8 inputs and "
+                             "16 distribution outputs")
+        pars = [p for a in self.agents for p in a.nn.parameters()]
+        device = pars[0].device
+        if device.type != "cuda" or any(p.device != device for p in pars):
+            raise ValueError("PopulationTrainer: every parameter must live on one GPU (there is no CPU form of the trainer's kernels)")
+        alpha_states = []
+        if type(a0.loss) is A0CLossTuned:
+            alpha_states = [a.loss.optimizer.state.get(a.loss.log_alpha, {}) for a in self.agents]
+            if any(alpha_states) and (not all(alpha_states) or len({float(s["step"]) for s in alpha_states}) != 1):
+                raise ValueError("PopulationTrainer: the agents' alpha optimisers must have taken the same number of steps")
+        from .. import _native   # raises if libazgym_hip.so is missing
+
+        # the native trainer first: if it cannot be created, the agents are left as they were
+        self.max_batch = int(max_batch)
+        self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0)
+        self.policy, self.loss = a0.nn, a0.loss
+        self.device = device
+        self.desc, self.flat = bind_flat([a.nn for a in self.agents])
+        lr, alpha, eps, wd = _rmsprop_settings(a0.optimizer)
+        self.opt = _capi.rmsprop_opt(lr=lr, alpha=alpha, eps=eps, weight_decay=wd)
+        self.square_avg = torch.zeros_like(self.flat)
+        for k, a in enumerate(self.agents):
+            off = 0
+            for p in _capi.policy_tensors(a.nn)[1]:
+                view = self.square_avg[k, off:off + p.numel()].view_as(p)
+                st = a.optimizer.state[p]
+                if "square_avg" in st:
+                    view.copy_(st["square_avg"])
+                else:
+                    st["step"] = torch.tensor(0.0)
+                st["square_avg"] = view
+                off += p.numel()
+        self.grads = torch.zeros_like(self.flat) if keep_grads else None
+        self.log_alpha, self.alpha_optimizer = None, None
+        if type(self.loss) is A0CLossTuned:
+            self.log_alpha = torch.stack([a.loss.log_alpha.detach().to(device) for a in self.agents]).requires_grad_(True)
+            g = a0.loss.optimizer.param_groups[0]
+            self.alpha_optimizer = torch.optim.Adam([self.log_alpha], lr=g["lr"], betas=g["betas"], eps=g["eps"],
+                                                    weight_decay=g["weight_decay"])
+            if any(alpha_states):
+                self.alpha_optimizer.state[self.log_alpha] = {
+                    "step": torch.tensor(float(alpha_states[0]["step"])),
+                    "exp_avg": torch.stack([s["exp_avg"].to(device) for s in alpha_states]),
+                    "exp_avg_sq": torch.stack([s["exp_avg_sq"].to(device) for s in alpha_states])}
+        self.last_raw: Optional[torch.Tensor] = None
+
+    def __len__(self) -> int:
+        return len(self.agents)
+
+    def _stacked(self, x) -> torch.Tensor:
+        """A batch field as one float32 [K, B, ...] tensor on the trainer's device (a sequence of K per-net fields is stacked)."""
+        if not isinstance(x, torch.Tensor):
+            x = torch.stack([f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)) for f in x])
+        return x.to(self.device, dtype=torch.float32).contiguous()
+
+    def update(self, batches) -> List[Dict[str, float]]:
+        """One optimiser step of every net on its own minibatch.  ``batches``: K tuples (states, actions, counts, Qs, V_target), the
+        argument of ``Agent.update``, with equal row counts -- or one such tuple of stacked [K, B, ...] tensors.  Returns what K
+        ``agent.update`` calls return."""
+        K = len(self.agents)
+        if isinstance(batches, (list, tuple)) and len(batches) == 5 and isinstance(batches[0], torch.Tensor) and batches[0].dim() == 3:
+            states, actions, counts, _, v_target = batches
+        else:
+            if len(batches) != K:
+                raise ValueError("PopulationTrainer.update: one minibatch per net")
+            if len({len(b[0]) for b in batches}) != 1:
+                raise ValueError("PopulationTrainer.update: every net's minibatch must have the same number of rows")
+            states, actions, counts, _, v_target = zip(*batches)
+        states, actions, counts = self._stacked(states), self._stacked(actions), self._stacked(counts)
+        B = states.shape[1]
+        values = self._stacked(v_target).reshape(K, B, 1)
+        if states.shape[0] != K or not 1 <= B <= self.max_batch:
+            raise ValueError(f"PopulationTrainer.update: needs [K = {K}, 1..{self.max_batch} rows, ...] minibatches")
+        states = states.reshape(K, B, -1)
+        raw = torch.empty((K, B, self.trainer.n_raw), dtype=torch.float32, device=self.device)
+        stream = torch.cuda.current_stream(self.device)
+        stream.synchronize()
+        self.trainer.forward(self.flat.data_ptr(), states.data_ptr(), B, raw.data_ptr())
+        self.last_raw = raw
+        raw.requires_grad_(True)
+        losses = population_loss(self.policy, self.loss, raw, actions, counts, values, self.log_alpha, self.alpha_optimizer)
+        losses["loss"].sum().backward()
+        d_raw = raw.grad.contiguous()
+        out = per_net(losses)   # (the copy to the host also completes d_raw)
+        stream.synchronize()
+        self.trainer.backward_step(self.flat.data_ptr(), d_raw.data_ptr(), B, self.opt, self.square_avg.data_ptr(),
+                                   self.grads.data_ptr() if self.grads is not None else None)
+        return out
+
+    def train_on_rows(self, rows_per_net, state_dim: int, K: int, batch_size: int = 32,
+                      shuffle_seeds: Optional[Sequence[int]] = None) -> List[Dict[str, float]]:
+        """``run.train_on_rows`` for every net at once: one epoch of minibatch updates over ``rows_per_net`` (K tensors [n, row] with
+        the same n, or one [K, n, row] tensor; row = obs | actions[K] | counts[K] | Q[K] | V), net k's rows shuffled with
+        ``shuffle_seeds[k]``; the last minibatch absorbs the remainder.  Returns per net the per-key sums."""
+        rows = rows_per_net if isinstance(rows_per_net, torch.Tensor) else torch.stack(list(rows_per_net))
+        rows = rows.to(self.device, dtype=torch.float32)
+        N, n = rows.shape[0], rows.shape[1]
+        if N != len(self.agents):
+            raise ValueError("PopulationTrainer.train_on_rows: one block of rows per net")
+        seeds = [0] * N if shuffle_seeds is None else list(shuffle_seeds)
+        order = torch.from_numpy(np.stack([np.random.RandomState(int(s)).permutation(n) for s in seeds])).to(self.device)
+        net = torch.arange(N, device=self.device)[:, None]
+        sums: List[Dict[str, float]] = [{} for _ in range(N)]
+        i = 0
+        while i < n:
+            j = n if i + 2 * batch_size > n else i + batch_size
+            b = rows[net, order[:, i:j]]
+            infos = self.update((b[..., :state_dim], b[..., state_dim:state_dim + K], b[..., state_dim + K:state_dim + 2 * K],
+                                 b[..., state_dim + 2 * K:state_dim + 3 * K], b[..., -1]))
+            for s, info in zip(sums, infos):
+                for key, val in info.items():
+                    s[key] = s.get(key, 0.0) + val
+            i = j
+        return sums
+
+    def export_alpha(self) -> None:
+        """Write every net's learned temperature and its Adam state (step, exp_avg, exp_avg_sq) back into its agent's loss object,
+        so that ``agent.update`` or a checkpoint of ``agent.loss`` continues from where the trainer stands.  ``close()`` does this;
+        between ``update`` calls the agents' own ``loss.log_alpha`` / ``loss.alpha`` are stale until it is called."""
+        if self.log_alpha is None:
+            return
+        state = self.alpha_optimizer.state.get(self.log_alpha, {})
+        with torch.no_grad():
+            for k, a in enumerate(self.agents):
+                la = a.loss.log_alpha
+                la.data.copy_(self.log_alpha[k])
+                a.loss.alpha = la.exp()
+                if state:
+                    a.loss.optimizer.state[la] = {"step": torch.tensor(float(state["step"])),
+                                                  "exp_avg": state["exp_avg"][k].detach().to(la.device).clone(),
+                                                  "exp_avg_sq": state["exp_avg_sq"][k].detach().to(la.device).clone()}
+
+    def close(self) -> None:
+        """Hand the learned temperatures back to the agents (``export_alpha``) and free the native trainer.  The parameters and the
+        RMSprop state need no hand-back: the agents' modules and optimisers are views of ``flat`` / ``square_avg``."""
+        if self.trainer._h:
+            self.export_alpha()
+        self.trainer.close()

@@ -313,6 +313,10 @@ class PopulationSelfPlay:
     def sync_weights(self, force: bool = False) -> None:
         self.mcts.sync_weights(force)
 
+    def upload_flat(self, desc, flat) -> None:
+        """``PopulationMCTS.upload_flat``: the hand-off of parameters trained in place by ``PopulationTrainer``."""
+        self.mcts.upload_flat(desc, flat)
+
     def play(self, n_steps: int) -> None:
         """n_steps self-play steps of every game of every net (asynchronous: launches only); rows accumulate in the device ring."""
         assert self.fifo or n_steps <= self.capacity

@@ -124,6 +124,24 @@ class PopulationMCTS:
             self.last_weight_sync = "host"
         self._versions = versions
 
+    def upload_flat(self, desc, flat) -> None:
+        """Upload every net from ``flat`` [n_models, P], the device tensor the models' parameters are views of
+        (agent.population_trainer.bind_flat): one gather launch, no per-net flattening.  For parameters a HIP kernel wrote in place
+        (PopulationTrainer): that does not bump torch's ``_version``, so ``sync_weights`` would not see it.  The models' current
+        versions are recorded, so that the next plain ``sync_weights()`` uploads nothing."""
+        import torch
+        if tuple(flat.shape[:1]) != (self.n_models,) or flat.dim() != 2 or not flat.is_contiguous() or flat.dtype != torch.float32:
+            raise ValueError("upload_flat: flat must be a contiguous float32 [n_models, P] tensor")
+        if not flat.is_cuda or flat.device.index != self.engine.cfg.device_id:
+            raise ValueError("upload_flat: flat must live on the engine's GPU")
+        torch.cuda.current_stream(flat.device).synchronize()
+        if self.n_models == 1:
+            self.engine.set_weights_device(desc, flat.data_ptr(), flat.shape[1])
+        else:
+            self.engine.set_population_weights_device(desc, flat.data_ptr(), flat.shape[1], self.n_models)
+        self._versions = [_weights_version(m) for m in self.models]
+        self.last_weight_sync = "device"
+
     def search(self, root_states: np.ndarray, root_n_carry: Optional[np.ndarray] = None) -> None:
         """root_states [n_trees, S] (or [n_models, trees_per_model, S]); tree k*T + j belongs to models[k]."""
         self.sync_weights()

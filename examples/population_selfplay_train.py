@@ -3,7 +3,8 @@
 Net k's games (--games-per-seed of them, global game ids k*T ...) are played on the device together with every other net's
 (azg_population_selfplay_begin: one search launch and one self-play launch per step for the whole population); each iteration
 downloads the new replay rows, trains every net on its own rows with its own optimiser, one net after another, and re-uploads
-the changed nets (one gather launch for all of them when the nets live on the GPU).
+the changed nets (one gather launch for all of them when the nets live on the GPU).  --trainer device takes every net's
+minibatch step at once instead (agent.population_trainer.PopulationTrainer: two HIP launches per step for all nets).
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
@@ -40,6 +41,8 @@ def parse_args(argv=None):
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--engine-seed", type=int, default=34, help="the engine's RNG seed (shared; games differ by their global ids)")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--trainer", choices=["torch", "device"], default="torch",
+                    help="torch: agent.update net by net; device: every net's optimiser step in two HIP launches (PopulationTrainer)")
     return ap.parse_args(argv)
 
 
@@ -66,6 +69,10 @@ def train(a, log=print, on_rows=None):
     rngs = [np.random.RandomState(s) for s in a.seeds]
     on_gpu = a.device.startswith("cuda")
     fs0, fc0 = np.zeros(len(a.seeds)), np.zeros(len(a.seeds), np.int64)
+    trainer = None
+    if a.trainer == "device":
+        from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
+        trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size))
     t0 = time.time()
     history = []
     for it in range(a.iters):
@@ -75,13 +82,25 @@ def train(a, log=print, on_rows=None):
         if on_rows is not None:
             on_rows(it, rows)
         losses = []
-        for agent, rng, r in zip(agents, rngs, rows):
-            pick = rng.choice(r.shape[0], size=min(a.train_rows, r.shape[0]), replace=False)
-            info = run.train_on_rows(agent, r[torch.from_numpy(pick).to(r.device)], state_dim, K, batch_size=a.batch_size,
-                                     shuffle_seed=int(rng.randint(2 ** 31 - 1)))
-            losses.append(info["loss"] / max(1, len(pick) // a.batch_size))
+        if trainer is None:
+            for agent, rng, r in zip(agents, rngs, rows):
+                pick = rng.choice(r.shape[0], size=min(a.train_rows, r.shape[0]), replace=False)
+                info = run.train_on_rows(agent, r[torch.from_numpy(pick).to(r.device)], state_dim, K, batch_size=a.batch_size,
+                                         shuffle_seed=int(rng.randint(2 ** 31 - 1)))
+                losses.append(info["loss"] / max(1, len(pick) // a.batch_size))
+        else:   # the same rows and shuffles, every net's minibatch step at once
+            picked, seeds = [], []
+            for rng, r in zip(rngs, rows):
+                pick = rng.choice(r.shape[0], size=min(a.train_rows, r.shape[0]), replace=False)
+                picked.append(r[torch.from_numpy(pick).to(r.device)])
+                seeds.append(int(rng.randint(2 ** 31 - 1)))
+            infos = trainer.train_on_rows(picked, state_dim, K, batch_size=a.batch_size, shuffle_seeds=seeds)
+            losses = [info["loss"] / max(1, picked[0].shape[0] // a.batch_size) for info in infos]
         t3 = time.time()
-        sp.sync_weights()
+        if trainer is None:
+            sp.sync_weights()
+        else:
+            sp.upload_flat(trainer.desc, trainer.flat)
         t4 = time.time()
         fs, fc = sp.finished_returns()
         mean_ret = (fs - fs0) / np.maximum(fc - fc0, 1)
@@ -93,6 +112,8 @@ def train(a, log=print, on_rows=None):
         if log:
             log(json.dumps(history[-1]), flush=True)
         fs0, fc0 = fs, fc
+    if trainer is not None:
+        trainer.close()
     sp.close()
     return history
 

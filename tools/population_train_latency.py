@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""One minibatch optimiser step of K nets, two ways in the same process: the loop of K agent.update calls, and
+PopulationTrainer.update (two HIP launches + the losses in PyTorch), with the latter's split into forward launch, PyTorch loss
+part and backward launch.  GPU box only:
+    python tools/population_train_latency.py [--ks 1,8,64,256] [--batch 128] [--reps 20] [--warmup 5] [--out profiles/population_train_latency.txt]
+Configurations: CartPole 2x128 ReLU and Pendulum 3x128 ELU (run.DISCRETE_DEFAULTS / CONTINUOUS_DEFAULTS, A0CLossTuned, RMSprop).
+Every figure is the median wall ms of --reps repetitions after --warmup, host clock around work that ends in a synchronise.  The
+file's header carries the errors printed by tests/test_population_trainer.py (--grad-errors FILE, the output of pytest -s: gradients
+against autograd, raw against azg_mlp_eval, first-step losses against float64) and the compiler's resource report of the two kernels."""
+import argparse
+import os
+import subprocess
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from alphazero_gym_amd import run  # noqa: E402
+from alphazero_gym_amd.agent import population_trainer as PT  # noqa: E402
+from alphazero_gym_amd.envs import make_game  # noqa: E402
+
+CONFIGS = {"cartpole_2x128": ("discrete", 4, 2), "pendulum_3x128": ("continuous", 3, 8)}   # kind, state_dim, actions per row
+
+
+def _batches(kind, K, B, S, A, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    states = torch.randn((K, B, S), generator=g)
+    actions = torch.arange(A, dtype=torch.float32).repeat(K, B, 1) if kind == "discrete" else torch.rand((K, B, A), generator=g) * 3.6 - 1.8
+    counts = torch.randint(1, 9, (K, B, A), generator=g).float()
+    v = torch.randn((K, B), generator=g)
+    return tuple(t.cuda() for t in (states, actions, counts, counts.clone(), v))
+
+
+def _median_ms(fn, reps, warmup):
+    out = []
+    for i in range(warmup + reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            out.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(out))
+
+
+def measure(name, K, B, reps, warmup):
+    kind, S, A = CONFIGS[name]
+    cfg = run._merge(run.CONTINUOUS_DEFAULTS if kind == "continuous" else run.DISCRETE_DEFAULTS, dict(device="cuda"))
+    env = make_game(cfg["game"])
+    torch.manual_seed(0)
+    agents = [run.make_agent(kind, cfg, env, tree_id_base=k) for k in range(K)]
+    stacked = _batches(kind, K, B, S, A)
+    per_net = [tuple(t[k] for t in stacked) for k in range(K)]
+
+    def loop():
+        for a, b in zip(agents, per_net):
+            a.update(b)
+
+    t_loop = _median_ms(loop, reps, warmup)
+    tr = PT.PopulationTrainer(agents, max_batch=max(512, 2 * B))
+    t_pop = _median_ms(lambda: tr.update(stacked), reps, warmup)
+    # the split: the same three parts, each timed on its own
+    states, actions, counts, _, v = stacked
+    values = v.reshape(K, B, 1)
+    raw = torch.empty((K, B, tr.trainer.n_raw), device="cuda")
+    t_fwd = _median_ms(lambda: tr.trainer.forward(tr.flat.data_ptr(), states.data_ptr(), B, raw.data_ptr()), reps, warmup)
+    box = {}
+
+    def loss_part():
+        r = raw.detach().requires_grad_(True)
+        losses = PT.population_loss(tr.policy, tr.loss, r, actions, counts, values, tr.log_alpha, tr.alpha_optimizer)
+        losses["loss"].sum().backward()
+        box["d_raw"] = r.grad.contiguous()
+        PT.per_net(losses)
+
+    t_loss = _median_ms(loss_part, reps, warmup)
+
+    def bwd():
+        tr.trainer.forward(tr.flat.data_ptr(), states.data_ptr(), B, raw.data_ptr())
+        tr.trainer.backward_step(tr.flat.data_ptr(), box["d_raw"].data_ptr(), B, tr.opt, tr.square_avg.data_ptr(), None)
+
+    t_bwd = _median_ms(bwd, reps, warmup) - t_fwd
+    tr.close()
+    return t_loop, t_pop, t_fwd, t_loss, t_bwd
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--ks", default="1,8,64,256")
+    ap.add_argument("--batch", type=int, default=128)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--configs", default=",".join(CONFIGS))
+    ap.add_argument("--grad-errors", default=None, help="output of pytest -s tests/test_population_trainer.py: its 'grad' lines go into the header")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    lines = ["# tools/population_train_latency.py: one minibatch optimiser step of K nets, batch %d, one MI355X; median wall ms of %d "
+             "repetitions after %d warm-up" % (a.batch, a.reps, a.warmup)]
+    if a.grad_errors and os.path.exists(a.grad_errors):
+        lines.append("# gradient errors against float64 autograd, max|g - g64| / max|g64| per parameter tensor (tests/test_population_trainer.py):")
+        log = [ln.strip().lstrip(".") for ln in open(a.grad_errors)]
+        lines += ["#   " + ln for ln in log if ln.startswith("grad ")]
+        lines.append("# raw against azg_mlp_eval's raw (bound 1e-5):")
+        lines += ["#   " + ln for ln in log if ln.startswith("forward vs ")]
+        lines.append("# first-step loss dictionaries against float64 (test_end_to_end_update):")
+        lines += ["#   " + ln for ln in log if ln.startswith(("discrete ", "continuous "))]
+    ru = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "resource_usage.py"), "dispatch_train", "train"],
+                        capture_output=True, text=True)
+    lines.append("# tools/resource_usage.py dispatch_train:")
+    lines += ["#   " + ln for ln in ru.stdout.splitlines()]
+    for name in a.configs.split(","):
+        lines.append(f"# {name}: loop of K agent.update | PopulationTrainer.update | ratio | forward launch | PyTorch loss part | backward launch")
+        for K in [int(k) for k in a.ks.split(",")]:
+            t_loop, t_pop, t_fwd, t_loss, t_bwd = measure(name, K, a.batch, a.reps, a.warmup)
+            lines.append(f"  {name} K={K:4d} loop {t_loop:9.3f} ms  population {t_pop:8.3f} ms  {t_loop / t_pop:7.2f}x  "
+                         f"forward {t_fwd:7.3f}  loss {t_loss:7.3f}  backward {t_bwd:7.3f}")
+            print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text)
+    else:
+        print(text)
+
+
+if __name__ == "__main__":
+    main()
