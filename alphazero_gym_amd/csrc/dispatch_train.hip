@@ -2,6 +2,7 @@
 #include <string>
 
 #include "../../include/azgym_train.h"
+#include "hip_host.h"
 #include "train.cuh"
 
 struct azg_trainer {
@@ -22,20 +23,6 @@ static int tfail(azg_trainer* t, int code, const std::string& msg) {
     return code;
 }
 
-namespace {
-// the caller's current HIP device is left as it was found
-struct TrainerDeviceScope {
-    int prev = -1;
-    bool ok;
-    explicit TrainerDeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = (prev == dev) || hipSetDevice(dev) == hipSuccess;
-        if (prev == dev) prev = -1;
-    }
-    ~TrainerDeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-}
-
 extern "C" {
 
 const char* azg_trainer_last_error(const azg_trainer* t) { return t ? t->err.c_str() : g_trainer_create_err.c_str(); }
@@ -44,7 +31,7 @@ size_t azg_trainer_param_count(const azg_trainer* t) { return t ? (size_t)t->d.P
 
 void azg_trainer_destroy(azg_trainer* t) {
     if (!t) return;
-    TrainerDeviceScope scope(t->device_id);
+    DeviceScope scope(t->device_id);
     if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
     if (t->scratch) (void)hipFree(t->scratch);
     delete t;
@@ -90,7 +77,7 @@ int azg_trainer_create(int32_t device_id, const azg_mlp_desc* desc, int32_t n_ne
     d.P = off;
     d.per_net = so;
     if (so >= ((size_t)1 << 32)) { delete t; return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: max_batch too large"); }
-    TrainerDeviceScope scope(device_id);
+    DeviceScope scope(device_id);
     if (!scope.ok) { delete t; return tfail(nullptr, AZG_E_DEVICE, "hipSetDevice failed"); }
     const size_t bytes = so * (size_t)n_nets * sizeof(float);
     // (not cleared: the forward launch writes every scratch element below its padded row count, and the backward launch of the
@@ -110,7 +97,7 @@ int azg_trainer_forward(azg_trainer* t, const float* params, const float* obs, i
     if (!t) return AZG_E_INVALID;
     if (!params || !obs || !raw) return tfail(t, AZG_E_INVALID, "azg_trainer_forward: NULL pointer");
     if (n_rows < 1 || n_rows > t->max_batch) return tfail(t, AZG_E_INVALID, "azg_trainer_forward: n_rows must be 1..max_batch");
-    TrainerDeviceScope scope(t->device_id);
+    DeviceScope scope(t->device_id);
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
     t->fwd_rows = 0;
     hipLaunchKernelGGL(train_forward_kernel, dim3((n_rows + 15) / 16, t->n_nets), dim3(64), 0, t->stream, t->d, params, obs, (int)n_rows, raw,
@@ -131,7 +118,7 @@ int azg_trainer_backward_step(azg_trainer* t, float* params, const float* d_raw,
     if (opt->momentum != 0.0 || opt->centered) return tfail(t, AZG_E_UNSUPPORTED, "azg_trainer_backward_step: RMSprop with momentum or centered is not built");
     if (opt->grad_clip != 0.0) return tfail(t, AZG_E_UNSUPPORTED, "azg_trainer_backward_step: gradient clipping is not built (a per-net global norm needs a pass of its own)");
     if (t->fwd_rows != n_rows) return tfail(t, AZG_E_STATE, "azg_trainer_backward_step: needs azg_trainer_forward of the same n_rows first");
-    TrainerDeviceScope scope(t->device_id);
+    DeviceScope scope(t->device_id);
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
     TrainOpt o;
     o.lr = (float)opt->lr; o.alpha = (float)opt->alpha; o.one_minus_alpha = (float)(1.0 - opt->alpha); o.eps = (float)opt->eps;

@@ -1,6 +1,8 @@
-// engine_host.h -- the engine object behind the C ABI, the host-side rules every kernel form shares, and the entry points of the
-// kernel translation units.  The search kernels are compiled in several translation units (dispatch_*.hip: one family of template
-// instantiations each) so that the library builds in parallel; azg_engine.hip holds the C ABI and the small kernels.
+// engine_host.h -- the engine object behind the C ABI, the helpers its translation units share, the host-side rules every kernel form
+// shares, and the entry points of the kernel translation units.  The C ABI: azg_engine.hip (creation, roots, search, results, dump,
+// info), engine_weights.hip (weight re-layout, populations), engine_selfplay.hip (device self-play, the results kernel's launch),
+// engine_selftest.hip (probes).  The search kernels are compiled in several translation units (dispatch_*.hip: one family of template
+// instantiations each) so that the library builds in parallel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,25 +10,28 @@
 #include <string>
 #include <vector>
 
+#include "hip_host.h"
 #include "records.h"
 #include "../../include/azgym_population.h"
 
 // diagnostic switches (environment variables, read once when the engine is created): force the other code paths in tests
 struct EngineOptions {
-    int force_persistent;      // AZG_FORCE_PERSISTENT=1: wide networks on the one-launch kernel instead of the lock-step path
-    int force_stream_weights;  // AZG_FORCE_STREAM_WEIGHTS=1: hidden->hidden weights streamed from L2 instead of register-resident
-    int force_global_tree;     // AZG_FORCE_GLOBAL_TREE=1: trees in global memory instead of LDS
-    int waves;                 // AZG_WAVES=4|8 (0: automatic)
-    int groups;                // AZG_GROUPS=1|2 (0: automatic)
-    int trace_cap;             // AZG_TRACE_CAP=n: traces a discrete tree may run per simulation step (0: automatic)
-    int no_spec;               // AZG_NO_SPEC=1: the general kernels where a compile-time specialised one exists (dispatch.cuh)
-    int tile_trees;            // AZG_TILE_TREES=16|8: trees per 16-column MFMA tile of the small-network kernels (0: automatic)
-    int ls_team;               // AZG_LS_TEAM=0: the per-layer launches instead of the persistent team kernel (team.cuh)
-    int team_wide;             // AZG_TEAM_WIDE=0: only the first form of the team kernel, 32-tree teams at two workgroups per CU (batches beyond that
-                               // then take the per-layer launches)
-    int team_tt;               // AZG_TEAM_TT=32 / 64: only teams of that many trees (default 0: 32, and 64 for batches beyond two 32-tree workgroups per CU)
-    long team_spin_limit;      // AZG_TEAM_SPIN_LIMIT=n: polls a team hand-off may wait before the launch gives up (tests: 0)
-    int no_lds_state;          // AZG_NO_LDS_STATE set: discrete LDS trees keep the expanded nodes' env states in the cold records only
+    int force_persistent = 0;      // AZG_FORCE_PERSISTENT=1: wide networks on the one-launch kernel instead of the lock-step path
+    int force_stream_weights = 0;  // AZG_FORCE_STREAM_WEIGHTS=1: hidden->hidden weights streamed from L2 instead of register-resident
+    int force_global_tree = 0;     // AZG_FORCE_GLOBAL_TREE=1: trees in global memory instead of LDS
+    int waves = 0;                 // AZG_WAVES=4|8 (0: automatic)
+    int groups = 0;                // AZG_GROUPS=1|2 (0: automatic)
+    int trace_cap = 0;             // AZG_TRACE_CAP=n: traces a discrete tree may run per simulation step (0: automatic)
+    int no_spec = 0;               // AZG_NO_SPEC=1: the general kernels where a compile-time specialised one exists (dispatch.cuh)
+    int tile_trees = 0;            // AZG_TILE_TREES=16|8: trees per 16-column MFMA tile of the small-network kernels (0: automatic)
+    int ls_team = 1;               // AZG_LS_TEAM=0: the per-layer launches instead of the persistent team kernel (team.cuh)
+    int team_wide = 1;             // AZG_TEAM_WIDE=0: only the first form of the team kernel, 32-tree teams at two workgroups per CU (batches beyond that
+                                   // then take the per-layer launches)
+    int team_tt = 0;               // AZG_TEAM_TT=32 / 64: only teams of that many trees (default 0: 32, and 64 for batches beyond two 32-tree workgroups per CU)
+    long team_spin_limit = 1L << 23;   // AZG_TEAM_SPIN_LIMIT=n: polls a team hand-off may wait before the launch gives up (tests: 0)
+    int no_lds_state = 0;          // AZG_NO_LDS_STATE set: discrete LDS trees keep the expanded nodes' env states in the cold records only
+    int publish_always = 0;        // AZG_PUBLISH_TREES=1: every search writes its LDS trees out in the global format (diagnostic tools)
+    static EngineOptions from_env();   // (azg_engine.hip)
 };
 #define AZG_MAX_DEVICES 64    // per-device caches of kernel attributes (host side)
 
@@ -40,7 +45,7 @@ struct LaunchRecord {
     int timed = 0;                            // the launch recorded ev0 / ev1 itself (hipExtLaunchKernelGGL)
 };
 
-// Where every element of the engine's weight buffer comes from, for one network shape (azg_engine.hip: build_weight_map)
+// Where every element of the engine's weight buffer comes from, for one network shape (engine_weights.hip: build_weight_map)
 struct WeightMap {
     bool valid = false;
     azg_mlp_desc desc;
@@ -49,62 +54,117 @@ struct WeightMap {
     size_t oW0, oW0b, ob0, oW0u, ob0u, oWl[MAX_STREAM_LAYERS], obl[MAX_STREAM_LAYERS], oWh, obh, olg[MAX_STREAM_LAYERS], olb[MAX_STREAM_LAYERS];
 };
 
-struct azg_engine {
-    azg_config cfg;
+// return_results' five arrays in ONE device block (float64 parts first) with a pinned host mirror: byte offsets for B trees of at most K
+// root children.  Every array ends where the next one begins.
+struct ResultsLayout {
+    size_t Q = 0, vt = 0, actions = 0, counts = 0, nch = 0, bytes = 0;
+    ResultsLayout() = default;
+    ResultsLayout(size_t B, size_t K) : vt(B * K * 8), actions(vt + B * 8), counts(actions + B * K * 4), nch(counts + B * K * 4), bytes(nch + B * 4) {}
+};
+
+// The engine's stream and the events around a search.  A base of azg_engine: destroyed after every member, that is after the memory.
+struct EngineQueue {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ~EngineQueue() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// (deleted by azg_engine_destroy with its device current and its stream idle)
+struct azg_engine : EngineQueue {
+    azg_config cfg{};
     EngineOptions opt;
-    int carry_max;           // largest carried root visit count of the uploaded roots
-    int S_env, S_obs, Kmax, Kp, R, nd, tab_n;
-    int mlp_ready, HP, n_hidden, n_out, act, nreg;
-    int n_cus;               // compute units of the device
+    int carry_max = 0;       // largest carried root visit count of the uploaded roots
+    int S_env = 0, S_obs = 0, Kmax = 0, Kp = 0, R = 0, nd = 0, tab_n = 0;
+    int mlp_ready = 0, HP = 0, n_hidden = 0, nreg = 0;
+    int n_cus = 256;         // compute units of the device
     LaunchRecord last;       // what the last search ran as
-    float ls_min, ls_max;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
-    KParams P;
-    std::vector<void*> dev_allocs;
-    float* d_wblob;          // every re-laid-out weight tensor of the current network in one buffer (reused while the shape stays)
-    size_t w_floats;
+    KParams P{};
+    DeviceAllocs mem;                // everything allocated once at creation
+    DeviceAllocs wblob_mem; float* d_wblob = nullptr;   // every re-laid-out weight tensor of the current network in one buffer (reused while the shape stays)
+    size_t w_floats = 0;
     std::vector<float> w_stage;      // host staging of that buffer
     WeightMap wmap;                  // the re-layout as an index map, rebuilt when the network shape changes
-    unsigned* d_wmap;                // its device copy (azg_set_weights_device)
-    std::vector<void*> dist_allocs;  // continuous mode: per-node mixture cache + root distribution staging, sized by the head
-    int dist_nd, dist_ncomp;
+    DeviceAllocs wmap_mem; unsigned* d_wmap = nullptr;   // its device copy (azg_set_weights_device)
+    DeviceAllocs dist_mem;           // continuous mode: per-node mixture cache + root distribution staging, sized by the head
+    int dist_nd = -1, dist_ncomp = -1;
     // results staging
-    float* d_actions; int* d_counts; double* d_Q; double* d_vt; int* d_nch; int* d_child_n; double* d_child_state;
-    float* d_rootV; float* d_rootdist;
-    char* d_res_block; void* h_res_block; size_t res_bytes;   // d_Q | d_vt | d_actions | d_counts | d_nch in one block + its pinned host mirror
-    double* d_roots; int* d_carry;
-    uint32_t search_idx;
-    int sp_on, sp_max_len, sp_det, sp_cap, sp_steps, sp_row;   // sp_steps = ReplayBuffer.size in steps
-    int sp_insert, sp_fs, sp_ring;   // ReplayBuffer.insert_index in steps; final selection; ring mode
-    long long sp_total;              // steps played since begin
-    double sp_agent_eps;
-    double* d_sp_ctab;
-    uint32_t sp_step_idx;
-    int* d_sp_t; int* d_sp_episode; int* d_sp_fcnt; double* d_sp_ret; double* d_sp_fsum; float* d_sp_rows;
-    std::vector<void*> sp_allocs;
-    unsigned* d_team_cnt; size_t team_cnt_bytes;   // team kernel: hand-off counters + abort word
-    int team_pending;        // a team kernel has been launched since its abort word was last read
-    int team_fallbacks;      // searches it gave up on (redone by the per-layer launches)
-    uint32_t team_search_idx;
-    int lds_warned;          // the one stderr line about it has been printed
-    LockStep ls;             // lock-step path for wide networks (lockstep.cuh)
-    std::vector<void*> ls_allocs;
-    int ls_hp;
-    float* d_eval; size_t eval_floats;   // scratch of azg_mlp_eval (grow-only)
-    int searched, results_valid;
-    int publish_always;      // AZG_PUBLISH_TREES=1: every search writes its LDS trees out in the global format (diagnostic tools)
-    int publish_once;        // set by azg_dump_tree around its re-run of the last search
-    int published;           // the last search's trees are in global memory (global-tree / lock-step / team forms always are)
-    int redo_ok;             // roots, carried counts and weights are still the ones the last search ran on: azg_dump_tree may re-run it
-    int n_nets;              // azg_set_population: the trees split into n_nets nets of n_trees / n_nets trees (1: one network)
-    std::vector<char> net_have;   // net k has weights (azg_set_net_weights); d_wblob holds n_nets blocks of w_floats
-    size_t stamp_n;          // rows of the diagnostic stamp buffer (P.stamps)
-    float last_ms;
-    uint32_t last_search_idx;   // the search index the last search ran under (azg_dump_tree re-runs it with this one)
-    float ms_kept; int ms_kept_valid;   // kernel time of the last search, kept across azg_dump_tree's re-run of it
+    float* d_actions = nullptr; int* d_counts = nullptr; double* d_Q = nullptr; double* d_vt = nullptr; int* d_nch = nullptr;
+    int* d_child_n = nullptr; double* d_child_state = nullptr; float* d_rootV = nullptr; float* d_rootdist = nullptr;
+    ResultsLayout res;                                // d_Q | d_vt | d_actions | d_counts | d_nch in one block
+    char* d_res_block = nullptr; PinnedBlock h_res;   // ... and its pinned host mirror
+    double* d_roots = nullptr; int* d_carry = nullptr;
+    uint32_t search_idx = 0;
+    int sp_on = 0, sp_max_len = 0, sp_det = 0, sp_cap = 0, sp_steps = 0, sp_row = 0;   // sp_steps = ReplayBuffer.size in steps
+    int sp_insert = 0, sp_fs = 0, sp_ring = 0;   // ReplayBuffer.insert_index in steps; final selection; ring mode
+    long long sp_total = 0;          // steps played since begin
+    double sp_agent_eps = 0.0;
+    double* d_sp_ctab = nullptr;
+    uint32_t sp_step_idx = 0;
+    int* d_sp_t = nullptr; int* d_sp_episode = nullptr; int* d_sp_fcnt = nullptr; double* d_sp_ret = nullptr; double* d_sp_fsum = nullptr;
+    float* d_sp_rows = nullptr;
+    DeviceAllocs sp_mem;
+    unsigned* d_team_cnt = nullptr; size_t team_cnt_bytes = 0;   // team kernel: hand-off counters + abort word
+    int team_pending = 0;    // a team kernel has been launched since its abort word was last read
+    int team_fallbacks = 0;  // searches it gave up on (redone by the per-layer launches)
+    uint32_t team_search_idx = 0;
+    int lds_warned = 0;      // the one stderr line about it has been printed
+    LockStep ls{};           // lock-step path for wide networks (lockstep.cuh)
+    DeviceAllocs ls_mem;
+    int ls_hp = 0;
+    DeviceAllocs eval_mem; float* d_eval = nullptr; size_t eval_floats = 0;   // scratch of azg_mlp_eval (grow-only)
+    int searched = 0, results_valid = 0;
+    int publish_once = 0;    // set by azg_dump_tree around its re-run of the last search
+    int published = 0;       // the last search's trees are in global memory (global-tree / lock-step / team forms always are)
+    int redo_ok = 0;         // roots, carried counts and weights are still the ones the last search ran on: azg_dump_tree may re-run it
+    int n_nets = 1;          // azg_set_population: the trees split into n_nets nets of n_trees / n_nets trees (1: one network)
+    std::vector<char> net_have = std::vector<char>(1, 0);   // net k has weights (azg_set_net_weights); d_wblob holds n_nets blocks of w_floats
+    DeviceAllocs stamp_mem; size_t stamp_n = 0;   // rows of the diagnostic stamp buffer (P.stamps)
+    uint32_t last_search_idx = 0;   // the search index the last search ran under (azg_dump_tree re-runs it with this one)
+    float ms_kept = 0.0f; int ms_kept_valid = 0;   // kernel time of the last search, kept across azg_dump_tree's re-run of it
     std::string err;
 };
+
+// ---- shared by the engine's translation units (engine-bound; DeviceScope and the memory owners: hip_host.h)
+
+// records msg as e's last error (e NULL: as the creation error) and returns code (azg_engine.hip)
+int fail(azg_engine* e, int code, const std::string& msg);
+
+#define HIPCHK(e, call)                                                                                  \
+    do {                                                                                                 \
+        hipError_t _rc = (call);                                                                         \
+        if (_rc != hipSuccess) return fail(e, AZG_E_DEVICE, std::string(#call) + ": " + hipGetErrorString(_rc)); \
+    } while (0)
+#define ON_DEVICE(e)                                     \
+    DeviceScope _scope((e)->cfg.device_id);              \
+    if (!_scope.ok) return fail(e, AZG_E_DEVICE, "hipSetDevice failed")
+#define D2H(dst, src, bytes) do { if (dst) HIPCHK(e, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); } while (0)
+
+template <typename T>
+static int dalloc(azg_engine* e, DeviceAllocs& mem, T** p, size_t n) {
+    if ((*p = mem.alloc<T>(n))) return AZG_OK;
+    return fail(e, AZG_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(mem.last));
+}
+
+// An abandoned team search (team_pending) is redone before anything reads its trees or changes its inputs: synchronises the stream
+// and re-runs the search where the team kernel gave up; nothing, and no synchronisation, when no team kernel is pending (azg_engine.hip)
+int settle_team(azg_engine* e);
+// return_results of the last search on e->stream where the search kernel did not write them itself (engine_selfplay.hip)
+int launch_results(azg_engine* e);
+
+// Rows (16 counters each) of the diagnostic stamp buffer: one per wave of the search kernel -- four waves per 4 trees at the least
+// filled tile shape, eight waves per 16-tree workgroup (also when the batch has fewer than 16 trees) -- or eight counters per
+// team-kernel workgroup (16 workgroups per 32 trees, at least one team).
+static inline size_t stamp_rows(size_t B) {
+    size_t r = ((B + 3) / 4) * 4;
+    const size_t r8 = ((B + 15) / 16) * 8, team = ((B + 31) / 32) * 16 * 3 / 2;   // (team kernel: 8 + 16 counters per workgroup)
+    if (r8 > r) r = r8;
+    if (team > r) r = team;
+    return r < 16 ? 16 : r;
+}
 
 // Trees the persistent kernel's grid covers with tpw trees per workgroup: every net's segment padded to whole workgroups (one net: the
 // batch rounded up to tpw).  The launch planning (dispatch.cuh) sizes the grid and picks its shapes from this count.

@@ -1,0 +1,174 @@
+// engine_selfplay.hip -- the C ABI's device-resident self-play (azg_selfplay_*, azg_population_selfplay_begin) and the launches of the
+// small kernels after a search: results_kernel and the self-play step (aux_kernels.cuh is compiled in this unit only).
+#include <cmath>
+#include <cstring>
+
+#include "engine_host.h"
+#include "mlp.cuh"
+#include "aux_kernels.cuh"
+
+int launch_results(azg_engine* e) {
+    if (!e->searched) return fail(e, AZG_E_STATE, "no search has run");
+    if (e->results_valid) return AZG_OK;
+    { int trc = settle_team(e); if (trc) return trc; }
+    int B = e->cfg.n_trees;
+    hipLaunchKernelGGL(results_kernel, dim3((B + RS_TREES - 1) / RS_TREES), dim3(16 * RS_TREES), 0, e->stream, e->P);
+    HIPCHK(e, hipGetLastError());
+    e->results_valid = 1;   // (in stream order: whatever reads the buffers is ordered after this launch)
+    return AZG_OK;
+}
+
+extern "C" {
+
+int azg_selfplay_row_len(const azg_engine* e) { return e ? e->S_obs + 3 * e->Kmax + 1 : AZG_E_INVALID; }
+
+// Common body of azg_selfplay_begin_ex and azg_population_selfplay_begin.  A population's games are its trees: net k plays games
+// k*T .. k*T+T-1 (global ids tree_id_base + k*T + j), and the self-play kernels work per tree on what the search returned, so the
+// steps, rows, ring and stats are those of an engine of one net.
+static int selfplay_begin_impl(azg_engine* e, const azg_selfplay_config* c) {
+    if (c->struct_size != (int32_t)sizeof(azg_selfplay_config)) return fail(e, AZG_E_INVALID, "azg_selfplay_config size mismatch");
+    if (c->max_episode_length < 1 || c->capacity_steps < 1) return fail(e, AZG_E_INVALID, "max_episode_length and capacity_steps must be >= 1");
+    if (c->final_selection != AZG_FS_MAX_VISIT && c->final_selection != AZG_FS_MAX_VALUE) return fail(e, AZG_E_INVALID, "unknown final_selection");
+    if (c->ring_mode != AZG_RING_STOP && c->ring_mode != AZG_RING_FIFO) return fail(e, AZG_E_INVALID, "unknown ring_mode");
+    if (!(c->temperature > 0.0)) return fail(e, AZG_E_INVALID, "temperature must be > 0");
+    if (c->agent_epsilon < 0.0 || c->agent_epsilon > 1.0) return fail(e, AZG_E_INVALID, "agent_epsilon must be in [0, 1]");
+    const bool discrete = e->cfg.mode == AZG_MODE_DISCRETE;
+    if (discrete && c->final_selection == AZG_FS_MAX_VALUE && c->temperature != 1.0)
+        return fail(e, AZG_E_UNSUPPORTED, "final_selection max_value on the device supports temperature 1 only");
+    ON_DEVICE(e);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->sp_mem.clear();
+    e->sp_on = 0;
+    const size_t B = e->cfg.n_trees;
+    e->sp_row = e->S_obs + 3 * e->Kmax + 1;
+    if (dalloc(e, e->sp_mem, &e->d_sp_t, B) || dalloc(e, e->sp_mem, &e->d_sp_episode, B) || dalloc(e, e->sp_mem, &e->d_sp_fcnt, B) ||
+        dalloc(e, e->sp_mem, &e->d_sp_ret, B) || dalloc(e, e->sp_mem, &e->d_sp_fsum, B) ||
+        dalloc(e, e->sp_mem, &e->d_sp_rows, (size_t)c->capacity_steps * B * e->sp_row))
+        return AZG_E_DEVICE;
+    e->d_sp_ctab = nullptr;
+    if (discrete && c->temperature != 1.0) {
+        // stable_normalizer (helpers.py:10-27) raises x / max(x) to the temperature: (c / m)^t for every pair of a root edge count c
+        // and the root's largest count m that can occur, python float pow = libm pow on the host (like check_pw's table)
+        const size_t ns = (size_t)e->cfg.n_sims;
+        if (ns > 2048) return fail(e, AZG_E_UNSUPPORTED, "temperature != 1 on the device supports n_sims <= 2048");
+        std::vector<double> tab((ns + 1) * (ns + 2) / 2, 0.0);
+        for (size_t m = 1; m <= ns; ++m)
+            for (size_t k = 0; k <= m; ++k) tab[m * (m + 1) / 2 + k] = std::pow((double)k / (double)m, c->temperature);
+        if (dalloc(e, e->sp_mem, &e->d_sp_ctab, tab.size())) return AZG_E_DEVICE;
+        HIPCHK(e, hipMemcpy(e->d_sp_ctab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    }
+    HIPCHK(e, hipMemset(e->d_sp_t, 0, B * 4));
+    HIPCHK(e, hipMemset(e->d_sp_episode, 0, B * 4));
+    HIPCHK(e, hipMemset(e->d_sp_fcnt, 0, B * 4));
+    HIPCHK(e, hipMemset(e->d_sp_ret, 0, B * 8));
+    HIPCHK(e, hipMemset(e->d_sp_fsum, 0, B * 8));
+    std::vector<double> roots(B * e->S_env);
+    azg_synthetic_roots(e, roots.data());
+    HIPCHK(e, hipMemcpy(e->d_roots, roots.data(), roots.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemset(e->d_carry, 0, B * 4));
+    e->carry_max = discrete ? e->cfg.n_sims : 0;   // a reused root carries its node count as a child: at most n_sims
+    e->sp_on = 1; e->sp_max_len = c->max_episode_length; e->sp_det = c->deterministic; e->sp_cap = c->capacity_steps; e->sp_steps = 0;
+    e->sp_insert = 0; e->sp_total = 0; e->sp_fs = c->final_selection; e->sp_ring = c->ring_mode; e->sp_agent_eps = c->agent_epsilon;
+    e->sp_step_idx = 0;
+    return AZG_OK;
+}
+
+int azg_selfplay_begin_ex(azg_engine* e, const azg_selfplay_config* c) {
+    if (!e || !c) return AZG_E_INVALID;
+    if (e->n_nets > 1)
+        return fail(e, AZG_E_UNSUPPORTED, "device self-play of a population (azg_set_population > 1) starts with azg_population_selfplay_begin");
+    return selfplay_begin_impl(e, c);
+}
+
+int azg_population_selfplay_begin(azg_engine* e, const azg_selfplay_config* c) {
+    if (!e || !c) return AZG_E_INVALID;
+    return selfplay_begin_impl(e, c);
+}
+
+int azg_selfplay_begin(azg_engine* e, int32_t max_episode_length, int32_t deterministic, int32_t capacity_steps) {
+    azg_selfplay_config c;
+    memset(&c, 0, sizeof(c));
+    c.struct_size = (int32_t)sizeof(c);
+    c.max_episode_length = max_episode_length; c.deterministic = deterministic; c.capacity_steps = capacity_steps;
+    c.final_selection = AZG_FS_MAX_VISIT; c.ring_mode = AZG_RING_STOP; c.temperature = 1.0; c.agent_epsilon = 0.0;
+    return azg_selfplay_begin_ex(e, &c);
+}
+
+int azg_selfplay_step(azg_engine* e) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (e->sp_ring == AZG_RING_STOP && e->sp_steps >= e->sp_cap) return fail(e, AZG_E_STATE, "replay ring is full: download and clear the rows");
+    int rc = azg_search_resident(e);
+    if (rc) return rc;
+    ON_DEVICE(e);
+    rc = settle_team(e);   // (wide networks: the persistent team kernel may have given up)
+    if (rc) return rc;
+    // ReplayBuffer.store (buffers.py:75-82) for this step's block of n_trees rows
+    int slot;
+    if (e->sp_steps < e->sp_cap) { slot = e->sp_steps; e->sp_steps += 1; }
+    else { slot = e->sp_insert; e->sp_insert = (e->sp_insert + 1) % e->sp_steps; }
+    SelfPlay sp;
+    sp.max_len = e->sp_max_len; sp.deterministic = e->sp_det; sp.step_idx = e->sp_step_idx;
+    sp.final_selection = e->sp_fs; sp.agent_eps = e->sp_agent_eps; sp.ctab = e->d_sp_ctab;
+    sp.t = e->d_sp_t; sp.episode = e->d_sp_episode; sp.fcnt = e->d_sp_fcnt; sp.ret = e->d_sp_ret; sp.fsum = e->d_sp_fsum;
+    sp.rows = e->d_sp_rows + (size_t)slot * e->cfg.n_trees * e->sp_row;
+    sp.roots = e->d_roots; sp.carry = e->d_carry;
+    const int B = e->cfg.n_trees;
+    e->redo_ok = 0;   // (the step moves the roots on: the search that just ran cannot be re-run for a dump)
+    if (e->Kmax <= 16) {
+        rc = launch_results(e);   // return_results of this search (a launch only after the lock-step / team kernels)
+        if (rc) return rc;
+    }
+    if (e->Kmax <= 16)
+        hipLaunchKernelGGL(selfplay_kernel16, dim3((B + SP_TREES - 1) / SP_TREES), dim3(16 * SP_TREES), 0, e->stream, e->P, sp, e->Kmax, e->cfg.v_target, e->cfg.env_id, e->S_obs);
+    else
+        hipLaunchKernelGGL(selfplay_kernel, dim3((B + RK_THREADS - 1) / RK_THREADS), dim3(RK_THREADS), 0, e->stream, e->P, sp, e->Kmax, e->cfg.v_target, e->cfg.env_id, e->S_obs);
+    HIPCHK(e, hipGetLastError());
+    e->sp_total += 1;
+    e->sp_step_idx += 1;
+    return AZG_OK;
+}
+
+int azg_selfplay_rows(azg_engine* e, float* rows, size_t max_rows, int32_t clear) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    ON_DEVICE(e);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    size_t n = (size_t)e->sp_steps * e->cfg.n_trees;
+    if (n > max_rows) n = max_rows;
+    if (rows && n) HIPCHK(e, hipMemcpy(rows, e->d_sp_rows, n * e->sp_row * 4, hipMemcpyDeviceToHost));
+    if (clear) { e->sp_steps = 0; e->sp_insert = 0; }   // ReplayBuffer.clear (buffers.py:56-60)
+    return (int)n;
+}
+
+int azg_selfplay_ring(azg_engine* e, int32_t* size_steps, int32_t* insert_step, int64_t* total_steps) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (size_steps) *size_steps = e->sp_steps;
+    if (insert_step) *insert_step = e->sp_insert;
+    if (total_steps) *total_steps = e->sp_total;
+    return AZG_OK;
+}
+
+int azg_selfplay_rows_device(azg_engine* e, void** device_ptr, size_t* capacity_rows, size_t* row_len) {
+    if (!e || !device_ptr) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    *device_ptr = e->d_sp_rows;
+    if (capacity_rows) *capacity_rows = (size_t)e->sp_cap * e->cfg.n_trees;
+    if (row_len) *row_len = (size_t)e->sp_row;
+    return AZG_OK;
+}
+
+int azg_selfplay_stats(azg_engine* e, double* fsum, int32_t* fcnt, double* env_state) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    ON_DEVICE(e);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    size_t B = e->cfg.n_trees;
+    D2H(fsum, e->d_sp_fsum, B * 8);
+    D2H(fcnt, e->d_sp_fcnt, B * 4);
+    D2H(env_state, e->d_roots, B * e->S_env * 8);
+    return AZG_OK;
+}
+
+}  // extern "C"

@@ -33,8 +33,8 @@ def native():
 
 
 def _shape(cfg, variant):
-    """The search_info a population of this configuration must report under the variant: dispatch.cuh's choices (and azg_engine.hip's
-    register residency) for a batch of fewer workgroups than the device has CUs."""
+    """The search_info a population of this configuration must report under the variant: dispatch.cuh's choices (and engine_weights.hip's
+    register residency, resident_layers) for a batch of fewer workgroups than the device has CUs."""
     env, mode, hidden, act, n_sims, extra, ncomp, ln = P.split_config(cfg)
     HP = -(-max(hidden) // 64) * 64
     nhh = len(hidden) - 1

@@ -21,7 +21,7 @@ for _ in range(2):
     e.search_resident()
 e.sync()
 print("kernel ms", e.last_search_ms())
-rows = max((B + 3) // 4 * 4, (B + 31) // 32 * 24, 16)       # azg_engine.hip stamp_rows
+rows = max((B + 3) // 4 * 4, (B + 31) // 32 * 24, 16)       # engine_host.h stamp_rows
 buf = np.zeros((rows, 16), np.uint64)
 lib = _native.lib()
 lib.azg_debug_stamps.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t]
