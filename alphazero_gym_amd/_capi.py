@@ -105,13 +105,36 @@ SYMBOLS = [
 OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device",
                     "population_selfplay_begin",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
-                    "trainer_backward_step"]
+                    "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw"]
 
 
 class AzgRmsprop(C.Structure):
     """include/azgym_train.h: azg_rmsprop"""
     _fields_ = [("struct_size", C.c_int32), ("centered", C.c_int32), ("lr", C.c_double), ("alpha", C.c_double), ("eps", C.c_double),
                 ("weight_decay", C.c_double), ("momentum", C.c_double), ("grad_clip", C.c_double)]
+
+
+LOSS_ALPHAZERO, LOSS_A0C, LOSS_A0C_TUNED = 0, 1, 2
+HEAD_DISCRETE, HEAD_NORMAL, HEAD_GMM = 0, 1, 2
+REDUCE = {"mean": 0, "sum": 1}
+LOSS_KEYS = ("loss", "policy_loss", "value_loss", "entropy_loss", "alpha_loss")   # the slots of losses[k][5]
+# the keys of population_loss's dictionary per loss kind, in its order
+LOSS_KEYS_OF = {LOSS_ALPHAZERO: ("loss", "policy_loss", "value_loss"), LOSS_A0C: ("loss", "policy_loss", "entropy_loss", "value_loss"),
+                LOSS_A0C_TUNED: ("loss", "policy_loss", "entropy_loss", "value_loss", "alpha_loss")}
+
+
+class AzgLossCfg(C.Structure):
+    """include/azgym_train.h: azg_loss_cfg"""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("head", C.c_int32), ("reduction", C.c_int32),
+                ("tau", C.c_double), ("policy_coeff", C.c_double), ("value_coeff", C.c_double), ("alpha", C.c_double),
+                ("target_entropy", C.c_double), ("alpha_lr", C.c_double), ("alpha_beta1", C.c_double), ("alpha_beta2", C.c_double),
+                ("alpha_eps", C.c_double), ("alpha_weight_decay", C.c_double), ("alpha_clip", C.c_double), ("action_bound", C.c_double)]
+
+
+class AzgAlphaState(C.Structure):
+    """include/azgym_train.h: azg_alpha_state"""
+    _fields_ = [("struct_size", C.c_int32), ("step", C.c_int32), ("log_alpha", C.c_void_p), ("exp_avg", C.c_void_p),
+                ("exp_avg_sq", C.c_void_p)]
 
 
 def bind(lib, prefix):
@@ -177,6 +200,11 @@ def bind(lib, prefix):
         f["trainer_param_count"].restype = C.c_size_t
         f["trainer_forward"].argtypes = [vp, vp, vp, C.c_int32, vp]
         f["trainer_backward_step"].argtypes = [vp, vp, vp, C.c_int32, C.POINTER(AzgRmsprop), vp, vp]
+    if "trainer_loss" in f:
+        f["trainer_loss"].argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.POINTER(AzgLossCfg), C.POINTER(AzgAlphaState), vp, vp]
+        f["trainer_step"].argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.POINTER(AzgLossCfg), C.POINTER(AzgAlphaState),
+                                      C.POINTER(AzgRmsprop), vp, vp, vp, vp]
+        f["trainer_read_d_raw"].argtypes = [vp, C.c_int32, vp]
     return f
 
 
@@ -565,6 +593,50 @@ def rmsprop_opt(lr, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, center
     return o
 
 
+def loss_cfg(policy, loss):
+    """azg_loss_cfg of a policy and loss pairing (one of a population's: all nets share them).  The head kind comes from the
+    policy's class, the loss kind from the loss's; names, not isinstance, so that the reference's objects work alike.  Raises
+    ``ValueError`` for what ``population_loss`` refuses."""
+    head = {"DiscretePolicy": HEAD_DISCRETE, "DiagonalNormalPolicy": HEAD_NORMAL, "DiagonalGMMPolicy": HEAD_GMM}.get(type(policy).__name__)
+    kind = {"AlphaZeroLoss": LOSS_ALPHAZERO, "A0CLoss": LOSS_A0C, "A0CLossTuned": LOSS_A0C_TUNED}.get(type(loss).__name__)
+    if head is None:
+        raise ValueError(f"loss_cfg: {type(policy).__name__} heads are not supported")
+    if kind is None:
+        raise ValueError(f"loss_cfg: {type(loss).__name__} is not supported")
+    if kind == LOSS_ALPHAZERO and head != HEAD_DISCRETE:
+        raise ValueError("loss_cfg: AlphaZeroLoss needs a discrete policy")
+    if loss.reduction not in REDUCE:
+        raise ValueError("loss_cfg: reduction must be 'mean' or 'sum'")
+    if head == HEAD_GMM and policy.num_components > 5:
+        raise ValueError("loss_cfg: at most 5 mixture components")
+    c = AzgLossCfg()
+    c.struct_size = C.sizeof(AzgLossCfg)
+    c.kind, c.head, c.reduction = kind, head, REDUCE[loss.reduction]
+    c.policy_coeff, c.value_coeff = float(loss.policy_coeff), float(loss.value_coeff)
+    c.action_bound = float(getattr(policy, "action_bound", 0.0) or 0.0) if head != HEAD_DISCRETE else 0.0
+    if kind != LOSS_ALPHAZERO:
+        c.tau = float(loss.tau)
+    if kind == LOSS_A0C:
+        c.alpha = float(loss.alpha)
+    if kind == LOSS_A0C_TUNED:
+        g = loss.optimizer.param_groups[0]
+        if type(loss.optimizer).__name__ != "Adam" or g.get("amsgrad", False) or g.get("maximize", False):
+            raise ValueError("loss_cfg: the learned temperature's optimiser must be plain torch.optim.Adam")
+        c.target_entropy = float(loss.target_entropy)
+        c.alpha_lr, (c.alpha_beta1, c.alpha_beta2) = float(g["lr"]), (float(b) for b in g["betas"])
+        c.alpha_eps, c.alpha_weight_decay, c.alpha_clip = float(g["eps"]), float(g["weight_decay"]), float(loss.clip or 0.0)
+    return c
+
+
+def alpha_state(step, log_alpha, exp_avg, exp_avg_sq):
+    """azg_alpha_state: ``step`` Adam steps taken so far, and the device addresses of the three [n_nets] float32 arrays."""
+    s = AzgAlphaState()
+    s.struct_size = C.sizeof(AzgAlphaState)
+    s.step = int(step)
+    s.log_alpha, s.exp_avg, s.exp_avg_sq = log_alpha or None, exp_avg or None, exp_avg_sq or None
+    return s
+
+
 class Trainer:
     """One ``azg_trainer*`` (include/azgym_train.h): forward and backward + RMSprop step of n_nets nets of shape ``desc`` in two
     launches.  Every array argument is a device address (int) of float32 memory on the trainer's GPU, complete when the call is
@@ -607,6 +679,29 @@ class Trainer:
         """azg_trainer_backward_step: back from d_raw, RMSprop update of params / square_avg in place; grads (optional) filled."""
         self._check(self._f["trainer_backward_step"](self._h, params or None, d_raw or None, int(n_rows),
                                                      C.byref(opt) if opt is not None else None, square_avg or None, grads or None))
+
+    def loss(self, raw, actions, counts, values, n_rows, n_actions, cfg, alpha, d_raw, losses):
+        """azg_trainer_loss: the loss kernel alone.  raw [n_nets, n_rows, 1 + n_dist], actions / counts [n_nets, n_rows, n_actions],
+        values [n_nets, n_rows] -> d_raw (raw's shape) and losses [n_nets, 5] (``LOSS_KEYS``); ``alpha`` (``alpha_state``, for
+        A0CLossTuned) is stepped in place."""
+        if "trainer_loss" not in self._f:
+            raise NotImplementedError("this engine library has no azg_trainer_loss")
+        self._check(self._f["trainer_loss"](self._h, raw or None, actions or None, counts or None, values or None, int(n_rows), int(n_actions),
+                                            C.byref(cfg) if cfg is not None else None, C.byref(alpha) if alpha is not None else None,
+                                            d_raw or None, losses or None))
+
+    def step(self, params, obs, actions, counts, values, n_rows, n_actions, cfg, alpha, opt, square_avg, grads, raw_out, losses):
+        """azg_trainer_step: forward, loss and backward + RMSprop of every net, three launches and one synchronisation."""
+        if "trainer_step" not in self._f:
+            raise NotImplementedError("this engine library has no azg_trainer_step")
+        self._check(self._f["trainer_step"](self._h, params or None, obs or None, actions or None, counts or None, values or None, int(n_rows),
+                                            int(n_actions), C.byref(cfg) if cfg is not None else None,
+                                            C.byref(alpha) if alpha is not None else None, C.byref(opt) if opt is not None else None,
+                                            square_avg or None, grads or None, raw_out or None, losses or None))
+
+    def read_d_raw(self, n_rows, d_raw):
+        """azg_trainer_read_d_raw: the last ``step``'s d_raw [n_nets, n_rows, 1 + n_dist] into the caller's device array."""
+        self._check(self._f["trainer_read_d_raw"](self._h, int(n_rows), d_raw or None))
 
 
 def pw_table(c_pw, kappa, n):

@@ -6,7 +6,9 @@ The K policies' parameters live in ONE float32 tensor ``flat[K, P]`` (``bind_fla
 (``PopulationMCTS.upload_flat``).  The boundary between HIP and PyTorch is the heads' raw output ``raw[K, B, 1 + n_dist]``:
 trunk, heads, their backward pass and the RMSprop step are kernels; the losses (``population_loss``: ``DiscreteAgent._loss`` /
 ``ContinuousAgent._loss`` restated once for a leading K axis, the tuned alpha's Adam step included) stay in PyTorch and give
-``d_raw`` by autograd on those small tensors.  The single-agent path (``Agent.update``) is untouched.
+``d_raw`` by autograd on those small tensors.  ``PopulationTrainer(..., losses="device")`` moves that boundary out of the step:
+the same losses, their ``d_raw`` and the tuned alpha's Adam step are one more kernel between the two (``azg_trainer_step``: three
+launches, one synchronisation, one copy of ``losses[K, 5]`` to the host).  The single-agent path (``Agent.update``) is untouched.
 """
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -192,9 +194,16 @@ class PopulationTrainer:
     ``self.square_avg`` [K, P] (state an agent already has is taken over; the agents' torch optimisers keep working on the same
     storage).  With ``A0CLossTuned`` the learned temperatures live in ``self.log_alpha`` [K] under one Adam; ``export_alpha()``
     (called by ``close()``) writes them and their Adam state back into the agents' loss objects, which are stale until then.  After ``update`` hand the weights to the search with
-    ``PopulationMCTS.upload_flat(trainer.desc, trainer.flat)``."""
+    ``PopulationMCTS.upload_flat(trainer.desc, trainer.flat)``.
 
-    def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False):
+    ``losses``: "torch" computes the losses and ``d_raw`` in PyTorch between the two launches; "device" computes them in a kernel of
+    the same step (``_capi.Trainer.step``).  Then ``log_alpha`` and its Adam state (``alpha_exp_avg``, ``alpha_exp_avg_sq``,
+    ``alpha_step``) are plain tensors of the trainer that the kernel steps in place, and there is no ``alpha_optimizer``."""
+
+    def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False, losses: str = "torch"):
+        if losses not in ("torch", "device"):
+            raise ValueError("losses must be 'torch' or 'device'")
+        self.losses = losses
         self.agents = list(agents)
         if not self.agents:
             raise ValueError("PopulationTrainer needs at least one agent")
@@ -229,6 +238,7 @@ class PopulationTrainer:
             alpha_states = [a.loss.optimizer.state.get(a.loss.log_alpha, {}) for a in self.agents]
             if any(alpha_states) and (not all(alpha_states) or len({float(s["step"]) for s in alpha_states}) != 1):
                 raise ValueError("PopulationTrainer: the agents' alpha optimisers must have taken the same number of steps")
+        self.loss_cfg = _capi.loss_cfg(a0.nn, a0.loss) if losses == "device" else None
         from .. import _native   # raises if libazgym_hip.so is missing
 
         # the native trainer first: if it cannot be created, the agents are left as they were
@@ -253,7 +263,15 @@ class PopulationTrainer:
                 off += p.numel()
         self.grads = torch.zeros_like(self.flat) if keep_grads else None
         self.log_alpha, self.alpha_optimizer = None, None
-        if type(self.loss) is A0CLossTuned:
+        self.alpha_exp_avg, self.alpha_exp_avg_sq, self.alpha_step = None, None, 0
+        if type(self.loss) is A0CLossTuned and losses == "device":
+            self.log_alpha = torch.stack([a.loss.log_alpha.detach().to(device, dtype=torch.float32) for a in self.agents]).contiguous()
+            self.alpha_exp_avg, self.alpha_exp_avg_sq = torch.zeros_like(self.log_alpha), torch.zeros_like(self.log_alpha)
+            if any(alpha_states):
+                self.alpha_step = int(float(alpha_states[0]["step"]))
+                self.alpha_exp_avg = torch.stack([s["exp_avg"].to(device, dtype=torch.float32) for s in alpha_states]).contiguous()
+                self.alpha_exp_avg_sq = torch.stack([s["exp_avg_sq"].to(device, dtype=torch.float32) for s in alpha_states]).contiguous()
+        elif type(self.loss) is A0CLossTuned:
             self.log_alpha = torch.stack([a.loss.log_alpha.detach().to(device) for a in self.agents]).requires_grad_(True)
             g = a0.loss.optimizer.param_groups[0]
             self.alpha_optimizer = torch.optim.Adam([self.log_alpha], lr=g["lr"], betas=g["betas"], eps=g["eps"],
@@ -264,6 +282,18 @@ class PopulationTrainer:
                     "exp_avg": torch.stack([s["exp_avg"].to(device) for s in alpha_states]),
                     "exp_avg_sq": torch.stack([s["exp_avg_sq"].to(device) for s in alpha_states])}
         self.last_raw: Optional[torch.Tensor] = None
+        self._last_d_raw: Optional[torch.Tensor] = None
+
+    @property
+    def last_d_raw(self) -> Optional[torch.Tensor]:
+        """d loss_k / d raw[k] of the last ``update``, [K, B, 1 + n_dist] (with ``losses="device"`` it stays in the native trainer
+        and is copied out when asked for)."""
+        if self._last_d_raw is None and self.last_raw is not None and self.losses == "device":
+            d = torch.empty_like(self.last_raw)
+            torch.cuda.current_stream(self.device).synchronize()
+            self.trainer.read_d_raw(d.shape[1], d.data_ptr())
+            self._last_d_raw = d
+        return self._last_d_raw
 
     def __len__(self) -> int:
         return len(self.agents)
@@ -295,18 +325,39 @@ class PopulationTrainer:
         states = states.reshape(K, B, -1)
         raw = torch.empty((K, B, self.trainer.n_raw), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device)
+        if self.losses == "device":
+            return self._update_device(states, actions, counts, values, raw, stream)
         stream.synchronize()
         self.trainer.forward(self.flat.data_ptr(), states.data_ptr(), B, raw.data_ptr())
         self.last_raw = raw
         raw.requires_grad_(True)
         losses = population_loss(self.policy, self.loss, raw, actions, counts, values, self.log_alpha, self.alpha_optimizer)
         losses["loss"].sum().backward()
-        d_raw = raw.grad.contiguous()
+        d_raw = self._last_d_raw = raw.grad.contiguous()
         out = per_net(losses)   # (the copy to the host also completes d_raw)
         stream.synchronize()
         self.trainer.backward_step(self.flat.data_ptr(), d_raw.data_ptr(), B, self.opt, self.square_avg.data_ptr(),
                                    self.grads.data_ptr() if self.grads is not None else None)
         return out
+
+    def _update_device(self, states, actions, counts, values, raw, stream) -> List[Dict[str, float]]:
+        """``update`` with the losses on the device: one native call (three launches), one copy of losses[K, 5] to the host."""
+        K, B = raw.shape[0], raw.shape[1]
+        actions, counts = actions.reshape(K, B, -1), counts.reshape(K, B, -1)
+        table = torch.empty((K, len(_capi.LOSS_KEYS)), dtype=torch.float32, device=self.device)
+        tuned = self.log_alpha is not None
+        state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
+                                  self.alpha_exp_avg_sq.data_ptr()) if tuned else None
+        stream.synchronize()
+        self.trainer.step(self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), B,
+                          actions.shape[2], self.loss_cfg, state, self.opt, self.square_avg.data_ptr(),
+                          self.grads.data_ptr() if self.grads is not None else None, raw.data_ptr(), table.data_ptr())
+        if tuned:
+            self.alpha_step += 1
+        self.last_raw, self._last_d_raw = raw, None
+        rows = table.cpu().tolist()
+        slots = [(key, _capi.LOSS_KEYS.index(key)) for key in _capi.LOSS_KEYS_OF[self.loss_cfg.kind]]
+        return [{key: row[i] for key, i in slots} for row in rows]
 
     def train_on_rows(self, rows_per_net, state_dim: int, K: int, batch_size: int = 32,
                       shuffle_seeds: Optional[Sequence[int]] = None) -> List[Dict[str, float]]:
@@ -340,7 +391,10 @@ class PopulationTrainer:
         between ``update`` calls the agents' own ``loss.log_alpha`` / ``loss.alpha`` are stale until it is called."""
         if self.log_alpha is None:
             return
-        state = self.alpha_optimizer.state.get(self.log_alpha, {})
+        if self.alpha_optimizer is None:   # losses="device": the trainer's own tensors
+            state = {"step": float(self.alpha_step), "exp_avg": self.alpha_exp_avg, "exp_avg_sq": self.alpha_exp_avg_sq} if self.alpha_step else {}
+        else:
+            state = self.alpha_optimizer.state.get(self.log_alpha, {})
         with torch.no_grad():
             for k, a in enumerate(self.agents):
                 la = a.loss.log_alpha

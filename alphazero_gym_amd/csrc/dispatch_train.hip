@@ -1,4 +1,5 @@
-// dispatch_train.hip -- the population trainer's C ABI (include/azgym_train.h): scratch, checks and the two launches of train.cuh.
+// dispatch_train.hip -- the population trainer's C ABI (include/azgym_train.h): scratch, checks and the three launches of train.cuh.
+#include <cmath>
 #include <string>
 
 #include "../../include/azgym_train.h"
@@ -9,8 +10,16 @@ struct azg_trainer {
     int device_id = 0;
     int n_nets = 0, max_batch = 0;
     int fwd_rows = 0;            // rows of the last azg_trainer_forward (0: none)
+    int step_rows = 0;           // rows of the d_raw the last azg_trainer_step left in d_raw_buf (0: none)
+    int num_components = 0;
+    float log_std_min = 0.0f, log_std_max = 0.0f;
     TrainDims d{};
     float* scratch = nullptr;
+    // the loss kernel's: the rows' terms [n_nets][3][max_batch] (float64), and azg_trainer_step's raw and d_raw [n_nets][max_batch][NO]
+    // (allocated by the first call that needs them)
+    double* loss_rows = nullptr;
+    float* raw_buf = nullptr;
+    float* d_raw_buf = nullptr;
     hipStream_t stream = nullptr;
     std::string err;
 };
@@ -34,6 +43,9 @@ void azg_trainer_destroy(azg_trainer* t) {
     DeviceScope scope(t->device_id);
     if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
     if (t->scratch) (void)hipFree(t->scratch);
+    if (t->loss_rows) (void)hipFree(t->loss_rows);
+    if (t->raw_buf) (void)hipFree(t->raw_buf);
+    if (t->d_raw_buf) (void)hipFree(t->d_raw_buf);
     delete t;
 }
 
@@ -56,6 +68,9 @@ int azg_trainer_create(int32_t device_id, const azg_mlp_desc* desc, int32_t n_ne
     t->device_id = device_id;
     t->n_nets = n_nets;
     t->max_batch = max_batch;
+    t->num_components = desc->num_components;
+    t->log_std_min = desc->log_std_min;
+    t->log_std_max = desc->log_std_max;
     TrainDims& d = t->d;
     d.n_layers = desc->n_hidden; d.in_dim = desc->in_dim; d.nd = desc->n_dist; d.NO = 1 + desc->n_dist; d.act = desc->activation;
     const size_t Bmax = ((size_t)max_batch + 15) / 16 * 16;
@@ -93,18 +108,134 @@ int azg_trainer_create(int32_t device_id, const azg_mlp_desc* desc, int32_t n_ne
     return AZG_OK;
 }
 
+// ---- each call in three parts: its checks (nothing launched, nothing written), its launch, and the public entry point ----
+
+static int check_forward(azg_trainer* t, const char* who, const float* params, const float* obs, int32_t n_rows) {
+    if (!params || !obs) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
+    if (n_rows < 1 || n_rows > t->max_batch) return tfail(t, AZG_E_INVALID, std::string(who) + ": n_rows must be 1..max_batch");
+    return AZG_OK;
+}
+
+static void launch_forward(azg_trainer* t, const float* params, const float* obs, int n_rows, float* raw) {
+    hipLaunchKernelGGL(train_forward_kernel, dim3((n_rows + 15) / 16, t->n_nets), dim3(64), 0, t->stream, t->d, params, obs, n_rows, raw,
+                       t->scratch);
+}
+
+static int check_backward(azg_trainer* t, const char* who, const float* params, const azg_rmsprop* opt, const float* square_avg,
+                          int32_t n_rows) {
+    const std::string w(who);
+    if (!params || !opt || !square_avg) return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
+    if (opt->struct_size != (int32_t)sizeof(azg_rmsprop)) return tfail(t, AZG_E_INVALID, w + ": azg_rmsprop.struct_size mismatch");
+    if (n_rows < 1 || n_rows > t->max_batch) return tfail(t, AZG_E_INVALID, w + ": n_rows must be 1..max_batch");
+    if (opt->momentum != 0.0 || opt->centered) return tfail(t, AZG_E_UNSUPPORTED, w + ": RMSprop with momentum or centered is not built");
+    if (opt->grad_clip != 0.0) return tfail(t, AZG_E_UNSUPPORTED, w + ": gradient clipping is not built (a per-net global norm needs a pass of its own)");
+    return AZG_OK;
+}
+
+static void launch_backward(azg_trainer* t, float* params, const float* d_raw, int n_rows, const azg_rmsprop* opt, float* square_avg,
+                            float* grads) {
+    TrainOpt o;
+    o.lr = (float)opt->lr; o.alpha = (float)opt->alpha; o.one_minus_alpha = (float)(1.0 - opt->alpha); o.eps = (float)opt->eps;
+    o.wd = (float)opt->weight_decay;
+    hipLaunchKernelGGL(train_backward_kernel, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, o, params, d_raw, n_rows,
+                       square_avg, grads, t->scratch);
+}
+
+// The loss settings as the kernel takes them; every refusal of azg_trainer_loss.
+static int check_loss(azg_trainer* t, const char* who, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* cfg,
+                      const azg_alpha_state* st, LossDims* out) {
+    const std::string w(who);
+    if (!cfg) return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
+    if (cfg->struct_size != (int32_t)sizeof(azg_loss_cfg)) return tfail(t, AZG_E_INVALID, w + ": azg_loss_cfg.struct_size mismatch");
+    if (n_rows < 1 || n_rows > t->max_batch) return tfail(t, AZG_E_INVALID, w + ": n_rows must be 1..max_batch");
+    if (n_actions < 1 || n_actions > TR_MAX_ACTIONS) return tfail(t, AZG_E_INVALID, w + ": n_actions must be 1..16");
+    if (cfg->kind != AZG_LOSS_ALPHAZERO && cfg->kind != AZG_LOSS_A0C && cfg->kind != AZG_LOSS_A0C_TUNED)
+        return tfail(t, AZG_E_UNSUPPORTED, w + ": unknown loss kind");
+    if (cfg->head != AZG_HEAD_DISCRETE && cfg->head != AZG_HEAD_NORMAL && cfg->head != AZG_HEAD_GMM)
+        return tfail(t, AZG_E_UNSUPPORTED, w + ": unknown head kind");
+    if (cfg->reduction != AZG_REDUCE_MEAN && cfg->reduction != AZG_REDUCE_SUM) return tfail(t, AZG_E_UNSUPPORTED, w + ": reduction must be mean or sum");
+    if (cfg->kind == AZG_LOSS_ALPHAZERO && cfg->head != AZG_HEAD_DISCRETE)
+        return tfail(t, AZG_E_UNSUPPORTED, w + ": AlphaZeroLoss needs a discrete head");
+    const int nd = t->d.nd;
+    int C = 1;
+    if (cfg->head == AZG_HEAD_GMM) {
+        C = t->num_components;
+        if (C > TR_MAX_COMP) return tfail(t, AZG_E_UNSUPPORTED, w + ": at most 5 mixture components");
+        if (C < 1 || nd != 3 * C) return tfail(t, AZG_E_UNSUPPORTED, w + ": a mixture head needs n_dist = 3 * num_components (one-dimensional actions)");
+    }
+    if (cfg->head == AZG_HEAD_NORMAL && nd != 2) return tfail(t, AZG_E_UNSUPPORTED, w + ": a Normal head needs n_dist = 2 (one-dimensional actions)");
+    if (cfg->kind == AZG_LOSS_ALPHAZERO && n_actions != nd) return tfail(t, AZG_E_INVALID, w + ": AlphaZeroLoss needs n_actions = n_dist");
+    if (!(cfg->action_bound >= 0.0)) return tfail(t, AZG_E_INVALID, w + ": action_bound must be >= 0");
+    const bool tuned = cfg->kind == AZG_LOSS_A0C_TUNED;
+    if (tuned) {
+        if (!st) return tfail(t, AZG_E_INVALID, w + ": A0CLossTuned needs an azg_alpha_state");
+        if (st->struct_size != (int32_t)sizeof(azg_alpha_state)) return tfail(t, AZG_E_INVALID, w + ": azg_alpha_state.struct_size mismatch");
+        if (!st->log_alpha || !st->exp_avg || !st->exp_avg_sq) return tfail(t, AZG_E_INVALID, w + ": NULL pointer in azg_alpha_state");
+        if (st->step < 0) return tfail(t, AZG_E_INVALID, w + ": azg_alpha_state.step must be >= 0");
+    }
+    LossDims c{};
+    c.kind = cfg->kind; c.head = cfg->head; c.nd = nd; c.C = C; c.A = n_actions;
+    c.squashed = cfg->head != AZG_HEAD_DISCRETE && cfg->action_bound > 0.0;
+    c.tau = cfg->tau; c.lmin = t->log_std_min; c.lmax = t->log_std_max;
+    if (c.squashed) {
+        const double eps = 1e-6, b = cfg->action_bound;   // SquashedNormal's epsilon
+        c.bpe = b + eps;
+        c.corr = 1.0 + eps / b;
+        // log|det J| counts log(bound) x.shape[-1] times: the row's actions for the Normal head, 1 for the mixture's components
+        c.ladj0 = (cfg->head == AZG_HEAD_NORMAL ? (double)n_actions : 1.0) * std::log(b);
+    }
+    const bool mean = cfg->reduction == AZG_REDUCE_MEAN;
+    const double B = (double)n_rows;
+    c.pc = cfg->policy_coeff; c.vc = cfg->value_coeff;
+    c.red = mean ? 1.0 / B : 1.0;
+    c.inv_rows = 1.0 / B;
+    // the discrete head's entropy is [B][A], every action of a row carrying the row's entropy: its mean is the mean over the rows,
+    // its sum A times their sum
+    c.ent_red = mean ? 1.0 / B : (cfg->head == AZG_HEAD_DISCRETE ? (double)n_actions : 1.0);
+    c.cP = c.pc * c.red; c.cV = c.vc * c.red; c.cE = cfg->kind == AZG_LOSS_ALPHAZERO ? 0.0 : c.ent_red;
+    c.alpha = cfg->alpha; c.target = cfg->target_entropy;
+    if (tuned) {
+        const double step = (double)st->step + 1.0;
+        c.lr = cfg->alpha_lr; c.b1 = cfg->alpha_beta1; c.b2 = cfg->alpha_beta2; c.eps = cfg->alpha_eps; c.wd = cfg->alpha_weight_decay;
+        c.clip = cfg->alpha_clip;
+        c.bc1 = 1.0 - std::pow(c.b1, step);
+        c.bc2_sqrt = std::sqrt(1.0 - std::pow(c.b2, step));
+    }
+    *out = c;
+    return AZG_OK;
+}
+
+static int ensure(azg_trainer* t, void** buf, size_t bytes) {
+    if (*buf) return AZG_OK;
+    const hipError_t rc = hipMalloc(buf, bytes);
+    if (rc != hipSuccess) { *buf = nullptr; return tfail(t, AZG_E_DEVICE, std::string("azg_trainer: ") + hipGetErrorString(rc)); }
+    return AZG_OK;
+}
+
+static void launch_loss(azg_trainer* t, const LossDims& c, const float* raw, const float* actions, const float* counts, const float* values,
+                        int n_rows, const azg_alpha_state* st, float* d_raw, float* losses) {
+    const bool tuned = c.kind == AZG_LOSS_A0C_TUNED;
+    hipLaunchKernelGGL(train_loss_kernel, dim3(t->n_nets), dim3(TR_LOSS_THREADS), 0, t->stream, c, raw, actions, counts, values, n_rows,
+                       tuned ? st->log_alpha : nullptr, tuned ? st->exp_avg : nullptr, tuned ? st->exp_avg_sq : nullptr, d_raw, losses,
+                       t->loss_rows, t->max_batch);
+}
+
+static int finish(azg_trainer* t, const char* who) {
+    hipError_t rc = hipGetLastError();
+    if (rc == hipSuccess) rc = hipStreamSynchronize(t->stream);
+    if (rc != hipSuccess) return tfail(t, AZG_E_DEVICE, std::string(who) + ": " + hipGetErrorString(rc));
+    return AZG_OK;
+}
+
 int azg_trainer_forward(azg_trainer* t, const float* params, const float* obs, int32_t n_rows, float* raw) {
     if (!t) return AZG_E_INVALID;
-    if (!params || !obs || !raw) return tfail(t, AZG_E_INVALID, "azg_trainer_forward: NULL pointer");
-    if (n_rows < 1 || n_rows > t->max_batch) return tfail(t, AZG_E_INVALID, "azg_trainer_forward: n_rows must be 1..max_batch");
+    if (!raw) return tfail(t, AZG_E_INVALID, "azg_trainer_forward: NULL pointer");
+    if (int rc = check_forward(t, "azg_trainer_forward", params, obs, n_rows)) return rc;
     DeviceScope scope(t->device_id);
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
     t->fwd_rows = 0;
-    hipLaunchKernelGGL(train_forward_kernel, dim3((n_rows + 15) / 16, t->n_nets), dim3(64), 0, t->stream, t->d, params, obs, (int)n_rows, raw,
-                       t->scratch);
-    hipError_t rc = hipGetLastError();
-    if (rc == hipSuccess) rc = hipStreamSynchronize(t->stream);
-    if (rc != hipSuccess) return tfail(t, AZG_E_DEVICE, std::string("azg_trainer_forward: ") + hipGetErrorString(rc));
+    launch_forward(t, params, obs, (int)n_rows, raw);
+    if (int rc = finish(t, "azg_trainer_forward")) return rc;
     t->fwd_rows = n_rows;
     return AZG_OK;
 }
@@ -112,24 +243,64 @@ int azg_trainer_forward(azg_trainer* t, const float* params, const float* obs, i
 int azg_trainer_backward_step(azg_trainer* t, float* params, const float* d_raw, int32_t n_rows, const azg_rmsprop* opt, float* square_avg,
                               float* grads) {
     if (!t) return AZG_E_INVALID;
-    if (!params || !d_raw || !opt || !square_avg) return tfail(t, AZG_E_INVALID, "azg_trainer_backward_step: NULL pointer");
-    if (opt->struct_size != (int32_t)sizeof(azg_rmsprop)) return tfail(t, AZG_E_INVALID, "azg_trainer_backward_step: azg_rmsprop.struct_size mismatch");
-    if (n_rows < 1 || n_rows > t->max_batch) return tfail(t, AZG_E_INVALID, "azg_trainer_backward_step: n_rows must be 1..max_batch");
-    if (opt->momentum != 0.0 || opt->centered) return tfail(t, AZG_E_UNSUPPORTED, "azg_trainer_backward_step: RMSprop with momentum or centered is not built");
-    if (opt->grad_clip != 0.0) return tfail(t, AZG_E_UNSUPPORTED, "azg_trainer_backward_step: gradient clipping is not built (a per-net global norm needs a pass of its own)");
+    if (!d_raw) return tfail(t, AZG_E_INVALID, "azg_trainer_backward_step: NULL pointer");
+    if (int rc = check_backward(t, "azg_trainer_backward_step", params, opt, square_avg, n_rows)) return rc;
     if (t->fwd_rows != n_rows) return tfail(t, AZG_E_STATE, "azg_trainer_backward_step: needs azg_trainer_forward of the same n_rows first");
     DeviceScope scope(t->device_id);
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
-    TrainOpt o;
-    o.lr = (float)opt->lr; o.alpha = (float)opt->alpha; o.one_minus_alpha = (float)(1.0 - opt->alpha); o.eps = (float)opt->eps;
-    o.wd = (float)opt->weight_decay;
     t->fwd_rows = 0;   // the scratch is consumed: dZ overwrites the activation derivatives
-    hipLaunchKernelGGL(train_backward_kernel, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, o, params, d_raw, (int)n_rows,
-                       square_avg, grads, t->scratch);
-    hipError_t rc = hipGetLastError();
-    if (rc == hipSuccess) rc = hipStreamSynchronize(t->stream);
-    if (rc != hipSuccess) return tfail(t, AZG_E_DEVICE, std::string("azg_trainer_backward_step: ") + hipGetErrorString(rc));
+    launch_backward(t, params, d_raw, (int)n_rows, opt, square_avg, grads);
+    return finish(t, "azg_trainer_backward_step");
+}
+
+int azg_trainer_loss(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values, int32_t n_rows,
+                     int32_t n_actions, const azg_loss_cfg* cfg, const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
+    if (!t) return AZG_E_INVALID;
+    if (!raw || !actions || !counts || !values || !d_raw || !losses) return tfail(t, AZG_E_INVALID, "azg_trainer_loss: NULL pointer");
+    LossDims c;
+    if (int rc = check_loss(t, "azg_trainer_loss", n_rows, n_actions, cfg, alpha_state, &c)) return rc;
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    if (int rc = ensure(t, (void**)&t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch * sizeof(double))) return rc;
+    launch_loss(t, c, raw, actions, counts, values, (int)n_rows, alpha_state, d_raw, losses);
+    return finish(t, "azg_trainer_loss");
+}
+
+int azg_trainer_step(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
+                     int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
+                     const azg_rmsprop* opt, float* square_avg, float* grads, float* raw_out, float* losses) {
+    if (!t) return AZG_E_INVALID;
+    if (!actions || !counts || !values || !losses) return tfail(t, AZG_E_INVALID, "azg_trainer_step: NULL pointer");
+    if (int rc = check_forward(t, "azg_trainer_step", params, obs, n_rows)) return rc;
+    LossDims c;
+    if (int rc = check_loss(t, "azg_trainer_step", n_rows, n_actions, loss_cfg, alpha_state, &c)) return rc;
+    if (int rc = check_backward(t, "azg_trainer_step", params, opt, square_avg, n_rows)) return rc;
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    const size_t per = (size_t)t->n_nets * t->max_batch * t->d.NO;
+    if (int rc = ensure(t, (void**)&t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch * sizeof(double))) return rc;
+    if (int rc = ensure(t, (void**)&t->d_raw_buf, per * sizeof(float))) return rc;
+    if (!raw_out) { if (int rc = ensure(t, (void**)&t->raw_buf, per * sizeof(float))) return rc; }
+    float* raw = raw_out ? raw_out : t->raw_buf;
+    t->fwd_rows = 0;
+    t->step_rows = 0;
+    launch_forward(t, params, obs, (int)n_rows, raw);
+    launch_loss(t, c, raw, actions, counts, values, (int)n_rows, alpha_state, t->d_raw_buf, losses);
+    launch_backward(t, params, t->d_raw_buf, (int)n_rows, opt, square_avg, grads);
+    if (int rc = finish(t, "azg_trainer_step")) return rc;
+    t->step_rows = n_rows;
     return AZG_OK;
+}
+
+int azg_trainer_read_d_raw(azg_trainer* t, int32_t n_rows, float* d_raw) {
+    if (!t) return AZG_E_INVALID;
+    if (!d_raw) return tfail(t, AZG_E_INVALID, "azg_trainer_read_d_raw: NULL pointer");
+    if (n_rows < 1 || t->step_rows != n_rows) return tfail(t, AZG_E_STATE, "azg_trainer_read_d_raw: needs an azg_trainer_step of the same n_rows first");
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    const hipError_t rc = hipMemcpyAsync(d_raw, t->d_raw_buf, (size_t)t->n_nets * n_rows * t->d.NO * sizeof(float), hipMemcpyDeviceToDevice, t->stream);
+    if (rc != hipSuccess) return tfail(t, AZG_E_DEVICE, std::string("azg_trainer_read_d_raw: ") + hipGetErrorString(rc));
+    return finish(t, "azg_trainer_read_d_raw");
 }
 
 }  // extern "C"

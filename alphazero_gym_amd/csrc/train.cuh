@@ -7,10 +7,14 @@
 // inside a block, MFMA step s = 0..3 adds the products of k = kk + s, kk + 4 + s, kk + 8 + s, kk + 12 + s (the four lane groups).
 // For dW the k axis is the batch row, so batch tiles are summed in tile order.  db sums rows r = 0, 4, 8, ... / 1, 5, ... / 2, ... /
 // 3, ... in four float64 chains, combined (s0 + s1) + (s2 + s3) and rounded once.
+//
+// train_loss_kernel (the losses between the two): one lane per row computes the row's loss terms and its d_raw in float64 from the
+// float32 inputs (d_raw rounded once per element); the sums over the rows are the same four float64 chains, rounded once.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/azg_math.h"
 #include "../../include/azgym.h"
+#include "../../include/azgym_train.h"
 
 typedef float tr_f32x4 __attribute__((ext_vector_type(4)));
 
@@ -157,15 +161,17 @@ __device__ __forceinline__ void tr_update(const TrainOpt& o, float* p, float* sq
 // sum over rows of one column, x(row): four interleaved float64 chains combined (s0 + s1) + (s2 + s3), rounded to float32 once
 // (a bias gradient is a plain sum of B float32 values: in float64 it is exact to the last bit for any B the trainer takes)
 template <class F>
-__device__ __forceinline__ float tr_colsum(int rows, F x) {
+__device__ __forceinline__ double tr_colsum64(int rows, F x) {
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     int rr = 0;
     for (; rr + 4 <= rows; rr += 4) { s0 = s0 + (double)x(rr); s1 = s1 + (double)x(rr + 1); s2 = s2 + (double)x(rr + 2); s3 = s3 + (double)x(rr + 3); }
     if (rr < rows) s0 = s0 + (double)x(rr);
     if (rr + 1 < rows) s1 = s1 + (double)x(rr + 1);
     if (rr + 2 < rows) s2 = s2 + (double)x(rr + 2);
-    return (float)((s0 + s1) + (s2 + s3));
+    return (s0 + s1) + (s2 + s3);
 }
+template <class F>
+__device__ __forceinline__ float tr_colsum(int rows, F x) { return (float)tr_colsum64(rows, x); }
 
 // One workgroup per net.  Per layer, from the heads down: (a) dA of the layer below = dZ W, times act' -> dZ of the layer below
 // (in place over D); barrier; (b) dW = dZ^T A_below, db, and the optimiser step of this layer's parameters.  (a) reads the layer's
@@ -254,4 +260,202 @@ __global__ __launch_bounds__(TR_BWD_THREADS) void train_backward_kernel(TrainDim
             tr_update(opt, p, sq, grads, idx, gsum);
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------ losses
+// agent/population_trainer.py's population_terms / population_loss as one kernel: per row the summands of the losses and
+// d loss_k / d raw by hand, then per net the reductions over the rows and, for the tuned loss, the Adam step of log_alpha.
+#define TR_LOSS_THREADS 256
+#define TR_MAX_ACTIONS 16
+#define TR_MAX_COMP 5
+
+struct LossDims {
+    int kind, head, nd, C, A, squashed;
+    float lmin, lmax;
+    double tau;
+    double bpe, corr, ladj0;         // SquashedNormal: bound + epsilon, 1 + epsilon / bound, x.shape[-1] * log(bound)
+    double cP, cV, cE;               // d loss / d (a row's policy term, squared error, entropy term), alpha not included
+    // the reductions (float64): policy_coeff, value_coeff, 1/B or 1, the entropy's reduction factor, 1/B, alpha, target entropy
+    double pc, vc, red, ent_red, inv_rows, alpha, target;
+    // Adam of log_alpha: bc1 = 1 - beta1^step, bc2_sqrt = sqrt(1 - beta2^step) of the step being taken
+    double lr, b1, b2, eps, wd, clip, bc1, bc2_sqrt;
+};
+
+// torch's softplus (beta 1, threshold 20)
+__device__ __forceinline__ double tr_softplus(double t) { return t > 20.0 ? t : log1p(exp(t)); }
+
+// One row: terms[0] the policy summand, terms[1] the squared value error, terms[2] the entropy summand; d[0 .. nd] = d loss / d raw.
+// z = raw + 1 is the distribution head.  The row's arithmetic is float64 from the float32 inputs, every sum over its actions and
+// components a chain in index order; d is rounded to float32 once per element.  (In float32 the row terms carry the 2^-24 of expf /
+// logf into sums that the float32 PyTorch path sometimes happens to hit exactly: DESIGN section 3.)
+__device__ __forceinline__ void tr_loss_row(const LossDims& c, double alpha, const float* raw, const float* act, const float* cnt, float v,
+                                            float* d, double (&terms)[3]) {
+    const double dv = (double)raw[0] - (double)v;
+    terms[1] = dv * dv;
+    d[0] = (float)(c.cV * (2.0 * dv));
+    const float* z = raw + 1;
+    const double aE = alpha * c.cE;
+    if (c.head == AZG_HEAD_DISCRETE) {
+        const int n = c.nd;
+        float mf = z[0];
+        for (int j = 1; j < n; ++j) mf = z[j] > mf ? z[j] : mf;
+        const double m = (double)mf;
+        double se = 0.0;
+        for (int j = 0; j < n; ++j) se = se + exp((double)z[j] - m);
+        const double lse = m + log(se);
+        if (c.kind == AZG_LOSS_ALPHAZERO) {
+            int t = 0;   // argmax of softmax(counts) = argmax of counts, the lowest index among equals
+            for (int i = 1; i < c.A; ++i) if (cnt[i] > cnt[t]) t = i;
+            terms[0] = -((double)z[t] - lse);
+            terms[2] = 0.0;
+            for (int j = 0; j < n; ++j) d[1 + j] = (float)(c.cP * (exp((double)z[j] - lse) - (j == t ? 1.0 : 0.0)));
+            return;
+        }
+        // log pi_i = lsm[a_i]; W[j] = the sum of the detached factors w_i = log pi_i - tau log(counts_i + 1) of the actions i with a_i = j
+        double W[TR_MAX_ACTIONS];
+#pragma unroll
+        for (int j = 0; j < TR_MAX_ACTIONS; ++j) W[j] = 0.0;
+        double pol = 0.0, wsum = 0.0;
+        for (int i = 0; i < c.A; ++i) {
+            int idx = (int)act[i];
+            idx = idx < 0 ? 0 : (idx >= n ? n - 1 : idx);
+            const double lp = (double)z[idx] - lse;
+            const double w = lp - c.tau * log((double)cnt[i] + 1.0);
+            pol = pol + w * lp;
+            wsum = wsum + w;
+#pragma unroll
+            for (int j = 0; j < TR_MAX_ACTIONS; ++j) W[j] = W[j] + (j == idx ? w : 0.0);
+        }
+        double H = 0.0;
+        for (int j = 0; j < n; ++j) { const double l = (double)z[j] - lse; H = H - exp(l) * l; }
+        terms[0] = pol;
+        terms[2] = H;
+#pragma unroll
+        for (int j = 0; j < TR_MAX_ACTIONS; ++j) {
+            if (j < n) {
+                const double l = (double)z[j] - lse, pj = exp(l);
+                d[1 + j] = (float)(c.cP * (W[j] - pj * wsum) - aE * (pj * (l + H)));
+            }
+        }
+        return;
+    }
+    // squashed Normal (C = 1) or mixture of C of them: z = mu[C] | log_std[C] ( | log_coeff[C])
+    const int C = c.C;
+    const bool gmm = c.head == AZG_HEAD_GMM;
+    double mu[TR_MAX_COMP], ls[TR_MAX_COMP], iv[TR_MAX_COMP], lmix[TR_MAX_COMP];
+    double dmu[TR_MAX_COMP], dls[TR_MAX_COMP], dlc[TR_MAX_COMP];
+    bool gate[TR_MAX_COMP];
+    float lcm = 0.0f;
+    if (gmm) { lcm = z[2 * C]; for (int k = 1; k < C; ++k) lcm = z[2 * C + k] > lcm ? z[2 * C + k] : lcm; }
+    double se = 0.0;
+#pragma unroll
+    for (int k = 0; k < TR_MAX_COMP; ++k) {
+        const bool on = k < C;
+        mu[k] = on ? (double)z[k] : 0.0;
+        const float l = on ? z[C + k] : 0.0f;
+        gate[k] = l >= c.lmin && l <= c.lmax;               // torch.clamp passes the gradient inside [min, max], ends included
+        ls[k] = (double)(l < c.lmin ? c.lmin : (l > c.lmax ? c.lmax : l));
+        iv[k] = exp(-2.0 * ls[k]);                          // 1 / sigma^2
+        lmix[k] = (on && gmm) ? (double)z[2 * C + k] - (double)lcm : 0.0;
+        if (on && gmm) se = se + exp(lmix[k]);
+        dmu[k] = 0.0; dls[k] = 0.0; dlc[k] = 0.0;
+    }
+    const double lse = gmm ? log(se) : 0.0;
+#pragma unroll
+    for (int k = 0; k < TR_MAX_COMP; ++k) lmix[k] = (k < C && gmm) ? lmix[k] - lse : 0.0;
+    double pol = 0.0, lpsum = 0.0;
+    const double inv_A = 1.0 / (double)c.A;
+    for (int i = 0; i < c.A; ++i) {
+        double x = (double)act[i], ladj = 0.0;
+        if (c.squashed) {
+            x = atanh(x / c.bpe);
+            const double cx = c.corr * x;
+            ladj = c.ladj0 + 2.0 * ((0.693147180559945286 - cx) - tr_softplus(-2.0 * cx));
+        }
+        double s[TR_MAX_COMP], sm = -1.0e300;
+#pragma unroll
+        for (int k = 0; k < TR_MAX_COMP; ++k) {
+            const double dx = x - mu[k];
+            s[k] = (((-0.5 * (dx * dx * iv[k]) - ls[k]) - 0.918938533204672742) - ladj) + lmix[k];
+            if (k < C) sm = s[k] > sm ? s[k] : sm;
+        }
+        double lp = s[0];
+        if (gmm) {
+            double e = 0.0;
+#pragma unroll
+            for (int k = 0; k < TR_MAX_COMP; ++k) if (k < C) e = e + exp(s[k] - sm);
+            lp = sm + log(e);
+        }
+        const double w = lp - c.tau * log((double)cnt[i]);
+        pol = pol + w * lp;
+        lpsum = lpsum + lp;
+        const double g = c.cP * w - aE * inv_A;   // d loss / d log pi_i: the policy term's detached factor, the entropy's -1/A
+#pragma unroll
+        for (int k = 0; k < TR_MAX_COMP; ++k) {
+            if (k < C) {
+                const double r = gmm ? exp(s[k] - lp) : 1.0;   // the component's responsibility
+                const double dx = x - mu[k], q = dx * dx * iv[k];
+                dmu[k] = dmu[k] + g * r * (dx * iv[k]);
+                dls[k] = dls[k] + g * r * (q - 1.0);
+                dlc[k] = dlc[k] + g * (r - exp(lmix[k]));
+            }
+        }
+    }
+    terms[0] = pol;
+    terms[2] = -lpsum * inv_A;
+#pragma unroll
+    for (int k = 0; k < TR_MAX_COMP; ++k) {
+        if (k < C) {
+            d[1 + k] = (float)dmu[k];
+            d[1 + C + k] = gate[k] ? (float)dls[k] : 0.0f;
+            if (gmm) d[1 + 2 * C + k] = (float)dlc[k];
+        }
+    }
+}
+
+// One workgroup per net, one lane per row (rows tid, tid + 256, ...).  rows: the trainer's float64 [n_nets][3][stride] array of the
+// rows' terms.  log_alpha[net] is read by every lane before the first barrier and written by lane 0 after the second.
+__global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_kernel(LossDims c, const float* raw, const float* actions, const float* counts,
+                                                                     const float* values, int n_rows, float* log_alpha, float* exp_avg,
+                                                                     float* exp_avg_sq, float* d_raw, float* losses, double* rows, int stride) {
+    const int net = blockIdx.x, tid = threadIdx.x, NO = 1 + c.nd;
+    const bool tuned = c.kind == AZG_LOSS_A0C_TUNED;
+    const float la = tuned ? log_alpha[net] : 0.0f;
+    const double alpha = tuned ? exp((double)la) : c.alpha;
+    double* rw = rows + (size_t)net * 3 * stride;
+    for (int row = tid; row < n_rows; row += TR_LOSS_THREADS) {
+        const size_t at = (size_t)net * n_rows + row;
+        double terms[3];
+        tr_loss_row(c, alpha, raw + at * NO, actions + at * c.A, counts + at * c.A, values[at], d_raw + at * NO, terms);
+        rw[row] = terms[0]; rw[stride + row] = terms[1]; rw[2 * stride + row] = terms[2];
+    }
+    __syncthreads();
+    __shared__ double sums[3];
+    if (tid < 3) sums[tid] = tr_colsum64(n_rows, [&](int r) { return rw[(size_t)tid * stride + r]; });
+    __syncthreads();
+    if (tid != 0) return;
+    float* out = losses + (size_t)net * AZG_LOSS_SLOTS;
+    const double policy = c.pc * (sums[0] * c.red), value = c.vc * (sums[1] * c.red);
+    if (c.kind == AZG_LOSS_ALPHAZERO) {
+        out[AZG_LOSS_TOTAL] = (float)(policy + value); out[AZG_LOSS_POLICY] = (float)policy; out[AZG_LOSS_VALUE] = (float)value;
+        out[AZG_LOSS_ENTROPY] = 0.0f; out[AZG_LOSS_ALPHA] = 0.0f;
+        return;
+    }
+    const double a = alpha;
+    const double entropy = a * (sums[2] * c.ent_red);
+    out[AZG_LOSS_TOTAL] = (float)((policy + entropy) + value); out[AZG_LOSS_POLICY] = (float)policy; out[AZG_LOSS_VALUE] = (float)value;
+    out[AZG_LOSS_ENTROPY] = (float)entropy;
+    if (!tuned) { out[AZG_LOSS_ALPHA] = 0.0f; return; }
+    // alpha_loss = mean(exp(log_alpha) * (entropy - target).detach()); its derivative by log_alpha is itself
+    const double alpha_loss = a * (sums[2] * c.inv_rows - c.target);
+    out[AZG_LOSS_ALPHA] = (float)alpha_loss;
+    double g = alpha_loss;
+    if (c.clip != 0.0) { const double f = c.clip / (fabs(g) + 1e-6); g = g * (f < 1.0 ? f : 1.0); }
+    double p = (double)la;
+    if (c.wd != 0.0) g = g + c.wd * p;
+    const double m0 = (double)exp_avg[net];
+    const double m = m0 + (g - m0) * (1.0 - c.b1);
+    const double s = c.b2 * (double)exp_avg_sq[net] + (1.0 - c.b2) * g * g;
+    p = p - (c.lr / c.bc1) * (m / (sqrt(s) / c.bc2_sqrt + c.eps));
+    exp_avg[net] = (float)m; exp_avg_sq[net] = (float)s; log_alpha[net] = (float)p;
 }

@@ -4,7 +4,8 @@ Net k's games (--games-per-seed of them, global game ids k*T ...) are played on 
 (azg_population_selfplay_begin: one search launch and one self-play launch per step for the whole population); each iteration
 downloads the new replay rows, trains every net on its own rows with its own optimiser, one net after another, and re-uploads
 the changed nets (one gather launch for all of them when the nets live on the GPU).  --trainer device takes every net's
-minibatch step at once instead (agent.population_trainer.PopulationTrainer: two HIP launches per step for all nets).
+minibatch step at once instead (agent.population_trainer.PopulationTrainer: two HIP launches per step for all nets, the losses
+in PyTorch between them); --trainer device-fused computes the losses on the device too (three launches, one host round trip).
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
@@ -41,8 +42,9 @@ def parse_args(argv=None):
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--engine-seed", type=int, default=34, help="the engine's RNG seed (shared; games differ by their global ids)")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
-    ap.add_argument("--trainer", choices=["torch", "device"], default="torch",
-                    help="torch: agent.update net by net; device: every net's optimiser step in two HIP launches (PopulationTrainer)")
+    ap.add_argument("--trainer", choices=["torch", "device", "device-fused"], default="torch",
+                    help="torch: agent.update net by net; device: every net's optimiser step in two HIP launches (PopulationTrainer) with "
+                         "the losses in PyTorch between them; device-fused: the losses in a kernel of the same step (losses='device')")
     return ap.parse_args(argv)
 
 
@@ -70,9 +72,9 @@ def train(a, log=print, on_rows=None):
     on_gpu = a.device.startswith("cuda")
     fs0, fc0 = np.zeros(len(a.seeds)), np.zeros(len(a.seeds), np.int64)
     trainer = None
-    if a.trainer == "device":
+    if a.trainer != "torch":
         from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
-        trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size))
+        trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size), losses="device" if a.trainer == "device-fused" else "torch")
     t0 = time.time()
     history = []
     for it in range(a.iters):

@@ -1,4 +1,4 @@
-/* azgym_train.h -- population training: one minibatch optimiser step of K nets of one shape in two launches (an extension of
+/* azgym_train.h -- population training: one minibatch optimiser step of K nets of one shape in two launches, or three with the losses on the device too (an extension of
  * azgym.h; same ABI version).
  *
  * A trainer owns scratch only.  The nets' parameters, the RMSprop state and every batch tensor are the caller's device arrays on
@@ -10,13 +10,21 @@
  *   raw        [n_nets][n_rows][1 + n_dist]  value head, then the untransformed distribution head (azg_mlp_eval's `raw`)
  *   d_raw      [n_nets][n_rows][1 + n_dist]  d(loss of net k) / d raw
  *   grads      [n_nets][P]   (optional) the parameter gradients, before weight decay
+ *   actions    [n_nets][n_rows][n_actions]   the searched actions of every row (indices for a discrete head), n_actions <= 16
+ *   counts     [n_nets][n_rows][n_actions]   their visit counts
+ *   values     [n_nets][n_rows]              the value targets
+ *   losses     [n_nets][AZG_LOSS_SLOTS]      loss, policy_loss, value_loss, entropy_loss, alpha_loss (0 where a slot does not apply)
  * Device memory is shared the way azg_set_weights_device shares it: inputs are complete when a call is made (their producer's
- * stream synchronised), outputs are complete when it returns.  That is two synchronisations per minibatch step, whatever n_nets.
+ * stream synchronised), outputs are complete when it returns.  With the losses in PyTorch (azg_trainer_forward, autograd on raw,
+ * azg_trainer_backward_step) that is two synchronisations per minibatch step, whatever n_nets; azg_trainer_step takes the losses on
+ * the device as well (azg_trainer_loss's kernel between the two) and synchronises once.
  *
  * Supported nets: Linear + activation trunks of 1..3 hidden layers, widths multiples of 16 up to 256, in_dim <= 8, n_dist <= 16,
  * every AZG_ACT_* activation; no LayerNorm.  Anything else: AZG_E_UNSUPPORTED from azg_trainer_create.
  * The arithmetic is float32 on v_mfma_f32_16x16x4_f32 with a fixed summation order and no atomics: the same inputs give the same
- * bits on every run, and net k's results do not depend on n_nets.  Rows are padded to 16 inside; padded rows contribute nothing. */
+ * bits on every run, and net k's results do not depend on n_nets.  Rows are padded to 16 inside; padded rows contribute nothing.
+ * The loss kernel computes every row's terms in float64 from the float32 inputs and every sum over the rows as fixed-order float64
+ * chains; d_raw and the loss values are rounded to float32 once. */
 #ifndef AZGYM_TRAIN_H
 #define AZGYM_TRAIN_H
 #include "azgym.h"
@@ -59,6 +67,68 @@ int azg_trainer_forward(azg_trainer* t, const float* params, const float* obs, i
  * AZG_E_UNSUPPORTED.  On an error nothing is written. */
 int azg_trainer_backward_step(azg_trainer* t, float* params, const float* d_raw, int32_t n_rows, const azg_rmsprop* opt,
                               float* square_avg, float* grads);
+
+/* ---- the losses on the device (agent/population_trainer.py: population_terms / population_loss, restated as one kernel) ---- */
+
+enum { AZG_LOSS_ALPHAZERO = 0, AZG_LOSS_A0C = 1, AZG_LOSS_A0C_TUNED = 2 };
+enum { AZG_HEAD_DISCRETE = 0, AZG_HEAD_NORMAL = 1, AZG_HEAD_GMM = 2 };
+enum { AZG_REDUCE_MEAN = 0, AZG_REDUCE_SUM = 1 };
+/* slots of losses[k][] */
+enum { AZG_LOSS_TOTAL = 0, AZG_LOSS_POLICY = 1, AZG_LOSS_VALUE = 2, AZG_LOSS_ENTROPY = 3, AZG_LOSS_ALPHA = 4, AZG_LOSS_SLOTS = 5 };
+
+/* What the loss object and the policy carry beyond azg_mlp_desc (which gives n_dist, num_components and the log_std clamp).
+ *   AZG_LOSS_ALPHAZERO  policy_coeff * CE(logits, argmax counts, lowest index on ties) + value_coeff * MSE; discrete head only,
+ *                       n_actions == n_dist
+ *   AZG_LOSS_A0C        policy_coeff * reduce_rows(sum_i (log pi_i - tau log n_i).detach() * log pi_i) + alpha * reduce(entropy)
+ *                       + value_coeff * MSE;  n_i = counts_i + 1 for a discrete head
+ *   AZG_LOSS_A0C_TUNED  the same with alpha = exp(log_alpha[k]) from before the call, then one Adam step (torch.optim.Adam's
+ *                       single-tensor form, no amsgrad) of log_alpha[k] on alpha_loss = mean(alpha * (entropy - target_entropy)), its
+ *                       gradient scaled by min(alpha_clip / (|g| + 1e-6), 1) when alpha_clip != 0
+ * Heads: DISCRETE (Categorical over n_dist logits; actions are indices 0 .. n_dist - 1; entropy per (row, action) = the row's
+ * Categorical entropy), NORMAL (n_dist = 2: mu, log_std) and GMM (n_dist = 3 C: mu | log_std | log_coeff, C <= 5), both of
+ * one-dimensional actions squashed to (-action_bound, action_bound) as network/distributions.py's SquashedNormal computes it
+ * (action_bound == 0: a plain Normal); entropy per row = -mean_i log pi_i. */
+typedef struct azg_loss_cfg {
+    int32_t struct_size;
+    int32_t kind;        /* AZG_LOSS_* */
+    int32_t head;        /* AZG_HEAD_* */
+    int32_t reduction;   /* AZG_REDUCE_* */
+    double tau, policy_coeff, value_coeff;
+    double alpha;            /* AZG_LOSS_A0C */
+    double target_entropy;   /* AZG_LOSS_A0C_TUNED, and the Adam settings of log_alpha: */
+    double alpha_lr, alpha_beta1, alpha_beta2, alpha_eps, alpha_weight_decay, alpha_clip;
+    double action_bound;
+} azg_loss_cfg;
+
+/* AZG_LOSS_A0C_TUNED's state, the caller's device arrays [n_nets] float32, updated in place; `step` = the Adam steps taken before
+ * this call (the caller counts). */
+typedef struct azg_alpha_state {
+    int32_t struct_size;
+    int32_t step;
+    float* log_alpha;
+    float* exp_avg;
+    float* exp_avg_sq;
+} azg_alpha_state;
+
+/* The loss kernel alone, one launch for every net: from raw, the batch and the loss settings to d_raw = d loss_k / d raw[k] (what
+ * population_loss(...)["loss"].sum().backward() leaves in raw.grad) and losses; with AZG_LOSS_A0C_TUNED also the Adam step of
+ * log_alpha.  alpha_state is needed for AZG_LOSS_A0C_TUNED only (else it may be NULL).  NULL required pointers, n_rows outside
+ * 1..max_batch, n_actions outside 1..16 (or != n_dist with AZG_LOSS_ALPHAZERO), a struct_size mismatch: AZG_E_INVALID; an unknown
+ * kind / head / reduction, AZG_LOSS_ALPHAZERO with a continuous head, more than 5 components or an n_dist that does not fit the
+ * head: AZG_E_UNSUPPORTED.  On an error nothing is written. */
+int azg_trainer_loss(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values, int32_t n_rows,
+                     int32_t n_actions, const azg_loss_cfg* cfg, const azg_alpha_state* alpha_state, float* d_raw, float* losses);
+
+/* One whole minibatch step of every net: azg_trainer_forward, azg_trainer_loss and azg_trainer_backward_step enqueued back to back
+ * with one synchronisation at the end.  raw_out (may be NULL) receives raw; d_raw stays in the trainer (azg_trainer_read_d_raw).
+ * Every check of the three calls is made before the first launch: on an error nothing is written. */
+int azg_trainer_step(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
+                     int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
+                     const azg_rmsprop* opt, float* square_avg, float* grads, float* raw_out, float* losses);
+
+/* Copies the d_raw [n_nets][n_rows][1 + n_dist] of the last azg_trainer_step to the caller's device array (AZG_E_STATE if there
+ * was none of that n_rows). */
+int azg_trainer_read_d_raw(azg_trainer* t, int32_t n_rows, float* d_raw);
 
 #ifdef __cplusplus
 }

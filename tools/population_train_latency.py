@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""One minibatch optimiser step of K nets, two ways in the same process: the loop of K agent.update calls, and
-PopulationTrainer.update (two HIP launches + the losses in PyTorch), with the latter's split into forward launch, PyTorch loss
-part and backward launch.  GPU box only:
+"""One minibatch optimiser step of K nets, three ways in the same process: the loop of K agent.update calls,
+PopulationTrainer.update (two HIP launches + the losses in PyTorch), with its split into forward launch, PyTorch loss part and
+backward launch, and PopulationTrainer(losses="device").update (three launches, the losses on the device).  GPU box only:
     python tools/population_train_latency.py [--ks 1,8,64,256] [--batch 128] [--reps 20] [--warmup 5] [--out profiles/population_train_latency.txt]
 Configurations: CartPole 2x128 ReLU and Pendulum 3x128 ELU (run.DISCRETE_DEFAULTS / CONTINUOUS_DEFAULTS, A0CLossTuned, RMSprop).
 Every figure is the median wall ms of --reps repetitions after --warmup, host clock around work that ends in a synchronise.  The
 file's header carries the errors printed by tests/test_population_trainer.py (--grad-errors FILE, the output of pytest -s: gradients
-against autograd, raw against azg_mlp_eval, first-step losses against float64) and the compiler's resource report of the two kernels."""
+against autograd, raw against azg_mlp_eval, first-step losses against float64; --loss-errors FILE, the same of
+tests/test_population_device_loss.py: the largest error per head and loss) and the compiler's resource report of the kernels."""
 import argparse
 import os
 import subprocess
@@ -83,7 +84,28 @@ def measure(name, K, B, reps, warmup):
 
     t_bwd = _median_ms(bwd, reps, warmup) - t_fwd
     tr.close()
-    return t_loop, t_pop, t_fwd, t_loss, t_bwd
+    # the losses on the device: new agents of the same seed (the first trainer's close() left its agents usable, but trained)
+    torch.manual_seed(0)
+    fused = PT.PopulationTrainer([run.make_agent(kind, cfg, env, tree_id_base=k) for k in range(K)], max_batch=max(512, 2 * B), losses="device")
+    t_fused = _median_ms(lambda: fused.update(stacked), reps, warmup)
+    fused.close()
+    return t_loop, t_pop, t_fwd, t_loss, t_bwd, t_fused
+
+
+def _worst_loss_errors(path):
+    """The 'loss <head> <loss> <reduction> B=.. net . <key>: float32 torch error X, kernel error Y' lines of pytest -s, reduced to the
+    largest pair per (head, loss, d_raw or loss values)."""
+    worst = {}
+    for ln in open(path):
+        ln = ln.strip().lstrip(".")
+        if not ln.startswith("loss ") or "kernel error" not in ln:
+            continue
+        w = ln.split()
+        key = (w[1], w[2], "d_raw (relative)" if w[7].startswith("d_raw") else "loss values (absolute)")
+        e_y, e_k = float(w[-4].rstrip(",")), float(w[-1])
+        old = worst.get(key, (0.0, 0.0))
+        worst[key] = (max(old[0], e_y), max(old[1], e_k))
+    return ["#   %s %s %s: float32 torch error <= %.3g, kernel error <= %.3g" % (k + v) for k, v in sorted(worst.items())]
 
 
 def main():
@@ -94,6 +116,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--configs", default=",".join(CONFIGS))
     ap.add_argument("--grad-errors", default=None, help="output of pytest -s tests/test_population_trainer.py: its 'grad' lines go into the header")
+    ap.add_argument("--loss-errors", default=None, help="output of pytest -s tests/test_population_device_loss.py: the largest errors go into the header")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = ["# tools/population_train_latency.py: one minibatch optimiser step of K nets, batch %d, one MI355X; median wall ms of %d "
@@ -106,16 +129,20 @@ def main():
         lines += ["#   " + ln for ln in log if ln.startswith("forward vs ")]
         lines.append("# first-step loss dictionaries against float64 (test_end_to_end_update):")
         lines += ["#   " + ln for ln in log if ln.startswith(("discrete ", "continuous "))]
+    if a.loss_errors and os.path.exists(a.loss_errors):
+        lines.append("# the loss kernel against float64 population_loss, largest of all nets, reductions and batch sizes (tests/test_population_device_loss.py):")
+        lines += _worst_loss_errors(a.loss_errors)
     ru = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "resource_usage.py"), "dispatch_train", "train"],
                         capture_output=True, text=True)
     lines.append("# tools/resource_usage.py dispatch_train:")
     lines += ["#   " + ln for ln in ru.stdout.splitlines()]
     for name in a.configs.split(","):
-        lines.append(f"# {name}: loop of K agent.update | PopulationTrainer.update | ratio | forward launch | PyTorch loss part | backward launch")
+        lines.append(f"# {name}: loop of K agent.update | PopulationTrainer.update | ratio | forward launch | PyTorch loss part | backward launch | "
+                     "PopulationTrainer(losses='device').update | ratio to losses='torch'")
         for K in [int(k) for k in a.ks.split(",")]:
-            t_loop, t_pop, t_fwd, t_loss, t_bwd = measure(name, K, a.batch, a.reps, a.warmup)
+            t_loop, t_pop, t_fwd, t_loss, t_bwd, t_fused = measure(name, K, a.batch, a.reps, a.warmup)
             lines.append(f"  {name} K={K:4d} loop {t_loop:9.3f} ms  population {t_pop:8.3f} ms  {t_loop / t_pop:7.2f}x  "
-                         f"forward {t_fwd:7.3f}  loss {t_loss:7.3f}  backward {t_bwd:7.3f}")
+                         f"forward {t_fwd:7.3f}  loss {t_loss:7.3f}  backward {t_bwd:7.3f}  device losses {t_fused:8.3f} ms  {t_pop / t_fused:6.2f}x")
             print(lines[-1], flush=True)
     text = "\n".join(lines) + "\n"
     if a.out:
