@@ -105,7 +105,7 @@ SYMBOLS = [
 OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device",
                     "population_selfplay_begin",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
-                    "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw"]
+                    "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch"]
 
 
 class AzgRmsprop(C.Structure):
@@ -135,6 +135,13 @@ class AzgAlphaState(C.Structure):
     """include/azgym_train.h: azg_alpha_state"""
     _fields_ = [("struct_size", C.c_int32), ("step", C.c_int32), ("log_alpha", C.c_void_p), ("exp_avg", C.c_void_p),
                 ("exp_avg_sq", C.c_void_p)]
+
+
+class AzgEpochRows(C.Structure):
+    """include/azgym_train.h: azg_epoch_rows"""
+    _fields_ = [("struct_size", C.c_int32), ("row_len", C.c_int32), ("state_dim", C.c_int32), ("n_actions", C.c_int32),
+                ("rows_per_net", C.c_int32), ("group", C.c_int32), ("group_stride", C.c_int64), ("net_stride", C.c_int64),
+                ("rows", C.c_void_p)]
 
 
 def bind(lib, prefix):
@@ -205,6 +212,9 @@ def bind(lib, prefix):
         f["trainer_step"].argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.POINTER(AzgLossCfg), C.POINTER(AzgAlphaState),
                                       C.POINTER(AzgRmsprop), vp, vp, vp, vp]
         f["trainer_read_d_raw"].argtypes = [vp, C.c_int32, vp]
+    if "trainer_epoch" in f:
+        f["trainer_epoch"].argtypes = [vp, vp, C.POINTER(AzgEpochRows), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(AzgLossCfg),
+                                       C.POINTER(AzgAlphaState), C.POINTER(AzgRmsprop), vp, vp, C.POINTER(C.c_int32)]
     return f
 
 
@@ -637,6 +647,24 @@ def alpha_state(step, log_alpha, exp_avg, exp_avg_sq):
     return s
 
 
+def epoch_rows(rows, state_dim, n_actions, rows_per_net, *, ring_trees=None, games_per_net=None):
+    """azg_epoch_rows: where a population's replay rows lie (``rows``: their device address).  Default: a plain
+    [n_nets, rows_per_net, row_len] array.  With ``ring_trees`` (the engine's n_trees) and ``games_per_net`` (T): the self-play
+    ring [capacity_steps, n_trees, row_len], where net k's row i is step i // T, game k * T + i % T -- the numbering of
+    ``PopulationSelfPlay._split``'s copies."""
+    r = AzgEpochRows()
+    r.struct_size = C.sizeof(AzgEpochRows)
+    r.state_dim, r.n_actions = int(state_dim), int(n_actions)
+    r.row_len = r.state_dim + 3 * r.n_actions + 1
+    r.rows_per_net = int(rows_per_net)
+    if ring_trees is None:
+        r.group, r.group_stride, r.net_stride = r.rows_per_net, r.rows_per_net, r.rows_per_net
+    else:
+        r.group, r.group_stride, r.net_stride = int(games_per_net), int(ring_trees), int(games_per_net)
+    r.rows = rows or None
+    return r
+
+
 class Trainer:
     """One ``azg_trainer*`` (include/azgym_train.h): forward and backward + RMSprop step of n_nets nets of shape ``desc`` in two
     launches.  Every array argument is a device address (int) of float32 memory on the trainer's GPU, complete when the call is
@@ -698,6 +726,26 @@ class Trainer:
                                             int(n_actions), C.byref(cfg) if cfg is not None else None,
                                             C.byref(alpha) if alpha is not None else None, C.byref(opt) if opt is not None else None,
                                             square_avg or None, grads or None, raw_out or None, losses or None))
+
+    def epoch(self, params, rows, order, batch_size, cfg, alpha, opt, square_avg, loss_sums):
+        """azg_trainer_epoch: one epoch of ``step``s of every net, the minibatches gathered on the device from ``rows``
+        (``epoch_rows``) by ``order`` (a HOST int array [n_nets, n_order]; consecutive slices of ``batch_size``, the last one
+        absorbing the remainder); one synchronisation.  ``loss_sums``: device float64 [n_nets, 5].  Returns the number of
+        minibatches (= Adam steps of a tuned alpha)."""
+        if "trainer_epoch" not in self._f:
+            raise NotImplementedError("this engine library has no azg_trainer_epoch")
+        n_order, ptr = 0, None
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.int32)
+            if order.ndim != 2 or order.shape[0] != self.n_nets:
+                raise ValueError("Trainer.epoch: order must be [n_nets, n_order]")
+            n_order, ptr = order.shape[1], _ptr(order, C.c_int32)
+        n_mb = C.c_int32(0)
+        self._check(self._f["trainer_epoch"](self._h, params or None, C.byref(rows) if rows is not None else None, ptr, n_order,
+                                             int(batch_size), C.byref(cfg) if cfg is not None else None,
+                                             C.byref(alpha) if alpha is not None else None, C.byref(opt) if opt is not None else None,
+                                             square_avg or None, loss_sums or None, C.byref(n_mb)))
+        return n_mb.value
 
     def read_d_raw(self, n_rows, d_raw):
         """azg_trainer_read_d_raw: the last ``step``'s d_raw [n_nets, n_rows, 1 + n_dist] into the caller's device array."""

@@ -8,7 +8,9 @@ trunk, heads, their backward pass and the RMSprop step are kernels; the losses (
 ``ContinuousAgent._loss`` restated once for a leading K axis, the tuned alpha's Adam step included) stay in PyTorch and give
 ``d_raw`` by autograd on those small tensors.  ``PopulationTrainer(..., losses="device")`` moves that boundary out of the step:
 the same losses, their ``d_raw`` and the tuned alpha's Adam step are one more kernel between the two (``azg_trainer_step``: three
-launches, one synchronisation, one copy of ``losses[K, 5]`` to the host).  The single-agent path (``Agent.update``) is untouched.
+launches, one synchronisation, one copy of ``losses[K, 5]`` to the host).  ``train_epoch`` / ``train_epoch_ring`` take the loop
+around that step to the device as well (``azg_trainer_epoch``): the minibatches are gathered by a kernel from the rows where they
+lie, the self-play ring included, and a whole epoch costs one synchronisation.  The single-agent path (``Agent.update``) is untouched.
 """
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -183,6 +185,25 @@ def _rmsprop_settings(opt) -> tuple:
     if g["momentum"] != 0 or g["centered"] or g.get("maximize", False):
         raise ValueError("PopulationTrainer: RMSprop with momentum, centered or maximize is not supported")
     return (g["lr"], g["alpha"], g["eps"], g["weight_decay"])
+
+
+def minibatch_bounds(n: int, batch_size: int) -> List[Tuple[int, int]]:
+    """The minibatches [i, j) of an epoch over n shuffled rows: consecutive slices of ``batch_size``, the last one absorbing the
+    remainder (``train_on_rows``'s and ``ReplayBuffer.__next__``'s rule; azg_trainer_epoch cuts the same way)."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be at least 1")
+    out, i = [], 0
+    while i < n:
+        j = n if i + 2 * batch_size > n else i + batch_size
+        out.append((i, j))
+        i = j
+    return out
+
+
+def _need_device_losses(losses: str, who: str) -> None:
+    if losses != "device":
+        raise ValueError(f'PopulationTrainer.{who} needs a trainer built with losses="device" (this one has losses="{losses}"): the '
+                         "epoch runs on the device from the gather to the loss sums")
 
 
 class PopulationTrainer:
@@ -384,6 +405,72 @@ class PopulationTrainer:
                     s[key] = s.get(key, 0.0) + val
             i = j
         return sums
+
+    def _epoch(self, who: str, where, order: np.ndarray, batch_size: int) -> List[Dict[str, float]]:
+        """azg_trainer_epoch on rows described by ``where`` (``_capi.epoch_rows``), their producers complete; the per-net sums."""
+        K = len(self.agents)
+        bounds = minibatch_bounds(order.shape[1], int(batch_size))
+        if not bounds or max(j - i for i, j in bounds) > self.max_batch:
+            raise ValueError(f"PopulationTrainer.{who}: needs minibatches of 1..{self.max_batch} rows")
+        sums = torch.empty((K, len(_capi.LOSS_KEYS)), dtype=torch.float64, device=self.device)
+        tuned = self.log_alpha is not None
+        state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
+                                  self.alpha_exp_avg_sq.data_ptr()) if tuned else None
+        torch.cuda.current_stream(self.device).synchronize()
+        n_steps = self.trainer.epoch(self.flat.data_ptr(), where, order, int(batch_size), self.loss_cfg, state, self.opt,
+                                     self.square_avg.data_ptr(), sums.data_ptr())
+        assert n_steps == len(bounds)
+        if tuned:
+            self.alpha_step += n_steps
+        self.last_raw, self._last_d_raw = None, None   # (the minibatches' raw outputs stay in the native trainer)
+        table = sums.cpu().tolist()
+        slots = [(key, _capi.LOSS_KEYS.index(key)) for key in _capi.LOSS_KEYS_OF[self.loss_cfg.kind]]
+        return [{key: row[i] for key, i in slots} for row in table]
+
+    def train_epoch(self, rows_per_net, state_dim: int, K: int, batch_size: int = 32,
+                    shuffle_seeds: Optional[Sequence[int]] = None) -> List[Dict[str, float]]:
+        """``train_on_rows`` as one native call (``azg_trainer_epoch``): the same arguments, minibatches, arithmetic and return
+        value, bit for bit, with one synchronisation for the whole epoch.  The permutations are built on the host as there; the
+        minibatches are gathered from ``rows_per_net`` on the device (a [K, n, row] float32 tensor on the trainer's GPU is read in
+        place).  Needs ``losses="device"``; ``grads`` (``keep_grads``) is not written."""
+        _need_device_losses(self.losses, "train_epoch")
+        rows = rows_per_net if isinstance(rows_per_net, torch.Tensor) else torch.stack(list(rows_per_net))
+        rows = rows.to(self.device, dtype=torch.float32).contiguous()
+        if rows.dim() != 3 or rows.shape[0] != len(self.agents):
+            raise ValueError("PopulationTrainer.train_epoch: one block of rows per net")
+        N, n = rows.shape[0], rows.shape[1]
+        if rows.shape[2] != state_dim + 3 * K + 1:
+            raise ValueError("PopulationTrainer.train_epoch: rows must be obs[state_dim] | actions[K] | counts[K] | Q[K] | V")
+        seeds = [0] * N if shuffle_seeds is None else list(shuffle_seeds)
+        order = np.stack([np.random.RandomState(int(s)).permutation(n) for s in seeds]).astype(np.int32)
+        return self._epoch("train_epoch", _capi.epoch_rows(rows.data_ptr(), state_dim, K, n), order, batch_size)
+
+    def train_epoch_ring(self, selfplay, order, batch_size: int = 32) -> List[Dict[str, float]]:
+        """One epoch straight from a ``PopulationSelfPlay`` / ``DeviceSelfPlay`` engine's replay ring, with no copy of the rows and
+        no index tensors on the device.  ``order``: int array [K, n_order]; order[k] numbers net k's rows of the ring as
+        ``PopulationSelfPlay._split`` orders them (row i = stored step i // T, game i % T of the net's T games) -- the caller's pick
+        and shuffle composed.  The engine's stream is synchronised first (``azg_sync``); the ring is neither cleared nor changed."""
+        _need_device_losses(self.losses, "train_epoch_ring")
+        engine = selfplay.engine
+        if int(engine.cfg.device_id) != (self.device.index or 0):
+            raise ValueError("PopulationTrainer.train_epoch_ring: the ring lies on another GPU than the trainer's nets")
+        if selfplay.n_nets != len(self.agents):
+            raise ValueError(f"PopulationTrainer.train_epoch_ring: the self-play engine has {selfplay.n_nets} nets, the trainer "
+                             f"{len(self.agents)}")
+        order = np.asarray(order)
+        if order.ndim != 2 or order.shape[0] != len(self.agents) or order.shape[1] < 1 or order.dtype.kind not in "iu":
+            raise ValueError("PopulationTrainer.train_epoch_ring: order must be an int array [K, n_order >= 1]")
+        T = selfplay.games_per_net
+        n = engine.selfplay_ring()[0] * T
+        if int(order.min()) < 0 or int(order.max()) >= n:
+            raise ValueError(f"PopulationTrainer.train_epoch_ring: order names rows outside the ring's {n} stored rows per net")
+        ptr, _, row_len = engine.selfplay_rows_device()
+        state_dim, A = engine.s_obs, engine.kmax
+        if row_len != state_dim + 3 * A + 1:
+            raise ValueError("PopulationTrainer.train_epoch_ring: unexpected replay row length")
+        where = _capi.epoch_rows(ptr, state_dim, A, n, ring_trees=selfplay.n_games, games_per_net=T)
+        engine.sync()
+        return self._epoch("train_epoch_ring", where, order.astype(np.int32), batch_size)
 
     def export_alpha(self) -> None:
         """Write every net's learned temperature and its Adam state (step, exp_avg, exp_avg_sq) back into its agent's loss object,

@@ -1,6 +1,9 @@
-// dispatch_train.hip -- the population trainer's C ABI (include/azgym_train.h): scratch, checks and the three launches of train.cuh.
+// dispatch_train.hip -- the population trainer's C ABI (include/azgym_train.h): scratch, checks and the three launches of train.cuh;
+// azg_trainer_epoch enqueues them for a whole epoch of minibatches behind a gather launch each.
 #include <cmath>
+#include <cstdint>
 #include <string>
+#include <vector>
 
 #include "../../include/azgym_train.h"
 #include "hip_host.h"
@@ -20,6 +23,12 @@ struct azg_trainer {
     double* loss_rows = nullptr;
     float* raw_buf = nullptr;
     float* d_raw_buf = nullptr;
+    // azg_trainer_epoch's, grown on demand: the uploaded order [n_nets][n_order], the minibatch staging arrays (obs [n_nets][B][in_dim] |
+    // actions | counts [n_nets][B][A] | values [n_nets][B], laid out for max_batch rows) and the loss table [n_minibatches][n_nets][5]
+    int* order_buf = nullptr;
+    float* stage_buf = nullptr;
+    float* loss_table = nullptr;
+    size_t order_bytes = 0, stage_bytes = 0, table_bytes = 0;
     hipStream_t stream = nullptr;
     std::string err;
 };
@@ -46,6 +55,9 @@ void azg_trainer_destroy(azg_trainer* t) {
     if (t->loss_rows) (void)hipFree(t->loss_rows);
     if (t->raw_buf) (void)hipFree(t->raw_buf);
     if (t->d_raw_buf) (void)hipFree(t->d_raw_buf);
+    if (t->order_buf) (void)hipFree(t->order_buf);
+    if (t->stage_buf) (void)hipFree(t->stage_buf);
+    if (t->loss_table) (void)hipFree(t->loss_table);
     delete t;
 }
 
@@ -212,6 +224,18 @@ static int ensure(azg_trainer* t, void** buf, size_t bytes) {
     return AZG_OK;
 }
 
+// (for buffers whose size depends on the call: a larger one replaces the old one; the stream is idle between calls)
+static int grow(azg_trainer* t, void** buf, size_t* have, size_t bytes) {
+    if (*buf && *have >= bytes) return AZG_OK;
+    void* p = nullptr;
+    const hipError_t rc = hipMalloc(&p, bytes);
+    if (rc != hipSuccess) return tfail(t, AZG_E_DEVICE, std::string("azg_trainer: ") + hipGetErrorString(rc));
+    if (*buf) (void)hipFree(*buf);
+    *buf = p;
+    *have = bytes;
+    return AZG_OK;
+}
+
 static void launch_loss(azg_trainer* t, const LossDims& c, const float* raw, const float* actions, const float* counts, const float* values,
                         int n_rows, const azg_alpha_state* st, float* d_raw, float* losses) {
     const bool tuned = c.kind == AZG_LOSS_A0C_TUNED;
@@ -289,6 +313,86 @@ int azg_trainer_step(azg_trainer* t, float* params, const float* obs, const floa
     launch_backward(t, params, t->d_raw_buf, (int)n_rows, opt, square_avg, grads);
     if (int rc = finish(t, "azg_trainer_step")) return rc;
     t->step_rows = n_rows;
+    return AZG_OK;
+}
+
+int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
+                      int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_rmsprop* opt,
+                      float* square_avg, double* loss_sums, int32_t* n_minibatches) {
+    if (!t) return AZG_E_INVALID;
+    const char* who = "azg_trainer_epoch";
+    const std::string w(who);
+    if (!params || !rows || !order || !loss_cfg || !opt || !square_avg || !loss_sums || !n_minibatches)
+        return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
+    if (rows->struct_size != (int32_t)sizeof(azg_epoch_rows)) return tfail(t, AZG_E_INVALID, w + ": azg_epoch_rows.struct_size mismatch");
+    if (!rows->rows) return tfail(t, AZG_E_INVALID, w + ": NULL pointer in azg_epoch_rows");
+    if (batch_size < 1 || n_order < 1) return tfail(t, AZG_E_INVALID, w + ": batch_size and n_order must be at least 1");
+    const int A = rows->n_actions;
+    if (A < 1 || A > TR_MAX_ACTIONS) return tfail(t, AZG_E_INVALID, w + ": n_actions must be 1..16");
+    if (rows->state_dim != t->d.in_dim) return tfail(t, AZG_E_INVALID, w + ": state_dim must be the trainer's in_dim");
+    if (rows->row_len != rows->state_dim + 3 * A + 1) return tfail(t, AZG_E_INVALID, w + ": row_len must be state_dim + 3 * n_actions + 1");
+    if (rows->rows_per_net < 1 || rows->group < 1) return tfail(t, AZG_E_INVALID, w + ": rows_per_net and group must be at least 1");
+    if (rows->group_stride < 0 || rows->net_stride < 0) return tfail(t, AZG_E_INVALID, w + ": strides must be >= 0");
+    // the minibatches: train_on_rows's rule, the last one absorbing the remainder
+    std::vector<int> first, count;
+    int largest = 0;
+    for (int64_t i = 0; i < n_order;) {
+        const int64_t j = i + 2 * (int64_t)batch_size > n_order ? (int64_t)n_order : i + batch_size;
+        first.push_back((int)i);
+        count.push_back((int)(j - i));
+        largest = (int)(j - i) > largest ? (int)(j - i) : largest;
+        i = j;
+    }
+    const int M = (int)first.size();
+    if (largest > t->max_batch) return tfail(t, AZG_E_INVALID, w + ": the largest minibatch exceeds max_batch");
+    // every refusal of azg_trainer_step, for every minibatch's row count and Adam step
+    const bool stepped = alpha_state && loss_cfg->struct_size == (int32_t)sizeof(azg_loss_cfg) && loss_cfg->kind == AZG_LOSS_A0C_TUNED &&
+                         alpha_state->struct_size == (int32_t)sizeof(azg_alpha_state);
+    if (stepped && alpha_state->step > INT32_MAX - M) return tfail(t, AZG_E_INVALID, w + ": azg_alpha_state.step too large");
+    std::vector<LossDims> dims((size_t)M);
+    for (int m = 0; m < M; ++m) {
+        azg_alpha_state st{};
+        if (stepped) { st = *alpha_state; st.step += m; }
+        if (int rc = check_loss(t, who, count[m], A, loss_cfg, stepped ? &st : alpha_state, &dims[m])) return rc;
+        if (int rc = check_backward(t, who, params, opt, square_avg, count[m])) return rc;
+    }
+    const size_t K = (size_t)t->n_nets;
+    for (size_t e = 0; e < K * (size_t)n_order; ++e)
+        if (order[e] < 0 || order[e] >= rows->rows_per_net) return tfail(t, AZG_E_INVALID, w + ": an order entry is outside 0 .. rows_per_net - 1");
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    const size_t mb = (size_t)t->max_batch, per = K * mb * t->d.NO, in_dim = (size_t)t->d.in_dim;
+    if (int rc = ensure(t, (void**)&t->loss_rows, K * 3 * mb * sizeof(double))) return rc;
+    if (int rc = ensure(t, (void**)&t->d_raw_buf, per * sizeof(float))) return rc;
+    if (int rc = ensure(t, (void**)&t->raw_buf, per * sizeof(float))) return rc;
+    if (int rc = grow(t, (void**)&t->order_buf, &t->order_bytes, K * (size_t)n_order * sizeof(int32_t))) return rc;
+    if (int rc = grow(t, (void**)&t->stage_buf, &t->stage_bytes, K * mb * (in_dim + 2 * (size_t)A + 1) * sizeof(float))) return rc;
+    if (int rc = grow(t, (void**)&t->loss_table, &t->table_bytes, (size_t)M * K * AZG_LOSS_SLOTS * sizeof(float))) return rc;
+    float* obs = t->stage_buf;
+    float* actions = obs + K * mb * in_dim;
+    float* counts = actions + K * mb * (size_t)A;
+    float* values = counts + K * mb * (size_t)A;
+    GatherDims g{};
+    g.row_len = rows->row_len; g.state_dim = rows->state_dim; g.A = A; g.group = rows->group; g.n_order = n_order;
+    g.group_stride = rows->group_stride; g.net_stride = rows->net_stride;
+    t->fwd_rows = 0;
+    t->step_rows = 0;
+    const hipError_t up = hipMemcpyAsync(t->order_buf, order, K * (size_t)n_order * sizeof(int32_t), hipMemcpyHostToDevice, t->stream);
+    if (up != hipSuccess) return tfail(t, AZG_E_DEVICE, w + ": " + hipGetErrorString(up));
+    for (int m = 0; m < M; ++m) {
+        const int B = count[m];
+        hipLaunchKernelGGL(train_gather_kernel, dim3((B + TR_GATHER_THREADS / 64 - 1) / (TR_GATHER_THREADS / 64), t->n_nets),
+                           dim3(TR_GATHER_THREADS), 0, t->stream, g, rows->rows, t->order_buf, first[m], B, obs, actions, counts, values);
+        launch_forward(t, params, obs, B, t->raw_buf);
+        launch_loss(t, dims[m], t->raw_buf, actions, counts, values, B, alpha_state, t->d_raw_buf,
+                    t->loss_table + (size_t)m * K * AZG_LOSS_SLOTS);
+        launch_backward(t, params, t->d_raw_buf, B, opt, square_avg, nullptr);
+    }
+    const int n_sums = t->n_nets * AZG_LOSS_SLOTS;
+    hipLaunchKernelGGL(train_loss_sum_kernel, dim3((n_sums + 63) / 64), dim3(64), 0, t->stream, t->loss_table, M, n_sums, loss_sums);
+    if (int rc = finish(t, who)) return rc;
+    t->step_rows = count[M - 1];
+    *n_minibatches = M;
     return AZG_OK;
 }
 

@@ -459,3 +459,47 @@ __global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_kernel(LossDims c,
     p = p - (c.lr / c.bc1) * (m / (sqrt(s) / c.bc2_sqrt + c.eps));
     exp_avg[net] = (float)m; exp_avg_sq[net] = (float)s; log_alpha[net] = (float)p;
 }
+
+// ------------------------------------------------------------------------------------------------ a whole epoch
+// azg_trainer_epoch's two kernels: the minibatch gather in front of every step, and the sum of the steps' losses after the last.
+#define TR_GATHER_THREADS 256
+
+struct GatherDims {
+    int row_len, state_dim, A;      // floats of a replay row: obs[state_dim] | actions[A] | counts[A] | Q[A] | V
+    int group, n_order;
+    long long group_stride, net_stride;
+};
+
+// grid (ceil(n_rows / 4), nets): one wave per minibatch row, lane c takes float c of the row, so a row is read as one coalesced
+// segment.  The row's number and address are the same for every lane of the wave (one computation per row, on the scalar unit).
+// Writes obs [nets][n_rows][state_dim], actions and counts [nets][n_rows][A] and values [nets][n_rows]; the Q columns are skipped.
+__global__ __launch_bounds__(TR_GATHER_THREADS) void train_gather_kernel(GatherDims g, const float* rows, const int* order, int first,
+                                                                         int n_rows, float* obs, float* actions, float* counts,
+                                                                         float* values) {
+    const int net = blockIdx.y, lane = threadIdx.x & 63;
+    const int b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (TR_GATHER_THREADS / 64) + (threadIdx.x >> 6)));
+    if (b >= n_rows) return;
+    const int i = __builtin_amdgcn_readfirstlane(order[(size_t)net * g.n_order + first + b]);
+    const long long at = (long long)(i / g.group) * g.group_stride + (long long)net * g.net_stride + (long long)(i % g.group);
+    const float* src = rows + at * g.row_len;
+    const size_t out = (size_t)net * n_rows + b;
+    const int a0 = g.state_dim, c0 = a0 + g.A, q0 = c0 + g.A, v0 = g.row_len - 1;
+    for (int c = lane; c < g.row_len; c += 64) {
+        if (c >= q0 && c < v0) continue;
+        const float x = src[c];
+        if (c < a0) obs[out * g.state_dim + c] = x;
+        else if (c < c0) actions[out * g.A + (c - a0)] = x;
+        else if (c < q0) counts[out * g.A + (c - c0)] = x;
+        else values[out] = x;
+    }
+}
+
+// One thread per (net, slot): table [n_minibatches][n_nets * AZG_LOSS_SLOTS] float32 -> sums [n_nets * AZG_LOSS_SLOTS] float64, the
+// minibatches added in order in one chain from 0.0 (what Python's 0.0 + l0 + l1 + ... of the steps' losses gives).
+__global__ __launch_bounds__(64) void train_loss_sum_kernel(const float* table, int n_minibatches, int n, double* sums) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= n) return;
+    double s = 0.0;
+    for (int m = 0; m < n_minibatches; ++m) s = s + (double)table[(size_t)m * n + e];
+    sums[e] = s;
+}

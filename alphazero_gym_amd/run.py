@@ -324,6 +324,14 @@ class PopulationSelfPlay:
         for _ in range(n_steps):
             self.engine.selfplay_step()
 
+    def play_device(self, n_steps: int):
+        """``play`` for a consumer that reads the ring where it lies (``PopulationTrainer.train_epoch_ring``): returns the ring's
+        (size_steps, insert_step) after the n_steps; nothing is copied and nothing cleared (``engine.selfplay_clear()`` is the
+        caller's, once it is done with the rows)."""
+        self.play(n_steps)
+        size, insert, _ = self.engine.selfplay_ring()
+        return size, insert
+
     def _split(self, rows, n_steps: int) -> List[torch.Tensor]:
         """[n_steps * n_games, row] in step-major order -> copies of net k's [n_steps * T, row] (the order of its DeviceSelfPlay)."""
         blocks = rows.reshape(n_steps, self.n_nets, self.games_per_net, rows.shape[-1])

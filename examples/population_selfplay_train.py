@@ -5,7 +5,9 @@ Net k's games (--games-per-seed of them, global game ids k*T ...) are played on 
 downloads the new replay rows, trains every net on its own rows with its own optimiser, one net after another, and re-uploads
 the changed nets (one gather launch for all of them when the nets live on the GPU).  --trainer device takes every net's
 minibatch step at once instead (agent.population_trainer.PopulationTrainer: two HIP launches per step for all nets, the losses
-in PyTorch between them); --trainer device-fused computes the losses on the device too (three launches, one host round trip).
+in PyTorch between them); --trainer device-fused computes the losses on the device too (three launches, one host round trip);
+--trainer device-epoch takes the whole epoch of those steps in one native call that reads the rows straight from the self-play ring
+(PopulationTrainer.train_epoch_ring: no copy of the rows, one synchronisation per iteration instead of one per minibatch).
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
@@ -42,9 +44,10 @@ def parse_args(argv=None):
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--engine-seed", type=int, default=34, help="the engine's RNG seed (shared; games differ by their global ids)")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
-    ap.add_argument("--trainer", choices=["torch", "device", "device-fused"], default="torch",
+    ap.add_argument("--trainer", choices=["torch", "device", "device-fused", "device-epoch"], default="torch",
                     help="torch: agent.update net by net; device: every net's optimiser step in two HIP launches (PopulationTrainer) with "
-                         "the losses in PyTorch between them; device-fused: the losses in a kernel of the same step (losses='device')")
+                         "the losses in PyTorch between them; device-fused: the losses in a kernel of the same step (losses='device'); "
+                         "device-epoch: device-fused's arithmetic, the whole epoch in one call on the rows in the self-play ring")
     return ap.parse_args(argv)
 
 
@@ -74,17 +77,34 @@ def train(a, log=print, on_rows=None):
     trainer = None
     if a.trainer != "torch":
         from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
-        trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size), losses="device" if a.trainer == "device-fused" else "torch")
+        trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size), losses="torch" if a.trainer == "device" else "device")
     t0 = time.time()
     history = []
     for it in range(a.iters):
         t1 = time.time()
-        rows = sp.collect_device(a.steps_per_iter) if on_gpu else sp.collect(a.steps_per_iter)
+        if a.trainer == "device-epoch":   # the rows stay in the ring
+            rows = None
+            n_ring = sp.play_device(a.steps_per_iter)[0] * sp.games_per_net
+            sp.engine.sync()
+        else:
+            rows = sp.collect_device(a.steps_per_iter) if on_gpu else sp.collect(a.steps_per_iter)
         t2 = time.time()
         if on_rows is not None:
-            on_rows(it, rows)
+            if rows is None:
+                from alphazero_gym_amd.agent.buffers import DeviceReplay
+                on_rows(it, sp._split(DeviceReplay(sp.engine, 1).rows(), n_ring // sp.games_per_net))
+            else:
+                on_rows(it, rows)
         losses = []
-        if trainer is None:
+        if rows is None:   # the other trainers' picks and shuffles from the same streams, composed into one order per net
+            order = []
+            for rng in rngs:
+                pick = rng.choice(n_ring, size=min(a.train_rows, n_ring), replace=False)
+                order.append(pick[np.random.RandomState(int(rng.randint(2 ** 31 - 1))).permutation(len(pick))])
+            infos = trainer.train_epoch_ring(sp, np.stack(order), batch_size=a.batch_size)
+            sp.engine.selfplay_clear()
+            losses = [info["loss"] / max(1, len(order[0]) // a.batch_size) for info in infos]
+        elif trainer is None:
             for agent, rng, r in zip(agents, rngs, rows):
                 pick = rng.choice(r.shape[0], size=min(a.train_rows, r.shape[0]), replace=False)
                 info = run.train_on_rows(agent, r[torch.from_numpy(pick).to(r.device)], state_dim, K, batch_size=a.batch_size,

@@ -1,5 +1,5 @@
-/* azgym_train.h -- population training: one minibatch optimiser step of K nets of one shape in two launches, or three with the losses on the device too (an extension of
- * azgym.h; same ABI version).
+/* azgym_train.h -- population training: one minibatch optimiser step of K nets of one shape in two launches, or three with the losses on the device too, and a
+ * whole epoch of such steps in one call (an extension of azgym.h; same ABI version).
  *
  * A trainer owns scratch only.  The nets' parameters, the RMSprop state and every batch tensor are the caller's device arrays on
  * the trainer's GPU, float32:
@@ -17,7 +17,9 @@
  * Device memory is shared the way azg_set_weights_device shares it: inputs are complete when a call is made (their producer's
  * stream synchronised), outputs are complete when it returns.  With the losses in PyTorch (azg_trainer_forward, autograd on raw,
  * azg_trainer_backward_step) that is two synchronisations per minibatch step, whatever n_nets; azg_trainer_step takes the losses on
- * the device as well (azg_trainer_loss's kernel between the two) and synchronises once.
+ * the device as well (azg_trainer_loss's kernel between the two) and synchronises once.  azg_trainer_epoch takes a whole epoch of
+ * such steps: it gathers every minibatch from the caller's replay rows where they lie (the self-play ring included) and
+ * synchronises once per epoch, whatever the number of minibatches.
  *
  * Supported nets: Linear + activation trunks of 1..3 hidden layers, widths multiples of 16 up to 256, in_dim <= 8, n_dist <= 16,
  * every AZG_ACT_* activation; no LayerNorm.  Anything else: AZG_E_UNSUPPORTED from azg_trainer_create.
@@ -129,6 +131,43 @@ int azg_trainer_step(azg_trainer* t, float* params, const float* obs, const floa
 /* Copies the d_raw [n_nets][n_rows][1 + n_dist] of the last azg_trainer_step to the caller's device array (AZG_E_STATE if there
  * was none of that n_rows). */
 int azg_trainer_read_d_raw(azg_trainer* t, int32_t n_rows, float* d_raw);
+
+/* ---- a whole epoch of minibatch steps in one call ---- */
+
+/* Where the replay rows lie.  A row is row_len floats: obs[state_dim] | actions[A] | counts[A] | Q[A] | V_target, A = n_actions
+ * (azg_selfplay_rows' layout).  Net k can be asked for rows 0 .. rows_per_net - 1;
+ *   row i of net k lives at rows + ((i / group) * group_stride + k * net_stride + i % group) * row_len.
+ * A plain [n_nets][n][row_len] array: group = n, net_stride = n (group_stride is never multiplied by anything but 0).
+ * The self-play ring [capacity_steps][n_trees][row_len] of azg_selfplay_rows_device, net k playing games k*T .. k*T + T - 1:
+ * group = T, group_stride = n_trees, net_stride = T -- net k's row i is step i / T, game i % T.
+ * The caller vouches that every such address lies inside its allocation. */
+typedef struct azg_epoch_rows {
+    int32_t struct_size;
+    int32_t row_len;
+    int32_t state_dim, n_actions;
+    int32_t rows_per_net;
+    int32_t group;
+    int64_t group_stride;
+    int64_t net_stride;
+    const float* rows;   /* device */
+} azg_epoch_rows;
+
+/* One epoch of azg_trainer_step calls of every net.  order is HOST memory, [n_nets][n_order] row numbers of each net; consecutive
+ * slices of batch_size entries are the minibatches, the last one absorbing the remainder (from position i the next minibatch ends
+ * at n_order if i + 2 * batch_size > n_order, else at i + batch_size), so a minibatch has 1 .. 2 * batch_size - 1 rows.  Per
+ * minibatch m one gather launch (order and the rows to the trainer's staging arrays; the Q columns are not read) and the three
+ * launches of azg_trainer_step with alpha_state->step + m, all enqueued without a synchronisation; then one launch adds every
+ * minibatch's float32 losses[k][slot] in minibatch order in one float64 chain from 0.0 into loss_sums (device,
+ * [n_nets][AZG_LOSS_SLOTS] float64, not rounded), and the call synchronises once.  *n_minibatches receives their number: the Adam steps
+ * the caller adds to its count.  params, square_avg and the alpha state end bit for bit where the same minibatches passed one by
+ * one to azg_trainer_step leave them.
+ * NULL pointers, a struct_size mismatch, batch_size < 1, n_order < 1, n_actions outside 1..16, row_len != state_dim +
+ * 3 * n_actions + 1, state_dim != the descriptor's in_dim, rows_per_net < 1, group < 1, negative strides, an order entry outside
+ * 0 .. rows_per_net - 1, a largest minibatch beyond max_batch: AZG_E_INVALID; whatever azg_trainer_step refuses is refused with
+ * its code.  Every check is made before the first launch: on an error nothing is written. */
+int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
+                      int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_rmsprop* opt,
+                      float* square_avg, double* loss_sums, int32_t* n_minibatches);
 
 #ifdef __cplusplus
 }

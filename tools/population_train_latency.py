@@ -7,7 +7,14 @@ Configurations: CartPole 2x128 ReLU and Pendulum 3x128 ELU (run.DISCRETE_DEFAULT
 Every figure is the median wall ms of --reps repetitions after --warmup, host clock around work that ends in a synchronise.  The
 file's header carries the errors printed by tests/test_population_trainer.py (--grad-errors FILE, the output of pytest -s: gradients
 against autograd, raw against azg_mlp_eval, first-step losses against float64; --loss-errors FILE, the same of
-tests/test_population_device_loss.py: the largest error per head and loss) and the compiler's resource report of the kernels."""
+tests/test_population_device_loss.py: the largest error per head and loss) and the compiler's resource report of the kernels.
+
+--epoch measures a whole epoch instead (--rows rows per net in minibatches of --batch): PopulationTrainer.train_epoch (one native
+call on a [K, n, row] array), train_epoch_ring (the same call on the self-play ring itself) and train_on_rows with
+losses="device" (one native call, one synchronisation and one host copy per minibatch, the minibatches gathered by torch), all three
+in one process on the same rows -- a PopulationSelfPlay's ring of K nets x 16 games -- CartPole 2x128 ReLU and Pendulum 3x128 ELU
+with a mixture of 2:
+    python tools/population_train_latency.py --epoch [--ks 1,8,64,256] [--rows 512] [--batch 128] [--out profiles/population_train_latency_epoch.txt]"""
 import argparse
 import os
 import subprocess
@@ -18,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from alphazero_gym_amd import run  # noqa: E402
+from alphazero_gym_amd import _capi, run  # noqa: E402
 from alphazero_gym_amd.agent import population_trainer as PT  # noqa: E402
 from alphazero_gym_amd.envs import make_game  # noqa: E402
 
@@ -92,6 +99,63 @@ def measure(name, K, B, reps, warmup):
     return t_loop, t_pop, t_fwd, t_loss, t_bwd, t_fused
 
 
+def measure_epoch(name, K, n_rows, B, reps, warmup, T=16):
+    """(train_epoch, train_epoch_ring, train_on_rows) median ms for one epoch of n_rows rows per net in minibatches of B."""
+    from alphazero_gym_amd.agent.buffers import DeviceReplay
+    kind, S, _ = CONFIGS[name]
+    over = dict(device="cuda", policy=dict(num_components=2)) if kind == "continuous" else dict(device="cuda")
+    cfg = run._merge(run.CONTINUOUS_DEFAULTS if kind == "continuous" else run.DISCRETE_DEFAULTS, over)
+    env = make_game(cfg["game"])
+    torch.manual_seed(0)
+    agents = [run.make_agent(kind, cfg, env, tree_id_base=k) for k in range(K)]
+    m = cfg["mcts"]
+    steps = (n_rows + T - 1) // T
+    sp = run.PopulationSelfPlay([a.nn for a in agents], game=cfg["game"], games_per_net=T, n_rollouts=8, c_uct=m["c_uct"], gamma=m["gamma"],
+                                epsilon=m["epsilon"], c_pw=m.get("c_pw", 1.0), kappa=m.get("kappa", 0.5), capacity_steps=steps)
+    sp.play_device(steps)
+    copies = torch.stack(sp._split(DeviceReplay(sp.engine, 1).rows(), steps))[:, :n_rows].contiguous()
+    A = sp.engine.kmax
+    tr = PT.PopulationTrainer(agents, max_batch=max(512, 2 * B), losses="device")
+    seeds = list(range(K))
+
+    def ring():
+        order = np.stack([np.random.RandomState(s).permutation(n_rows) for s in seeds])
+        tr.train_epoch_ring(sp, order, batch_size=B)
+
+    t_epoch = _median_ms(lambda: tr.train_epoch(copies, S, A, batch_size=B, shuffle_seeds=seeds), reps, warmup)
+    t_ring = _median_ms(ring, reps, warmup)
+    t_rows = _median_ms(lambda: tr.train_on_rows(copies, S, A, batch_size=B, shuffle_seeds=seeds), reps, warmup)
+    # the split of train_epoch: the K host permutations (all three paths build them) and the native call on a prepared order
+    t_perm = _median_ms(lambda: np.stack([np.random.RandomState(s).permutation(n_rows) for s in seeds]), reps, warmup)
+    order = np.stack([np.random.RandomState(s).permutation(n_rows) for s in seeds]).astype(np.int32)
+    where = _capi.epoch_rows(copies.data_ptr(), S, A, n_rows)
+    t_call = _median_ms(lambda: tr._epoch("train_epoch", where, order, B), reps, warmup)
+    tr.close()
+    sp.close()
+    return t_epoch, t_ring, t_rows, t_perm, t_call, A
+
+
+def main_epoch(a):
+    n_mb = len(PT.minibatch_bounds(a.rows, a.batch))
+    lines = ["# tools/population_train_latency.py --epoch: one epoch of K nets, %d rows per net in minibatches of %d (%d minibatches), one "
+             "MI355X; median wall ms of %d repetitions after %d warm-up, all three in one process on the same self-play rows"
+             % (a.rows, a.batch, n_mb, a.reps, a.warmup)]
+    ru = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "resource_usage.py"), "dispatch_train", "train"],
+                        capture_output=True, text=True)
+    lines.append("# tools/resource_usage.py dispatch_train:")
+    lines += ["#   " + ln for ln in ru.stdout.splitlines()]
+    for name in a.configs.split(","):
+        lines.append(f"# {name}: train_epoch | train_epoch_ring | train_on_rows(losses='device') | train_on_rows / train_epoch | "
+                     "train_on_rows / train_epoch_ring | of train_epoch: the K host permutations alone | the native call with its host copy "
+                     "alone")
+        for K in [int(k) for k in a.ks.split(",")]:
+            t_epoch, t_ring, t_rows, t_perm, t_call, A = measure_epoch(name, K, a.rows, a.batch, a.reps, a.warmup)
+            lines.append(f"  {name} K={K:4d} A={A:2d} epoch {t_epoch:8.3f} ms  epoch on the ring {t_ring:8.3f} ms  train_on_rows {t_rows:8.3f} ms  "
+                         f"{t_rows / t_epoch:6.2f}x  {t_rows / t_ring:6.2f}x  permutations {t_perm:8.3f} ms  native call {t_call:7.3f} ms")
+            print(lines[-1], flush=True)
+    return lines
+
+
 def _worst_loss_errors(path):
     """The 'loss <head> <loss> <reduction> B=.. net . <key>: float32 torch error X, kernel error Y' lines of pytest -s, reduced to the
     largest pair per (head, loss, d_raw or loss values)."""
@@ -117,8 +181,16 @@ def main():
     ap.add_argument("--configs", default=",".join(CONFIGS))
     ap.add_argument("--grad-errors", default=None, help="output of pytest -s tests/test_population_trainer.py: its 'grad' lines go into the header")
     ap.add_argument("--loss-errors", default=None, help="output of pytest -s tests/test_population_device_loss.py: the largest errors go into the header")
+    ap.add_argument("--epoch", action="store_true", help="measure a whole epoch: train_epoch, train_epoch_ring and train_on_rows")
+    ap.add_argument("--rows", type=int, default=512, help="--epoch: rows per net")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.epoch:
+        text = "\n".join(main_epoch(a)) + "\n"
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
     lines = ["# tools/population_train_latency.py: one minibatch optimiser step of K nets, batch %d, one MI355X; median wall ms of %d "
              "repetitions after %d warm-up" % (a.batch, a.reps, a.warmup)]
     if a.grad_errors and os.path.exists(a.grad_errors):
