@@ -80,6 +80,13 @@ class AzgSelfplayConfig(C.Structure):
     ]
 
 
+class AzgRolloutConfig(C.Structure):
+    """include/azgym_eval.h: azg_rollout_config"""
+    _fields_ = [("struct_size", C.c_int32), ("episodes_per_net", C.c_int32), ("max_episode_length", C.c_int32),
+                ("action_rule", C.c_int32), ("game_id_base", C.c_uint32), ("episode", C.c_uint32)]
+
+
+ROLLOUT_RULE = {"mode": 0, "sample": 1}   # include/azgym_eval.h: AZG_ROLLOUT_*
 FINAL_SELECTION = {"max_visit": 0, "max_visits": 0, "max_value": 1}   # the reference's configs spell it both ways
 
 
@@ -103,7 +110,7 @@ SYMBOLS = [
 # entry points a library may lack (the tests' CPU oracle binds SYMBOLS only): bound when present, else the methods that need
 # them raise
 OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device",
-                    "population_selfplay_begin",
+                    "population_selfplay_begin", "policy_rollout",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
                     "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch"]
 
@@ -197,6 +204,9 @@ def bind(lib, prefix):
         f["set_population_weights_device"].argtypes = [vp, C.POINTER(AzgMlpDesc), C.c_void_p, C.c_size_t, C.c_int32]
     if "population_selfplay_begin" in f:
         f["population_selfplay_begin"].argtypes = [vp, C.POINTER(AzgSelfplayConfig)]
+    if "policy_rollout" in f:   # include/azgym_eval.h
+        f["policy_rollout"].argtypes = [vp, C.POINTER(AzgRolloutConfig), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_float)]
     if "trainer_create" in f:   # include/azgym_train.h
         f["trainer_create"].argtypes = [C.c_int32, C.POINTER(AzgMlpDesc), C.c_int32, C.c_int32, C.POINTER(vp)]
         f["trainer_destroy"].argtypes = [vp]
@@ -502,6 +512,25 @@ class Engine:
         self._check(self._f["mlp_eval"](self._h, _ptr(obs, C.c_float), n, _ptr(value, C.c_float), _ptr(dist, C.c_float),
                                         _ptr(raw, C.c_float)))
         return value, dist, raw
+
+    def policy_rollout(self, episodes_per_net, max_episode_length, rule="mode", game_id_base=0, episode=0):
+        """azg_policy_rollout (include/azgym_eval.h): ``episodes_per_net`` whole episodes per net played by the network alone,
+        one launch.  Game j of every net starts at the reset state of global game ``game_id_base + j``, episode ``episode``.
+        Returns a dict of [n_nets, episodes_per_net] arrays: returns (float64), lengths, terminated (bool), first_value."""
+        fn = self._optional("policy_rollout")
+        c = AzgRolloutConfig()
+        c.struct_size = C.sizeof(AzgRolloutConfig)
+        c.episodes_per_net, c.max_episode_length = int(episodes_per_net), int(max_episode_length)
+        c.action_rule = ROLLOUT_RULE[rule] if isinstance(rule, str) else int(rule)
+        c.game_id_base, c.episode = int(game_id_base), int(episode)
+        shape = (int(getattr(self, "n_nets", 1)), max(int(episodes_per_net), 0))
+        returns = np.empty(shape, np.float64)
+        lengths = np.empty(shape, np.int32)
+        terminated = np.empty(shape, np.int32)
+        first_value = np.empty(shape, np.float32)
+        self._check(fn(self._h, C.byref(c), _ptr(returns, C.c_double), _ptr(lengths, C.c_int32), _ptr(terminated, C.c_int32),
+                       _ptr(first_value, C.c_float)))
+        return {"returns": returns, "lengths": lengths, "terminated": terminated.astype(bool), "first_value": first_value}
 
     def dump_tree(self):
         B, R = self.n_trees, self.max_records

@@ -1,7 +1,7 @@
 // engine_host.h -- the engine object behind the C ABI, the helpers its translation units share, the host-side rules every kernel form
 // shares, and the entry points of the kernel translation units.  The C ABI: azg_engine.hip (creation, roots, search, results, dump,
 // info), engine_weights.hip (weight re-layout, populations), engine_selfplay.hip (device self-play, the results kernel's launch),
-// engine_selftest.hip (probes).  The search kernels are compiled in several translation units (dispatch_*.hip: one family of template
+// engine_selftest.hip (probes), dispatch_rollout.hip (policy rollouts, with their kernel).  The search kernels are compiled in several translation units (dispatch_*.hip: one family of template
 // instantiations each) so that the library builds in parallel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -116,6 +116,8 @@ struct azg_engine : EngineQueue {
     DeviceAllocs ls_mem;
     int ls_hp = 0;
     DeviceAllocs eval_mem; float* d_eval = nullptr; size_t eval_floats = 0;   // scratch of azg_mlp_eval (grow-only)
+    DeviceAllocs rollout_mem; char* d_rollout = nullptr; size_t rollout_bytes = 0;   // outputs of azg_policy_rollout (grow-only)
+    std::vector<char> rollout_stage;                                                  // ... and their host copy
     int searched = 0, results_valid = 0;
     int publish_once = 0;    // set by azg_dump_tree around its re-run of the last search
     int published = 0;       // the last search's trees are in global memory (global-tree / lock-step / team forms always are)

@@ -270,6 +270,11 @@ class BatchedSelfPlay:
         return torch.cat(rows, 0)
 
 
+# evaluate()'s default game ids start here: far above any self-play game, and the same for every engine and rank, so that
+# separately evaluated nets see the same start states too
+EVAL_GAME_ID_BASE = 1 << 30
+
+
 class PopulationSelfPlay:
     """Self-play with everything but the optimiser on the GPU (azg_selfplay_* in include/azgym.h), for K policies in ONE engine:
     games, final action rule, env step, episode resets and the replay ring live on the device; the host only downloads rows to
@@ -296,6 +301,7 @@ class PopulationSelfPlay:
         self.n_nets, self.games_per_net, self.n_games = self.mcts.n_models, self.mcts.trees_per_model, self.mcts.n_trees
         self.capacity = capacity_steps
         self.fifo = fifo
+        self.max_episode_length, self.tree_id_base = max_episode_length, tree_id_base
         self._replay = None
         # (one net: the plain engine's entry point, which the tests' CPU oracle also has)
         begin = self.engine.selfplay_begin if self.n_nets == 1 else self.engine.population_selfplay_begin
@@ -383,6 +389,32 @@ class PopulationSelfPlay:
             s += fsum[:, j]
             c += fcnt[:, j]
         return s, c
+
+    def evaluate(self, episodes_per_net: int, rule: str = "mode", max_episode_length: Optional[int] = None, episode: int = 0,
+                 game_id_base: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """How good each net is by itself: ``episodes_per_net`` whole episodes per net played by the raw policy, no search, in one
+        launch (azg_policy_rollout).  Game j of EVERY net starts from the same state (that of global game ``game_id_base + j``,
+        episode ``episode``), so the nets' returns can be ranked; another ``episode`` draws fresh start states.  ``rule``:
+        "mode" (arg-max logit / the squashed mean) or "sample" (the policy's own distribution, the engine's Philox streams).
+        ``max_episode_length`` None: the self-play's own limit; ``game_id_base`` None: ``EVAL_GAME_ID_BASE``, or the first id
+        above this engine's self-play games where those reach it.  Pending weight uploads are applied first, as ``play`` does;
+        self-play, searches and their results are left untouched.  Returns [n_nets, episodes_per_net] arrays "returns",
+        "lengths", "terminated", "first_value" (the value head at the start state) and "mean_return" [n_nets]."""
+        if rule not in _capi.ROLLOUT_RULE:
+            raise ValueError(f"evaluate: rule must be one of {sorted(_capi.ROLLOUT_RULE)}, not {rule!r}")
+        if int(episodes_per_net) < 1:
+            raise ValueError("evaluate: episodes_per_net must be >= 1")
+        if max_episode_length is None:
+            max_episode_length = self.max_episode_length
+        if int(max_episode_length) < 1:
+            raise ValueError("evaluate: max_episode_length must be >= 1")
+        if game_id_base is None:
+            game_id_base = max(EVAL_GAME_ID_BASE, self.tree_id_base + self.n_games)
+        self.sync_weights()
+        out = self.engine.policy_rollout(int(episodes_per_net), int(max_episode_length), rule=rule, game_id_base=int(game_id_base),
+                                         episode=int(episode))
+        out["mean_return"] = out["returns"].mean(axis=1)
+        return out
 
     def close(self) -> None:
         self.engine.close()

@@ -13,7 +13,8 @@ in PyTorch between them); --trainer device-fused computes the losses on the devi
 
 Seed k sets net k's initial weights (torch.manual_seed), and its own np.random.RandomState picks the training rows and the
 minibatch shuffles.  Prints one JSON line per iteration: per-seed mean return of the episodes finished in it and mean loss, and
-the time spent in self-play, training and weight sync."""
+the time spent in self-play, training and weight sync.  --eval-episodes N adds eval_return: each seed's raw policy (no search) over
+the same N start states, the number by which the seeds can be ranked."""
 import argparse
 import json
 import os
@@ -48,6 +49,11 @@ def parse_args(argv=None):
                     help="torch: agent.update net by net; device: every net's optimiser step in two HIP launches (PopulationTrainer) with "
                          "the losses in PyTorch between them; device-fused: the losses in a kernel of the same step (losses='device'); "
                          "device-epoch: device-fused's arithmetic, the whole epoch in one call on the rows in the self-play ring")
+    ap.add_argument("--eval-episodes", type=int, default=0,
+                    help="after every iteration play this many whole episodes per seed with the raw policy, no search, in one launch "
+                         "(PopulationSelfPlay.evaluate) and add the per-seed mean return as eval_return; every seed starts from the same "
+                         "states, so the numbers can be ranked (0: no evaluation)")
+    ap.add_argument("--eval-rule", choices=["mode", "sample"], default="mode", help="the evaluation's action rule")
     return ap.parse_args(argv)
 
 
@@ -131,6 +137,9 @@ def train(a, log=print, on_rows=None):
                         "selfplay_s": round(t2 - t1, 4), "train_s": round(t3 - t2, 4), "sync_s": round(t4 - t3, 4),
                         "weight_sync": sp.last_weight_sync,
                         "env_steps": (it + 1) * a.steps_per_iter * sp.n_games, "elapsed_s": round(time.time() - t0, 2)})
+        if a.eval_episodes > 0:   # the nets as just trained and uploaded, each by itself, over the same start states
+            ev = sp.evaluate(a.eval_episodes, rule=a.eval_rule)
+            history[-1]["eval_return"] = [round(float(x), 2) for x in ev["mean_return"]]
         if log:
             log(json.dumps(history[-1]), flush=True)
         fs0, fc0 = fs, fc

@@ -1,0 +1,293 @@
+"""Policy rollouts on the device (azg_policy_rollout, include/azgym_eval.h; run.PopulationSelfPlay.evaluate).
+
+The truth is a CPU rollout composed from the oracle's exports (rollout_ref.py): per net a single-net OracleEngine's mlp_eval, the
+action rule restated in numpy, the oracle's env step and reset law.  Returns, lengths, terminated flags and first values must be
+EQUAL: the HIP network and the oracle are bit-exact by the project's own rule, and everything after the network is float64
+arithmetic shared through include/azg_math.h."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+import rollout_ref as R
+from alphazero_gym_amd import _capi
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+
+KEYS = ("returns", "lengths", "terminated", "first_value")
+BASE = 1000   # game ids of the rollouts here
+
+
+def _hip():
+    from alphazero_gym_amd import _native
+    _native.lib()
+    return _native.HipEngine
+
+
+def _engine(game, net, wseeds, scale=1.0, n_trees=None):
+    """A HIP engine of len(wseeds) nets of shape ``net`` = (hidden, head, act, layernorm), net k with weights wseeds[k]."""
+    hidden, head, act, ln = net
+    K = len(wseeds)
+    e = _hip()(**dict(R.GAMES[game], n_trees=n_trees or K))
+    desc = R.net_desc(game, hidden, head, act, ln)
+    if K == 1:
+        e.set_weights(desc, R.net_blob(game, hidden, head, ln, wseeds[0], scale))
+    else:
+        e.set_population(K)
+        for k, ws in enumerate(wseeds):
+            e.set_net_weights(k, desc, R.net_blob(game, hidden, head, ln, ws, scale))
+    return e
+
+
+def _reference(game, net, wseeds, scale, G, max_len, rule, episode=0):
+    hidden, head, act, ln = net
+    per_net = [R.reference(game, tuple(hidden), head, act, ln, ws, scale, G, max_len, rule, BASE, episode) for ws in wseeds]
+    return {k: np.stack([r[k] for r in per_net]) for k in KEYS}
+
+
+def _assert_equal(got, want, what):
+    for k in KEYS:
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, (what, k)
+        np.testing.assert_array_equal(got[k], want[k], err_msg=f"{what}: {k}")
+
+
+# A reduced cross product: every G in {1, 16, 17, 33}, K in {1, 3}, the six environments, the three heads, hidden [16], [128, 128],
+# [256, 256] (+ three hidden layers: two register-resident hidden->hidden layers), a LayerNorm trunk and a rare activation (the
+# weight-streaming kernels), and both rules occur at least once.
+# name: game, (hidden, head, activation, layernorm), K, G, max_episode_length, rule
+SHAPES = {
+    "cartpole_2x128_relu_K3_G33_mode": ("cartpole", ((128, 128), "discrete", "relu", False), 3, 33, 40, "mode"),
+    "cartpole_1x16_elu_K1_G17_sample": ("cartpole", ((16,), "discrete", "elu", False), 1, 17, 30, "sample"),
+    "cartpole_2x128_ln_relu_K3_G17_sample": ("cartpole", ((128, 128), "discrete", "relu", True), 3, 17, 30, "sample"),
+    "mountaincar_1x16_relu_K3_G16_sample": ("mountaincar", ((16,), "discrete", "relu", False), 3, 16, 12, "sample"),
+    "acrobot_2x256_elu_K1_G17_mode": ("acrobot", ((256, 256), "discrete", "elu", False), 1, 17, 8, "mode"),
+    "acrobot_2x64_relu_K3_G1_sample": ("acrobot", ((64, 64), "discrete", "relu", False), 3, 1, 8, "sample"),
+    "pendulum_v1_2x256_elu_K3_G33_sample": ("pendulum_v1", ((256, 256), "normal", "elu", False), 3, 33, 10, "sample"),
+    "pendulum_v1_2x256_elu_K1_G16_mode": ("pendulum_v1", ((256, 256), "normal", "elu", False), 1, 16, 10, "mode"),
+    "pendulum_v0_3x128_gmm2_K3_G17_sample": ("pendulum_v0", ((128, 128, 128), "gmm2", "elu", False), 3, 17, 10, "sample"),
+    "pendulum_v1_2x128_gmm2_K1_G1_mode": ("pendulum_v1", ((128, 128), "gmm2", "relu", False), 1, 1, 6, "mode"),
+    "pendulum_v0_2x48_ln_silu_K1_G16_sample": ("pendulum_v0", ((48, 48), "normal", "silu", True), 1, 16, 10, "sample"),
+    "mcc_2x64_elu_K1_G16_mode": ("mcc", ((64, 64), "normal", "elu", False), 1, 16, 15, "mode"),
+    "mcc_2x64_elu_K3_G17_sample": ("mcc", ((64, 64), "normal", "elu", False), 3, 17, 15, "sample"),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_rollout_equals_cpu_rollout(name):
+    game, net, K, G, max_len, rule = SHAPES[name]
+    wseeds = [500 + 7 * k for k in range(K)]
+    want = _reference(game, net, wseeds, 1.0, G, max_len, rule)
+    e = _engine(game, net, wseeds)
+    got = e.policy_rollout(G, max_len, rule=rule, game_id_base=BASE)
+    e.close()
+    _assert_equal(got, want, name)
+
+
+# Frozen games: inside ONE 16-game group some games end early (at several different steps) while others run to the length limit.
+# name: game, net, weight seed, weight scale, max_episode_length, rule -- chosen so that the CPU rollout alone shows the spread
+FROZEN = {
+    "cartpole": ("cartpole", ((128, 128), "discrete", "relu", False), 200, 1.0, 14, "sample"),
+    "acrobot": ("acrobot", ((64, 64), "discrete", "relu", False), 314, 4.0, 90, "mode"),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(FROZEN))
+def test_frozen_games(name):
+    game, net, wseed, scale, max_len, rule = FROZEN[name]
+    want = _reference(game, net, [wseed], scale, 16, max_len, rule)
+    lengths, term = want["lengths"][0], want["terminated"][0]
+    assert len(set(lengths.tolist())) >= 3, lengths
+    assert term.any() and (~term).any(), term
+    assert (lengths[~term] == max_len).all() and (lengths[term] <= max_len).all()
+    e = _engine(game, net, [wseed], scale)
+    got = e.policy_rollout(16, max_len, rule=rule, game_id_base=BASE)
+    e.close()
+    _assert_equal(got, want, name)
+
+
+@pytest.mark.gpu
+def test_common_start_states():
+    """Game j starts from the same state for every net: identical weights give identical arrays; different weights differ in the
+    value of that common start state.  Another ``episode`` is another set of start states."""
+    game, net = "pendulum_v1", ((128, 128), "normal", "elu", False)
+    same = _engine(game, net, [510, 510, 510])
+    got = same.policy_rollout(17, 8, rule="sample", game_id_base=BASE)
+    other = same.policy_rollout(17, 8, rule="sample", game_id_base=BASE, episode=1)
+    same.close()
+    for k in KEYS:
+        for n in (1, 2):
+            np.testing.assert_array_equal(got[k][n], got[k][0], err_msg=k)
+    assert (other["first_value"] != got["first_value"]).all()
+    diff = _engine(game, net, [510, 517, 524])
+    got_d = diff.policy_rollout(17, 8, rule="sample", game_id_base=BASE)
+    diff.close()
+    np.testing.assert_array_equal(got_d["first_value"][0], got["first_value"][0])
+    assert (got_d["first_value"][1] != got_d["first_value"][0]).all() and (got_d["first_value"][2] != got_d["first_value"][0]).all()
+
+
+@pytest.mark.gpu
+def test_no_side_effects_on_selfplay():
+    """Two self-play populations with the same seeds play 3 steps; one evaluates between step 1 and step 2: same rows, ring, returns."""
+    import torch
+    from alphazero_gym_amd import run
+    from selfplay_train import build_agent
+    _hip()
+
+    def make():
+        nets = []
+        for s in (3, 11):
+            torch.manual_seed(s)
+            nets.append(build_agent("CartPole-v0", [32, 32], 6, "cpu", 1e-3)[0].nn)
+        return run.PopulationSelfPlay(nets, game="CartPole-v0", games_per_net=3, n_rollouts=6, c_uct=1.0, max_episode_length=2,
+                                      capacity_steps=4, seed=5)
+    a, b = make(), make()
+    a.play(1)
+    b.play(1)
+    ev = a.evaluate(5, rule="sample", max_episode_length=20)
+    assert ev["returns"].shape == (2, 5) and ev["mean_return"].shape == (2,)
+    np.testing.assert_array_equal(ev["returns"], ev["lengths"].astype(np.float64))   # CartPole pays 1 per step
+    a.play(2)
+    b.play(2)
+    assert a.engine.selfplay_ring() == b.engine.selfplay_ring() == (3, 0, 3)
+    np.testing.assert_array_equal(a.engine.selfplay_rows(clear=False), b.engine.selfplay_rows(clear=False))
+    for x, y in zip(a.finished_returns(), b.finished_returns()):
+        np.testing.assert_array_equal(x, y)
+    assert a.finished_returns()[1].sum() > 0
+    for x, y in zip(a.engine.selfplay_stats(), b.engine.selfplay_stats()):
+        np.testing.assert_array_equal(x, y)
+    a.close()
+    b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("game,net", [("cartpole", ((128, 128), "discrete", "relu", False)),
+                                      ("pendulum_v1", ((256, 256), "normal", "elu", False))])
+def test_no_side_effects_on_search(game, net):
+    """A search's results are still there after a rollout, and the same search (roots, search index) gives them again."""
+    e = _engine(game, net, [500, 507, 514], n_trees=6)
+    roots = e.synthetic_roots()
+    e.set_search_index(3)
+    e.search(roots)
+    before = e.results()
+    e.policy_rollout(17, 6, rule="sample", game_id_base=BASE)
+    after = e.results()
+    e.set_search_index(3)
+    e.search(roots)
+    again = e.results()
+    e.close()
+    for k in before:
+        np.testing.assert_array_equal(after[k], before[k], err_msg=k)
+        np.testing.assert_array_equal(again[k], before[k], err_msg=k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("game,net,rule", [("cartpole", ((128, 128), "discrete", "relu", False), "sample"),
+                                           ("pendulum_v0", ((128, 128, 128), "gmm2", "elu", False), "sample"),
+                                           ("mcc", ((64, 64), "normal", "elu", False), "mode")])
+def test_population_invariance(game, net, rule):
+    """Net k of a K = 3 rollout is what a one-net engine with net k's weights plays under the same config."""
+    wseeds = [500, 507, 514]
+    pop = _engine(game, net, wseeds)
+    got = pop.policy_rollout(17, 9, rule=rule, game_id_base=BASE, episode=2)
+    pop.close()
+    for k, ws in enumerate(wseeds):
+        one = _engine(game, net, [ws])
+        alone = one.policy_rollout(17, 9, rule=rule, game_id_base=BASE, episode=2)
+        one.close()
+        for key in KEYS:
+            np.testing.assert_array_equal(got[key][k], alone[key][0], err_msg=f"net {k} {key}")
+
+
+@pytest.mark.gpu
+def test_abi_errors():
+    """Every refusal returns its code with a message and leaves the output arrays alone."""
+    import ctypes as C
+    from alphazero_gym_amd import _native
+    f = _native.fns()
+    rollout, last_error = f["policy_rollout"], f["last_error"]
+    G = 4
+    out = None
+
+    def sentinels():
+        return (np.full((3, G), -7.5), np.full((3, G), -7, np.int32), np.full((3, G), -7, np.int32), np.full((3, G), -7.5, np.float32))
+
+    def cfg(**over):
+        c = _capi.AzgRolloutConfig()
+        c.struct_size = C.sizeof(_capi.AzgRolloutConfig)
+        c.episodes_per_net, c.max_episode_length, c.action_rule, c.game_id_base, c.episode = G, 5, 0, BASE, 0
+        for k, v in over.items():
+            setattr(c, k, v)
+        return c
+
+    def call(e, c, skip=()):
+        nonlocal out
+        out = sentinels()
+        ptrs = [_capi._ptr(out[0], C.c_double), _capi._ptr(out[1], C.c_int32), _capi._ptr(out[2], C.c_int32), _capi._ptr(out[3], C.c_float)]
+        for i in skip:
+            ptrs[i] = None
+        return rollout(e._h if e is not None else None, C.byref(c) if c is not None else None, *ptrs)
+
+    def refused(e, code, c, skip=(), message=True):
+        assert call(e, c, skip) == code
+        if message:
+            assert (last_error(e._h) or b"").decode() != ""
+        for arr, s in zip(out, sentinels()):
+            np.testing.assert_array_equal(arr, s)
+
+    game, net = "cartpole", ((128, 128), "discrete", "relu", False)
+    e = _engine(game, net, [500, 507, 514])
+    refused(None, _capi.AZG_E_INVALID, cfg(), message=False)
+    refused(e, _capi.AZG_E_INVALID, None)
+    refused(e, _capi.AZG_E_INVALID, cfg(), skip=(0,))
+    refused(e, _capi.AZG_E_INVALID, cfg(), skip=(1,))
+    refused(e, _capi.AZG_E_INVALID, cfg(struct_size=8))
+    refused(e, _capi.AZG_E_INVALID, cfg(episodes_per_net=0))
+    refused(e, _capi.AZG_E_INVALID, cfg(max_episode_length=0))
+    refused(e, _capi.AZG_E_INVALID, cfg(action_rule=2))
+    refused(e, _capi.AZG_E_INVALID, cfg(action_rule=-1))
+    # terminated and first_value may be NULL
+    assert call(e, cfg(), skip=(2, 3)) == 0
+    assert (out[1] > 0).all() and (out[2] == -7).all() and (out[3] == -7.5).all()
+    # a net without weights: a fresh population, two of three nets uploaded
+    e.set_population(1)
+    e.set_population(3)
+    desc = R.net_desc(game, *net)
+    for k in (0, 1):
+        e.set_net_weights(k, desc, R.net_blob(game, net[0], net[1], net[3], 500 + k))
+    refused(e, _capi.AZG_E_STATE, cfg())
+    e.close()
+    fresh = _hip()(**dict(R.GAMES[game], n_trees=3))
+    refused(fresh, _capi.AZG_E_STATE, cfg())
+    # networks of 512 (padded) units and wider: one-net engines only
+    wide = ((512, 512), "discrete", "relu", False)
+    fresh.set_weights(R.net_desc(game, *wide), R.net_blob(game, wide[0], wide[1], False, 500))
+    refused(fresh, _capi.AZG_E_UNSUPPORTED, cfg())
+    fresh.close()
+
+
+def _example(*extra):
+    import population_selfplay_train as P
+    return P, P.parse_args(["--game", "CartPole-v0", "--seeds", "3", "11", "5", "--games-per-seed", "4", "--n-rollouts", "6", "--iters", "2",
+                            "--steps-per-iter", "6", "--train-rows", "20", "--batch-size", "8", "--hidden", "32", "32",
+                            "--max-episode-length", "8", "--device", "cpu", *extra])
+
+
+@pytest.mark.gpu
+def test_example_eval_return():
+    _hip()
+    P, a = _example("--eval-episodes", "8")
+    hist = P.train(a, log=None)
+    assert len(hist) == 2
+    for rec in hist:
+        assert len(rec["eval_return"]) == 3 and np.isfinite(rec["eval_return"]).all()
+        assert all(1.0 <= x <= 8.0 for x in rec["eval_return"])   # CartPole: one per step, at most max_episode_length steps
+    P, a = _example()
+    plain = P.train(a, log=None)
+    assert all("eval_return" not in rec for rec in plain)
+    # the evaluation does not disturb the loop it is added to
+    for rec, ref in zip(hist, plain):
+        assert rec["mean_return"] == ref["mean_return"] and rec["loss"] == ref["loss"]
