@@ -98,6 +98,10 @@ int azg_selfplay_step(azg_engine* e) {
     if (!e) return AZG_E_INVALID;
     if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
     if (e->sp_ring == AZG_RING_STOP && e->sp_steps >= e->sp_cap) return fail(e, AZG_E_STATE, "replay ring is full: download and clear the rows");
+    // selfplay_kernel (roots with more than 16 children) knows the continuous final-action rule only: a discrete engine has its env's
+    // 2 or 3 actions per node (azg_engine_create), so this cannot happen
+    if (e->Kmax > 16 && e->cfg.mode != AZG_MODE_CONTINUOUS)
+        return fail(e, AZG_E_STATE, "device self-play with more than 16 actions per node supports continuous mode only");
     int rc = azg_search_resident(e);
     if (rc) return rc;
     ON_DEVICE(e);
@@ -108,7 +112,7 @@ int azg_selfplay_step(azg_engine* e) {
     if (e->sp_steps < e->sp_cap) { slot = e->sp_steps; e->sp_steps += 1; }
     else { slot = e->sp_insert; e->sp_insert = (e->sp_insert + 1) % e->sp_steps; }
     SelfPlay sp;
-    sp.max_len = e->sp_max_len; sp.deterministic = e->sp_det; sp.step_idx = e->sp_step_idx;
+    sp.max_len = e->sp_max_len; sp.deterministic = e->sp_det; sp.S_obs = e->S_obs; sp.step_idx = e->sp_step_idx;
     sp.final_selection = e->sp_fs; sp.agent_eps = e->sp_agent_eps; sp.ctab = e->d_sp_ctab;
     sp.t = e->d_sp_t; sp.episode = e->d_sp_episode; sp.fcnt = e->d_sp_fcnt; sp.ret = e->d_sp_ret; sp.fsum = e->d_sp_fsum;
     sp.rows = e->d_sp_rows + (size_t)slot * e->cfg.n_trees * e->sp_row;
@@ -118,11 +122,10 @@ int azg_selfplay_step(azg_engine* e) {
     if (e->Kmax <= 16) {
         rc = launch_results(e);   // return_results of this search (a launch only after the lock-step / team kernels)
         if (rc) return rc;
+        hipLaunchKernelGGL(selfplay_kernel16, dim3((B + SP_TREES - 1) / SP_TREES), dim3(16 * SP_TREES), 0, e->stream, e->P, sp);
+    } else {
+        hipLaunchKernelGGL(selfplay_kernel, dim3((B + SPW_THREADS - 1) / SPW_THREADS), dim3(SPW_THREADS), 0, e->stream, e->P, sp);   // (reads the trees)
     }
-    if (e->Kmax <= 16)
-        hipLaunchKernelGGL(selfplay_kernel16, dim3((B + SP_TREES - 1) / SP_TREES), dim3(16 * SP_TREES), 0, e->stream, e->P, sp, e->Kmax, e->cfg.v_target, e->cfg.env_id, e->S_obs);
-    else
-        hipLaunchKernelGGL(selfplay_kernel, dim3((B + RK_THREADS - 1) / RK_THREADS), dim3(RK_THREADS), 0, e->stream, e->P, sp, e->Kmax, e->cfg.v_target, e->cfg.env_id, e->S_obs);
     HIPCHK(e, hipGetLastError());
     e->sp_total += 1;
     e->sp_step_idx += 1;

@@ -164,3 +164,26 @@ __device__ __forceinline__ void pendulum_step(int v1, const double* s, double sn
     pendulum_dynamics(v1, s, sn_th, action, o);
     *done = 0;
 }
+
+// ------------------------------------------------------------------------------------------------ a real game, env chosen at run time
+
+// The kernels that play real games -- the self-play step (aux_kernels.cuh) and the policy rollouts (rollout.cuh) -- observe and step a
+// game through these two and nothing else; discrete or continuous and Pendulum's version follow from env_id alone.  (The tree phases
+// are compiled per env family and keep env_obs<ENV> / family_env_step<ENV>.)
+__device__ __forceinline__ bool env_is_continuous(int env_id) {
+    return env_id == AZG_ENV_PENDULUM_V0 || env_id == AZG_ENV_PENDULUM_V1 || env_id == AZG_ENV_MOUNTAINCAR_CONT;
+}
+// the network's eight inputs of state s (those beyond the env's observation are zero), and Pendulum's sin(theta) for game_step
+__device__ __forceinline__ void game_obs(int env_id, const double* s, float* obs8, double* sn) {
+    if (!env_is_continuous(env_id)) { discrete_env_obs(env_id, s, obs8); *sn = 0.0; return; }
+    if (env_id == AZG_ENV_MOUNTAINCAR_CONT) env_obs<AZG_ENV_MOUNTAINCAR_CONT>(s, obs8, sn);
+    else env_obs<AZG_ENV_PENDULUM_V1>(s, obs8, sn);
+    obs8[4] = obs8[5] = obs8[6] = obs8[7] = 0.0f;
+}
+// one step from s, the state game_obs saw (sn: its sine); a discrete action arrives as the float its caller holds, an index
+__device__ __forceinline__ void game_step(int env_id, const double* s, double sn, float action, double* ns, double* reward, int* done) {
+    if (env_id == AZG_ENV_ACROBOT) azg_acrobot_step(s, (int)action, ns, reward, done);
+    else if (!env_is_continuous(env_id)) discrete_env_step(env_id, s, (int)action, ns, reward, done);
+    else if (env_id == AZG_ENV_MOUNTAINCAR_CONT) mountaincar_cont_step(s, action, ns, reward, done);
+    else pendulum_step(env_id == AZG_ENV_PENDULUM_V1, s, sn, action, ns, reward, done);
+}

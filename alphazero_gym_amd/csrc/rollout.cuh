@@ -1,7 +1,8 @@
 // rollout.cuh -- policy rollouts (azg_policy_rollout, include/azgym_eval.h): whole episodes played by the network alone, one launch.
 // Grid (ceil(G / 16), n_nets): one workgroup carries 16 games of one net from reset through every step.  Per step the games'
 // observations go to LDS, mlp_forward runs (the search's network phase: same MFMA chains and chunked head sums, so the head outputs
-// are azg_mlp_eval's), and one lane per game turns them into an action, steps the env in float64 and adds the reward.  A finished game
+// are azg_mlp_eval's), and one lane per game turns them into an action, steps the env in float64 and adds the reward; observing and
+// stepping are env.cuh's game_obs / game_step, the game interface this kernel shares with the self-play step.  A finished game
 // is frozen (its lane skips the step; its column still rides through the network and every barrier); the loop ends when wave 0 finds
 // no live game, which it tells the workgroup through LDS, so the exit is uniform.  No atomics: every output has one writer.
 // NREG > 0: the hidden->hidden weights stay in registers for the whole rollout (the nets the search keeps resident: resident_layers,
@@ -115,7 +116,6 @@ __global__ __launch_bounds__(256, 1) void rollout_kernel(KParams P, Rollout ro) 
     const int game = blockIdx.x * 16 + tid;
     const bool mine = tid < 16 && game < ro.G;
     const unsigned gid = ro.game_id_base + (unsigned)game;
-    const bool cont = P.mode == AZG_MODE_CONTINUOUS;
     double s[4] = {0.0, 0.0, 0.0, 0.0}, ret = 0.0;
     int t = 0, term = 0;
     float v0 = 0.0f;
@@ -128,11 +128,7 @@ __global__ __launch_bounds__(256, 1) void rollout_kernel(KParams P, Rollout ro) 
         double sn = 0.0;   // Pendulum: sin(theta) of the state observed, for its step
         if (tid < 16) {
             float obs[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-            if (mine) {
-                if (!cont) discrete_env_obs(P.env_id, s, obs);
-                else if (P.env_id == AZG_ENV_MOUNTAINCAR_CONT) env_obs<AZG_ENV_MOUNTAINCAR_CONT>(s, obs, &sn);
-                else env_obs<AZG_ENV_PENDULUM_V1>(s, obs, &sn);
-            }
+            if (mine) game_obs(P.env_id, s, obs, &sn);
 #pragma unroll
             for (int k = 0; k < 8; ++k) s_obsT[k * 16 + tid] = obs[k];
         }
@@ -153,10 +149,7 @@ __global__ __launch_bounds__(256, 1) void rollout_kernel(KParams P, Rollout ro) 
             const float a = rollout_action<NCH>(P, ro, s_parts, s_bhead, tid, gid, (unsigned)t);
             double ns[4] = {0.0, 0.0, 0.0, 0.0}, r;
             int done;
-            if (!cont && P.env_id == AZG_ENV_ACROBOT) azg_acrobot_step(s, (int)a, ns, &r, &done);
-            else if (!cont) discrete_env_step(P.env_id, s, (int)a, ns, &r, &done);
-            else if (P.env_id == AZG_ENV_MOUNTAINCAR_CONT) mountaincar_cont_step(s, a, ns, &r, &done);
-            else pendulum_step(P.v1, s, sn, a, ns, &r, &done);
+            game_step(P.env_id, s, sn, a, ns, &r, &done);
             ret = ret + r;
             t += 1;
 #pragma unroll
