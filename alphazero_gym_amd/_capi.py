@@ -112,13 +112,24 @@ SYMBOLS = [
 OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device",
                     "population_selfplay_begin", "policy_rollout",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
-                    "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch"]
+                    "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch",
+                    "trainer_backward_step_opt", "trainer_step_opt", "trainer_epoch_opt"]
 
 
 class AzgRmsprop(C.Structure):
     """include/azgym_train.h: azg_rmsprop"""
     _fields_ = [("struct_size", C.c_int32), ("centered", C.c_int32), ("lr", C.c_double), ("alpha", C.c_double), ("eps", C.c_double),
                 ("weight_decay", C.c_double), ("momentum", C.c_double), ("grad_clip", C.c_double)]
+
+
+OPT_RMSPROP, OPT_ADAM = 0, 1
+
+
+class AzgOptim(C.Structure):
+    """include/azgym_train.h: azg_optim"""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("lr", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("alpha", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("grad_clip", C.c_double),
+                ("state0", C.c_void_p), ("state1", C.c_void_p), ("grad_norms", C.c_void_p), ("step", C.c_int32)]
 
 
 LOSS_ALPHAZERO, LOSS_A0C, LOSS_A0C_TUNED = 0, 1, 2
@@ -225,6 +236,12 @@ def bind(lib, prefix):
     if "trainer_epoch" in f:
         f["trainer_epoch"].argtypes = [vp, vp, C.POINTER(AzgEpochRows), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(AzgLossCfg),
                                        C.POINTER(AzgAlphaState), C.POINTER(AzgRmsprop), vp, vp, C.POINTER(C.c_int32)]
+    if "trainer_backward_step_opt" in f:
+        f["trainer_backward_step_opt"].argtypes = [vp, vp, vp, C.c_int32, C.POINTER(AzgOptim), vp]
+        f["trainer_step_opt"].argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.POINTER(AzgLossCfg), C.POINTER(AzgAlphaState),
+                                          C.POINTER(AzgOptim), vp, vp, vp]
+        f["trainer_epoch_opt"].argtypes = [vp, vp, C.POINTER(AzgEpochRows), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(AzgLossCfg),
+                                           C.POINTER(AzgAlphaState), C.POINTER(AzgOptim), vp, C.POINTER(C.c_int32)]
     return f
 
 
@@ -632,6 +649,21 @@ def rmsprop_opt(lr, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, center
     return o
 
 
+def optim(kind, lr, state0, state1=None, *, eps=None, weight_decay=0.0, alpha=0.99, betas=(0.9, 0.999), grad_clip=0.0, step=0,
+          grad_norms=None):
+    """azg_optim.  ``kind``: "rmsprop" / "adam" (or OPT_*), with torch.optim.RMSprop's / torch.optim.Adam's keyword names and defaults
+    (eps 1e-8); ``state0`` / ``state1`` / ``grad_norms``: device addresses ([n_nets, P] square_avg or exp_avg_sq; [n_nets, P]
+    exp_avg; optional [n_nets]); ``step``: the Adam steps taken so far."""
+    o = AzgOptim()
+    o.struct_size = C.sizeof(AzgOptim)
+    o.kind = {"rmsprop": OPT_RMSPROP, "adam": OPT_ADAM}.get(kind, kind)
+    o.lr, o.eps, o.weight_decay = float(lr), float(1e-8 if eps is None else eps), float(weight_decay)
+    o.alpha, (o.beta1, o.beta2), o.grad_clip = float(alpha), (float(b) for b in betas), float(grad_clip)
+    o.state0, o.state1, o.grad_norms = state0 or None, state1 or None, grad_norms or None
+    o.step = int(step)
+    return o
+
+
 def loss_cfg(policy, loss):
     """azg_loss_cfg of a policy and loss pairing (one of a population's: all nets share them).  The head kind comes from the
     policy's class, the loss kind from the loss's; names, not isinstance, so that the reference's objects work alike.  Raises
@@ -774,6 +806,41 @@ class Trainer:
                                              int(batch_size), C.byref(cfg) if cfg is not None else None,
                                              C.byref(alpha) if alpha is not None else None, C.byref(opt) if opt is not None else None,
                                              square_avg or None, loss_sums or None, C.byref(n_mb)))
+        return n_mb.value
+
+    def backward_step_opt(self, params, d_raw, n_rows, opt, grads=None):
+        """azg_trainer_backward_step_opt: ``backward_step`` with an ``optim`` (RMSprop or Adam, optional gradient clipping; the
+        optimiser state's addresses are in ``opt``)."""
+        if "trainer_backward_step_opt" not in self._f:
+            raise NotImplementedError("this engine library has no azg_trainer_backward_step_opt")
+        self._check(self._f["trainer_backward_step_opt"](self._h, params or None, d_raw or None, int(n_rows),
+                                                         C.byref(opt) if opt is not None else None, grads or None))
+
+    def step_opt(self, params, obs, actions, counts, values, n_rows, n_actions, cfg, alpha, opt, grads, raw_out, losses):
+        """azg_trainer_step_opt: ``step`` with an ``optim``."""
+        if "trainer_step_opt" not in self._f:
+            raise NotImplementedError("this engine library has no azg_trainer_step_opt")
+        self._check(self._f["trainer_step_opt"](self._h, params or None, obs or None, actions or None, counts or None, values or None,
+                                                int(n_rows), int(n_actions), C.byref(cfg) if cfg is not None else None,
+                                                C.byref(alpha) if alpha is not None else None, C.byref(opt) if opt is not None else None,
+                                                grads or None, raw_out or None, losses or None))
+
+    def epoch_opt(self, params, rows, order, batch_size, cfg, alpha, opt, loss_sums):
+        """azg_trainer_epoch_opt: ``epoch`` with an ``optim``; minibatch m is Adam step ``opt.step + m + 1``.  Returns the number of
+        minibatches."""
+        if "trainer_epoch_opt" not in self._f:
+            raise NotImplementedError("this engine library has no azg_trainer_epoch_opt")
+        n_order, ptr = 0, None
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.int32)
+            if order.ndim != 2 or order.shape[0] != self.n_nets:
+                raise ValueError("Trainer.epoch_opt: order must be [n_nets, n_order]")
+            n_order, ptr = order.shape[1], _ptr(order, C.c_int32)
+        n_mb = C.c_int32(0)
+        self._check(self._f["trainer_epoch_opt"](self._h, params or None, C.byref(rows) if rows is not None else None, ptr, n_order,
+                                                 int(batch_size), C.byref(cfg) if cfg is not None else None,
+                                                 C.byref(alpha) if alpha is not None else None, C.byref(opt) if opt is not None else None,
+                                                 loss_sums or None, C.byref(n_mb)))
         return n_mb.value
 
     def read_d_raw(self, n_rows, d_raw):

@@ -4,7 +4,7 @@ loop over the nets.
 The K policies' parameters live in ONE float32 tensor ``flat[K, P]`` (``bind_flat``; state_dict order, the order of
 ``_capi.policy_tensors``) that the trainer's kernels update in place and the search engine's gather reads directly
 (``PopulationMCTS.upload_flat``).  The boundary between HIP and PyTorch is the heads' raw output ``raw[K, B, 1 + n_dist]``:
-trunk, heads, their backward pass and the RMSprop step are kernels; the losses (``population_loss``: ``DiscreteAgent._loss`` /
+trunk, heads, their backward pass and the optimiser step (RMSprop; with ``optimizers="agents"`` also Adam and gradient clipping) are kernels; the losses (``population_loss``: ``DiscreteAgent._loss`` /
 ``ContinuousAgent._loss`` restated once for a leading K axis, the tuned alpha's Adam step included) stay in PyTorch and give
 ``d_raw`` by autograd on those small tensors.  ``PopulationTrainer(..., losses="device")`` moves that boundary out of the step:
 the same losses, their ``d_raw`` and the tuned alpha's Adam step are one more kernel between the two (``azg_trainer_step``: three
@@ -187,6 +187,26 @@ def _rmsprop_settings(opt) -> tuple:
     return (g["lr"], g["alpha"], g["eps"], g["weight_decay"])
 
 
+def _optimizer_settings(opt) -> tuple:
+    """(class, settings) of an agent's optimiser as ``optimizers="agents"`` takes it: plain RMSprop, or Adam without amsgrad."""
+    if type(opt) not in (torch.optim.RMSprop, torch.optim.Adam):
+        raise ValueError(f"PopulationTrainer: the nets' optimiser must be torch.optim.RMSprop or torch.optim.Adam, not {type(opt).__name__}")
+    if len(opt.param_groups) != 1:
+        raise ValueError("PopulationTrainer: one parameter group per agent's optimiser")
+    g = opt.param_groups[0]
+    if g.get("maximize", False):
+        raise ValueError("PopulationTrainer: an optimiser with maximize is not supported")
+    if type(opt) is torch.optim.RMSprop:
+        if g["momentum"] != 0 or g["centered"]:
+            raise ValueError("PopulationTrainer: RMSprop with momentum or centered is not supported")
+        return (torch.optim.RMSprop, float(g["lr"]), float(g["alpha"]), float(g["eps"]), float(g["weight_decay"]))
+    if g.get("amsgrad", False):
+        raise ValueError("PopulationTrainer: Adam with amsgrad is not supported")
+    if g.get("capturable", False) or g.get("differentiable", False):
+        raise ValueError("PopulationTrainer: Adam with capturable or differentiable is not supported")
+    return (torch.optim.Adam, float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"]))
+
+
 def minibatch_bounds(n: int, batch_size: int) -> List[Tuple[int, int]]:
     """The minibatches [i, j) of an epoch over n shuffled rows: consecutive slices of ``batch_size``, the last one absorbing the
     remainder (``train_on_rows``'s and ``ReplayBuffer.__next__``'s rule; azg_trainer_epoch cuts the same way)."""
@@ -209,7 +229,8 @@ def _need_device_losses(losses: str, who: str) -> None:
 class PopulationTrainer:
     """The optimiser step of K agents of one shape, all at once.  Raises ``ValueError`` naming the reason when the agents cannot be
     trained here (the caller then keeps the per-agent ``agent.update`` loop): different network shapes, LayerNorm, gradient
-    clipping, an optimiser other than plain RMSprop, different losses or hyper-parameters, parameters not on a GPU.
+    clipping or an optimiser other than plain RMSprop (unless ``optimizers="agents"``), different losses or hyper-parameters,
+    parameters not on a GPU.
 
     Binds the agents' parameters to ``self.flat`` [K, P] (``bind_flat``) and their RMSprop ``square_avg`` state to
     ``self.square_avg`` [K, P] (state an agent already has is taken over; the agents' torch optimisers keep working on the same
@@ -219,12 +240,24 @@ class PopulationTrainer:
 
     ``losses``: "torch" computes the losses and ``d_raw`` in PyTorch between the two launches; "device" computes them in a kernel of
     the same step (``_capi.Trainer.step``).  Then ``log_alpha`` and its Adam state (``alpha_exp_avg``, ``alpha_exp_avg_sq``,
-    ``alpha_step``) are plain tensors of the trainer that the kernel steps in place, and there is no ``alpha_optimizer``."""
+    ``alpha_step``) are plain tensors of the trainer that the kernel steps in place, and there is no ``alpha_optimizer``.
 
-    def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False, losses: str = "torch"):
+    ``optimizers``: "rmsprop" (the default) takes plain RMSprop without gradient clipping and steps it inside the backward kernel.
+    "agents" takes what the agents carry -- plain RMSprop or ``torch.optim.Adam`` (no amsgrad), and their ``grad_clip`` -- through
+    the ``*_opt`` entry points: the backward launch writes the gradients first, then computes every net's global norm, clips and
+    steps.  Every agent must have the same optimiser class, settings and ``grad_clip``, and, with Adam, have taken the same number
+    of steps.  Adam's ``exp_avg`` / ``exp_avg_sq`` become ``self.exp_avg`` / ``self.exp_avg_sq`` [K, P] with the agents' optimiser
+    state as views of their rows; ``self.opt_step`` counts the steps and ``export_alpha()`` / ``close()`` write it to every
+    ``state[p]["step"]``.  ``self.last_grad_norms`` [K] holds every net's gradient norm (before clipping) of the last step."""
+
+    def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False, losses: str = "torch",
+                 optimizers: str = "rmsprop"):
         if losses not in ("torch", "device"):
             raise ValueError("losses must be 'torch' or 'device'")
+        if optimizers not in ("rmsprop", "agents"):
+            raise ValueError("optimizers must be 'rmsprop' or 'agents'")
         self.losses = losses
+        self.optimizers = optimizers
         self.agents = list(agents)
         if not self.agents:
             raise ValueError("PopulationTrainer needs at least one agent")
@@ -236,10 +269,27 @@ class PopulationTrainer:
             raise ValueError(f"PopulationTrainer: policy {type(a0.nn).__name__} is not supported")
         if any(a.nn.layernorm for a in self.agents):
             raise ValueError("PopulationTrainer: LayerNorm trunks are not trained on the device")
-        if any(a.clip for a in self.agents):
-            raise ValueError("PopulationTrainer: grad_clip != 0 is not supported (a per-net global norm needs a pass of its own)")
-        if len({_rmsprop_settings(a.optimizer) for a in self.agents}) != 1:
-            raise ValueError("PopulationTrainer: every agent must have the same RMSprop settings")
+        opt_states: List[List[dict]] = []
+        if optimizers == "agents":
+            if any(float(a.clip or 0.0) < 0 for a in self.agents):
+                raise ValueError("PopulationTrainer: grad_clip must be >= 0")
+            if len({float(a.clip or 0.0) for a in self.agents}) != 1:
+                raise ValueError("PopulationTrainer: every agent must have the same grad_clip")
+            settings = [_optimizer_settings(a.optimizer) for a in self.agents]
+            if len({st[0] for st in settings}) != 1:
+                raise ValueError("PopulationTrainer: every agent must have the same optimiser class")
+            if len(set(settings)) != 1:
+                raise ValueError(f"PopulationTrainer: every agent must have the same {settings[0][0].__name__} settings")
+            if settings[0][0] is torch.optim.Adam:
+                opt_states = [[a.optimizer.state.get(p, {}) for p in a.nn.parameters()] for a in self.agents]
+                flat_states = [st for sts in opt_states for st in sts]
+                if any(flat_states) and (not all(flat_states) or len({float(st["step"]) for st in flat_states}) != 1):
+                    raise ValueError("PopulationTrainer: the agents' Adam optimisers must have taken the same number of steps")
+        else:
+            if any(a.clip for a in self.agents):
+                raise ValueError("PopulationTrainer: grad_clip != 0 is not supported (a per-net global norm needs a pass of its own)")
+            if len({_rmsprop_settings(a.optimizer) for a in self.agents}) != 1:
+                raise ValueError("PopulationTrainer: every agent must have the same RMSprop settings")
         if len({_loss_settings(a.loss) for a in self.agents}) != 1:
             raise ValueError("PopulationTrainer: every agent must have the same loss class and hyper-parameters")
         descs = [_capi.policy_tensors(a.nn) for a in self.agents]
@@ -268,19 +318,36 @@ class PopulationTrainer:
         self.policy, self.loss = a0.nn, a0.loss
         self.device = device
         self.desc, self.flat = bind_flat([a.nn for a in self.agents])
-        lr, alpha, eps, wd = _rmsprop_settings(a0.optimizer)
-        self.opt = _capi.rmsprop_opt(lr=lr, alpha=alpha, eps=eps, weight_decay=wd)
-        self.square_avg = torch.zeros_like(self.flat)
+        self.square_avg, self.exp_avg, self.exp_avg_sq, self.opt_step = None, None, None, 0
+        self.opt, self.last_grad_norms = None, None
+        adam = optimizers == "agents" and type(a0.optimizer) is torch.optim.Adam
+        if optimizers == "agents":
+            self._opt_settings = _optimizer_settings(a0.optimizer)
+            self.grad_clip = float(a0.clip or 0.0)
+            self.last_grad_norms = torch.zeros(K, dtype=torch.float32, device=device)
+        else:
+            lr, alpha, eps, wd = _rmsprop_settings(a0.optimizer)
+            self.opt = _capi.rmsprop_opt(lr=lr, alpha=alpha, eps=eps, weight_decay=wd)
+        if adam:
+            self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+            if opt_states and opt_states[0] and opt_states[0][0]:
+                self.opt_step = int(float(opt_states[0][0]["step"]))
+            bound = (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq))
+        else:
+            self.square_avg = torch.zeros_like(self.flat)
+            bound = (("square_avg", self.square_avg),)
         for k, a in enumerate(self.agents):
             off = 0
+            g = a.optimizer.param_groups[0]
             for p in _capi.policy_tensors(a.nn)[1]:
-                view = self.square_avg[k, off:off + p.numel()].view_as(p)
                 st = a.optimizer.state[p]
-                if "square_avg" in st:
-                    view.copy_(st["square_avg"])
-                else:
-                    st["step"] = torch.tensor(0.0)
-                st["square_avg"] = view
+                if "step" not in st:   # (torch keeps the count on the host unless the optimiser is capturable or fused)
+                    st["step"] = torch.tensor(0.0, device=p.device if (g.get("capturable") or g.get("fused")) else "cpu")
+                for name, table in bound:
+                    view = table[k, off:off + p.numel()].view_as(p)
+                    if name in st:
+                        view.copy_(st[name])
+                    st[name] = view
                 off += p.numel()
         self.grads = torch.zeros_like(self.flat) if keep_grads else None
         self.log_alpha, self.alpha_optimizer = None, None
@@ -357,9 +424,24 @@ class PopulationTrainer:
         d_raw = self._last_d_raw = raw.grad.contiguous()
         out = per_net(losses)   # (the copy to the host also completes d_raw)
         stream.synchronize()
-        self.trainer.backward_step(self.flat.data_ptr(), d_raw.data_ptr(), B, self.opt, self.square_avg.data_ptr(),
-                                   self.grads.data_ptr() if self.grads is not None else None)
+        grads = self.grads.data_ptr() if self.grads is not None else None
+        if self.optimizers == "agents":   # (the clip happens inside: PyTorch never sees the parameter gradients)
+            self.trainer.backward_step_opt(self.flat.data_ptr(), d_raw.data_ptr(), B, self._optim(), grads)
+            self.opt_step += 1
+        else:
+            self.trainer.backward_step(self.flat.data_ptr(), d_raw.data_ptr(), B, self.opt, self.square_avg.data_ptr(), grads)
         return out
+
+    def _optim(self):
+        """azg_optim of the next step (``optimizers="agents"``): the agents' settings, the trainer's state tensors and step count."""
+        st = self._opt_settings
+        common = dict(grad_clip=self.grad_clip, step=self.opt_step, grad_norms=self.last_grad_norms.data_ptr())
+        if st[0] is torch.optim.Adam:
+            _, lr, betas, eps, wd = st
+            return _capi.optim("adam", lr, self.exp_avg_sq.data_ptr(), self.exp_avg.data_ptr(), eps=eps, weight_decay=wd, betas=betas,
+                               **common)
+        _, lr, alpha, eps, wd = st
+        return _capi.optim("rmsprop", lr, self.square_avg.data_ptr(), eps=eps, weight_decay=wd, alpha=alpha, **common)
 
     def _update_device(self, states, actions, counts, values, raw, stream) -> List[Dict[str, float]]:
         """``update`` with the losses on the device: one native call (three launches), one copy of losses[K, 5] to the host."""
@@ -370,9 +452,15 @@ class PopulationTrainer:
         state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
                                   self.alpha_exp_avg_sq.data_ptr()) if tuned else None
         stream.synchronize()
-        self.trainer.step(self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), B,
-                          actions.shape[2], self.loss_cfg, state, self.opt, self.square_avg.data_ptr(),
-                          self.grads.data_ptr() if self.grads is not None else None, raw.data_ptr(), table.data_ptr())
+        grads = self.grads.data_ptr() if self.grads is not None else None
+        if self.optimizers == "agents":
+            self.trainer.step_opt(self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), B,
+                                  actions.shape[2], self.loss_cfg, state, self._optim(), grads, raw.data_ptr(), table.data_ptr())
+            self.opt_step += 1
+        else:
+            self.trainer.step(self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), B,
+                              actions.shape[2], self.loss_cfg, state, self.opt, self.square_avg.data_ptr(), grads, raw.data_ptr(),
+                              table.data_ptr())
         if tuned:
             self.alpha_step += 1
         self.last_raw, self._last_d_raw = raw, None
@@ -417,8 +505,13 @@ class PopulationTrainer:
         state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
                                   self.alpha_exp_avg_sq.data_ptr()) if tuned else None
         torch.cuda.current_stream(self.device).synchronize()
-        n_steps = self.trainer.epoch(self.flat.data_ptr(), where, order, int(batch_size), self.loss_cfg, state, self.opt,
-                                     self.square_avg.data_ptr(), sums.data_ptr())
+        if self.optimizers == "agents":
+            n_steps = self.trainer.epoch_opt(self.flat.data_ptr(), where, order, int(batch_size), self.loss_cfg, state, self._optim(),
+                                             sums.data_ptr())
+            self.opt_step += n_steps
+        else:
+            n_steps = self.trainer.epoch(self.flat.data_ptr(), where, order, int(batch_size), self.loss_cfg, state, self.opt,
+                                         self.square_avg.data_ptr(), sums.data_ptr())
         assert n_steps == len(bounds)
         if tuned:
             self.alpha_step += n_steps
@@ -475,7 +568,12 @@ class PopulationTrainer:
     def export_alpha(self) -> None:
         """Write every net's learned temperature and its Adam state (step, exp_avg, exp_avg_sq) back into its agent's loss object,
         so that ``agent.update`` or a checkpoint of ``agent.loss`` continues from where the trainer stands.  ``close()`` does this;
-        between ``update`` calls the agents' own ``loss.log_alpha`` / ``loss.alpha`` are stale until it is called."""
+        between ``update`` calls the agents' own ``loss.log_alpha`` / ``loss.alpha`` are stale until it is called.  With Adam under
+        ``optimizers="agents"`` it also writes the trainer's step count into every ``optimizer.state[p]["step"]``."""
+        if self.exp_avg is not None:
+            for a in self.agents:
+                for p in a.nn.parameters():
+                    a.optimizer.state[p]["step"].fill_(float(self.opt_step))
         if self.log_alpha is None:
             return
         if self.alpha_optimizer is None:   # losses="device": the trainer's own tensors
@@ -486,15 +584,17 @@ class PopulationTrainer:
             for k, a in enumerate(self.agents):
                 la = a.loss.log_alpha
                 la.data.copy_(self.log_alpha[k])
-                a.loss.alpha = la.exp()
+                with torch.enable_grad():   # (the loss object's next _update_alpha differentiates alpha by log_alpha)
+                    a.loss.alpha = la.exp()
                 if state:
                     a.loss.optimizer.state[la] = {"step": torch.tensor(float(state["step"])),
                                                   "exp_avg": state["exp_avg"][k].detach().to(la.device).clone(),
                                                   "exp_avg_sq": state["exp_avg_sq"][k].detach().to(la.device).clone()}
 
     def close(self) -> None:
-        """Hand the learned temperatures back to the agents (``export_alpha``) and free the native trainer.  The parameters and the
-        RMSprop state need no hand-back: the agents' modules and optimisers are views of ``flat`` / ``square_avg``."""
+        """Hand the learned temperatures and Adam's step count back to the agents (``export_alpha``) and free the native trainer.
+        The parameters and the optimiser state need no hand-back: the agents' modules and optimisers are views of ``flat`` /
+        ``square_avg`` (or ``exp_avg`` / ``exp_avg_sq``)."""
         if self.trainer._h:
             self.export_alpha()
         self.trainer.close()

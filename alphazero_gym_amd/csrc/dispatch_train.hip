@@ -1,5 +1,6 @@
 // dispatch_train.hip -- the population trainer's C ABI (include/azgym_train.h): scratch, checks and the three launches of train.cuh;
-// azg_trainer_epoch enqueues them for a whole epoch of minibatches behind a gather launch each.
+// azg_trainer_epoch enqueues them for a whole epoch of minibatches behind a gather launch each.  The *_opt entry points take an
+// azg_optim and choose the backward launch's form: fused RMSprop, or gradients first and norm, clip and update after the last layer.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -18,6 +19,7 @@ struct azg_trainer {
     float log_std_min = 0.0f, log_std_max = 0.0f;
     TrainDims d{};
     float* scratch = nullptr;
+    float* grad_buf = nullptr;   // [n_nets][P]: where the deferred backward form keeps the gradients when the caller gives no grads
     // the loss kernel's: the rows' terms [n_nets][3][max_batch] (float64), and azg_trainer_step's raw and d_raw [n_nets][max_batch][NO]
     // (allocated by the first call that needs them)
     double* loss_rows = nullptr;
@@ -52,6 +54,7 @@ void azg_trainer_destroy(azg_trainer* t) {
     DeviceScope scope(t->device_id);
     if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
     if (t->scratch) (void)hipFree(t->scratch);
+    if (t->grad_buf) (void)hipFree(t->grad_buf);
     if (t->loss_rows) (void)hipFree(t->loss_rows);
     if (t->raw_buf) (void)hipFree(t->raw_buf);
     if (t->d_raw_buf) (void)hipFree(t->d_raw_buf);
@@ -110,6 +113,7 @@ int azg_trainer_create(int32_t device_id, const azg_mlp_desc* desc, int32_t n_ne
     // (not cleared: the forward launch writes every scratch element below its padded row count, and the backward launch of the
     // same n_rows reads nothing else)
     hipError_t rc = hipMalloc((void**)&t->scratch, bytes);
+    if (rc == hipSuccess) rc = hipMalloc((void**)&t->grad_buf, (size_t)n_nets * (size_t)d.P * sizeof(float));
     if (rc == hipSuccess) rc = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
     if (rc != hipSuccess) {
         const std::string msg = std::string("azg_trainer_create: ") + hipGetErrorString(rc);
@@ -151,6 +155,71 @@ static void launch_backward(azg_trainer* t, float* params, const float* d_raw, i
     o.wd = (float)opt->weight_decay;
     hipLaunchKernelGGL(train_backward_kernel, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, o, params, d_raw, n_rows,
                        square_avg, grads, t->scratch);
+}
+
+// An azg_optim as the launch takes it: the fused kernel with the old settings (plain RMSprop, nothing asked of the gradients as a
+// whole), or the deferred kernel's TrainOptD for the step opt->step + step_add + 1.
+struct OptPlan {
+    bool fused;
+    azg_rmsprop rms;
+    TrainOptD o;
+};
+
+static int check_optim(azg_trainer* t, const char* who, const float* params, const azg_optim* opt, int32_t n_rows, int step_add,
+                       OptPlan* out) {
+    const std::string w(who);
+    if (!params || !opt) return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
+    if (opt->struct_size != (int32_t)sizeof(azg_optim)) return tfail(t, AZG_E_INVALID, w + ": azg_optim.struct_size mismatch");
+    if (n_rows < 1 || n_rows > t->max_batch) return tfail(t, AZG_E_INVALID, w + ": n_rows must be 1..max_batch");
+    if (opt->kind != AZG_OPT_RMSPROP && opt->kind != AZG_OPT_ADAM) return tfail(t, AZG_E_UNSUPPORTED, w + ": unknown optimiser kind");
+    const bool adam = opt->kind == AZG_OPT_ADAM;
+    if (!opt->state0 || (adam && !opt->state1)) return tfail(t, AZG_E_INVALID, w + ": NULL state pointer in azg_optim");
+    if (!(opt->lr >= 0.0) || !(opt->eps >= 0.0)) return tfail(t, AZG_E_INVALID, w + ": lr and eps must be >= 0");
+    if (!(opt->grad_clip >= 0.0)) return tfail(t, AZG_E_INVALID, w + ": grad_clip must be >= 0");
+    if (opt->step < 0 || opt->step > INT32_MAX - 1 - step_add) return tfail(t, AZG_E_INVALID, w + ": azg_optim.step must be >= 0 (and fit with the epoch's steps)");
+    if (adam && !(opt->beta1 >= 0.0 && opt->beta1 < 1.0 && opt->beta2 >= 0.0 && opt->beta2 < 1.0))
+        return tfail(t, AZG_E_INVALID, w + ": Adam's betas must lie in [0, 1)");
+    OptPlan pl{};
+    pl.fused = !adam && opt->grad_clip == 0.0 && !opt->grad_norms;
+    pl.rms.struct_size = (int32_t)sizeof(azg_rmsprop);
+    pl.rms.lr = opt->lr; pl.rms.alpha = opt->alpha; pl.rms.eps = opt->eps; pl.rms.weight_decay = opt->weight_decay;
+    TrainOptD& o = pl.o;
+    o.rms.lr = (float)opt->lr; o.rms.alpha = (float)opt->alpha; o.rms.one_minus_alpha = (float)(1.0 - opt->alpha);
+    o.rms.eps = (float)opt->eps; o.rms.wd = (float)opt->weight_decay;
+    o.kind = opt->kind;
+    o.clip = (float)opt->grad_clip;
+    o.want_norm = (opt->grad_clip != 0.0 || opt->grad_norms) ? 1 : 0;
+    if (adam) {
+        const double step = (double)opt->step + (double)step_add + 1.0;
+        o.lr = opt->lr; o.b1 = opt->beta1; o.b2 = opt->beta2; o.eps = opt->eps; o.wd = opt->weight_decay;
+        o.bc1 = 1.0 - std::pow(o.b1, step);
+        o.bc2_sqrt = std::sqrt(1.0 - std::pow(o.b2, step));
+    }
+    *out = pl;
+    return AZG_OK;
+}
+
+// The optimiser argument of a step or an epoch in either form: (azg_rmsprop, square_avg) of the first entry points, or an azg_optim.
+struct OptArg {
+    bool opt_form;
+    const azg_rmsprop* rms;
+    float* square_avg;
+    const azg_optim* opt;
+};
+
+static int check_opt_arg(azg_trainer* t, const char* who, const float* params, const OptArg& a, int32_t n_rows, int step_add, OptPlan* pl) {
+    if (a.opt_form) return check_optim(t, who, params, a.opt, n_rows, step_add, pl);
+    if (int rc = check_backward(t, who, params, a.rms, a.square_avg, n_rows)) return rc;
+    pl->fused = true;
+    pl->rms = *a.rms;
+    return AZG_OK;
+}
+
+static void launch_backward_arg(azg_trainer* t, float* params, const float* d_raw, int n_rows, const OptPlan& pl, const OptArg& a,
+                                float* grads) {
+    if (pl.fused) { launch_backward(t, params, d_raw, n_rows, &pl.rms, a.opt_form ? a.opt->state0 : a.square_avg, grads); return; }
+    hipLaunchKernelGGL(train_backward_deferred_kernel, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, pl.o, params, d_raw,
+                       n_rows, a.opt->state0, a.opt->state1, grads ? grads : t->grad_buf, a.opt->grad_norms, t->scratch);
 }
 
 // The loss settings as the kernel takes them; every refusal of azg_trainer_loss.
@@ -277,6 +346,19 @@ int azg_trainer_backward_step(azg_trainer* t, float* params, const float* d_raw,
     return finish(t, "azg_trainer_backward_step");
 }
 
+int azg_trainer_backward_step_opt(azg_trainer* t, float* params, const float* d_raw, int32_t n_rows, const azg_optim* opt, float* grads) {
+    if (!t) return AZG_E_INVALID;
+    if (!d_raw) return tfail(t, AZG_E_INVALID, "azg_trainer_backward_step_opt: NULL pointer");
+    OptPlan pl;
+    if (int rc = check_optim(t, "azg_trainer_backward_step_opt", params, opt, n_rows, 0, &pl)) return rc;
+    if (t->fwd_rows != n_rows) return tfail(t, AZG_E_STATE, "azg_trainer_backward_step_opt: needs azg_trainer_forward of the same n_rows first");
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    t->fwd_rows = 0;
+    launch_backward_arg(t, params, d_raw, (int)n_rows, pl, OptArg{true, nullptr, nullptr, opt}, grads);
+    return finish(t, "azg_trainer_backward_step_opt");
+}
+
 int azg_trainer_loss(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values, int32_t n_rows,
                      int32_t n_actions, const azg_loss_cfg* cfg, const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
     if (!t) return AZG_E_INVALID;
@@ -290,15 +372,16 @@ int azg_trainer_loss(azg_trainer* t, const float* raw, const float* actions, con
     return finish(t, "azg_trainer_loss");
 }
 
-int azg_trainer_step(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
-                     int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
-                     const azg_rmsprop* opt, float* square_avg, float* grads, float* raw_out, float* losses) {
+static int step_impl(azg_trainer* t, const char* who, float* params, const float* obs, const float* actions, const float* counts,
+                     const float* values, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg,
+                     const azg_alpha_state* alpha_state, const OptArg& oa, float* grads, float* raw_out, float* losses) {
     if (!t) return AZG_E_INVALID;
-    if (!actions || !counts || !values || !losses) return tfail(t, AZG_E_INVALID, "azg_trainer_step: NULL pointer");
-    if (int rc = check_forward(t, "azg_trainer_step", params, obs, n_rows)) return rc;
+    if (!actions || !counts || !values || !losses) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
+    if (int rc = check_forward(t, who, params, obs, n_rows)) return rc;
     LossDims c;
-    if (int rc = check_loss(t, "azg_trainer_step", n_rows, n_actions, loss_cfg, alpha_state, &c)) return rc;
-    if (int rc = check_backward(t, "azg_trainer_step", params, opt, square_avg, n_rows)) return rc;
+    if (int rc = check_loss(t, who, n_rows, n_actions, loss_cfg, alpha_state, &c)) return rc;
+    OptPlan pl;
+    if (int rc = check_opt_arg(t, who, params, oa, n_rows, 0, &pl)) return rc;
     DeviceScope scope(t->device_id);
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
     const size_t per = (size_t)t->n_nets * t->max_batch * t->d.NO;
@@ -310,19 +393,33 @@ int azg_trainer_step(azg_trainer* t, float* params, const float* obs, const floa
     t->step_rows = 0;
     launch_forward(t, params, obs, (int)n_rows, raw);
     launch_loss(t, c, raw, actions, counts, values, (int)n_rows, alpha_state, t->d_raw_buf, losses);
-    launch_backward(t, params, t->d_raw_buf, (int)n_rows, opt, square_avg, grads);
-    if (int rc = finish(t, "azg_trainer_step")) return rc;
+    launch_backward_arg(t, params, t->d_raw_buf, (int)n_rows, pl, oa, grads);
+    if (int rc = finish(t, who)) return rc;
     t->step_rows = n_rows;
     return AZG_OK;
 }
 
-int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
-                      int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_rmsprop* opt,
-                      float* square_avg, double* loss_sums, int32_t* n_minibatches) {
+int azg_trainer_step(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
+                     int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
+                     const azg_rmsprop* opt, float* square_avg, float* grads, float* raw_out, float* losses) {
+    return step_impl(t, "azg_trainer_step", params, obs, actions, counts, values, n_rows, n_actions, loss_cfg, alpha_state,
+                     OptArg{false, opt, square_avg, nullptr}, grads, raw_out, losses);
+}
+
+int azg_trainer_step_opt(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
+                         int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
+                         const azg_optim* opt, float* grads, float* raw_out, float* losses) {
+    return step_impl(t, "azg_trainer_step_opt", params, obs, actions, counts, values, n_rows, n_actions, loss_cfg, alpha_state,
+                     OptArg{true, nullptr, nullptr, opt}, grads, raw_out, losses);
+}
+
+static int epoch_impl(azg_trainer* t, const char* who, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
+                      int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const OptArg& oa,
+                      double* loss_sums, int32_t* n_minibatches) {
     if (!t) return AZG_E_INVALID;
-    const char* who = "azg_trainer_epoch";
     const std::string w(who);
-    if (!params || !rows || !order || !loss_cfg || !opt || !square_avg || !loss_sums || !n_minibatches)
+    const bool no_opt = oa.opt_form ? !oa.opt : (!oa.rms || !oa.square_avg);
+    if (!params || !rows || !order || !loss_cfg || no_opt || !loss_sums || !n_minibatches)
         return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
     if (rows->struct_size != (int32_t)sizeof(azg_epoch_rows)) return tfail(t, AZG_E_INVALID, w + ": azg_epoch_rows.struct_size mismatch");
     if (!rows->rows) return tfail(t, AZG_E_INVALID, w + ": NULL pointer in azg_epoch_rows");
@@ -350,11 +447,12 @@ int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows,
                          alpha_state->struct_size == (int32_t)sizeof(azg_alpha_state);
     if (stepped && alpha_state->step > INT32_MAX - M) return tfail(t, AZG_E_INVALID, w + ": azg_alpha_state.step too large");
     std::vector<LossDims> dims((size_t)M);
+    std::vector<OptPlan> plans((size_t)M);
     for (int m = 0; m < M; ++m) {
         azg_alpha_state st{};
         if (stepped) { st = *alpha_state; st.step += m; }
         if (int rc = check_loss(t, who, count[m], A, loss_cfg, stepped ? &st : alpha_state, &dims[m])) return rc;
-        if (int rc = check_backward(t, who, params, opt, square_avg, count[m])) return rc;
+        if (int rc = check_opt_arg(t, who, params, oa, count[m], m, &plans[m])) return rc;
     }
     const size_t K = (size_t)t->n_nets;
     for (size_t e = 0; e < K * (size_t)n_order; ++e)
@@ -386,7 +484,7 @@ int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows,
         launch_forward(t, params, obs, B, t->raw_buf);
         launch_loss(t, dims[m], t->raw_buf, actions, counts, values, B, alpha_state, t->d_raw_buf,
                     t->loss_table + (size_t)m * K * AZG_LOSS_SLOTS);
-        launch_backward(t, params, t->d_raw_buf, B, opt, square_avg, nullptr);
+        launch_backward_arg(t, params, t->d_raw_buf, B, plans[m], oa, nullptr);
     }
     const int n_sums = t->n_nets * AZG_LOSS_SLOTS;
     hipLaunchKernelGGL(train_loss_sum_kernel, dim3((n_sums + 63) / 64), dim3(64), 0, t->stream, t->loss_table, M, n_sums, loss_sums);
@@ -394,6 +492,20 @@ int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows,
     t->step_rows = count[M - 1];
     *n_minibatches = M;
     return AZG_OK;
+}
+
+int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
+                      int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_rmsprop* opt,
+                      float* square_avg, double* loss_sums, int32_t* n_minibatches) {
+    return epoch_impl(t, "azg_trainer_epoch", params, rows, order, n_order, batch_size, loss_cfg, alpha_state,
+                      OptArg{false, opt, square_avg, nullptr}, loss_sums, n_minibatches);
+}
+
+int azg_trainer_epoch_opt(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
+                          int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_optim* opt,
+                          double* loss_sums, int32_t* n_minibatches) {
+    return epoch_impl(t, "azg_trainer_epoch_opt", params, rows, order, n_order, batch_size, loss_cfg, alpha_state,
+                      OptArg{true, nullptr, nullptr, opt}, loss_sums, n_minibatches);
 }
 
 int azg_trainer_read_d_raw(azg_trainer* t, int32_t n_rows, float* d_raw) {

@@ -1,4 +1,5 @@
-// train.cuh -- population training (include/azgym_train.h): forward, backward and RMSprop step of K small MLPs on
+// train.cuh -- population training (include/azgym_train.h): forward, backward and optimiser step (RMSprop fused into the backward
+// pass; or Adam / RMSprop with gradient clipping as a phase after it) of K small MLPs on
 // v_mfma_f32_16x16x4_f32.  Parameters are read in state_dict order straight from the caller's [K][P] array; activations live in
 // the trainer's scratch (global memory, L2-resident at these sizes), so every GEMM operand is addressed as element (row, k) of some
 // array and one routine (mma_strip) serves Z = A W^T, dA = dZ W and dW = dZ^T A.
@@ -178,86 +179,90 @@ __device__ __forceinline__ float tr_colsum(int rows, F x) { return (float)tr_col
 // weights before the barrier and (b) writes them after it; (b) of one layer and (a) of the next touch different arrays.
 __global__ __launch_bounds__(TR_BWD_THREADS) void train_backward_kernel(TrainDims d, TrainOpt opt, float* params, const float* d_raw, int n_rows,
                                                                         float* square_avg, float* grads_all, float* scratch) {
-    const int net = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
-    const int NWV = TR_BWD_THREADS / 64;
-    float* p = params + (size_t)net * d.P;
-    float* sq = square_avg + (size_t)net * d.P;
-    float* grads = grads_all ? grads_all + (size_t)net * d.P : nullptr;
-    float* sc = scratch + (size_t)net * d.per_net;
-    const int Bpad = (n_rows + 15) / 16 * 16, MT = Bpad / 16;
-    const int L = d.n_layers, NO = d.NO, NOT = (NO + 15) / 16;
-    const float* dr = d_raw + (size_t)net * n_rows * NO;
-    auto dzh = [&](int row, int o) { return (row < n_rows && o < NO) ? dr[(size_t)row * NO + o] : 0.0f; };
+#define TR_EMIT(idx, grad) tr_update(opt, p, sq, grads, idx, grad)
+#include "train_backward_layers.inc"
+#undef TR_EMIT
+}
 
-    for (int l = L; l >= 0; --l) {
-        const bool head = l == L;
-        const int Hl = head ? NO : d.H[l];                      // outputs of this layer
-        const int MTl = head ? NOT : Hl / 16;                   // ... in tiles
-        const int Hp = l > 0 ? d.H[l - 1] : d.in_dim;           // inputs of this layer
-        const float* Aprev = l > 0 ? sc + d.s_A[l - 1] : sc + d.s_obs;
-        const int lda = l > 0 ? Hp : TR_OBS_LD;
-        const float* dZ = head ? nullptr : sc + d.s_D[l];       // [Bpad][Hl]
-        float* W = p + (head ? d.offWv : d.offW[l]);
-        if (l > 0) {
-            // (a) dZ_{l-1}[row][j] = D_{l-1}[row][j] * sum_u dZ_l[row][u] W_l[u][j]
-            float* Dp = sc + d.s_D[l - 1];
-            const int ns = (Hp + 63) / 64, kdim = head ? NOT * 16 : Hl;
-            for (int s = wave; s < MT * ns; s += NWV) {
-                const int m0 = (s / ns) * 16, n0 = (s % ns) * 64;
-                const int nt = (Hp - n0) >= 64 ? 4 : (Hp - n0) / 16;
-                tr_f32x4 acc[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) acc[t] = tr_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                if (head)
-                    mma_strip<4>(acc, nt, kdim, [&](int k) { return dzh(m0 + r, k); },
-                                 [&](int t, int k) { return k < NO ? W[(size_t)k * Hp + (k > 0) + n0 + 16 * t + r] : 0.0f; }, g);
-                else
-                    mma_strip<4>(acc, nt, kdim, [&](int k) { return dZ[(size_t)(m0 + r) * Hl + k]; },
-                                 [&](int t, int k) { return W[(size_t)k * Hp + n0 + 16 * t + r]; }, g);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    if (t < nt) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const size_t at = (size_t)(m0 + 4 * g + i) * Hp + n0 + 16 * t + r;
-                            Dp[at] = acc[t][i] * Dp[at];
-                        }
-                    }
-                }
-            }
+// ------------------------------------------------------------------------------------------------ backward, then the optimiser
+// torch.optim.Adam's single-tensor step (no amsgrad, not capturable) of one element in float64 from its float32 state: weight decay
+// into the gradient, exp_avg by lerp, exp_avg_sq, then p -= (lr / bc1) * exp_avg / (sqrt(exp_avg_sq) / bc2_sqrt + eps) with
+// bc1 = 1 - beta1^t and bc2_sqrt = sqrt(1 - beta2^t) of the step t being taken (host, float64).  exp_avg and exp_avg_sq are rounded
+// to float32 once and stored; the caller rounds and stores p.  The loss kernel's log_alpha and the deferred backward kernel's
+// parameters both step through it.
+__device__ __forceinline__ void tr_adam(double& p, float* exp_avg, float* exp_avg_sq, double g, double lr, double b1, double b2, double eps,
+                                        double wd, double bc1, double bc2_sqrt) {
+    if (wd != 0.0) g = g + wd * p;
+    const double m0 = (double)*exp_avg;
+    const double m = m0 + (g - m0) * (1.0 - b1);
+    const double s = b2 * (double)*exp_avg_sq + (1.0 - b2) * g * g;
+    p = p - (lr / bc1) * (m / (sqrt(s) / bc2_sqrt + eps));
+    *exp_avg = (float)m; *exp_avg_sq = (float)s;
+}
+
+// The deferred form's optimiser settings (azg_optim as the kernel takes it).
+struct TrainOptD {
+    TrainOpt rms;                       // AZG_OPT_RMSPROP: tr_update's
+    int kind, want_norm;                // AZG_OPT_*; compute the norm (grad_clip != 0 or grad_norms given)
+    float clip;                         // 0: off
+    double lr, b1, b2, eps, wd, bc1, bc2_sqrt;   // AZG_OPT_ADAM: tr_adam's
+};
+
+// The same walk through the layers, the same GEMMs in the same order, with every gradient element stored to grads_all [K][P] and
+// no parameter written.  Then, behind a workgroup barrier (the workgroup's own global stores are complete and visible to its own
+// later loads), the optimiser as a phase of its own, thread t taking elements t, t + 1024, ...:
+//   norm    each thread sums (double)g * (double)g of its elements in one float64 chain (the products are exact); the 1024 partials
+//           are added pairwise through LDS, partner t + 512, t + 256, ... t + 1: a fixed tree.  total_norm = (float)sqrt(sum).
+//   clip    torch's clip_grad_norm_: coef = min(clip / (total_norm + 1e-6f), 1) in float32, every gradient times coef (coef == 1
+//           included).  grads_all keeps the gradients as they were before clipping and weight decay.
+//   update  tr_update (RMSprop, float32, the fused form's own) or tr_adam (float64, rounded once) of every element.
+// state0: square_avg / exp_avg_sq, state1: exp_avg.  norms (may be NULL): total_norm of every net.
+__global__ __launch_bounds__(TR_BWD_THREADS) void train_backward_deferred_kernel(TrainDims d, TrainOptD o, float* params, const float* d_raw,
+                                                                                 int n_rows, float* state0, float* state1, float* grads_all,
+                                                                                 float* norms, float* scratch) {
+    {
+        float* square_avg = state0;
+#define TR_EMIT(idx, grad) ((void)sq, grads[idx] = (grad))
+#include "train_backward_layers.inc"
+#undef TR_EMIT
+    }
+    // every wave's gradient stores have completed before any wave passes the barrier and loads them
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const int net = blockIdx.x, tid = threadIdx.x, P = d.P;
+    float* p = params + (size_t)net * P;
+    float* s0 = state0 + (size_t)net * P;
+    float* grads = grads_all + (size_t)net * P;
+    float coef = 1.0f;
+    if (o.want_norm) {
+        __shared__ double part[TR_BWD_THREADS];
+        double acc = 0.0;
+        for (int i = tid; i < P; i += TR_BWD_THREADS) { const double gd = (double)grads[i]; acc = acc + gd * gd; }
+        part[tid] = acc;
+        __syncthreads();
+        for (int st = TR_BWD_THREADS / 2; st > 0; st >>= 1) {
+            if (tid < st) part[tid] = part[tid] + part[tid + st];
             __syncthreads();
         }
-        // (b) dW_l[u][j] = sum_row dZ_l[row][u] A_{l-1}[row][j]: the k axis is the batch row
-        const int ns = (Hp + 63) / 64;
-        for (int s = wave; s < MTl * ns; s += NWV) {
-            const int m0 = (s / ns) * 16, n0 = (s % ns) * 64;
-            const int nt = (Hp - n0) >= 64 ? 4 : (Hp - n0 + 15) / 16;
-            tr_f32x4 acc[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = tr_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            auto fb = [&](int t, int k) { const int j = n0 + 16 * t + r; return j < Hp ? Aprev[(size_t)k * lda + j] : 0.0f; };
-            if (head) mma_strip<4>(acc, nt, Bpad, [&](int k) { return dzh(k, m0 + r); }, fb, g);
-            else mma_strip<4>(acc, nt, Bpad, [&](int k) { return dZ[(size_t)k * Hl + m0 + r]; }, fb, g);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                if (t < nt) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int u = m0 + 4 * g + i, j = n0 + 16 * t + r;
-                        if (u < Hl && j < Hp) {
-                            const int idx = head ? d.offWv + u * Hp + (u > 0) + j : d.offW[l] + u * Hp + j;
-                            tr_update(opt, p, sq, grads, idx, acc[t][i]);
-                        }
-                    }
-                }
-            }
+        const float total = (float)sqrt(part[0]);
+        if (norms && tid == 0) norms[net] = total;
+        if (o.clip != 0.0f) { const float c = o.clip / (total + 1e-6f); coef = c < 1.0f ? c : 1.0f; }
+    }
+    const bool clipped = o.clip != 0.0f;
+    if (o.kind == AZG_OPT_ADAM) {
+        float* s1 = state1 + (size_t)net * P;
+        for (int i = tid; i < P; i += TR_BWD_THREADS) {
+            float g = grads[i];
+            if (clipped) g = g * coef;
+            double pv = (double)p[i];
+            tr_adam(pv, s1 + i, s0 + i, (double)g, o.lr, o.b1, o.b2, o.eps, o.wd, o.bc1, o.bc2_sqrt);
+            p[i] = (float)pv;
         }
-        for (int u = tid; u < Hl; u += TR_BWD_THREADS) {
-            float gsum;
-            if (head) gsum = tr_colsum(n_rows, [&](int row) { return dr[(size_t)row * NO + u]; });
-            else gsum = tr_colsum(Bpad, [&](int row) { return dZ[(size_t)row * Hl + u]; });
-            const int idx = head ? (u == 0 ? d.offbv : d.offbd + u - 1) : d.offb[l] + u;
-            tr_update(opt, p, sq, grads, idx, gsum);
+    } else {
+        for (int i = tid; i < P; i += TR_BWD_THREADS) {
+            float g = grads[i];
+            if (clipped) g = g * coef;
+            tr_update(o.rms, p, s0, nullptr, i, g);
         }
     }
 }
@@ -452,12 +457,8 @@ __global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_kernel(LossDims c,
     double g = alpha_loss;
     if (c.clip != 0.0) { const double f = c.clip / (fabs(g) + 1e-6); g = g * (f < 1.0 ? f : 1.0); }
     double p = (double)la;
-    if (c.wd != 0.0) g = g + c.wd * p;
-    const double m0 = (double)exp_avg[net];
-    const double m = m0 + (g - m0) * (1.0 - c.b1);
-    const double s = c.b2 * (double)exp_avg_sq[net] + (1.0 - c.b2) * g * g;
-    p = p - (c.lr / c.bc1) * (m / (sqrt(s) / c.bc2_sqrt + c.eps));
-    exp_avg[net] = (float)m; exp_avg_sq[net] = (float)s; log_alpha[net] = (float)p;
+    tr_adam(p, exp_avg + net, exp_avg_sq + net, g, c.lr, c.b1, c.b2, c.eps, c.wd, c.bc1, c.bc2_sqrt);
+    log_alpha[net] = (float)p;
 }
 
 // ------------------------------------------------------------------------------------------------ a whole epoch

@@ -29,6 +29,7 @@ from .search.mcts import BatchedMCTS, PopulationMCTS
 LOSS_TUNED = dict(_target_="alphazero_gym_amd.agent.losses.A0CLossTuned", action_dim=1, alpha_init=1.0, lr=0.001, tau=0.1,
                   policy_coeff=0.1, value_coeff=1.0, reduction="mean", grad_clip=0, device="cpu")
 RMSPROP = dict(_target_="torch.optim.RMSprop", lr=0.001, alpha=0.9, eps=1e-10, weight_decay=0, momentum=0)
+ADAM = dict(_target_="torch.optim.Adam", lr=0.001, betas=(0.9, 0.99), weight_decay=0, eps=1e-07, amsgrad=False)   # config/optimizer/Adam.yaml
 
 CONTINUOUS_DEFAULTS = dict(
     game="Pendulum-v0", seed=34, num_train_episodes=45, max_episode_length=200, device="cpu",

@@ -8,6 +8,7 @@ minibatch step at once instead (agent.population_trainer.PopulationTrainer: two 
 in PyTorch between them); --trainer device-fused computes the losses on the device too (three launches, one host round trip);
 --trainer device-epoch takes the whole epoch of those steps in one native call that reads the rows straight from the self-play ring
 (PopulationTrainer.train_epoch_ring: no copy of the rows, one synchronisation per iteration instead of one per minibatch).
+--optimizer adam and --grad-clip X give every net the reference's Adam settings and gradient clipping, on every trainer.
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
@@ -43,6 +44,10 @@ def parse_args(argv=None):
     ap.add_argument("--hidden", type=int, nargs="+", default=[128, 128])
     ap.add_argument("--max-episode-length", type=int, default=200)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--optimizer", choices=["rmsprop", "adam"], default="rmsprop",
+                    help="every net's optimiser; adam: the reference's Adam settings (run.ADAM).  With adam or --grad-clip the device "
+                         "trainers are built with optimizers='agents'")
+    ap.add_argument("--grad-clip", type=float, default=0.0, help="clip_grad_norm_ bound of every net's optimiser step (0: off)")
     ap.add_argument("--engine-seed", type=int, default=34, help="the engine's RNG seed (shared; games differ by their global ids)")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--trainer", choices=["torch", "device", "device-fused", "device-epoch"], default="torch",
@@ -62,7 +67,7 @@ def build_population(a):
     agents = []
     for s in a.seeds:
         torch.manual_seed(s)
-        agent, state_dim = build_agent(a.game, a.hidden, a.n_rollouts, a.device, a.lr)
+        agent, state_dim = build_agent(a.game, a.hidden, a.n_rollouts, a.device, a.lr, a.optimizer, a.grad_clip)
         agents.append(agent)
     m = agents[0].mcts
     sp = run.PopulationSelfPlay([ag.nn for ag in agents], game=a.game, games_per_net=a.games_per_seed, n_rollouts=a.n_rollouts,
@@ -83,7 +88,8 @@ def train(a, log=print, on_rows=None):
     trainer = None
     if a.trainer != "torch":
         from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
-        trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size), losses="torch" if a.trainer == "device" else "device")
+        trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size), losses="torch" if a.trainer == "device" else "device",
+                                    optimizers="agents" if (a.optimizer != "rmsprop" or a.grad_clip) else "rmsprop")
     t0 = time.time()
     history = []
     for it in range(a.iters):

@@ -1,7 +1,7 @@
 /* azgym_train.h -- population training: one minibatch optimiser step of K nets of one shape in two launches, or three with the losses on the device too, and a
  * whole epoch of such steps in one call (an extension of azgym.h; same ABI version).
  *
- * A trainer owns scratch only.  The nets' parameters, the RMSprop state and every batch tensor are the caller's device arrays on
+ * A trainer owns scratch only.  The nets' parameters, the optimiser state and every batch tensor are the caller's device arrays on
  * the trainer's GPU, float32:
  *   params     [n_nets][P]   net k's parameters in azg_set_weights blob order (= state_dict order), P = azg_trainer_param_count.
  *                            This array is the master copy: azg_set_population_weights_device reads it as it stands.
@@ -9,7 +9,7 @@
  *   obs        [n_nets][n_rows][in_dim]      net k's own minibatch
  *   raw        [n_nets][n_rows][1 + n_dist]  value head, then the untransformed distribution head (azg_mlp_eval's `raw`)
  *   d_raw      [n_nets][n_rows][1 + n_dist]  d(loss of net k) / d raw
- *   grads      [n_nets][P]   (optional) the parameter gradients, before weight decay
+ *   grads      [n_nets][P]   (optional) the parameter gradients, before clipping and weight decay
  *   actions    [n_nets][n_rows][n_actions]   the searched actions of every row (indices for a discrete head), n_actions <= 16
  *   counts     [n_nets][n_rows][n_actions]   their visit counts
  *   values     [n_nets][n_rows]              the value targets
@@ -20,6 +20,10 @@
  * the device as well (azg_trainer_loss's kernel between the two) and synchronises once.  azg_trainer_epoch takes a whole epoch of
  * such steps: it gathers every minibatch from the caller's replay rows where they lie (the self-play ring included) and
  * synchronises once per epoch, whatever the number of minibatches.
+ *
+ * The optimiser is torch.optim.RMSprop applied in the backward kernel's tile epilogues (azg_rmsprop: the default, no gradient
+ * clipping), or, through the *_opt entry points (azg_optim), RMSprop or torch.optim.Adam with an optional per-net clip_grad_norm_:
+ * the backward launch then writes the gradients first and runs norm, clip and update as a phase after the last layer.
  *
  * Supported nets: Linear + activation trunks of 1..3 hidden layers, widths multiples of 16 up to 256, in_dim <= 8, n_dist <= 16,
  * every AZG_ACT_* activation; no LayerNorm.  Anything else: AZG_E_UNSUPPORTED from azg_trainer_create.
@@ -69,6 +73,44 @@ int azg_trainer_forward(azg_trainer* t, const float* params, const float* obs, i
  * AZG_E_UNSUPPORTED.  On an error nothing is written. */
 int azg_trainer_backward_step(azg_trainer* t, float* params, const float* d_raw, int32_t n_rows, const azg_rmsprop* opt,
                               float* square_avg, float* grads);
+
+/* ---- Adam, and gradient clipping: the optimiser as a phase of its own after the backward pass ---- */
+
+enum { AZG_OPT_RMSPROP = 0, AZG_OPT_ADAM = 1 };
+
+/* The optimiser of the *_opt entry points, with its state: the caller's device arrays [n_nets][P] float32, updated in place.
+ *   AZG_OPT_RMSPROP  torch.optim.RMSprop(lr, alpha, eps, weight_decay), momentum 0, not centered; state0 = square_avg
+ *   AZG_OPT_ADAM     torch.optim.Adam(lr, (beta1, beta2), eps, weight_decay), single-tensor form, no amsgrad:
+ *                    g += weight_decay * p;  exp_avg += (g - exp_avg) * (1 - beta1);  exp_avg_sq = beta2 * exp_avg_sq + (1 - beta2) g g;
+ *                    p -= lr / (1 - beta1^t) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^t) + eps),  t = step + 1;
+ *                    state0 = exp_avg_sq, state1 = exp_avg.  `step` = the Adam steps taken before this call (the caller counts).
+ * grad_clip != 0: torch.nn.utils.clip_grad_norm_(net k's parameters, grad_clip) between the backward pass and the step, per net:
+ * total_norm = the L2 norm of all P gradients (float64 sum in a fixed order, rounded to float32 once), every gradient times
+ * min(grad_clip / (total_norm + 1e-6), 1).  grad_norms (may be NULL): [n_nets] float32 device array that receives every net's
+ * total_norm, before clipping.
+ * With AZG_OPT_RMSPROP, grad_clip == 0 and no grad_norms a call runs the fused kernel of azg_trainer_backward_step and gives its
+ * bits.  Otherwise the backward launch takes its deferred form: the same GEMMs in the same order write the gradients to `grads`
+ * (or to the trainer's own [n_nets][P] array) and no parameter; then, in the same launch, norm, clip and update.  The gradients are
+ * bit for bit the fused form's; RMSprop's arithmetic is the fused form's, Adam's is float64 per element, rounded once. */
+typedef struct azg_optim {
+    int32_t struct_size;
+    int32_t kind;          /* AZG_OPT_* */
+    double lr, eps, weight_decay;
+    double alpha;          /* AZG_OPT_RMSPROP */
+    double beta1, beta2;   /* AZG_OPT_ADAM */
+    double grad_clip;      /* 0 = off */
+    float* state0;
+    float* state1;         /* AZG_OPT_ADAM only (else ignored) */
+    float* grad_norms;     /* optional */
+    int32_t step;          /* AZG_OPT_ADAM */
+} azg_optim;
+
+/* azg_trainer_backward_step with an azg_optim in place of (azg_rmsprop, square_avg).  grads (may be NULL) receives the gradients
+ * before clipping and weight decay.  NULL params / d_raw / opt / state0, NULL state1 with Adam, a struct_size mismatch, lr < 0,
+ * eps < 0, a beta outside [0, 1) (Adam), grad_clip < 0, step < 0, n_rows outside 1..max_batch:
+ * AZG_E_INVALID; an unknown kind: AZG_E_UNSUPPORTED; no azg_trainer_forward of the same n_rows before it: AZG_E_STATE.  On an error
+ * nothing is written. */
+int azg_trainer_backward_step_opt(azg_trainer* t, float* params, const float* d_raw, int32_t n_rows, const azg_optim* opt, float* grads);
 
 /* ---- the losses on the device (agent/population_trainer.py: population_terms / population_loss, restated as one kernel) ---- */
 
@@ -128,6 +170,11 @@ int azg_trainer_step(azg_trainer* t, float* params, const float* obs, const floa
                      int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
                      const azg_rmsprop* opt, float* square_avg, float* grads, float* raw_out, float* losses);
 
+/* azg_trainer_step with an azg_optim: every check of azg_trainer_step and azg_trainer_backward_step_opt before the first launch. */
+int azg_trainer_step_opt(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
+                         int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
+                         const azg_optim* opt, float* grads, float* raw_out, float* losses);
+
 /* Copies the d_raw [n_nets][n_rows][1 + n_dist] of the last azg_trainer_step to the caller's device array (AZG_E_STATE if there
  * was none of that n_rows). */
 int azg_trainer_read_d_raw(azg_trainer* t, int32_t n_rows, float* d_raw);
@@ -168,6 +215,13 @@ typedef struct azg_epoch_rows {
 int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
                       int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_rmsprop* opt,
                       float* square_avg, double* loss_sums, int32_t* n_minibatches);
+
+/* azg_trainer_epoch with an azg_optim: minibatch m steps with opt->step + m (and alpha_state->step + m); the caller adds
+ * *n_minibatches to both counts.  grad_norms, if given, ends up holding the last minibatch's norms.  params, the optimiser state and
+ * the alpha state end bit for bit where the same minibatches passed one by one to azg_trainer_step_opt leave them. */
+int azg_trainer_epoch_opt(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
+                          int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_optim* opt,
+                          double* loss_sums, int32_t* n_minibatches);
 
 #ifdef __cplusplus
 }

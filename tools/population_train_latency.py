@@ -14,7 +14,13 @@ call on a [K, n, row] array), train_epoch_ring (the same call on the self-play r
 losses="device" (one native call, one synchronisation and one host copy per minibatch, the minibatches gathered by torch), all three
 in one process on the same rows -- a PopulationSelfPlay's ring of K nets x 16 games -- CartPole 2x128 ReLU and Pendulum 3x128 ELU
 with a mixture of 2:
-    python tools/population_train_latency.py --epoch [--ks 1,8,64,256] [--rows 512] [--batch 128] [--out profiles/population_train_latency_epoch.txt]"""
+    python tools/population_train_latency.py --epoch [--ks 1,8,64,256] [--rows 512] [--batch 128] [--out profiles/population_train_latency_epoch.txt]
+
+--optimizer adam and / or --grad-clip X measure PopulationTrainer(optimizers="agents", losses="device").update (the backward launch in
+its deferred form: gradients first, then norm, clip and update) against the loop of agent.update calls of the same agents and against
+the fused RMSprop step (default agents, losses="device") in the same process, CartPole 2x128 ReLU and Pendulum 3x128 ELU with a
+mixture of 2:
+    python tools/population_train_latency.py --optimizer adam --grad-clip 1.0    (writes profiles/population_train_latency_adam.txt)"""
 import argparse
 import os
 import subprocess
@@ -97,6 +103,52 @@ def measure(name, K, B, reps, warmup):
     t_fused = _median_ms(lambda: fused.update(stacked), reps, warmup)
     fused.close()
     return t_loop, t_pop, t_fwd, t_loss, t_bwd, t_fused
+
+
+def measure_optim(name, K, B, reps, warmup, optimizer, grad_clip):
+    """(loop of agent.update, optimizers="agents" step, fused RMSprop step) median ms, losses on the device in both trainers."""
+    kind, S, A = CONFIGS[name]
+    over = dict(device="cuda", policy=dict(num_components=2)) if kind == "continuous" else dict(device="cuda")
+    base = run._merge(run.CONTINUOUS_DEFAULTS if kind == "continuous" else run.DISCRETE_DEFAULTS, over)
+    cfg = dict(base, agent=dict(base["agent"], grad_clip=grad_clip))
+    if optimizer == "adam":
+        cfg["optimizer"] = dict(run.ADAM)
+    env = make_game(cfg["game"])
+    stacked = _batches(kind, K, B, S, A)
+    per_net = [tuple(t[k] for t in stacked) for k in range(K)]
+
+    def agents_of(c):
+        torch.manual_seed(0)
+        return [run.make_agent(kind, c, env, tree_id_base=k) for k in range(K)]
+
+    agents = agents_of(cfg)
+
+    def loop():
+        for a, b in zip(agents, per_net):
+            a.update(b)
+
+    t_loop = _median_ms(loop, reps, warmup)
+    tr = PT.PopulationTrainer(agents_of(cfg), max_batch=max(512, 2 * B), losses="device", optimizers="agents")
+    t_opt = _median_ms(lambda: tr.update(stacked), reps, warmup)
+    tr.close()
+    fused = PT.PopulationTrainer(agents_of(base), max_batch=max(512, 2 * B), losses="device")
+    t_fused = _median_ms(lambda: fused.update(stacked), reps, warmup)
+    fused.close()
+    return t_loop, t_opt, t_fused
+
+
+def main_optim(a):
+    lines = ["# tools/population_train_latency.py --optimizer %s --grad-clip %g: one minibatch optimiser step of K nets, batch %d, one MI355X; "
+             "median wall ms of %d repetitions after %d warm-up, all three in one process" % (a.optimizer, a.grad_clip, a.batch, a.reps, a.warmup)]
+    for name in a.configs.split(","):
+        lines.append(f"# {name}: loop of K agent.update ({a.optimizer}, grad_clip {a.grad_clip:g}) | PopulationTrainer(optimizers='agents', "
+                     "losses='device').update | ratio | fused RMSprop step (losses='device') | deferred / fused")
+        for K in [int(k) for k in a.ks.split(",")]:
+            t_loop, t_opt, t_fused = measure_optim(name, K, a.batch, a.reps, a.warmup, a.optimizer, a.grad_clip)
+            lines.append(f"  {name} K={K:4d} loop {t_loop:9.3f} ms  optimizers='agents' {t_opt:8.3f} ms  {t_loop / t_opt:7.2f}x  "
+                         f"fused RMSprop {t_fused:8.3f} ms  {t_opt / t_fused:6.3f}x")
+            print(lines[-1], flush=True)
+    return lines
 
 
 def measure_epoch(name, K, n_rows, B, reps, warmup, T=16):
@@ -183,8 +235,15 @@ def main():
     ap.add_argument("--loss-errors", default=None, help="output of pytest -s tests/test_population_device_loss.py: the largest errors go into the header")
     ap.add_argument("--epoch", action="store_true", help="measure a whole epoch: train_epoch, train_epoch_ring and train_on_rows")
     ap.add_argument("--rows", type=int, default=512, help="--epoch: rows per net")
+    ap.add_argument("--optimizer", choices=["rmsprop", "adam"], default="rmsprop", help="adam (the reference's settings): measure optimizers='agents'")
+    ap.add_argument("--grad-clip", type=float, default=0.0, help="a bound > 0: measure optimizers='agents' with gradient clipping")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.optimizer != "rmsprop" or a.grad_clip:
+        out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "population_train_latency_adam.txt")
+        with open(out, "w") as f:
+            f.write("\n".join(main_optim(a)) + "\n")
+        return
     if a.epoch:
         text = "\n".join(main_epoch(a)) + "\n"
         if a.out:
