@@ -21,6 +21,12 @@
 #ifndef AZG_DEFER
 #define AZG_DEFER 1   // eight-wave / 16-tree continuous kernels: the new node's bookkeeping behind the barrier, first layer by the non-walking waves (0: A/B builds)
 #endif
+#ifndef AZG_EARLY_PATH
+#define AZG_EARLY_PATH 1      // with AZG_HELPER_POLICY: the backup's path rewards / returns are requested in front of the network phase (0: A/B builds)
+#endif
+#ifndef AZG_HELPER_POLICY
+#define AZG_HELPER_POLICY 1   // the same kernels: a leaf's mu / sigma by a non-walking wave during the tree phases, the walking waves take V only (0: A/B builds)
+#endif
 
 // Dynamic LDS layout of a workgroup, shared by the kernel and the host's launch planning
 struct LdsLayout {
@@ -75,6 +81,19 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
     // SPLIT; a counter in LDS instead of the barrier behind that layer, so that nobody waits for the walking waves there).
     constexpr bool DEFER = AZG_DEFER && NW == 8 && NG == 1 && ENV == AZG_ENV_PENDULUM_V1 && TLDS != TS_GLOBAL && NREG > 0 && !GMM && HP <= 256;
     __shared__ int s_l0;                // (DEFER) first-layer tiles published so far, all network phases of the search
+    // HPOL: from the first trace on, phase A on the walking waves takes only the leaf's value and goes straight into the backup; the
+    // leaf's policy is summed, clamped, exponentiated and stored by wave NW/2 right behind the network phase (tree_phases.cuh:
+    // PolicyMailbox, policy_finish_helper), in issue slots its SIMD does not use during the tree phases.
+    constexpr bool HPOL = AZG_HELPER_POLICY && DEFER;
+    // EARLYP: the finish-leaf work that HPOL removes used to cover the latency of the backup's first loads (the path slots' cold[].r and
+    // edge_W[], beyond L2 at 4096 trees); without it the backup waits for those loads instead and the search gains nothing
+    // (profiles/helper_policy_finish_ab.txt: AZG_EARLY_PATH=0 against 1).  They are therefore requested before the network phase, right
+    // behind tree_phase_b2, which wrote the last of them; nothing writes them in between.  Two doubles across the network phase: the one
+    // exception to LEAN's rule below, inside the kernels' register budget (no spilled VGPR, no scratch).
+    constexpr bool EARLYP = AZG_EARLY_PATH && HPOL;
+    // (HPOL only.  No other kernel form refers to it and the compiler drops it there: their LDS sizes, register counts and device assembly
+    // were compared with the build before this array existed and are the same)
+    __shared__ PolicyMailbox s_mb;
     extern __shared__ double s_dyn[];   // sqrt_tab [tab_n], pw_need [n_sims+2] u16, activation buffers, (TLDS) the trees' hot records
 
     const int tid = threadIdx.x;
@@ -92,7 +111,7 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
     // instructions is carried across the network phase there.  The per-tree context (indices, global base pointers, LDS bases)
     // is rebuilt from the thread index at the top of every tree phase, the loop-carried tree state crosses the network phase
     // packed two fields to a register, and the path's rewards / returns are fetched after the network phase instead of during
-    // the descent.  With one wave per SIMD (NW = 4: 512 registers) everything stays in registers (measured faster there).
+    // the descent (EARLYP kernels: in front of it, see above).  With one wave per SIMD (NW = 4: 512 registers) everything stays in registers (measured faster there).
     constexpr bool LEAN = (NW == 8);   // (also for the 16-tree shape: carrying everything instead costs 7 spilled registers and 0.7 % time)
     const LdsLayout L = lds_layout(P.tab_n, P.n_sims, HP, NG, act_buffers(NREG), P.R, CONT, TLDS, P.lds_state, NT);
     double* s_sqrt = s_dyn;
@@ -103,6 +122,7 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
     if (CONT) for (int i = tid; i < P.n_sims + 2; i += 64 * NW) s_pw[i] = (unsigned short)(P.pw_need[i] < 65535 ? P.pw_need[i] : 65535);
     if (tid < 16) s_bhead[tid] = P.bhead[wofs + tid];
     if (tid == 0) { s_done = 0; s_l0 = 0; }
+    if constexpr (HPOL) { if (tid < 16) s_mb.flag[tid] = 0; }   // (step numbers start at 1)
 
     // register-resident weights
     typedef WRegs<HP, NREG, NW, DEFER> WR;
@@ -209,12 +229,18 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
         if constexpr (DEFER) {
             // the rest of the node phase B has just created (the other waves are in the first layer meanwhile)
             STAMP2(t_b2a, 12, -1);
-            if (cx.live) tree_phase_b2<ENV, TLDS, SPEC>(P, st, cx.ts, cx.cold, cx.edge_W, cx.action, bdef, cx.sub, cx.gtree, s_pw);
+            if (cx.live) tree_phase_b2<ENV, TLDS, SPEC, false, unsigned short, HPOL>(P, st, cx.ts, cx.cold, cx.edge_W, cx.action, bdef, cx.sub, cx.gtree, s_pw);
             bdef.pending = false;
             STAMP2(t_b2b, 12, -1);
 #ifdef AZG_STAMP_ONLY
             STAMP_ADD(12, t_b2a, t_b2b);   // (single-pair builds only: slot 12 counts descent levels in the full set)
 #endif
+        }
+        // (EARLYP) the path slot's reward and return, requested here: two registers each across the network phase, within the kernel's budget
+        [[maybe_unused]] double pre_pr = 0.0, pre_pW = 0.0;
+        if constexpr (EARLYP) {
+            tree_fence();   // (tree_phase_b2's stores of the new leaf's r and W come first)
+            if (cx.live && sim >= 0 && st.my_depth >= 1) { pre_pr = cx.cold[st.pid].r; pre_pW = cx.edge_W[st.pid]; }
         }
         unsigned pk0 = 0, pk1 = 0, pk2 = 0, pk3 = 0;
         int tid_o = tid;
@@ -232,6 +258,11 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
         mlp_forward<HP, NREG, NW, NG, PSTR, WR, NT, IN8, DEFER>(P, wr, s_obsT, s_actA, s_actB, s_parts, s_ln, wave, lane, &s_l0, sim + 2, wofs);
 #endif
         STAMP2(t_c, 1, 2);
+        if constexpr (HPOL) {
+            // the policy of the leaves just evaluated: one lane per tree on the first non-walking wave (it waits for nobody)
+            if (wave == NW / 2 && lane < 16 && sim >= 0)
+                policy_finish_helper<NCH, PSTR>(P, P.cold + (size_t)tree0 * P.R, lane, n_live, &s_mb, sim + 2, s_parts, s_bhead);
+        }
         if constexpr (LEAN) {
             // opaque to the optimiser: whatever is derived from these is computed HERE, not kept alive across the network phase
             asm volatile("" : "+v"(pk0), "+v"(pk1), "+v"(pk2), "+v"(pk3), "+v"(tid_o));
@@ -242,21 +273,22 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
             cx = make_ctx(tid_o);
             // the path's rewards and cumulative returns (the descent did not fetch them: tree_phase_b<..., FETCH = false>)
             st.pr = 0.0; st.pW = 0.0;
-            if (cx.live && (MULTI ? my_sim : sim) >= 0 && st.my_depth >= 1) {
+            if constexpr (EARLYP) { st.pr = pre_pr; st.pW = pre_pW; }
+            else if (cx.live && (MULTI ? my_sim : sim) >= 0 && st.my_depth >= 1) {
                 st.pr = CONT ? cx.cold[st.pid].r : discrete_env_reward(Spec<SPEC, ENV>::env(P));
                 st.pW = cx.edge_W[st.pid];
             }
         }
         if constexpr (!MULTI) {
             // ================= tree phase A: finish the evaluated leaf, back up =================
-            if (cx.live) tree_phase_a<ENV, TLDS, GMM, NCH, PSTR, !CONT, SPEC>(P, st, cx.ts, cx.cold, cx.edge_W, cx.action, cx.tb, sim, cx.sub, cx.tl % NT, cx.gtree, cx.my_parts, s_bhead, s_sqrt STAMP_ARG, s_pw);
+            if (cx.live) tree_phase_a<ENV, TLDS, GMM, NCH, PSTR, !CONT, SPEC, unsigned short, HPOL>(P, st, cx.ts, cx.cold, cx.edge_W, cx.action, cx.tb, sim, cx.sub, cx.tl % NT, cx.gtree, cx.my_parts, s_bhead, s_sqrt STAMP_ARG, s_pw);
             if (sim == P.n_sims - 1) break;
             if constexpr (DEFER) { if (sim < 0 && cx.live) eps_prepare(P, st, cx.gtree, cx.sub); }   // (no tree_phase_b2 in front of the first trace)
             tree_fence();
             STAMP2(t_d, 2, 3);
             // ================= tree phase B: next trace: select down, step the env, expand =================
             st.need_eval = false;
-            if (cx.live) tree_phase_b<ENV, TLDS, GMM, TPW, unsigned short, !LEAN, !CONT, SPEC, IN8, DEFER>(P, st, cx.ts, cx.cold, cx.edge_W, cx.action, cx.tb, cx.sub, cx.tl, cx.gtree, s_sqrt, s_pw, s_obsT STAMP_ARG, &bdef);
+            if (cx.live) tree_phase_b<ENV, TLDS, GMM, TPW, unsigned short, !LEAN, !CONT, SPEC, IN8, DEFER, HPOL>(P, st, cx.ts, cx.cold, cx.edge_W, cx.action, cx.tb, cx.sub, cx.tl, cx.gtree, s_sqrt, s_pw, s_obsT STAMP_ARG, &bdef, &s_mb, sim);
             tree_fence();
             STAMP2(t_e, 3, -1);
             STAMP_ADD(2, t_c, t_d);   // finish leaf + backup

@@ -240,7 +240,9 @@ __device__ __forceinline__ void tree_init_root(const KParams& P, TreeState& st, 
 // for the tree's group of 16 (PSTR entries per chunk), tl = the tree's column in that group.
 // RESUME (discrete mode, cached selections): also work out where the next descent leaves this trace's path (st.resume).
 // s_pw: continuous mode, the widening thresholds (the backup keeps the path nodes' widens-at-next-visit bits: tree.cuh set_wnext).
-template <int ENV, int TLDS, bool GMM, int NCH, int PSTR = 64, bool RESUME = false, int SPEC = 0, typename PW = int>
+// HPOL (search_kernel.cuh: the eight-wave / 16-tree continuous kernels): from the first trace on (sim >= 0) only the leaf's value is taken
+// here -- the backup waits for nothing else -- and the leaf's policy (mu, sigma) is a non-walking wave's work (policy_finish_helper).
+template <int ENV, int TLDS, bool GMM, int NCH, int PSTR = 64, bool RESUME = false, int SPEC = 0, typename PW = int, bool HPOL = false>
 __device__ __forceinline__ void tree_phase_a(const KParams& P, TreeState& st, const TreeStore<TLDS>& ts, Cold* cold, double* edge_W,
                                              float* action, size_t tb, int sim, int sub, int tl, unsigned gtree, const f32x4* parts,
                                              const float* bhead, const double* s_sqrt STAMP_PARAM_OPT, const PW* s_pw = nullptr) {
@@ -254,7 +256,9 @@ __device__ __forceinline__ void tree_phase_a(const KParams& P, TreeState& st, co
         f32x4 out4 = {0.0f, 0.0f, 0.0f, 0.0f};
         if constexpr (!CONT) { out4 = head_output4<NCH, PSTR>(parts, bhead, tl); V = out4.x; }
         else V = head_output<NCH, PSTR>(parts, bhead, tl, 0);
-        if (CONT) {
+        if (CONT && HPOL && sim >= 0) {
+            if (sub == 0) cold[st.leaf].V = V;
+        } else if (CONT) {
             float mu, sg;
             float gd[15];
             if constexpr (GMM) {
@@ -408,6 +412,41 @@ __device__ __forceinline__ void eps_prepare(const KParams& P, TreeState& st, uns
     st.eps_next = __shfl(st.eps_c, st.nrec - st.kbase, 16);
 }
 
+// HPOL: the policy half of leaf finishing, done by a non-walking wave of the eight-wave / 16-tree continuous kernels while the walking
+// waves back up and descend (its SIMD's walking wave is stalled on LDS and memory round trips for most of that time, and the non-walking
+// waves would otherwise sit at the step's barrier).  One lane per tree of the group.  The hand-over, all in LDS, per workgroup:
+//   pleaf[s & 1][t]  the leaf of tree t that network phase s evaluates (-1: none), written by the walking waves at the end of phase B,
+//                    visible through the barrier in front of the network phase; two buffers, because the walking waves write step
+//                    s + 1's entry while the helper may still be reading step s's;
+//   pol[t], flag[t]  the mailbox: mu and sigma of that leaf, then flag = s with workgroup-scope release.  A trace that widens at the leaf
+//                    of its own step (a fresh node widens at its first visit) takes them from here after an acquire-load of the flag;
+//                    every later reader finds them in the cold record, behind at least one barrier.
+// No deadlock: between the two barriers of a step the helper waits for nobody and publishes every tree's flag, evaluated leaf or not,
+// before it arrives at the next barrier; a walking wave waits only for that flag.  One workgroup is one CU: workgroup scope suffices.
+struct PolicyMailbox {
+    int pleaf[2][16];
+    float pol[16][2];
+    int flag[16];
+};
+
+// the helper's side: lane tl < 16 finishes tree tl's leaf.  `cold_wg`: the cold records of the workgroup's first tree; `parts` / `bhead`:
+// the group's head partials and the net's head bias, summed exactly as tree_phase_a sums them (head_output: bias first, chunks in order).
+template <int NCH, int PSTR>
+__device__ __forceinline__ void policy_finish_helper(const KParams& P, Cold* cold_wg, int tl, int n_live, PolicyMailbox* mb, int step,
+                                                     const f32x4* parts, const float* bhead) {
+    const int leaf = mb->pleaf[step & 1][tl];
+    if (tl < n_live && leaf >= 0) {
+        const float mu = head_output<NCH, PSTR>(parts, bhead, tl, 1);
+        float ls = head_output<NCH, PSTR>(parts, bhead, tl, 2);
+        ls = ls < P.ls_min ? P.ls_min : (ls > P.ls_max ? P.ls_max : ls);
+        const float sg = azg_expf(ls);
+        Cold* c = cold_wg + (size_t)tl * P.R + leaf;
+        c->mu = mu; c->sg = sg;
+        mb->pol[tl][0] = mu; mb->pol[tl][1] = sg;
+    }
+    __hip_atomic_store(&mb->flag[tl], step, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 struct BDeferred {
     bool pending, widen;
     int p, chosen;          // parent node, the new record
@@ -416,7 +455,9 @@ struct BDeferred {
 
 // the deferred half of phase B (Pendulum family: the nodes never end an episode).  The parent's records are read again here (nothing
 // has touched them since the descent): carrying them across the barrier would cost the lean walkers registers they do not have.
-template <int ENV, int TLDS, int SPEC, bool FETCH = false, typename PW = int>
+// HPOL: no zeros for V, mu and sigma -- no node of this family is terminal, so the same step's leaf finish (tree_phase_a: V,
+// policy_finish_helper: mu, sigma) overwrites all three before anything reads them.
+template <int ENV, int TLDS, int SPEC, bool FETCH = false, typename PW = int, bool HPOL = false>
 __device__ __forceinline__ void tree_phase_b2(const KParams& P, TreeState& st, const TreeStore<TLDS>& ts, Cold* cold, double* edge_W, float* action,
                                               const BDeferred& d, int sub, unsigned gtree, const PW* s_pw) {
     typedef typename TreeStore<TLDS>::Rec Rec;
@@ -453,7 +494,8 @@ __device__ __forceinline__ void tree_phase_b2(const KParams& P, TreeState& st, c
         float zero = 0.0f;
         asm volatile("" : "+v"(zero));
         Cold* c = cold + d.chosen;
-        c->s[3] = 0.0; c->r = r; c->V = zero; c->mu = zero; c->sg = zero; c->pad = zero;
+        c->s[3] = 0.0; c->r = r; c->pad = zero;
+        if constexpr (!HPOL) { c->V = zero; c->mu = zero; c->sg = zero; }
     }
     eps_prepare(P, st, gtree, sub);
 }
@@ -465,11 +507,14 @@ __device__ __forceinline__ void tree_phase_b2(const KParams& P, TreeState& st, c
 // tree_phase_a<..., RESUME = true>) instead of at the root; the path slots above that depth are still in the lanes.
 // DEFER: the new node's records, reward and cold record are left to tree_phase_b2 (`def`), which also hands the leaf's path slot its
 // reward (st.pr) when the path's rewards travel in the lanes (FETCH).
-template <int ENV, int TLDS, bool GMM, int TPW = 16, typename PW = int, bool FETCH = true, bool RESUME = false, int SPEC = 0, bool OBS8 = false, bool DEFER = false>
+// HPOL (`mb`, `sim`): the policy of the leaf evaluated in this step comes from the mailbox (PolicyMailbox), and the new leaf's id goes there.
+template <int ENV, int TLDS, bool GMM, int TPW = 16, typename PW = int, bool FETCH = true, bool RESUME = false, int SPEC = 0, bool OBS8 = false, bool DEFER = false, bool HPOL = false>
 __device__ __forceinline__ void tree_phase_b(const KParams& P, TreeState& st, const TreeStore<TLDS>& ts, Cold* cold, double* edge_W,
                                              float* action, size_t tb, int sub, int tl, unsigned gtree, const double* s_sqrt,
-                                             const PW* s_pw, float* obsT STAMP_PARAM, BDeferred* def = nullptr) {
+                                             const PW* s_pw, float* obsT STAMP_PARAM, BDeferred* def = nullptr, PolicyMailbox* mb = nullptr, int sim = -1) {
     static_assert(!DEFER || (ENV == AZG_ENV_PENDULUM_V1 && !GMM), "deferred expansion: Pendulum family, squashed-Normal head");
+    static_assert(!HPOL || (DEFER && TPW == 16), "policy mailbox: the eight-wave / 16-tree continuous kernels");
+    const int mstep = sim >= 0 ? sim + 2 : 0;   // (HPOL) the helper's stamp for this step's leaf; 0: the root's evaluation, finished by this wave itself
     constexpr bool CONT = EnvFamily<ENV>::CONT;
     constexpr int S = CONT ? 2 : 4;
     typedef typename TreeStore<TLDS>::Rec Rec;
@@ -500,6 +545,14 @@ __device__ __forceinline__ void tree_phase_b(const KParams& P, TreeState& st, co
     if constexpr (!CONT && TLDS != TS_GLOBAL) from_cold = (ts.state == nullptr);   // (LDS-resident env states: read after the descent)
     if (from_cold) cp = cold[p];   // (p: the root, or the node a resumed descent starts from)
     else { cp.s[0] = cp.s[1] = cp.s[2] = cp.s[3] = 0.0; }
+    // (HPOL) a first look at the mailbox, together with the root's record: by now the helper has long published (it needs a fraction of
+    // the backup's time), so the widening below normally finds the values in registers
+    bool mb_ready = false;
+    float mb_mu = 0.0f, mb_sg = 0.0f;
+    if constexpr (HPOL) {
+        mb_ready = __hip_atomic_load(&mb->flag[tl], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == mstep;
+        mb_mu = mb->pol[tl][0]; mb_sg = mb->pol[tl][1];
+    }
     if (!resumed) { st.path_D = 0; st.my_depth = sub == 0 ? 0 : -1; st.pid = 0; }
     if (!keep_slot) { st.pr = 0.0; st.pW = 0.0; }
     int chosen = 0;
@@ -578,6 +631,16 @@ __device__ __forceinline__ void tree_phase_b(const KParams& P, TreeState& st, co
             chosen = st.nrec++;
             float eps = DEFER ? st.eps_next : __shfl(st.eps_c, chosen - st.kbase, 16);
             float wmu = cp.mu, wsg = cp.sg;
+            if constexpr (HPOL) {
+                // the node is this step's leaf: its cold record may not hold the policy yet (the only wait the hand-over adds)
+                if (mstep != 0 && p == st.leaf) {
+                    if (!mb_ready) {
+                        while (__hip_atomic_load(&mb->flag[tl], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != mstep) __builtin_amdgcn_s_sleep(1);
+                        mb_mu = mb->pol[tl][0]; mb_sg = mb->pol[tl][1];
+                    }
+                    wmu = mb_mu; wsg = mb_sg;
+                }
+            }
             if constexpr (GMM) {
                 float gd[15];
                 const float* g = P.gmm + (tb + p) * 3 * GMM_MAXC;
@@ -668,4 +731,5 @@ __device__ __forceinline__ void tree_phase_b(const KParams& P, TreeState& st, co
             obsT[sub * TPW + tl] = done ? 0.0f : v;
         }
     }
+    if constexpr (HPOL) { if (sub == 0) mb->pleaf[(sim + 3) & 1][tl] = st.need_eval ? st.leaf : -1; }   // (read by the helper in network phase sim + 3)
 }
