@@ -36,14 +36,14 @@ __global__ __launch_bounds__(256) void ls_tree_kernel(KParams P, LockStep L, int
     Cold* cold = P.cold + tb;
     double* edge_W = P.edge_W + tb;
     float* action = P.action + tb;
-    TreeStore<false> ts;
+    TreeStore<TS_GLOBAL> ts;
     ts.hot = P.hot + tb;
     ts.child = P.child + tb * P.Kp;
     ts.prior = P.prior + tb;
     float* obsT = L.obsT + (size_t)tg * 64;
     TreeState st;
     if (sim == -2) {
-        tree_init_root<ENV, false>(P, st, ts, cold, edge_W, action, tree, live, sub, tl, gtree, obsT);
+        tree_init_root<ENV, TS_GLOBAL>(P, st, ts, cold, edge_W, action, tree, live, sub, tl, gtree, obsT);
     } else {
         const LsTree t = L.tree[live ? tree : 0];
 #ifdef AZG_STAMPS
@@ -52,12 +52,12 @@ __global__ __launch_bounds__(256) void ls_tree_kernel(KParams P, LockStep L, int
         const LsLane ln = L.lane[(size_t)(live ? tree : 0) * 16 + sub];
         st.nrec = t.nrec; st.eps_draws = t.eps_draws; st.leaf = t.leaf; st.need_eval = live && t.need_eval; st.path_D = t.path_D;
         st.kbase = t.kbase; st.my_depth = ln.my_depth; st.pid = ln.pid; st.pr = ln.pr; st.pW = ln.pW; st.eps_c = ln.eps_c;
-        if (live) tree_phase_a<ENV, false, GMM, NCH>(P, st, ts, cold, edge_W, action, tb, sim, sub, tl, gtree,
+        if (live) tree_phase_a<ENV, TS_GLOBAL, GMM, NCH>(P, st, ts, cold, edge_W, action, tb, sim, sub, tl, gtree,
                                                      L.parts + (size_t)tg * NCH * 64, P.bhead, s_sqrt STAMP_ARG, s_pw);
         st.need_eval = false;
         if (sim < P.n_sims - 1) {
             __threadfence_block();
-            if (live) tree_phase_b<ENV, false, GMM>(P, st, ts, cold, edge_W, action, tb, sub, tl, gtree, s_sqrt, s_pw, obsT STAMP_ARG);
+            if (live) tree_phase_b<ENV, TS_GLOBAL, GMM>(P, st, ts, cold, edge_W, action, tb, sub, tl, gtree, s_sqrt, s_pw, obsT STAMP_ARG);
             else if (sub < 4) obsT[sub * 16 + tl] = 0.0f;
         } else if (live && sub == 0) {
             P.n_rec[tree] = st.nrec;

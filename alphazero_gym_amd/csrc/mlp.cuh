@@ -153,11 +153,8 @@ __device__ __forceinline__ void layer_norm_wg(const KParams& P, int layer, f32x4
 // the walking waves look at the counter when they get there.
 template <int HP, int NREG, int NW = 4, int NG = 1, int PSTR = 64, typename WR = WRegs<HP, NREG, NW>, int NT = 16, bool IN8 = false, bool SPLIT = false>
 __device__ __forceinline__ void mlp_forward(const KParams& P, const WR& wr, const float* obsT, f32x4* actA, f32x4* actB,
-                                            f32x4* parts, float* s_ln, int wave, int lane
-#ifdef AZG_STAMPS
-                                            , unsigned long long* st_acc
-#endif
-                                            , int* l0_flag = nullptr, int step = 0, size_t wofs = 0) {
+                                            f32x4* parts, float* s_ln, int wave, int lane STAMP_PARAM,
+                                            int* l0_flag = nullptr, int step = 0, size_t wofs = 0) {
     STAMP_M(m0, 4, -1);
     static_assert(!SPLIT || (NW == 8 && NG == 1 && NT == 16 && HP <= 256 && NREG > 0 && !IN8), "split first layer: the eight-wave / 16-tree shape");
     constexpr int NTW = HP / (16 * NW);    // output tiles per wave

@@ -34,10 +34,8 @@ __global__ __launch_bounds__(256, 1) void mlp_eval_kernel(KParams P, const float
     __syncthreads();
 #ifdef AZG_STAMPS
     unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    mlp_forward<HP, 0, 4, 1, 64, WRegs<HP, 0, 4>, 16, true>(P, wr, s_obsT, s_act, s_act + HP / 16 * 64, s_parts, s_ln, wave, lane, st_acc);
-#else
-    mlp_forward<HP, 0, 4, 1, 64, WRegs<HP, 0, 4>, 16, true>(P, wr, s_obsT, s_act, s_act + HP / 16 * 64, s_parts, s_ln, wave, lane);
 #endif
+    mlp_forward<HP, 0, 4, 1, 64, WRegs<HP, 0, 4>, 16, true>(P, wr, s_obsT, s_act, s_act + HP / 16 * 64, s_parts, s_ln, wave, lane STAMP_ARG);
     const int row = blockIdx.x * 16 + tid;
     if (tid >= 16 || row >= n) return;
     const int tl = tid;

@@ -139,11 +139,7 @@ __global__ __launch_bounds__(256, 1) void rollout_kernel(KParams P, Rollout ro) 
         __syncthreads();
         // (s_live and s_obsT are next written behind mlp_forward's closing barrier, which every wave passes after reading them)
         if (!s_live) break;
-#ifdef AZG_STAMPS
-        mlp_forward<HP, NREG, 4, 1, 64, WR, 16, true>(P, wr, s_obsT, s_act, s_act + HP / 16 * 64, s_parts, s_ln, wave, lane, st_acc, nullptr, 0, wofs);
-#else
-        mlp_forward<HP, NREG, 4, 1, 64, WR, 16, true>(P, wr, s_obsT, s_act, s_act + HP / 16 * 64, s_parts, s_ln, wave, lane, nullptr, 0, wofs);
-#endif
+        mlp_forward<HP, NREG, 4, 1, 64, WR, 16, true>(P, wr, s_obsT, s_act, s_act + HP / 16 * 64, s_parts, s_ln, wave, lane STAMP_ARG, nullptr, 0, wofs);
         if (!fin) {
             if (t == 0) v0 = head_output<NCH, 64>(s_parts, s_bhead, tid, 0);
             const float a = rollout_action<NCH>(P, ro, s_parts, s_bhead, tid, gid, (unsigned)t);

@@ -252,11 +252,7 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
             pk3 = (unsigned)st.ptop | ((unsigned)st.need_eval << 16) | ((unsigned)st.resume << 20);
             asm volatile("" : "+v"(pk0), "+v"(pk1), "+v"(pk2), "+v"(pk3));
         }
-#ifdef AZG_STAMPS
-        mlp_forward<HP, NREG, NW, NG, PSTR, WR, NT, IN8, DEFER>(P, wr, s_obsT, s_actA, s_actB, s_parts, s_ln, wave, lane, st_acc, &s_l0, sim + 2, wofs);
-#else
-        mlp_forward<HP, NREG, NW, NG, PSTR, WR, NT, IN8, DEFER>(P, wr, s_obsT, s_actA, s_actB, s_parts, s_ln, wave, lane, &s_l0, sim + 2, wofs);
-#endif
+        mlp_forward<HP, NREG, NW, NG, PSTR, WR, NT, IN8, DEFER>(P, wr, s_obsT, s_actA, s_actB, s_parts, s_ln, wave, lane STAMP_ARG, &s_l0, sim + 2, wofs);
         STAMP2(t_c, 1, 2);
         if constexpr (HPOL) {
             // the policy of the leaves just evaluated: one lane per tree on the first non-walking wave (it waits for nobody)
