@@ -113,13 +113,18 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "population_selfplay_begin", "policy_rollout",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
                     "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch",
-                    "trainer_backward_step_opt", "trainer_step_opt", "trainer_epoch_opt"]
+                    "trainer_backward_step_opt", "trainer_step_opt", "trainer_epoch_opt", "trainer_create_ex"]
 
 
 class AzgRmsprop(C.Structure):
     """include/azgym_train.h: azg_rmsprop"""
     _fields_ = [("struct_size", C.c_int32), ("centered", C.c_int32), ("lr", C.c_double), ("alpha", C.c_double), ("eps", C.c_double),
                 ("weight_decay", C.c_double), ("momentum", C.c_double), ("grad_clip", C.c_double)]
+
+
+class AzgTrainerOptions(C.Structure):
+    """include/azgym_train.h: azg_trainer_options"""
+    _fields_ = [("struct_size", C.c_int32), ("layernorm", C.c_int32)]
 
 
 OPT_RMSPROP, OPT_ADAM = 0, 1
@@ -242,6 +247,8 @@ def bind(lib, prefix):
                                           C.POINTER(AzgOptim), vp, vp, vp]
         f["trainer_epoch_opt"].argtypes = [vp, vp, C.POINTER(AzgEpochRows), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(AzgLossCfg),
                                            C.POINTER(AzgAlphaState), C.POINTER(AzgOptim), vp, C.POINTER(C.c_int32)]
+    if "trainer_create_ex" in f:
+        f["trainer_create_ex"].argtypes = [C.c_int32, C.POINTER(AzgMlpDesc), C.c_int32, C.c_int32, C.POINTER(AzgTrainerOptions), C.POINTER(vp)]
     return f
 
 
@@ -729,15 +736,22 @@ def epoch_rows(rows, state_dim, n_actions, rows_per_net, *, ring_trees=None, gam
 class Trainer:
     """One ``azg_trainer*`` (include/azgym_train.h): forward and backward + RMSprop step of n_nets nets of shape ``desc`` in two
     launches.  Every array argument is a device address (int) of float32 memory on the trainer's GPU, complete when the call is
-    made; outputs are complete when it returns."""
+    made; outputs are complete when it returns.  ``layernorm=True`` creates it with azg_trainer_create_ex, which also takes
+    descriptors of LayerNorm trunks (per trunk layer weight, bias, ln.weight, ln.bias in ``params``)."""
 
-    def __init__(self, fns, desc, n_nets, max_batch, device_id=0):
+    def __init__(self, fns, desc, n_nets, max_batch, device_id=0, layernorm=False):
         if "trainer_create" not in fns:
             raise NotImplementedError("this engine library has no azg_trainer_* entry points")
+        if layernorm and "trainer_create_ex" not in fns:
+            raise NotImplementedError("this engine library has no azg_trainer_create_ex")
         self._f = fns
         self._h = C.c_void_p()
-        rc = fns["trainer_create"](int(device_id), C.byref(desc) if desc is not None else None, int(n_nets), int(max_batch),
-                                   C.byref(self._h))
+        dref = C.byref(desc) if desc is not None else None
+        if layernorm:
+            opts = AzgTrainerOptions(C.sizeof(AzgTrainerOptions), 1)
+            rc = fns["trainer_create_ex"](int(device_id), dref, int(n_nets), int(max_batch), C.byref(opts), C.byref(self._h))
+        else:
+            rc = fns["trainer_create"](int(device_id), dref, int(n_nets), int(max_batch), C.byref(self._h))
         if rc != 0:
             raise EngineError(rc, (fns["trainer_last_error"](None) or b"").decode())
         self.n_nets, self.max_batch, self.device_id = int(n_nets), int(max_batch), int(device_id)

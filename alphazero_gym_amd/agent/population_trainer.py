@@ -228,9 +228,9 @@ def _need_device_losses(losses: str, who: str) -> None:
 
 class PopulationTrainer:
     """The optimiser step of K agents of one shape, all at once.  Raises ``ValueError`` naming the reason when the agents cannot be
-    trained here (the caller then keeps the per-agent ``agent.update`` loop): different network shapes, LayerNorm, gradient
-    clipping or an optimiser other than plain RMSprop (unless ``optimizers="agents"``), different losses or hyper-parameters,
-    parameters not on a GPU.
+    trained here (the caller then keeps the per-agent ``agent.update`` loop): different network shapes, LayerNorm (unless
+    ``layernorm=True``), gradient clipping or an optimiser other than plain RMSprop (unless ``optimizers="agents"``), different
+    losses or hyper-parameters, parameters not on a GPU.
 
     Binds the agents' parameters to ``self.flat`` [K, P] (``bind_flat``) and their RMSprop ``square_avg`` state to
     ``self.square_avg`` [K, P] (state an agent already has is taken over; the agents' torch optimisers keep working on the same
@@ -248,10 +248,14 @@ class PopulationTrainer:
     steps.  Every agent must have the same optimiser class, settings and ``grad_clip``, and, with Adam, have taken the same number
     of steps.  Adam's ``exp_avg`` / ``exp_avg_sq`` become ``self.exp_avg`` / ``self.exp_avg_sq`` [K, P] with the agents' optimiser
     state as views of their rows; ``self.opt_step`` counts the steps and ``export_alpha()`` / ``close()`` write it to every
-    ``state[p]["step"]``.  ``self.last_grad_norms`` [K] holds every net's gradient norm (before clipping) of the last step."""
+    ``state[p]["step"]``.  ``self.last_grad_norms`` [K] holds every net's gradient norm (before clipping) of the last step.
+
+    ``layernorm``: True also takes agents whose trunks have ``nn.LayerNorm`` after every activation (all of them, or none: a mix is
+    a different network shape).  The native trainer is then made by azg_trainer_create_ex and runs the LayerNorm forms of its
+    kernels; ``flat``, the optimiser state, ``grads`` and the gradient norm cover ln.weight and ln.bias like every other parameter."""
 
     def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False, losses: str = "torch",
-                 optimizers: str = "rmsprop"):
+                 optimizers: str = "rmsprop", layernorm: bool = False):
         if losses not in ("torch", "device"):
             raise ValueError("losses must be 'torch' or 'device'")
         if optimizers not in ("rmsprop", "agents"):
@@ -267,7 +271,8 @@ class PopulationTrainer:
             raise ValueError("PopulationTrainer: every agent must have the same policy class")
         if not isinstance(a0.nn, (DiscretePolicy, DiagonalNormalPolicy, DiagonalGMMPolicy)):
             raise ValueError(f"PopulationTrainer: policy {type(a0.nn).__name__} is not supported")
-        if any(a.nn.layernorm for a in self.agents):
+        self.layernorm = bool(layernorm)
+        if not self.layernorm and any(a.nn.layernorm for a in self.agents):
             raise ValueError("PopulationTrainer: LayerNorm trunks are not trained on the device")
         opt_states: List[List[dict]] = []
         if optimizers == "agents":
@@ -314,7 +319,10 @@ class PopulationTrainer:
 
         # the native trainer first: if it cannot be created, the agents are left as they were
         self.max_batch = int(max_batch)
-        self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0)
+        if self.layernorm:
+            self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0, layernorm=True)
+        else:
+            self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0)
         self.policy, self.loss = a0.nn, a0.loss
         self.device = device
         self.desc, self.flat = bind_flat([a.nn for a in self.agents])

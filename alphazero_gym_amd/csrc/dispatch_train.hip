@@ -17,7 +17,8 @@ struct azg_trainer {
     int step_rows = 0;           // rows of the d_raw the last azg_trainer_step left in d_raw_buf (0: none)
     int num_components = 0;
     float log_std_min = 0.0f, log_std_max = 0.0f;
-    TrainDims d{};
+    bool ln = false;             // the LN = true kernels (a LayerNorm descriptor through azg_trainer_create_ex)
+    TrainDimsLN d{};
     float* scratch = nullptr;
     float* grad_buf = nullptr;   // [n_nets][P]: where the deferred backward form keeps the gradients when the caller gives no grads
     // the loss kernel's: the rows' terms [n_nets][3][max_batch] (float64), and azg_trainer_step's raw and d_raw [n_nets][max_batch][NO]
@@ -64,12 +65,11 @@ void azg_trainer_destroy(azg_trainer* t) {
     delete t;
 }
 
-int azg_trainer_create(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, azg_trainer** out) {
-    if (!desc || !out) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create: NULL argument");
-    *out = nullptr;
+// azg_trainer_create (layernorm_ok = false) and azg_trainer_create_ex
+static int create_impl(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, bool layernorm_ok, azg_trainer** out) {
     if (desc->struct_size != (int32_t)sizeof(azg_mlp_desc)) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create: azg_mlp_desc.struct_size mismatch");
     if (n_nets < 1 || max_batch < 1) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create: n_nets and max_batch must be at least 1");
-    if (desc->layernorm) return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: LayerNorm trunks are not trained on the device");
+    if (desc->layernorm && !layernorm_ok) return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: LayerNorm trunks are not trained on the device");
     if (desc->n_hidden < 1 || desc->n_hidden > TR_MAX_LAYERS)
         return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: 1 to 3 hidden layers");
     if (desc->in_dim < 1 || desc->in_dim > TR_OBS_LD) return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: in_dim must be 1..8");
@@ -86,7 +86,9 @@ int azg_trainer_create(int32_t device_id, const azg_mlp_desc* desc, int32_t n_ne
     t->num_components = desc->num_components;
     t->log_std_min = desc->log_std_min;
     t->log_std_max = desc->log_std_max;
-    TrainDims& d = t->d;
+    TrainDimsLN& d = t->d;
+    t->ln = desc->layernorm != 0;
+    d.layernorm = t->ln ? 1 : 0;
     d.n_layers = desc->n_hidden; d.in_dim = desc->in_dim; d.nd = desc->n_dist; d.NO = 1 + desc->n_dist; d.act = desc->activation;
     const size_t Bmax = ((size_t)max_batch + 15) / 16 * 16;
     int off = 0, prev = d.in_dim;
@@ -96,8 +98,14 @@ int azg_trainer_create(int32_t device_id, const azg_mlp_desc* desc, int32_t n_ne
         d.H[l] = desc->hidden[l];
         d.offW[l] = off; off += d.H[l] * prev;
         d.offb[l] = off; off += d.H[l];
+        if (t->ln) { d.offG[l] = off; off += d.H[l]; d.offB[l] = off; off += d.H[l]; }
         d.s_A[l] = (unsigned)so; so += Bmax * d.H[l];
         d.s_D[l] = (unsigned)so; so += Bmax * d.H[l];
+        if (t->ln) {
+            d.s_X[l] = (unsigned)so; so += Bmax * d.H[l];
+            d.s_G[l] = (unsigned)so; so += Bmax * d.H[l];
+            d.s_R[l] = (unsigned)so; so += Bmax;
+        }
         prev = d.H[l];
     }
     d.offWv = off; off += prev;
@@ -124,6 +132,21 @@ int azg_trainer_create(int32_t device_id, const azg_mlp_desc* desc, int32_t n_ne
     return AZG_OK;
 }
 
+int azg_trainer_create(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, azg_trainer** out) {
+    if (!desc || !out) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create: NULL argument");
+    *out = nullptr;
+    return create_impl(device_id, desc, n_nets, max_batch, false, out);
+}
+
+int azg_trainer_create_ex(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, const azg_trainer_options* opts,
+                          azg_trainer** out) {
+    if (!desc || !opts || !out) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_ex: NULL argument");
+    *out = nullptr;
+    if (opts->struct_size != (int32_t)sizeof(azg_trainer_options))
+        return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_ex: azg_trainer_options.struct_size mismatch");
+    return create_impl(device_id, desc, n_nets, max_batch, opts->layernorm != 0, out);
+}
+
 // ---- each call in three parts: its checks (nothing launched, nothing written), its launch, and the public entry point ----
 
 static int check_forward(azg_trainer* t, const char* who, const float* params, const float* obs, int32_t n_rows) {
@@ -133,8 +156,9 @@ static int check_forward(azg_trainer* t, const char* who, const float* params, c
 }
 
 static void launch_forward(azg_trainer* t, const float* params, const float* obs, int n_rows, float* raw) {
-    hipLaunchKernelGGL(train_forward_kernel, dim3((n_rows + 15) / 16, t->n_nets), dim3(64), 0, t->stream, t->d, params, obs, n_rows, raw,
-                       t->scratch);
+    const dim3 grid((n_rows + 15) / 16, t->n_nets);
+    if (t->ln) hipLaunchKernelGGL(train_forward_kernel<true>, grid, dim3(64), 0, t->stream, t->d, params, obs, n_rows, raw, t->scratch);
+    else hipLaunchKernelGGL(train_forward_kernel<false>, grid, dim3(64), 0, t->stream, (const TrainDims&)t->d, params, obs, n_rows, raw, t->scratch);
 }
 
 static int check_backward(azg_trainer* t, const char* who, const float* params, const azg_rmsprop* opt, const float* square_avg,
@@ -153,8 +177,12 @@ static void launch_backward(azg_trainer* t, float* params, const float* d_raw, i
     TrainOpt o;
     o.lr = (float)opt->lr; o.alpha = (float)opt->alpha; o.one_minus_alpha = (float)(1.0 - opt->alpha); o.eps = (float)opt->eps;
     o.wd = (float)opt->weight_decay;
-    hipLaunchKernelGGL(train_backward_kernel, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, o, params, d_raw, n_rows,
-                       square_avg, grads, t->scratch);
+    if (t->ln)
+        hipLaunchKernelGGL(train_backward_kernel<true>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, o, params, d_raw, n_rows,
+                           square_avg, grads, t->scratch);
+    else
+        hipLaunchKernelGGL(train_backward_kernel<false>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, (const TrainDims&)t->d, o, params,
+                           d_raw, n_rows, square_avg, grads, t->scratch);
 }
 
 // An azg_optim as the launch takes it: the fused kernel with the old settings (plain RMSprop, nothing asked of the gradients as a
@@ -218,8 +246,13 @@ static int check_opt_arg(azg_trainer* t, const char* who, const float* params, c
 static void launch_backward_arg(azg_trainer* t, float* params, const float* d_raw, int n_rows, const OptPlan& pl, const OptArg& a,
                                 float* grads) {
     if (pl.fused) { launch_backward(t, params, d_raw, n_rows, &pl.rms, a.opt_form ? a.opt->state0 : a.square_avg, grads); return; }
-    hipLaunchKernelGGL(train_backward_deferred_kernel, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, pl.o, params, d_raw,
-                       n_rows, a.opt->state0, a.opt->state1, grads ? grads : t->grad_buf, a.opt->grad_norms, t->scratch);
+    float* gr = grads ? grads : t->grad_buf;
+    if (t->ln)
+        hipLaunchKernelGGL(train_backward_deferred_kernel<true>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, pl.o, params, d_raw,
+                           n_rows, a.opt->state0, a.opt->state1, gr, a.opt->grad_norms, t->scratch);
+    else
+        hipLaunchKernelGGL(train_backward_deferred_kernel<false>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, (const TrainDims&)t->d,
+                           pl.o, params, d_raw, n_rows, a.opt->state0, a.opt->state1, gr, a.opt->grad_norms, t->scratch);
 }
 
 // The loss settings as the kernel takes them; every refusal of azg_trainer_loss.

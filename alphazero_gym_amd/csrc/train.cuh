@@ -9,6 +9,19 @@
 // For dW the k axis is the batch row, so batch tiles are summed in tile order.  db sums rows r = 0, 4, 8, ... / 1, 5, ... / 2, ... /
 // 3, ... in four float64 chains, combined (s0 + s1) + (s2 + s3) and rounded once.
 //
+// LayerNorm trunks (the LN = true instantiations; azg_trainer_create_ex).  After trunk layer m's A = act(Z): X = (A - mean) * rstd,
+// Y = X * gamma + beta; Y is what the next layer, the heads and dW read, and takes A's place in the scratch; X, rstd and
+// G = dZ_{m+1} W_{m+1} (the gradient by Y) have arrays of their own.  Every sum over the H columns of a row -- the mean, the variance
+// of the centred values (biased, eps 1e-5), and backward the means of dx = G * gamma and of dx * X -- has one order: sixteen
+// consecutive lanes share the row, lane c of them adds columns c, c + 16, c + 32, ... in that order in one float64 chain from the
+// float32 values (A, dx; A - mean and dx * X are formed in float64), and the sixteen partials are combined by a butterfly,
+// s = s + s[lane ^ 1], then ^ 2, ^ 4, ^ 8: the tree ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)) + ..., in which every lane
+// ends with the same bits because each step adds the same two numbers on both sides.  The sum is divided by H in float64 and rounded
+// to float32 once (the mean, rstd = 1 / sqrt(var + eps), and the two backward means); the elementwise X, Y, dx and
+// dA = rstd * ((dx - m1) - X * m2) are float32.  Which wave owns a row differs between the forward and the backward kernel and with
+// the row's number; which lane takes which column and how the partials meet does not, so it depends on neither K nor n_rows.
+// dgamma = sum over rows of G * X (the products exact in float64) and dbeta = sum over rows of G are db's four float64 chains.
+//
 // train_loss_kernel (the losses between the two): one lane per row computes the row's loss terms and its d_raw in float64 from the
 // float32 inputs (d_raw rounded once per element); the sums over the rows are the same four float64 chains, rounded once.
 #pragma once
@@ -34,6 +47,18 @@ struct TrainDims {
     unsigned s_obs, s_A[TR_MAX_LAYERS], s_D[TR_MAX_LAYERS];
     size_t per_net;
 };
+
+// The LN = true kernels' argument: TrainDims and what a LayerNorm trunk adds (the LN = false kernels keep taking TrainDims itself, so
+// their argument block and their code stay what they were).
+struct TrainDimsLN : TrainDims {
+    int layernorm;                                  // the descriptor's flag (0: a trainer made by create_ex for a plain trunk)
+    int offG[TR_MAX_LAYERS], offB[TR_MAX_LAYERS];   // ln.weight, ln.bias of the trunk layers
+    // per layer X_l [Bmax][H_l], G_l [Bmax][H_l] (d loss / d Y_l) and rstd_l [Bmax]; with LayerNorm s_A holds Y_l
+    unsigned s_X[TR_MAX_LAYERS], s_G[TR_MAX_LAYERS], s_R[TR_MAX_LAYERS];
+};
+template <bool LN> struct TrainDimsOf { typedef TrainDims type; };
+template <> struct TrainDimsOf<true> { typedef TrainDimsLN type; };
+#define TR_LN_EPS 1e-5
 
 struct TrainOpt {
     float lr, alpha, one_minus_alpha, eps, wd;
@@ -71,10 +96,40 @@ __device__ __forceinline__ void mma_strip(tr_f32x4 (&acc)[NT], int nt, int kdim,
     }
 }
 
+// The sum of s over the sixteen lanes that share a row (lanes 16 g .. 16 g + 15 of the wave): the butterfly of the header comment.
+__device__ __forceinline__ double tr_row16_sum(double s) {
+    s = s + __shfl_xor(s, 1);
+    s = s + __shfl_xor(s, 2);
+    s = s + __shfl_xor(s, 4);
+    s = s + __shfl_xor(s, 8);
+    return s;
+}
+
+// LayerNorm of one row after the layer's strips are stored: a[0 .. H) holds A and leaves holding Y; x receives X, *rstd_out rstd.
+// Called by all sixteen lanes c = 0 .. 15 of the row's group.  A row of equal values (a padded row) has var = 0 and rstd =
+// 1 / sqrt(eps): finite.
+__device__ __forceinline__ void tr_ln_row_forward(int H, int c, float* a, float* x, float* rstd_out, const float* gam, const float* bet) {
+    double s = 0.0;
+    for (int j = c; j < H; j += 16) s = s + (double)a[j];
+    const double mean = tr_row16_sum(s) / (double)H;
+    double v = 0.0;
+    for (int j = c; j < H; j += 16) { const double dc = (double)a[j] - mean; v = v + dc * dc; }
+    const double var = tr_row16_sum(v) / (double)H;
+    const float mf = (float)mean, rstd = (float)(1.0 / sqrt(var + TR_LN_EPS));
+    for (int j = c; j < H; j += 16) {
+        const float xv = (a[j] - mf) * rstd;
+        x[j] = xv;
+        a[j] = xv * gam[j] + bet[j];
+    }
+    if (c == 0) *rstd_out = rstd;
+}
+
 // ------------------------------------------------------------------------------------------------ forward
 // grid (row tiles, nets), one wave per workgroup: the wave carries its 16 rows through every layer, so nothing crosses waves.
-__global__ __launch_bounds__(64) void train_forward_kernel(TrainDims d, const float* params, const float* obs, int n_rows, float* raw,
-                                                           float* scratch) {
+// LN: after a layer's strips are stored the wave makes the row pass over its own 16 rows, four rows at a time.
+template <bool LN>
+__global__ __launch_bounds__(64) void train_forward_kernel(typename TrainDimsOf<LN>::type d, const float* params, const float* obs, int n_rows,
+                                                           float* raw, float* scratch) {
     const int net = blockIdx.y, m0 = blockIdx.x * 16, lane = threadIdx.x, r = lane & 15, g = lane >> 4;
     const float* p = params + (size_t)net * d.P;
     float* sc = scratch + (size_t)net * d.per_net;
@@ -118,6 +173,13 @@ __global__ __launch_bounds__(64) void train_forward_kernel(TrainDims d, const fl
             }
         }
         __syncthreads();
+        if constexpr (LN) {
+            for (int q = 0; q < 4; ++q) {
+                const size_t row = (size_t)(m0 + 4 * q + g);
+                tr_ln_row_forward(H, r, A + row * H, sc + d.s_X[l] + row * H, sc + d.s_R[l] + row, p + d.offG[l], p + d.offB[l]);
+            }
+            __syncthreads();
+        }
         Ain = A; lda = H; kin = H;
     }
     // heads: output o = 0 is the value head, 1 .. nd the distribution head
@@ -177,8 +239,13 @@ __device__ __forceinline__ float tr_colsum(int rows, F x) { return (float)tr_col
 // One workgroup per net.  Per layer, from the heads down: (a) dA of the layer below = dZ W, times act' -> dZ of the layer below
 // (in place over D); barrier; (b) dW = dZ^T A_below, db, and the optimiser step of this layer's parameters.  (a) reads the layer's
 // weights before the barrier and (b) writes them after it; (b) of one layer and (a) of the next touch different arrays.
-__global__ __launch_bounds__(TR_BWD_THREADS) void train_backward_kernel(TrainDims d, TrainOpt opt, float* params, const float* d_raw, int n_rows,
-                                                                        float* square_avg, float* grads_all, float* scratch) {
+// LN: (a) stores G = dZ W instead; barrier; the row pass reads G, gamma, X, rstd and turns D into dZ of the layer below; then the
+// barrier that was there.  (b) also emits dgamma and dbeta of the layer below from G and X, so gamma, like W, is read in front of a
+// barrier and stepped behind it, and G, X of one layer are not written again in this launch.
+template <bool LN>
+__global__ __launch_bounds__(TR_BWD_THREADS) void train_backward_kernel(typename TrainDimsOf<LN>::type d, TrainOpt opt, float* params,
+                                                                        const float* d_raw, int n_rows, float* square_avg, float* grads_all,
+                                                                        float* scratch) {
 #define TR_EMIT(idx, grad) tr_update(opt, p, sq, grads, idx, grad)
 #include "train_backward_layers.inc"
 #undef TR_EMIT
@@ -217,9 +284,10 @@ struct TrainOptD {
 //           included).  grads_all keeps the gradients as they were before clipping and weight decay.
 //   update  tr_update (RMSprop, float32, the fused form's own) or tr_adam (float64, rounded once) of every element.
 // state0: square_avg / exp_avg_sq, state1: exp_avg.  norms (may be NULL): total_norm of every net.
-__global__ __launch_bounds__(TR_BWD_THREADS) void train_backward_deferred_kernel(TrainDims d, TrainOptD o, float* params, const float* d_raw,
-                                                                                 int n_rows, float* state0, float* state1, float* grads_all,
-                                                                                 float* norms, float* scratch) {
+template <bool LN>
+__global__ __launch_bounds__(TR_BWD_THREADS) void train_backward_deferred_kernel(typename TrainDimsOf<LN>::type d, TrainOptD o, float* params,
+                                                                                 const float* d_raw, int n_rows, float* state0, float* state1,
+                                                                                 float* grads_all, float* norms, float* scratch) {
     {
         float* square_avg = state0;
 #define TR_EMIT(idx, grad) ((void)sq, grads[idx] = (grad))

@@ -1,6 +1,7 @@
 // train_backward_layers.inc -- the backward kernels' walk through the layers (train.cuh includes it once per kernel form, so that
 // both forms are the same text and the fused kernel compiles to the code it always was).  Expects the kernel's arguments d, params,
-// d_raw, n_rows, square_avg, grads_all and scratch in scope, and TR_EMIT(idx, grad): what a finished gradient element goes into.
+// d_raw, n_rows, square_avg, grads_all and scratch in scope, the kernel's template parameter LN, and TR_EMIT(idx, grad): what a
+// finished gradient element goes into.
     const int net = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
     const int NWV = TR_BWD_THREADS / 64;
     float* p = params + (size_t)net * d.P;
@@ -24,6 +25,8 @@
         if (l > 0) {
             // (a) dZ_{l-1}[row][j] = D_{l-1}[row][j] * sum_u dZ_l[row][u] W_l[u][j]
             float* Dp = sc + d.s_D[l - 1];
+            float* Gp = nullptr;
+            if constexpr (LN) Gp = sc + d.s_G[l - 1];
             const int ns = (Hp + 63) / 64, kdim = head ? NOT * 16 : Hl;
             for (int s = wave; s < MT * ns; s += NWV) {
                 const int m0 = (s / ns) * 16, n0 = (s % ns) * 64;
@@ -43,8 +46,33 @@
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
                             const size_t at = (size_t)(m0 + 4 * g + i) * Hp + n0 + 16 * t + r;
-                            Dp[at] = acc[t][i] * Dp[at];
+                            if constexpr (LN) Gp[at] = acc[t][i];
+                            else Dp[at] = acc[t][i] * Dp[at];
                         }
+                    }
+                }
+            }
+            if constexpr (LN) {
+                // the row pass of LayerNorm l - 1: sixteen lanes per row, four rows per wave at a time (Bpad is a multiple of 16, so
+                // a wave's four rows are inside or outside together)
+                __syncthreads();
+                const float* gam = p + d.offG[l - 1];
+                const float* Xp = sc + d.s_X[l - 1];
+                const float* Rp = sc + d.s_R[l - 1];
+                for (int row = 4 * wave + g; row < Bpad; row += 4 * NWV) {
+                    const size_t base = (size_t)row * Hp;
+                    double s1 = 0.0, s2 = 0.0;
+                    for (int j = r; j < Hp; j += 16) {
+                        const float dx = Gp[base + j] * gam[j];
+                        s1 = s1 + (double)dx;
+                        s2 = s2 + (double)dx * (double)Xp[base + j];
+                    }
+                    const float m1 = (float)(tr_row16_sum(s1) / (double)Hp), m2 = (float)(tr_row16_sum(s2) / (double)Hp);
+                    const float rstd = Rp[row];
+                    for (int j = r; j < Hp; j += 16) {
+                        const float dx = Gp[base + j] * gam[j];
+                        const float dA = rstd * ((dx - m1) - Xp[base + j] * m2);
+                        Dp[base + j] = dA * Dp[base + j];
                     }
                 }
             }
@@ -81,5 +109,20 @@
             else gsum = tr_colsum(Bpad, [&](int row) { return dZ[(size_t)row * Hl + u]; });
             const int idx = head ? (u == 0 ? d.offbv : d.offbd + u - 1) : d.offb[l] + u;
             TR_EMIT(idx, gsum);
+        }
+        if constexpr (LN) {
+            // dgamma and dbeta of LayerNorm l - 1 (widths are at most 256: threads 256 .. and 512 .. take them beside db's 0 ..)
+            if (l > 0) {
+                const float* Gq = sc + d.s_G[l - 1];
+                const float* Xq = sc + d.s_X[l - 1];
+                for (int u = tid - 256; u >= 0 && u < Hp; u += TR_BWD_THREADS) {
+                    const float gsum = tr_colsum(Bpad, [&](int row) { return (double)Gq[(size_t)row * Hp + u] * (double)Xq[(size_t)row * Hp + u]; });
+                    TR_EMIT(d.offG[l - 1] + u, gsum);
+                }
+                for (int u = tid - 512; u >= 0 && u < Hp; u += TR_BWD_THREADS) {
+                    const float gsum = tr_colsum(Bpad, [&](int row) { return Gq[(size_t)row * Hp + u]; });
+                    TR_EMIT(d.offB[l - 1] + u, gsum);
+                }
+            }
         }
     }

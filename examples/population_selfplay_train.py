@@ -9,6 +9,7 @@ in PyTorch between them); --trainer device-fused computes the losses on the devi
 --trainer device-epoch takes the whole epoch of those steps in one native call that reads the rows straight from the self-play ring
 (PopulationTrainer.train_epoch_ring: no copy of the rows, one synchronisation per iteration instead of one per minibatch).
 --optimizer adam and --grad-clip X give every net the reference's Adam settings and gradient clipping, on every trainer.
+--layernorm builds every net with LayerNorm after each trunk activation; the device trainers are then built with layernorm=True.
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
@@ -48,6 +49,8 @@ def parse_args(argv=None):
                     help="every net's optimiser; adam: the reference's Adam settings (run.ADAM).  With adam or --grad-clip the device "
                          "trainers are built with optimizers='agents'")
     ap.add_argument("--grad-clip", type=float, default=0.0, help="clip_grad_norm_ bound of every net's optimiser step (0: off)")
+    ap.add_argument("--layernorm", action="store_true",
+                    help="LayerNorm after every trunk activation (the reference's policy.layernorm); the device trainers get layernorm=True")
     ap.add_argument("--engine-seed", type=int, default=34, help="the engine's RNG seed (shared; games differ by their global ids)")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--trainer", choices=["torch", "device", "device-fused", "device-epoch"], default="torch",
@@ -67,7 +70,7 @@ def build_population(a):
     agents = []
     for s in a.seeds:
         torch.manual_seed(s)
-        agent, state_dim = build_agent(a.game, a.hidden, a.n_rollouts, a.device, a.lr, a.optimizer, a.grad_clip)
+        agent, state_dim = build_agent(a.game, a.hidden, a.n_rollouts, a.device, a.lr, a.optimizer, a.grad_clip, a.layernorm)
         agents.append(agent)
     m = agents[0].mcts
     sp = run.PopulationSelfPlay([ag.nn for ag in agents], game=a.game, games_per_net=a.games_per_seed, n_rollouts=a.n_rollouts,
@@ -89,7 +92,8 @@ def train(a, log=print, on_rows=None):
     if a.trainer != "torch":
         from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
         trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size), losses="torch" if a.trainer == "device" else "device",
-                                    optimizers="agents" if (a.optimizer != "rmsprop" or a.grad_clip) else "rmsprop")
+                                    optimizers="agents" if (a.optimizer != "rmsprop" or a.grad_clip) else "rmsprop",
+                                    layernorm=a.layernorm)
     t0 = time.time()
     history = []
     for it in range(a.iters):

@@ -26,21 +26,23 @@ from alphazero_gym_amd import distributed as D, run  # noqa: E402
 from alphazero_gym_amd.agent.agents import ContinuousAgent, DiscreteAgent  # noqa: E402
 
 
-def build_agent(game, hidden, n_rollouts, device, lr, optimizer="rmsprop", grad_clip=0.0):
+def build_agent(game, hidden, n_rollouts, device, lr, optimizer="rmsprop", grad_clip=0.0, layernorm=False):
     """optimizer: "rmsprop" (run.RMSPROP) or "adam" (run.ADAM, the reference's Adam settings); grad_clip: the agent's clip_grad_norm_
-    bound (0: off)."""
+    bound (0: off); layernorm: nn.LayerNorm after every trunk activation (policy.layernorm)."""
     opt = dict(run.ADAM if optimizer == "adam" else run.RMSPROP, lr=lr)
     loss = dict(run.LOSS_TUNED, device=device)
     if game.lower().startswith("pendulum"):
         cfg = run.CONTINUOUS_DEFAULTS
-        policy = dict(cfg["policy"], hidden_dimensions=hidden, representation_dim=3, action_dim=1, action_bound=2.0)
+        policy = dict(cfg["policy"], hidden_dimensions=hidden, representation_dim=3, action_dim=1, action_bound=2.0,
+                      layernorm=layernorm)
         mcts = dict(cfg["mcts"], n_rollouts=n_rollouts, device=device)
         return ContinuousAgent(policy_cfg=policy, mcts_cfg=mcts, loss_cfg=loss, optimizer_cfg=opt, device=device,
                                **dict(cfg["agent"], grad_clip=grad_clip)), 3
     cfg = run.DISCRETE_DEFAULTS
     g = game.lower()   # MountainCar-v0: two observations, three actions; Acrobot-v1: six observations, three actions
     obs_dim, n_act = (2, 3) if g.startswith("mountaincar") else ((6, 3) if g.startswith("acrobot") else (4, 2))
-    policy = dict(cfg["policy"], hidden_dimensions=hidden, representation_dim=obs_dim, action_dim=1, num_actions=n_act)
+    policy = dict(cfg["policy"], hidden_dimensions=hidden, representation_dim=obs_dim, action_dim=1, num_actions=n_act,
+                  layernorm=layernorm)
     mcts = dict(cfg["mcts"], n_rollouts=n_rollouts, device=device, num_actions=n_act)
     return DiscreteAgent(policy_cfg=policy, mcts_cfg=mcts, loss_cfg=loss, optimizer_cfg=opt, device=device,
                          **dict(cfg["agent"], grad_clip=grad_clip)), obs_dim
@@ -60,6 +62,7 @@ def parse_args(argv=None):
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--optimizer", choices=["rmsprop", "adam"], default="rmsprop", help="adam: the reference's Adam settings (run.ADAM)")
     ap.add_argument("--grad-clip", type=float, default=0.0, help="clip_grad_norm_ bound of every optimiser step (0: off)")
+    ap.add_argument("--layernorm", action="store_true", help="LayerNorm after every trunk activation (the reference's policy.layernorm)")
     ap.add_argument("--seed", type=int, default=34)
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     return ap.parse_args(argv)
@@ -71,7 +74,7 @@ def train(a, log=print):
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
     torch.manual_seed(a.seed)   # same initial weights on every rank
-    agent, state_dim = build_agent(a.game, a.hidden, a.n_rollouts, a.device, a.lr, a.optimizer, a.grad_clip)
+    agent, state_dim = build_agent(a.game, a.hidden, a.n_rollouts, a.device, a.lr, a.optimizer, a.grad_clip, a.layernorm)
     continuous = state_dim == 3
     m = agent.mcts
     sp = run.DeviceSelfPlay(agent.nn, game=a.game, n_games=a.games, n_rollouts=a.n_rollouts, c_uct=m.c_uct, gamma=m.gamma,

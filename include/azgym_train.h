@@ -26,7 +26,8 @@
  * the backward launch then writes the gradients first and runs norm, clip and update as a phase after the last layer.
  *
  * Supported nets: Linear + activation trunks of 1..3 hidden layers, widths multiples of 16 up to 256, in_dim <= 8, n_dist <= 16,
- * every AZG_ACT_* activation; no LayerNorm.  Anything else: AZG_E_UNSUPPORTED from azg_trainer_create.
+ * every AZG_ACT_* activation; LayerNorm after every trunk activation (nn.LayerNorm's defaults: eps 1e-5, affine) only from a trainer
+ * made by azg_trainer_create_ex with options.layernorm set.  Anything else: AZG_E_UNSUPPORTED from azg_trainer_create(_ex).
  * The arithmetic is float32 on v_mfma_f32_16x16x4_f32 with a fixed summation order and no atomics: the same inputs give the same
  * bits on every run, and net k's results do not depend on n_nets.  Rows are padded to 16 inside; padded rows contribute nothing.
  * The loss kernel computes every row's terms in float64 from the float32 inputs and every sum over the rows as fixed-order float64
@@ -58,6 +59,19 @@ void azg_trainer_destroy(azg_trainer* t);
 const char* azg_trainer_last_error(const azg_trainer* t);
 /* P: floats per net */
 size_t azg_trainer_param_count(const azg_trainer* t);
+
+/* azg_trainer_create with options.  layernorm != 0: a descriptor with layernorm = 1 is accepted as well (one without runs the same
+ * kernels azg_trainer_create's trainer runs); every other limit is azg_trainer_create's.  Per trunk layer the parameters are then
+ * weight, bias, ln.weight, ln.bias (state_dict order), and P counts them.  Every entry point below works on such a trainer unchanged;
+ * the trunk computes Y = LayerNorm(act(Y_prev W^T + b)) with the row statistics in float64 from the float32 activations (a fixed
+ * order over a row's columns, independent of n_nets and n_rows), and the gradients of ln.weight / ln.bias are sums over the rows in
+ * db's fixed order.  NULL opts or a wrong opts->struct_size: AZG_E_INVALID. */
+typedef struct azg_trainer_options {
+    int32_t struct_size;
+    int32_t layernorm;
+} azg_trainer_options;
+int azg_trainer_create_ex(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, const azg_trainer_options* opts,
+                          azg_trainer** out);
 
 /* The forward pass of a minibatch optimiser step (the network half of agents.py:319-392, 539-603: policy.get_train_data's
  * trunk and heads) for every net on its own n_rows rows: one launch.  Writes raw and keeps obs, every layer's activations and

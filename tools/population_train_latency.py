@@ -20,7 +20,12 @@ with a mixture of 2:
 its deferred form: gradients first, then norm, clip and update) against the loop of agent.update calls of the same agents and against
 the fused RMSprop step (default agents, losses="device") in the same process, CartPole 2x128 ReLU and Pendulum 3x128 ELU with a
 mixture of 2:
-    python tools/population_train_latency.py --optimizer adam --grad-clip 1.0    (writes profiles/population_train_latency_adam.txt)"""
+    python tools/population_train_latency.py --optimizer adam --grad-clip 1.0    (writes profiles/population_train_latency_adam.txt)
+
+--layernorm measures the step of agents whose trunks have nn.LayerNorm after every activation (policy.layernorm = True):
+PopulationTrainer(layernorm=True).update with the losses in PyTorch and on the device against the loop of agent.update calls of the
+same LayerNorm agents, and beside them the device-loss step of the same nets without LayerNorm, all in one process:
+    python tools/population_train_latency.py --layernorm    (writes profiles/population_train_latency_layernorm.txt)"""
 import argparse
 import os
 import subprocess
@@ -137,6 +142,50 @@ def measure_optim(name, K, B, reps, warmup, optimizer, grad_clip):
     return t_loop, t_opt, t_fused
 
 
+def measure_layernorm(name, K, B, reps, warmup):
+    """(loop of agent.update, layernorm=True step with torch losses, with device losses, the plain nets' device-loss step) median ms."""
+    kind, S, A = CONFIGS[name]
+    base = run.CONTINUOUS_DEFAULTS if kind == "continuous" else run.DISCRETE_DEFAULTS
+    cfg = run._merge(base, dict(device="cuda", policy=dict(layernorm=True)))
+    plain_cfg = run._merge(base, dict(device="cuda"))
+    env = make_game(cfg["game"])
+    stacked = _batches(kind, K, B, S, A)
+    per_net = [tuple(t[k] for t in stacked) for k in range(K)]
+
+    def agents_of(c):
+        torch.manual_seed(0)
+        return [run.make_agent(kind, c, env, tree_id_base=k) for k in range(K)]
+
+    agents = agents_of(cfg)
+
+    def loop():
+        for a, b in zip(agents, per_net):
+            a.update(b)
+
+    t_loop = _median_ms(loop, reps, warmup)
+    out = [t_loop]
+    for c, kw in ((cfg, dict(layernorm=True)), (cfg, dict(layernorm=True, losses="device")), (plain_cfg, dict(losses="device"))):
+        tr = PT.PopulationTrainer(agents_of(c), max_batch=max(512, 2 * B), **kw)
+        out.append(_median_ms(lambda: tr.update(stacked), reps, warmup))
+        tr.close()
+    return out
+
+
+def main_layernorm(a):
+    lines = ["# tools/population_train_latency.py --layernorm: one minibatch optimiser step of K nets with LayerNorm trunks, batch %d, one "
+             "MI355X; median wall ms of %d repetitions after %d warm-up, all four in one process" % (a.batch, a.reps, a.warmup)]
+    for name in a.configs.split(","):
+        lines.append(f"# {name}: loop of K agent.update (LayerNorm agents) | PopulationTrainer(layernorm=True).update | ratio | "
+                     "PopulationTrainer(layernorm=True, losses='device').update | ratio to the loop | the same nets without LayerNorm, "
+                     "losses='device' | LayerNorm / plain")
+        for K in [int(k) for k in a.ks.split(",")]:
+            t_loop, t_pop, t_dev, t_plain = measure_layernorm(name, K, a.batch, a.reps, a.warmup)
+            lines.append(f"  {name} K={K:4d} loop {t_loop:9.3f} ms  layernorm=True {t_pop:8.3f} ms  {t_loop / t_pop:7.2f}x  "
+                         f"device losses {t_dev:8.3f} ms  {t_loop / t_dev:7.2f}x  plain nets {t_plain:8.3f} ms  {t_dev / t_plain:6.3f}x")
+            print(lines[-1], flush=True)
+    return lines
+
+
 def main_optim(a):
     lines = ["# tools/population_train_latency.py --optimizer %s --grad-clip %g: one minibatch optimiser step of K nets, batch %d, one MI355X; "
              "median wall ms of %d repetitions after %d warm-up, all three in one process" % (a.optimizer, a.grad_clip, a.batch, a.reps, a.warmup)]
@@ -237,8 +286,14 @@ def main():
     ap.add_argument("--rows", type=int, default=512, help="--epoch: rows per net")
     ap.add_argument("--optimizer", choices=["rmsprop", "adam"], default="rmsprop", help="adam (the reference's settings): measure optimizers='agents'")
     ap.add_argument("--grad-clip", type=float, default=0.0, help="a bound > 0: measure optimizers='agents' with gradient clipping")
+    ap.add_argument("--layernorm", action="store_true", help="measure PopulationTrainer(layernorm=True) on LayerNorm agents")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.layernorm:
+        out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "population_train_latency_layernorm.txt")
+        with open(out, "w") as f:
+            f.write("\n".join(main_layernorm(a)) + "\n")
+        return
     if a.optimizer != "rmsprop" or a.grad_clip:
         out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "population_train_latency_adam.txt")
         with open(out, "w") as f:
