@@ -252,10 +252,15 @@ class PopulationTrainer:
 
     ``layernorm``: True also takes agents whose trunks have ``nn.LayerNorm`` after every activation (all of them, or none: a mix is
     a different network shape).  The native trainer is then made by azg_trainer_create_ex and runs the LayerNorm forms of its
-    kernels; ``flat``, the optimiser state, ``grads`` and the gradient norm cover ln.weight and ln.bias like every other parameter."""
+    kernels; ``flat``, the optimiser state, ``grads`` and the gradient norm cover ln.weight and ln.bias like every other parameter.
+
+    ``wide``: True takes every network shape the engine can search: 1-8 hidden layers of widths 16, 32, ... 1024 (narrow agents
+    too).  The native trainer is then made by azg_trainer_create_wide, whose kernels spread every layer over the chip, one launch
+    per layer and direction; a shape the default trainer also takes gets the same bits.  LayerNorm trunks are not among them:
+    ``wide=True`` with ``layernorm=True`` or with LayerNorm agents raises."""
 
     def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False, losses: str = "torch",
-                 optimizers: str = "rmsprop", layernorm: bool = False):
+                 optimizers: str = "rmsprop", layernorm: bool = False, wide: bool = False):
         if losses not in ("torch", "device"):
             raise ValueError("losses must be 'torch' or 'device'")
         if optimizers not in ("rmsprop", "agents"):
@@ -272,6 +277,9 @@ class PopulationTrainer:
         if not isinstance(a0.nn, (DiscretePolicy, DiagonalNormalPolicy, DiagonalGMMPolicy)):
             raise ValueError(f"PopulationTrainer: policy {type(a0.nn).__name__} is not supported")
         self.layernorm = bool(layernorm)
+        self.wide = bool(wide)
+        if self.wide and (self.layernorm or any(a.nn.layernorm for a in self.agents)):
+            raise ValueError("PopulationTrainer: wide=True does not train LayerNorm trunks on the device")
         if not self.layernorm and any(a.nn.layernorm for a in self.agents):
             raise ValueError("PopulationTrainer: LayerNorm trunks are not trained on the device")
         opt_states: List[List[dict]] = []
@@ -297,14 +305,19 @@ class PopulationTrainer:
                 raise ValueError("PopulationTrainer: every agent must have the same RMSprop settings")
         if len({_loss_settings(a.loss) for a in self.agents}) != 1:
             raise ValueError("PopulationTrainer: every agent must have the same loss class and hyper-parameters")
+        max_layers, max_width = (8, 1024) if self.wide else (3, 256)
+        unsupported = (f"PopulationTrainer: supported nets have 1-{max_layers} hidden layers of widths 16, 32, ... {max_width}, at most "
+                       "8 inputs and 16 distribution outputs")
+        if any(len(list(a.nn.hidden_dimensions)) > _capi.MAX_HIDDEN for a in self.agents):   # (more than a descriptor holds)
+            raise ValueError(unsupported)
         descs = [_capi.policy_tensors(a.nn) for a in self.agents]
         if any([tuple(t.shape) for t in ts] != [tuple(t.shape) for t in descs[0][1]] or bytes(d) != bytes(descs[0][0]) for d, ts in descs):
             raise ValueError("PopulationTrainer: every agent must have the same network shape, activation and head settings")
         d0 = descs[0][0]
         hidden = [d0.hidden[i] for i in range(d0.n_hidden)]
-        if not (1 <= d0.n_hidden <= 3 and all(h % 16 == 0 and 16 <= h <= 256 for h in hidden) and d0.in_dim <= 8 and d0.n_dist <= 16):
-            raise ValueError("PopulationTrainer: supported nets have 1-3 hidden layers of widths 16, 32, ... 256, at most 8 inputs and "
-                             "16 distribution outputs")
+        if not (1 <= d0.n_hidden <= max_layers and all(h % 16 == 0 and 16 <= h <= max_width for h in hidden) and d0.in_dim <= 8
+                and d0.n_dist <= 16):
+            raise ValueError(unsupported)
         pars = [p for a in self.agents for p in a.nn.parameters()]
         device = pars[0].device
         if device.type != "cuda" or any(p.device != device for p in pars):
@@ -319,7 +332,9 @@ class PopulationTrainer:
 
         # the native trainer first: if it cannot be created, the agents are left as they were
         self.max_batch = int(max_batch)
-        if self.layernorm:
+        if self.wide:
+            self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0, wide=True)
+        elif self.layernorm:
             self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0, layernorm=True)
         else:
             self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0)

@@ -1,6 +1,8 @@
 // dispatch_train.hip -- the population trainer's C ABI (include/azgym_train.h): scratch, checks and the three launches of train.cuh;
 // azg_trainer_epoch enqueues them for a whole epoch of minibatches behind a gather launch each.  The *_opt entry points take an
 // azg_optim and choose the backward launch's form: fused RMSprop, or gradients first and norm, clip and update after the last layer.
+// A trainer made by azg_trainer_create_wide keeps its dims in `wide` and takes dispatch_train_wide.hip's launches (one per layer and
+// role) wherever a narrow one takes train.cuh's; every check, buffer and synchronisation is the same code.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -9,6 +11,7 @@
 #include "../../include/azgym_train.h"
 #include "hip_host.h"
 #include "train.cuh"
+#include "train_wide_host.h"
 
 struct azg_trainer {
     int device_id = 0;
@@ -19,6 +22,8 @@ struct azg_trainer {
     float log_std_min = 0.0f, log_std_max = 0.0f;
     bool ln = false;             // the LN = true kernels (a LayerNorm descriptor through azg_trainer_create_ex)
     TrainDimsLN d{};
+    TrainWide* wide = nullptr;   // azg_trainer_create_wide: d then holds only what the host reads (P, NO, nd, in_dim, n_layers)
+    double* norm_part = nullptr; // ... and the deferred norm's partial chains [n_nets][1024]
     float* scratch = nullptr;
     float* grad_buf = nullptr;   // [n_nets][P]: where the deferred backward form keeps the gradients when the caller gives no grads
     // the loss kernel's: the rows' terms [n_nets][3][max_batch] (float64), and azg_trainer_step's raw and d_raw [n_nets][max_batch][NO]
@@ -62,6 +67,8 @@ void azg_trainer_destroy(azg_trainer* t) {
     if (t->order_buf) (void)hipFree(t->order_buf);
     if (t->stage_buf) (void)hipFree(t->stage_buf);
     if (t->loss_table) (void)hipFree(t->loss_table);
+    if (t->norm_part) (void)hipFree(t->norm_part);
+    if (t->wide) tw_free(t->wide);
     delete t;
 }
 
@@ -147,6 +154,41 @@ int azg_trainer_create_ex(int32_t device_id, const azg_mlp_desc* desc, int32_t n
     return create_impl(device_id, desc, n_nets, max_batch, opts->layernorm != 0, out);
 }
 
+int azg_trainer_create_wide(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, azg_trainer** out) {
+    if (!desc || !out) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide: NULL argument");
+    if (desc->struct_size != (int32_t)sizeof(azg_mlp_desc)) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide: azg_mlp_desc.struct_size mismatch");
+    if (n_nets < 1 || max_batch < 1) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide: n_nets and max_batch must be at least 1");
+    TrainWide* w = nullptr;
+    std::string msg;
+    if (int rc = tw_plan(desc, max_batch, &w, &msg)) return tfail(nullptr, rc, msg);
+    azg_trainer* t = new azg_trainer();
+    t->wide = w;
+    t->device_id = device_id;
+    t->n_nets = n_nets;
+    t->max_batch = max_batch;
+    t->num_components = desc->num_components;
+    t->log_std_min = desc->log_std_min;
+    t->log_std_max = desc->log_std_max;
+    t->d.n_layers = desc->n_hidden; t->d.in_dim = desc->in_dim; t->d.nd = desc->n_dist; t->d.NO = 1 + desc->n_dist; t->d.act = desc->activation;
+    t->d.P = tw_param_count(w);
+    t->d.per_net = tw_scratch_floats(w);
+    DeviceScope scope(device_id);
+    if (!scope.ok) { azg_trainer_destroy(t); return tfail(nullptr, AZG_E_DEVICE, "hipSetDevice failed"); }
+    // (the scratch is not cleared, for azg_trainer_create's reason)
+    hipError_t rc = hipMalloc((void**)&t->scratch, t->d.per_net * (size_t)n_nets * sizeof(float));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&t->grad_buf, (size_t)n_nets * (size_t)t->d.P * sizeof(float));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&t->norm_part, (size_t)n_nets * TR_BWD_THREADS * sizeof(double));
+    if (rc == hipSuccess) rc = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
+    if (rc != hipSuccess) {
+        const std::string m = std::string("azg_trainer_create_wide: ") + hipGetErrorString(rc);
+        (void)hipGetLastError();
+        azg_trainer_destroy(t);
+        return tfail(nullptr, AZG_E_DEVICE, m);
+    }
+    *out = t;
+    return AZG_OK;
+}
+
 // ---- each call in three parts: its checks (nothing launched, nothing written), its launch, and the public entry point ----
 
 static int check_forward(azg_trainer* t, const char* who, const float* params, const float* obs, int32_t n_rows) {
@@ -156,6 +198,7 @@ static int check_forward(azg_trainer* t, const char* who, const float* params, c
 }
 
 static void launch_forward(azg_trainer* t, const float* params, const float* obs, int n_rows, float* raw) {
+    if (t->wide) { tw_launch_forward(t->wide, t->stream, t->n_nets, params, obs, n_rows, raw, t->scratch); return; }
     const dim3 grid((n_rows + 15) / 16, t->n_nets);
     if (t->ln) hipLaunchKernelGGL(train_forward_kernel<true>, grid, dim3(64), 0, t->stream, t->d, params, obs, n_rows, raw, t->scratch);
     else hipLaunchKernelGGL(train_forward_kernel<false>, grid, dim3(64), 0, t->stream, (const TrainDims&)t->d, params, obs, n_rows, raw, t->scratch);
@@ -177,6 +220,7 @@ static void launch_backward(azg_trainer* t, float* params, const float* d_raw, i
     TrainOpt o;
     o.lr = (float)opt->lr; o.alpha = (float)opt->alpha; o.one_minus_alpha = (float)(1.0 - opt->alpha); o.eps = (float)opt->eps;
     o.wd = (float)opt->weight_decay;
+    if (t->wide) { tw_launch_backward(t->wide, t->stream, t->n_nets, o, params, d_raw, n_rows, square_avg, grads, t->scratch); return; }
     if (t->ln)
         hipLaunchKernelGGL(train_backward_kernel<true>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, o, params, d_raw, n_rows,
                            square_avg, grads, t->scratch);
@@ -247,6 +291,11 @@ static void launch_backward_arg(azg_trainer* t, float* params, const float* d_ra
                                 float* grads) {
     if (pl.fused) { launch_backward(t, params, d_raw, n_rows, &pl.rms, a.opt_form ? a.opt->state0 : a.square_avg, grads); return; }
     float* gr = grads ? grads : t->grad_buf;
+    if (t->wide) {
+        tw_launch_backward_deferred(t->wide, t->stream, t->n_nets, pl.o, params, d_raw, n_rows, a.opt->state0, a.opt->state1, gr,
+                                    a.opt->grad_norms, t->scratch, t->norm_part);
+        return;
+    }
     if (t->ln)
         hipLaunchKernelGGL(train_backward_deferred_kernel<true>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, pl.o, params, d_raw,
                            n_rows, a.opt->state0, a.opt->state1, gr, a.opt->grad_norms, t->scratch);

@@ -486,6 +486,9 @@ __device__ __forceinline__ void tr_loss_row(const LossDims& c, double alpha, con
     }
 }
 
+// (TR_NO_SHARED_KERNELS: a second translation unit that wants this header's device routines and templates, not another copy of the
+// three plain kernels below -- dispatch_train_wide.hip)
+#ifndef TR_NO_SHARED_KERNELS
 // One workgroup per net, one lane per row (rows tid, tid + 256, ...).  rows: the trainer's float64 [n_nets][3][stride] array of the
 // rows' terms.  log_alpha[net] is read by every lane before the first barrier and written by lane 0 after the second.
 __global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_kernel(LossDims c, const float* raw, const float* actions, const float* counts,
@@ -572,3 +575,4 @@ __global__ __launch_bounds__(64) void train_loss_sum_kernel(const float* table, 
     for (int m = 0; m < n_minibatches; ++m) s = s + (double)table[(size_t)m * n + e];
     sums[e] = s;
 }
+#endif  // TR_NO_SHARED_KERNELS

@@ -10,6 +10,9 @@ in PyTorch between them); --trainer device-fused computes the losses on the devi
 (PopulationTrainer.train_epoch_ring: no copy of the rows, one synchronisation per iteration instead of one per minibatch).
 --optimizer adam and --grad-clip X give every net the reference's Adam settings and gradient clipping, on every trainer.
 --layernorm builds every net with LayerNorm after each trunk activation; the device trainers are then built with layernorm=True.
+--wide builds the device trainers with wide=True, which trains nets of up to 8 hidden layers and widths up to 1024 (--hidden 1024
+1024 1024 1024).  The search engine takes a population of more than one net only up to width 256, so a wide run is one seed:
+--seeds 0 --hidden 512 272 --wide.
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
@@ -51,6 +54,9 @@ def parse_args(argv=None):
     ap.add_argument("--grad-clip", type=float, default=0.0, help="clip_grad_norm_ bound of every net's optimiser step (0: off)")
     ap.add_argument("--layernorm", action="store_true",
                     help="LayerNorm after every trunk activation (the reference's policy.layernorm); the device trainers get layernorm=True")
+    ap.add_argument("--wide", action="store_true",
+                    help="build the device trainers with wide=True: 1-8 hidden layers of widths 16 ... 1024 (no LayerNorm).  One search "
+                         "engine cannot hold a population of several nets wider than 256, so use it with one seed (--seeds 0)")
     ap.add_argument("--engine-seed", type=int, default=34, help="the engine's RNG seed (shared; games differ by their global ids)")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--trainer", choices=["torch", "device", "device-fused", "device-epoch"], default="torch",
@@ -81,8 +87,9 @@ def build_population(a):
     return agents, state_dim, sp
 
 
-def train(a, log=print, on_rows=None):
-    """Runs the loop; returns the per-iteration records.  ``on_rows(it, rows)``, if given, sees every iteration's per-seed rows."""
+def train(a, log=print, on_rows=None, on_end=None):
+    """Runs the loop; returns the per-iteration records.  ``on_rows(it, rows)``, if given, sees every iteration's per-seed rows;
+    ``on_end(agents)`` the agents after the last iteration."""
     agents, state_dim, sp = build_population(a)
     K = sp.engine.kmax
     rngs = [np.random.RandomState(s) for s in a.seeds]
@@ -93,7 +100,7 @@ def train(a, log=print, on_rows=None):
         from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
         trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size), losses="torch" if a.trainer == "device" else "device",
                                     optimizers="agents" if (a.optimizer != "rmsprop" or a.grad_clip) else "rmsprop",
-                                    layernorm=a.layernorm)
+                                    layernorm=a.layernorm, wide=a.wide)
     t0 = time.time()
     history = []
     for it in range(a.iters):
@@ -155,6 +162,8 @@ def train(a, log=print, on_rows=None):
         fs0, fc0 = fs, fc
     if trainer is not None:
         trainer.close()
+    if on_end is not None:
+        on_end(agents)
     sp.close()
     return history
 

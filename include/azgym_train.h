@@ -28,6 +28,9 @@
  * Supported nets: Linear + activation trunks of 1..3 hidden layers, widths multiples of 16 up to 256, in_dim <= 8, n_dist <= 16,
  * every AZG_ACT_* activation; LayerNorm after every trunk activation (nn.LayerNorm's defaults: eps 1e-5, affine) only from a trainer
  * made by azg_trainer_create_ex with options.layernorm set.  Anything else: AZG_E_UNSUPPORTED from azg_trainer_create(_ex).
+ * azg_trainer_create_wide takes every shape the search engine takes -- 1..AZG_MAX_HIDDEN_LAYERS (8) hidden layers, widths multiples
+ * of 16 up to 1024, no LayerNorm -- and spreads every layer over the chip: one launch per layer in the forward pass, two per layer
+ * in the backward pass.  A shape both constructors accept gives the same bits from either trainer.
  * The arithmetic is float32 on v_mfma_f32_16x16x4_f32 with a fixed summation order and no atomics: the same inputs give the same
  * bits on every run, and net k's results do not depend on n_nets.  Rows are padded to 16 inside; padded rows contribute nothing.
  * The loss kernel computes every row's terms in float64 from the float32 inputs and every sum over the rows as fixed-order float64
@@ -72,6 +75,23 @@ typedef struct azg_trainer_options {
 } azg_trainer_options;
 int azg_trainer_create_ex(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, const azg_trainer_options* opts,
                           azg_trainer** out);
+
+/* A trainer for wide nets.  Accepted: Linear + activation trunks of 1..AZG_MAX_HIDDEN_LAYERS hidden layers of widths 16, 32, ... 1024,
+ * in_dim <= 8, n_dist <= 16, every AZG_ACT_* activation.  desc->layernorm set (wide LayerNorm trunks are not built) and every other
+ * shape outside that set: AZG_E_UNSUPPORTED with a message (azg_trainer_last_error(NULL)); NULL pointers, n_nets < 1 or max_batch < 1:
+ * AZG_E_INVALID; a max_batch whose scratch offsets do not fit 32 bits, or a failed allocation: an error code, nothing is leaked
+ * and *out is untouched.  The handle is an ordinary azg_trainer: every entry point of this header works on it with the same
+ * signatures, checks, error codes, stream behaviour and "on an error nothing is written" rule.  Where azg_trainer_create's trainer
+ * makes one launch for the forward pass and one for the backward pass, this one makes a launch per layer and role on the same
+ * stream: n_hidden + 1 forward (the layers, the heads) and 2 * n_hidden + 1 backward ((a) dZ of the layer below, (b) dW, db and the
+ * optimiser step of the layer; (a) of a layer reads the weights that (b) of the same layer, in the next launch, rewrites); the
+ * deferred form (azg_optim with Adam, grad_clip or grad_norms) adds one launch for the norm's 1024 partial chains and one for norm
+ * tree, clip and update.  No atomics and no waiting between workgroups.  The summation orders are azg_trainer_create's for every
+ * width: an output element is one accumulator chain over its k-blocks of 16 in order, dW sums the batch tiles in order, db is four
+ * float64 chains, the norm is 1024 float64 chains and a pairwise tree; so the results do not depend on n_nets or on the run, the
+ * fused and the deferred form give the same gradients, and for 1..3 layers of width <= 256 every output (raw, gradients, params,
+ * optimiser state, grad_norms, d_raw, losses, an epoch's results) has the bits azg_trainer_create's trainer gives. */
+int azg_trainer_create_wide(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, azg_trainer** out);
 
 /* The forward pass of a minibatch optimiser step (the network half of agents.py:319-392, 539-603: policy.get_train_data's
  * trunk and heads) for every net on its own n_rows rows: one launch.  Writes raw and keeps obs, every layer's activations and

@@ -25,7 +25,14 @@ mixture of 2:
 --layernorm measures the step of agents whose trunks have nn.LayerNorm after every activation (policy.layernorm = True):
 PopulationTrainer(layernorm=True).update with the losses in PyTorch and on the device against the loop of agent.update calls of the
 same LayerNorm agents, and beside them the device-loss step of the same nets without LayerNorm, all in one process:
-    python tools/population_train_latency.py --layernorm    (writes profiles/population_train_latency_layernorm.txt)"""
+    python tools/population_train_latency.py --layernorm    (writes profiles/population_train_latency_layernorm.txt)
+
+--wide measures PopulationTrainer(wide=True) on nets the first trainer refuses -- Pendulum 4x1024 ELU with a mixture of 2 (config E's
+net) and CartPole 2x512 ReLU, K in 1,4,16 -- with the losses in PyTorch and on the device against the loop of agent.update calls of
+the same agents, all in one process; with --epoch also train_epoch against train_on_rows on synthetic rows.  The header carries the
+gradient errors of tests/test_population_trainer_wide.py (--grad-errors FILE), the launches per step and the compiler's resource
+report of the wide kernels:
+    python tools/population_train_latency.py --wide [--epoch]    (writes profiles/population_train_latency_wide.txt)"""
 import argparse
 import os
 import subprocess
@@ -171,6 +178,88 @@ def measure_layernorm(name, K, B, reps, warmup):
     return out
 
 
+# --wide: kind, state_dim, actions per row, hidden widths, policy overrides
+WIDE_CONFIGS = {"pendulum_4x1024_gmm2": ("continuous", 3, 8, [1024] * 4, dict(num_components=2)),
+                "cartpole_2x512": ("discrete", 4, 2, [512, 512], {})}
+
+
+def measure_wide(name, K, B, reps, warmup, epoch_rows=0):
+    """(loop of agent.update, wide step with torch losses, with device losses[, train_epoch, train_on_rows]) median ms."""
+    kind, S, A, hidden, over = WIDE_CONFIGS[name]
+    base = run.CONTINUOUS_DEFAULTS if kind == "continuous" else run.DISCRETE_DEFAULTS
+    cfg = run._merge(base, dict(device="cuda", policy=dict(over, hidden_dimensions=hidden)))
+    env = make_game(cfg["game"])
+    stacked = _batches(kind, K, B, S, A)
+    per_net = [tuple(t[k] for t in stacked) for k in range(K)]
+
+    def agents_of():
+        torch.manual_seed(0)
+        return [run.make_agent(kind, cfg, env, tree_id_base=k) for k in range(K)]
+
+    agents = agents_of()
+
+    def loop():
+        for a, b in zip(agents, per_net):
+            a.update(b)
+
+    out = [_median_ms(loop, reps, warmup)]
+    del agents
+    for losses in ("torch", "device"):
+        tr = PT.PopulationTrainer(agents_of(), max_batch=max(512, 2 * B), wide=True, losses=losses)
+        out.append(_median_ms(lambda: tr.update(stacked), reps, warmup))
+        if losses == "device" and epoch_rows:
+            big = _batches(kind, K, epoch_rows, S, A, seed=1)
+            rows = torch.cat([big[0], big[1], big[2], big[3], big[4].unsqueeze(-1)], dim=-1).contiguous()
+            seeds = list(range(K))
+            out.append(_median_ms(lambda: tr.train_epoch(rows, S, A, batch_size=B, shuffle_seeds=seeds), reps, warmup))
+            out.append(_median_ms(lambda: tr.train_on_rows(rows, S, A, batch_size=B, shuffle_seeds=seeds), reps, warmup))
+        tr.close()
+    return out
+
+
+def main_wide(a):
+    lines = ["# tools/population_train_latency.py --wide%s: one minibatch optimiser step of K wide nets (PopulationTrainer(wide=True), RMSprop "
+             "fused into the backward launches), batch %d, one MI355X; median wall ms of %d repetitions after %d warm-up, every row in one process"
+             % (" --epoch" if a.epoch else "", a.batch, a.reps, a.warmup)]
+    if a.grad_errors and os.path.exists(a.grad_errors):
+        lines.append("# gradient errors against float64 autograd, max|g - g64| / max|g64| per parameter tensor (tests/test_population_trainer_wide.py; "
+                     "the bound is the factor times the float32 autograd error):")
+        log = [ln.strip().lstrip(".") for ln in open(a.grad_errors)]
+        lines += ["#   " + ln for ln in log if ln.startswith("grad ")]
+        lines.append("# raw against azg_mlp_eval's raw (bound 1e-5):")
+        lines += ["#   " + ln for ln in log if ln.startswith("forward vs ")]
+        lines.append("# first-step loss dictionary against float64 (test_end_to_end):")
+        lines += ["#   " + ln for ln in log if ln.startswith("wide continuous ")]
+    lines.append("# launches per step of a net with L hidden layers: forward L + 1, loss kernel 1, backward 2 L + 1 (fused RMSprop): 3 L + 3; "
+                 "Adam / grad_clip / grad_norms: + 2 (norm chains, update), + 1 without a norm")
+    for name in a.configs.split(","):
+        L = len(WIDE_CONFIGS[name][3])
+        lines.append(f"#   {name}: {3 * L + 3} launches per step ({3 * L + 5} in the deferred form); an epoch adds one gather launch per "
+                     "minibatch and one loss-sum launch")
+    ru = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "resource_usage.py"), "dispatch_train_wide", "train"],
+                        capture_output=True, text=True)
+    lines.append("# tools/resource_usage.py dispatch_train_wide:")
+    lines += ["#   " + ln for ln in ru.stdout.splitlines()]
+    misses = []
+    for name in a.configs.split(","):
+        lines.append(f"# {name}: loop of K agent.update | PopulationTrainer(wide=True).update | ratio | "
+                     "PopulationTrainer(wide=True, losses='device').update | ratio to the loop"
+                     + (f" | train_epoch of {a.rows} rows per net | train_on_rows | train_on_rows / train_epoch" if a.epoch else ""))
+        for K in [int(k) for k in a.ks.split(",")]:
+            t = measure_wide(name, K, a.batch, a.reps, a.warmup, a.rows if a.epoch else 0)
+            line = (f"  {name} K={K:4d} loop {t[0]:9.3f} ms  wide {t[1]:8.3f} ms  {t[0] / t[1]:7.2f}x  device losses {t[2]:8.3f} ms  "
+                    f"{t[0] / t[2]:7.2f}x")
+            if a.epoch:
+                line += f"  epoch {t[3]:9.3f} ms  train_on_rows {t[4]:9.3f} ms  {t[4] / t[3]:6.2f}x"
+            if t[2] > t[0]:
+                misses.append(f"{name} K={K}: device-loss step {t[2]:.3f} ms against the loop's {t[0]:.3f} ms")
+            lines.append(line)
+            print(line, flush=True)
+    lines.append("# held to: the device-loss step's median must not exceed the loop's at any point measured.  "
+                 + ("Every point holds." if not misses else "MISSED at: " + "; ".join(misses)))
+    return lines
+
+
 def main_layernorm(a):
     lines = ["# tools/population_train_latency.py --layernorm: one minibatch optimiser step of K nets with LayerNorm trunks, batch %d, one "
              "MI355X; median wall ms of %d repetitions after %d warm-up, all four in one process" % (a.batch, a.reps, a.warmup)]
@@ -287,8 +376,18 @@ def main():
     ap.add_argument("--optimizer", choices=["rmsprop", "adam"], default="rmsprop", help="adam (the reference's settings): measure optimizers='agents'")
     ap.add_argument("--grad-clip", type=float, default=0.0, help="a bound > 0: measure optimizers='agents' with gradient clipping")
     ap.add_argument("--layernorm", action="store_true", help="measure PopulationTrainer(layernorm=True) on LayerNorm agents")
+    ap.add_argument("--wide", action="store_true", help="measure PopulationTrainer(wide=True) on 4x1024 and 2x512 nets (with --epoch: an epoch too)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.wide:
+        if a.ks == ap.get_default("ks"):
+            a.ks = "1,4,16"
+        if a.configs == ap.get_default("configs"):
+            a.configs = ",".join(WIDE_CONFIGS)
+        out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "population_train_latency_wide.txt")
+        with open(out, "w") as f:
+            f.write("\n".join(main_wide(a)) + "\n")
+        return
     if a.layernorm:
         out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "population_train_latency_layernorm.txt")
         with open(out, "w") as f:
