@@ -3,6 +3,18 @@
 #include "records.h"
 #include "env.cuh"
 #include "tree.cuh"
+#include "mlp.cuh"
+
+// fn_ids 13 / 14: act4<false> (mlp.cuh: the device-only ELU / ReLU of the register-resident kernels) on in[i], placed in component
+// i & 3 of the vector; the other three components hold fixed bystanders (a positive, a negative, a clamped one and a zero).
+// fn_id 15: tree_div over operand pairs: in[2j] is the numerator and in[2j + 1] the divisor (a positive count) of pair j, and both
+// out[2j] and out[2j + 1] receive the quotient (n must be even; a numerator without a divisor yields 0).
+__device__ __forceinline__ double act4_probe(int act, float x, int comp) {
+    f32x4 v = {3.0f, -0.5f, -100.0f, 0.0f};
+    if (comp == 0) v.x = x; else if (comp == 1) v.y = x; else if (comp == 2) v.z = x; else v.w = x;
+    const f32x4 r = act4<false>(act, v);
+    return (double)(comp == 0 ? r.x : comp == 1 ? r.y : comp == 2 ? r.z : r.w);
+}
 
 __global__ void math_selftest_kernel(int fn_id, const double* in, double* out, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -22,6 +34,9 @@ __global__ void math_selftest_kernel(int fn_id, const double* in, double* out, s
         case 10: out[i] = (double)__builtin_sqrtf((float)x); break;
         case 11: out[i] = x / 3.0; break;
         case 12: out[i] = __builtin_sqrt(x); break;
+        case 13: out[i] = act4_probe(AZG_ACT_ELU, (float)x, (int)(i & 3)); break;
+        case 14: out[i] = act4_probe(AZG_ACT_RELU, (float)x, (int)(i & 3)); break;
+        case 15: out[i] = (i | 1) < n ? tree_div(in[i & ~(size_t)1], in[i | 1]) : 0.0; break;
         default: out[i] = 0.0;
     }
 }

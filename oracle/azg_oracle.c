@@ -1093,6 +1093,9 @@ int azo_math_eval(int fn_id, const double* in, double* out, size_t n) {
             case 10: out[i] = (double)__builtin_sqrtf((float)x); break;
             case 11: out[i] = x / 3.0; break;
             case 12: out[i] = sqrt(x); break;
+            case 13: out[i] = (double)azg_activation(1, (float)x); break;   /* 13-15: the device's act4 (ELU, ReLU) and tree_div (pairs) */
+            case 14: out[i] = (double)((float)x > 0.0f ? (float)x : 0.0f); break;
+            case 15: out[i] = (i | 1) < n ? in[i & ~(size_t)1] / in[i | 1] : 0.0; break;
             default: return AZG_E_INVALID;
         }
     }

@@ -4,6 +4,7 @@ import os
 import numpy as np
 import pytest
 
+import edge_values as E
 import oracle_lib as O
 import parity_util as P
 from alphazero_gym_amd import _capi
@@ -25,6 +26,9 @@ MATH_INPUTS = {
     9: np.linspace(-50, 50, 20001), 10: np.linspace(0, 50, 20001), 11: np.linspace(-50, 50, 20001),
     12: np.concatenate([np.arange(1, 20001, dtype=np.float64), np.linspace(2e4, 2e9, 20001)]),   # sqrt(n + 1) beyond the host table
 }
+# ... and each function's own thresholds with their float32 neighbours, +-0, subnormals, the ends of the documented domains and points
+# far beyond them (edge_values.MATH_EDGES; the host side of the same inputs is held to mpmath in test_math_env_abi.py)
+MATH_INPUTS = {k: np.concatenate([v, E.MATH_EDGES.get(k, np.empty(0))]) for k, v in MATH_INPUTS.items()}
 
 
 @pytest.mark.parametrize("fn_id", sorted(MATH_INPUTS))
@@ -49,6 +53,51 @@ def test_mfma_f32_is_a_k_ordered_fma_chain(native):
         # float32 fma: exact product in float64 (24+24 bits), one rounding after the add (double rounding is vanishingly rare)
         chain = np.float32(np.float64(a[k]) * np.float64(b[k]) + np.float64(chain))
     assert np.float32(dev) == chain, (dev, chain, acc)
+
+
+def _fma_chain(a, b, c):
+    """The float32 fma chain D = fma(a_k, b_k, D) from D = c, subnormals kept: each step exact in float64 (a 48-bit product plus a
+    24-bit addend whose exponents stay within float64's reach) and then rounded once to float32 -- numpy's float64 -> float32
+    conversion rounds to nearest even into the subnormals too.  (Double rounding: the float64 sum is itself rounded only when product and
+    addend are more than 53 bits apart, and then the addend or the product alone decides the float32 result.)"""
+    chain = np.float32(c)
+    for k in range(len(a)):
+        chain = np.float32(np.float64(a[k]) * np.float64(b[k]) + np.float64(chain))
+    return chain
+
+
+MFMA_EDGE_CHAINS = {
+    # products of 1e-20-sized factors: every product (about 1e-40) and every partial sum is subnormal, from a subnormal accumulator
+    "subnormal_products": lambda rng: (rng.uniform(0.5, 2.0, 64) * 1e-20, rng.uniform(-2.0, 2.0, 64) * 1e-20, 3e-41),
+    # normal factors, subnormal products added to a normal accumulator of the smallest binade, and back below it
+    "across_min_normal": lambda rng: (rng.uniform(0.5, 2.0, 64) * 1e-19, rng.uniform(-2.0, 2.0, 64) * 1e-19, -1.2e-38),
+    # subnormal FACTORS (the A / B inputs themselves) against large ones
+    "subnormal_factors": lambda rng: (rng.uniform(0.5, 2.0, 64) * 1e-41, rng.uniform(-2.0, 2.0, 64) * 1e20, 1e-22),
+    # pairs that cancel exactly: the accumulator returns to +0 after every second step and ends there
+    # (12-bit factors: each product is exact in float32, so the second fma of a pair returns exactly +0)
+    "cancels_to_zero": lambda rng: (np.repeat(rng.integers(1, 4096, 32), 2) / 64.0, np.tile([1.0, -1.0], 32) * np.repeat(rng.integers(1, 4096, 32), 2) / 8.0, 0.0),
+}
+
+
+@pytest.mark.parametrize("name", sorted(MFMA_EDGE_CHAINS))
+def test_mfma_chain_keeps_subnormals(native, name):
+    """The k-ordered fma chain with subnormal products, subnormal factors, a subnormal accumulator and exact cancellation: the search
+    kernels are compiled in hipcc's default float mode, in which float32 subnormals are kept (an MFMA never flushes its C input or D
+    output; its A / B inputs follow the kernel's denormal mode like the vector ALU's), so the device's MFMA sums equal the oracle's
+    fmaf chain down to the last subnormal bit.  Nothing else in the suite would notice a flush-to-zero build."""
+    a, b, c = MFMA_EDGE_CHAINS[name](np.random.Generator(np.random.PCG64(3)))
+    a, b, c = a.astype(np.float32), b.astype(np.float32), np.float32(c)
+    want = _fma_chain(a, b, c)
+    tiny = np.finfo(np.float32).tiny
+    if name == "cancels_to_zero":
+        assert want == 0.0 and not np.signbit(want)
+    elif name in ("subnormal_products", "subnormal_factors"):
+        assert (np.abs(a.astype(np.float64) * b.astype(np.float64)) < tiny).all() if name == "subnormal_products" else (np.abs(a) < tiny).all()
+        assert want != 0.0
+    if name == "subnormal_products":
+        assert 0.0 < abs(float(c)) < tiny and abs(float(want)) < tiny          # the flushed result would be 0
+    dev = np.float32(native.math_selftest(100, np.concatenate([a, b, [c]]).astype(np.float64))[0])
+    assert dev.view(np.uint32) == want.view(np.uint32), (name, float(dev), float(want))
 
 
 def _kernel_form(e):
