@@ -71,7 +71,7 @@ __device__ __forceinline__ float tr_dact(int act, float z, float a) {
         case AZG_ACT_LEAKYRELU: return z > 0.0f ? 1.0f : 0.01f;
         case AZG_ACT_RELU6: return (z > 0.0f && z < 6.0f) ? 1.0f : 0.0f;
         case AZG_ACT_SILU: { const float s = 1.0f / (1.0f + azg_expf(-z)); return s * (1.0f + z * (1.0f - s)); }
-        case AZG_ACT_HARDSWISH: return z < -3.0f ? 0.0f : (z <= 3.0f ? z / 3.0f + 0.5f : 1.0f);
+        case AZG_ACT_HARDSWISH: return z <= -3.0f ? 0.0f : (z < 3.0f ? z / 3.0f + 0.5f : 1.0f);   // 0 at -3 and 1 at 3, not -0.5 and 1.5
         default: return z > 0.0f ? 1.0f : 0.0f;
     }
 }
