@@ -113,7 +113,8 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "population_selfplay_begin", "policy_rollout",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
                     "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch",
-                    "trainer_backward_step_opt", "trainer_step_opt", "trainer_epoch_opt", "trainer_create_ex", "trainer_create_wide"]
+                    "trainer_backward_step_opt", "trainer_step_opt", "trainer_epoch_opt", "trainer_create_ex", "trainer_create_wide",
+                    "trainer_create_wide_ex"]
 
 
 class AzgRmsprop(C.Structure):
@@ -251,6 +252,9 @@ def bind(lib, prefix):
         f["trainer_create_ex"].argtypes = [C.c_int32, C.POINTER(AzgMlpDesc), C.c_int32, C.c_int32, C.POINTER(AzgTrainerOptions), C.POINTER(vp)]
     if "trainer_create_wide" in f:
         f["trainer_create_wide"].argtypes = [C.c_int32, C.POINTER(AzgMlpDesc), C.c_int32, C.c_int32, C.POINTER(vp)]
+    if "trainer_create_wide_ex" in f:
+        f["trainer_create_wide_ex"].argtypes = [C.c_int32, C.POINTER(AzgMlpDesc), C.c_int32, C.c_int32, C.POINTER(AzgTrainerOptions),
+                                                C.POINTER(vp)]
     return f
 
 
@@ -740,13 +744,19 @@ class Trainer:
     launches.  Every array argument is a device address (int) of float32 memory on the trainer's GPU, complete when the call is
     made; outputs are complete when it returns.  ``layernorm=True`` creates it with azg_trainer_create_ex, which also takes
     descriptors of LayerNorm trunks (per trunk layer weight, bias, ln.weight, ln.bias in ``params``).  ``wide=True`` creates it with
-    azg_trainer_create_wide: 1-8 hidden layers of widths up to 1024 (no LayerNorm), a launch per layer; every method works the same."""
+    azg_trainer_create_wide: 1-8 hidden layers of widths up to 1024 (no LayerNorm), a launch per layer; every method works the same.
+    ``wide_layernorm=True`` creates it with azg_trainer_create_wide_ex and options.layernorm set: the wide trainer that also takes
+    descriptors of LayerNorm trunks."""
 
-    def __init__(self, fns, desc, n_nets, max_batch, device_id=0, layernorm=False, wide=False):
+    def __init__(self, fns, desc, n_nets, max_batch, device_id=0, layernorm=False, wide=False, wide_layernorm=False):
         if wide and layernorm:
             raise ValueError("Trainer: wide=True does not take LayerNorm trunks (layernorm=True)")
+        if wide_layernorm and layernorm:
+            raise ValueError("Trainer: wide_layernorm=True and layernorm=True ask for two different trainers")
         if "trainer_create" not in fns:
             raise NotImplementedError("this engine library has no azg_trainer_* entry points")
+        if wide_layernorm and "trainer_create_wide_ex" not in fns:
+            raise NotImplementedError("this engine library has no azg_trainer_create_wide_ex")
         if layernorm and "trainer_create_ex" not in fns:
             raise NotImplementedError("this engine library has no azg_trainer_create_ex")
         if wide and "trainer_create_wide" not in fns:
@@ -754,7 +764,10 @@ class Trainer:
         self._f = fns
         self._h = C.c_void_p()
         dref = C.byref(desc) if desc is not None else None
-        if wide:
+        if wide_layernorm:
+            opts = AzgTrainerOptions(C.sizeof(AzgTrainerOptions), 1)
+            rc = fns["trainer_create_wide_ex"](int(device_id), dref, int(n_nets), int(max_batch), C.byref(opts), C.byref(self._h))
+        elif wide:
             rc = fns["trainer_create_wide"](int(device_id), dref, int(n_nets), int(max_batch), C.byref(self._h))
         elif layernorm:
             opts = AzgTrainerOptions(C.sizeof(AzgTrainerOptions), 1)

@@ -136,8 +136,8 @@ class HipEngine(_capi.Engine):
 class HipTrainer(_capi.Trainer):
     """Population trainer on one MI355X (include/azgym_train.h)."""
 
-    def __init__(self, desc, n_nets, max_batch, device_id=0, layernorm=False, wide=False):
-        super().__init__(fns(), desc, n_nets, max_batch, device_id, layernorm=layernorm, wide=wide)
+    def __init__(self, desc, n_nets, max_batch, device_id=0, layernorm=False, wide=False, wide_layernorm=False):
+        super().__init__(fns(), desc, n_nets, max_batch, device_id, layernorm=layernorm, wide=wide, wide_layernorm=wide_layernorm)
 
 
 def math_selftest(fn_id, x, device_id=0):

@@ -257,10 +257,14 @@ class PopulationTrainer:
     ``wide``: True takes every network shape the engine can search: 1-8 hidden layers of widths 16, 32, ... 1024 (narrow agents
     too).  The native trainer is then made by azg_trainer_create_wide, whose kernels spread every layer over the chip, one launch
     per layer and direction; a shape the default trainer also takes gets the same bits.  LayerNorm trunks are not among them:
-    ``wide=True`` with ``layernorm=True`` or with LayerNorm agents raises."""
+    ``wide=True`` with ``layernorm=True`` or with LayerNorm agents raises.
+
+    ``wide_layernorm``: True is the wide trainer that also takes LayerNorm agents (agents without LayerNorm too): the same 8 x 1024
+    limits, checks and behaviour as ``wide=True``, the native trainer made by azg_trainer_create_wide_ex, which adds a row pass per
+    LayerNorm and direction to the wide trainer's launches.  Together with ``layernorm=True`` it raises: two different trainers."""
 
     def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False, losses: str = "torch",
-                 optimizers: str = "rmsprop", layernorm: bool = False, wide: bool = False):
+                 optimizers: str = "rmsprop", layernorm: bool = False, wide: bool = False, wide_layernorm: bool = False):
         if losses not in ("torch", "device"):
             raise ValueError("losses must be 'torch' or 'device'")
         if optimizers not in ("rmsprop", "agents"):
@@ -278,9 +282,12 @@ class PopulationTrainer:
             raise ValueError(f"PopulationTrainer: policy {type(a0.nn).__name__} is not supported")
         self.layernorm = bool(layernorm)
         self.wide = bool(wide)
-        if self.wide and (self.layernorm or any(a.nn.layernorm for a in self.agents)):
+        self.wide_layernorm = bool(wide_layernorm)
+        if self.wide_layernorm and self.layernorm:
+            raise ValueError("PopulationTrainer: wide_layernorm=True and layernorm=True ask for two different trainers")
+        if self.wide and not self.wide_layernorm and (self.layernorm or any(a.nn.layernorm for a in self.agents)):
             raise ValueError("PopulationTrainer: wide=True does not train LayerNorm trunks on the device")
-        if not self.layernorm and any(a.nn.layernorm for a in self.agents):
+        if not self.layernorm and not self.wide_layernorm and any(a.nn.layernorm for a in self.agents):
             raise ValueError("PopulationTrainer: LayerNorm trunks are not trained on the device")
         opt_states: List[List[dict]] = []
         if optimizers == "agents":
@@ -305,7 +312,7 @@ class PopulationTrainer:
                 raise ValueError("PopulationTrainer: every agent must have the same RMSprop settings")
         if len({_loss_settings(a.loss) for a in self.agents}) != 1:
             raise ValueError("PopulationTrainer: every agent must have the same loss class and hyper-parameters")
-        max_layers, max_width = (8, 1024) if self.wide else (3, 256)
+        max_layers, max_width = (8, 1024) if (self.wide or self.wide_layernorm) else (3, 256)
         unsupported = (f"PopulationTrainer: supported nets have 1-{max_layers} hidden layers of widths 16, 32, ... {max_width}, at most "
                        "8 inputs and 16 distribution outputs")
         if any(len(list(a.nn.hidden_dimensions)) > _capi.MAX_HIDDEN for a in self.agents):   # (more than a descriptor holds)
@@ -332,7 +339,9 @@ class PopulationTrainer:
 
         # the native trainer first: if it cannot be created, the agents are left as they were
         self.max_batch = int(max_batch)
-        if self.wide:
+        if self.wide_layernorm:
+            self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0, wide_layernorm=True)
+        elif self.wide:
             self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0, wide=True)
         elif self.layernorm:
             self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0, layernorm=True)

@@ -1,7 +1,7 @@
 // dispatch_train.hip -- the population trainer's C ABI (include/azgym_train.h): scratch, checks and the three launches of train.cuh;
 // azg_trainer_epoch enqueues them for a whole epoch of minibatches behind a gather launch each.  The *_opt entry points take an
 // azg_optim and choose the backward launch's form: fused RMSprop, or gradients first and norm, clip and update after the last layer.
-// A trainer made by azg_trainer_create_wide keeps its dims in `wide` and takes dispatch_train_wide.hip's launches (one per layer and
+// A trainer made by azg_trainer_create_wide(_ex) keeps its dims in `wide` and takes dispatch_train_wide.hip's launches (one per layer and
 // role) wherever a narrow one takes train.cuh's; every check, buffer and synchronisation is the same code.
 #include <cmath>
 #include <cstdint>
@@ -22,7 +22,7 @@ struct azg_trainer {
     float log_std_min = 0.0f, log_std_max = 0.0f;
     bool ln = false;             // the LN = true kernels (a LayerNorm descriptor through azg_trainer_create_ex)
     TrainDimsLN d{};
-    TrainWide* wide = nullptr;   // azg_trainer_create_wide: d then holds only what the host reads (P, NO, nd, in_dim, n_layers)
+    TrainWide* wide = nullptr;   // azg_trainer_create_wide(_ex): d then holds only what the host reads (P, NO, nd, in_dim, n_layers)
     double* norm_part = nullptr; // ... and the deferred norm's partial chains [n_nets][1024]
     float* scratch = nullptr;
     float* grad_buf = nullptr;   // [n_nets][P]: where the deferred backward form keeps the gradients when the caller gives no grads
@@ -154,13 +154,14 @@ int azg_trainer_create_ex(int32_t device_id, const azg_mlp_desc* desc, int32_t n
     return create_impl(device_id, desc, n_nets, max_batch, opts->layernorm != 0, out);
 }
 
-int azg_trainer_create_wide(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, azg_trainer** out) {
-    if (!desc || !out) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide: NULL argument");
+// azg_trainer_create_wide (layernorm_ok = false) and azg_trainer_create_wide_ex, behind their NULL checks
+static int create_wide_impl(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, bool layernorm_ok,
+                            azg_trainer** out) {
     if (desc->struct_size != (int32_t)sizeof(azg_mlp_desc)) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide: azg_mlp_desc.struct_size mismatch");
     if (n_nets < 1 || max_batch < 1) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide: n_nets and max_batch must be at least 1");
     TrainWide* w = nullptr;
     std::string msg;
-    if (int rc = tw_plan(desc, max_batch, &w, &msg)) return tfail(nullptr, rc, msg);
+    if (int rc = tw_plan(desc, max_batch, layernorm_ok, &w, &msg)) return tfail(nullptr, rc, msg);
     azg_trainer* t = new azg_trainer();
     t->wide = w;
     t->device_id = device_id;
@@ -187,6 +188,19 @@ int azg_trainer_create_wide(int32_t device_id, const azg_mlp_desc* desc, int32_t
     }
     *out = t;
     return AZG_OK;
+}
+
+int azg_trainer_create_wide(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, azg_trainer** out) {
+    if (!desc || !out) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide: NULL argument");
+    return create_wide_impl(device_id, desc, n_nets, max_batch, false, out);
+}
+
+int azg_trainer_create_wide_ex(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, const azg_trainer_options* opts,
+                               azg_trainer** out) {
+    if (!desc || !opts || !out) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide_ex: NULL argument");
+    if (opts->struct_size != (int32_t)sizeof(azg_trainer_options))
+        return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide_ex: azg_trainer_options.struct_size mismatch");
+    return create_wide_impl(device_id, desc, n_nets, max_batch, opts->layernorm != 0, out);
 }
 
 // ---- each call in three parts: its checks (nothing launched, nothing written), its launch, and the public entry point ----

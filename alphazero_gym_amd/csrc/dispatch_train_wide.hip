@@ -1,6 +1,7 @@
-// dispatch_train_wide.hip -- the wide trainer (azg_trainer_create_wide): its descriptor checks and layout, and the launches of
-// train_wide.cuh, one per layer and role.  The C ABI itself is dispatch_train.hip's; a wide handle takes these launches where a
-// narrow one takes train.cuh's.
+// dispatch_train_wide.hip -- the wide trainer (azg_trainer_create_wide, azg_trainer_create_wide_ex): its descriptor checks and layout,
+// and the launches of train_wide.cuh, one per layer and role (with LayerNorm: a row pass behind every layer's forward launch and
+// between (a) and (b) of every layer above the first).  The C ABI itself is dispatch_train.hip's; a wide handle takes these launches
+// where a narrow one takes train.cuh's.
 #include <cstdint>
 #include <string>
 
@@ -14,9 +15,9 @@ struct TrainWide {
     TrainDimsW d{};
 };
 
-int tw_plan(const azg_mlp_desc* desc, int32_t max_batch, TrainWide** out, std::string* msg) {
+int tw_plan(const azg_mlp_desc* desc, int32_t max_batch, bool layernorm_ok, TrainWide** out, std::string* msg) {
     auto fail = [&](int code, const char* m) { *msg = std::string("azg_trainer_create_wide: ") + m; return code; };
-    if (desc->layernorm) return fail(AZG_E_UNSUPPORTED, "wide LayerNorm trunks are not trained on the device");
+    if (desc->layernorm && !layernorm_ok) return fail(AZG_E_UNSUPPORTED, "wide LayerNorm trunks are not trained on the device");
     if (desc->n_hidden < 1 || desc->n_hidden > TW_MAX_LAYERS) return fail(AZG_E_UNSUPPORTED, "1 to 8 hidden layers");
     if (desc->in_dim < 1 || desc->in_dim > TR_OBS_LD) return fail(AZG_E_UNSUPPORTED, "in_dim must be 1..8");
     if (desc->n_dist < 1 || desc->n_dist > 16) return fail(AZG_E_UNSUPPORTED, "n_dist must be 1..16");
@@ -27,6 +28,7 @@ int tw_plan(const azg_mlp_desc* desc, int32_t max_batch, TrainWide** out, std::s
     TrainWide* w = new TrainWide();
     TrainDimsW& d = w->d;
     d.n_layers = desc->n_hidden; d.in_dim = desc->in_dim; d.nd = desc->n_dist; d.NO = 1 + desc->n_dist; d.act = desc->activation;
+    d.layernorm = desc->layernorm ? 1 : 0;
     const size_t Bmax = ((size_t)max_batch + 15) / 16 * 16;
     // (at most 8 * 1024 * 1024 + ... parameters: off stays far below 2^31; the scratch offsets are checked as they are laid out)
     int off = 0, prev = d.in_dim;
@@ -37,9 +39,16 @@ int tw_plan(const azg_mlp_desc* desc, int32_t max_batch, TrainWide** out, std::s
         d.H[l] = desc->hidden[l];
         d.offW[l] = off; off += d.H[l] * prev;
         d.offb[l] = off; off += d.H[l];
-        if (so + 2 * Bmax * d.H[l] >= limit) { delete w; return fail(AZG_E_UNSUPPORTED, "max_batch too large"); }
+        if (d.layernorm) { d.offG[l] = off; off += d.H[l]; d.offB[l] = off; off += d.H[l]; }
+        const size_t need = d.layernorm ? 4 * Bmax * d.H[l] + Bmax : 2 * Bmax * d.H[l];
+        if (so + need >= limit) { delete w; return fail(AZG_E_UNSUPPORTED, "max_batch too large"); }
         d.s_A[l] = (unsigned)so; so += Bmax * d.H[l];
         d.s_D[l] = (unsigned)so; so += Bmax * d.H[l];
+        if (d.layernorm) {
+            d.s_X[l] = (unsigned)so; so += Bmax * d.H[l];
+            d.s_G[l] = (unsigned)so; so += Bmax * d.H[l];
+            d.s_R[l] = (unsigned)so; so += Bmax;
+        }
         prev = d.H[l];
     }
     d.offWv = off; off += prev;
@@ -72,6 +81,14 @@ static int strip_blocks(int row_tiles, int cols, int nt) {
 #define TW_BY_NT(nt, CALL) \
     do { if ((nt) == 4) { CALL(4); } else if ((nt) == 2) { CALL(2); } else { CALL(1); } } while (0)
 
+// the row pass of LayerNorm l
+static TwRow row_pass(const TrainDimsW& d, int l) {
+    TwRow rw{};
+    rw.H = d.H[l]; rw.P = d.P; rw.offG = d.offG[l]; rw.offB = d.offB[l];
+    rw.s_A = d.s_A[l]; rw.s_D = d.s_D[l]; rw.s_X = d.s_X[l]; rw.s_G = d.s_G[l]; rw.s_R = d.s_R[l]; rw.per_net = d.per_net;
+    return rw;
+}
+
 void tw_launch_forward(const TrainWide* w, hipStream_t stream, int n_nets, const float* params, const float* obs, int n_rows, float* raw,
                        float* scratch) {
     const TrainDimsW& d = w->d;
@@ -86,6 +103,10 @@ void tw_launch_forward(const TrainWide* w, hipStream_t stream, int n_nets, const
 #define TW_CALL(N) hipLaunchKernelGGL(train_wide_forward_kernel<N>, grid, dim3(TW_THREADS), 0, stream, a, params, obs, n_rows, scratch)
         TW_BY_NT(nt, TW_CALL);
 #undef TW_CALL
+        if (d.layernorm) {
+            const TwRow rw = row_pass(d, l);
+            hipLaunchKernelGGL(train_wide_ln_forward_kernel, dim3(MT, n_nets), dim3(TW_THREADS), 0, stream, rw, params, scratch);
+        }
     }
     TwHead h{};
     h.HL = d.H[d.n_layers - 1]; h.NO = d.NO; h.P = d.P; h.offWv = d.offWv; h.offbv = d.offbv; h.offbd = d.offbd;
@@ -93,30 +114,39 @@ void tw_launch_forward(const TrainWide* w, hipStream_t stream, int n_nets, const
     hipLaunchKernelGGL(train_wide_heads_kernel, dim3(MT, n_nets), dim3(64), 0, stream, h, params, n_rows, raw, scratch);
 }
 
-// The walk from the heads down.  FUSED: opt and square_avg are tr_update's; else the gradients go to grads.
-template <bool FUSED>
+// The walk from the heads down.  FUSED: opt and square_avg are tr_update's; else the gradients go to grads.  LN: the trunk has
+// LayerNorm; per layer above the first (a), the row pass of the LayerNorm below, (b).
+template <bool FUSED, bool LN>
 static void launch_layers(const TrainDimsW& d, hipStream_t stream, int n_nets, const TrainOpt& opt, float* params, const float* d_raw,
                           int n_rows, float* square_avg, float* grads, float* scratch) {
     const int MT = (n_rows + 15) / 16, L = d.n_layers;
     for (int l = L; l >= 0; --l) {
         const bool head = l == L;
-        TwBwd a{};
+        typename TwBwdOf<LN>::type a{};
         a.head = head; a.Hl = head ? d.NO : d.H[l]; a.Hp = l > 0 ? d.H[l - 1] : d.in_dim; a.lda = l > 0 ? a.Hp : TR_OBS_LD; a.NO = d.NO; a.P = d.P;
         a.offW = head ? 0 : d.offW[l]; a.offb = head ? 0 : d.offb[l];
         a.offWv = d.offWv; a.offbv = d.offbv; a.offbd = d.offbd;
         a.s_dZ = head ? 0 : d.s_D[l]; a.s_Dp = l > 0 ? d.s_D[l - 1] : 0; a.s_Ap = l > 0 ? d.s_A[l - 1] : d.s_obs; a.per_net = d.per_net;
+        if constexpr (LN) {
+            if (l > 0) { a.offGp = d.offG[l - 1]; a.offBp = d.offB[l - 1]; a.s_Gp = d.s_G[l - 1]; a.s_Xp = d.s_X[l - 1]; }
+        }
         if (l > 0) {
             const int nt = pick_nt(MT, a.Hp, n_nets);
             const dim3 grid(strip_blocks(MT, a.Hp, nt), n_nets);
-#define TW_CALL(N) hipLaunchKernelGGL(train_wide_backward_a_kernel<N>, grid, dim3(TW_THREADS), 0, stream, a, params, d_raw, n_rows, scratch)
+#define TW_CALL(N) hipLaunchKernelGGL((train_wide_backward_a_kernel<N, LN>), grid, dim3(TW_THREADS), 0, stream, a, params, d_raw, n_rows, scratch)
             TW_BY_NT(nt, TW_CALL);
 #undef TW_CALL
+            if constexpr (LN) {
+                const TwRow rw = row_pass(d, l - 1);
+                hipLaunchKernelGGL(train_wide_ln_backward_kernel, dim3(MT, n_nets), dim3(TW_THREADS), 0, stream, rw, params, scratch);
+            }
         }
         const int MTl = (a.Hl + 15) / 16;
         const int nt = pick_nt(MTl, a.Hp, n_nets);
         a.strip_blocks = strip_blocks(MTl, a.Hp, nt);
-        const dim3 grid(a.strip_blocks + (a.Hl + TW_THREADS - 1) / TW_THREADS, n_nets);
-#define TW_CALL(N) hipLaunchKernelGGL((train_wide_backward_b_kernel<N, FUSED>), grid, dim3(TW_THREADS), 0, stream, a, opt, params, d_raw, \
+        const int ln_blocks = (LN && l > 0) ? 2 * ((a.Hp + TW_THREADS - 1) / TW_THREADS) : 0;   // dgamma, dbeta of LayerNorm l - 1
+        const dim3 grid(a.strip_blocks + (a.Hl + TW_THREADS - 1) / TW_THREADS + ln_blocks, n_nets);
+#define TW_CALL(N) hipLaunchKernelGGL((train_wide_backward_b_kernel<N, FUSED, LN>), grid, dim3(TW_THREADS), 0, stream, a, opt, params, d_raw, \
                                       n_rows, square_avg, grads, scratch)
         TW_BY_NT(nt, TW_CALL);
 #undef TW_CALL
@@ -125,13 +155,15 @@ static void launch_layers(const TrainDimsW& d, hipStream_t stream, int n_nets, c
 
 void tw_launch_backward(const TrainWide* w, hipStream_t stream, int n_nets, const TrainOpt& opt, float* params, const float* d_raw, int n_rows,
                         float* square_avg, float* grads, float* scratch) {
-    launch_layers<true>(w->d, stream, n_nets, opt, params, d_raw, n_rows, square_avg, grads, scratch);
+    if (w->d.layernorm) launch_layers<true, true>(w->d, stream, n_nets, opt, params, d_raw, n_rows, square_avg, grads, scratch);
+    else launch_layers<true, false>(w->d, stream, n_nets, opt, params, d_raw, n_rows, square_avg, grads, scratch);
 }
 
 void tw_launch_backward_deferred(const TrainWide* w, hipStream_t stream, int n_nets, const TrainOptD& opt, float* params, const float* d_raw,
                                  int n_rows, float* state0, float* state1, float* grads, float* norms, float* scratch, double* partials) {
     const TrainDimsW& d = w->d;
-    launch_layers<false>(d, stream, n_nets, opt.rms, params, d_raw, n_rows, nullptr, grads, scratch);
+    if (d.layernorm) launch_layers<false, true>(d, stream, n_nets, opt.rms, params, d_raw, n_rows, nullptr, grads, scratch);
+    else launch_layers<false, false>(d, stream, n_nets, opt.rms, params, d_raw, n_rows, nullptr, grads, scratch);
     if (opt.want_norm)
         hipLaunchKernelGGL(train_wide_norm_kernel, dim3(TW_NORM_CHAINS / 64, n_nets), dim3(64), 0, stream, d.P, grads, partials);
     hipLaunchKernelGGL(train_wide_update_kernel, dim3((d.P + TW_UPDATE_SPAN - 1) / TW_UPDATE_SPAN, n_nets), dim3(TR_BWD_THREADS), 0, stream,

@@ -9,6 +9,15 @@
 // Launches of one step (L hidden layers): forward L + 1 (the layers, the heads); backward 2 L + 1: from the heads down, (a) dZ of
 // the layer below, then (b) dW, db and the optimiser step (or the gradient store) of the layer.  (a) of layer l reads W_l and (b) of
 // layer l rewrites it, in the next launch.  Deferred form: + the norm's partial chains (when a norm is wanted) + the update.
+//
+// LayerNorm trunks (azg_trainer_create_wide_ex; the LN = true instantiations and the two row-pass kernels): train.cuh's LayerNorm
+// arithmetic with a launch where its kernels have a barrier.  Forward 2 L + 1: behind every layer's launch a row pass, sixteen lanes
+// per row running tr_ln_row_forward itself, leaves Y in A's place and X, rstd in arrays of their own.  Backward 3 L + 1: per layer,
+// from the heads down, (a) of layer l stores G = dZ_l W_l; the row pass of LayerNorm l - 1 reads G, gamma, X and rstd and turns D into
+// dZ of the layer below; (b) of layer l also emits dgamma and dbeta of LayerNorm l - 1 from G and X in workgroups beside db's.  In this
+// order gamma of layer l - 1, like W_l, is read in a launch before the one that steps it, and G, X of a layer are written once per
+// step.  A row's sums keep train.cuh's order at every width: lane c of the row's sixteen adds columns c, c + 16, ... in one float64
+// chain (64 links at width 1024), the partials meet in tr_row16_sum, one division by H and one rounding.
 #pragma once
 #include "train.cuh"
 
@@ -17,6 +26,7 @@
 #define TW_WAVES (TW_THREADS / 64)
 #define TW_NORM_CHAINS TR_BWD_THREADS  // the deferred norm's partial chains: train.cuh's one per thread of its workgroup
 #define TW_UPDATE_SPAN 4096            // elements of one net that a workgroup of the update kernel steps
+#define TW_ROW_AHEAD 8                 // links of a lane's row chain whose loads the backward row pass issues ahead of their additions
 
 // The host's description of a wide trainer (TrainDims with 8 layers); a launch gets the slice it needs as one of the structs below.
 struct TrainDimsW {
@@ -27,6 +37,11 @@ struct TrainDimsW {
     int P;
     unsigned s_obs, s_A[TW_MAX_LAYERS], s_D[TW_MAX_LAYERS];
     size_t per_net;
+    // LayerNorm trunks (TrainDimsLN's fields): the flag, ln.weight / ln.bias of the trunk layers, and per layer X_l [Bmax][H_l],
+    // G_l [Bmax][H_l] (d loss / d Y_l) and rstd_l [Bmax]; s_A then holds Y_l
+    int layernorm;
+    int offG[TW_MAX_LAYERS], offB[TW_MAX_LAYERS];
+    unsigned s_X[TW_MAX_LAYERS], s_G[TW_MAX_LAYERS], s_R[TW_MAX_LAYERS];
 };
 
 // the strip of wave `s`: row tile m0, first column n0, nt tiles of the `cols` columns (cols need not be a multiple of 16: dW_0)
@@ -100,6 +115,25 @@ __global__ __launch_bounds__(TW_THREADS) void train_wide_forward_kernel(TwFwd a,
     }
 }
 
+// The row pass of one LayerNorm, forward or backward: H columns, Bpad rows.
+struct TwRow {
+    int H, P;
+    int offG, offB;
+    unsigned s_A, s_D, s_X, s_G, s_R;
+    size_t per_net;
+};
+
+// grid (row tiles, nets): wave w of the workgroup takes rows m0 + 4 w .. m0 + 4 w + 3, sixteen lanes each (padded rows included: a
+// tile's sixteen rows lie below the padded row count together, so all 64 lanes of a wave meet in the butterfly).  A -> Y in place,
+// X and rstd to their arrays: tr_ln_row_forward as train_forward_kernel<true> calls it.
+__global__ __launch_bounds__(TW_THREADS) void train_wide_ln_forward_kernel(TwRow a, const float* params, float* scratch) {
+    const int net = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+    const size_t row = (size_t)blockIdx.x * 16 + 4 * wave + g;
+    const float* p = params + (size_t)net * a.P;
+    float* sc = scratch + (size_t)net * a.per_net;
+    tr_ln_row_forward(a.H, r, sc + a.s_A + row * a.H, sc + a.s_X + row * a.H, sc + a.s_R + row, p + a.offG, p + a.offB);
+}
+
 struct TwHead {
     int HL, NO, P;
     int offWv, offbv, offbd;
@@ -148,11 +182,20 @@ struct TwBwd {
     unsigned s_dZ, s_Dp, s_Ap;
     size_t per_net;
 };
+// The LN = true forms' argument: TwBwd and the LayerNorm below the layer (the LN = false forms keep taking TwBwd itself, so their
+// argument block and their code stay what they were).
+struct TwBwdLN : TwBwd {
+    int offGp, offBp;        // ln.weight, ln.bias of LayerNorm l - 1
+    unsigned s_Gp, s_Xp;     // G_{l-1}, X_{l-1}
+};
+template <bool LN> struct TwBwdOf { typedef TwBwd type; };
+template <> struct TwBwdOf<true> { typedef TwBwdLN type; };
 
 // (a) grid (ceil(row tiles * strips / 4), nets): dZ_{l-1}[row][j] = D_{l-1}[row][j] * sum_u dZ_l[row][u] W_l[u][j]
-template <int NT>
-__global__ __launch_bounds__(TW_THREADS) void train_wide_backward_a_kernel(TwBwd a, const float* params, const float* d_raw, int n_rows,
-                                                                           float* scratch) {
+// LN: G_{l-1}[row][j] = the sum alone (padded rows: dZ_l is 0 there, so their G is 0); the row pass below makes dZ_{l-1} of it.
+template <int NT, bool LN = false>
+__global__ __launch_bounds__(TW_THREADS) void train_wide_backward_a_kernel(typename TwBwdOf<LN>::type a, const float* params,
+                                                                           const float* d_raw, int n_rows, float* scratch) {
     const int net = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
     const int MT = (n_rows + 15) / 16, Hl = a.Hl, Hp = a.Hp, NO = a.NO;
     const int s = blockIdx.x * TW_WAVES + wave;
@@ -183,18 +226,72 @@ __global__ __launch_bounds__(TW_THREADS) void train_wide_backward_a_kernel(TwBwd
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const size_t at = (size_t)(m0 + 4 * g + i) * Hp + n0 + 16 * t + r;
-                Dp[at] = acc[t][i] * Dp[at];
+                if constexpr (LN) sc[a.s_Gp + at] = acc[t][i];
+                else Dp[at] = acc[t][i] * Dp[at];
             }
         }
+    }
+}
+
+// The row pass of LayerNorm l - 1, grid (row tiles, nets), rows to waves as in train_wide_ln_forward_kernel: the loop of
+// train_backward_layers.inc restated, element for element and link for link (m1, m2 float64 chains rounded once; dA float32),
+// D_{l-1} -> dZ_{l-1} in place.
+__global__ __launch_bounds__(TW_THREADS) void train_wide_ln_backward_kernel(TwRow a, const float* params, float* scratch) {
+    const int net = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+    const int Hp = a.H;
+    const size_t row = (size_t)blockIdx.x * 16 + 4 * wave + g;
+    float* sc = scratch + (size_t)net * a.per_net;
+    const float* gam = params + (size_t)net * a.P + a.offG;
+    const float* Gp = sc + a.s_G;
+    const float* Xp = sc + a.s_X;
+    float* Dp = sc + a.s_D;
+    const size_t base = row * Hp;
+    // (a lane's links in the same order, the loads of eight of them issued ahead of their additions: at width 1024 a chain is 64
+    // links, and one load round trip per link is what this launch would otherwise take)
+    double s1 = 0.0, s2 = 0.0;
+    int j = r;
+    for (; j + 16 * (TW_ROW_AHEAD - 1) < Hp; j += 16 * TW_ROW_AHEAD) {
+        float dx[TW_ROW_AHEAD], xv[TW_ROW_AHEAD];
+#pragma unroll
+        for (int q = 0; q < TW_ROW_AHEAD; ++q) { dx[q] = Gp[base + j + 16 * q] * gam[j + 16 * q]; xv[q] = Xp[base + j + 16 * q]; }
+#pragma unroll
+        for (int q = 0; q < TW_ROW_AHEAD; ++q) { s1 = s1 + (double)dx[q]; s2 = s2 + (double)dx[q] * (double)xv[q]; }
+    }
+    for (; j < Hp; j += 16) {
+        const float dx = Gp[base + j] * gam[j];
+        s1 = s1 + (double)dx;
+        s2 = s2 + (double)dx * (double)Xp[base + j];
+    }
+    const float m1 = (float)(tr_row16_sum(s1) / (double)Hp), m2 = (float)(tr_row16_sum(s2) / (double)Hp);
+    const float rstd = sc[a.s_R + row];
+    j = r;
+    for (; j + 16 * (TW_ROW_AHEAD - 1) < Hp; j += 16 * TW_ROW_AHEAD) {
+        float dA[TW_ROW_AHEAD], dv[TW_ROW_AHEAD];
+#pragma unroll
+        for (int q = 0; q < TW_ROW_AHEAD; ++q) {
+            const float dx = Gp[base + j + 16 * q] * gam[j + 16 * q];
+            dA[q] = rstd * ((dx - m1) - Xp[base + j + 16 * q] * m2);
+            dv[q] = Dp[base + j + 16 * q];
+        }
+#pragma unroll
+        for (int q = 0; q < TW_ROW_AHEAD; ++q) Dp[base + j + 16 * q] = dA[q] * dv[q];
+    }
+    for (; j < Hp; j += 16) {
+        const float dx = Gp[base + j] * gam[j];
+        const float dA = rstd * ((dx - m1) - Xp[base + j] * m2);
+        Dp[base + j] = dA * Dp[base + j];
     }
 }
 
 // (b) grid (strip_blocks + ceil(Hl / 256), nets): dW_l[u][j] = sum_row dZ_l[row][u] A_{l-1}[row][j] (the k axis is the batch row) in the
 // first strip_blocks workgroups, db_l[u] one thread per column in the rest.  FUSED: every finished element is stepped by tr_update
 // (and stored to grads when given); else it is stored to grads and no parameter is written.
-template <int NT, bool FUSED>
-__global__ __launch_bounds__(TW_THREADS) void train_wide_backward_b_kernel(TwBwd a, TrainOpt opt, float* params, const float* d_raw, int n_rows,
-                                                                           float* square_avg, float* grads_all, const float* scratch) {
+// LN (layers above the first): behind db's workgroups ceil(Hp / 256) more for dgamma and as many for dbeta of LayerNorm l - 1, one
+// thread per column: the sums over the rows of G X (the products exact in float64) and of G, through tr_colsum into the same emit.
+template <int NT, bool FUSED, bool LN = false>
+__global__ __launch_bounds__(TW_THREADS) void train_wide_backward_b_kernel(typename TwBwdOf<LN>::type a, TrainOpt opt, float* params,
+                                                                           const float* d_raw, int n_rows, float* square_avg,
+                                                                           float* grads_all, const float* scratch) {
     const int net = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
     const int Bpad = (n_rows + 15) / 16 * 16, Hl = a.Hl, Hp = a.Hp, NO = a.NO;
     const bool head = a.head != 0;
@@ -209,6 +306,20 @@ __global__ __launch_bounds__(TW_THREADS) void train_wide_backward_b_kernel(TwBwd
         else grads[idx] = grad;
     };
     if ((int)blockIdx.x >= a.strip_blocks) {
+        if constexpr (LN) {
+            const int nb = (Hl + TW_THREADS - 1) / TW_THREADS, ng = (Hp + TW_THREADS - 1) / TW_THREADS;
+            const int blk = (int)blockIdx.x - a.strip_blocks - nb;
+            if (blk >= 0) {
+                const bool beta = blk >= ng;
+                const int j = (beta ? blk - ng : blk) * TW_THREADS + tid;
+                if (j >= Hp) return;
+                const float* Gq = sc + a.s_Gp;
+                const float* Xq = sc + a.s_Xp;
+                if (beta) emit(a.offBp + j, tr_colsum(Bpad, [&](int row) { return Gq[(size_t)row * Hp + j]; }));
+                else emit(a.offGp + j, tr_colsum(Bpad, [&](int row) { return (double)Gq[(size_t)row * Hp + j] * (double)Xq[(size_t)row * Hp + j]; }));
+                return;
+            }
+        }
         const int u = ((int)blockIdx.x - a.strip_blocks) * TW_THREADS + tid;
         if (u >= Hl) return;
         float gsum;

@@ -11,14 +11,14 @@
 
 struct TrainWide;   // the dims of a wide trainer (train_wide.cuh: TrainDimsW); host memory only
 
-// Checks the descriptor against azg_trainer_create_wide's accepted set and lays out parameters and scratch.  AZG_OK and *out, or a
-// code and *msg (nothing allocated).
-int tw_plan(const azg_mlp_desc* desc, int32_t max_batch, TrainWide** out, std::string* msg);
+// Checks the descriptor against azg_trainer_create_wide's accepted set (layernorm_ok: azg_trainer_create_wide_ex's, which also has
+// LayerNorm trunks) and lays out parameters and scratch.  AZG_OK and *out, or a code and *msg (nothing allocated).
+int tw_plan(const azg_mlp_desc* desc, int32_t max_batch, bool layernorm_ok, TrainWide** out, std::string* msg);
 void tw_free(TrainWide* w);
 int tw_param_count(const TrainWide* w);
 size_t tw_scratch_floats(const TrainWide* w);   // per net
 
-// Enqueue on `stream`: the forward launches; the backward launches with the fused RMSprop step; the backward launches that store the
+// Enqueue on `stream` (a LayerNorm plan: with the row passes): the forward launches; the backward launches with the fused RMSprop step; the backward launches that store the
 // gradients, then norm (partials: [n_nets][1024] float64 of the trainer), clip and update.
 void tw_launch_forward(const TrainWide* w, hipStream_t stream, int n_nets, const float* params, const float* obs, int n_rows, float* raw,
                        float* scratch);

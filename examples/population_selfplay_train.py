@@ -12,7 +12,7 @@ in PyTorch between them); --trainer device-fused computes the losses on the devi
 --layernorm builds every net with LayerNorm after each trunk activation; the device trainers are then built with layernorm=True.
 --wide builds the device trainers with wide=True, which trains nets of up to 8 hidden layers and widths up to 1024 (--hidden 1024
 1024 1024 1024).  The search engine takes a population of more than one net only up to width 256, so a wide run is one seed:
---seeds 0 --hidden 512 272 --wide.
+--seeds 0 --hidden 512 272 --wide.  --wide --layernorm together build them with wide_layernorm=True: wide nets with LayerNorm.
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
@@ -53,9 +53,11 @@ def parse_args(argv=None):
                          "trainers are built with optimizers='agents'")
     ap.add_argument("--grad-clip", type=float, default=0.0, help="clip_grad_norm_ bound of every net's optimiser step (0: off)")
     ap.add_argument("--layernorm", action="store_true",
-                    help="LayerNorm after every trunk activation (the reference's policy.layernorm); the device trainers get layernorm=True")
+                    help="LayerNorm after every trunk activation (the reference's policy.layernorm); the device trainers get layernorm=True "
+                         "(with --wide: wide_layernorm=True)")
     ap.add_argument("--wide", action="store_true",
-                    help="build the device trainers with wide=True: 1-8 hidden layers of widths 16 ... 1024 (no LayerNorm).  One search "
+                    help="build the device trainers with wide=True: 1-8 hidden layers of widths 16 ... 1024 (with --layernorm: "
+                         "wide_layernorm=True, the wide trainer that takes LayerNorm trunks).  One search "
                          "engine cannot hold a population of several nets wider than 256, so use it with one seed (--seeds 0)")
     ap.add_argument("--engine-seed", type=int, default=34, help="the engine's RNG seed (shared; games differ by their global ids)")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
@@ -100,7 +102,8 @@ def train(a, log=print, on_rows=None, on_end=None):
         from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
         trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size), losses="torch" if a.trainer == "device" else "device",
                                     optimizers="agents" if (a.optimizer != "rmsprop" or a.grad_clip) else "rmsprop",
-                                    layernorm=a.layernorm, wide=a.wide)
+                                    layernorm=a.layernorm and not a.wide, wide=a.wide and not a.layernorm,
+                                    wide_layernorm=a.wide and a.layernorm)
     t0 = time.time()
     history = []
     for it in range(a.iters):

@@ -31,6 +31,9 @@
  * azg_trainer_create_wide takes every shape the search engine takes -- 1..AZG_MAX_HIDDEN_LAYERS (8) hidden layers, widths multiples
  * of 16 up to 1024, no LayerNorm -- and spreads every layer over the chip: one launch per layer in the forward pass, two per layer
  * in the backward pass.  A shape both constructors accept gives the same bits from either trainer.
+ * azg_trainer_create_wide_ex with options.layernorm set takes the same shapes with or without LayerNorm after every trunk
+ * activation: with it, 2 * n_hidden + 1 launches forward and 3 * n_hidden + 1 backward (a row pass per LayerNorm and direction), and
+ * for 1..3 layers of width <= 256 the bits of azg_trainer_create_ex's trainer.
  * The arithmetic is float32 on v_mfma_f32_16x16x4_f32 with a fixed summation order and no atomics: the same inputs give the same
  * bits on every run, and net k's results do not depend on n_nets.  Rows are padded to 16 inside; padded rows contribute nothing.
  * The loss kernel computes every row's terms in float64 from the float32 inputs and every sum over the rows as fixed-order float64
@@ -92,6 +95,24 @@ int azg_trainer_create_ex(int32_t device_id, const azg_mlp_desc* desc, int32_t n
  * fused and the deferred form give the same gradients, and for 1..3 layers of width <= 256 every output (raw, gradients, params,
  * optimiser state, grad_norms, d_raw, losses, an epoch's results) has the bits azg_trainer_create's trainer gives. */
 int azg_trainer_create_wide(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, azg_trainer** out);
+
+/* azg_trainer_create_wide with options.  opts->layernorm != 0: everything azg_trainer_create_wide accepts, with desc->layernorm 0 or
+ * 1 (a descriptor without LayerNorm runs exactly the launches of azg_trainer_create_wide's trainer); opts->layernorm == 0: it is
+ * azg_trainer_create_wide, its refusal of a LayerNorm descriptor included.  NULL opts or a wrong opts->struct_size: AZG_E_INVALID;
+ * every other code and message is azg_trainer_create_wide's, *out is untouched on an error and nothing is leaked.  With LayerNorm
+ * the parameters per trunk layer are weight, bias, ln.weight, ln.bias (state_dict order) and P counts them; every entry point works
+ * on the handle unchanged.  The arithmetic is azg_trainer_create_ex's, element for element: a row's sums (the mean, the variance of
+ * the centred values, backward the means of dx = G * gamma and of dx * X) are sixteen float64 chains -- lane c of the row's sixteen
+ * adds columns c, c + 16, ... in order, 64 links at width 1024 -- combined by the same butterfly, divided by the width in float64
+ * and rounded once; dgamma and dbeta are db's four float64 chains over the rows.  So for 1..3 layers of width <= 256 every output
+ * has the bits azg_trainer_create_ex's trainer gives, and at every width the results depend on neither n_nets nor the run.  Where
+ * the one-workgroup kernels have a barrier this trainer has a launch: behind every trunk layer's forward launch a row pass (Y in
+ * A's place, X and rstd kept), 2 * n_hidden + 1 launches forward; backward, per layer above the first, (a) stores G = dZ W, a row
+ * pass of the LayerNorm below turns act' into dZ of the layer below, and (b) also emits that LayerNorm's dgamma and dbeta into the
+ * same optimiser step or gradient store, 3 * n_hidden + 1 launches -- so gamma, like W, is read in a launch before the one that
+ * steps it.  The deferred form's two launches are azg_trainer_create_wide's. */
+int azg_trainer_create_wide_ex(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, const azg_trainer_options* opts,
+                               azg_trainer** out);
 
 /* The forward pass of a minibatch optimiser step (the network half of agents.py:319-392, 539-603: policy.get_train_data's
  * trunk and heads) for every net on its own n_rows rows: one launch.  Writes raw and keeps obs, every layer's activations and

@@ -32,7 +32,12 @@ net) and CartPole 2x512 ReLU, K in 1,4,16 -- with the losses in PyTorch and on t
 the same agents, all in one process; with --epoch also train_epoch against train_on_rows on synthetic rows.  The header carries the
 gradient errors of tests/test_population_trainer_wide.py (--grad-errors FILE), the launches per step and the compiler's resource
 report of the wide kernels:
-    python tools/population_train_latency.py --wide [--epoch]    (writes profiles/population_train_latency_wide.txt)"""
+    python tools/population_train_latency.py --wide [--epoch]    (writes profiles/population_train_latency_wide.txt)
+
+--wide --layernorm measures PopulationTrainer(wide_layernorm=True) on the same nets with LayerNorm trunks (1, 4, 16 of the 4x1024 nets,
+1 ... 256 of the 2x512 ones) against the loop of agent.update calls on those agents, and beside it the same nets without LayerNorm
+on PopulationTrainer(wide=True) from the same run:
+    python tools/population_train_latency.py --wide --layernorm [--epoch]    (writes profiles/population_train_latency_wide_layernorm.txt)"""
 import argparse
 import os
 import subprocess
@@ -183,18 +188,21 @@ WIDE_CONFIGS = {"pendulum_4x1024_gmm2": ("continuous", 3, 8, [1024] * 4, dict(nu
                 "cartpole_2x512": ("discrete", 4, 2, [512, 512], {})}
 
 
-def measure_wide(name, K, B, reps, warmup, epoch_rows=0):
-    """(loop of agent.update, wide step with torch losses, with device losses[, train_epoch, train_on_rows]) median ms."""
+def measure_wide(name, K, B, reps, warmup, epoch_rows=0, layernorm=False):
+    """(loop of agent.update, wide step with torch losses, with device losses[, train_epoch, train_on_rows]) median ms.
+    layernorm: the agents have LayerNorm trunks and the trainer is PopulationTrainer(wide_layernorm=True); the last entry is then the
+    device-loss step of the same nets without LayerNorm on PopulationTrainer(wide=True)."""
     kind, S, A, hidden, over = WIDE_CONFIGS[name]
     base = run.CONTINUOUS_DEFAULTS if kind == "continuous" else run.DISCRETE_DEFAULTS
-    cfg = run._merge(base, dict(device="cuda", policy=dict(over, hidden_dimensions=hidden)))
+    plain_cfg = run._merge(base, dict(device="cuda", policy=dict(over, hidden_dimensions=hidden)))
+    cfg = run._merge(plain_cfg, dict(policy=dict(layernorm=True))) if layernorm else plain_cfg
     env = make_game(cfg["game"])
     stacked = _batches(kind, K, B, S, A)
     per_net = [tuple(t[k] for t in stacked) for k in range(K)]
 
-    def agents_of():
+    def agents_of(c=cfg):
         torch.manual_seed(0)
-        return [run.make_agent(kind, cfg, env, tree_id_base=k) for k in range(K)]
+        return [run.make_agent(kind, c, env, tree_id_base=k) for k in range(K)]
 
     agents = agents_of()
 
@@ -204,8 +212,9 @@ def measure_wide(name, K, B, reps, warmup, epoch_rows=0):
 
     out = [_median_ms(loop, reps, warmup)]
     del agents
+    which = dict(wide_layernorm=True) if layernorm else dict(wide=True)
     for losses in ("torch", "device"):
-        tr = PT.PopulationTrainer(agents_of(), max_batch=max(512, 2 * B), wide=True, losses=losses)
+        tr = PT.PopulationTrainer(agents_of(), max_batch=max(512, 2 * B), losses=losses, **which)
         out.append(_median_ms(lambda: tr.update(stacked), reps, warmup))
         if losses == "device" and epoch_rows:
             big = _batches(kind, K, epoch_rows, S, A, seed=1)
@@ -214,7 +223,40 @@ def measure_wide(name, K, B, reps, warmup, epoch_rows=0):
             out.append(_median_ms(lambda: tr.train_epoch(rows, S, A, batch_size=B, shuffle_seeds=seeds), reps, warmup))
             out.append(_median_ms(lambda: tr.train_on_rows(rows, S, A, batch_size=B, shuffle_seeds=seeds), reps, warmup))
         tr.close()
+    if layernorm:
+        tr = PT.PopulationTrainer(agents_of(plain_cfg), max_batch=max(512, 2 * B), wide=True, losses="device")
+        out.append(_median_ms(lambda: tr.update(stacked), reps, warmup))
+        tr.close()
     return out
+
+
+def main_wide_layernorm(a):
+    lines = ["# tools/population_train_latency.py --wide --layernorm%s: one minibatch optimiser step of K wide nets with LayerNorm trunks "
+             "(PopulationTrainer(wide_layernorm=True), RMSprop fused into the backward launches), batch %d, one MI355X; median wall ms of %d "
+             "repetitions after %d warm-up, every row in one process" % (" --epoch" if a.epoch else "", a.batch, a.reps, a.warmup),
+             "# launches per step of a net with L hidden layers: forward 2 L + 1, loss kernel 1, backward 3 L + 1 (fused RMSprop): 5 L + 3; "
+             "Adam / grad_clip / grad_norms: + 2 (norm chains, update), + 1 without a norm"]
+    misses = []
+    for name in a.configs.split(","):
+        lines.append(f"# {name} with LayerNorm: loop of K agent.update | PopulationTrainer(wide_layernorm=True).update | ratio | "
+                     "PopulationTrainer(wide_layernorm=True, losses='device').update | ratio to the loop"
+                     + (f" | train_epoch of {a.rows} rows per net | train_on_rows" if a.epoch else "")
+                     + " | the same nets without LayerNorm, PopulationTrainer(wide=True, losses='device').update | LayerNorm / plain")
+        ks = a.ks if a.ks else ("1,4,16" if name.startswith("pendulum") else "1,4,16,64,256")
+        for K in [int(k) for k in ks.split(",")]:
+            t = measure_wide(name, K, a.batch, a.reps, a.warmup, a.rows if a.epoch else 0, layernorm=True)
+            line = (f"  {name} K={K:4d} loop {t[0]:9.3f} ms  wide_layernorm {t[1]:8.3f} ms  {t[0] / t[1]:7.2f}x  device losses {t[2]:8.3f} ms  "
+                    f"{t[0] / t[2]:7.2f}x")
+            if a.epoch:
+                line += f"  epoch {t[3]:9.3f} ms  train_on_rows {t[4]:9.3f} ms"
+            line += f"  plain nets {t[-1]:8.3f} ms  {t[2] / t[-1]:6.3f}x"
+            if t[2] > t[0]:
+                misses.append(f"{name} K={K}: device-loss step {t[2]:.3f} ms against the loop's {t[0]:.3f} ms")
+            lines.append(line)
+            print(line, flush=True)
+    lines.append("# held to: the device-loss step's median must not exceed the loop's at any point measured.  "
+                 + ("Every point holds." if not misses else "MISSED at: " + "; ".join(misses)))
+    return lines
 
 
 def main_wide(a):
@@ -379,6 +421,15 @@ def main():
     ap.add_argument("--wide", action="store_true", help="measure PopulationTrainer(wide=True) on 4x1024 and 2x512 nets (with --epoch: an epoch too)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.wide and a.layernorm:
+        a.ks = "" if a.ks == ap.get_default("ks") else a.ks   # (the default: 1, 4, 16 of the 4x1024 nets, 1 ... 256 of the 2x512 ones)
+        if a.configs == ap.get_default("configs"):
+            a.configs = ",".join(WIDE_CONFIGS)
+        out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                    "population_train_latency_wide_layernorm.txt")
+        with open(out, "w") as f:
+            f.write("\n".join(main_wide_layernorm(a)) + "\n")
+        return
     if a.wide:
         if a.ks == ap.get_default("ks"):
             a.ks = "1,4,16"
