@@ -324,6 +324,13 @@ def make_desc(in_dim, hidden, n_dist, activation, log_std_min=-5.0, log_std_max=
     return desc
 
 
+def lockstep_shaped(in_dim, hidden, layernorm=False):
+    """The engine's rule (engine_host.h: azg_lockstep_shaped) for a network it searches as team / per-layer launches: padded width
+    >= 512, at least two hidden layers, no LayerNorm, at most four inputs.  A population of such nets needs a multiple of 32 trees
+    per net (azg_set_net_weights refuses others with AZG_E_UNSUPPORTED); every other shape takes any number."""
+    return -(-max(hidden) // 64) * 64 >= 512 and len(hidden) >= 2 and not layernorm and in_dim <= 4
+
+
 class Engine:
     """One batched MCTS engine (B trees).  Mirrors MCTS*.__init__ kwargs (alphazero/search/mcts.py:316-327, 537-549)."""
 

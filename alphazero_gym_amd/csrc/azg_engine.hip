@@ -51,8 +51,7 @@ static int ls_prepare(azg_engine* e) {
 
 static bool use_lockstep(const azg_engine* e) {
     if (e->opt.force_persistent) return false;
-    if (e->P.in8) return false;   // (more than four network inputs: the lock-step / team kernels' first layer takes one k-step only)
-    return e->HP >= 512 && e->n_hidden >= 2 && !e->P.layernorm;
+    return azg_lockstep_shaped(e->HP, e->n_hidden, e->P.layernorm != 0, e->S_obs);
 }
 
 // One search of all trees on e->stream: the kernels of the engine's family (azg_kernel_env) on its path, by network width.
@@ -342,8 +341,6 @@ int azg_search_resident(azg_engine* e) {
     if (!e->mlp_ready)
         return fail(e, AZG_E_STATE, e->n_nets > 1 ? "azg_set_net_weights has not been called for every net of the population"
                                                  : "azg_set_weights has not been called");
-    if (e->n_nets > 1 && use_lockstep(e))   // (set_weights_impl, engine_weights.hip, refuses these networks; kept as the guard of the one-launch forms)
-        return fail(e, AZG_E_UNSUPPORTED, "populations run on the one-launch search kernel only");
     ON_DEVICE(e);
     e->P.search_idx = e->search_idx;
     e->last_search_idx = e->search_idx;
@@ -565,7 +562,8 @@ static int kernel_name(const azg_engine* e, char* buf, size_t n) {
     switch (r.form) {
         case AZG_FORM_PERSISTENT: return snprintf(buf, n, "search_kernel<%d, %d, %d, %d, %s, %d, %d, %d, %d>", env, e->HP, e->nreg, r.tree_lds, gmm, r.waves, r.groups, r.tile_trees, r.spec);
         case AZG_FORM_PER_LAYER: return snprintf(buf, n, "ls_tree_kernel<%d, ...> + ls_layer0_kernel + ls_hidden_tiled_kernel<%d, ...> per simulation step", env, e->HP);
-        case AZG_FORM_TEAM: return snprintf(buf, n, "ls_team_kernel<%d, %d, %s, %d, %d, %d, %d, %d>", env, e->HP, gmm, r.tree_lds, r.team_kc, r.team_minb, r.spec, r.team_tt);
+        case AZG_FORM_TEAM: return snprintf(buf, n, "ls_team_kernel<%d, %d, %s, %d, %d, %d, %d, %d%s>", env, e->HP, gmm, r.tree_lds, r.team_kc, r.team_minb, r.spec, r.team_tt,
+                                            r.team_pop ? ", true" : "");   // (a population's instantiation: POP)
         default: return snprintf(buf, n, "(no search yet)");
     }
 }

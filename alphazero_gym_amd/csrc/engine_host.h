@@ -42,6 +42,7 @@ struct LaunchRecord {
     int lds_exit = AZG_LDS_NOT_APPLICABLE;    // AZG_LDS_*: why search_kernel's trees were not LDS-resident (azg_tree_storage)
     int waves = 0, groups = 0, tile_trees = 0;   // search_kernel: waves / tree groups per workgroup, trees per group (16, or 8 / 4)
     int team_kc = 0, team_minb = 0, team_tt = 0, team_parts = 0;   // team kernel: chunk length, workgroups per CU, trees per team, launches
+    int team_pop = 0;                         // ... and its population instantiation (team.cuh: POP)
     int timed = 0;                            // the launch recorded ev0 / ev1 itself (hipExtLaunchKernelGGL)
 };
 
@@ -173,6 +174,14 @@ static inline size_t stamp_rows(size_t B) {
 static inline long azg_padded_trees(const azg_engine* e, int tpw) {
     const long T = e->cfg.n_trees / e->n_nets;
     return (long)e->n_nets * ((T + tpw - 1) / tpw * tpw);
+}
+
+// Lock-step shaped: a network an unforced engine searches on the team / per-layer path (padded width HP >= 512, at least two hidden
+// layers, no LayerNorm, at most four inputs -- those kernels' first layer takes one k-step).  Every other wide network runs on the
+// one-launch search kernel.  A population of lock-step shaped nets needs a multiple of 32 trees per net (engine_weights.hip): every
+// 32-tree team, and every tile pair of the per-layer kernels, then belongs to exactly one net (lockstep.cuh: ls_net_wofs).
+static inline bool azg_lockstep_shaped(int HP, int n_hidden, bool layernorm, int in_dim) {
+    return HP >= 512 && n_hidden >= 2 && !layernorm && in_dim <= 4;
 }
 
 // The kernels' environment family, their ENV template argument (env.cuh: EnvFamily): 0 CartPole / MountainCar, 5 Acrobot,

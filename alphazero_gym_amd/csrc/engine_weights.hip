@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void weight_gather_nets_kernel(const unsigned*
     if (i < n) { const unsigned s = src[i]; out[k * n + i] = s ? blob[k * blob_stride + s - 1] : 0.0f; }
 }
 
-// KParams' weight pointers: net 0's tensors in the engine's weight buffer (the search kernel adds net_wstride per net)
+// KParams' weight pointers: net 0's tensors in the engine's weight buffer (the kernels add net_wstride per net)
 static void bind_weights(azg_engine* e, const WeightMap& m, const azg_mlp_desc* d) {
     const float* wb = e->d_wblob;
     e->P.net_wstride = e->n_nets > 1 ? m.src.size() : 0;
@@ -225,9 +225,12 @@ static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* b
     bool others = false;   // a net of the population that keeps its weights already has some: they fix the descriptor
     for (int k = 0; k < NN; ++k) others = others || ((k < net || k >= net + n_write) && e->net_have[k]);
     if (NN > 1) {
-        if (HP >= 512)
-            return fail(e, AZG_E_UNSUPPORTED, "populations: networks wider than 256 (padded) run as team / per-layer searches, which take one "
-                                              "network per engine");
+        // decided by the descriptor alone, AZG_FORCE_PERSISTENT or not; the other wide shapes (LayerNorm, one hidden layer, more than
+        // four inputs) run on the one-launch search kernel, any number of trees per net
+        const int T = e->cfg.n_trees / NN;
+        if (azg_lockstep_shaped(HP, d->n_hidden, d->layernorm != 0, d->in_dim) && T % 32 != 0)
+            return fail(e, AZG_E_UNSUPPORTED, "populations of team / per-layer networks (padded width >= 512) need a multiple of 32 trees per net (got " +
+                                              std::to_string(T) + "): a 32-tree team serves one net");
         if (others && !(e->wmap.valid && e->wmap.HP == HP && same_desc(e->wmap.desc, *d) && d->activation == e->wmap.desc.activation &&
                         d->num_components == e->wmap.desc.num_components && d->log_std_min == e->wmap.desc.log_std_min &&
                         d->log_std_max == e->wmap.desc.log_std_max))

@@ -15,9 +15,25 @@
 #include "tree.cuh"
 #include "tree_phases.cuh"
 
+// Populations (azg_set_population): net k owns trees k * net_T .. k * net_T + net_T - 1, and on these paths net_T is a multiple of 32
+// (engine_weights.hip), so every 16-tree group, 32-tree tile pair and team belongs to ONE net: the one of its first tree.  Its tensors
+// sit ls_net_wofs floats past net 0's (mlp.cuh: net_ptr).  The offset is uniform over the workgroup and constant for the launch: taken
+// once at kernel entry, never inside a loop.  The buffers' padding groups (ls_prepare) lie beyond the last tree: clamped to the last net.
+// POP (a template argument of every kernel here, false by default): the population forms.  The one-net kernels are compiled without
+// the offset -- as a run-time value it cost the team kernels 1-9 VGPRs, up to 10 more spilled SGPRs and, in one instantiation, a
+// resident wave per SIMD (profiles/population_wide_resource_usage.txt) -- and are the code they were before populations ran here.
+template <bool POP>
+__device__ __forceinline__ size_t ls_net_wofs(const KParams& P, int tg) {
+    if constexpr (!POP) return 0;
+    else {
+        const int t = tg * TREES_PER_WG;
+        return (size_t)((t < P.B ? t : P.B - 1) / P.net_T) * P.net_wstride;
+    }
+}
+
 // g_base = first tree group of the launch.  (Measured and removed, HISTORY.md: the earlier 16-tree x 256-unit weight-streaming layer
 // kernel; the first layer in this kernel's tail, +3.6 % time; the batch cut into pipelines on several streams, +6 % / +40 %.)
-template <int ENV, bool GMM, int NCH, int HP>
+template <int ENV, bool GMM, int NCH, int HP, bool POP = false>
 __global__ __launch_bounds__(256) void ls_tree_kernel(KParams P, LockStep L, int sim, int g_base) {
     constexpr bool CONT = EnvFamily<ENV>::CONT;
     extern __shared__ double s_dyn[];   // sqrt_tab [tab_n], pw_need [n_sims+2]
@@ -53,7 +69,7 @@ __global__ __launch_bounds__(256) void ls_tree_kernel(KParams P, LockStep L, int
         st.nrec = t.nrec; st.eps_draws = t.eps_draws; st.leaf = t.leaf; st.need_eval = live && t.need_eval; st.path_D = t.path_D;
         st.kbase = t.kbase; st.my_depth = ln.my_depth; st.pid = ln.pid; st.pr = ln.pr; st.pW = ln.pW; st.eps_c = ln.eps_c;
         if (live) tree_phase_a<ENV, TS_GLOBAL, GMM, NCH>(P, st, ts, cold, edge_W, action, tb, sim, sub, tl, gtree,
-                                                     L.parts + (size_t)tg * NCH * 64, P.bhead, s_sqrt STAMP_ARG, s_pw);
+                                                     L.parts + (size_t)tg * NCH * 64, P.bhead + ls_net_wofs<POP>(P, tg), s_sqrt STAMP_ARG, s_pw);
         st.need_eval = false;
         if (sim < P.n_sims - 1) {
             __threadfence_block();
@@ -76,17 +92,20 @@ __global__ __launch_bounds__(256) void ls_tree_kernel(KParams P, LockStep L, int
     }
 }
 
-template <int HP>
+template <int HP, bool POP = false>
 __global__ __launch_bounds__(256) void ls_layer0_kernel(KParams P, LockStep L, int g_base) {
     constexpr int NS = HP / 256;
     const int tg = g_base + blockIdx.x / NS, sl = blockIdx.x % NS;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float b = L.obsT[(size_t)tg * 64 + lane];
+    const size_t wofs = ls_net_wofs<POP>(P, tg);
+    const float* W0 = P.W0 + wofs;
+    const f32x4* b0 = net_ptr(P.b0, wofs);
     f32x4* out = L.act[0] + (size_t)tg * (HP / 16) * 64;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int tile = sl * 16 + wave * 4 + i;
-        f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(P.W0[tile * 64 + lane], b, P.b0[tile * 64 + lane], 0, 0, 0);
+        f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(W0[tile * 64 + lane], b, b0[tile * 64 + lane], 0, 0, 0);
         out[tile * 64 + lane] = act4<true>(P.act, acc);
     }
 }
@@ -168,7 +187,7 @@ struct TileMem {
 // under the wait: 13.38 against 13.23 ms per search at 1024 trees on one box, 24.17 against 24.25 ms at 2048 -- the registers that hold
 // the requested weights through the wait cost more than the round trip; not kept.)
 template <int HP, bool LAST, int TG, int UT, bool SC1, int KC_ = LS_KC, int DBG = 0>
-__device__ __forceinline__ void ls_tile(const KParams& P, const LockStep& L, int layer, int in_buf, int us, int g0, f32x4* s_ab, bool wt = true) {
+__device__ __forceinline__ void ls_tile(const KParams& P, const LockStep& L, int layer, int in_buf, int us, int g0, f32x4* s_ab, bool wt = true, size_t wofs = 0) {
     static_assert(!LAST || UT == 4, "a head chunk is 4 tiles");
     static_assert(TG == 4 || TG == 2, "4 waves: one or two per tree group");
     constexpr int WPG = 4 / TG;            // waves per tree group
@@ -183,7 +202,9 @@ __device__ __forceinline__ void ls_tile(const KParams& P, const LockStep& L, int
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int t0 = us * UT;                          // the UT output tiles
     const int wg = wave % TG, wt0 = (wave / TG) * WT;   // this wave: tree group g0 + wg, tiles t0 + wt0 .. + WT
-    const f32x4* W = P.Wl[layer - 1];
+    const f32x4* W = net_ptr(P.Wl[layer - 1], wofs);   // (wofs: the net of these tree groups, ls_net_wofs)
+    const f32x4* bias = net_ptr(P.bl[layer - 1], wofs);
+    const f32x4* Whead = net_ptr(P.Whead, wofs);
     const TileMem<SC1> in(L.act[in_buf]), out(L.act[in_buf ^ 1], wt), parts(L.parts, wt);
     f32x4 ra[NLA], rb[NLB];
     // piece j of a chunk's staging: NLA float4 of the weights, then NLB of the activations, per thread
@@ -210,7 +231,7 @@ __device__ __forceinline__ void ls_tile(const KParams& P, const LockStep& L, int
     };
     f32x4 acc[WT];   // bias first: store_chunk's wait for the chunk then covers it
 #pragma unroll
-    for (int i = 0; i < WT; ++i) acc[i] = P.bl[layer - 1][(t0 + wt0 + i) * 64 + lane];
+    for (int i = 0; i < WT; ++i) acc[i] = bias[(t0 + wt0 + i) * 64 + lane];
     load_chunk(0);
     store_chunk(0);
     if (PIPE >= 2 && NCHUNK > 1) load_chunk(1);
@@ -367,19 +388,19 @@ __device__ __forceinline__ void ls_tile(const KParams& P, const LockStep& L, int
             // (all MFMA reads of the stages are behind the loop's last barrier)
             if (wt0 == 0) {
 #pragma unroll
-                for (int i = 0; i < WT; ++i) hs = mfma4(P.Whead[(t0 + i) * 64 + lane], h[i], hs);
+                for (int i = 0; i < WT; ++i) hs = mfma4(Whead[(t0 + i) * 64 + lane], h[i], hs);
                 s_ab[wg * 64 + lane] = hs;
             }
             __syncthreads();
             if (wt0 != 0) {
                 hs = s_ab[wg * 64 + lane];
 #pragma unroll
-                for (int i = 0; i < WT; ++i) hs = mfma4(P.Whead[(t0 + wt0 + i) * 64 + lane], h[i], hs);
+                for (int i = 0; i < WT; ++i) hs = mfma4(Whead[(t0 + wt0 + i) * 64 + lane], h[i], hs);
                 parts.store4(((size_t)tg * NU + us) * 64 + lane, hs);
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) hs = mfma4(P.Whead[(t0 + i) * 64 + lane], h[i], hs);
+            for (int i = 0; i < 4; ++i) hs = mfma4(Whead[(t0 + i) * 64 + lane], h[i], hs);
             parts.store4(((size_t)tg * NU + us) * 64 + lane, hs);
         }
     }
@@ -394,7 +415,7 @@ __device__ __forceinline__ void ls_tile(const KParams& P, const LockStep& L, int
 // Schedule: ls_tile's number 4 (barrier in front of the chunk's last k-block, the next chunk's first operands behind it).
 // s_b: two stages of TG * KC * 64 float4.
 template <int HP, bool LAST, int TG, bool SC1, int KC>
-__device__ __forceinline__ void ls_tile_wd(const KParams& P, const LockStep& L, int layer, int in_buf, int us, int g0, f32x4* s_b, bool wt = true) {
+__device__ __forceinline__ void ls_tile_wd(const KParams& P, const LockStep& L, int layer, int in_buf, int us, int g0, f32x4* s_b, bool wt = true, size_t wofs = 0) {
     constexpr int S4 = HP / 16, NU = HP / 64, NCHUNK = S4 / KC;
     constexpr int BSZ = TG * KC * 64;                 // float4 entries of a stage: [TG groups][KC][64]
     constexpr int NLB = BSZ / 256;                    // float4 of the activations per thread per chunk
@@ -402,7 +423,7 @@ __device__ __forceinline__ void ls_tile_wd(const KParams& P, const LockStep& L, 
     static_assert(KC >= 2 && 4 * (KC - 1) >= NLB, "the staging pieces are dealt out over the first KC - 1 k-blocks");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tile = us * 4 + wave;                   // this wave's unit tile
-    const f32x4* W = P.Wl[layer - 1] + (size_t)tile * S4 * 64 + lane;   // k-block kb of it: W[kb * 64]
+    const f32x4* W = net_ptr(P.Wl[layer - 1], wofs) + (size_t)tile * S4 * 64 + lane;   // k-block kb of it: W[kb * 64]
     // (timing experiment, round 5: the activations through the L2 with plain loads -- stale data, wrong results -- 13.68 against 12.78 ms:
     // they push the slices' weights out of the XCD's L2; the sc1 loads around it are the faster way as well as the coherent one)
     const TileMem<SC1> in(L.act[in_buf]), out(L.act[in_buf ^ 1], wt), parts(L.parts, wt);
@@ -415,9 +436,9 @@ __device__ __forceinline__ void ls_tile_wd(const KParams& P, const LockStep& L, 
     auto store_b = [&](int st, int j) { s_b[st * BSZ + j * 256 + tid] = rb[j]; };
     f32x4 acc[TG];
 #pragma unroll
-    for (int g = 0; g < TG; ++g) acc[g] = P.bl[layer - 1][tile * 64 + lane];
+    for (int g = 0; g < TG; ++g) acc[g] = net_ptr(P.bl[layer - 1], wofs)[tile * 64 + lane];
     f32x4 whead = {0.0f, 0.0f, 0.0f, 0.0f};          // (last layer: this tile's head weights, requested here -- the head chain runs from
-    if constexpr (LAST) whead = P.Whead[tile * 64 + lane];   // wave to wave, a round trip to L2 in each link would be four in a row)
+    if constexpr (LAST) whead = net_ptr(P.Whead, wofs)[tile * 64 + lane];   // wave to wave, a round trip to L2 in each link would be four in a row)
 #pragma unroll
     for (int s = 0; s < KC; ++s) aw[0][s] = W[s * 64];
 #pragma unroll
@@ -514,7 +535,7 @@ __device__ __forceinline__ void ls_tile_wd(const KParams& P, const LockStep& L, 
 }
 
 // A hidden->hidden layer as a launch of its own: one tile per workgroup.
-template <int HP, bool LAST, int TG, int UT>
+template <int HP, bool LAST, int TG, int UT, bool POP = false>
 __global__ __launch_bounds__(256) void ls_hidden_tiled_kernel(KParams P, LockStep L, int layer, int in_buf, int TQ, int g_base) {
     constexpr int NU = HP / (16 * UT);
     extern __shared__ f32x4 s_ab[];                        // two stages
@@ -534,6 +555,8 @@ __global__ __launch_bounds__(256) void ls_hidden_tiled_kernel(KParams P, LockSte
         if (nb % 8 == 0) m = (blockIdx.x % 8) * (nb / 8) + blockIdx.x / 8;
         us = m / TQ; tq = m % TQ;
     }
-    if constexpr (LS_LAYER_WD && UT == 4) ls_tile_wd<HP, LAST, TG, false, LS_LAYER_KC>(P, L, layer, in_buf, us, g_base + tq * TG, s_ab);
-    else ls_tile<HP, LAST, TG, UT, false>(P, L, layer, in_buf, us, g_base + tq * TG, s_ab);
+    const int g0 = g_base + tq * TG;
+    static_assert(!POP || TG * TREES_PER_WG <= 32, "a tile's tree groups belong to one net of a population: 32 trees at most");
+    if constexpr (LS_LAYER_WD && UT == 4) ls_tile_wd<HP, LAST, TG, false, LS_LAYER_KC>(P, L, layer, in_buf, us, g0, s_ab, true, ls_net_wofs<POP>(P, g0));
+    else ls_tile<HP, LAST, TG, UT, false>(P, L, layer, in_buf, us, g0, s_ab, true, ls_net_wofs<POP>(P, g0));
 }

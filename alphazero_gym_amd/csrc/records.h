@@ -123,6 +123,7 @@ struct KParams {
     unsigned long long* stamps; // diagnostic build only (-DAZG_STAMPS): [grid][8] cycle sums per phase
     // populations (azg_set_population): net k searches trees k*net_T .. k*net_T+net_T-1 in net_wgs workgroups of its own (the last
     // one padded) with the weights at net_wstride * k floats past the tensors above.  One net: net_T = B, net_wgs = the grid, 0.
+    // (The team / per-layer kernels do not pad: there net_T is a multiple of 32 and a team's net is its first tree / net_T, lockstep.cuh.)
     int net_T, net_wgs;
     size_t net_wstride;
 };

@@ -132,12 +132,14 @@ __device__ __forceinline__ bool team_wait(const unsigned* c, unsigned target, co
 // SPEC: compile-time knowledge about run-time parameters for the tree phases (tree_phases.cuh: Spec<>; 0 = the general code).
 // TT: trees of a team, 32 or 64 (TGN = 2 or 4 tree groups: the tile is TT trees x 64 units; 64 halves the weight bytes staged per
 // MFMA and the barriers per MFMA, and needs twice the batch for the same number of workgroups).
-template <int ENV, int HP, bool GMM, int TLDS, int KC = LS_KC, int MINB = 2, int SPEC = 0, int TT = 32>
+// POP: the population form (lockstep.cuh: ls_net_wofs) -- the team's net's weights; 32-tree teams only, so that a team serves one net.
+template <int ENV, int HP, bool GMM, int TLDS, int KC = LS_KC, int MINB = 2, int SPEC = 0, int TT = 32, bool POP = false>
 __global__ __launch_bounds__(256, MINB) void ls_team_kernel(KParams P, LockStep L, TeamCtl T, int TQ, int g_base) {
     constexpr bool CONT = EnvFamily<ENV>::CONT;
     constexpr int NU = HP / 64, NCH = HP / 64, TGN = TT / 16;
     constexpr int TPW = TT / NU;        // trees a workgroup owns: 16 lanes each, the first 16 * TPW lanes of wave 0
     static_assert(TT == 32 || TT == 64, "a team is two or four 16-tree groups");
+    static_assert(!POP || TT == 32, "a population's nets have a multiple of 32 trees: a 64-tree team could straddle two nets");
     static_assert(TPW >= 1 && TPW <= 4, "a team is TT trees over HP/64 workgroups");
     typedef typename TreeStore<TLDS>::Rec Rec;
     extern __shared__ f32x4 s_ab[];     // the tile routine's two stages (between tiles: the head partials of this workgroup's
@@ -164,6 +166,8 @@ __global__ __launch_bounds__(256, MINB) void ls_team_kernel(KParams P, LockStep 
     const int g0 = g_base + TGN * tq;                        // the team's tree groups g0 .. g0 + TGN - 1
     unsigned* cnt = T.cnt + (size_t)(g0 / 2) * TEAM_MAX_CNT * TEAM_CNT_STRIDE;   // (one block of counters per 32 trees: a 64-tree team uses every other one)
     const int n_layers = P.n_hidden - 1;                     // hidden->hidden layers 1 .. n_layers
+    // populations: a 32-tree team belongs to one net (lockstep.cuh: ls_net_wofs), whose weights it reads for the whole search
+    const size_t wofs = ls_net_wofs<POP>(P, g0);
 
     // ---- this workgroup's trees
     const int tj = lane >> 4;                                // tree slot of the lane
@@ -235,8 +239,9 @@ __global__ __launch_bounds__(256, MINB) void ls_team_kernel(KParams P, LockStep 
 #pragma unroll
         for (int h = 0; h < UPT / 4; ++h) {
             const int u = u0 + 4 * h;
-            f32x4 acc = P.b0u[u / 4];
-            const f32x4 wa = P.W0u[u], wb = P.W0u[u + 1], wc = P.W0u[u + 2], wd = P.W0u[u + 3];
+            f32x4 acc = net_ptr(P.b0u, wofs)[u / 4];
+            const f32x4* W0u = net_ptr(P.W0u, wofs);
+            const f32x4 wa = W0u[u], wb = W0u[u + 1], wc = W0u[u + 2], wd = W0u[u + 3];
             acc.x = __builtin_fmaf(wa.x, x0, acc.x); acc.x = __builtin_fmaf(wa.y, x1, acc.x); acc.x = __builtin_fmaf(wa.z, x2, acc.x); acc.x = __builtin_fmaf(wa.w, x3, acc.x);
             acc.y = __builtin_fmaf(wb.x, x0, acc.y); acc.y = __builtin_fmaf(wb.y, x1, acc.y); acc.y = __builtin_fmaf(wb.z, x2, acc.y); acc.y = __builtin_fmaf(wb.w, x3, acc.y);
             acc.z = __builtin_fmaf(wc.x, x0, acc.z); acc.z = __builtin_fmaf(wc.y, x1, acc.z); acc.z = __builtin_fmaf(wc.z, x2, acc.z); acc.z = __builtin_fmaf(wc.w, x3, acc.z);
@@ -285,11 +290,11 @@ __global__ __launch_bounds__(256, MINB) void ls_team_kernel(KParams P, LockStep 
             const int in_buf = (l - 1) & 1;
             TSTAMP(ta);
 #if TEAM_WD
-            if (l == n_layers) ls_tile_wd<HP, true, TGN, true, KC>(P, L, l, in_buf, us, g0, s_ab, wt);
-            else ls_tile_wd<HP, false, TGN, true, KC>(P, L, l, in_buf, us, g0, s_ab, wt);
+            if (l == n_layers) ls_tile_wd<HP, true, TGN, true, KC>(P, L, l, in_buf, us, g0, s_ab, wt, wofs);
+            else ls_tile_wd<HP, false, TGN, true, KC>(P, L, l, in_buf, us, g0, s_ab, wt, wofs);
 #else
-            if (l == n_layers) ls_tile<HP, true, TGN, 4, true, KC, TEAM_TILE_DBG>(P, L, l, in_buf, us, g0, s_ab, wt);
-            else ls_tile<HP, false, TGN, 4, true, KC, TEAM_TILE_DBG>(P, L, l, in_buf, us, g0, s_ab, wt);
+            if (l == n_layers) ls_tile<HP, true, TGN, 4, true, KC, TEAM_TILE_DBG>(P, L, l, in_buf, us, g0, s_ab, wt, wofs);
+            else ls_tile<HP, false, TGN, 4, true, KC, TEAM_TILE_DBG>(P, L, l, in_buf, us, g0, s_ab, wt, wofs);
 #endif
             TSTAMP(tb_);
             team_arrive(cnt + l * TEAM_CNT_STRIDE);
@@ -309,7 +314,7 @@ __global__ __launch_bounds__(256, MINB) void ls_team_kernel(KParams P, LockStep 
         __syncthreads();
         TSTAMP(tp0);
         __builtin_amdgcn_s_setprio(3);   // the walking wave ahead of the other workgroups' MFMA waves on its SIMD (-0.7 % per search)
-        if (live) tree_phase_a<ENV, TLDS, GMM, NCH, 64, false, SPEC>(P, st, ts, cold, edge_W, action, tb, sim, sub, tj, gtree, s_ab, P.bhead, s_sqrt STAMP_ARG, s_pw);
+        if (live) tree_phase_a<ENV, TLDS, GMM, NCH, 64, false, SPEC>(P, st, ts, cold, edge_W, action, tb, sim, sub, tj, gtree, s_ab, P.bhead + wofs, s_sqrt STAMP_ARG, s_pw);
         st.need_eval = false;
         TSTAMP(tp1);
         if constexpr (BDEF) { if (k == 0 && live) eps_prepare(P, st, gtree, sub); }   // (no tree_phase_b2 in front of the first trace)

@@ -18,8 +18,8 @@
 
 // One variant: hipErrorNotReady when its workgroups cannot all be resident at once (or the shape is not its).
 // wider_form_exists: a form built for more workgroups per CU follows for this shape, so this one takes batches of up to MINB per CU only;
-// otherwise it takes whatever the occupancy query allows (up to 6).  dry: check only, launch nothing.
-template <int ENV, int HP, bool GMM, int TLDS, int KC, int MINB, int SPEC = 0, int TT = 32>
+// otherwise it takes whatever the occupancy query allows (up to 6).  dry: check only, launch nothing.  POP: the population form.
+template <int ENV, int HP, bool GMM, int TLDS, int KC, int MINB, int SPEC = 0, int TT = 32, bool POP = false>
 static hipError_t team_launch_form(azg_engine* e, bool wider_form_exists, int g_base, int G, bool dry = false) {
     constexpr int NU = HP / 64, TPW = TT / NU, TGN = TT / 16;
     constexpr bool CONT = EnvFamily<ENV>::CONT;
@@ -28,7 +28,7 @@ static hipError_t team_launch_form(azg_engine* e, bool wider_form_exists, int g_
     const bool lds_cold = TEAM_LDS_COLD && HP == 1024 && TT == 32 && MINB == 2 && TLDS == TS_LDS8;
     const size_t lds = team_tree_off(e->tab_n, e->cfg.n_sims, KC, TGN) + (size_t)TPW * (team_tree_bytes(e->R, CONT, TLDS) + (lds_cold ? team_cold_bytes(e->R) : 0));
     if ((lds + 1024) * MINB > 160 * 1024) return hipErrorNotReady;
-    auto kern = ls_team_kernel<ENV, HP, GMM, TLDS, KC, MINB, SPEC, TT>;
+    auto kern = ls_team_kernel<ENV, HP, GMM, TLDS, KC, MINB, SPEC, TT, POP>;
     static KernelAttrs attrs;
     int per_cu = 0;
     hipError_t rc = attrs.occupancy(e, (const void*)kern, 256, lds, &per_cu);
@@ -50,7 +50,7 @@ static hipError_t team_launch_form(azg_engine* e, bool wider_form_exists, int g_
     e->team_pending = 1;
     LaunchRecord& r = e->last;
     r.form = AZG_FORM_TEAM; r.tree_lds = TLDS; r.spec = SPEC;
-    r.team_kc = KC; r.team_minb = MINB; r.team_tt = TT;
+    r.team_kc = KC; r.team_minb = MINB; r.team_tt = TT; r.team_pop = POP ? 1 : 0;
     return hipGetLastError();
 }
 
@@ -62,9 +62,17 @@ static hipError_t team_launch_form(azg_engine* e, bool wider_form_exists, int g_
 //   <= 3 of those per CU (3072 trees)                                                                                      32.9 ms (0.75; per-layer
 //        launches: 38.2 ms)
 // AZG_TEAM_WIDE=0: the first form only; AZG_TEAM_TT=32 / 64: only teams of that size (A/B runs).
+// A population (azg_set_population; 32 trees per net or a multiple, so that a team serves one net) takes the base form only, in its
+// population instantiation: 32-tree teams, two per CU, the general tree phases, trees in LDS with 8-bit ids or in global memory (trees
+// of 256 .. 511 records: global).  No three-per-CU forms, no 64-tree teams -- they could straddle two nets --, no two-part launches: a
+// batch the base form cannot hold resident is the per-layer launches'.
 template <int ENV, int HP, bool GMM, int TLDS>
 static hipError_t team_launch_part(azg_engine* e, int g_base, int G, bool dry = false) {
     constexpr bool WIDE = HP == 1024 && !GMM && TLDS == TS_LDS8 && ENV == AZG_ENV_PENDULUM_V1;
+    if (e->n_nets > 1) {
+        if constexpr (TLDS == TS_LDS9) return hipErrorNotReady;
+        else return team_launch_form<ENV, HP, GMM, TLDS, TEAM_KC32, 2, 0, 32, true>(e, false, g_base, G, dry);
+    }
     if constexpr (!WIDE) return team_launch_form<ENV, HP, GMM, TLDS, TEAM_KC32, 2>(e, false, g_base, G, dry);
     else {
         // (the BASELINE shape's tree phases compiled for the common parameter set -- dispatch.cuh: SPEC --; AZG_NO_SPEC=1: the general kernel)
@@ -105,7 +113,7 @@ static hipError_t team_launch(azg_engine* e) {
     const int G = (e->cfg.n_trees + TREES_PER_WG - 1) / TREES_PER_WG;
     const int G_MAX = 3 * e->n_cus / (HP / 64) * 4;                      // 64-tree teams, three workgroups on every CU
     e->last.team_parts = 1;
-    if (!WIDE || G <= G_MAX || !e->opt.team_wide || e->opt.team_tt == 32) return team_launch_part<ENV, HP, GMM, TLDS>(e, 0, G);
+    if (!WIDE || G <= G_MAX || !e->opt.team_wide || e->opt.team_tt == 32 || e->n_nets > 1) return team_launch_part<ENV, HP, GMM, TLDS>(e, 0, G);
     const int parts = (G + G_MAX - 1) / G_MAX, per = ((G + parts - 1) / parts + 3) / 4 * 4;   // (whole 64-tree teams)
     if (parts > 2) return hipErrorNotReady;
     // both parts' residency (occupancy, LDS) is checked before the first one is launched: a second part that does not fit

@@ -11,8 +11,10 @@ in PyTorch between them); --trainer device-fused computes the losses on the devi
 --optimizer adam and --grad-clip X give every net the reference's Adam settings and gradient clipping, on every trainer.
 --layernorm builds every net with LayerNorm after each trunk activation; the device trainers are then built with layernorm=True.
 --wide builds the device trainers with wide=True, which trains nets of up to 8 hidden layers and widths up to 1024 (--hidden 1024
-1024 1024 1024).  The search engine takes a population of more than one net only up to width 256, so a wide run is one seed:
---seeds 0 --hidden 512 272 --wide.  --wide --layernorm together build them with wide_layernorm=True: wide nets with LayerNorm.
+1024 1024 1024).  The search engine holds several such nets too: nets it searches as teams of 32 trees (padded width >= 512, two or
+more hidden layers, no LayerNorm, at most four observations) need --games-per-seed to be a multiple of 32 when there is more than one
+seed -- --seeds 3 11 --hidden 512 512 --wide --games-per-seed 32 -- and every other shape takes any number.  --wide --layernorm
+together build the trainers with wide_layernorm=True: wide nets with LayerNorm.
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
@@ -57,8 +59,9 @@ def parse_args(argv=None):
                          "(with --wide: wide_layernorm=True)")
     ap.add_argument("--wide", action="store_true",
                     help="build the device trainers with wide=True: 1-8 hidden layers of widths 16 ... 1024 (with --layernorm: "
-                         "wide_layernorm=True, the wide trainer that takes LayerNorm trunks).  One search "
-                         "engine cannot hold a population of several nets wider than 256, so use it with one seed (--seeds 0)")
+                         "wide_layernorm=True, the wide trainer that takes LayerNorm trunks).  With several "
+                         "seeds, nets the engine searches as 32-tree teams (width >= 512, two or more hidden layers, no LayerNorm, at most "
+                         "four observations) need --games-per-seed to be a multiple of 32")
     ap.add_argument("--engine-seed", type=int, default=34, help="the engine's RNG seed (shared; games differ by their global ids)")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--trainer", choices=["torch", "device", "device-fused", "device-epoch"], default="torch",
@@ -70,7 +73,23 @@ def parse_args(argv=None):
                          "(PopulationSelfPlay.evaluate) and add the per-seed mean return as eval_return; every seed starts from the same "
                          "states, so the numbers can be ranked (0: no evaluation)")
     ap.add_argument("--eval-rule", choices=["mode", "sample"], default="mode", help="the evaluation's action rule")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    why = check_population_shape(a)
+    if why:
+        ap.error(why)
+    return a
+
+
+def check_population_shape(a):
+    """Why the search engine would refuse this population (None: it takes it): several nets that it searches as teams of 32 trees
+    need a multiple of 32 games each (_capi.lockstep_shaped).  Asked before anything is built."""
+    from alphazero_gym_amd import _capi
+    from alphazero_gym_amd.envs import make_game
+    in_dim = make_game(a.game).observation_space.shape[0]
+    if len(a.seeds) > 1 and a.games_per_seed % 32 != 0 and _capi.lockstep_shaped(in_dim, a.hidden, a.layernorm):
+        return (f"--hidden {' '.join(map(str, a.hidden))} on {a.game} is searched as teams of 32 trees, one net per team: with "
+                f"{len(a.seeds)} seeds --games-per-seed must be a multiple of 32 (got {a.games_per_seed}); or run one seed")
+    return None
 
 
 def build_population(a):

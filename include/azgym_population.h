@@ -7,10 +7,14 @@
  * shapes.  Changing n_nets drops every weight; 1 restores the single-network engine.  All nets share the game, azg_config and the
  * network descriptor; they differ in their weights.
  * With n_nets > 1: azg_set_weights / _device return AZG_E_STATE; azg_search* and azg_selfplay_step return AZG_E_STATE until every
- * net has weights; networks wider than 256 (padded: the team / per-layer forms), azg_selfplay_begin / _ex (a population starts
- * self-play with azg_population_selfplay_begin), azg_mlp_eval and azg_root_eval return AZG_E_UNSUPPORTED; azg_set_population
- * while self-play runs returns AZG_E_UNSUPPORTED.  The CPU oracle does not export these: the tests hold a K-net engine against K
- * single-net engines. */
+ * net has weights; azg_selfplay_begin / _ex (a population starts self-play with azg_population_selfplay_begin), azg_mlp_eval and
+ * azg_root_eval return AZG_E_UNSUPPORTED; azg_set_population while self-play runs returns AZG_E_UNSUPPORTED.
+ * Wide networks (hidden width, padded to a multiple of 64, >= 512).  Those an engine searches as teams of 32 trees / per-layer launches
+ * -- two or more hidden layers, no LayerNorm, at most four inputs -- need T to be a multiple of 32, so that every team serves one net:
+ * any other T makes azg_set_net_weights* return AZG_E_UNSUPPORTED (the message names T; the engine keeps the weights it had).  The
+ * rule looks at the descriptor only, also under AZG_FORCE_PERSISTENT=1.  The other wide shapes (LayerNorm, one hidden layer, more than
+ * four inputs) run on the one-launch search kernel at any T.  azg_policy_rollout still refuses widths >= 512.
+ * The CPU oracle does not export these: the tests hold a K-net engine against K single-net engines. */
 #ifndef AZGYM_POPULATION_H
 #define AZGYM_POPULATION_H
 #include "azgym.h"
@@ -26,8 +30,9 @@ int azg_set_net_weights(azg_engine* e, int32_t net, const azg_mlp_desc* desc, co
 int azg_set_net_weights_device(azg_engine* e, int32_t net, const azg_mlp_desc* desc, const float* device_blob, size_t n_floats);
 /* every net at once from one device array [n_nets][n_floats_per_net] (blob k: net k, azg_set_weights blob order): one gather launch
  * and one stream synchronisation.  n_nets must equal the engine's (1: azg_set_weights_device).  Every net gets `desc`; the
- * population checks of azg_set_net_weights apply (HP >= 512: AZG_E_UNSUPPORTED).  NULL pointers or a wrong n_floats_per_net:
- * AZG_E_INVALID.  On failure no net has weights (nothing half written is searched). */
+ * population checks of azg_set_net_weights apply (team / per-layer networks with n_trees / n_nets not a multiple of 32:
+ * AZG_E_UNSUPPORTED, and the engine keeps the weights it had).  NULL pointers or a wrong n_floats_per_net: AZG_E_INVALID.  On a
+ * failure later than these checks no net has weights (nothing half written is searched). */
 int azg_set_population_weights_device(azg_engine* e, const azg_mlp_desc* desc, const float* device_blobs, size_t n_floats_per_net,
                                       int32_t n_nets);
 /* azg_selfplay_begin_ex for an engine with any n_nets (1: exactly azg_selfplay_begin_ex).  Net k plays games k*T .. k*T+T-1 with

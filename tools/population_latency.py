@@ -5,7 +5,14 @@ GPU box only:  python tools/population_latency.py [--ks 1,3,8,32,128,256] [--ste
 Configurations: Pendulum-v0, 3x128 ELU GMM-2 policy, 25 rollouts (run_continuous.py with the reference's GMM); CartPole-v0, 2x128
 ReLU, 8 rollouts, epsilon 0.1 (run_discrete.py).  Per K: kernel ms per launch (azg_last_search_ms; one-by-one: the mean of the K
 single-tree launches, and their sum), wall ms per population step, wall ms of the K one-by-one act() calls, and the speed-up.
-Every act searches from the same fresh root (reset_mcts before each step; the envs are not stepped)."""
+Every act searches from the same fresh root (reset_mcts before each step; the envs are not stepped).
+
+--wide: populations of wide nets (padded width >= 512: team kernel / per-layer launches), engine level:
+    python tools/population_latency.py --wide [--splits 1x1024,2x512,4x256,8x128,16x64,32x32] [--steps 5] [--warmup 2]
+Configurations: Pendulum-v1 4x1024 ELU x 200 simulations, CartPole 2x512 ReLU x 100 simulations.  Per split K x T: ms per search of
+ONE engine that holds the K nets (K x T trees in one search) and the form that ran, against the loop it replaces -- K one-net engines
+of T trees searched one after another, each search synchronised before the next starts, which is all an engine could do before
+it took several wide nets -- on the same box."""
 import argparse
 import json
 import os
@@ -78,14 +85,112 @@ def measure(kind, over, K, steps, warmup):
                 kernel=form["kernel_name"], waves=form.get("waves"), tile_trees=form.get("tile_trees"))
 
 
-def main():
+# name: engine kwargs, (network inputs, hidden widths, distribution outputs, activation)
+WIDE_CONFIGS = {
+    "pendulum_4x1024_200": (dict(env_id=2, mode=1, n_sims=200, c_uct=0.05, gamma=1.0, c_pw=1.0, kappa=0.5, seed=34), (3, [1024] * 4, 2, "elu")),
+    "cartpole_2x512_100": (dict(env_id=0, mode=0, num_actions=2, n_sims=100, c_uct=1.5, gamma=1.0, seed=34), (4, [512, 512], 2, "relu")),
+}
+WIDE_SPLITS = "1x1024,2x512,4x256,8x128,16x64,32x32"
+
+
+def parse_splits(spec):
+    """"2x512,4x256" -> [(2, 512), (4, 256)]: K nets x T trees per net; T a multiple of 32 wherever K > 1 (a team serves one net)."""
+    out = []
+    for part in spec.split(","):
+        k, t = (int(x) for x in part.lower().split("x"))
+        if k < 1 or t < 1 or (k > 1 and t % 32):
+            raise ValueError(f"split {part!r}: K nets x T trees per net, T a multiple of 32 when K > 1")
+        out.append((k, t))
+    return out
+
+
+def measure_wide(name, K, T, steps, warmup):
+    from alphazero_gym_amd import _capi, _native
+    from alphazero_gym_amd.synthetic import make_weights
+    kw, (in_dim, hidden, n_dist, act) = WIDE_CONFIGS[name]
+    desc = _capi.make_desc(in_dim, hidden, n_dist, act)
+    blobs = [make_weights(34 + k, in_dim, hidden, n_dist) for k in range(K)]
+    pop = _native.HipEngine(**dict(kw, n_trees=K * T))
+    if K > 1:
+        pop.set_population(K)
+        for k in range(K):
+            pop.set_net_weights(k, desc, blobs[k])
+    else:
+        pop.set_weights(desc, blobs[0])
+    roots = pop.synthetic_roots()
+    kern_pop, wall_pop = [], []
+    for i in range(warmup + steps):
+        t0 = time.perf_counter()
+        pop.search(roots)
+        t1 = time.perf_counter()
+        if i >= warmup:
+            wall_pop.append((t1 - t0) * 1e3)
+            kern_pop.append(pop.last_search_ms())
+    info = pop.search_info()
+    pop.close()
+    singles = []
+    for k in range(K):
+        e = _native.HipEngine(**dict(kw, n_trees=T, tree_id_base=k * T))
+        e.set_weights(desc, blobs[k])
+        singles.append(e)
+    kern_seq, wall_seq = [], []
+    for i in range(warmup + steps):
+        t0 = time.perf_counter()
+        for k, e in enumerate(singles):
+            e.search(roots[k * T:(k + 1) * T])
+        t1 = time.perf_counter()
+        if i >= warmup:
+            wall_seq.append((t1 - t0) * 1e3)
+            kern_seq.append(sum(e.last_search_ms() for e in singles))
+    form1 = singles[0].search_info()
+    for e in singles:
+        e.close()
+    med = lambda x: float(np.median(x))   # noqa: E731
+    return dict(K=K, T=T, kernel_ms_population=round(med(kern_pop), 3), wall_ms_population=round(med(wall_pop), 3), form=info["kernel_form"],
+                kernel=info["kernel_name"], team_fallbacks=info["team_fallbacks"], kernel_ms_loop=round(med(kern_seq), 3),
+                wall_ms_loop=round(med(wall_seq), 3), loop_form=form1["kernel_form"], speedup_wall=round(med(wall_seq) / med(wall_pop), 2))
+
+
+def main_wide(a):
+    for name in a.configs.split(","):
+        print(f"# {name}: medians over {a.steps} searches (after {a.warmup} warm-up searches); loop = K one-net engines of T trees, one after another")
+        print(f"# {'K x T':>9} {'population ms (kernel / wall)':>30} {'form':>10} {'loop ms (kernel / wall)':>26} {'speed-up':>9}")
+        for K, T in parse_splits(a.splits):
+            r = measure_wide(name, K, T, a.steps, a.warmup)
+            print(f"  {K:3d} x {T:4d} {r['kernel_ms_population']:14.3f} / {r['wall_ms_population']:11.3f} {r['form']:>10} "
+                  f"{r['kernel_ms_loop']:12.3f} / {r['wall_ms_loop']:9.3f} {r['speedup_wall']:8.2f}x")
+            print(json.dumps(dict(config=name, **r)), flush=True)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--ks", default="1,3,8,32,128,256")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--configs", default=",".join(CONFIGS))
-    a = ap.parse_args()
+    ap.add_argument("--steps", type=int, default=None, help="measured steps per point (default 20; --wide: 5)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps per point (default 3; --wide: 2)")
+    ap.add_argument("--wide", action="store_true", help="the wide configurations: one engine of K nets against K one-net engines in a loop")
+    ap.add_argument("--splits", default=WIDE_SPLITS, help="--wide: the K x T points")
+    ap.add_argument("--configs", default=None)
+    a = ap.parse_args(argv)
+    known = WIDE_CONFIGS if a.wide else CONFIGS
+    a.configs = a.configs or ",".join(known)
+    for name in a.configs.split(","):
+        if name not in known:
+            ap.error(f"unknown configuration {name!r}: {', '.join(known)}")
+    if a.wide:
+        try:
+            parse_splits(a.splits)
+        except ValueError as err:
+            ap.error(str(err))
+    a.steps = a.steps if a.steps is not None else (5 if a.wide else 20)
+    a.warmup = a.warmup if a.warmup is not None else (2 if a.wide else 3)
+    return a
+
+
+def main():
+    a = parse_args()
     os.environ.setdefault("AZG_QUIET", "1")
+    if a.wide:
+        return main_wide(a)
     for name in a.configs.split(","):
         kind, over = CONFIGS[name]
         print(f"# {name}: medians over {a.steps} steps (after {a.warmup} warm-up steps)")
