@@ -86,7 +86,13 @@ class AzgRolloutConfig(C.Structure):
                 ("action_rule", C.c_int32), ("game_id_base", C.c_uint32), ("episode", C.c_uint32)]
 
 
+class AzgRolloutInfo(C.Structure):
+    """include/azgym_eval.h: azg_rollout_info"""
+    _fields_ = [("struct_size", C.c_int32), ("form", C.c_int32), ("launches", C.c_int32), ("team_fallbacks", C.c_int32)]
+
+
 ROLLOUT_RULE = {"mode": 0, "sample": 1}   # include/azgym_eval.h: AZG_ROLLOUT_*
+ROLLOUT_FORM = {0: "group", 1: "team"}    # include/azgym_eval.h: AZG_ROLLOUT_FORM_*
 FINAL_SELECTION = {"max_visit": 0, "max_visits": 0, "max_value": 1}   # the reference's configs spell it both ways
 
 
@@ -110,7 +116,7 @@ SYMBOLS = [
 # entry points a library may lack (the tests' CPU oracle binds SYMBOLS only): bound when present, else the methods that need
 # them raise
 OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device",
-                    "population_selfplay_begin", "policy_rollout",
+                    "population_selfplay_begin", "policy_rollout", "policy_rollout_ex",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
                     "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch",
                     "trainer_backward_step_opt", "trainer_step_opt", "trainer_epoch_opt", "trainer_create_ex", "trainer_create_wide",
@@ -224,6 +230,9 @@ def bind(lib, prefix):
     if "policy_rollout" in f:   # include/azgym_eval.h
         f["policy_rollout"].argtypes = [vp, C.POINTER(AzgRolloutConfig), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+    if "policy_rollout_ex" in f:
+        f["policy_rollout_ex"].argtypes = [vp, C.POINTER(AzgRolloutConfig), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(AzgRolloutInfo)]
     if "trainer_create" in f:   # include/azgym_train.h
         f["trainer_create"].argtypes = [C.c_int32, C.POINTER(AzgMlpDesc), C.c_int32, C.c_int32, C.POINTER(vp)]
         f["trainer_destroy"].argtypes = [vp]
@@ -333,6 +342,8 @@ def lockstep_shaped(in_dim, hidden, layernorm=False):
 
 class Engine:
     """One batched MCTS engine (B trees).  Mirrors MCTS*.__init__ kwargs (alphazero/search/mcts.py:316-327, 537-549)."""
+
+    last_rollout_info = None   # what the last policy_rollout ran as (azg_rollout_info as a dict)
 
     def __init__(self, fns, *, env_id, mode, n_trees, n_sims, c_uct, gamma, epsilon=0.0, num_actions=0, c_pw=1.0,
                  kappa=0.5, v_target="off_policy", reward_scale=PENDULUM_R_SCALE, action_bound=2.0, seed=34,
@@ -551,10 +562,14 @@ class Engine:
         return value, dist, raw
 
     def policy_rollout(self, episodes_per_net, max_episode_length, rule="mode", game_id_base=0, episode=0):
-        """azg_policy_rollout (include/azgym_eval.h): ``episodes_per_net`` whole episodes per net played by the network alone,
-        one launch.  Game j of every net starts at the reset state of global game ``game_id_base + j``, episode ``episode``.
-        Returns a dict of [n_nets, episodes_per_net] arrays: returns (float64), lengths, terminated (bool), first_value."""
-        fn = self._optional("policy_rollout")
+        """azg_policy_rollout_ex (include/azgym_eval.h; a library without it: azg_policy_rollout, widths up to 256 only):
+        ``episodes_per_net`` whole episodes per net played by the network alone, on the device.  Game j of every net starts at the
+        reset state of global game ``game_id_base + j``, episode ``episode``.
+        Returns a dict of [n_nets, episodes_per_net] arrays: returns (float64), lengths, terminated (bool), first_value.
+        ``self.last_rollout_info`` is then what ran: ``form`` ("group" / "team"), ``launches``, ``team_fallbacks`` (None after the
+        old entry point, which does not report)."""
+        fn_ex = self._f.get("policy_rollout_ex")
+        fn = fn_ex if fn_ex is not None else self._optional("policy_rollout")
         c = AzgRolloutConfig()
         c.struct_size = C.sizeof(AzgRolloutConfig)
         c.episodes_per_net, c.max_episode_length = int(episodes_per_net), int(max_episode_length)
@@ -565,8 +580,16 @@ class Engine:
         lengths = np.empty(shape, np.int32)
         terminated = np.empty(shape, np.int32)
         first_value = np.empty(shape, np.float32)
-        self._check(fn(self._h, C.byref(c), _ptr(returns, C.c_double), _ptr(lengths, C.c_int32), _ptr(terminated, C.c_int32),
-                       _ptr(first_value, C.c_float)))
+        outs = (_ptr(returns, C.c_double), _ptr(lengths, C.c_int32), _ptr(terminated, C.c_int32), _ptr(first_value, C.c_float))
+        if fn_ex is not None:
+            info = AzgRolloutInfo()
+            info.struct_size = C.sizeof(AzgRolloutInfo)
+            self._check(fn_ex(self._h, C.byref(c), *outs, C.byref(info)))
+            self.last_rollout_info = {"form": ROLLOUT_FORM.get(info.form, str(info.form)), "launches": int(info.launches),
+                                      "team_fallbacks": int(info.team_fallbacks)}
+        else:
+            self._check(fn(self._h, C.byref(c), *outs))
+            self.last_rollout_info = None
         return {"returns": returns, "lengths": lengths, "terminated": terminated.astype(bool), "first_value": first_value}
 
     def dump_tree(self):

@@ -143,6 +143,7 @@ EngineOptions EngineOptions::from_env() {
     if (const char* v = getenv("AZG_TEAM_SPIN_LIMIT")) o.team_spin_limit = atol(v);
     o.no_lds_state = getenv("AZG_NO_LDS_STATE") != nullptr;
     o.publish_always = digit("AZG_PUBLISH_TREES", 0) == 1;
+    { const int t = num("AZG_ROLLOUT_TEAMS"); o.rollout_teams = t > 0 ? t : 0; }
     return o;
 }
 

@@ -31,6 +31,7 @@ struct EngineOptions {
     long team_spin_limit = 1L << 23;   // AZG_TEAM_SPIN_LIMIT=n: polls a team hand-off may wait before the launch gives up (tests: 0)
     int no_lds_state = 0;          // AZG_NO_LDS_STATE set: discrete LDS trees keep the expanded nodes' env states in the cold records only
     int publish_always = 0;        // AZG_PUBLISH_TREES=1: every search writes its LDS trees out in the global format (diagnostic tools)
+    int rollout_teams = 0;         // AZG_ROLLOUT_TEAMS=n: at most n teams per launch of the team rollout (tests: several launches; 0: all that fit)
     static EngineOptions from_env();   // (azg_engine.hip)
 };
 #define AZG_MAX_DEVICES 64    // per-device caches of kernel attributes (host side)
@@ -119,6 +120,12 @@ struct azg_engine : EngineQueue {
     DeviceAllocs eval_mem; float* d_eval = nullptr; size_t eval_floats = 0;   // scratch of azg_mlp_eval (grow-only)
     DeviceAllocs rollout_mem; char* d_rollout = nullptr; size_t rollout_bytes = 0;   // outputs of azg_policy_rollout (grow-only)
     std::vector<char> rollout_stage;                                                  // ... and their host copy
+    // team rollouts (rollout_team.cuh) own their hand-off memory, grow-only: activations and head partials (ro_ls.act / parts, sized in
+    // team x width units), live-game counts and counters + abort word (sized in teams).  Nothing of the search's (ls, d_team_cnt) is used.
+    DeviceAllocs ro_team_mem; LockStep ro_ls{}; float* d_ro_live = nullptr; unsigned* d_ro_cnt = nullptr;
+    size_t ro_team_units = 0; int ro_team_cap = 0;
+    int ro_team_off = 0;        // a team rollout of this engine gave up: its rollouts take the group form from then on (opt.ls_team is the search's)
+    int ro_team_fallbacks = 0;  // team rollouts that gave up and were replayed in the group form
     int searched = 0, results_valid = 0;
     int publish_once = 0;    // set by azg_dump_tree around its re-run of the last search
     int published = 0;       // the last search's trees are in global memory (global-tree / lock-step / team forms always are)
@@ -246,5 +253,9 @@ template <int ENV> hipError_t azg_lockstep_search(azg_engine* e);   // wide netw
 template <int ENV> hipError_t azg_team_search(azg_engine* e);       // (team_dispatch.cuh)
 // the team kernel's forms for more than two 32-tree workgroups per CU (config E's network; team_dispatch.cuh); dry: residency check only
 hipError_t azg_team_wide_forms(azg_engine* e, int g_base, int G, bool dry, bool common, bool t32, bool t64);
+// policy rollout in the team form (dispatch_rollout_team.hip): every team of the call as one or more launches on e->stream, counted into
+// *launches; the counters and the abort word (*abort_word: its device address) are zeroed first.  hipErrorNotReady: not a shape or a
+// device the team form can hold resident, nothing was launched -- use the group form.
+hipError_t azg_rollout_team(azg_engine* e, const struct Rollout& ro, int* launches, unsigned** abort_word);
 // batched network inference of n observations (device pointers) on e->stream (mlp_eval.cuh)
 hipError_t azg_dispatch_mlp_eval(azg_engine* e, const float* obs, int n, float* value, float* dist, float* raw);

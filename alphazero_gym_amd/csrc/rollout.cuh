@@ -1,4 +1,4 @@
-// rollout.cuh -- policy rollouts (azg_policy_rollout, include/azgym_eval.h): whole episodes played by the network alone, one launch.
+// rollout.cuh -- policy rollouts (azg_policy_rollout / azg_policy_rollout_ex, include/azgym_eval.h): whole episodes played by the network alone, one launch.
 // Grid (ceil(G / 16), n_nets): one workgroup carries 16 games of one net from reset through every step.  Per step the games'
 // observations go to LDS, mlp_forward runs (the search's network phase: same MFMA chains and chunked head sums, so the head outputs
 // are azg_mlp_eval's), and one lane per game turns them into an action, steps the env in float64 and adds the reward; observing and
@@ -7,7 +7,9 @@
 // no live game, which it tells the workgroup through LDS, so the exit is uniform.  No atomics: every output has one writer.
 // NREG > 0: the hidden->hidden weights stay in registers for the whole rollout (the nets the search keeps resident: resident_layers,
 // engine_weights.hip); NREG == 0: they are streamed from L2 every step (any depth, LayerNorm, the rare activations).  The first layer
-// and (NREG > 0) the head are register-resident either way.
+// and (NREG > 0) the head are register-resident either way -- up to HP = 256.  HP = 512 / 1024 (azg_policy_rollout_ex: NREG == 0 only)
+// stream the first layer too, as mlp_eval_kernel does: the GROUP form of the wide rollouts, which takes every wide shape and is what
+// the team form (rollout_team.cuh) falls back to.
 #pragma once
 #include "records.h"
 #include "env.cuh"
@@ -92,11 +94,13 @@ __global__ __launch_bounds__(256, 1) void rollout_kernel(KParams P, Rollout ro) 
     typedef WRegs<HP, NREG, 4> WR;
     WR wr;
     constexpr int NTW = HP / 64;
+    if constexpr (HP <= 256) {   // (wider: mlp_forward streams the first layer too, as in mlp_eval_kernel)
 #pragma unroll
-    for (int i = 0; i < NTW; ++i) {
-        wr.w0[i] = P.W0[wofs + (wave * NTW + i) * 64 + lane];
-        if (P.in8) wr.w0b[i] = P.W0b[wofs + (wave * NTW + i) * 64 + lane];
-        wr.b0[i] = net_ptr(P.b0, wofs)[(wave * NTW + i) * 64 + lane];
+        for (int i = 0; i < NTW; ++i) {
+            wr.w0[i] = P.W0[wofs + (wave * NTW + i) * 64 + lane];
+            if (P.in8) wr.w0b[i] = P.W0b[wofs + (wave * NTW + i) * 64 + lane];
+            wr.b0[i] = net_ptr(P.b0, wofs)[(wave * NTW + i) * 64 + lane];
+        }
     }
     if constexpr (NREG > 0) {
         constexpr int S4 = HP / 16;

@@ -393,8 +393,8 @@ class PopulationSelfPlay:
 
     def evaluate(self, episodes_per_net: int, rule: str = "mode", max_episode_length: Optional[int] = None, episode: int = 0,
                  game_id_base: Optional[int] = None) -> Dict[str, np.ndarray]:
-        """How good each net is by itself: ``episodes_per_net`` whole episodes per net played by the raw policy, no search, in one
-        launch (azg_policy_rollout).  Game j of EVERY net starts from the same state (that of global game ``game_id_base + j``,
+        """How good each net is by itself: ``episodes_per_net`` whole episodes per net played by the raw policy, no search, on the
+        device in one call (azg_policy_rollout_ex: every width the engine accepts).  Game j of EVERY net starts from the same state (that of global game ``game_id_base + j``,
         episode ``episode``), so the nets' returns can be ranked; another ``episode`` draws fresh start states.  ``rule``:
         "mode" (arg-max logit / the squashed mean) or "sample" (the policy's own distribution, the engine's Philox streams).
         ``max_episode_length`` None: the self-play's own limit; ``game_id_base`` None: ``EVAL_GAME_ID_BASE``, or the first id

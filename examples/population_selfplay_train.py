@@ -14,7 +14,8 @@ in PyTorch between them); --trainer device-fused computes the losses on the devi
 1024 1024 1024).  The search engine holds several such nets too: nets it searches as teams of 32 trees (padded width >= 512, two or
 more hidden layers, no LayerNorm, at most four observations) need --games-per-seed to be a multiple of 32 when there is more than one
 seed -- --seeds 3 11 --hidden 512 512 --wide --games-per-seed 32 -- and every other shape takes any number.  --wide --layernorm
-together build the trainers with wide_layernorm=True: wide nets with LayerNorm.
+together build the trainers with wide_layernorm=True: wide nets with LayerNorm.  --eval-episodes works at every width: wide nets are
+rolled out on the device too, all seeds in one call (--seeds 3 11 --hidden 512 512 --wide --games-per-seed 32 --eval-episodes 32).
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
@@ -69,9 +70,9 @@ def parse_args(argv=None):
                          "the losses in PyTorch between them; device-fused: the losses in a kernel of the same step (losses='device'); "
                          "device-epoch: device-fused's arithmetic, the whole epoch in one call on the rows in the self-play ring")
     ap.add_argument("--eval-episodes", type=int, default=0,
-                    help="after every iteration play this many whole episodes per seed with the raw policy, no search, in one launch "
-                         "(PopulationSelfPlay.evaluate) and add the per-seed mean return as eval_return; every seed starts from the same "
-                         "states, so the numbers can be ranked (0: no evaluation)")
+                    help="after every iteration play this many whole episodes per seed with the raw policy, no search, on the device in "
+                         "one call (PopulationSelfPlay.evaluate; any width, --wide nets included) and add the per-seed mean return as "
+                         "eval_return; every seed starts from the same states, so the numbers can be ranked (0: no evaluation)")
     ap.add_argument("--eval-rule", choices=["mode", "sample"], default="mode", help="the evaluation's action rule")
     a = ap.parse_args(argv)
     why = check_population_shape(a)
