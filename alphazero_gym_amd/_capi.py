@@ -120,7 +120,8 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
                     "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch",
                     "trainer_backward_step_opt", "trainer_step_opt", "trainer_epoch_opt", "trainer_create_ex", "trainer_create_wide",
-                    "trainer_create_wide_ex"]
+                    "trainer_create_wide_ex",
+                    "trainer_backward_step_nets", "trainer_loss_nets", "trainer_step_nets", "trainer_epoch_nets"]
 
 
 class AzgRmsprop(C.Structure):
@@ -264,6 +265,11 @@ def bind(lib, prefix):
     if "trainer_create_wide_ex" in f:
         f["trainer_create_wide_ex"].argtypes = [C.c_int32, C.POINTER(AzgMlpDesc), C.c_int32, C.c_int32, C.POINTER(AzgTrainerOptions),
                                                 C.POINTER(vp)]
+    if "trainer_backward_step_nets" in f:   # the *_opt prototypes with arrays of n_nets entries
+        f["trainer_backward_step_nets"].argtypes = f["trainer_backward_step_opt"].argtypes
+        f["trainer_loss_nets"].argtypes = f["trainer_loss"].argtypes
+        f["trainer_step_nets"].argtypes = f["trainer_step_opt"].argtypes
+        f["trainer_epoch_nets"].argtypes = f["trainer_epoch_opt"].argtypes
     return f
 
 
@@ -907,6 +913,58 @@ class Trainer:
                                                  int(batch_size), C.byref(cfg) if cfg is not None else None,
                                                  C.byref(alpha) if alpha is not None else None, C.byref(opt) if opt is not None else None,
                                                  loss_sums or None, C.byref(n_mb)))
+        return n_mb.value
+
+    # ---- per-net settings: the *_opt calls with one azg_optim / azg_loss_cfg per net ----
+
+    def _entries(self, who, items, ctype):
+        """A sequence of n_nets ``ctype`` structures as the contiguous array the *_nets entry points read (None stays NULL)."""
+        if "trainer_step_nets" not in self._f:
+            raise NotImplementedError("this engine library has no azg_trainer_*_nets entry points")
+        if items is None:
+            return None
+        if isinstance(items, C.Array) and items._type_ is ctype and len(items) == self.n_nets:   # (ready: no copy)
+            return items
+        items = list(items)
+        if len(items) != self.n_nets:
+            raise ValueError(f"Trainer.{who}: one {ctype.__name__} per net ({self.n_nets}), not {len(items)}")
+        return (ctype * len(items))(*items)
+
+    def backward_step_nets(self, params, d_raw, n_rows, opts, grads=None):
+        """azg_trainer_backward_step_nets: ``backward_step_opt`` with ``opts``, a sequence of n_nets ``optim``s whose numeric
+        settings (lr, eps, weight_decay, alpha, betas, grad_clip) may differ; kind, state addresses and step must be equal."""
+        arr = self._entries("backward_step_nets", opts, AzgOptim)
+        self._check(self._f["trainer_backward_step_nets"](self._h, params or None, d_raw or None, int(n_rows), arr, grads or None))
+
+    def loss_nets(self, raw, actions, counts, values, n_rows, n_actions, cfgs, alpha, d_raw, losses):
+        """azg_trainer_loss_nets: ``loss`` with ``cfgs``, a sequence of n_nets ``loss_cfg``s whose numeric settings may differ;
+        kind, head, reduction and action_bound must be equal."""
+        arr = self._entries("loss_nets", cfgs, AzgLossCfg)
+        self._check(self._f["trainer_loss_nets"](self._h, raw or None, actions or None, counts or None, values or None, int(n_rows),
+                                                 int(n_actions), arr, C.byref(alpha) if alpha is not None else None, d_raw or None,
+                                                 losses or None))
+
+    def step_nets(self, params, obs, actions, counts, values, n_rows, n_actions, cfgs, alpha, opts, grads, raw_out, losses):
+        """azg_trainer_step_nets: ``step_opt`` with one ``loss_cfg`` and one ``optim`` per net."""
+        carr, oarr = self._entries("step_nets", cfgs, AzgLossCfg), self._entries("step_nets", opts, AzgOptim)
+        self._check(self._f["trainer_step_nets"](self._h, params or None, obs or None, actions or None, counts or None, values or None,
+                                                 int(n_rows), int(n_actions), carr, C.byref(alpha) if alpha is not None else None, oarr,
+                                                 grads or None, raw_out or None, losses or None))
+
+    def epoch_nets(self, params, rows, order, batch_size, cfgs, alpha, opts, loss_sums):
+        """azg_trainer_epoch_nets: ``epoch_opt`` with one ``loss_cfg`` and one ``optim`` per net.  Returns the number of
+        minibatches."""
+        carr, oarr = self._entries("epoch_nets", cfgs, AzgLossCfg), self._entries("epoch_nets", opts, AzgOptim)
+        n_order, ptr = 0, None
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.int32)
+            if order.ndim != 2 or order.shape[0] != self.n_nets:
+                raise ValueError("Trainer.epoch_nets: order must be [n_nets, n_order]")
+            n_order, ptr = order.shape[1], _ptr(order, C.c_int32)
+        n_mb = C.c_int32(0)
+        self._check(self._f["trainer_epoch_nets"](self._h, params or None, C.byref(rows) if rows is not None else None, ptr, n_order,
+                                                  int(batch_size), carr, C.byref(alpha) if alpha is not None else None, oarr,
+                                                  loss_sums or None, C.byref(n_mb)))
         return n_mb.value
 
     def read_d_raw(self, n_rows, d_raw):

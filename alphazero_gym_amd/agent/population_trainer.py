@@ -12,6 +12,7 @@ launches, one synchronisation, one copy of ``losses[K, 5]`` to the host).  ``tra
 around that step to the device as well (``azg_trainer_epoch``): the minibatches are gathered by a kernel from the rows where they
 lie, the self-play ring included, and a whole epoch costs one synchronisation.  The single-agent path (``Agent.update``) is untouched.
 """
+import ctypes as C
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -176,6 +177,15 @@ def _loss_settings(loss) -> tuple:
     raise ValueError(f"PopulationTrainer: loss {type(loss).__name__} is not supported (AlphaZeroLoss, A0CLoss, A0CLossTuned)")
 
 
+def _loss_shared(loss) -> tuple:
+    """What ``per_net=True`` still asks every agent's loss to share: the class, the reduction and (tuned) the alpha optimiser's kind.
+    Everything else in ``_loss_settings`` is a number that azg_loss_cfg carries per net."""
+    _loss_settings(loss)   # (its refusal of other loss classes)
+    if type(loss) is A0CLossTuned:
+        return (A0CLossTuned, loss.reduction, type(loss.optimizer), loss.optimizer.param_groups[0].get("amsgrad", False))
+    return (type(loss), loss.reduction)
+
+
 def _rmsprop_settings(opt) -> tuple:
     if type(opt) is not torch.optim.RMSprop:
         raise ValueError(f"PopulationTrainer: the nets' optimiser must be torch.optim.RMSprop, not {type(opt).__name__}")
@@ -261,14 +271,26 @@ class PopulationTrainer:
 
     ``wide_layernorm``: True is the wide trainer that also takes LayerNorm agents (agents without LayerNorm too): the same 8 x 1024
     limits, checks and behaviour as ``wide=True``, the native trainer made by azg_trainer_create_wide_ex, which adds a row pass per
-    LayerNorm and direction to the wide trainer's launches.  Together with ``layernorm=True`` it raises: two different trainers."""
+    LayerNorm and direction to the wide trainer's launches.  Together with ``layernorm=True`` it raises: two different trainers.
+
+    ``per_net``: True (needs ``optimizers="agents"``) lets the agents differ in their optimiser's numeric settings (lr, eps,
+    weight_decay, RMSprop's alpha, Adam's betas) and in ``grad_clip``, and with ``losses="device"`` also in their loss's numeric
+    settings (tau, the coefficients, A0CLoss's alpha, the tuned loss's target entropy, alpha optimiser settings and clip): a
+    learning-rate sweep in one trainer.  Optimiser class, loss class, reduction, network shape and step counts are still shared.
+    Every call then goes through the ``*_nets`` entry points, which read one settings entry per net; agents with equal settings
+    get the bits of ``per_net=False``.  ``reload_settings()`` reads the agents' settings again, e.g. after a schedule or an
+    exploit/explore step changed ``optimizer.param_groups[0]["lr"]``."""
 
     def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False, losses: str = "torch",
-                 optimizers: str = "rmsprop", layernorm: bool = False, wide: bool = False, wide_layernorm: bool = False):
+                 optimizers: str = "rmsprop", layernorm: bool = False, wide: bool = False, wide_layernorm: bool = False,
+                 per_net: bool = False):
         if losses not in ("torch", "device"):
             raise ValueError("losses must be 'torch' or 'device'")
         if optimizers not in ("rmsprop", "agents"):
             raise ValueError("optimizers must be 'rmsprop' or 'agents'")
+        if per_net and optimizers != "agents":
+            raise ValueError('PopulationTrainer: per_net=True requires optimizers="agents"')
+        self.per_net = bool(per_net)
         self.losses = losses
         self.optimizers = optimizers
         self.agents = list(agents)
@@ -290,7 +312,9 @@ class PopulationTrainer:
         if not self.layernorm and not self.wide_layernorm and any(a.nn.layernorm for a in self.agents):
             raise ValueError("PopulationTrainer: LayerNorm trunks are not trained on the device")
         opt_states: List[List[dict]] = []
-        if optimizers == "agents":
+        if self.per_net:
+            settings, net_clips = self._per_net_optim()
+        elif optimizers == "agents":
             if any(float(a.clip or 0.0) < 0 for a in self.agents):
                 raise ValueError("PopulationTrainer: grad_clip must be >= 0")
             if len({float(a.clip or 0.0) for a in self.agents}) != 1:
@@ -300,6 +324,7 @@ class PopulationTrainer:
                 raise ValueError("PopulationTrainer: every agent must have the same optimiser class")
             if len(set(settings)) != 1:
                 raise ValueError(f"PopulationTrainer: every agent must have the same {settings[0][0].__name__} settings")
+        if optimizers == "agents":
             if settings[0][0] is torch.optim.Adam:
                 opt_states = [[a.optimizer.state.get(p, {}) for p in a.nn.parameters()] for a in self.agents]
                 flat_states = [st for sts in opt_states for st in sts]
@@ -310,7 +335,9 @@ class PopulationTrainer:
                 raise ValueError("PopulationTrainer: grad_clip != 0 is not supported (a per-net global norm needs a pass of its own)")
             if len({_rmsprop_settings(a.optimizer) for a in self.agents}) != 1:
                 raise ValueError("PopulationTrainer: every agent must have the same RMSprop settings")
-        if len({_loss_settings(a.loss) for a in self.agents}) != 1:
+        if self.per_net:
+            self._per_net_loss()
+        elif len({_loss_settings(a.loss) for a in self.agents}) != 1:
             raise ValueError("PopulationTrainer: every agent must have the same loss class and hyper-parameters")
         max_layers, max_width = (8, 1024) if (self.wide or self.wide_layernorm) else (3, 256)
         unsupported = (f"PopulationTrainer: supported nets have 1-{max_layers} hidden layers of widths 16, 32, ... {max_width}, at most "
@@ -335,6 +362,8 @@ class PopulationTrainer:
             if any(alpha_states) and (not all(alpha_states) or len({float(s["step"]) for s in alpha_states}) != 1):
                 raise ValueError("PopulationTrainer: the agents' alpha optimisers must have taken the same number of steps")
         self.loss_cfg = _capi.loss_cfg(a0.nn, a0.loss) if losses == "device" else None
+        net_cfgs = [_capi.loss_cfg(a.nn, a.loss) for a in self.agents] if (self.per_net and losses == "device") else None
+        self.loss_cfgs = None   # (per_net=True, losses="device": one azg_loss_cfg per net)
         from .. import _native   # raises if libazgym_hip.so is missing
 
         # the native trainer first: if it cannot be created, the agents are left as they were
@@ -403,6 +432,8 @@ class PopulationTrainer:
                     "exp_avg_sq": torch.stack([s["exp_avg_sq"].to(device) for s in alpha_states])}
         self.last_raw: Optional[torch.Tensor] = None
         self._last_d_raw: Optional[torch.Tensor] = None
+        if self.per_net:
+            self._set_net_entries(settings, net_clips, net_cfgs)
 
     @property
     def last_d_raw(self) -> Optional[torch.Tensor]:
@@ -458,11 +489,79 @@ class PopulationTrainer:
         stream.synchronize()
         grads = self.grads.data_ptr() if self.grads is not None else None
         if self.optimizers == "agents":   # (the clip happens inside: PyTorch never sees the parameter gradients)
-            self.trainer.backward_step_opt(self.flat.data_ptr(), d_raw.data_ptr(), B, self._optim(), grads)
+            if self.per_net:
+                self.trainer.backward_step_nets(self.flat.data_ptr(), d_raw.data_ptr(), B, self._optims(), grads)
+            else:
+                self.trainer.backward_step_opt(self.flat.data_ptr(), d_raw.data_ptr(), B, self._optim(), grads)
             self.opt_step += 1
         else:
             self.trainer.backward_step(self.flat.data_ptr(), d_raw.data_ptr(), B, self.opt, self.square_avg.data_ptr(), grads)
         return out
+
+    def _per_net_optim(self) -> Tuple[List[tuple], List[float]]:
+        """``per_net=True``: every agent's (class, settings) and grad_clip, after the checks that remain -- a supported optimiser of
+        one class for all, grad_clip >= 0."""
+        if any(float(a.clip or 0.0) < 0 for a in self.agents):
+            raise ValueError("PopulationTrainer: grad_clip must be >= 0")
+        settings = [_optimizer_settings(a.optimizer) for a in self.agents]
+        if len({st[0] for st in settings}) != 1:
+            raise ValueError("PopulationTrainer: every agent must have the same optimiser class")
+        return settings, [float(a.clip or 0.0) for a in self.agents]
+
+    def _per_net_loss(self) -> None:
+        """``per_net=True``: the loss objects share what they must (``losses="device"``), or everything (``losses="torch"``:
+        ``population_loss`` is written for one set of settings)."""
+        if self.losses == "device":
+            if len({_loss_shared(a.loss) for a in self.agents}) != 1:
+                raise ValueError("PopulationTrainer: every agent must have the same loss class and hyper-parameters")
+        elif len({_loss_settings(a.loss) for a in self.agents}) != 1:
+            raise ValueError("PopulationTrainer: every agent must have the same loss class and hyper-parameters "
+                             '(per-net loss settings need losses="device")')
+
+    def reload_settings(self) -> None:
+        """Read every agent's ``optimizer.param_groups[0]``, ``clip`` and loss object again (``per_net=True`` only), with the
+        constructor's checks; the next ``update`` / epoch uses them.  If a check refuses, it raises ``ValueError`` and the trainer
+        keeps the settings it had.  The optimiser state, the step counts and the learned temperatures are the trainer's and are
+        not touched."""
+        if not self.per_net:
+            raise ValueError("PopulationTrainer.reload_settings needs a trainer built with per_net=True")
+        settings, clips = self._per_net_optim()
+        if settings[0][0] is not self._opt_settings[0]:
+            raise ValueError("PopulationTrainer.reload_settings: the optimiser class cannot change")
+        self._per_net_loss()
+        cfgs = None
+        if self.losses == "device":
+            cfgs = [_capi.loss_cfg(a.nn, a.loss) for a in self.agents]
+            if any((c.kind, c.head, c.reduction, c.action_bound) != (self.loss_cfg.kind, self.loss_cfg.head, self.loss_cfg.reduction,
+                                                                     self.loss_cfg.action_bound) for c in cfgs):
+                raise ValueError("PopulationTrainer.reload_settings: loss class, head and reduction cannot change")
+        self._set_net_entries(settings, clips, cfgs)
+
+    def _set_net_entries(self, settings: List[tuple], clips: List[float], cfgs: Optional[list]) -> None:
+        """``per_net=True``: the arrays the ``*_nets`` calls read, built once per set of settings -- one azg_optim per net (its
+        agent's settings over the shared state tensors; ``_optims`` writes the step count into all of them) and, with
+        ``losses="device"``, one azg_loss_cfg per net."""
+        out = []
+        for st, clip in zip(settings, clips):
+            common = dict(grad_clip=clip, step=self.opt_step, grad_norms=self.last_grad_norms.data_ptr())
+            if st[0] is torch.optim.Adam:
+                _, lr, betas, eps, wd = st
+                out.append(_capi.optim("adam", lr, self.exp_avg_sq.data_ptr(), self.exp_avg.data_ptr(), eps=eps, weight_decay=wd,
+                                       betas=betas, **common))
+            else:
+                _, lr, alpha, eps, wd = st
+                out.append(_capi.optim("rmsprop", lr, self.square_avg.data_ptr(), eps=eps, weight_decay=wd, alpha=alpha, **common))
+        opts = (_capi.AzgOptim * len(out))(*out)
+        words = C.sizeof(_capi.AzgOptim) // 4
+        steps = np.frombuffer(opts, dtype=np.int32).reshape(len(out), words)[:, _capi.AzgOptim.step.offset // 4]
+        self._net_opt_settings, self._net_clips = settings, clips
+        self._net_opts, self._net_steps = opts, steps
+        self.loss_cfgs = (_capi.AzgLossCfg * len(cfgs))(*cfgs) if cfgs is not None else None
+
+    def _optims(self):
+        """``per_net=True``: the azg_optim array of the next step."""
+        self._net_steps[:] = self.opt_step
+        return self._net_opts
 
     def _optim(self):
         """azg_optim of the next step (``optimizers="agents"``): the agents' settings, the trainer's state tensors and step count."""
@@ -485,7 +584,11 @@ class PopulationTrainer:
                                   self.alpha_exp_avg_sq.data_ptr()) if tuned else None
         stream.synchronize()
         grads = self.grads.data_ptr() if self.grads is not None else None
-        if self.optimizers == "agents":
+        if self.per_net:
+            self.trainer.step_nets(self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), B,
+                                   actions.shape[2], self.loss_cfgs, state, self._optims(), grads, raw.data_ptr(), table.data_ptr())
+            self.opt_step += 1
+        elif self.optimizers == "agents":
             self.trainer.step_opt(self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), B,
                                   actions.shape[2], self.loss_cfg, state, self._optim(), grads, raw.data_ptr(), table.data_ptr())
             self.opt_step += 1
@@ -537,7 +640,11 @@ class PopulationTrainer:
         state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
                                   self.alpha_exp_avg_sq.data_ptr()) if tuned else None
         torch.cuda.current_stream(self.device).synchronize()
-        if self.optimizers == "agents":
+        if self.per_net:
+            n_steps = self.trainer.epoch_nets(self.flat.data_ptr(), where, order, int(batch_size), self.loss_cfgs, state, self._optims(),
+                                              sums.data_ptr())
+            self.opt_step += n_steps
+        elif self.optimizers == "agents":
             n_steps = self.trainer.epoch_opt(self.flat.data_ptr(), where, order, int(batch_size), self.loss_cfg, state, self._optim(),
                                              sums.data_ptr())
             self.opt_step += n_steps

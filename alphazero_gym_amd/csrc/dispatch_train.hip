@@ -1,6 +1,8 @@
 // dispatch_train.hip -- the population trainer's C ABI (include/azgym_train.h): scratch, checks and the three launches of train.cuh;
 // azg_trainer_epoch enqueues them for a whole epoch of minibatches behind a gather launch each.  The *_opt entry points take an
 // azg_optim and choose the backward launch's form: fused RMSprop, or gradients first and norm, clip and update after the last layer.
+// The *_nets entry points take one azg_optim / azg_loss_cfg per net: the same checks per entry, the launch-ready settings in a device
+// table, and the per-net forms of the deferred backward, update and loss kernels, which read their net's entry from it.
 // A trainer made by azg_trainer_create_wide(_ex) keeps its dims in `wide` and takes dispatch_train_wide.hip's launches (one per layer and
 // role) wherever a narrow one takes train.cuh's; every check, buffer and synchronisation is the same code.
 #include <cmath>
@@ -37,6 +39,13 @@ struct azg_trainer {
     float* stage_buf = nullptr;
     float* loss_table = nullptr;
     size_t order_bytes = 0, stage_bytes = 0, table_bytes = 0;
+    // the *_nets entry points': the launch-ready settings of every (minibatch, net), [M][n_nets] TrainOptD | [M][n_nets] LossDims (a
+    // part the call has no entries for is empty), filled on the host for the whole call and uploaded in one copy; grown on demand
+    std::vector<unsigned char> nets_host;
+    unsigned char* nets_dev = nullptr;
+    size_t nets_bytes = 0;
+    size_t nets_loss_off = 0;    // where the LossDims part starts
+    bool nets_any_norm = false;  // some net of the call clips or reports its norm
     hipStream_t stream = nullptr;
     std::string err;
 };
@@ -68,6 +77,7 @@ void azg_trainer_destroy(azg_trainer* t) {
     if (t->stage_buf) (void)hipFree(t->stage_buf);
     if (t->loss_table) (void)hipFree(t->loss_table);
     if (t->norm_part) (void)hipFree(t->norm_part);
+    if (t->nets_dev) (void)hipFree(t->nets_dev);
     if (t->wide) tw_free(t->wide);
     delete t;
 }
@@ -409,6 +419,106 @@ static void launch_loss(azg_trainer* t, const LossDims& c, const float* raw, con
                        t->loss_rows, t->max_batch);
 }
 
+// ---- the *_nets entry points: one azg_optim and / or one azg_loss_cfg per net ----
+
+static int nets_differ(azg_trainer* t, const char* who, const char* field, int k) {
+    return tfail(t, AZG_E_INVALID, std::string(who) + ": " + field + " of net " + std::to_string(k) + " differs from net 0's (it must be equal in every entry)");
+}
+
+// (check_optim / check_loss, called without a name, refused entry k: their message behind the entry point's name and the net)
+static int net_refused(azg_trainer* t, const char* who, int k, int rc) {
+    t->err = std::string(who) + " (net " + std::to_string(k) + ")" + t->err;
+    return rc;
+}
+
+// Entry 0 has passed the *_opt call's checks.  Here: entries 1 .. n_nets - 1 equal entry 0 where they must; then every entry goes
+// through check_optim / check_loss for every minibatch (count[m] rows, Adam steps + m) -- the expressions of the one-net call, so
+// the bias corrections and every derived factor are that call's -- and what they return fills the host table.  (They are called with
+// an empty name, which a refusal gets from net_refused: a call that passes builds no message string per net.)  opts or cfgs may be
+// NULL (a call without that kind of entry).  Nothing is launched or written to the device.
+static int plan_nets(azg_trainer* t, const char* who, const float* params, const azg_optim* opts, const azg_loss_cfg* cfgs,
+                     const azg_alpha_state* alpha_state, bool stepped, int32_t n_actions, const int* count, int M) {
+    const int K = t->n_nets;
+    for (int k = 1; k < K; ++k) {
+        if (opts) {
+            const azg_optim &a = opts[0], &b = opts[k];
+            if (b.struct_size != a.struct_size) return nets_differ(t, who, "azg_optim.struct_size", k);
+            if (b.kind != a.kind) return nets_differ(t, who, "azg_optim.kind", k);
+            if (b.state0 != a.state0) return nets_differ(t, who, "azg_optim.state0", k);
+            if (b.state1 != a.state1) return nets_differ(t, who, "azg_optim.state1", k);
+            if (b.grad_norms != a.grad_norms) return nets_differ(t, who, "azg_optim.grad_norms", k);
+            if (b.step != a.step) return nets_differ(t, who, "azg_optim.step", k);
+        }
+        if (cfgs) {
+            const azg_loss_cfg &a = cfgs[0], &b = cfgs[k];
+            if (b.struct_size != a.struct_size) return nets_differ(t, who, "azg_loss_cfg.struct_size", k);
+            if (b.kind != a.kind) return nets_differ(t, who, "azg_loss_cfg.kind", k);
+            if (b.head != a.head) return nets_differ(t, who, "azg_loss_cfg.head", k);
+            if (b.reduction != a.reduction) return nets_differ(t, who, "azg_loss_cfg.reduction", k);
+            if (!(b.action_bound == a.action_bound)) return nets_differ(t, who, "azg_loss_cfg.action_bound", k);
+        }
+    }
+    const size_t n = (size_t)M * (size_t)K;
+    t->nets_loss_off = opts ? n * sizeof(TrainOptD) : 0;
+    t->nets_host.resize(t->nets_loss_off + (cfgs ? n * sizeof(LossDims) : 0));
+    TrainOptD* od = reinterpret_cast<TrainOptD*>(t->nets_host.data());
+    LossDims* ld = reinterpret_cast<LossDims*>(t->nets_host.data() + t->nets_loss_off);
+    t->nets_any_norm = false;
+    for (int m = 0; m < M; ++m) {
+        azg_alpha_state st{};
+        if (stepped) { st = *alpha_state; st.step += m; }
+        for (int k = 0; k < K; ++k) {
+            if (opts) {
+                OptPlan pl;
+                if (int rc = check_optim(t, "", params, &opts[k], count[m], m, &pl)) return net_refused(t, who, k, rc);
+                od[(size_t)m * K + k] = pl.o;
+                t->nets_any_norm = t->nets_any_norm || pl.o.want_norm;
+            }
+            if (cfgs) {
+                if (int rc = check_loss(t, "", count[m], n_actions, &cfgs[k], stepped ? &st : alpha_state, &ld[(size_t)m * K + k]))
+                    return net_refused(t, who, k, rc);
+            }
+        }
+    }
+    return AZG_OK;
+}
+
+// The table to the device: one asynchronous copy on the trainer's stream, in front of the call's first launch.  nets_host stays as
+// it is until the call's synchronisation.
+static int upload_nets(azg_trainer* t, const char* who) {
+    const size_t bytes = t->nets_host.size();
+    if (int rc = grow(t, (void**)&t->nets_dev, &t->nets_bytes, bytes)) return rc;
+    const hipError_t up = hipMemcpyAsync(t->nets_dev, t->nets_host.data(), bytes, hipMemcpyHostToDevice, t->stream);
+    if (up != hipSuccess) return tfail(t, AZG_E_DEVICE, std::string(who) + ": " + hipGetErrorString(up));
+    return AZG_OK;
+}
+
+// minibatch m's launches with every net's own entry
+static void launch_loss_nets(azg_trainer* t, int m, int kind, const float* raw, const float* actions, const float* counts, const float* values,
+                             int n_rows, const azg_alpha_state* st, float* d_raw, float* losses) {
+    const bool tuned = kind == AZG_LOSS_A0C_TUNED;
+    const LossDims* table = reinterpret_cast<const LossDims*>(t->nets_dev + t->nets_loss_off) + (size_t)m * t->n_nets;
+    hipLaunchKernelGGL(train_loss_nets_kernel, dim3(t->n_nets), dim3(TR_LOSS_THREADS), 0, t->stream, table, raw, actions, counts, values, n_rows,
+                       tuned ? st->log_alpha : nullptr, tuned ? st->exp_avg : nullptr, tuned ? st->exp_avg_sq : nullptr, d_raw, losses,
+                       t->loss_rows, t->max_batch);
+}
+
+static void launch_backward_nets(azg_trainer* t, int m, float* params, const float* d_raw, int n_rows, const azg_optim* opts, float* grads) {
+    const TrainOptD* table = reinterpret_cast<const TrainOptD*>(t->nets_dev) + (size_t)m * t->n_nets;
+    float* gr = grads ? grads : t->grad_buf;
+    if (t->wide) {
+        tw_launch_backward_deferred_nets(t->wide, t->stream, t->n_nets, table, t->nets_any_norm, params, d_raw, n_rows, opts->state0,
+                                         opts->state1, gr, opts->grad_norms, t->scratch, t->norm_part);
+        return;
+    }
+    if (t->ln)
+        hipLaunchKernelGGL(train_backward_deferred_nets_kernel<true>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, table, params,
+                           d_raw, n_rows, opts->state0, opts->state1, gr, opts->grad_norms, t->scratch);
+    else
+        hipLaunchKernelGGL(train_backward_deferred_nets_kernel<false>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream,
+                           (const TrainDims&)t->d, table, params, d_raw, n_rows, opts->state0, opts->state1, gr, opts->grad_norms, t->scratch);
+}
+
 static int finish(azg_trainer* t, const char* who) {
     hipError_t rc = hipGetLastError();
     if (rc == hipSuccess) rc = hipStreamSynchronize(t->stream);
@@ -470,7 +580,8 @@ int azg_trainer_loss(azg_trainer* t, const float* raw, const float* actions, con
 
 static int step_impl(azg_trainer* t, const char* who, float* params, const float* obs, const float* actions, const float* counts,
                      const float* values, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg,
-                     const azg_alpha_state* alpha_state, const OptArg& oa, float* grads, float* raw_out, float* losses) {
+                     const azg_alpha_state* alpha_state, const OptArg& oa, float* grads, float* raw_out, float* losses,
+                     bool nets = false) {
     if (!t) return AZG_E_INVALID;
     if (!actions || !counts || !values || !losses) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
     if (int rc = check_forward(t, who, params, obs, n_rows)) return rc;
@@ -478,6 +589,8 @@ static int step_impl(azg_trainer* t, const char* who, float* params, const float
     if (int rc = check_loss(t, who, n_rows, n_actions, loss_cfg, alpha_state, &c)) return rc;
     OptPlan pl;
     if (int rc = check_opt_arg(t, who, params, oa, n_rows, 0, &pl)) return rc;
+    const int rows1 = n_rows;
+    if (nets) { if (int rc = plan_nets(t, who, params, oa.opt, loss_cfg, alpha_state, false, n_actions, &rows1, 1)) return rc; }
     DeviceScope scope(t->device_id);
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
     const size_t per = (size_t)t->n_nets * t->max_batch * t->d.NO;
@@ -485,11 +598,17 @@ static int step_impl(azg_trainer* t, const char* who, float* params, const float
     if (int rc = ensure(t, (void**)&t->d_raw_buf, per * sizeof(float))) return rc;
     if (!raw_out) { if (int rc = ensure(t, (void**)&t->raw_buf, per * sizeof(float))) return rc; }
     float* raw = raw_out ? raw_out : t->raw_buf;
+    if (nets) { if (int rc = upload_nets(t, who)) return rc; }
     t->fwd_rows = 0;
     t->step_rows = 0;
     launch_forward(t, params, obs, (int)n_rows, raw);
-    launch_loss(t, c, raw, actions, counts, values, (int)n_rows, alpha_state, t->d_raw_buf, losses);
-    launch_backward_arg(t, params, t->d_raw_buf, (int)n_rows, pl, oa, grads);
+    if (nets) {
+        launch_loss_nets(t, 0, c.kind, raw, actions, counts, values, (int)n_rows, alpha_state, t->d_raw_buf, losses);
+        launch_backward_nets(t, 0, params, t->d_raw_buf, (int)n_rows, oa.opt, grads);
+    } else {
+        launch_loss(t, c, raw, actions, counts, values, (int)n_rows, alpha_state, t->d_raw_buf, losses);
+        launch_backward_arg(t, params, t->d_raw_buf, (int)n_rows, pl, oa, grads);
+    }
     if (int rc = finish(t, who)) return rc;
     t->step_rows = n_rows;
     return AZG_OK;
@@ -511,7 +630,7 @@ int azg_trainer_step_opt(azg_trainer* t, float* params, const float* obs, const 
 
 static int epoch_impl(azg_trainer* t, const char* who, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
                       int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const OptArg& oa,
-                      double* loss_sums, int32_t* n_minibatches) {
+                      double* loss_sums, int32_t* n_minibatches, bool nets = false) {
     if (!t) return AZG_E_INVALID;
     const std::string w(who);
     const bool no_opt = oa.opt_form ? !oa.opt : (!oa.rms || !oa.square_avg);
@@ -550,6 +669,7 @@ static int epoch_impl(azg_trainer* t, const char* who, float* params, const azg_
         if (int rc = check_loss(t, who, count[m], A, loss_cfg, stepped ? &st : alpha_state, &dims[m])) return rc;
         if (int rc = check_opt_arg(t, who, params, oa, count[m], m, &plans[m])) return rc;
     }
+    if (nets) { if (int rc = plan_nets(t, who, params, oa.opt, loss_cfg, alpha_state, stepped, A, count.data(), M)) return rc; }
     const size_t K = (size_t)t->n_nets;
     for (size_t e = 0; e < K * (size_t)n_order; ++e)
         if (order[e] < 0 || order[e] >= rows->rows_per_net) return tfail(t, AZG_E_INVALID, w + ": an order entry is outside 0 .. rows_per_net - 1");
@@ -571,6 +691,7 @@ static int epoch_impl(azg_trainer* t, const char* who, float* params, const azg_
     g.group_stride = rows->group_stride; g.net_stride = rows->net_stride;
     t->fwd_rows = 0;
     t->step_rows = 0;
+    if (nets) { if (int rc = upload_nets(t, who)) return rc; }
     const hipError_t up = hipMemcpyAsync(t->order_buf, order, K * (size_t)n_order * sizeof(int32_t), hipMemcpyHostToDevice, t->stream);
     if (up != hipSuccess) return tfail(t, AZG_E_DEVICE, w + ": " + hipGetErrorString(up));
     for (int m = 0; m < M; ++m) {
@@ -578,9 +699,14 @@ static int epoch_impl(azg_trainer* t, const char* who, float* params, const azg_
         hipLaunchKernelGGL(train_gather_kernel, dim3((B + TR_GATHER_THREADS / 64 - 1) / (TR_GATHER_THREADS / 64), t->n_nets),
                            dim3(TR_GATHER_THREADS), 0, t->stream, g, rows->rows, t->order_buf, first[m], B, obs, actions, counts, values);
         launch_forward(t, params, obs, B, t->raw_buf);
-        launch_loss(t, dims[m], t->raw_buf, actions, counts, values, B, alpha_state, t->d_raw_buf,
-                    t->loss_table + (size_t)m * K * AZG_LOSS_SLOTS);
-        launch_backward_arg(t, params, t->d_raw_buf, B, plans[m], oa, nullptr);
+        float* mb_losses = t->loss_table + (size_t)m * K * AZG_LOSS_SLOTS;
+        if (nets) {
+            launch_loss_nets(t, m, dims[m].kind, t->raw_buf, actions, counts, values, B, alpha_state, t->d_raw_buf, mb_losses);
+            launch_backward_nets(t, m, params, t->d_raw_buf, B, oa.opt, nullptr);
+        } else {
+            launch_loss(t, dims[m], t->raw_buf, actions, counts, values, B, alpha_state, t->d_raw_buf, mb_losses);
+            launch_backward_arg(t, params, t->d_raw_buf, B, plans[m], oa, nullptr);
+        }
     }
     const int n_sums = t->n_nets * AZG_LOSS_SLOTS;
     hipLaunchKernelGGL(train_loss_sum_kernel, dim3((n_sums + 63) / 64), dim3(64), 0, t->stream, t->loss_table, M, n_sums, loss_sums);
@@ -602,6 +728,54 @@ int azg_trainer_epoch_opt(azg_trainer* t, float* params, const azg_epoch_rows* r
                           double* loss_sums, int32_t* n_minibatches) {
     return epoch_impl(t, "azg_trainer_epoch_opt", params, rows, order, n_order, batch_size, loss_cfg, alpha_state,
                       OptArg{true, nullptr, nullptr, opt}, loss_sums, n_minibatches);
+}
+
+int azg_trainer_backward_step_nets(azg_trainer* t, float* params, const float* d_raw, int32_t n_rows, const azg_optim* opts, float* grads) {
+    if (!t) return AZG_E_INVALID;
+    const char* who = "azg_trainer_backward_step_nets";
+    if (!d_raw) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
+    OptPlan pl;
+    if (int rc = check_optim(t, who, params, opts, n_rows, 0, &pl)) return rc;
+    const int rows1 = n_rows;
+    if (int rc = plan_nets(t, who, params, opts, nullptr, nullptr, false, 0, &rows1, 1)) return rc;
+    if (t->fwd_rows != n_rows) return tfail(t, AZG_E_STATE, std::string(who) + ": needs azg_trainer_forward of the same n_rows first");
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    if (int rc = upload_nets(t, who)) return rc;
+    t->fwd_rows = 0;
+    launch_backward_nets(t, 0, params, d_raw, (int)n_rows, opts, grads);
+    return finish(t, who);
+}
+
+int azg_trainer_loss_nets(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values, int32_t n_rows,
+                          int32_t n_actions, const azg_loss_cfg* cfgs, const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
+    if (!t) return AZG_E_INVALID;
+    const char* who = "azg_trainer_loss_nets";
+    if (!raw || !actions || !counts || !values || !d_raw || !losses) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
+    LossDims c;
+    if (int rc = check_loss(t, who, n_rows, n_actions, cfgs, alpha_state, &c)) return rc;
+    const int rows1 = n_rows;
+    if (int rc = plan_nets(t, who, nullptr, nullptr, cfgs, alpha_state, false, n_actions, &rows1, 1)) return rc;
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    if (int rc = ensure(t, (void**)&t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch * sizeof(double))) return rc;
+    if (int rc = upload_nets(t, who)) return rc;
+    launch_loss_nets(t, 0, c.kind, raw, actions, counts, values, (int)n_rows, alpha_state, d_raw, losses);
+    return finish(t, who);
+}
+
+int azg_trainer_step_nets(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
+                          int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfgs, const azg_alpha_state* alpha_state,
+                          const azg_optim* opts, float* grads, float* raw_out, float* losses) {
+    return step_impl(t, "azg_trainer_step_nets", params, obs, actions, counts, values, n_rows, n_actions, loss_cfgs, alpha_state,
+                     OptArg{true, nullptr, nullptr, opts}, grads, raw_out, losses, true);
+}
+
+int azg_trainer_epoch_nets(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
+                           int32_t batch_size, const azg_loss_cfg* loss_cfgs, const azg_alpha_state* alpha_state, const azg_optim* opts,
+                           double* loss_sums, int32_t* n_minibatches) {
+    return epoch_impl(t, "azg_trainer_epoch_nets", params, rows, order, n_order, batch_size, loss_cfgs, alpha_state,
+                      OptArg{true, nullptr, nullptr, opts}, loss_sums, n_minibatches, true);
 }
 
 int azg_trainer_read_d_raw(azg_trainer* t, int32_t n_rows, float* d_raw) {

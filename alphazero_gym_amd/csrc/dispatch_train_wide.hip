@@ -169,3 +169,16 @@ void tw_launch_backward_deferred(const TrainWide* w, hipStream_t stream, int n_n
     hipLaunchKernelGGL(train_wide_update_kernel, dim3((d.P + TW_UPDATE_SPAN - 1) / TW_UPDATE_SPAN, n_nets), dim3(TR_BWD_THREADS), 0, stream,
                        d.P, opt, params, state0, state1, grads, norms, partials);
 }
+
+void tw_launch_backward_deferred_nets(const TrainWide* w, hipStream_t stream, int n_nets, const TrainOptD* table, bool any_norm, float* params,
+                                      const float* d_raw, int n_rows, float* state0, float* state1, float* grads, float* norms,
+                                      float* scratch, double* partials) {
+    const TrainDimsW& d = w->d;
+    const TrainOpt unused{};   // (the layers' deferred form stores gradients and steps nothing)
+    if (d.layernorm) launch_layers<false, true>(d, stream, n_nets, unused, params, d_raw, n_rows, nullptr, grads, scratch);
+    else launch_layers<false, false>(d, stream, n_nets, unused, params, d_raw, n_rows, nullptr, grads, scratch);
+    if (any_norm)
+        hipLaunchKernelGGL(train_wide_norm_kernel, dim3(TW_NORM_CHAINS / 64, n_nets), dim3(64), 0, stream, d.P, grads, partials);
+    hipLaunchKernelGGL(train_wide_update_nets_kernel, dim3((d.P + TW_UPDATE_SPAN - 1) / TW_UPDATE_SPAN, n_nets), dim3(TR_BWD_THREADS), 0, stream,
+                       d.P, table, params, state0, state1, grads, norms, partials);
+}

@@ -335,6 +335,76 @@ __global__ __launch_bounds__(TR_BWD_THREADS) void train_backward_deferred_kernel
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the optimiser, settings per net
+// The *_nets entry points: every net has its own TrainOptD, element (minibatch, net) of a table in device memory that the host
+// filled before the first launch.  A workgroup copies its net's entry once at entry -- the address is the same in every lane -- and
+// from there on runs the deferred form's text with that copy in the kernel argument's place, so net k ends with the bits a one-net
+// launch with entry k gives.  The kernels above are not touched by it: the per-net forms have their own copy of the optimiser phase
+// (tr_optim_span, shared by this header's and train_wide.cuh's per-net kernel).
+
+// Norm tree, clip and update of the elements i0 .. i1 - 1 of one net, thread tid taking i0 + tid, i0 + tid + 1024, ...: the phase
+// behind train_backward_deferred_kernel's barrier, operation for operation.  my_part: this thread's partial chain of the squared
+// gradients (read only if o.want_norm).  write_norm: this workgroup stores the net's norm.
+__device__ __forceinline__ void tr_optim_span(const TrainOptD& o, double my_part, bool write_norm, float* norm_out, float* p, float* s0,
+                                              float* s1, const float* grads, int i0, int i1) {
+    const int tid = threadIdx.x;
+    float coef = 1.0f;
+    if (o.want_norm) {
+        __shared__ double part[TR_BWD_THREADS];
+        part[tid] = my_part;
+        __syncthreads();
+        for (int st = TR_BWD_THREADS / 2; st > 0; st >>= 1) {
+            if (tid < st) part[tid] = part[tid] + part[tid + st];
+            __syncthreads();
+        }
+        const float total = (float)sqrt(part[0]);
+        if (norm_out && write_norm && tid == 0) *norm_out = total;
+        if (o.clip != 0.0f) { const float c = o.clip / (total + 1e-6f); coef = c < 1.0f ? c : 1.0f; }
+    }
+    const bool clipped = o.clip != 0.0f;
+    if (o.kind == AZG_OPT_ADAM) {
+        for (int i = i0 + tid; i < i1; i += TR_BWD_THREADS) {
+            float g = grads[i];
+            if (clipped) g = g * coef;
+            double pv = (double)p[i];
+            tr_adam(pv, s1 + i, s0 + i, (double)g, o.lr, o.b1, o.b2, o.eps, o.wd, o.bc1, o.bc2_sqrt);
+            p[i] = (float)pv;
+        }
+    } else {
+        for (int i = i0 + tid; i < i1; i += TR_BWD_THREADS) {
+            float g = grads[i];
+            if (clipped) g = g * coef;
+            tr_update(o.rms, p, s0, nullptr, i, g);
+        }
+    }
+}
+
+// train_backward_deferred_kernel with the settings of net blockIdx.x from table[blockIdx.x].
+template <bool LN>
+__global__ __launch_bounds__(TR_BWD_THREADS) void train_backward_deferred_nets_kernel(typename TrainDimsOf<LN>::type d,
+                                                                                      const TrainOptD* __restrict__ table, float* params,
+                                                                                      const float* d_raw, int n_rows, float* state0,
+                                                                                      float* state1, float* grads_all, float* norms,
+                                                                                      float* scratch) {
+    const TrainOptD o = table[blockIdx.x];
+    {
+        float* square_avg = state0;
+#define TR_EMIT(idx, grad) ((void)sq, grads[idx] = (grad))
+#include "train_backward_layers.inc"
+#undef TR_EMIT
+    }
+    // every wave's gradient stores have completed before any wave passes the barrier and loads them
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const int net = blockIdx.x, tid = threadIdx.x, P = d.P;
+    const float* grads = grads_all + (size_t)net * P;
+    double acc = 0.0;
+    if (o.want_norm)
+        for (int i = tid; i < P; i += TR_BWD_THREADS) { const double gd = (double)grads[i]; acc = acc + gd * gd; }
+    tr_optim_span(o, acc, true, norms ? norms + net : nullptr, params + (size_t)net * P, state0 + (size_t)net * P,
+                  state1 ? state1 + (size_t)net * P : nullptr, grads, 0, P);
+}
+
 // ------------------------------------------------------------------------------------------------ losses
 // agent/population_trainer.py's population_terms / population_loss as one kernel: per row the summands of the losses and
 // d loss_k / d raw by hand, then per net the reductions over the rows and, for the tuned loss, the Adam step of log_alpha.
@@ -523,6 +593,51 @@ __global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_kernel(LossDims c,
     out[AZG_LOSS_ENTROPY] = (float)entropy;
     if (!tuned) { out[AZG_LOSS_ALPHA] = 0.0f; return; }
     // alpha_loss = mean(exp(log_alpha) * (entropy - target).detach()); its derivative by log_alpha is itself
+    const double alpha_loss = a * (sums[2] * c.inv_rows - c.target);
+    out[AZG_LOSS_ALPHA] = (float)alpha_loss;
+    double g = alpha_loss;
+    if (c.clip != 0.0) { const double f = c.clip / (fabs(g) + 1e-6); g = g * (f < 1.0 ? f : 1.0); }
+    double p = (double)la;
+    tr_adam(p, exp_avg + net, exp_avg_sq + net, g, c.lr, c.b1, c.b2, c.eps, c.wd, c.bc1, c.bc2_sqrt);
+    log_alpha[net] = (float)p;
+}
+
+// train_loss_kernel with the settings of net blockIdx.x from table[blockIdx.x] (azg_trainer_loss_nets; kind, head and the squashing
+// are the same in every entry).  The entry is copied once at entry; what follows is train_loss_kernel's own text, kept as a copy so
+// that the kernel above compiles to the code it always was.
+__global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_nets_kernel(const LossDims* __restrict__ table, const float* raw,
+                                                                          const float* actions, const float* counts, const float* values,
+                                                                          int n_rows, float* log_alpha, float* exp_avg, float* exp_avg_sq,
+                                                                          float* d_raw, float* losses, double* rows, int stride) {
+    const LossDims c = table[blockIdx.x];
+    const int net = blockIdx.x, tid = threadIdx.x, NO = 1 + c.nd;
+    const bool tuned = c.kind == AZG_LOSS_A0C_TUNED;
+    const float la = tuned ? log_alpha[net] : 0.0f;
+    const double alpha = tuned ? exp((double)la) : c.alpha;
+    double* rw = rows + (size_t)net * 3 * stride;
+    for (int row = tid; row < n_rows; row += TR_LOSS_THREADS) {
+        const size_t at = (size_t)net * n_rows + row;
+        double terms[3];
+        tr_loss_row(c, alpha, raw + at * NO, actions + at * c.A, counts + at * c.A, values[at], d_raw + at * NO, terms);
+        rw[row] = terms[0]; rw[stride + row] = terms[1]; rw[2 * stride + row] = terms[2];
+    }
+    __syncthreads();
+    __shared__ double sums[3];
+    if (tid < 3) sums[tid] = tr_colsum64(n_rows, [&](int r) { return rw[(size_t)tid * stride + r]; });
+    __syncthreads();
+    if (tid != 0) return;
+    float* out = losses + (size_t)net * AZG_LOSS_SLOTS;
+    const double policy = c.pc * (sums[0] * c.red), value = c.vc * (sums[1] * c.red);
+    if (c.kind == AZG_LOSS_ALPHAZERO) {
+        out[AZG_LOSS_TOTAL] = (float)(policy + value); out[AZG_LOSS_POLICY] = (float)policy; out[AZG_LOSS_VALUE] = (float)value;
+        out[AZG_LOSS_ENTROPY] = 0.0f; out[AZG_LOSS_ALPHA] = 0.0f;
+        return;
+    }
+    const double a = alpha;
+    const double entropy = a * (sums[2] * c.ent_red);
+    out[AZG_LOSS_TOTAL] = (float)((policy + entropy) + value); out[AZG_LOSS_POLICY] = (float)policy; out[AZG_LOSS_VALUE] = (float)value;
+    out[AZG_LOSS_ENTROPY] = (float)entropy;
+    if (!tuned) { out[AZG_LOSS_ALPHA] = 0.0f; return; }
     const double alpha_loss = a * (sums[2] * c.inv_rows - c.target);
     out[AZG_LOSS_ALPHA] = (float)alpha_loss;
     double g = alpha_loss;

@@ -417,3 +417,17 @@ __global__ __launch_bounds__(TR_BWD_THREADS) void train_wide_update_kernel(int P
         }
     }
 }
+
+// train_wide_update_kernel with the settings of net blockIdx.y from table[blockIdx.y] (the *_nets entry points): every workgroup of
+// a net copies the same entry once at entry, then runs train.cuh's tr_optim_span -- the text above -- on its span.  A net that
+// neither clips nor reports its norm never reads `partials`, whatever the other nets of the launch ask for.
+__global__ __launch_bounds__(TR_BWD_THREADS) void train_wide_update_nets_kernel(int P, const TrainOptD* __restrict__ table, float* params,
+                                                                                float* state0, float* state1, const float* grads_all,
+                                                                                float* norms, const double* partials) {
+    const TrainOptD o = table[blockIdx.y];
+    const int net = blockIdx.y;
+    const int i0 = blockIdx.x * TW_UPDATE_SPAN, i1 = i0 + TW_UPDATE_SPAN < P ? i0 + TW_UPDATE_SPAN : P;
+    const double mine = o.want_norm ? partials[(size_t)net * TW_NORM_CHAINS + threadIdx.x] : 0.0;
+    tr_optim_span(o, mine, blockIdx.x == 0, norms ? norms + net : nullptr, params + (size_t)net * P, state0 + (size_t)net * P,
+                  state1 ? state1 + (size_t)net * P : nullptr, grads_all + (size_t)net * P, i0, i1);
+}

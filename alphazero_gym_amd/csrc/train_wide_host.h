@@ -26,3 +26,8 @@ void tw_launch_backward(const TrainWide* w, hipStream_t stream, int n_nets, cons
                         float* square_avg, float* grads, float* scratch);
 void tw_launch_backward_deferred(const TrainWide* w, hipStream_t stream, int n_nets, const TrainOptD& opt, float* params, const float* d_raw,
                                  int n_rows, float* state0, float* state1, float* grads, float* norms, float* scratch, double* partials);
+// ... with every net's own settings: table = [n_nets] TrainOptD in device memory, filled by a copy enqueued on `stream` before this;
+// any_norm = some entry has want_norm set (the norm launch is made for all nets then).
+void tw_launch_backward_deferred_nets(const TrainWide* w, hipStream_t stream, int n_nets, const TrainOptD* table, bool any_norm, float* params,
+                                      const float* d_raw, int n_rows, float* state0, float* state1, float* grads, float* norms,
+                                      float* scratch, double* partials);

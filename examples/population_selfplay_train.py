@@ -51,6 +51,9 @@ def parse_args(argv=None):
     ap.add_argument("--hidden", type=int, nargs="+", default=[128, 128])
     ap.add_argument("--max-episode-length", type=int, default=200)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--lrs", type=float, nargs="+", default=None,
+                    help="a learning-rate sweep: one value per --seeds entry, in place of --lr.  The device trainers are then built "
+                         "with per_net=True (which implies optimizers='agents'): every net steps with its own lr in the same launches")
     ap.add_argument("--optimizer", choices=["rmsprop", "adam"], default="rmsprop",
                     help="every net's optimiser; adam: the reference's Adam settings (run.ADAM).  With adam or --grad-clip the device "
                          "trainers are built with optimizers='agents'")
@@ -75,6 +78,8 @@ def parse_args(argv=None):
                          "eval_return; every seed starts from the same states, so the numbers can be ranked (0: no evaluation)")
     ap.add_argument("--eval-rule", choices=["mode", "sample"], default="mode", help="the evaluation's action rule")
     a = ap.parse_args(argv)
+    if a.lrs is not None and len(a.lrs) != len(a.seeds):
+        ap.error(f"--lrs needs one value per --seeds entry ({len(a.seeds)}), got {len(a.lrs)}")
     why = check_population_shape(a)
     if why:
         ap.error(why)
@@ -96,9 +101,10 @@ def check_population_shape(a):
 def build_population(a):
     """One agent per seed (its initial weights drawn after torch.manual_seed(seed)) and the self-play engine of them all."""
     agents = []
-    for s in a.seeds:
+    for i, s in enumerate(a.seeds):
         torch.manual_seed(s)
-        agent, state_dim = build_agent(a.game, a.hidden, a.n_rollouts, a.device, a.lr, a.optimizer, a.grad_clip, a.layernorm)
+        lr = a.lrs[i] if a.lrs is not None else a.lr
+        agent, state_dim = build_agent(a.game, a.hidden, a.n_rollouts, a.device, lr, a.optimizer, a.grad_clip, a.layernorm)
         agents.append(agent)
     m = agents[0].mcts
     sp = run.PopulationSelfPlay([ag.nn for ag in agents], game=a.game, games_per_net=a.games_per_seed, n_rollouts=a.n_rollouts,
@@ -121,7 +127,8 @@ def train(a, log=print, on_rows=None, on_end=None):
     if a.trainer != "torch":
         from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
         trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size), losses="torch" if a.trainer == "device" else "device",
-                                    optimizers="agents" if (a.optimizer != "rmsprop" or a.grad_clip) else "rmsprop",
+                                    optimizers="agents" if (a.optimizer != "rmsprop" or a.grad_clip or a.lrs is not None) else "rmsprop",
+                                    per_net=a.lrs is not None,
                                     layernorm=a.layernorm and not a.wide, wide=a.wide and not a.layernorm,
                                     wide_layernorm=a.wide and a.layernorm)
     t0 = time.time()

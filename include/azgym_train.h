@@ -23,7 +23,8 @@
  *
  * The optimiser is torch.optim.RMSprop applied in the backward kernel's tile epilogues (azg_rmsprop: the default, no gradient
  * clipping), or, through the *_opt entry points (azg_optim), RMSprop or torch.optim.Adam with an optional per-net clip_grad_norm_:
- * the backward launch then writes the gradients first and runs norm, clip and update as a phase after the last layer.
+ * the backward launch then writes the gradients first and runs norm, clip and update as a phase after the last layer.  The *_nets
+ * entry points take one azg_optim and one azg_loss_cfg per net, so the nets of one call can differ in every numeric setting.
  *
  * Supported nets: Linear + activation trunks of 1..3 hidden layers, widths multiples of 16 up to 256, in_dim <= 8, n_dist <= 16,
  * every AZG_ACT_* activation; LayerNorm after every trunk activation (nn.LayerNorm's defaults: eps 1e-5, affine) only from a trainer
@@ -277,6 +278,40 @@ int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows,
 int azg_trainer_epoch_opt(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
                           int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_optim* opt,
                           double* loss_sums, int32_t* n_minibatches);
+
+/* ---- settings per net: a learning-rate (or clip, tau, entropy coefficient ...) sweep in one call ---- */
+
+/* The four *_nets entry points are azg_trainer_backward_step_opt, azg_trainer_loss, azg_trainer_step_opt and azg_trainer_epoch_opt
+ * with HOST arrays of n_nets entries, entry k for net k, where those take one struct.  They work on every trainer handle.
+ *   may differ per net   azg_optim: lr, eps, weight_decay, alpha, beta1, beta2, grad_clip
+ *                        azg_loss_cfg: tau, policy_coeff, value_coeff, alpha, target_entropy, alpha_lr, alpha_beta1, alpha_beta2,
+ *                        alpha_eps, alpha_weight_decay, alpha_clip
+ *   equal in every entry azg_optim: struct_size, kind, state0, state1, grad_norms, step (the state arrays are [n_nets][P] as before);
+ *                        azg_loss_cfg: struct_size, kind, head, reduction, action_bound.  An entry k >= 1 that differs from entry 0
+ *                        in one of them: AZG_E_INVALID, the message names the field and k; this is checked before the entries'
+ *                        own values.
+ * Every entry passes the checks of the *_opt call with their codes (entry 0 first, as that call would make them; the message of a
+ * later entry names its net).  All checks are made before the first launch: on an error nothing is written.
+ * Net k's outputs -- params, state0 / state1, grads, grad_norms, d_raw, losses, log_alpha and its Adam state, an epoch's loss_sums --
+ * are bit for bit what a one-net trainer of the same shape, given entry k through the *_opt entry point, produces from net k's
+ * slices; n_nets identical entries give the *_opt call's bits.  The backward pass always takes its deferred form (whose gradients
+ * and RMSprop arithmetic are the fused form's, see azg_optim), and the norm, the clip and the bias corrections are per net: a net
+ * with grad_clip == 0 is not clipped because another net is, and Adam's 1 - beta^t is computed on the host from entry k's betas.
+ * The launch-ready settings of every (minibatch, net) go to a device table of the trainer (grown on demand; a failed allocation is
+ * an error before any launch) in one asynchronous copy on the trainer's stream in front of the first launch; every workgroup reads
+ * its net's entry from there.  An epoch uploads all its minibatches' entries at once and still synchronises once. */
+int azg_trainer_backward_step_nets(azg_trainer* t, float* params, const float* d_raw, int32_t n_rows, const azg_optim* opts /* [n_nets] */,
+                                   float* grads);
+int azg_trainer_loss_nets(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values, int32_t n_rows,
+                          int32_t n_actions, const azg_loss_cfg* cfgs /* [n_nets] */, const azg_alpha_state* alpha_state, float* d_raw,
+                          float* losses);
+int azg_trainer_step_nets(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
+                          int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfgs /* [n_nets] */,
+                          const azg_alpha_state* alpha_state, const azg_optim* opts /* [n_nets] */, float* grads, float* raw_out,
+                          float* losses);
+int azg_trainer_epoch_nets(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
+                           int32_t batch_size, const azg_loss_cfg* loss_cfgs /* [n_nets] */, const azg_alpha_state* alpha_state,
+                           const azg_optim* opts /* [n_nets] */, double* loss_sums, int32_t* n_minibatches);
 
 #ifdef __cplusplus
 }

@@ -37,7 +37,15 @@ report of the wide kernels:
 --wide --layernorm measures PopulationTrainer(wide_layernorm=True) on the same nets with LayerNorm trunks (1, 4, 16 of the 4x1024 nets,
 1 ... 256 of the 2x512 ones) against the loop of agent.update calls on those agents, and beside it the same nets without LayerNorm
 on PopulationTrainer(wide=True) from the same run:
-    python tools/population_train_latency.py --wide --layernorm [--epoch]    (writes profiles/population_train_latency_wide_layernorm.txt)"""
+    python tools/population_train_latency.py --wide --layernorm [--epoch]    (writes profiles/population_train_latency_wide_layernorm.txt)
+
+--per-net measures a learning-rate sweep, K nets with K different lr, four ways in one process: (a) PopulationTrainer(per_net=True,
+optimizers="agents", losses="device").update, every net reading its own settings from the trainer's device table; (b) the same
+trainer without per_net on agents of one lr (the shared-settings deferred step); (c) K one-net PopulationTrainers stepped in turn;
+(d) the loop of agent.update calls.  CartPole 2x128 at K = 1, 8, 64, 256 and Pendulum 4x1024 (wide=True) at K = 1, 4, 16.  (a) and
+(b) are measured --rounds times in turn; the spread of a figure is the largest minus the smallest of its medians, and the file says
+whether (a) stays within (b)'s spread.  --bench FILE appends bench.py result lines recorded elsewhere:
+    python tools/population_train_latency.py --per-net    (writes profiles/population_train_latency_pernet.txt)"""
 import argparse
 import os
 import subprocess
@@ -230,6 +238,87 @@ def measure_wide(name, K, B, reps, warmup, epoch_rows=0, layernorm=False):
     return out
 
 
+PERNET_CONFIGS = {"cartpole_2x128": ("discrete", 4, 2, [128, 128], {}, False, "1,8,64,256"),
+                  "pendulum_4x1024": ("continuous", 3, 8, [1024] * 4, dict(num_components=2), True, "1,4,16")}
+
+
+def measure_pernet(name, K, B, reps, warmup, rounds):
+    """((a) medians per round, (b) medians per round, (c), (d)) in ms: the per-net step with K different lr, the shared-settings
+    deferred step, K one-net trainers in turn, the loop of agent.update."""
+    kind, S, A, hidden, over, wide, _ = PERNET_CONFIGS[name]
+    base = run.CONTINUOUS_DEFAULTS if kind == "continuous" else run.DISCRETE_DEFAULTS
+    cfg = run._merge(base, dict(device="cuda", policy=dict(over, hidden_dimensions=hidden)))
+    env = make_game(cfg["game"])
+    stacked = _batches(kind, K, B, S, A)
+    per_net = [tuple(t[k] for t in stacked) for k in range(K)]
+    kw = dict(max_batch=max(512, 2 * B), losses="device", optimizers="agents", wide=wide)
+
+    def agents_of(sweep):
+        torch.manual_seed(0)
+        agents = [run.make_agent(kind, cfg, env, tree_id_base=k) for k in range(K)]
+        if sweep:
+            for k, ag in enumerate(agents):
+                ag.optimizer.param_groups[0]["lr"] *= 1.0 + k / K
+        return agents
+
+    nets = PT.PopulationTrainer(agents_of(True), per_net=True, **kw)
+    shared = PT.PopulationTrainer(agents_of(False), **kw)
+    t_a, t_b = [], []
+    for _ in range(rounds):
+        t_a.append(_median_ms(lambda: nets.update(stacked), reps, warmup))
+        t_b.append(_median_ms(lambda: shared.update(stacked), reps, warmup))
+    nets.close()
+    shared.close()
+    ones = [PT.PopulationTrainer([ag], **kw) for ag in agents_of(True)]
+    singles = [tuple(t[k:k + 1] for t in stacked) for k in range(K)]
+
+    def in_turn():
+        for tr, b in zip(ones, singles):
+            tr.update(b)
+
+    t_c = _median_ms(in_turn, reps, warmup)
+    for tr in ones:
+        tr.close()
+    agents = agents_of(True)
+
+    def loop():
+        for ag, b in zip(agents, per_net):
+            ag.update(b)
+
+    t_d = _median_ms(loop, reps, warmup)
+    return t_a, t_b, t_c, t_d
+
+
+def main_pernet(a):
+    lines = ["# tools/population_train_latency.py --per-net: one minibatch optimiser step of K nets with K different learning rates, batch %d, "
+             "one MI355X; median wall ms of %d repetitions after %d warm-up, every figure of a row in one process; (a) and (b) measured %d "
+             "times in turn, spread = largest - smallest of a figure's medians" % (a.batch, a.reps, a.warmup, a.rounds),
+             "# (a) PopulationTrainer(per_net=True, optimizers='agents', losses='device').update: azg_trainer_step_nets, settings from the device table",
+             "# (b) PopulationTrainer(optimizers='agents', losses='device').update on agents of one lr: azg_trainer_step_opt's deferred form",
+             "# (c) K one-net PopulationTrainers stepped in turn  (d) the loop of K agent.update calls"]
+    outside = []
+    for name in a.configs.split(","):
+        ks = a.ks if a.ks else PERNET_CONFIGS[name][6]
+        for K in [int(k) for k in ks.split(",")]:
+            t_a, t_b, t_c, t_d = measure_pernet(name, K, a.batch, a.reps, a.warmup, a.rounds)
+            med_a, med_b = float(np.median(t_a)), float(np.median(t_b))
+            spread = max(t_b) - min(t_b)
+            within = med_a - med_b <= spread
+            if not within:
+                outside.append(f"{name} K={K}: (a) {med_a:.3f} ms against (b) {med_b:.3f} ms + spread {spread:.3f} ms")
+            lines.append(f"  {name} K={K:4d} (a) per-net {med_a:8.3f} ms [{min(t_a):.3f} .. {max(t_a):.3f}]  (b) shared {med_b:8.3f} ms "
+                         f"[{min(t_b):.3f} .. {max(t_b):.3f}]  (a) - (b) {med_a - med_b:+7.3f} ms  spread of (b) {spread:6.3f} ms  "
+                         f"{'within' if within else 'OUTSIDE'}  (c) one-net trainers {t_c:9.3f} ms  {t_c / med_a:7.2f}x  "
+                         f"(d) agent.update loop {t_d:9.3f} ms  {t_d / med_a:7.2f}x")
+            print(lines[-1], flush=True)
+    lines.append("# target: (a) stays within the measured spread of (b).  "
+                 + ("It does at every point." if not outside else "It does NOT at: " + "; ".join(outside)))
+    if a.bench and os.path.exists(a.bench):
+        lines.append("# bench.py --gpus 1 of the parent commit's library and of this build's, in turn in one run (the search code is the same):")
+        lines += ["#   " + ln.rstrip() for ln in open(a.bench) if ln.strip()]
+    return lines
+
+
 def main_wide_layernorm(a):
     lines = ["# tools/population_train_latency.py --wide --layernorm%s: one minibatch optimiser step of K wide nets with LayerNorm trunks "
              "(PopulationTrainer(wide_layernorm=True), RMSprop fused into the backward launches), batch %d, one MI355X; median wall ms of %d "
@@ -419,8 +508,19 @@ def main():
     ap.add_argument("--grad-clip", type=float, default=0.0, help="a bound > 0: measure optimizers='agents' with gradient clipping")
     ap.add_argument("--layernorm", action="store_true", help="measure PopulationTrainer(layernorm=True) on LayerNorm agents")
     ap.add_argument("--wide", action="store_true", help="measure PopulationTrainer(wide=True) on 4x1024 and 2x512 nets (with --epoch: an epoch too)")
+    ap.add_argument("--per-net", action="store_true", help="measure PopulationTrainer(per_net=True) on a learning-rate sweep (see the docstring)")
+    ap.add_argument("--rounds", type=int, default=3, help="--per-net: how often (a) and (b) are measured in turn")
+    ap.add_argument("--bench", default=None, help="--per-net: a file of bench.py result lines to append")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.per_net:
+        a.ks = "" if a.ks == ap.get_default("ks") else a.ks
+        if a.configs == ap.get_default("configs"):
+            a.configs = ",".join(PERNET_CONFIGS)
+        out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "population_train_latency_pernet.txt")
+        with open(out, "w") as f:
+            f.write("\n".join(main_pernet(a)) + "\n")
+        return
     if a.wide and a.layernorm:
         a.ks = "" if a.ks == ap.get_default("ks") else a.ks   # (the default: 1, 4, 16 of the 4x1024 nets, 1 ... 256 of the 2x512 ones)
         if a.configs == ap.get_default("configs"):
