@@ -100,16 +100,20 @@ TEETH = {env: _find_teeth(env) for env in ENV}
 # ------------------------------------------------------------------------------------------------ hand-built networks
 # blob layout (synthetic.make_weights): per trunk layer W [h, k] and b [h]; value W [1, k], b [1]; dist W [n_dist, k], b [n_dist]
 
-def net_blob(in_dim, hidden, n_dist, value_bias=0.0, dist_bias=None, trunk=None, dist_w=None):
+def net_blob(in_dim, hidden, n_dist, value_bias=0.0, dist_bias=None, trunk=None, dist_w=None, trunk_bias=None):
     """A network of zeros with the given value bias and distribution bias; trunk: {(layer, unit, input): weight}, dist_w:
-    {(output, unit): weight}.  With a zero value row the value head returns the bias itself, bit for bit (a subnormal included)."""
+    {(output, unit): weight}, trunk_bias: {(layer, unit): bias}.  With a zero value row the value head returns the bias itself, bit
+    for bit (a subnormal included)."""
     parts, k = [], in_dim
     for li, h in enumerate(hidden):
-        W = np.zeros((h, k), np.float32)
+        W, b = np.zeros((h, k), np.float32), np.zeros(h, np.float32)
         for (l, u, i), w in (trunk or {}).items():
             if l == li:
                 W[u, i] = w
-        parts += [W.ravel(), np.zeros(h, np.float32)]
+        for (l, u), v in (trunk_bias or {}).items():
+            if l == li:
+                b[u] = v
+        parts += [W.ravel(), b]
         k = h
     parts += [np.zeros(k, np.float32), np.array([value_bias], np.float32)]
     Wd = np.zeros((n_dist, k), np.float32)

@@ -21,14 +21,16 @@ def _obs(env_id, state, n_obs):
     return out[:n_obs].copy()
 
 
-def _action(kw, ncomp, rule, raw, dist, seed, gid, t):
-    """The action of one game from its head outputs at step t."""
+def _action(kw, ncomp, rule, raw, dist, seed, gid, t, rec=None):
+    """The action of one game from its head outputs at step t.  rec (a dict, optional) receives the draws used: ``u`` (the float64
+    draw of the discrete walk, or the float32 draw that picks a mixture's component), ``eps`` and, with a mixture head, ``comp``."""
+    rec = {} if rec is None else rec
     sample = rule == "sample"
     if kw["mode"] == _capi.MODE_DISCRETE:
         logits = raw[1:]
         if not sample:
             return float(int(np.argmax(logits)))   # (first index on ties)
-        u = O.act_draw(seed, gid, t)[1]
+        u = rec["u"] = O.act_draw(seed, gid, t)[1]
         c = 0.0
         for a, p in enumerate(dist):
             c = c + float(p)   # float64 sum of the float32 probabilities, in index order
@@ -39,7 +41,7 @@ def _action(kw, ncomp, rule, raw, dist, seed, gid, t):
     if ncomp >= 2:
         mu, sigma, cum = dist[:ncomp], dist[ncomp:2 * ncomp], dist[2 * ncomp:3 * ncomp]
         if sample:
-            u = np.float32(O.gmm_u(seed, gid, t, 0))
+            u = rec["u"] = np.float32(O.gmm_u(seed, gid, t, 0))
             comp = ncomp - 1
             for i in range(ncomp):
                 if u < cum[i]:
@@ -48,14 +50,18 @@ def _action(kw, ncomp, rule, raw, dist, seed, gid, t):
         else:
             comp = int(np.argmax(raw[1 + 2 * ncomp:1 + 3 * ncomp]))
         m, s = mu[comp], sigma[comp]
+        rec["comp"] = comp
     else:
         m, s = dist[0], dist[1]
-    eps = O.normal(seed, gid, t, 0) if sample else 0.0
+    eps = rec["eps"] = O.normal(seed, gid, t, 0) if sample else 0.0
     return float(O.sample_action(m, s, eps, bound))
 
 
-def cpu_rollout(kw, desc, blob, G, max_len, rule, game_id_base, episode):
-    """One net's G episodes: dict of returns [G] float64, lengths, terminated, first_value."""
+def cpu_rollout(kw, desc, blob, G, max_len, rule, game_id_base, episode, trace=None):
+    """One net's G episodes: dict of returns [G] float64, lengths, terminated, first_value.
+    trace (a list, optional) receives one dict per game and step, in step order: ``game``, ``t``, ``raw`` (the head outputs), ``dist``
+    (what the heads derive from them), the draws used (``u`` / ``eps`` / ``comp``, see _action), ``action``, ``state`` (before the
+    step), ``next_state``, ``reward`` and ``done``."""
     o = O.OracleEngine(**dict(kw, n_trees=1, tree_id_base=0))
     o.set_weights(desc, blob)
     env_id, seed, n_obs = kw["env_id"], kw.get("seed", 34), o.s_obs
@@ -75,10 +81,14 @@ def cpu_rollout(kw, desc, blob, G, max_len, rule, game_id_base, episode):
         for i, j in enumerate(live):
             if t == 0:
                 first_value[j] = raw[i, 0]
-            a = _action(kw, ncomp, rule, raw[i], dist[i], seed, game_id_base + j, t)
+            rec = {}
+            a = _action(kw, ncomp, rule, raw[i], dist[i], seed, game_id_base + j, t, rec)
             nxt, r, done, _ = O.env_step(env_id, states[j], a)
             if o.s_env < 4:
                 nxt[o.s_env:] = 0.0
+            if trace is not None:
+                trace.append(dict(rec, game=j, t=t, raw=raw[i].copy(), dist=dist[i].copy(), action=np.float32(a), state=states[j].copy(),
+                                  next_state=nxt.copy(), reward=r, done=done))
             states[j] = nxt
             returns[j] = returns[j] + r
             lengths[j] = t + 1

@@ -59,9 +59,15 @@ def _reference(game, net, wseeds, scale, G, max_len, rule, episode=0):
 
 
 def _assert_equal(got, want, what):
+    """Equal by bit pattern (-0.0 is not +0.0), and no float is NaN (a NaN that both sides produce would have equal bits)."""
     for k in KEYS:
-        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, (what, k)
-        np.testing.assert_array_equal(got[k], want[k], err_msg=f"{what}: {k}")
+        g, w = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
+        assert g.dtype == w.dtype and g.shape == w.shape, (what, k)
+        if g.dtype.kind == "f":
+            assert not np.isnan(g).any() and not np.isnan(w).any(), f"{what}: {k} holds a NaN"
+            g, w = g.view(f"u{g.dtype.itemsize}"), w.view(f"u{w.dtype.itemsize}")
+        bad = np.argwhere(g != w)
+        assert bad.size == 0, f"{what}: {k} differs at {bad[:8].tolist()}: {got[k][tuple(bad[0])]!r} != {want[k][tuple(bad[0])]!r}"
 
 
 def _assert_form(e, form, what, fallbacks_before=0):
