@@ -91,6 +91,11 @@ class AzgRolloutInfo(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("form", C.c_int32), ("launches", C.c_int32), ("team_fallbacks", C.c_int32)]
 
 
+class AzgEvalInfo(C.Structure):
+    """include/azgym_eval.h: azg_eval_info"""
+    _fields_ = [("struct_size", C.c_int32), ("resident", C.c_int32), ("groups", C.c_int32), ("tiles", C.c_int32)]
+
+
 ROLLOUT_RULE = {"mode": 0, "sample": 1}   # include/azgym_eval.h: AZG_ROLLOUT_*
 ROLLOUT_FORM = {0: "group", 1: "team"}    # include/azgym_eval.h: AZG_ROLLOUT_FORM_*
 FINAL_SELECTION = {"max_visit": 0, "max_visits": 0, "max_value": 1}   # the reference's configs spell it both ways
@@ -117,6 +122,7 @@ SYMBOLS = [
 # them raise
 OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device",
                     "population_selfplay_begin", "policy_rollout", "policy_rollout_ex",
+                    "population_mlp_eval", "population_mlp_eval_device", "population_root_eval",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
                     "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch",
                     "trainer_backward_step_opt", "trainer_step_opt", "trainer_epoch_opt", "trainer_create_ex", "trainer_create_wide",
@@ -234,6 +240,13 @@ def bind(lib, prefix):
     if "policy_rollout_ex" in f:
         f["policy_rollout_ex"].argtypes = [vp, C.POINTER(AzgRolloutConfig), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(AzgRolloutInfo)]
+    if "population_mlp_eval" in f:
+        f["population_mlp_eval"].argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                             C.POINTER(C.c_float), C.POINTER(AzgEvalInfo)]
+    if "population_mlp_eval_device" in f:
+        f["population_mlp_eval_device"].argtypes = [vp, vp, C.c_size_t, C.c_int32, vp, vp, vp, C.POINTER(AzgEvalInfo)]
+    if "population_root_eval" in f:
+        f["population_root_eval"].argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     if "trainer_create" in f:   # include/azgym_train.h
         f["trainer_create"].argtypes = [C.c_int32, C.POINTER(AzgMlpDesc), C.c_int32, C.c_int32, C.POINTER(vp)]
         f["trainer_destroy"].argtypes = [vp]
@@ -350,6 +363,7 @@ class Engine:
     """One batched MCTS engine (B trees).  Mirrors MCTS*.__init__ kwargs (alphazero/search/mcts.py:316-327, 537-549)."""
 
     last_rollout_info = None   # what the last policy_rollout ran as (azg_rollout_info as a dict)
+    last_eval_info = None      # what the last population_mlp_eval* ran as (azg_eval_info as a dict)
 
     def __init__(self, fns, *, env_id, mode, n_trees, n_sims, c_uct, gamma, epsilon=0.0, num_actions=0, c_pw=1.0,
                  kappa=0.5, v_target="off_policy", reward_scale=PENDULUM_R_SCALE, action_bound=2.0, seed=34,
@@ -566,6 +580,73 @@ class Engine:
         self._check(self._f["mlp_eval"](self._h, _ptr(obs, C.c_float), n, _ptr(value, C.c_float), _ptr(dist, C.c_float),
                                         _ptr(raw, C.c_float)))
         return value, dist, raw
+
+    def _eval_rows(self, who, shape, shared):
+        """n of a population_mlp_eval* call with observations of ``shape``; a wrong shape raises before anything native is touched."""
+        K = int(getattr(self, "n_nets", 1))
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != (2 if shared else 3) or shape[-1] != self.s_obs or not (shared or shape[0] == K):
+            expected = f"[n, {self.s_obs}]" if shared else f"[{K}, n, {self.s_obs}]"
+            raise ValueError(f"{who}: obs has shape {list(shape)}, expected {expected}" + (" (shared=True)" if shared else ""))
+        return shape[-2]
+
+    def _eval_info(self, info):
+        self.last_eval_info = {"resident": int(info.resident), "groups": int(info.groups), "tiles": int(info.tiles)}
+
+    def population_mlp_eval(self, obs, shared=False):
+        """azg_population_mlp_eval (include/azgym_eval.h): every net of the engine evaluated in ONE launch, net k on ``obs[k]`` (obs
+        [n_nets, n, obs_dim]), or with ``shared`` every net on the same rows (obs [n, obs_dim]).  Returns (value [n_nets, n], dist
+        [n_nets, n, n_dist], raw [n_nets, n, 1 + n_dist]) with mlp_eval's bits per net; ``self.last_eval_info`` is then what ran
+        (``resident``, ``groups``, ``tiles``)."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        n = self._eval_rows("population_mlp_eval", obs.shape, shared)
+        fn = self._optional("population_mlp_eval")
+        K = int(getattr(self, "n_nets", 1))
+        value = np.empty((K, n), np.float32)
+        dist = np.empty((K, n, self.n_dist), np.float32)
+        raw = np.empty((K, n, 1 + self.n_dist), np.float32)
+        info = AzgEvalInfo()
+        info.struct_size = C.sizeof(AzgEvalInfo)
+        self._check(fn(self._h, _ptr(obs, C.c_float), n, 1 if shared else 0, _ptr(value, C.c_float), _ptr(dist, C.c_float),
+                       _ptr(raw, C.c_float), C.byref(info)))
+        self._eval_info(info)
+        return value, dist, raw
+
+    def population_mlp_eval_device(self, obs, shared=False, out=None):
+        """azg_population_mlp_eval_device: ``obs`` is a float32 torch tensor on the engine's GPU (shapes as population_mlp_eval); the
+        torch stream is synchronised once, then the kernel reads it in place and writes torch tensors (value, dist, raw) --
+        ``out``, a triple of contiguous float32 tensors of those shapes on the same GPU, or new ones.  Nothing crosses PCIe."""
+        import torch
+        n = self._eval_rows("population_mlp_eval_device", obs.shape, shared)
+        fn = self._optional("population_mlp_eval_device")
+        if not obs.is_cuda or obs.device.index != self.cfg.device_id or obs.dtype != torch.float32:
+            raise ValueError("population_mlp_eval_device: obs must be a float32 tensor on the engine's GPU")
+        obs = obs.contiguous()
+        K = int(getattr(self, "n_nets", 1))
+        shapes = ((K, n), (K, n, self.n_dist), (K, n, 1 + self.n_dist))
+        if out is None:
+            out = tuple(torch.empty(s, dtype=torch.float32, device=obs.device) for s in shapes)
+        else:
+            out = tuple(out)
+            for t, s in zip(out, shapes):
+                if tuple(t.shape) != s or t.dtype != torch.float32 or t.device != obs.device or not t.is_contiguous():
+                    raise ValueError(f"population_mlp_eval_device: out must be contiguous float32 tensors of shapes {shapes} on the engine's GPU")
+        torch.cuda.current_stream(obs.device).synchronize()
+        info = AzgEvalInfo()
+        info.struct_size = C.sizeof(AzgEvalInfo)
+        self._check(fn(self._h, C.c_void_p(obs.data_ptr()), n, 1 if shared else 0, *[C.c_void_p(t.data_ptr()) for t in out],
+                       C.byref(info)))
+        self._eval_info(info)
+        return out
+
+    def population_root_eval(self):
+        """azg_population_root_eval: root_eval for any number of nets -- (value [n_trees], dist [n_trees, n_dist]) of the last search,
+        rows in tree order k*T + j."""
+        fn = self._optional("population_root_eval")
+        value = np.empty((self.n_trees,), np.float32)
+        dist = np.empty((self.n_trees, self.n_dist), np.float32)
+        self._check(fn(self._h, _ptr(value, C.c_float), _ptr(dist, C.c_float)))
+        return value, dist
 
     def policy_rollout(self, episodes_per_net, max_episode_length, rule="mode", game_id_base=0, episode=0):
         """azg_policy_rollout_ex (include/azgym_eval.h; a library without it: azg_policy_rollout, widths up to 256 only):

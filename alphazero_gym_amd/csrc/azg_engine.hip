@@ -144,6 +144,7 @@ EngineOptions EngineOptions::from_env() {
     o.no_lds_state = getenv("AZG_NO_LDS_STATE") != nullptr;
     o.publish_always = digit("AZG_PUBLISH_TREES", 0) == 1;
     { const int t = num("AZG_ROLLOUT_TEAMS"); o.rollout_teams = t > 0 ? t : 0; }
+    { const int t = num("AZG_EVAL_GROUPS"); o.eval_groups = t > 0 ? t : 0; }
     return o;
 }
 
@@ -454,7 +455,7 @@ int azg_root_children(azg_engine* e, int32_t* child_n, double* child_state) {
 
 int azg_root_eval(azg_engine* e, float* value, float* dist) {
     if (!e) return AZG_E_INVALID;
-    if (e->n_nets > 1) return fail(e, AZG_E_UNSUPPORTED, "azg_root_eval: not available for populations (azg_set_population > 1)");
+    if (e->n_nets > 1) return fail(e, AZG_E_UNSUPPORTED, "azg_root_eval: not available for populations (azg_set_population > 1): azg_population_root_eval takes them");
     int rc = gather_results(e);
     if (rc) return rc;
     size_t B = e->cfg.n_trees;
@@ -465,7 +466,7 @@ int azg_root_eval(azg_engine* e, float* value, float* dist) {
 
 int azg_mlp_eval(azg_engine* e, const float* obs, size_t n, float* value, float* dist, float* raw) {
     if (!e || !obs) return AZG_E_INVALID;
-    if (e->n_nets > 1) return fail(e, AZG_E_UNSUPPORTED, "azg_mlp_eval: not available for populations (azg_set_population > 1): evaluate each net's policy");
+    if (e->n_nets > 1) return fail(e, AZG_E_UNSUPPORTED, "azg_mlp_eval: not available for populations (azg_set_population > 1): azg_population_mlp_eval evaluates every net");
     if (!e->mlp_ready) return fail(e, AZG_E_STATE, "azg_set_weights has not been called");
     if (n == 0) return AZG_OK;
     if (n > (size_t)1 << 24) return fail(e, AZG_E_INVALID, "too many observations in one call");

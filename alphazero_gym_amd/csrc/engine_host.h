@@ -1,7 +1,8 @@
 // engine_host.h -- the engine object behind the C ABI, the helpers its translation units share, the host-side rules every kernel form
 // shares, and the entry points of the kernel translation units.  The C ABI: azg_engine.hip (creation, roots, search, results, dump,
 // info), engine_weights.hip (weight re-layout, populations), engine_selfplay.hip (device self-play, the results kernel's launch),
-// engine_selftest.hip (probes), dispatch_rollout.hip (policy rollouts, with their kernel).  The search kernels are compiled in several translation units (dispatch_*.hip: one family of template
+// engine_selftest.hip (probes), dispatch_rollout.hip (policy rollouts, with their kernel), dispatch_population_eval.hip (a population's
+// batched inference, with its kernel).  The search kernels are compiled in several translation units (dispatch_*.hip: one family of template
 // instantiations each) so that the library builds in parallel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +33,7 @@ struct EngineOptions {
     int no_lds_state = 0;          // AZG_NO_LDS_STATE set: discrete LDS trees keep the expanded nodes' env states in the cold records only
     int publish_always = 0;        // AZG_PUBLISH_TREES=1: every search writes its LDS trees out in the global format (diagnostic tools)
     int rollout_teams = 0;         // AZG_ROLLOUT_TEAMS=n: at most n teams per launch of the team rollout (tests: several launches; 0: all that fit)
+    int eval_groups = 0;           // AZG_EVAL_GROUPS=g: workgroups per net of azg_population_mlp_eval, instead of its own cap (tests; 0: automatic)
     static EngineOptions from_env();   // (azg_engine.hip)
 };
 #define AZG_MAX_DEVICES 64    // per-device caches of kernel attributes (host side)
@@ -118,6 +120,7 @@ struct azg_engine : EngineQueue {
     DeviceAllocs ls_mem;
     int ls_hp = 0;
     DeviceAllocs eval_mem; float* d_eval = nullptr; size_t eval_floats = 0;   // scratch of azg_mlp_eval (grow-only)
+    DeviceAllocs peval_mem; float* d_peval = nullptr; size_t peval_floats = 0;   // scratch of azg_population_mlp_eval (grow-only)
     DeviceAllocs rollout_mem; char* d_rollout = nullptr; size_t rollout_bytes = 0;   // outputs of azg_policy_rollout (grow-only)
     std::vector<char> rollout_stage;                                                  // ... and their host copy
     // team rollouts (rollout_team.cuh) own their hand-off memory, grow-only: activations and head partials (ro_ls.act / parts, sized in

@@ -168,6 +168,22 @@ class PopulationMCTS:
     def root_children(self):
         return self.engine.root_children()
 
+    def root_eval(self):
+        """(value [n_trees], dist [n_trees, n_dist]) of the roots of the last search as their nets evaluated them, rows in tree order."""
+        return self.engine.root_eval() if self.n_models == 1 else self.engine.population_root_eval()   # (one model: the plain entry point)
+
+    def evaluate_observations(self, obs, shared: bool = False):
+        """Value and policy heads of EVERY model on given observations, in one launch and with the search's own arithmetic:
+        ``obs`` [n_models, n, obs_dim] (model k on ``obs[k]``), or with ``shared`` [n, obs_dim] (every model on the same rows).
+        A numpy array takes the host form and returns numpy arrays; a torch tensor on the engine's GPU is read in place and torch
+        tensors come back.  Returns (value [n_models, n], dist [n_models, n, n_dist], raw [n_models, n, 1 + n_dist])."""
+        self.sync_weights()
+        if hasattr(obs, "is_cuda"):
+            if obs.is_cuda:
+                return self.engine.population_mlp_eval_device(obs, shared=shared)
+            obs = obs.detach().numpy()
+        return self.engine.population_mlp_eval(obs, shared=shared)
+
     def close(self):
         self.engine.close()
 

@@ -1,5 +1,5 @@
-/* azgym_eval.h -- policy rollouts: whole episodes played by the network alone, no tree (an extension of azgym.h; same ABI
- * version).
+/* azgym_eval.h -- policy rollouts: whole episodes played by the network alone, no tree; and batched inference for every net of a
+ * population (azg_population_mlp_eval, below).  An extension of azgym.h; same ABI version.
  *
  * azg_policy_rollout plays episodes_per_net (G) episodes per net of the engine in ONE kernel launch, from reset to their end: the
  * raw policy's return, the number the reference's users read off a deployed net.  Game j of EVERY net starts at
@@ -77,6 +77,47 @@ typedef struct azg_rollout_info {
 
 int azg_policy_rollout_ex(azg_engine* e, const azg_rollout_config* cfg, double* returns, int32_t* lengths, int32_t* terminated,
                           float* first_value, azg_rollout_info* info /* may be NULL */);
+
+/* Batched inference for EVERY net of the engine in one launch: azg_mlp_eval for any n_nets (azg_set_population).
+ *
+ * Net k is evaluated on its own n observations, obs [n_nets][n][obs_dim]; with shared_obs != 0 obs is [n][obs_dim] and every net is
+ * evaluated on the same rows (uploaded once).  Outputs, each may be NULL: value [n_nets][n], dist [n_nets][n][n_dist] (azg_mlp_eval's
+ * distribution parameters), raw [n_nets][n][1 + n_dist] (the head outputs).  A row's outputs have the bits azg_mlp_eval gives on a
+ * one-net engine with net k's weights: they do not depend on n, n_nets, the row's position, the form of the call or the grid.  With
+ * n_nets == 1 both calls are azg_mlp_eval (same bits).
+ *
+ * One kernel launch of (groups, n_nets) workgroups: workgroup (g, k) reads net k's weights once -- into registers where the search keeps
+ * that shape resident (`resident`) -- and walks the 16-observation tiles g, g + groups, ... of net k.  groups = min(tiles, cap), the cap
+ * chosen so that the workgroups of a large call, over all nets, are all resident at once (the chip filled once); AZG_EVAL_GROUPS=g
+ * (read when the engine is created) replaces the cap, for tests.
+ *
+ * azg_population_mlp_eval takes host arrays and keeps device scratch of its own that only grows.  azg_population_mlp_eval_device takes
+ * obs / value / dist / raw in DEVICE memory on the engine's GPU: inputs complete when the call is made (their producer's stream
+ * synchronised), no staging and no host copy.  Either enqueues the kernel on the engine's stream and synchronises once: outputs are
+ * complete on return.  Both read the nets' weights and nothing else of the engine: they may be called between self-play steps, and after
+ * a search without spoiling azg_results, azg_root_children or a later azg_dump_tree.
+ *
+ * Errors (nothing is written): NULL e / obs, an info with a wrong struct_size, n_nets * n > 2^24, n_nets > 65535: AZG_E_INVALID; a net
+ * without weights: AZG_E_STATE.  n == 0: AZG_OK, nothing happens.  info (may be NULL) is written on success only.
+ * The CPU oracle does not export these: the tests hold a K-net engine against K single-net engines' azg_mlp_eval.
+ *
+ * azg_population_root_eval is azg_root_eval for any n_nets: the root's value [n_trees] and distribution parameters [n_trees][n_dist]
+ * of the last search, in the tree order of azg_results (net k: trees k*T .. k*T+T-1).  Each may be NULL. */
+typedef struct azg_eval_info {   /* written on success only */
+    int32_t struct_size;         /* checked */
+    int32_t resident;            /* 1: hidden weights register-resident (NREG > 0) */
+    int32_t groups;              /* workgroups per net */
+    int32_t tiles;               /* 16-observation tiles per net */
+} azg_eval_info;
+
+/* host arrays */
+int azg_population_mlp_eval(azg_engine* e, const float* obs, size_t n, int32_t shared_obs,
+                            float* value, float* dist, float* raw, azg_eval_info* info);
+/* the same with obs / value / dist / raw in DEVICE memory on the engine's GPU */
+int azg_population_mlp_eval_device(azg_engine* e, const float* obs, size_t n, int32_t shared_obs,
+                                   float* value, float* dist, float* raw, azg_eval_info* info);
+/* azg_root_eval for any n_nets: [n_trees] / [n_trees][n_dist], tree order as azg_results */
+int azg_population_root_eval(azg_engine* e, float* value, float* dist);
 
 #ifdef __cplusplus
 }

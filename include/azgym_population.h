@@ -8,7 +8,8 @@
  * network descriptor; they differ in their weights.
  * With n_nets > 1: azg_set_weights / _device return AZG_E_STATE; azg_search* and azg_selfplay_step return AZG_E_STATE until every
  * net has weights; azg_selfplay_begin / _ex (a population starts self-play with azg_population_selfplay_begin), azg_mlp_eval and
- * azg_root_eval return AZG_E_UNSUPPORTED; azg_set_population while self-play runs returns AZG_E_UNSUPPORTED.
+ * azg_root_eval return AZG_E_UNSUPPORTED (azg_population_mlp_eval and azg_population_root_eval, azgym_eval.h, take any n_nets);
+ * azg_set_population while self-play runs returns AZG_E_UNSUPPORTED.
  * Wide networks (hidden width, padded to a multiple of 64, >= 512).  Those an engine searches as teams of 32 trees / per-layer launches
  * -- two or more hidden layers, no LayerNorm, at most four inputs -- need T to be a multiple of 32, so that every team serves one net:
  * any other T makes azg_set_net_weights* return AZG_E_UNSUPPORTED (the message names T; the engine keeps the weights it had).  The

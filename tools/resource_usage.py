@@ -2,6 +2,8 @@
 """Compiler's register / scratch / LDS report for the kernels of one translation unit, plus static instruction counts from the
 gfx950 ISA it generates (no GPU needed):
     python tools/resource_usage.py dispatch_cartpole [filter] [extra hipcc flags]   -> one line per kernel instantiation
+    python tools/resource_usage.py inference                                       -> the inference kernels: mlp_eval_kernel and
+                                                                                      population_eval_kernel, every instantiation
 Columns: VGPR / AGPR / SGPR counts, spilled VGPRs and SGPRs (an SGPR spill is a v_writelane / v_readlane pair into a spare VGPR:
 no scratch memory, but instructions in the stream), scratch bytes per lane, occupancy, static LDS; then the kernel's static
 instruction mix: all | vector ALU (v_*, without MFMA and lane moves) | scalar ALU + branches (s_*, without waits / nops) | MFMA |
@@ -60,10 +62,18 @@ def instruction_mix(asm_path):
     return out
 
 
+GROUPS = {"inference": ["dispatch_mlp_eval", "dispatch_population_eval"]}   # a name for several translation units
+
+
 def main():
     tu = sys.argv[1] if len(sys.argv) > 1 else "dispatch_pendulum_large"
     flt = sys.argv[2] if len(sys.argv) > 2 else "kernel"
     extra = sys.argv[3:]
+    for one in GROUPS.get(tu, [tu]):
+        report(one, flt, list(extra))
+
+
+def report(tu, flt, extra):
     if tu in ("dispatch_pendulum_large", "dispatch_team_wide", "dispatch_mcc") and "-licm" not in " ".join(extra):   # (as alphazero_gym_amd/csrc/Makefile builds them)
         extra = extra + ["-mllvm", "-disable-machine-licm"]
     with tempfile.TemporaryDirectory() as tmp:
