@@ -120,7 +120,7 @@ SYMBOLS = [
 ]
 # entry points a library may lack (the tests' CPU oracle binds SYMBOLS only): bound when present, else the methods that need
 # them raise
-OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device",
+OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device", "set_net_search",
                     "population_selfplay_begin", "policy_rollout", "policy_rollout_ex",
                     "population_mlp_eval", "population_mlp_eval_device", "population_root_eval",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
@@ -128,6 +128,41 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "trainer_backward_step_opt", "trainer_step_opt", "trainer_epoch_opt", "trainer_create_ex", "trainer_create_wide",
                     "trainer_create_wide_ex",
                     "trainer_backward_step_nets", "trainer_loss_nets", "trainer_step_nets", "trainer_epoch_nets"]
+
+
+class AzgNetSearch(C.Structure):
+    """include/azgym_population.h: azg_net_search"""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("c_uct", C.c_double), ("gamma", C.c_double), ("epsilon", C.c_double),
+                ("c_pw", C.c_double), ("kappa", C.c_double)]
+
+
+NET_SEARCH_KEYS = ("c_uct", "gamma", "epsilon", "c_pw", "kappa")   # the MCTS settings a population's nets may each have their own of
+
+
+def net_search_entries(settings, n_nets, shared):
+    """The per-net settings of a population as K complete dicts: ``settings`` is a list of K dicts whose keys are a subset of
+    NET_SEARCH_KEYS; a missing key takes its value from ``shared`` (the engine's own settings)."""
+    settings = list(settings)
+    if len(settings) != n_nets:
+        raise ValueError(f"net_settings has {len(settings)} entries for {n_nets} nets: one per net")
+    out = []
+    for k, st in enumerate(settings):
+        unknown = sorted(set(st) - set(NET_SEARCH_KEYS))
+        if unknown:
+            raise ValueError(f"net_settings[{k}]: unknown keys {unknown}; per-net search settings are {list(NET_SEARCH_KEYS)}")
+        out.append({key: float(st.get(key, shared[key])) for key in NET_SEARCH_KEYS})
+    return out
+
+
+def widest_pw(entries, n_sims):
+    """The (c_pw, kappa) pair among ``entries`` (dicts) whose progressive widening reaches the most children within n_sims simulations
+    (the engine's Kmax): the pair an engine is created with so that every net fits.  The first such pair on a tie."""
+    best, best_k = None, -1
+    for st in entries:
+        k = max(pw_table(st["c_pw"], st["kappa"], n_sims))
+        if k > best_k:
+            best, best_k = (st["c_pw"], st["kappa"]), k
+    return best
 
 
 class AzgRmsprop(C.Structure):
@@ -226,6 +261,8 @@ def bind(lib, prefix):
             f[s] = fn
     if "set_population" in f:
         f["set_population"].argtypes = [vp, C.c_int32]
+    if "set_net_search" in f:
+        f["set_net_search"].argtypes = [vp, C.POINTER(AzgNetSearch), C.c_int32]
     if "set_net_weights" in f:
         f["set_net_weights"].argtypes = [vp, C.c_int32, C.POINTER(AzgMlpDesc), C.POINTER(C.c_float), C.c_size_t]
     if "set_net_weights_device" in f:
@@ -470,6 +507,21 @@ class Engine:
         when n_nets changes; 1 is the single-network engine."""
         self._check(self._optional("set_population")(self._h, int(n_nets)))
         self.n_nets = int(n_nets)
+
+    def set_net_search(self, settings):
+        """azg_set_net_search: net k searches with settings[k], a dict with all of c_uct, gamma, epsilon, c_pw, kappa (discrete mode
+        ignores the last two), instead of the engine's shared settings; None returns to those.  One entry per net of the population."""
+        fn = self._optional("set_net_search")
+        if settings is None:
+            self._check(fn(self._h, None, 0))
+            return
+        settings = list(settings)
+        arr = (AzgNetSearch * max(len(settings), 1))()
+        for k, st in enumerate(settings):
+            arr[k].struct_size = C.sizeof(AzgNetSearch)
+            for key in NET_SEARCH_KEYS:
+                setattr(arr[k], key, float(st[key]))
+        self._check(fn(self._h, arr, len(settings)))
 
     def set_net_weights(self, net, desc, blob):
         blob = np.ascontiguousarray(blob, dtype=np.float32)

@@ -25,9 +25,16 @@ class AgentPopulation:
 
     ``seeds``: agent k's ``np.random`` / ``random`` streams start as if seeded with seeds[k] (default: as the global streams stand
     now).  Every host-side draw of agent k -- its final action rule in ``act``, its buffer's reshuffle in ``train`` -- runs on its
-    own streams, which are saved and restored around it (``rng(k)``), so that K agents' draws do not interleave."""
+    own streams, which are saved and restored around it (``rng(k)``), so that K agents' draws do not interleave.
 
-    def __init__(self, agents: Sequence[Any], seeds: Optional[Sequence[int]] = None, tree_id_base: int = 0):
+    ``per_agent_search=True`` (opt-in): the agents may differ in ``mcts.c_uct`` / ``gamma`` / ``epsilon`` and (continuous) ``c_pw`` /
+    ``kappa``; agent k's tree is searched with its own values, still in the one launch (PopulationMCTS ``net_settings``).  Everything
+    else must still agree."""
+
+    PER_AGENT = _capi.NET_SEARCH_KEYS
+
+    def __init__(self, agents: Sequence[Any], seeds: Optional[Sequence[int]] = None, tree_id_base: int = 0,
+                 per_agent_search: bool = False):
         self.agents = list(agents)
         if not self.agents:
             raise ValueError("AgentPopulation needs at least one agent")
@@ -37,10 +44,14 @@ class AgentPopulation:
             self.discrete = False
         else:
             raise ValueError("AgentPopulation: all agents must be DiscreteAgents or all ContinuousAgents")
+        self.per_agent_search = bool(per_agent_search)
         keys = {self._settings(a) for a in self.agents}
         if len(keys) != 1:
-            raise ValueError("AgentPopulation: every agent must have the same MCTS settings (per-agent search hyper-parameters are not "
-                             "supported)")
+            if not self.per_agent_search:
+                raise ValueError("AgentPopulation: every agent must have the same MCTS settings (per-agent search hyper-parameters are not "
+                                 "supported)")
+            raise ValueError("AgentPopulation(per_agent_search=True): the agents may differ in c_uct, gamma, epsilon, c_pw and kappa only; "
+                             "n_rollouts, V_target_policy, seed, device and the other engine settings must agree")
         self.tree_id_base = int(tree_id_base)
         K = len(self.agents)
         if seeds is not None and len(seeds) != K:
@@ -63,7 +74,15 @@ class AgentPopulation:
     def _settings(self, agent) -> tuple:
         m = agent.mcts
         key = (type(m), m.n_rollouts, m.c_uct, m.gamma, m.epsilon, m.V_target_policy, m.seed, device_ordinal(m.device))
-        return key + tuple(sorted(m._engine_kwargs().items()))
+        if self.per_agent_search:   # (the five settings an agent may have its own of do not have to agree)
+            key = (type(m), m.n_rollouts, m.V_target_policy, m.seed, device_ordinal(m.device))
+        return key + tuple(sorted((k, v) for k, v in m._engine_kwargs().items() if not (self.per_agent_search and k in self.PER_AGENT)))
+
+    def _net_settings(self) -> Optional[List[Dict[str, float]]]:
+        """Each agent's own values of the per-agent search settings (None without ``per_agent_search``)."""
+        if not self.per_agent_search:
+            return None
+        return [{k: float(getattr(a.mcts, k)) for k in self.PER_AGENT if hasattr(a.mcts, k)} for a in self.agents]
 
     @contextlib.contextmanager
     def rng(self, k: int):
@@ -87,7 +106,8 @@ class AgentPopulation:
             self._pop = PopulationMCTS([a.nn for a in self.agents], trees_per_model=1, env_id=env_id,
                                        mode=_capi.MODE_DISCRETE if self.discrete else _capi.MODE_CONTINUOUS, n_rollouts=m.n_rollouts,
                                        c_uct=m.c_uct, gamma=m.gamma, epsilon=m.epsilon, V_target_policy=m.V_target_policy, seed=m.seed,
-                                       tree_id_base=self.tree_id_base, device_id=device_ordinal(m.device), **m._engine_kwargs())
+                                       tree_id_base=self.tree_id_base, device_id=device_ordinal(m.device), **m._engine_kwargs(),
+                                       **({"net_settings": self._net_settings()} if self.per_agent_search else {}))
             self._env_id = env_id
         return self._pop
 

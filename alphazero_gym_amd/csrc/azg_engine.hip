@@ -61,6 +61,7 @@ static hipError_t search_path(azg_engine* e, bool lockstep) {
         if constexpr (ENV == AZG_ENV_ACROBOT) return hipErrorInvalidValue;   // (six network inputs: never lock-step, use_lockstep)
         else return azg_lockstep_search<ENV>(e);
     }
+    if (e->net_search.rec) return e->HP <= 128 ? azg_persistent_search_nets<ENV, false>(e) : azg_persistent_search_nets<ENV, true>(e);
     return e->HP <= 128 ? azg_persistent_search<ENV, false>(e) : azg_persistent_search<ENV, true>(e);
 }
 static hipError_t search_launch(azg_engine* e, bool lockstep) {
@@ -202,15 +203,7 @@ static int engine_build(azg_engine* e) {
     const int ns = cfg->n_sims;
     std::vector<int> pw(ns + 2, 0);
     if (cfg->mode == AZG_MODE_CONTINUOUS) {
-        int kmax = 1;
-        for (int n = 0; n < ns + 2; ++n) {
-            // NodeContinuous.check_pw (states.py:271-273): python float pow + math.ceil, evaluated on the host with libm
-            double v = std::ceil(cfg->c_pw * std::pow((double)(n + 1), cfg->kappa));
-            if (v > 1e6) v = 1e6;
-            pw[n] = (int)v;
-            if (n < ns && pw[n] > kmax) kmax = pw[n];
-        }
-        e->Kmax = kmax;
+        e->Kmax = azg_pw_table(cfg->c_pw, cfg->kappa, ns, pw);
         e->R = ns + 2;
         e->nd = 2;
     } else {
@@ -293,7 +286,7 @@ int azg_engine_create(const azg_config* cfg, azg_engine** out) {
     if (cfg->tie_break != AZG_TIE_FIRST && cfg->tie_break != AZG_TIE_RANDOM) return fail(nullptr, AZG_E_INVALID, "unknown tie_break");
     // progressive widening (states.py:271-275): ceil(c_pw (n + 1)^kappa) children; with c_pw <= 0 no node is ever entitled to a child and the
     // reference's first selection takes the arg-max of an empty list (helpers.py:30-52 raises)
-    if (cfg->mode == AZG_MODE_CONTINUOUS && !(cfg->c_pw > 0.0 && cfg->c_pw < 1e6 && cfg->kappa >= 0.0 && cfg->kappa <= 8.0))
+    if (cfg->mode == AZG_MODE_CONTINUOUS && !azg_pw_params_ok(cfg->c_pw, cfg->kappa))
         return fail(nullptr, AZG_E_INVALID, "c_pw must be > 0 and kappa >= 0 (progressive widening: ceil(c_pw (n + 1)^kappa) children)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, AZG_E_DEVICE, "no HIP device available");
@@ -343,6 +336,11 @@ int azg_search_resident(azg_engine* e) {
     if (!e->mlp_ready)
         return fail(e, AZG_E_STATE, e->n_nets > 1 ? "azg_set_net_weights has not been called for every net of the population"
                                                  : "azg_set_weights has not been called");
+    // per-net settings exist in search_kernel's form for widths up to 256 only: the team kernel, the per-layer launches and the wide
+    // networks' one-launch kernels all search with the engine's shared settings
+    if (e->net_search.rec && e->HP >= 512)
+        return fail(e, AZG_E_UNSUPPORTED, "per-net search settings (azg_set_net_search) need a padded hidden width of at most 256: nets of width >= 512 "
+                                          "search with the engine's shared settings only (azg_set_net_search(e, NULL, 0) returns to them)");
     ON_DEVICE(e);
     e->P.search_idx = e->search_idx;
     e->last_search_idx = e->search_idx;
@@ -562,7 +560,7 @@ static int kernel_name(const azg_engine* e, char* buf, size_t n) {
     const char* gmm = (env != AZG_ENV_CARTPOLE && e->P.ncomp >= 2) ? "true" : "false";
     const LaunchRecord& r = e->last;
     switch (r.form) {
-        case AZG_FORM_PERSISTENT: return snprintf(buf, n, "search_kernel<%d, %d, %d, %d, %s, %d, %d, %d, %d>", env, e->HP, e->nreg, r.tree_lds, gmm, r.waves, r.groups, r.tile_trees, r.spec);
+        case AZG_FORM_PERSISTENT: return snprintf(buf, n, r.nets ? "search_kernel_nets<%d, %d, %d, %d, %s, %d, %d, %d, %d>" : "search_kernel<%d, %d, %d, %d, %s, %d, %d, %d, %d>", env, e->HP, e->nreg, r.tree_lds, gmm, r.waves, r.groups, r.tile_trees, r.spec);
         case AZG_FORM_PER_LAYER: return snprintf(buf, n, "ls_tree_kernel<%d, ...> + ls_layer0_kernel + ls_hidden_tiled_kernel<%d, ...> per simulation step", env, e->HP);
         case AZG_FORM_TEAM: return snprintf(buf, n, "ls_team_kernel<%d, %d, %s, %d, %d, %d, %d, %d%s>", env, e->HP, gmm, r.tree_lds, r.team_kc, r.team_minb, r.spec, r.team_tt,
                                             r.team_pop ? ", true" : "");   // (a population's instantiation: POP)

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -46,6 +47,7 @@ struct LaunchRecord {
     int waves = 0, groups = 0, tile_trees = 0;   // search_kernel: waves / tree groups per workgroup, trees per group (16, or 8 / 4)
     int team_kc = 0, team_minb = 0, team_tt = 0, team_parts = 0;   // team kernel: chunk length, workgroups per CU, trees per team, launches
     int team_pop = 0;                         // ... and its population instantiation (team.cuh: POP)
+    int nets = 0;                             // search_kernel_nets: the launch took the per-net settings table (azg_set_net_search)
     int timed = 0;                            // the launch recorded ev0 / ev1 itself (hipExtLaunchKernelGGL)
 };
 
@@ -135,6 +137,8 @@ struct azg_engine : EngineQueue {
     int redo_ok = 0;         // roots, carried counts and weights are still the ones the last search ran on: azg_dump_tree may re-run it
     int n_nets = 1;          // azg_set_population: the trees split into n_nets nets of n_trees / n_nets trees (1: one network)
     std::vector<char> net_have = std::vector<char>(1, 0);   // net k has weights (azg_set_net_weights); d_wblob holds n_nets blocks of w_floats
+    // azg_set_net_search: per-net MCTS settings.  net_search.rec != nullptr: the engine carries a table and searches with search_kernel_nets
+    DeviceAllocs net_search_mem; NetSearchTable net_search{};
     DeviceAllocs stamp_mem; size_t stamp_n = 0;   // rows of the diagnostic stamp buffer (P.stamps)
     uint32_t last_search_idx = 0;   // the search index the last search ran under (azg_dump_tree re-runs it with this one)
     float ms_kept = 0.0f; int ms_kept_valid = 0;   // kernel time of the last search, kept across azg_dump_tree's re-run of it
@@ -185,6 +189,22 @@ static inline long azg_padded_trees(const azg_engine* e, int tpw) {
     const long T = e->cfg.n_trees / e->n_nets;
     return (long)e->n_nets * ((T + tpw - 1) / tpw * tpw);
 }
+
+// Progressive widening (NodeContinuous.check_pw, states.py:271-273: python float pow + math.ceil, evaluated on the host with libm): the
+// children a node with n visits is entitled to, n = 0 .. n_sims + 1, into pw; returns the largest entitlement a search reaches (Kmax).
+static inline int azg_pw_table(double c_pw, double kappa, int n_sims, std::vector<int>& pw) {
+    pw.assign((size_t)n_sims + 2, 0);
+    int kmax = 1;
+    for (int n = 0; n < n_sims + 2; ++n) {
+        double v = std::ceil(c_pw * std::pow((double)(n + 1), kappa));
+        if (v > 1e6) v = 1e6;
+        pw[n] = (int)v;
+        if (n < n_sims && pw[n] > kmax) kmax = pw[n];
+    }
+    return kmax;
+}
+// azg_engine_create's rule for the widening parameters (continuous mode)
+static inline bool azg_pw_params_ok(double c_pw, double kappa) { return c_pw > 0.0 && c_pw < 1e6 && kappa >= 0.0 && kappa <= 8.0; }
 
 // Lock-step shaped: a network an unforced engine searches on the team / per-layer path (padded width HP >= 512, at least two hidden
 // layers, no LayerNorm, at most four inputs -- those kernels' first layer takes one k-step).  Every other wide network runs on the
@@ -252,6 +272,7 @@ struct KernelAttrs {
 // in the dispatch_*.hip translation units.  hipErrorInvalidValue: no kernel for this width; hipErrorNotReady (team kernel): its workgroups
 // cannot all be resident, use the per-layer launches.
 template <int ENV, bool WIDE> hipError_t azg_persistent_search(azg_engine* e);   // search_kernel, widths up to 128 / 256 and up (dispatch.cuh)
+template <int ENV, bool WIDE> hipError_t azg_persistent_search_nets(azg_engine* e);   // the same as search_kernel_nets (per-net settings, widths up to 256)
 template <int ENV> hipError_t azg_lockstep_search(azg_engine* e);   // wide networks: the team kernel, else per-layer launches (ls_dispatch.cuh)
 template <int ENV> hipError_t azg_team_search(azg_engine* e);       // (team_dispatch.cuh)
 // the team kernel's forms for more than two 32-tree workgroups per CU (config E's network; team_dispatch.cuh); dry: residency check only

@@ -329,10 +329,75 @@ int azg_set_population(azg_engine* e, int32_t n_nets) {
     // every weight goes: the next search needs the weights of every net again
     e->wblob_mem.clear();
     e->d_wblob = nullptr; e->w_floats = 0;
+    // ... and so do per-net search settings: their table has one entry per net of the old split
+    e->net_search = NetSearchTable{};
+    e->net_search_mem.clear();
     e->n_nets = n_nets;
     e->net_have.assign(n_nets, 0);
     e->mlp_ready = 0; e->results_valid = 0; e->redo_ok = 0; e->searched = 0;
     e->P.net_T = e->cfg.n_trees / n_nets; e->P.net_wstride = 0;
+    return AZG_OK;
+}
+
+// Per-net MCTS settings: validated on the host, then one record and one widening table per net on the device (records.h:
+// NetSearchTable).  The buffers are allocated when the table appears and reused while it stays; the copies go on the engine's stream,
+// behind whatever search is running there.
+int azg_set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_nets) {
+    if (!e) return AZG_E_INVALID;
+    const bool clear = !nets || n_nets == 0;
+    const bool cont = e->cfg.mode == AZG_MODE_CONTINUOUS;
+    const int ns = e->cfg.n_sims;
+    std::vector<NetSearchRec> rec;
+    std::vector<int> pw_all, pw;
+    if (!clear) {
+        if (n_nets != e->n_nets)
+            return fail(e, AZG_E_INVALID, "azg_set_net_search: n_nets must equal the engine's number of nets (azg_set_population): got " +
+                                          std::to_string(n_nets) + ", the engine has " + std::to_string(e->n_nets));
+        rec.resize(n_nets);
+        pw_all.assign((size_t)n_nets * (ns + 2), 0);
+        for (int k = 0; k < n_nets; ++k) {
+            const azg_net_search& s = nets[k];
+            const std::string who = "azg_set_net_search: net " + std::to_string(k) + ": ";
+            if (s.struct_size != (int32_t)sizeof(azg_net_search)) return fail(e, AZG_E_INVALID, who + "azg_net_search size mismatch");
+            if (!std::isfinite(s.c_uct) || !std::isfinite(s.gamma) || !std::isfinite(s.epsilon))
+                return fail(e, AZG_E_INVALID, who + "c_uct, gamma and epsilon must be finite");
+            NetSearchRec& r = rec[k];
+            r.c_uct = s.c_uct; r.gamma = s.gamma; r.epsilon = s.epsilon;
+            r.c_uct_f = (float)s.c_uct; r.gamma_f = (float)s.gamma;
+            r.c_pw = 0.0; r.kappa = 0.0; r.pw0 = 0; r.pad = 0;
+            if (!cont) continue;   // (discrete mode: no widening)
+            if (!azg_pw_params_ok(s.c_pw, s.kappa))
+                return fail(e, AZG_E_INVALID, who + "c_pw must be > 0 and kappa >= 0 (progressive widening: ceil(c_pw (n + 1)^kappa) children)");
+            // the trees, the child lists and the results were sized at creation for azg_config's widening: every net must stay inside
+            const int kmax = azg_pw_table(s.c_pw, s.kappa, ns, pw);
+            if (kmax > e->Kmax)
+                return fail(e, AZG_E_INVALID, who + "its widening (c_pw, kappa) entitles a node to " + std::to_string(kmax) + " children, the engine was "
+                                              "created for at most " + std::to_string(e->Kmax) + " (azg_max_children): create it with the widest net's c_pw / kappa");
+            r.c_pw = s.c_pw; r.kappa = s.kappa; r.pw0 = pw[0];
+            std::copy(pw.begin(), pw.end(), pw_all.begin() + (size_t)k * (ns + 2));
+        }
+    }
+    ON_DEVICE(e);
+    { int trc = settle_team(e); if (trc) return trc; }   // an abandoned team search is redone with the settings it was started with
+    e->redo_ok = 0;   // (azg_dump_tree re-runs a search only while its inputs stand: the table is one of them)
+    if (clear) {
+        if (!e->net_search.rec) return AZG_OK;
+        HIPCHK(e, hipStreamSynchronize(e->stream));   // a running search still reads the table
+        e->net_search = NetSearchTable{};
+        e->net_search_mem.clear();
+        return AZG_OK;
+    }
+    if (!e->net_search.rec) {
+        NetSearchRec* d_rec = nullptr; int* d_pw = nullptr;
+        if (dalloc(e, e->net_search_mem, &d_rec, (size_t)n_nets) || dalloc(e, e->net_search_mem, &d_pw, pw_all.size())) {
+            e->net_search_mem.clear();
+            return AZG_E_DEVICE;
+        }
+        e->net_search.rec = d_rec; e->net_search.pw_need = d_pw;
+    }
+    HIPCHK(e, hipMemcpyAsync((void*)e->net_search.rec, rec.data(), rec.size() * sizeof(NetSearchRec), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync((void*)e->net_search.pw_need, pw_all.data(), pw_all.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));   // (the staging vectors go when this returns)
     return AZG_OK;
 }
 

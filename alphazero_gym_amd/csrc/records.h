@@ -128,6 +128,19 @@ struct KParams {
     size_t net_wstride;
 };
 
+// Per-net MCTS settings of a population (azg_set_net_search; search_kernel.cuh: search_kernel_nets): one record per net with what
+// KParams holds of them, and the nets' widening tables (n_sims + 2 entries each) one after the other.
+struct __attribute__((aligned(16))) NetSearchRec {
+    double c_uct, gamma, epsilon, c_pw, kappa;
+    float c_uct_f, gamma_f;
+    int pw0, pad;
+};
+static_assert(sizeof(NetSearchRec) == 64, "NetSearchRec must be 64 bytes");
+struct NetSearchTable {
+    const NetSearchRec* rec;   // [n_nets]
+    const int* pw_need;        // [n_nets][n_sims + 2]
+};
+
 // ---- state of the lock-step path (lockstep.cuh) between its launches
 struct LsLane { int my_depth, pid; double pr, pW; float eps_c; float pad; };
 struct LsTree { int nrec; unsigned eps_draws; int leaf, need_eval, path_D, kbase; };

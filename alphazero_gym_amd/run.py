@@ -147,25 +147,37 @@ def make_agent(kind: str, cfg: dict, Env, tree_id_base: int = 0):
 
 
 def run_population(kind: str, seeds: List[int], cfg: Optional[dict] = None, log: Optional[Callable[[Dict, int, int], None]] = None,
-                   agents: Optional[List] = None) -> List[List[float]]:
+                   agents: Optional[List] = None, sweep: Optional[Dict[str, List[float]]] = None) -> List[List[float]]:
     """run_continuous.py / run_discrete.py for K seeds at once (kind "continuous" / "discrete"; cfg as for run_*_agent, its
     ``seed`` replaced by ``seeds``).  Agent k plays its own game (env seeded with seeds[k]) with its own network, buffer,
     optimiser and np.random / random streams (seeded with seeds[k]); every environment step searches all agents' trees in ONE
     launch (AgentPopulation; agent k is tree k).  Agents whose episode has ended sit the remaining steps of that episode out.
     ``agents``: K agents built beforehand (default: built here from cfg).  Returns per seed its episode returns;
-    ``log(info, episode, k)`` gets agent k's training losses and its "Episode reward"."""
+    ``log(info, episode, k)`` gets agent k's training losses and its "Episode reward".
+    ``sweep``: search settings swept over the seeds, {"c_uct": [...], "gamma": [...], "epsilon": [...], "c_pw": [...], "kappa": [...]}
+    (any subset; one list entry per seed): agent k is built with its own values in place of cfg["mcts"]'s, and all agents are still
+    searched in one launch (AgentPopulation(per_agent_search=True))."""
     cfg = _merge(CONTINUOUS_DEFAULTS if kind == "continuous" else DISCRETE_DEFAULTS, cfg)
     K = len(seeds)
+    sweep = dict(sweep or {})
+    for key, vals in sweep.items():
+        if key not in _capi.NET_SEARCH_KEYS or (kind != "continuous" and key in ("c_pw", "kappa")):
+            raise ValueError(f"sweep: {key!r} is not a per-agent search setting of a {kind} agent ({list(_capi.NET_SEARCH_KEYS)})")
+        if len(vals) != K:
+            raise ValueError(f"sweep[{key!r}] has {len(vals)} entries for {K} seeds: one per seed")
+    if sweep and agents is not None:
+        raise ValueError("sweep builds the agents itself: pass either sweep or agents")
     envs = []
     for s in seeds:
         Env = make_game(cfg["game"])
         Env.seed(s)
         envs.append(Env)
     if agents is None:
-        agents = [make_agent(kind, cfg, envs[k], tree_id_base=k) for k in range(K)]
+        agents = [make_agent(kind, dict(cfg, mcts=dict(cfg["mcts"], **{key: vals[k] for key, vals in sweep.items()})), envs[k],
+                             tree_id_base=k) for k in range(K)]
     assert len(agents) == K
     buffers = [ReplayBuffer(**cfg["buffer"]) for _ in range(K)]
-    pop = AgentPopulation(agents, seeds=seeds)
+    pop = AgentPopulation(agents, seeds=seeds, per_agent_search=bool(sweep))
     returns: List[List[float]] = [[] for _ in range(K)]
     try:
         for ep in range(cfg["num_train_episodes"]):
@@ -281,7 +293,8 @@ class PopulationSelfPlay:
     games, final action rule, env step, episode resets and the replay ring live on the device; the host only downloads rows to
     train on.  ``policies[k]`` plays games k*T .. k*T+T-1 (T = ``games_per_net``) with global ids ``tree_id_base + k*T + j``, the
     games ``DeviceSelfPlay(policies[k], n_games=T, rank=k)`` plays, bit for bit, with one search launch and one self-play launch
-    per step for the whole population.  The game, search and self-play settings are shared by every net.  The agents' final
+    per step for the whole population.  The game, search and self-play settings are shared by every net, except that
+    ``net_settings`` (``PopulationMCTS``: a list of K dicts) gives net k its own c_uct / gamma / epsilon / c_pw / kappa.  The agents' final
     action rules run on the device too: ``final_selection`` "max_visit" / "max_value", discrete ``temperature`` and
     ``deterministic``, continuous ``agent_epsilon`` (agents.py:294-301, 524-535; include/azgym.h).  ``fifo=True`` turns the
     replay ring into the reference's overwrite-the-oldest buffer (buffers.py:75-82).  Weights are re-uploaded only when some
@@ -290,11 +303,14 @@ class PopulationSelfPlay:
     def __init__(self, policies, *, game: str, games_per_net: int, n_rollouts: int, c_uct: float, gamma: float = 1.0, epsilon: float = 0.0,
                  c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
                  deterministic: bool = False, capacity_steps: int = 64, seed: int = 34, tree_id_base: int = 0, device_id: int = 0,
-                 final_selection: str = "max_visit", temperature: float = 1.0, agent_epsilon: float = 0.0, fifo: bool = False):
+                 final_selection: str = "max_visit", temperature: float = 1.0, agent_epsilon: float = 0.0, fifo: bool = False,
+                 net_settings: Optional[List[dict]] = None):
         policies = list(policies)
         if not policies or games_per_net < 1:
             raise ValueError(f"{type(self).__name__} needs at least one policy and games_per_net >= 1")
         kw = _game_engine_kwargs(game, policies[0], c_pw, kappa)
+        if net_settings is not None:   # (opt-in: net k searches with its own c_uct / gamma / epsilon / c_pw / kappa, PopulationMCTS)
+            kw["net_settings"] = net_settings
         self.continuous = kw["mode"] == _capi.MODE_CONTINUOUS
         self.mcts = self._search(policies, games_per_net, n_rollouts=n_rollouts, c_uct=c_uct, gamma=gamma, epsilon=epsilon,
                                  V_target_policy=V_target_policy, seed=seed, tree_id_base=tree_id_base, device_id=device_id, **kw)

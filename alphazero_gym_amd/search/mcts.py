@@ -80,19 +80,32 @@ class PopulationMCTS:
     """K models (same network shape, own weights) searched in ONE launch: trees k*T .. k*T+T-1 (T = ``trees_per_model``) use
     ``models[k]``, with the RNG streams of global trees ``tree_id_base + k*T + j`` -- what K ``BatchedMCTS`` engines with
     ``tree_id_base + k*T`` compute, one launch and one synchronisation instead of K (azg_set_population).  kwargs = the reference's
-    MCTS kwargs + batch geometry; the search settings and the search index are shared.  Each model's weights are re-uploaded only
-    when they changed (models train at different times).  One model is the plain single-net engine."""
+    MCTS kwargs + batch geometry; the search index is shared, and so are the search settings unless ``net_settings`` is given.  Each
+    model's weights are re-uploaded only when they changed (models train at different times).  One model is the plain single-net engine.
+
+    ``net_settings`` (opt-in; None: shared settings): a list of K dicts with keys among ``c_uct``, ``gamma``, ``epsilon``, ``c_pw``,
+    ``kappa`` -- model k searches with its own values, a missing key takes the shared kwarg -- still in one launch, bit for bit what a
+    one-model engine with those kwargs computes (azg_set_net_search).  The engine is created with the (c_pw, kappa) pair that widens
+    furthest, so that every model's trees fit; ``set_net_settings`` changes the settings between searches.  Networks of padded hidden
+    width >= 512 search with shared settings only: ValueError."""
 
     def __init__(self, models: Sequence[Any], *, trees_per_model: int = 1, env_id: int, mode: int, n_rollouts: int, c_uct: float,
                  gamma: float, epsilon: float = 0.0, num_actions: int = 0, c_pw: float = 1.0, kappa: float = 0.5,
                  V_target_policy: str = "off_policy", action_bound: float = 2.0, seed: int = 34, tree_id_base: int = 0,
-                 device_id: int = 0):
+                 device_id: int = 0, net_settings: Optional[Sequence[dict]] = None):
         from .. import _native   # raises if libazgym_hip.so is missing
 
         self.models = list(models)
         if not self.models or trees_per_model < 1:
             raise ValueError("PopulationMCTS needs at least one model and trees_per_model >= 1")
         self.n_models = len(self.models)
+        self.n_rollouts = int(n_rollouts)
+        self._shared = dict(c_uct=c_uct, gamma=gamma, epsilon=epsilon, c_pw=c_pw, kappa=kappa)
+        self.net_settings: Optional[List[dict]] = None
+        if net_settings is not None:
+            entries = self._net_entries(net_settings)
+            if mode == _capi.MODE_CONTINUOUS:
+                c_pw, kappa = _capi.widest_pw(entries, self.n_rollouts)
         self.trees_per_model = int(trees_per_model)
         self.n_trees = self.n_models * self.trees_per_model
         self.engine = _native.HipEngine(env_id=env_id, mode=mode, n_trees=self.n_trees, n_sims=n_rollouts, c_uct=c_uct, gamma=gamma,
@@ -103,7 +116,31 @@ class PopulationMCTS:
         self._versions: List[Any] = [None] * self.n_models
         self._cliff_warned = False
         self.last_weight_sync: Optional[str] = None
+        if net_settings is not None:
+            self.engine.set_net_search(entries)
+            self.net_settings = entries
         self.sync_weights()
+
+    def _net_entries(self, net_settings) -> List[dict]:
+        """``net_settings`` completed with the shared kwargs and checked: one entry per model, known keys, widths up to 256."""
+        entries = _capi.net_search_entries(net_settings, self.n_models, self._shared)
+        for m in self.models:
+            width = max(m.hidden_dimensions)
+            if (width + 63) // 64 * 64 >= 512:
+                raise ValueError(f"net_settings: per-model search settings need a hidden width of at most 256 (padded to a multiple of 64); "
+                                 f"this model's is {width}. Wider networks search with shared settings only")
+        return entries
+
+    def set_net_settings(self, net_settings: Optional[Sequence[dict]]) -> None:
+        """Change the per-model search settings between searches (same rules as the constructor's ``net_settings``); None returns to
+        the shared settings.  Every model's widening must fit the engine as it was created (azg_max_children): EngineError otherwise."""
+        if net_settings is None:
+            self.engine.set_net_search(None)
+            self.net_settings = None
+            return
+        entries = self._net_entries(net_settings)
+        self.engine.set_net_search(entries)
+        self.net_settings = entries
 
     def sync_weights(self, force: bool = False) -> None:
         """Upload the weights of every model that changed since its last upload (net k = models[k]; after every optimiser step).

@@ -9,6 +9,8 @@ in PyTorch between them); --trainer device-fused computes the losses on the devi
 --trainer device-epoch takes the whole epoch of those steps in one native call that reads the rows straight from the self-play ring
 (PopulationTrainer.train_epoch_ring: no copy of the rows, one synchronisation per iteration instead of one per minibatch).
 --optimizer adam and --grad-clip X give every net the reference's Adam settings and gradient clipping, on every trainer.
+--c-ucts / --gammas / --search-epsilons (and, continuous games, --c-pws / --kappas) sweep the SEARCH's settings over the seeds as --lrs
+sweeps the learning rate: one value per seed, every net still searched in the one launch (PopulationSelfPlay net_settings; hidden widths up to 256).
 --layernorm builds every net with LayerNorm after each trunk activation; the device trainers are then built with layernorm=True.
 --wide builds the device trainers with wide=True, which trains nets of up to 8 hidden layers and widths up to 1024 (--hidden 1024
 1024 1024 1024).  The search engine holds several such nets too: nets it searches as teams of 32 trees (padded width >= 512, two or
@@ -54,6 +56,13 @@ def parse_args(argv=None):
     ap.add_argument("--lrs", type=float, nargs="+", default=None,
                     help="a learning-rate sweep: one value per --seeds entry, in place of --lr.  The device trainers are then built "
                          "with per_net=True (which implies optimizers='agents'): every net steps with its own lr in the same launches")
+    sweep = "one value per --seeds entry: net k searches with its own value, all nets still in one search launch per step "
+    ap.add_argument("--c-ucts", type=float, nargs="+", default=None, help="a sweep of the search's c_uct, " + sweep)
+    ap.add_argument("--gammas", type=float, nargs="+", default=None, help="a sweep of the search's discount gamma, " + sweep)
+    ap.add_argument("--search-epsilons", type=float, nargs="+", default=None, help="a sweep of the search's epsilon-greedy epsilon, " + sweep)
+    ap.add_argument("--c-pws", type=float, nargs="+", default=None,
+                    help="continuous games: a sweep of progressive widening's c_pw, " + sweep + "(the rows are as wide as the widest net's)")
+    ap.add_argument("--kappas", type=float, nargs="+", default=None, help="continuous games: a sweep of progressive widening's kappa, " + sweep)
     ap.add_argument("--optimizer", choices=["rmsprop", "adam"], default="rmsprop",
                     help="every net's optimiser; adam: the reference's Adam settings (run.ADAM).  With adam or --grad-clip the device "
                          "trainers are built with optimizers='agents'")
@@ -80,10 +89,27 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.lrs is not None and len(a.lrs) != len(a.seeds):
         ap.error(f"--lrs needs one value per --seeds entry ({len(a.seeds)}), got {len(a.lrs)}")
+    for flag, vals in search_sweeps(a).items():
+        if vals is not None and len(vals) != len(a.seeds):
+            ap.error(f"--{flag} needs one value per --seeds entry ({len(a.seeds)}), got {len(vals)}")
     why = check_population_shape(a)
     if why:
         ap.error(why)
     return a
+
+
+def search_sweeps(a):
+    """The search-setting sweeps by flag name."""
+    return {"c-ucts": a.c_ucts, "gammas": a.gammas, "search-epsilons": a.search_epsilons, "c-pws": a.c_pws, "kappas": a.kappas}
+
+
+def net_settings(a):
+    """PopulationSelfPlay's ``net_settings`` for the sweeps given (None: no sweep, every net searches with the shared settings)."""
+    keys = {"c-ucts": "c_uct", "gammas": "gamma", "search-epsilons": "epsilon", "c-pws": "c_pw", "kappas": "kappa"}
+    given = {keys[flag]: vals for flag, vals in search_sweeps(a).items() if vals is not None}
+    if not given:
+        return None
+    return [{key: vals[k] for key, vals in given.items()} for k in range(len(a.seeds))]
 
 
 def check_population_shape(a):
@@ -110,7 +136,7 @@ def build_population(a):
     sp = run.PopulationSelfPlay([ag.nn for ag in agents], game=a.game, games_per_net=a.games_per_seed, n_rollouts=a.n_rollouts,
                                 c_uct=m.c_uct, gamma=m.gamma, epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0),
                                 kappa=getattr(m, "kappa", 0.5), max_episode_length=a.max_episode_length,
-                                capacity_steps=a.steps_per_iter, seed=a.engine_seed,
+                                capacity_steps=a.steps_per_iter, seed=a.engine_seed, net_settings=net_settings(a),
                                 device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0)
     return agents, state_dim, sp
 

@@ -42,6 +42,30 @@ int azg_set_population_weights_device(azg_engine* e, const azg_mlp_desc* desc, c
  * net k's rows of a step are the block k*T .. k*T+T-1.  azg_set_net_weights* between steps replace nets' weights. */
 int azg_population_selfplay_begin(azg_engine* e, const azg_selfplay_config* cfg);
 
+/* Per-net MCTS settings, opt-in: net k searches with nets[k] instead of azg_config's c_uct / gamma / epsilon / c_pw / kappa, in the
+ * same single launch -- bit for bit what a one-net engine created with those five values (and tree_id_base + k*T) computes.
+ * Everything else stays per engine: n_sims, v_target, tie_break, num_actions, reward_scale, action_bound, seed.
+ * Call it after azg_set_population(e, n_nets); n_nets must equal the population's size (1 for an engine of one net).  NULL / 0
+ * returns to azg_config's shared settings; azg_set_population with another size clears the table as well.  The call may be repeated
+ * between searches and between self-play steps (azg_selfplay_step searches with the table); it is ordered behind a running search on
+ * the engine's stream.  azg_dump_tree right after a search re-runs it with the table it ran under; once the table has changed since,
+ * it returns AZG_E_STATE as it does after new roots or weights.
+ * Every entry is checked like azg_config's fields (continuous mode: c_pw > 0, kappa >= 0; discrete mode ignores both), and c_uct,
+ * gamma, epsilon must be finite.  In continuous mode a net's widening may entitle a node to at most azg_max_children(e) children --
+ * the trees, child lists and result arrays were sized at creation -- so create the engine with the (c_pw, kappa) of the widest net;
+ * a net with fewer children leaves its remaining result columns empty as a tree with fewer root children does.  A wrong n_nets or
+ * struct_size, an invalid value or a net that does not fit: AZG_E_INVALID (the message names the net), and the engine keeps the table
+ * it had.
+ * Widths: padded hidden width <= 256.  An engine whose nets are 512 or wider keeps the table but azg_search* / azg_selfplay_step return
+ * AZG_E_UNSUPPORTED while it is set: the team, per-layer and wide one-launch kernels search with shared settings only. */
+typedef struct azg_net_search {
+    int32_t struct_size;     /* sizeof(azg_net_search), checked */
+    int32_t reserved;        /* 0 */
+    double c_uct, gamma, epsilon;
+    double c_pw, kappa;      /* continuous mode; ignored in discrete mode */
+} azg_net_search;
+int azg_set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_nets);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,16 @@ Every act searches from the same fresh root (reset_mcts before each step; the en
 Configurations: Pendulum-v1 4x1024 ELU x 200 simulations, CartPole 2x512 ReLU x 100 simulations.  Per split K x T: ms per search of
 ONE engine that holds the K nets (K x T trees in one search) and the form that ran, against the loop it replaces -- K one-net engines
 of T trees searched one after another, each search synchronised before the next starts, which is all an engine could do before
-it took several wide nets -- on the same box."""
+it took several wide nets -- on the same box.
+
+--per-net: per-net MCTS settings (azg_set_net_search), engine level, 64 trees per net:
+    python tools/population_latency.py --per-net [--steps 20] [--warmup 3] [--out profiles/population_latency_pernet.txt]
+Configurations: CartPole 2x128 ReLU x 100 simulations at K = 1 / 8 / 64 nets, Pendulum-v1 2x256 ELU x 200 simulations at K = 1 / 4 / 16.
+Per K, ms per search (kernel time, azg_last_search_ms, and wall time of search()) of (a) ONE engine whose K nets search with K
+different settings (search_kernel_nets), (a=) the same with a table whose K entries all equal the shared settings -- the very search
+of (b) on the general kernels with the table, so (a=) against (b) is what the mechanism costs, while (a) also searches other trees --
+(b) the same engine with the shared settings (the kernel it ran before there was a table, compile-time specialised where one exists),
+(c) K one-net engines with net k's settings, searched one after another.  The table is printed and written to --out."""
 import argparse
 import json
 import os
@@ -151,6 +160,100 @@ def measure_wide(name, K, T, steps, warmup):
                 wall_ms_loop=round(med(wall_seq), 3), loop_form=form1["kernel_form"], speedup_wall=round(med(wall_seq) / med(wall_pop), 2))
 
 
+# name: engine kwargs, (network inputs, hidden widths, distribution outputs, activation), the K values
+PER_NET_CONFIGS = {
+    "cartpole_2x128_100": (dict(env_id=0, mode=0, num_actions=2, n_sims=100, c_uct=1.5, gamma=1.0, seed=34), (4, [128, 128], 2, "relu"), (1, 8, 64)),
+    "pendulum_2x256_200": (dict(env_id=2, mode=1, n_sims=200, c_uct=0.05, gamma=1.0, c_pw=1.0, kappa=0.5, seed=34), (3, [256, 256], 2, "elu"), (1, 4, 16)),
+}
+PER_NET_TREES = 64
+
+
+def per_net_settings(kw, K):
+    """K different settings around the configuration's own: c_uct over a factor of 16, gamma 1.0 / 0.99 / 0.97 in turn (the closed-form
+    backup and the general chain in one launch); epsilon and the widening stay the configuration's."""
+    out = []
+    for k in range(K):
+        f = 4.0 ** (2.0 * k / max(K - 1, 1) - 1.0) if K > 1 else 2.0
+        out.append(dict(c_uct=kw["c_uct"] * f, gamma=(1.0, 0.99, 0.97)[k % 3], epsilon=0.0, c_pw=kw.get("c_pw", 1.0), kappa=kw.get("kappa", 0.5)))
+    return out
+
+
+def _timed_searches(search, ms, steps, warmup):
+    kern, wall = [], []
+    for i in range(warmup + steps):
+        t0 = time.perf_counter()
+        search()
+        t1 = time.perf_counter()
+        if i >= warmup:
+            wall.append((t1 - t0) * 1e3)
+            kern.append(ms())
+    return float(np.median(kern)), float(np.median(wall))
+
+
+def measure_per_net(name, K, steps, warmup):
+    from alphazero_gym_amd import _capi, _native
+    from alphazero_gym_amd.synthetic import make_weights
+    kw, (in_dim, hidden, n_dist, act), _ = PER_NET_CONFIGS[name]
+    T = PER_NET_TREES
+    desc = _capi.make_desc(in_dim, hidden, n_dist, act)
+    blobs = [make_weights(34 + k, in_dim, hidden, n_dist) for k in range(K)]
+    settings = per_net_settings(kw, K)
+    pop = _native.HipEngine(**dict(kw, n_trees=K * T))
+    if K > 1:
+        pop.set_population(K)
+        for k in range(K):
+            pop.set_net_weights(k, desc, blobs[k])
+    else:
+        pop.set_weights(desc, blobs[0])
+    roots = pop.synthetic_roots()
+    b_kern, b_wall = _timed_searches(lambda: pop.search(roots), pop.last_search_ms, steps, warmup)
+    b_name = pop.search_info()["kernel_name"]
+    shared = dict(c_uct=kw["c_uct"], gamma=kw["gamma"], epsilon=kw.get("epsilon", 0.0), c_pw=kw.get("c_pw", 1.0), kappa=kw.get("kappa", 0.5))
+    pop.set_net_search([shared] * K)
+    e_kern, e_wall = _timed_searches(lambda: pop.search(roots), pop.last_search_ms, steps, warmup)
+    pop.set_net_search(settings)
+    a_kern, a_wall = _timed_searches(lambda: pop.search(roots), pop.last_search_ms, steps, warmup)
+    a_name = pop.search_info()["kernel_name"]
+    pop.close()
+    singles = []
+    for k in range(K):
+        st = {key: v for key, v in settings[k].items() if kw["mode"] == 1 or key not in ("c_pw", "kappa")}
+        e = _native.HipEngine(**dict(kw, n_trees=T, tree_id_base=k * T, **st))
+        e.set_weights(desc, blobs[k])
+        singles.append(e)
+
+    def loop():
+        for k, e in enumerate(singles):
+            e.search(roots[k * T:(k + 1) * T])
+
+    c_kern, c_wall = _timed_searches(loop, lambda: sum(e.last_search_ms() for e in singles), steps, warmup)
+    for e in singles:
+        e.close()
+    return dict(K=K, T=T, a_kernel_ms=round(a_kern, 4), a_wall_ms=round(a_wall, 3), a_kernel=a_name, a_equal_kernel_ms=round(e_kern, 4),
+                a_equal_wall_ms=round(e_wall, 3), b_kernel_ms=round(b_kern, 4),
+                b_wall_ms=round(b_wall, 3), b_kernel=b_name, c_kernel_ms=round(c_kern, 4), c_wall_ms=round(c_wall, 3))
+
+
+def main_per_net(a):
+    lines = ["# per-net MCTS settings in one launch (azg_set_net_search): ms per search, kernel / wall, medians over "
+             f"{a.steps} searches after {a.warmup} warm-up searches; {PER_NET_TREES} trees per net",
+             "# (a) one engine, K nets with K different settings (search_kernel_nets)   (a=) the same, K entries equal to the shared settings:",
+             "# the search of (b) on the general kernels with the table   (b) the same engine, shared settings (its kernel without a table)",
+             "# (c) K one-net engines with net k's settings, one after another"]
+    for name in a.configs.split(","):
+        lines.append(f"# {name}")
+        lines.append(f"# {'K':>4} {'(a) per-net ms':>22} {'(a=) equal entries ms':>22} {'(b) shared ms':>22} {'(c) K engines ms':>22} {'a=/b kernel':>12} {'c/a wall':>9}")
+        for K in PER_NET_CONFIGS[name][2]:
+            r = measure_per_net(name, K, a.steps, a.warmup)
+            lines.append(f"  {K:4d} {r['a_kernel_ms']:10.4f} / {r['a_wall_ms']:9.3f} {r['a_equal_kernel_ms']:10.4f} / {r['a_equal_wall_ms']:9.3f} "
+                         f"{r['b_kernel_ms']:10.4f} / {r['b_wall_ms']:9.3f} {r['c_kernel_ms']:10.4f} / {r['c_wall_ms']:9.3f} "
+                         f"{r['a_equal_kernel_ms'] / r['b_kernel_ms']:11.3f}x {r['c_wall_ms'] / r['a_wall_ms']:8.2f}x")
+            lines.append(json.dumps(dict(config=name, **r)))
+            print("\n".join(lines[-2:]), flush=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main_wide(a):
     for name in a.configs.split(","):
         print(f"# {name}: medians over {a.steps} searches (after {a.warmup} warm-up searches); loop = K one-net engines of T trees, one after another")
@@ -169,9 +272,14 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=None, help="warm-up steps per point (default 3; --wide: 2)")
     ap.add_argument("--wide", action="store_true", help="the wide configurations: one engine of K nets against K one-net engines in a loop")
     ap.add_argument("--splits", default=WIDE_SPLITS, help="--wide: the K x T points")
+    ap.add_argument("--per-net", action="store_true", help="per-net MCTS settings: one launch of K settings against shared settings and K engines")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                  "population_latency_pernet.txt"), help="--per-net: the file the table is written to")
     ap.add_argument("--configs", default=None)
     a = ap.parse_args(argv)
-    known = WIDE_CONFIGS if a.wide else CONFIGS
+    if a.wide and a.per_net:
+        ap.error("--wide and --per-net are separate measurements")
+    known = PER_NET_CONFIGS if a.per_net else WIDE_CONFIGS if a.wide else CONFIGS
     a.configs = a.configs or ",".join(known)
     for name in a.configs.split(","):
         if name not in known:
@@ -191,6 +299,8 @@ def main():
     os.environ.setdefault("AZG_QUIET", "1")
     if a.wide:
         return main_wide(a)
+    if a.per_net:
+        return main_per_net(a)
     for name in a.configs.split(","):
         kind, over = CONFIGS[name]
         print(f"# {name}: medians over {a.steps} steps (after {a.warmup} warm-up steps)")
