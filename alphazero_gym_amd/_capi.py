@@ -908,6 +908,18 @@ def epoch_rows(rows, state_dim, n_actions, rows_per_net, *, ring_trees=None, gam
     return r
 
 
+def _ref(x):
+    """``byref(x)``; None stays NULL."""
+    return C.byref(x) if x is not None else None
+
+
+def _require(fns, symbol, what=None):
+    """The library's ``symbol``, or the refusal that names what it lacks."""
+    if symbol not in fns:
+        raise NotImplementedError(f"this engine library has no azg_{what or symbol}")
+    return fns[symbol]
+
+
 class Trainer:
     """One ``azg_trainer*`` (include/azgym_train.h): forward and backward + RMSprop step of n_nets nets of shape ``desc`` in two
     launches.  Every array argument is a device address (int) of float32 memory on the trainer's GPU, complete when the call is
@@ -917,32 +929,28 @@ class Trainer:
     ``wide_layernorm=True`` creates it with azg_trainer_create_wide_ex and options.layernorm set: the wide trainer that also takes
     descriptors of LayerNorm trunks."""
 
+    # which azg_trainer_create* a constructor flag asks for, in the order they are looked at: (flag, symbol, with options)
+    _CREATE = (("wide_layernorm", "trainer_create_wide_ex", True), ("wide", "trainer_create_wide", False),
+               ("layernorm", "trainer_create_ex", True))
+
     def __init__(self, fns, desc, n_nets, max_batch, device_id=0, layernorm=False, wide=False, wide_layernorm=False):
         if wide and layernorm:
             raise ValueError("Trainer: wide=True does not take LayerNorm trunks (layernorm=True)")
         if wide_layernorm and layernorm:
             raise ValueError("Trainer: wide_layernorm=True and layernorm=True ask for two different trainers")
-        if "trainer_create" not in fns:
-            raise NotImplementedError("this engine library has no azg_trainer_* entry points")
-        if wide_layernorm and "trainer_create_wide_ex" not in fns:
-            raise NotImplementedError("this engine library has no azg_trainer_create_wide_ex")
-        if layernorm and "trainer_create_ex" not in fns:
-            raise NotImplementedError("this engine library has no azg_trainer_create_ex")
-        if wide and "trainer_create_wide" not in fns:
-            raise NotImplementedError("this engine library has no azg_trainer_create_wide")
+        _require(fns, "trainer_create", "trainer_* entry points")
+        flags = {"wide_layernorm": wide_layernorm, "wide": wide, "layernorm": layernorm}
+        asked = [(symbol, options) for flag, symbol, options in self._CREATE if flags[flag]] + [("trainer_create", False)]
+        for symbol, _ in asked:   # (every refusal before any native call)
+            _require(fns, symbol)
+        symbol, options = asked[0]
         self._f = fns
         self._h = C.c_void_p()
-        dref = C.byref(desc) if desc is not None else None
-        if wide_layernorm:
+        args = [int(device_id), _ref(desc), int(n_nets), int(max_batch)]
+        if options:
             opts = AzgTrainerOptions(C.sizeof(AzgTrainerOptions), 1)
-            rc = fns["trainer_create_wide_ex"](int(device_id), dref, int(n_nets), int(max_batch), C.byref(opts), C.byref(self._h))
-        elif wide:
-            rc = fns["trainer_create_wide"](int(device_id), dref, int(n_nets), int(max_batch), C.byref(self._h))
-        elif layernorm:
-            opts = AzgTrainerOptions(C.sizeof(AzgTrainerOptions), 1)
-            rc = fns["trainer_create_ex"](int(device_id), dref, int(n_nets), int(max_batch), C.byref(opts), C.byref(self._h))
-        else:
-            rc = fns["trainer_create"](int(device_id), dref, int(n_nets), int(max_batch), C.byref(self._h))
+            args.append(C.byref(opts))
+        rc = fns[symbol](*args, C.byref(self._h))
         if rc != 0:
             raise EngineError(rc, (fns["trainer_last_error"](None) or b"").decode())
         self.n_nets, self.max_batch, self.device_id = int(n_nets), int(max_batch), int(device_id)
@@ -965,95 +973,86 @@ class Trainer:
         except Exception:
             pass
 
+    def _order(self, who, order):
+        """An epoch's ``order`` as (n_order, pointer to its int32 copy); None stays NULL."""
+        if order is None:
+            return 0, None
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        if order.ndim != 2 or order.shape[0] != self.n_nets:
+            raise ValueError(f"Trainer.{who}: order must be [n_nets, n_order]")
+        return order.shape[1], _ptr(order, C.c_int32)
+
+    # The three forms of every call differ in the native symbol, in ``cfg`` (a reference to one azg_loss_cfg, or the array of
+    # ``_entries``) and in ``opt``, the optimiser's arguments as the symbol takes them: (azg_rmsprop, square_avg), (azg_optim,) or
+    # (the array of azg_optim,).
+
+    def _backward_step(self, symbol, params, d_raw, n_rows, opt, grads):
+        self._check(_require(self._f, symbol)(self._h, params or None, d_raw or None, int(n_rows), *opt, grads or None))
+
+    def _loss(self, symbol, raw, actions, counts, values, n_rows, n_actions, cfg, alpha, d_raw, losses):
+        self._check(_require(self._f, symbol)(self._h, raw or None, actions or None, counts or None, values or None, int(n_rows),
+                                              int(n_actions), cfg, _ref(alpha), d_raw or None, losses or None))
+
+    def _step(self, symbol, params, obs, actions, counts, values, n_rows, n_actions, cfg, alpha, opt, grads, raw_out, losses):
+        self._check(_require(self._f, symbol)(self._h, params or None, obs or None, actions or None, counts or None, values or None,
+                                              int(n_rows), int(n_actions), cfg, _ref(alpha), *opt, grads or None, raw_out or None,
+                                              losses or None))
+
+    def _epoch(self, symbol, who, params, rows, order, batch_size, cfg, alpha, opt, loss_sums):
+        fn = _require(self._f, symbol)
+        n_order, ptr = self._order(who, order)
+        n_mb = C.c_int32(0)
+        self._check(fn(self._h, params or None, _ref(rows), ptr, n_order, int(batch_size), cfg, _ref(alpha), *opt, loss_sums or None,
+                       C.byref(n_mb)))
+        return n_mb.value
+
     def forward(self, params, obs, n_rows, raw):
         """azg_trainer_forward: params [n_nets, P], obs [n_nets, n_rows, in_dim] -> raw [n_nets, n_rows, 1 + n_dist]."""
         self._check(self._f["trainer_forward"](self._h, params or None, obs or None, int(n_rows), raw or None))
 
     def backward_step(self, params, d_raw, n_rows, opt, square_avg, grads=None):
         """azg_trainer_backward_step: back from d_raw, RMSprop update of params / square_avg in place; grads (optional) filled."""
-        self._check(self._f["trainer_backward_step"](self._h, params or None, d_raw or None, int(n_rows),
-                                                     C.byref(opt) if opt is not None else None, square_avg or None, grads or None))
+        self._backward_step("trainer_backward_step", params, d_raw, n_rows, (_ref(opt), square_avg or None), grads)
 
     def loss(self, raw, actions, counts, values, n_rows, n_actions, cfg, alpha, d_raw, losses):
         """azg_trainer_loss: the loss kernel alone.  raw [n_nets, n_rows, 1 + n_dist], actions / counts [n_nets, n_rows, n_actions],
         values [n_nets, n_rows] -> d_raw (raw's shape) and losses [n_nets, 5] (``LOSS_KEYS``); ``alpha`` (``alpha_state``, for
         A0CLossTuned) is stepped in place."""
-        if "trainer_loss" not in self._f:
-            raise NotImplementedError("this engine library has no azg_trainer_loss")
-        self._check(self._f["trainer_loss"](self._h, raw or None, actions or None, counts or None, values or None, int(n_rows), int(n_actions),
-                                            C.byref(cfg) if cfg is not None else None, C.byref(alpha) if alpha is not None else None,
-                                            d_raw or None, losses or None))
+        self._loss("trainer_loss", raw, actions, counts, values, n_rows, n_actions, _ref(cfg), alpha, d_raw, losses)
 
     def step(self, params, obs, actions, counts, values, n_rows, n_actions, cfg, alpha, opt, square_avg, grads, raw_out, losses):
         """azg_trainer_step: forward, loss and backward + RMSprop of every net, three launches and one synchronisation."""
-        if "trainer_step" not in self._f:
-            raise NotImplementedError("this engine library has no azg_trainer_step")
-        self._check(self._f["trainer_step"](self._h, params or None, obs or None, actions or None, counts or None, values or None, int(n_rows),
-                                            int(n_actions), C.byref(cfg) if cfg is not None else None,
-                                            C.byref(alpha) if alpha is not None else None, C.byref(opt) if opt is not None else None,
-                                            square_avg or None, grads or None, raw_out or None, losses or None))
+        self._step("trainer_step", params, obs, actions, counts, values, n_rows, n_actions, _ref(cfg), alpha,
+                   (_ref(opt), square_avg or None), grads, raw_out, losses)
 
     def epoch(self, params, rows, order, batch_size, cfg, alpha, opt, square_avg, loss_sums):
         """azg_trainer_epoch: one epoch of ``step``s of every net, the minibatches gathered on the device from ``rows``
         (``epoch_rows``) by ``order`` (a HOST int array [n_nets, n_order]; consecutive slices of ``batch_size``, the last one
         absorbing the remainder); one synchronisation.  ``loss_sums``: device float64 [n_nets, 5].  Returns the number of
         minibatches (= Adam steps of a tuned alpha)."""
-        if "trainer_epoch" not in self._f:
-            raise NotImplementedError("this engine library has no azg_trainer_epoch")
-        n_order, ptr = 0, None
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.int32)
-            if order.ndim != 2 or order.shape[0] != self.n_nets:
-                raise ValueError("Trainer.epoch: order must be [n_nets, n_order]")
-            n_order, ptr = order.shape[1], _ptr(order, C.c_int32)
-        n_mb = C.c_int32(0)
-        self._check(self._f["trainer_epoch"](self._h, params or None, C.byref(rows) if rows is not None else None, ptr, n_order,
-                                             int(batch_size), C.byref(cfg) if cfg is not None else None,
-                                             C.byref(alpha) if alpha is not None else None, C.byref(opt) if opt is not None else None,
-                                             square_avg or None, loss_sums or None, C.byref(n_mb)))
-        return n_mb.value
+        return self._epoch("trainer_epoch", "epoch", params, rows, order, batch_size, _ref(cfg), alpha, (_ref(opt), square_avg or None),
+                           loss_sums)
 
     def backward_step_opt(self, params, d_raw, n_rows, opt, grads=None):
         """azg_trainer_backward_step_opt: ``backward_step`` with an ``optim`` (RMSprop or Adam, optional gradient clipping; the
         optimiser state's addresses are in ``opt``)."""
-        if "trainer_backward_step_opt" not in self._f:
-            raise NotImplementedError("this engine library has no azg_trainer_backward_step_opt")
-        self._check(self._f["trainer_backward_step_opt"](self._h, params or None, d_raw or None, int(n_rows),
-                                                         C.byref(opt) if opt is not None else None, grads or None))
+        self._backward_step("trainer_backward_step_opt", params, d_raw, n_rows, (_ref(opt),), grads)
 
     def step_opt(self, params, obs, actions, counts, values, n_rows, n_actions, cfg, alpha, opt, grads, raw_out, losses):
         """azg_trainer_step_opt: ``step`` with an ``optim``."""
-        if "trainer_step_opt" not in self._f:
-            raise NotImplementedError("this engine library has no azg_trainer_step_opt")
-        self._check(self._f["trainer_step_opt"](self._h, params or None, obs or None, actions or None, counts or None, values or None,
-                                                int(n_rows), int(n_actions), C.byref(cfg) if cfg is not None else None,
-                                                C.byref(alpha) if alpha is not None else None, C.byref(opt) if opt is not None else None,
-                                                grads or None, raw_out or None, losses or None))
+        self._step("trainer_step_opt", params, obs, actions, counts, values, n_rows, n_actions, _ref(cfg), alpha, (_ref(opt),), grads,
+                   raw_out, losses)
 
     def epoch_opt(self, params, rows, order, batch_size, cfg, alpha, opt, loss_sums):
         """azg_trainer_epoch_opt: ``epoch`` with an ``optim``; minibatch m is Adam step ``opt.step + m + 1``.  Returns the number of
         minibatches."""
-        if "trainer_epoch_opt" not in self._f:
-            raise NotImplementedError("this engine library has no azg_trainer_epoch_opt")
-        n_order, ptr = 0, None
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.int32)
-            if order.ndim != 2 or order.shape[0] != self.n_nets:
-                raise ValueError("Trainer.epoch_opt: order must be [n_nets, n_order]")
-            n_order, ptr = order.shape[1], _ptr(order, C.c_int32)
-        n_mb = C.c_int32(0)
-        self._check(self._f["trainer_epoch_opt"](self._h, params or None, C.byref(rows) if rows is not None else None, ptr, n_order,
-                                                 int(batch_size), C.byref(cfg) if cfg is not None else None,
-                                                 C.byref(alpha) if alpha is not None else None, C.byref(opt) if opt is not None else None,
-                                                 loss_sums or None, C.byref(n_mb)))
-        return n_mb.value
+        return self._epoch("trainer_epoch_opt", "epoch_opt", params, rows, order, batch_size, _ref(cfg), alpha, (_ref(opt),), loss_sums)
 
     # ---- per-net settings: the *_opt calls with one azg_optim / azg_loss_cfg per net ----
 
     def _entries(self, who, items, ctype):
         """A sequence of n_nets ``ctype`` structures as the contiguous array the *_nets entry points read (None stays NULL)."""
-        if "trainer_step_nets" not in self._f:
-            raise NotImplementedError("this engine library has no azg_trainer_*_nets entry points")
+        _require(self._f, "trainer_step_nets", "trainer_*_nets entry points")
         if items is None:
             return None
         if isinstance(items, C.Array) and items._type_ is ctype and len(items) == self.n_nets:   # (ready: no copy)
@@ -1067,38 +1066,25 @@ class Trainer:
         """azg_trainer_backward_step_nets: ``backward_step_opt`` with ``opts``, a sequence of n_nets ``optim``s whose numeric
         settings (lr, eps, weight_decay, alpha, betas, grad_clip) may differ; kind, state addresses and step must be equal."""
         arr = self._entries("backward_step_nets", opts, AzgOptim)
-        self._check(self._f["trainer_backward_step_nets"](self._h, params or None, d_raw or None, int(n_rows), arr, grads or None))
+        self._backward_step("trainer_backward_step_nets", params, d_raw, n_rows, (arr,), grads)
 
     def loss_nets(self, raw, actions, counts, values, n_rows, n_actions, cfgs, alpha, d_raw, losses):
         """azg_trainer_loss_nets: ``loss`` with ``cfgs``, a sequence of n_nets ``loss_cfg``s whose numeric settings may differ;
         kind, head, reduction and action_bound must be equal."""
         arr = self._entries("loss_nets", cfgs, AzgLossCfg)
-        self._check(self._f["trainer_loss_nets"](self._h, raw or None, actions or None, counts or None, values or None, int(n_rows),
-                                                 int(n_actions), arr, C.byref(alpha) if alpha is not None else None, d_raw or None,
-                                                 losses or None))
+        self._loss("trainer_loss_nets", raw, actions, counts, values, n_rows, n_actions, arr, alpha, d_raw, losses)
 
     def step_nets(self, params, obs, actions, counts, values, n_rows, n_actions, cfgs, alpha, opts, grads, raw_out, losses):
         """azg_trainer_step_nets: ``step_opt`` with one ``loss_cfg`` and one ``optim`` per net."""
         carr, oarr = self._entries("step_nets", cfgs, AzgLossCfg), self._entries("step_nets", opts, AzgOptim)
-        self._check(self._f["trainer_step_nets"](self._h, params or None, obs or None, actions or None, counts or None, values or None,
-                                                 int(n_rows), int(n_actions), carr, C.byref(alpha) if alpha is not None else None, oarr,
-                                                 grads or None, raw_out or None, losses or None))
+        self._step("trainer_step_nets", params, obs, actions, counts, values, n_rows, n_actions, carr, alpha, (oarr,), grads, raw_out,
+                   losses)
 
     def epoch_nets(self, params, rows, order, batch_size, cfgs, alpha, opts, loss_sums):
         """azg_trainer_epoch_nets: ``epoch_opt`` with one ``loss_cfg`` and one ``optim`` per net.  Returns the number of
         minibatches."""
         carr, oarr = self._entries("epoch_nets", cfgs, AzgLossCfg), self._entries("epoch_nets", opts, AzgOptim)
-        n_order, ptr = 0, None
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.int32)
-            if order.ndim != 2 or order.shape[0] != self.n_nets:
-                raise ValueError("Trainer.epoch_nets: order must be [n_nets, n_order]")
-            n_order, ptr = order.shape[1], _ptr(order, C.c_int32)
-        n_mb = C.c_int32(0)
-        self._check(self._f["trainer_epoch_nets"](self._h, params or None, C.byref(rows) if rows is not None else None, ptr, n_order,
-                                                  int(batch_size), carr, C.byref(alpha) if alpha is not None else None, oarr,
-                                                  loss_sums or None, C.byref(n_mb)))
-        return n_mb.value
+        return self._epoch("trainer_epoch_nets", "epoch_nets", params, rows, order, batch_size, carr, alpha, (oarr,), loss_sums)
 
     def read_d_raw(self, n_rows, d_raw):
         """azg_trainer_read_d_raw: the last ``step``'s d_raw [n_nets, n_rows, 1 + n_dist] into the caller's device array."""

@@ -13,6 +13,7 @@ around that step to the device as well (``azg_trainer_epoch``): the minibatches 
 lie, the self-play ring included, and a whole epoch costs one synchronisation.  The single-agent path (``Agent.update``) is untouched.
 """
 import ctypes as C
+from collections import namedtuple
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -236,6 +237,12 @@ def _need_device_losses(losses: str, who: str) -> None:
                          "epoch runs on the device from the gather to the loss sums")
 
 
+# How a trainer makes its native calls, chosen once in ``__init__``: the suffix of the ``_capi.Trainer`` methods, what to pass them
+# as the optimiser's arguments and as the loss settings (callables: the step count and ``reload_settings`` change them), and whether
+# the trainer counts the optimiser's steps.
+_CallForm = namedtuple("_CallForm", "suffix opt_args cfg counts_steps")
+
+
 class PopulationTrainer:
     """The optimiser step of K agents of one shape, all at once.  Raises ``ValueError`` naming the reason when the agents cannot be
     trained here (the caller then keeps the per-agent ``agent.update`` loop): different network shapes, LayerNorm (unless
@@ -312,19 +319,8 @@ class PopulationTrainer:
         if not self.layernorm and not self.wide_layernorm and any(a.nn.layernorm for a in self.agents):
             raise ValueError("PopulationTrainer: LayerNorm trunks are not trained on the device")
         opt_states: List[List[dict]] = []
-        if self.per_net:
-            settings, net_clips = self._per_net_optim()
-        elif optimizers == "agents":
-            if any(float(a.clip or 0.0) < 0 for a in self.agents):
-                raise ValueError("PopulationTrainer: grad_clip must be >= 0")
-            if len({float(a.clip or 0.0) for a in self.agents}) != 1:
-                raise ValueError("PopulationTrainer: every agent must have the same grad_clip")
-            settings = [_optimizer_settings(a.optimizer) for a in self.agents]
-            if len({st[0] for st in settings}) != 1:
-                raise ValueError("PopulationTrainer: every agent must have the same optimiser class")
-            if len(set(settings)) != 1:
-                raise ValueError(f"PopulationTrainer: every agent must have the same {settings[0][0].__name__} settings")
         if optimizers == "agents":
+            settings, net_clips = self._agents_optim(shared=not self.per_net)
             if settings[0][0] is torch.optim.Adam:
                 opt_states = [[a.optimizer.state.get(p, {}) for p in a.nn.parameters()] for a in self.agents]
                 flat_states = [st for sts in opt_states for st in sts]
@@ -368,14 +364,8 @@ class PopulationTrainer:
 
         # the native trainer first: if it cannot be created, the agents are left as they were
         self.max_batch = int(max_batch)
-        if self.wide_layernorm:
-            self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0, wide_layernorm=True)
-        elif self.wide:
-            self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0, wide=True)
-        elif self.layernorm:
-            self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0, layernorm=True)
-        else:
-            self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0)
+        kind = "wide_layernorm" if self.wide_layernorm else "wide" if self.wide else "layernorm" if self.layernorm else None
+        self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0, **({kind: True} if kind else {}))
         self.policy, self.loss = a0.nn, a0.loss
         self.device = device
         self.desc, self.flat = bind_flat([a.nn for a in self.agents])
@@ -386,9 +376,14 @@ class PopulationTrainer:
             self._opt_settings = _optimizer_settings(a0.optimizer)
             self.grad_clip = float(a0.clip or 0.0)
             self.last_grad_norms = torch.zeros(K, dtype=torch.float32, device=device)
+            if self.per_net:
+                self._form = _CallForm("_nets", lambda: (self._optims(),), lambda: self.loss_cfgs, True)
+            else:
+                self._form = _CallForm("_opt", lambda: (self._optim(),), lambda: self.loss_cfg, True)
         else:
             lr, alpha, eps, wd = _rmsprop_settings(a0.optimizer)
             self.opt = _capi.rmsprop_opt(lr=lr, alpha=alpha, eps=eps, weight_decay=wd)
+            self._form = _CallForm("", lambda: (self.opt, self.square_avg.data_ptr()), lambda: self.loss_cfg, False)
         if adam:
             self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
             if opt_states and opt_states[0] and opt_states[0][0]:
@@ -488,25 +483,32 @@ class PopulationTrainer:
         out = per_net(losses)   # (the copy to the host also completes d_raw)
         stream.synchronize()
         grads = self.grads.data_ptr() if self.grads is not None else None
-        if self.optimizers == "agents":   # (the clip happens inside: PyTorch never sees the parameter gradients)
-            if self.per_net:
-                self.trainer.backward_step_nets(self.flat.data_ptr(), d_raw.data_ptr(), B, self._optims(), grads)
-            else:
-                self.trainer.backward_step_opt(self.flat.data_ptr(), d_raw.data_ptr(), B, self._optim(), grads)
-            self.opt_step += 1
-        else:
-            self.trainer.backward_step(self.flat.data_ptr(), d_raw.data_ptr(), B, self.opt, self.square_avg.data_ptr(), grads)
+        # (a clip happens inside: PyTorch never sees the parameter gradients)
+        self._call("backward_step", (self.flat.data_ptr(), d_raw.data_ptr(), B), (grads,))
         return out
 
-    def _per_net_optim(self) -> Tuple[List[tuple], List[float]]:
-        """``per_net=True``: every agent's (class, settings) and grad_clip, after the checks that remain -- a supported optimiser of
-        one class for all, grad_clip >= 0."""
-        if any(float(a.clip or 0.0) < 0 for a in self.agents):
+    def _call(self, family: str, head: tuple, tail: tuple):
+        """The trainer's ``family`` call in this trainer's form: ``head``, the optimiser's arguments, ``tail``.  Counts the steps it
+        took (an epoch returns their number)."""
+        n_steps = getattr(self.trainer, family + self._form.suffix)(*head, *self._form.opt_args(), *tail)
+        if self._form.counts_steps:
+            self.opt_step += 1 if n_steps is None else n_steps
+        return n_steps
+
+    def _agents_optim(self, shared: bool) -> Tuple[List[tuple], List[float]]:
+        """``optimizers="agents"``: every agent's (class, settings) and grad_clip after the checks -- grad_clip >= 0 and a supported
+        optimiser of one class for all; ``shared`` (``per_net=False``): with one grad_clip and one set of settings."""
+        clips = [float(a.clip or 0.0) for a in self.agents]
+        if any(c < 0 for c in clips):
             raise ValueError("PopulationTrainer: grad_clip must be >= 0")
+        if shared and len(set(clips)) != 1:
+            raise ValueError("PopulationTrainer: every agent must have the same grad_clip")
         settings = [_optimizer_settings(a.optimizer) for a in self.agents]
         if len({st[0] for st in settings}) != 1:
             raise ValueError("PopulationTrainer: every agent must have the same optimiser class")
-        return settings, [float(a.clip or 0.0) for a in self.agents]
+        if shared and len(set(settings)) != 1:
+            raise ValueError(f"PopulationTrainer: every agent must have the same {settings[0][0].__name__} settings")
+        return settings, clips
 
     def _per_net_loss(self) -> None:
         """``per_net=True``: the loss objects share what they must (``losses="device"``), or everything (``losses="torch"``:
@@ -525,7 +527,7 @@ class PopulationTrainer:
         not touched."""
         if not self.per_net:
             raise ValueError("PopulationTrainer.reload_settings needs a trainer built with per_net=True")
-        settings, clips = self._per_net_optim()
+        settings, clips = self._agents_optim(shared=False)
         if settings[0][0] is not self._opt_settings[0]:
             raise ValueError("PopulationTrainer.reload_settings: the optimiser class cannot change")
         self._per_net_loss()
@@ -541,16 +543,7 @@ class PopulationTrainer:
         """``per_net=True``: the arrays the ``*_nets`` calls read, built once per set of settings -- one azg_optim per net (its
         agent's settings over the shared state tensors; ``_optims`` writes the step count into all of them) and, with
         ``losses="device"``, one azg_loss_cfg per net."""
-        out = []
-        for st, clip in zip(settings, clips):
-            common = dict(grad_clip=clip, step=self.opt_step, grad_norms=self.last_grad_norms.data_ptr())
-            if st[0] is torch.optim.Adam:
-                _, lr, betas, eps, wd = st
-                out.append(_capi.optim("adam", lr, self.exp_avg_sq.data_ptr(), self.exp_avg.data_ptr(), eps=eps, weight_decay=wd,
-                                       betas=betas, **common))
-            else:
-                _, lr, alpha, eps, wd = st
-                out.append(_capi.optim("rmsprop", lr, self.square_avg.data_ptr(), eps=eps, weight_decay=wd, alpha=alpha, **common))
+        out = [self._azg_optim(st, clip) for st, clip in zip(settings, clips)]
         opts = (_capi.AzgOptim * len(out))(*out)
         words = C.sizeof(_capi.AzgOptim) // 4
         steps = np.frombuffer(opts, dtype=np.int32).reshape(len(out), words)[:, _capi.AzgOptim.step.offset // 4]
@@ -563,16 +556,19 @@ class PopulationTrainer:
         self._net_steps[:] = self.opt_step
         return self._net_opts
 
-    def _optim(self):
-        """azg_optim of the next step (``optimizers="agents"``): the agents' settings, the trainer's state tensors and step count."""
-        st = self._opt_settings
-        common = dict(grad_clip=self.grad_clip, step=self.opt_step, grad_norms=self.last_grad_norms.data_ptr())
+    def _azg_optim(self, st: tuple, clip: float):
+        """azg_optim of an ``_optimizer_settings`` tuple and a grad_clip over the trainer's state tensors and step count."""
+        common = dict(grad_clip=clip, step=self.opt_step, grad_norms=self.last_grad_norms.data_ptr())
         if st[0] is torch.optim.Adam:
             _, lr, betas, eps, wd = st
             return _capi.optim("adam", lr, self.exp_avg_sq.data_ptr(), self.exp_avg.data_ptr(), eps=eps, weight_decay=wd, betas=betas,
                                **common)
         _, lr, alpha, eps, wd = st
         return _capi.optim("rmsprop", lr, self.square_avg.data_ptr(), eps=eps, weight_decay=wd, alpha=alpha, **common)
+
+    def _optim(self):
+        """azg_optim of the next step (``optimizers="agents"``): the agents' settings, the trainer's state tensors and step count."""
+        return self._azg_optim(self._opt_settings, self.grad_clip)
 
     def _update_device(self, states, actions, counts, values, raw, stream) -> List[Dict[str, float]]:
         """``update`` with the losses on the device: one native call (three launches), one copy of losses[K, 5] to the host."""
@@ -584,18 +580,8 @@ class PopulationTrainer:
                                   self.alpha_exp_avg_sq.data_ptr()) if tuned else None
         stream.synchronize()
         grads = self.grads.data_ptr() if self.grads is not None else None
-        if self.per_net:
-            self.trainer.step_nets(self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), B,
-                                   actions.shape[2], self.loss_cfgs, state, self._optims(), grads, raw.data_ptr(), table.data_ptr())
-            self.opt_step += 1
-        elif self.optimizers == "agents":
-            self.trainer.step_opt(self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), B,
-                                  actions.shape[2], self.loss_cfg, state, self._optim(), grads, raw.data_ptr(), table.data_ptr())
-            self.opt_step += 1
-        else:
-            self.trainer.step(self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), B,
-                              actions.shape[2], self.loss_cfg, state, self.opt, self.square_avg.data_ptr(), grads, raw.data_ptr(),
-                              table.data_ptr())
+        self._call("step", (self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), B,
+                              actions.shape[2], self._form.cfg(), state), (grads, raw.data_ptr(), table.data_ptr()))
         if tuned:
             self.alpha_step += 1
         self.last_raw, self._last_d_raw = raw, None
@@ -640,17 +626,7 @@ class PopulationTrainer:
         state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
                                   self.alpha_exp_avg_sq.data_ptr()) if tuned else None
         torch.cuda.current_stream(self.device).synchronize()
-        if self.per_net:
-            n_steps = self.trainer.epoch_nets(self.flat.data_ptr(), where, order, int(batch_size), self.loss_cfgs, state, self._optims(),
-                                              sums.data_ptr())
-            self.opt_step += n_steps
-        elif self.optimizers == "agents":
-            n_steps = self.trainer.epoch_opt(self.flat.data_ptr(), where, order, int(batch_size), self.loss_cfg, state, self._optim(),
-                                             sums.data_ptr())
-            self.opt_step += n_steps
-        else:
-            n_steps = self.trainer.epoch(self.flat.data_ptr(), where, order, int(batch_size), self.loss_cfg, state, self.opt,
-                                         self.square_avg.data_ptr(), sums.data_ptr())
+        n_steps = self._call("epoch", (self.flat.data_ptr(), where, order, int(batch_size), self._form.cfg(), state), (sums.data_ptr(),))
         assert n_steps == len(bounds)
         if tuned:
             self.alpha_step += n_steps

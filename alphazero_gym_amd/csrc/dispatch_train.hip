@@ -1,12 +1,16 @@
-// dispatch_train.hip -- the population trainer's C ABI (include/azgym_train.h): scratch, checks and the three launches of train.cuh;
-// azg_trainer_epoch enqueues them for a whole epoch of minibatches behind a gather launch each.  The *_opt entry points take an
-// azg_optim and choose the backward launch's form: fused RMSprop, or gradients first and norm, clip and update after the last layer.
-// The *_nets entry points take one azg_optim / azg_loss_cfg per net: the same checks per entry, the launch-ready settings in a device
-// table, and the per-net forms of the deferred backward, update and loss kernels, which read their net's entry from it.
-// A trainer made by azg_trainer_create_wide(_ex) keeps its dims in `wide` and takes dispatch_train_wide.hip's launches (one per layer and
-// role) wherever a narrow one takes train.cuh's; every check, buffer and synchronisation is the same code.
+// dispatch_train.hip -- the population trainer's C ABI (include/azgym_train.h).
+// Creation: one routine checks the descriptor against the entry point's limits and lays out parameters and scratch (describe_net);
+// all four azg_trainer_create* make their handle through create_trainer.  The handle keeps that one TrainNet, the narrow kernels'
+// TrainDimsLN copied from it once, and owns its device memory: what lives as long as the handle in a DeviceAllocs, what a call may
+// need larger in a DeviceBuffer each.
+// Calls: each entry point's checks (nothing launched, nothing written) fill one TrainPlan -- the backward launch's form (fused RMSprop;
+// gradients first and norm, clip and update after the last layer; or that with every net's own entry of a device table), the state
+// pointers, and per minibatch the launch-ready TrainOptD and LossDims -- before the device scope is entered.  launch_forward,
+// launch_loss and launch_backward are the only places that choose between the forms and between train.cuh's kernels (plain,
+// LayerNorm) and dispatch_train_wide.hip's launches; a step is an epoch's minibatch body with one minibatch.
 #include <cmath>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -22,12 +26,12 @@ struct azg_trainer {
     int step_rows = 0;           // rows of the d_raw the last azg_trainer_step left in d_raw_buf (0: none)
     int num_components = 0;
     float log_std_min = 0.0f, log_std_max = 0.0f;
-    bool ln = false;             // the LN = true kernels (a LayerNorm descriptor through azg_trainer_create_ex)
-    TrainDimsLN d{};
-    TrainWide* wide = nullptr;   // azg_trainer_create_wide(_ex): d then holds only what the host reads (P, NO, nd, in_dim, n_layers)
-    double* norm_part = nullptr; // ... and the deferred norm's partial chains [n_nets][1024]
+    TrainNet net{};
+    TrainDimsLN dims{};          // a narrow trainer's kernel argument: net's first TR_MAX_LAYERS layers (the LN = false kernels take its base)
+    DeviceAllocs mem;            // everything below up to d_raw_buf
     float* scratch = nullptr;
     float* grad_buf = nullptr;   // [n_nets][P]: where the deferred backward form keeps the gradients when the caller gives no grads
+    double* norm_part = nullptr; // a wide trainer's: the deferred norm's partial chains [n_nets][1024]
     // the loss kernel's: the rows' terms [n_nets][3][max_batch] (float64), and azg_trainer_step's raw and d_raw [n_nets][max_batch][NO]
     // (allocated by the first call that needs them)
     double* loss_rows = nullptr;
@@ -35,17 +39,11 @@ struct azg_trainer {
     float* d_raw_buf = nullptr;
     // azg_trainer_epoch's, grown on demand: the uploaded order [n_nets][n_order], the minibatch staging arrays (obs [n_nets][B][in_dim] |
     // actions | counts [n_nets][B][A] | values [n_nets][B], laid out for max_batch rows) and the loss table [n_minibatches][n_nets][5]
-    int* order_buf = nullptr;
-    float* stage_buf = nullptr;
-    float* loss_table = nullptr;
-    size_t order_bytes = 0, stage_bytes = 0, table_bytes = 0;
+    DeviceBuffer order_buf, stage_buf, loss_table;
     // the *_nets entry points': the launch-ready settings of every (minibatch, net), [M][n_nets] TrainOptD | [M][n_nets] LossDims (a
     // part the call has no entries for is empty), filled on the host for the whole call and uploaded in one copy; grown on demand
     std::vector<unsigned char> nets_host;
-    unsigned char* nets_dev = nullptr;
-    size_t nets_bytes = 0;
-    size_t nets_loss_off = 0;    // where the LossDims part starts
-    bool nets_any_norm = false;  // some net of the call clips or reports its norm
+    DeviceBuffer nets_dev;
     hipStream_t stream = nullptr;
     std::string err;
 };
@@ -58,56 +56,35 @@ static int tfail(azg_trainer* t, int code, const std::string& msg) {
     return code;
 }
 
-extern "C" {
+// What an entry point accepts of a descriptor, and how it says no.
+struct TrainLimits {
+    int max_layers, max_width;
+    const char* who;            // the message prefix: azg_trainer_create also for _ex, azg_trainer_create_wide also for _wide_ex
+    const char* ln_refusal;     // the refusal of a LayerNorm descriptor where layernorm_ok is false
+    bool layernorm_ok;
+    bool wide;
+};
 
-const char* azg_trainer_last_error(const azg_trainer* t) { return t ? t->err.c_str() : g_trainer_create_err.c_str(); }
-
-size_t azg_trainer_param_count(const azg_trainer* t) { return t ? (size_t)t->d.P : 0; }
-
-void azg_trainer_destroy(azg_trainer* t) {
-    if (!t) return;
-    DeviceScope scope(t->device_id);
-    if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
-    if (t->scratch) (void)hipFree(t->scratch);
-    if (t->grad_buf) (void)hipFree(t->grad_buf);
-    if (t->loss_rows) (void)hipFree(t->loss_rows);
-    if (t->raw_buf) (void)hipFree(t->raw_buf);
-    if (t->d_raw_buf) (void)hipFree(t->d_raw_buf);
-    if (t->order_buf) (void)hipFree(t->order_buf);
-    if (t->stage_buf) (void)hipFree(t->stage_buf);
-    if (t->loss_table) (void)hipFree(t->loss_table);
-    if (t->norm_part) (void)hipFree(t->norm_part);
-    if (t->nets_dev) (void)hipFree(t->nets_dev);
-    if (t->wide) tw_free(t->wide);
-    delete t;
-}
-
-// azg_trainer_create (layernorm_ok = false) and azg_trainer_create_ex
-static int create_impl(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, bool layernorm_ok, azg_trainer** out) {
-    if (desc->struct_size != (int32_t)sizeof(azg_mlp_desc)) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create: azg_mlp_desc.struct_size mismatch");
-    if (n_nets < 1 || max_batch < 1) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create: n_nets and max_batch must be at least 1");
-    if (desc->layernorm && !layernorm_ok) return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: LayerNorm trunks are not trained on the device");
-    if (desc->n_hidden < 1 || desc->n_hidden > TR_MAX_LAYERS)
-        return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: 1 to 3 hidden layers");
-    if (desc->in_dim < 1 || desc->in_dim > TR_OBS_LD) return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: in_dim must be 1..8");
-    if (desc->n_dist < 1 || desc->n_dist > 16) return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: n_dist must be 1..16");
-    if (desc->activation < AZG_ACT_RELU || desc->activation > AZG_ACT_HARDSWISH)
-        return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: unknown activation");
+// Checks the descriptor against the limits and lays out parameters and scratch.  AZG_OK and *out, or a code and the creation error.
+static int describe_net(const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, const TrainLimits& lim, TrainNet* out) {
+    const std::string w = std::string(lim.who) + ": ";
+    if (desc->struct_size != (int32_t)sizeof(azg_mlp_desc)) return tfail(nullptr, AZG_E_INVALID, w + "azg_mlp_desc.struct_size mismatch");
+    if (n_nets < 1 || max_batch < 1) return tfail(nullptr, AZG_E_INVALID, w + "n_nets and max_batch must be at least 1");
+    if (desc->layernorm && !lim.layernorm_ok) return tfail(nullptr, AZG_E_UNSUPPORTED, w + lim.ln_refusal);
+    if (desc->n_hidden < 1 || desc->n_hidden > lim.max_layers)
+        return tfail(nullptr, AZG_E_UNSUPPORTED, w + "1 to " + std::to_string(lim.max_layers) + " hidden layers");
+    if (desc->in_dim < 1 || desc->in_dim > TR_OBS_LD) return tfail(nullptr, AZG_E_UNSUPPORTED, w + "in_dim must be 1..8");
+    if (desc->n_dist < 1 || desc->n_dist > 16) return tfail(nullptr, AZG_E_UNSUPPORTED, w + "n_dist must be 1..16");
+    if (desc->activation < AZG_ACT_RELU || desc->activation > AZG_ACT_HARDSWISH) return tfail(nullptr, AZG_E_UNSUPPORTED, w + "unknown activation");
     for (int l = 0; l < desc->n_hidden; ++l)
-        if (desc->hidden[l] < 16 || desc->hidden[l] > 256 || desc->hidden[l] % 16)
-            return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: hidden widths must be multiples of 16 up to 256");
-    azg_trainer* t = new azg_trainer();
-    t->device_id = device_id;
-    t->n_nets = n_nets;
-    t->max_batch = max_batch;
-    t->num_components = desc->num_components;
-    t->log_std_min = desc->log_std_min;
-    t->log_std_max = desc->log_std_max;
-    TrainDimsLN& d = t->d;
-    t->ln = desc->layernorm != 0;
-    d.layernorm = t->ln ? 1 : 0;
+        if (desc->hidden[l] < 16 || desc->hidden[l] > lim.max_width || desc->hidden[l] % 16)
+            return tfail(nullptr, AZG_E_UNSUPPORTED, w + "hidden widths must be multiples of 16 up to " + std::to_string(lim.max_width));
+    TrainNet d{};
+    d.wide = lim.wide;
     d.n_layers = desc->n_hidden; d.in_dim = desc->in_dim; d.nd = desc->n_dist; d.NO = 1 + desc->n_dist; d.act = desc->activation;
+    d.layernorm = desc->layernorm ? 1 : 0;
     const size_t Bmax = ((size_t)max_batch + 15) / 16 * 16;
+    // (at most 8 * 1024 * 1024 + ... parameters: off stays far below 2^31; so, in 64 bits, stays below 2^47 and is checked at the end)
     int off = 0, prev = d.in_dim;
     size_t so = 0;
     d.s_obs = (unsigned)so; so += Bmax * TR_OBS_LD;
@@ -115,10 +92,10 @@ static int create_impl(int32_t device_id, const azg_mlp_desc* desc, int32_t n_ne
         d.H[l] = desc->hidden[l];
         d.offW[l] = off; off += d.H[l] * prev;
         d.offb[l] = off; off += d.H[l];
-        if (t->ln) { d.offG[l] = off; off += d.H[l]; d.offB[l] = off; off += d.H[l]; }
+        if (d.layernorm) { d.offG[l] = off; off += d.H[l]; d.offB[l] = off; off += d.H[l]; }
         d.s_A[l] = (unsigned)so; so += Bmax * d.H[l];
         d.s_D[l] = (unsigned)so; so += Bmax * d.H[l];
-        if (t->ln) {
+        if (d.layernorm) {
             d.s_X[l] = (unsigned)so; so += Bmax * d.H[l];
             d.s_G[l] = (unsigned)so; so += Bmax * d.H[l];
             d.s_R[l] = (unsigned)so; so += Bmax;
@@ -131,28 +108,88 @@ static int create_impl(int32_t device_id, const azg_mlp_desc* desc, int32_t n_ne
     d.offbd = off; off += d.nd;
     d.P = off;
     d.per_net = so;
-    if (so >= ((size_t)1 << 32)) { delete t; return tfail(nullptr, AZG_E_UNSUPPORTED, "azg_trainer_create: max_batch too large"); }
-    DeviceScope scope(device_id);
-    if (!scope.ok) { delete t; return tfail(nullptr, AZG_E_DEVICE, "hipSetDevice failed"); }
-    const size_t bytes = so * (size_t)n_nets * sizeof(float);
-    // (not cleared: the forward launch writes every scratch element below its padded row count, and the backward launch of the
-    // same n_rows reads nothing else)
-    hipError_t rc = hipMalloc((void**)&t->scratch, bytes);
-    if (rc == hipSuccess) rc = hipMalloc((void**)&t->grad_buf, (size_t)n_nets * (size_t)d.P * sizeof(float));
-    if (rc == hipSuccess) rc = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
-    if (rc != hipSuccess) {
-        const std::string msg = std::string("azg_trainer_create: ") + hipGetErrorString(rc);
-        azg_trainer_destroy(t);
-        return tfail(nullptr, AZG_E_DEVICE, msg);
-    }
-    *out = t;
+    if (so >= ((size_t)1 << 32)) return tfail(nullptr, AZG_E_UNSUPPORTED, w + "max_batch too large");   // the kernels' offsets are 32 bits
+    *out = d;
     return AZG_OK;
 }
+
+// the narrow kernels' argument
+static TrainDimsLN narrow_dims(const TrainNet& n) {
+    TrainDimsLN d{};
+    d.n_layers = n.n_layers; d.in_dim = n.in_dim; d.nd = n.nd; d.NO = n.NO; d.act = n.act;
+    d.offWv = n.offWv; d.offbv = n.offbv; d.offbd = n.offbd; d.P = n.P;
+    d.s_obs = n.s_obs; d.per_net = n.per_net; d.layernorm = n.layernorm;
+    for (int l = 0; l < TR_MAX_LAYERS; ++l) {
+        d.H[l] = n.H[l]; d.offW[l] = n.offW[l]; d.offb[l] = n.offb[l]; d.s_A[l] = n.s_A[l]; d.s_D[l] = n.s_D[l];
+        d.offG[l] = n.offG[l]; d.offB[l] = n.offB[l]; d.s_X[l] = n.s_X[l]; d.s_G[l] = n.s_G[l]; d.s_R[l] = n.s_R[l];
+    }
+    return d;
+}
+
+extern "C" {
+
+const char* azg_trainer_last_error(const azg_trainer* t) { return t ? t->err.c_str() : g_trainer_create_err.c_str(); }
+
+size_t azg_trainer_param_count(const azg_trainer* t) { return t ? (size_t)t->net.P : 0; }
+
+// (the handle's owners free its device memory, with its device current)
+void azg_trainer_destroy(azg_trainer* t) {
+    if (!t) return;
+    DeviceScope scope(t->device_id);
+    if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
+    delete t;
+}
+
+}  // extern "C"
+
+namespace { struct TrainerDestroy { void operator()(azg_trainer* t) const { azg_trainer_destroy(t); } }; }
+
+// The four azg_trainer_create*, behind their NULL and struct_size checks.
+static int create_trainer(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, const TrainLimits& lim,
+                          azg_trainer** out) {
+    TrainNet net;
+    if (int rc = describe_net(desc, n_nets, max_batch, lim, &net)) return rc;
+    std::unique_ptr<azg_trainer, TrainerDestroy> t(new azg_trainer());   // (a failure below leaves through azg_trainer_destroy)
+    t->net = net;
+    if (!lim.wide) t->dims = narrow_dims(net);
+    t->device_id = device_id;
+    t->n_nets = n_nets;
+    t->max_batch = max_batch;
+    t->num_components = desc->num_components;
+    t->log_std_min = desc->log_std_min;
+    t->log_std_max = desc->log_std_max;
+    DeviceScope scope(device_id);
+    if (!scope.ok) return tfail(nullptr, AZG_E_DEVICE, "hipSetDevice failed");
+    // (the scratch is not cleared: the forward launch writes every scratch element below its padded row count, and the backward
+    // launch of the same n_rows reads nothing else)
+    const size_t K = (size_t)n_nets;
+    hipError_t rc = hipSuccess;
+    if (!(t->scratch = t->mem.alloc<float>(t->net.per_net * K)) || !(t->grad_buf = t->mem.alloc<float>(K * (size_t)t->net.P)) ||
+        (lim.wide && !(t->norm_part = t->mem.alloc<double>(K * TR_BWD_THREADS))))
+        rc = t->mem.last;
+    if (rc == hipSuccess) rc = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
+    if (rc != hipSuccess) {
+        (void)hipGetLastError();   // (not left for a later call's finish to report)
+        return tfail(nullptr, AZG_E_DEVICE, std::string(lim.who) + ": " + hipGetErrorString(rc));
+    }
+    *out = t.release();
+    return AZG_OK;
+}
+
+static TrainLimits narrow_limits(bool layernorm_ok) {
+    return TrainLimits{TR_MAX_LAYERS, 256, "azg_trainer_create", "LayerNorm trunks are not trained on the device", layernorm_ok, false};
+}
+static TrainLimits wide_limits(bool layernorm_ok) {
+    return TrainLimits{AZG_MAX_HIDDEN_LAYERS, 1024, "azg_trainer_create_wide", "wide LayerNorm trunks are not trained on the device",
+                       layernorm_ok, true};
+}
+
+extern "C" {
 
 int azg_trainer_create(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, azg_trainer** out) {
     if (!desc || !out) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create: NULL argument");
     *out = nullptr;
-    return create_impl(device_id, desc, n_nets, max_batch, false, out);
+    return create_trainer(device_id, desc, n_nets, max_batch, narrow_limits(false), out);
 }
 
 int azg_trainer_create_ex(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, const azg_trainer_options* opts,
@@ -161,48 +198,13 @@ int azg_trainer_create_ex(int32_t device_id, const azg_mlp_desc* desc, int32_t n
     *out = nullptr;
     if (opts->struct_size != (int32_t)sizeof(azg_trainer_options))
         return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_ex: azg_trainer_options.struct_size mismatch");
-    return create_impl(device_id, desc, n_nets, max_batch, opts->layernorm != 0, out);
+    return create_trainer(device_id, desc, n_nets, max_batch, narrow_limits(opts->layernorm != 0), out);
 }
 
-// azg_trainer_create_wide (layernorm_ok = false) and azg_trainer_create_wide_ex, behind their NULL checks
-static int create_wide_impl(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, bool layernorm_ok,
-                            azg_trainer** out) {
-    if (desc->struct_size != (int32_t)sizeof(azg_mlp_desc)) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide: azg_mlp_desc.struct_size mismatch");
-    if (n_nets < 1 || max_batch < 1) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide: n_nets and max_batch must be at least 1");
-    TrainWide* w = nullptr;
-    std::string msg;
-    if (int rc = tw_plan(desc, max_batch, layernorm_ok, &w, &msg)) return tfail(nullptr, rc, msg);
-    azg_trainer* t = new azg_trainer();
-    t->wide = w;
-    t->device_id = device_id;
-    t->n_nets = n_nets;
-    t->max_batch = max_batch;
-    t->num_components = desc->num_components;
-    t->log_std_min = desc->log_std_min;
-    t->log_std_max = desc->log_std_max;
-    t->d.n_layers = desc->n_hidden; t->d.in_dim = desc->in_dim; t->d.nd = desc->n_dist; t->d.NO = 1 + desc->n_dist; t->d.act = desc->activation;
-    t->d.P = tw_param_count(w);
-    t->d.per_net = tw_scratch_floats(w);
-    DeviceScope scope(device_id);
-    if (!scope.ok) { azg_trainer_destroy(t); return tfail(nullptr, AZG_E_DEVICE, "hipSetDevice failed"); }
-    // (the scratch is not cleared, for azg_trainer_create's reason)
-    hipError_t rc = hipMalloc((void**)&t->scratch, t->d.per_net * (size_t)n_nets * sizeof(float));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&t->grad_buf, (size_t)n_nets * (size_t)t->d.P * sizeof(float));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&t->norm_part, (size_t)n_nets * TR_BWD_THREADS * sizeof(double));
-    if (rc == hipSuccess) rc = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
-    if (rc != hipSuccess) {
-        const std::string m = std::string("azg_trainer_create_wide: ") + hipGetErrorString(rc);
-        (void)hipGetLastError();
-        azg_trainer_destroy(t);
-        return tfail(nullptr, AZG_E_DEVICE, m);
-    }
-    *out = t;
-    return AZG_OK;
-}
-
+// (the wide entry points leave *out untouched on an error, as their header says; the first two clear it)
 int azg_trainer_create_wide(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, azg_trainer** out) {
     if (!desc || !out) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide: NULL argument");
-    return create_wide_impl(device_id, desc, n_nets, max_batch, false, out);
+    return create_trainer(device_id, desc, n_nets, max_batch, wide_limits(false), out);
 }
 
 int azg_trainer_create_wide_ex(int32_t device_id, const azg_mlp_desc* desc, int32_t n_nets, int32_t max_batch, const azg_trainer_options* opts,
@@ -210,10 +212,37 @@ int azg_trainer_create_wide_ex(int32_t device_id, const azg_mlp_desc* desc, int3
     if (!desc || !opts || !out) return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide_ex: NULL argument");
     if (opts->struct_size != (int32_t)sizeof(azg_trainer_options))
         return tfail(nullptr, AZG_E_INVALID, "azg_trainer_create_wide_ex: azg_trainer_options.struct_size mismatch");
-    return create_wide_impl(device_id, desc, n_nets, max_batch, opts->layernorm != 0, out);
+    return create_trainer(device_id, desc, n_nets, max_batch, wide_limits(opts->layernorm != 0), out);
 }
 
-// ---- each call in three parts: its checks (nothing launched, nothing written), its launch, and the public entry point ----
+}  // extern "C"
+
+// ---- what a call launches ----
+
+enum class OptForm { fused, deferred, table };
+
+struct Minibatch {
+    int first = 0, rows = 0;     // its rows of the epoch's order
+    TrainOptD o{};               // fused: o.rms is the kernel's TrainOpt
+    LossDims c{};                // (table: entry 0's, for its kind)
+};
+
+// Seeded by the entry point with the form its name implies (fused for the azg_rmsprop ones, which never leave it; table for *_nets)
+// and filled by the checks below.
+struct TrainPlan {
+    OptForm form = OptForm::fused;
+    float* state0 = nullptr;     // square_avg, or Adam's exp_avg_sq
+    float* state1 = nullptr;     // Adam's exp_avg
+    float* grad_norms = nullptr;
+    const azg_alpha_state* alpha = nullptr;   // the tuned loss's state
+    // table: where the LossDims part starts in nets_host / nets_dev, and whether some net of the call clips or reports its norm
+    size_t loss_off = 0;
+    bool any_norm = false;
+    std::vector<Minibatch> mb;
+    explicit TrainPlan(OptForm f, int n_rows = 0) : form(f), mb(1) { mb[0].rows = n_rows; }
+};
+
+// ---- the checks: nothing launched, nothing written ----
 
 static int check_forward(azg_trainer* t, const char* who, const float* params, const float* obs, int32_t n_rows) {
     if (!params || !obs) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
@@ -221,48 +250,32 @@ static int check_forward(azg_trainer* t, const char* who, const float* params, c
     return AZG_OK;
 }
 
-static void launch_forward(azg_trainer* t, const float* params, const float* obs, int n_rows, float* raw) {
-    if (t->wide) { tw_launch_forward(t->wide, t->stream, t->n_nets, params, obs, n_rows, raw, t->scratch); return; }
-    const dim3 grid((n_rows + 15) / 16, t->n_nets);
-    if (t->ln) hipLaunchKernelGGL(train_forward_kernel<true>, grid, dim3(64), 0, t->stream, t->d, params, obs, n_rows, raw, t->scratch);
-    else hipLaunchKernelGGL(train_forward_kernel<false>, grid, dim3(64), 0, t->stream, (const TrainDims&)t->d, params, obs, n_rows, raw, t->scratch);
+static TrainOpt rmsprop_step(double lr, double alpha, double eps, double weight_decay) {
+    TrainOpt o;
+    o.lr = (float)lr; o.alpha = (float)alpha; o.one_minus_alpha = (float)(1.0 - alpha); o.eps = (float)eps;
+    o.wd = (float)weight_decay;
+    return o;
 }
 
-static int check_backward(azg_trainer* t, const char* who, const float* params, const azg_rmsprop* opt, const float* square_avg,
-                          int32_t n_rows) {
+// The (azg_rmsprop, square_avg) of the first entry points: always the fused form.
+static int check_backward(azg_trainer* t, const char* who, const float* params, const azg_rmsprop* opt, float* square_avg, int32_t n_rows,
+                          TrainPlan* plan, TrainOptD* out) {
     const std::string w(who);
     if (!params || !opt || !square_avg) return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
     if (opt->struct_size != (int32_t)sizeof(azg_rmsprop)) return tfail(t, AZG_E_INVALID, w + ": azg_rmsprop.struct_size mismatch");
     if (n_rows < 1 || n_rows > t->max_batch) return tfail(t, AZG_E_INVALID, w + ": n_rows must be 1..max_batch");
     if (opt->momentum != 0.0 || opt->centered) return tfail(t, AZG_E_UNSUPPORTED, w + ": RMSprop with momentum or centered is not built");
     if (opt->grad_clip != 0.0) return tfail(t, AZG_E_UNSUPPORTED, w + ": gradient clipping is not built (a per-net global norm needs a pass of its own)");
+    plan->state0 = square_avg;
+    out->rms = rmsprop_step(opt->lr, opt->alpha, opt->eps, opt->weight_decay);
     return AZG_OK;
 }
 
-static void launch_backward(azg_trainer* t, float* params, const float* d_raw, int n_rows, const azg_rmsprop* opt, float* square_avg,
-                            float* grads) {
-    TrainOpt o;
-    o.lr = (float)opt->lr; o.alpha = (float)opt->alpha; o.one_minus_alpha = (float)(1.0 - opt->alpha); o.eps = (float)opt->eps;
-    o.wd = (float)opt->weight_decay;
-    if (t->wide) { tw_launch_backward(t->wide, t->stream, t->n_nets, o, params, d_raw, n_rows, square_avg, grads, t->scratch); return; }
-    if (t->ln)
-        hipLaunchKernelGGL(train_backward_kernel<true>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, o, params, d_raw, n_rows,
-                           square_avg, grads, t->scratch);
-    else
-        hipLaunchKernelGGL(train_backward_kernel<false>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, (const TrainDims&)t->d, o, params,
-                           d_raw, n_rows, square_avg, grads, t->scratch);
-}
-
-// An azg_optim as the launch takes it: the fused kernel with the old settings (plain RMSprop, nothing asked of the gradients as a
-// whole), or the deferred kernel's TrainOptD for the step opt->step + step_add + 1.
-struct OptPlan {
-    bool fused;
-    azg_rmsprop rms;
-    TrainOptD o;
-};
-
+// An azg_optim as the launch takes it, for the step opt->step + step_add + 1: with plain RMSprop and nothing asked of the gradients
+// as a whole the fused kernel (out->rms), else the deferred one.  plan: the form (unless the call's is the table) and the state
+// pointers; NULL for the entries of a table, which entry 0 has set.
 static int check_optim(azg_trainer* t, const char* who, const float* params, const azg_optim* opt, int32_t n_rows, int step_add,
-                       OptPlan* out) {
+                       TrainPlan* plan, TrainOptD* out) {
     const std::string w(who);
     if (!params || !opt) return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
     if (opt->struct_size != (int32_t)sizeof(azg_optim)) return tfail(t, AZG_E_INVALID, w + ": azg_optim.struct_size mismatch");
@@ -275,13 +288,8 @@ static int check_optim(azg_trainer* t, const char* who, const float* params, con
     if (opt->step < 0 || opt->step > INT32_MAX - 1 - step_add) return tfail(t, AZG_E_INVALID, w + ": azg_optim.step must be >= 0 (and fit with the epoch's steps)");
     if (adam && !(opt->beta1 >= 0.0 && opt->beta1 < 1.0 && opt->beta2 >= 0.0 && opt->beta2 < 1.0))
         return tfail(t, AZG_E_INVALID, w + ": Adam's betas must lie in [0, 1)");
-    OptPlan pl{};
-    pl.fused = !adam && opt->grad_clip == 0.0 && !opt->grad_norms;
-    pl.rms.struct_size = (int32_t)sizeof(azg_rmsprop);
-    pl.rms.lr = opt->lr; pl.rms.alpha = opt->alpha; pl.rms.eps = opt->eps; pl.rms.weight_decay = opt->weight_decay;
-    TrainOptD& o = pl.o;
-    o.rms.lr = (float)opt->lr; o.rms.alpha = (float)opt->alpha; o.rms.one_minus_alpha = (float)(1.0 - opt->alpha);
-    o.rms.eps = (float)opt->eps; o.rms.wd = (float)opt->weight_decay;
+    TrainOptD o{};
+    o.rms = rmsprop_step(opt->lr, opt->alpha, opt->eps, opt->weight_decay);
     o.kind = opt->kind;
     o.clip = (float)opt->grad_clip;
     o.want_norm = (opt->grad_clip != 0.0 || opt->grad_norms) ? 1 : 0;
@@ -291,41 +299,20 @@ static int check_optim(azg_trainer* t, const char* who, const float* params, con
         o.bc1 = 1.0 - std::pow(o.b1, step);
         o.bc2_sqrt = std::sqrt(1.0 - std::pow(o.b2, step));
     }
-    *out = pl;
-    return AZG_OK;
-}
-
-// The optimiser argument of a step or an epoch in either form: (azg_rmsprop, square_avg) of the first entry points, or an azg_optim.
-struct OptArg {
-    bool opt_form;
-    const azg_rmsprop* rms;
-    float* square_avg;
-    const azg_optim* opt;
-};
-
-static int check_opt_arg(azg_trainer* t, const char* who, const float* params, const OptArg& a, int32_t n_rows, int step_add, OptPlan* pl) {
-    if (a.opt_form) return check_optim(t, who, params, a.opt, n_rows, step_add, pl);
-    if (int rc = check_backward(t, who, params, a.rms, a.square_avg, n_rows)) return rc;
-    pl->fused = true;
-    pl->rms = *a.rms;
-    return AZG_OK;
-}
-
-static void launch_backward_arg(azg_trainer* t, float* params, const float* d_raw, int n_rows, const OptPlan& pl, const OptArg& a,
-                                float* grads) {
-    if (pl.fused) { launch_backward(t, params, d_raw, n_rows, &pl.rms, a.opt_form ? a.opt->state0 : a.square_avg, grads); return; }
-    float* gr = grads ? grads : t->grad_buf;
-    if (t->wide) {
-        tw_launch_backward_deferred(t->wide, t->stream, t->n_nets, pl.o, params, d_raw, n_rows, a.opt->state0, a.opt->state1, gr,
-                                    a.opt->grad_norms, t->scratch, t->norm_part);
-        return;
+    if (plan) {
+        if (plan->form != OptForm::table) plan->form = (!adam && !o.want_norm) ? OptForm::fused : OptForm::deferred;
+        plan->state0 = opt->state0; plan->state1 = opt->state1; plan->grad_norms = opt->grad_norms;
     }
-    if (t->ln)
-        hipLaunchKernelGGL(train_backward_deferred_kernel<true>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, pl.o, params, d_raw,
-                           n_rows, a.opt->state0, a.opt->state1, gr, a.opt->grad_norms, t->scratch);
-    else
-        hipLaunchKernelGGL(train_backward_deferred_kernel<false>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, (const TrainDims&)t->d,
-                           pl.o, params, d_raw, n_rows, a.opt->state0, a.opt->state1, gr, a.opt->grad_norms, t->scratch);
+    *out = o;
+    return AZG_OK;
+}
+
+// The optimiser of minibatch m, in the form the caller gave it: (rms, square_avg), or opt (entry 0 of a table).
+static int check_optimiser(azg_trainer* t, const char* who, const float* params, const azg_rmsprop* rms, float* square_avg,
+                           const azg_optim* opt, TrainPlan* plan, int m) {
+    Minibatch& mb = plan->mb[m];
+    if (rms || square_avg) return check_backward(t, who, params, rms, square_avg, mb.rows, plan, &mb.o);
+    return check_optim(t, who, params, opt, mb.rows, m, plan, &mb.o);
 }
 
 // The loss settings as the kernel takes them; every refusal of azg_trainer_loss.
@@ -343,7 +330,7 @@ static int check_loss(azg_trainer* t, const char* who, int32_t n_rows, int32_t n
     if (cfg->reduction != AZG_REDUCE_MEAN && cfg->reduction != AZG_REDUCE_SUM) return tfail(t, AZG_E_UNSUPPORTED, w + ": reduction must be mean or sum");
     if (cfg->kind == AZG_LOSS_ALPHAZERO && cfg->head != AZG_HEAD_DISCRETE)
         return tfail(t, AZG_E_UNSUPPORTED, w + ": AlphaZeroLoss needs a discrete head");
-    const int nd = t->d.nd;
+    const int nd = t->net.nd;
     int C = 1;
     if (cfg->head == AZG_HEAD_GMM) {
         C = t->num_components;
@@ -392,35 +379,6 @@ static int check_loss(azg_trainer* t, const char* who, int32_t n_rows, int32_t n
     return AZG_OK;
 }
 
-static int ensure(azg_trainer* t, void** buf, size_t bytes) {
-    if (*buf) return AZG_OK;
-    const hipError_t rc = hipMalloc(buf, bytes);
-    if (rc != hipSuccess) { *buf = nullptr; return tfail(t, AZG_E_DEVICE, std::string("azg_trainer: ") + hipGetErrorString(rc)); }
-    return AZG_OK;
-}
-
-// (for buffers whose size depends on the call: a larger one replaces the old one; the stream is idle between calls)
-static int grow(azg_trainer* t, void** buf, size_t* have, size_t bytes) {
-    if (*buf && *have >= bytes) return AZG_OK;
-    void* p = nullptr;
-    const hipError_t rc = hipMalloc(&p, bytes);
-    if (rc != hipSuccess) return tfail(t, AZG_E_DEVICE, std::string("azg_trainer: ") + hipGetErrorString(rc));
-    if (*buf) (void)hipFree(*buf);
-    *buf = p;
-    *have = bytes;
-    return AZG_OK;
-}
-
-static void launch_loss(azg_trainer* t, const LossDims& c, const float* raw, const float* actions, const float* counts, const float* values,
-                        int n_rows, const azg_alpha_state* st, float* d_raw, float* losses) {
-    const bool tuned = c.kind == AZG_LOSS_A0C_TUNED;
-    hipLaunchKernelGGL(train_loss_kernel, dim3(t->n_nets), dim3(TR_LOSS_THREADS), 0, t->stream, c, raw, actions, counts, values, n_rows,
-                       tuned ? st->log_alpha : nullptr, tuned ? st->exp_avg : nullptr, tuned ? st->exp_avg_sq : nullptr, d_raw, losses,
-                       t->loss_rows, t->max_batch);
-}
-
-// ---- the *_nets entry points: one azg_optim and / or one azg_loss_cfg per net ----
-
 static int nets_differ(azg_trainer* t, const char* who, const char* field, int k) {
     return tfail(t, AZG_E_INVALID, std::string(who) + ": " + field + " of net " + std::to_string(k) + " differs from net 0's (it must be equal in every entry)");
 }
@@ -432,12 +390,12 @@ static int net_refused(azg_trainer* t, const char* who, int k, int rc) {
 }
 
 // Entry 0 has passed the *_opt call's checks.  Here: entries 1 .. n_nets - 1 equal entry 0 where they must; then every entry goes
-// through check_optim / check_loss for every minibatch (count[m] rows, Adam steps + m) -- the expressions of the one-net call, so
+// through check_optim / check_loss for every minibatch (its rows, Adam steps + m) -- the expressions of the one-net call, so
 // the bias corrections and every derived factor are that call's -- and what they return fills the host table.  (They are called with
 // an empty name, which a refusal gets from net_refused: a call that passes builds no message string per net.)  opts or cfgs may be
 // NULL (a call without that kind of entry).  Nothing is launched or written to the device.
-static int plan_nets(azg_trainer* t, const char* who, const float* params, const azg_optim* opts, const azg_loss_cfg* cfgs,
-                     const azg_alpha_state* alpha_state, bool stepped, int32_t n_actions, const int* count, int M) {
+static int plan_nets(azg_trainer* t, const char* who, const float* params, const azg_optim* opts, const azg_loss_cfg* cfgs, bool stepped,
+                     int32_t n_actions, TrainPlan* plan) {
     const int K = t->n_nets;
     for (int k = 1; k < K; ++k) {
         if (opts) {
@@ -458,24 +416,24 @@ static int plan_nets(azg_trainer* t, const char* who, const float* params, const
             if (!(b.action_bound == a.action_bound)) return nets_differ(t, who, "azg_loss_cfg.action_bound", k);
         }
     }
-    const size_t n = (size_t)M * (size_t)K;
-    t->nets_loss_off = opts ? n * sizeof(TrainOptD) : 0;
-    t->nets_host.resize(t->nets_loss_off + (cfgs ? n * sizeof(LossDims) : 0));
+    const size_t M = plan->mb.size(), n = M * (size_t)K;
+    plan->loss_off = opts ? n * sizeof(TrainOptD) : 0;
+    t->nets_host.resize(plan->loss_off + (cfgs ? n * sizeof(LossDims) : 0));
     TrainOptD* od = reinterpret_cast<TrainOptD*>(t->nets_host.data());
-    LossDims* ld = reinterpret_cast<LossDims*>(t->nets_host.data() + t->nets_loss_off);
-    t->nets_any_norm = false;
-    for (int m = 0; m < M; ++m) {
+    LossDims* ld = reinterpret_cast<LossDims*>(t->nets_host.data() + plan->loss_off);
+    plan->any_norm = false;
+    for (size_t m = 0; m < M; ++m) {
+        const int rows = plan->mb[m].rows;
         azg_alpha_state st{};
-        if (stepped) { st = *alpha_state; st.step += m; }
+        if (stepped) { st = *plan->alpha; st.step += (int)m; }
         for (int k = 0; k < K; ++k) {
             if (opts) {
-                OptPlan pl;
-                if (int rc = check_optim(t, "", params, &opts[k], count[m], m, &pl)) return net_refused(t, who, k, rc);
-                od[(size_t)m * K + k] = pl.o;
-                t->nets_any_norm = t->nets_any_norm || pl.o.want_norm;
+                TrainOptD& o = od[m * K + k];
+                if (int rc = check_optim(t, "", params, &opts[k], rows, (int)m, nullptr, &o)) return net_refused(t, who, k, rc);
+                plan->any_norm = plan->any_norm || o.want_norm;
             }
             if (cfgs) {
-                if (int rc = check_loss(t, "", count[m], n_actions, &cfgs[k], stepped ? &st : alpha_state, &ld[(size_t)m * K + k]))
+                if (int rc = check_loss(t, "", rows, n_actions, &cfgs[k], stepped ? &st : plan->alpha, &ld[m * K + k]))
                     return net_refused(t, who, k, rc);
             }
         }
@@ -483,40 +441,94 @@ static int plan_nets(azg_trainer* t, const char* who, const float* params, const
     return AZG_OK;
 }
 
-// The table to the device: one asynchronous copy on the trainer's stream, in front of the call's first launch.  nets_host stays as
-// it is until the call's synchronisation.
-static int upload_nets(azg_trainer* t, const char* who) {
+// ---- the launches ----
+
+template <typename T>
+static int ensure(azg_trainer* t, T*& buf, size_t n) {
+    if (buf) return AZG_OK;
+    buf = t->mem.alloc<T>(n);
+    if (!buf) return tfail(t, AZG_E_DEVICE, std::string("azg_trainer: ") + hipGetErrorString(t->mem.last));
+    return AZG_OK;
+}
+
+static int grow(azg_trainer* t, DeviceBuffer& buf, size_t bytes) {
+    if (!buf.reserve(bytes)) return tfail(t, AZG_E_DEVICE, std::string("azg_trainer: ") + hipGetErrorString(buf.last));
+    return AZG_OK;
+}
+
+// A table plan's settings to the device: one asynchronous copy on the trainer's stream, in front of the call's first launch.
+// nets_host stays as it is until the call's synchronisation.
+static int upload_nets(azg_trainer* t, const char* who, const TrainPlan& plan) {
+    if (plan.form != OptForm::table) return AZG_OK;
     const size_t bytes = t->nets_host.size();
-    if (int rc = grow(t, (void**)&t->nets_dev, &t->nets_bytes, bytes)) return rc;
-    const hipError_t up = hipMemcpyAsync(t->nets_dev, t->nets_host.data(), bytes, hipMemcpyHostToDevice, t->stream);
+    if (int rc = grow(t, t->nets_dev, bytes)) return rc;
+    const hipError_t up = hipMemcpyAsync(t->nets_dev.p, t->nets_host.data(), bytes, hipMemcpyHostToDevice, t->stream);
     if (up != hipSuccess) return tfail(t, AZG_E_DEVICE, std::string(who) + ": " + hipGetErrorString(up));
     return AZG_OK;
 }
 
-// minibatch m's launches with every net's own entry
-static void launch_loss_nets(azg_trainer* t, int m, int kind, const float* raw, const float* actions, const float* counts, const float* values,
-                             int n_rows, const azg_alpha_state* st, float* d_raw, float* losses) {
-    const bool tuned = kind == AZG_LOSS_A0C_TUNED;
-    const LossDims* table = reinterpret_cast<const LossDims*>(t->nets_dev + t->nets_loss_off) + (size_t)m * t->n_nets;
-    hipLaunchKernelGGL(train_loss_nets_kernel, dim3(t->n_nets), dim3(TR_LOSS_THREADS), 0, t->stream, table, raw, actions, counts, values, n_rows,
-                       tuned ? st->log_alpha : nullptr, tuned ? st->exp_avg : nullptr, tuned ? st->exp_avg_sq : nullptr, d_raw, losses,
-                       t->loss_rows, t->max_batch);
+static void launch_forward(azg_trainer* t, const float* params, const float* obs, int n_rows, float* raw) {
+    if (t->net.wide) { tw_launch_forward(t->net, t->stream, t->n_nets, params, obs, n_rows, raw, t->scratch); return; }
+    const dim3 grid((n_rows + 15) / 16, t->n_nets);
+    if (t->net.layernorm) hipLaunchKernelGGL(train_forward_kernel<true>, grid, dim3(64), 0, t->stream, t->dims, params, obs, n_rows, raw, t->scratch);
+    else hipLaunchKernelGGL(train_forward_kernel<false>, grid, dim3(64), 0, t->stream, (const TrainDims&)t->dims, params, obs, n_rows, raw, t->scratch);
 }
 
-static void launch_backward_nets(azg_trainer* t, int m, float* params, const float* d_raw, int n_rows, const azg_optim* opts, float* grads) {
-    const TrainOptD* table = reinterpret_cast<const TrainOptD*>(t->nets_dev) + (size_t)m * t->n_nets;
-    float* gr = grads ? grads : t->grad_buf;
-    if (t->wide) {
-        tw_launch_backward_deferred_nets(t->wide, t->stream, t->n_nets, table, t->nets_any_norm, params, d_raw, n_rows, opts->state0,
-                                         opts->state1, gr, opts->grad_norms, t->scratch, t->norm_part);
-        return;
+// minibatch m's losses: with the plan's LossDims, or every net with its own entry of the table
+static void launch_loss(azg_trainer* t, const TrainPlan& plan, int m, const float* raw, const float* actions, const float* counts,
+                        const float* values, float* d_raw, float* losses) {
+    const Minibatch& mb = plan.mb[m];
+    const bool tuned = mb.c.kind == AZG_LOSS_A0C_TUNED;
+    float* log_alpha = tuned ? plan.alpha->log_alpha : nullptr;
+    float* exp_avg = tuned ? plan.alpha->exp_avg : nullptr;
+    float* exp_avg_sq = tuned ? plan.alpha->exp_avg_sq : nullptr;
+    if (plan.form == OptForm::table) {
+        const LossDims* table = reinterpret_cast<const LossDims*>((const unsigned char*)t->nets_dev.p + plan.loss_off) + (size_t)m * t->n_nets;
+        hipLaunchKernelGGL(train_loss_nets_kernel, dim3(t->n_nets), dim3(TR_LOSS_THREADS), 0, t->stream, table, raw, actions, counts, values,
+                           mb.rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, t->loss_rows, t->max_batch);
+    } else {
+        hipLaunchKernelGGL(train_loss_kernel, dim3(t->n_nets), dim3(TR_LOSS_THREADS), 0, t->stream, mb.c, raw, actions, counts, values,
+                           mb.rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, t->loss_rows, t->max_batch);
     }
-    if (t->ln)
-        hipLaunchKernelGGL(train_backward_deferred_nets_kernel<true>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream, t->d, table, params,
-                           d_raw, n_rows, opts->state0, opts->state1, gr, opts->grad_norms, t->scratch);
-    else
-        hipLaunchKernelGGL(train_backward_deferred_nets_kernel<false>, dim3(t->n_nets), dim3(TR_BWD_THREADS), 0, t->stream,
-                           (const TrainDims&)t->d, table, params, d_raw, n_rows, opts->state0, opts->state1, gr, opts->grad_norms, t->scratch);
+}
+
+// minibatch m's backward pass and optimiser step, in the plan's form (a deferred form without the caller's grads keeps them in grad_buf)
+static void launch_backward(azg_trainer* t, const TrainPlan& plan, int m, float* params, const float* d_raw, float* grads) {
+    const Minibatch& mb = plan.mb[m];
+    const int K = t->n_nets, n_rows = mb.rows;
+    const dim3 grid(K), block(TR_BWD_THREADS);
+    const bool wide = t->net.wide, ln = t->net.layernorm != 0;
+    const TrainDimsLN& d = t->dims;
+    const TrainDims& d0 = t->dims;
+    float *s0 = plan.state0, *s1 = plan.state1, *norms = plan.grad_norms;
+    float* gr = grads ? grads : t->grad_buf;
+    switch (plan.form) {
+    case OptForm::fused:
+        if (wide) tw_launch_backward(t->net, t->stream, K, mb.o.rms, params, d_raw, n_rows, s0, grads, t->scratch);
+        else if (ln) hipLaunchKernelGGL(train_backward_kernel<true>, grid, block, 0, t->stream, d, mb.o.rms, params, d_raw, n_rows, s0, grads, t->scratch);
+        else hipLaunchKernelGGL(train_backward_kernel<false>, grid, block, 0, t->stream, d0, mb.o.rms, params, d_raw, n_rows, s0, grads, t->scratch);
+        break;
+    case OptForm::deferred:
+        if (wide) tw_launch_backward_deferred(t->net, t->stream, K, mb.o, params, d_raw, n_rows, s0, s1, gr, norms, t->scratch, t->norm_part);
+        else if (ln) hipLaunchKernelGGL(train_backward_deferred_kernel<true>, grid, block, 0, t->stream, d, mb.o, params, d_raw, n_rows, s0, s1, gr, norms, t->scratch);
+        else hipLaunchKernelGGL(train_backward_deferred_kernel<false>, grid, block, 0, t->stream, d0, mb.o, params, d_raw, n_rows, s0, s1, gr, norms, t->scratch);
+        break;
+    case OptForm::table: {
+        const TrainOptD* table = reinterpret_cast<const TrainOptD*>(t->nets_dev.p) + (size_t)m * K;
+        if (wide) tw_launch_backward_deferred_nets(t->net, t->stream, K, table, plan.any_norm, params, d_raw, n_rows, s0, s1, gr, norms, t->scratch, t->norm_part);
+        else if (ln) hipLaunchKernelGGL(train_backward_deferred_nets_kernel<true>, grid, block, 0, t->stream, d, table, params, d_raw, n_rows, s0, s1, gr, norms, t->scratch);
+        else hipLaunchKernelGGL(train_backward_deferred_nets_kernel<false>, grid, block, 0, t->stream, d0, table, params, d_raw, n_rows, s0, s1, gr, norms, t->scratch);
+        break;
+    }
+    }
+}
+
+// one minibatch: forward, losses (d_raw to d_raw_buf), backward and step
+static void launch_minibatch(azg_trainer* t, const TrainPlan& plan, int m, float* params, const float* obs, const float* actions,
+                             const float* counts, const float* values, float* raw, float* grads, float* losses) {
+    launch_forward(t, params, obs, plan.mb[m].rows, raw);
+    launch_loss(t, plan, m, raw, actions, counts, values, t->d_raw_buf, losses);
+    launch_backward(t, plan, m, params, t->d_raw_buf, grads);
 }
 
 static int finish(azg_trainer* t, const char* who) {
@@ -525,6 +537,153 @@ static int finish(azg_trainer* t, const char* who) {
     if (rc != hipSuccess) return tfail(t, AZG_E_DEVICE, std::string(who) + ": " + hipGetErrorString(rc));
     return AZG_OK;
 }
+
+// ---- the entry points: one body per family; form = what the entry point's name implies (TrainPlan) ----
+
+static int backward_step_impl(azg_trainer* t, const char* who, OptForm form, float* params, const float* d_raw, int32_t n_rows,
+                              const azg_rmsprop* rms, float* square_avg, const azg_optim* opt, float* grads) {
+    if (!t) return AZG_E_INVALID;
+    if (!d_raw) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
+    TrainPlan plan(form, n_rows);
+    if (int rc = check_optimiser(t, who, params, rms, square_avg, opt, &plan, 0)) return rc;
+    if (form == OptForm::table) { if (int rc = plan_nets(t, who, params, opt, nullptr, false, 0, &plan)) return rc; }
+    if (t->fwd_rows != n_rows) return tfail(t, AZG_E_STATE, std::string(who) + ": needs azg_trainer_forward of the same n_rows first");
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    if (int rc = upload_nets(t, who, plan)) return rc;
+    t->fwd_rows = 0;   // the scratch is consumed: dZ overwrites the activation derivatives
+    launch_backward(t, plan, 0, params, d_raw, grads);
+    return finish(t, who);
+}
+
+static int loss_impl(azg_trainer* t, const char* who, OptForm form, const float* raw, const float* actions, const float* counts,
+                     const float* values, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* cfg, const azg_alpha_state* alpha_state,
+                     float* d_raw, float* losses) {
+    if (!t) return AZG_E_INVALID;
+    if (!raw || !actions || !counts || !values || !d_raw || !losses) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
+    TrainPlan plan(form, n_rows);
+    plan.alpha = alpha_state;
+    if (int rc = check_loss(t, who, n_rows, n_actions, cfg, alpha_state, &plan.mb[0].c)) return rc;
+    if (form == OptForm::table) { if (int rc = plan_nets(t, who, nullptr, nullptr, cfg, false, n_actions, &plan)) return rc; }
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    if (int rc = ensure(t, t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch)) return rc;
+    if (int rc = upload_nets(t, who, plan)) return rc;
+    launch_loss(t, plan, 0, raw, actions, counts, values, d_raw, losses);
+    return finish(t, who);
+}
+
+static int step_impl(azg_trainer* t, const char* who, OptForm form, float* params, const float* obs, const float* actions,
+                     const float* counts, const float* values, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg,
+                     const azg_alpha_state* alpha_state, const azg_rmsprop* rms, float* square_avg, const azg_optim* opt, float* grads,
+                     float* raw_out, float* losses) {
+    if (!t) return AZG_E_INVALID;
+    if (!actions || !counts || !values || !losses) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
+    if (int rc = check_forward(t, who, params, obs, n_rows)) return rc;
+    TrainPlan plan(form, n_rows);
+    plan.alpha = alpha_state;
+    if (int rc = check_loss(t, who, n_rows, n_actions, loss_cfg, alpha_state, &plan.mb[0].c)) return rc;
+    if (int rc = check_optimiser(t, who, params, rms, square_avg, opt, &plan, 0)) return rc;
+    if (form == OptForm::table) { if (int rc = plan_nets(t, who, params, opt, loss_cfg, false, n_actions, &plan)) return rc; }
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    const size_t per = (size_t)t->n_nets * t->max_batch * t->net.NO;
+    if (int rc = ensure(t, t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch)) return rc;
+    if (int rc = ensure(t, t->d_raw_buf, per)) return rc;
+    if (!raw_out) { if (int rc = ensure(t, t->raw_buf, per)) return rc; }
+    if (int rc = upload_nets(t, who, plan)) return rc;
+    t->fwd_rows = 0;
+    t->step_rows = 0;
+    launch_minibatch(t, plan, 0, params, obs, actions, counts, values, raw_out ? raw_out : t->raw_buf, grads, losses);
+    if (int rc = finish(t, who)) return rc;
+    t->step_rows = n_rows;
+    return AZG_OK;
+}
+
+static int epoch_impl(azg_trainer* t, const char* who, OptForm form, float* params, const azg_epoch_rows* rows, const int32_t* order,
+                      int32_t n_order, int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
+                      const azg_rmsprop* rms, float* square_avg, const azg_optim* opt, double* loss_sums, int32_t* n_minibatches) {
+    if (!t) return AZG_E_INVALID;
+    const std::string w(who);
+    if (!params || !rows || !order || !loss_cfg || !(opt || (rms && square_avg)) || !loss_sums || !n_minibatches)
+        return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
+    if (rows->struct_size != (int32_t)sizeof(azg_epoch_rows)) return tfail(t, AZG_E_INVALID, w + ": azg_epoch_rows.struct_size mismatch");
+    if (!rows->rows) return tfail(t, AZG_E_INVALID, w + ": NULL pointer in azg_epoch_rows");
+    if (batch_size < 1 || n_order < 1) return tfail(t, AZG_E_INVALID, w + ": batch_size and n_order must be at least 1");
+    const int A = rows->n_actions;
+    if (A < 1 || A > TR_MAX_ACTIONS) return tfail(t, AZG_E_INVALID, w + ": n_actions must be 1..16");
+    if (rows->state_dim != t->net.in_dim) return tfail(t, AZG_E_INVALID, w + ": state_dim must be the trainer's in_dim");
+    if (rows->row_len != rows->state_dim + 3 * A + 1) return tfail(t, AZG_E_INVALID, w + ": row_len must be state_dim + 3 * n_actions + 1");
+    if (rows->rows_per_net < 1 || rows->group < 1) return tfail(t, AZG_E_INVALID, w + ": rows_per_net and group must be at least 1");
+    if (rows->group_stride < 0 || rows->net_stride < 0) return tfail(t, AZG_E_INVALID, w + ": strides must be >= 0");
+    // the minibatches: train_on_rows's rule, the last one absorbing the remainder
+    TrainPlan plan(form);
+    plan.alpha = alpha_state;
+    plan.mb.clear();
+    int largest = 0;
+    for (int64_t i = 0; i < n_order;) {
+        const int64_t j = i + 2 * (int64_t)batch_size > n_order ? (int64_t)n_order : i + batch_size;
+        Minibatch mb;
+        mb.first = (int)i;
+        mb.rows = (int)(j - i);
+        plan.mb.push_back(mb);
+        largest = mb.rows > largest ? mb.rows : largest;
+        i = j;
+    }
+    const int M = (int)plan.mb.size();
+    if (largest > t->max_batch) return tfail(t, AZG_E_INVALID, w + ": the largest minibatch exceeds max_batch");
+    // every refusal of azg_trainer_step, for every minibatch's row count and Adam step
+    const bool stepped = alpha_state && loss_cfg->struct_size == (int32_t)sizeof(azg_loss_cfg) && loss_cfg->kind == AZG_LOSS_A0C_TUNED &&
+                         alpha_state->struct_size == (int32_t)sizeof(azg_alpha_state);
+    if (stepped && alpha_state->step > INT32_MAX - M) return tfail(t, AZG_E_INVALID, w + ": azg_alpha_state.step too large");
+    for (int m = 0; m < M; ++m) {
+        azg_alpha_state st{};
+        if (stepped) { st = *alpha_state; st.step += m; }
+        if (int rc = check_loss(t, who, plan.mb[m].rows, A, loss_cfg, stepped ? &st : alpha_state, &plan.mb[m].c)) return rc;
+        if (int rc = check_optimiser(t, who, params, rms, square_avg, opt, &plan, m)) return rc;
+    }
+    if (form == OptForm::table) { if (int rc = plan_nets(t, who, params, opt, loss_cfg, stepped, A, &plan)) return rc; }
+    const size_t K = (size_t)t->n_nets;
+    for (size_t e = 0; e < K * (size_t)n_order; ++e)
+        if (order[e] < 0 || order[e] >= rows->rows_per_net) return tfail(t, AZG_E_INVALID, w + ": an order entry is outside 0 .. rows_per_net - 1");
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    const size_t mb = (size_t)t->max_batch, per = K * mb * t->net.NO, in_dim = (size_t)t->net.in_dim;
+    if (int rc = ensure(t, t->loss_rows, K * 3 * mb)) return rc;
+    if (int rc = ensure(t, t->d_raw_buf, per)) return rc;
+    if (int rc = ensure(t, t->raw_buf, per)) return rc;
+    if (int rc = grow(t, t->order_buf, K * (size_t)n_order * sizeof(int32_t))) return rc;
+    if (int rc = grow(t, t->stage_buf, K * mb * (in_dim + 2 * (size_t)A + 1) * sizeof(float))) return rc;
+    if (int rc = grow(t, t->loss_table, (size_t)M * K * AZG_LOSS_SLOTS * sizeof(float))) return rc;
+    int* order_dev = (int*)t->order_buf.p;
+    float* loss_table = (float*)t->loss_table.p;
+    float* obs = (float*)t->stage_buf.p;
+    float* actions = obs + K * mb * in_dim;
+    float* counts = actions + K * mb * (size_t)A;
+    float* values = counts + K * mb * (size_t)A;
+    GatherDims g{};
+    g.row_len = rows->row_len; g.state_dim = rows->state_dim; g.A = A; g.group = rows->group; g.n_order = n_order;
+    g.group_stride = rows->group_stride; g.net_stride = rows->net_stride;
+    t->fwd_rows = 0;
+    t->step_rows = 0;
+    if (int rc = upload_nets(t, who, plan)) return rc;
+    const hipError_t up = hipMemcpyAsync(order_dev, order, K * (size_t)n_order * sizeof(int32_t), hipMemcpyHostToDevice, t->stream);
+    if (up != hipSuccess) return tfail(t, AZG_E_DEVICE, w + ": " + hipGetErrorString(up));
+    for (int m = 0; m < M; ++m) {
+        const int B = plan.mb[m].rows;
+        hipLaunchKernelGGL(train_gather_kernel, dim3((B + TR_GATHER_THREADS / 64 - 1) / (TR_GATHER_THREADS / 64), t->n_nets),
+                           dim3(TR_GATHER_THREADS), 0, t->stream, g, rows->rows, order_dev, plan.mb[m].first, B, obs, actions, counts, values);
+        launch_minibatch(t, plan, m, params, obs, actions, counts, values, t->raw_buf, nullptr, loss_table + (size_t)m * K * AZG_LOSS_SLOTS);
+    }
+    const int n_sums = t->n_nets * AZG_LOSS_SLOTS;
+    hipLaunchKernelGGL(train_loss_sum_kernel, dim3((n_sums + 63) / 64), dim3(64), 0, t->stream, loss_table, M, n_sums, loss_sums);
+    if (int rc = finish(t, who)) return rc;
+    t->step_rows = plan.mb[M - 1].rows;
+    *n_minibatches = M;
+    return AZG_OK;
+}
+
+extern "C" {
 
 int azg_trainer_forward(azg_trainer* t, const float* params, const float* obs, int32_t n_rows, float* raw) {
     if (!t) return AZG_E_INVALID;
@@ -541,241 +700,67 @@ int azg_trainer_forward(azg_trainer* t, const float* params, const float* obs, i
 
 int azg_trainer_backward_step(azg_trainer* t, float* params, const float* d_raw, int32_t n_rows, const azg_rmsprop* opt, float* square_avg,
                               float* grads) {
-    if (!t) return AZG_E_INVALID;
-    if (!d_raw) return tfail(t, AZG_E_INVALID, "azg_trainer_backward_step: NULL pointer");
-    if (int rc = check_backward(t, "azg_trainer_backward_step", params, opt, square_avg, n_rows)) return rc;
-    if (t->fwd_rows != n_rows) return tfail(t, AZG_E_STATE, "azg_trainer_backward_step: needs azg_trainer_forward of the same n_rows first");
-    DeviceScope scope(t->device_id);
-    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
-    t->fwd_rows = 0;   // the scratch is consumed: dZ overwrites the activation derivatives
-    launch_backward(t, params, d_raw, (int)n_rows, opt, square_avg, grads);
-    return finish(t, "azg_trainer_backward_step");
+    return backward_step_impl(t, "azg_trainer_backward_step", OptForm::fused, params, d_raw, n_rows, opt, square_avg, nullptr, grads);
 }
 
 int azg_trainer_backward_step_opt(azg_trainer* t, float* params, const float* d_raw, int32_t n_rows, const azg_optim* opt, float* grads) {
-    if (!t) return AZG_E_INVALID;
-    if (!d_raw) return tfail(t, AZG_E_INVALID, "azg_trainer_backward_step_opt: NULL pointer");
-    OptPlan pl;
-    if (int rc = check_optim(t, "azg_trainer_backward_step_opt", params, opt, n_rows, 0, &pl)) return rc;
-    if (t->fwd_rows != n_rows) return tfail(t, AZG_E_STATE, "azg_trainer_backward_step_opt: needs azg_trainer_forward of the same n_rows first");
-    DeviceScope scope(t->device_id);
-    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
-    t->fwd_rows = 0;
-    launch_backward_arg(t, params, d_raw, (int)n_rows, pl, OptArg{true, nullptr, nullptr, opt}, grads);
-    return finish(t, "azg_trainer_backward_step_opt");
+    return backward_step_impl(t, "azg_trainer_backward_step_opt", OptForm::fused, params, d_raw, n_rows, nullptr, nullptr, opt, grads);
+}
+
+int azg_trainer_backward_step_nets(azg_trainer* t, float* params, const float* d_raw, int32_t n_rows, const azg_optim* opts, float* grads) {
+    return backward_step_impl(t, "azg_trainer_backward_step_nets", OptForm::table, params, d_raw, n_rows, nullptr, nullptr, opts, grads);
 }
 
 int azg_trainer_loss(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values, int32_t n_rows,
                      int32_t n_actions, const azg_loss_cfg* cfg, const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
-    if (!t) return AZG_E_INVALID;
-    if (!raw || !actions || !counts || !values || !d_raw || !losses) return tfail(t, AZG_E_INVALID, "azg_trainer_loss: NULL pointer");
-    LossDims c;
-    if (int rc = check_loss(t, "azg_trainer_loss", n_rows, n_actions, cfg, alpha_state, &c)) return rc;
-    DeviceScope scope(t->device_id);
-    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
-    if (int rc = ensure(t, (void**)&t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch * sizeof(double))) return rc;
-    launch_loss(t, c, raw, actions, counts, values, (int)n_rows, alpha_state, d_raw, losses);
-    return finish(t, "azg_trainer_loss");
+    return loss_impl(t, "azg_trainer_loss", OptForm::fused, raw, actions, counts, values, n_rows, n_actions, cfg, alpha_state, d_raw, losses);
 }
 
-static int step_impl(azg_trainer* t, const char* who, float* params, const float* obs, const float* actions, const float* counts,
-                     const float* values, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg,
-                     const azg_alpha_state* alpha_state, const OptArg& oa, float* grads, float* raw_out, float* losses,
-                     bool nets = false) {
-    if (!t) return AZG_E_INVALID;
-    if (!actions || !counts || !values || !losses) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
-    if (int rc = check_forward(t, who, params, obs, n_rows)) return rc;
-    LossDims c;
-    if (int rc = check_loss(t, who, n_rows, n_actions, loss_cfg, alpha_state, &c)) return rc;
-    OptPlan pl;
-    if (int rc = check_opt_arg(t, who, params, oa, n_rows, 0, &pl)) return rc;
-    const int rows1 = n_rows;
-    if (nets) { if (int rc = plan_nets(t, who, params, oa.opt, loss_cfg, alpha_state, false, n_actions, &rows1, 1)) return rc; }
-    DeviceScope scope(t->device_id);
-    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
-    const size_t per = (size_t)t->n_nets * t->max_batch * t->d.NO;
-    if (int rc = ensure(t, (void**)&t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch * sizeof(double))) return rc;
-    if (int rc = ensure(t, (void**)&t->d_raw_buf, per * sizeof(float))) return rc;
-    if (!raw_out) { if (int rc = ensure(t, (void**)&t->raw_buf, per * sizeof(float))) return rc; }
-    float* raw = raw_out ? raw_out : t->raw_buf;
-    if (nets) { if (int rc = upload_nets(t, who)) return rc; }
-    t->fwd_rows = 0;
-    t->step_rows = 0;
-    launch_forward(t, params, obs, (int)n_rows, raw);
-    if (nets) {
-        launch_loss_nets(t, 0, c.kind, raw, actions, counts, values, (int)n_rows, alpha_state, t->d_raw_buf, losses);
-        launch_backward_nets(t, 0, params, t->d_raw_buf, (int)n_rows, oa.opt, grads);
-    } else {
-        launch_loss(t, c, raw, actions, counts, values, (int)n_rows, alpha_state, t->d_raw_buf, losses);
-        launch_backward_arg(t, params, t->d_raw_buf, (int)n_rows, pl, oa, grads);
-    }
-    if (int rc = finish(t, who)) return rc;
-    t->step_rows = n_rows;
-    return AZG_OK;
+int azg_trainer_loss_nets(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values, int32_t n_rows,
+                          int32_t n_actions, const azg_loss_cfg* cfgs, const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
+    return loss_impl(t, "azg_trainer_loss_nets", OptForm::table, raw, actions, counts, values, n_rows, n_actions, cfgs, alpha_state, d_raw, losses);
 }
 
 int azg_trainer_step(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
                      int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
                      const azg_rmsprop* opt, float* square_avg, float* grads, float* raw_out, float* losses) {
-    return step_impl(t, "azg_trainer_step", params, obs, actions, counts, values, n_rows, n_actions, loss_cfg, alpha_state,
-                     OptArg{false, opt, square_avg, nullptr}, grads, raw_out, losses);
+    return step_impl(t, "azg_trainer_step", OptForm::fused, params, obs, actions, counts, values, n_rows, n_actions, loss_cfg, alpha_state,
+                     opt, square_avg, nullptr, grads, raw_out, losses);
 }
 
 int azg_trainer_step_opt(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
                          int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
                          const azg_optim* opt, float* grads, float* raw_out, float* losses) {
-    return step_impl(t, "azg_trainer_step_opt", params, obs, actions, counts, values, n_rows, n_actions, loss_cfg, alpha_state,
-                     OptArg{true, nullptr, nullptr, opt}, grads, raw_out, losses);
-}
-
-static int epoch_impl(azg_trainer* t, const char* who, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
-                      int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const OptArg& oa,
-                      double* loss_sums, int32_t* n_minibatches, bool nets = false) {
-    if (!t) return AZG_E_INVALID;
-    const std::string w(who);
-    const bool no_opt = oa.opt_form ? !oa.opt : (!oa.rms || !oa.square_avg);
-    if (!params || !rows || !order || !loss_cfg || no_opt || !loss_sums || !n_minibatches)
-        return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
-    if (rows->struct_size != (int32_t)sizeof(azg_epoch_rows)) return tfail(t, AZG_E_INVALID, w + ": azg_epoch_rows.struct_size mismatch");
-    if (!rows->rows) return tfail(t, AZG_E_INVALID, w + ": NULL pointer in azg_epoch_rows");
-    if (batch_size < 1 || n_order < 1) return tfail(t, AZG_E_INVALID, w + ": batch_size and n_order must be at least 1");
-    const int A = rows->n_actions;
-    if (A < 1 || A > TR_MAX_ACTIONS) return tfail(t, AZG_E_INVALID, w + ": n_actions must be 1..16");
-    if (rows->state_dim != t->d.in_dim) return tfail(t, AZG_E_INVALID, w + ": state_dim must be the trainer's in_dim");
-    if (rows->row_len != rows->state_dim + 3 * A + 1) return tfail(t, AZG_E_INVALID, w + ": row_len must be state_dim + 3 * n_actions + 1");
-    if (rows->rows_per_net < 1 || rows->group < 1) return tfail(t, AZG_E_INVALID, w + ": rows_per_net and group must be at least 1");
-    if (rows->group_stride < 0 || rows->net_stride < 0) return tfail(t, AZG_E_INVALID, w + ": strides must be >= 0");
-    // the minibatches: train_on_rows's rule, the last one absorbing the remainder
-    std::vector<int> first, count;
-    int largest = 0;
-    for (int64_t i = 0; i < n_order;) {
-        const int64_t j = i + 2 * (int64_t)batch_size > n_order ? (int64_t)n_order : i + batch_size;
-        first.push_back((int)i);
-        count.push_back((int)(j - i));
-        largest = (int)(j - i) > largest ? (int)(j - i) : largest;
-        i = j;
-    }
-    const int M = (int)first.size();
-    if (largest > t->max_batch) return tfail(t, AZG_E_INVALID, w + ": the largest minibatch exceeds max_batch");
-    // every refusal of azg_trainer_step, for every minibatch's row count and Adam step
-    const bool stepped = alpha_state && loss_cfg->struct_size == (int32_t)sizeof(azg_loss_cfg) && loss_cfg->kind == AZG_LOSS_A0C_TUNED &&
-                         alpha_state->struct_size == (int32_t)sizeof(azg_alpha_state);
-    if (stepped && alpha_state->step > INT32_MAX - M) return tfail(t, AZG_E_INVALID, w + ": azg_alpha_state.step too large");
-    std::vector<LossDims> dims((size_t)M);
-    std::vector<OptPlan> plans((size_t)M);
-    for (int m = 0; m < M; ++m) {
-        azg_alpha_state st{};
-        if (stepped) { st = *alpha_state; st.step += m; }
-        if (int rc = check_loss(t, who, count[m], A, loss_cfg, stepped ? &st : alpha_state, &dims[m])) return rc;
-        if (int rc = check_opt_arg(t, who, params, oa, count[m], m, &plans[m])) return rc;
-    }
-    if (nets) { if (int rc = plan_nets(t, who, params, oa.opt, loss_cfg, alpha_state, stepped, A, count.data(), M)) return rc; }
-    const size_t K = (size_t)t->n_nets;
-    for (size_t e = 0; e < K * (size_t)n_order; ++e)
-        if (order[e] < 0 || order[e] >= rows->rows_per_net) return tfail(t, AZG_E_INVALID, w + ": an order entry is outside 0 .. rows_per_net - 1");
-    DeviceScope scope(t->device_id);
-    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
-    const size_t mb = (size_t)t->max_batch, per = K * mb * t->d.NO, in_dim = (size_t)t->d.in_dim;
-    if (int rc = ensure(t, (void**)&t->loss_rows, K * 3 * mb * sizeof(double))) return rc;
-    if (int rc = ensure(t, (void**)&t->d_raw_buf, per * sizeof(float))) return rc;
-    if (int rc = ensure(t, (void**)&t->raw_buf, per * sizeof(float))) return rc;
-    if (int rc = grow(t, (void**)&t->order_buf, &t->order_bytes, K * (size_t)n_order * sizeof(int32_t))) return rc;
-    if (int rc = grow(t, (void**)&t->stage_buf, &t->stage_bytes, K * mb * (in_dim + 2 * (size_t)A + 1) * sizeof(float))) return rc;
-    if (int rc = grow(t, (void**)&t->loss_table, &t->table_bytes, (size_t)M * K * AZG_LOSS_SLOTS * sizeof(float))) return rc;
-    float* obs = t->stage_buf;
-    float* actions = obs + K * mb * in_dim;
-    float* counts = actions + K * mb * (size_t)A;
-    float* values = counts + K * mb * (size_t)A;
-    GatherDims g{};
-    g.row_len = rows->row_len; g.state_dim = rows->state_dim; g.A = A; g.group = rows->group; g.n_order = n_order;
-    g.group_stride = rows->group_stride; g.net_stride = rows->net_stride;
-    t->fwd_rows = 0;
-    t->step_rows = 0;
-    if (nets) { if (int rc = upload_nets(t, who)) return rc; }
-    const hipError_t up = hipMemcpyAsync(t->order_buf, order, K * (size_t)n_order * sizeof(int32_t), hipMemcpyHostToDevice, t->stream);
-    if (up != hipSuccess) return tfail(t, AZG_E_DEVICE, w + ": " + hipGetErrorString(up));
-    for (int m = 0; m < M; ++m) {
-        const int B = count[m];
-        hipLaunchKernelGGL(train_gather_kernel, dim3((B + TR_GATHER_THREADS / 64 - 1) / (TR_GATHER_THREADS / 64), t->n_nets),
-                           dim3(TR_GATHER_THREADS), 0, t->stream, g, rows->rows, t->order_buf, first[m], B, obs, actions, counts, values);
-        launch_forward(t, params, obs, B, t->raw_buf);
-        float* mb_losses = t->loss_table + (size_t)m * K * AZG_LOSS_SLOTS;
-        if (nets) {
-            launch_loss_nets(t, m, dims[m].kind, t->raw_buf, actions, counts, values, B, alpha_state, t->d_raw_buf, mb_losses);
-            launch_backward_nets(t, m, params, t->d_raw_buf, B, oa.opt, nullptr);
-        } else {
-            launch_loss(t, dims[m], t->raw_buf, actions, counts, values, B, alpha_state, t->d_raw_buf, mb_losses);
-            launch_backward_arg(t, params, t->d_raw_buf, B, plans[m], oa, nullptr);
-        }
-    }
-    const int n_sums = t->n_nets * AZG_LOSS_SLOTS;
-    hipLaunchKernelGGL(train_loss_sum_kernel, dim3((n_sums + 63) / 64), dim3(64), 0, t->stream, t->loss_table, M, n_sums, loss_sums);
-    if (int rc = finish(t, who)) return rc;
-    t->step_rows = count[M - 1];
-    *n_minibatches = M;
-    return AZG_OK;
-}
-
-int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
-                      int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_rmsprop* opt,
-                      float* square_avg, double* loss_sums, int32_t* n_minibatches) {
-    return epoch_impl(t, "azg_trainer_epoch", params, rows, order, n_order, batch_size, loss_cfg, alpha_state,
-                      OptArg{false, opt, square_avg, nullptr}, loss_sums, n_minibatches);
-}
-
-int azg_trainer_epoch_opt(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
-                          int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_optim* opt,
-                          double* loss_sums, int32_t* n_minibatches) {
-    return epoch_impl(t, "azg_trainer_epoch_opt", params, rows, order, n_order, batch_size, loss_cfg, alpha_state,
-                      OptArg{true, nullptr, nullptr, opt}, loss_sums, n_minibatches);
-}
-
-int azg_trainer_backward_step_nets(azg_trainer* t, float* params, const float* d_raw, int32_t n_rows, const azg_optim* opts, float* grads) {
-    if (!t) return AZG_E_INVALID;
-    const char* who = "azg_trainer_backward_step_nets";
-    if (!d_raw) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
-    OptPlan pl;
-    if (int rc = check_optim(t, who, params, opts, n_rows, 0, &pl)) return rc;
-    const int rows1 = n_rows;
-    if (int rc = plan_nets(t, who, params, opts, nullptr, nullptr, false, 0, &rows1, 1)) return rc;
-    if (t->fwd_rows != n_rows) return tfail(t, AZG_E_STATE, std::string(who) + ": needs azg_trainer_forward of the same n_rows first");
-    DeviceScope scope(t->device_id);
-    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
-    if (int rc = upload_nets(t, who)) return rc;
-    t->fwd_rows = 0;
-    launch_backward_nets(t, 0, params, d_raw, (int)n_rows, opts, grads);
-    return finish(t, who);
-}
-
-int azg_trainer_loss_nets(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values, int32_t n_rows,
-                          int32_t n_actions, const azg_loss_cfg* cfgs, const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
-    if (!t) return AZG_E_INVALID;
-    const char* who = "azg_trainer_loss_nets";
-    if (!raw || !actions || !counts || !values || !d_raw || !losses) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
-    LossDims c;
-    if (int rc = check_loss(t, who, n_rows, n_actions, cfgs, alpha_state, &c)) return rc;
-    const int rows1 = n_rows;
-    if (int rc = plan_nets(t, who, nullptr, nullptr, cfgs, alpha_state, false, n_actions, &rows1, 1)) return rc;
-    DeviceScope scope(t->device_id);
-    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
-    if (int rc = ensure(t, (void**)&t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch * sizeof(double))) return rc;
-    if (int rc = upload_nets(t, who)) return rc;
-    launch_loss_nets(t, 0, c.kind, raw, actions, counts, values, (int)n_rows, alpha_state, d_raw, losses);
-    return finish(t, who);
+    return step_impl(t, "azg_trainer_step_opt", OptForm::fused, params, obs, actions, counts, values, n_rows, n_actions, loss_cfg, alpha_state,
+                     nullptr, nullptr, opt, grads, raw_out, losses);
 }
 
 int azg_trainer_step_nets(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
                           int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfgs, const azg_alpha_state* alpha_state,
                           const azg_optim* opts, float* grads, float* raw_out, float* losses) {
-    return step_impl(t, "azg_trainer_step_nets", params, obs, actions, counts, values, n_rows, n_actions, loss_cfgs, alpha_state,
-                     OptArg{true, nullptr, nullptr, opts}, grads, raw_out, losses, true);
+    return step_impl(t, "azg_trainer_step_nets", OptForm::table, params, obs, actions, counts, values, n_rows, n_actions, loss_cfgs,
+                     alpha_state, nullptr, nullptr, opts, grads, raw_out, losses);
+}
+
+int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
+                      int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_rmsprop* opt,
+                      float* square_avg, double* loss_sums, int32_t* n_minibatches) {
+    return epoch_impl(t, "azg_trainer_epoch", OptForm::fused, params, rows, order, n_order, batch_size, loss_cfg, alpha_state, opt, square_avg,
+                      nullptr, loss_sums, n_minibatches);
+}
+
+int azg_trainer_epoch_opt(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
+                          int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_optim* opt,
+                          double* loss_sums, int32_t* n_minibatches) {
+    return epoch_impl(t, "azg_trainer_epoch_opt", OptForm::fused, params, rows, order, n_order, batch_size, loss_cfg, alpha_state, nullptr,
+                      nullptr, opt, loss_sums, n_minibatches);
 }
 
 int azg_trainer_epoch_nets(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
                            int32_t batch_size, const azg_loss_cfg* loss_cfgs, const azg_alpha_state* alpha_state, const azg_optim* opts,
                            double* loss_sums, int32_t* n_minibatches) {
-    return epoch_impl(t, "azg_trainer_epoch_nets", params, rows, order, n_order, batch_size, loss_cfgs, alpha_state,
-                      OptArg{true, nullptr, nullptr, opts}, loss_sums, n_minibatches, true);
+    return epoch_impl(t, "azg_trainer_epoch_nets", OptForm::table, params, rows, order, n_order, batch_size, loss_cfgs, alpha_state, nullptr,
+                      nullptr, opts, loss_sums, n_minibatches);
 }
 
 int azg_trainer_read_d_raw(azg_trainer* t, int32_t n_rows, float* d_raw) {
@@ -784,7 +769,7 @@ int azg_trainer_read_d_raw(azg_trainer* t, int32_t n_rows, float* d_raw) {
     if (n_rows < 1 || t->step_rows != n_rows) return tfail(t, AZG_E_STATE, "azg_trainer_read_d_raw: needs an azg_trainer_step of the same n_rows first");
     DeviceScope scope(t->device_id);
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
-    const hipError_t rc = hipMemcpyAsync(d_raw, t->d_raw_buf, (size_t)t->n_nets * n_rows * t->d.NO * sizeof(float), hipMemcpyDeviceToDevice, t->stream);
+    const hipError_t rc = hipMemcpyAsync(d_raw, t->d_raw_buf, (size_t)t->n_nets * n_rows * t->net.NO * sizeof(float), hipMemcpyDeviceToDevice, t->stream);
     if (rc != hipSuccess) return tfail(t, AZG_E_DEVICE, std::string("azg_trainer_read_d_raw: ") + hipGetErrorString(rc));
     return finish(t, "azg_trainer_read_d_raw");
 }

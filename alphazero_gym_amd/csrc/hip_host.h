@@ -38,6 +38,28 @@ struct DeviceAllocs {
     ~DeviceAllocs() { clear(); }
 };
 
+// One device buffer whose size depends on the call: a larger one replaces it (the owner's stream is idle between calls).  Freed with
+// the owner, whose device must be current then.
+struct DeviceBuffer {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipError_t last = hipSuccess;   // why the last reserve returned false
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    bool reserve(size_t n) {   // the new buffer first: a failure leaves the old one in place
+        if (p && bytes >= n) return true;
+        void* q = nullptr;
+        last = hipMalloc(&q, n);
+        if (last != hipSuccess) return false;
+        if (p) (void)hipFree(p);
+        p = q;
+        bytes = n;
+        return true;
+    }
+    ~DeviceBuffer() { if (p) (void)hipFree(p); }
+};
+
 // One block of pinned host memory (hipHostMalloc)
 struct PinnedBlock {   // (only ever a member of an object that cannot be copied)
     void* p = nullptr;

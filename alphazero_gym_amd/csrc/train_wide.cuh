@@ -28,22 +28,6 @@
 #define TW_UPDATE_SPAN 4096            // elements of one net that a workgroup of the update kernel steps
 #define TW_ROW_AHEAD 8                 // links of a lane's row chain whose loads the backward row pass issues ahead of their additions
 
-// The host's description of a wide trainer (TrainDims with 8 layers); a launch gets the slice it needs as one of the structs below.
-struct TrainDimsW {
-    int n_layers, in_dim, nd, NO, act;
-    int H[TW_MAX_LAYERS];
-    int offW[TW_MAX_LAYERS], offb[TW_MAX_LAYERS];
-    int offWv, offbv, offbd;
-    int P;
-    unsigned s_obs, s_A[TW_MAX_LAYERS], s_D[TW_MAX_LAYERS];
-    size_t per_net;
-    // LayerNorm trunks (TrainDimsLN's fields): the flag, ln.weight / ln.bias of the trunk layers, and per layer X_l [Bmax][H_l],
-    // G_l [Bmax][H_l] (d loss / d Y_l) and rstd_l [Bmax]; s_A then holds Y_l
-    int layernorm;
-    int offG[TW_MAX_LAYERS], offB[TW_MAX_LAYERS];
-    unsigned s_X[TW_MAX_LAYERS], s_G[TW_MAX_LAYERS], s_R[TW_MAX_LAYERS];
-};
-
 // the strip of wave `s`: row tile m0, first column n0, nt tiles of the `cols` columns (cols need not be a multiple of 16: dW_0)
 template <int NT>
 __device__ __forceinline__ void tw_strip_of(int s, int cols, int& m0, int& n0, int& nt) {

@@ -3,18 +3,16 @@
     hipcc <the Makefile's HIPFLAGS> -S --cuda-device-only -o parent.s alphazero_gym_amd/csrc/dispatch_train.hip     (in a checkout of the parent)
     hipcc <the Makefile's HIPFLAGS> -S --cuda-device-only -o change.s alphazero_gym_amd/csrc/dispatch_train.hip     (in this tree)
     python tools/train_asm_identity.py parent.s change.s
-A kernel's text runs from its label to its .Lfunc_end, the kernel descriptor (.amdhsa_ block: registers, LDS, kernarg size) included.
+(likewise dispatch_train_wide.hip).  Every kernel of either file -- every symbol with an .amdhsa_kernel block -- is compared with
+the kernel of the same mangled name in the other; a kernel that only one file has is a difference.  A kernel's text runs from its
+label to its .Lfunc_end, the kernel descriptor (.amdhsa_ block: registers, LDS, kernarg size) included.
 Before the comparison comments are dropped, basic-block labels are renumbered in order of appearance (their numbers count the
-functions of the file), the kernel's own mangled name is replaced by KERNEL (a template instantiation is named differently from a
-plain function) and the `.text` / `.section .text.<name>,...,comdat` line that follows a kernel is dropped (an instantiation lives
-in a comdat section).  Of a templated kernel the instantiation without LayerNorm (<false>) is taken.  Exit status 1 if any differs."""
+functions of the file) and the `.text` / `.section .text.<name>,...,comdat` line that follows a kernel is dropped (an instantiation
+lives in a comdat section).  With --renamed OLD=NEW (mangled names, repeatable) a kernel that was renamed is compared with its
+successor, the kernel's own name replaced by KERNEL on both sides.  Exit status 1 on any difference."""
 import difflib
 import re
 import sys
-
-KERNELS = ("train_forward_kernel", "train_backward_kernel", "train_backward_deferred_kernel", "train_loss_kernel", "train_gather_kernel",
-           "train_loss_sum_kernel")
-
 
 def functions(path):
     out, cur = {}, None
@@ -38,32 +36,46 @@ def body(lines, name):
         if not ln.strip() or ln.strip() == ".text" or ln.strip().startswith(".section"):
             continue
         ln = re.sub(r"\.LBB\d+_\d+", lambda m: labels.setdefault(m.group(0), "L%d" % len(labels)), ln)
-        res.append(ln.replace(name, "KERNEL"))
+        res.append(ln.replace(name, "KERNEL") if name else ln)
     return res
 
 
-def pick(funcs, base):
-    names = [k for k in funcs if re.match(r"_Z\d+" + base + r"(?![a-z_])", k) and "ILb1E" not in k]
-    return names[0] if names else None
+def kernels(path):
+    return [m.group(1) for m in (re.match(r"^\s*\.amdhsa_kernel\s+(\S+)", line) for line in open(path)) if m]
 
 
 def main():
-    a, b = functions(sys.argv[1]), functions(sys.argv[2])
+    args, renamed = [], {}
+    for arg in sys.argv[1:]:
+        if arg.startswith("--renamed="):
+            old, new = arg[len("--renamed="):].split("=")
+            renamed[old] = new
+        elif arg != "--renamed":
+            args.append(arg)
+    a, b = functions(args[0]), functions(args[1])
+    ka, kb = kernels(args[0]), kernels(args[1])
     bad = 0
-    for base in KERNELS:
-        ka, kb = pick(a, base), pick(b, base)
-        if ka is None or kb is None:
-            print(f"{base:32s} {'absent from the first file' if ka is None else 'absent from the second file'}")
+    for name in ka:
+        other = renamed.get(name, name)
+        if other not in kb:
+            bad += 1
+            print(f"{name}\n    absent from the second file: DIFFERENT")
             continue
-        na, nb = body(a[ka], ka), body(b[kb], kb)
+        # (the KERNEL substitution only where the names differ)
+        na, nb = body(a[name], name if other != name else None), body(b[other], other if other != name else None)
         insts = sum(1 for ln in na if ln.startswith("\t") and not ln.strip().startswith("."))
         same = na == nb
         bad += not same
-        print(f"{base:32s} lines {len(na):5d} / {len(nb):5d}  instructions {insts:5d}  {'identical' if same else 'DIFFERENT'}")
+        print(f"{name}\n    lines {len(na):5d} / {len(nb):5d}  instructions {insts:5d}  {'identical' if same else 'DIFFERENT'}")
         if not same:
             for i, ln in enumerate(difflib.unified_diff(na, nb, lineterm="", n=0)):
                 if i < 60:
                     print("    " + ln)
+    for name in kb:
+        if name not in ka and name not in renamed.values():
+            bad += 1
+            print(f"{name}\n    absent from the first file: DIFFERENT")
+    print(f"{len(ka)} / {len(kb)} kernels, {bad} different")
     return 1 if bad else 0
 
 
