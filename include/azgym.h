@@ -220,7 +220,9 @@ int azg_selfplay_begin(azg_engine* e, int32_t max_episode_length, int32_t determ
  *   discrete   pi = stable_normalizer(x, temperature) = |y / sum(y)|, y = (x / max(x))^temperature (helpers.py:9-27);
  *              action = pi.argmax() (deterministic) or sampled from pi by inverse CDF as numpy's choice() does
  *              (cdf = cumsum(pi) / cdf[-1], first index with u < cdf) with u from the engine's Philox stream.
- *              Counts: any temperature (c^t from a host-built libm table, (c / max)^t = c^t / max^t); Qs: temperature 1 only.
+ *              Counts: any temperature ((c / max)^t from a host-built libm table, n_sims <= 2048); Qs: temperature 1 only.
+ *              "max_value" with a largest root Q of exactly 0 makes every pi entry NaN (Q / max Q): the reference's
+ *              np.random.choice raises; the engine picks index 0 when deterministic and the last child when sampled.
  *   continuous actions[x.argmax()] (first index on ties), or with probability agent_epsilon a uniformly random root action
  *              (ContinuousAgent.epsilon_greedy, agents.py:471-490)
  *   ring_mode  AZG_RING_STOP: azg_selfplay_step fails once capacity_steps steps are stored (download and clear);

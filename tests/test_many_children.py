@@ -21,6 +21,7 @@ import pytest
 import oracle_lib as O
 import parity_util as P
 from alphazero_gym_amd import _capi
+from selfplay_ref import assert_stats_bits
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
 
@@ -278,8 +279,7 @@ def test_final_action_rules_differ_on_the_oracle():
 
 def _assert_played_the_same(got, want, what):
     np.testing.assert_array_equal(got[0].view(np.uint32), want[0].view(np.uint32), err_msg=f"{what}: rows")
-    for x, y, k in zip(got[1], want[1], ("fsum", "fcnt", "env state")):
-        np.testing.assert_array_equal(x, y, err_msg=f"{what}: {k}")
+    assert_stats_bits(got[1], want[1], what)
     assert got[2] == want[2], what
     assert got[4:] == want[4:], what
 

@@ -13,6 +13,7 @@ import torch
 
 import oracle_lib as O
 from alphazero_gym_amd import _capi
+from selfplay_ref import assert_stats_bits
 from test_population import CASES, K, _blob, _desc, _hip
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
@@ -58,9 +59,7 @@ def _compare_step(pop, singles, T, what):
         np.testing.assert_array_equal(ring[:, k].reshape(-1, r.shape[1]), r, err_msg=f"{what}: net {k} rows")
         sf, sc, ss = s.selfplay_stats()
         sl = slice(k * T, (k + 1) * T)
-        np.testing.assert_array_equal(fsum[sl], sf, err_msg=f"{what}: net {k} fsum")
-        np.testing.assert_array_equal(fcnt[sl], sc, err_msg=f"{what}: net {k} fcnt")
-        np.testing.assert_array_equal(state[sl], ss, err_msg=f"{what}: net {k} env state")
+        assert_stats_bits((fsum[sl], fcnt[sl], state[sl]), (sf, sc, ss), f"{what}: net {k}")
     return fcnt
 
 
@@ -169,8 +168,7 @@ def test_population_selfplay_begin_with_one_net_is_selfplay_begin_ex(name):
         b.selfplay_step()
     np.testing.assert_array_equal(a.selfplay_rows(clear=False), b.selfplay_rows(clear=False))
     assert a.selfplay_ring() == b.selfplay_ring()
-    for x, y in zip(a.selfplay_stats(), b.selfplay_stats()):
-        np.testing.assert_array_equal(x, y)
+    assert_stats_bits(a.selfplay_stats(), b.selfplay_stats(), name)
     _close(a, b)
 
 

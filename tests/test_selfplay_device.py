@@ -10,6 +10,7 @@ import pytest
 
 import oracle_lib as O
 from alphazero_gym_amd import _capi
+from selfplay_ref import assert_stats_bits
 
 CASES = {
     "pendulum": dict(kw=dict(env_id=2, mode=1, n_sims=30, c_uct=0.05, gamma=1.0, c_pw=1.0, kappa=0.5, seed=11, tree_id_base=5),
@@ -76,8 +77,7 @@ def test_selfplay_hip_matches_oracle_bit_for_bit(case):
     a_rows, a_stats = play(_native.HipEngine, case)
     b_rows, b_stats = play(O.OracleEngine, case)
     np.testing.assert_array_equal(a_rows.view(np.uint32), b_rows.view(np.uint32))
-    for x, y in zip(a_stats, b_stats):
-        np.testing.assert_array_equal(x, y)
+    assert_stats_bits(a_stats, b_stats, case)
 
 
 @pytest.mark.gpu
@@ -107,8 +107,7 @@ def test_selfplay_at_baseline_size_hip_matches_oracle(which):
     (a_rows, a_stats), (b_rows, b_stats) = out
     assert a_rows.shape[0] == steps * 4096
     np.testing.assert_array_equal(a_rows.view(np.uint32), b_rows.view(np.uint32))
-    for x, y in zip(a_stats, b_stats):
-        np.testing.assert_array_equal(x, y)
+    assert_stats_bits(a_stats, b_stats, which)
     if which == "cartpole_4096":
         assert a_stats[1].sum() > 0      # episodes did end (and restart) inside the window
 
@@ -243,8 +242,7 @@ def test_selfplay_variants_hip_matches_oracle_bit_for_bit(name):
         out.append((e.selfplay_rows(clear=False), e.selfplay_stats(), e.selfplay_ring()))
         e.close()
     np.testing.assert_array_equal(out[0][0].view(np.uint32), out[1][0].view(np.uint32))
-    for x, y in zip(out[0][1], out[1][1]):
-        np.testing.assert_array_equal(x, y)
+    assert_stats_bits(out[0][1], out[1][1], name)
     assert out[0][2] == out[1][2]
 
 
