@@ -596,7 +596,9 @@ __device__ __forceinline__ void tree_phase_b(const KParams& P, TreeState& st, co
         hp = hc;
         if (sub == (st.path_D & 15)) {   // the level's path slot: its depth, its record, its reward and W (used by backup_path)
             st.my_depth = st.path_D; st.pid = chosen;
-            // continuous mode (2-3 levels, a slow scored descent): fetched here, in the shadow of the level's LDS waits;
+            // continuous mode (2-4 levels under the configs' widening law, a slow scored descent; the depth is unbounded -- kappa = 0
+            // gives every node one child, a path of n_sims levels whose slots wrap every 16: tests/test_deep_paths.py holds that):
+            // fetched here, in the shadow of the level's LDS waits;
             // discrete mode (8-9 levels of pointer chasing): all levels at once after the loop (measured both ways)
             if (CONT && FETCH) { st.pr = EARLY_COLD ? cn.r : cold[chosen].r; st.pW = edge_W[chosen]; }
             if (!CONT && FETCH) { st.pr = r_step; st.pW = edge_W[chosen]; }   // (consumed by the backup; requested as the record enters the path)

@@ -327,6 +327,20 @@ T1_CASES = {
     "t1_mountaincar_epsgreedy_reuse": dict(env_id=3, mode=0, num_actions=3, n_sims=40, c_uct=2.0, gamma=1, epsilon=0.15,
                                            v_target="on_policy", hidden=[128, 128], act="elu", wseed=19, seed=22, wscale=3.0,
                                            reuse_steps=3, roots=[[-0.45, 0.01], [0.41, 0.04]]),
+    # MCTSContinuous deeper than 16 levels (mcts.py:260-267 backprop over a long path; tests/deep_paths.py).  Widening gives a node
+    # ceil(c_pw (n + 1)^kappa) children: kappa 0 -> one child per node, the tree is a chain of n_sims levels; c_pw 0.2 -> a branching tree
+    # about 30 levels deep.  gamma 0.99 puts the float32 first-level product and the float64 `gamma * R` above it on every level.
+    "t1_pendulum_v1_chain40": dict(env_id=2, mode=1, n_sims=40, c_uct=0.05, c_pw=1, kappa=0, gamma=0.99, epsilon=0.0,
+                                   v_target="off_policy", hidden=[64, 64], act="elu", wseed=81, seed=82,
+                                   roots=[[0.75, -0.5], [-2.9, 0.9], [3.0, 0.1]]),
+    "t1_pendulum_v1_narrow200": dict(env_id=2, mode=1, n_sims=200, c_uct=0.05, c_pw=0.2, kappa=0.5, gamma=1, epsilon=0.0,
+                                     v_target="off_policy", hidden=[64, 64], act="elu", wseed=83, seed=84, tree_id_base=20,
+                                     roots=[[0.75, -0.5], [-2.9, 0.9], [3.0, 0.1]]),
+    # ... and over an env whose episodes end: roots on the lower slope, 17 to 30 steps from the flag (deep_paths.lower_slope_roots,
+    # i = 2, 7, 9, 11, 4), so that terminal nodes sit deeper than 16 levels and most later traces end in them (V = 0, no new record)
+    "t1_mcc_chain80": dict(env_id=4, mode=1, n_sims=80, c_uct=0.05, c_pw=1, kappa=0, gamma=0.99, epsilon=0.0, v_target="off_policy",
+                           hidden=[64, 64], act="elu", wseed=88, seed=86, action_bound=1.0,
+                           roots=[[-0.35 + 0.5 * (i / 18.0), 0.035 + 0.03 * ((7.0 * i / 18.0) % 1.0)] for i in (2, 7, 9, 11, 4)]),
 }
 
 

@@ -14,6 +14,8 @@ T1_NAMES = [
     "t1_cartpole_epsgreedy", "t1_cartpole_explore", "t1_cartpole_reuse", "t1_mountaincar_default", "t1_mountaincar_epsgreedy_reuse",
     "t1_mcc_terminal", "t1_mcc_terminal_eps",   # MCTSContinuous with terminal nodes (MountainCarContinuous-v0; mcts.py:619-623, 682)
     "t1_acrobot_default", "t1_acrobot_epsgreedy_reuse",   # six observations, reward 0 on the terminal step (Acrobot-v1)
+    # MCTSContinuous deeper than 16 levels: a chain of 40 (kappa 0), a branching tree of ~30 levels (c_pw 0.2), terminal nodes below level 16
+    "t1_pendulum_v1_chain40", "t1_pendulum_v1_narrow200", "t1_mcc_chain80",
 ]
 
 DUMP_INT = ("n_records", "parent", "edge_n", "node_n", "node_flags")
