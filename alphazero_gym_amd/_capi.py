@@ -121,6 +121,7 @@ SYMBOLS = [
 # entry points a library may lack (the tests' CPU oracle binds SYMBOLS only): bound when present, else the methods that need
 # them raise
 OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device", "set_net_search",
+                    "set_net_search_ex",
                     "population_selfplay_begin", "policy_rollout", "policy_rollout_ex",
                     "population_mlp_eval", "population_mlp_eval_device", "population_root_eval",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
@@ -136,6 +137,7 @@ class AzgNetSearch(C.Structure):
                 ("c_pw", C.c_double), ("kappa", C.c_double)]
 
 
+NET_SEARCH_WIDE = 1   # AZG_NET_SEARCH_WIDE: the table may be searched by nets of padded width >= 512 (azg_set_net_search_ex)
 NET_SEARCH_KEYS = ("c_uct", "gamma", "epsilon", "c_pw", "kappa")   # the MCTS settings a population's nets may each have their own of
 
 
@@ -263,6 +265,8 @@ def bind(lib, prefix):
         f["set_population"].argtypes = [vp, C.c_int32]
     if "set_net_search" in f:
         f["set_net_search"].argtypes = [vp, C.POINTER(AzgNetSearch), C.c_int32]
+    if "set_net_search_ex" in f:
+        f["set_net_search_ex"].argtypes = [vp, C.POINTER(AzgNetSearch), C.c_int32, C.c_uint32]
     if "set_net_weights" in f:
         f["set_net_weights"].argtypes = [vp, C.c_int32, C.POINTER(AzgMlpDesc), C.POINTER(C.c_float), C.c_size_t]
     if "set_net_weights_device" in f:
@@ -508,10 +512,17 @@ class Engine:
         self._check(self._optional("set_population")(self._h, int(n_nets)))
         self.n_nets = int(n_nets)
 
-    def set_net_search(self, settings):
+    def set_net_search(self, settings, wide=False):
         """azg_set_net_search: net k searches with settings[k], a dict with all of c_uct, gamma, epsilon, c_pw, kappa (discrete mode
-        ignores the last two), instead of the engine's shared settings; None returns to those.  One entry per net of the population."""
-        fn = self._optional("set_net_search")
+        ignores the last two), instead of the engine's shared settings; None returns to those.  One entry per net of the population.
+        ``wide=True``: azg_set_net_search_ex with AZG_NET_SEARCH_WIDE -- the table may be searched by nets of padded width >= 512."""
+        if wide:
+            ex = self._optional("set_net_search_ex")
+
+            def fn(h, arr, n):
+                return ex(h, arr, n, NET_SEARCH_WIDE)
+        else:
+            fn = self._optional("set_net_search")
         if settings is None:
             self._check(fn(self._h, None, 0))
             return

@@ -29,12 +29,13 @@ class AgentPopulation:
 
     ``per_agent_search=True`` (opt-in): the agents may differ in ``mcts.c_uct`` / ``gamma`` / ``epsilon`` and (continuous) ``c_pw`` /
     ``kappa``; agent k's tree is searched with its own values, still in the one launch (PopulationMCTS ``net_settings``).  Everything
-    else must still agree."""
+    else must still agree.  ``wide_search=True`` with it: agents whose networks are 512 or wider (PopulationMCTS
+    ``net_settings_wide``)."""
 
     PER_AGENT = _capi.NET_SEARCH_KEYS
 
     def __init__(self, agents: Sequence[Any], seeds: Optional[Sequence[int]] = None, tree_id_base: int = 0,
-                 per_agent_search: bool = False):
+                 per_agent_search: bool = False, wide_search: bool = False):
         self.agents = list(agents)
         if not self.agents:
             raise ValueError("AgentPopulation needs at least one agent")
@@ -45,6 +46,9 @@ class AgentPopulation:
         else:
             raise ValueError("AgentPopulation: all agents must be DiscreteAgents or all ContinuousAgents")
         self.per_agent_search = bool(per_agent_search)
+        if wide_search and not self.per_agent_search:
+            raise ValueError("AgentPopulation: wide_search=True goes with per_agent_search=True (it lets wide networks search with per-agent settings)")
+        self.wide_search = bool(wide_search)
         keys = {self._settings(a) for a in self.agents}
         if len(keys) != 1:
             if not self.per_agent_search:
@@ -107,7 +111,8 @@ class AgentPopulation:
                                        mode=_capi.MODE_DISCRETE if self.discrete else _capi.MODE_CONTINUOUS, n_rollouts=m.n_rollouts,
                                        c_uct=m.c_uct, gamma=m.gamma, epsilon=m.epsilon, V_target_policy=m.V_target_policy, seed=m.seed,
                                        tree_id_base=self.tree_id_base, device_id=device_ordinal(m.device), **m._engine_kwargs(),
-                                       **({"net_settings": self._net_settings()} if self.per_agent_search else {}))
+                                       **({"net_settings": self._net_settings()} if self.per_agent_search else {}),
+                                       **({"net_settings_wide": True} if self.wide_search else {}))
             self._env_id = env_id
         return self._pop
 

@@ -59,9 +59,10 @@ template <int ENV>
 static hipError_t search_path(azg_engine* e, bool lockstep) {
     if (lockstep) {
         if constexpr (ENV == AZG_ENV_ACROBOT) return hipErrorInvalidValue;   // (six network inputs: never lock-step, use_lockstep)
-        else return azg_lockstep_search<ENV>(e);
+        else return e->net_search.rec ? azg_lockstep_search_nets<ENV>(e) : azg_lockstep_search<ENV>(e);
     }
-    if (e->net_search.rec) return e->HP <= 128 ? azg_persistent_search_nets<ENV, false>(e) : azg_persistent_search_nets<ENV, true>(e);
+    if (e->net_search.rec)
+        return e->HP <= 128 ? azg_persistent_search_nets<ENV, false>(e) : e->HP <= 256 ? azg_persistent_search_nets<ENV, true>(e) : azg_persistent_search_nets_wide<ENV>(e);
     return e->HP <= 128 ? azg_persistent_search<ENV, false>(e) : azg_persistent_search<ENV, true>(e);
 }
 static hipError_t search_launch(azg_engine* e, bool lockstep) {
@@ -336,11 +337,12 @@ int azg_search_resident(azg_engine* e) {
     if (!e->mlp_ready)
         return fail(e, AZG_E_STATE, e->n_nets > 1 ? "azg_set_net_weights has not been called for every net of the population"
                                                  : "azg_set_weights has not been called");
-    // per-net settings exist in search_kernel's form for widths up to 256 only: the team kernel, the per-layer launches and the wide
-    // networks' one-launch kernels all search with the engine's shared settings
-    if (e->net_search.rec && e->HP >= 512)
+    // a table set through azg_set_net_search is searched at widths up to 256 only; the team kernel, the per-layer launches and the wide
+    // networks' one-launch kernels take one that came with AZG_NET_SEARCH_WIDE
+    if (e->net_search.rec && e->HP >= 512 && !e->net_search_wide)
         return fail(e, AZG_E_UNSUPPORTED, "per-net search settings (azg_set_net_search) need a padded hidden width of at most 256: nets of width >= 512 "
-                                          "search with the engine's shared settings only (azg_set_net_search(e, NULL, 0) returns to them)");
+                                          "search with the engine's shared settings (azg_set_net_search(e, NULL, 0) returns to them), or with a table "
+                                          "set through azg_set_net_search_ex with AZG_NET_SEARCH_WIDE");
     ON_DEVICE(e);
     e->P.search_idx = e->search_idx;
     e->last_search_idx = e->search_idx;
@@ -561,8 +563,11 @@ static int kernel_name(const azg_engine* e, char* buf, size_t n) {
     const LaunchRecord& r = e->last;
     switch (r.form) {
         case AZG_FORM_PERSISTENT: return snprintf(buf, n, r.nets ? "search_kernel_nets<%d, %d, %d, %d, %s, %d, %d, %d, %d>" : "search_kernel<%d, %d, %d, %d, %s, %d, %d, %d, %d>", env, e->HP, e->nreg, r.tree_lds, gmm, r.waves, r.groups, r.tile_trees, r.spec);
-        case AZG_FORM_PER_LAYER: return snprintf(buf, n, "ls_tree_kernel<%d, ...> + ls_layer0_kernel + ls_hidden_tiled_kernel<%d, ...> per simulation step", env, e->HP);
-        case AZG_FORM_TEAM: return snprintf(buf, n, "ls_team_kernel<%d, %d, %s, %d, %d, %d, %d, %d%s>", env, e->HP, gmm, r.tree_lds, r.team_kc, r.team_minb, r.spec, r.team_tt,
+        case AZG_FORM_PER_LAYER: return snprintf(buf, n, "%s<%d, ...> + ls_layer0_kernel + ls_hidden_tiled_kernel<%d, ...> per simulation step",
+                                                 r.nets ? "ls_tree_kernel_nets" : "ls_tree_kernel", env, e->HP);
+        case AZG_FORM_TEAM:
+            if (r.nets) return snprintf(buf, n, "ls_team_kernel_nets<%d, %d, %s, %d, %d, %d>", env, e->HP, gmm, r.tree_lds, r.team_kc, r.team_minb);
+            return snprintf(buf, n, "ls_team_kernel<%d, %d, %s, %d, %d, %d, %d, %d%s>", env, e->HP, gmm, r.tree_lds, r.team_kc, r.team_minb, r.spec, r.team_tt,
                                             r.team_pop ? ", true" : "");   // (a population's instantiation: POP)
         default: return snprintf(buf, n, "(no search yet)");
     }

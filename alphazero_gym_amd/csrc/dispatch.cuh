@@ -128,6 +128,14 @@ static hipError_t launch(azg_engine* e) {
     return launch_t<NETS, ENV, HP, NREG, TS_GLOBAL, 4, 1>(e);
 }
 
+// hidden widths (padded) 512 and 1024: every layer's weights streamed from L2, trees in LDS with 8-bit ids or in global memory
+template <bool NETS, int ENV>
+static hipError_t wide_launch(azg_engine* e) {
+    if (e->HP == 512) return launch<NETS, ENV, 512, 0>(e);
+    if (e->HP == 1024) return launch<NETS, ENV, 1024, 0>(e);
+    return hipErrorInvalidValue;
+}
+
 // hidden widths (padded) 64 and 128, or (WIDE) 256 and up (one or two hidden->hidden layers are kept in registers; deeper trunks
 // stream their weights from L2: any depth)
 template <bool NETS, int ENV, bool WIDE>
@@ -138,11 +146,8 @@ static hipError_t persistent_search(azg_engine* e) {
         if (HP == 128) return NR == 1 ? launch<NETS, ENV, 128, 1>(e) : NR == 2 ? launch<NETS, ENV, 128, 2>(e) : launch<NETS, ENV, 128, 0>(e);
     } else {
         if (HP == 256) return NR == 1 ? launch<NETS, ENV, 256, 1>(e) : launch<NETS, ENV, 256, 0>(e);
-        // (per-net settings: widths up to 256 only -- azg_search_resident refuses wider engines that carry a table before it gets here)
-        if constexpr (!NETS) {
-            if (HP == 512) return launch<NETS, ENV, 512, 0>(e);
-            if (HP == 1024) return launch<NETS, ENV, 1024, 0>(e);
-        }
+        // (per-net settings at these widths: azg_persistent_search_nets_wide below, translation units of its own)
+        if constexpr (!NETS) return wide_launch<NETS, ENV>(e);
     }
     return hipErrorInvalidValue;
 }
@@ -151,3 +156,7 @@ hipError_t azg_persistent_search(azg_engine* e) { return persistent_search<false
 // the same choice of shape with search_kernel_nets (instantiated by the dispatch_nets_*.hip translation units)
 template <int ENV, bool WIDE>
 hipError_t azg_persistent_search_nets(azg_engine* e) { return persistent_search<true, ENV, WIDE>(e); }
+// ... and search_kernel_nets at widths 512 and 1024 (azg_set_net_search_ex with AZG_NET_SEARCH_WIDE): the shapes that are not lock-step
+// shaped, and anything under AZG_FORCE_PERSISTENT=1 (instantiated by the dispatch_nets_wide_*.hip translation units)
+template <int ENV>
+hipError_t azg_persistent_search_nets_wide(azg_engine* e) { return wide_launch<true, ENV>(e); }

@@ -1,0 +1,4 @@
+// persistent team kernel with per-net MCTS settings (ls_team_kernel_nets) for wide networks, the CartPole and Pendulum families
+#include "team_dispatch.cuh"
+template hipError_t azg_team_search_nets<AZG_ENV_CARTPOLE>(azg_engine*);
+template hipError_t azg_team_search_nets<AZG_ENV_PENDULUM_V1>(azg_engine*);

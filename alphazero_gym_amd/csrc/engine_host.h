@@ -47,7 +47,8 @@ struct LaunchRecord {
     int waves = 0, groups = 0, tile_trees = 0;   // search_kernel: waves / tree groups per workgroup, trees per group (16, or 8 / 4)
     int team_kc = 0, team_minb = 0, team_tt = 0, team_parts = 0;   // team kernel: chunk length, workgroups per CU, trees per team, launches
     int team_pop = 0;                         // ... and its population instantiation (team.cuh: POP)
-    int nets = 0;                             // search_kernel_nets: the launch took the per-net settings table (azg_set_net_search)
+    int nets = 0;                             // the launch took the per-net settings table (azg_set_net_search): search_kernel_nets,
+                                              // ls_team_kernel_nets, ls_tree_kernel_nets
     int timed = 0;                            // the launch recorded ev0 / ev1 itself (hipExtLaunchKernelGGL)
 };
 
@@ -137,8 +138,10 @@ struct azg_engine : EngineQueue {
     int redo_ok = 0;         // roots, carried counts and weights are still the ones the last search ran on: azg_dump_tree may re-run it
     int n_nets = 1;          // azg_set_population: the trees split into n_nets nets of n_trees / n_nets trees (1: one network)
     std::vector<char> net_have = std::vector<char>(1, 0);   // net k has weights (azg_set_net_weights); d_wblob holds n_nets blocks of w_floats
-    // azg_set_net_search: per-net MCTS settings.  net_search.rec != nullptr: the engine carries a table and searches with search_kernel_nets
+    // azg_set_net_search: per-net MCTS settings.  net_search.rec != nullptr: the engine carries a table and searches with the kernels that
+    // take it.  net_search_wide: the table came with AZG_NET_SEARCH_WIDE (azg_set_net_search_ex) and may be searched at widths >= 512
     DeviceAllocs net_search_mem; NetSearchTable net_search{};
+    int net_search_wide = 0;
     DeviceAllocs stamp_mem; size_t stamp_n = 0;   // rows of the diagnostic stamp buffer (P.stamps)
     uint32_t last_search_idx = 0;   // the search index the last search ran under (azg_dump_tree re-runs it with this one)
     float ms_kept = 0.0f; int ms_kept_valid = 0;   // kernel time of the last search, kept across azg_dump_tree's re-run of it
@@ -275,6 +278,11 @@ template <int ENV, bool WIDE> hipError_t azg_persistent_search(azg_engine* e);  
 template <int ENV, bool WIDE> hipError_t azg_persistent_search_nets(azg_engine* e);   // the same as search_kernel_nets (per-net settings, widths up to 256)
 template <int ENV> hipError_t azg_lockstep_search(azg_engine* e);   // wide networks: the team kernel, else per-layer launches (ls_dispatch.cuh)
 template <int ENV> hipError_t azg_team_search(azg_engine* e);       // (team_dispatch.cuh)
+// the three wide paths with the per-net settings table (azg_set_net_search_ex, AZG_NET_SEARCH_WIDE): search_kernel_nets at widths 512 and
+// 1024, ls_team_kernel_nets, ls_tree_kernel_nets
+template <int ENV> hipError_t azg_persistent_search_nets_wide(azg_engine* e);
+template <int ENV> hipError_t azg_lockstep_search_nets(azg_engine* e);
+template <int ENV> hipError_t azg_team_search_nets(azg_engine* e);
 // the team kernel's forms for more than two 32-tree workgroups per CU (config E's network; team_dispatch.cuh); dry: residency check only
 hipError_t azg_team_wide_forms(azg_engine* e, int g_base, int G, bool dry, bool common, bool t32, bool t64);
 // policy rollout in the team form (dispatch_rollout_team.hip): every team of the call as one or more launches on e->stream, counted into

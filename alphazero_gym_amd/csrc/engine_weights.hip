@@ -332,6 +332,7 @@ int azg_set_population(azg_engine* e, int32_t n_nets) {
     // ... and so do per-net search settings: their table has one entry per net of the old split
     e->net_search = NetSearchTable{};
     e->net_search_mem.clear();
+    e->net_search_wide = 0;
     e->n_nets = n_nets;
     e->net_have.assign(n_nets, 0);
     e->mlp_ready = 0; e->results_valid = 0; e->redo_ok = 0; e->searched = 0;
@@ -341,9 +342,9 @@ int azg_set_population(azg_engine* e, int32_t n_nets) {
 
 // Per-net MCTS settings: validated on the host, then one record and one widening table per net on the device (records.h:
 // NetSearchTable).  The buffers are allocated when the table appears and reused while it stays; the copies go on the engine's stream,
-// behind whatever search is running there.
-int azg_set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_nets) {
-    if (!e) return AZG_E_INVALID;
+// behind whatever search is running there.  wide: the table may be searched at padded widths >= 512 (AZG_NET_SEARCH_WIDE); a call that
+// fails leaves the table and its permission as they were.
+static int set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_nets, bool wide) {
     const bool clear = !nets || n_nets == 0;
     const bool cont = e->cfg.mode == AZG_MODE_CONTINUOUS;
     const int ns = e->cfg.n_sims;
@@ -385,6 +386,7 @@ int azg_set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_nets
         HIPCHK(e, hipStreamSynchronize(e->stream));   // a running search still reads the table
         e->net_search = NetSearchTable{};
         e->net_search_mem.clear();
+        e->net_search_wide = 0;
         return AZG_OK;
     }
     if (!e->net_search.rec) {
@@ -398,7 +400,19 @@ int azg_set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_nets
     HIPCHK(e, hipMemcpyAsync((void*)e->net_search.rec, rec.data(), rec.size() * sizeof(NetSearchRec), hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipMemcpyAsync((void*)e->net_search.pw_need, pw_all.data(), pw_all.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));   // (the staging vectors go when this returns)
+    e->net_search_wide = wide ? 1 : 0;
     return AZG_OK;
+}
+
+int azg_set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_nets) {
+    if (!e) return AZG_E_INVALID;
+    return set_net_search(e, nets, n_nets, false);
+}
+
+int azg_set_net_search_ex(azg_engine* e, const azg_net_search* nets, int32_t n_nets, uint32_t flags) {
+    if (!e) return AZG_E_INVALID;
+    if (flags & ~(uint32_t)AZG_NET_SEARCH_WIDE) return fail(e, AZG_E_INVALID, "azg_set_net_search_ex: unknown flag bits (AZG_NET_SEARCH_WIDE is the only flag)");
+    return set_net_search(e, nets, n_nets, (flags & AZG_NET_SEARCH_WIDE) != 0);
 }
 
 int azg_set_net_weights(azg_engine* e, int32_t net, const azg_mlp_desc* d, const float* blob, size_t n_floats) {

@@ -35,61 +35,32 @@ __device__ __forceinline__ size_t ls_net_wofs(const KParams& P, int tg) {
 // kernel; the first layer in this kernel's tail, +3.6 % time; the batch cut into pipelines on several streams, +6 % / +40 %.)
 template <int ENV, bool GMM, int NCH, int HP, bool POP = false>
 __global__ __launch_bounds__(256) void ls_tree_kernel(KParams P, LockStep L, int sim, int g_base) {
-    constexpr bool CONT = EnvFamily<ENV>::CONT;
-    extern __shared__ double s_dyn[];   // sqrt_tab [tab_n], pw_need [n_sims+2]
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, sub = lane & 15;
-    const int tl = wave * 4 + (lane >> 4);
-    const int tg = g_base + blockIdx.x;
-    const int tree = tg * TREES_PER_WG + tl;
-    const bool live = tree < P.B;
-    const unsigned gtree = (unsigned)(P.tree_base + tree);
-    double* s_sqrt = s_dyn;
-    int* s_pw = (int*)(s_dyn + P.tab_n);
-    for (int i = tid; i < P.tab_n; i += 256) s_sqrt[i] = P.sqrt_tab[i];
-    if (CONT) for (int i = tid; i < P.n_sims + 2; i += 256) s_pw[i] = P.pw_need[i];
-    __syncthreads();
-    const size_t tb = (size_t)(live ? tree : 0) * P.R;
-    Cold* cold = P.cold + tb;
-    double* edge_W = P.edge_W + tb;
-    float* action = P.action + tb;
-    TreeStore<TS_GLOBAL> ts;
-    ts.hot = P.hot + tb;
-    ts.child = P.child + tb * P.Kp;
-    ts.prior = P.prior + tb;
-    float* obsT = L.obsT + (size_t)tg * 64;
-    TreeState st;
-    if (sim == -2) {
-        tree_init_root<ENV, TS_GLOBAL>(P, st, ts, cold, edge_W, action, tree, live, sub, tl, gtree, obsT);
-    } else {
-        const LsTree t = L.tree[live ? tree : 0];
-#ifdef AZG_STAMPS
-        unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // diagnostic build: discarded here
-#endif
-        const LsLane ln = L.lane[(size_t)(live ? tree : 0) * 16 + sub];
-        st.nrec = t.nrec; st.eps_draws = t.eps_draws; st.leaf = t.leaf; st.need_eval = live && t.need_eval; st.path_D = t.path_D;
-        st.kbase = t.kbase; st.my_depth = ln.my_depth; st.pid = ln.pid; st.pr = ln.pr; st.pW = ln.pW; st.eps_c = ln.eps_c;
-        if (live) tree_phase_a<ENV, TS_GLOBAL, GMM, NCH>(P, st, ts, cold, edge_W, action, tb, sim, sub, tl, gtree,
-                                                     L.parts + (size_t)tg * NCH * 64, P.bhead + ls_net_wofs<POP>(P, tg), s_sqrt STAMP_ARG, s_pw);
-        st.need_eval = false;
-        if (sim < P.n_sims - 1) {
-            __threadfence_block();
-            if (live) tree_phase_b<ENV, TS_GLOBAL, GMM>(P, st, ts, cold, edge_W, action, tb, sub, tl, gtree, s_sqrt, s_pw, obsT STAMP_ARG);
-            else if (sub < 4) obsT[sub * 16 + tl] = 0.0f;
-        } else if (live && sub == 0) {
-            P.n_rec[tree] = st.nrec;
-        }
-    }
-    if (live) {
-        if (sub == 0) {
-            LsTree t;
-            t.nrec = st.nrec; t.eps_draws = st.eps_draws; t.leaf = st.leaf; t.need_eval = st.need_eval ? 1 : 0; t.path_D = st.path_D;
-            t.kbase = st.kbase;
-            L.tree[tree] = t;
-        }
-        LsLane ln;
-        ln.my_depth = st.my_depth; ln.pid = st.pid; ln.pr = st.pr; ln.pW = st.pW; ln.eps_c = st.eps_c; ln.pad = 0.0f;
-        L.lane[(size_t)tree * 16 + sub] = ln;
-    }
+    const KParams& PT = P;   // (the tree phases read the launch's shared settings: see ls_tree_kernel_nets)
+#include "ls_tree_kernel_body.inc"
+}
+
+// Per-net MCTS settings at these widths (azg_set_net_search_ex with AZG_NET_SEARCH_WIDE).  A 16-tree group, a tile pair and a team belong
+// to one net -- ls_net_wofs's -- so the workgroup reads that net's record once at kernel entry (wave-uniform loads: the index comes from
+// the workgroup id) into a copy of the parameter block whose c_uct, gamma, epsilon, pw0 and widening table are the net's; the tree phases
+// run on the copy, and s_pw is filled from the net's table.  Everything that touches the network keeps reading the kernel argument: the
+// tile routines index its per-layer pointer arrays at run time, which would pin a copy in scratch memory (search_kernel.cuh).
+__device__ __forceinline__ KParams ls_net_params(const KParams& P, const NetSearchTable& nets, int tg) {
+    const int t = tg * TREES_PER_WG;
+    const int k = (t < P.B ? t : P.B - 1) / P.net_T;   // (< the table's n_nets; the padding groups take the last net's)
+    const NetSearchRec& r = nets.rec[k];
+    KParams Q = P;
+    Q.c_uct = r.c_uct; Q.gamma = r.gamma; Q.epsilon = r.epsilon;
+    Q.c_uct_f = r.c_uct_f; Q.gamma_f = r.gamma_f; Q.pw0 = r.pw0;
+    Q.pw_need = nets.pw_need + (size_t)k * (P.n_sims + 2);
+    return Q;
+}
+
+// ls_tree_kernel's population form with the table: the launches of a search all read the same record for a given tree group.
+template <int ENV, bool GMM, int NCH, int HP>
+__global__ __launch_bounds__(256) void ls_tree_kernel_nets(KParams P, LockStep L, int sim, int g_base, NetSearchTable nets) {
+    constexpr bool POP = true;
+    const KParams PT = ls_net_params(P, nets, g_base + (int)blockIdx.x);
+#include "ls_tree_kernel_body.inc"
 }
 
 template <int HP, bool POP = false>

@@ -18,9 +18,11 @@
 
 // One variant: hipErrorNotReady when its workgroups cannot all be resident at once (or the shape is not its).
 // wider_form_exists: a form built for more workgroups per CU follows for this shape, so this one takes batches of up to MINB per CU only;
-// otherwise it takes whatever the occupancy query allows (up to 6).  dry: check only, launch nothing.  POP: the population form.
-template <int ENV, int HP, bool GMM, int TLDS, int KC, int MINB, int SPEC = 0, int TT = 32, bool POP = false>
+// otherwise it takes whatever the occupancy query allows (up to 6).  dry: check only, launch nothing.  POP: the population form;
+// NSET: ls_team_kernel_nets, the population form that takes the engine's table of per-net MCTS settings.
+template <int ENV, int HP, bool GMM, int TLDS, int KC, int MINB, int SPEC = 0, int TT = 32, bool POP = false, bool NSET = false>
 static hipError_t team_launch_form(azg_engine* e, bool wider_form_exists, int g_base, int G, bool dry = false) {
+    static_assert(!NSET || (POP && SPEC == 0 && TT == 32), "per-net settings run the base population form");
     constexpr int NU = HP / 64, TPW = TT / NU, TGN = TT / 16;
     constexpr bool CONT = EnvFamily<ENV>::CONT;
     if (e->n_hidden - 1 >= TEAM_CNT_XB) return hipErrorNotReady;   // (one counter per hidden layer)
@@ -28,7 +30,11 @@ static hipError_t team_launch_form(azg_engine* e, bool wider_form_exists, int g_
     const bool lds_cold = TEAM_LDS_COLD && HP == 1024 && TT == 32 && MINB == 2 && TLDS == TS_LDS8;
     const size_t lds = team_tree_off(e->tab_n, e->cfg.n_sims, KC, TGN) + (size_t)TPW * (team_tree_bytes(e->R, CONT, TLDS) + (lds_cold ? team_cold_bytes(e->R) : 0));
     if ((lds + 1024) * MINB > 160 * 1024) return hipErrorNotReady;
-    auto kern = ls_team_kernel<ENV, HP, GMM, TLDS, KC, MINB, SPEC, TT, POP>;
+    const auto kern_of = [] {
+        if constexpr (NSET) return ls_team_kernel_nets<ENV, HP, GMM, TLDS, KC, MINB>;
+        else return ls_team_kernel<ENV, HP, GMM, TLDS, KC, MINB, SPEC, TT, POP>;
+    };
+    auto kern = kern_of();
     static KernelAttrs attrs;
     int per_cu = 0;
     hipError_t rc = attrs.occupancy(e, (const void*)kern, 256, lds, &per_cu);
@@ -46,11 +52,12 @@ static hipError_t team_launch_form(azg_engine* e, bool wider_form_exists, int g_
     T.cnt = e->d_team_cnt;
     T.abort = e->d_team_cnt + (e->team_cnt_bytes / 4 - 1);   // the last word
     T.spin_limit = (unsigned)e->opt.team_spin_limit;
-    hipLaunchKernelGGL(kern, dim3(TQ * NU), dim3(256), lds, e->stream, e->P, e->ls, T, TQ, g_base);
+    if constexpr (NSET) hipLaunchKernelGGL(kern, dim3(TQ * NU), dim3(256), lds, e->stream, e->P, e->ls, T, TQ, g_base, e->net_search);
+    else hipLaunchKernelGGL(kern, dim3(TQ * NU), dim3(256), lds, e->stream, e->P, e->ls, T, TQ, g_base);
     e->team_pending = 1;
     LaunchRecord& r = e->last;
     r.form = AZG_FORM_TEAM; r.tree_lds = TLDS; r.spec = SPEC;
-    r.team_kc = KC; r.team_minb = MINB; r.team_tt = TT; r.team_pop = POP ? 1 : 0;
+    r.team_kc = KC; r.team_minb = MINB; r.team_tt = TT; r.team_pop = POP ? 1 : 0; r.nets = NSET;
     return hipGetLastError();
 }
 
@@ -65,15 +72,18 @@ static hipError_t team_launch_form(azg_engine* e, bool wider_form_exists, int g_
 // A population (azg_set_population; 32 trees per net or a multiple, so that a team serves one net) takes the base form only, in its
 // population instantiation: 32-tree teams, two per CU, the general tree phases, trees in LDS with 8-bit ids or in global memory (trees
 // of 256 .. 511 records: global).  No three-per-CU forms, no 64-tree teams -- they could straddle two nets --, no two-part launches: a
-// batch the base form cannot hold resident is the per-layer launches'.
-template <int ENV, int HP, bool GMM, int TLDS>
+// batch the base form cannot hold resident is the per-layer launches'.  An engine with per-net MCTS settings (NSET) is searched the same
+// way, with that form's table variant, whatever its number of nets (one net: net_T = B).
+template <int ENV, int HP, bool GMM, int TLDS, bool NSET>
 static hipError_t team_launch_part(azg_engine* e, int g_base, int G, bool dry = false) {
     constexpr bool WIDE = HP == 1024 && !GMM && TLDS == TS_LDS8 && ENV == AZG_ENV_PENDULUM_V1;
-    if (e->n_nets > 1) {
+    if constexpr (NSET) {
+        if constexpr (TLDS == TS_LDS9) return hipErrorNotReady;
+        else return team_launch_form<ENV, HP, GMM, TLDS, TEAM_KC32, 2, 0, 32, true, true>(e, false, g_base, G, dry);
+    } else if (e->n_nets > 1) {
         if constexpr (TLDS == TS_LDS9) return hipErrorNotReady;
         else return team_launch_form<ENV, HP, GMM, TLDS, TEAM_KC32, 2, 0, 32, true>(e, false, g_base, G, dry);
-    }
-    if constexpr (!WIDE) return team_launch_form<ENV, HP, GMM, TLDS, TEAM_KC32, 2>(e, false, g_base, G, dry);
+    } else if constexpr (!WIDE) return team_launch_form<ENV, HP, GMM, TLDS, TEAM_KC32, 2>(e, false, g_base, G, dry);
     else {
         // (the BASELINE shape's tree phases compiled for the common parameter set -- dispatch.cuh: SPEC --; AZG_NO_SPEC=1: the general kernel)
         const bool common = e->cfg.epsilon == 0.0 && e->cfg.tie_break == AZG_TIE_FIRST && e->cfg.env_id == AZG_ENV_PENDULUM_V1 && !e->opt.no_spec;
@@ -107,41 +117,46 @@ hipError_t azg_team_wide_forms(azg_engine* e, int g_base, int G, bool dry, bool 
 // stream (trees are independent; a launch's workgroups all have to be resident at once): 4096 trees 46.5 ms against 48.7 ms for the
 // per-layer launches.  Those get better with the batch (8192 trees: 92.7 ms = 0.71 of the fp32 MFMA peak; three team launches: 99.2 ms):
 // batches of more than two parts are theirs.
-template <int ENV, int HP, bool GMM, int TLDS>
+template <int ENV, int HP, bool GMM, int TLDS, bool NSET>
 static hipError_t team_launch(azg_engine* e) {
     constexpr bool WIDE = HP == 1024 && !GMM && TLDS == TS_LDS8 && ENV == AZG_ENV_PENDULUM_V1;
     const int G = (e->cfg.n_trees + TREES_PER_WG - 1) / TREES_PER_WG;
     const int G_MAX = 3 * e->n_cus / (HP / 64) * 4;                      // 64-tree teams, three workgroups on every CU
     e->last.team_parts = 1;
-    if (!WIDE || G <= G_MAX || !e->opt.team_wide || e->opt.team_tt == 32 || e->n_nets > 1) return team_launch_part<ENV, HP, GMM, TLDS>(e, 0, G);
+    if (!WIDE || G <= G_MAX || !e->opt.team_wide || e->opt.team_tt == 32 || e->n_nets > 1 || NSET) return team_launch_part<ENV, HP, GMM, TLDS, NSET>(e, 0, G);
     const int parts = (G + G_MAX - 1) / G_MAX, per = ((G + parts - 1) / parts + 3) / 4 * 4;   // (whole 64-tree teams)
     if (parts > 2) return hipErrorNotReady;
     // both parts' residency (occupancy, LDS) is checked before the first one is launched: a second part that does not fit
     // would otherwise send the whole search to another form behind an orphaned first launch
     hipError_t rc = hipSuccess;
-    for (int g = 0; g < G && rc == hipSuccess; g += per) rc = team_launch_part<ENV, HP, GMM, TLDS>(e, g, G - g < per ? G - g : per, true);
+    for (int g = 0; g < G && rc == hipSuccess; g += per) rc = team_launch_part<ENV, HP, GMM, TLDS, NSET>(e, g, G - g < per ? G - g : per, true);
     if (rc != hipSuccess) return rc;
-    for (int g = 0; g < G && rc == hipSuccess; g += per) rc = team_launch_part<ENV, HP, GMM, TLDS>(e, g, G - g < per ? G - g : per);
+    for (int g = 0; g < G && rc == hipSuccess; g += per) rc = team_launch_part<ENV, HP, GMM, TLDS, NSET>(e, g, G - g < per ? G - g : per);
     e->last.team_parts = parts;
     return rc;
 }
 
 // trees in the workgroups' LDS when they fit (azg_tree_storage: the team kernel has 9-bit-id variants for every head), else in global memory
-template <int ENV, int HP, bool GMM>
+template <int ENV, int HP, bool GMM, bool NSET>
 static hipError_t team_storage(azg_engine* e) {
     const int ts = azg_tree_storage(e, true).ts;
     hipError_t rc = hipErrorNotReady;
-    if (ts == TS_LDS8) rc = team_launch<ENV, HP, GMM, TS_LDS8>(e);
-    if (ts == TS_LDS9) rc = team_launch<ENV, HP, GMM, TS_LDS9>(e);
-    if (rc == hipErrorNotReady) rc = team_launch<ENV, HP, GMM, TS_GLOBAL>(e);
+    if (ts == TS_LDS8) rc = team_launch<ENV, HP, GMM, TS_LDS8, NSET>(e);
+    if (ts == TS_LDS9) rc = team_launch<ENV, HP, GMM, TS_LDS9, NSET>(e);
+    if (rc == hipErrorNotReady) rc = team_launch<ENV, HP, GMM, TS_GLOBAL, NSET>(e);
     return rc;
 }
 
-template <int ENV>
-hipError_t azg_team_search(azg_engine* e) {
+template <int ENV, bool NSET>
+static hipError_t team_search(azg_engine* e) {
     constexpr bool CONT = EnvFamily<ENV>::CONT;   // (mixture heads: the continuous family only)
     const bool gmm = CONT && e->P.ncomp >= 2;
-    if (e->HP == 512) return gmm ? team_storage<ENV, 512, CONT>(e) : team_storage<ENV, 512, false>(e);
-    if (e->HP == 1024) return gmm ? team_storage<ENV, 1024, CONT>(e) : team_storage<ENV, 1024, false>(e);
+    if (e->HP == 512) return gmm ? team_storage<ENV, 512, CONT, NSET>(e) : team_storage<ENV, 512, false, NSET>(e);
+    if (e->HP == 1024) return gmm ? team_storage<ENV, 1024, CONT, NSET>(e) : team_storage<ENV, 1024, false, NSET>(e);
     return hipErrorNotReady;
 }
+template <int ENV>
+hipError_t azg_team_search(azg_engine* e) { return team_search<ENV, false>(e); }
+// the same with the engine's table of per-net MCTS settings (instantiated by the dispatch_nets_*.hip translation units)
+template <int ENV>
+hipError_t azg_team_search_nets(azg_engine* e) { return team_search<ENV, true>(e); }

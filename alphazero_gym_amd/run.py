@@ -294,7 +294,8 @@ class PopulationSelfPlay:
     train on.  ``policies[k]`` plays games k*T .. k*T+T-1 (T = ``games_per_net``) with global ids ``tree_id_base + k*T + j``, the
     games ``DeviceSelfPlay(policies[k], n_games=T, rank=k)`` plays, bit for bit, with one search launch and one self-play launch
     per step for the whole population.  The game, search and self-play settings are shared by every net, except that
-    ``net_settings`` (``PopulationMCTS``: a list of K dicts) gives net k its own c_uct / gamma / epsilon / c_pw / kappa.  The agents' final
+    ``net_settings`` (``PopulationMCTS``: a list of K dicts) gives net k its own c_uct / gamma / epsilon / c_pw / kappa;
+    ``net_settings_wide=True`` lets nets of padded hidden width >= 512 search with them.  The agents' final
     action rules run on the device too: ``final_selection`` "max_visit" / "max_value", discrete ``temperature`` and
     ``deterministic``, continuous ``agent_epsilon`` (agents.py:294-301, 524-535; include/azgym.h).  ``fifo=True`` turns the
     replay ring into the reference's overwrite-the-oldest buffer (buffers.py:75-82).  Weights are re-uploaded only when some
@@ -304,13 +305,15 @@ class PopulationSelfPlay:
                  c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
                  deterministic: bool = False, capacity_steps: int = 64, seed: int = 34, tree_id_base: int = 0, device_id: int = 0,
                  final_selection: str = "max_visit", temperature: float = 1.0, agent_epsilon: float = 0.0, fifo: bool = False,
-                 net_settings: Optional[List[dict]] = None):
+                 net_settings: Optional[List[dict]] = None, net_settings_wide: Optional[bool] = None):
         policies = list(policies)
         if not policies or games_per_net < 1:
             raise ValueError(f"{type(self).__name__} needs at least one policy and games_per_net >= 1")
         kw = _game_engine_kwargs(game, policies[0], c_pw, kappa)
         if net_settings is not None:   # (opt-in: net k searches with its own c_uct / gamma / epsilon / c_pw / kappa, PopulationMCTS)
             kw["net_settings"] = net_settings
+        if net_settings_wide is not None:   # (opt-in: the table may be searched by nets of width >= 512)
+            kw["net_settings_wide"] = net_settings_wide
         self.continuous = kw["mode"] == _capi.MODE_CONTINUOUS
         self.mcts = self._search(policies, games_per_net, n_rollouts=n_rollouts, c_uct=c_uct, gamma=gamma, epsilon=epsilon,
                                  V_target_policy=V_target_policy, seed=seed, tree_id_base=tree_id_base, device_id=device_id, **kw)

@@ -87,12 +87,13 @@ class PopulationMCTS:
     ``kappa`` -- model k searches with its own values, a missing key takes the shared kwarg -- still in one launch, bit for bit what a
     one-model engine with those kwargs computes (azg_set_net_search).  The engine is created with the (c_pw, kappa) pair that widens
     furthest, so that every model's trees fit; ``set_net_settings`` changes the settings between searches.  Networks of padded hidden
-    width >= 512 search with shared settings only: ValueError."""
+    width >= 512 need ``net_settings_wide=True`` (azg_set_net_search_ex with AZG_NET_SEARCH_WIDE: the team, per-layer and wide
+    one-launch kernels' table forms); without it they search with shared settings only: ValueError."""
 
     def __init__(self, models: Sequence[Any], *, trees_per_model: int = 1, env_id: int, mode: int, n_rollouts: int, c_uct: float,
                  gamma: float, epsilon: float = 0.0, num_actions: int = 0, c_pw: float = 1.0, kappa: float = 0.5,
                  V_target_policy: str = "off_policy", action_bound: float = 2.0, seed: int = 34, tree_id_base: int = 0,
-                 device_id: int = 0, net_settings: Optional[Sequence[dict]] = None):
+                 device_id: int = 0, net_settings: Optional[Sequence[dict]] = None, net_settings_wide: bool = False):
         from .. import _native   # raises if libazgym_hip.so is missing
 
         self.models = list(models)
@@ -102,11 +103,12 @@ class PopulationMCTS:
         self.n_rollouts = int(n_rollouts)
         self._shared = dict(c_uct=c_uct, gamma=gamma, epsilon=epsilon, c_pw=c_pw, kappa=kappa)
         self.net_settings: Optional[List[dict]] = None
+        self.net_settings_wide = bool(net_settings_wide)
+        self.trees_per_model = int(trees_per_model)
         if net_settings is not None:
-            entries = self._net_entries(net_settings)
+            entries = self._net_entries(net_settings, self.net_settings_wide)
             if mode == _capi.MODE_CONTINUOUS:
                 c_pw, kappa = _capi.widest_pw(entries, self.n_rollouts)
-        self.trees_per_model = int(trees_per_model)
         self.n_trees = self.n_models * self.trees_per_model
         self.engine = _native.HipEngine(env_id=env_id, mode=mode, n_trees=self.n_trees, n_sims=n_rollouts, c_uct=c_uct, gamma=gamma,
                                         epsilon=epsilon, num_actions=num_actions, c_pw=c_pw, kappa=kappa, v_target=V_target_policy,
@@ -117,30 +119,43 @@ class PopulationMCTS:
         self._cliff_warned = False
         self.last_weight_sync: Optional[str] = None
         if net_settings is not None:
-            self.engine.set_net_search(entries)
-            self.net_settings = entries
+            self._push_net_settings(entries, self.net_settings_wide)
         self.sync_weights()
 
-    def _net_entries(self, net_settings) -> List[dict]:
-        """``net_settings`` completed with the shared kwargs and checked: one entry per model, known keys, widths up to 256."""
+    def _net_entries(self, net_settings, wide: bool) -> List[dict]:
+        """``net_settings`` completed with the shared kwargs and checked: one entry per model, known keys; widths up to 256, or
+        (``wide``) any width, with whole 32-tree teams per model where the models are searched as teams."""
         entries = _capi.net_search_entries(net_settings, self.n_models, self._shared)
         for m in self.models:
+            if wide:
+                norm = any(type(mod).__name__ == "LayerNorm" for mod in m.trunk)
+                if self.n_models > 1 and self.trees_per_model % 32 and _capi.lockstep_shaped(m.state_dim, list(m.hidden_dimensions), norm):
+                    raise ValueError(f"net_settings: models of this shape are searched as teams of 32 trees, so trees_per_model must be a multiple "
+                                     f"of 32 (got {self.trees_per_model}) for every team to serve one model")
+                continue
             width = max(m.hidden_dimensions)
             if (width + 63) // 64 * 64 >= 512:
                 raise ValueError(f"net_settings: per-model search settings need a hidden width of at most 256 (padded to a multiple of 64); "
-                                 f"this model's is {width}. Wider networks search with shared settings only")
+                                 f"this model's is {width}. Wider networks search with shared settings only, or with net_settings_wide=True")
         return entries
 
-    def set_net_settings(self, net_settings: Optional[Sequence[dict]]) -> None:
+    def _push_net_settings(self, entries: List[dict], wide: bool) -> None:
+        if wide:
+            self.engine.set_net_search(entries, wide=True)
+        else:
+            self.engine.set_net_search(entries)
+        self.net_settings, self.net_settings_wide = entries, wide
+
+    def set_net_settings(self, net_settings: Optional[Sequence[dict]], wide: Optional[bool] = None) -> None:
         """Change the per-model search settings between searches (same rules as the constructor's ``net_settings``); None returns to
-        the shared settings.  Every model's widening must fit the engine as it was created (azg_max_children): EngineError otherwise."""
+        the shared settings.  ``wide``: as the constructor's ``net_settings_wide`` (None: what the constructor was given).  Every
+        model's widening must fit the engine as it was created (azg_max_children): EngineError otherwise."""
         if net_settings is None:
             self.engine.set_net_search(None)
             self.net_settings = None
             return
-        entries = self._net_entries(net_settings)
-        self.engine.set_net_search(entries)
-        self.net_settings = entries
+        wide = self.net_settings_wide if wide is None else bool(wide)
+        self._push_net_settings(self._net_entries(net_settings, wide), wide)
 
     def sync_weights(self, force: bool = False) -> None:
         """Upload the weights of every model that changed since its last upload (net k = models[k]; after every optimiser step).

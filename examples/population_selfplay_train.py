@@ -10,7 +10,8 @@ in PyTorch between them); --trainer device-fused computes the losses on the devi
 (PopulationTrainer.train_epoch_ring: no copy of the rows, one synchronisation per iteration instead of one per minibatch).
 --optimizer adam and --grad-clip X give every net the reference's Adam settings and gradient clipping, on every trainer.
 --c-ucts / --gammas / --search-epsilons (and, continuous games, --c-pws / --kappas) sweep the SEARCH's settings over the seeds as --lrs
-sweeps the learning rate: one value per seed, every net still searched in the one launch (PopulationSelfPlay net_settings; hidden widths up to 256).
+sweeps the learning rate: one value per seed, every net still searched in the one launch (PopulationSelfPlay net_settings; hidden widths up
+to 256, and with --wide every width: net_settings_wide=True).
 --layernorm builds every net with LayerNorm after each trunk activation; the device trainers are then built with layernorm=True.
 --wide builds the device trainers with wide=True, which trains nets of up to 8 hidden layers and widths up to 1024 (--hidden 1024
 1024 1024 1024).  The search engine holds several such nets too: nets it searches as teams of 32 trees (padded width >= 512, two or
@@ -112,6 +113,15 @@ def net_settings(a):
     return [{key: vals[k] for key, vals in given.items()} for k in range(len(a.seeds))]
 
 
+def search_kwargs(a):
+    """PopulationSelfPlay's keywords for the sweeps given: ``net_settings``, and with --wide the opt-in that lets nets of width >= 512
+    search with them (``net_settings_wide=True``).  No sweep: the shared settings, no keyword."""
+    settings = net_settings(a)
+    if settings is None:
+        return {}
+    return dict(net_settings=settings, net_settings_wide=True) if a.wide else dict(net_settings=settings)
+
+
 def check_population_shape(a):
     """Why the search engine would refuse this population (None: it takes it): several nets that it searches as teams of 32 trees
     need a multiple of 32 games each (_capi.lockstep_shaped).  Asked before anything is built."""
@@ -136,8 +146,8 @@ def build_population(a):
     sp = run.PopulationSelfPlay([ag.nn for ag in agents], game=a.game, games_per_net=a.games_per_seed, n_rollouts=a.n_rollouts,
                                 c_uct=m.c_uct, gamma=m.gamma, epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0),
                                 kappa=getattr(m, "kappa", 0.5), max_episode_length=a.max_episode_length,
-                                capacity_steps=a.steps_per_iter, seed=a.engine_seed, net_settings=net_settings(a),
-                                device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0)
+                                capacity_steps=a.steps_per_iter, seed=a.engine_seed,
+                                device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0, **search_kwargs(a))
     return agents, state_dim, sp
 
 

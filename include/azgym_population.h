@@ -56,8 +56,12 @@ int azg_population_selfplay_begin(azg_engine* e, const azg_selfplay_config* cfg)
  * a net with fewer children leaves its remaining result columns empty as a tree with fewer root children does.  A wrong n_nets or
  * struct_size, an invalid value or a net that does not fit: AZG_E_INVALID (the message names the net), and the engine keeps the table
  * it had.
- * Widths: padded hidden width <= 256.  An engine whose nets are 512 or wider keeps the table but azg_search* / azg_selfplay_step return
- * AZG_E_UNSUPPORTED while it is set: the team, per-layer and wide one-launch kernels search with shared settings only. */
+ * Widths: padded hidden width <= 256.  An engine whose nets are 512 or wider keeps a table set through azg_set_net_search but
+ * azg_search* / azg_selfplay_step return AZG_E_UNSUPPORTED while it is set.  Nets of width >= 512 are searched with per-net settings
+ * through azg_set_net_search_ex with AZG_NET_SEARCH_WIDE (below): the team kernel, the per-layer launches and the wide one-launch kernels
+ * have forms that take the table.  What is still one per call at those widths: the team kernel's three-per-CU, 64-tree, compile-time
+ * specialised and two-part forms have no table variant -- a batch the base form (32-tree teams, two per CU) cannot hold resident runs
+ * as per-layer launches, as a population's does. */
 typedef struct azg_net_search {
     int32_t struct_size;     /* sizeof(azg_net_search), checked */
     int32_t reserved;        /* 0 */
@@ -65,6 +69,13 @@ typedef struct azg_net_search {
     double c_pw, kappa;      /* continuous mode; ignored in discrete mode */
 } azg_net_search;
 int azg_set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_nets);
+/* azg_set_net_search with flags (0: exactly azg_set_net_search).  AZG_NET_SEARCH_WIDE: the table may also be searched by nets of padded
+ * width >= 512 -- same fields, same rules, same bits as a one-net engine created with each net's settings; an engine with such a table
+ * searches the population kernels even with one net.  On narrower nets the flag permits and changes nothing else.  The permission
+ * belongs to the table: a later azg_set_net_search (no flag) drops it, and clearing the table (NULL / 0, or azg_set_population with
+ * another size) clears it too; a call that fails keeps the table and the permission the engine had.  Unknown flag bits: AZG_E_INVALID. */
+#define AZG_NET_SEARCH_WIDE 1u
+int azg_set_net_search_ex(azg_engine* e, const azg_net_search* nets, int32_t n_nets, uint32_t flags);
 
 #ifdef __cplusplus
 }

@@ -21,7 +21,14 @@ Per K, ms per search (kernel time, azg_last_search_ms, and wall time of search()
 different settings (search_kernel_nets), (a=) the same with a table whose K entries all equal the shared settings -- the very search
 of (b) on the general kernels with the table, so (a=) against (b) is what the mechanism costs, while (a) also searches other trees --
 (b) the same engine with the shared settings (the kernel it ran before there was a table, compile-time specialised where one exists),
-(c) K one-net engines with net k's settings, searched one after another.  The table is printed and written to --out."""
+(c) K one-net engines with net k's settings, searched one after another.  The table is printed and written to --out.
+
+--wide --per-net: the same question for wide nets (azg_set_net_search_ex with AZG_NET_SEARCH_WIDE), 1024 trees in all:
+    python tools/population_latency.py --wide --per-net [--splits 2x512,8x128,32x32] [--steps 20] [--warmup 3] [--out profiles/population_latency_wide_pernet.txt]
+Configurations: Pendulum-v1 4x1024 ELU x 200 simulations, CartPole 2x512 ReLU x 100 simulations.  Per split, INTERLEAVED -- every
+measured round runs (a), (a=), (b), (b) again and (c) once, in that order -- medians of kernel / wall ms per search: (a) one engine, a
+table of K distinct c_uct; (a=) the table's entries equal to the shared settings; (b) the same engine without a table, twice, so that
+the spread of two runs of the same thing stands next to a/b; (c) K one-net engines with net k's c_uct, one after another."""
 import argparse
 import json
 import os
@@ -234,6 +241,89 @@ def measure_per_net(name, K, steps, warmup):
                 b_wall_ms=round(b_wall, 3), b_kernel=b_name, c_kernel_ms=round(c_kern, 4), c_wall_ms=round(c_wall, 3))
 
 
+WIDE_PER_NET_SPLITS = "2x512,8x128,32x32"
+
+
+def measure_wide_per_net(name, K, T, steps, warmup):
+    from alphazero_gym_amd import _capi, _native
+    from alphazero_gym_amd.synthetic import make_weights
+    kw, (in_dim, hidden, n_dist, act) = WIDE_CONFIGS[name]
+    desc = _capi.make_desc(in_dim, hidden, n_dist, act)
+    blobs = [make_weights(34 + k, in_dim, hidden, n_dist) for k in range(K)]
+    shared = dict(c_uct=kw["c_uct"], gamma=kw["gamma"], epsilon=0.0, c_pw=kw.get("c_pw", 1.0), kappa=kw.get("kappa", 0.5))
+    settings = [dict(shared, c_uct=kw["c_uct"] * 4.0 ** (2.0 * k / (K - 1) - 1.0)) for k in range(K)]   # c_uct over a factor of 16
+    pop = _native.HipEngine(**dict(kw, n_trees=K * T))
+    pop.set_population(K)
+    for k in range(K):
+        pop.set_net_weights(k, desc, blobs[k])
+    roots = pop.synthetic_roots()
+    singles = []
+    for k in range(K):
+        st = {key: v for key, v in settings[k].items() if kw["mode"] == 1 or key not in ("c_pw", "kappa")}
+        e = _native.HipEngine(**dict(kw, n_trees=T, tree_id_base=k * T, **st))
+        e.set_weights(desc, blobs[k])
+        singles.append(e)
+
+    def loop():
+        for k, e in enumerate(singles):
+            e.search(roots[k * T:(k + 1) * T])
+
+    runs = {key: ([], []) for key in ("a", "a_equal", "b", "b_again", "c")}
+    names = {}
+
+    def timed(key, search, ms):
+        t0 = time.perf_counter()
+        search()
+        t1 = time.perf_counter()
+        return key, ms(), (t1 - t0) * 1e3
+
+    for i in range(warmup + steps):
+        out = []
+        pop.set_net_search(settings, wide=True)
+        out.append(timed("a", lambda: pop.search(roots), pop.last_search_ms))
+        names["a"] = pop.search_info()
+        pop.set_net_search([shared] * K, wide=True)
+        out.append(timed("a_equal", lambda: pop.search(roots), pop.last_search_ms))
+        pop.set_net_search(None)
+        out.append(timed("b", lambda: pop.search(roots), pop.last_search_ms))
+        names["b"] = pop.search_info()
+        out.append(timed("b_again", lambda: pop.search(roots), pop.last_search_ms))
+        out.append(timed("c", loop, lambda: sum(e.last_search_ms() for e in singles)))
+        if i >= warmup:
+            for key, kern, wall in out:
+                runs[key][0].append(kern)
+                runs[key][1].append(wall)
+    pop.close()
+    for e in singles:
+        e.close()
+    r = dict(K=K, T=T, a_kernel=names["a"]["kernel_name"], b_kernel=names["b"]["kernel_name"],
+             team_fallbacks=names["a"]["team_fallbacks"] + names["b"]["team_fallbacks"])
+    for key, (kern, wall) in runs.items():
+        r[key + "_kernel_ms"], r[key + "_wall_ms"] = round(float(np.median(kern)), 4), round(float(np.median(wall)), 3)
+    return r
+
+
+def main_wide_per_net(a):
+    lines = ["# per-net MCTS settings of wide nets in one search (azg_set_net_search_ex, AZG_NET_SEARCH_WIDE): ms per search, kernel / wall,",
+             f"# medians over {a.steps} interleaved rounds after {a.warmup} warm-up rounds; K nets x T trees = 1024 trees",
+             "# (a) one engine, a table of K distinct c_uct   (a=) its entries equal to the shared settings   (b), (b') the same engine without a",
+             "# table (the shared-settings kernel), measured twice per round   (c) K one-net engines with net k's c_uct, one after another"]
+    for name in a.configs.split(","):
+        lines.append(f"# {name}")
+        lines.append(f"# {'K x T':>9} {'(a) per-net ms':>20} {'(a=) equal ms':>20} {'(b) shared ms':>20} {'(b) again ms':>20} {'(c) K engines ms':>20} "
+                     f"{'a/b':>7} {'a=/b':>7} {'b/b':>7} {'c/a wall':>9}")
+        for K, T in parse_splits(a.splits):
+            r = measure_wide_per_net(name, K, T, a.steps, a.warmup)
+            cell = lambda key: f"{r[key + '_kernel_ms']:9.3f} / {r[key + '_wall_ms']:8.3f}"   # noqa: E731
+            lines.append(f"  {K:3d} x {T:4d} {cell('a')} {cell('a_equal')} {cell('b')} {cell('b_again')} {cell('c')} "
+                         f"{r['a_kernel_ms'] / r['b_kernel_ms']:6.3f}x {r['a_equal_kernel_ms'] / r['b_kernel_ms']:6.3f}x "
+                         f"{r['b_again_kernel_ms'] / r['b_kernel_ms']:6.3f}x {r['c_wall_ms'] / r['a_wall_ms']:8.2f}x")
+            lines.append(json.dumps(dict(config=name, **r)))
+            print("\n".join(lines[-2:]), flush=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main_per_net(a):
     lines = ["# per-net MCTS settings in one launch (azg_set_net_search): ms per search, kernel / wall, medians over "
              f"{a.steps} searches after {a.warmup} warm-up searches; {PER_NET_TREES} trees per net",
@@ -271,32 +361,36 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=None, help="measured steps per point (default 20; --wide: 5)")
     ap.add_argument("--warmup", type=int, default=None, help="warm-up steps per point (default 3; --wide: 2)")
     ap.add_argument("--wide", action="store_true", help="the wide configurations: one engine of K nets against K one-net engines in a loop")
-    ap.add_argument("--splits", default=WIDE_SPLITS, help="--wide: the K x T points")
+    ap.add_argument("--splits", default=None, help=f"--wide: the K x T points (default {WIDE_SPLITS}; with --per-net {WIDE_PER_NET_SPLITS})")
     ap.add_argument("--per-net", action="store_true", help="per-net MCTS settings: one launch of K settings against shared settings and K engines")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                  "population_latency_pernet.txt"), help="--per-net: the file the table is written to")
+    ap.add_argument("--out", default=None, help="--per-net: the file the table is written to (default profiles/population_latency_pernet.txt; "
+                                                "with --wide profiles/population_latency_wide_pernet.txt)")
     ap.add_argument("--configs", default=None)
     a = ap.parse_args(argv)
-    if a.wide and a.per_net:
-        ap.error("--wide and --per-net are separate measurements")
-    known = PER_NET_CONFIGS if a.per_net else WIDE_CONFIGS if a.wide else CONFIGS
+    known = WIDE_CONFIGS if a.wide else PER_NET_CONFIGS if a.per_net else CONFIGS
+    profiles = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    a.out = a.out or os.path.join(profiles, "population_latency_wide_pernet.txt" if a.wide else "population_latency_pernet.txt")
+    a.splits = a.splits or (WIDE_PER_NET_SPLITS if a.per_net else WIDE_SPLITS)
     a.configs = a.configs or ",".join(known)
     for name in a.configs.split(","):
         if name not in known:
             ap.error(f"unknown configuration {name!r}: {', '.join(known)}")
     if a.wide:
         try:
-            parse_splits(a.splits)
+            if any(k < 2 for k, _ in parse_splits(a.splits)) and a.per_net:
+                raise ValueError("--wide --per-net compares K >= 2 nets")
         except ValueError as err:
             ap.error(str(err))
-    a.steps = a.steps if a.steps is not None else (5 if a.wide else 20)
-    a.warmup = a.warmup if a.warmup is not None else (2 if a.wide else 3)
+    a.steps = a.steps if a.steps is not None else (5 if a.wide and not a.per_net else 20)
+    a.warmup = a.warmup if a.warmup is not None else (2 if a.wide and not a.per_net else 3)
     return a
 
 
 def main():
     a = parse_args()
     os.environ.setdefault("AZG_QUIET", "1")
+    if a.wide and a.per_net:
+        return main_wide_per_net(a)
     if a.wide:
         return main_wide(a)
     if a.per_net:

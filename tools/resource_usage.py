@@ -74,7 +74,8 @@ def main():
 
 
 def report(tu, flt, extra):
-    if tu in ("dispatch_pendulum_large", "dispatch_team_wide", "dispatch_mcc", "dispatch_nets_pendulum_large", "dispatch_nets_mcc") and "-licm" not in " ".join(extra):   # (as alphazero_gym_amd/csrc/Makefile builds them)
+    if tu in ("dispatch_pendulum_large", "dispatch_team_wide", "dispatch_mcc", "dispatch_nets_pendulum_large", "dispatch_nets_mcc", "dispatch_nets_wide_pendulum",
+              "dispatch_nets_wide_mcc", "dispatch_nets_mcc_wide") and "-licm" not in " ".join(extra):   # (as alphazero_gym_amd/csrc/Makefile builds them)
         extra = extra + ["-mllvm", "-disable-machine-licm"]
     with tempfile.TemporaryDirectory() as tmp:
         asm = os.path.join(tmp, tu + ".s")
