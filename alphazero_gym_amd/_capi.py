@@ -133,7 +133,7 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
 
 class AzgNetSearch(C.Structure):
     """include/azgym_population.h: azg_net_search"""
-    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("c_uct", C.c_double), ("gamma", C.c_double), ("epsilon", C.c_double),
+    _fields_ = [("struct_size", C.c_int32), ("n_sims", C.c_int32), ("c_uct", C.c_double), ("gamma", C.c_double), ("epsilon", C.c_double),
                 ("c_pw", C.c_double), ("kappa", C.c_double)]
 
 
@@ -512,10 +512,12 @@ class Engine:
         self._check(self._optional("set_population")(self._h, int(n_nets)))
         self.n_nets = int(n_nets)
 
-    def set_net_search(self, settings, wide=False):
+    def set_net_search(self, settings, wide=False, n_sims=None):
         """azg_set_net_search: net k searches with settings[k], a dict with all of c_uct, gamma, epsilon, c_pw, kappa (discrete mode
         ignores the last two), instead of the engine's shared settings; None returns to those.  One entry per net of the population.
-        ``wide=True``: azg_set_net_search_ex with AZG_NET_SEARCH_WIDE -- the table may be searched by nets of padded width >= 512."""
+        ``wide=True``: azg_set_net_search_ex with AZG_NET_SEARCH_WIDE -- the table may be searched by nets of padded width >= 512.
+        ``n_sims`` (optional): one int per net, net k's own simulation budget (azg_net_search.n_sims: 0 = the engine's, else 1 .. the
+        engine's n_sims, which stays the capacity)."""
         if wide:
             ex = self._optional("set_net_search_ex")
 
@@ -527,9 +529,14 @@ class Engine:
             self._check(fn(self._h, None, 0))
             return
         settings = list(settings)
+        if n_sims is not None:
+            n_sims = [int(n) for n in n_sims]
+            if len(n_sims) != len(settings):
+                raise ValueError(f"set_net_search: n_sims has {len(n_sims)} entries for {len(settings)} nets: one per net")
         arr = (AzgNetSearch * max(len(settings), 1))()
         for k, st in enumerate(settings):
             arr[k].struct_size = C.sizeof(AzgNetSearch)
+            arr[k].n_sims = 0 if n_sims is None else n_sims[k]
             for key in NET_SEARCH_KEYS:
                 setattr(arr[k], key, float(st[key]))
         self._check(fn(self._h, arr, len(settings)))

@@ -30,12 +30,14 @@ class AgentPopulation:
     ``per_agent_search=True`` (opt-in): the agents may differ in ``mcts.c_uct`` / ``gamma`` / ``epsilon`` and (continuous) ``c_pw`` /
     ``kappa``; agent k's tree is searched with its own values, still in the one launch (PopulationMCTS ``net_settings``).  Everything
     else must still agree.  ``wide_search=True`` with it: agents whose networks are 512 or wider (PopulationMCTS
-    ``net_settings_wide``)."""
+    ``net_settings_wide``).  ``per_agent_rollouts=True`` with it: the agents may also differ in ``mcts.n_rollouts``; the engine is
+    created with the largest budget and agent k's tree runs its own (PopulationMCTS ``net_rollouts``), and the visit count a reused
+    discrete root carries grows by agent k's own budget."""
 
     PER_AGENT = _capi.NET_SEARCH_KEYS
 
     def __init__(self, agents: Sequence[Any], seeds: Optional[Sequence[int]] = None, tree_id_base: int = 0,
-                 per_agent_search: bool = False, wide_search: bool = False):
+                 per_agent_search: bool = False, wide_search: bool = False, per_agent_rollouts: bool = False):
         self.agents = list(agents)
         if not self.agents:
             raise ValueError("AgentPopulation needs at least one agent")
@@ -49,11 +51,17 @@ class AgentPopulation:
         if wide_search and not self.per_agent_search:
             raise ValueError("AgentPopulation: wide_search=True goes with per_agent_search=True (it lets wide networks search with per-agent settings)")
         self.wide_search = bool(wide_search)
+        if per_agent_rollouts and not self.per_agent_search:
+            raise ValueError("AgentPopulation: per_agent_rollouts=True goes with per_agent_search=True (the budgets travel in the per-agent table)")
+        self.per_agent_rollouts = bool(per_agent_rollouts)
         keys = {self._settings(a) for a in self.agents}
         if len(keys) != 1:
             if not self.per_agent_search:
                 raise ValueError("AgentPopulation: every agent must have the same MCTS settings (per-agent search hyper-parameters are not "
                                  "supported)")
+            if self.per_agent_rollouts:
+                raise ValueError("AgentPopulation(per_agent_search=True, per_agent_rollouts=True): the agents may differ in n_rollouts, c_uct, "
+                                 "gamma, epsilon, c_pw and kappa only; V_target_policy, seed, device and the other engine settings must agree")
             raise ValueError("AgentPopulation(per_agent_search=True): the agents may differ in c_uct, gamma, epsilon, c_pw and kappa only; "
                              "n_rollouts, V_target_policy, seed, device and the other engine settings must agree")
         self.tree_id_base = int(tree_id_base)
@@ -79,7 +87,7 @@ class AgentPopulation:
         m = agent.mcts
         key = (type(m), m.n_rollouts, m.c_uct, m.gamma, m.epsilon, m.V_target_policy, m.seed, device_ordinal(m.device))
         if self.per_agent_search:   # (the five settings an agent may have its own of do not have to agree)
-            key = (type(m), m.n_rollouts, m.V_target_policy, m.seed, device_ordinal(m.device))
+            key = (type(m), None if self.per_agent_rollouts else m.n_rollouts, m.V_target_policy, m.seed, device_ordinal(m.device))
         return key + tuple(sorted((k, v) for k, v in m._engine_kwargs().items() if not (self.per_agent_search and k in self.PER_AGENT)))
 
     def _net_settings(self) -> Optional[List[Dict[str, float]]]:
@@ -87,6 +95,12 @@ class AgentPopulation:
         if not self.per_agent_search:
             return None
         return [{k: float(getattr(a.mcts, k)) for k in self.PER_AGENT if hasattr(a.mcts, k)} for a in self.agents]
+
+    def _net_rollouts(self) -> Optional[List[int]]:
+        """Each agent's own simulation budget (None without ``per_agent_rollouts``)."""
+        if not self.per_agent_rollouts:
+            return None
+        return [int(a.mcts.n_rollouts) for a in self.agents]
 
     @contextlib.contextmanager
     def rng(self, k: int):
@@ -108,11 +122,13 @@ class AgentPopulation:
                 self._pop.close()
             m = self.agents[0].mcts
             self._pop = PopulationMCTS([a.nn for a in self.agents], trees_per_model=1, env_id=env_id,
-                                       mode=_capi.MODE_DISCRETE if self.discrete else _capi.MODE_CONTINUOUS, n_rollouts=m.n_rollouts,
+                                       mode=_capi.MODE_DISCRETE if self.discrete else _capi.MODE_CONTINUOUS,
+                                       n_rollouts=max(self._net_rollouts()) if self.per_agent_rollouts else m.n_rollouts,
                                        c_uct=m.c_uct, gamma=m.gamma, epsilon=m.epsilon, V_target_policy=m.V_target_policy, seed=m.seed,
                                        tree_id_base=self.tree_id_base, device_id=device_ordinal(m.device), **m._engine_kwargs(),
                                        **({"net_settings": self._net_settings()} if self.per_agent_search else {}),
-                                       **({"net_settings_wide": True} if self.wide_search else {}))
+                                       **({"net_settings_wide": True} if self.wide_search else {}),
+                                       **({"net_rollouts": self._net_rollouts()} if self.per_agent_rollouts else {}))
             self._env_id = env_id
         return self._pop
 

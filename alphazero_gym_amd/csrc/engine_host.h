@@ -142,6 +142,7 @@ struct azg_engine : EngineQueue {
     // take it.  net_search_wide: the table came with AZG_NET_SEARCH_WIDE (azg_set_net_search_ex) and may be searched at widths >= 512
     DeviceAllocs net_search_mem; NetSearchTable net_search{};
     int net_search_wide = 0;
+    int net_sims_max = 0;    // the table's largest per-net simulation budget (azg_net_search::n_sims): the per-layer launches' step count
     DeviceAllocs stamp_mem; size_t stamp_n = 0;   // rows of the diagnostic stamp buffer (P.stamps)
     uint32_t last_search_idx = 0;   // the search index the last search ran under (azg_dump_tree re-runs it with this one)
     float ms_kept = 0.0f; int ms_kept_valid = 0;   // kernel time of the last search, kept across azg_dump_tree's re-run of it
@@ -195,6 +196,7 @@ static inline long azg_padded_trees(const azg_engine* e, int tpw) {
 
 // Progressive widening (NodeContinuous.check_pw, states.py:271-273: python float pow + math.ceil, evaluated on the host with libm): the
 // children a node with n visits is entitled to, n = 0 .. n_sims + 1, into pw; returns the largest entitlement a search reaches (Kmax).
+// (Entry n does not depend on n_sims: a table built for a smaller budget is a prefix of one built for a larger.)
 static inline int azg_pw_table(double c_pw, double kappa, int n_sims, std::vector<int>& pw) {
     pw.assign((size_t)n_sims + 2, 0);
     int kmax = 1;

@@ -333,6 +333,7 @@ int azg_set_population(azg_engine* e, int32_t n_nets) {
     e->net_search = NetSearchTable{};
     e->net_search_mem.clear();
     e->net_search_wide = 0;
+    e->net_sims_max = 0;
     e->n_nets = n_nets;
     e->net_have.assign(n_nets, 0);
     e->mlp_ready = 0; e->results_valid = 0; e->redo_ok = 0; e->searched = 0;
@@ -344,12 +345,17 @@ int azg_set_population(azg_engine* e, int32_t n_nets) {
 // NetSearchTable).  The buffers are allocated when the table appears and reused while it stays; the copies go on the engine's stream,
 // behind whatever search is running there.  wide: the table may be searched at padded widths >= 512 (AZG_NET_SEARCH_WIDE); a call that
 // fails leaves the table and its permission as they were.
+// Budgets: azg_net_search::n_sims (0: the engine's) is the net's own number of simulations, at most azg_config's, which stays the
+// capacity everything was sized for at creation.  The net's widening table is built with its own budget -- the entries a one-net engine
+// created with that budget builds, the rest of its capacity-sized row zero and never read (tree.cuh: pw_at clamps at the budget + 1) --
+// and its Kmax check counts the children its own budget reaches.
 static int set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_nets, bool wide) {
     const bool clear = !nets || n_nets == 0;
     const bool cont = e->cfg.mode == AZG_MODE_CONTINUOUS;
     const int ns = e->cfg.n_sims;
     std::vector<NetSearchRec> rec;
     std::vector<int> pw_all, pw;
+    int sims_max = 0;
     if (!clear) {
         if (n_nets != e->n_nets)
             return fail(e, AZG_E_INVALID, "azg_set_net_search: n_nets must equal the engine's number of nets (azg_set_population): got " +
@@ -362,15 +368,20 @@ static int set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_n
             if (s.struct_size != (int32_t)sizeof(azg_net_search)) return fail(e, AZG_E_INVALID, who + "azg_net_search size mismatch");
             if (!std::isfinite(s.c_uct) || !std::isfinite(s.gamma) || !std::isfinite(s.epsilon))
                 return fail(e, AZG_E_INVALID, who + "c_uct, gamma and epsilon must be finite");
+            if (s.n_sims < 0 || s.n_sims > ns)
+                return fail(e, AZG_E_INVALID, who + "n_sims must be 0 (the engine's) or 1 .. " + std::to_string(ns) + ", the n_sims the engine was created "
+                                              "with (its capacity): got " + std::to_string(s.n_sims));
+            const int ns_k = s.n_sims ? s.n_sims : ns;
+            if (ns_k > sims_max) sims_max = ns_k;
             NetSearchRec& r = rec[k];
             r.c_uct = s.c_uct; r.gamma = s.gamma; r.epsilon = s.epsilon;
             r.c_uct_f = (float)s.c_uct; r.gamma_f = (float)s.gamma;
-            r.c_pw = 0.0; r.kappa = 0.0; r.pw0 = 0; r.pad = 0;
+            r.c_pw = 0.0; r.kappa = 0.0; r.pw0 = 0; r.n_sims = ns_k;
             if (!cont) continue;   // (discrete mode: no widening)
             if (!azg_pw_params_ok(s.c_pw, s.kappa))
                 return fail(e, AZG_E_INVALID, who + "c_pw must be > 0 and kappa >= 0 (progressive widening: ceil(c_pw (n + 1)^kappa) children)");
             // the trees, the child lists and the results were sized at creation for azg_config's widening: every net must stay inside
-            const int kmax = azg_pw_table(s.c_pw, s.kappa, ns, pw);
+            const int kmax = azg_pw_table(s.c_pw, s.kappa, ns_k, pw);   // (ns_k + 2 entries)
             if (kmax > e->Kmax)
                 return fail(e, AZG_E_INVALID, who + "its widening (c_pw, kappa) entitles a node to " + std::to_string(kmax) + " children, the engine was "
                                               "created for at most " + std::to_string(e->Kmax) + " (azg_max_children): create it with the widest net's c_pw / kappa");
@@ -387,6 +398,7 @@ static int set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_n
         e->net_search = NetSearchTable{};
         e->net_search_mem.clear();
         e->net_search_wide = 0;
+        e->net_sims_max = 0;
         return AZG_OK;
     }
     if (!e->net_search.rec) {
@@ -401,6 +413,7 @@ static int set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_n
     HIPCHK(e, hipMemcpyAsync((void*)e->net_search.pw_need, pw_all.data(), pw_all.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));   // (the staging vectors go when this returns)
     e->net_search_wide = wide ? 1 : 0;
+    e->net_sims_max = sims_max;
     return AZG_OK;
 }
 

@@ -50,16 +50,22 @@ __device__ __forceinline__ KParams ls_net_params(const KParams& P, const NetSear
     const NetSearchRec& r = nets.rec[k];
     KParams Q = P;
     Q.c_uct = r.c_uct; Q.gamma = r.gamma; Q.epsilon = r.epsilon;
-    Q.c_uct_f = r.c_uct_f; Q.gamma_f = r.gamma_f; Q.pw0 = r.pw0;
+    Q.c_uct_f = r.c_uct_f; Q.gamma_f = r.gamma_f; Q.pw0 = r.pw0; Q.n_sims = r.n_sims;   // (the net's own budget: the tree phases' loop bound)
     Q.pw_need = nets.pw_need + (size_t)k * (P.n_sims + 2);
     return Q;
 }
 
 // ls_tree_kernel's population form with the table: the launches of a search all read the same record for a given tree group.
+// Budgets: the host launches a search's steps up to the LARGEST budget of the table (ls_dispatch.cuh).  A group's net finishes at its
+// own: the launch with sim = its budget - 1 backs up the last trace and publishes n_rec (the body's last-step branch, taken once), and
+// in every later launch the group leaves right here -- its trees, its LsTree / LsLane state and its observations stay as that launch
+// left them, and the layer kernels keep computing on those stale observations into activations nobody reads.  Nothing waits: a launch
+// has one barrier per workgroup (the tables' fill), in front of which the whole workgroup -- one net -- has either left or stayed.
 template <int ENV, bool GMM, int NCH, int HP>
 __global__ __launch_bounds__(256) void ls_tree_kernel_nets(KParams P, LockStep L, int sim, int g_base, NetSearchTable nets) {
     constexpr bool POP = true;
     const KParams PT = ls_net_params(P, nets, g_base + (int)blockIdx.x);
+    if (sim >= PT.n_sims) return;   // (uniform over the workgroup: past its net's last trace)
 #include "ls_tree_kernel_body.inc"
 }
 

@@ -9,6 +9,8 @@
 // not host-bound.  Cutting the batch into pipelines on several streams measured +6 % / +40 % time at config E: removed, HISTORY.md.)
 // POP: the kernels' population forms (lockstep.cuh: every tree group and tile pair reads its net's weights).
 // NSET: the population forms with the engine's table of per-net MCTS settings -- ls_tree_kernel_nets; the layer kernels read no setting.
+// With a table the steps run to its largest per-net budget (azg_engine::net_sims_max <= cfg.n_sims); a tree group whose net has a
+// smaller one finishes in the tree launch of its own last step and sits the later ones out (lockstep.cuh: ls_tree_kernel_nets).
 template <int ENV, int HP, bool GMM, bool POP, bool NSET = false>
 static hipError_t ls_enqueue(azg_engine* e, hipStream_t st) {
     static_assert(!NSET || POP, "per-net settings run the population forms");
@@ -31,7 +33,8 @@ static hipError_t ls_enqueue(azg_engine* e, hipStream_t st) {
     if (rc == hipSuccess) rc = tkl_attrs.set_dyn_lds(e, (const void*)tkl, tiled_bytes);
     if (rc != hipSuccess) return rc;
     tree_launch(-2);
-    for (int sim = -1; sim < e->cfg.n_sims; ++sim) {
+    const int n_steps = NSET ? e->net_sims_max : e->cfg.n_sims;
+    for (int sim = -1; sim < n_steps; ++sim) {
         hipLaunchKernelGGL((ls_layer0_kernel<HP, POP>), dim3(G * NS), dim3(256), 0, st, e->P, e->ls, 0);
         for (int l = 1; l < e->n_hidden; ++l) {
             auto k = l == e->n_hidden - 1 ? tkl : tkh;

@@ -36,7 +36,7 @@
         if (live) tree_phase_a<ENV, TS_GLOBAL, GMM, NCH>(PT, st, ts, cold, edge_W, action, tb, sim, sub, tl, gtree,
                                                      L.parts + (size_t)tg * NCH * 64, P.bhead + ls_net_wofs<POP>(P, tg), s_sqrt STAMP_ARG, s_pw);
         st.need_eval = false;
-        if (sim < P.n_sims - 1) {
+        if (sim < PT.n_sims - 1) {   // (PT: the net's own budget; the tables above are laid out for P.n_sims, the engine's)
             __threadfence_block();
             if (live) tree_phase_b<ENV, TS_GLOBAL, GMM>(PT, st, ts, cold, edge_W, action, tb, sub, tl, gtree, s_sqrt, s_pw, obsT STAMP_ARG);
             else if (sub < 4) obsT[sub * 16 + tl] = 0.0f;

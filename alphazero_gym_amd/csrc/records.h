@@ -129,16 +129,18 @@ struct KParams {
 };
 
 // Per-net MCTS settings of a population (azg_set_net_search; search_kernel.cuh: search_kernel_nets): one record per net with what
-// KParams holds of them, and the nets' widening tables (n_sims + 2 entries each) one after the other.
+// KParams holds of them, and the nets' widening tables one after the other.  n_sims: the net's own simulation budget, 1 .. the
+// engine's (the host resolves azg_net_search's 0 to the engine's): the LOOP BOUND of the net's trees.  KParams::n_sims of the kernel
+// argument stays the engine's -- the CAPACITY everything is laid out for: records per tree, the tables' lengths and strides, LDS.
 struct __attribute__((aligned(16))) NetSearchRec {
     double c_uct, gamma, epsilon, c_pw, kappa;
     float c_uct_f, gamma_f;
-    int pw0, pad;
+    int pw0, n_sims;
 };
 static_assert(sizeof(NetSearchRec) == 64, "NetSearchRec must be 64 bytes");
 struct NetSearchTable {
     const NetSearchRec* rec;   // [n_nets]
-    const int* pw_need;        // [n_nets][n_sims + 2]
+    const int* pw_need;        // [n_nets][KParams::n_sims + 2] (net k's first NetSearchRec::n_sims + 2 entries are its own engine's)
 };
 
 // ---- state of the lock-step path (lockstep.cuh) between its launches

@@ -65,6 +65,12 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel(KParam
 // phase and the weight loads keep reading the kernel argument itself (PN): it indexes the per-layer pointer arrays at run time,
 // which would pin a copy of the whole block in scratch memory (728 bytes per lane in every weight-streaming kernel) instead of
 // leaving the copy's fields in scalar registers.  SPEC = 0 only: the compile-time specialisations assume one parameter set for the launch.
+// The copy's n_sims is the net's own simulation budget: the body bounds its loops and clamps its widening look-ups with P.n_sims and
+// takes everything that is layout (lds_layout, the length of s_pw, the state slots, the table stride) from PN.n_sims, the engine's.
+// Who waits for whom: every wait of the body is workgroup-wide -- __syncthreads, the first-layer counter s_l0 and the policy mailbox
+// s_mb (both in the workgroup's LDS, step numbers the workgroup's own), s_done (counts this workgroup's trees).  A workgroup belongs
+// to ONE net, so all of its threads hold the same bound, run the same number of steps and leave together; no workgroup waits for
+// another, so nets of different budgets in one grid never meet.
 template <int ENV, int HP, int NREG, int TLDS, bool GMM, int NW, int NG, int NT = 16, int SPEC = 0>
 __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel_nets(KParams P0, NetSearchTable nets) {
     static_assert(SPEC == 0, "per-net settings run the general kernels");
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(64 * NW, NT < 16 ? 2 : 1) void search_kernel_nets(K
         const int k = (int)blockIdx.x / P0.net_wgs;   // (< the table's n_nets: the grid has n_nets * net_wgs workgroups)
         const NetSearchRec& r = nets.rec[k];
         P.c_uct = r.c_uct; P.gamma = r.gamma; P.epsilon = r.epsilon;
-        P.c_uct_f = r.c_uct_f; P.gamma_f = r.gamma_f; P.pw0 = r.pw0;
+        P.c_uct_f = r.c_uct_f; P.gamma_f = r.gamma_f; P.pw0 = r.pw0; P.n_sims = r.n_sims;
         P.pw_need = nets.pw_need + (size_t)k * (P0.n_sims + 2);
     }
 #include "search_kernel_body.inc"

@@ -1,6 +1,7 @@
 // search_kernel_body.inc -- the body of the persistent search kernel, included by each of its two entry points (search_kernel.cuh):
 // search_kernel, whose KParams P is the kernel argument, and search_kernel_nets, whose P is a copy with its net's MCTS settings.
-// Both are the same text, so the kernels differ only in where P comes from.  PN is the kernel argument in both: the network's tensors.
+// Both are the same text, so the kernels differ only in where P comes from.  PN is the kernel argument in both: the network's tensors
+// and the layout (PN.n_sims: the engine's capacity; P.n_sims: the simulations this workgroup's trees run -- the same object in search_kernel).
     constexpr bool CONT = EnvFamily<ENV>::CONT;
     static_assert(NT == 16 || (NG == 1 && NW == 4 && (NT == 8 || NT == 4)), "half-filled tiles: one group, four waves");
     constexpr int TPW = NT * NG;        // trees per workgroup
@@ -60,13 +61,13 @@
     // packed two fields to a register, and the path's rewards / returns are fetched after the network phase instead of during
     // the descent (EARLYP kernels: in front of it, see above).  With one wave per SIMD (NW = 4: 512 registers) everything stays in registers (measured faster there).
     constexpr bool LEAN = (NW == 8);   // (also for the 16-tree shape: carrying everything instead costs 7 spilled registers and 0.7 % time)
-    const LdsLayout L = lds_layout(P.tab_n, P.n_sims, HP, NG, act_buffers(NREG), P.R, CONT, TLDS, P.lds_state, NT);
+    const LdsLayout L = lds_layout(P.tab_n, PN.n_sims, HP, NG, act_buffers(NREG), P.R, CONT, TLDS, P.lds_state, NT);
     double* s_sqrt = s_dyn;
     unsigned short* s_pw = (unsigned short*)(s_dyn + P.tab_n);   // widening thresholds, clamped (a node has < 32768 children)
     f32x4* s_actA = (f32x4*)((char*)s_dyn + L.act_off);
     f32x4* s_actB = act_buffers(NREG) == 2 ? s_actA + NG * (HP / 16 * 64) : s_actA;
     for (int i = tid; i < P.tab_n; i += 64 * NW) s_sqrt[i] = P.sqrt_tab[i];
-    if (CONT) for (int i = tid; i < P.n_sims + 2; i += 64 * NW) s_pw[i] = (unsigned short)(P.pw_need[i] < 65535 ? P.pw_need[i] : 65535);
+    if (CONT) for (int i = tid; i < PN.n_sims + 2; i += 64 * NW) s_pw[i] = (unsigned short)(P.pw_need[i] < 65535 ? P.pw_need[i] : 65535);
     if (tid < 16) s_bhead[tid] = PN.bhead[wofs + tid];
     if (tid == 0) { s_done = 0; s_l0 = 0; }
     if constexpr (HPOL) { if (tid < 16) s_mb.flag[tid] = 0; }   // (step numbers start at 1)

@@ -142,6 +142,11 @@ __global__ __launch_bounds__(256, MINB) void ls_team_kernel(KParams P, LockStep 
 
 // Per-net MCTS settings (lockstep.cuh: ls_net_params): the base population form -- 32-tree teams, two per CU, the general tree phases --
 // whose workgroups read their team's net's record once at kernel entry, outside the simulation loop, and walk their trees with it.
+// Budgets: the simulation loop and its two `k < n_sims` tests read PT.n_sims, the net's own; team_tree_off and the s_pw fill keep
+// P.n_sims, the engine's (layout).  Who waits for whom: team_wait / team_arrive work on the TEAM's counters (cnt: one block per 32
+// trees) with targets NU * (k + 1), and a workgroup's barriers are its own.  All NU workgroups of a team derive their net from the
+// team's first tree group, read the same record and so run the same k = 0 .. n_sims: each arrives exactly once per hand-off the others
+// wait for, and the team leaves together after its own last step.  No wait spans two teams, so a team that has left owes nothing.
 template <int ENV, int HP, bool GMM, int TLDS, int KC = LS_KC, int MINB = 2>
 __global__ __launch_bounds__(256, MINB) void ls_team_kernel_nets(KParams P, LockStep L, TeamCtl T, int TQ, int g_base, NetSearchTable nets) {
     constexpr int SPEC = 0, TT = 32;

@@ -138,7 +138,7 @@
     unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     TSTAMP(t_begin);
-    for (int k = 0; k <= P.n_sims; ++k) {                    // evaluation k follows trace k - 1 (k = 0: the roots)
+    for (int k = 0; k <= PT.n_sims; ++k) {                    // evaluation k follows trace k - 1 (k = 0: the roots)
         const int sim = k - 1;
         TSTAMP(t0);
         if (!team_wait(cnt, (unsigned)(NU * (k + 1)), T, &s_ok)) return;
@@ -185,7 +185,7 @@
         st.need_eval = false;
         TSTAMP(tp1);
         if constexpr (BDEF) { if (k == 0 && live) eps_prepare(PT, st, gtree, sub); }   // (no tree_phase_b2 in front of the first trace)
-        if (k < P.n_sims) {
+        if (k < PT.n_sims) {
             tree_fence();
             if (live) tree_phase_b<ENV, TLDS, GMM, TPW, int, true, false, SPEC, false, BDEF>(PT, st, ts, cold, edge_W, action, tb, sub, tj, gtree, s_sqrt, s_pw, s_obs STAMP_ARG, &bdef);
         }
@@ -194,7 +194,7 @@
 #ifdef AZG_STAMPS
         st_acc[0] += tp0 - te; st_acc[1] += tp1 - tp0; st_acc[2] += tp2 - tp1;
 #endif
-        if (k < P.n_sims) {
+        if (k < PT.n_sims) {
             __syncthreads();
             first_layer(wt);
             team_arrive(cnt);

@@ -147,7 +147,8 @@ def make_agent(kind: str, cfg: dict, Env, tree_id_base: int = 0):
 
 
 def run_population(kind: str, seeds: List[int], cfg: Optional[dict] = None, log: Optional[Callable[[Dict, int, int], None]] = None,
-                   agents: Optional[List] = None, sweep: Optional[Dict[str, List[float]]] = None) -> List[List[float]]:
+                   agents: Optional[List] = None, sweep: Optional[Dict[str, List[float]]] = None,
+                   rollouts: Optional[List[int]] = None) -> List[List[float]]:
     """run_continuous.py / run_discrete.py for K seeds at once (kind "continuous" / "discrete"; cfg as for run_*_agent, its
     ``seed`` replaced by ``seeds``).  Agent k plays its own game (env seeded with seeds[k]) with its own network, buffer,
     optimiser and np.random / random streams (seeded with seeds[k]); every environment step searches all agents' trees in ONE
@@ -156,7 +157,10 @@ def run_population(kind: str, seeds: List[int], cfg: Optional[dict] = None, log:
     ``log(info, episode, k)`` gets agent k's training losses and its "Episode reward".
     ``sweep``: search settings swept over the seeds, {"c_uct": [...], "gamma": [...], "epsilon": [...], "c_pw": [...], "kappa": [...]}
     (any subset; one list entry per seed): agent k is built with its own values in place of cfg["mcts"]'s, and all agents are still
-    searched in one launch (AgentPopulation(per_agent_search=True))."""
+    searched in one launch (AgentPopulation(per_agent_search=True)).
+    ``rollouts``: simulation budgets swept over the seeds, one int >= 1 per seed: agent k is built with ``n_rollouts = rollouts[k]``
+    and all agents are still searched in one launch, in an engine created for the largest budget
+    (AgentPopulation(per_agent_rollouts=True)).  It combines with ``sweep``; ``sweep={"n_rollouts": ...}`` is not the way in."""
     cfg = _merge(CONTINUOUS_DEFAULTS if kind == "continuous" else DISCRETE_DEFAULTS, cfg)
     K = len(seeds)
     sweep = dict(sweep or {})
@@ -167,17 +171,28 @@ def run_population(kind: str, seeds: List[int], cfg: Optional[dict] = None, log:
             raise ValueError(f"sweep[{key!r}] has {len(vals)} entries for {K} seeds: one per seed")
     if sweep and agents is not None:
         raise ValueError("sweep builds the agents itself: pass either sweep or agents")
+    if rollouts is not None:
+        if agents is not None:
+            raise ValueError("rollouts builds the agents itself: pass either rollouts or agents")
+        if len(rollouts) != K:
+            raise ValueError(f"rollouts has {len(rollouts)} entries for {K} seeds: one per seed")
+        if any(int(n) != n or int(n) < 1 for n in rollouts):
+            raise ValueError(f"rollouts: every seed's budget is an int >= 1, got {list(rollouts)}")
     envs = []
     for s in seeds:
         Env = make_game(cfg["game"])
         Env.seed(s)
         envs.append(Env)
     if agents is None:
-        agents = [make_agent(kind, dict(cfg, mcts=dict(cfg["mcts"], **{key: vals[k] for key, vals in sweep.items()})), envs[k],
-                             tree_id_base=k) for k in range(K)]
+        own = [dict({key: vals[k] for key, vals in sweep.items()}, **({} if rollouts is None else {"n_rollouts": int(rollouts[k])}))
+               for k in range(K)]
+        agents = [make_agent(kind, dict(cfg, mcts=dict(cfg["mcts"], **own[k])), envs[k], tree_id_base=k) for k in range(K)]
     assert len(agents) == K
     buffers = [ReplayBuffer(**cfg["buffer"]) for _ in range(K)]
-    pop = AgentPopulation(agents, seeds=seeds, per_agent_search=bool(sweep))
+    if rollouts is not None:   # (opt-in: the agents' budgets differ; with or without swept settings)
+        pop = AgentPopulation(agents, seeds=seeds, per_agent_search=True, per_agent_rollouts=True)
+    else:
+        pop = AgentPopulation(agents, seeds=seeds, per_agent_search=bool(sweep))
     returns: List[List[float]] = [[] for _ in range(K)]
     try:
         for ep in range(cfg["num_train_episodes"]):
@@ -295,7 +310,8 @@ class PopulationSelfPlay:
     games ``DeviceSelfPlay(policies[k], n_games=T, rank=k)`` plays, bit for bit, with one search launch and one self-play launch
     per step for the whole population.  The game, search and self-play settings are shared by every net, except that
     ``net_settings`` (``PopulationMCTS``: a list of K dicts) gives net k its own c_uct / gamma / epsilon / c_pw / kappa;
-    ``net_settings_wide=True`` lets nets of padded hidden width >= 512 search with them.  The agents' final
+    ``net_settings_wide=True`` lets nets of padded hidden width >= 512 search with them; ``net_rollouts`` (K ints in 1 ..
+    ``n_rollouts``) gives net k its own simulation budget, ``n_rollouts`` staying the engine's capacity.  The agents' final
     action rules run on the device too: ``final_selection`` "max_visit" / "max_value", discrete ``temperature`` and
     ``deterministic``, continuous ``agent_epsilon`` (agents.py:294-301, 524-535; include/azgym.h).  ``fifo=True`` turns the
     replay ring into the reference's overwrite-the-oldest buffer (buffers.py:75-82).  Weights are re-uploaded only when some
@@ -305,7 +321,8 @@ class PopulationSelfPlay:
                  c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
                  deterministic: bool = False, capacity_steps: int = 64, seed: int = 34, tree_id_base: int = 0, device_id: int = 0,
                  final_selection: str = "max_visit", temperature: float = 1.0, agent_epsilon: float = 0.0, fifo: bool = False,
-                 net_settings: Optional[List[dict]] = None, net_settings_wide: Optional[bool] = None):
+                 net_settings: Optional[List[dict]] = None, net_settings_wide: Optional[bool] = None,
+                 net_rollouts: Optional[List[int]] = None):
         policies = list(policies)
         if not policies or games_per_net < 1:
             raise ValueError(f"{type(self).__name__} needs at least one policy and games_per_net >= 1")
@@ -314,6 +331,8 @@ class PopulationSelfPlay:
             kw["net_settings"] = net_settings
         if net_settings_wide is not None:   # (opt-in: the table may be searched by nets of width >= 512)
             kw["net_settings_wide"] = net_settings_wide
+        if net_rollouts is not None:   # (opt-in: net k runs its own number of simulations per search, PopulationMCTS)
+            kw["net_rollouts"] = net_rollouts
         self.continuous = kw["mode"] == _capi.MODE_CONTINUOUS
         self.mcts = self._search(policies, games_per_net, n_rollouts=n_rollouts, c_uct=c_uct, gamma=gamma, epsilon=epsilon,
                                  V_target_policy=V_target_policy, seed=seed, tree_id_base=tree_id_base, device_id=device_id, **kw)

@@ -88,12 +88,19 @@ class PopulationMCTS:
     one-model engine with those kwargs computes (azg_set_net_search).  The engine is created with the (c_pw, kappa) pair that widens
     furthest, so that every model's trees fit; ``set_net_settings`` changes the settings between searches.  Networks of padded hidden
     width >= 512 need ``net_settings_wide=True`` (azg_set_net_search_ex with AZG_NET_SEARCH_WIDE: the team, per-layer and wide
-    one-launch kernels' table forms); without it they search with shared settings only: ValueError."""
+    one-launch kernels' table forms); without it they search with shared settings only: ValueError.
+
+    ``net_rollouts`` (opt-in; None: every model runs ``n_rollouts``): K ints in 1 .. ``n_rollouts`` -- model k runs its own number of
+    simulations per search, in the same launch, bit for bit what a one-model engine created with that ``n_rollouts`` computes
+    (azg_net_search.n_sims).  ``n_rollouts`` stays the engine's capacity: storage, tables and the kernel form follow it.  With or
+    without ``net_settings`` (without: every model's five settings are the shared ones); the same width and ``net_settings_wide``
+    rules apply.  ``set_net_rollouts`` changes the budgets between searches."""
 
     def __init__(self, models: Sequence[Any], *, trees_per_model: int = 1, env_id: int, mode: int, n_rollouts: int, c_uct: float,
                  gamma: float, epsilon: float = 0.0, num_actions: int = 0, c_pw: float = 1.0, kappa: float = 0.5,
                  V_target_policy: str = "off_policy", action_bound: float = 2.0, seed: int = 34, tree_id_base: int = 0,
-                 device_id: int = 0, net_settings: Optional[Sequence[dict]] = None, net_settings_wide: bool = False):
+                 device_id: int = 0, net_settings: Optional[Sequence[dict]] = None, net_settings_wide: bool = False,
+                 net_rollouts: Optional[Sequence[int]] = None):
         from .. import _native   # raises if libazgym_hip.so is missing
 
         self.models = list(models)
@@ -104,7 +111,9 @@ class PopulationMCTS:
         self._shared = dict(c_uct=c_uct, gamma=gamma, epsilon=epsilon, c_pw=c_pw, kappa=kappa)
         self.net_settings: Optional[List[dict]] = None
         self.net_settings_wide = bool(net_settings_wide)
+        self.net_rollouts: Optional[List[int]] = None
         self.trees_per_model = int(trees_per_model)
+        rollouts = None if net_rollouts is None else self._net_budgets(net_rollouts, self.net_settings_wide)
         if net_settings is not None:
             entries = self._net_entries(net_settings, self.net_settings_wide)
             if mode == _capi.MODE_CONTINUOUS:
@@ -118,8 +127,8 @@ class PopulationMCTS:
         self._versions: List[Any] = [None] * self.n_models
         self._cliff_warned = False
         self.last_weight_sync: Optional[str] = None
-        if net_settings is not None:
-            self._push_net_settings(entries, self.net_settings_wide)
+        if net_settings is not None or rollouts is not None:
+            self._push_net_settings(entries if net_settings is not None else None, self.net_settings_wide, rollouts)
         self.sync_weights()
 
     def _net_entries(self, net_settings, wide: bool) -> List[dict]:
@@ -139,23 +148,55 @@ class PopulationMCTS:
                                  f"this model's is {width}. Wider networks search with shared settings only, or with net_settings_wide=True")
         return entries
 
-    def _push_net_settings(self, entries: List[dict], wide: bool) -> None:
+    def _net_budgets(self, net_rollouts, wide: bool) -> List[int]:
+        """``net_rollouts`` checked: one int per model in 1 .. n_rollouts, and the width rules of ``net_settings``."""
+        budgets = list(net_rollouts)
+        if len(budgets) != self.n_models:
+            raise ValueError(f"net_rollouts has {len(budgets)} entries for {self.n_models} models: one per model")
+        for k, n in enumerate(budgets):
+            if int(n) != n or not 1 <= int(n) <= self.n_rollouts:
+                raise ValueError(f"net_rollouts[{k}] = {n!r}: a model's own budget is an int in 1 .. n_rollouts ({self.n_rollouts}, the "
+                                 "engine's capacity)")
+        self._net_entries([{}] * self.n_models, wide)
+        return [int(n) for n in budgets]
+
+    def _push_net_settings(self, entries: Optional[List[dict]], wide: bool, rollouts: Optional[List[int]] = None) -> None:
+        """The table as it now stands goes to the engine: ``entries`` (None: every model's five settings are the shared ones) and
+        ``rollouts`` (None: no budgets -- the calls are those of a table without them)."""
+        table = entries if entries is not None else [dict(self._shared) for _ in range(self.n_models)]
+        kw = {} if rollouts is None else {"n_sims": rollouts}
         if wide:
-            self.engine.set_net_search(entries, wide=True)
+            self.engine.set_net_search(table, wide=True, **kw)
         else:
-            self.engine.set_net_search(entries)
-        self.net_settings, self.net_settings_wide = entries, wide
+            self.engine.set_net_search(table, **kw)
+        self.net_settings, self.net_settings_wide, self.net_rollouts = entries, wide, rollouts
 
     def set_net_settings(self, net_settings: Optional[Sequence[dict]], wide: Optional[bool] = None) -> None:
         """Change the per-model search settings between searches (same rules as the constructor's ``net_settings``); None returns to
-        the shared settings.  ``wide``: as the constructor's ``net_settings_wide`` (None: what the constructor was given).  Every
-        model's widening must fit the engine as it was created (azg_max_children): EngineError otherwise."""
+        the shared settings (per-model budgets, ``net_rollouts``, stay).  ``wide``: as the constructor's ``net_settings_wide`` (None:
+        what the constructor was given).  Every model's widening must fit the engine as it was created (azg_max_children): EngineError
+        otherwise."""
         if net_settings is None:
+            if self.net_rollouts is not None:
+                self._push_net_settings(None, self.net_settings_wide, self.net_rollouts)
+                return
             self.engine.set_net_search(None)
             self.net_settings = None
             return
         wide = self.net_settings_wide if wide is None else bool(wide)
-        self._push_net_settings(self._net_entries(net_settings, wide), wide)
+        self._push_net_settings(self._net_entries(net_settings, wide), wide, self.net_rollouts)
+
+    def set_net_rollouts(self, net_rollouts: Optional[Sequence[int]]) -> None:
+        """Change the per-model simulation budgets between searches (same rules as the constructor's ``net_rollouts``); None: every
+        model runs ``n_rollouts`` again (per-model settings, ``net_settings``, stay)."""
+        if net_rollouts is None:
+            if self.net_settings is not None:
+                self._push_net_settings(self.net_settings, self.net_settings_wide)
+            else:
+                self.engine.set_net_search(None)
+                self.net_rollouts = None
+            return
+        self._push_net_settings(self.net_settings, self.net_settings_wide, self._net_budgets(net_rollouts, self.net_settings_wide))
 
     def sync_weights(self, force: bool = False) -> None:
         """Upload the weights of every model that changed since its last upload (net k = models[k]; after every optimiser step).

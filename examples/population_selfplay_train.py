@@ -12,6 +12,8 @@ in PyTorch between them); --trainer device-fused computes the losses on the devi
 --c-ucts / --gammas / --search-epsilons (and, continuous games, --c-pws / --kappas) sweep the SEARCH's settings over the seeds as --lrs
 sweeps the learning rate: one value per seed, every net still searched in the one launch (PopulationSelfPlay net_settings; hidden widths up
 to 256, and with --wide every width: net_settings_wide=True).
+--n-rollouts-per-seed sweeps the SIMULATION BUDGET the same way: one value in 1 .. --n-rollouts per seed, net k runs its own number of
+simulations per search while --n-rollouts stays the engine's capacity (PopulationSelfPlay net_rollouts); alone or with the sweeps above.
 --layernorm builds every net with LayerNorm after each trunk activation; the device trainers are then built with layernorm=True.
 --wide builds the device trainers with wide=True, which trains nets of up to 8 hidden layers and widths up to 1024 (--hidden 1024
 1024 1024 1024).  The search engine holds several such nets too: nets it searches as teams of 32 trees (padded width >= 512, two or
@@ -64,6 +66,9 @@ def parse_args(argv=None):
     ap.add_argument("--c-pws", type=float, nargs="+", default=None,
                     help="continuous games: a sweep of progressive widening's c_pw, " + sweep + "(the rows are as wide as the widest net's)")
     ap.add_argument("--kappas", type=float, nargs="+", default=None, help="continuous games: a sweep of progressive widening's kappa, " + sweep)
+    ap.add_argument("--n-rollouts-per-seed", type=int, nargs="+", default=None,
+                    help="a sweep of the search's simulation budget, one value in 1 .. --n-rollouts per --seeds entry: net k runs its own "
+                         "number of simulations, all nets still in one search launch per step; --n-rollouts stays the engine's capacity")
     ap.add_argument("--optimizer", choices=["rmsprop", "adam"], default="rmsprop",
                     help="every net's optimiser; adam: the reference's Adam settings (run.ADAM).  With adam or --grad-clip the device "
                          "trainers are built with optimizers='agents'")
@@ -93,6 +98,11 @@ def parse_args(argv=None):
     for flag, vals in search_sweeps(a).items():
         if vals is not None and len(vals) != len(a.seeds):
             ap.error(f"--{flag} needs one value per --seeds entry ({len(a.seeds)}), got {len(vals)}")
+    if a.n_rollouts_per_seed is not None:
+        if len(a.n_rollouts_per_seed) != len(a.seeds):
+            ap.error(f"--n-rollouts-per-seed needs one value per --seeds entry ({len(a.seeds)}), got {len(a.n_rollouts_per_seed)}")
+        if not all(1 <= n <= a.n_rollouts for n in a.n_rollouts_per_seed):
+            ap.error(f"--n-rollouts-per-seed: every budget lies in 1 .. --n-rollouts ({a.n_rollouts}), the engine's capacity")
     why = check_population_shape(a)
     if why:
         ap.error(why)
@@ -114,12 +124,17 @@ def net_settings(a):
 
 
 def search_kwargs(a):
-    """PopulationSelfPlay's keywords for the sweeps given: ``net_settings``, and with --wide the opt-in that lets nets of width >= 512
-    search with them (``net_settings_wide=True``).  No sweep: the shared settings, no keyword."""
+    """PopulationSelfPlay's keywords for the sweeps given: ``net_settings``, ``net_rollouts`` (--n-rollouts-per-seed), and with --wide
+    the opt-in that lets nets of width >= 512 search with them (``net_settings_wide=True``).  No sweep: the shared settings, no keyword."""
+    kw = {}
     settings = net_settings(a)
-    if settings is None:
-        return {}
-    return dict(net_settings=settings, net_settings_wide=True) if a.wide else dict(net_settings=settings)
+    if settings is not None:
+        kw["net_settings"] = settings
+    if getattr(a, "n_rollouts_per_seed", None) is not None:
+        kw["net_rollouts"] = list(a.n_rollouts_per_seed)
+    if kw and a.wide:
+        kw["net_settings_wide"] = True
+    return kw
 
 
 def check_population_shape(a):

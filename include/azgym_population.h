@@ -44,7 +44,15 @@ int azg_population_selfplay_begin(azg_engine* e, const azg_selfplay_config* cfg)
 
 /* Per-net MCTS settings, opt-in: net k searches with nets[k] instead of azg_config's c_uct / gamma / epsilon / c_pw / kappa, in the
  * same single launch -- bit for bit what a one-net engine created with those five values (and tree_id_base + k*T) computes.
- * Everything else stays per engine: n_sims, v_target, tie_break, num_actions, reward_scale, action_bound, seed.
+ * Everything else stays per engine: v_target, tie_break, num_actions, reward_scale, action_bound, seed.
+ * Simulation budgets: nets[k].n_sims gives net k its own number of simulations per search.  0: azg_config.n_sims (what a zeroed field
+ * always meant); 1 .. azg_config.n_sims: net k's own budget; negative or above azg_config.n_sims: AZG_E_INVALID (the message names the
+ * net).  azg_config.n_sims is the engine's CAPACITY: storage, tables, the choice of kernel form and azg_max_records follow it, whatever
+ * the nets' budgets are.  Net k's trees are bit for bit what a one-net engine created with n_sims = nets[k].n_sims, its other settings
+ * and tree_id_base + k*T computes: per-child result columns beyond that engine's own Kmax are empty slots, n_rec is that engine's, a
+ * dumped tree's records beyond n_rec are zero.  The carried root count of a reused discrete root stays bounded by the capacity.
+ * In continuous mode the Kmax rule below counts the children net k's own budget reaches.  One launch costs about what its largest
+ * budget costs: the workgroups / teams of a net with a smaller one leave early.
  * Call it after azg_set_population(e, n_nets); n_nets must equal the population's size (1 for an engine of one net).  NULL / 0
  * returns to azg_config's shared settings; azg_set_population with another size clears the table as well.  The call may be repeated
  * between searches and between self-play steps (azg_selfplay_step searches with the table); it is ordered behind a running search on
@@ -64,7 +72,7 @@ int azg_population_selfplay_begin(azg_engine* e, const azg_selfplay_config* cfg)
  * as per-layer launches, as a population's does. */
 typedef struct azg_net_search {
     int32_t struct_size;     /* sizeof(azg_net_search), checked */
-    int32_t reserved;        /* 0 */
+    int32_t n_sims;          /* net k's simulation budget: 0 = azg_config.n_sims, else 1 .. azg_config.n_sims (was `reserved`, always 0) */
     double c_uct, gamma, epsilon;
     double c_pw, kappa;      /* continuous mode; ignored in discrete mode */
 } azg_net_search;

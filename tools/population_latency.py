@@ -28,7 +28,16 @@ of (b) on the general kernels with the table, so (a=) against (b) is what the me
 Configurations: Pendulum-v1 4x1024 ELU x 200 simulations, CartPole 2x512 ReLU x 100 simulations.  Per split, INTERLEAVED -- every
 measured round runs (a), (a=), (b), (b) again and (c) once, in that order -- medians of kernel / wall ms per search: (a) one engine, a
 table of K distinct c_uct; (a=) the table's entries equal to the shared settings; (b) the same engine without a table, twice, so that
-the spread of two runs of the same thing stands next to a/b; (c) K one-net engines with net k's c_uct, one after another."""
+the spread of two runs of the same thing stands next to a/b; (c) K one-net engines with net k's c_uct, one after another.
+
+--per-net-rollouts: per-net simulation budgets (azg_net_search.n_sims) in one launch; with --wide the wide nets' table forms:
+    python tools/population_latency.py --per-net-rollouts [--wide] [--steps 10] [--warmup 2] [--out profiles/population_latency_rollouts.txt]
+Configurations: CartPole 2x128 x 100 at K = 8 / 64 and Pendulum-v1 2x256 x 200 at K = 4 / 16, 64 trees per net; --wide: Pendulum-v1 4x1024
+x 200 over 1024 trees at 2 / 8 / 32 nets.  The nets' budgets run from the capacity down to 1 in equal steps (rollout_budgets); all five
+settings are the shared ones.  INTERLEAVED rounds, medians of kernel / wall ms per search: (a) one engine, the K distinct budgets;
+(a=) every budget equal to the capacity; (b) the same table without budgets, twice -- (a=) goes in front of that pair in even rounds and
+behind it in odd ones; (c) K one-net engines CREATED with net k's budget, one after another.  Simulations per search are the budgets summed over the trees.  --table-only measures (b) alone, four times per round:
+run under AZG_HIP_LIB=<another build's library> it gives that build's launch of the same table and its own run-to-run spread."""
 import argparse
 import json
 import os
@@ -303,6 +312,117 @@ def measure_wide_per_net(name, K, T, steps, warmup):
     return r
 
 
+def rollout_budgets(capacity, K):
+    """K budgets from the capacity down to 1 in equal steps (K = 1: the capacity)."""
+    if K == 1:
+        return [capacity]
+    return [int(round(capacity - k * (capacity - 1) / (K - 1))) for k in range(K)]
+
+
+def measure_rollouts(name, K, T, steps, warmup, wide, table_only=False):
+    from alphazero_gym_amd import _capi, _native
+    from alphazero_gym_amd.synthetic import make_weights
+    kw, (in_dim, hidden, n_dist, act) = WIDE_CONFIGS[name] if wide else PER_NET_CONFIGS[name][:2]
+    desc = _capi.make_desc(in_dim, hidden, n_dist, act)
+    blobs = [make_weights(34 + k, in_dim, hidden, n_dist) for k in range(K)]
+    shared = dict(c_uct=kw["c_uct"], gamma=kw["gamma"], epsilon=kw.get("epsilon", 0.0), c_pw=kw.get("c_pw", 1.0), kappa=kw.get("kappa", 0.5))
+    budgets = rollout_budgets(kw["n_sims"], K)
+    pop = _native.HipEngine(**dict(kw, n_trees=K * T))
+    pop.set_population(K)
+    for k in range(K):
+        pop.set_net_weights(k, desc, blobs[k])
+    roots = pop.synthetic_roots()
+    singles = []
+    for k in range(0 if table_only else K):
+        e = _native.HipEngine(**dict(kw, n_trees=T, tree_id_base=k * T, n_sims=budgets[k]))
+        e.set_weights(desc, blobs[k])
+        singles.append(e)
+
+    def loop():
+        for k, e in enumerate(singles):
+            e.search(roots[k * T:(k + 1) * T])
+
+    keys = ("b", "b_again", "b_3", "b_4") if table_only else ("a", "a_equal", "b", "b_again", "c")
+    runs = {key: ([], []) for key in keys}
+    names = {}
+
+    def timed(key, search, ms):
+        t0 = time.perf_counter()
+        search()
+        t1 = time.perf_counter()
+        return key, ms(), (t1 - t0) * 1e3
+
+    search = lambda: pop.search(roots)   # noqa: E731
+    def equal_budgets(out):
+        pop.set_net_search([shared] * K, wide=wide, n_sims=[kw["n_sims"]] * K)
+        out.append(timed("a_equal", search, pop.last_search_ms))
+
+    for i in range(warmup + steps):
+        out = []
+        if not table_only:
+            pop.set_net_search([shared] * K, wide=wide, n_sims=budgets)
+            out.append(timed("a", search, pop.last_search_ms))
+            names["a"] = pop.search_info()
+            if i % 2 == 0:   # (a=) and the (b) pair upload the same records: they swap places every round, so that neither always follows (a)
+                equal_budgets(out)
+        pop.set_net_search([shared] * K, wide=wide)
+        for key in keys:
+            if key.startswith("b"):
+                out.append(timed(key, search, pop.last_search_ms))
+        names["b"] = pop.search_info()
+        if not table_only and i % 2 == 1:
+            equal_budgets(out)
+        if not table_only:
+            out.append(timed("c", loop, lambda: sum(e.last_search_ms() for e in singles)))
+        if i >= warmup:
+            for key, kern, wall in out:
+                runs[key][0].append(kern)
+                runs[key][1].append(wall)
+    pop.close()
+    for e in singles:
+        e.close()
+    r = dict(K=K, T=T, capacity=kw["n_sims"], budgets=budgets, sims_per_search_a=sum(budgets) * T, sims_per_search_b=kw["n_sims"] * K * T,
+             b_kernel=names["b"]["kernel_name"], team_fallbacks=sum(n["team_fallbacks"] for n in names.values()))
+    for key, (kern, wall) in runs.items():
+        r[key + "_kernel_ms"], r[key + "_wall_ms"] = round(float(np.median(kern)), 4), round(float(np.median(wall)), 3)
+    return r
+
+
+def main_rollouts(a):
+    what = "widths >= 512, AZG_NET_SEARCH_WIDE; K nets x T trees = 1024 trees" if a.wide else f"{PER_NET_TREES} trees per net"
+    lines = [f"# per-net simulation budgets in one launch (azg_net_search.n_sims; {what}): ms per search, kernel / wall,",
+             f"# medians over {a.steps} interleaved rounds after {a.warmup} warm-up rounds; budgets from the capacity down to 1 in equal steps",
+             "# (a) one engine, K distinct budgets   (a=) every budget equal to the capacity   (b), (b') the same table without budgets, twice per round",
+             "# (round order: a, a=, b, b', c in even rounds and a, b, b', a=, c in odd ones)",
+             "# (c) K one-net engines created with net k's budget, one after another   M sims/s: (a)'s budgets summed over its trees / its kernel time"]
+    if a.table_only:
+        lines = [f"# the table without budgets alone, four launches per round ({what}): kernel ms per search, medians over {a.steps} rounds after "
+                 f"{a.warmup}; library: {os.environ.get('AZG_HIP_LIB') or 'this build'}"]
+    for name in a.configs.split(","):
+        lines.append(f"# {name}")
+        if a.table_only:
+            lines.append(f"# {'K x T':>9} {'(b)':>9} {'(b)':>9} {'(b)':>9} {'(b)':>9} {'max/min':>8}")
+        else:
+            lines.append(f"# {'K x T':>9} {'(a) budgets ms':>20} {'(a=) capacity ms':>20} {'(b) no budgets ms':>20} {'(b) again ms':>20} {'(c) K engines ms':>20} "
+                         f"{'a/b':>7} {'a=/b':>7} {'b/b':>7} {'c/a kern':>9} {'c/a wall':>9} {'(a) M sims/s':>12}")
+        points = parse_splits(a.splits) if a.wide else [(K, PER_NET_TREES) for K in PER_NET_CONFIGS[name][2] if K > 1]
+        for K, T in points:
+            r = measure_rollouts(name, K, T, a.steps, a.warmup, a.wide, a.table_only)
+            if a.table_only:
+                ms = [r[key + "_kernel_ms"] for key in ("b", "b_again", "b_3", "b_4")]
+                lines.append(f"  {K:3d} x {T:4d} " + " ".join(f"{m:9.4f}" for m in ms) + f" {max(ms) / min(ms):7.3f}x")
+            else:
+                cell = lambda key: f"{r[key + '_kernel_ms']:9.4f} / {r[key + '_wall_ms']:8.3f}"   # noqa: E731
+                lines.append(f"  {K:3d} x {T:4d} {cell('a')} {cell('a_equal')} {cell('b')} {cell('b_again')} {cell('c')} "
+                             f"{r['a_kernel_ms'] / r['b_kernel_ms']:6.3f}x {r['a_equal_kernel_ms'] / r['b_kernel_ms']:6.3f}x "
+                             f"{r['b_again_kernel_ms'] / r['b_kernel_ms']:6.3f}x {r['c_kernel_ms'] / r['a_kernel_ms']:8.2f}x "
+                             f"{r['c_wall_ms'] / r['a_wall_ms']:8.2f}x {r['sims_per_search_a'] / r['a_kernel_ms'] / 1e3:12.1f}")
+            lines.append(json.dumps(dict(config=name, **r)))
+            print("\n".join(lines[-2:]), flush=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main_wide_per_net(a):
     lines = ["# per-net MCTS settings of wide nets in one search (azg_set_net_search_ex, AZG_NET_SEARCH_WIDE): ms per search, kernel / wall,",
              f"# medians over {a.steps} interleaved rounds after {a.warmup} warm-up rounds; K nets x T trees = 1024 trees",
@@ -363,24 +483,33 @@ def parse_args(argv=None):
     ap.add_argument("--wide", action="store_true", help="the wide configurations: one engine of K nets against K one-net engines in a loop")
     ap.add_argument("--splits", default=None, help=f"--wide: the K x T points (default {WIDE_SPLITS}; with --per-net {WIDE_PER_NET_SPLITS})")
     ap.add_argument("--per-net", action="store_true", help="per-net MCTS settings: one launch of K settings against shared settings and K engines")
+    ap.add_argument("--per-net-rollouts", action="store_true",
+                    help="per-net simulation budgets: one launch of K budgets against the table without budgets and K engines (also with --wide)")
+    ap.add_argument("--table-only", action="store_true", help="--per-net-rollouts: only the table without budgets, four launches per round")
     ap.add_argument("--out", default=None, help="--per-net: the file the table is written to (default profiles/population_latency_pernet.txt; "
                                                 "with --wide profiles/population_latency_wide_pernet.txt)")
     ap.add_argument("--configs", default=None)
     a = ap.parse_args(argv)
     known = WIDE_CONFIGS if a.wide else PER_NET_CONFIGS if a.per_net else CONFIGS
     profiles = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    if a.per_net_rollouts:
+        known = {"pendulum_4x1024_200": WIDE_CONFIGS["pendulum_4x1024_200"]} if a.wide and not a.configs else known if a.wide else PER_NET_CONFIGS
+        a.out = a.out or os.path.join(profiles, "population_latency_rollouts_wide.txt" if a.wide else "population_latency_rollouts.txt")
     a.out = a.out or os.path.join(profiles, "population_latency_wide_pernet.txt" if a.wide else "population_latency_pernet.txt")
-    a.splits = a.splits or (WIDE_PER_NET_SPLITS if a.per_net else WIDE_SPLITS)
+    a.splits = a.splits or (WIDE_PER_NET_SPLITS if a.per_net or a.per_net_rollouts else WIDE_SPLITS)
     a.configs = a.configs or ",".join(known)
     for name in a.configs.split(","):
         if name not in known:
             ap.error(f"unknown configuration {name!r}: {', '.join(known)}")
     if a.wide:
         try:
-            if any(k < 2 for k, _ in parse_splits(a.splits)) and a.per_net:
+            if any(k < 2 for k, _ in parse_splits(a.splits)) and (a.per_net or a.per_net_rollouts):
                 raise ValueError("--wide --per-net compares K >= 2 nets")
         except ValueError as err:
             ap.error(str(err))
+    if a.per_net_rollouts:
+        a.steps = a.steps if a.steps is not None else 10
+        a.warmup = a.warmup if a.warmup is not None else 2
     a.steps = a.steps if a.steps is not None else (5 if a.wide and not a.per_net else 20)
     a.warmup = a.warmup if a.warmup is not None else (2 if a.wide and not a.per_net else 3)
     return a
@@ -389,6 +518,8 @@ def parse_args(argv=None):
 def main():
     a = parse_args()
     os.environ.setdefault("AZG_QUIET", "1")
+    if a.per_net_rollouts:
+        return main_rollouts(a)
     if a.wide and a.per_net:
         return main_wide_per_net(a)
     if a.wide:
