@@ -122,7 +122,8 @@ SYMBOLS = [
 # them raise
 OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device", "set_net_search",
                     "set_net_search_ex",
-                    "population_selfplay_begin", "policy_rollout", "policy_rollout_ex",
+                    "population_selfplay_begin", "selfplay_keep_states", "selfplay_states", "selfplay_reanalyse",
+                    "policy_rollout", "policy_rollout_ex",
                     "population_mlp_eval", "population_mlp_eval_device", "population_root_eval",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
                     "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch",
@@ -275,6 +276,10 @@ def bind(lib, prefix):
         f["set_population_weights_device"].argtypes = [vp, C.POINTER(AzgMlpDesc), C.c_void_p, C.c_size_t, C.c_int32]
     if "population_selfplay_begin" in f:
         f["population_selfplay_begin"].argtypes = [vp, C.POINTER(AzgSelfplayConfig)]
+    if "selfplay_reanalyse" in f:   # include/azgym_reanalyse.h
+        f["selfplay_keep_states"].argtypes = [vp, C.c_int32]
+        f["selfplay_states"].argtypes = [vp, C.POINTER(C.c_double), C.c_size_t]
+        f["selfplay_reanalyse"].argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.c_uint32]
     if "policy_rollout" in f:   # include/azgym_eval.h
         f["policy_rollout"].argtypes = [vp, C.POINTER(AzgRolloutConfig), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float)]
@@ -832,7 +837,36 @@ def _selfplay_methods():
         self._check(self._f["selfplay_stats"](self._h, _ptr(fsum, C.c_double), _ptr(fcnt, C.c_int32), _ptr(state, C.c_double)))
         return fsum, fcnt, state
 
-    for fn in (selfplay_begin, population_selfplay_begin, selfplay_ring, selfplay_rows_device, selfplay_step, selfplay_rows, selfplay_clear, selfplay_stats):
+    def selfplay_keep_states(self, on=True):
+        """azg_selfplay_keep_states: keep every stored step's float64 env states beside the replay ring (what selfplay_reanalyse
+        searches from).  Right after a begin, while the ring is empty; the next begin drops it."""
+        self._check(self._optional("selfplay_keep_states")(self._h, int(bool(on))))
+
+    def selfplay_states(self):
+        """The kept env states of the stored steps, [steps*B, S_env] float64, ordered like selfplay_rows."""
+        fn = self._optional("selfplay_states")
+        states = np.empty((self._sp_cap * self.n_trees, self.s_env), np.float64)
+        n = fn(self._h, _ptr(states, C.c_double), states.shape[0])
+        if n < 0:
+            self._check(n)
+        return states[:n]
+
+    def selfplay_reanalyse(self, slots=None, search_index=0):
+        """azg_selfplay_reanalyse: search stored positions again with the current weights and settings, under RNG search index
+        ``search_index``, and overwrite their rows' actions | counts | Q | V_target columns (asynchronous).  ``slots``: an int --
+        every game re-searches its position in that ring slot -- or one slot per game, length n_trees (game t rewrites row
+        (slots[t], t)); None is slot 0."""
+        fn = self._optional("selfplay_reanalyse")
+        if slots is None or np.ndim(slots) == 0:
+            self._check(fn(self._h, None, int(0 if slots is None else slots), int(search_index) & 0xFFFFFFFF))
+            return
+        arr = np.ascontiguousarray(slots, dtype=np.int32)
+        if arr.shape != (self.n_trees,):
+            raise ValueError(f"slots: an int or one slot per game (length {self.n_trees}), got shape {arr.shape}")
+        self._check(fn(self._h, _ptr(arr, C.c_int32), 0, int(search_index) & 0xFFFFFFFF))
+
+    for fn in (selfplay_begin, population_selfplay_begin, selfplay_ring, selfplay_rows_device, selfplay_step, selfplay_rows, selfplay_clear, selfplay_stats,
+               selfplay_keep_states, selfplay_states, selfplay_reanalyse):
         setattr(Engine, fn.__name__, fn)
 
 

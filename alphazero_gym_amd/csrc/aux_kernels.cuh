@@ -3,6 +3,9 @@
 // selfplay_kernel16 (at most 16 root children, 16 lanes per game, from MCTS.return_results) and selfplay_kernel (more, continuous
 // mode only, one thread per game, from the published trees).  What follows the pick is selfplay_finish for both, and the game itself
 // is env.cuh's game_obs / game_step, shared with the policy rollouts (rollout.cuh).
+// A row's actions | counts | Q columns and its value target have one definition per form (row_targets16, row_targets), shared by the
+// self-play kernels and by the reanalysis kernels at the end of this file, which rewrite those columns of a stored row from a fresh
+// search of its kept state.
 #pragma once
 #include "records.h"
 #include "env.cuh"
@@ -41,6 +44,7 @@ struct SelfPlay {
     int* t; int* episode; int* fcnt;
     double* ret; double* fsum;
     float* rows;          // this step's block [B][row_len]
+    double* states;       // this step's block of the state ring [B][S] (azg_selfplay_keep_states), NULL: states are not kept
     double* roots; int* carry;
 };
 
@@ -52,6 +56,8 @@ __device__ __forceinline__ void selfplay_finish(const KParams& P, const SelfPlay
     const int S = P.S;
     double root[4] = {0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < S; ++k) root[k] = sp.roots[(size_t)tree * S + k];
+    if (sp.states)   // the state this step's search started from, beside its row
+        for (int k = 0; k < S; ++k) sp.states[(size_t)tree * S + k] = root[k];
     // (the MountainCars' observation is (position, velocity), S_obs = 2; Acrobot: six)
     float obs[8];
     double sn;
@@ -79,27 +85,20 @@ __device__ __forceinline__ void selfplay_finish(const KParams& P, const SelfPlay
     for (int k = 0; k < S; ++k) sp.roots[(size_t)tree * S + k] = ns[k];
 }
 
-// The common case (at most 16 root children: every LDS-tree configuration): 16 lanes per game, lane a = root child a.  The replay
-// row is written by the lanes side by side; totals are row reductions that do not depend on the order (integer sum, maximum,
-// first index of the largest count); everything whose float64 order matters (on-policy target, normaliser sums, the inverse-CDF
-// walk of numpy's random.choice) is added up by the game's first lane in the reference's order, reading the lanes' values by
-// shuffles; that lane also finishes the step (selfplay_finish).  Same arithmetic as selfplay_kernel below (roots with more children)
-// and as the oracle.
-#define SP_TREES 16
-__global__ __launch_bounds__(16 * SP_TREES) void selfplay_kernel16(KParams P, SelfPlay sp) {
-    const int sub = threadIdx.x & 15;
-    const int tree = blockIdx.x * SP_TREES + (threadIdx.x >> 4);
-    if (tree >= P.B) return;
+// Lane `sub` of a game's 16 on the root's children as MCTS.return_results left them (written by the search kernel's epilogue from its
+// LDS-resident trees, or by results_kernel after the lock-step / team kernels): no tree record is read here, so a search need not
+// publish its trees.  Writes the row's actions | counts | Q columns side by side and returns the row's totals; the on-policy value
+// target is added up in the reference's order, reading the lanes' values by shuffles (executed by the whole row: loop bounds are
+// row-uniform).
+struct RootLane { int edge_n, node_n; double Q; float act; bool has; };
+struct RootTotals { int nc, tot, cmax, amax; double qmax, v_target; };
+__device__ __forceinline__ RootTotals row_targets16(const KParams& P, int tree, int sub, float* targets, RootLane& h) {
     const bool cont = P.mode == AZG_MODE_CONTINUOUS;
-    const unsigned gtree = (unsigned)(P.tree_base + tree);
-    const int K = P.res_Kmax, S_obs = sp.S_obs;
-    float* row = sp.rows + (size_t)tree * (S_obs + 3 * K + 1);
-    // The root's children as MCTS.return_results left them (written by the search kernel's epilogue from its LDS-resident trees, or
-    // by results_kernel after the lock-step / team kernels): no tree record is read here, so a search need not publish its trees.
+    const int K = P.res_Kmax;
+    RootTotals r;
     const int nc = P.res_nch[tree];
     // lane a: root child a
     const bool has = sub < nc;
-    struct { int edge_n, node_n; double Q; } h;
     {
         const size_t o = (size_t)tree * K + (sub < K ? sub : 0);
         const int cn = P.res_child_n[o];                   // the child node's visit count, -1: the edge has no child node yet
@@ -107,11 +106,12 @@ __global__ __launch_bounds__(16 * SP_TREES) void selfplay_kernel16(KParams P, Se
         h.Q = has ? P.res_Q[o] : 0.0;
         h.node_n = (has && cn >= 0) ? cn : 0;
     }
-    const float act = has ? (cont ? P.res_actions[(size_t)tree * K + sub] : (float)sub) : 0.0f;
+    h.has = has;
+    h.act = has ? (cont ? P.res_actions[(size_t)tree * K + sub] : (float)sub) : 0.0f;
     if (sub < K) {
-        row[S_obs + sub] = act;
-        row[S_obs + K + sub] = has ? (float)h.edge_n : 0.0f;
-        row[S_obs + 2 * K + sub] = has ? (float)h.Q : 0.0f;
+        targets[sub] = h.act;
+        targets[K + sub] = has ? (float)h.edge_n : 0.0f;
+        targets[2 * K + sub] = has ? (float)h.Q : 0.0f;
     }
     int tot = has ? h.edge_n : 0;
     double qmax = has ? h.Q : -__builtin_huge_val();
@@ -124,15 +124,6 @@ __global__ __launch_bounds__(16 * SP_TREES) void selfplay_kernel16(KParams P, Se
         ckey = ok > ckey ? ok : ckey;
     }
     if (nc == 0) qmax = 0.0;
-    const int cmax = ckey >> 4, amax = 15 - (ckey & 15);
-    // discrete: the lane's unnormalised pi entry (stable_normalizer's x / max(x), to the temperature)
-    double x = 0.0;
-    if (!cont && has) {
-        if (sp.final_selection == AZG_FS_MAX_VALUE) x = h.Q / qmax;
-        else x = sp.ctab ? sp.ctab[(size_t)cmax * (cmax + 1) / 2 + h.edge_n] : (double)h.edge_n / (double)cmax;
-    }
-    // ---- the game's first lane: order-sensitive sums, the final action, the rest of the step (the shuffles are executed by the
-    // whole row: loop bounds are row-uniform)
     double onp = 0.0;
     if (P.res_v_target == AZG_VT_ON_POLICY) {
         if (!cont) {
@@ -144,6 +135,40 @@ __global__ __launch_bounds__(16 * SP_TREES) void selfplay_kernel16(KParams P, Se
             }
         }
     }
+    r.nc = nc; r.tot = tot; r.qmax = qmax; r.cmax = ckey >> 4; r.amax = 15 - (ckey & 15);
+    r.v_target = P.res_v_target == AZG_VT_ON_POLICY ? onp : qmax;
+    return r;
+}
+
+// The common case (at most 16 root children: every LDS-tree configuration): 16 lanes per game, lane a = root child a.  The replay
+// row is written by the lanes side by side (row_targets16); totals are row reductions that do not depend on the order (integer sum,
+// maximum, first index of the largest count); everything whose float64 order matters (on-policy target, normaliser sums, the
+// inverse-CDF walk of numpy's random.choice) is added up by the game's first lane in the reference's order, reading the lanes' values
+// by shuffles; that lane also finishes the step (selfplay_finish).  Same arithmetic as selfplay_kernel below (roots with more
+// children) and as the oracle.
+#define SP_TREES 16
+__global__ __launch_bounds__(16 * SP_TREES) void selfplay_kernel16(KParams P, SelfPlay sp) {
+    const int sub = threadIdx.x & 15;
+    const int tree = blockIdx.x * SP_TREES + (threadIdx.x >> 4);
+    if (tree >= P.B) return;
+    const bool cont = P.mode == AZG_MODE_CONTINUOUS;
+    const unsigned gtree = (unsigned)(P.tree_base + tree);
+    const int K = P.res_Kmax, S_obs = sp.S_obs;
+    float* row = sp.rows + (size_t)tree * (S_obs + 3 * K + 1);
+    RootLane h;
+    const RootTotals rt = row_targets16(P, tree, sub, row + S_obs, h);
+    const int nc = rt.nc, cmax = rt.cmax, amax = rt.amax;
+    const double qmax = rt.qmax;
+    const bool has = h.has;
+    const float act = h.act;
+    // discrete: the lane's unnormalised pi entry (stable_normalizer's x / max(x), to the temperature)
+    double x = 0.0;
+    if (!cont && has) {
+        if (sp.final_selection == AZG_FS_MAX_VALUE) x = h.Q / qmax;
+        else x = sp.ctab ? sp.ctab[(size_t)cmax * (cmax + 1) / 2 + h.edge_n] : (double)h.edge_n / (double)cmax;
+    }
+    // ---- the game's first lane: order-sensitive sums, the final action, the rest of the step (the shuffles are executed by the
+    // whole row: loop bounds are row-uniform)
     int pick = 0;
     if (cont) {
         // ContinuousAgent.act (agents.py:524-535): actions[Qs.argmax()] / actions[counts.argmax()], first index on ties
@@ -188,7 +213,44 @@ __global__ __launch_bounds__(16 * SP_TREES) void selfplay_kernel16(KParams P, Se
     const float pact = __shfl(act, pick, 16);
     const int pnode_n = __shfl(h.node_n, pick, 16);   // (0 where the picked edge has no child node yet)
     if (sub != 0) return;
-    selfplay_finish(P, sp, tree, row, pact, P.res_v_target == AZG_VT_ON_POLICY ? onp : qmax, cont ? 0 : pnode_n);
+    selfplay_finish(P, sp, tree, row, pact, rt.v_target, cont ? 0 : pnode_n);
+}
+
+// A root's child edges in the published (global) trees, for one thread: child a's record id (beyond the last child: record 0, the
+// root itself, so that no read leaves the tree), its record and its action
+struct RootEdges {
+    const KParams& P;
+    size_t tb;
+    int nc;
+    __device__ __forceinline__ RootEdges(const KParams& P_, int tree) : P(P_), tb((size_t)tree * P_.R), nc(P_.hot[(size_t)tree * P_.R].n_child) {}
+    __device__ __forceinline__ int id(int a) const { return a < nc ? (int)P.child[tb * P.Kp + a] : 0; }
+    __device__ __forceinline__ RecL rec(int a) const { return P.hot[tb + id(a)]; }
+    __device__ __forceinline__ float act(int a) const { return P.action[tb + id(a)]; }
+};
+// The row's actions | counts | Q columns from those edges (continuous mode); returns the value target and the first index of the
+// largest count.
+__device__ __forceinline__ double row_targets(const KParams& P, const RootEdges& re, float* targets, int* amax_out) {
+    const int K = P.res_Kmax, nc = re.nc;
+    double qmax = 0.0, onp = 0.0;
+    long tot = 0;
+    int cmax = 0, amax = 0;
+    for (int a = 0; a < nc; ++a) tot += re.rec(a).edge_n;
+    for (int a = 0; a < K; ++a) {
+        const bool has = a < nc;
+        const RecL h = re.rec(a);
+        targets[a] = has ? re.act(a) : 0.0f;
+        targets[K + a] = has ? (float)h.edge_n : 0.0f;
+        targets[2 * K + a] = has ? (float)h.Q : 0.0f;
+        if (has) {
+            if (a == 0 || h.Q > qmax) qmax = h.Q;
+            if (a == 0 || h.edge_n > cmax) { cmax = h.edge_n; amax = a; }
+        }
+    }
+    if (P.res_v_target == AZG_VT_ON_POLICY)
+        for (int a = 0; a < nc; ++a)
+            for (int b = 0; b < nc; ++b) onp += ((double)re.rec(b).edge_n / (double)tot) * re.rec(a).Q;
+    *amax_out = amax;
+    return P.res_v_target == AZG_VT_ON_POLICY ? onp : qmax;
 }
 
 // Roots with more than 16 children: one thread per game, reading the root's child edges from the published (global) trees, so this
@@ -199,44 +261,70 @@ __global__ __launch_bounds__(16 * SP_TREES) void selfplay_kernel16(KParams P, Se
 __global__ __launch_bounds__(SPW_THREADS) void selfplay_kernel(KParams P, SelfPlay sp) {
     const int tree = blockIdx.x * blockDim.x + threadIdx.x;
     if (tree >= P.B) return;
-    const size_t tb = (size_t)tree * P.R;
     const unsigned gtree = (unsigned)(P.tree_base + tree);
     const int K = P.res_Kmax, S_obs = sp.S_obs;
     float* row = sp.rows + (size_t)tree * (S_obs + 3 * K + 1);
-    const int nc = P.hot[tb].n_child;
-    // child a of the root: its record id (beyond the last child: record 0, the root itself, so that no read leaves the tree), its
-    // record and its action
-    auto id = [&](int a) { return a < nc ? (int)P.child[tb * P.Kp + a] : 0; };
-    auto rec = [&](int a) { return P.hot[tb + id(a)]; };
-    auto act = [&](int a) { return P.action[tb + id(a)]; };
-    double qmax = 0.0, onp = 0.0;
-    long tot = 0;
-    int cmax = 0, amax = 0;
-    for (int a = 0; a < nc; ++a) tot += rec(a).edge_n;
-    for (int a = 0; a < K; ++a) {
-        const bool has = a < nc;
-        const RecL h = rec(a);
-        row[S_obs + a] = has ? act(a) : 0.0f;
-        row[S_obs + K + a] = has ? (float)h.edge_n : 0.0f;
-        row[S_obs + 2 * K + a] = has ? (float)h.Q : 0.0f;
-        if (has) {
-            if (a == 0 || h.Q > qmax) qmax = h.Q;
-            if (a == 0 || h.edge_n > cmax) { cmax = h.edge_n; amax = a; }
-        }
-    }
-    if (P.res_v_target == AZG_VT_ON_POLICY)
-        for (int a = 0; a < nc; ++a)
-            for (int b = 0; b < nc; ++b) onp += ((double)rec(b).edge_n / (double)tot) * rec(a).Q;
+    const RootEdges re(P, tree);
+    const int nc = re.nc;
+    int amax = 0;
+    const double v_target = row_targets(P, re, row + S_obs, &amax);
     // ContinuousAgent.act (agents.py:524-535): actions[Qs.argmax()] / actions[counts.argmax()], first index on ties
     int pick = amax;
     if (sp.final_selection == AZG_FS_MAX_VALUE) {
         double qb = 0.0;
-        for (int a = 0; a < nc; ++a) { const double q = rec(a).Q; if (a == 0 || q > qb) { qb = q; pick = a; } }
+        for (int a = 0; a < nc; ++a) { const double q = re.rec(a).Q; if (a == 0 || q > qb) { qb = q; pick = a; } }
     }
     if (sp.agent_eps != 0.0) {
         // epsilon_greedy (agents.py:471-490): random.random() < epsilon -> np.random.choice(actions)
         azg_u32x4 b = azg_draw(P.seed, gtree, sp.step_idx, 0u, AZG_STREAM_ACT);
         if ((double)azg_u01(b.v[0]) < sp.agent_eps) pick = (int)(b.v[1] % (unsigned)nc);
     }
-    selfplay_finish(P, sp, tree, row, act(pick), P.res_v_target == AZG_VT_ON_POLICY ? onp : qmax, 0);
+    selfplay_finish(P, sp, tree, row, re.act(pick), v_target, 0);
+}
+
+// ------------------------------------------------------------------------------------------------ reanalysis of stored rows
+
+// Search stored positions again (azg_selfplay_reanalyse): tree t takes the kept state of its own game column in ring slot slots[t]
+// (NULL: `slot` for every tree) as a fresh root.  slots, when given, is the device copy the host has range-checked.
+struct Reanalyse {
+    const int* slots;
+    int slot;
+    int S_obs;
+    const double* states;   // the state ring [capacity_steps][B][S]
+    float* rows;            // the replay ring [capacity_steps][B][row_len]
+    double* roots; int* carry;   // the search's staging roots [B][S] and carried counts [B] (zero)
+};
+__device__ __forceinline__ int reanalyse_slot(const Reanalyse& ra, int tree) { return ra.slots ? ra.slots[tree] : ra.slot; }
+__device__ __forceinline__ float* reanalyse_row(const KParams& P, const Reanalyse& ra, int tree) {
+    return ra.rows + ((size_t)reanalyse_slot(ra, tree) * P.B + tree) * (size_t)(ra.S_obs + 3 * P.res_Kmax + 1);
+}
+
+#define RA_THREADS 256
+__global__ __launch_bounds__(RA_THREADS) void reanalyse_gather_kernel(KParams P, Reanalyse ra) {
+    const int tree = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tree >= P.B) return;
+    const double* src = ra.states + ((size_t)reanalyse_slot(ra, tree) * P.B + tree) * P.S;
+    for (int k = 0; k < P.S; ++k) ra.roots[(size_t)tree * P.S + k] = src[k];
+    ra.carry[tree] = 0;
+}
+
+// The two self-play kernels without the pick, the env step and the books: the target columns of row (slot, tree) from the search that
+// just ran.  The observation columns stay; every row has one writer.
+__global__ __launch_bounds__(16 * SP_TREES) void reanalyse_kernel16(KParams P, Reanalyse ra) {
+    const int sub = threadIdx.x & 15;
+    const int tree = blockIdx.x * SP_TREES + (threadIdx.x >> 4);
+    if (tree >= P.B) return;
+    float* row = reanalyse_row(P, ra, tree);
+    RootLane h;
+    const RootTotals rt = row_targets16(P, tree, sub, row + ra.S_obs, h);
+    if (sub == 0) row[ra.S_obs + 3 * P.res_Kmax] = (float)rt.v_target;
+}
+__global__ __launch_bounds__(SPW_THREADS) void reanalyse_kernel(KParams P, Reanalyse ra) {
+    const int tree = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tree >= P.B) return;
+    float* row = reanalyse_row(P, ra, tree);
+    const RootEdges re(P, tree);
+    int amax = 0;
+    const double v_target = row_targets(P, re, row + ra.S_obs, &amax);
+    row[ra.S_obs + 3 * P.res_Kmax] = (float)v_target;
 }

@@ -97,6 +97,20 @@ int settle_team(azg_engine* e) {
     return team_check(e);
 }
 
+// What azg_search_resident refuses before it launches anything (azg_selfplay_reanalyse asks first, before its own launches)
+int search_refusal(azg_engine* e) {
+    if (!e->mlp_ready)
+        return fail(e, AZG_E_STATE, e->n_nets > 1 ? "azg_set_net_weights has not been called for every net of the population"
+                                                 : "azg_set_weights has not been called");
+    // a table set through azg_set_net_search is searched at widths up to 256 only; the team kernel, the per-layer launches and the wide
+    // networks' one-launch kernels take one that came with AZG_NET_SEARCH_WIDE
+    if (e->net_search.rec && e->HP >= 512 && !e->net_search_wide)
+        return fail(e, AZG_E_UNSUPPORTED, "per-net search settings (azg_set_net_search) need a padded hidden width of at most 256: nets of width >= 512 "
+                                          "search with the engine's shared settings (azg_set_net_search(e, NULL, 0) returns to them), or with a table "
+                                          "set through azg_set_net_search_ex with AZG_NET_SEARCH_WIDE");
+    return AZG_OK;
+}
+
 // Per environment (AZG_ENV_*): float64 words of a state, network inputs, discrete actions (0: a continuous-action env)
 struct EnvFacts { int state_words, obs_width, discrete, n_actions; };
 static constexpr EnvFacts kEnv[AZG_ENV_ACROBOT + 1] = {
@@ -334,15 +348,7 @@ int azg_upload_roots(azg_engine* e, const double* roots, const int32_t* carry) {
 
 int azg_search_resident(azg_engine* e) {
     if (!e) return AZG_E_INVALID;
-    if (!e->mlp_ready)
-        return fail(e, AZG_E_STATE, e->n_nets > 1 ? "azg_set_net_weights has not been called for every net of the population"
-                                                 : "azg_set_weights has not been called");
-    // a table set through azg_set_net_search is searched at widths up to 256 only; the team kernel, the per-layer launches and the wide
-    // networks' one-launch kernels take one that came with AZG_NET_SEARCH_WIDE
-    if (e->net_search.rec && e->HP >= 512 && !e->net_search_wide)
-        return fail(e, AZG_E_UNSUPPORTED, "per-net search settings (azg_set_net_search) need a padded hidden width of at most 256: nets of width >= 512 "
-                                          "search with the engine's shared settings (azg_set_net_search(e, NULL, 0) returns to them), or with a table "
-                                          "set through azg_set_net_search_ex with AZG_NET_SEARCH_WIDE");
+    { int rrc = search_refusal(e); if (rrc) return rrc; }
     ON_DEVICE(e);
     e->P.search_idx = e->search_idx;
     e->last_search_idx = e->search_idx;

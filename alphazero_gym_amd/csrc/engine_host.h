@@ -113,6 +113,10 @@ struct azg_engine : EngineQueue {
     uint32_t sp_step_idx = 0;
     int* d_sp_t = nullptr; int* d_sp_episode = nullptr; int* d_sp_fcnt = nullptr; double* d_sp_ret = nullptr; double* d_sp_fsum = nullptr;
     float* d_sp_rows = nullptr;
+    // azg_selfplay_keep_states: the stored steps' env states beside the rows [sp_cap][n_trees][S_env] (NULL: not kept; _mem: the allocation), and what a
+    // reanalysis searches from: staging roots [n_trees][S_env], zero carried counts and the device copy of its slots [n_trees]
+    double* d_sp_states = nullptr; double* d_sp_states_mem = nullptr; double* d_ra_roots = nullptr; int* d_ra_carry = nullptr; int* d_ra_slots = nullptr;
+    std::vector<int32_t> ra_slots;   // host side of d_ra_slots (outlives the asynchronous copy)
     DeviceAllocs sp_mem;
     unsigned* d_team_cnt = nullptr; size_t team_cnt_bytes = 0;   // team kernel: hand-off counters + abort word
     int team_pending = 0;    // a team kernel has been launched since its abort word was last read
@@ -173,6 +177,9 @@ static int dalloc(azg_engine* e, DeviceAllocs& mem, T** p, size_t n) {
 // An abandoned team search (team_pending) is redone before anything reads its trees or changes its inputs: synchronises the stream
 // and re-runs the search where the team kernel gave up; nothing, and no synchronisation, when no team kernel is pending (azg_engine.hip)
 int settle_team(azg_engine* e);
+// What azg_search_resident refuses before it launches anything: weights not set, a settings table on wide nets without the wide flag
+// (azg_engine.hip)
+int search_refusal(azg_engine* e);
 // return_results of the last search on e->stream where the search kernel did not write them itself (engine_selfplay.hip)
 int launch_results(azg_engine* e);
 

@@ -1,9 +1,11 @@
-// engine_selfplay.hip -- the C ABI's device-resident self-play (azg_selfplay_*, azg_population_selfplay_begin) and the launches of the
-// small kernels after a search: results_kernel and the self-play step (aux_kernels.cuh is compiled in this unit only).
+// engine_selfplay.hip -- the C ABI's device-resident self-play (azg_selfplay_*, azg_population_selfplay_begin), the reanalysis of its
+// replay ring (azgym_reanalyse.h) and the launches of the small kernels after a search: results_kernel, the self-play step and the
+// reanalysis' gather and row kernels (aux_kernels.cuh is compiled in this unit only).
 #include <cmath>
 #include <cstring>
 
 #include "engine_host.h"
+#include "../../include/azgym_reanalyse.h"
 #include "mlp.cuh"
 #include "aux_kernels.cuh"
 
@@ -39,6 +41,7 @@ static int selfplay_begin_impl(azg_engine* e, const azg_selfplay_config* c) {
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->sp_mem.clear();
     e->sp_on = 0;
+    e->d_sp_states = e->d_sp_states_mem = nullptr;   // (azg_selfplay_keep_states is asked for again after every begin)
     const size_t B = e->cfg.n_trees;
     e->sp_row = e->S_obs + 3 * e->Kmax + 1;
     if (dalloc(e, e->sp_mem, &e->d_sp_t, B) || dalloc(e, e->sp_mem, &e->d_sp_episode, B) || dalloc(e, e->sp_mem, &e->d_sp_fcnt, B) ||
@@ -116,6 +119,7 @@ int azg_selfplay_step(azg_engine* e) {
     sp.final_selection = e->sp_fs; sp.agent_eps = e->sp_agent_eps; sp.ctab = e->d_sp_ctab;
     sp.t = e->d_sp_t; sp.episode = e->d_sp_episode; sp.fcnt = e->d_sp_fcnt; sp.ret = e->d_sp_ret; sp.fsum = e->d_sp_fsum;
     sp.rows = e->d_sp_rows + (size_t)slot * e->cfg.n_trees * e->sp_row;
+    sp.states = e->d_sp_states ? e->d_sp_states + (size_t)slot * e->cfg.n_trees * e->S_env : nullptr;
     sp.roots = e->d_roots; sp.carry = e->d_carry;
     const int B = e->cfg.n_trees;
     e->redo_ok = 0;   // (the step moves the roots on: the search that just ran cannot be re-run for a dump)
@@ -171,6 +175,88 @@ int azg_selfplay_stats(azg_engine* e, double* fsum, int32_t* fcnt, double* env_s
     D2H(fsum, e->d_sp_fsum, B * 8);
     D2H(fcnt, e->d_sp_fcnt, B * 4);
     D2H(env_state, e->d_roots, B * e->S_env * 8);
+    return AZG_OK;
+}
+
+// ---- reanalysis (include/azgym_reanalyse.h)
+
+int azg_selfplay_keep_states(azg_engine* e, int32_t on) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (e->sp_steps != 0) return fail(e, AZG_E_STATE, "azg_selfplay_keep_states: the replay ring is not empty (call it right after begin, or after clearing the rows)");
+    if (!on) { e->d_sp_states = nullptr; return AZG_OK; }   // (the memory goes with the next begin)
+    if (e->d_sp_states) return AZG_OK;
+    ON_DEVICE(e);
+    const size_t B = e->cfg.n_trees, S = e->S_env;
+    if (!e->d_sp_states_mem &&   // (switched off and on again within one begin: the ring is still there)
+        (dalloc(e, e->sp_mem, &e->d_sp_states_mem, (size_t)e->sp_cap * B * S) || dalloc(e, e->sp_mem, &e->d_ra_roots, B * S) ||
+         dalloc(e, e->sp_mem, &e->d_ra_carry, B) || dalloc(e, e->sp_mem, &e->d_ra_slots, B))) {
+        e->d_sp_states_mem = nullptr;
+        return AZG_E_DEVICE;
+    }
+    e->d_sp_states = e->d_sp_states_mem;
+    return AZG_OK;
+}
+
+int azg_selfplay_states(azg_engine* e, double* states, size_t max_rows) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (!e->d_sp_states) return fail(e, AZG_E_STATE, "azg_selfplay_keep_states has not been called");
+    ON_DEVICE(e);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    size_t n = (size_t)e->sp_steps * e->cfg.n_trees;
+    if (n > max_rows) n = max_rows;
+    if (states && n) HIPCHK(e, hipMemcpy(states, e->d_sp_states, n * e->S_env * 8, hipMemcpyDeviceToHost));
+    return (int)n;
+}
+
+int azg_selfplay_reanalyse(azg_engine* e, const int32_t* slots, int32_t slot, uint32_t search_index) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (!e->d_sp_states) return fail(e, AZG_E_STATE, "azg_selfplay_keep_states has not been called: the stored positions' env states were not kept");
+    const int B = e->cfg.n_trees;
+    for (int t = 0; t < (slots ? B : 1); ++t) {
+        const int s = slots ? slots[t] : slot;
+        if (s < 0 || s >= e->sp_steps) return fail(e, AZG_E_INVALID, "azg_selfplay_reanalyse: slot " + std::to_string(s) + " is not a stored step (size_steps " + std::to_string(e->sp_steps) + ")");
+    }
+    if (e->Kmax > 16 && e->cfg.mode != AZG_MODE_CONTINUOUS)   // (as azg_selfplay_step: cannot happen)
+        return fail(e, AZG_E_STATE, "device self-play with more than 16 actions per node supports continuous mode only");
+    int rc = search_refusal(e);
+    if (rc) return rc;
+    ON_DEVICE(e);
+    rc = settle_team(e);   // (an abandoned team search is redone on the roots it was started with, before this one's take their place)
+    if (rc) return rc;
+    Reanalyse ra;
+    ra.slots = nullptr; ra.slot = slot; ra.S_obs = e->S_obs;
+    ra.states = e->d_sp_states; ra.rows = e->d_sp_rows; ra.roots = e->d_ra_roots; ra.carry = e->d_ra_carry;
+    if (slots) {
+        e->ra_slots.assign(slots, slots + B);
+        HIPCHK(e, hipMemcpyAsync(e->d_ra_slots, e->ra_slots.data(), (size_t)B * 4, hipMemcpyHostToDevice, e->stream));
+        ra.slots = e->d_ra_slots;
+    }
+    hipLaunchKernelGGL(reanalyse_gather_kernel, dim3((B + RA_THREADS - 1) / RA_THREADS), dim3(RA_THREADS), 0, e->stream, e->P, ra);
+    HIPCHK(e, hipGetLastError());
+    // One ordinary search from the staging roots (fresh roots: no carried count) under search_index.  The live games' roots and
+    // carried counts are not touched -- the kernels read KParams' pointers -- and the running search index comes back; an abandoned
+    // team search is redone while the staging roots are still the engine's.
+    const double* const live_roots = e->P.roots;
+    const int* const live_carry = e->P.carry;
+    const int live_carry_max = e->carry_max;
+    const uint32_t idx_now = e->search_idx;
+    e->P.roots = e->d_ra_roots; e->P.carry = e->d_ra_carry; e->carry_max = 0; e->search_idx = search_index;
+    rc = azg_search_resident(e);
+    if (!rc) rc = settle_team(e);
+    e->P.roots = live_roots; e->P.carry = live_carry; e->carry_max = live_carry_max; e->search_idx = idx_now;
+    if (rc) return rc;
+    e->redo_ok = 0;   // (the roots are the live games' again: the search that just ran cannot be re-run for a dump)
+    if (e->Kmax <= 16) {
+        rc = launch_results(e);
+        if (rc) return rc;
+        hipLaunchKernelGGL(reanalyse_kernel16, dim3((B + SP_TREES - 1) / SP_TREES), dim3(16 * SP_TREES), 0, e->stream, e->P, ra);
+    } else {
+        hipLaunchKernelGGL(reanalyse_kernel, dim3((B + SPW_THREADS - 1) / SPW_THREADS), dim3(SPW_THREADS), 0, e->stream, e->P, ra);   // (reads the trees)
+    }
+    HIPCHK(e, hipGetLastError());
     return AZG_OK;
 }
 

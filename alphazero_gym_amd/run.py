@@ -301,6 +301,10 @@ class BatchedSelfPlay:
 # evaluate()'s default game ids start here: far above any self-play game, and the same for every engine and rank, so that
 # separately evaluated nets see the same start states too
 EVAL_GAME_ID_BASE = 1 << 30
+# reanalysis searches draw their RNG search indices from a counter of their own that starts here, far above any self-play step's
+# (a step's search runs under the engine's running index, which counts up from 0): no reanalysis shares an index with a self-play
+# search of the same tree
+REANALYSE_INDEX_BASE = 1 << 31
 
 
 class PopulationSelfPlay:
@@ -315,14 +319,16 @@ class PopulationSelfPlay:
     action rules run on the device too: ``final_selection`` "max_visit" / "max_value", discrete ``temperature`` and
     ``deterministic``, continuous ``agent_epsilon`` (agents.py:294-301, 524-535; include/azgym.h).  ``fifo=True`` turns the
     replay ring into the reference's overwrite-the-oldest buffer (buffers.py:75-82).  Weights are re-uploaded only when some
-    policy changed (``PopulationMCTS.sync_weights``; ``last_weight_sync``: "device", "host" or None when nothing changed)."""
+    policy changed (``PopulationMCTS.sync_weights``; ``last_weight_sync``: "device", "host" or None when nothing changed).
+    ``reanalyse=True`` keeps every stored step's env states beside the ring, so that ``reanalyse()`` can search stored positions
+    again with the current weights and overwrite their rows' targets."""
 
     def __init__(self, policies, *, game: str, games_per_net: int, n_rollouts: int, c_uct: float, gamma: float = 1.0, epsilon: float = 0.0,
                  c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
                  deterministic: bool = False, capacity_steps: int = 64, seed: int = 34, tree_id_base: int = 0, device_id: int = 0,
                  final_selection: str = "max_visit", temperature: float = 1.0, agent_epsilon: float = 0.0, fifo: bool = False,
                  net_settings: Optional[List[dict]] = None, net_settings_wide: Optional[bool] = None,
-                 net_rollouts: Optional[List[int]] = None):
+                 net_rollouts: Optional[List[int]] = None, reanalyse: bool = False):
         policies = list(policies)
         if not policies or games_per_net < 1:
             raise ValueError(f"{type(self).__name__} needs at least one policy and games_per_net >= 1")
@@ -346,6 +352,11 @@ class PopulationSelfPlay:
         begin = self.engine.selfplay_begin if self.n_nets == 1 else self.engine.population_selfplay_begin
         begin(max_episode_length, deterministic, capacity_steps, final_selection=final_selection, temperature=temperature,
               agent_epsilon=agent_epsilon, fifo=fifo)
+        self.reanalysing = bool(reanalyse)
+        self._reanalyse_index = REANALYSE_INDEX_BASE
+        self._reanalyse_rng = np.random.default_rng(seed)
+        if self.reanalysing:
+            self.engine.selfplay_keep_states(True)
 
     @staticmethod
     def _search(policies, games_per_net: int, **kw) -> PopulationMCTS:
@@ -368,6 +379,30 @@ class PopulationSelfPlay:
         self.sync_weights()
         for _ in range(n_steps):
             self.engine.selfplay_step()
+
+    def reanalyse(self, slots=None, n: int = 1, rng: Optional[np.random.Generator] = None) -> list:
+        """MuZero's Reanalyse on the device ring: search stored positions again with the CURRENT weights (pending uploads are
+        applied first, as ``play`` does) and overwrite their rows' actions | counts | Q | V_target; observations, the live games
+        and the ring's books stay as they are (asynchronous: launches only).  ``slots`` None: ``n`` stored slots (at most the
+        ring's size) chosen uniformly without replacement by ``rng`` (default: this object's generator, seeded from the engine
+        seed); a list of slots: each is reanalysed for every game; one ``[n_games]`` integer array: a single search in which game
+        t re-searches its position in slot ``slots[t]``.  Every search takes the next index of a counter that starts at
+        ``REANALYSE_INDEX_BASE``.  Returns the slots used (the per-game array: a one-element list holding it)."""
+        if not self.reanalysing:
+            raise RuntimeError(f"{type(self).__name__}.reanalyse needs the stored positions' env states: create it with reanalyse=True")
+        self.sync_weights()
+        if slots is None:
+            size = self.engine.selfplay_ring()[0]
+            gen = self._reanalyse_rng if rng is None else rng
+            used = [int(s) for s in gen.choice(size, size=min(int(n), size), replace=False)] if size else []
+        elif isinstance(slots, np.ndarray) and slots.ndim == 1 and slots.shape[0] == self.n_games:
+            used = [np.ascontiguousarray(slots, dtype=np.int32)]
+        else:
+            used = [int(s) for s in slots]
+        for s in used:
+            self.engine.selfplay_reanalyse(s, search_index=self._reanalyse_index)
+            self._reanalyse_index += 1
+        return used
 
     def play_device(self, n_steps: int):
         """``play`` for a consumer that reads the ring where it lies (``PopulationTrainer.train_epoch_ring``): returns the ring's

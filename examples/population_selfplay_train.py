@@ -22,6 +22,12 @@ seed -- --seeds 3 11 --hidden 512 512 --wide --games-per-seed 32 -- and every ot
 together build the trainers with wide_layernorm=True: wide nets with LayerNorm.  --eval-episodes works at every width: wide nets are
 rolled out on the device too, all seeds in one call (--seeds 3 11 --hidden 512 512 --wide --games-per-seed 32 --eval-episodes 32).
 
+--replay-steps R keeps the newest R self-play steps in the device ring across iterations (the reference's overwrite-the-oldest
+buffer, PopulationSelfPlay fifo=True) and every iteration trains on rows picked from all of them, instead of on the iteration's own
+steps; it needs the nets on the GPU.  --reanalyse-slots N then searches N random stored steps again with the current weights before
+each iteration's training and overwrites their targets (PopulationSelfPlay.reanalyse: MuZero's Reanalyse, on the device).  It applies
+where rows stay in the ring -- --replay-steps, or --trainer device-epoch -- and is refused elsewhere.
+
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
 Seed k sets net k's initial weights (torch.manual_seed), and its own np.random.RandomState picks the training rows and the
@@ -92,7 +98,16 @@ def parse_args(argv=None):
                          "one call (PopulationSelfPlay.evaluate; any width, --wide nets included) and add the per-seed mean return as "
                          "eval_return; every seed starts from the same states, so the numbers can be ranked (0: no evaluation)")
     ap.add_argument("--eval-rule", choices=["mode", "sample"], default="mode", help="the evaluation's action rule")
+    ap.add_argument("--replay-steps", type=int, default=0,
+                    help="keep the newest R self-play steps in the device ring across iterations (FIFO) and train on rows picked from all "
+                         "of them (0: every iteration trains on its own steps and clears the ring); R >= --steps-per-iter, nets on the GPU")
+    ap.add_argument("--reanalyse-slots", type=int, default=0,
+                    help="before each iteration's training, search this many random stored steps again with the current weights and "
+                         "overwrite their targets (0: off); with --replay-steps or --trainer device-epoch")
     a = ap.parse_args(argv)
+    why = check_replay(a)
+    if why:
+        ap.error(why)
     if a.lrs is not None and len(a.lrs) != len(a.seeds):
         ap.error(f"--lrs needs one value per --seeds entry ({len(a.seeds)}), got {len(a.lrs)}")
     for flag, vals in search_sweeps(a).items():
@@ -137,6 +152,20 @@ def search_kwargs(a):
     return kw
 
 
+def check_replay(a):
+    """Why --replay-steps / --reanalyse-slots cannot be honoured as given (None: they can)."""
+    if a.replay_steps < 0 or a.reanalyse_slots < 0:
+        return "--replay-steps and --reanalyse-slots must be >= 0"
+    if a.replay_steps and a.replay_steps < a.steps_per_iter:
+        return f"--replay-steps ({a.replay_steps}) must hold at least one iteration's steps (--steps-per-iter {a.steps_per_iter})"
+    if a.replay_steps and not a.device.startswith("cuda"):
+        return "--replay-steps trains from the device ring where it lies: it needs --device cuda"
+    if a.reanalyse_slots and not (a.replay_steps or a.trainer == "device-epoch"):
+        return ("--reanalyse-slots rewrites rows that stay in the device ring: use it with --replay-steps R (the FIFO ring) or with "
+                "--trainer device-epoch; the other modes copy the rows out and clear the ring every iteration")
+    return None
+
+
 def check_population_shape(a):
     """Why the search engine would refuse this population (None: it takes it): several nets that it searches as teams of 32 trees
     need a multiple of 32 games each (_capi.lockstep_shaped).  Asked before anything is built."""
@@ -161,7 +190,8 @@ def build_population(a):
     sp = run.PopulationSelfPlay([ag.nn for ag in agents], game=a.game, games_per_net=a.games_per_seed, n_rollouts=a.n_rollouts,
                                 c_uct=m.c_uct, gamma=m.gamma, epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0),
                                 kappa=getattr(m, "kappa", 0.5), max_episode_length=a.max_episode_length,
-                                capacity_steps=a.steps_per_iter, seed=a.engine_seed,
+                                capacity_steps=getattr(a, "replay_steps", 0) or a.steps_per_iter, fifo=bool(getattr(a, "replay_steps", 0)),
+                                reanalyse=getattr(a, "reanalyse_slots", 0) > 0, seed=a.engine_seed,
                                 device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0, **search_kwargs(a))
     return agents, state_dim, sp
 
@@ -182,6 +212,8 @@ def train(a, log=print, on_rows=None, on_end=None):
                                     per_net=a.lrs is not None,
                                     layernorm=a.layernorm and not a.wide, wide=a.wide and not a.layernorm,
                                     wide_layernorm=a.wide and a.layernorm)
+    replay_steps, reanalyse_slots = getattr(a, "replay_steps", 0), getattr(a, "reanalyse_slots", 0)
+    ring_view = None
     t0 = time.time()
     history = []
     for it in range(a.iters):
@@ -189,7 +221,17 @@ def train(a, log=print, on_rows=None, on_end=None):
         if a.trainer == "device-epoch":   # the rows stay in the ring
             rows = None
             n_ring = sp.play_device(a.steps_per_iter)[0] * sp.games_per_net
+            if reanalyse_slots:   # stored steps searched again with the weights as last trained: fresh targets, same observations
+                sp.reanalyse(n=reanalyse_slots)
             sp.engine.sync()
+        elif replay_steps:   # the FIFO ring: the newest replay_steps steps, every net's rows read where they lie
+            if ring_view is None:
+                from alphazero_gym_amd.agent.buffers import DeviceReplay
+                ring_view = DeviceReplay(sp.engine, 1)
+            size = sp.play_device(a.steps_per_iter)[0]
+            if reanalyse_slots:
+                sp.reanalyse(n=reanalyse_slots)
+            rows = sp._split(ring_view.rows(), size)
         else:
             rows = sp.collect_device(a.steps_per_iter) if on_gpu else sp.collect(a.steps_per_iter)
         t2 = time.time()
@@ -206,7 +248,8 @@ def train(a, log=print, on_rows=None, on_end=None):
                 pick = rng.choice(n_ring, size=min(a.train_rows, n_ring), replace=False)
                 order.append(pick[np.random.RandomState(int(rng.randint(2 ** 31 - 1))).permutation(len(pick))])
             infos = trainer.train_epoch_ring(sp, np.stack(order), batch_size=a.batch_size)
-            sp.engine.selfplay_clear()
+            if not replay_steps:
+                sp.engine.selfplay_clear()
             losses = [info["loss"] / max(1, len(order[0]) // a.batch_size) for info in infos]
         elif trainer is None:
             for agent, rng, r in zip(agents, rngs, rows):

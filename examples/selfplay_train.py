@@ -9,6 +9,10 @@ and re-syncs the weights into the engine.
 
 Prints the mean return of the episodes finished in each iteration (one JSON line per iteration).
 
+--replay-steps R keeps the newest R self-play steps in the device ring across iterations (the reference's overwrite-the-oldest buffer)
+and trains on rows picked from all of them; --reanalyse-slots N then searches N random stored steps again with the current weights
+before each iteration's training and overwrites their targets (DeviceSelfPlay.reanalyse).  One process, policy on the GPU.
+
 Multi-GPU (one process per GPU, RCCL):  python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
     examples/selfplay_train.py ...    Every rank plays --games games of its own (global game ids rank*games ...), the replay
 rows are all-gathered, rank 0 runs the optimiser step and broadcasts the weights (alphazero_gym_amd/distributed.py)."""
@@ -65,7 +69,23 @@ def parse_args(argv=None):
     ap.add_argument("--layernorm", action="store_true", help="LayerNorm after every trunk activation (the reference's policy.layernorm)")
     ap.add_argument("--seed", type=int, default=34)
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
-    return ap.parse_args(argv)
+    ap.add_argument("--replay-steps", type=int, default=0,
+                    help="keep the newest R self-play steps in the device ring across iterations (FIFO) and train on rows picked from all "
+                         "of them (0: every iteration trains on its own steps); R >= --steps-per-iter, one process, --device cuda")
+    ap.add_argument("--reanalyse-slots", type=int, default=0,
+                    help="before each iteration's training, search this many random stored steps again with the current weights and "
+                         "overwrite their targets (0: off); needs --replay-steps")
+    a = ap.parse_args(argv)
+    if a.replay_steps < 0 or a.reanalyse_slots < 0:
+        ap.error("--replay-steps and --reanalyse-slots must be >= 0")
+    if a.replay_steps and a.replay_steps < a.steps_per_iter:
+        ap.error(f"--replay-steps ({a.replay_steps}) must hold at least one iteration's steps (--steps-per-iter {a.steps_per_iter})")
+    if a.replay_steps and (not a.device.startswith("cuda") or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--replay-steps trains from the device ring where it lies: one process with --device cuda")
+    if a.reanalyse_slots and not a.replay_steps:
+        ap.error("--reanalyse-slots rewrites rows that stay in the device ring: use it with --replay-steps R (the FIFO ring); without it "
+                 "every iteration copies its rows out and clears the ring")
+    return a
 
 
 def train(a, log=print):
@@ -77,9 +97,11 @@ def train(a, log=print):
     agent, state_dim = build_agent(a.game, a.hidden, a.n_rollouts, a.device, a.lr, a.optimizer, a.grad_clip, a.layernorm)
     continuous = state_dim == 3
     m = agent.mcts
+    replay_steps, reanalyse_slots = getattr(a, "replay_steps", 0), getattr(a, "reanalyse_slots", 0)
     sp = run.DeviceSelfPlay(agent.nn, game=a.game, n_games=a.games, n_rollouts=a.n_rollouts, c_uct=m.c_uct, gamma=m.gamma,
                             epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0), kappa=getattr(m, "kappa", 0.5),
-                            max_episode_length=a.max_episode_length, capacity_steps=a.steps_per_iter, seed=a.seed, rank=rank,
+                            max_episode_length=a.max_episode_length, capacity_steps=replay_steps or a.steps_per_iter, fifo=bool(replay_steps),
+                            reanalyse=reanalyse_slots > 0, seed=a.seed, rank=rank,
                             device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0)
     K = sp.engine.kmax if continuous else 2
     rng = np.random.RandomState(a.seed)
@@ -91,7 +113,13 @@ def train(a, log=print):
     on_gpu = a.device.startswith("cuda")
     replay = sp.replay(a.batch_size) if on_gpu else None
     for it in range(a.iters):
-        rows = sp.collect_device(a.steps_per_iter, replay) if on_gpu else sp.collect(a.steps_per_iter)
+        if replay_steps:   # the FIFO ring: the newest replay_steps steps stay where they lie, all of them are this iteration's rows
+            sp.play(a.steps_per_iter)
+            if reanalyse_slots:   # stored steps searched again with the weights as last trained: fresh targets, same observations
+                sp.reanalyse(n=reanalyse_slots)
+            rows = replay.rows()
+        else:
+            rows = sp.collect_device(a.steps_per_iter, replay) if on_gpu else sp.collect(a.steps_per_iter)
         if world > 1:
             # every rank plays a.games games for steps_per_iter steps: equal blocks, known without a length exchange (whatever a.games
             # and the world size are: the job as a whole plays a.games * world games)
