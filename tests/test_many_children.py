@@ -391,7 +391,7 @@ def test_device_trainer_refuses_rows_of_20_actions_untouched():
     from alphazero_gym_amd import run
     from alphazero_gym_amd.agent.buffers import DeviceReplay
     from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
-    from test_population_train_epoch import assert_same, make_agents, state_of
+    from trainer_util import assert_same, make_agents, state_of
     K, T, steps = 2, 4, 3
     agents = make_agents("gmm2", "a0c_tuned", K)
     sp = run.PopulationSelfPlay([a.nn for a in agents], game="Pendulum-v1", games_per_net=T, n_rollouts=24, c_uct=0.05, c_pw=4.0,

@@ -2,7 +2,6 @@
 d_raw and the loss values against float64 autograd with float32 PyTorch as the yardstick, determinism and population invariance
 bit for bit, the learned temperature's Adam step, the end-to-end update against the losses="torch" path, the ABI's errors and
 the example."""
-import ctypes as C
 import os
 import sys
 
@@ -10,101 +9,15 @@ import numpy as np
 import pytest
 import torch
 
+import trainer_util as TU
 from alphazero_gym_amd import _capi, run
-from alphazero_gym_amd.agent.losses import A0CLoss, A0CLossTuned, AlphaZeroLoss
-from alphazero_gym_amd.agent.population_trainer import PopulationTrainer, population_loss
-from alphazero_gym_amd.network.policies import make_policy
+from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
+from device_loss_util import HEADS, LOG_ALPHA0, alpha_tensors, kernel_loss, make_head, make_inputs, make_loss, make_trainer, torch_loss, ulp32
+from trainer_util import DEV
 
 pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
-
-DEV = "cuda"
-BOUND = 2.0
-# head: (kind, logits or components, actions per row)
-HEADS = {"discrete2": ("discrete", 2, 2), "discrete3": ("discrete", 3, 3), "normal": ("normal", 1, 8), "gmm2": ("gmm", 2, 5),
-         "gmm5": ("gmm", 5, 16)}
-LOG_ALPHA0 = [float(np.log(a)) for a in (0.5, 1.0, 2.0, 0.25, 1.5)]
-
-
-def _native():
-    from alphazero_gym_amd import _native as N
-    N.lib()
-    return N
-
-
-def make_head(head):
-    kind, n, _ = HEADS[head]
-    torch.manual_seed(0)
-    if kind == "discrete":
-        return make_policy(3, 1, "discrete", [16], "relu", num_actions=n)
-    return make_policy(3, 1, "normal", [16], "elu", num_components=n, action_bound=BOUND)
-
-
-def make_loss(name, reduction, clip=0.0):
-    if name == "alphazero":
-        return AlphaZeroLoss(policy_coeff=1.0, value_coeff=0.5, reduction=reduction)
-    if name == "a0c":
-        return A0CLoss(tau=0.1, policy_coeff=0.1, alpha=0.05, value_coeff=1.0, reduction=reduction)
-    return A0CLossTuned(action_dim=1, alpha_init=1.0, lr=1e-3, tau=0.1, policy_coeff=0.1, value_coeff=1.0, reduction=reduction,
-                        grad_clip=clip, device="cpu")
-
-
-def make_inputs(head, K, B, seed):
-    """(raw [K, B, 1 + n_dist], actions [K, B, A], counts [K, B, A], values [K, B]) on the CPU, float32."""
-    kind, n, A = HEADS[head]
-    g = torch.Generator().manual_seed(seed)
-    n_dist = {"discrete": n, "normal": 2, "gmm": 3 * n}[kind]
-    raw = torch.randn((K, B, 1 + n_dist), generator=g)
-    if kind == "normal":
-        raw[..., 2] *= 4.0            # log_std on both sides of the clamp [-5, 2]
-    elif kind == "gmm":
-        raw[..., 1 + n:1 + 2 * n] *= 4.0
-    if kind == "discrete":
-        actions = torch.arange(A, dtype=torch.float32).repeat(K, B, 1)
-        counts = torch.randint(0, 9, (K, B, A), generator=g).float()
-    else:
-        actions = 0.98 * BOUND * torch.tanh(torch.randn((K, B, A), generator=g))
-        extra = torch.randint(0, A, (K, B, 25 - A), generator=g)      # positive integers that sum to 25
-        counts = torch.ones((K, B, A)).scatter_add_(2, extra, torch.ones(extra.shape))
-    values = torch.randn((K, B), generator=g)
-    return raw, actions, counts, values
-
-
-def torch_loss(policy, loss, inputs, dtype, log_alpha=None, alpha_optimizer=None):
-    """population_loss on the CPU in ``dtype``: ({key: [K]}, raw.grad)."""
-    raw, actions, counts, values = (x.detach().to(dtype) for x in inputs)
-    raw = raw.clone().requires_grad_(True)
-    out = population_loss(policy, loss, raw, actions, counts, values.unsqueeze(-1), log_alpha, alpha_optimizer)
-    out["loss"].sum().backward()
-    return {k: v.detach() for k, v in out.items()}, raw.grad
-
-
-def kernel_loss(tr, cfg, inputs, state=None):
-    """azg_trainer_loss: (losses [K, 5], d_raw) on the CPU."""
-    raw, actions, counts, values = (x.to(DEV).contiguous() for x in inputs)
-    d_raw = torch.full_like(raw, float("nan"))
-    losses = torch.full((raw.shape[0], 5), float("nan"), device=DEV)
-    torch.cuda.synchronize()
-    tr.loss(raw.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), raw.shape[1], actions.shape[2], cfg, state,
-            d_raw.data_ptr(), losses.data_ptr())
-    return losses.cpu(), d_raw.cpu()
-
-
-def make_trainer(head, K, max_batch=128):
-    policy = make_head(head)
-    desc = _capi.policy_tensors(policy)[0]
-    return policy, _native().HipTrainer(desc, K, max_batch)
-
-
-def alpha_tensors(K, dtype=torch.float32, device=DEV):
-    return (torch.tensor(LOG_ALPHA0[:K], dtype=dtype, device=device), torch.zeros(K, dtype=dtype, device=device),
-            torch.zeros(K, dtype=dtype, device=device))
-
-
-def ulp32(x):
-    return float(np.spacing(np.float32(abs(float(x)))))
-
 
 CASES = [(h, "alphazero") for h in ("discrete2", "discrete3")] + [(h, l) for h in HEADS for l in ("a0c", "a0c_tuned")]
 
@@ -228,35 +141,9 @@ def test_alpha_step(head, clip):
     assert not fails, fails
 
 
-def _e2e_agents(kind, K):
-    from alphazero_gym_amd.envs import make_game
-    cfg = run._merge(run.CONTINUOUS_DEFAULTS if kind == "continuous" else run.DISCRETE_DEFAULTS, dict(device=DEV))
-    env = make_game(cfg["game"])
-    agents = []
-    for k in range(K):
-        torch.manual_seed(70 + k)
-        agents.append(run.make_agent(kind, cfg, env, tree_id_base=k))
-    return cfg, agents
-
-
-def _twin(kind, cfg, agent, device, dtype=torch.float32):
-    from alphazero_gym_amd.envs import make_game
-    a = run.make_agent(kind, dict(cfg, device=device), make_game(cfg["game"]))
-    a.nn.load_state_dict({k: v.detach().to(device) for k, v in agent.nn.state_dict().items()})
-    a.nn.to(dtype)
-    return a
-
-
-def _update_f64(kind, cfg, agent, batch):
-    a = _twin(kind, cfg, agent, "cpu", torch.float64)
-    s, ac, c, _, v = (x.detach().cpu().double() for x in batch)
-    d = a._loss(s, ac, c, v.reshape(-1, 1))
-    return {k: float(x.detach()) if hasattr(x, "detach") else float(x) for k, x in d.items()}
-
-
 def _step_f64(kind, cfg, agent, batch):
     """The agent's whole optimiser step in float64 on the CPU: the parameters after it, in blob order."""
-    a = _twin(kind, cfg, agent, "cpu", torch.float64)
+    a = TU.twin(kind, cfg, agent, "cpu", torch.float64)
     s, ac, c, _, v = (x.detach().cpu().double() for x in batch)
     a.optimizer.zero_grad(set_to_none=True)
     a._loss(s, ac, c, v.reshape(-1, 1))["loss"].backward()
@@ -273,8 +160,8 @@ def test_end_to_end_update(kind):
     bound 0.5 ulp + 16 * 2^-24 * |delta p| between the two paths, test_optimiser_step_given_gradient's, is too tight here: the
     two paths' d_raw differ by 1.5e-8 of the largest, and on one MI355X the largest err/bound was 1.42 for CartPole.)"""
     K = 4
-    cfg, agents = _e2e_agents(kind, K)
-    others = [_twin(kind, cfg, a, DEV) for a in agents]
+    cfg, agents = TU.e2e_agents(kind, K)
+    others = [TU.twin(kind, cfg, a, DEV) for a in agents]
     m = cfg["mcts"]
     sp = run.PopulationSelfPlay([a.nn for a in agents], game=cfg["game"], games_per_net=8, n_rollouts=m["n_rollouts"], c_uct=m["c_uct"],
                                 gamma=m["gamma"], epsilon=m["epsilon"], c_pw=m.get("c_pw", 1.0), kappa=m.get("kappa", 0.5),
@@ -282,10 +169,10 @@ def test_end_to_end_update(kind):
     rows = sp.collect_device(8)
     S, A = sp.engine.s_obs, sp.engine.kmax
     sp.close()
-    batches = [(r[:, :S], r[:, S:S + A], r[:, S + A:S + 2 * A], r[:, S + 2 * A:S + 3 * A], r[:, -1]) for r in rows]
-    truth = [_update_f64(kind, cfg, a, b) for a, b in zip(agents, batches)]
+    batches = TU.batches(rows, S, A)
+    truth = [TU.update_f64(kind, cfg, a, b) for a, b in zip(agents, batches)]
     p64 = torch.stack([_step_f64(kind, cfg, a, b) for a, b in zip(agents, batches)])
-    yard = [_twin(kind, cfg, a, DEV).update(b) for a, b in zip(agents, batches)]
+    yard = [TU.twin(kind, cfg, a, DEV).update(b) for a, b in zip(agents, batches)]
     before = torch.from_numpy(np.stack([_capi.policy_blob(a.nn)[1] for a in agents])).double()
     tr = PopulationTrainer(agents, losses="device")
     got = tr.update(batches)
@@ -329,7 +216,7 @@ def test_end_to_end_update(kind):
 
 
 def test_abi_errors():
-    N = _native()
+    N = TU.native()
     K, B, A = 2, 16, 5
     policy = make_head("gmm2")
     desc = _capi.policy_tensors(policy)[0]

@@ -9,23 +9,13 @@ import pytest
 import torch
 
 import trainer_edges as E
+import trainer_util as TU
 from alphazero_gym_amd import _capi
-from test_population_device_loss import LOG_ALPHA0, alpha_tensors, kernel_loss, make_inputs, make_loss, make_trainer, torch_loss, ulp32
+from device_loss_util import LOG_ALPHA0, alpha_tensors, kernel_loss, make_inputs, make_loss, make_trainer, torch_loss, ulp32
 
 pytestmark = pytest.mark.gpu
 
 NOISE = 2.0 ** -30      # float64 PyTorch's own error at the squash's pole, with a 4 x margin over test_trainer_edges_host.py's pin
-
-
-def _native():
-    from alphazero_gym_amd import _native as N
-    N.lib()
-    return N
-
-
-def _ulp32(x):
-    return torch.from_numpy(np.spacing(np.abs(x.numpy()).astype(np.float32)).astype(np.float64))
-
 
 EDGE_CASES = [(h, l) for h in E.DISCRETE_HEADS for l in ("alphazero", "a0c", "a0c_tuned")] + [
     (h, l) for h in E.CONT_HEADS for l in ("a0c", "a0c_tuned")]
@@ -53,14 +43,14 @@ def test_edge_rows_against_float64(head, loss_name, reduction):
     if tuned:
         la, m, v = alpha_tensors(K)
         state = _capi.alpha_state(0, la.data_ptr(), m.data_ptr(), v.data_ptr())
-    tr = _native().HipTrainer(desc, K, 64)
+    tr = TU.native().HipTrainer(desc, K, 64)
     got, d_raw = kernel_loss(tr, _capi.loss_cfg(policy, loss), inputs, state)
     tr.close()
     assert torch.isfinite(d_raw).all() and torch.isfinite(got).all()
     fails = []
     for k in range(K):
         scale = float(g64[k].abs().max())
-        bound = _ulp32(g64[k]) + NOISE * scale
+        bound = TU.ulp(g64[k]) + NOISE * scale
         e_k = (d_raw[k].double() - g64[k]).abs()
         e_y = (g32[k].double() - g64[k]).abs()
         print(f"edge loss {head} {loss_name} {reduction} B={B} net {k} d_raw: kernel error {float((e_k / bound).max()):.3g} of its bound "

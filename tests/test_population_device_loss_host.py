@@ -1,6 +1,5 @@
 """CPU: the host half of the population trainer's device losses -- the ``losses=`` keyword of PopulationTrainer and
 ``_capi.loss_cfg``.  The kernel is tested on the GPU in test_population_device_loss.py."""
-import copy
 import ctypes as C
 import re
 
@@ -11,24 +10,12 @@ from alphazero_gym_amd import _capi
 from alphazero_gym_amd.agent.losses import A0CLoss, A0CLossTuned, AlphaZeroLoss
 from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
 from alphazero_gym_amd.network.policies import make_policy
-from test_population_trainer_host import make_agent
-
-
-def _untouched(agents, before, ptrs):
-    for a, sd, pp in zip(agents, before, ptrs):   # same values, same storage, no optimiser state
-        for name, v in a.nn.state_dict().items():
-            assert torch.equal(v, sd[name])
-        assert [p.data_ptr() for p in a.nn.parameters()] == pp and not a.optimizer.state
+from trainer_util import make_agent, refused
 
 
 @pytest.mark.parametrize("value", ["hip", "", None, "Device"])
 def test_unknown_losses_value(value):
-    agents = [make_agent("normal") for _ in range(2)]
-    before = copy.deepcopy([a.nn.state_dict() for a in agents])
-    ptrs = [[p.data_ptr() for p in a.nn.parameters()] for a in agents]
-    with pytest.raises(ValueError, match=re.escape("losses must be 'torch' or 'device'")):
-        PopulationTrainer(agents, losses=value)
-    _untouched(agents, before, ptrs)
+    refused([make_agent("normal") for _ in range(2)], "losses must be 'torch' or 'device'", losses=value)
     # the check comes first: agents that would be refused for another reason are not looked at
     with pytest.raises(ValueError, match=re.escape("losses must be 'torch' or 'device'")):
         PopulationTrainer([], losses=value)
@@ -36,12 +23,7 @@ def test_unknown_losses_value(value):
 
 @pytest.mark.parametrize("losses", ["torch", "device"])
 def test_cpu_agents_still_refused(losses):
-    agents = [make_agent("gmm2") for _ in range(2)]
-    before = copy.deepcopy([a.nn.state_dict() for a in agents])
-    ptrs = [[p.data_ptr() for p in a.nn.parameters()] for a in agents]
-    with pytest.raises(ValueError, match=re.escape("must live on one GPU")):
-        PopulationTrainer(agents, losses=losses)
-    _untouched(agents, before, ptrs)
+    refused([make_agent("gmm2") for _ in range(2)], "must live on one GPU", losses=losses)
 
 
 def _policy(head):

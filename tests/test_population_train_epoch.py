@@ -9,84 +9,17 @@ import numpy as np
 import pytest
 import torch
 
+import trainer_util as TU
 from alphazero_gym_amd import _capi, run
-from alphazero_gym_amd.agent.agents import ContinuousAgent, DiscreteAgent
 from alphazero_gym_amd.agent.buffers import DeviceReplay
 from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
+from trainer_util import DEV, DIMS
 
 pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
 
-DEV = "cuda"
-LOSSES = {
-    "alphazero": dict(_target_="alphazero_gym_amd.agent.losses.AlphaZeroLoss", policy_coeff=1.0, value_coeff=0.5, reduction="mean"),
-    "a0c": dict(_target_="alphazero_gym_amd.agent.losses.A0CLoss", tau=0.1, policy_coeff=0.1, alpha=0.05, value_coeff=1.0, reduction="mean"),
-    "a0c_tuned": dict(run.LOSS_TUNED, device=DEV),
-}
-OPT = dict(run.RMSPROP, weight_decay=1e-4)
-# head: (observations, actions per row)
-DIMS = {"discrete": (4, 2), "gmm2": (3, 4)}
 COMBOS = [("discrete", "alphazero"), ("discrete", "a0c_tuned"), ("gmm2", "a0c"), ("gmm2", "a0c_tuned")]
-
-
-def _native():
-    from alphazero_gym_amd import _native as N
-    N.lib()
-    return N
-
-
-def make_agents(head, loss, K, first_seed=0):
-    """Net k's initial weights come from torch.manual_seed(first_seed + k): two calls give identical populations."""
-    agents = []
-    for k in range(K):
-        torch.manual_seed(first_seed + k)
-        if head == "discrete":   # 4 inputs, [32, 32], 2 actions, ReLU
-            cfg = run.DISCRETE_DEFAULTS
-            policy = dict(cfg["policy"], hidden_dimensions=[32, 32], representation_dim=4, action_dim=1, num_actions=2)
-            agents.append(DiscreteAgent(policy_cfg=policy, mcts_cfg=dict(cfg["mcts"], device=DEV, num_actions=2), loss_cfg=LOSSES[loss],
-                                        optimizer_cfg=OPT, device=DEV, **cfg["agent"]))
-        else:                    # 3 inputs, [32, 16], a mixture of 2, ELU
-            cfg = run.CONTINUOUS_DEFAULTS
-            policy = dict(cfg["policy"], hidden_dimensions=[32, 16], representation_dim=3, action_dim=1, action_bound=2.0, num_components=2)
-            agents.append(ContinuousAgent(policy_cfg=policy, mcts_cfg=dict(cfg["mcts"], device=DEV), loss_cfg=LOSSES[loss],
-                                          optimizer_cfg=OPT, device=DEV, **cfg["agent"]))
-    return agents
-
-
-def make_rows(head, K, n, seed):
-    """[K, n, row] float32 on the GPU: obs | actions[A] | counts[A] | Q[A] | V."""
-    S, A = DIMS[head]
-    rng = np.random.RandomState(seed)
-    obs = rng.randn(K, n, S)
-    if head == "discrete":
-        actions = np.tile(np.arange(A, dtype=np.float64), (K, n, 1))
-        counts = rng.randint(0, 9, (K, n, A))
-    else:
-        actions = rng.uniform(-1.9, 1.9, (K, n, A))
-        counts = rng.randint(1, 9, (K, n, A))
-    q = rng.randn(K, n, A)
-    v = rng.randn(K, n, 1)
-    return torch.from_numpy(np.concatenate([obs, actions, counts, q, v], axis=-1).astype(np.float32)).to(DEV)
-
-
-def state_of(tr):
-    """Everything an epoch may change, as CPU copies."""
-    s = {"flat": tr.flat, "square_avg": tr.square_avg}
-    if tr.log_alpha is not None:
-        s.update(log_alpha=tr.log_alpha, alpha_exp_avg=tr.alpha_exp_avg, alpha_exp_avg_sq=tr.alpha_exp_avg_sq)
-    out = {k: v.detach().cpu().clone() for k, v in s.items()}
-    out["alpha_step"] = torch.tensor(tr.alpha_step)
-    return out
-
-
-def assert_same(a, b, what, nets=None):
-    assert set(a) == set(b)
-    for key in a:
-        x, y = a[key], b[key]
-        if nets is not None and x.dim() > 0:
-            x, y = x[nets[0]], y[nets[1]]
-        assert torch.equal(x, y), f"{what}: {key} differs"
 
 
 @pytest.mark.parametrize("n,batch", [(150, 64), (33, 16), (10, 32), (1, 1), (96, 32)])
@@ -98,12 +31,12 @@ def test_epoch_equals_loop_of_steps(head, loss, n, batch):
     minibatch; (1, 1); (96, 32): three equal minibatches."""
     K = 3
     S, A = DIMS[head]
-    ref = PopulationTrainer(make_agents(head, loss, K), max_batch=128, losses="device")
-    ep = PopulationTrainer(make_agents(head, loss, K), max_batch=128, losses="device")
-    start = state_of(ref)
-    assert_same(start, state_of(ep), "initial state")
+    ref = PopulationTrainer(TU.make_agents(head, loss, K), max_batch=128, losses="device")
+    ep = PopulationTrainer(TU.make_agents(head, loss, K), max_batch=128, losses="device")
+    start = TU.state_of(ref)
+    TU.assert_same(start, TU.state_of(ep), "initial state")
     for epoch in range(2):
-        rows = make_rows(head, K, n, 100 + epoch)
+        rows = TU.make_rows(head, K, n, 100 + epoch)
         keep = rows.clone()
         seeds = [11 + epoch, 22, 33 + 5 * epoch]
         want = ref.train_on_rows(rows, S, A, batch_size=batch, shuffle_seeds=seeds)
@@ -111,17 +44,17 @@ def test_epoch_equals_loop_of_steps(head, loss, n, batch):
         assert torch.equal(rows, keep)
         assert got == want, f"epoch {epoch}"
         assert all(isinstance(v, float) and np.isfinite(v) for g in got for v in g.values())
-        assert_same(state_of(ref), state_of(ep), f"epoch {epoch}")
-    end = state_of(ep)
+        TU.assert_same(TU.state_of(ref), TU.state_of(ep), f"epoch {epoch}")
+    end = TU.state_of(ep)
     assert not torch.equal(end["flat"], start["flat"]) and not torch.equal(end["square_avg"], start["square_avg"])
     n_mb = 2 * max(1, n // batch)
     assert int(end["alpha_step"]) == (n_mb if loss == "a0c_tuned" else 0)
     if loss == "a0c_tuned":
         assert not torch.equal(end["log_alpha"], start["log_alpha"])
     # a list of K tensors is stacked as train_on_rows stacks it
-    rows = make_rows(head, K, n, 200)
+    rows = TU.make_rows(head, K, n, 200)
     assert ep.train_epoch(list(rows), S, A, batch_size=batch) == ref.train_on_rows(list(rows), S, A, batch_size=batch)
-    assert_same(state_of(ref), state_of(ep), "rows given as a list")
+    TU.assert_same(TU.state_of(ref), TU.state_of(ep), "rows given as a list")
     ref.close()
     ep.close()
 
@@ -130,7 +63,7 @@ def test_ring_addressing():
     """train_epoch_ring on a PopulationSelfPlay's ring (K = 3, T = 4, 5 steps) against the same orders on _split's copies."""
     K, T, steps, batch = 3, 4, 5, 8
     S, A = DIMS["discrete"]
-    agents = make_agents("discrete", "a0c_tuned", K)
+    agents = TU.make_agents("discrete", "a0c_tuned", K)
     sp = run.PopulationSelfPlay([a.nn for a in agents], game="CartPole-v0", games_per_net=T, n_rollouts=8, c_uct=1.5, epsilon=0.1,
                                 capacity_steps=8)
     assert sp.play_device(steps) == (steps, 0)   # (insert_index moves only once the ring is full)
@@ -138,36 +71,36 @@ def test_ring_addressing():
     n = steps * T
     assert copies.shape == (K, n, S + 3 * A + 1) and len({c.cpu().numpy().tobytes() for c in copies}) == K
     ring = PopulationTrainer(agents, max_batch=64, losses="device")
-    copy = PopulationTrainer(make_agents("discrete", "a0c_tuned", K), max_batch=64, losses="device")
+    copy = PopulationTrainer(TU.make_agents("discrete", "a0c_tuned", K), max_batch=64, losses="device")
     # (a) every row once: the orders train_epoch draws from these seeds
     seeds = [3, 1, 4]
     order = np.stack([np.random.RandomState(s).permutation(n) for s in seeds])
     got = ring.train_epoch_ring(sp, order, batch_size=batch)
     want = copy.train_epoch(copies, S, A, batch_size=batch, shuffle_seeds=seeds)
     assert got == want
-    assert_same(state_of(ring), state_of(copy), "ring, whole permutation")
+    TU.assert_same(TU.state_of(ring), TU.state_of(copy), "ring, whole permutation")
     # (b) a hand-made order: first and last row, repeats, 13 entries (the remainder of 5 is absorbed: one minibatch of 13)
     order = np.array([[0, n - 1, 5, 5, 7, 12, 19, 3, 8, 1, 16, 11, 4], [n - 1, 0, 2, 9, 9, 9, 14, 6, 18, 10, 13, 17, 15],
                       [4, 8, 12, 16, 0, 1, 2, 3, n - 1, n - 2, 7, 7, 6]])
     got = ring.train_epoch_ring(sp, order, batch_size=batch)
     want = copy._epoch("train_epoch", _capi.epoch_rows(copies.data_ptr(), S, A, n), order.astype(np.int32), batch)
     assert got == want
-    assert_same(state_of(ring), state_of(copy), "ring, hand-made order")
+    TU.assert_same(TU.state_of(ring), TU.state_of(copy), "ring, hand-made order")
     assert ring.alpha_step == 2 + 1   # (a): 8 + 12 rows
     # the ring is read, not changed or cleared
     assert sp.engine.selfplay_ring()[0] == steps
     assert torch.equal(torch.stack(sp._split(DeviceReplay(sp.engine, 1).rows(), steps)), copies)
     # refusals, before anything is touched
-    before = state_of(ring)
+    before = TU.state_of(ring)
     with pytest.raises(ValueError, match="outside the ring"):
         ring.train_epoch_ring(sp, np.array([[0, 1], [2, n], [3, 4]]), batch_size=batch)
     with pytest.raises(ValueError, match="outside the ring"):
         ring.train_epoch_ring(sp, np.array([[0, 1], [2, -1], [3, 4]]), batch_size=batch)
-    one = PopulationTrainer(make_agents("discrete", "a0c_tuned", 1, first_seed=9), max_batch=64, losses="device")
+    one = PopulationTrainer(TU.make_agents("discrete", "a0c_tuned", 1, first_seed=9), max_batch=64, losses="device")
     with pytest.raises(ValueError, match="3 nets, the trainer 1"):
         one.train_epoch_ring(sp, np.array([[0, 1]]), batch_size=batch)
     one.close()
-    assert_same(state_of(ring), before, "after refusals")
+    TU.assert_same(TU.state_of(ring), before, "after refusals")
     # the trained nets go to the search as after train_on_rows
     sp.upload_flat(ring.desc, ring.flat)
     assert sp.last_weight_sync == "device"
@@ -183,7 +116,7 @@ def test_strides_are_independent():
     head, loss = "gmm2", "a0c_tuned"
     S, A = DIMS[head]
     n = groups * G
-    plain = make_rows(head, K, n, 300)
+    plain = TU.make_rows(head, K, n, 300)
     row_len = plain.shape[2]
     buf = torch.full(((groups - 1) * g_stride + (K - 1) * n_stride + G, row_len), float("nan"), device=DEV)
     for k in range(K):
@@ -192,12 +125,12 @@ def test_strides_are_independent():
     where = _capi.epoch_rows(buf.data_ptr(), S, A, n)
     where.group, where.group_stride, where.net_stride = G, g_stride, n_stride
     order = np.stack([np.random.RandomState(40 + k).permutation(n) for k in range(K)]).astype(np.int32)
-    a = PopulationTrainer(make_agents(head, loss, K), max_batch=32, losses="device")
-    b = PopulationTrainer(make_agents(head, loss, K), max_batch=32, losses="device")
+    a = PopulationTrainer(TU.make_agents(head, loss, K), max_batch=32, losses="device")
+    b = PopulationTrainer(TU.make_agents(head, loss, K), max_batch=32, losses="device")
     got = a._epoch("train_epoch", where, order, batch)
     want = b._epoch("train_epoch", _capi.epoch_rows(plain.data_ptr(), S, A, n), order, batch)
     assert got == want and all(np.isfinite(v) for g in got for v in g.values())
-    assert_same(state_of(a), state_of(b), "strided buffer")
+    TU.assert_same(TU.state_of(a), TU.state_of(b), "strided buffer")
     assert torch.isfinite(a.flat).all()
     a.close()
     b.close()
@@ -208,32 +141,32 @@ def test_population_invariance_and_determinism(head, loss):
     """Net k of a K = 3 epoch equals a K = 1 trainer's epoch on net k's rows and seed, bit for bit; two K = 3 runs are equal."""
     K, n, batch = 3, 33, 16
     S, A = DIMS[head]
-    rows = make_rows(head, K, n, 400)
+    rows = TU.make_rows(head, K, n, 400)
     seeds = [7, 8, 9]
     runs = []
     for _ in range(2):
-        tr = PopulationTrainer(make_agents(head, loss, K), max_batch=64, losses="device")
+        tr = PopulationTrainer(TU.make_agents(head, loss, K), max_batch=64, losses="device")
         info = tr.train_epoch(rows, S, A, batch_size=batch, shuffle_seeds=seeds)
-        runs.append((info, state_of(tr)))
+        runs.append((info, TU.state_of(tr)))
         tr.close()
     assert runs[0][0] == runs[1][0]
-    assert_same(runs[0][1], runs[1][1], "two runs")
+    TU.assert_same(runs[0][1], runs[1][1], "two runs")
     for k in range(K):
-        tr = PopulationTrainer(make_agents(head, loss, 1, first_seed=k), max_batch=64, losses="device")
+        tr = PopulationTrainer(TU.make_agents(head, loss, 1, first_seed=k), max_batch=64, losses="device")
         info = tr.train_epoch(rows[k:k + 1].contiguous(), S, A, batch_size=batch, shuffle_seeds=seeds[k:k + 1])
         assert info[0] == runs[0][0][k]
-        assert_same(runs[0][1], state_of(tr), f"net {k}: K = 3 and K = 1", nets=(k, 0))
+        TU.assert_same(runs[0][1], TU.state_of(tr), f"net {k}: K = 3 and K = 1", nets=(k, 0))
         tr.close()
 
 
 def test_abi_errors_leave_everything_untouched():
     """Every refusal of azg_trainer_epoch through the raw ABI: the host checks reject each input before a launch, params,
     square_avg, loss_sums and the alpha state stay as they were, and a valid call follows."""
-    N = _native()
+    N = TU.native()
     K, n, batch, max_batch = 2, 40, 16, 32
     head = "gmm2"
     S, A = DIMS[head]
-    agent = make_agents(head, "a0c_tuned", 1)[0]
+    agent = TU.make_agents(head, "a0c_tuned", 1)[0]
     desc = _capi.policy_tensors(agent.nn)[0]
     cfg = _capi.loss_cfg(agent.nn, agent.loss)
     tr = N.HipTrainer(desc, K, max_batch)
@@ -242,7 +175,7 @@ def test_abi_errors_leave_everything_untouched():
     sq = torch.full_like(params, 0.25)
     sums = torch.full((K, 5), 7.0, dtype=torch.float64, device=DEV)
     la, m, v = (torch.tensor([0.1, -0.2], device=DEV), torch.zeros(K, device=DEV), torch.zeros(K, device=DEV))
-    rows = make_rows(head, K, n, 500)
+    rows = TU.make_rows(head, K, n, 500)
     written = (params, sq, sums, la, m, v, rows)
     keep = [t.clone() for t in written]
     st = _capi.alpha_state(0, la.data_ptr(), m.data_ptr(), v.data_ptr())

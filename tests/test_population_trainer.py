@@ -10,135 +10,27 @@ import numpy as np
 import pytest
 import torch
 
+import trainer_util as TU
 from alphazero_gym_amd import _capi, run
-from alphazero_gym_amd.network.policies import make_policy
+from trainer_util import DEV, OPT
 
 pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
 
-DEV = "cuda"
-U = 2.0 ** -24
-
-
-def _native():
-    from alphazero_gym_amd import _native as N
-    N.lib()
-    return N
-
-
-def _policy(in_dim, hidden, head, act, seed):
-    """head: ("discrete", n_actions) | ("normal",) | ("gmm", components)"""
-    torch.manual_seed(seed)
-    if head[0] == "discrete":
-        return make_policy(in_dim, 1, "discrete", list(hidden), act, num_actions=head[1])
-    return make_policy(in_dim, 1, "normal", list(hidden), act, num_components=1 if head[0] == "normal" else head[1], action_bound=2.0)
-
-
-def _flat(policies):
-    return torch.from_numpy(np.stack([_capi.policy_blob(p)[1] for p in policies])).to(DEV)
-
-
-def _raw_of(pol, x):
-    h = pol.trunk(x)
-    return torch.cat([pol.value_head(h), pol.dist_head(h)], dim=-1)
-
-
-def _data(K, B, in_dim, n_raw, seed):
-    g = torch.Generator().manual_seed(seed)
-    obs = torch.randn((K, B, in_dim), generator=g)
-    d_raw = torch.randn((K, B, n_raw), generator=g) / B
-    return obs, d_raw
-
-
-def _step(tr, params, obs, d_raw, opt, sq):
-    """One forward + backward/optimiser step: (raw, grads); params and sq are updated in place."""
-    K, B = obs.shape[:2]
-    raw = torch.empty((K, B, tr.n_raw), device=DEV)
-    grads = torch.zeros_like(params)
-    torch.cuda.synchronize()
-    tr.forward(params.data_ptr(), obs.data_ptr(), B, raw.data_ptr())
-    tr.backward_step(params.data_ptr(), d_raw.data_ptr(), B, opt, sq.data_ptr(), grads.data_ptr())
-    return raw, grads
-
-
-OPT = dict(lr=1e-3, alpha=0.9, eps=1e-10)
-
-# (in_dim, hidden, head, activation): 1, 2 and 3 hidden layers; widths 16, 128, 256; 2, 3, 4 and 6 inputs; the three head kinds
-SHAPES = [
-    (2, [16], ("normal",), "elu"),
-    (4, [128, 128], ("discrete", 2), "relu"),
-    (3, [128, 128, 128], ("gmm", 2), "elu"),
-    (6, [256, 16], ("discrete", 3), "relu"),
-    (3, [256, 256, 256], ("normal",), "elu"),
-]
+SHAPES = TU.NARROW
 
 
 @pytest.mark.parametrize("B", [1, 17, 128, 383])
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}in_{'x'.join(map(str, s[1]))}_{'_'.join(map(str, s[2]))}")
 def test_population_invariance(shape, B):
     """Net k of a K = 5 trainer equals a K = 1 trainer on net k's data, bit for bit; so do two runs of the same call."""
-    N = _native()
-    in_dim, hidden, head, act = shape
-    K = 5
-    pols = [_policy(in_dim, hidden, head, act, 50 + k) for k in range(K)]
-    desc = _capi.policy_tensors(pols[0])[0]
-    opt = _capi.rmsprop_opt(weight_decay=1e-4, **OPT)
-    obs, d_raw = _data(K, B, in_dim, 1 + desc.n_dist, 7)
-    obs, d_raw = obs.to(DEV), d_raw.to(DEV)
-    runs = []
-    for _ in range(2):
-        tr = N.HipTrainer(desc, K, 512)
-        params, sq = _flat(pols), torch.full((K, tr.n_params), 0.25, device=DEV)
-        raw, grads = _step(tr, params, obs, d_raw, opt, sq)
-        runs.append([t.cpu() for t in (raw, grads, params, sq)])
-        tr.close()
-    for a, b, name in zip(runs[0], runs[1], ("raw", "grads", "params", "square_avg")):
-        assert torch.equal(a, b), f"{name}: two runs differ"
-    assert torch.isfinite(runs[0][1]).all() and not torch.equal(runs[0][2], _flat(pols).cpu())
-    tr1 = N.HipTrainer(desc, 1, 512)
-    for k in range(K):
-        params, sq = _flat(pols[k:k + 1]), torch.full((1, tr1.n_params), 0.25, device=DEV)
-        raw, grads = _step(tr1, params, obs[k:k + 1].contiguous(), d_raw[k:k + 1].contiguous(), opt, sq)
-        for a, b, name in zip(runs[0], (raw, grads, params, sq), ("raw", "grads", "params", "square_avg")):
-            assert torch.equal(a[k], b[0].cpu()), f"{name} of net {k}: K = 5 and K = 1 differ"
-    tr1.close()
+    TU.check_population_invariance(shape, B, None, [TU.policy(*shape, 50 + k) for k in range(5)], forms=("fused",))
 
 
 @pytest.mark.parametrize("shape", SHAPES[1:4], ids=["cartpole", "pendulum_gmm2", "acrobot"])
 def test_forward_against_engine(shape):
-    """raw against azg_mlp_eval's raw of a single-net engine with the same weights (T2: 1e-5; the head sums are ordered
-    differently from mlp.cuh's chunked ones, so not bit for bit)."""
-    N = _native()
-    in_dim, hidden, head, act = shape
-    pol = _policy(in_dim, hidden, head, act, 3)
-    desc, blob = _capi.policy_blob(pol)
-    if head[0] == "discrete":
-        kw = dict(env_id={4: _capi.ENV_CARTPOLE, 6: _capi.ENV_ACROBOT}[in_dim], mode=_capi.MODE_DISCRETE, num_actions=head[1])
-    else:
-        kw = dict(env_id=_capi.ENV_PENDULUM_V0, mode=_capi.MODE_CONTINUOUS)
-    e = N.HipEngine(n_trees=16, n_sims=8, c_uct=1.0, gamma=1.0, **kw)
-    e.set_weights(desc, blob)
-    B = 77
-    obs, _ = _data(1, B, in_dim, 1, 11)
-    _, _, want = e.mlp_eval(obs[0].numpy())
-    e.close()
-    tr = N.HipTrainer(desc, 1, 128)
-    raw = torch.empty((1, B, tr.n_raw), device=DEV)
-    params, o = _flat([pol]), obs.to(DEV)
-    torch.cuda.synchronize()
-    tr.forward(params.data_ptr(), o.data_ptr(), B, raw.data_ptr())
-    tr.close()
-    err = np.abs(raw[0].cpu().numpy() - want).max()
-    print(f"forward vs azg_mlp_eval {shape}: max abs difference {err:.3g}")
-    assert err <= 1e-5
-
-
-def _autograd(pol, obs, d_raw, dtype):
-    p = copy.deepcopy(pol).to(dtype)
-    raw = _raw_of(p, obs.to(dtype))
-    (raw * d_raw.to(dtype)).sum().backward()
-    return [t.grad for t in _capi.policy_tensors(p)[1]]
+    TU.check_forward_against_engine(shape, None, TU.policy(*shape, 3), f"forward vs azg_mlp_eval {shape}")
 
 
 GRAD_CASES = [(s, 128) for s in SHAPES] + [(SHAPES[1], 17), (SHAPES[2], 17)] + [
@@ -147,97 +39,12 @@ GRAD_CASES = [(s, 128) for s in SHAPES] + [(SHAPES[1], 17), (SHAPES[2], 17)] + [
 
 @pytest.mark.parametrize("shape,B", GRAD_CASES, ids=lambda v: str(v).replace(" ", ""))
 def test_gradients_against_autograd(shape, B):
-    """Truth: float64 autograd on CPU.  Yardstick: float32 autograd on CPU, error max|g32 - g64| / max|g64| per parameter tensor;
-    the kernel's error by the same measure may be at most 4 x that.  B = 17: padded rows must contribute nothing."""
-    N = _native()
-    in_dim, hidden, head, act = shape
-    pol = _policy(in_dim, hidden, head, act, 21)
-    desc = _capi.policy_tensors(pol)[0]
-    obs, d_raw = _data(1, B, in_dim, 1 + desc.n_dist, 13)
-    g64 = _autograd(pol, obs[0], d_raw[0], torch.float64)
-    g32 = _autograd(pol, obs[0], d_raw[0], torch.float32)
-    tr = N.HipTrainer(desc, 1, 512)
-    params, sq = _flat([pol]), torch.zeros((1, tr.n_params), device=DEV)
-    _, grads = _step(tr, params, obs.to(DEV), d_raw.to(DEV), _capi.rmsprop_opt(**OPT), sq)
-    tr.close()
-    grads = grads[0].cpu()
-    off, fails = 0, []
-    names = [n for n, _ in pol.named_parameters()]
-    for name, a64, a32 in zip(names, g64, g32):
-        gk = grads[off:off + a64.numel()].view_as(a64).double()
-        off += a64.numel()
-        scale = a64.abs().max()
-        e32, ek = float((a32.double() - a64).abs().max() / scale), float((gk - a64).abs().max() / scale)
-        print(f"grad {shape} B={B} {name}: float32 autograd error {e32:.3g}, kernel error {ek:.3g}")
-        if not ek <= 4 * e32:
-            fails.append((name, e32, ek))
-    assert off == grads.numel() and not fails, fails
+    TU.check_gradients_against_autograd(shape, B, None, TU.policy(*shape, 21), f"grad {shape} B={B}")
 
 
 @pytest.mark.parametrize("weight_decay", [0.0, 1e-4])
 def test_optimiser_step_given_gradient(weight_decay):
-    """Three consecutive steps; after each, the kernel's parameters against torch.optim.RMSprop in float64 fed the kernel's own
-    gradients: at most half an ulp of the parameter plus 16 * 2^-24 * |delta p|."""
-    N = _native()
-    in_dim, hidden, head, act = SHAPES[2]
-    pol = _policy(in_dim, hidden, head, act, 31)
-    desc = _capi.policy_tensors(pol)[0]
-    tr = N.HipTrainer(desc, 1, 512)
-    params, sq = _flat([pol]), torch.zeros((1, tr.n_params), device=DEV)
-    ref = params[0].cpu().double().clone().requires_grad_(True)
-    ropt = torch.optim.RMSprop([ref], weight_decay=weight_decay, momentum=0, centered=False, **OPT)
-    opt = _capi.rmsprop_opt(weight_decay=weight_decay, **OPT)
-    for step in range(3):
-        obs, d_raw = _data(1, 64, in_dim, 1 + desc.n_dist, 40 + step)
-        before = params[0].cpu().double()
-        # the float64 optimiser starts every step from the kernel's parameters, so only this step's arithmetic is compared
-        # (its square_avg carries over on its own)
-        with torch.no_grad():
-            ref.copy_(before)
-        sq_before = sq[0].cpu().double()
-        _, grads = _step(tr, params, obs.to(DEV), d_raw.to(DEV), opt, sq)
-        ref.grad = grads[0].cpu().double()
-        ropt.step()
-        got, want = params[0].cpu(), ref.detach()
-        ulp = torch.from_numpy(np.spacing(np.abs(got.numpy()))).double()
-        bound = 0.5 * ulp + 16 * U * (want - before).abs()
-        err = (got.double() - want).abs()
-        print(f"step {step} wd {weight_decay}: max err/bound {float((err / bound).max()):.3g}")
-        assert torch.all(err <= bound)
-        # square_avg = alpha sq + (1 - alpha) g'^2 with g' = g + wd p rounded in float32: |g'| <= |g| + wd |p| bounds both terms' rounding
-        sq_want = OPT["alpha"] * sq_before + (1 - OPT["alpha"]) * (ref.grad + weight_decay * before) ** 2
-        sq_tol = 8 * U * (OPT["alpha"] * sq_before + (1 - OPT["alpha"]) * (ref.grad.abs() + weight_decay * before.abs()) ** 2)
-        assert torch.all((sq[0].cpu().double() - sq_want).abs() <= sq_tol)
-    tr.close()
-
-
-def _e2e_agents(kind, K):
-    cfg = run._merge(run.CONTINUOUS_DEFAULTS if kind == "continuous" else run.DISCRETE_DEFAULTS, dict(device=DEV))
-    from alphazero_gym_amd.envs import make_game
-    env = make_game(cfg["game"])
-    agents = []
-    for k in range(K):
-        torch.manual_seed(70 + k)
-        agents.append(run.make_agent(kind, cfg, env, tree_id_base=k))
-    return cfg, agents
-
-
-def _twin(kind, cfg, agent, device, dtype=torch.float32):
-    """A new agent with ``agent``'s weights (the agents here have taken no optimiser step yet, so their optimisers and learned
-    temperatures are as new; a tuned loss holds a non-leaf alpha, which copy.deepcopy refuses)."""
-    from alphazero_gym_amd.envs import make_game
-    a = run.make_agent(kind, dict(cfg, device=device), make_game(cfg["game"]))
-    a.nn.load_state_dict({k: v.detach().to(device) for k, v in agent.nn.state_dict().items()})
-    a.nn.to(dtype)
-    return a
-
-
-def _update_f64(kind, cfg, agent, batch):
-    """The agent's loss dictionary in float64 on the CPU."""
-    a = _twin(kind, cfg, agent, "cpu", torch.float64)
-    s, ac, c, _, v = (x.detach().cpu().double() for x in batch)
-    d = a._loss(s, ac, c, v.reshape(-1, 1))
-    return {k: float(x.detach()) if hasattr(x, "detach") else float(x) for k, x in d.items()}
+    TU.check_rmsprop_step_given_gradient(SHAPES[2], None, TU.policy(*SHAPES[2], 31), weight_decay)
 
 
 @pytest.mark.parametrize("kind", ["discrete", "continuous"])
@@ -245,16 +52,16 @@ def test_end_to_end_update(kind):
     from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
     from alphazero_gym_amd.search.mcts import PopulationMCTS
     K = 4
-    cfg, agents = _e2e_agents(kind, K)
+    cfg, agents = TU.e2e_agents(kind, K)
     m = cfg["mcts"]
     sp = run.PopulationSelfPlay([a.nn for a in agents], game=cfg["game"], games_per_net=8, n_rollouts=m["n_rollouts"], c_uct=m["c_uct"],
                                 gamma=m["gamma"], epsilon=m["epsilon"], c_pw=m.get("c_pw", 1.0), kappa=m.get("kappa", 0.5),
                                 capacity_steps=8)
     rows = sp.collect_device(8)
     S, A = sp.engine.s_obs, sp.engine.kmax
-    batches = [(r[:, :S], r[:, S:S + A], r[:, S + A:S + 2 * A], r[:, S + 2 * A:S + 3 * A], r[:, -1]) for r in rows]
-    truth = [_update_f64(kind, cfg, a, b) for a, b in zip(agents, batches)]
-    yard = [_twin(kind, cfg, a, DEV).update(b) for a, b in zip(agents, batches)]
+    batches = TU.batches(rows, S, A)
+    truth = [TU.update_f64(kind, cfg, a, b) for a, b in zip(agents, batches)]
+    yard = [TU.twin(kind, cfg, a, DEV).update(b) for a, b in zip(agents, batches)]
     tr = PopulationTrainer(agents)
     got = tr.update(batches)
     assert [set(g) for g in got] == [set(y) for y in yard]
@@ -306,7 +113,7 @@ def test_end_to_end_update(kind):
 
 
 def test_abi_errors():
-    N = _native()
+    N = TU.native()
     f = N.fns()
     ln = _capi.make_desc(4, [128, 128], 2, "relu", layernorm=True)
     wide = _capi.make_desc(4, [512], 2, "relu")
@@ -323,7 +130,7 @@ def test_abi_errors():
     params = torch.randn((2, tr.n_params), device=DEV)
     sq = torch.zeros_like(params)
     keep, keep_sq = params.clone(), sq.clone()
-    obs, d_raw = (t.to(DEV) for t in _data(2, 64, 4, 3, 1))
+    obs, d_raw = (t.to(DEV) for t in TU.data(2, 64, 4, 3, 1))
     raw = torch.zeros((2, 64, 3), device=DEV)
     opt = _capi.rmsprop_opt(**OPT)
     torch.cuda.synchronize()

@@ -6,48 +6,29 @@ import pytest
 import torch
 
 import trainer_edges as E
+import trainer_util as TU
 from alphazero_gym_amd import _capi
 from alphazero_gym_amd.network.policies import make_policy
+from trainer_util import ADAM, DEV, OPT
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-OPT = dict(lr=1e-3, alpha=0.9, eps=1e-10)
-ADAM = dict(lr=1e-3, betas=(0.9, 0.99), eps=1e-7)
-
-
-def _native():
-    from alphazero_gym_amd import _native as N
-    N.lib()
-    return N
-
-
-def _flat(pol):
-    return torch.from_numpy(_capi.policy_blob(pol)[1][None]).to(DEV)
-
-
-def _forward(tr, params, obs):
-    raw = torch.empty((1, obs.shape[1], tr.n_raw), device=DEV)
-    torch.cuda.synchronize()
-    tr.forward(params.data_ptr(), obs.data_ptr(), obs.shape[1], raw.data_ptr())
-    return raw
 
 
 def _fused(tr, pol, obs, d_raw, sq0=0.0):
     """forward + backward_step (RMSprop, no weight decay): CPU copies of (grads, params, square_avg)."""
-    params, sq = _flat(pol), torch.full((1, tr.n_params), sq0, device=DEV)
+    params, sq = TU.flat([pol]), torch.full((1, tr.n_params), sq0, device=DEV)
     grads = torch.full_like(params, float("nan"))
-    _forward(tr, params, obs)
+    TU.forward(tr, params, obs)
     tr.backward_step(params.data_ptr(), d_raw.data_ptr(), obs.shape[1], _capi.rmsprop_opt(**OPT), sq.data_ptr(), grads.data_ptr())
     return grads[0].cpu(), params[0].cpu(), sq[0].cpu()
 
 
 def _deferred(tr, pol, obs, d_raw, kind, clip=0.0, m0=0.0, v0=0.0):
     """forward + backward_step_opt with grad_norms: CPU copies of (grads, params, state0 = square_avg | exp_avg_sq, exp_avg, norm)."""
-    params = _flat(pol)
+    params = TU.flat([pol])
     s0, s1 = torch.full((1, tr.n_params), v0, device=DEV), torch.full((1, tr.n_params), m0, device=DEV)
     grads, norms = torch.full_like(params, float("nan")), torch.full((1,), -1.0, device=DEV)
-    _forward(tr, params, obs)
+    TU.forward(tr, params, obs)
     if kind == "adam":
         opt = _capi.optim("adam", ADAM["lr"], s0.data_ptr(), s1.data_ptr(), eps=ADAM["eps"], betas=ADAM["betas"], grad_clip=clip,
                           grad_norms=norms.data_ptr())
@@ -100,11 +81,11 @@ def test_kink_nets(act):
     is zero exactly where float64's is (ReLU at +-0, ReLU6 at 0 and 6, Hardswish at and below -3), so at ELU's and LeakyReLU's 0
     and one float32 step inside Hardswish's +-3 it is not, and there the tensor's tolerance holds it to float64's derivatives 1,
     0.01, -0.5 and 1.5 (torch's own value at -3 is 0 and at 3 is 1: test_trainer_edges_host.py); the three forms give the same bits."""
-    N = _native()
+    N = TU.native()
     pol = E.kink_net(act)
     desc = _capi.policy_tensors(pol)[0]
     obs, d_raw = E.kink_data()
-    g64, g32 = E.autograd(pol, obs, d_raw, torch.float64), E.autograd(pol, obs, d_raw, torch.float32)
+    g64, g32 = TU.autograd(pol, obs, d_raw, torch.float64), TU.autograd(pol, obs, d_raw, torch.float32)
     o, d = _dev(obs, d_raw)
     tr = N.HipTrainer(desc, 1, 32)
     fused = _fused(tr, pol, o, d)
@@ -135,14 +116,14 @@ def test_dead_rows_keep_their_bits(wide):
     columns that read them and the heads' have a gradient of exactly 0 in float64.  On the device those gradients are 0, and after one
     RMSprop step (weight_decay 0, square_avg 0) and one Adam step (both moments 0) those parameters keep their bits, their state
     stays 0 and nothing is NaN: 0 / (sqrt(0) + eps) is 0."""
-    N = _native()
+    N = TU.native()
     pol = E.kink_net("relu")
     desc = _capi.policy_tensors(pol)[0]
     obs, d_raw = E.kink_data()
-    dead = torch.cat([g.reshape(-1) == 0 for g in E.autograd(pol, obs, d_raw, torch.float64)])
+    dead = torch.cat([g.reshape(-1) == 0 for g in TU.autograd(pol, obs, d_raw, torch.float64)])
     assert int(dead.sum()) >= 9 * 4 + 9 + 9 * 32 + 23 * 9 + 9 + 3 * 9 and not bool(dead.all())
     o, d = _dev(obs, d_raw)
-    before = _flat(pol)[0].cpu()
+    before = TU.flat([pol])[0].cpu()
     tr = N.HipTrainer(desc, 1, 32, wide=True) if wide else N.HipTrainer(desc, 1, 32)
     runs = {"fused rmsprop": _fused(tr, pol, o, d), "deferred rmsprop": _deferred(tr, pol, o, d, "rmsprop")[:3],
             "deferred adam": _deferred(tr, pol, o, d, "adam")[:4]}
@@ -161,7 +142,7 @@ def test_dead_rows_keep_their_bits(wide):
 def test_zero_d_raw_zero_norm(kind, wide):
     """An all-zero d_raw with grad_clip 1 and grad_norms: the norm is exactly 0, the clip coefficient min(1 / (0 + 1e-6), 1) is 1,
     no parameter moves and no state is NaN -- clip_grad_norm_'s own behaviour."""
-    N = _native()
+    N = TU.native()
     pol = E.kink_net("relu")
     desc = _capi.policy_tensors(pol)[0]
     obs, d_raw = E.kink_data()
@@ -171,7 +152,7 @@ def test_zero_d_raw_zero_norm(kind, wide):
     tr.close()
     assert norm == 0.0
     assert bool((grads == 0).all())
-    assert torch.equal(_bits(params), _bits(_flat(pol)[0].cpu()))
+    assert torch.equal(_bits(params), _bits(TU.flat([pol])[0].cpu()))
     assert bool((s0 == 0).all()) and bool((s1 == 0).all())
 
 
@@ -181,20 +162,20 @@ def test_layernorm_constant_row(form):
     """[48, 80] with LayerNorm, 17 rows of which one leaves every first-layer unit at 0 (var = 0, rstd = 1 / sqrt(1e-5), X = 0):
     every tensor's gradient, gamma's and beta's included, against float64 autograd by test_population_trainer_layernorm.py's rule,
     and everything finite."""
-    N = _native()
+    N = TU.native()
     pol = E.layernorm_net()
     desc = _capi.policy_tensors(pol)[0]
     obs, d_raw = E.layernorm_data()
-    g64, g32 = E.autograd(pol, obs, d_raw, torch.float64), E.autograd(pol, obs, d_raw, torch.float32)
+    g64, g32 = TU.autograd(pol, obs, d_raw, torch.float64), TU.autograd(pol, obs, d_raw, torch.float32)
     assert len(g64) == 12
     o, d = _dev(obs, d_raw)
     tr = N.HipTrainer(desc, 1, 32, layernorm=True)
-    raw = _forward(tr, _flat(pol), o)
+    raw = TU.forward(tr, TU.flat([pol]), o)
     out = _fused(tr, pol, o, d) if form == "fused" else _deferred(tr, pol, o, d, "adam")[:4]
     tr.close()
     assert torch.isfinite(raw).all() and all(torch.isfinite(t).all() for t in out)
     _hold_to_autograd(f"LayerNorm constant row {form}", pol, out[0], g64, g32)
-    assert not torch.equal(out[1], _flat(pol)[0].cpu())
+    assert not torch.equal(out[1], TU.flat([pol])[0].cpu())
 
 
 # ------------------------------------------------------------------------------------------------ 257 rows
@@ -222,14 +203,14 @@ def test_257_rows(case):
     """257 rows: gradients against float64 autograd by the form's own file's rule (the wide trainer's factor is 4 sqrt(528 / 256)).
     And rows 0-255 padded to 257 with a row whose d_raw is 0 give the 256-row call's gradients bit for bit (so the same step): the
     17th tile adds zeros to every chain."""
-    N = _native()
+    N = TU.native()
     make, kw, run, factor = ROWS_CASES[case]
     pol = make()
     desc = _capi.policy_tensors(pol)[0]
     g = torch.Generator().manual_seed(79)
     obs = torch.randn((257, pol.state_dim), generator=g)
     d_raw = torch.randn((257, 1 + desc.n_dist), generator=g) / 257
-    g64, g32 = E.autograd(pol, obs, d_raw, torch.float64), E.autograd(pol, obs, d_raw, torch.float32)
+    g64, g32 = TU.autograd(pol, obs, d_raw, torch.float64), TU.autograd(pol, obs, d_raw, torch.float32)
     padded = d_raw.clone()
     padded[256] = 0.0
     tr = N.HipTrainer(desc, 1, 512, **kw)
@@ -245,4 +226,4 @@ def test_257_rows(case):
     names = ("grads", "params", "state0", "state1")
     for a, b, name in zip(pad[:4], short[:4], names):
         assert torch.equal(a, b), f"{name}: 256 rows and the same rows padded to 257 differ"
-    assert not torch.equal(full[0], short[0]) and not torch.equal(short[1], _flat(pol)[0].cpu())
+    assert not torch.equal(full[0], short[0]) and not torch.equal(short[1], TU.flat([pol])[0].cpu())

@@ -1,57 +1,16 @@
 """CPU: the host half of population training (agent/population_trainer.py) -- bind_flat, population_loss against the per-agent
 code it restates, PopulationTrainer's refusals.  The kernels are tested on the GPU in test_population_trainer.py."""
-import copy
-import re
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from alphazero_gym_amd import _capi, run
-from alphazero_gym_amd.agent.agents import ContinuousAgent, DiscreteAgent
-from alphazero_gym_amd.agent.population_trainer import PopulationTrainer, bind_flat, population_loss, population_terms
+from alphazero_gym_amd.agent.agents import DiscreteAgent
+from alphazero_gym_amd.agent.population_trainer import bind_flat, population_loss, population_terms
+from trainer_util import HOST_ACTIONS, HOST_HEADS as HEADS, HOST_ROWS, LOSSES, U, make_agent, make_batch, refused
 
-U = 2.0 ** -24   # float32 unit round-off
-# B is a multiple of 16, the float32 lanes of the widest CPU vector unit: torch's CPU kernels compute an element in their vector body
-# or in their scalar tail depending on where it sits in the tensor, and the two differ in the last bit of exp / log.  With whole
-# vectors per net, an element of net k is computed the same way in the agent's [B, ...] tensors and in the population's [K * B, ...].
-K, B, A = 3, 32, 5
-
-LOSSES = {
-    "alphazero": dict(_target_="alphazero_gym_amd.agent.losses.AlphaZeroLoss", policy_coeff=1.0, value_coeff=0.5, reduction="mean"),
-    "a0c": dict(_target_="alphazero_gym_amd.agent.losses.A0CLoss", tau=0.1, policy_coeff=0.1, alpha=0.05, value_coeff=1.0, reduction="mean"),
-    "a0c_tuned": run.LOSS_TUNED,
-}
-HEADS = {"discrete": dict(), "normal": dict(num_components=1), "gmm2": dict(num_components=2)}
-
-
-def make_agent(head, loss="a0c_tuned", seed=0, hidden=(32, 32), layernorm=False, optimizer=None, grad_clip=0, device="cpu"):
-    torch.manual_seed(seed)
-    opt = optimizer or run.RMSPROP
-    if head == "discrete":
-        cfg = run.DISCRETE_DEFAULTS
-        policy = dict(cfg["policy"], hidden_dimensions=list(hidden), representation_dim=4, action_dim=1, num_actions=A, layernorm=layernorm)
-        return DiscreteAgent(policy_cfg=policy, mcts_cfg=dict(cfg["mcts"], device=device, num_actions=A), loss_cfg=LOSSES[loss],
-                             optimizer_cfg=opt, device=device, **dict(cfg["agent"], grad_clip=grad_clip))
-    cfg = run.CONTINUOUS_DEFAULTS
-    policy = dict(cfg["policy"], hidden_dimensions=list(hidden), representation_dim=3, action_dim=1, action_bound=2.0, layernorm=layernorm,
-                  **HEADS[head])
-    return ContinuousAgent(policy_cfg=policy, mcts_cfg=dict(cfg["mcts"], device=device), loss_cfg=LOSSES[loss], optimizer_cfg=opt,
-                           device=device, **dict(cfg["agent"], grad_clip=grad_clip))
-
-
-def make_batch(head, seed):
-    rng = np.random.RandomState(seed)
-    if head == "discrete":
-        states = rng.randn(B, 4).astype(np.float32)
-        actions = np.tile(np.arange(A, dtype=np.float32), (B, 1))
-    else:
-        states = rng.randn(B, 3).astype(np.float32)
-        actions = rng.uniform(-1.9, 1.9, (B, A)).astype(np.float32)
-    counts = rng.randint(0 if head == "discrete" else 1, 9, (B, A)).astype(np.float32)
-    values = rng.randn(B).astype(np.float32)
-    return states, actions, counts, values
+K, B, A = 3, HOST_ROWS, HOST_ACTIONS
 
 
 def test_bind_flat():
@@ -252,12 +211,4 @@ REFUSALS = {
 @pytest.mark.parametrize("why", list(REFUSALS))
 def test_population_trainer_refuses(why):
     build, reason = REFUSALS[why]
-    agents = build()
-    before = copy.deepcopy([a.nn.state_dict() for a in agents])
-    ptrs = [[p.data_ptr() for p in a.nn.parameters()] for a in agents]
-    with pytest.raises(ValueError, match=re.escape(reason)):
-        PopulationTrainer(agents)
-    for a, sd, pp in zip(agents, before, ptrs):   # a refused population is left as it was: same values, same storage, no optimiser state
-        for name, v in a.nn.state_dict().items():
-            assert torch.equal(v, sd[name])
-        assert [p.data_ptr() for p in a.nn.parameters()] == pp and not a.optimizer.state
+    refused(build(), reason)

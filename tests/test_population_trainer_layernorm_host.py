@@ -1,42 +1,23 @@
 """CPU: the host half of training LayerNorm trunks in the population trainer -- PopulationTrainer(layernorm=True) no longer refuses
 LayerNorm agents (the CPU refusal, which comes last, is what is left), what it still refuses, and the azg_trainer_create_ex binding.
 The kernels are tested on the GPU in test_population_trainer_layernorm.py."""
-import copy
 import ctypes as C
+import functools
 import os
 import re
 
 import pytest
 import torch
 
-from alphazero_gym_amd import _capi, run
-from alphazero_gym_amd.agent.agents import ContinuousAgent
+from alphazero_gym_amd import _capi
 from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
+from trainer_util import normal_agent, refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ADAM = dict(_target_="torch.optim.Adam", lr=1e-3)
 
 
-def make_agent(seed=0, hidden=(32, 32), layernorm=True, optimizer=None, grad_clip=0):
-    torch.manual_seed(seed)
-    cfg = run.CONTINUOUS_DEFAULTS
-    policy = dict(cfg["policy"], hidden_dimensions=list(hidden), representation_dim=3, action_dim=1, action_bound=2.0, layernorm=layernorm,
-                  num_components=1)
-    return ContinuousAgent(policy_cfg=policy, mcts_cfg=dict(cfg["mcts"], device="cpu"), loss_cfg=run.LOSS_TUNED,
-                           optimizer_cfg=optimizer or run.RMSPROP, device="cpu", **dict(cfg["agent"], grad_clip=grad_clip))
-
-
-def _refused(agents, reason, **kw):
-    """PopulationTrainer(agents, **kw) raises a ValueError naming ``reason`` and leaves the agents as they were: same values, same
-    storage, no optimiser state."""
-    before = copy.deepcopy([a.nn.state_dict() for a in agents])
-    ptrs = [[p.data_ptr() for p in a.nn.parameters()] for a in agents]
-    with pytest.raises(ValueError, match=re.escape(reason)):
-        PopulationTrainer(agents, **kw)
-    for a, sd, pp in zip(agents, before, ptrs):
-        for name, v in a.nn.state_dict().items():
-            assert torch.equal(v, sd[name])
-        assert [p.data_ptr() for p in a.nn.parameters()] == pp and not a.optimizer.state
+make_agent = functools.partial(normal_agent, hidden=(32, 32), layernorm=True)
 
 
 @pytest.mark.parametrize("form", ["rmsprop", "agents_adam_clip"])
@@ -46,19 +27,19 @@ def test_layernorm_agents_reach_the_last_refusal(form):
         agents, kw = [make_agent(s) for s in range(2)], {}
     else:
         agents, kw = [make_agent(s, optimizer=ADAM, grad_clip=0.5) for s in range(2)], dict(optimizers="agents")
-    _refused(agents, "must live on one GPU", layernorm=True, **kw)
+    refused(agents, "must live on one GPU", layernorm=True, **kw)
     # plain agents are taken by such a trainer as well
     plain = [make_agent(s, layernorm=False) for s in range(2)]
-    _refused(plain, "must live on one GPU", layernorm=True, **kw)
+    refused(plain, "must live on one GPU", layernorm=True, **kw)
 
 
 def test_default_still_refuses_layernorm():
-    _refused([make_agent(s) for s in range(2)], "LayerNorm")
-    _refused([make_agent(s) for s in range(2)], "LayerNorm", layernorm=False)
+    refused([make_agent(s) for s in range(2)], "LayerNorm")
+    refused([make_agent(s) for s in range(2)], "LayerNorm", layernorm=False)
 
 
 def test_mixed_layernorm_and_plain_is_another_shape():
-    _refused([make_agent(0), make_agent(1, layernorm=False)], "same network shape", layernorm=True)
+    refused([make_agent(0), make_agent(1, layernorm=False)], "same network shape", layernorm=True)
 
 
 @pytest.mark.parametrize("kw", [dict(eps=1e-3), dict(elementwise_affine=False)], ids=["eps", "no_affine"])

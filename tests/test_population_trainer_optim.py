@@ -11,80 +11,40 @@ import numpy as np
 import pytest
 import torch
 
+import trainer_util as TU
 from alphazero_gym_amd import _capi, run
-from alphazero_gym_amd.agent.agents import ContinuousAgent, DiscreteAgent
 from alphazero_gym_amd.agent.buffers import DeviceReplay
 from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
-from test_population_trainer import DEV, OPT, SHAPES, _data, _e2e_agents, _flat, _native, _policy, _step, _twin
+from trainer_util import ADAM, DEV, DIMS, OPT
 
 pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
 
-ADAM = dict(lr=1e-3, betas=(0.9, 0.99), eps=1e-7)   # the reference's Adam settings
+SHAPES = TU.NARROW
 TWO = [(SHAPES[0], 1), (SHAPES[2], 17)]              # a width-16 single layer with one row; three layers with padded rows
-
-
-def _sizes(pol):
-    return [t.numel() for t in _capi.policy_tensors(pol)[1]]
-
-
-def _forward(tr, params, obs):
-    K, B = obs.shape[:2]
-    raw = torch.empty((K, B, tr.n_raw), device=DEV)
-    torch.cuda.synchronize()
-    tr.forward(params.data_ptr(), obs.data_ptr(), B, raw.data_ptr())
-    return raw
-
-
-def _step_opt(tr, params, obs, d_raw, make_opt):
-    """forward + backward_step_opt; make_opt(grad_norms address) -> azg_optim.  Returns (grads, grad_norms)."""
-    K, B = obs.shape[:2]
-    _forward(tr, params, obs)
-    grads, norms = torch.zeros_like(params), torch.full((K,), -1.0, device=DEV)
-    tr.backward_step_opt(params.data_ptr(), d_raw.data_ptr(), B, make_opt(norms.data_ptr()), grads.data_ptr())
-    return grads, norms
-
-
-def _ulp(x):
-    """One float32 unit in the last place of every element of the (float64) tensor x."""
-    return torch.from_numpy(np.spacing(np.abs(x.numpy()).astype(np.float32))).double()
-
-
-def _against_yardstick(name, got, truth, yard, sizes, fails):
-    """Per parameter tensor: the kernel's error against the float64 truth is at most 4 x the float32 yardstick's largest error
-    plus one ulp of the element."""
-    off = 0
-    for i, n in enumerate(sizes):
-        sl = slice(off, off + n)
-        off += n
-        e_k, e_y = (got[sl].double() - truth[sl]).abs(), (yard[sl].double() - truth[sl]).abs()
-        print(f"{name} tensor {i}: float32 torch error {float(e_y.max()):.3g}, kernel error {float(e_k.max()):.3g}")
-        if not torch.all(e_k <= 4 * e_y.max() + _ulp(truth[sl])):
-            fails.append((name, i, float(e_y.max()), float(e_k.max())))
-    assert off == got.numel()
 
 
 @pytest.mark.parametrize("shape,B", TWO, ids=["16_normal_B1", "3x128_gmm2_B17"])
 def test_plain_rmsprop_runs_the_fused_kernel(shape, B):
     """backward_step_opt with RMSprop, no clipping and no grad_norms against backward_step: the same bits."""
-    N = _native()
+    N = TU.native()
     in_dim, hidden, head, act = shape
     K = 2
-    pols = [_policy(in_dim, hidden, head, act, 60 + k) for k in range(K)]
+    pols = [TU.policy(in_dim, hidden, head, act, 60 + k) for k in range(K)]
     desc = _capi.policy_tensors(pols[0])[0]
-    obs, d_raw = (t.to(DEV) for t in _data(K, B, in_dim, 1 + desc.n_dist, 5))
+    obs, d_raw = (t.to(DEV) for t in TU.data(K, B, in_dim, 1 + desc.n_dist, 5))
     tr = N.HipTrainer(desc, K, 64)
-    p0, s0 = _flat(pols), torch.full((K, tr.n_params), 0.25, device=DEV)
-    _, g0 = _step(tr, p0, obs, d_raw, _capi.rmsprop_opt(weight_decay=1e-4, **OPT), s0)
-    p1, s1 = _flat(pols), torch.full((K, tr.n_params), 0.25, device=DEV)
-    _forward(tr, p1, obs)
+    p0, s0 = TU.flat(pols), torch.full((K, tr.n_params), 0.25, device=DEV)
+    _, g0 = TU.step(tr, p0, obs, d_raw, _capi.rmsprop_opt(weight_decay=1e-4, **OPT), s0)
+    p1, s1 = TU.flat(pols), torch.full((K, tr.n_params), 0.25, device=DEV)
+    TU.forward(tr, p1, obs)
     g1 = torch.zeros_like(p1)
     tr.backward_step_opt(p1.data_ptr(), d_raw.data_ptr(), B, _capi.optim("rmsprop", OPT["lr"], s1.data_ptr(), alpha=OPT["alpha"],
                                                                           eps=OPT["eps"], weight_decay=1e-4), g1.data_ptr())
     tr.close()
     assert torch.equal(p0, p1) and torch.equal(s0, s1) and torch.equal(g0, g1)
-    assert not torch.equal(p0, _flat(pols))
+    assert not torch.equal(p0, TU.flat(pols))
 
 
 @pytest.mark.parametrize("shape,B", TWO, ids=["16_normal_B1", "3x128_gmm2_B17"])
@@ -92,21 +52,21 @@ def test_deferred_gradients_and_norm(shape, B):
     """The deferred form (Adam) hands back the fused form's gradients bit for bit, and grad_norms is sqrt(sum g^2) of them: the
     kernel's sum is float64 (exact products, 2^-53-scale chain error) rounded to float32 once, so it lies within one float32 ulp
     of the float64 value however that is summed."""
-    N = _native()
+    N = TU.native()
     in_dim, hidden, head, act = shape
     K = 2
-    pols = [_policy(in_dim, hidden, head, act, 60 + k) for k in range(K)]
+    pols = [TU.policy(in_dim, hidden, head, act, 60 + k) for k in range(K)]
     desc = _capi.policy_tensors(pols[0])[0]
-    obs, d_raw = (t.to(DEV) for t in _data(K, B, in_dim, 1 + desc.n_dist, 5))
+    obs, d_raw = (t.to(DEV) for t in TU.data(K, B, in_dim, 1 + desc.n_dist, 5))
     tr = N.HipTrainer(desc, K, 64)
-    p0 = _flat(pols)
-    _, g0 = _step(tr, p0, obs, d_raw, _capi.rmsprop_opt(**OPT), torch.zeros((K, tr.n_params), device=DEV))
-    p1, m, v = _flat(pols), torch.zeros((K, tr.n_params), device=DEV), torch.zeros((K, tr.n_params), device=DEV)
-    g1, norms = _step_opt(tr, p1, obs, d_raw, lambda n: _capi.optim("adam", ADAM["lr"], v.data_ptr(), m.data_ptr(), eps=ADAM["eps"],
+    p0 = TU.flat(pols)
+    _, g0 = TU.step(tr, p0, obs, d_raw, _capi.rmsprop_opt(**OPT), torch.zeros((K, tr.n_params), device=DEV))
+    p1, m, v = TU.flat(pols), torch.zeros((K, tr.n_params), device=DEV), torch.zeros((K, tr.n_params), device=DEV)
+    _, g1, norms = TU.step_opt(tr, p1, obs, d_raw, lambda n: _capi.optim("adam", ADAM["lr"], v.data_ptr(), m.data_ptr(), eps=ADAM["eps"],
                                                                    betas=ADAM["betas"], grad_norms=n))
     tr.close()
     assert torch.equal(g0, g1)
-    assert not torch.equal(p1, _flat(pols)) and bool((m != 0).any()) and bool((v != 0).any())
+    assert not torch.equal(p1, TU.flat(pols)) and bool((m != 0).any()) and bool((v != 0).any())
     for k in range(K):
         want = float(torch.sqrt((g1[k].cpu().double() ** 2).sum()))
         got = float(norms[k])
@@ -117,23 +77,23 @@ def test_deferred_gradients_and_norm(shape, B):
 def test_clip():
     """RMSprop with clip_grad_norm_: a net whose norm is below the bound steps exactly as without clipping (coef == 1), a net above
     it as float64 clip_grad_norm_ + torch.optim.RMSprop step from the kernel's own gradients."""
-    N = _native()
+    N = TU.native()
     in_dim, hidden, head, act = SHAPES[1]
     K, B = 3, 64
-    pols = [_policy(in_dim, hidden, head, act, 80 + k) for k in range(K)]
+    pols = [TU.policy(in_dim, hidden, head, act, 80 + k) for k in range(K)]
     desc = _capi.policy_tensors(pols[0])[0]
-    obs, d_raw = _data(K, B, in_dim, 1 + desc.n_dist, 9)
+    obs, d_raw = TU.data(K, B, in_dim, 1 + desc.n_dist, 9)
     d_raw[0] *= 1e-3
     d_raw[2] *= 1e3
     obs, d_raw = obs.to(DEV), d_raw.to(DEV)
     tr = N.HipTrainer(desc, K, 64)
     mk = lambda sq, clip: (lambda n: _capi.optim("rmsprop", OPT["lr"], sq.data_ptr(), alpha=OPT["alpha"], eps=OPT["eps"],   # noqa: E731
                                                  grad_clip=clip, grad_norms=n))
-    pa, sa = _flat(pols), torch.zeros((K, tr.n_params), device=DEV)
-    ga, na = _step_opt(tr, pa, obs, d_raw, mk(sa, 0.0))
+    pa, sa = TU.flat(pols), torch.zeros((K, tr.n_params), device=DEV)
+    _, ga, na = TU.step_opt(tr, pa, obs, d_raw, mk(sa, 0.0))
     clip = float(na[1])
-    pb, sb = _flat(pols), torch.zeros((K, tr.n_params), device=DEV)
-    gb, nb = _step_opt(tr, pb, obs, d_raw, mk(sb, clip))
+    pb, sb = TU.flat(pols), torch.zeros((K, tr.n_params), device=DEV)
+    _, gb, nb = TU.step_opt(tr, pb, obs, d_raw, mk(sb, clip))
     tr.close()
     print(f"clip: norms {na.tolist()}, bound {clip}")
     assert float(nb[0]) < clip < float(nb[2])
@@ -142,144 +102,35 @@ def test_clip():
     assert not torch.equal(pa[2], pb[2])
     res = {}
     for dtype in (torch.float64, torch.float32):
-        p = _flat(pols)[2].cpu().to(dtype).clone().requires_grad_(True)
+        p = TU.flat(pols)[2].cpu().to(dtype).clone().requires_grad_(True)
         p.grad = gb[2].cpu().to(dtype)
         torch.nn.utils.clip_grad_norm_([p], clip)
         o = torch.optim.RMSprop([p], momentum=0, centered=False, foreach=False, **OPT)
         o.step()
         res[dtype] = (p.detach(), o.state[p]["square_avg"])
-    fails, sizes = [], _sizes(pols[0])
-    _against_yardstick("clip params", pb[2].cpu(), res[torch.float64][0], res[torch.float32][0], sizes, fails)
-    _against_yardstick("clip square_avg", sb[2].cpu(), res[torch.float64][1], res[torch.float32][1], sizes, fails)
+    fails, sizes = [], TU.sizes(pols[0])
+    TU.against_yardstick("clip params", pb[2].cpu(), res[torch.float64][0], res[torch.float32][0], sizes, fails)
+    TU.against_yardstick("clip square_avg", sb[2].cpu(), res[torch.float64][1], res[torch.float32][1], sizes, fails)
     assert not fails, fails
 
 
 @pytest.mark.parametrize("weight_decay", [0.0, 1e-4])
 def test_adam_step_given_gradient(weight_decay):
-    """Three consecutive steps from step 0 and one from step 1000.  Truth: torch.optim.Adam (single-tensor) in float64 on the CPU, fed
-    the kernel's gradients and restarted every step from the kernel's parameters and state; yardstick: the same in float32."""
-    N = _native()
-    in_dim, hidden, head, act = SHAPES[2]
-    pol = _policy(in_dim, hidden, head, act, 31)
-    desc = _capi.policy_tensors(pol)[0]
-    tr = N.HipTrainer(desc, 1, 512)
-    params = _flat([pol])
-    m, v = torch.zeros_like(params), torch.zeros_like(params)
-    sizes, fails = _sizes(pol), []
-    for i, step in enumerate((0, 1, 2, 1000)):
-        obs, d_raw = _data(1, 64, in_dim, 1 + desc.n_dist, 40 + i)
-        before = [t[0].cpu().clone() for t in (params, m, v)]
-        grads, _ = _step_opt(tr, params, obs.to(DEV), d_raw.to(DEV),
-                             lambda n: _capi.optim("adam", ADAM["lr"], v.data_ptr(), m.data_ptr(), eps=ADAM["eps"], betas=ADAM["betas"],
-                                                   weight_decay=weight_decay, step=step))
-        res = {}
-        for dtype in (torch.float64, torch.float32):
-            p = before[0].to(dtype).clone().requires_grad_(True)
-            p.grad = grads[0].cpu().to(dtype)
-            o = torch.optim.Adam([p], weight_decay=weight_decay, amsgrad=False, foreach=False, **ADAM)
-            if step:
-                o.state[p] = {"step": torch.tensor(float(step)), "exp_avg": before[1].to(dtype).clone(), "exp_avg_sq": before[2].to(dtype).clone()}
-            o.step()
-            assert float(o.state[p]["step"]) == step + 1
-            res[dtype] = (p.detach(), o.state[p]["exp_avg"], o.state[p]["exp_avg_sq"])
-        for j, (name, got) in enumerate((("params", params), ("exp_avg", m), ("exp_avg_sq", v))):
-            _against_yardstick(f"adam step {step} wd {weight_decay} {name}", got[0].cpu(), res[torch.float64][j], res[torch.float32][j], sizes, fails)
-        assert not torch.equal(params[0].cpu(), before[0])
-    tr.close()
-    assert not fails, fails
+    """Three consecutive steps from step 0 and one from step 1000, no clip."""
+    TU.check_adam_step_given_gradient(SHAPES[2], None, TU.policy(*SHAPES[2], 31), weight_decay, (0, 1, 2, 1000),
+                                      f"adam step {{step}} wd {weight_decay}")
 
 
 @pytest.mark.parametrize("B", [1, 17, 128])
 @pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[2], SHAPES[3]], ids=["16_normal", "3x128_gmm2", "256x16_discrete3"])
 def test_population_invariance(shape, B):
-    """Adam + grad_clip + weight_decay: net k of a K = 5 trainer equals a K = 1 trainer on net k's data bit for bit, and so do two
-    runs of the same call."""
-    N = _native()
-    in_dim, hidden, head, act = shape
-    K = 5
-    pols = [_policy(in_dim, hidden, head, act, 50 + k) for k in range(K)]
-    desc = _capi.policy_tensors(pols[0])[0]
-    obs, d_raw = (t.to(DEV) for t in _data(K, B, in_dim, 1 + desc.n_dist, 7))
-
-    def run_once(tr, ks):
-        n = len(ks)
-        params = _flat([pols[k] for k in ks])
-        m, v = torch.full((n, tr.n_params), 0.01, device=DEV), torch.full((n, tr.n_params), 0.25, device=DEV)
-        o, d = obs[ks].contiguous(), d_raw[ks].contiguous()
-        grads, norms = _step_opt(tr, params, o, d, lambda nn: _capi.optim("adam", ADAM["lr"], v.data_ptr(), m.data_ptr(), eps=ADAM["eps"],
-                                                                          betas=ADAM["betas"], weight_decay=1e-4, grad_clip=0.05, step=3,
-                                                                          grad_norms=nn))
-        return [t.cpu() for t in (params, m, v, grads, norms)]
-
-    names = ("params", "exp_avg", "exp_avg_sq", "grads", "grad_norms")
-    runs = []
-    for _ in range(2):
-        tr = N.HipTrainer(desc, K, 512)
-        runs.append(run_once(tr, list(range(K))))
-        tr.close()
-    for a, b, name in zip(runs[0], runs[1], names):
-        assert torch.equal(a, b), f"{name}: two runs differ"
-    assert torch.isfinite(runs[0][0]).all() and not torch.equal(runs[0][0], _flat(pols).cpu())
-    tr1 = N.HipTrainer(desc, 1, 512)
-    for k in range(K):
-        for a, b, name in zip(runs[0], run_once(tr1, [k]), names):
-            assert torch.equal(a[k], b[0]), f"{name} of net {k}: K = 5 and K = 1 differ"
-    tr1.close()
+    """Adam + grad_clip + weight_decay, K = 5."""
+    TU.check_population_invariance(shape, B, None, [TU.policy(*shape, 50 + k) for k in range(5)], forms=("adam",), grad_clip=0.05)
 
 
-LOSS_TUNED = dict(run.LOSS_TUNED, device=DEV)
-ADAM_CFG = dict(run.ADAM, weight_decay=1e-4)
-DIMS = {"discrete": (4, 2), "gmm2": (3, 4)}
-
-
-def make_agents(head, K, first_seed=0, clip=0.5):
-    """A0C-tuned agents with the reference's Adam settings and a grad_clip; net k's weights from torch.manual_seed(first_seed + k)."""
-    agents = []
-    for k in range(K):
-        torch.manual_seed(first_seed + k)
-        if head == "discrete":
-            cfg = run.DISCRETE_DEFAULTS
-            policy = dict(cfg["policy"], hidden_dimensions=[32, 32], representation_dim=4, action_dim=1, num_actions=2)
-            agents.append(DiscreteAgent(policy_cfg=policy, mcts_cfg=dict(cfg["mcts"], device=DEV, num_actions=2), loss_cfg=LOSS_TUNED,
-                                        optimizer_cfg=ADAM_CFG, device=DEV, **dict(cfg["agent"], grad_clip=clip)))
-        else:
-            cfg = run.CONTINUOUS_DEFAULTS
-            policy = dict(cfg["policy"], hidden_dimensions=[32, 16], representation_dim=3, action_dim=1, action_bound=2.0, num_components=2)
-            agents.append(ContinuousAgent(policy_cfg=policy, mcts_cfg=dict(cfg["mcts"], device=DEV), loss_cfg=LOSS_TUNED,
-                                          optimizer_cfg=ADAM_CFG, device=DEV, **dict(cfg["agent"], grad_clip=clip)))
-    return agents
-
-
-def make_rows(head, K, n, seed):
-    """[K, n, row] float32 on the GPU: obs | actions[A] | counts[A] | Q[A] | V."""
-    S, A = DIMS[head]
-    rng = np.random.RandomState(seed)
-    obs = rng.randn(K, n, S)
-    if head == "discrete":
-        actions, counts = np.tile(np.arange(A, dtype=np.float64), (K, n, 1)), rng.randint(0, 9, (K, n, A))
-    else:
-        actions, counts = rng.uniform(-1.9, 1.9, (K, n, A)), rng.randint(1, 9, (K, n, A))
-    return torch.from_numpy(np.concatenate([obs, actions, counts, rng.randn(K, n, A), rng.randn(K, n, 1)], axis=-1).astype(np.float32)).to(DEV)
-
-
-def state_of(tr, rows_of_d_raw=None):
-    """Everything a step may change, as CPU copies (and the d_raw the native trainer holds)."""
-    s = dict(flat=tr.flat, exp_avg=tr.exp_avg, exp_avg_sq=tr.exp_avg_sq, log_alpha=tr.log_alpha, alpha_exp_avg=tr.alpha_exp_avg,
-             alpha_exp_avg_sq=tr.alpha_exp_avg_sq, grad_norms=tr.last_grad_norms)
-    out = {k: v.detach().cpu().clone() for k, v in s.items()}
-    out["steps"] = torch.tensor([tr.alpha_step, tr.opt_step])
-    if rows_of_d_raw:
-        d = torch.empty((len(tr.agents), rows_of_d_raw, tr.trainer.n_raw), device=DEV)
-        torch.cuda.synchronize()
-        tr.trainer.read_d_raw(rows_of_d_raw, d.data_ptr())
-        out["d_raw"] = d.cpu()
-    return out
-
-
-def assert_same(a, b, what):
-    assert set(a) == set(b)
-    for key in a:
-        assert torch.equal(a[key], b[key]), f"{what}: {key} differs"
+def _adam_agents(head, K, first_seed=0):
+    """A0C-tuned agents with the reference's Adam settings, weight decay and a grad_clip of 0.5."""
+    return TU.make_agents(head, "a0c_tuned", K, first_seed, optimizer=TU.ADAM_WD, clip=0.5)
 
 
 @pytest.mark.parametrize("head", ["discrete", "gmm2"])
@@ -287,10 +138,10 @@ def test_step_is_forward_loss_backward(head):
     """step_opt against azg_trainer_forward + azg_trainer_loss + backward_step_opt on the same inputs."""
     K, B = 3, 24
     S, A = DIMS[head]
-    one = PopulationTrainer(make_agents(head, K), max_batch=64, losses="device", optimizers="agents")
-    parts = PopulationTrainer(make_agents(head, K), max_batch=64, losses="device", optimizers="agents")
-    rows = make_rows(head, K, B, 3)
-    batch = (rows[..., :S], rows[..., S:S + A], rows[..., S + A:S + 2 * A], rows[..., S + 2 * A:S + 3 * A], rows[..., -1])
+    one = PopulationTrainer(_adam_agents(head, K), max_batch=64, losses="device", optimizers="agents")
+    parts = PopulationTrainer(_adam_agents(head, K), max_batch=64, losses="device", optimizers="agents")
+    rows = TU.make_rows(head, K, B, 3)
+    batch = TU.split_rows(rows, S, A)
     got = one.update(batch)
     obs, actions, counts, values = (t.contiguous() for t in (batch[0], batch[1], batch[2], batch[4]))
     t = parts.trainer
@@ -303,7 +154,7 @@ def test_step_is_forward_loss_backward(head):
            d_raw.data_ptr(), table.data_ptr())
     t.backward_step_opt(parts.flat.data_ptr(), d_raw.data_ptr(), B, parts._optim())
     parts.alpha_step, parts.opt_step = 1, 1
-    assert_same(state_of(one), state_of(parts), "step_opt against its parts")
+    TU.assert_same(TU.state_of_agents_optimisers(one), TU.state_of_agents_optimisers(parts), "step_opt against its parts")
     assert torch.equal(one.last_d_raw, d_raw) and torch.equal(one.last_raw, raw)
     want = table.cpu().tolist()
     for k in range(K):
@@ -319,15 +170,15 @@ def test_epoch_is_its_steps(head):
     """epoch_opt (the array form) against its two minibatches, 16 + 24 rows, passed one by one to step_opt with step + m."""
     K, n, batch = 3, 40, 16
     S, A = DIMS[head]
-    ref = PopulationTrainer(make_agents(head, K), max_batch=64, losses="device", optimizers="agents")
-    ep = PopulationTrainer(make_agents(head, K), max_batch=64, losses="device", optimizers="agents")
+    ref = PopulationTrainer(_adam_agents(head, K), max_batch=64, losses="device", optimizers="agents")
+    ep = PopulationTrainer(_adam_agents(head, K), max_batch=64, losses="device", optimizers="agents")
     for epoch in range(2):   # (the second epoch starts from Adam step 2)
-        rows = make_rows(head, K, n, 100 + epoch)
+        rows = TU.make_rows(head, K, n, 100 + epoch)
         seeds = [11 + epoch, 22, 33]
         want = ref.train_on_rows(rows, S, A, batch_size=batch, shuffle_seeds=seeds)
         got = ep.train_epoch(rows, S, A, batch_size=batch, shuffle_seeds=seeds)
         assert got == want and all(np.isfinite(v) for g in got for v in g.values())
-        assert_same(state_of(ref, 24), state_of(ep, 24), f"epoch {epoch}")
+        TU.assert_same(TU.state_of_agents_optimisers(ref, 24), TU.state_of_agents_optimisers(ep, 24), f"epoch {epoch}")
         assert ep.opt_step == ep.alpha_step == 2 * (epoch + 1)
     ref.close()
     ep.close()
@@ -337,20 +188,20 @@ def test_ring_epoch_is_its_steps():
     """epoch_opt on the self-play ring (K = 3, T = 4, 10 steps: 40 rows per net, minibatches of 16 + 24) against step_opt on copies."""
     K, T, steps, batch = 3, 4, 10, 16
     S, A = DIMS["discrete"]
-    agents = make_agents("discrete", K)
+    agents = _adam_agents("discrete", K)
     sp = run.PopulationSelfPlay([a.nn for a in agents], game="CartPole-v0", games_per_net=T, n_rollouts=8, c_uct=1.5, epsilon=0.1,
                                 capacity_steps=16)
     assert sp.play_device(steps) == (steps, 0)
     copies = torch.stack(sp._split(DeviceReplay(sp.engine, 1).rows(), steps))
     n = steps * T
     ring = PopulationTrainer(agents, max_batch=64, losses="device", optimizers="agents")
-    ref = PopulationTrainer(make_agents("discrete", K), max_batch=64, losses="device", optimizers="agents")
+    ref = PopulationTrainer(_adam_agents("discrete", K), max_batch=64, losses="device", optimizers="agents")
     seeds = [3, 1, 4]
     order = np.stack([np.random.RandomState(s).permutation(n) for s in seeds])
     got = ring.train_epoch_ring(sp, order, batch_size=batch)
     want = ref.train_on_rows(copies, S, A, batch_size=batch, shuffle_seeds=seeds)
     assert got == want
-    assert_same(state_of(ring, 24), state_of(ref, 24), "ring")
+    TU.assert_same(TU.state_of_agents_optimisers(ring, 24), TU.state_of_agents_optimisers(ref, 24), "ring")
     assert ring.opt_step == ring.alpha_step == 2
     ring.close()
     ref.close()
@@ -359,7 +210,7 @@ def test_ring_epoch_is_its_steps():
 
 def _f64_step(kind, cfg, agent, batch, clip):
     """The agent's optimiser step in float64 on the CPU: (parameters after it, the gradient norm before clipping)."""
-    a = _twin(kind, cfg, agent, "cpu", torch.float64)
+    a = TU.twin(kind, cfg, agent, "cpu", torch.float64)
     s, ac, c, _, v = (x.detach().cpu().double() for x in batch)
     a.optimizer.zero_grad(set_to_none=True)
     a._loss(s, ac, c, v.reshape(-1, 1))["loss"].backward()
@@ -374,7 +225,7 @@ def test_end_to_end_update(kind, losses):
     """PopulationTrainer(optimizers="agents").update of K = 4 default agents with the reference's Adam settings and a grad_clip
     against their float64 twins' steps, float32 agent.update twins as the yardstick."""
     K, clip = 4, 0.1
-    cfg, _ = _e2e_agents(kind, 0)
+    cfg, _ = TU.e2e_agents(kind, 0)
     cfg["optimizer"] = dict(run.ADAM)
     cfg["agent"] = dict(cfg["agent"], grad_clip=clip)
     from alphazero_gym_amd.envs import make_game
@@ -390,11 +241,11 @@ def test_end_to_end_update(kind, losses):
     rows = sp.collect_device(8)
     S, A = sp.engine.s_obs, sp.engine.kmax
     sp.close()
-    batches = [(r[:, :S], r[:, S:S + A], r[:, S + A:S + 2 * A], r[:, S + 2 * A:S + 3 * A], r[:, -1]) for r in rows]
+    batches = TU.batches(rows, S, A)
     truth = [_f64_step(kind, cfg, a, b, clip) for a, b in zip(agents, batches)]
     print(f"{kind}: float64 gradient norms {[t[1] for t in truth]}, grad_clip {clip}")
     assert any(t[1] > clip for t in truth)
-    yard_agents = [_twin(kind, cfg, a, DEV) for a in agents]
+    yard_agents = [TU.twin(kind, cfg, a, DEV) for a in agents]
     yard = [y.update(b) for y, b in zip(yard_agents, batches)]
     tr = PopulationTrainer(agents, optimizers="agents", losses=losses)
     got = tr.update(batches)
@@ -409,7 +260,7 @@ def test_end_to_end_update(kind, losses):
             off += want.numel()
             e_y, e_t = (y.detach().cpu().double() - want).abs().max(), (mine - want).abs()
             print(f"{kind} {losses} net {k} tensor {i}: agent.update float32 distance {float(e_y):.3g}, trainer distance {float(e_t.max()):.3g}")
-            if not torch.all(e_t <= 4 * e_y + _ulp(want)):
+            if not torch.all(e_t <= 4 * e_y + TU.ulp(want)):
                 fails.append((k, i, float(e_y), float(e_t.max())))
     assert not fails, fails
     before = tr.flat.clone()
@@ -428,13 +279,13 @@ def test_end_to_end_update(kind, losses):
 
 
 def test_abi_errors():
-    N = _native()
+    N = TU.native()
     desc = _capi.make_desc(4, [32, 32], 2, "relu")
     tr = N.HipTrainer(desc, 2, 64)
     params = torch.randn((2, tr.n_params), device=DEV)
     m, v = torch.zeros_like(params), torch.full_like(params, 0.25)
     keep = [t.clone() for t in (params, m, v)]
-    obs, d_raw = (t.to(DEV) for t in _data(2, 64, 4, 3, 1))
+    obs, d_raw = (t.to(DEV) for t in TU.data(2, 64, 4, 3, 1))
     raw = torch.zeros((2, 64, 3), device=DEV)
     P, O, D, R, M, V = (t.data_ptr() for t in (params, obs, d_raw, raw, m, v))
     torch.cuda.synchronize()

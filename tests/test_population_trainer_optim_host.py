@@ -3,7 +3,6 @@ refuses, the azg_optim binding and the example's flags.  The kernels are tested 
 import copy
 import ctypes as C
 import os
-import re
 import sys
 
 import pytest
@@ -11,26 +10,11 @@ import torch
 
 from alphazero_gym_amd import _capi, run
 from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
-from test_population_trainer_host import make_agent
+from trainer_util import make_agent, make_batch, refused
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
 
 ADAM = dict(run.ADAM)
-
-
-def _check_untouched(agents, before, ptrs):
-    for a, sd, pp in zip(agents, before, ptrs):
-        for name, v in a.nn.state_dict().items():
-            assert torch.equal(v, sd[name])
-        assert [p.data_ptr() for p in a.nn.parameters()] == pp and not a.optimizer.state
-
-
-def _refused(agents, reason, **kw):
-    before = copy.deepcopy([a.nn.state_dict() for a in agents])
-    ptrs = [[p.data_ptr() for p in a.nn.parameters()] for a in agents]
-    with pytest.raises(ValueError, match=re.escape(reason)):
-        PopulationTrainer(agents, **kw)
-    _check_untouched(agents, before, ptrs)
 
 
 # The agents live on the CPU, which PopulationTrainer refuses last of all: agents refused for that reason passed every other check.
@@ -44,7 +28,7 @@ ACCEPTED = {
 
 @pytest.mark.parametrize("what", list(ACCEPTED))
 def test_agents_optimisers_pass_every_host_check(what):
-    _refused(ACCEPTED[what](), "must live on one GPU", optimizers="agents")
+    refused(ACCEPTED[what](), "must live on one GPU", optimizers="agents")
 
 
 REFUSALS = {
@@ -66,16 +50,15 @@ REFUSALS = {
 @pytest.mark.parametrize("why", list(REFUSALS))
 def test_agents_optimisers_refusals(why):
     build, reason = REFUSALS[why]
-    _refused(build(), reason, optimizers="agents")
+    refused(build(), reason, optimizers="agents")
 
 
 def test_bad_optimizers_value():
-    _refused([make_agent("normal") for _ in range(2)], "optimizers must be 'rmsprop' or 'agents'", optimizers="adam")
+    refused([make_agent("normal") for _ in range(2)], "optimizers must be 'rmsprop' or 'agents'", optimizers="adam")
 
 
 def test_adam_step_counts_must_agree():
     """One agent has taken an Adam step, the other has not: refused, and the optimiser state that was there stays."""
-    from test_population_trainer_host import make_batch
     agents = [make_agent("normal", optimizer=ADAM, seed=s) for s in range(2)]
     states, actions, counts, values = make_batch("normal", 3)
     agents[0].update((states, actions, counts, None, values))
@@ -90,9 +73,9 @@ def test_adam_step_counts_must_agree():
 
 def test_default_keeps_its_refusals():
     """optimizers="rmsprop" is the default and says what it always said."""
-    _refused([make_agent("normal", optimizer=dict(_target_="torch.optim.Adam", lr=1e-3)) for _ in range(2)],
+    refused([make_agent("normal", optimizer=dict(_target_="torch.optim.Adam", lr=1e-3)) for _ in range(2)],
              "must be torch.optim.RMSprop, not Adam", optimizers="rmsprop")
-    _refused([make_agent("normal", grad_clip=1.0) for _ in range(2)],
+    refused([make_agent("normal", grad_clip=1.0) for _ in range(2)],
              "grad_clip != 0 is not supported (a per-net global norm needs a pass of its own)")
 
 

@@ -7,11 +7,12 @@ import numpy as np
 import pytest
 import torch
 
+import trainer_util as TU
 from alphazero_gym_amd import _capi, run
 from alphazero_gym_amd.agent.agents import ContinuousAgent, DiscreteAgent
 from alphazero_gym_amd.agent.buffers import DeviceReplay
 from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
-from test_population_trainer import DEV, _native
+from trainer_util import ADAM_WD as ADAM_CFG, DEV, DIMS
 
 pytestmark = pytest.mark.gpu
 
@@ -116,7 +117,7 @@ def _same(got, want, k, what):
 def test_nets_against_one_net_trainers(trainer, optimizer, pair):
     """step_nets of K = 3 nets with three different settings, two consecutive steps, against three one-net step_opt runs.  With
     RMSprop no grad_norms are asked for, so net 0's and net 2's one-net runs take the FUSED backward kernel; with Adam they are."""
-    N = _native()
+    N = TU.native()
     _, hidden, kw, ln = trainer
     desc = _desc(pair, hidden, ln)
     A = PAIR_DIMS[pair][2]
@@ -165,7 +166,7 @@ def test_nets_against_one_net_trainers(trainer, optimizer, pair):
 @pytest.mark.parametrize("optimizer", ["rmsprop", "adam"])
 def test_identical_entries_are_step_opt(optimizer):
     """K identical entries: step_nets gives step_opt's bits (RMSprop without clip or norms: the fused kernel's)."""
-    N = _native()
+    N = TU.native()
     pair = "tuned_gmm2"
     desc = _desc(pair, [32, 16], False)
     A = PAIR_DIMS[pair][2]
@@ -195,7 +196,7 @@ def test_identical_entries_are_step_opt(optimizer):
 def test_epoch_nets():
     """epoch_nets over 7 ordered rows, batch_size 2 (minibatches of 2, 2 and 3 rows), Adam and a tuned alpha with three settings:
     against the same minibatches through step_nets one by one (steps + 0, + 1, + 2), and per net against a one-net epoch_opt."""
-    N = _native()
+    N = TU.native()
     pair, optimizer, n, in_dim = "tuned_gmm2", "adam", 7, 3
     desc = _desc(pair, [32, 16], False)
     A = PAIR_DIMS[pair][2]
@@ -251,8 +252,6 @@ def test_epoch_nets():
 # ---- PopulationTrainer(per_net=True) ----
 
 LOSS_TUNED = dict(run.LOSS_TUNED, device=DEV)
-ADAM_CFG = dict(run.ADAM, weight_decay=1e-4)
-DIMS = {"discrete": (4, 2), "gmm2": (3, 4)}
 NET_SETTINGS = [dict(lr=1e-3, clip=0.5, tau=1.0), dict(lr=3e-4, clip=0.0, tau=0.5), dict(lr=3e-3, clip=0.05, tau=2.0)]
 
 
@@ -295,10 +294,6 @@ def _state(tr):
     return {k: v.detach().cpu().clone() for k, v in s.items()}
 
 
-def _split(rows, S, A):
-    return (rows[..., :S], rows[..., S:S + A], rows[..., S + A:S + 2 * A], rows[..., S + 2 * A:S + 3 * A], rows[..., -1])
-
-
 def test_population_trainer_per_net():
     """update and train_epoch of three agents with different lr / grad_clip / tau against three one-agent PopulationTrainers."""
     head, K = "gmm2", 3
@@ -306,13 +301,13 @@ def test_population_trainer_per_net():
     tr = PopulationTrainer(_agents(head, range(K), [32, 16]), max_batch=64, losses="device", optimizers="agents", per_net=True)
     ones = [PopulationTrainer(_agents(head, [k], [32, 16]), max_batch=64, losses="device", optimizers="agents") for k in range(K)]
     batch, rows, seeds = _rows(head, K, 21, 3), _rows(head, K, 40, 4), [5, 6, 7]
-    got = tr.update(_split(batch, S, A))
+    got = tr.update(TU.split_rows(batch, S, A))
     after_update = _state(tr)
     got_epoch = tr.train_epoch(rows, S, A, batch_size=16, shuffle_seeds=seeds)
     after_epoch = _state(tr)
     assert tr.opt_step == tr.alpha_step == 3
     for k, one in enumerate(ones):
-        assert one.update(_split(batch[k:k + 1], S, A)) == [got[k]]
+        assert one.update(TU.split_rows(batch[k:k + 1], S, A)) == [got[k]]
         for key, val in _state(one).items():
             assert torch.equal(after_update[key][k], val[0]), f"update: {key} of net {k}"
         assert one.train_epoch(rows[k:k + 1], S, A, batch_size=16, shuffle_seeds=seeds[k:k + 1]) == [got_epoch[k]]
@@ -334,7 +329,7 @@ def test_per_net_equal_settings_is_the_shared_trainer():
     a = PopulationTrainer(_agents(head, range(K), [32, 16], same), max_batch=64, losses="device", optimizers="agents", per_net=True)
     b = PopulationTrainer(_agents(head, range(K), [32, 16], same), max_batch=64, losses="device", optimizers="agents")
     batch, rows = _rows(head, K, 21, 3), _rows(head, K, 40, 4)
-    assert a.update(_split(batch, S, A)) == b.update(_split(batch, S, A))
+    assert a.update(TU.split_rows(batch, S, A)) == b.update(TU.split_rows(batch, S, A))
     assert a.train_epoch(rows, S, A, batch_size=16, shuffle_seeds=[1, 2, 3]) == b.train_epoch(rows, S, A, batch_size=16, shuffle_seeds=[1, 2, 3])
     sa, sb = _state(a), _state(b)
     for key in sa:
@@ -375,7 +370,7 @@ def test_reload_settings():
     S, A = DIMS[head]
     changed = PopulationTrainer(_agents(head, range(K), [32, 16]), max_batch=64, losses="device", optimizers="agents", per_net=True)
     kept = PopulationTrainer(_agents(head, range(K), [32, 16]), max_batch=64, losses="device", optimizers="agents", per_net=True)
-    b0, b1 = _split(_rows(head, K, 21, 8), S, A), _split(_rows(head, K, 21, 9), S, A)
+    b0, b1 = TU.split_rows(_rows(head, K, 21, 8), S, A), TU.split_rows(_rows(head, K, 21, 9), S, A)
     assert changed.update(b0) == kept.update(b0)
     changed.agents[1].optimizer.param_groups[0]["lr"] = 5e-3
     before = _state(changed)
@@ -413,7 +408,7 @@ def test_reload_settings():
 # ---- refusals ----
 
 def test_refusals_write_nothing():
-    N = _native()
+    N = TU.native()
     pair, K, B = "tuned_gmm2", 2, 8
     A = PAIR_DIMS[pair][2]
     desc = _desc(pair, [32, 16], False)

@@ -1,10 +1,8 @@
 """CPU: the host half of PopulationTrainer(per_net=True) -- what it accepts (agents that differ in numeric optimiser and loss
 settings) and what it still refuses, the *_nets bindings and the example's --lrs.  The kernels are tested on the GPU in
 test_population_trainer_pernet.py."""
-import copy
 import ctypes as C
 import os
-import re
 import sys
 
 import pytest
@@ -12,23 +10,11 @@ import torch
 
 from alphazero_gym_amd import _capi, run
 from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
-from test_population_trainer_host import make_agent
+from trainer_util import make_agent, refused
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
 
 ADAM = dict(run.ADAM)
-
-
-def _refused(agents, reason, **kw):
-    """PopulationTrainer raises ValueError with ``reason`` and leaves the agents as they were."""
-    before = copy.deepcopy([a.nn.state_dict() for a in agents])
-    ptrs = [[p.data_ptr() for p in a.nn.parameters()] for a in agents]
-    with pytest.raises(ValueError, match=re.escape(reason)):
-        PopulationTrainer(agents, **kw)
-    for a, sd, pp in zip(agents, before, ptrs):
-        for name, v in a.nn.state_dict().items():
-            assert torch.equal(v, sd[name])
-        assert [p.data_ptr() for p in a.nn.parameters()] == pp and not a.optimizer.state
 
 
 def _with(agent, **attrs):
@@ -52,12 +38,12 @@ MIXED = {
 
 @pytest.mark.parametrize("what", list(MIXED))
 def test_mixed_settings_pass_every_host_check(what):
-    _refused(MIXED[what](), "must live on one GPU", optimizers="agents", losses="device", per_net=True)
+    refused(MIXED[what](), "must live on one GPU", optimizers="agents", losses="device", per_net=True)
 
 
 @pytest.mark.parametrize("what", ["lr_rmsprop", "lr_betas_adam", "weight_decay", "grad_clip"])
 def test_mixed_optimiser_settings_pass_with_torch_losses(what):
-    _refused(MIXED[what](), "must live on one GPU", optimizers="agents", losses="torch", per_net=True)
+    refused(MIXED[what](), "must live on one GPU", optimizers="agents", losses="torch", per_net=True)
 
 
 def _one_step_ahead():
@@ -71,8 +57,8 @@ def _one_step_ahead():
 
 
 def test_per_net_needs_agents_optimisers():
-    _refused([make_agent("normal") for _ in range(2)], 'per_net=True requires optimizers="agents"', per_net=True)
-    _refused([make_agent("normal") for _ in range(2)], 'per_net=True requires optimizers="agents"', optimizers="rmsprop", per_net=True)
+    refused([make_agent("normal") for _ in range(2)], 'per_net=True requires optimizers="agents"', per_net=True)
+    refused([make_agent("normal") for _ in range(2)], 'per_net=True requires optimizers="agents"', optimizers="rmsprop", per_net=True)
 
 
 PER_NET_REFUSALS = {
@@ -92,7 +78,7 @@ PER_NET_REFUSALS = {
 @pytest.mark.parametrize("why", list(PER_NET_REFUSALS))
 def test_per_net_refusals(why):
     build, reason, losses = PER_NET_REFUSALS[why]
-    _refused(build(), reason, optimizers="agents", losses=losses, per_net=True)
+    refused(build(), reason, optimizers="agents", losses=losses, per_net=True)
 
 
 def test_per_net_step_counts_must_agree():
@@ -113,10 +99,10 @@ DEFAULT_STILL_REFUSES = {
 @pytest.mark.parametrize("what", list(DEFAULT_STILL_REFUSES))
 def test_default_constructor_keeps_its_messages(what):
     reason, kw = DEFAULT_STILL_REFUSES[what]
-    _refused(MIXED[what](), reason, **kw)
-    _refused(MIXED[what](), reason, per_net=False, **kw)
+    refused(MIXED[what](), reason, **kw)
+    refused(MIXED[what](), reason, per_net=False, **kw)
     if what == "lr_rmsprop":
-        _refused(MIXED[what](), reason)
+        refused(MIXED[what](), reason)
 
 
 def test_nets_symbols_and_signatures():

@@ -1,40 +1,19 @@
 """CPU: the host half of training wide nets in the population trainer -- the azg_trainer_create_wide declaration and binding,
 _capi.Trainer(wide=True)'s choice of constructor, and what PopulationTrainer(wide=True) takes and still refuses (the CPU refusal,
 which comes last, is what is left for the nets it takes).  The kernels are tested on the GPU in test_population_trainer_wide.py."""
-import copy
+import functools
 import os
 import re
 
 import pytest
-import torch
 
-from alphazero_gym_amd import _capi, run
-from alphazero_gym_amd.agent.agents import ContinuousAgent
-from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
+from alphazero_gym_amd import _capi
+from trainer_util import normal_agent, refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def make_agent(seed=0, hidden=(512, 272), layernorm=False):
-    torch.manual_seed(seed)
-    cfg = run.CONTINUOUS_DEFAULTS
-    policy = dict(cfg["policy"], hidden_dimensions=list(hidden), representation_dim=3, action_dim=1, action_bound=2.0, layernorm=layernorm,
-                  num_components=1)
-    return ContinuousAgent(policy_cfg=policy, mcts_cfg=dict(cfg["mcts"], device="cpu"), loss_cfg=run.LOSS_TUNED,
-                           optimizer_cfg=run.RMSPROP, device="cpu", **dict(cfg["agent"], grad_clip=0))
-
-
-def _refused(agents, reason, **kw):
-    """PopulationTrainer(agents, **kw) raises a ValueError naming ``reason`` and leaves the agents as they were: same values, same
-    storage, no optimiser state."""
-    before = copy.deepcopy([a.nn.state_dict() for a in agents])
-    ptrs = [[p.data_ptr() for p in a.nn.parameters()] for a in agents]
-    with pytest.raises(ValueError, match=re.escape(reason)):
-        PopulationTrainer(agents, **kw)
-    for a, sd, pp in zip(agents, before, ptrs):
-        for name, v in a.nn.state_dict().items():
-            assert torch.equal(v, sd[name])
-        assert [p.data_ptr() for p in a.nn.parameters()] == pp and not a.optimizer.state
+make_agent = functools.partial(normal_agent, layernorm=False)   # [512, 272]
 
 
 def test_header_declares_create_wide():
@@ -84,25 +63,25 @@ def test_trainer_chooses_the_constructor():
 
 
 def test_default_refuses_wide_nets():
-    _refused([make_agent(s) for s in range(2)], "supported nets have 1-3 hidden layers of widths 16, 32, ... 256")
-    _refused([make_agent(s) for s in range(2)], "supported nets have 1-3 hidden layers of widths 16, 32, ... 256", wide=False)
+    refused([make_agent(s) for s in range(2)], "supported nets have 1-3 hidden layers of widths 16, 32, ... 256")
+    refused([make_agent(s) for s in range(2)], "supported nets have 1-3 hidden layers of widths 16, 32, ... 256", wide=False)
 
 
 def test_wide_agents_reach_the_last_refusal():
-    _refused([make_agent(s) for s in range(2)], "must live on one GPU", wide=True)
-    _refused([make_agent(0, hidden=[1024] * 2)], "must live on one GPU", wide=True)
-    _refused([make_agent(0, hidden=[16] * 8)], "must live on one GPU", wide=True)
+    refused([make_agent(s) for s in range(2)], "must live on one GPU", wide=True)
+    refused([make_agent(0, hidden=[1024] * 2)], "must live on one GPU", wide=True)
+    refused([make_agent(0, hidden=[16] * 8)], "must live on one GPU", wide=True)
     # narrow agents are taken by such a trainer as well
-    _refused([make_agent(s, hidden=(32, 32)) for s in range(2)], "must live on one GPU", wide=True)
+    refused([make_agent(s, hidden=(32, 32)) for s in range(2)], "must live on one GPU", wide=True)
 
 
 @pytest.mark.parametrize("hidden", [[16] * 9, [1040], [40], [512, 40]], ids=["9_layers", "1040", "40", "512x40"])
 def test_shapes_that_stay_refused(hidden):
-    _refused([make_agent(0, hidden=hidden)], "supported nets have 1-8 hidden layers of widths 16, 32, ... 1024", wide=True)
+    refused([make_agent(0, hidden=hidden)], "supported nets have 1-8 hidden layers of widths 16, 32, ... 1024", wide=True)
 
 
 def test_wide_refuses_layernorm():
-    _refused([make_agent(s, hidden=(32, 32), layernorm=True) for s in range(2)], "LayerNorm", wide=True)
-    _refused([make_agent(s, hidden=(32, 32), layernorm=True) for s in range(2)], "LayerNorm", wide=True, layernorm=True)
-    _refused([make_agent(s, hidden=(32, 32)) for s in range(2)], "LayerNorm", wide=True, layernorm=True)
-    _refused([make_agent(s) for s in range(2)], "LayerNorm", wide=True, layernorm=True)
+    refused([make_agent(s, hidden=(32, 32), layernorm=True) for s in range(2)], "LayerNorm", wide=True)
+    refused([make_agent(s, hidden=(32, 32), layernorm=True) for s in range(2)], "LayerNorm", wide=True, layernorm=True)
+    refused([make_agent(s, hidden=(32, 32)) for s in range(2)], "LayerNorm", wide=True, layernorm=True)
+    refused([make_agent(s) for s in range(2)], "LayerNorm", wide=True, layernorm=True)

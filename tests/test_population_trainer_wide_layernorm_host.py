@@ -2,41 +2,19 @@
 binding, _capi.Trainer(wide_layernorm=True)'s choice of constructor, and what PopulationTrainer(wide_layernorm=True) takes and still
 refuses (the CPU refusal, which comes last, is what is left for the nets it takes).  The kernels are tested on the GPU in
 test_population_trainer_wide_layernorm.py."""
-import copy
+import functools
 import os
 import re
 
 import pytest
-import torch
 
-from alphazero_gym_amd import _capi, run
-from alphazero_gym_amd.agent.agents import ContinuousAgent
-from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
+from alphazero_gym_amd import _capi
+from trainer_util import normal_agent, refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def make_agent(seed=0, hidden=(512, 272), layernorm=True):
-    torch.manual_seed(seed)
-    cfg = run.CONTINUOUS_DEFAULTS
-    policy = dict(cfg["policy"], hidden_dimensions=list(hidden), representation_dim=3, action_dim=1, action_bound=2.0, layernorm=layernorm,
-                  num_components=1)
-    return ContinuousAgent(policy_cfg=policy, mcts_cfg=dict(cfg["mcts"], device="cpu"), loss_cfg=run.LOSS_TUNED,
-                           optimizer_cfg=run.RMSPROP, device="cpu", **dict(cfg["agent"], grad_clip=0))
-
-
-def _refused(agents, reason, **kw):
-    """PopulationTrainer(agents, **kw) raises a ValueError naming ``reason`` and leaves the agents untouched: the same values in the
-    same storage, and optimisers without state."""
-    values = [copy.deepcopy(a.nn.state_dict()) for a in agents]
-    storage = [[p.data_ptr() for p in a.nn.parameters()] for a in agents]
-    with pytest.raises(ValueError, match=re.escape(reason)):
-        PopulationTrainer(agents, **kw)
-    for a, sd, pp in zip(agents, values, storage):
-        now = a.nn.state_dict()
-        assert list(now) == list(sd) and all(torch.equal(now[name], sd[name]) for name in sd)
-        assert [p.data_ptr() for p in a.nn.parameters()] == pp
-        assert not a.optimizer.state
+make_agent = functools.partial(normal_agent, layernorm=True)   # [512, 272]
 
 
 def test_header_declares_create_wide_ex():
@@ -109,24 +87,24 @@ def test_the_options_passed_ask_for_layernorm():
 
 
 def test_wide_layernorm_agents_reach_the_last_refusal():
-    _refused([make_agent(s) for s in range(2)], "must live on one GPU", wide_layernorm=True)
-    _refused([make_agent(0, hidden=[1024] * 2)], "must live on one GPU", wide_layernorm=True)
+    refused([make_agent(s) for s in range(2)], "must live on one GPU", wide_layernorm=True)
+    refused([make_agent(0, hidden=[1024] * 2)], "must live on one GPU", wide_layernorm=True)
     # agents without LayerNorm, and narrow ones, are taken as well
-    _refused([make_agent(s, layernorm=False) for s in range(2)], "must live on one GPU", wide_layernorm=True)
-    _refused([make_agent(s, hidden=(32, 32)) for s in range(2)], "must live on one GPU", wide_layernorm=True)
+    refused([make_agent(s, layernorm=False) for s in range(2)], "must live on one GPU", wide_layernorm=True)
+    refused([make_agent(s, hidden=(32, 32)) for s in range(2)], "must live on one GPU", wide_layernorm=True)
 
 
 @pytest.mark.parametrize("hidden", [[16] * 9, [1040], [40], [512, 40]], ids=["9_layers", "1040", "40", "512x40"])
 def test_shapes_that_stay_refused(hidden):
-    _refused([make_agent(0, hidden=hidden)], "supported nets have 1-8 hidden layers of widths 16, 32, ... 1024", wide_layernorm=True)
+    refused([make_agent(0, hidden=hidden)], "supported nets have 1-8 hidden layers of widths 16, 32, ... 1024", wide_layernorm=True)
 
 
 def test_two_trainers_at_once_are_refused():
-    _refused([make_agent(s, hidden=(32, 32)) for s in range(2)], "wide_layernorm=True and layernorm=True", wide_layernorm=True, layernorm=True)
+    refused([make_agent(s, hidden=(32, 32)) for s in range(2)], "wide_layernorm=True and layernorm=True", wide_layernorm=True, layernorm=True)
 
 
 def test_the_spellings_of_before_keep_their_refusals():
-    _refused([make_agent(s) for s in range(2)], "LayerNorm", wide=True)
-    _refused([make_agent(s) for s in range(2)], "LayerNorm", wide=True, layernorm=True)
-    _refused([make_agent(s) for s in range(2)], "LayerNorm")
-    _refused([make_agent(s) for s in range(2)], "supported nets have 1-3 hidden layers of widths 16, 32, ... 256", layernorm=True)
+    refused([make_agent(s) for s in range(2)], "LayerNorm", wide=True)
+    refused([make_agent(s) for s in range(2)], "LayerNorm", wide=True, layernorm=True)
+    refused([make_agent(s) for s in range(2)], "LayerNorm")
+    refused([make_agent(s) for s in range(2)], "supported nets have 1-3 hidden layers of widths 16, 32, ... 256", layernorm=True)

@@ -6,7 +6,8 @@ import pytest
 import torch
 
 import trainer_edges as E
-from test_population_device_loss import LOG_ALPHA0, make_loss, torch_loss
+import trainer_util as TU
+from device_loss_util import LOG_ALPHA0, make_loss, torch_loss
 
 F32_MAX = float(np.finfo(np.float32).max)
 
@@ -123,9 +124,9 @@ def test_kink_net(act):
         assert (zk[:, signed].view(np.uint32) == table[signed].view(np.uint32)).all()
         assert (zk[:, 1] == 0).all()
     for dtype in (torch.float64, torch.float32):
-        assert all(bool(torch.isfinite(g).all()) for g in E.autograd(pol, obs, d_raw, dtype))
+        assert all(bool(torch.isfinite(g).all()) for g in TU.autograd(pol, obs, d_raw, dtype))
     # the zero pattern of float64's bias gradients on the kink units is the derivative's
-    g64 = E.autograd(pol, obs, d_raw, torch.float64)
+    g64 = TU.autograd(pol, obs, d_raw, torch.float64)
     zero = E.dact64(act, table) == 0
     for db in (g64[1], g64[3]):
         assert ((db[:E.KINK_UNITS].numpy() == 0) == zero).all()
@@ -175,7 +176,7 @@ def test_layernorm_net():
     others = [r for r in range(obs.shape[0]) if r != E.LN_ZERO_ROW]
     assert bool((a1[others].var(dim=1) > 0).all())
     for dtype in (torch.float64, torch.float32):
-        assert all(bool(torch.isfinite(g).all()) for g in E.autograd(pol, obs, d_raw, dtype))
+        assert all(bool(torch.isfinite(g).all()) for g in TU.autograd(pol, obs, d_raw, dtype))
 
 
 # ------------------------------------------------------------------------------------------------ the reference at the pole

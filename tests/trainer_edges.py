@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from alphazero_gym_amd.network.policies import make_policy
+from device_loss_util import make_head
 
 BOUND = 2.0
 LMIN, LMAX = -5.0, 2.0                   # make_policy's log_param_min / log_param_max
@@ -145,11 +146,10 @@ def discrete_table(head):
 
 
 def head_policy(head):
-    """test_population_device_loss.py's make_head, and its 16-logit sibling."""
+    """device_loss_util.py's make_head, and its 16-logit sibling."""
     if head == "discrete16":
         torch.manual_seed(0)
         return make_policy(3, 1, "discrete", [16], "relu", num_actions=16)
-    from test_population_device_loss import make_head
     return make_head(head)
 
 
@@ -252,19 +252,3 @@ def layernorm_data():
     obs[LN_ZERO_ROW] = 0.0
     d_raw = torch.randn((17, 3), generator=g) / 17
     return obs, d_raw
-
-
-# ------------------------------------------------------------------------------------------------ float64 autograd
-def raw_of(pol, x):
-    h = pol.trunk(x)
-    return torch.cat([pol.value_head(h), pol.dist_head(h)], dim=-1)
-
-
-def autograd(pol, obs, d_raw, dtype):
-    """Gradients of sum(raw * d_raw) by every parameter in blob order, on the CPU in ``dtype``."""
-    import copy
-
-    from alphazero_gym_amd import _capi
-    p = copy.deepcopy(pol).to(dtype)
-    (raw_of(p, obs.to(dtype)) * d_raw.to(dtype)).sum().backward()
-    return [t.grad for t in _capi.policy_tensors(p)[1]]
