@@ -96,6 +96,19 @@ class AzgEvalInfo(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("resident", C.c_int32), ("groups", C.c_int32), ("tiles", C.c_int32)]
 
 
+class AzgSearchRolloutConfig(C.Structure):
+    """include/azgym_search_rollout.h: azg_search_rollout_config"""
+    _fields_ = [("struct_size", C.c_int32), ("episodes_per_game", C.c_int32), ("max_episode_length", C.c_int32),
+                ("final_selection", C.c_int32), ("deterministic", C.c_int32), ("poll_steps", C.c_int32),
+                ("game_id_base", C.c_uint32), ("episode", C.c_uint32), ("index_base", C.c_uint32),
+                ("temperature", C.c_double), ("agent_epsilon", C.c_double)]
+
+
+class AzgSearchRolloutInfo(C.Structure):
+    """include/azgym_search_rollout.h: azg_search_rollout_info"""
+    _fields_ = [("struct_size", C.c_int32), ("steps", C.c_int32), ("polls", C.c_int32)]
+
+
 ROLLOUT_RULE = {"mode": 0, "sample": 1}   # include/azgym_eval.h: AZG_ROLLOUT_*
 ROLLOUT_FORM = {0: "group", 1: "team"}    # include/azgym_eval.h: AZG_ROLLOUT_FORM_*
 FINAL_SELECTION = {"max_visit": 0, "max_visits": 0, "max_value": 1}   # the reference's configs spell it both ways
@@ -123,7 +136,7 @@ SYMBOLS = [
 OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device", "set_net_search",
                     "set_net_search_ex",
                     "population_selfplay_begin", "selfplay_keep_states", "selfplay_states", "selfplay_reanalyse",
-                    "policy_rollout", "policy_rollout_ex",
+                    "policy_rollout", "policy_rollout_ex", "search_rollout",
                     "population_mlp_eval", "population_mlp_eval_device", "population_root_eval",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
                     "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch",
@@ -280,6 +293,9 @@ def bind(lib, prefix):
         f["selfplay_keep_states"].argtypes = [vp, C.c_int32]
         f["selfplay_states"].argtypes = [vp, C.POINTER(C.c_double), C.c_size_t]
         f["selfplay_reanalyse"].argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.c_uint32]
+    if "search_rollout" in f:   # include/azgym_search_rollout.h
+        f["search_rollout"].argtypes = [vp, C.POINTER(AzgSearchRolloutConfig), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), C.POINTER(AzgSearchRolloutInfo)]
     if "policy_rollout" in f:   # include/azgym_eval.h
         f["policy_rollout"].argtypes = [vp, C.POINTER(AzgRolloutConfig), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float)]
@@ -753,6 +769,37 @@ class Engine:
             self._check(fn(self._h, C.byref(c), *outs))
             self.last_rollout_info = None
         return {"returns": returns, "lengths": lengths, "terminated": terminated.astype(bool), "first_value": first_value}
+
+    def search_rollout(self, episodes_per_game, max_episode_length, final_selection="max_visit", deterministic=True, temperature=1.0,
+                       agent_epsilon=0.0, game_id_base=0, episode=0, index_base=0, poll_steps=8, out=None):
+        """azg_search_rollout (include/azgym_search_rollout.h): every game of the engine plays ``episodes_per_game`` whole episodes
+        under MCTS on the device, on evaluation state of its own: self-play, the ring and the running search index are left as they
+        were.  Game j of every net starts its i-th episode at the reset state of global game ``game_id_base + j``, episode
+        ``episode + i``; step s of the call searches under RNG search index ``index_base + s``.  final_selection / deterministic /
+        temperature / agent_epsilon: the final-action rule, as selfplay_begin's.
+        Returns a dict of [n_trees, episodes_per_game] arrays: returns (float64), lengths, terminated (bool), and ``steps`` /
+        ``polls`` (the searches run; the times the host read the device's count of unfinished games).  ``out``: (returns, lengths,
+        terminated int32) arrays to write into."""
+        fn = self._optional("search_rollout")
+        c = AzgSearchRolloutConfig()
+        c.struct_size = C.sizeof(AzgSearchRolloutConfig)
+        c.episodes_per_game, c.max_episode_length = int(episodes_per_game), int(max_episode_length)
+        c.final_selection = FINAL_SELECTION[final_selection] if isinstance(final_selection, str) else int(final_selection)
+        c.deterministic, c.poll_steps = int(bool(deterministic)), int(poll_steps)
+        c.game_id_base, c.episode, c.index_base = int(game_id_base) & 0xFFFFFFFF, int(episode) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF
+        c.temperature, c.agent_epsilon = float(temperature), float(agent_epsilon)
+        shape = (self.n_trees, max(int(episodes_per_game), 0))
+        if out is None:
+            out = (np.empty(shape, np.float64), np.empty(shape, np.int32), np.empty(shape, np.int32))
+        returns, lengths, terminated = out
+        for a, dt in zip(out, (np.float64, np.int32, np.int32)):
+            if a.shape != shape or a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError(f"search_rollout: out must be contiguous float64 / int32 / int32 arrays of shape {shape}")
+        info = AzgSearchRolloutInfo()
+        info.struct_size = C.sizeof(AzgSearchRolloutInfo)
+        self._check(fn(self._h, C.byref(c), _ptr(returns, C.c_double), _ptr(lengths, C.c_int32), _ptr(terminated, C.c_int32), C.byref(info)))
+        return {"returns": returns, "lengths": lengths, "terminated": terminated.astype(bool), "steps": int(info.steps),
+                "polls": int(info.polls)}
 
     def dump_tree(self):
         B, R = self.n_trees, self.max_records

@@ -4,8 +4,9 @@
 // mode only, one thread per game, from the published trees).  What follows the pick is selfplay_finish for both, and the game itself
 // is env.cuh's game_obs / game_step, shared with the policy rollouts (rollout.cuh).
 // A row's actions | counts | Q columns and its value target have one definition per form (row_targets16, row_targets), shared by the
-// self-play kernels and by the reanalysis kernels at the end of this file, which rewrite those columns of a stored row from a fresh
-// search of its kept state.
+// self-play kernels and by the reanalysis kernels, which rewrite those columns of a stored row from a fresh search of its kept state.
+// The pick has one definition per form too (final_pick16, final_pick), shared by the self-play kernels and by the search rollouts at the
+// end of this file (azgym_search_rollout.h): whole evaluation episodes under MCTS, the same step without a replay row.
 #pragma once
 #include "records.h"
 #include "env.cuh"
@@ -34,13 +35,18 @@ __global__ __launch_bounds__(16 * RS_TREES) void results_kernel(KParams P) {
 // One self-play step after a search: replay row, the agent's final action rule, the real env step, episode bookkeeping and the
 // next search's root (the CPU oracle restates the same arithmetic for the parity tests).  Kmax, the value target and the env are
 // KParams' res_Kmax, res_v_target and env_id.
-struct SelfPlay {
-    int max_len, deterministic;
-    int S_obs;                // width of the env's observation: the row's first columns
+// The agents' final-action rule and the step its AZG_STREAM_ACT draw is keyed with
+struct ActRule {
+    int deterministic;
     int final_selection;      // AZG_FS_*
     double agent_eps;         // ContinuousAgent.epsilon
     const double* ctab;       // (c / m)^temperature at [m (m + 1) / 2 + c], 0 <= c <= m <= n_sims, built by the host (NULL: temperature 1)
     unsigned step_idx;
+};
+struct SelfPlay {
+    int max_len;
+    int S_obs;                // width of the env's observation: the row's first columns
+    ActRule rule;
     int* t; int* episode; int* fcnt;
     double* ret; double* fsum;
     float* rows;          // this step's block [B][row_len]
@@ -87,12 +93,12 @@ __device__ __forceinline__ void selfplay_finish(const KParams& P, const SelfPlay
 
 // Lane `sub` of a game's 16 on the root's children as MCTS.return_results left them (written by the search kernel's epilogue from its
 // LDS-resident trees, or by results_kernel after the lock-step / team kernels): no tree record is read here, so a search need not
-// publish its trees.  Writes the row's actions | counts | Q columns side by side and returns the row's totals; the on-policy value
-// target is added up in the reference's order, reading the lanes' values by shuffles (executed by the whole row: loop bounds are
-// row-uniform).
+// publish its trees.  root_totals16 returns the root's totals; want_target (a constant at every call): with the value target, whose
+// on-policy form is added up in the reference's order, reading the lanes' values by shuffles (executed by the whole row: loop bounds
+// are row-uniform).  row_targets16 also writes the row's actions | counts | Q columns side by side.
 struct RootLane { int edge_n, node_n; double Q; float act; bool has; };
 struct RootTotals { int nc, tot, cmax, amax; double qmax, v_target; };
-__device__ __forceinline__ RootTotals row_targets16(const KParams& P, int tree, int sub, float* targets, RootLane& h) {
+__device__ __forceinline__ RootTotals root_totals16(const KParams& P, int tree, int sub, RootLane& h, bool want_target) {
     const bool cont = P.mode == AZG_MODE_CONTINUOUS;
     const int K = P.res_Kmax;
     RootTotals r;
@@ -108,11 +114,6 @@ __device__ __forceinline__ RootTotals row_targets16(const KParams& P, int tree, 
     }
     h.has = has;
     h.act = has ? (cont ? P.res_actions[(size_t)tree * K + sub] : (float)sub) : 0.0f;
-    if (sub < K) {
-        targets[sub] = h.act;
-        targets[K + sub] = has ? (float)h.edge_n : 0.0f;
-        targets[2 * K + sub] = has ? (float)h.Q : 0.0f;
-    }
     int tot = has ? h.edge_n : 0;
     double qmax = has ? h.Q : -__builtin_huge_val();
     int ckey = has ? ((h.edge_n << 4) | (15 - sub)) : -1;          // largest count, lowest index on ties (counts < 2^27)
@@ -125,7 +126,7 @@ __device__ __forceinline__ RootTotals row_targets16(const KParams& P, int tree, 
     }
     if (nc == 0) qmax = 0.0;
     double onp = 0.0;
-    if (P.res_v_target == AZG_VT_ON_POLICY) {
+    if (want_target && P.res_v_target == AZG_VT_ON_POLICY) {
         if (!cont) {
             for (int a = 0; a < nc; ++a) onp += ((double)__shfl(h.edge_n, a, 16) / (double)tot) * __shfl(h.Q, a, 16);
         } else {
@@ -139,48 +140,42 @@ __device__ __forceinline__ RootTotals row_targets16(const KParams& P, int tree, 
     r.v_target = P.res_v_target == AZG_VT_ON_POLICY ? onp : qmax;
     return r;
 }
+__device__ __forceinline__ RootTotals row_targets16(const KParams& P, int tree, int sub, float* targets, RootLane& h) {
+    const RootTotals r = root_totals16(P, tree, sub, h, true);
+    const int K = P.res_Kmax;
+    if (sub < K) {
+        targets[sub] = h.act;
+        targets[K + sub] = h.has ? (float)h.edge_n : 0.0f;
+        targets[2 * K + sub] = h.has ? (float)h.Q : 0.0f;
+    }
+    return r;
+}
 
-// The common case (at most 16 root children: every LDS-tree configuration): 16 lanes per game, lane a = root child a.  The replay
-// row is written by the lanes side by side (row_targets16); totals are row reductions that do not depend on the order (integer sum,
-// maximum, first index of the largest count); everything whose float64 order matters (on-policy target, normaliser sums, the
-// inverse-CDF walk of numpy's random.choice) is added up by the game's first lane in the reference's order, reading the lanes' values
-// by shuffles; that lane also finishes the step (selfplay_finish).  Same arithmetic as selfplay_kernel below (roots with more
-// children) and as the oracle.
-#define SP_TREES 16
-__global__ __launch_bounds__(16 * SP_TREES) void selfplay_kernel16(KParams P, SelfPlay sp) {
-    const int sub = threadIdx.x & 15;
-    const int tree = blockIdx.x * SP_TREES + (threadIdx.x >> 4);
-    if (tree >= P.B) return;
+// The final action of a game with at most 16 root children, for the game's 16 lanes (all of them return the pick; the shuffles are
+// executed by the whole row: loop bounds are row-uniform).  Everything whose float64 order matters (normaliser sums, the inverse-CDF
+// walk of numpy's random.choice) is added up in the reference's order, reading the lanes' values by shuffles.
+__device__ __forceinline__ int final_pick16(const KParams& P, const ActRule& ar, unsigned gtree, const RootTotals& rt, const RootLane& h) {
     const bool cont = P.mode == AZG_MODE_CONTINUOUS;
-    const unsigned gtree = (unsigned)(P.tree_base + tree);
-    const int K = P.res_Kmax, S_obs = sp.S_obs;
-    float* row = sp.rows + (size_t)tree * (S_obs + 3 * K + 1);
-    RootLane h;
-    const RootTotals rt = row_targets16(P, tree, sub, row + S_obs, h);
-    const int nc = rt.nc, cmax = rt.cmax, amax = rt.amax;
-    const double qmax = rt.qmax;
+    const int nc = rt.nc, cmax = rt.cmax;
     const bool has = h.has;
-    const float act = h.act;
     // discrete: the lane's unnormalised pi entry (stable_normalizer's x / max(x), to the temperature)
     double x = 0.0;
     if (!cont && has) {
-        if (sp.final_selection == AZG_FS_MAX_VALUE) x = h.Q / qmax;
-        else x = sp.ctab ? sp.ctab[(size_t)cmax * (cmax + 1) / 2 + h.edge_n] : (double)h.edge_n / (double)cmax;
+        if (ar.final_selection == AZG_FS_MAX_VALUE) x = h.Q / rt.qmax;
+        else x = ar.ctab ? ar.ctab[(size_t)cmax * (cmax + 1) / 2 + h.edge_n] : (double)h.edge_n / (double)cmax;
     }
-    // ---- the game's first lane: order-sensitive sums, the final action, the rest of the step (the shuffles are executed by the
-    // whole row: loop bounds are row-uniform)
     int pick = 0;
     if (cont) {
         // ContinuousAgent.act (agents.py:524-535): actions[Qs.argmax()] / actions[counts.argmax()], first index on ties
-        pick = amax;
-        if (sp.final_selection == AZG_FS_MAX_VALUE) {
+        pick = rt.amax;
+        if (ar.final_selection == AZG_FS_MAX_VALUE) {
             double qb = 0.0;
             for (int a = 0; a < nc; ++a) { const double q = __shfl(h.Q, a, 16); if (a == 0 || q > qb) { qb = q; pick = a; } }
         }
-        if (sp.agent_eps != 0.0) {
+        if (ar.agent_eps != 0.0) {
             // epsilon_greedy (agents.py:471-490): random.random() < epsilon -> np.random.choice(actions)
-            azg_u32x4 b = azg_draw(P.seed, gtree, sp.step_idx, 0u, AZG_STREAM_ACT);
-            if ((double)azg_u01(b.v[0]) < sp.agent_eps) pick = (int)(b.v[1] % (unsigned)nc);
+            azg_u32x4 b = azg_draw(P.seed, gtree, ar.step_idx, 0u, AZG_STREAM_ACT);
+            if ((double)azg_u01(b.v[0]) < ar.agent_eps) pick = (int)(b.v[1] % (unsigned)nc);
         }
     } else {
         // DiscreteAgent.act (agents.py:294-301): pi = stable_normalizer(Qs | counts, temperature) (helpers.py:26-27), then
@@ -194,8 +189,8 @@ __global__ __launch_bounds__(16 * SP_TREES) void selfplay_kernel16(KParams P, Se
             if (a == 0 || pa > best) { best = pa; pick = a; }
             cum = cum + pa;
         }
-        if (!sp.deterministic) {
-            azg_u32x4 b = azg_draw(P.seed, gtree, sp.step_idx, 0u, AZG_STREAM_ACT);
+        if (!ar.deterministic) {
+            azg_u32x4 b = azg_draw(P.seed, gtree, ar.step_idx, 0u, AZG_STREAM_ACT);
             const double u = ((double)b.v[0] + 0.5) * (1.0 / 4294967296.0);
             const double last = cum;
             double c = 0.0;
@@ -210,7 +205,28 @@ __global__ __launch_bounds__(16 * SP_TREES) void selfplay_kernel16(KParams P, Se
             }
         }
     }
-    const float pact = __shfl(act, pick, 16);
+    return pick;
+}
+
+// The common case (at most 16 root children: every LDS-tree configuration): 16 lanes per game, lane a = root child a.  The replay
+// row is written by the lanes side by side (row_targets16); totals are row reductions that do not depend on the order (integer sum,
+// maximum, first index of the largest count); everything whose float64 order matters (on-policy target, normaliser sums, the
+// inverse-CDF walk of numpy's random.choice) is added up in the reference's order, reading the lanes' values by shuffles
+// (final_pick16); the game's first lane finishes the step (selfplay_finish).  Same arithmetic as selfplay_kernel below (roots with
+// more children) and as the oracle.
+#define SP_TREES 16
+__global__ __launch_bounds__(16 * SP_TREES) void selfplay_kernel16(KParams P, SelfPlay sp) {
+    const int sub = threadIdx.x & 15;
+    const int tree = blockIdx.x * SP_TREES + (threadIdx.x >> 4);
+    if (tree >= P.B) return;
+    const bool cont = P.mode == AZG_MODE_CONTINUOUS;
+    const unsigned gtree = (unsigned)(P.tree_base + tree);
+    const int K = P.res_Kmax, S_obs = sp.S_obs;
+    float* row = sp.rows + (size_t)tree * (S_obs + 3 * K + 1);
+    RootLane h;
+    const RootTotals rt = row_targets16(P, tree, sub, row + S_obs, h);
+    const int pick = final_pick16(P, sp.rule, gtree, rt, h);
+    const float pact = __shfl(h.act, pick, 16);
     const int pnode_n = __shfl(h.node_n, pick, 16);   // (0 where the picked edge has no child node yet)
     if (sub != 0) return;
     selfplay_finish(P, sp, tree, row, pact, rt.v_target, cont ? 0 : pnode_n);
@@ -227,30 +243,51 @@ struct RootEdges {
     __device__ __forceinline__ RecL rec(int a) const { return P.hot[tb + id(a)]; }
     __device__ __forceinline__ float act(int a) const { return P.action[tb + id(a)]; }
 };
-// The row's actions | counts | Q columns from those edges (continuous mode); returns the value target and the first index of the
-// largest count.
-__device__ __forceinline__ double row_targets(const KParams& P, const RootEdges& re, float* targets, int* amax_out) {
-    const int K = P.res_Kmax, nc = re.nc;
+// The root's totals from those edges (continuous mode): the first index of the largest count and, with want_target (a constant at
+// every call), the value target.  row_targets also writes the row's actions | counts | Q columns.
+__device__ __forceinline__ double root_totals(const KParams& P, const RootEdges& re, int* amax_out, bool want_target) {
+    const int nc = re.nc;
     double qmax = 0.0, onp = 0.0;
     long tot = 0;
     int cmax = 0, amax = 0;
-    for (int a = 0; a < nc; ++a) tot += re.rec(a).edge_n;
+    for (int a = 0; a < nc; ++a) {
+        const RecL h = re.rec(a);
+        tot += h.edge_n;
+        if (a == 0 || h.Q > qmax) qmax = h.Q;
+        if (a == 0 || h.edge_n > cmax) { cmax = h.edge_n; amax = a; }
+    }
+    if (want_target && P.res_v_target == AZG_VT_ON_POLICY)
+        for (int a = 0; a < nc; ++a)
+            for (int b = 0; b < nc; ++b) onp += ((double)re.rec(b).edge_n / (double)tot) * re.rec(a).Q;
+    *amax_out = amax;
+    return P.res_v_target == AZG_VT_ON_POLICY ? onp : qmax;
+}
+__device__ __forceinline__ double row_targets(const KParams& P, const RootEdges& re, float* targets, int* amax_out) {
+    const int K = P.res_Kmax, nc = re.nc;
     for (int a = 0; a < K; ++a) {
         const bool has = a < nc;
         const RecL h = re.rec(a);
         targets[a] = has ? re.act(a) : 0.0f;
         targets[K + a] = has ? (float)h.edge_n : 0.0f;
         targets[2 * K + a] = has ? (float)h.Q : 0.0f;
-        if (has) {
-            if (a == 0 || h.Q > qmax) qmax = h.Q;
-            if (a == 0 || h.edge_n > cmax) { cmax = h.edge_n; amax = a; }
-        }
     }
-    if (P.res_v_target == AZG_VT_ON_POLICY)
-        for (int a = 0; a < nc; ++a)
-            for (int b = 0; b < nc; ++b) onp += ((double)re.rec(b).edge_n / (double)tot) * re.rec(a).Q;
-    *amax_out = amax;
-    return P.res_v_target == AZG_VT_ON_POLICY ? onp : qmax;
+    return root_totals(P, re, amax_out, true);
+}
+// The final action of a game from those edges (continuous mode), by one thread; amax: root_totals' first index of the largest count.
+__device__ __forceinline__ int final_pick(const KParams& P, const ActRule& ar, unsigned gtree, const RootEdges& re, int amax) {
+    const int nc = re.nc;
+    // ContinuousAgent.act (agents.py:524-535): actions[Qs.argmax()] / actions[counts.argmax()], first index on ties
+    int pick = amax;
+    if (ar.final_selection == AZG_FS_MAX_VALUE) {
+        double qb = 0.0;
+        for (int a = 0; a < nc; ++a) { const double q = re.rec(a).Q; if (a == 0 || q > qb) { qb = q; pick = a; } }
+    }
+    if (ar.agent_eps != 0.0) {
+        // epsilon_greedy (agents.py:471-490): random.random() < epsilon -> np.random.choice(actions)
+        azg_u32x4 b = azg_draw(P.seed, gtree, ar.step_idx, 0u, AZG_STREAM_ACT);
+        if ((double)azg_u01(b.v[0]) < ar.agent_eps) pick = (int)(b.v[1] % (unsigned)nc);
+    }
+    return pick;
 }
 
 // Roots with more than 16 children: one thread per game, reading the root's child edges from the published (global) trees, so this
@@ -265,20 +302,9 @@ __global__ __launch_bounds__(SPW_THREADS) void selfplay_kernel(KParams P, SelfPl
     const int K = P.res_Kmax, S_obs = sp.S_obs;
     float* row = sp.rows + (size_t)tree * (S_obs + 3 * K + 1);
     const RootEdges re(P, tree);
-    const int nc = re.nc;
     int amax = 0;
     const double v_target = row_targets(P, re, row + S_obs, &amax);
-    // ContinuousAgent.act (agents.py:524-535): actions[Qs.argmax()] / actions[counts.argmax()], first index on ties
-    int pick = amax;
-    if (sp.final_selection == AZG_FS_MAX_VALUE) {
-        double qb = 0.0;
-        for (int a = 0; a < nc; ++a) { const double q = re.rec(a).Q; if (a == 0 || q > qb) { qb = q; pick = a; } }
-    }
-    if (sp.agent_eps != 0.0) {
-        // epsilon_greedy (agents.py:471-490): random.random() < epsilon -> np.random.choice(actions)
-        azg_u32x4 b = azg_draw(P.seed, gtree, sp.step_idx, 0u, AZG_STREAM_ACT);
-        if ((double)azg_u01(b.v[0]) < sp.agent_eps) pick = (int)(b.v[1] % (unsigned)nc);
-    }
+    const int pick = final_pick(P, sp.rule, gtree, re, amax);
     selfplay_finish(P, sp, tree, row, re.act(pick), v_target, 0);
 }
 
@@ -327,4 +353,99 @@ __global__ __launch_bounds__(SPW_THREADS) void reanalyse_kernel(KParams P, Reana
     int amax = 0;
     const double v_target = row_targets(P, re, row + ra.S_obs, &amax);
     row[ra.S_obs + 3 * P.res_Kmax] = (float)v_target;
+}
+
+// ------------------------------------------------------------------------------------------------ search rollouts
+
+// Whole evaluation episodes under MCTS (azg_search_rollout, include/azgym_search_rollout.h): every game plays E episodes, each step
+// an ordinary search from the call's own roots followed by one of the step kernels below -- the self-play step without a replay row.
+// Tree t = k*T + j starts its i-th episode from the reset state of global game game_id_base + j, episode episode + i; the draws stay
+// keyed by tree_base + t.
+struct SearchRollout {
+    int max_len, E, T;            // episode length limit, episodes per game, games per net
+    unsigned game_id_base, episode;
+    ActRule rule;
+    int* t; int* ep;              // [B] steps into the running episode, episodes finished (E: the game is parked)
+    double* ret;                  // [B] the running episode's return
+    double* returns; int* lengths; int* terminated;   // [B][E]
+    double* roots; int* carry;    // the searches' roots [B][S] and carried counts [B]
+    int* unfinished;              // games that have not finished their E-th episode
+};
+
+#define SR_THREADS 256
+__global__ __launch_bounds__(SR_THREADS) void search_rollout_init_kernel(KParams P, SearchRollout sr) {
+    const int tree = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tree == 0) *sr.unfinished = P.B;
+    if (tree >= P.B) return;
+    double ns[4] = {0.0, 0.0, 0.0, 0.0};
+    azg_reset_state(P.seed, sr.game_id_base + (unsigned)(tree % sr.T), sr.episode, azg_reset_kind(P.env_id), ns);
+    for (int k = 0; k < P.S; ++k) sr.roots[(size_t)tree * P.S + k] = ns[k];
+    sr.carry[tree] = 0;
+    sr.t[tree] = 0;
+    sr.ep[tree] = 0;
+    sr.ret[tree] = 0.0;
+    for (int i = 0; i < sr.E; ++i) {
+        sr.returns[(size_t)tree * sr.E + i] = 0.0;
+        sr.lengths[(size_t)tree * sr.E + i] = 0;
+        sr.terminated[(size_t)tree * sr.E + i] = 0;
+    }
+}
+
+// What follows the pick, for one game by its one writer: the real env step with the picked action, the episode's books, its outputs at
+// its end and the next search's root.  carry: as selfplay_finish.  A parked game (E episodes finished) is left as it is.
+__device__ __forceinline__ void search_rollout_finish(const KParams& P, const SearchRollout& sr, int tree, float action, int carry) {
+    int ep = sr.ep[tree];
+    if (ep >= sr.E) return;
+    const int S = P.S;
+    double root[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < S; ++k) root[k] = sr.roots[(size_t)tree * S + k];
+    float obs[8];
+    double sn;
+    game_obs(P.env_id, root, obs, &sn);
+    double ns[4] = {0.0, 0.0, 0.0, 0.0}, r;
+    int done;
+    game_step(P.env_id, root, sn, action, ns, &r, &done);
+    double ret = sr.ret[tree] + r;
+    int t = sr.t[tree] + 1;
+    if (done || t >= sr.max_len) {
+        const size_t o = (size_t)tree * sr.E + ep;
+        sr.returns[o] = ret;
+        sr.lengths[o] = t;
+        sr.terminated[o] = done ? 1 : 0;
+        ret = 0.0;
+        t = 0;
+        ep += 1;
+        sr.ep[tree] = ep;
+        // (after the E-th episode: the root the game is parked on)
+        azg_reset_state(P.seed, sr.game_id_base + (unsigned)(tree % sr.T), sr.episode + (unsigned)ep, azg_reset_kind(P.env_id), ns);
+        carry = 0;
+        if (ep == sr.E) atomicSub(sr.unfinished, 1);
+    }
+    sr.carry[tree] = carry;
+    sr.ret[tree] = ret;
+    sr.t[tree] = t;
+    for (int k = 0; k < S; ++k) sr.roots[(size_t)tree * S + k] = ns[k];
+}
+
+// The two self-play kernels without the row: totals, pick (final_pick16 / final_pick) and search_rollout_finish.
+__global__ __launch_bounds__(16 * SP_TREES) void search_rollout_kernel16(KParams P, SearchRollout sr) {
+    const int sub = threadIdx.x & 15;
+    const int tree = blockIdx.x * SP_TREES + (threadIdx.x >> 4);
+    if (tree >= P.B) return;
+    RootLane h;
+    const RootTotals rt = root_totals16(P, tree, sub, h, false);
+    const int pick = final_pick16(P, sr.rule, (unsigned)(P.tree_base + tree), rt, h);
+    const float pact = __shfl(h.act, pick, 16);
+    const int pnode_n = __shfl(h.node_n, pick, 16);   // (0 where the picked edge has no child node yet)
+    if (sub != 0) return;
+    search_rollout_finish(P, sr, tree, pact, P.mode == AZG_MODE_CONTINUOUS ? 0 : pnode_n);
+}
+__global__ __launch_bounds__(SPW_THREADS) void search_rollout_kernel(KParams P, SearchRollout sr) {
+    const int tree = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tree >= P.B) return;
+    const RootEdges re(P, tree);
+    int amax = 0;
+    (void)root_totals(P, re, &amax, false);
+    const int pick = final_pick(P, sr.rule, (unsigned)(P.tree_base + tree), re, amax);
+    search_rollout_finish(P, sr, tree, re.act(pick), 0);
 }

@@ -118,6 +118,7 @@ struct azg_engine : EngineQueue {
     double* d_sp_states = nullptr; double* d_sp_states_mem = nullptr; double* d_ra_roots = nullptr; int* d_ra_carry = nullptr; int* d_ra_slots = nullptr;
     std::vector<int32_t> ra_slots;   // host side of d_ra_slots (outlives the asynchronous copy)
     DeviceAllocs sp_mem;
+    DeviceBuffer sr_buf, sr_ctab;    // azg_search_rollout: its roots, carried counts, books and outputs in one block; its (c / m)^temperature table (grow-only)
     unsigned* d_team_cnt = nullptr; size_t team_cnt_bytes = 0;   // team kernel: hand-off counters + abort word
     int team_pending = 0;    // a team kernel has been launched since its abort word was last read
     int team_fallbacks = 0;  // searches it gave up on (redone by the per-layer launches)

@@ -1,11 +1,13 @@
 // engine_selfplay.hip -- the C ABI's device-resident self-play (azg_selfplay_*, azg_population_selfplay_begin), the reanalysis of its
-// replay ring (azgym_reanalyse.h) and the launches of the small kernels after a search: results_kernel, the self-play step and the
-// reanalysis' gather and row kernels (aux_kernels.cuh is compiled in this unit only).
+// replay ring (azgym_reanalyse.h), the search rollouts (azgym_search_rollout.h) and the launches of the small kernels after a search:
+// results_kernel, the self-play step, the reanalysis' gather and row kernels and the search rollouts' step (aux_kernels.cuh is
+// compiled in this unit only).
 #include <cmath>
 #include <cstring>
 
 #include "engine_host.h"
 #include "../../include/azgym_reanalyse.h"
+#include "../../include/azgym_search_rollout.h"
 #include "mlp.cuh"
 #include "aux_kernels.cuh"
 
@@ -17,6 +19,30 @@ int launch_results(azg_engine* e) {
     hipLaunchKernelGGL(results_kernel, dim3((B + RS_TREES - 1) / RS_TREES), dim3(16 * RS_TREES), 0, e->stream, e->P);
     HIPCHK(e, hipGetLastError());
     e->results_valid = 1;   // (in stream order: whatever reads the buffers is ordered after this launch)
+    return AZG_OK;
+}
+
+// The final-action rule's settings, as azg_selfplay_config and azg_search_rollout_config carry them: what both refuse
+static int act_rule_refusal(azg_engine* e, int final_selection, double temperature, double agent_epsilon) {
+    if (final_selection != AZG_FS_MAX_VISIT && final_selection != AZG_FS_MAX_VALUE) return fail(e, AZG_E_INVALID, "unknown final_selection");
+    if (!(temperature > 0.0)) return fail(e, AZG_E_INVALID, "temperature must be > 0");
+    if (agent_epsilon < 0.0 || agent_epsilon > 1.0) return fail(e, AZG_E_INVALID, "agent_epsilon must be in [0, 1]");
+    if (e->cfg.mode == AZG_MODE_DISCRETE && final_selection == AZG_FS_MAX_VALUE && temperature != 1.0)
+        return fail(e, AZG_E_UNSUPPORTED, "final_selection max_value on the device supports temperature 1 only");
+    return AZG_OK;
+}
+
+// Discrete mode with temperature != 1: stable_normalizer (helpers.py:10-27) raises x / max(x) to the temperature: (c / m)^t for every
+// pair of a root edge count c and the root's largest count m that can occur, python float pow = libm pow on the host (like check_pw's
+// table), at [m (m + 1) / 2 + c].  Empty (and AZG_OK) where the rule needs no table.
+static int act_rule_ctab(azg_engine* e, double temperature, std::vector<double>& tab) {
+    tab.clear();
+    if (e->cfg.mode != AZG_MODE_DISCRETE || temperature == 1.0) return AZG_OK;
+    const size_t ns = (size_t)e->cfg.n_sims;
+    if (ns > 2048) return fail(e, AZG_E_UNSUPPORTED, "temperature != 1 on the device supports n_sims <= 2048");
+    tab.assign((ns + 1) * (ns + 2) / 2, 0.0);
+    for (size_t m = 1; m <= ns; ++m)
+        for (size_t k = 0; k <= m; ++k) tab[m * (m + 1) / 2 + k] = std::pow((double)k / (double)m, temperature);
     return AZG_OK;
 }
 
@@ -32,11 +58,8 @@ static int selfplay_begin_impl(azg_engine* e, const azg_selfplay_config* c) {
     if (c->max_episode_length < 1 || c->capacity_steps < 1) return fail(e, AZG_E_INVALID, "max_episode_length and capacity_steps must be >= 1");
     if (c->final_selection != AZG_FS_MAX_VISIT && c->final_selection != AZG_FS_MAX_VALUE) return fail(e, AZG_E_INVALID, "unknown final_selection");
     if (c->ring_mode != AZG_RING_STOP && c->ring_mode != AZG_RING_FIFO) return fail(e, AZG_E_INVALID, "unknown ring_mode");
-    if (!(c->temperature > 0.0)) return fail(e, AZG_E_INVALID, "temperature must be > 0");
-    if (c->agent_epsilon < 0.0 || c->agent_epsilon > 1.0) return fail(e, AZG_E_INVALID, "agent_epsilon must be in [0, 1]");
+    { int rrc = act_rule_refusal(e, c->final_selection, c->temperature, c->agent_epsilon); if (rrc) return rrc; }
     const bool discrete = e->cfg.mode == AZG_MODE_DISCRETE;
-    if (discrete && c->final_selection == AZG_FS_MAX_VALUE && c->temperature != 1.0)
-        return fail(e, AZG_E_UNSUPPORTED, "final_selection max_value on the device supports temperature 1 only");
     ON_DEVICE(e);
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->sp_mem.clear();
@@ -49,16 +72,14 @@ static int selfplay_begin_impl(azg_engine* e, const azg_selfplay_config* c) {
         dalloc(e, e->sp_mem, &e->d_sp_rows, (size_t)c->capacity_steps * B * e->sp_row))
         return AZG_E_DEVICE;
     e->d_sp_ctab = nullptr;
-    if (discrete && c->temperature != 1.0) {
-        // stable_normalizer (helpers.py:10-27) raises x / max(x) to the temperature: (c / m)^t for every pair of a root edge count c
-        // and the root's largest count m that can occur, python float pow = libm pow on the host (like check_pw's table)
-        const size_t ns = (size_t)e->cfg.n_sims;
-        if (ns > 2048) return fail(e, AZG_E_UNSUPPORTED, "temperature != 1 on the device supports n_sims <= 2048");
-        std::vector<double> tab((ns + 1) * (ns + 2) / 2, 0.0);
-        for (size_t m = 1; m <= ns; ++m)
-            for (size_t k = 0; k <= m; ++k) tab[m * (m + 1) / 2 + k] = std::pow((double)k / (double)m, c->temperature);
-        if (dalloc(e, e->sp_mem, &e->d_sp_ctab, tab.size())) return AZG_E_DEVICE;
-        HIPCHK(e, hipMemcpy(e->d_sp_ctab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    {
+        std::vector<double> tab;
+        int trc = act_rule_ctab(e, c->temperature, tab);
+        if (trc) return trc;
+        if (!tab.empty()) {
+            if (dalloc(e, e->sp_mem, &e->d_sp_ctab, tab.size())) return AZG_E_DEVICE;
+            HIPCHK(e, hipMemcpy(e->d_sp_ctab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+        }
     }
     HIPCHK(e, hipMemset(e->d_sp_t, 0, B * 4));
     HIPCHK(e, hipMemset(e->d_sp_episode, 0, B * 4));
@@ -115,8 +136,9 @@ int azg_selfplay_step(azg_engine* e) {
     if (e->sp_steps < e->sp_cap) { slot = e->sp_steps; e->sp_steps += 1; }
     else { slot = e->sp_insert; e->sp_insert = (e->sp_insert + 1) % e->sp_steps; }
     SelfPlay sp;
-    sp.max_len = e->sp_max_len; sp.deterministic = e->sp_det; sp.S_obs = e->S_obs; sp.step_idx = e->sp_step_idx;
-    sp.final_selection = e->sp_fs; sp.agent_eps = e->sp_agent_eps; sp.ctab = e->d_sp_ctab;
+    sp.max_len = e->sp_max_len; sp.S_obs = e->S_obs;
+    sp.rule.deterministic = e->sp_det; sp.rule.final_selection = e->sp_fs; sp.rule.agent_eps = e->sp_agent_eps; sp.rule.ctab = e->d_sp_ctab;
+    sp.rule.step_idx = e->sp_step_idx;
     sp.t = e->d_sp_t; sp.episode = e->d_sp_episode; sp.fcnt = e->d_sp_fcnt; sp.ret = e->d_sp_ret; sp.fsum = e->d_sp_fsum;
     sp.rows = e->d_sp_rows + (size_t)slot * e->cfg.n_trees * e->sp_row;
     sp.states = e->d_sp_states ? e->d_sp_states + (size_t)slot * e->cfg.n_trees * e->S_env : nullptr;
@@ -257,6 +279,104 @@ int azg_selfplay_reanalyse(azg_engine* e, const int32_t* slots, int32_t slot, ui
         hipLaunchKernelGGL(reanalyse_kernel, dim3((B + SPW_THREADS - 1) / SPW_THREADS), dim3(SPW_THREADS), 0, e->stream, e->P, ra);   // (reads the trees)
     }
     HIPCHK(e, hipGetLastError());
+    return AZG_OK;
+}
+
+// ---- search rollouts (include/azgym_search_rollout.h)
+
+// The steps of azg_search_rollout, with the evaluation's roots in place of the engine's: one ordinary search per step under search
+// index index_base + s, then the step kernel; the count of unfinished games is read every poll_steps steps.
+static int search_rollout_steps(azg_engine* e, const azg_search_rollout_config* c, SearchRollout& sr, int* steps, int* polls) {
+    const int B = e->cfg.n_trees;
+    const long long bound = (long long)c->episodes_per_game * c->max_episode_length;
+    for (long long s = 0; s < bound; ++s) {
+        e->search_idx = c->index_base + (uint32_t)s;
+        int rc = azg_search_resident(e);
+        if (!rc) rc = settle_team(e);   // (wide networks: the persistent team kernel may have given up)
+        if (rc) return rc;
+        sr.rule.step_idx = c->index_base + (uint32_t)s;
+        if (e->Kmax <= 16) {
+            rc = launch_results(e);
+            if (rc) return rc;
+            hipLaunchKernelGGL(search_rollout_kernel16, dim3((B + SP_TREES - 1) / SP_TREES), dim3(16 * SP_TREES), 0, e->stream, e->P, sr);
+        } else {
+            hipLaunchKernelGGL(search_rollout_kernel, dim3((B + SPW_THREADS - 1) / SPW_THREADS), dim3(SPW_THREADS), 0, e->stream, e->P, sr);   // (reads the trees)
+        }
+        HIPCHK(e, hipGetLastError());
+        *steps += 1;
+        if ((s + 1) % c->poll_steps == 0 && s + 1 < bound) {
+            int left = 0;
+            HIPCHK(e, hipMemcpyAsync(&left, sr.unfinished, 4, hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(e, hipStreamSynchronize(e->stream));
+            *polls += 1;
+            if (left == 0) break;
+        }
+    }
+    return AZG_OK;
+}
+
+int azg_search_rollout(azg_engine* e, const azg_search_rollout_config* c, double* returns, int32_t* lengths, int32_t* terminated,
+                       azg_search_rollout_info* info) {
+    if (!e) return AZG_E_INVALID;
+    if (!c || !returns || !lengths) return fail(e, AZG_E_INVALID, "azg_search_rollout: cfg, returns and lengths must not be NULL");
+    if (c->struct_size != (int32_t)sizeof(azg_search_rollout_config)) return fail(e, AZG_E_INVALID, "azg_search_rollout_config size mismatch");
+    if (info && info->struct_size != (int32_t)sizeof(azg_search_rollout_info)) return fail(e, AZG_E_INVALID, "azg_search_rollout_info size mismatch");
+    if (c->episodes_per_game < 1 || c->max_episode_length < 1 || c->poll_steps < 1)
+        return fail(e, AZG_E_INVALID, "episodes_per_game, max_episode_length and poll_steps must be >= 1");
+    if ((long long)c->episodes_per_game * c->max_episode_length > (1LL << 30))
+        return fail(e, AZG_E_INVALID, "episodes_per_game * max_episode_length must be at most 2^30 steps");
+    int rc = act_rule_refusal(e, c->final_selection, c->temperature, c->agent_epsilon);
+    if (rc) return rc;
+    std::vector<double> tab;
+    rc = act_rule_ctab(e, c->temperature, tab);
+    if (rc) return rc;
+    if (e->Kmax > 16 && e->cfg.mode != AZG_MODE_CONTINUOUS)   // (as azg_selfplay_step: cannot happen)
+        return fail(e, AZG_E_STATE, "search rollouts with more than 16 actions per node support continuous mode only");
+    rc = search_refusal(e);
+    if (rc) return rc;
+    ON_DEVICE(e);
+    rc = settle_team(e);   // (an abandoned team search is redone on the roots it was started with, before the evaluation's take their place)
+    if (rc) return rc;
+    // evaluation state and outputs in one block that only grows: float64 parts first
+    const size_t B = e->cfg.n_trees, S = e->S_env, E = c->episodes_per_game;
+    const size_t o_roots = 0, o_ret = o_roots + B * S * 8, o_returns = o_ret + B * 8, o_lengths = o_returns + B * E * 8,
+                 o_term = o_lengths + B * E * 4, o_carry = o_term + B * E * 4, o_t = o_carry + B * 4, o_ep = o_t + B * 4, o_left = o_ep + B * 4,
+                 bytes = o_left + 16;
+    if (!e->sr_buf.reserve(bytes)) return fail(e, AZG_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e->sr_buf.last));
+    if (!tab.empty()) {
+        if (!e->sr_ctab.reserve(tab.size() * 8)) return fail(e, AZG_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e->sr_ctab.last));
+        HIPCHK(e, hipMemcpy(e->sr_ctab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    }
+    char* const base = (char*)e->sr_buf.p;
+    SearchRollout sr;
+    sr.max_len = c->max_episode_length; sr.E = (int)E; sr.T = (int)(B / e->n_nets);
+    sr.game_id_base = c->game_id_base; sr.episode = c->episode;
+    sr.rule.deterministic = c->deterministic; sr.rule.final_selection = c->final_selection; sr.rule.agent_eps = c->agent_epsilon;
+    sr.rule.ctab = tab.empty() ? nullptr : (const double*)e->sr_ctab.p; sr.rule.step_idx = c->index_base;
+    sr.roots = (double*)(base + o_roots); sr.ret = (double*)(base + o_ret); sr.returns = (double*)(base + o_returns);
+    sr.lengths = (int*)(base + o_lengths); sr.terminated = (int*)(base + o_term); sr.carry = (int*)(base + o_carry);
+    sr.t = (int*)(base + o_t); sr.ep = (int*)(base + o_ep); sr.unfinished = (int*)(base + o_left);
+    hipLaunchKernelGGL(search_rollout_init_kernel, dim3(((int)B + SR_THREADS - 1) / SR_THREADS), dim3(SR_THREADS), 0, e->stream, e->P, sr);
+    HIPCHK(e, hipGetLastError());
+    // Ordinary searches from the evaluation's roots and carried counts.  The live games' are not touched -- the kernels read KParams'
+    // pointers -- and the running search index comes back on every path; an abandoned team search is redone while the evaluation's
+    // roots are still the engine's.
+    const double* const live_roots = e->P.roots;
+    const int* const live_carry = e->P.carry;
+    const int live_carry_max = e->carry_max;
+    const uint32_t idx_now = e->search_idx;
+    e->P.roots = sr.roots; e->P.carry = sr.carry;
+    e->carry_max = e->cfg.mode == AZG_MODE_DISCRETE ? e->cfg.n_sims : 0;   // (as self-play: a reused root carries at most n_sims)
+    int steps = 0, polls = 0;
+    rc = search_rollout_steps(e, c, sr, &steps, &polls);
+    e->P.roots = live_roots; e->P.carry = live_carry; e->carry_max = live_carry_max; e->search_idx = idx_now;
+    if (steps) e->redo_ok = 0;   // (the roots are the live games' again: the search that just ran cannot be re-run for a dump)
+    if (rc) { (void)hipStreamSynchronize(e->stream); return rc; }
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipMemcpy(returns, sr.returns, B * E * 8, hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(lengths, sr.lengths, B * E * 4, hipMemcpyDeviceToHost));
+    D2H(terminated, sr.terminated, B * E * 4);
+    if (info) { info->steps = steps; info->polls = polls; }
     return AZG_OK;
 }
 

@@ -305,6 +305,9 @@ EVAL_GAME_ID_BASE = 1 << 30
 # (a step's search runs under the engine's running index, which counts up from 0): no reanalysis shares an index with a self-play
 # search of the same tree
 REANALYSE_INDEX_BASE = 1 << 31
+# evaluate_search()'s searches run under RNG search indices from here on: above self-play's and apart from the reanalyses' first
+# 2^30.  The default is the same at every call, so the same nets give the same number
+EVAL_SEARCH_INDEX_BASE = 3 << 30
 
 
 class PopulationSelfPlay:
@@ -489,6 +492,49 @@ class PopulationSelfPlay:
                                          episode=int(episode))
         out["mean_return"] = out["returns"].mean(axis=1)
         return out
+
+    def evaluate_search(self, episodes_per_game: int = 1, final_selection: str = "max_visit", deterministic: bool = True,
+                        temperature: float = 1.0, agent_epsilon: float = 0.0, max_episode_length: Optional[int] = None, episode: int = 0,
+                        game_id_base: Optional[int] = None, index_base: int = EVAL_SEARCH_INDEX_BASE,
+                        poll_steps: int = 8) -> Dict[str, np.ndarray]:
+        """How good each net is when it acts with its search: every game of the engine plays ``episodes_per_game`` whole episodes
+        under MCTS on the device in one call (azg_search_rollout), with the engine's own search -- per-net settings and budgets
+        included -- and the final-action rule given here (``evaluate``'s counterpart for ``Agent.act``; the defaults are the greedy
+        rule).  Game j of EVERY net starts its i-th episode from the state of global game ``game_id_base + j``, episode
+        ``episode + i``: ``evaluate``'s start states, so the nets can be ranked and compared with their raw policies.  Step s
+        searches under RNG search index ``index_base + s``: the same nets give the same number at every call.
+        ``max_episode_length`` None: the self-play's own limit; ``game_id_base`` None: as ``evaluate``.  Pending weight uploads are
+        applied first, as ``play`` does; the self-play's games, ring and search index are left untouched.  Returns
+        [n_nets, games_per_net, episodes_per_game] arrays "returns", "lengths", "terminated", plus "mean_return" [n_nets] and
+        "steps" (the searches run)."""
+        if final_selection not in _capi.FINAL_SELECTION:
+            raise ValueError(f"evaluate_search: final_selection must be one of {sorted(_capi.FINAL_SELECTION)}, not {final_selection!r}")
+        if int(episodes_per_game) < 1:
+            raise ValueError("evaluate_search: episodes_per_game must be >= 1")
+        if max_episode_length is None:
+            max_episode_length = self.max_episode_length
+        if int(max_episode_length) < 1:
+            raise ValueError("evaluate_search: max_episode_length must be >= 1")
+        if int(poll_steps) < 1:
+            raise ValueError("evaluate_search: poll_steps must be >= 1")
+        if not float(temperature) > 0.0:
+            raise ValueError("evaluate_search: temperature must be > 0")
+        if not 0.0 <= float(agent_epsilon) <= 1.0:
+            raise ValueError("evaluate_search: agent_epsilon must be in [0, 1]")
+        if not 0 <= int(index_base) < (1 << 32) or not 0 <= int(episode) < (1 << 32):
+            raise ValueError("evaluate_search: index_base and episode must fit 32 bits")
+        if game_id_base is None:
+            game_id_base = max(EVAL_GAME_ID_BASE, self.tree_id_base + self.n_games)
+        self.sync_weights()
+        out = self.engine.search_rollout(int(episodes_per_game), int(max_episode_length), final_selection=final_selection,
+                                         deterministic=bool(deterministic), temperature=float(temperature),
+                                         agent_epsilon=float(agent_epsilon), game_id_base=int(game_id_base), episode=int(episode),
+                                         index_base=int(index_base), poll_steps=int(poll_steps))
+        shape = (self.n_nets, self.games_per_net, int(episodes_per_game))
+        res = {k: out[k].reshape(shape) for k in ("returns", "lengths", "terminated")}
+        res["mean_return"] = res["returns"].reshape(self.n_nets, -1).mean(axis=1)
+        res["steps"] = out["steps"]
+        return res
 
     def close(self) -> None:
         self.engine.close()

@@ -33,7 +33,10 @@ where rows stay in the ring -- --replay-steps, or --trainer device-epoch -- and 
 Seed k sets net k's initial weights (torch.manual_seed), and its own np.random.RandomState picks the training rows and the
 minibatch shuffles.  Prints one JSON line per iteration: per-seed mean return of the episodes finished in it and mean loss, and
 the time spent in self-play, training and weight sync.  --eval-episodes N adds eval_return: each seed's raw policy (no search) over
-the same N start states, the number by which the seeds can be ranked."""
+the same N start states, the number by which the seeds can be ranked.  --eval-search-episodes E adds eval_search_return beside it:
+every game of every seed plays E whole episodes under MCTS -- the seed's own settings and budget, the greedy final-action rule -- on the
+device in one call and on state of its own (PopulationSelfPlay.evaluate_search): each seed's return as the agent acts, over those same
+start states; with --n-rollouts-per-seed it is a strength-against-budget curve."""
 import argparse
 import json
 import os
@@ -98,6 +101,11 @@ def parse_args(argv=None):
                          "one call (PopulationSelfPlay.evaluate; any width, --wide nets included) and add the per-seed mean return as "
                          "eval_return; every seed starts from the same states, so the numbers can be ranked (0: no evaluation)")
     ap.add_argument("--eval-rule", choices=["mode", "sample"], default="mode", help="the evaluation's action rule")
+    ap.add_argument("--eval-search-episodes", type=int, default=0,
+                    help="after every iteration let every game of every seed play this many whole episodes under MCTS (the seed's own "
+                         "search settings and budget, the greedy final-action rule) on the device in one call "
+                         "(PopulationSelfPlay.evaluate_search) and add the per-seed mean return as eval_search_return, over "
+                         "--eval-episodes' start states; the self-play's games are left as they are (0: no evaluation)")
     ap.add_argument("--replay-steps", type=int, default=0,
                     help="keep the newest R self-play steps in the device ring across iterations (FIFO) and train on rows picked from all "
                          "of them (0: every iteration trains on its own steps and clears the ring); R >= --steps-per-iter, nets on the GPU")
@@ -108,6 +116,8 @@ def parse_args(argv=None):
     why = check_replay(a)
     if why:
         ap.error(why)
+    if a.eval_search_episodes < 0:
+        ap.error("--eval-search-episodes must be >= 0")
     if a.lrs is not None and len(a.lrs) != len(a.seeds):
         ap.error(f"--lrs needs one value per --seeds entry ({len(a.seeds)}), got {len(a.lrs)}")
     for flag, vals in search_sweeps(a).items():
@@ -281,6 +291,9 @@ def train(a, log=print, on_rows=None, on_end=None):
         if a.eval_episodes > 0:   # the nets as just trained and uploaded, each by itself, over the same start states
             ev = sp.evaluate(a.eval_episodes, rule=a.eval_rule)
             history[-1]["eval_return"] = [round(float(x), 2) for x in ev["mean_return"]]
+        if getattr(a, "eval_search_episodes", 0) > 0:   # the same nets acting with their search, over those same start states
+            ev = sp.evaluate_search(a.eval_search_episodes)
+            history[-1]["eval_search_return"] = [round(float(x), 2) for x in ev["mean_return"]]
         if log:
             log(json.dumps(history[-1]), flush=True)
         fs0, fc0 = fs, fc

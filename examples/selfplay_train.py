@@ -13,6 +13,10 @@ Prints the mean return of the episodes finished in each iteration (one JSON line
 and trains on rows picked from all of them; --reanalyse-slots N then searches N random stored steps again with the current weights
 before each iteration's training and overwrites their targets (DeviceSelfPlay.reanalyse).  One process, policy on the GPU.
 
+--eval-search-episodes E adds eval_search_return: after every iteration every game plays E whole episodes under MCTS with the greedy
+final-action rule, on the device in one call and on state of its own (DeviceSelfPlay.evaluate_search): the return of the agent as it
+acts, over the same start states at every iteration.
+
 Multi-GPU (one process per GPU, RCCL):  python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
     examples/selfplay_train.py ...    Every rank plays --games games of its own (global game ids rank*games ...), the replay
 rows are all-gathered, rank 0 runs the optimiser step and broadcasts the weights (alphazero_gym_amd/distributed.py)."""
@@ -75,7 +79,13 @@ def parse_args(argv=None):
     ap.add_argument("--reanalyse-slots", type=int, default=0,
                     help="before each iteration's training, search this many random stored steps again with the current weights and "
                          "overwrite their targets (0: off); needs --replay-steps")
+    ap.add_argument("--eval-search-episodes", type=int, default=0,
+                    help="after every iteration let every game play this many whole episodes under MCTS with the greedy final-action "
+                         "rule, on the device in one call (DeviceSelfPlay.evaluate_search), and add their mean return as "
+                         "eval_search_return; the self-play's games are left as they are (0: no evaluation)")
     a = ap.parse_args(argv)
+    if a.eval_search_episodes < 0:
+        ap.error("--eval-search-episodes must be >= 0")
     if a.replay_steps < 0 or a.reanalyse_slots < 0:
         ap.error("--replay-steps and --reanalyse-slots must be >= 0")
     if a.replay_steps and a.replay_steps < a.steps_per_iter:
@@ -141,6 +151,9 @@ def train(a, log=print):
         history.append({"iter": it, "episodes_finished": fc - fc0, "mean_return": round(mean_ret, 2),
                         "loss": round(info["loss"] / n_batches, 4), "env_steps": (it + 1) * a.steps_per_iter * a.games * world,
                         "elapsed_s": round(time.time() - t0, 1)})
+        if getattr(a, "eval_search_episodes", 0) > 0:   # the net as just trained, acting with its search (this rank's games)
+            ev = sp.evaluate_search(a.eval_search_episodes)
+            history[-1]["eval_search_return"] = round(float(ev["mean_return"][0]), 2)
         if log and rank == 0:
             log(json.dumps(history[-1]), flush=True)
         fs0, fc0 = fs, fc
