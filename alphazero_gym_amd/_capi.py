@@ -96,6 +96,15 @@ class AzgEvalInfo(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("resident", C.c_int32), ("groups", C.c_int32), ("tiles", C.c_int32)]
 
 
+class AzgNstepConfig(C.Structure):
+    """include/azgym_nstep.h: azg_nstep_config"""
+    _fields_ = [("struct_size", C.c_int32), ("n_step", C.c_int32), ("gamma", C.c_double), ("flags", C.c_int32)]
+
+
+NSTEP_SEARCH_GAMMA = 1   # AZG_NSTEP_SEARCH_GAMMA: discount with the search's own gamma (the row's net's where a per-net table is set)
+END_NONE, END_TERMINAL, END_LENGTH = 0, 1, 2   # AZG_END_*: how a stored self-play step ended
+
+
 class AzgSearchRolloutConfig(C.Structure):
     """include/azgym_search_rollout.h: azg_search_rollout_config"""
     _fields_ = [("struct_size", C.c_int32), ("episodes_per_game", C.c_int32), ("max_episode_length", C.c_int32),
@@ -136,6 +145,7 @@ SYMBOLS = [
 OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device", "set_population_weights_device", "set_net_search",
                     "set_net_search_ex",
                     "population_selfplay_begin", "selfplay_keep_states", "selfplay_states", "selfplay_reanalyse",
+                    "selfplay_keep_transitions", "selfplay_transitions", "selfplay_nstep_targets",
                     "policy_rollout", "policy_rollout_ex", "search_rollout",
                     "population_mlp_eval", "population_mlp_eval_device", "population_root_eval",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
@@ -293,6 +303,11 @@ def bind(lib, prefix):
         f["selfplay_keep_states"].argtypes = [vp, C.c_int32]
         f["selfplay_states"].argtypes = [vp, C.POINTER(C.c_double), C.c_size_t]
         f["selfplay_reanalyse"].argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.c_uint32]
+    if "selfplay_nstep_targets" in f:   # include/azgym_nstep.h
+        f["selfplay_keep_transitions"].argtypes = [vp, C.c_int32]
+        f["selfplay_transitions"].argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                              C.c_size_t]
+        f["selfplay_nstep_targets"].argtypes = [vp, C.POINTER(AzgNstepConfig)]
     if "search_rollout" in f:   # include/azgym_search_rollout.h
         f["search_rollout"].argtypes = [vp, C.POINTER(AzgSearchRolloutConfig), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.POINTER(AzgSearchRolloutInfo)]
@@ -912,8 +927,40 @@ def _selfplay_methods():
             raise ValueError(f"slots: an int or one slot per game (length {self.n_trees}), got shape {arr.shape}")
         self._check(fn(self._h, _ptr(arr, C.c_int32), 0, int(search_index) & 0xFFFFFFFF))
 
+    def selfplay_keep_transitions(self, on=True):
+        """azg_selfplay_keep_transitions: keep every stored step's reward, float64 value target, action and end kind beside the
+        replay ring (what selfplay_nstep_targets reads).  Right after a begin, while the ring is empty; the next begin drops it."""
+        self._check(self._optional("selfplay_keep_transitions")(self._h, int(bool(on))))
+
+    def selfplay_transitions(self):
+        """The kept transitions of the stored steps, ordered like selfplay_rows: a dict of [steps*B] arrays "reward" float64 (in a
+        tree node's units: continuous mode divided by reward_scale), "value" float64 (the value target before its rounding to the
+        row), "action" float32 and "end" int32 (END_NONE / END_TERMINAL / END_LENGTH)."""
+        fn = self._optional("selfplay_transitions")
+        cap = getattr(self, "_sp_cap", 0) * self.n_trees   # (before any begin: nothing to hold, the engine refuses)
+        d = dict(reward=np.empty(cap, np.float64), value=np.empty(cap, np.float64), action=np.empty(cap, np.float32),
+                 end=np.empty(cap, np.int32))
+        n = fn(self._h, _ptr(d["reward"], C.c_double), _ptr(d["value"], C.c_double), _ptr(d["action"], C.c_float),
+               _ptr(d["end"], C.c_int32), cap)
+        if n < 0:
+            self._check(n)
+        return {k: v[:n] for k, v in d.items()}
+
+    def selfplay_nstep_targets(self, n_step, gamma=None):
+        """azg_selfplay_nstep_targets: rewrite every stored row's V_target column as the n-step return of its game column from the
+        kept transitions -- discounted rewards up to the first terminal step, else bootstrapped from the search value n_step steps
+        on, at the first time-limit step or at the newest stored step, whichever comes first (include/azgym_nstep.h; asynchronous).
+        ``gamma`` None: the search's own gamma, the row's net's where a per-net table is set."""
+        c = AzgNstepConfig()
+        c.struct_size = C.sizeof(AzgNstepConfig)
+        c.n_step = int(n_step)
+        c.gamma = 0.0 if gamma is None else float(gamma)
+        c.flags = NSTEP_SEARCH_GAMMA if gamma is None else 0
+        self._check(self._optional("selfplay_nstep_targets")(self._h, C.byref(c)))
+
     for fn in (selfplay_begin, population_selfplay_begin, selfplay_ring, selfplay_rows_device, selfplay_step, selfplay_rows, selfplay_clear, selfplay_stats,
-               selfplay_keep_states, selfplay_states, selfplay_reanalyse):
+               selfplay_keep_states, selfplay_states, selfplay_reanalyse, selfplay_keep_transitions, selfplay_transitions,
+               selfplay_nstep_targets):
         setattr(Engine, fn.__name__, fn)
 
 

@@ -12,6 +12,7 @@
 #include "env.cuh"
 #include "tree.cuh"
 #include "results.cuh"
+#include "../../include/azgym_nstep.h"
 
 // ------------------------------------------------------------------------------------------------ result gathering
 
@@ -51,12 +52,16 @@ struct SelfPlay {
     double* ret; double* fsum;
     float* rows;          // this step's block [B][row_len]
     double* states;       // this step's block of the state ring [B][S] (azg_selfplay_keep_states), NULL: states are not kept
+    // this step's blocks [B] of the kept transitions (azg_selfplay_keep_transitions, azgym_nstep.h), all NULL: not kept
+    double* tr_reward; double* tr_value; float* tr_action; int* tr_end;
     double* roots; int* carry;
 };
 
 // What follows the pick, for one game by its one writer: the row's observation and value-target columns, the real env step with the
 // picked action, the episode's books and the next search's root.  carry: the visit count of the picked child's node where the next
-// search may start from it (discrete mode), else 0; an episode's end drops it.
+// search may start from it (discrete mode), else 0; an episode's end drops it.  Where transitions are kept, the step's entry: the reward
+// in a tree node's units (Cold::r: continuous mode divides by reward_scale, as tree_phases.cuh does), the value target before its
+// rounding, the action and how the step ended.
 __device__ __forceinline__ void selfplay_finish(const KParams& P, const SelfPlay& sp, int tree, float* row, float action, double v_target,
                                                 int carry) {
     const int S = P.S;
@@ -75,6 +80,12 @@ __device__ __forceinline__ void selfplay_finish(const KParams& P, const SelfPlay
     game_step(P.env_id, root, sn, action, ns, &r, &done);
     double ret = sp.ret[tree] + r;
     int t = sp.t[tree] + 1;
+    if (sp.tr_reward) {
+        sp.tr_reward[tree] = P.mode == AZG_MODE_CONTINUOUS ? r / P.reward_scale : r;
+        sp.tr_value[tree] = v_target;
+        sp.tr_action[tree] = action;
+        sp.tr_end[tree] = done ? AZG_END_TERMINAL : (t >= sp.max_len ? AZG_END_LENGTH : AZG_END_NONE);
+    }
     if (done || t >= sp.max_len) {
         sp.fsum[tree] = sp.fsum[tree] + ret;
         sp.fcnt[tree] += 1;
@@ -319,6 +330,7 @@ struct Reanalyse {
     const double* states;   // the state ring [capacity_steps][B][S]
     float* rows;            // the replay ring [capacity_steps][B][row_len]
     double* roots; int* carry;   // the search's staging roots [B][S] and carried counts [B] (zero)
+    double* tr_value;       // the kept float64 value targets [capacity_steps][B] (azg_selfplay_keep_transitions), NULL: not kept
 };
 __device__ __forceinline__ int reanalyse_slot(const Reanalyse& ra, int tree) { return ra.slots ? ra.slots[tree] : ra.slot; }
 __device__ __forceinline__ float* reanalyse_row(const KParams& P, const Reanalyse& ra, int tree) {
@@ -343,7 +355,9 @@ __global__ __launch_bounds__(16 * SP_TREES) void reanalyse_kernel16(KParams P, R
     float* row = reanalyse_row(P, ra, tree);
     RootLane h;
     const RootTotals rt = row_targets16(P, tree, sub, row + ra.S_obs, h);
-    if (sub == 0) row[ra.S_obs + 3 * P.res_Kmax] = (float)rt.v_target;
+    if (sub != 0) return;
+    row[ra.S_obs + 3 * P.res_Kmax] = (float)rt.v_target;
+    if (ra.tr_value) ra.tr_value[(size_t)reanalyse_slot(ra, tree) * P.B + tree] = rt.v_target;
 }
 __global__ __launch_bounds__(SPW_THREADS) void reanalyse_kernel(KParams P, Reanalyse ra) {
     const int tree = blockIdx.x * blockDim.x + threadIdx.x;
@@ -353,6 +367,49 @@ __global__ __launch_bounds__(SPW_THREADS) void reanalyse_kernel(KParams P, Reana
     int amax = 0;
     const double v_target = row_targets(P, re, row + ra.S_obs, &amax);
     row[ra.S_obs + 3 * P.res_Kmax] = (float)v_target;
+    if (ra.tr_value) ra.tr_value[(size_t)reanalyse_slot(ra, tree) * P.B + tree] = v_target;
+}
+
+// ------------------------------------------------------------------------------------------------ n-step return targets
+
+// The V_target column of every stored row from the kept transitions (azg_selfplay_nstep_targets, include/azgym_nstep.h states the
+// rule).  One thread per stored row: thread pos * B + tree takes the row at chronological position pos of game column `tree`, so
+// consecutive lanes are consecutive trees of one slot and every load of the [slot][tree] arrays is coalesced.  Position p lies in
+// ring slot (oldest + p) mod size.  A streaming pass: a forward scan of at most n_step end kinds, a backward fold over as many
+// rewards, one store.
+struct NStep {
+    int B, T;                 // games; games per net
+    int size, oldest;         // stored steps; the ring slot of the oldest one
+    int n_step;               // (the host clamps it to size: a longer window cannot reach further)
+    int row_len, vcol;        // a row's length and its V_target column
+    double gamma;             // where nets is NULL
+    const NetSearchRec* nets; // AZG_NSTEP_SEARCH_GAMMA with a per-net table: net tree / T discounts with its own gamma
+    const double* reward; const double* value; const int* end;   // [capacity_steps][B]
+    float* rows;              // the replay ring [capacity_steps][B][row_len]
+};
+#define NS_THREADS 256
+__global__ __launch_bounds__(NS_THREADS) void nstep_targets_kernel(NStep ns) {
+    const long long idx = (long long)blockIdx.x * NS_THREADS + threadIdx.x;
+    if (idx >= (long long)ns.size * ns.B) return;
+    const int s = (int)(idx / ns.B), tree = (int)(idx - (long long)s * ns.B);
+    const double gamma = ns.nets ? ns.nets[tree / ns.T].gamma : ns.gamma;
+    const int last = ns.size - 1;
+    // element (position p, tree) of a [slot][tree] array (p <= last: the sum stays below 2 * size)
+    auto at = [&](int p) { int slot = ns.oldest + p; if (slot >= ns.size) slot -= ns.size; return (size_t)slot * ns.B + tree; };
+    // the window's far end: the first step in s .. s + n_step - 1 that ended its episode, else L = min(s + n_step, last)
+    int L = s + ns.n_step < last ? s + ns.n_step : last;
+    const int hi = s + ns.n_step - 1 < last ? s + ns.n_step - 1 : last;
+    bool terminal = false;
+    for (int i = s; i <= hi; ++i) {
+        const int end = ns.end[at(i)];
+        if (end != AZG_END_NONE) { L = i; terminal = end == AZG_END_TERMINAL; break; }
+    }
+    // terminal: rewards s .. L and nothing beyond; else rewards s .. L - 1 and L's search value
+    double acc = 0.0;
+    int i = L;
+    if (!terminal) { acc = ns.value[at(L)]; i = L - 1; }
+    for (; i >= s; --i) acc = ns.reward[at(i)] + gamma * acc;
+    ns.rows[at(s) * (size_t)ns.row_len + ns.vcol] = (float)acc;
 }
 
 // ------------------------------------------------------------------------------------------------ search rollouts

@@ -117,6 +117,10 @@ struct azg_engine : EngineQueue {
     // reanalysis searches from: staging roots [n_trees][S_env], zero carried counts and the device copy of its slots [n_trees]
     double* d_sp_states = nullptr; double* d_sp_states_mem = nullptr; double* d_ra_roots = nullptr; int* d_ra_carry = nullptr; int* d_ra_slots = nullptr;
     std::vector<int32_t> ra_slots;   // host side of d_ra_slots (outlives the asynchronous copy)
+    // azg_selfplay_keep_transitions: the stored steps' reward, float64 value target, action and end kind beside the rows, each
+    // [sp_cap][n_trees] (sp_tr_on 0: not kept; the allocations stay until the next begin)
+    int sp_tr_on = 0;
+    double* d_sp_tr_reward = nullptr; double* d_sp_tr_value = nullptr; float* d_sp_tr_action = nullptr; int* d_sp_tr_end = nullptr;
     DeviceAllocs sp_mem;
     DeviceBuffer sr_buf, sr_ctab;    // azg_search_rollout: its roots, carried counts, books and outputs in one block; its (c / m)^temperature table (grow-only)
     unsigned* d_team_cnt = nullptr; size_t team_cnt_bytes = 0;   // team kernel: hand-off counters + abort word

@@ -1,12 +1,13 @@
 // engine_selfplay.hip -- the C ABI's device-resident self-play (azg_selfplay_*, azg_population_selfplay_begin), the reanalysis of its
-// replay ring (azgym_reanalyse.h), the search rollouts (azgym_search_rollout.h) and the launches of the small kernels after a search:
-// results_kernel, the self-play step, the reanalysis' gather and row kernels and the search rollouts' step (aux_kernels.cuh is
-// compiled in this unit only).
+// replay ring (azgym_reanalyse.h), the ring's n-step return targets (azgym_nstep.h), the search rollouts (azgym_search_rollout.h) and the
+// launches of the small kernels after a search: results_kernel, the self-play step, the reanalysis' gather and row kernels, the n-step
+// target kernel and the search rollouts' step (aux_kernels.cuh is compiled in this unit only).
 #include <cmath>
 #include <cstring>
 
 #include "engine_host.h"
 #include "../../include/azgym_reanalyse.h"
+#include "../../include/azgym_nstep.h"
 #include "../../include/azgym_search_rollout.h"
 #include "mlp.cuh"
 #include "aux_kernels.cuh"
@@ -65,6 +66,8 @@ static int selfplay_begin_impl(azg_engine* e, const azg_selfplay_config* c) {
     e->sp_mem.clear();
     e->sp_on = 0;
     e->d_sp_states = e->d_sp_states_mem = nullptr;   // (azg_selfplay_keep_states is asked for again after every begin)
+    e->sp_tr_on = 0;                                 // (azg_selfplay_keep_transitions too)
+    e->d_sp_tr_reward = e->d_sp_tr_value = nullptr; e->d_sp_tr_action = nullptr; e->d_sp_tr_end = nullptr;
     const size_t B = e->cfg.n_trees;
     e->sp_row = e->S_obs + 3 * e->Kmax + 1;
     if (dalloc(e, e->sp_mem, &e->d_sp_t, B) || dalloc(e, e->sp_mem, &e->d_sp_episode, B) || dalloc(e, e->sp_mem, &e->d_sp_fcnt, B) ||
@@ -144,6 +147,9 @@ int azg_selfplay_step(azg_engine* e) {
     sp.states = e->d_sp_states ? e->d_sp_states + (size_t)slot * e->cfg.n_trees * e->S_env : nullptr;
     sp.roots = e->d_roots; sp.carry = e->d_carry;
     const int B = e->cfg.n_trees;
+    const size_t tr_at = (size_t)slot * B;
+    sp.tr_reward = e->sp_tr_on ? e->d_sp_tr_reward + tr_at : nullptr; sp.tr_value = e->sp_tr_on ? e->d_sp_tr_value + tr_at : nullptr;
+    sp.tr_action = e->sp_tr_on ? e->d_sp_tr_action + tr_at : nullptr; sp.tr_end = e->sp_tr_on ? e->d_sp_tr_end + tr_at : nullptr;
     e->redo_ok = 0;   // (the step moves the roots on: the search that just ran cannot be re-run for a dump)
     if (e->Kmax <= 16) {
         rc = launch_results(e);   // return_results of this search (a launch only after the lock-step / team kernels)
@@ -251,6 +257,7 @@ int azg_selfplay_reanalyse(azg_engine* e, const int32_t* slots, int32_t slot, ui
     Reanalyse ra;
     ra.slots = nullptr; ra.slot = slot; ra.S_obs = e->S_obs;
     ra.states = e->d_sp_states; ra.rows = e->d_sp_rows; ra.roots = e->d_ra_roots; ra.carry = e->d_ra_carry;
+    ra.tr_value = e->sp_tr_on ? e->d_sp_tr_value : nullptr;
     if (slots) {
         e->ra_slots.assign(slots, slots + B);
         HIPCHK(e, hipMemcpyAsync(e->d_ra_slots, e->ra_slots.data(), (size_t)B * 4, hipMemcpyHostToDevice, e->stream));
@@ -278,6 +285,72 @@ int azg_selfplay_reanalyse(azg_engine* e, const int32_t* slots, int32_t slot, ui
     } else {
         hipLaunchKernelGGL(reanalyse_kernel, dim3((B + SPW_THREADS - 1) / SPW_THREADS), dim3(SPW_THREADS), 0, e->stream, e->P, ra);   // (reads the trees)
     }
+    HIPCHK(e, hipGetLastError());
+    return AZG_OK;
+}
+
+// ---- n-step return targets (include/azgym_nstep.h)
+
+int azg_selfplay_keep_transitions(azg_engine* e, int32_t on) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (e->sp_steps != 0) return fail(e, AZG_E_STATE, "azg_selfplay_keep_transitions: the replay ring is not empty (call it right after begin, or after clearing the rows)");
+    if (!on) { e->sp_tr_on = 0; return AZG_OK; }   // (the memory goes with the next begin)
+    if (e->sp_tr_on) return AZG_OK;
+    ON_DEVICE(e);
+    const size_t n = (size_t)e->sp_cap * e->cfg.n_trees;
+    if (!e->d_sp_tr_reward &&   // (switched off and on again within one begin: the blocks are still there)
+        (dalloc(e, e->sp_mem, &e->d_sp_tr_reward, n) || dalloc(e, e->sp_mem, &e->d_sp_tr_value, n) ||
+         dalloc(e, e->sp_mem, &e->d_sp_tr_action, n) || dalloc(e, e->sp_mem, &e->d_sp_tr_end, n))) {
+        e->d_sp_tr_reward = nullptr;
+        return AZG_E_DEVICE;
+    }
+    e->sp_tr_on = 1;
+    return AZG_OK;
+}
+
+int azg_selfplay_transitions(azg_engine* e, double* reward, double* value, float* action, int32_t* end, size_t max_rows) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (!e->sp_tr_on) return fail(e, AZG_E_STATE, "azg_selfplay_keep_transitions has not been called");
+    ON_DEVICE(e);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    size_t n = (size_t)e->sp_steps * e->cfg.n_trees;
+    if (n > max_rows) n = max_rows;
+    if (n) {
+        D2H(reward, e->d_sp_tr_reward, n * 8);
+        D2H(value, e->d_sp_tr_value, n * 8);
+        D2H(action, e->d_sp_tr_action, n * 4);
+        D2H(end, e->d_sp_tr_end, n * 4);
+    }
+    return (int)n;
+}
+
+int azg_selfplay_nstep_targets(azg_engine* e, const azg_nstep_config* c) {
+    if (!e) return AZG_E_INVALID;
+    if (!c) return fail(e, AZG_E_INVALID, "azg_selfplay_nstep_targets: cfg must not be NULL");
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (!e->sp_tr_on) return fail(e, AZG_E_STATE, "azg_selfplay_keep_transitions has not been called: the stored steps' rewards and ends were not kept");
+    if (c->struct_size != (int32_t)sizeof(azg_nstep_config)) return fail(e, AZG_E_INVALID, "azg_nstep_config size mismatch");
+    if (c->n_step < 0) return fail(e, AZG_E_INVALID, "azg_selfplay_nstep_targets: n_step must be >= 0");
+    if (c->flags & ~(int32_t)AZG_NSTEP_SEARCH_GAMMA) return fail(e, AZG_E_INVALID, "azg_selfplay_nstep_targets: unknown flag bits (AZG_NSTEP_SEARCH_GAMMA is the only flag)");
+    const bool search_gamma = (c->flags & AZG_NSTEP_SEARCH_GAMMA) != 0;
+    if (!search_gamma && !(c->gamma >= 0.0 && std::isfinite(c->gamma)))
+        return fail(e, AZG_E_INVALID, "azg_selfplay_nstep_targets: gamma must be finite and >= 0 (or set AZG_NSTEP_SEARCH_GAMMA)");
+    if (e->sp_steps == 0) return AZG_OK;
+    ON_DEVICE(e);
+    NStep ns;
+    ns.B = e->cfg.n_trees; ns.T = e->cfg.n_trees / e->n_nets;
+    // ReplayBuffer.store's order: while the ring fills, slot 0 holds the oldest step (and the insert index is 0); once it overwrites,
+    // the oldest step is the next one to go, at the insert index
+    ns.size = e->sp_steps; ns.oldest = e->sp_insert;
+    ns.n_step = c->n_step < e->sp_steps ? c->n_step : e->sp_steps;
+    ns.row_len = e->sp_row; ns.vcol = e->sp_row - 1;
+    ns.gamma = search_gamma ? e->cfg.gamma : c->gamma;
+    ns.nets = search_gamma ? e->net_search.rec : nullptr;
+    ns.reward = e->d_sp_tr_reward; ns.value = e->d_sp_tr_value; ns.end = e->d_sp_tr_end; ns.rows = e->d_sp_rows;
+    const long long rows = (long long)ns.size * ns.B;
+    hipLaunchKernelGGL(nstep_targets_kernel, dim3((unsigned)((rows + NS_THREADS - 1) / NS_THREADS)), dim3(NS_THREADS), 0, e->stream, ns);
     HIPCHK(e, hipGetLastError());
     return AZG_OK;
 }

@@ -324,14 +324,21 @@ class PopulationSelfPlay:
     replay ring into the reference's overwrite-the-oldest buffer (buffers.py:75-82).  Weights are re-uploaded only when some
     policy changed (``PopulationMCTS.sync_weights``; ``last_weight_sync``: "device", "host" or None when nothing changed).
     ``reanalyse=True`` keeps every stored step's env states beside the ring, so that ``reanalyse()`` can search stored positions
-    again with the current weights and overwrite their rows' targets."""
+    again with the current weights and overwrite their rows' targets.
+    ``n_step`` (an integer >= 0; None: off, nothing is kept and the rows are today's) turns the rows' value targets into n-step
+    returns: the engine keeps every stored step's reward, search value and end kind beside the ring, and ``play`` and
+    ``reanalyse`` end with ``nstep_targets()``, which rewrites the ring's V_target column as the discounted rewards of the next
+    ``n_step`` steps plus the discounted search value after them (include/azgym_nstep.h: a terminal step closes the window with
+    no bootstrap; a time-limit step and the newest stored step bootstrap from their own search value).  ``target_gamma`` None:
+    the search's gamma, net k's own where ``net_settings`` gives it one."""
 
     def __init__(self, policies, *, game: str, games_per_net: int, n_rollouts: int, c_uct: float, gamma: float = 1.0, epsilon: float = 0.0,
                  c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
                  deterministic: bool = False, capacity_steps: int = 64, seed: int = 34, tree_id_base: int = 0, device_id: int = 0,
                  final_selection: str = "max_visit", temperature: float = 1.0, agent_epsilon: float = 0.0, fifo: bool = False,
                  net_settings: Optional[List[dict]] = None, net_settings_wide: Optional[bool] = None,
-                 net_rollouts: Optional[List[int]] = None, reanalyse: bool = False):
+                 net_rollouts: Optional[List[int]] = None, reanalyse: bool = False, n_step: Optional[int] = None,
+                 target_gamma: Optional[float] = None):
         policies = list(policies)
         if not policies or games_per_net < 1:
             raise ValueError(f"{type(self).__name__} needs at least one policy and games_per_net >= 1")
@@ -360,6 +367,12 @@ class PopulationSelfPlay:
         self._reanalyse_rng = np.random.default_rng(seed)
         if self.reanalysing:
             self.engine.selfplay_keep_states(True)
+        if n_step is not None and int(n_step) < 0:
+            raise ValueError(f"{type(self).__name__}: n_step must be >= 0 or None")
+        self.n_step = None if n_step is None else int(n_step)
+        self.target_gamma = None if target_gamma is None else float(target_gamma)
+        if self.n_step is not None:
+            self.engine.selfplay_keep_transitions(True)
 
     @staticmethod
     def _search(policies, games_per_net: int, **kw) -> PopulationMCTS:
@@ -382,6 +395,16 @@ class PopulationSelfPlay:
         self.sync_weights()
         for _ in range(n_steps):
             self.engine.selfplay_step()
+        if self.n_step is not None:
+            self.nstep_targets()
+
+    def nstep_targets(self, n_step: Optional[int] = None, gamma: Optional[float] = None) -> None:
+        """Rewrite the V_target column of every stored row as its n-step return (``Engine.selfplay_nstep_targets``; asynchronous:
+        one launch).  ``n_step`` / ``gamma`` None: the ones given at creation (``target_gamma`` None: the search's gamma).
+        Idempotent: ``play`` and ``reanalyse`` already end with it."""
+        if self.n_step is None:
+            raise RuntimeError(f"{type(self).__name__}.nstep_targets needs the stored steps' rewards and ends: create it with n_step=...")
+        self.engine.selfplay_nstep_targets(self.n_step if n_step is None else int(n_step), self.target_gamma if gamma is None else float(gamma))
 
     def reanalyse(self, slots=None, n: int = 1, rng: Optional[np.random.Generator] = None) -> list:
         """MuZero's Reanalyse on the device ring: search stored positions again with the CURRENT weights (pending uploads are
@@ -405,6 +428,8 @@ class PopulationSelfPlay:
         for s in used:
             self.engine.selfplay_reanalyse(s, search_index=self._reanalyse_index)
             self._reanalyse_index += 1
+        if self.n_step is not None:   # (the reanalysed rows hold plain search values again: back to n-step returns, from the fresh values)
+            self.nstep_targets()
         return used
 
     def play_device(self, n_steps: int):

@@ -28,6 +28,10 @@ steps; it needs the nets on the GPU.  --reanalyse-slots N then searches N random
 each iteration's training and overwrites their targets (PopulationSelfPlay.reanalyse: MuZero's Reanalyse, on the device).  It applies
 where rows stay in the ring -- --replay-steps, or --trainer device-epoch -- and is refused elsewhere.
 
+--n-step N trains the value heads on n-step returns instead of the search's root value: the discounted rewards of the next N steps
+plus the discounted search value after them, computed on the device from the transitions kept beside the ring (PopulationSelfPlay
+n_step=N; an episode's terminal step closes the window, a time limit and the newest stored step bootstrap from their own search value).
+
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
 Seed k sets net k's initial weights (torch.manual_seed), and its own np.random.RandomState picks the training rows and the
@@ -112,6 +116,9 @@ def parse_args(argv=None):
     ap.add_argument("--reanalyse-slots", type=int, default=0,
                     help="before each iteration's training, search this many random stored steps again with the current weights and "
                          "overwrite their targets (0: off); with --replay-steps or --trainer device-epoch")
+    ap.add_argument("--n-step", type=int, default=None,
+                    help="value targets are n-step returns over the stored steps (discounted with each net's search gamma) instead of "
+                         "the search's root value; 0 keeps the root value (default: off, nothing is kept)")
     a = ap.parse_args(argv)
     why = check_replay(a)
     if why:
@@ -166,6 +173,8 @@ def check_replay(a):
     """Why --replay-steps / --reanalyse-slots cannot be honoured as given (None: they can)."""
     if a.replay_steps < 0 or a.reanalyse_slots < 0:
         return "--replay-steps and --reanalyse-slots must be >= 0"
+    if getattr(a, "n_step", None) is not None and a.n_step < 0:
+        return "--n-step must be >= 0"
     if a.replay_steps and a.replay_steps < a.steps_per_iter:
         return f"--replay-steps ({a.replay_steps}) must hold at least one iteration's steps (--steps-per-iter {a.steps_per_iter})"
     if a.replay_steps and not a.device.startswith("cuda"):
@@ -201,7 +210,7 @@ def build_population(a):
                                 c_uct=m.c_uct, gamma=m.gamma, epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0),
                                 kappa=getattr(m, "kappa", 0.5), max_episode_length=a.max_episode_length,
                                 capacity_steps=getattr(a, "replay_steps", 0) or a.steps_per_iter, fifo=bool(getattr(a, "replay_steps", 0)),
-                                reanalyse=getattr(a, "reanalyse_slots", 0) > 0, seed=a.engine_seed,
+                                reanalyse=getattr(a, "reanalyse_slots", 0) > 0, n_step=getattr(a, "n_step", None), seed=a.engine_seed,
                                 device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0, **search_kwargs(a))
     return agents, state_dim, sp
 

@@ -13,6 +13,10 @@ Prints the mean return of the episodes finished in each iteration (one JSON line
 and trains on rows picked from all of them; --reanalyse-slots N then searches N random stored steps again with the current weights
 before each iteration's training and overwrites their targets (DeviceSelfPlay.reanalyse).  One process, policy on the GPU.
 
+--n-step N trains the value head on n-step returns instead of the search's root value: the discounted rewards of the next N steps plus
+the discounted search value after them, computed on the device from the transitions kept beside the ring (DeviceSelfPlay n_step=N;
+an episode's terminal step closes the window, a time limit and the newest stored step bootstrap from their own search value).
+
 --eval-search-episodes E adds eval_search_return: after every iteration every game plays E whole episodes under MCTS with the greedy
 final-action rule, on the device in one call and on state of its own (DeviceSelfPlay.evaluate_search): the return of the agent as it
 acts, over the same start states at every iteration.
@@ -83,11 +87,16 @@ def parse_args(argv=None):
                     help="after every iteration let every game play this many whole episodes under MCTS with the greedy final-action "
                          "rule, on the device in one call (DeviceSelfPlay.evaluate_search), and add their mean return as "
                          "eval_search_return; the self-play's games are left as they are (0: no evaluation)")
+    ap.add_argument("--n-step", type=int, default=None,
+                    help="value targets are n-step returns over the stored steps (discounted with the search's gamma) instead of the "
+                         "search's root value; 0 keeps the root value (default: off, nothing is kept)")
     a = ap.parse_args(argv)
     if a.eval_search_episodes < 0:
         ap.error("--eval-search-episodes must be >= 0")
     if a.replay_steps < 0 or a.reanalyse_slots < 0:
         ap.error("--replay-steps and --reanalyse-slots must be >= 0")
+    if a.n_step is not None and a.n_step < 0:
+        ap.error("--n-step must be >= 0")
     if a.replay_steps and a.replay_steps < a.steps_per_iter:
         ap.error(f"--replay-steps ({a.replay_steps}) must hold at least one iteration's steps (--steps-per-iter {a.steps_per_iter})")
     if a.replay_steps and (not a.device.startswith("cuda") or int(os.environ.get("WORLD_SIZE", "1")) > 1):
@@ -111,7 +120,7 @@ def train(a, log=print):
     sp = run.DeviceSelfPlay(agent.nn, game=a.game, n_games=a.games, n_rollouts=a.n_rollouts, c_uct=m.c_uct, gamma=m.gamma,
                             epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0), kappa=getattr(m, "kappa", 0.5),
                             max_episode_length=a.max_episode_length, capacity_steps=replay_steps or a.steps_per_iter, fifo=bool(replay_steps),
-                            reanalyse=reanalyse_slots > 0, seed=a.seed, rank=rank,
+                            reanalyse=reanalyse_slots > 0, n_step=getattr(a, "n_step", None), seed=a.seed, rank=rank,
                             device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0)
     K = sp.engine.kmax if continuous else 2
     rng = np.random.RandomState(a.seed)
