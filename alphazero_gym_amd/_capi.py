@@ -105,6 +105,20 @@ NSTEP_SEARCH_GAMMA = 1   # AZG_NSTEP_SEARCH_GAMMA: discount with the search's ow
 END_NONE, END_TERMINAL, END_LENGTH = 0, 1, 2   # AZG_END_*: how a stored self-play step ended
 
 
+class AzgPriorityConfig(C.Structure):
+    """include/azgym_priority.h: azg_priority_config"""
+    _fields_ = [("struct_size", C.c_int32), ("source", C.c_int32), ("alpha", C.c_float), ("eps", C.c_float),
+                ("given", C.POINTER(C.c_float))]
+
+
+class AzgSampleConfig(C.Structure):
+    """include/azgym_priority.h: azg_sample_config"""
+    _fields_ = [("struct_size", C.c_int32), ("n_order", C.c_int32), ("sample_index", C.c_uint32)]
+
+
+PRIO_VALUE_GAP, PRIO_GIVEN = 0, 1   # AZG_PRIO_*: a row's priority from |search value - V_target|, or from the caller's array
+
+
 class AzgSearchRolloutConfig(C.Structure):
     """include/azgym_search_rollout.h: azg_search_rollout_config"""
     _fields_ = [("struct_size", C.c_int32), ("episodes_per_game", C.c_int32), ("max_episode_length", C.c_int32),
@@ -146,6 +160,8 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "set_net_search_ex",
                     "population_selfplay_begin", "selfplay_keep_states", "selfplay_states", "selfplay_reanalyse",
                     "selfplay_keep_transitions", "selfplay_transitions", "selfplay_nstep_targets",
+                    "selfplay_keep_priorities", "selfplay_priorities", "selfplay_priority_values", "selfplay_sample_rows",
+                    "selfplay_sample_slots",
                     "policy_rollout", "policy_rollout_ex", "search_rollout",
                     "population_mlp_eval", "population_mlp_eval_device", "population_root_eval",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
@@ -308,6 +324,12 @@ def bind(lib, prefix):
         f["selfplay_transitions"].argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                               C.c_size_t]
         f["selfplay_nstep_targets"].argtypes = [vp, C.POINTER(AzgNstepConfig)]
+    if "selfplay_sample_rows" in f:   # include/azgym_priority.h
+        f["selfplay_keep_priorities"].argtypes = [vp, C.c_int32]
+        f["selfplay_priorities"].argtypes = [vp, C.POINTER(AzgPriorityConfig)]
+        f["selfplay_priority_values"].argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t]
+        f["selfplay_sample_rows"].argtypes = [vp, C.POINTER(AzgSampleConfig), C.POINTER(C.c_int32)]
+        f["selfplay_sample_slots"].argtypes = [vp, C.c_uint32, C.POINTER(C.c_int32)]
     if "search_rollout" in f:   # include/azgym_search_rollout.h
         f["search_rollout"].argtypes = [vp, C.POINTER(AzgSearchRolloutConfig), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.POINTER(AzgSearchRolloutInfo)]
@@ -958,9 +980,58 @@ def _selfplay_methods():
         c.flags = NSTEP_SEARCH_GAMMA if gamma is None else 0
         self._check(self._optional("selfplay_nstep_targets")(self._h, C.byref(c)))
 
+    def selfplay_keep_priorities(self, on=True):
+        """azg_selfplay_keep_priorities: keep a fixed-point priority per stored row beside the replay ring, and the scratch of the
+        proportional draws (include/azgym_priority.h).  After a begin, at any ring size; the next begin drops it."""
+        self._check(self._optional("selfplay_keep_priorities")(self._h, int(bool(on))))
+
+    def selfplay_priorities(self, alpha, eps, given=None):
+        """azg_selfplay_priorities: the priority of every stored row, (d + eps)^alpha in fixed point (asynchronous: one launch).
+        ``given`` None: d is |kept search value - the row's V_target| (needs selfplay_keep_transitions); else d is ``given``, a
+        float32 array with one entry >= 0 per stored row, ordered like selfplay_rows."""
+        c = AzgPriorityConfig()
+        c.struct_size = C.sizeof(AzgPriorityConfig)
+        c.source = PRIO_VALUE_GAP if given is None else PRIO_GIVEN
+        c.alpha, c.eps = float(alpha), float(eps)
+        if given is not None:
+            given = np.ascontiguousarray(given, np.float32).reshape(-1)
+            size = self.selfplay_ring()[0] if getattr(self, "_sp_cap", 0) else 0
+            if given.shape[0] != size * self.n_trees:
+                raise ValueError(f"given: one entry per stored row ({size * self.n_trees}), got {given.shape[0]}")
+            c.given = _ptr(given, C.c_float)
+        self._check(self._optional("selfplay_priorities")(self._h, C.byref(c)))
+
+    def selfplay_priority_values(self):
+        """The stored rows' priorities as the draws see them: uint64 [steps*B] with 20 fractional bits, ordered like selfplay_rows."""
+        fn = self._optional("selfplay_priority_values")
+        q = np.empty(getattr(self, "_sp_cap", 0) * self.n_trees, np.uint64)
+        n = fn(self._h, _ptr(q, C.c_uint64), q.shape[0])
+        if n < 0:
+            self._check(n)
+        return q[:n]
+
+    def selfplay_sample_rows(self, n_order, sample_index):
+        """azg_selfplay_sample_rows: ``n_order`` row numbers per net drawn in proportion to the priorities, with replacement, on the
+        device: int32 [n_nets, n_order], net k's rows numbered slot * T + game as a training epoch over the ring numbers them.  The
+        same ``sample_index`` gives the same draws.  Needs selfplay_priorities since the last step, clear or begin."""
+        c = AzgSampleConfig()
+        c.struct_size = C.sizeof(AzgSampleConfig)
+        c.n_order, c.sample_index = int(n_order), int(sample_index) & 0xFFFFFFFF
+        order = np.empty((int(getattr(self, "n_nets", 1)), max(int(n_order), 1)), np.int32)
+        self._check(self._optional("selfplay_sample_rows")(self._h, C.byref(c), _ptr(order, C.c_int32)))
+        return order
+
+    def selfplay_sample_slots(self, sample_index):
+        """azg_selfplay_sample_slots: one stored slot per game drawn in proportion to the priorities of the game's column: int32
+        [n_trees], what selfplay_reanalyse takes as ``slots``."""
+        slots = np.empty(self.n_trees, np.int32)
+        self._check(self._optional("selfplay_sample_slots")(self._h, int(sample_index) & 0xFFFFFFFF, _ptr(slots, C.c_int32)))
+        return slots
+
     for fn in (selfplay_begin, population_selfplay_begin, selfplay_ring, selfplay_rows_device, selfplay_step, selfplay_rows, selfplay_clear, selfplay_stats,
                selfplay_keep_states, selfplay_states, selfplay_reanalyse, selfplay_keep_transitions, selfplay_transitions,
-               selfplay_nstep_targets):
+               selfplay_nstep_targets, selfplay_keep_priorities, selfplay_priorities, selfplay_priority_values, selfplay_sample_rows,
+               selfplay_sample_slots):
         setattr(Engine, fn.__name__, fn)
 
 

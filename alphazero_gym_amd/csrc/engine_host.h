@@ -121,7 +121,19 @@ struct azg_engine : EngineQueue {
     // [sp_cap][n_trees] (sp_tr_on 0: not kept; the allocations stay until the next begin)
     int sp_tr_on = 0;
     double* d_sp_tr_reward = nullptr; double* d_sp_tr_value = nullptr; float* d_sp_tr_action = nullptr; int* d_sp_tr_end = nullptr;
+    // azg_selfplay_keep_priorities (azgym_priority.h): a priority q per stored row [sp_cap][n_trees] (sp_prio_on 0: not kept; the
+    // allocations stay until the next begin), the upload of a caller's d [sp_cap][n_trees], the draws' prefix sums (within a segment
+    // [sp_cap][n_trees], segment totals [sp_prio_segs]) and the drawn slots [n_trees]
+    int sp_prio_on = 0;
+    unsigned long long* d_sp_prio_q = nullptr; float* d_sp_prio_given = nullptr; unsigned long long* d_sp_prio_within = nullptr;
+    unsigned long long* d_sp_prio_seg = nullptr; int* d_sp_prio_slots = nullptr;
+    size_t sp_prio_segs = 0;
+    std::vector<float> prio_given;   // host side of d_sp_prio_given (outlives the asynchronous copy)
+    // sp_rows_gen counts the changes of the ring's set of stored rows (a step, a clear, a begin); sp_prio_gen: its value when
+    // azg_selfplay_priorities last ran (-1: never since the begin or since priorities were switched on)
+    long long sp_rows_gen = 0, sp_prio_gen = -1;
     DeviceAllocs sp_mem;
+    DeviceBuffer sp_order_buf;       // azg_selfplay_sample_rows: the drawn row numbers [n_nets][n_order] (grow-only)
     DeviceBuffer sr_buf, sr_ctab;    // azg_search_rollout: its roots, carried counts, books and outputs in one block; its (c / m)^temperature table (grow-only)
     unsigned* d_team_cnt = nullptr; size_t team_cnt_bytes = 0;   // team kernel: hand-off counters + abort word
     int team_pending = 0;    // a team kernel has been launched since its abort word was last read

@@ -1,16 +1,19 @@
 // engine_selfplay.hip -- the C ABI's device-resident self-play (azg_selfplay_*, azg_population_selfplay_begin), the reanalysis of its
-// replay ring (azgym_reanalyse.h), the ring's n-step return targets (azgym_nstep.h), the search rollouts (azgym_search_rollout.h) and the
-// launches of the small kernels after a search: results_kernel, the self-play step, the reanalysis' gather and row kernels, the n-step
-// target kernel and the search rollouts' step (aux_kernels.cuh is compiled in this unit only).
+// replay ring (azgym_reanalyse.h), the ring's n-step return targets (azgym_nstep.h), its prioritised sampling (azgym_priority.h), the
+// search rollouts (azgym_search_rollout.h) and the launches of the small kernels after a search: results_kernel, the self-play step,
+// the reanalysis' gather and row kernels, the n-step target kernel, the priority, scan and draw kernels and the search rollouts' step
+// (aux_kernels.cuh and priority.cuh are compiled in this unit only).
 #include <cmath>
 #include <cstring>
 
 #include "engine_host.h"
 #include "../../include/azgym_reanalyse.h"
 #include "../../include/azgym_nstep.h"
+#include "../../include/azgym_priority.h"
 #include "../../include/azgym_search_rollout.h"
 #include "mlp.cuh"
 #include "aux_kernels.cuh"
+#include "priority.cuh"
 
 int launch_results(azg_engine* e) {
     if (!e->searched) return fail(e, AZG_E_STATE, "no search has run");
@@ -68,6 +71,9 @@ static int selfplay_begin_impl(azg_engine* e, const azg_selfplay_config* c) {
     e->d_sp_states = e->d_sp_states_mem = nullptr;   // (azg_selfplay_keep_states is asked for again after every begin)
     e->sp_tr_on = 0;                                 // (azg_selfplay_keep_transitions too)
     e->d_sp_tr_reward = e->d_sp_tr_value = nullptr; e->d_sp_tr_action = nullptr; e->d_sp_tr_end = nullptr;
+    e->sp_prio_on = 0;                               // (azg_selfplay_keep_priorities too)
+    e->d_sp_prio_q = e->d_sp_prio_within = e->d_sp_prio_seg = nullptr; e->d_sp_prio_given = nullptr; e->d_sp_prio_slots = nullptr;
+    e->sp_rows_gen += 1; e->sp_prio_gen = -1;
     const size_t B = e->cfg.n_trees;
     e->sp_row = e->S_obs + 3 * e->Kmax + 1;
     if (dalloc(e, e->sp_mem, &e->d_sp_t, B) || dalloc(e, e->sp_mem, &e->d_sp_episode, B) || dalloc(e, e->sp_mem, &e->d_sp_fcnt, B) ||
@@ -161,6 +167,7 @@ int azg_selfplay_step(azg_engine* e) {
     HIPCHK(e, hipGetLastError());
     e->sp_total += 1;
     e->sp_step_idx += 1;
+    e->sp_rows_gen += 1;
     return AZG_OK;
 }
 
@@ -172,7 +179,7 @@ int azg_selfplay_rows(azg_engine* e, float* rows, size_t max_rows, int32_t clear
     size_t n = (size_t)e->sp_steps * e->cfg.n_trees;
     if (n > max_rows) n = max_rows;
     if (rows && n) HIPCHK(e, hipMemcpy(rows, e->d_sp_rows, n * e->sp_row * 4, hipMemcpyDeviceToHost));
-    if (clear) { e->sp_steps = 0; e->sp_insert = 0; }   // ReplayBuffer.clear (buffers.py:56-60)
+    if (clear) { e->sp_steps = 0; e->sp_insert = 0; e->sp_rows_gen += 1; }   // ReplayBuffer.clear (buffers.py:56-60)
     return (int)n;
 }
 
@@ -352,6 +359,134 @@ int azg_selfplay_nstep_targets(azg_engine* e, const azg_nstep_config* c) {
     const long long rows = (long long)ns.size * ns.B;
     hipLaunchKernelGGL(nstep_targets_kernel, dim3((unsigned)((rows + NS_THREADS - 1) / NS_THREADS)), dim3(NS_THREADS), 0, e->stream, ns);
     HIPCHK(e, hipGetLastError());
+    return AZG_OK;
+}
+
+// ---- prioritised sampling (include/azgym_priority.h)
+
+int azg_selfplay_keep_priorities(azg_engine* e, int32_t on) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (!on) { e->sp_prio_on = 0; e->sp_prio_gen = -1; return AZG_OK; }   // (the memory goes with the next begin)
+    if (e->sp_prio_on) return AZG_OK;
+    const size_t n = (size_t)e->sp_cap * e->cfg.n_trees;
+    if (n >= ((size_t)1 << 31)) return fail(e, AZG_E_UNSUPPORTED, "azg_selfplay_keep_priorities: capacity_steps * n_trees must stay below 2^31 rows");
+    ON_DEVICE(e);
+    // every net's last segment may be partial: at most one segment more per net than the rows fill, and a net has at least one game
+    const size_t segs = n / PR_SEG + (size_t)e->cfg.n_trees + 1;
+    if (!e->d_sp_prio_q &&   // (switched off and on again within one begin: the blocks are still there)
+        (dalloc(e, e->sp_mem, &e->d_sp_prio_q, n) || dalloc(e, e->sp_mem, &e->d_sp_prio_within, n) ||
+         dalloc(e, e->sp_mem, &e->d_sp_prio_seg, segs) || dalloc(e, e->sp_mem, &e->d_sp_prio_given, n) ||
+         dalloc(e, e->sp_mem, &e->d_sp_prio_slots, (size_t)e->cfg.n_trees))) {
+        e->d_sp_prio_q = nullptr;
+        return AZG_E_DEVICE;
+    }
+    e->sp_prio_segs = segs;
+    e->sp_prio_on = 1; e->sp_prio_gen = -1;
+    return AZG_OK;
+}
+
+int azg_selfplay_priorities(azg_engine* e, const azg_priority_config* c) {
+    if (!e) return AZG_E_INVALID;
+    if (!c) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities: cfg must not be NULL");
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (!e->sp_prio_on) return fail(e, AZG_E_STATE, "azg_selfplay_keep_priorities has not been called");
+    if (c->struct_size != (int32_t)sizeof(azg_priority_config)) return fail(e, AZG_E_INVALID, "azg_priority_config size mismatch");
+    if (c->source != AZG_PRIO_VALUE_GAP && c->source != AZG_PRIO_GIVEN) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities: unknown source");
+    if (c->source == AZG_PRIO_VALUE_GAP && !e->sp_tr_on)
+        return fail(e, AZG_E_STATE, "azg_selfplay_priorities: AZG_PRIO_VALUE_GAP needs azg_selfplay_keep_transitions: the stored steps' search values were not kept");
+    if (!(c->alpha >= 0.0f && std::isfinite(c->alpha))) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities: alpha must be finite and >= 0");
+    if (!(c->eps > 0.0f && std::isfinite(c->eps))) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities: eps must be finite and > 0");
+    const size_t n = (size_t)e->sp_steps * e->cfg.n_trees;
+    if (c->source == AZG_PRIO_GIVEN) {
+        if (!c->given) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities: AZG_PRIO_GIVEN needs the given array");
+        for (size_t i = 0; i < n; ++i)
+            if (!(c->given[i] >= 0.0f)) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities: given[" + std::to_string(i) + "] is negative or NaN");
+    }
+    if (n == 0) { e->sp_prio_gen = e->sp_rows_gen; return AZG_OK; }
+    ON_DEVICE(e);
+    Priorities pr;
+    pr.rows_n = (long long)n; pr.source = c->source;
+    pr.row_len = e->sp_row; pr.vcol = e->sp_row - 1;
+    pr.alpha = c->alpha; pr.eps = c->eps;
+    pr.value = e->d_sp_tr_value; pr.rows = e->d_sp_rows; pr.given = e->d_sp_prio_given; pr.q = e->d_sp_prio_q;
+    if (c->source == AZG_PRIO_GIVEN) {
+        e->prio_given.assign(c->given, c->given + n);
+        HIPCHK(e, hipMemcpyAsync(e->d_sp_prio_given, e->prio_given.data(), n * 4, hipMemcpyHostToDevice, e->stream));
+    }
+    hipLaunchKernelGGL(priorities_kernel, dim3((unsigned)((n + PR_THREADS - 1) / PR_THREADS)), dim3(PR_THREADS), 0, e->stream, pr);
+    HIPCHK(e, hipGetLastError());
+    e->sp_prio_gen = e->sp_rows_gen;
+    return AZG_OK;
+}
+
+int azg_selfplay_priority_values(azg_engine* e, uint64_t* q, size_t max_rows) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (!e->sp_prio_on) return fail(e, AZG_E_STATE, "azg_selfplay_keep_priorities has not been called");
+    ON_DEVICE(e);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    size_t n = (size_t)e->sp_steps * e->cfg.n_trees;
+    if (n > max_rows) n = max_rows;
+    if (n) D2H(q, e->d_sp_prio_q, n * 8);
+    return (int)n;
+}
+
+// What both draws refuse: no begin, no keep_priorities, priorities older than the ring's set of stored rows, an empty ring
+static int sample_refusal(azg_engine* e, const char* who) {
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (!e->sp_prio_on) return fail(e, AZG_E_STATE, "azg_selfplay_keep_priorities has not been called");
+    if (e->sp_prio_gen != e->sp_rows_gen)
+        return fail(e, AZG_E_STATE, std::string(who) + ": azg_selfplay_priorities has not run since the ring's stored rows last changed (a step, a clear or a begin)");
+    if (e->sp_steps == 0) return fail(e, AZG_E_STATE, std::string(who) + ": the replay ring is empty");
+    return AZG_OK;
+}
+
+int azg_selfplay_sample_rows(azg_engine* e, const azg_sample_config* c, int32_t* order) {
+    if (!e) return AZG_E_INVALID;
+    if (!c || !order) return fail(e, AZG_E_INVALID, "azg_selfplay_sample_rows: cfg and order must not be NULL");
+    if (c->struct_size != (int32_t)sizeof(azg_sample_config)) return fail(e, AZG_E_INVALID, "azg_sample_config size mismatch");
+    if (c->n_order < 1) return fail(e, AZG_E_INVALID, "azg_selfplay_sample_rows: n_order must be >= 1");
+    int rc = sample_refusal(e, "azg_selfplay_sample_rows");
+    if (rc) return rc;
+    const int K = e->n_nets;
+    PrioScan ps;
+    ps.B = e->cfg.n_trees; ps.T = e->cfg.n_trees / K;
+    ps.N = e->sp_steps * ps.T; ps.nseg = (ps.N + PR_SEG - 1) / PR_SEG;
+    ps.q = e->d_sp_prio_q; ps.within = e->d_sp_prio_within; ps.seg = e->d_sp_prio_seg;
+    if ((size_t)K * ps.nseg > e->sp_prio_segs || K * ps.T != ps.B)   // (the population was changed after keep_priorities)
+        return fail(e, AZG_E_STATE, "azg_selfplay_sample_rows: the population changed since azg_selfplay_keep_priorities");
+    ON_DEVICE(e);
+    const size_t out_n = (size_t)K * c->n_order;
+    if (!e->sp_order_buf.reserve(out_n * 4)) return fail(e, AZG_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e->sp_order_buf.last));
+    hipLaunchKernelGGL(prio_scan_segments_kernel, dim3(ps.nseg, K), dim3(PR_THREADS), 0, e->stream, ps);
+    HIPCHK(e, hipGetLastError());
+    hipLaunchKernelGGL(prio_scan_totals_kernel, dim3(K), dim3(64), 0, e->stream, ps);
+    HIPCHK(e, hipGetLastError());
+    PrioRows dr;
+    dr.ps = ps; dr.n_order = c->n_order; dr.sample_index = c->sample_index; dr.tree_base = (unsigned)e->cfg.tree_id_base;
+    dr.seed = e->cfg.seed; dr.order = (int*)e->sp_order_buf.p;
+    hipLaunchKernelGGL(prio_draw_rows_kernel, dim3((c->n_order + PR_THREADS - 1) / PR_THREADS, K), dim3(PR_THREADS), 0, e->stream, dr);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(order, dr.order, out_n * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return AZG_OK;
+}
+
+int azg_selfplay_sample_slots(azg_engine* e, uint32_t sample_index, int32_t* slots) {
+    if (!e) return AZG_E_INVALID;
+    if (!slots) return fail(e, AZG_E_INVALID, "azg_selfplay_sample_slots: slots must not be NULL");
+    int rc = sample_refusal(e, "azg_selfplay_sample_slots");
+    if (rc) return rc;
+    ON_DEVICE(e);
+    const int B = e->cfg.n_trees;
+    PrioSlots dr;
+    dr.B = B; dr.size = e->sp_steps; dr.sample_index = sample_index; dr.tree_base = (unsigned)e->cfg.tree_id_base;
+    dr.seed = e->cfg.seed; dr.q = e->d_sp_prio_q; dr.slots = e->d_sp_prio_slots;
+    hipLaunchKernelGGL(prio_draw_slots_kernel, dim3((B + PR_THREADS - 1) / PR_THREADS), dim3(PR_THREADS), 0, e->stream, dr);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(slots, dr.slots, (size_t)B * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
     return AZG_OK;
 }
 

@@ -330,7 +330,13 @@ class PopulationSelfPlay:
     ``reanalyse`` end with ``nstep_targets()``, which rewrites the ring's V_target column as the discounted rewards of the next
     ``n_step`` steps plus the discounted search value after them (include/azgym_nstep.h: a terminal step closes the window with
     no bootstrap; a time-limit step and the newest stored step bootstrap from their own search value).  ``target_gamma`` None:
-    the search's gamma, net k's own where ``net_settings`` gives it one."""
+    the search's gamma, net k's own where ``net_settings`` gives it one.
+    ``prioritized`` (``{"alpha": 0.6, "eps": 1e-3}``; None: off, nothing is kept and behaviour is today's) keeps a priority per
+    stored row beside the ring (include/azgym_priority.h): ``(|search value - V_target| + eps) ** alpha``, MuZero's, which needs
+    ``n_step``.  ``sample_order(n)`` then draws training rows per net in proportion to it, on the device, in the form
+    ``PopulationTrainer.train_epoch_ring`` takes as its order, and ``reanalyse(by="priority")`` draws the reanalysed position of
+    every game the same way.  The draws are biased towards surprising rows and nothing corrects the loss for it: there are no
+    importance-sampling weights."""
 
     def __init__(self, policies, *, game: str, games_per_net: int, n_rollouts: int, c_uct: float, gamma: float = 1.0, epsilon: float = 0.0,
                  c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
@@ -338,10 +344,16 @@ class PopulationSelfPlay:
                  final_selection: str = "max_visit", temperature: float = 1.0, agent_epsilon: float = 0.0, fifo: bool = False,
                  net_settings: Optional[List[dict]] = None, net_settings_wide: Optional[bool] = None,
                  net_rollouts: Optional[List[int]] = None, reanalyse: bool = False, n_step: Optional[int] = None,
-                 target_gamma: Optional[float] = None):
+                 target_gamma: Optional[float] = None, prioritized: Optional[dict] = None):
         policies = list(policies)
         if not policies or games_per_net < 1:
             raise ValueError(f"{type(self).__name__} needs at least one policy and games_per_net >= 1")
+        if prioritized is not None:
+            if set(prioritized) - {"alpha", "eps"}:
+                raise ValueError(f"{type(self).__name__}: prioritized takes alpha and eps, not {sorted(set(prioritized) - {'alpha', 'eps'})}")
+            if n_step is None:
+                raise ValueError(f"{type(self).__name__}: prioritized needs n_step (the priority is |search value - n-step target|, and "
+                                 "both are kept only then)")
         kw = _game_engine_kwargs(game, policies[0], c_pw, kappa)
         if net_settings is not None:   # (opt-in: net k searches with its own c_uct / gamma / epsilon / c_pw / kappa, PopulationMCTS)
             kw["net_settings"] = net_settings
@@ -373,6 +385,13 @@ class PopulationSelfPlay:
         self.target_gamma = None if target_gamma is None else float(target_gamma)
         if self.n_step is not None:
             self.engine.selfplay_keep_transitions(True)
+        self.prioritized = None if prioritized is None else dict(alpha=float(prioritized.get("alpha", 0.6)),
+                                                                 eps=float(prioritized.get("eps", 1e-3)))
+        # the row draws and the slot draws take their sample indices from a counter each, both from 0: the streams differ
+        self._sample_index = 0
+        self._slot_sample_index = 0
+        if self.prioritized is not None:
+            self.engine.selfplay_keep_priorities(True)
 
     @staticmethod
     def _search(policies, games_per_net: int, **kw) -> PopulationMCTS:
@@ -406,18 +425,47 @@ class PopulationSelfPlay:
             raise RuntimeError(f"{type(self).__name__}.nstep_targets needs the stored steps' rewards and ends: create it with n_step=...")
         self.engine.selfplay_nstep_targets(self.n_step if n_step is None else int(n_step), self.target_gamma if gamma is None else float(gamma))
 
-    def reanalyse(self, slots=None, n: int = 1, rng: Optional[np.random.Generator] = None) -> list:
+    def priorities(self, given=None) -> None:
+        """Compute the priority of every stored row (``Engine.selfplay_priorities`` with the ``alpha`` and ``eps`` given at
+        creation; asynchronous: one launch).  ``given`` None: from |kept search value - V_target|; else from ``given``, a float32
+        array with one entry >= 0 per stored row ordered like the ring ([size_steps, n_games]): a training loop's own TD errors."""
+        if self.prioritized is None:
+            raise RuntimeError(f"{type(self).__name__}.priorities needs a priority per stored row: create it with prioritized={{...}}")
+        self.engine.selfplay_priorities(self.prioritized["alpha"], self.prioritized["eps"], given)
+
+    def sample_order(self, n_order: int, given=None) -> np.ndarray:
+        """``n_order`` training rows per net drawn on the device in proportion to the rows' priorities, with replacement: int32
+        [K, n_order], what ``PopulationTrainer.train_epoch_ring(sp, order)`` takes.  The priorities are recomputed first
+        (``priorities(given)``); every call takes the next index of a counter that starts at 0.  The draw is biased towards large
+        priorities; the loss is not reweighted."""
+        self.priorities(given)
+        order = self.engine.selfplay_sample_rows(int(n_order), self._sample_index)
+        self._sample_index += 1
+        return order
+
+    def reanalyse(self, slots=None, n: int = 1, rng: Optional[np.random.Generator] = None, by: str = "uniform") -> list:
         """MuZero's Reanalyse on the device ring: search stored positions again with the CURRENT weights (pending uploads are
         applied first, as ``play`` does) and overwrite their rows' actions | counts | Q | V_target; observations, the live games
         and the ring's books stay as they are (asynchronous: launches only).  ``slots`` None: ``n`` stored slots (at most the
         ring's size) chosen uniformly without replacement by ``rng`` (default: this object's generator, seeded from the engine
         seed); a list of slots: each is reanalysed for every game; one ``[n_games]`` integer array: a single search in which game
         t re-searches its position in slot ``slots[t]``.  Every search takes the next index of a counter that starts at
-        ``REANALYSE_INDEX_BASE``.  Returns the slots used (the per-game array: a one-element list holding it)."""
+        ``REANALYSE_INDEX_BASE``.  Returns the slots used (the per-game array: a one-element list holding it).
+        ``by="priority"`` (with ``prioritized`` and ``slots`` None): one search in which game t re-searches the slot drawn for it
+        on the device in proportion to the priorities of its column (recomputed first); the draws take the next index of a second
+        counter that starts at 0.  ``by="uniform"`` is the rest of this description."""
+        if by not in ("uniform", "priority"):
+            raise ValueError(f"reanalyse: by must be 'uniform' or 'priority', not {by!r}")
         if not self.reanalysing:
             raise RuntimeError(f"{type(self).__name__}.reanalyse needs the stored positions' env states: create it with reanalyse=True")
         self.sync_weights()
-        if slots is None:
+        if by == "priority":
+            if slots is not None:
+                raise ValueError("reanalyse: by='priority' draws the slots itself")
+            self.priorities()
+            used = [self.engine.selfplay_sample_slots(self._slot_sample_index)] if self.engine.selfplay_ring()[0] else []
+            self._slot_sample_index += 1
+        elif slots is None:
             size = self.engine.selfplay_ring()[0]
             gen = self._reanalyse_rng if rng is None else rng
             used = [int(s) for s in gen.choice(size, size=min(int(n), size), replace=False)] if size else []

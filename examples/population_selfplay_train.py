@@ -32,6 +32,11 @@ where rows stay in the ring -- --replay-steps, or --trainer device-epoch -- and 
 plus the discounted search value after them, computed on the device from the transitions kept beside the ring (PopulationSelfPlay
 n_step=N; an episode's terminal step closes the window, a time limit and the newest stored step bootstrap from their own search value).
 
+--prioritized-alpha A [--prioritized-eps E], with --replay-steps and --n-step, replaces the uniform pick of training rows by a draw
+in proportion to (|search value - value target| + E)^A, made on the device from priorities kept beside the ring (PopulationSelfPlay
+prioritized=..., sample_order); with --reanalyse-slots N the reanalysed positions are drawn the same way, one per game and search.
+The draw is with replacement and biased; the loss is not reweighted (no importance-sampling weights).
+
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
 Seed k sets net k's initial weights (torch.manual_seed), and its own np.random.RandomState picks the training rows and the
@@ -119,6 +124,11 @@ def parse_args(argv=None):
     ap.add_argument("--n-step", type=int, default=None,
                     help="value targets are n-step returns over the stored steps (discounted with each net's search gamma) instead of "
                          "the search's root value; 0 keeps the root value (default: off, nothing is kept)")
+    ap.add_argument("--prioritized-alpha", type=float, default=None,
+                    help="draw the training rows (and with --reanalyse-slots the reanalysed positions) in proportion to "
+                         "(|search value - value target| + eps)^alpha on the device instead of uniformly; needs --replay-steps and "
+                         "--n-step (default: off, nothing is kept)")
+    ap.add_argument("--prioritized-eps", type=float, default=1e-3, help="the eps of --prioritized-alpha")
     a = ap.parse_args(argv)
     why = check_replay(a)
     if why:
@@ -179,6 +189,13 @@ def check_replay(a):
         return f"--replay-steps ({a.replay_steps}) must hold at least one iteration's steps (--steps-per-iter {a.steps_per_iter})"
     if a.replay_steps and not a.device.startswith("cuda"):
         return "--replay-steps trains from the device ring where it lies: it needs --device cuda"
+    if getattr(a, "prioritized_alpha", None) is not None:
+        if not a.replay_steps:
+            return "--prioritized-alpha draws from the rows kept in the FIFO ring: use it with --replay-steps R"
+        if getattr(a, "n_step", None) is None:
+            return "--prioritized-alpha needs --n-step N: the priority is |search value - n-step target|, and both are kept only then"
+        if not (a.prioritized_alpha >= 0.0 and a.prioritized_eps > 0.0):
+            return "--prioritized-alpha must be >= 0 and --prioritized-eps > 0"
     if a.reanalyse_slots and not (a.replay_steps or a.trainer == "device-epoch"):
         return ("--reanalyse-slots rewrites rows that stay in the device ring: use it with --replay-steps R (the FIFO ring) or with "
                 "--trainer device-epoch; the other modes copy the rows out and clear the ring every iteration")
@@ -197,6 +214,13 @@ def check_population_shape(a):
     return None
 
 
+def prioritized(a):
+    """PopulationSelfPlay's ``prioritized`` for --prioritized-alpha / --prioritized-eps (None: off)."""
+    if getattr(a, "prioritized_alpha", None) is None:
+        return None
+    return {"alpha": a.prioritized_alpha, "eps": getattr(a, "prioritized_eps", 1e-3)}
+
+
 def build_population(a):
     """One agent per seed (its initial weights drawn after torch.manual_seed(seed)) and the self-play engine of them all."""
     agents = []
@@ -210,8 +234,8 @@ def build_population(a):
                                 c_uct=m.c_uct, gamma=m.gamma, epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0),
                                 kappa=getattr(m, "kappa", 0.5), max_episode_length=a.max_episode_length,
                                 capacity_steps=getattr(a, "replay_steps", 0) or a.steps_per_iter, fifo=bool(getattr(a, "replay_steps", 0)),
-                                reanalyse=getattr(a, "reanalyse_slots", 0) > 0, n_step=getattr(a, "n_step", None), seed=a.engine_seed,
-                                device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0, **search_kwargs(a))
+                                reanalyse=getattr(a, "reanalyse_slots", 0) > 0, n_step=getattr(a, "n_step", None), prioritized=prioritized(a),
+                                seed=a.engine_seed, device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0, **search_kwargs(a))
     return agents, state_dim, sp
 
 
@@ -232,6 +256,21 @@ def train(a, log=print, on_rows=None, on_end=None):
                                     layernorm=a.layernorm and not a.wide, wide=a.wide and not a.layernorm,
                                     wide_layernorm=a.wide and a.layernorm)
     replay_steps, reanalyse_slots = getattr(a, "replay_steps", 0), getattr(a, "reanalyse_slots", 0)
+    by_priority = sp.prioritized is not None
+
+    def reanalyse():
+        if by_priority:   # one search per "slot": every game re-searches the position drawn for it
+            for _ in range(reanalyse_slots):
+                sp.reanalyse(by="priority")
+        else:
+            sp.reanalyse(n=reanalyse_slots)
+
+    def pick_rows(k, rng, n):
+        """Net k's training rows of this iteration: the device's prioritised draw, else the seed's own uniform pick."""
+        if prio_order is not None:
+            return prio_order[k].astype(np.int64)
+        return rng.choice(n, size=min(a.train_rows, n), replace=False)
+
     ring_view = None
     t0 = time.time()
     history = []
@@ -241,7 +280,7 @@ def train(a, log=print, on_rows=None, on_end=None):
             rows = None
             n_ring = sp.play_device(a.steps_per_iter)[0] * sp.games_per_net
             if reanalyse_slots:   # stored steps searched again with the weights as last trained: fresh targets, same observations
-                sp.reanalyse(n=reanalyse_slots)
+                reanalyse()
             sp.engine.sync()
         elif replay_steps:   # the FIFO ring: the newest replay_steps steps, every net's rows read where they lie
             if ring_view is None:
@@ -249,8 +288,9 @@ def train(a, log=print, on_rows=None, on_end=None):
                 ring_view = DeviceReplay(sp.engine, 1)
             size = sp.play_device(a.steps_per_iter)[0]
             if reanalyse_slots:
-                sp.reanalyse(n=reanalyse_slots)
+                reanalyse()
             rows = sp._split(ring_view.rows(), size)
+            n_ring = size * sp.games_per_net
         else:
             rows = sp.collect_device(a.steps_per_iter) if on_gpu else sp.collect(a.steps_per_iter)
         t2 = time.time()
@@ -261,25 +301,27 @@ def train(a, log=print, on_rows=None, on_end=None):
             else:
                 on_rows(it, rows)
         losses = []
+        # (net k's rows are numbered slot * T + game in the ring and in _split's copies alike)
+        prio_order = sp.sample_order(min(a.train_rows, n_ring)) if by_priority else None
         if rows is None:   # the other trainers' picks and shuffles from the same streams, composed into one order per net
             order = []
-            for rng in rngs:
-                pick = rng.choice(n_ring, size=min(a.train_rows, n_ring), replace=False)
+            for k, rng in enumerate(rngs):
+                pick = pick_rows(k, rng, n_ring)
                 order.append(pick[np.random.RandomState(int(rng.randint(2 ** 31 - 1))).permutation(len(pick))])
             infos = trainer.train_epoch_ring(sp, np.stack(order), batch_size=a.batch_size)
             if not replay_steps:
                 sp.engine.selfplay_clear()
             losses = [info["loss"] / max(1, len(order[0]) // a.batch_size) for info in infos]
         elif trainer is None:
-            for agent, rng, r in zip(agents, rngs, rows):
-                pick = rng.choice(r.shape[0], size=min(a.train_rows, r.shape[0]), replace=False)
+            for k, (agent, rng, r) in enumerate(zip(agents, rngs, rows)):
+                pick = pick_rows(k, rng, r.shape[0])
                 info = run.train_on_rows(agent, r[torch.from_numpy(pick).to(r.device)], state_dim, K, batch_size=a.batch_size,
                                          shuffle_seed=int(rng.randint(2 ** 31 - 1)))
                 losses.append(info["loss"] / max(1, len(pick) // a.batch_size))
         else:   # the same rows and shuffles, every net's minibatch step at once
             picked, seeds = [], []
-            for rng, r in zip(rngs, rows):
-                pick = rng.choice(r.shape[0], size=min(a.train_rows, r.shape[0]), replace=False)
+            for k, (rng, r) in enumerate(zip(rngs, rows)):
+                pick = pick_rows(k, rng, r.shape[0])
                 picked.append(r[torch.from_numpy(pick).to(r.device)])
                 seeds.append(int(rng.randint(2 ** 31 - 1)))
             infos = trainer.train_on_rows(picked, state_dim, K, batch_size=a.batch_size, shuffle_seeds=seeds)

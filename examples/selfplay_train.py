@@ -17,6 +17,11 @@ before each iteration's training and overwrites their targets (DeviceSelfPlay.re
 the discounted search value after them, computed on the device from the transitions kept beside the ring (DeviceSelfPlay n_step=N;
 an episode's terminal step closes the window, a time limit and the newest stored step bootstrap from their own search value).
 
+--prioritized-alpha A [--prioritized-eps E], with --replay-steps and --n-step, replaces the uniform pick of training rows by a draw in
+proportion to (|search value - value target| + E)^A, made on the device from priorities kept beside the ring (DeviceSelfPlay
+prioritized=..., sample_order); with --reanalyse-slots N the reanalysed positions are drawn the same way, one per game and search.  The
+draw is with replacement and biased; the loss is not reweighted (no importance-sampling weights).
+
 --eval-search-episodes E adds eval_search_return: after every iteration every game plays E whole episodes under MCTS with the greedy
 final-action rule, on the device in one call and on state of its own (DeviceSelfPlay.evaluate_search): the return of the agent as it
 acts, over the same start states at every iteration.
@@ -90,6 +95,11 @@ def parse_args(argv=None):
     ap.add_argument("--n-step", type=int, default=None,
                     help="value targets are n-step returns over the stored steps (discounted with the search's gamma) instead of the "
                          "search's root value; 0 keeps the root value (default: off, nothing is kept)")
+    ap.add_argument("--prioritized-alpha", type=float, default=None,
+                    help="draw the training rows (and with --reanalyse-slots the reanalysed positions) in proportion to "
+                         "(|search value - value target| + eps)^alpha on the device instead of uniformly; needs --replay-steps and "
+                         "--n-step (default: off, nothing is kept)")
+    ap.add_argument("--prioritized-eps", type=float, default=1e-3, help="the eps of --prioritized-alpha")
     a = ap.parse_args(argv)
     if a.eval_search_episodes < 0:
         ap.error("--eval-search-episodes must be >= 0")
@@ -104,6 +114,13 @@ def parse_args(argv=None):
     if a.reanalyse_slots and not a.replay_steps:
         ap.error("--reanalyse-slots rewrites rows that stay in the device ring: use it with --replay-steps R (the FIFO ring); without it "
                  "every iteration copies its rows out and clears the ring")
+    if a.prioritized_alpha is not None:
+        if not a.replay_steps:
+            ap.error("--prioritized-alpha draws from the rows kept in the FIFO ring: use it with --replay-steps R")
+        if a.n_step is None:
+            ap.error("--prioritized-alpha needs --n-step N: the priority is |search value - n-step target|, and both are kept only then")
+        if not (a.prioritized_alpha >= 0.0 and a.prioritized_eps > 0.0):
+            ap.error("--prioritized-alpha must be >= 0 and --prioritized-eps > 0")
     return a
 
 
@@ -117,10 +134,14 @@ def train(a, log=print):
     continuous = state_dim == 3
     m = agent.mcts
     replay_steps, reanalyse_slots = getattr(a, "replay_steps", 0), getattr(a, "reanalyse_slots", 0)
+    prioritized = None
+    if getattr(a, "prioritized_alpha", None) is not None:
+        prioritized = {"alpha": a.prioritized_alpha, "eps": getattr(a, "prioritized_eps", 1e-3)}
     sp = run.DeviceSelfPlay(agent.nn, game=a.game, n_games=a.games, n_rollouts=a.n_rollouts, c_uct=m.c_uct, gamma=m.gamma,
                             epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0), kappa=getattr(m, "kappa", 0.5),
                             max_episode_length=a.max_episode_length, capacity_steps=replay_steps or a.steps_per_iter, fifo=bool(replay_steps),
-                            reanalyse=reanalyse_slots > 0, n_step=getattr(a, "n_step", None), seed=a.seed, rank=rank,
+                            reanalyse=reanalyse_slots > 0, n_step=getattr(a, "n_step", None), prioritized=prioritized,
+                            seed=a.seed, rank=rank,
                             device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0)
     K = sp.engine.kmax if continuous else 2
     rng = np.random.RandomState(a.seed)
@@ -134,7 +155,10 @@ def train(a, log=print):
     for it in range(a.iters):
         if replay_steps:   # the FIFO ring: the newest replay_steps steps stay where they lie, all of them are this iteration's rows
             sp.play(a.steps_per_iter)
-            if reanalyse_slots:   # stored steps searched again with the weights as last trained: fresh targets, same observations
+            if reanalyse_slots and prioritized:   # one search per "slot": every game re-searches the position drawn for it
+                for _ in range(reanalyse_slots):
+                    sp.reanalyse(by="priority")
+            elif reanalyse_slots:   # stored steps searched again with the weights as last trained: fresh targets, same observations
                 sp.reanalyse(n=reanalyse_slots)
             rows = replay.rows()
         else:
@@ -144,7 +168,10 @@ def train(a, log=print):
             # and the world size are: the job as a whole plays a.games * world games)
             rows = D.gather_replay_rows(rows, counts=[rows.shape[0]] * world)
         info = {"loss": 0.0}
-        pick = rng.choice(rows.shape[0], size=min(a.train_rows, rows.shape[0]), replace=False)
+        if prioritized:   # (the ring's rows in slot order are the engine's own numbering slot * games + game)
+            pick = sp.sample_order(min(a.train_rows, rows.shape[0]))[0].astype(np.int64)
+        else:
+            pick = rng.choice(rows.shape[0], size=min(a.train_rows, rows.shape[0]), replace=False)
         if rank == 0:
             info = run.train_on_rows(agent, rows[torch.from_numpy(pick).to(rows.device)], state_dim, K, batch_size=a.batch_size, shuffle_seed=it)
         if world > 1:

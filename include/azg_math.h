@@ -305,6 +305,8 @@ AZG_HD float azg_u01(uint32_t x) {
 #define AZG_STREAM_ROOT 2u    /* synthetic root states (bench / self-play resets): counter (tree, episode, 0, stream) */
 #define AZG_STREAM_TIE 4u     /* AZG_TIE_RANDOM: v[0] picks among tied children: counter (tree, search, node_n << 16 ^ node record, stream) */
 #define AZG_STREAM_ACT 3u     /* self-play: final action sampled from the visit counts: counter (tree, step, 0, stream) */
+#define AZG_STREAM_SAMPLE 5u  /* prioritised row draws (azgym_priority.h): v[0], v[1] -> 64 bits: counter (net's first tree, sample index, draw, stream) */
+#define AZG_STREAM_SLOT 6u    /* prioritised slot draws: v[0], v[1] -> 64 bits: counter (tree, sample index, 0, stream) */
 
 /* fixed-seed reset state of game `tree`, episode `episode` (Pendulum theta~U(-pi,pi), theta_dot~U(-1,1);
  * CartPole ~U(-0.05,0.05)^4; MountainCar position~U(-0.6,-0.4), velocity 0: the envs' own reset laws).
