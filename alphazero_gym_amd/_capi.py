@@ -161,14 +161,16 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "population_selfplay_begin", "selfplay_keep_states", "selfplay_states", "selfplay_reanalyse",
                     "selfplay_keep_transitions", "selfplay_transitions", "selfplay_nstep_targets",
                     "selfplay_keep_priorities", "selfplay_priorities", "selfplay_priority_values", "selfplay_sample_rows",
-                    "selfplay_sample_slots",
+                    "selfplay_sample_slots", "selfplay_is_weights", "selfplay_is_weights_device", "selfplay_is_weight_values",
                     "policy_rollout", "policy_rollout_ex", "search_rollout",
                     "population_mlp_eval", "population_mlp_eval_device", "population_root_eval",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
                     "trainer_backward_step", "trainer_loss", "trainer_step", "trainer_read_d_raw", "trainer_epoch",
                     "trainer_backward_step_opt", "trainer_step_opt", "trainer_epoch_opt", "trainer_create_ex", "trainer_create_wide",
                     "trainer_create_wide_ex",
-                    "trainer_backward_step_nets", "trainer_loss_nets", "trainer_step_nets", "trainer_epoch_nets"]
+                    "trainer_backward_step_nets", "trainer_loss_nets", "trainer_step_nets", "trainer_epoch_nets",
+                    "trainer_loss_weighted", "trainer_loss_nets_weighted", "trainer_step_opt_weighted", "trainer_step_nets_weighted",
+                    "trainer_epoch_opt_weighted", "trainer_epoch_nets_weighted"]
 
 
 class AzgNetSearch(C.Structure):
@@ -330,6 +332,10 @@ def bind(lib, prefix):
         f["selfplay_priority_values"].argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t]
         f["selfplay_sample_rows"].argtypes = [vp, C.POINTER(AzgSampleConfig), C.POINTER(C.c_int32)]
         f["selfplay_sample_slots"].argtypes = [vp, C.c_uint32, C.POINTER(C.c_int32)]
+    if "selfplay_is_weights" in f:   # include/azgym_priority.h: the importance-sampling weights
+        f["selfplay_is_weights"].argtypes = [vp, C.c_float]
+        f["selfplay_is_weights_device"].argtypes = [vp, C.POINTER(C.c_void_p)]
+        f["selfplay_is_weight_values"].argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
     if "search_rollout" in f:   # include/azgym_search_rollout.h
         f["search_rollout"].argtypes = [vp, C.POINTER(AzgSearchRolloutConfig), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.POINTER(AzgSearchRolloutInfo)]
@@ -382,6 +388,13 @@ def bind(lib, prefix):
         f["trainer_loss_nets"].argtypes = f["trainer_loss"].argtypes
         f["trainer_step_nets"].argtypes = f["trainer_step_opt"].argtypes
         f["trainer_epoch_nets"].argtypes = f["trainer_epoch_opt"].argtypes
+    if "trainer_loss_weighted" in f:   # include/azgym_train_weighted.h: the namesake's prototype with `weights` added
+        def with_weights(name, at):
+            args = list(f[name].argtypes)
+            return args[:at] + [vp] + args[at:]
+        f["trainer_loss_weighted"].argtypes = f["trainer_loss_nets_weighted"].argtypes = with_weights("trainer_loss", 5)
+        f["trainer_step_opt_weighted"].argtypes = f["trainer_step_nets_weighted"].argtypes = with_weights("trainer_step_opt", 6)
+        f["trainer_epoch_opt_weighted"].argtypes = f["trainer_epoch_nets_weighted"].argtypes = with_weights("trainer_epoch_opt", 3)
     return f
 
 
@@ -1028,10 +1041,32 @@ def _selfplay_methods():
         self._check(self._optional("selfplay_sample_slots")(self._h, int(sample_index) & 0xFFFFFFFF, _ptr(slots, C.c_int32)))
         return slots
 
+    def selfplay_is_weights(self, beta):
+        """azg_selfplay_is_weights: the importance-sampling weight (q_min / q)^beta of every stored row, q_min the least priority of
+        the row's net, into a device array slot-aligned with the rows (asynchronous).  Needs selfplay_priorities since the last
+        step, clear or begin."""
+        self._check(self._optional("selfplay_is_weights")(self._h, float(beta)))
+
+    def selfplay_is_weights_device(self):
+        """azg_selfplay_is_weights_device: the device address of the weights [capacity_steps, n_trees] float32, for a trainer on the
+        same GPU.  Refused until selfplay_is_weights has run since the stored rows or their priorities last changed."""
+        ptr = C.c_void_p()
+        self._check(self._optional("selfplay_is_weights_device")(self._h, C.byref(ptr)))
+        return int(ptr.value)
+
+    def selfplay_is_weight_values(self):
+        """The stored rows' weights as the array holds them: float32 [steps*B], ordered like selfplay_rows."""
+        fn = self._optional("selfplay_is_weight_values")
+        w = np.empty(getattr(self, "_sp_cap", 0) * self.n_trees, np.float32)
+        n = fn(self._h, _ptr(w, C.c_float), w.shape[0])
+        if n < 0:
+            self._check(n)
+        return w[:n]
+
     for fn in (selfplay_begin, population_selfplay_begin, selfplay_ring, selfplay_rows_device, selfplay_step, selfplay_rows, selfplay_clear, selfplay_stats,
                selfplay_keep_states, selfplay_states, selfplay_reanalyse, selfplay_keep_transitions, selfplay_transitions,
                selfplay_nstep_targets, selfplay_keep_priorities, selfplay_priorities, selfplay_priority_values, selfplay_sample_rows,
-               selfplay_sample_slots):
+               selfplay_sample_slots, selfplay_is_weights, selfplay_is_weights_device, selfplay_is_weight_values):
         setattr(Engine, fn.__name__, fn)
 
 
@@ -1206,20 +1241,22 @@ class Trainer:
     def _backward_step(self, symbol, params, d_raw, n_rows, opt, grads):
         self._check(_require(self._f, symbol)(self._h, params or None, d_raw or None, int(n_rows), *opt, grads or None))
 
-    def _loss(self, symbol, raw, actions, counts, values, n_rows, n_actions, cfg, alpha, d_raw, losses):
-        self._check(_require(self._f, symbol)(self._h, raw or None, actions or None, counts or None, values or None, int(n_rows),
+    # ``weights``: () for the unweighted symbols, (address,) for the *_weighted ones, whose extra argument follows the row arrays.
+
+    def _loss(self, symbol, raw, actions, counts, values, n_rows, n_actions, cfg, alpha, d_raw, losses, weights=()):
+        self._check(_require(self._f, symbol)(self._h, raw or None, actions or None, counts or None, values or None, *weights, int(n_rows),
                                               int(n_actions), cfg, _ref(alpha), d_raw or None, losses or None))
 
-    def _step(self, symbol, params, obs, actions, counts, values, n_rows, n_actions, cfg, alpha, opt, grads, raw_out, losses):
+    def _step(self, symbol, params, obs, actions, counts, values, n_rows, n_actions, cfg, alpha, opt, grads, raw_out, losses, weights=()):
         self._check(_require(self._f, symbol)(self._h, params or None, obs or None, actions or None, counts or None, values or None,
-                                              int(n_rows), int(n_actions), cfg, _ref(alpha), *opt, grads or None, raw_out or None,
+                                              *weights, int(n_rows), int(n_actions), cfg, _ref(alpha), *opt, grads or None, raw_out or None,
                                               losses or None))
 
-    def _epoch(self, symbol, who, params, rows, order, batch_size, cfg, alpha, opt, loss_sums):
+    def _epoch(self, symbol, who, params, rows, order, batch_size, cfg, alpha, opt, loss_sums, weights=()):
         fn = _require(self._f, symbol)
         n_order, ptr = self._order(who, order)
         n_mb = C.c_int32(0)
-        self._check(fn(self._h, params or None, _ref(rows), ptr, n_order, int(batch_size), cfg, _ref(alpha), *opt, loss_sums or None,
+        self._check(fn(self._h, params or None, _ref(rows), *weights, ptr, n_order, int(batch_size), cfg, _ref(alpha), *opt, loss_sums or None,
                        C.byref(n_mb)))
         return n_mb.value
 
@@ -1302,6 +1339,45 @@ class Trainer:
         minibatches."""
         carr, oarr = self._entries("epoch_nets", cfgs, AzgLossCfg), self._entries("epoch_nets", opts, AzgOptim)
         return self._epoch("trainer_epoch_nets", "epoch_nets", params, rows, order, batch_size, carr, alpha, (oarr,), loss_sums)
+
+    # ---- weighted losses (include/azgym_train_weighted.h): the namesake with ``weights``, a device address of float32 ----
+
+    def loss_weighted(self, raw, actions, counts, values, weights, n_rows, n_actions, cfg, alpha, d_raw, losses):
+        """azg_trainer_loss_weighted: ``loss`` with a weight per row, weights [n_nets, n_rows], multiplied into the row's summands of
+        every loss and into its d_raw in float64; the reductions stay.  Weights of 1 give ``loss``'s bits."""
+        self._loss("trainer_loss_weighted", raw, actions, counts, values, n_rows, n_actions, _ref(cfg), alpha, d_raw, losses,
+                   (weights or None,))
+
+    def loss_nets_weighted(self, raw, actions, counts, values, weights, n_rows, n_actions, cfgs, alpha, d_raw, losses):
+        """azg_trainer_loss_nets_weighted: ``loss_nets`` with a weight per row."""
+        arr = self._entries("loss_nets_weighted", cfgs, AzgLossCfg)
+        self._loss("trainer_loss_nets_weighted", raw, actions, counts, values, n_rows, n_actions, arr, alpha, d_raw, losses,
+                   (weights or None,))
+
+    def step_opt_weighted(self, params, obs, actions, counts, values, weights, n_rows, n_actions, cfg, alpha, opt, grads, raw_out, losses):
+        """azg_trainer_step_opt_weighted: ``step_opt`` with a weight per row, weights [n_nets, n_rows]."""
+        self._step("trainer_step_opt_weighted", params, obs, actions, counts, values, n_rows, n_actions, _ref(cfg), alpha, (_ref(opt),),
+                   grads, raw_out, losses, (weights or None,))
+
+    def step_nets_weighted(self, params, obs, actions, counts, values, weights, n_rows, n_actions, cfgs, alpha, opts, grads, raw_out,
+                           losses):
+        """azg_trainer_step_nets_weighted: ``step_nets`` with a weight per row."""
+        carr, oarr = self._entries("step_nets_weighted", cfgs, AzgLossCfg), self._entries("step_nets_weighted", opts, AzgOptim)
+        self._step("trainer_step_nets_weighted", params, obs, actions, counts, values, n_rows, n_actions, carr, alpha, (oarr,), grads,
+                   raw_out, losses, (weights or None,))
+
+    def epoch_opt_weighted(self, params, rows, weights, order, batch_size, cfg, alpha, opt, loss_sums):
+        """azg_trainer_epoch_opt_weighted: ``epoch_opt`` with a weight per replay row.  ``weights`` is addressed like ``rows`` with a
+        row length of 1: [n_nets, rows_per_net] beside a plain rows array, [capacity_steps, n_trees] beside the self-play ring
+        (``Engine.selfplay_is_weights_device``)."""
+        return self._epoch("trainer_epoch_opt_weighted", "epoch_opt_weighted", params, rows, order, batch_size, _ref(cfg), alpha,
+                           (_ref(opt),), loss_sums, (weights or None,))
+
+    def epoch_nets_weighted(self, params, rows, weights, order, batch_size, cfgs, alpha, opts, loss_sums):
+        """azg_trainer_epoch_nets_weighted: ``epoch_nets`` with a weight per replay row."""
+        carr, oarr = self._entries("epoch_nets_weighted", cfgs, AzgLossCfg), self._entries("epoch_nets_weighted", opts, AzgOptim)
+        return self._epoch("trainer_epoch_nets_weighted", "epoch_nets_weighted", params, rows, order, batch_size, carr, alpha, (oarr,),
+                           loss_sums, (weights or None,))
 
     def read_d_raw(self, n_rows, d_raw):
         """azg_trainer_read_d_raw: the last ``step``'s d_raw [n_nets, n_rows, 1 + n_dist] into the caller's device array."""

@@ -119,8 +119,20 @@ def population_terms(policy, loss, raw, actions, counts, values) -> Dict[str, to
             "log_probs": log_probs.reshape(K, B, A)}
 
 
+def _weighted_terms(terms: Dict[str, torch.Tensor], weights: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """Every per-row summand times its row's weight ``weights`` [K, B] (an importance-sampling weight of prioritised replay): the
+    value's [K, B, 1] and the discrete head's entropy [K, B, A] carry the row's weight in every element."""
+    out = dict(terms)
+    for key in ("policy", "value", "entropy"):
+        if key in terms:
+            t = terms[key]
+            out[key] = t * weights.reshape(weights.shape + (1,) * (t.dim() - 2))
+    return out
+
+
 def population_loss(policy, loss, raw, actions, counts, values, log_alpha: Optional[torch.Tensor] = None,
-                    alpha_optimizer: Optional[torch.optim.Optimizer] = None) -> Dict[str, torch.Tensor]:
+                    alpha_optimizer: Optional[torch.optim.Optimizer] = None,
+                    weights: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """The K-axis form of ``DiscreteAgent._loss`` / ``ContinuousAgent._loss`` from the heads' raw outputs.
 
     ``policy`` / ``loss``: one of the K policies / loss objects (all nets share head kind, loss class and hyper-parameters);
@@ -128,9 +140,21 @@ def population_loss(policy, loss, raw, actions, counts, values, log_alpha: Optio
     ``log_alpha`` [K] holds every net's own learned temperature and ``alpha_optimizer`` (one Adam over that tensor: Adam is
     element-wise, so element k is net k's own Adam) takes the step ``A0CLossTuned.forward`` takes.
     Returns {key: [K] tensor} with the keys of ``Agent.update``'s dictionary; ``out["loss"].sum().backward()`` gives every net's
-    own ``d loss_k / d raw[k]`` (the nets are independent).  ``per_net`` turns it into K dictionaries of floats."""
+    own ``d loss_k / d raw[k]`` (the nets are independent).  ``per_net`` turns it into K dictionaries of floats.
+
+    ``weights`` [K, B] (None: unweighted, the code path as it always was): a weight per row multiplies every per-row summand of
+    every loss before the reduction, which stays what it is (``mean`` divides by the number of rows); ``alpha_loss`` becomes
+    mean(alpha * w * gap).  The truth of the weighted loss kernel (include/azgym_train_weighted.h); weights of 1 give the
+    unweighted bits."""
     K = raw.shape[0]
     terms = population_terms(policy, loss, raw, actions, counts, values)
+    if weights is not None:
+        if tuple(weights.shape) != tuple(raw.shape[:2]):
+            raise ValueError("population_loss: weights must be [K, B]")
+        if type(loss) is A0CLossTuned:
+            gap_w = weights.reshape(weights.shape + (1,) * (terms["entropy"].dim() - 2))
+            unweighted_entropy = terms["entropy"]
+        terms = _weighted_terms(terms, weights.to(raw.dtype))
     policy_loss = loss.policy_coeff * _reduce(terms["policy"], loss.reduction)
     value_loss = loss.value_coeff * _reduce(terms["value"], loss.reduction)
     if type(loss) is AlphaZeroLoss:
@@ -146,7 +170,10 @@ def population_loss(policy, loss, raw, actions, counts, values, log_alpha: Optio
     entropy_loss = alpha.detach() * _reduce(entropy, loss.reduction)
     total = policy_loss + entropy_loss + value_loss
     # A0CLossTuned._update_alpha for every net at once
-    gap = (entropy - loss.target_entropy).detach()
+    if weights is None:
+        gap = (entropy - loss.target_entropy).detach()
+    else:
+        gap = (gap_w.to(raw.dtype) * (unweighted_entropy - loss.target_entropy)).detach()
     alpha_loss = (alpha.reshape((K,) + (1,) * (gap.dim() - 1)) * gap).mean(dim=tuple(range(1, gap.dim())))
     if alpha_optimizer is not None:
         log_alpha.grad = None
@@ -450,10 +477,21 @@ class PopulationTrainer:
             x = torch.stack([f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)) for f in x])
         return x.to(self.device, dtype=torch.float32).contiguous()
 
-    def update(self, batches) -> List[Dict[str, float]]:
+    def _row_weights(self, who: str, weights, K: int, B: int) -> torch.Tensor:
+        """``weights`` as a contiguous float32 [K, B] tensor on the trainer's device."""
+        if not isinstance(weights, torch.Tensor):
+            weights = torch.as_tensor(np.asarray(weights, dtype=np.float32))
+        weights = weights.to(self.device, dtype=torch.float32).contiguous()
+        if tuple(weights.shape) != (K, B):
+            raise ValueError(f"PopulationTrainer.{who}: weights must be [K = {K}, {B}]")
+        return weights
+
+    def update(self, batches, weights=None) -> List[Dict[str, float]]:
         """One optimiser step of every net on its own minibatch.  ``batches``: K tuples (states, actions, counts, Qs, V_target), the
         argument of ``Agent.update``, with equal row counts -- or one such tuple of stacked [K, B, ...] tensors.  Returns what K
-        ``agent.update`` calls return."""
+        ``agent.update`` calls return.  ``weights``: a [K, B] tensor, one weight per minibatch row (importance-sampling weights of
+        prioritised rows), multiplied into the row's summands of every loss (``population_loss``; with ``losses="device"`` the
+        weighted loss kernel); None is the unweighted step."""
         K = len(self.agents)
         if isinstance(batches, (list, tuple)) and len(batches) == 5 and isinstance(batches[0], torch.Tensor) and batches[0].dim() == 3:
             states, actions, counts, _, v_target = batches
@@ -471,13 +509,19 @@ class PopulationTrainer:
         states = states.reshape(K, B, -1)
         raw = torch.empty((K, B, self.trainer.n_raw), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device)
+        if weights is not None:
+            weights = self._row_weights("update", weights, K, B)
         if self.losses == "device":
-            return self._update_device(states, actions, counts, values, raw, stream)
+            return self._update_device(states, actions, counts, values, raw, stream, weights)
         stream.synchronize()
         self.trainer.forward(self.flat.data_ptr(), states.data_ptr(), B, raw.data_ptr())
         self.last_raw = raw
         raw.requires_grad_(True)
-        losses = population_loss(self.policy, self.loss, raw, actions, counts, values, self.log_alpha, self.alpha_optimizer)
+        if weights is None:
+            losses = population_loss(self.policy, self.loss, raw, actions, counts, values, self.log_alpha, self.alpha_optimizer)
+        else:
+            losses = population_loss(self.policy, self.loss, raw, actions, counts, values, self.log_alpha, self.alpha_optimizer,
+                                     weights=weights)
         losses["loss"].sum().backward()
         d_raw = self._last_d_raw = raw.grad.contiguous()
         out = per_net(losses)   # (the copy to the host also completes d_raw)
@@ -487,10 +531,19 @@ class PopulationTrainer:
         self._call("backward_step", (self.flat.data_ptr(), d_raw.data_ptr(), B), (grads,))
         return out
 
-    def _call(self, family: str, head: tuple, tail: tuple):
+    def _call(self, family: str, head: tuple, tail: tuple, weighted: bool = False):
         """The trainer's ``family`` call in this trainer's form: ``head``, the optimiser's arguments, ``tail``.  Counts the steps it
-        took (an epoch returns their number)."""
-        n_steps = getattr(self.trainer, family + self._form.suffix)(*head, *self._form.opt_args(), *tail)
+        took (an epoch returns their number).  ``weighted``: the ``*_weighted`` method of the form (``head`` carries the weights);
+        the azg_rmsprop family has none, and its trainer calls ``*_opt_weighted`` with the same RMSprop and no clip: the same bits."""
+        if weighted:
+            suffix, opt_args = self._form.suffix, self._form.opt_args()
+            if not suffix:
+                o = self.opt
+                suffix, opt_args = "_opt", (_capi.optim("rmsprop", o.lr, self.square_avg.data_ptr(), eps=o.eps,
+                                                        weight_decay=o.weight_decay, alpha=o.alpha),)
+            n_steps = getattr(self.trainer, family + suffix + "_weighted")(*head, *opt_args, *tail)
+        else:
+            n_steps = getattr(self.trainer, family + self._form.suffix)(*head, *self._form.opt_args(), *tail)
         if self._form.counts_steps:
             self.opt_step += 1 if n_steps is None else n_steps
         return n_steps
@@ -570,7 +623,7 @@ class PopulationTrainer:
         """azg_optim of the next step (``optimizers="agents"``): the agents' settings, the trainer's state tensors and step count."""
         return self._azg_optim(self._opt_settings, self.grad_clip)
 
-    def _update_device(self, states, actions, counts, values, raw, stream) -> List[Dict[str, float]]:
+    def _update_device(self, states, actions, counts, values, raw, stream, weights=None) -> List[Dict[str, float]]:
         """``update`` with the losses on the device: one native call (three launches), one copy of losses[K, 5] to the host."""
         K, B = raw.shape[0], raw.shape[1]
         actions, counts = actions.reshape(K, B, -1), counts.reshape(K, B, -1)
@@ -580,8 +633,10 @@ class PopulationTrainer:
                                   self.alpha_exp_avg_sq.data_ptr()) if tuned else None
         stream.synchronize()
         grads = self.grads.data_ptr() if self.grads is not None else None
-        self._call("step", (self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), B,
-                              actions.shape[2], self._form.cfg(), state), (grads, raw.data_ptr(), table.data_ptr()))
+        w = () if weights is None else (weights.data_ptr(),)
+        self._call("step", (self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), *w, B,
+                              actions.shape[2], self._form.cfg(), state), (grads, raw.data_ptr(), table.data_ptr()),
+                   weighted=weights is not None)
         if tuned:
             self.alpha_step += 1
         self.last_raw, self._last_d_raw = raw, None
@@ -590,15 +645,18 @@ class PopulationTrainer:
         return [{key: row[i] for key, i in slots} for row in rows]
 
     def train_on_rows(self, rows_per_net, state_dim: int, K: int, batch_size: int = 32,
-                      shuffle_seeds: Optional[Sequence[int]] = None) -> List[Dict[str, float]]:
+                      shuffle_seeds: Optional[Sequence[int]] = None, weights=None) -> List[Dict[str, float]]:
         """``run.train_on_rows`` for every net at once: one epoch of minibatch updates over ``rows_per_net`` (K tensors [n, row] with
         the same n, or one [K, n, row] tensor; row = obs | actions[K] | counts[K] | Q[K] | V), net k's rows shuffled with
-        ``shuffle_seeds[k]``; the last minibatch absorbs the remainder.  Returns per net the per-key sums."""
+        ``shuffle_seeds[k]``; the last minibatch absorbs the remainder.  Returns per net the per-key sums.  ``weights``: a [K, n]
+        tensor, one weight per row, gathered with every minibatch and passed to ``update`` (None: unweighted)."""
         rows = rows_per_net if isinstance(rows_per_net, torch.Tensor) else torch.stack(list(rows_per_net))
         rows = rows.to(self.device, dtype=torch.float32)
         N, n = rows.shape[0], rows.shape[1]
         if N != len(self.agents):
             raise ValueError("PopulationTrainer.train_on_rows: one block of rows per net")
+        if weights is not None:
+            weights = self._row_weights("train_on_rows", weights, N, n)
         seeds = [0] * N if shuffle_seeds is None else list(shuffle_seeds)
         order = torch.from_numpy(np.stack([np.random.RandomState(int(s)).permutation(n) for s in seeds])).to(self.device)
         net = torch.arange(N, device=self.device)[:, None]
@@ -607,16 +665,18 @@ class PopulationTrainer:
         while i < n:
             j = n if i + 2 * batch_size > n else i + batch_size
             b = rows[net, order[:, i:j]]
-            infos = self.update((b[..., :state_dim], b[..., state_dim:state_dim + K], b[..., state_dim + K:state_dim + 2 * K],
-                                 b[..., state_dim + 2 * K:state_dim + 3 * K], b[..., -1]))
+            batch = (b[..., :state_dim], b[..., state_dim:state_dim + K], b[..., state_dim + K:state_dim + 2 * K],
+                     b[..., state_dim + 2 * K:state_dim + 3 * K], b[..., -1])
+            infos = self.update(batch) if weights is None else self.update(batch, weights=weights[net, order[:, i:j]])
             for s, info in zip(sums, infos):
                 for key, val in info.items():
                     s[key] = s.get(key, 0.0) + val
             i = j
         return sums
 
-    def _epoch(self, who: str, where, order: np.ndarray, batch_size: int) -> List[Dict[str, float]]:
-        """azg_trainer_epoch on rows described by ``where`` (``_capi.epoch_rows``), their producers complete; the per-net sums."""
+    def _epoch(self, who: str, where, order: np.ndarray, batch_size: int, weights: Optional[int] = None) -> List[Dict[str, float]]:
+        """azg_trainer_epoch on rows described by ``where`` (``_capi.epoch_rows``), their producers complete; the per-net sums.
+        ``weights``: the device address of a float32 array addressed like the rows (None: the unweighted epoch)."""
         K = len(self.agents)
         bounds = minibatch_bounds(order.shape[1], int(batch_size))
         if not bounds or max(j - i for i, j in bounds) > self.max_batch:
@@ -626,7 +686,9 @@ class PopulationTrainer:
         state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
                                   self.alpha_exp_avg_sq.data_ptr()) if tuned else None
         torch.cuda.current_stream(self.device).synchronize()
-        n_steps = self._call("epoch", (self.flat.data_ptr(), where, order, int(batch_size), self._form.cfg(), state), (sums.data_ptr(),))
+        w = () if weights is None else (weights,)
+        n_steps = self._call("epoch", (self.flat.data_ptr(), where, *w, order, int(batch_size), self._form.cfg(), state),
+                             (sums.data_ptr(),), weighted=weights is not None)
         assert n_steps == len(bounds)
         if tuned:
             self.alpha_step += n_steps
@@ -636,11 +698,12 @@ class PopulationTrainer:
         return [{key: row[i] for key, i in slots} for row in table]
 
     def train_epoch(self, rows_per_net, state_dim: int, K: int, batch_size: int = 32,
-                    shuffle_seeds: Optional[Sequence[int]] = None) -> List[Dict[str, float]]:
+                    shuffle_seeds: Optional[Sequence[int]] = None, weights=None) -> List[Dict[str, float]]:
         """``train_on_rows`` as one native call (``azg_trainer_epoch``): the same arguments, minibatches, arithmetic and return
         value, bit for bit, with one synchronisation for the whole epoch.  The permutations are built on the host as there; the
         minibatches are gathered from ``rows_per_net`` on the device (a [K, n, row] float32 tensor on the trainer's GPU is read in
-        place).  Needs ``losses="device"``; ``grads`` (``keep_grads``) is not written."""
+        place).  Needs ``losses="device"``; ``grads`` (``keep_grads``) is not written.  ``weights``: a [K, n] float32 tensor, one
+        weight per row, gathered with the row (azg_trainer_epoch_opt_weighted); None is the unweighted epoch."""
         _need_device_losses(self.losses, "train_epoch")
         rows = rows_per_net if isinstance(rows_per_net, torch.Tensor) else torch.stack(list(rows_per_net))
         rows = rows.to(self.device, dtype=torch.float32).contiguous()
@@ -651,14 +714,27 @@ class PopulationTrainer:
             raise ValueError("PopulationTrainer.train_epoch: rows must be obs[state_dim] | actions[K] | counts[K] | Q[K] | V")
         seeds = [0] * N if shuffle_seeds is None else list(shuffle_seeds)
         order = np.stack([np.random.RandomState(int(s)).permutation(n) for s in seeds]).astype(np.int32)
-        return self._epoch("train_epoch", _capi.epoch_rows(rows.data_ptr(), state_dim, K, n), order, batch_size)
+        if weights is not None:
+            weights = self._row_weights("train_epoch", weights, N, n)
+        return self._epoch("train_epoch", _capi.epoch_rows(rows.data_ptr(), state_dim, K, n), order, batch_size,
+                           None if weights is None else weights.data_ptr())
 
-    def train_epoch_ring(self, selfplay, order, batch_size: int = 32) -> List[Dict[str, float]]:
+    def train_epoch_ring(self, selfplay, order, batch_size: int = 32, weights=None) -> List[Dict[str, float]]:
         """One epoch straight from a ``PopulationSelfPlay`` / ``DeviceSelfPlay`` engine's replay ring, with no copy of the rows and
         no index tensors on the device.  ``order``: int array [K, n_order]; order[k] numbers net k's rows of the ring as
         ``PopulationSelfPlay._split`` orders them (row i = stored step i // T, game i % T of the net's T games) -- the caller's pick
-        and shuffle composed.  The engine's stream is synchronised first (``azg_sync``); the ring is neither cleared nor changed."""
+        and shuffle composed.  The engine's stream is synchronised first (``azg_sync``); the ring is neither cleared nor changed.
+
+        ``weights``: "priority" trains with the engine's importance-sampling weights (``PopulationSelfPlay.is_weights`` must have run
+        since the last ``priorities``; the engine's refusal surfaces as it is); a [capacity_steps, n_games] float32 tensor on the
+        trainer's GPU gives a weight per ring slot and game; None runs the unweighted calls."""
         _need_device_losses(self.losses, "train_epoch_ring")
+        if isinstance(weights, str):
+            if weights != "priority":
+                raise ValueError('PopulationTrainer.train_epoch_ring: weights must be "priority", a tensor or None')
+            if getattr(selfplay, "prioritized", None) is None:
+                raise ValueError('PopulationTrainer.train_epoch_ring: weights="priority" needs a self-play engine built with '
+                                 "prioritized=")
         engine = selfplay.engine
         if int(engine.cfg.device_id) != (self.device.index or 0):
             raise ValueError("PopulationTrainer.train_epoch_ring: the ring lies on another GPU than the trainer's nets")
@@ -677,8 +753,17 @@ class PopulationTrainer:
         if row_len != state_dim + 3 * A + 1:
             raise ValueError("PopulationTrainer.train_epoch_ring: unexpected replay row length")
         where = _capi.epoch_rows(ptr, state_dim, A, n, ring_trees=selfplay.n_games, games_per_net=T)
+        w_ptr = None
+        if isinstance(weights, str):
+            w_ptr = engine.selfplay_is_weights_device()
+        elif weights is not None:
+            if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.device != self.device or \
+                    not weights.is_contiguous() or tuple(weights.shape) != (int(selfplay.capacity), int(selfplay.n_games)):
+                raise ValueError("PopulationTrainer.train_epoch_ring: weights must be a contiguous float32 tensor "
+                                 "[capacity_steps, n_games] on the trainer's GPU")
+            w_ptr = weights.data_ptr()
         engine.sync()
-        return self._epoch("train_epoch_ring", where, order.astype(np.int32), batch_size)
+        return self._epoch("train_epoch_ring", where, order.astype(np.int32), batch_size, w_ptr)
 
     def export_alpha(self) -> None:
         """Write every net's learned temperature and its Adam state (step, exp_avg, exp_avg_sq) back into its agent's loss object,

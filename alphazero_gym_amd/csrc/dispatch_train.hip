@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/azgym_train.h"
+#include "../../include/azgym_train_weighted.h"
 #include "hip_host.h"
 #include "train.cuh"
 #include "train_wide_host.h"
@@ -35,11 +36,13 @@ struct azg_trainer {
     // the loss kernel's: the rows' terms [n_nets][3][max_batch] (float64), and azg_trainer_step's raw and d_raw [n_nets][max_batch][NO]
     // (allocated by the first call that needs them)
     double* loss_rows = nullptr;
+    double* loss_rows_w = nullptr;   // the weighted loss kernels' own: [n_nets][4][max_batch], allocated by the first weighted call
     float* raw_buf = nullptr;
     float* d_raw_buf = nullptr;
     // azg_trainer_epoch's, grown on demand: the uploaded order [n_nets][n_order], the minibatch staging arrays (obs [n_nets][B][in_dim] |
     // actions | counts [n_nets][B][A] | values [n_nets][B], laid out for max_batch rows) and the loss table [n_minibatches][n_nets][5]
     DeviceBuffer order_buf, stage_buf, loss_table;
+    DeviceBuffer stage_w;        // a weighted epoch's staged weights [n_nets][max_batch]
     // the *_nets entry points': the launch-ready settings of every (minibatch, net), [M][n_nets] TrainOptD | [M][n_nets] LossDims (a
     // part the call has no entries for is empty), filled on the host for the whole call and uploaded in one copy; grown on demand
     std::vector<unsigned char> nets_host;
@@ -218,6 +221,13 @@ int azg_trainer_create_wide_ex(int32_t device_id, const azg_mlp_desc* desc, int3
 }  // extern "C"
 
 // ---- what a call launches ----
+
+// The weights argument of a call: `asked` for the *_weighted entry points (whose NULL is a refusal), w the caller's device array.
+struct RowWeights {
+    bool asked = false;
+    const float* w = nullptr;
+};
+static const RowWeights kNoWeights{};
 
 enum class OptForm { fused, deferred, table };
 
@@ -467,6 +477,12 @@ static int upload_nets(azg_trainer* t, const char* who, const TrainPlan& plan) {
     return AZG_OK;
 }
 
+// the loss kernels' float64 rows: the unweighted path's three columns, or the weighted path's four in an array of its own
+static int ensure_loss_rows(azg_trainer* t, const RowWeights& wt) {
+    if (wt.asked) return ensure(t, t->loss_rows_w, (size_t)t->n_nets * 4 * t->max_batch);
+    return ensure(t, t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch);
+}
+
 static void launch_forward(azg_trainer* t, const float* params, const float* obs, int n_rows, float* raw) {
     if (t->net.wide) { tw_launch_forward(t->net, t->stream, t->n_nets, params, obs, n_rows, raw, t->scratch); return; }
     const dim3 grid((n_rows + 15) / 16, t->n_nets);
@@ -475,13 +491,25 @@ static void launch_forward(azg_trainer* t, const float* params, const float* obs
 }
 
 // minibatch m's losses: with the plan's LossDims, or every net with its own entry of the table
+// (weights: [n_nets][rows] or NULL; the weighted kernels keep their rows' terms in loss_rows_w)
 static void launch_loss(azg_trainer* t, const TrainPlan& plan, int m, const float* raw, const float* actions, const float* counts,
-                        const float* values, float* d_raw, float* losses) {
+                        const float* values, const float* weights, float* d_raw, float* losses) {
     const Minibatch& mb = plan.mb[m];
     const bool tuned = mb.c.kind == AZG_LOSS_A0C_TUNED;
     float* log_alpha = tuned ? plan.alpha->log_alpha : nullptr;
     float* exp_avg = tuned ? plan.alpha->exp_avg : nullptr;
     float* exp_avg_sq = tuned ? plan.alpha->exp_avg_sq : nullptr;
+    if (weights) {
+        if (plan.form == OptForm::table) {
+            const LossDims* table = reinterpret_cast<const LossDims*>((const unsigned char*)t->nets_dev.p + plan.loss_off) + (size_t)m * t->n_nets;
+            hipLaunchKernelGGL(train_loss_nets_weighted_kernel, dim3(t->n_nets), dim3(TR_LOSS_THREADS), 0, t->stream, table, raw, actions, counts,
+                               values, weights, mb.rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, t->loss_rows_w, t->max_batch);
+        } else {
+            hipLaunchKernelGGL(train_loss_weighted_kernel, dim3(t->n_nets), dim3(TR_LOSS_THREADS), 0, t->stream, mb.c, raw, actions, counts,
+                               values, weights, mb.rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, t->loss_rows_w, t->max_batch);
+        }
+        return;
+    }
     if (plan.form == OptForm::table) {
         const LossDims* table = reinterpret_cast<const LossDims*>((const unsigned char*)t->nets_dev.p + plan.loss_off) + (size_t)m * t->n_nets;
         hipLaunchKernelGGL(train_loss_nets_kernel, dim3(t->n_nets), dim3(TR_LOSS_THREADS), 0, t->stream, table, raw, actions, counts, values,
@@ -525,9 +553,9 @@ static void launch_backward(azg_trainer* t, const TrainPlan& plan, int m, float*
 
 // one minibatch: forward, losses (d_raw to d_raw_buf), backward and step
 static void launch_minibatch(azg_trainer* t, const TrainPlan& plan, int m, float* params, const float* obs, const float* actions,
-                             const float* counts, const float* values, float* raw, float* grads, float* losses) {
+                             const float* counts, const float* values, const float* weights, float* raw, float* grads, float* losses) {
     launch_forward(t, params, obs, plan.mb[m].rows, raw);
-    launch_loss(t, plan, m, raw, actions, counts, values, t->d_raw_buf, losses);
+    launch_loss(t, plan, m, raw, actions, counts, values, weights, t->d_raw_buf, losses);
     launch_backward(t, plan, m, params, t->d_raw_buf, grads);
 }
 
@@ -557,28 +585,29 @@ static int backward_step_impl(azg_trainer* t, const char* who, OptForm form, flo
 }
 
 static int loss_impl(azg_trainer* t, const char* who, OptForm form, const float* raw, const float* actions, const float* counts,
-                     const float* values, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* cfg, const azg_alpha_state* alpha_state,
-                     float* d_raw, float* losses) {
+                     const float* values, const RowWeights& wt, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* cfg,
+                     const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
     if (!t) return AZG_E_INVALID;
-    if (!raw || !actions || !counts || !values || !d_raw || !losses) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
+    if (!raw || !actions || !counts || !values || !d_raw || !losses || (wt.asked && !wt.w))
+        return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
     TrainPlan plan(form, n_rows);
     plan.alpha = alpha_state;
     if (int rc = check_loss(t, who, n_rows, n_actions, cfg, alpha_state, &plan.mb[0].c)) return rc;
     if (form == OptForm::table) { if (int rc = plan_nets(t, who, nullptr, nullptr, cfg, false, n_actions, &plan)) return rc; }
     DeviceScope scope(t->device_id);
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
-    if (int rc = ensure(t, t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch)) return rc;
+    if (int rc = ensure_loss_rows(t, wt)) return rc;
     if (int rc = upload_nets(t, who, plan)) return rc;
-    launch_loss(t, plan, 0, raw, actions, counts, values, d_raw, losses);
+    launch_loss(t, plan, 0, raw, actions, counts, values, wt.w, d_raw, losses);
     return finish(t, who);
 }
 
 static int step_impl(azg_trainer* t, const char* who, OptForm form, float* params, const float* obs, const float* actions,
-                     const float* counts, const float* values, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg,
-                     const azg_alpha_state* alpha_state, const azg_rmsprop* rms, float* square_avg, const azg_optim* opt, float* grads,
-                     float* raw_out, float* losses) {
+                     const float* counts, const float* values, const RowWeights& wt, int32_t n_rows, int32_t n_actions,
+                     const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_rmsprop* rms, float* square_avg,
+                     const azg_optim* opt, float* grads, float* raw_out, float* losses) {
     if (!t) return AZG_E_INVALID;
-    if (!actions || !counts || !values || !losses) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
+    if (!actions || !counts || !values || !losses || (wt.asked && !wt.w)) return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
     if (int rc = check_forward(t, who, params, obs, n_rows)) return rc;
     TrainPlan plan(form, n_rows);
     plan.alpha = alpha_state;
@@ -588,24 +617,24 @@ static int step_impl(azg_trainer* t, const char* who, OptForm form, float* param
     DeviceScope scope(t->device_id);
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
     const size_t per = (size_t)t->n_nets * t->max_batch * t->net.NO;
-    if (int rc = ensure(t, t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch)) return rc;
+    if (int rc = ensure_loss_rows(t, wt)) return rc;
     if (int rc = ensure(t, t->d_raw_buf, per)) return rc;
     if (!raw_out) { if (int rc = ensure(t, t->raw_buf, per)) return rc; }
     if (int rc = upload_nets(t, who, plan)) return rc;
     t->fwd_rows = 0;
     t->step_rows = 0;
-    launch_minibatch(t, plan, 0, params, obs, actions, counts, values, raw_out ? raw_out : t->raw_buf, grads, losses);
+    launch_minibatch(t, plan, 0, params, obs, actions, counts, values, wt.w, raw_out ? raw_out : t->raw_buf, grads, losses);
     if (int rc = finish(t, who)) return rc;
     t->step_rows = n_rows;
     return AZG_OK;
 }
 
-static int epoch_impl(azg_trainer* t, const char* who, OptForm form, float* params, const azg_epoch_rows* rows, const int32_t* order,
-                      int32_t n_order, int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
+static int epoch_impl(azg_trainer* t, const char* who, OptForm form, float* params, const azg_epoch_rows* rows, const RowWeights& wt,
+                      const int32_t* order, int32_t n_order, int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
                       const azg_rmsprop* rms, float* square_avg, const azg_optim* opt, double* loss_sums, int32_t* n_minibatches) {
     if (!t) return AZG_E_INVALID;
     const std::string w(who);
-    if (!params || !rows || !order || !loss_cfg || !(opt || (rms && square_avg)) || !loss_sums || !n_minibatches)
+    if (!params || !rows || !order || !loss_cfg || !(opt || (rms && square_avg)) || !loss_sums || !n_minibatches || (wt.asked && !wt.w))
         return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
     if (rows->struct_size != (int32_t)sizeof(azg_epoch_rows)) return tfail(t, AZG_E_INVALID, w + ": azg_epoch_rows.struct_size mismatch");
     if (!rows->rows) return tfail(t, AZG_E_INVALID, w + ": NULL pointer in azg_epoch_rows");
@@ -649,7 +678,8 @@ static int epoch_impl(azg_trainer* t, const char* who, OptForm form, float* para
     DeviceScope scope(t->device_id);
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
     const size_t mb = (size_t)t->max_batch, per = K * mb * t->net.NO, in_dim = (size_t)t->net.in_dim;
-    if (int rc = ensure(t, t->loss_rows, K * 3 * mb)) return rc;
+    if (int rc = ensure_loss_rows(t, wt)) return rc;
+    if (wt.asked) { if (int rc = grow(t, t->stage_w, K * mb * sizeof(float))) return rc; }
     if (int rc = ensure(t, t->d_raw_buf, per)) return rc;
     if (int rc = ensure(t, t->raw_buf, per)) return rc;
     if (int rc = grow(t, t->order_buf, K * (size_t)n_order * sizeof(int32_t))) return rc;
@@ -661,6 +691,7 @@ static int epoch_impl(azg_trainer* t, const char* who, OptForm form, float* para
     float* actions = obs + K * mb * in_dim;
     float* counts = actions + K * mb * (size_t)A;
     float* values = counts + K * mb * (size_t)A;
+    float* staged_w = wt.asked ? (float*)t->stage_w.p : nullptr;
     GatherDims g{};
     g.row_len = rows->row_len; g.state_dim = rows->state_dim; g.A = A; g.group = rows->group; g.n_order = n_order;
     g.group_stride = rows->group_stride; g.net_stride = rows->net_stride;
@@ -671,9 +702,15 @@ static int epoch_impl(azg_trainer* t, const char* who, OptForm form, float* para
     if (up != hipSuccess) return tfail(t, AZG_E_DEVICE, w + ": " + hipGetErrorString(up));
     for (int m = 0; m < M; ++m) {
         const int B = plan.mb[m].rows;
-        hipLaunchKernelGGL(train_gather_kernel, dim3((B + TR_GATHER_THREADS / 64 - 1) / (TR_GATHER_THREADS / 64), t->n_nets),
-                           dim3(TR_GATHER_THREADS), 0, t->stream, g, rows->rows, order_dev, plan.mb[m].first, B, obs, actions, counts, values);
-        launch_minibatch(t, plan, m, params, obs, actions, counts, values, t->raw_buf, nullptr, loss_table + (size_t)m * K * AZG_LOSS_SLOTS);
+        const dim3 ggrid((B + TR_GATHER_THREADS / 64 - 1) / (TR_GATHER_THREADS / 64), t->n_nets);
+        if (wt.asked)
+            hipLaunchKernelGGL(train_gather_weighted_kernel, ggrid, dim3(TR_GATHER_THREADS), 0, t->stream, g, rows->rows, wt.w, order_dev,
+                               plan.mb[m].first, B, obs, actions, counts, values, staged_w);
+        else
+            hipLaunchKernelGGL(train_gather_kernel, ggrid, dim3(TR_GATHER_THREADS), 0, t->stream, g, rows->rows, order_dev, plan.mb[m].first, B,
+                               obs, actions, counts, values);
+        launch_minibatch(t, plan, m, params, obs, actions, counts, values, staged_w, t->raw_buf, nullptr,
+                         loss_table + (size_t)m * K * AZG_LOSS_SLOTS);
     }
     const int n_sums = t->n_nets * AZG_LOSS_SLOTS;
     hipLaunchKernelGGL(train_loss_sum_kernel, dim3((n_sums + 63) / 64), dim3(64), 0, t->stream, loss_table, M, n_sums, loss_sums);
@@ -713,54 +750,100 @@ int azg_trainer_backward_step_nets(azg_trainer* t, float* params, const float* d
 
 int azg_trainer_loss(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values, int32_t n_rows,
                      int32_t n_actions, const azg_loss_cfg* cfg, const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
-    return loss_impl(t, "azg_trainer_loss", OptForm::fused, raw, actions, counts, values, n_rows, n_actions, cfg, alpha_state, d_raw, losses);
+    return loss_impl(t, "azg_trainer_loss", OptForm::fused, raw, actions, counts, values, kNoWeights, n_rows, n_actions, cfg, alpha_state, d_raw, losses);
 }
 
 int azg_trainer_loss_nets(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values, int32_t n_rows,
                           int32_t n_actions, const azg_loss_cfg* cfgs, const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
-    return loss_impl(t, "azg_trainer_loss_nets", OptForm::table, raw, actions, counts, values, n_rows, n_actions, cfgs, alpha_state, d_raw, losses);
+    return loss_impl(t, "azg_trainer_loss_nets", OptForm::table, raw, actions, counts, values, kNoWeights, n_rows, n_actions, cfgs, alpha_state, d_raw, losses);
 }
 
 int azg_trainer_step(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
                      int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
                      const azg_rmsprop* opt, float* square_avg, float* grads, float* raw_out, float* losses) {
-    return step_impl(t, "azg_trainer_step", OptForm::fused, params, obs, actions, counts, values, n_rows, n_actions, loss_cfg, alpha_state,
+    return step_impl(t, "azg_trainer_step", OptForm::fused, params, obs, actions, counts, values, kNoWeights, n_rows, n_actions, loss_cfg, alpha_state,
                      opt, square_avg, nullptr, grads, raw_out, losses);
 }
 
 int azg_trainer_step_opt(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
                          int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
                          const azg_optim* opt, float* grads, float* raw_out, float* losses) {
-    return step_impl(t, "azg_trainer_step_opt", OptForm::fused, params, obs, actions, counts, values, n_rows, n_actions, loss_cfg, alpha_state,
+    return step_impl(t, "azg_trainer_step_opt", OptForm::fused, params, obs, actions, counts, values, kNoWeights, n_rows, n_actions, loss_cfg, alpha_state,
                      nullptr, nullptr, opt, grads, raw_out, losses);
 }
 
 int azg_trainer_step_nets(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts, const float* values,
                           int32_t n_rows, int32_t n_actions, const azg_loss_cfg* loss_cfgs, const azg_alpha_state* alpha_state,
                           const azg_optim* opts, float* grads, float* raw_out, float* losses) {
-    return step_impl(t, "azg_trainer_step_nets", OptForm::table, params, obs, actions, counts, values, n_rows, n_actions, loss_cfgs,
+    return step_impl(t, "azg_trainer_step_nets", OptForm::table, params, obs, actions, counts, values, kNoWeights, n_rows, n_actions, loss_cfgs,
                      alpha_state, nullptr, nullptr, opts, grads, raw_out, losses);
 }
 
 int azg_trainer_epoch(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
                       int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_rmsprop* opt,
                       float* square_avg, double* loss_sums, int32_t* n_minibatches) {
-    return epoch_impl(t, "azg_trainer_epoch", OptForm::fused, params, rows, order, n_order, batch_size, loss_cfg, alpha_state, opt, square_avg,
+    return epoch_impl(t, "azg_trainer_epoch", OptForm::fused, params, rows, kNoWeights, order, n_order, batch_size, loss_cfg, alpha_state, opt, square_avg,
                       nullptr, loss_sums, n_minibatches);
 }
 
 int azg_trainer_epoch_opt(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
                           int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_optim* opt,
                           double* loss_sums, int32_t* n_minibatches) {
-    return epoch_impl(t, "azg_trainer_epoch_opt", OptForm::fused, params, rows, order, n_order, batch_size, loss_cfg, alpha_state, nullptr,
+    return epoch_impl(t, "azg_trainer_epoch_opt", OptForm::fused, params, rows, kNoWeights, order, n_order, batch_size, loss_cfg, alpha_state, nullptr,
                       nullptr, opt, loss_sums, n_minibatches);
 }
 
 int azg_trainer_epoch_nets(azg_trainer* t, float* params, const azg_epoch_rows* rows, const int32_t* order, int32_t n_order,
                            int32_t batch_size, const azg_loss_cfg* loss_cfgs, const azg_alpha_state* alpha_state, const azg_optim* opts,
                            double* loss_sums, int32_t* n_minibatches) {
-    return epoch_impl(t, "azg_trainer_epoch_nets", OptForm::table, params, rows, order, n_order, batch_size, loss_cfgs, alpha_state, nullptr,
+    return epoch_impl(t, "azg_trainer_epoch_nets", OptForm::table, params, rows, kNoWeights, order, n_order, batch_size, loss_cfgs, alpha_state, nullptr,
                       nullptr, opts, loss_sums, n_minibatches);
+}
+
+// ---- the weighted forms (include/azgym_train_weighted.h): the namesake's body with the weights
+
+int azg_trainer_loss_weighted(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values,
+                              const float* weights, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* cfg,
+                              const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
+    return loss_impl(t, "azg_trainer_loss_weighted", OptForm::fused, raw, actions, counts, values, RowWeights{true, weights}, n_rows, n_actions,
+                     cfg, alpha_state, d_raw, losses);
+}
+
+int azg_trainer_loss_nets_weighted(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values,
+                                   const float* weights, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* cfgs,
+                                   const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
+    return loss_impl(t, "azg_trainer_loss_nets_weighted", OptForm::table, raw, actions, counts, values, RowWeights{true, weights}, n_rows,
+                     n_actions, cfgs, alpha_state, d_raw, losses);
+}
+
+int azg_trainer_step_opt_weighted(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts,
+                                  const float* values, const float* weights, int32_t n_rows, int32_t n_actions,
+                                  const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_optim* opt, float* grads,
+                                  float* raw_out, float* losses) {
+    return step_impl(t, "azg_trainer_step_opt_weighted", OptForm::fused, params, obs, actions, counts, values, RowWeights{true, weights}, n_rows,
+                     n_actions, loss_cfg, alpha_state, nullptr, nullptr, opt, grads, raw_out, losses);
+}
+
+int azg_trainer_step_nets_weighted(azg_trainer* t, float* params, const float* obs, const float* actions, const float* counts,
+                                   const float* values, const float* weights, int32_t n_rows, int32_t n_actions,
+                                   const azg_loss_cfg* loss_cfgs, const azg_alpha_state* alpha_state, const azg_optim* opts, float* grads,
+                                   float* raw_out, float* losses) {
+    return step_impl(t, "azg_trainer_step_nets_weighted", OptForm::table, params, obs, actions, counts, values, RowWeights{true, weights}, n_rows,
+                     n_actions, loss_cfgs, alpha_state, nullptr, nullptr, opts, grads, raw_out, losses);
+}
+
+int azg_trainer_epoch_opt_weighted(azg_trainer* t, float* params, const azg_epoch_rows* rows, const float* weights, const int32_t* order,
+                                   int32_t n_order, int32_t batch_size, const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state,
+                                   const azg_optim* opt, double* loss_sums, int32_t* n_minibatches) {
+    return epoch_impl(t, "azg_trainer_epoch_opt_weighted", OptForm::fused, params, rows, RowWeights{true, weights}, order, n_order, batch_size,
+                      loss_cfg, alpha_state, nullptr, nullptr, opt, loss_sums, n_minibatches);
+}
+
+int azg_trainer_epoch_nets_weighted(azg_trainer* t, float* params, const azg_epoch_rows* rows, const float* weights, const int32_t* order,
+                                    int32_t n_order, int32_t batch_size, const azg_loss_cfg* loss_cfgs, const azg_alpha_state* alpha_state,
+                                    const azg_optim* opts, double* loss_sums, int32_t* n_minibatches) {
+    return epoch_impl(t, "azg_trainer_epoch_nets_weighted", OptForm::table, params, rows, RowWeights{true, weights}, order, n_order, batch_size,
+                      loss_cfgs, alpha_state, nullptr, nullptr, opts, loss_sums, n_minibatches);
 }
 
 int azg_trainer_read_d_raw(azg_trainer* t, int32_t n_rows, float* d_raw) {

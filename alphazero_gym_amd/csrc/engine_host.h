@@ -132,6 +132,11 @@ struct azg_engine : EngineQueue {
     // sp_rows_gen counts the changes of the ring's set of stored rows (a step, a clear, a begin); sp_prio_gen: its value when
     // azg_selfplay_priorities last ran (-1: never since the begin or since priorities were switched on)
     long long sp_rows_gen = 0, sp_prio_gen = -1;
+    // azg_selfplay_is_weights: the weight of every stored row [sp_cap][n_trees] and the minima of q (a partial minimum per scan segment
+    // [sp_prio_segs], then one per net [n_trees]), allocated by the first call; sp_isw_gen: sp_rows_gen when the weights were last
+    // computed from the priorities that stand (-1: never, or azg_selfplay_priorities has run since)
+    float* d_sp_isw = nullptr; unsigned long long* d_sp_isw_min = nullptr;
+    long long sp_isw_gen = -1;
     DeviceAllocs sp_mem;
     DeviceBuffer sp_order_buf;       // azg_selfplay_sample_rows: the drawn row numbers [n_nets][n_order] (grow-only)
     DeviceBuffer sr_buf, sr_ctab;    // azg_search_rollout: its roots, carried counts, books and outputs in one block; its (c / m)^temperature table (grow-only)

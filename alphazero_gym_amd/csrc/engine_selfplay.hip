@@ -73,7 +73,8 @@ static int selfplay_begin_impl(azg_engine* e, const azg_selfplay_config* c) {
     e->d_sp_tr_reward = e->d_sp_tr_value = nullptr; e->d_sp_tr_action = nullptr; e->d_sp_tr_end = nullptr;
     e->sp_prio_on = 0;                               // (azg_selfplay_keep_priorities too)
     e->d_sp_prio_q = e->d_sp_prio_within = e->d_sp_prio_seg = nullptr; e->d_sp_prio_given = nullptr; e->d_sp_prio_slots = nullptr;
-    e->sp_rows_gen += 1; e->sp_prio_gen = -1;
+    e->d_sp_isw = nullptr; e->d_sp_isw_min = nullptr;
+    e->sp_rows_gen += 1; e->sp_prio_gen = -1; e->sp_isw_gen = -1;
     const size_t B = e->cfg.n_trees;
     e->sp_row = e->S_obs + 3 * e->Kmax + 1;
     if (dalloc(e, e->sp_mem, &e->d_sp_t, B) || dalloc(e, e->sp_mem, &e->d_sp_episode, B) || dalloc(e, e->sp_mem, &e->d_sp_fcnt, B) ||
@@ -367,7 +368,7 @@ int azg_selfplay_nstep_targets(azg_engine* e, const azg_nstep_config* c) {
 int azg_selfplay_keep_priorities(azg_engine* e, int32_t on) {
     if (!e) return AZG_E_INVALID;
     if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
-    if (!on) { e->sp_prio_on = 0; e->sp_prio_gen = -1; return AZG_OK; }   // (the memory goes with the next begin)
+    if (!on) { e->sp_prio_on = 0; e->sp_prio_gen = -1; e->sp_isw_gen = -1; return AZG_OK; }   // (the memory goes with the next begin)
     if (e->sp_prio_on) return AZG_OK;
     const size_t n = (size_t)e->sp_cap * e->cfg.n_trees;
     if (n >= ((size_t)1 << 31)) return fail(e, AZG_E_UNSUPPORTED, "azg_selfplay_keep_priorities: capacity_steps * n_trees must stay below 2^31 rows");
@@ -403,6 +404,7 @@ int azg_selfplay_priorities(azg_engine* e, const azg_priority_config* c) {
         for (size_t i = 0; i < n; ++i)
             if (!(c->given[i] >= 0.0f)) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities: given[" + std::to_string(i) + "] is negative or NaN");
     }
+    e->sp_isw_gen = -1;   // (weights computed from the priorities before these are no longer handed out)
     if (n == 0) { e->sp_prio_gen = e->sp_rows_gen; return AZG_OK; }
     ON_DEVICE(e);
     Priorities pr;
@@ -488,6 +490,64 @@ int azg_selfplay_sample_slots(azg_engine* e, uint32_t sample_index, int32_t* slo
     HIPCHK(e, hipMemcpyAsync(slots, dr.slots, (size_t)B * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return AZG_OK;
+}
+
+// ---- importance-sampling weights of the stored rows (include/azgym_priority.h)
+
+int azg_selfplay_is_weights(azg_engine* e, float beta) {
+    if (!e) return AZG_E_INVALID;
+    int rc = sample_refusal(e, "azg_selfplay_is_weights");
+    if (rc) return rc;
+    if (!(beta >= 0.0f && std::isfinite(beta))) return fail(e, AZG_E_INVALID, "azg_selfplay_is_weights: beta must be finite and >= 0");
+    const int K = e->n_nets;
+    PrioMin pm;
+    pm.B = e->cfg.n_trees; pm.T = e->cfg.n_trees / K;
+    pm.N = e->sp_steps * pm.T; pm.nseg = (pm.N + PR_SEG - 1) / PR_SEG;
+    if ((size_t)K * pm.nseg > e->sp_prio_segs || K * pm.T != pm.B)   // (the population was changed after keep_priorities)
+        return fail(e, AZG_E_STATE, "azg_selfplay_is_weights: the population changed since azg_selfplay_keep_priorities");
+    ON_DEVICE(e);
+    if (!e->d_sp_isw) {   // one block: the minima (uint64) in front of the weights, so a failure leaves nothing behind
+        const size_t n_min = e->sp_prio_segs + (size_t)e->cfg.n_trees, n_w = (size_t)e->sp_cap * e->cfg.n_trees;
+        unsigned long long* block = nullptr;
+        if (dalloc(e, e->sp_mem, &block, n_min + (n_w + 1) / 2)) return AZG_E_DEVICE;
+        e->d_sp_isw_min = block; e->d_sp_isw = reinterpret_cast<float*>(block + n_min);
+    }
+    pm.q = e->d_sp_prio_q; pm.seg_min = e->d_sp_isw_min; pm.net_min = e->d_sp_isw_min + e->sp_prio_segs;
+    hipLaunchKernelGGL(prio_min_segments_kernel, dim3(pm.nseg, K), dim3(PR_THREADS), 0, e->stream, pm);
+    HIPCHK(e, hipGetLastError());
+    hipLaunchKernelGGL(prio_min_nets_kernel, dim3(K), dim3(64), 0, e->stream, pm);
+    HIPCHK(e, hipGetLastError());
+    IsWeights iw;
+    iw.rows_n = (long long)e->sp_steps * pm.B; iw.B = pm.B; iw.T = pm.T; iw.beta = beta;
+    iw.q = e->d_sp_prio_q; iw.net_min = pm.net_min; iw.w = e->d_sp_isw;
+    hipLaunchKernelGGL(is_weights_kernel, dim3((unsigned)((iw.rows_n + PR_THREADS - 1) / PR_THREADS)), dim3(PR_THREADS), 0, e->stream, iw);
+    HIPCHK(e, hipGetLastError());
+    e->sp_isw_gen = e->sp_rows_gen;
+    return AZG_OK;
+}
+
+int azg_selfplay_is_weights_device(azg_engine* e, const float** w) {
+    if (!e) return AZG_E_INVALID;
+    if (!w) return fail(e, AZG_E_INVALID, "azg_selfplay_is_weights_device: w must not be NULL");
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (!e->sp_prio_on) return fail(e, AZG_E_STATE, "azg_selfplay_keep_priorities has not been called");
+    if (!e->d_sp_isw || e->sp_isw_gen != e->sp_rows_gen)
+        return fail(e, AZG_E_STATE, "azg_selfplay_is_weights_device: azg_selfplay_is_weights has not run since the ring's stored rows or their priorities last changed");
+    *w = e->d_sp_isw;
+    return AZG_OK;
+}
+
+int azg_selfplay_is_weight_values(azg_engine* e, float* w, size_t max_rows) {
+    if (!e) return AZG_E_INVALID;
+    if (!e->sp_on) return fail(e, AZG_E_STATE, "azg_selfplay_begin has not been called");
+    if (!e->sp_prio_on) return fail(e, AZG_E_STATE, "azg_selfplay_keep_priorities has not been called");
+    if (!e->d_sp_isw) return fail(e, AZG_E_STATE, "azg_selfplay_is_weight_values: azg_selfplay_is_weights has not been called");
+    ON_DEVICE(e);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    size_t n = (size_t)e->sp_steps * e->cfg.n_trees;
+    if (n > max_rows) n = max_rows;
+    if (n) D2H(w, e->d_sp_isw, n * 4);
+    return (int)n;
 }
 
 // ---- search rollouts (include/azgym_search_rollout.h)

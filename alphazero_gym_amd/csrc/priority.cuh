@@ -1,8 +1,9 @@
 // priority.cuh -- prioritised sampling from the device replay ring (include/azgym_priority.h states the rule; compiled in one translation
-// unit: engine_selfplay.hip).  Four kernels: the priority q of every stored row; the prefix sums of a net's q in two levels (each
+// unit: engine_selfplay.hip).  The draws' kernels: the priority q of every stored row; the prefix sums of a net's q in two levels (each
 // segment of PR_SEG rows scanned by one workgroup, then the segment totals scanned by one wave per net); the row draws, each a binary
 // search over the segment totals and then within one segment; the slot draws, one thread per game column.  Every sum is an integer add
-// of uint64 values whose total stays below 2^63, so the sums are exact whatever the order and nothing here is atomic.
+// of uint64 values whose total stays below 2^63, so the sums are exact whatever the order and nothing here is atomic.  The
+// importance-sampling weights' kernels (at the end): a net's least q in the same two levels, then the weight of every stored row.
 #pragma once
 #include "../../include/azg_math.h"
 #include "../../include/azgym_priority.h"
@@ -176,4 +177,78 @@ __global__ __launch_bounds__(PR_THREADS) void prio_draw_slots_kernel(PrioSlots d
         if (run > target) break;
     }
     dr.slots[t] = s;
+}
+
+// ------------------------------------------------------------------------------------------------ importance-sampling weights
+
+// q, the least q of the row's net, beta -> w = (q_min / q)^beta.  Every step is rounded on its own, as in priority_q.
+__host__ __device__ __forceinline__ float priority_is_weight(pr_u64 q, pr_u64 q_min, float beta) {
+#pragma clang fp contract(off)
+    if (beta == 0.0f || q == q_min) return 1.0f;
+    const float r = (float)((double)q_min / (double)q);   // both at most 2^40: exact conversions, one rounded division
+    const float m = beta * azg_logf(r);
+    return azg_expf(m);
+}
+
+// The least q of every net, in the scan's two levels and over the scan's segments (PrioScan's numbering of a net's rows).
+struct PrioMin {
+    int B, T;
+    int N, nseg;
+    const pr_u64* q;     // [capacity_steps][B]
+    pr_u64* seg_min;     // [n_nets][nseg]: a segment's least q
+    pr_u64* net_min;     // [n_nets]
+};
+__device__ __forceinline__ pr_u64 wave_min_u64(pr_u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const pr_u64 other = __shfl_xor(v, o, 64);
+        v = other < v ? other : v;
+    }
+    return v;
+}
+
+// grid (nseg, n_nets): one workgroup folds one segment (a row past N counts as the largest uint64; a segment has at least one row)
+__global__ __launch_bounds__(PR_THREADS) void prio_min_segments_kernel(PrioMin pm) {
+    __shared__ pr_u64 wave_least[PR_THREADS / 64];
+    const int k = blockIdx.y, seg = blockIdx.x;
+    const int i = seg * PR_SEG + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    pr_u64 v = ~0ull;
+    if (i < pm.N) {
+        const int slot = i / pm.T;
+        v = pm.q[(size_t)slot * pm.B + (size_t)k * pm.T + (i - slot * pm.T)];
+    }
+    v = wave_min_u64(v);
+    if (lane == 0) wave_least[wave] = v;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int w = 1; w < PR_THREADS / 64; ++w) v = wave_least[w] < v ? wave_least[w] : v;
+    pm.seg_min[(size_t)k * pm.nseg + seg] = v;
+}
+
+// grid (n_nets), one wave: lane l folds segments l, l + 64, ...; then the wave's least
+__global__ __launch_bounds__(64) void prio_min_nets_kernel(PrioMin pm) {
+    const pr_u64* seg = pm.seg_min + (size_t)blockIdx.x * pm.nseg;
+    pr_u64 v = ~0ull;
+    for (int s = threadIdx.x; s < pm.nseg; s += 64) v = seg[s] < v ? seg[s] : v;
+    v = wave_min_u64(v);
+    if (threadIdx.x == 0) pm.net_min[blockIdx.x] = v;
+}
+
+// One thread per stored row, thread slot * B + tree, like priorities_kernel: q and w are coalesced, the net's minimum is one of a few
+// addresses per wave.
+struct IsWeights {
+    long long rows_n;         // stored rows: size_steps * n_trees
+    int B, T;
+    float beta;
+    const pr_u64* q;          // [capacity_steps][B]
+    const pr_u64* net_min;    // [n_nets] (after both minimum kernels)
+    float* w;                 // [capacity_steps][B]
+};
+__global__ __launch_bounds__(PR_THREADS) void is_weights_kernel(IsWeights iw) {
+    const long long idx = (long long)blockIdx.x * PR_THREADS + threadIdx.x;
+    if (idx >= iw.rows_n) return;
+    const int tree = (int)(idx % iw.B);
+    iw.w[idx] = priority_is_weight(iw.q[idx], iw.net_min[tree / iw.T], iw.beta);
 }

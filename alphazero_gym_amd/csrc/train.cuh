@@ -431,11 +431,21 @@ __device__ __forceinline__ double tr_softplus(double t) { return t > 20.0 ? t : 
 // z = raw + 1 is the distribution head.  The row's arithmetic is float64 from the float32 inputs, every sum over its actions and
 // components a chain in index order; d is rounded to float32 once per element.  (In float32 the row terms carry the 2^-24 of expf /
 // logf into sums that the float32 PyTorch path sometimes happens to hit exactly: DESIGN section 3.)
-__device__ __forceinline__ void tr_loss_row(const LossDims& c, double alpha, const float* raw, const float* act, const float* cnt, float v,
-                                            float* d, double (&terms)[3]) {
+//
+// WT (the weighted losses, azgym_train_weighted.h): the row's weight w multiplies every element of d in float64 before its one
+// rounding, (float)(w * x) with x the value the WT = false form rounds; terms stay unweighted (the caller multiplies them).  w = 1 gives
+// the WT = false bits: 1.0 * x is exact.
+template <bool WT>
+__device__ __forceinline__ float tr_round_w(double w, double x) {
+    if constexpr (WT) return (float)(w * x);
+    else return (float)x;
+}
+template <bool WT>
+__device__ __forceinline__ void tr_loss_row_t(const LossDims& c, double alpha, const float* raw, const float* act, const float* cnt, float v,
+                                              double w_row, float* d, double (&terms)[3]) {
     const double dv = (double)raw[0] - (double)v;
     terms[1] = dv * dv;
-    d[0] = (float)(c.cV * (2.0 * dv));
+    d[0] = tr_round_w<WT>(w_row, c.cV * (2.0 * dv));
     const float* z = raw + 1;
     const double aE = alpha * c.cE;
     if (c.head == AZG_HEAD_DISCRETE) {
@@ -451,7 +461,7 @@ __device__ __forceinline__ void tr_loss_row(const LossDims& c, double alpha, con
             for (int i = 1; i < c.A; ++i) if (cnt[i] > cnt[t]) t = i;
             terms[0] = -((double)z[t] - lse);
             terms[2] = 0.0;
-            for (int j = 0; j < n; ++j) d[1 + j] = (float)(c.cP * (exp((double)z[j] - lse) - (j == t ? 1.0 : 0.0)));
+            for (int j = 0; j < n; ++j) d[1 + j] = tr_round_w<WT>(w_row, c.cP * (exp((double)z[j] - lse) - (j == t ? 1.0 : 0.0)));
             return;
         }
         // log pi_i = lsm[a_i]; W[j] = the sum of the detached factors w_i = log pi_i - tau log(counts_i + 1) of the actions i with a_i = j
@@ -477,7 +487,7 @@ __device__ __forceinline__ void tr_loss_row(const LossDims& c, double alpha, con
         for (int j = 0; j < TR_MAX_ACTIONS; ++j) {
             if (j < n) {
                 const double l = (double)z[j] - lse, pj = exp(l);
-                d[1 + j] = (float)(c.cP * (W[j] - pj * wsum) - aE * (pj * (l + H)));
+                d[1 + j] = tr_round_w<WT>(w_row, c.cP * (W[j] - pj * wsum) - aE * (pj * (l + H)));
             }
         }
         return;
@@ -549,11 +559,16 @@ __device__ __forceinline__ void tr_loss_row(const LossDims& c, double alpha, con
 #pragma unroll
     for (int k = 0; k < TR_MAX_COMP; ++k) {
         if (k < C) {
-            d[1 + k] = (float)dmu[k];
-            d[1 + C + k] = gate[k] ? (float)dls[k] : 0.0f;
-            if (gmm) d[1 + 2 * C + k] = (float)dlc[k];
+            d[1 + k] = tr_round_w<WT>(w_row, dmu[k]);
+            d[1 + C + k] = gate[k] ? tr_round_w<WT>(w_row, dls[k]) : 0.0f;
+            if (gmm) d[1 + 2 * C + k] = tr_round_w<WT>(w_row, dlc[k]);
         }
     }
+}
+
+__device__ __forceinline__ void tr_loss_row(const LossDims& c, double alpha, const float* raw, const float* act, const float* cnt, float v,
+                                            float* d, double (&terms)[3]) {
+    tr_loss_row_t<false>(c, alpha, raw, act, cnt, v, 1.0, d, terms);
 }
 
 // (TR_NO_SHARED_KERNELS: a second translation unit that wants this header's device routines and templates, not another copy of the
@@ -689,5 +704,94 @@ __global__ __launch_bounds__(64) void train_loss_sum_kernel(const float* table, 
     double s = 0.0;
     for (int m = 0; m < n_minibatches; ++m) s = s + (double)table[(size_t)m * n + e];
     sums[e] = s;
+}
+// ------------------------------------------------------------------------------------------------ weighted losses
+// include/azgym_train_weighted.h: a float32 weight per minibatch row, weights [n_nets][n_rows], multiplies the row's summands and its
+// d_raw in float64 before the reductions, which stay what they are.  rows: a float64 [n_nets][4][stride] array of the weighted path's
+// own -- the three weighted terms and, fourth, the weight itself, whose sum S_w the tuned loss's alpha_loss needs:
+// alpha * (S_wH / n - target * (S_w / n)).  train_loss_kernel's text with those changes; weights of 1.0f give its bits (every product
+// with 1.0 is exact and S_w / n is 1).
+__device__ __forceinline__ void tr_loss_weighted_body(const LossDims& c, const float* raw, const float* actions, const float* counts,
+                                                      const float* values, const float* weights, int n_rows, float* log_alpha,
+                                                      float* exp_avg, float* exp_avg_sq, float* d_raw, float* losses, double* rows,
+                                                      int stride) {
+    const int net = blockIdx.x, tid = threadIdx.x, NO = 1 + c.nd;
+    const bool tuned = c.kind == AZG_LOSS_A0C_TUNED;
+    const float la = tuned ? log_alpha[net] : 0.0f;
+    const double alpha = tuned ? exp((double)la) : c.alpha;
+    double* rw = rows + (size_t)net * 4 * stride;
+    for (int row = tid; row < n_rows; row += TR_LOSS_THREADS) {
+        const size_t at = (size_t)net * n_rows + row;
+        const double w = (double)weights[at];
+        double terms[3];
+        tr_loss_row_t<true>(c, alpha, raw + at * NO, actions + at * c.A, counts + at * c.A, values[at], w, d_raw + at * NO, terms);
+        rw[row] = w * terms[0]; rw[stride + row] = w * terms[1]; rw[2 * stride + row] = w * terms[2]; rw[3 * (size_t)stride + row] = w;
+    }
+    __syncthreads();
+    __shared__ double sums[4];
+    if (tid < 4) sums[tid] = tr_colsum64(n_rows, [&](int r) { return rw[(size_t)tid * stride + r]; });
+    __syncthreads();
+    if (tid != 0) return;
+    float* out = losses + (size_t)net * AZG_LOSS_SLOTS;
+    const double policy = c.pc * (sums[0] * c.red), value = c.vc * (sums[1] * c.red);
+    if (c.kind == AZG_LOSS_ALPHAZERO) {
+        out[AZG_LOSS_TOTAL] = (float)(policy + value); out[AZG_LOSS_POLICY] = (float)policy; out[AZG_LOSS_VALUE] = (float)value;
+        out[AZG_LOSS_ENTROPY] = 0.0f; out[AZG_LOSS_ALPHA] = 0.0f;
+        return;
+    }
+    const double a = alpha;
+    const double entropy = a * (sums[2] * c.ent_red);
+    out[AZG_LOSS_TOTAL] = (float)((policy + entropy) + value); out[AZG_LOSS_POLICY] = (float)policy; out[AZG_LOSS_VALUE] = (float)value;
+    out[AZG_LOSS_ENTROPY] = (float)entropy;
+    if (!tuned) { out[AZG_LOSS_ALPHA] = 0.0f; return; }
+    // alpha_loss = mean(exp(log_alpha) * w * (entropy - target).detach())
+    const double alpha_loss = a * (sums[2] * c.inv_rows - c.target * (sums[3] / (double)n_rows));
+    out[AZG_LOSS_ALPHA] = (float)alpha_loss;
+    double g = alpha_loss;
+    if (c.clip != 0.0) { const double f = c.clip / (fabs(g) + 1e-6); g = g * (f < 1.0 ? f : 1.0); }
+    double p = (double)la;
+    tr_adam(p, exp_avg + net, exp_avg_sq + net, g, c.lr, c.b1, c.b2, c.eps, c.wd, c.bc1, c.bc2_sqrt);
+    log_alpha[net] = (float)p;
+}
+
+__global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_weighted_kernel(LossDims c, const float* raw, const float* actions,
+                                                                              const float* counts, const float* values, const float* weights,
+                                                                              int n_rows, float* log_alpha, float* exp_avg, float* exp_avg_sq,
+                                                                              float* d_raw, float* losses, double* rows, int stride) {
+    tr_loss_weighted_body(c, raw, actions, counts, values, weights, n_rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, rows, stride);
+}
+
+// ... with the settings of net blockIdx.x from table[blockIdx.x] (the *_nets_weighted entry points)
+__global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_nets_weighted_kernel(const LossDims* __restrict__ table, const float* raw,
+                                                                                   const float* actions, const float* counts,
+                                                                                   const float* values, const float* weights, int n_rows,
+                                                                                   float* log_alpha, float* exp_avg, float* exp_avg_sq,
+                                                                                   float* d_raw, float* losses, double* rows, int stride) {
+    const LossDims c = table[blockIdx.x];
+    tr_loss_weighted_body(c, raw, actions, counts, values, weights, n_rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, rows, stride);
+}
+
+// train_gather_kernel, and the wave that copies row `at` also stages weights[at] -- the weight array is addressed like the rows with
+// a row length of 1 -- into wout [nets][n_rows].
+__global__ __launch_bounds__(TR_GATHER_THREADS) void train_gather_weighted_kernel(GatherDims g, const float* rows, const float* weights,
+                                                                                  const int* order, int first, int n_rows, float* obs,
+                                                                                  float* actions, float* counts, float* values, float* wout) {
+    const int net = blockIdx.y, lane = threadIdx.x & 63;
+    const int b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (TR_GATHER_THREADS / 64) + (threadIdx.x >> 6)));
+    if (b >= n_rows) return;
+    const int i = __builtin_amdgcn_readfirstlane(order[(size_t)net * g.n_order + first + b]);
+    const long long at = (long long)(i / g.group) * g.group_stride + (long long)net * g.net_stride + (long long)(i % g.group);
+    const float* src = rows + at * g.row_len;
+    const size_t out = (size_t)net * n_rows + b;
+    const int a0 = g.state_dim, c0 = a0 + g.A, q0 = c0 + g.A, v0 = g.row_len - 1;
+    for (int c = lane; c < g.row_len; c += 64) {
+        if (c >= q0 && c < v0) continue;
+        const float x = src[c];
+        if (c < a0) obs[out * g.state_dim + c] = x;
+        else if (c < c0) actions[out * g.A + (c - a0)] = x;
+        else if (c < q0) counts[out * g.A + (c - c0)] = x;
+        else values[out] = x;
+    }
+    if (lane == 0) wout[out] = weights[at];
 }
 #endif  // TR_NO_SHARED_KERNELS

@@ -335,8 +335,10 @@ class PopulationSelfPlay:
     stored row beside the ring (include/azgym_priority.h): ``(|search value - V_target| + eps) ** alpha``, MuZero's, which needs
     ``n_step``.  ``sample_order(n)`` then draws training rows per net in proportion to it, on the device, in the form
     ``PopulationTrainer.train_epoch_ring`` takes as its order, and ``reanalyse(by="priority")`` draws the reanalysed position of
-    every game the same way.  The draws are biased towards surprising rows and nothing corrects the loss for it: there are no
-    importance-sampling weights."""
+    every game the same way.  The draws are biased towards surprising rows; with ``"beta"`` in ``prioritized`` (optional; absent:
+    no weight is ever computed) ``is_weights()`` computes the importance-sampling weight ``(q_min / q) ** beta`` of every stored
+    row on the device, q_min the least priority of the row's net, and ``PopulationTrainer.train_epoch_ring(sp, order,
+    weights="priority")`` multiplies it into the row's losses."""
 
     def __init__(self, policies, *, game: str, games_per_net: int, n_rollouts: int, c_uct: float, gamma: float = 1.0, epsilon: float = 0.0,
                  c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
@@ -349,8 +351,15 @@ class PopulationSelfPlay:
         if not policies or games_per_net < 1:
             raise ValueError(f"{type(self).__name__} needs at least one policy and games_per_net >= 1")
         if prioritized is not None:
-            if set(prioritized) - {"alpha", "eps"}:
-                raise ValueError(f"{type(self).__name__}: prioritized takes alpha and eps, not {sorted(set(prioritized) - {'alpha', 'eps'})}")
+            if set(prioritized) - {"alpha", "eps", "beta"}:
+                raise ValueError(f"{type(self).__name__}: prioritized takes alpha, eps and beta, not "
+                                 f"{sorted(set(prioritized) - {'alpha', 'eps', 'beta'})}")
+            if prioritized.get("beta") is not None:
+                if "alpha" not in prioritized:
+                    raise ValueError(f"{type(self).__name__}: prioritized takes alpha and eps, and beta only beside alpha (the weights "
+                                     "correct a draw by priority)")
+                if not (float(prioritized["beta"]) >= 0.0 and np.isfinite(float(prioritized["beta"]))):
+                    raise ValueError(f"{type(self).__name__}: prioritized beta must be finite and >= 0")
             if n_step is None:
                 raise ValueError(f"{type(self).__name__}: prioritized needs n_step (the priority is |search value - n-step target|, and "
                                  "both are kept only then)")
@@ -387,6 +396,8 @@ class PopulationSelfPlay:
             self.engine.selfplay_keep_transitions(True)
         self.prioritized = None if prioritized is None else dict(alpha=float(prioritized.get("alpha", 0.6)),
                                                                  eps=float(prioritized.get("eps", 1e-3)))
+        if self.prioritized is not None and prioritized.get("beta") is not None:
+            self.prioritized["beta"] = float(prioritized["beta"])
         # the row draws and the slot draws take their sample indices from a counter each, both from 0: the streams differ
         self._sample_index = 0
         self._slot_sample_index = 0
@@ -437,11 +448,26 @@ class PopulationSelfPlay:
         """``n_order`` training rows per net drawn on the device in proportion to the rows' priorities, with replacement: int32
         [K, n_order], what ``PopulationTrainer.train_epoch_ring(sp, order)`` takes.  The priorities are recomputed first
         (``priorities(given)``); every call takes the next index of a counter that starts at 0.  The draw is biased towards large
-        priorities; the loss is not reweighted."""
+        priorities; ``is_weights()`` after it computes the weights that correct the loss."""
         self.priorities(given)
         order = self.engine.selfplay_sample_rows(int(n_order), self._sample_index)
         self._sample_index += 1
         return order
+
+    def is_weights(self, beta: Optional[float] = None) -> None:
+        """Compute the importance-sampling weight of every stored row from the priorities that stand
+        (``Engine.selfplay_is_weights``; asynchronous: three launches): ``(q_min / q) ** beta`` with q_min the least priority of the
+        row's net.  ``beta`` None: the one given at creation.  Call it after ``sample_order`` (which recomputes the priorities);
+        ``PopulationTrainer.train_epoch_ring(sp, order, weights="priority")`` then reads the weights where they lie."""
+        if self.prioritized is None:
+            raise RuntimeError(f"{type(self).__name__}.is_weights needs a priority per stored row: create it with prioritized={{...}}")
+        if beta is None:
+            beta = self.prioritized.get("beta")
+        if beta is None:
+            raise ValueError(f'{type(self).__name__}.is_weights needs a beta: pass one, or create it with prioritized={{..., "beta": b}}')
+        if not (float(beta) >= 0.0 and np.isfinite(float(beta))):
+            raise ValueError(f"{type(self).__name__}.is_weights: beta must be finite and >= 0")
+        self.engine.selfplay_is_weights(float(beta))
 
     def reanalyse(self, slots=None, n: int = 1, rng: Optional[np.random.Generator] = None, by: str = "uniform") -> list:
         """MuZero's Reanalyse on the device ring: search stored positions again with the CURRENT weights (pending uploads are

@@ -35,6 +35,10 @@ n_step=N; an episode's terminal step closes the window, a time limit and the new
 --prioritized-alpha A [--prioritized-eps E], with --replay-steps and --n-step, replaces the uniform pick of training rows by a draw
 in proportion to (|search value - value target| + E)^A, made on the device from priorities kept beside the ring (PopulationSelfPlay
 prioritized=..., sample_order); with --reanalyse-slots N the reanalysed positions are drawn the same way, one per game and search.
+--prioritized-beta B corrects the draw's bias: after the draw the engine computes every stored row's importance-sampling weight
+(the net's least priority / the row's priority)^B on the device (is_weights), and the population trainer multiplies it into the row's
+losses -- --trainer device-epoch reads the weights where they lie (train_epoch_ring(weights="priority")), --trainer device and
+device-fused pass the gathered weights to update.  It needs one of those three trainers.
 The draw is with replacement and biased; the loss is not reweighted (no importance-sampling weights).
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
@@ -129,6 +133,10 @@ def parse_args(argv=None):
                          "(|search value - value target| + eps)^alpha on the device instead of uniformly; needs --replay-steps and "
                          "--n-step (default: off, nothing is kept)")
     ap.add_argument("--prioritized-eps", type=float, default=1e-3, help="the eps of --prioritized-alpha")
+    ap.add_argument("--prioritized-beta", type=float, default=None,
+                    help="correct the prioritised draw's bias: multiply every drawn row's losses by its importance-sampling weight "
+                         "(least priority of the net / the row's priority)^beta, computed on the device; needs --prioritized-alpha and a --trainer other than torch "
+                         "(default: off, no weight is computed)")
     a = ap.parse_args(argv)
     why = check_replay(a)
     if why:
@@ -196,6 +204,14 @@ def check_replay(a):
             return "--prioritized-alpha needs --n-step N: the priority is |search value - n-step target|, and both are kept only then"
         if not (a.prioritized_alpha >= 0.0 and a.prioritized_eps > 0.0):
             return "--prioritized-alpha must be >= 0 and --prioritized-eps > 0"
+    if getattr(a, "prioritized_beta", None) is not None:
+        if getattr(a, "prioritized_alpha", None) is None:
+            return "--prioritized-beta weighs rows drawn by priority: it needs --prioritized-alpha A"
+        if not (a.prioritized_beta >= 0.0 and np.isfinite(a.prioritized_beta)):
+            return "--prioritized-beta must be finite and >= 0"
+        if a.trainer == "torch":
+            return ("--prioritized-beta: the weighted losses are the population trainer's: use --trainer device, device-fused or "
+                    "device-epoch (the per-agent update loop of --trainer torch takes no weights)")
     if a.reanalyse_slots and not (a.replay_steps or a.trainer == "device-epoch"):
         return ("--reanalyse-slots rewrites rows that stay in the device ring: use it with --replay-steps R (the FIFO ring) or with "
                 "--trainer device-epoch; the other modes copy the rows out and clear the ring every iteration")
@@ -215,10 +231,13 @@ def check_population_shape(a):
 
 
 def prioritized(a):
-    """PopulationSelfPlay's ``prioritized`` for --prioritized-alpha / --prioritized-eps (None: off)."""
+    """PopulationSelfPlay's ``prioritized`` for --prioritized-alpha / --prioritized-eps / --prioritized-beta (None: off)."""
     if getattr(a, "prioritized_alpha", None) is None:
         return None
-    return {"alpha": a.prioritized_alpha, "eps": getattr(a, "prioritized_eps", 1e-3)}
+    out = {"alpha": a.prioritized_alpha, "eps": getattr(a, "prioritized_eps", 1e-3)}
+    if getattr(a, "prioritized_beta", None) is not None:
+        out["beta"] = a.prioritized_beta
+    return out
 
 
 def build_population(a):
@@ -257,6 +276,7 @@ def train(a, log=print, on_rows=None, on_end=None):
                                     wide_layernorm=a.wide and a.layernorm)
     replay_steps, reanalyse_slots = getattr(a, "replay_steps", 0), getattr(a, "reanalyse_slots", 0)
     by_priority = sp.prioritized is not None
+    weighted = by_priority and "beta" in sp.prioritized
 
     def reanalyse():
         if by_priority:   # one search per "slot": every game re-searches the position drawn for it
@@ -303,12 +323,14 @@ def train(a, log=print, on_rows=None, on_end=None):
         losses = []
         # (net k's rows are numbered slot * T + game in the ring and in _split's copies alike)
         prio_order = sp.sample_order(min(a.train_rows, n_ring)) if by_priority else None
+        if weighted:   # the weights of the priorities the draw was just made from
+            sp.is_weights()
         if rows is None:   # the other trainers' picks and shuffles from the same streams, composed into one order per net
             order = []
             for k, rng in enumerate(rngs):
                 pick = pick_rows(k, rng, n_ring)
                 order.append(pick[np.random.RandomState(int(rng.randint(2 ** 31 - 1))).permutation(len(pick))])
-            infos = trainer.train_epoch_ring(sp, np.stack(order), batch_size=a.batch_size)
+            infos = trainer.train_epoch_ring(sp, np.stack(order), batch_size=a.batch_size, weights="priority" if weighted else None)
             if not replay_steps:
                 sp.engine.selfplay_clear()
             losses = [info["loss"] / max(1, len(order[0]) // a.batch_size) for info in infos]
@@ -319,12 +341,19 @@ def train(a, log=print, on_rows=None, on_end=None):
                                          shuffle_seed=int(rng.randint(2 ** 31 - 1)))
                 losses.append(info["loss"] / max(1, len(pick) // a.batch_size))
         else:   # the same rows and shuffles, every net's minibatch step at once
-            picked, seeds = [], []
+            picked, seeds, picked_w = [], [], []
+            if weighted:   # [size, n_games] -> net k's rows in _split's numbering, slot * T + game
+                T = sp.games_per_net
+                w_ring = torch.from_numpy(sp.engine.selfplay_is_weight_values()).to(rows[0].device).reshape(-1, sp.n_games)
             for k, (rng, r) in enumerate(zip(rngs, rows)):
                 pick = pick_rows(k, rng, r.shape[0])
-                picked.append(r[torch.from_numpy(pick).to(r.device)])
+                at = torch.from_numpy(pick).to(r.device)
+                picked.append(r[at])
+                if weighted:
+                    picked_w.append(w_ring[:, k * T:(k + 1) * T].reshape(-1)[at])
                 seeds.append(int(rng.randint(2 ** 31 - 1)))
-            infos = trainer.train_on_rows(picked, state_dim, K, batch_size=a.batch_size, shuffle_seeds=seeds)
+            infos = trainer.train_on_rows(picked, state_dim, K, batch_size=a.batch_size, shuffle_seeds=seeds,
+                                          weights=torch.stack(picked_w) if weighted else None)
             losses = [info["loss"] / max(1, picked[0].shape[0] // a.batch_size) for info in infos]
         t3 = time.time()
         if trainer is None:

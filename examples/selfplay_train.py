@@ -20,7 +20,9 @@ an episode's terminal step closes the window, a time limit and the newest stored
 --prioritized-alpha A [--prioritized-eps E], with --replay-steps and --n-step, replaces the uniform pick of training rows by a draw in
 proportion to (|search value - value target| + E)^A, made on the device from priorities kept beside the ring (DeviceSelfPlay
 prioritized=..., sample_order); with --reanalyse-slots N the reanalysed positions are drawn the same way, one per game and search.  The
-draw is with replacement and biased; the loss is not reweighted (no importance-sampling weights).
+draw is with replacement and biased; --prioritized-beta B corrects for it: every drawn row's losses are multiplied by its
+importance-sampling weight (least priority / the row's priority)^B, computed on the device (DeviceSelfPlay.is_weights), and the
+optimiser steps go through a one-net PopulationTrainer(losses="device"), whose update takes the gathered weights.
 
 --eval-search-episodes E adds eval_search_return: after every iteration every game plays E whole episodes under MCTS with the greedy
 final-action rule, on the device in one call and on state of its own (DeviceSelfPlay.evaluate_search): the return of the agent as it
@@ -100,6 +102,10 @@ def parse_args(argv=None):
                          "(|search value - value target| + eps)^alpha on the device instead of uniformly; needs --replay-steps and "
                          "--n-step (default: off, nothing is kept)")
     ap.add_argument("--prioritized-eps", type=float, default=1e-3, help="the eps of --prioritized-alpha")
+    ap.add_argument("--prioritized-beta", type=float, default=None,
+                    help="correct the prioritised draw's bias: multiply every drawn row's losses by its importance-sampling weight "
+                         "(least priority of the net / the row's priority)^beta, computed on the device; needs --prioritized-alpha "
+                         "(default: off, no weight is computed)")
     a = ap.parse_args(argv)
     if a.eval_search_episodes < 0:
         ap.error("--eval-search-episodes must be >= 0")
@@ -121,7 +127,28 @@ def parse_args(argv=None):
             ap.error("--prioritized-alpha needs --n-step N: the priority is |search value - n-step target|, and both are kept only then")
         if not (a.prioritized_alpha >= 0.0 and a.prioritized_eps > 0.0):
             ap.error("--prioritized-alpha must be >= 0 and --prioritized-eps > 0")
+    if a.prioritized_beta is not None:
+        if a.prioritized_alpha is None:
+            ap.error("--prioritized-beta weighs rows drawn by priority: it needs --prioritized-alpha A")
+        if not (a.prioritized_beta >= 0.0 and np.isfinite(a.prioritized_beta)):
+            ap.error("--prioritized-beta must be finite and >= 0")
     return a
+
+
+def weighted_epoch(trainer, rows, weights, state_dim, K, batch_size, shuffle_seed):
+    """run.train_on_rows's epoch through a one-net PopulationTrainer: the same shuffle and minibatches, every minibatch passed to
+    ``update`` with its rows' importance-sampling weights."""
+    from alphazero_gym_amd.agent.population_trainer import minibatch_bounds
+    order = np.random.RandomState(shuffle_seed).permutation(rows.shape[0])
+    sums = {}
+    for i, j in minibatch_bounds(rows.shape[0], batch_size):
+        idx = torch.from_numpy(order[i:j]).to(rows.device)
+        b = rows[idx].unsqueeze(0)
+        batch = (b[..., :state_dim], b[..., state_dim:state_dim + K], b[..., state_dim + K:state_dim + 2 * K],
+                 b[..., state_dim + 2 * K:state_dim + 3 * K], b[..., -1])
+        for key, val in trainer.update(batch, weights=weights[idx].unsqueeze(0))[0].items():
+            sums[key] = sums.get(key, 0.0) + val
+    return sums
 
 
 def train(a, log=print):
@@ -137,6 +164,9 @@ def train(a, log=print):
     prioritized = None
     if getattr(a, "prioritized_alpha", None) is not None:
         prioritized = {"alpha": a.prioritized_alpha, "eps": getattr(a, "prioritized_eps", 1e-3)}
+        if getattr(a, "prioritized_beta", None) is not None:
+            prioritized["beta"] = a.prioritized_beta
+    weighted = prioritized is not None and "beta" in prioritized
     sp = run.DeviceSelfPlay(agent.nn, game=a.game, n_games=a.games, n_rollouts=a.n_rollouts, c_uct=m.c_uct, gamma=m.gamma,
                             epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0), kappa=getattr(m, "kappa", 0.5),
                             max_episode_length=a.max_episode_length, capacity_steps=replay_steps or a.steps_per_iter, fifo=bool(replay_steps),
@@ -145,6 +175,12 @@ def train(a, log=print):
                             device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0)
     K = sp.engine.kmax if continuous else 2
     rng = np.random.RandomState(a.seed)
+    trainer = None
+    if weighted:   # the weighted losses are the population trainer's: one net, the agent's own optimiser and clip
+        from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
+        wide = len(a.hidden) > 3 or max(a.hidden) > 256
+        trainer = PopulationTrainer([agent], max_batch=max(512, 2 * a.batch_size), losses="device", optimizers="agents",
+                                    layernorm=a.layernorm and not wide, wide=wide and not a.layernorm, wide_layernorm=wide and a.layernorm)
     fs0, fc0 = 0.0, 0
     t0 = time.time()
     history = []
@@ -172,7 +208,13 @@ def train(a, log=print):
             pick = sp.sample_order(min(a.train_rows, rows.shape[0]))[0].astype(np.int64)
         else:
             pick = rng.choice(rows.shape[0], size=min(a.train_rows, rows.shape[0]), replace=False)
-        if rank == 0:
+        if weighted:   # the weights of the priorities the draw was made from, in the ring's row numbering
+            sp.is_weights()
+            w = torch.from_numpy(sp.engine.selfplay_is_weight_values()).to(rows.device)
+            at = torch.from_numpy(pick).to(rows.device)
+            info = weighted_epoch(trainer, rows[at], w[at], state_dim, K, a.batch_size, it)
+            sp.upload_flat(trainer.desc, trainer.flat)
+        elif rank == 0:
             info = run.train_on_rows(agent, rows[torch.from_numpy(pick).to(rows.device)], state_dim, K, batch_size=a.batch_size, shuffle_seed=it)
         if world > 1:
             D.broadcast_weights(agent.nn, src=0)
@@ -193,6 +235,8 @@ def train(a, log=print):
         if log and rank == 0:
             log(json.dumps(history[-1]), flush=True)
         fs0, fc0 = fs, fc
+    if trainer is not None:
+        trainer.close()
     return history
 
 

@@ -6,8 +6,9 @@
  * of azg_selfplay_keep_transitions and the row's V_target column).  This header adds one fixed-point priority q per stored row
  * (azg_selfplay_priorities) and two proportional draws that run on the device: row numbers per net in the form a training epoch takes
  * as its order (azg_selfplay_sample_rows), and one slot per game in the form azg_selfplay_reanalyse takes as `slots`
- * (azg_selfplay_sample_slots).  Only the drawn indices come back to the host.  The draw is biased towards large priorities and nothing
- * here corrects for it: importance-sampling weights are not part of this interface.
+ * (azg_selfplay_sample_slots).  Only the drawn indices come back to the host.  The draw is biased towards large priorities; its
+ * correction is the importance-sampling weight of every stored row (azg_selfplay_is_weights, below), which stays on the device for the
+ * trainer's weighted losses (azgym_train_weighted.h).
  *
  * The rule is exact by construction: any implementation gives the same bits.
  *
@@ -34,7 +35,17 @@
  *
  * Slot draw: game t under sample_index.  The same construction over the stored slots of column t in ring-slot order, with
  *     w = azg_draw(cfg.seed, tree_id_base + t, sample_index, 0, AZG_STREAM_SLOT);
- * the result is the least slot whose running sum exceeds target. */
+ * the result is the least slot whose running sum exceeds target.
+ *
+ * Importance-sampling weight of the stored row i of net k under beta: prioritised replay's (N P(i))^-beta divided by the largest such
+ * weight any stored row of the same net has.  P(i) = q_i / total_k, so N and the total cancel:
+ *     w_i = (q_min_k / q_i)^beta,   q_min_k = the least q over net k's stored rows (the set the row draw sums over).
+ * q_min_k is an integer minimum (any order).  Then, float32 with every step rounded on its own (no fused multiply-add):
+ *     beta == 0 or q_i == q_min_k:  w = 1.0f exactly;
+ *     otherwise  r = (float)((double)q_min_k / (double)q_i)  (both at most 2^40: the conversions are exact, the division is rounded once,
+ *     then once more to float32) and w = azg_expf(beta * azg_logf(r)).
+ * Every w lies in [0, 1] and is whatever azg_expf returns, an underflow for a large beta included.  Normalised by the ring's minimum,
+ * not by a minibatch's maximum, a row's weight does not depend on what else was drawn. */
 #ifndef AZGYM_PRIORITY_H
 #define AZGYM_PRIORITY_H
 #include "azgym_nstep.h"
@@ -85,6 +96,24 @@ int azg_selfplay_sample_rows(azg_engine* e, const azg_sample_config* cfg, int32_
 /* One slot draw per game into the host array slots [n_trees]: what azg_selfplay_reanalyse takes as its per-game slots.  The same
  * staleness rule and refusals as azg_selfplay_sample_rows. */
 int azg_selfplay_sample_slots(azg_engine* e, uint32_t sample_index, int32_t* slots);
+
+/* Write the importance-sampling weight w (the rule above) of every stored row into a device array [capacity_steps][n_trees] float32,
+ * slot-aligned with the rows and with q, and nothing else.  Asynchronous like azg_selfplay_priorities: the per-net minimum in two
+ * launches, then one thread per stored row.  The first call allocates the array and the minima (AZG_E_DEVICE if that fails: nothing is
+ * launched); it goes where q goes (keep_priorities(0) drops it, the next begin frees it).  Refusals, before any launch and with the
+ * array untouched: azg_selfplay_sample_rows' staleness rule and codes (no begin, no keep_priorities, no azg_selfplay_priorities since
+ * the ring's set of stored rows last changed, an empty ring: AZG_E_STATE); beta negative or not finite: AZG_E_INVALID. */
+int azg_selfplay_is_weights(azg_engine* e, float beta);
+
+/* The device pointer of that array, for a trainer on the same GPU (azg_trainer_epoch_opt_weighted over the ring: the array is addressed
+ * like the rows, with a row length of 1).  AZG_E_STATE without keep_priorities, and if no weights were computed since the set of stored
+ * rows last changed or since the last azg_selfplay_priorities (a step, a clear, a begin or new priorities invalidate them; a reanalysis
+ * or an n-step call does not). */
+int azg_selfplay_is_weights_device(azg_engine* e, const float** w);
+
+/* The stored rows' weights as the array holds them, ordered like azg_selfplay_rows.  Returns the number of rows copied.  Synchronises
+ * the engine's stream.  AZG_E_STATE without keep_priorities or before the first azg_selfplay_is_weights. */
+int azg_selfplay_is_weight_values(azg_engine* e, float* w, size_t max_rows);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,9 @@ label to its .Lfunc_end, the kernel descriptor (.amdhsa_ block: registers, LDS, 
 Before the comparison comments are dropped, basic-block labels are renumbered in order of appearance (their numbers count the
 functions of the file) and the `.text` / `.section .text.<name>,...,comdat` line that follows a kernel is dropped (an instantiation
 lives in a comdat section).  With --renamed OLD=NEW (mangled names, repeatable) a kernel that was renamed is compared with its
-successor, the kernel's own name replaced by KERNEL on both sides.  Exit status 1 on any difference."""
+successor, the kernel's own name replaced by KERNEL on both sides.  With --added-ok a kernel that only the second file has is
+listed as added and is not a difference (a change that adds kernels beside the ones it must leave alone).  Exit status 1 on any
+difference."""
 import difflib
 import re
 import sys
@@ -45,9 +47,11 @@ def kernels(path):
 
 
 def main():
-    args, renamed = [], {}
+    args, renamed, added_ok = [], {}, False
     for arg in sys.argv[1:]:
-        if arg.startswith("--renamed="):
+        if arg == "--added-ok":
+            added_ok = True
+        elif arg.startswith("--renamed="):
             old, new = arg[len("--renamed="):].split("=")
             renamed[old] = new
         elif arg != "--renamed":
@@ -73,6 +77,9 @@ def main():
                     print("    " + ln)
     for name in kb:
         if name not in ka and name not in renamed.values():
+            if added_ok:
+                print(f"{name}\n    absent from the first file: added")
+                continue
             bad += 1
             print(f"{name}\n    absent from the first file: DIFFERENT")
     print(f"{len(ka)} / {len(kb)} kernels, {bad} different")
