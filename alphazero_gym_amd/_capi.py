@@ -476,6 +476,7 @@ class Engine:
 
     last_rollout_info = None   # what the last policy_rollout ran as (azg_rollout_info as a dict)
     last_eval_info = None      # what the last population_mlp_eval* ran as (azg_eval_info as a dict)
+    _sp_cap = 0                # the replay ring's capacity in steps (selfplay_begin; 0: no begin yet, the engine refuses the ring's calls)
 
     def __init__(self, fns, *, env_id, mode, n_trees, n_sims, c_uct, gamma, epsilon=0.0, num_actions=0, c_pw=1.0,
                  kappa=0.5, v_target="off_policy", reward_scale=PENDULUM_R_SCALE, action_bound=2.0, seed=34,
@@ -912,14 +913,21 @@ def _selfplay_methods():
         """One search + final action + env step + bookkeeping for all games, entirely on the device (asynchronous)."""
         self._check(self._f["selfplay_step"](self._h))
 
+    def _ring_download(self, fn, columns, *extra):
+        """The ring's row-aligned downloads: fn(engine, one array per column..., max_rows, extra...) fills arrays that hold the ring's
+        capacity in rows and returns the stored rows n; the arrays' first n rows, in order.  columns: (dtype, ctypes type, shape of a
+        row).  Before any begin the capacity is 0: nothing to hold, the engine refuses."""
+        cap = self._sp_cap * self.n_trees
+        arrays = [np.empty((cap,) + tuple(shape), dt) for dt, _, shape in columns]
+        n = fn(self._h, *(_ptr(a, ct) for a, (_, ct, _) in zip(arrays, columns)), cap, *extra)
+        if n < 0:
+            self._check(n)
+        return [a[:n] for a in arrays]
+
     def selfplay_rows(self, clear=True):
         """Replay rows [steps*B, row_len] float32 of the steps since the last clear: obs | actions[K] | counts[K] | Q[K] | V."""
         rl = self._f["selfplay_row_len"](self._h)
-        rows = np.empty((self._sp_cap * self.n_trees, rl), np.float32)
-        n = self._f["selfplay_rows"](self._h, _ptr(rows, C.c_float), rows.shape[0], int(bool(clear)))
-        if n < 0:
-            self._check(n)
-        return rows[:n]
+        return _ring_download(self, self._f["selfplay_rows"], [(np.float32, C.c_float, (rl,))], int(bool(clear)))[0]
 
     def selfplay_clear(self):
         """ReplayBuffer.clear (buffers.py:56-60) for the device ring, without downloading anything."""
@@ -941,12 +949,7 @@ def _selfplay_methods():
 
     def selfplay_states(self):
         """The kept env states of the stored steps, [steps*B, S_env] float64, ordered like selfplay_rows."""
-        fn = self._optional("selfplay_states")
-        states = np.empty((self._sp_cap * self.n_trees, self.s_env), np.float64)
-        n = fn(self._h, _ptr(states, C.c_double), states.shape[0])
-        if n < 0:
-            self._check(n)
-        return states[:n]
+        return _ring_download(self, self._optional("selfplay_states"), [(np.float64, C.c_double, (self.s_env,))])[0]
 
     def selfplay_reanalyse(self, slots=None, search_index=0):
         """azg_selfplay_reanalyse: search stored positions again with the current weights and settings, under RNG search index
@@ -971,15 +974,8 @@ def _selfplay_methods():
         """The kept transitions of the stored steps, ordered like selfplay_rows: a dict of [steps*B] arrays "reward" float64 (in a
         tree node's units: continuous mode divided by reward_scale), "value" float64 (the value target before its rounding to the
         row), "action" float32 and "end" int32 (END_NONE / END_TERMINAL / END_LENGTH)."""
-        fn = self._optional("selfplay_transitions")
-        cap = getattr(self, "_sp_cap", 0) * self.n_trees   # (before any begin: nothing to hold, the engine refuses)
-        d = dict(reward=np.empty(cap, np.float64), value=np.empty(cap, np.float64), action=np.empty(cap, np.float32),
-                 end=np.empty(cap, np.int32))
-        n = fn(self._h, _ptr(d["reward"], C.c_double), _ptr(d["value"], C.c_double), _ptr(d["action"], C.c_float),
-               _ptr(d["end"], C.c_int32), cap)
-        if n < 0:
-            self._check(n)
-        return {k: v[:n] for k, v in d.items()}
+        columns = [(np.float64, C.c_double, ()), (np.float64, C.c_double, ()), (np.float32, C.c_float, ()), (np.int32, C.c_int32, ())]
+        return dict(zip(("reward", "value", "action", "end"), _ring_download(self, self._optional("selfplay_transitions"), columns)))
 
     def selfplay_nstep_targets(self, n_step, gamma=None):
         """azg_selfplay_nstep_targets: rewrite every stored row's V_target column as the n-step return of its game column from the
@@ -1008,7 +1004,7 @@ def _selfplay_methods():
         c.alpha, c.eps = float(alpha), float(eps)
         if given is not None:
             given = np.ascontiguousarray(given, np.float32).reshape(-1)
-            size = self.selfplay_ring()[0] if getattr(self, "_sp_cap", 0) else 0
+            size = self.selfplay_ring()[0] if self._sp_cap else 0
             if given.shape[0] != size * self.n_trees:
                 raise ValueError(f"given: one entry per stored row ({size * self.n_trees}), got {given.shape[0]}")
             c.given = _ptr(given, C.c_float)
@@ -1016,12 +1012,7 @@ def _selfplay_methods():
 
     def selfplay_priority_values(self):
         """The stored rows' priorities as the draws see them: uint64 [steps*B] with 20 fractional bits, ordered like selfplay_rows."""
-        fn = self._optional("selfplay_priority_values")
-        q = np.empty(getattr(self, "_sp_cap", 0) * self.n_trees, np.uint64)
-        n = fn(self._h, _ptr(q, C.c_uint64), q.shape[0])
-        if n < 0:
-            self._check(n)
-        return q[:n]
+        return _ring_download(self, self._optional("selfplay_priority_values"), [(np.uint64, C.c_uint64, ())])[0]
 
     def selfplay_sample_rows(self, n_order, sample_index):
         """azg_selfplay_sample_rows: ``n_order`` row numbers per net drawn in proportion to the priorities, with replacement, on the
@@ -1056,12 +1047,7 @@ def _selfplay_methods():
 
     def selfplay_is_weight_values(self):
         """The stored rows' weights as the array holds them: float32 [steps*B], ordered like selfplay_rows."""
-        fn = self._optional("selfplay_is_weight_values")
-        w = np.empty(getattr(self, "_sp_cap", 0) * self.n_trees, np.float32)
-        n = fn(self._h, _ptr(w, C.c_float), w.shape[0])
-        if n < 0:
-            self._check(n)
-        return w[:n]
+        return _ring_download(self, self._optional("selfplay_is_weight_values"), [(np.float32, C.c_float, ())])[0]
 
     for fn in (selfplay_begin, population_selfplay_begin, selfplay_ring, selfplay_rows_device, selfplay_step, selfplay_rows, selfplay_clear, selfplay_stats,
                selfplay_keep_states, selfplay_states, selfplay_reanalyse, selfplay_keep_transitions, selfplay_transitions,

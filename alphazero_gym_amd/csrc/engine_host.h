@@ -1,9 +1,9 @@
 // engine_host.h -- the engine object behind the C ABI, the helpers its translation units share, the host-side rules every kernel form
 // shares, and the entry points of the kernel translation units.  The C ABI: azg_engine.hip (creation, roots, search, results, dump,
-// info), engine_weights.hip (weight re-layout, populations), engine_selfplay.hip (device self-play, the results kernel's launch),
-// engine_selftest.hip (probes), dispatch_rollout.hip (policy rollouts, with their kernel), dispatch_population_eval.hip (a population's
-// batched inference, with its kernel).  The search kernels are compiled in several translation units (dispatch_*.hip: one family of template
-// instantiations each) so that the library builds in parallel.
+// info), engine_weights.hip (weight re-layout, populations), engine_selfplay.hip (device self-play on the engine's one ReplayRing,
+// replay_ring.h; search rollouts; the results kernel's launch), engine_selftest.hip (probes), dispatch_rollout.hip (policy rollouts, with
+// their kernel), dispatch_population_eval.hip (a population's batched inference, with its kernel).  The search kernels are compiled in
+// several translation units (dispatch_*.hip: one family of template instantiations each) so that the library builds in parallel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,7 @@
 
 #include "hip_host.h"
 #include "records.h"
+#include "replay_ring.h"
 #include "../../include/azgym_population.h"
 
 // diagnostic switches (environment variables, read once when the engine is created): force the other code paths in tests
@@ -105,39 +106,7 @@ struct azg_engine : EngineQueue {
     char* d_res_block = nullptr; PinnedBlock h_res;   // ... and its pinned host mirror
     double* d_roots = nullptr; int* d_carry = nullptr;
     uint32_t search_idx = 0;
-    int sp_on = 0, sp_max_len = 0, sp_det = 0, sp_cap = 0, sp_steps = 0, sp_row = 0;   // sp_steps = ReplayBuffer.size in steps
-    int sp_insert = 0, sp_fs = 0, sp_ring = 0;   // ReplayBuffer.insert_index in steps; final selection; ring mode
-    long long sp_total = 0;          // steps played since begin
-    double sp_agent_eps = 0.0;
-    double* d_sp_ctab = nullptr;
-    uint32_t sp_step_idx = 0;
-    int* d_sp_t = nullptr; int* d_sp_episode = nullptr; int* d_sp_fcnt = nullptr; double* d_sp_ret = nullptr; double* d_sp_fsum = nullptr;
-    float* d_sp_rows = nullptr;
-    // azg_selfplay_keep_states: the stored steps' env states beside the rows [sp_cap][n_trees][S_env] (NULL: not kept; _mem: the allocation), and what a
-    // reanalysis searches from: staging roots [n_trees][S_env], zero carried counts and the device copy of its slots [n_trees]
-    double* d_sp_states = nullptr; double* d_sp_states_mem = nullptr; double* d_ra_roots = nullptr; int* d_ra_carry = nullptr; int* d_ra_slots = nullptr;
-    std::vector<int32_t> ra_slots;   // host side of d_ra_slots (outlives the asynchronous copy)
-    // azg_selfplay_keep_transitions: the stored steps' reward, float64 value target, action and end kind beside the rows, each
-    // [sp_cap][n_trees] (sp_tr_on 0: not kept; the allocations stay until the next begin)
-    int sp_tr_on = 0;
-    double* d_sp_tr_reward = nullptr; double* d_sp_tr_value = nullptr; float* d_sp_tr_action = nullptr; int* d_sp_tr_end = nullptr;
-    // azg_selfplay_keep_priorities (azgym_priority.h): a priority q per stored row [sp_cap][n_trees] (sp_prio_on 0: not kept; the
-    // allocations stay until the next begin), the upload of a caller's d [sp_cap][n_trees], the draws' prefix sums (within a segment
-    // [sp_cap][n_trees], segment totals [sp_prio_segs]) and the drawn slots [n_trees]
-    int sp_prio_on = 0;
-    unsigned long long* d_sp_prio_q = nullptr; float* d_sp_prio_given = nullptr; unsigned long long* d_sp_prio_within = nullptr;
-    unsigned long long* d_sp_prio_seg = nullptr; int* d_sp_prio_slots = nullptr;
-    size_t sp_prio_segs = 0;
-    std::vector<float> prio_given;   // host side of d_sp_prio_given (outlives the asynchronous copy)
-    // sp_rows_gen counts the changes of the ring's set of stored rows (a step, a clear, a begin); sp_prio_gen: its value when
-    // azg_selfplay_priorities last ran (-1: never since the begin or since priorities were switched on)
-    long long sp_rows_gen = 0, sp_prio_gen = -1;
-    // azg_selfplay_is_weights: the weight of every stored row [sp_cap][n_trees] and the minima of q (a partial minimum per scan segment
-    // [sp_prio_segs], then one per net [n_trees]), allocated by the first call; sp_isw_gen: sp_rows_gen when the weights were last
-    // computed from the priorities that stand (-1: never, or azg_selfplay_priorities has run since)
-    float* d_sp_isw = nullptr; unsigned long long* d_sp_isw_min = nullptr;
-    long long sp_isw_gen = -1;
-    DeviceAllocs sp_mem;
+    ReplayRing ring;                 // device self-play: the replay ring, its books, game settings and kept columns (replay_ring.h)
     DeviceBuffer sp_order_buf;       // azg_selfplay_sample_rows: the drawn row numbers [n_nets][n_order] (grow-only)
     DeviceBuffer sr_buf, sr_ctab;    // azg_search_rollout: its roots, carried counts, books and outputs in one block; its (c / m)^temperature table (grow-only)
     unsigned* d_team_cnt = nullptr; size_t team_cnt_bytes = 0;   // team kernel: hand-off counters + abort word

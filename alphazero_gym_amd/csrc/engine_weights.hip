@@ -311,7 +311,7 @@ int azg_set_population(azg_engine* e, int32_t n_nets) {
     if (!e) return AZG_E_INVALID;
     if (n_nets < 1 || n_nets > e->cfg.n_trees || e->cfg.n_trees % n_nets != 0)
         return fail(e, AZG_E_INVALID, "azg_set_population: n_nets must divide n_trees (trees k*T .. k*T+T-1 belong to net k, T = n_trees / n_nets)");
-    if (e->sp_on) return fail(e, AZG_E_UNSUPPORTED, "azg_set_population: device self-play is running on this engine (one network per engine)");
+    if (e->ring.on) return fail(e, AZG_E_UNSUPPORTED, "azg_set_population: device self-play is running on this engine (one network per engine)");
     if (n_nets == e->n_nets) return AZG_OK;
     ON_DEVICE(e);
     HIPCHK(e, hipStreamSynchronize(e->stream));

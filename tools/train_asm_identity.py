@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Compare the trainer kernels' gfx950 device assembly of two builds, kernel by kernel (no GPU needed):
+"""Compare the kernels' gfx950 device assembly of two builds of one translation unit, kernel by kernel (no GPU needed); written for the
+trainer's units, it takes any two .s files:
     hipcc <the Makefile's HIPFLAGS> -S --cuda-device-only -o parent.s alphazero_gym_amd/csrc/dispatch_train.hip     (in a checkout of the parent)
     hipcc <the Makefile's HIPFLAGS> -S --cuda-device-only -o change.s alphazero_gym_amd/csrc/dispatch_train.hip     (in this tree)
     python tools/train_asm_identity.py parent.s change.s
-(likewise dispatch_train_wide.hip).  Every kernel of either file -- every symbol with an .amdhsa_kernel block -- is compared with
+(likewise dispatch_train_wide.hip, engine_selfplay.hip, ...).  Every kernel of either file -- every symbol with an .amdhsa_kernel block -- is compared with
 the kernel of the same mangled name in the other; a kernel that only one file has is a difference.  A kernel's text runs from its
 label to its .Lfunc_end, the kernel descriptor (.amdhsa_ block: registers, LDS, kernarg size) included.
 Before the comparison comments are dropped, basic-block labels are renumbered in order of appearance (their numbers count the
