@@ -119,6 +119,30 @@ class AzgSampleConfig(C.Structure):
 PRIO_VALUE_GAP, PRIO_GIVEN = 0, 1   # AZG_PRIO_*: a row's priority from |search value - V_target|, or from the caller's array
 
 
+class AzgTrainedPriorityConfig(C.Structure):
+    """include/azgym_priority.h: azg_trained_priority_config"""
+    _fields_ = [("struct_size", C.c_int32), ("unseen", C.c_int32), ("alpha", C.c_float), ("eps", C.c_float), ("unseen_d", C.c_float)]
+
+
+UNSEEN_MAX, UNSEEN_VALUE_GAP, UNSEEN_CONSTANT = 0, 1, 2   # AZG_UNSEEN_*: the d of a row never trained on since it was stored
+ERR_UNSEEN = np.float32(-1.0)                             # ... and its entry in the kept errors
+
+
+def unseen_mode(feedback):
+    """(AZG_UNSEEN_*, unseen_d) of a ``feedback`` setting: "max", "value_gap" or a finite number >= 0 (the constant d)."""
+    if isinstance(feedback, str):
+        modes = {"max": UNSEEN_MAX, "value_gap": UNSEEN_VALUE_GAP}
+        if feedback not in modes:
+            raise ValueError(f"feedback: \"max\", \"value_gap\" or a number >= 0, got {feedback!r}")
+        return modes[feedback], 0.0
+    if isinstance(feedback, bool) or not isinstance(feedback, (int, float, np.integer, np.floating)):
+        raise ValueError(f"feedback: \"max\", \"value_gap\" or a number >= 0, got {feedback!r}")
+    d = float(feedback)
+    if not (d >= 0.0 and np.isfinite(d)):
+        raise ValueError(f"feedback: the constant d of unseen rows must be finite and >= 0, got {feedback!r}")
+    return UNSEEN_CONSTANT, d
+
+
 class AzgSearchRolloutConfig(C.Structure):
     """include/azgym_search_rollout.h: azg_search_rollout_config"""
     _fields_ = [("struct_size", C.c_int32), ("episodes_per_game", C.c_int32), ("max_episode_length", C.c_int32),
@@ -162,6 +186,8 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "selfplay_keep_transitions", "selfplay_transitions", "selfplay_nstep_targets",
                     "selfplay_keep_priorities", "selfplay_priorities", "selfplay_priority_values", "selfplay_sample_rows",
                     "selfplay_sample_slots", "selfplay_is_weights", "selfplay_is_weights_device", "selfplay_is_weight_values",
+                    "selfplay_keep_errors", "selfplay_errors_device", "selfplay_error_values", "selfplay_set_error_values",
+                    "selfplay_priorities_trained",
                     "policy_rollout", "policy_rollout_ex", "search_rollout",
                     "population_mlp_eval", "population_mlp_eval_device", "population_root_eval",
                     "trainer_create", "trainer_destroy", "trainer_last_error", "trainer_param_count", "trainer_forward",
@@ -170,7 +196,8 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "trainer_create_wide_ex",
                     "trainer_backward_step_nets", "trainer_loss_nets", "trainer_step_nets", "trainer_epoch_nets",
                     "trainer_loss_weighted", "trainer_loss_nets_weighted", "trainer_step_opt_weighted", "trainer_step_nets_weighted",
-                    "trainer_epoch_opt_weighted", "trainer_epoch_nets_weighted"]
+                    "trainer_epoch_opt_weighted", "trainer_epoch_nets_weighted",
+                    "trainer_loss_errors", "trainer_loss_nets_errors", "trainer_epoch_opt_errors", "trainer_epoch_nets_errors"]
 
 
 class AzgNetSearch(C.Structure):
@@ -336,6 +363,12 @@ def bind(lib, prefix):
         f["selfplay_is_weights"].argtypes = [vp, C.c_float]
         f["selfplay_is_weights_device"].argtypes = [vp, C.POINTER(C.c_void_p)]
         f["selfplay_is_weight_values"].argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
+    if "selfplay_priorities_trained" in f:   # include/azgym_priority.h: priorities fed back from the trainer's value errors
+        f["selfplay_keep_errors"].argtypes = [vp, C.c_int32]
+        f["selfplay_errors_device"].argtypes = [vp, C.POINTER(C.c_void_p)]
+        f["selfplay_error_values"].argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
+        f["selfplay_set_error_values"].argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
+        f["selfplay_priorities_trained"].argtypes = [vp, C.POINTER(AzgTrainedPriorityConfig)]
     if "search_rollout" in f:   # include/azgym_search_rollout.h
         f["search_rollout"].argtypes = [vp, C.POINTER(AzgSearchRolloutConfig), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.POINTER(AzgSearchRolloutInfo)]
@@ -395,6 +428,12 @@ def bind(lib, prefix):
         f["trainer_loss_weighted"].argtypes = f["trainer_loss_nets_weighted"].argtypes = with_weights("trainer_loss", 5)
         f["trainer_step_opt_weighted"].argtypes = f["trainer_step_nets_weighted"].argtypes = with_weights("trainer_step_opt", 6)
         f["trainer_epoch_opt_weighted"].argtypes = f["trainer_epoch_nets_weighted"].argtypes = with_weights("trainer_epoch_opt", 3)
+    if "trainer_loss_errors" in f:   # include/azgym_train_errors.h: the weighted prototype with `errors` after `weights`
+        def with_errors(name, at):
+            args = list(f[name].argtypes)
+            return args[:at] + [vp] + args[at:]
+        f["trainer_loss_errors"].argtypes = f["trainer_loss_nets_errors"].argtypes = with_errors("trainer_loss_weighted", 6)
+        f["trainer_epoch_opt_errors"].argtypes = f["trainer_epoch_nets_errors"].argtypes = with_errors("trainer_epoch_opt_weighted", 4)
     return f
 
 
@@ -1049,6 +1088,40 @@ def _selfplay_methods():
         """The stored rows' weights as the array holds them: float32 [steps*B], ordered like selfplay_rows."""
         return _ring_download(self, self._optional("selfplay_is_weight_values"), [(np.float32, C.c_float, ())])[0]
 
+    def selfplay_keep_errors(self, on=True):
+        """azg_selfplay_keep_errors: keep the trainer's value error per stored row beside the priorities (-1: never trained on since
+        it was stored); every step then resets the entries of the slot it stores into.  Needs selfplay_keep_priorities."""
+        self._check(self._optional("selfplay_keep_errors")(self._h, int(bool(on))))
+
+    def selfplay_errors_device(self):
+        """azg_selfplay_errors_device: the device address of the errors [capacity_steps, n_trees] float32, for a trainer on the same
+        GPU to write (PopulationTrainer.train_epoch_ring(errors=True))."""
+        ptr = C.c_void_p()
+        self._check(self._optional("selfplay_errors_device")(self._h, C.byref(ptr)))
+        return int(ptr.value)
+
+    def selfplay_error_values(self):
+        """The stored rows' errors as the array holds them: float32 [steps*B], ordered like selfplay_rows."""
+        return _ring_download(self, self._optional("selfplay_error_values"), [(np.float32, C.c_float, ())])[0]
+
+    def selfplay_set_error_values(self, err):
+        """azg_selfplay_set_error_values: upload one error per stored row, ordered like selfplay_rows; every entry -1, NaN or >= 0."""
+        err = np.ascontiguousarray(err, np.float32).reshape(-1)
+        self._check(self._optional("selfplay_set_error_values")(self._h, _ptr(err, C.c_float), err.shape[0]))
+
+    def selfplay_priorities_trained(self, alpha, eps, unseen="max"):
+        """azg_selfplay_priorities_trained: the priority of every stored row from the kept errors, (d + eps)^alpha in fixed point with
+        d the row's error; a row never trained on takes ``unseen``: "max" (the largest seen error of its net, 1 if none),
+        "value_gap" (|kept search value - V_target|, needs selfplay_keep_transitions) or a constant d >= 0.  Asynchronous."""
+        c = AzgTrainedPriorityConfig()
+        c.struct_size = C.sizeof(AzgTrainedPriorityConfig)
+        c.unseen, c.unseen_d = unseen_mode(unseen)
+        c.alpha, c.eps = float(alpha), float(eps)
+        self._check(self._optional("selfplay_priorities_trained")(self._h, C.byref(c)))
+
+    for fn in (selfplay_keep_errors, selfplay_errors_device, selfplay_error_values, selfplay_set_error_values, selfplay_priorities_trained):
+        setattr(Engine, fn.__name__, fn)
+
     for fn in (selfplay_begin, population_selfplay_begin, selfplay_ring, selfplay_rows_device, selfplay_step, selfplay_rows, selfplay_clear, selfplay_stats,
                selfplay_keep_states, selfplay_states, selfplay_reanalyse, selfplay_keep_transitions, selfplay_transitions,
                selfplay_nstep_targets, selfplay_keep_priorities, selfplay_priorities, selfplay_priority_values, selfplay_sample_rows,
@@ -1364,6 +1437,33 @@ class Trainer:
         carr, oarr = self._entries("epoch_nets_weighted", cfgs, AzgLossCfg), self._entries("epoch_nets_weighted", opts, AzgOptim)
         return self._epoch("trainer_epoch_nets_weighted", "epoch_nets_weighted", params, rows, order, batch_size, carr, alpha, (oarr,),
                            loss_sums, (weights or None,))
+
+    # ---- value errors out of the loss launch (include/azgym_train_errors.h): the weighted namesake with ``errors``, a device
+    # address of float32 that receives |V - z| of every row; ``weights`` may be None (unweighted) ----
+
+    def loss_errors(self, raw, actions, counts, values, weights, errors, n_rows, n_actions, cfg, alpha, d_raw, losses):
+        """azg_trainer_loss_errors: ``loss_weighted`` that also writes errors [n_nets, n_rows]."""
+        self._loss("trainer_loss_errors", raw, actions, counts, values, n_rows, n_actions, _ref(cfg), alpha, d_raw, losses,
+                   (weights or None, errors or None))
+
+    def loss_nets_errors(self, raw, actions, counts, values, weights, errors, n_rows, n_actions, cfgs, alpha, d_raw, losses):
+        """azg_trainer_loss_nets_errors: ``loss_nets_weighted`` that also writes errors [n_nets, n_rows]."""
+        arr = self._entries("loss_nets_errors", cfgs, AzgLossCfg)
+        self._loss("trainer_loss_nets_errors", raw, actions, counts, values, n_rows, n_actions, arr, alpha, d_raw, losses,
+                   (weights or None, errors or None))
+
+    def epoch_opt_errors(self, params, rows, weights, errors, order, batch_size, cfg, alpha, opt, loss_sums):
+        """azg_trainer_epoch_opt_errors: ``epoch_opt_weighted`` whose loss launches also write every trained row's error into
+        ``errors``, addressed like ``weights``: [n_nets, rows_per_net] beside a plain rows array, [capacity_steps, n_trees] beside
+        the self-play ring (``Engine.selfplay_errors_device``).  Rows not drawn keep their entries."""
+        return self._epoch("trainer_epoch_opt_errors", "epoch_opt_errors", params, rows, order, batch_size, _ref(cfg), alpha,
+                           (_ref(opt),), loss_sums, (weights or None, errors or None))
+
+    def epoch_nets_errors(self, params, rows, weights, errors, order, batch_size, cfgs, alpha, opts, loss_sums):
+        """azg_trainer_epoch_nets_errors: ``epoch_nets_weighted`` that also writes the trained rows' errors."""
+        carr, oarr = self._entries("epoch_nets_errors", cfgs, AzgLossCfg), self._entries("epoch_nets_errors", opts, AzgOptim)
+        return self._epoch("trainer_epoch_nets_errors", "epoch_nets_errors", params, rows, order, batch_size, carr, alpha, (oarr,),
+                           loss_sums, (weights or None, errors or None))
 
     def read_d_raw(self, n_rows, d_raw):
         """azg_trainer_read_d_raw: the last ``step``'s d_raw [n_nets, n_rows, 1 + n_dist] into the caller's device array."""

@@ -531,17 +531,18 @@ class PopulationTrainer:
         self._call("backward_step", (self.flat.data_ptr(), d_raw.data_ptr(), B), (grads,))
         return out
 
-    def _call(self, family: str, head: tuple, tail: tuple, weighted: bool = False):
+    def _call(self, family: str, head: tuple, tail: tuple, weighted: bool = False, errors: bool = False):
         """The trainer's ``family`` call in this trainer's form: ``head``, the optimiser's arguments, ``tail``.  Counts the steps it
         took (an epoch returns their number).  ``weighted``: the ``*_weighted`` method of the form (``head`` carries the weights);
-        the azg_rmsprop family has none, and its trainer calls ``*_opt_weighted`` with the same RMSprop and no clip: the same bits."""
-        if weighted:
+        the azg_rmsprop family has none, and its trainer calls ``*_opt_weighted`` with the same RMSprop and no clip: the same bits.
+        ``errors``: the ``*_errors`` method likewise (``head`` carries the weights, or None, and the errors)."""
+        if weighted or errors:
             suffix, opt_args = self._form.suffix, self._form.opt_args()
             if not suffix:
                 o = self.opt
                 suffix, opt_args = "_opt", (_capi.optim("rmsprop", o.lr, self.square_avg.data_ptr(), eps=o.eps,
                                                         weight_decay=o.weight_decay, alpha=o.alpha),)
-            n_steps = getattr(self.trainer, family + suffix + "_weighted")(*head, *opt_args, *tail)
+            n_steps = getattr(self.trainer, family + suffix + ("_errors" if errors else "_weighted"))(*head, *opt_args, *tail)
         else:
             n_steps = getattr(self.trainer, family + self._form.suffix)(*head, *self._form.opt_args(), *tail)
         if self._form.counts_steps:
@@ -674,9 +675,11 @@ class PopulationTrainer:
             i = j
         return sums
 
-    def _epoch(self, who: str, where, order: np.ndarray, batch_size: int, weights: Optional[int] = None) -> List[Dict[str, float]]:
+    def _epoch(self, who: str, where, order: np.ndarray, batch_size: int, weights: Optional[int] = None,
+               errors: Optional[int] = None) -> List[Dict[str, float]]:
         """azg_trainer_epoch on rows described by ``where`` (``_capi.epoch_rows``), their producers complete; the per-net sums.
-        ``weights``: the device address of a float32 array addressed like the rows (None: the unweighted epoch)."""
+        ``weights``: the device address of a float32 array addressed like the rows (None: the unweighted epoch).  ``errors``: the
+        device address of a float32 array addressed like them that receives the trained rows' value errors (None: none)."""
         K = len(self.agents)
         bounds = minibatch_bounds(order.shape[1], int(batch_size))
         if not bounds or max(j - i for i, j in bounds) > self.max_batch:
@@ -687,8 +690,10 @@ class PopulationTrainer:
                                   self.alpha_exp_avg_sq.data_ptr()) if tuned else None
         torch.cuda.current_stream(self.device).synchronize()
         w = () if weights is None else (weights,)
+        if errors is not None:
+            w = (weights, errors)
         n_steps = self._call("epoch", (self.flat.data_ptr(), where, *w, order, int(batch_size), self._form.cfg(), state),
-                             (sums.data_ptr(),), weighted=weights is not None)
+                             (sums.data_ptr(),), weighted=weights is not None, errors=errors is not None)
         assert n_steps == len(bounds)
         if tuned:
             self.alpha_step += n_steps
@@ -698,12 +703,14 @@ class PopulationTrainer:
         return [{key: row[i] for key, i in slots} for row in table]
 
     def train_epoch(self, rows_per_net, state_dim: int, K: int, batch_size: int = 32,
-                    shuffle_seeds: Optional[Sequence[int]] = None, weights=None) -> List[Dict[str, float]]:
+                    shuffle_seeds: Optional[Sequence[int]] = None, weights=None, errors=None) -> List[Dict[str, float]]:
         """``train_on_rows`` as one native call (``azg_trainer_epoch``): the same arguments, minibatches, arithmetic and return
         value, bit for bit, with one synchronisation for the whole epoch.  The permutations are built on the host as there; the
         minibatches are gathered from ``rows_per_net`` on the device (a [K, n, row] float32 tensor on the trainer's GPU is read in
         place).  Needs ``losses="device"``; ``grads`` (``keep_grads``) is not written.  ``weights``: a [K, n] float32 tensor, one
-        weight per row, gathered with the row (azg_trainer_epoch_opt_weighted); None is the unweighted epoch."""
+        weight per row, gathered with the row (azg_trainer_epoch_opt_weighted); None is the unweighted epoch.  ``errors``: a
+        contiguous [K, n] float32 tensor on the trainer's GPU that receives the value error |V - z| of every row trained on, written
+        by the minibatches' loss launches (azg_trainer_epoch_opt_errors); entries of rows not drawn stay as they are."""
         _need_device_losses(self.losses, "train_epoch")
         rows = rows_per_net if isinstance(rows_per_net, torch.Tensor) else torch.stack(list(rows_per_net))
         rows = rows.to(self.device, dtype=torch.float32).contiguous()
@@ -716,10 +723,14 @@ class PopulationTrainer:
         order = np.stack([np.random.RandomState(int(s)).permutation(n) for s in seeds]).astype(np.int32)
         if weights is not None:
             weights = self._row_weights("train_epoch", weights, N, n)
+        if errors is not None:
+            if not isinstance(errors, torch.Tensor) or errors.dtype != torch.float32 or errors.device != self.device or \
+                    not errors.is_contiguous() or tuple(errors.shape) != (N, n):
+                raise ValueError(f"PopulationTrainer.train_epoch: errors must be a contiguous float32 tensor [{N}, {n}] on the trainer's GPU")
         return self._epoch("train_epoch", _capi.epoch_rows(rows.data_ptr(), state_dim, K, n), order, batch_size,
-                           None if weights is None else weights.data_ptr())
+                           None if weights is None else weights.data_ptr(), None if errors is None else errors.data_ptr())
 
-    def train_epoch_ring(self, selfplay, order, batch_size: int = 32, weights=None) -> List[Dict[str, float]]:
+    def train_epoch_ring(self, selfplay, order, batch_size: int = 32, weights=None, errors: bool = False) -> List[Dict[str, float]]:
         """One epoch straight from a ``PopulationSelfPlay`` / ``DeviceSelfPlay`` engine's replay ring, with no copy of the rows and
         no index tensors on the device.  ``order``: int array [K, n_order]; order[k] numbers net k's rows of the ring as
         ``PopulationSelfPlay._split`` orders them (row i = stored step i // T, game i % T of the net's T games) -- the caller's pick
@@ -727,8 +738,15 @@ class PopulationTrainer:
 
         ``weights``: "priority" trains with the engine's importance-sampling weights (``PopulationSelfPlay.is_weights`` must have run
         since the last ``priorities``; the engine's refusal surfaces as it is); a [capacity_steps, n_games] float32 tensor on the
-        trainer's GPU gives a weight per ring slot and game; None runs the unweighted calls."""
+        trainer's GPU gives a weight per ring slot and game; None runs the unweighted calls.
+
+        ``errors``: True also writes the value error |V - z| of every row trained on into the engine's kept errors
+        (``PopulationSelfPlay(prioritized={..., "feedback": ...})``), from the minibatches' own loss launches; the next
+        ``priorities()`` of the self-play engine reads them.  A row in several minibatches keeps the last one's error."""
         _need_device_losses(self.losses, "train_epoch_ring")
+        if errors and "feedback" not in (getattr(selfplay, "prioritized", None) or {}):
+            raise ValueError('PopulationTrainer.train_epoch_ring: errors=True needs a self-play engine built with '
+                             'prioritized={..., "feedback": ...}')
         if isinstance(weights, str):
             if weights != "priority":
                 raise ValueError('PopulationTrainer.train_epoch_ring: weights must be "priority", a tensor or None')
@@ -762,8 +780,9 @@ class PopulationTrainer:
                 raise ValueError("PopulationTrainer.train_epoch_ring: weights must be a contiguous float32 tensor "
                                  "[capacity_steps, n_games] on the trainer's GPU")
             w_ptr = weights.data_ptr()
+        e_ptr = engine.selfplay_errors_device() if errors else None
         engine.sync()
-        return self._epoch("train_epoch_ring", where, order.astype(np.int32), batch_size, w_ptr)
+        return self._epoch("train_epoch_ring", where, order.astype(np.int32), batch_size, w_ptr, e_ptr)
 
     def export_alpha(self) -> None:
         """Write every net's learned temperature and its Adam state (step, exp_avg, exp_avg_sq) back into its agent's loss object,

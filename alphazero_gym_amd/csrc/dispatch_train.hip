@@ -16,6 +16,7 @@
 
 #include "../../include/azgym_train.h"
 #include "../../include/azgym_train_weighted.h"
+#include "../../include/azgym_train_errors.h"
 #include "hip_host.h"
 #include "train.cuh"
 #include "train_wide_host.h"
@@ -43,6 +44,7 @@ struct azg_trainer {
     // actions | counts [n_nets][B][A] | values [n_nets][B], laid out for max_batch rows) and the loss table [n_minibatches][n_nets][5]
     DeviceBuffer order_buf, stage_buf, loss_table;
     DeviceBuffer stage_w;        // a weighted epoch's staged weights [n_nets][max_batch]
+    DeviceBuffer stage_at;       // an errors epoch's staged element indices [n_nets][max_batch] (int64): where each row's error goes
     // the *_nets entry points': the launch-ready settings of every (minibatch, net), [M][n_nets] TrainOptD | [M][n_nets] LossDims (a
     // part the call has no entries for is empty), filled on the host for the whole call and uploaded in one copy; grown on demand
     std::vector<unsigned char> nets_host;
@@ -223,11 +225,18 @@ int azg_trainer_create_wide_ex(int32_t device_id, const azg_mlp_desc* desc, int3
 // ---- what a call launches ----
 
 // The weights argument of a call: `asked` for the *_weighted entry points (whose NULL is a refusal), w the caller's device array.
+// The *_errors entry points (azgym_train_errors.h): err_asked, whose NULL `errors` is a refusal and whose NULL w means unweighted; they
+// run the weighted path's errors kernels either way.
 struct RowWeights {
     bool asked = false;
     const float* w = nullptr;
+    bool err_asked = false;
+    float* errors = nullptr;
+    bool weighted_path() const { return asked || err_asked; }
+    bool refused() const { return (asked && !w) || (err_asked && !errors); }
 };
 static const RowWeights kNoWeights{};
+static RowWeights with_errors(const float* w, float* errors) { return RowWeights{false, w, true, errors}; }
 
 enum class OptForm { fused, deferred, table };
 
@@ -479,7 +488,7 @@ static int upload_nets(azg_trainer* t, const char* who, const TrainPlan& plan) {
 
 // the loss kernels' float64 rows: the unweighted path's three columns, or the weighted path's four in an array of its own
 static int ensure_loss_rows(azg_trainer* t, const RowWeights& wt) {
-    if (wt.asked) return ensure(t, t->loss_rows_w, (size_t)t->n_nets * 4 * t->max_batch);
+    if (wt.weighted_path()) return ensure(t, t->loss_rows_w, (size_t)t->n_nets * 4 * t->max_batch);
     return ensure(t, t->loss_rows, (size_t)t->n_nets * 3 * t->max_batch);
 }
 
@@ -491,14 +500,27 @@ static void launch_forward(azg_trainer* t, const float* params, const float* obs
 }
 
 // minibatch m's losses: with the plan's LossDims, or every net with its own entry of the table
-// (weights: [n_nets][rows] or NULL; the weighted kernels keep their rows' terms in loss_rows_w)
+// (weights: [n_nets][rows] or NULL; the weighted kernels keep their rows' terms in loss_rows_w.  errors: NULL, or where the errors
+// forms of the weighted kernels write each row's value error: errors[err_at[.]], dense with err_at NULL)
 static void launch_loss(azg_trainer* t, const TrainPlan& plan, int m, const float* raw, const float* actions, const float* counts,
-                        const float* values, const float* weights, float* d_raw, float* losses) {
+                        const float* values, const float* weights, float* d_raw, float* losses, const long long* err_at = nullptr,
+                        float* errors = nullptr) {
     const Minibatch& mb = plan.mb[m];
     const bool tuned = mb.c.kind == AZG_LOSS_A0C_TUNED;
     float* log_alpha = tuned ? plan.alpha->log_alpha : nullptr;
     float* exp_avg = tuned ? plan.alpha->exp_avg : nullptr;
     float* exp_avg_sq = tuned ? plan.alpha->exp_avg_sq : nullptr;
+    if (errors) {
+        if (plan.form == OptForm::table) {
+            const LossDims* table = reinterpret_cast<const LossDims*>((const unsigned char*)t->nets_dev.p + plan.loss_off) + (size_t)m * t->n_nets;
+            hipLaunchKernelGGL(train_loss_nets_errors_kernel, dim3(t->n_nets), dim3(TR_LOSS_THREADS), 0, t->stream, table, raw, actions, counts,
+                               values, weights, mb.rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, t->loss_rows_w, t->max_batch, err_at, errors);
+        } else {
+            hipLaunchKernelGGL(train_loss_errors_kernel, dim3(t->n_nets), dim3(TR_LOSS_THREADS), 0, t->stream, mb.c, raw, actions, counts,
+                               values, weights, mb.rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, t->loss_rows_w, t->max_batch, err_at, errors);
+        }
+        return;
+    }
     if (weights) {
         if (plan.form == OptForm::table) {
             const LossDims* table = reinterpret_cast<const LossDims*>((const unsigned char*)t->nets_dev.p + plan.loss_off) + (size_t)m * t->n_nets;
@@ -553,9 +575,10 @@ static void launch_backward(azg_trainer* t, const TrainPlan& plan, int m, float*
 
 // one minibatch: forward, losses (d_raw to d_raw_buf), backward and step
 static void launch_minibatch(azg_trainer* t, const TrainPlan& plan, int m, float* params, const float* obs, const float* actions,
-                             const float* counts, const float* values, const float* weights, float* raw, float* grads, float* losses) {
+                             const float* counts, const float* values, const float* weights, float* raw, float* grads, float* losses,
+                             const long long* err_at = nullptr, float* errors = nullptr) {
     launch_forward(t, params, obs, plan.mb[m].rows, raw);
-    launch_loss(t, plan, m, raw, actions, counts, values, weights, t->d_raw_buf, losses);
+    launch_loss(t, plan, m, raw, actions, counts, values, weights, t->d_raw_buf, losses, err_at, errors);
     launch_backward(t, plan, m, params, t->d_raw_buf, grads);
 }
 
@@ -588,7 +611,7 @@ static int loss_impl(azg_trainer* t, const char* who, OptForm form, const float*
                      const float* values, const RowWeights& wt, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* cfg,
                      const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
     if (!t) return AZG_E_INVALID;
-    if (!raw || !actions || !counts || !values || !d_raw || !losses || (wt.asked && !wt.w))
+    if (!raw || !actions || !counts || !values || !d_raw || !losses || wt.refused())
         return tfail(t, AZG_E_INVALID, std::string(who) + ": NULL pointer");
     TrainPlan plan(form, n_rows);
     plan.alpha = alpha_state;
@@ -598,7 +621,7 @@ static int loss_impl(azg_trainer* t, const char* who, OptForm form, const float*
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
     if (int rc = ensure_loss_rows(t, wt)) return rc;
     if (int rc = upload_nets(t, who, plan)) return rc;
-    launch_loss(t, plan, 0, raw, actions, counts, values, wt.w, d_raw, losses);
+    launch_loss(t, plan, 0, raw, actions, counts, values, wt.w, d_raw, losses, nullptr, wt.errors);
     return finish(t, who);
 }
 
@@ -634,7 +657,7 @@ static int epoch_impl(azg_trainer* t, const char* who, OptForm form, float* para
                       const azg_rmsprop* rms, float* square_avg, const azg_optim* opt, double* loss_sums, int32_t* n_minibatches) {
     if (!t) return AZG_E_INVALID;
     const std::string w(who);
-    if (!params || !rows || !order || !loss_cfg || !(opt || (rms && square_avg)) || !loss_sums || !n_minibatches || (wt.asked && !wt.w))
+    if (!params || !rows || !order || !loss_cfg || !(opt || (rms && square_avg)) || !loss_sums || !n_minibatches || wt.refused())
         return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
     if (rows->struct_size != (int32_t)sizeof(azg_epoch_rows)) return tfail(t, AZG_E_INVALID, w + ": azg_epoch_rows.struct_size mismatch");
     if (!rows->rows) return tfail(t, AZG_E_INVALID, w + ": NULL pointer in azg_epoch_rows");
@@ -679,7 +702,8 @@ static int epoch_impl(azg_trainer* t, const char* who, OptForm form, float* para
     if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
     const size_t mb = (size_t)t->max_batch, per = K * mb * t->net.NO, in_dim = (size_t)t->net.in_dim;
     if (int rc = ensure_loss_rows(t, wt)) return rc;
-    if (wt.asked) { if (int rc = grow(t, t->stage_w, K * mb * sizeof(float))) return rc; }
+    if (wt.weighted_path()) { if (int rc = grow(t, t->stage_w, K * mb * sizeof(float))) return rc; }
+    if (wt.err_asked) { if (int rc = grow(t, t->stage_at, K * mb * sizeof(long long))) return rc; }
     if (int rc = ensure(t, t->d_raw_buf, per)) return rc;
     if (int rc = ensure(t, t->raw_buf, per)) return rc;
     if (int rc = grow(t, t->order_buf, K * (size_t)n_order * sizeof(int32_t))) return rc;
@@ -691,7 +715,8 @@ static int epoch_impl(azg_trainer* t, const char* who, OptForm form, float* para
     float* actions = obs + K * mb * in_dim;
     float* counts = actions + K * mb * (size_t)A;
     float* values = counts + K * mb * (size_t)A;
-    float* staged_w = wt.asked ? (float*)t->stage_w.p : nullptr;
+    float* staged_w = wt.weighted_path() ? (float*)t->stage_w.p : nullptr;
+    long long* staged_at = wt.err_asked ? (long long*)t->stage_at.p : nullptr;
     GatherDims g{};
     g.row_len = rows->row_len; g.state_dim = rows->state_dim; g.A = A; g.group = rows->group; g.n_order = n_order;
     g.group_stride = rows->group_stride; g.net_stride = rows->net_stride;
@@ -703,14 +728,17 @@ static int epoch_impl(azg_trainer* t, const char* who, OptForm form, float* para
     for (int m = 0; m < M; ++m) {
         const int B = plan.mb[m].rows;
         const dim3 ggrid((B + TR_GATHER_THREADS / 64 - 1) / (TR_GATHER_THREADS / 64), t->n_nets);
-        if (wt.asked)
+        if (wt.err_asked)
+            hipLaunchKernelGGL(train_gather_errors_kernel, ggrid, dim3(TR_GATHER_THREADS), 0, t->stream, g, rows->rows, wt.w, order_dev,
+                               plan.mb[m].first, B, obs, actions, counts, values, staged_w, staged_at);
+        else if (wt.asked)
             hipLaunchKernelGGL(train_gather_weighted_kernel, ggrid, dim3(TR_GATHER_THREADS), 0, t->stream, g, rows->rows, wt.w, order_dev,
                                plan.mb[m].first, B, obs, actions, counts, values, staged_w);
         else
             hipLaunchKernelGGL(train_gather_kernel, ggrid, dim3(TR_GATHER_THREADS), 0, t->stream, g, rows->rows, order_dev, plan.mb[m].first, B,
                                obs, actions, counts, values);
         launch_minibatch(t, plan, m, params, obs, actions, counts, values, staged_w, t->raw_buf, nullptr,
-                         loss_table + (size_t)m * K * AZG_LOSS_SLOTS);
+                         loss_table + (size_t)m * K * AZG_LOSS_SLOTS, staged_at, wt.errors);
     }
     const int n_sums = t->n_nets * AZG_LOSS_SLOTS;
     hipLaunchKernelGGL(train_loss_sum_kernel, dim3((n_sums + 63) / 64), dim3(64), 0, t->stream, loss_table, M, n_sums, loss_sums);
@@ -843,6 +871,36 @@ int azg_trainer_epoch_nets_weighted(azg_trainer* t, float* params, const azg_epo
                                     int32_t n_order, int32_t batch_size, const azg_loss_cfg* loss_cfgs, const azg_alpha_state* alpha_state,
                                     const azg_optim* opts, double* loss_sums, int32_t* n_minibatches) {
     return epoch_impl(t, "azg_trainer_epoch_nets_weighted", OptForm::table, params, rows, RowWeights{true, weights}, order, n_order, batch_size,
+                      loss_cfgs, alpha_state, nullptr, nullptr, opts, loss_sums, n_minibatches);
+}
+
+// ---- the errors forms (include/azgym_train_errors.h): the weighted namesake's body, the rows' value errors written by the loss launch
+
+int azg_trainer_loss_errors(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values,
+                            const float* weights, float* errors, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* cfg,
+                            const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
+    return loss_impl(t, "azg_trainer_loss_errors", OptForm::fused, raw, actions, counts, values, with_errors(weights, errors), n_rows, n_actions,
+                     cfg, alpha_state, d_raw, losses);
+}
+
+int azg_trainer_loss_nets_errors(azg_trainer* t, const float* raw, const float* actions, const float* counts, const float* values,
+                                 const float* weights, float* errors, int32_t n_rows, int32_t n_actions, const azg_loss_cfg* cfgs,
+                                 const azg_alpha_state* alpha_state, float* d_raw, float* losses) {
+    return loss_impl(t, "azg_trainer_loss_nets_errors", OptForm::table, raw, actions, counts, values, with_errors(weights, errors), n_rows,
+                     n_actions, cfgs, alpha_state, d_raw, losses);
+}
+
+int azg_trainer_epoch_opt_errors(azg_trainer* t, float* params, const azg_epoch_rows* rows, const float* weights, float* errors,
+                                 const int32_t* order, int32_t n_order, int32_t batch_size, const azg_loss_cfg* loss_cfg,
+                                 const azg_alpha_state* alpha_state, const azg_optim* opt, double* loss_sums, int32_t* n_minibatches) {
+    return epoch_impl(t, "azg_trainer_epoch_opt_errors", OptForm::fused, params, rows, with_errors(weights, errors), order, n_order, batch_size,
+                      loss_cfg, alpha_state, nullptr, nullptr, opt, loss_sums, n_minibatches);
+}
+
+int azg_trainer_epoch_nets_errors(azg_trainer* t, float* params, const azg_epoch_rows* rows, const float* weights, float* errors,
+                                  const int32_t* order, int32_t n_order, int32_t batch_size, const azg_loss_cfg* loss_cfgs,
+                                  const azg_alpha_state* alpha_state, const azg_optim* opts, double* loss_sums, int32_t* n_minibatches) {
+    return epoch_impl(t, "azg_trainer_epoch_nets_errors", OptForm::table, params, rows, with_errors(weights, errors), order, n_order, batch_size,
                       loss_cfgs, alpha_state, nullptr, nullptr, opts, loss_sums, n_minibatches);
 }
 

@@ -1,7 +1,7 @@
 // engine_selfplay.hip -- the C ABI's device-resident self-play (azg_selfplay_*, azg_population_selfplay_begin), the reanalysis of its
 // replay ring (azgym_reanalyse.h), the ring's n-step return targets (azgym_nstep.h), its prioritised sampling (azgym_priority.h), the
 // search rollouts (azgym_search_rollout.h) and the launches of the small kernels after a search: results_kernel, the self-play step,
-// the reanalysis' gather and row kernels, the n-step target kernel, the priority, scan and draw kernels and the search rollouts' step
+// the reanalysis' gather and row kernels, the n-step target kernel, the priority, scan, draw and error-maximum kernels and the search rollouts' step
 // (aux_kernels.cuh and priority.cuh are compiled in this unit only).  The ring is the engine's one ReplayRing (replay_ring.h); what its
 // entry points share stands once, in front of them: their refusals, the row-aligned download, the keep_* calls' allocate-once, the
 // per-net partition, the launch after a search and the scoped swap of the engine's roots (reanalysis, search rollouts).
@@ -86,7 +86,7 @@ static int act_rule_ctab(azg_engine* e, double temperature, std::vector<double>&
 // ---- what the ring's entry points share
 
 // What a ring entry point refuses first: no engine, no begin, a column of `need` not kept (`why`: what the entry point adds to that)
-enum { NEED_STATES = 1, NEED_TRANSITIONS = 2, NEED_PRIORITIES = 4 };
+enum { NEED_STATES = 1, NEED_TRANSITIONS = 2, NEED_PRIORITIES = 4, NEED_ERRORS = 8 };
 static int ring_refusal(azg_engine* e, int need = 0, const char* why = "") {
     if (!e) return AZG_E_INVALID;
     const ReplayRing& r = e->ring;
@@ -94,6 +94,7 @@ static int ring_refusal(azg_engine* e, int need = 0, const char* why = "") {
     if ((need & NEED_STATES) && !r.states.on) return fail(e, AZG_E_STATE, std::string("azg_selfplay_keep_states has not been called") + why);
     if ((need & NEED_TRANSITIONS) && !r.tr.on) return fail(e, AZG_E_STATE, std::string("azg_selfplay_keep_transitions has not been called") + why);
     if ((need & NEED_PRIORITIES) && !r.prio.on) return fail(e, AZG_E_STATE, std::string("azg_selfplay_keep_priorities has not been called") + why);
+    if ((need & NEED_ERRORS) && !r.prio.err_on) return fail(e, AZG_E_STATE, std::string("azg_selfplay_keep_errors has not been called") + why);
     return AZG_OK;
 }
 
@@ -242,6 +243,8 @@ int azg_selfplay_step(azg_engine* e) {
     e->redo_ok = 0;   // (the step moves the roots on: the search that just ran cannot be re-run for a dump)
     rc = launch_after_search(e, selfplay_kernel16, selfplay_kernel, sp);
     if (rc) return rc;
+    // kept errors (azg_selfplay_keep_errors): the rows of this slot have not been trained on
+    if (r.prio.err_on) HIPCHK(e, hipMemsetD32Async((hipDeviceptr_t)(r.prio.err + at), (int)PR_ERR_UNSEEN_BITS, (size_t)e->cfg.n_trees, e->stream));
     r.stepped();
     return AZG_OK;
 }
@@ -390,7 +393,7 @@ int azg_selfplay_keep_priorities(azg_engine* e, int32_t on) {   // (at any ring 
     if (int rc = ring_refusal(e)) return rc;
     ReplayRing& r = e->ring;
     ReplayRing::Priorities& p = r.prio;
-    if (!on) p.gen = p.w_gen = -1;   // (so a switch-on finds gen -1: what was computed before is not handed out)
+    if (!on) { p.gen = p.w_gen = -1; p.err_on = 0; }   // (so a switch-on finds gen -1: what was computed before is not handed out)
     const size_t B = e->cfg.n_trees, n = (size_t)r.cap * B;
     if (on && !p.on && n >= ((size_t)1 << 31)) return fail(e, AZG_E_UNSUPPORTED, "azg_selfplay_keep_priorities: capacity_steps * n_trees must stay below 2^31 rows");
     return keep_column(e, on, &p.on, &p.q, [&] {
@@ -530,6 +533,96 @@ int azg_selfplay_is_weight_values(azg_engine* e, float* w, size_t max_rows) {
     if (int rc = ring_refusal(e, NEED_PRIORITIES)) return rc;
     if (!e->ring.prio.w) return fail(e, AZG_E_STATE, "azg_selfplay_is_weight_values: azg_selfplay_is_weights has not been called");
     return ring_download(e, max_rows, {{w, e->ring.prio.w, 4}});
+}
+
+// ---- priorities fed back from the trainer's value errors (include/azgym_priority.h)
+
+int azg_selfplay_keep_errors(azg_engine* e, int32_t on) {   // (at any ring size, like the priorities it belongs to)
+    if (int rc = ring_refusal(e, on ? NEED_PRIORITIES : 0, ": the errors are kept beside the priorities")) return rc;
+    ReplayRing& r = e->ring;
+    ReplayRing::Priorities& p = r.prio;
+    if (!on) { p.err_on = 0; return AZG_OK; }
+    if (p.err_on) return AZG_OK;
+    ON_DEVICE(e);
+    const size_t n = (size_t)r.cap * e->cfg.n_trees;
+    if (!p.err) {   // one block: the maxima's bits (int32: per scan segment, then per net) in front of the errors
+        const size_t n_max = p.segs + (size_t)e->cfg.n_trees;
+        int* block = nullptr;
+        if (dalloc(e, r.mem, &block, n_max + n)) return AZG_E_DEVICE;
+        p.err_max = block; p.err = reinterpret_cast<float*>(block + n_max);
+    }
+    HIPCHK(e, hipMemsetD32Async((hipDeviceptr_t)p.err, (int)PR_ERR_UNSEEN_BITS, n, e->stream));
+    p.err_on = 1;
+    return AZG_OK;
+}
+
+int azg_selfplay_errors_device(azg_engine* e, float** err) {
+    if (!e) return AZG_E_INVALID;
+    if (!err) return fail(e, AZG_E_INVALID, "azg_selfplay_errors_device: err must not be NULL");
+    if (int rc = ring_refusal(e, NEED_PRIORITIES | NEED_ERRORS)) return rc;
+    *err = e->ring.prio.err;
+    return AZG_OK;
+}
+
+int azg_selfplay_error_values(azg_engine* e, float* err, size_t max_rows) {
+    if (int rc = ring_refusal(e, NEED_PRIORITIES | NEED_ERRORS)) return rc;
+    return ring_download(e, max_rows, {{err, e->ring.prio.err, 4}});
+}
+
+int azg_selfplay_set_error_values(azg_engine* e, const float* err, size_t n_rows) {
+    if (!e) return AZG_E_INVALID;
+    if (!err) return fail(e, AZG_E_INVALID, "azg_selfplay_set_error_values: err must not be NULL");
+    if (int rc = ring_refusal(e, NEED_PRIORITIES | NEED_ERRORS)) return rc;
+    ReplayRing::Priorities& p = e->ring.prio;
+    const size_t n = e->ring.stored_rows();
+    if (n_rows != n) return fail(e, AZG_E_INVALID, "azg_selfplay_set_error_values: n_rows must be the stored rows (" + std::to_string(n) + ")");
+    for (size_t i = 0; i < n; ++i)
+        if (!(err[i] >= 0.0f || err[i] == PR_ERR_UNSEEN || err[i] != err[i]))
+            return fail(e, AZG_E_INVALID, "azg_selfplay_set_error_values: err[" + std::to_string(i) + "] is neither -1, NaN nor >= 0");
+    if (n == 0) return AZG_OK;
+    ON_DEVICE(e);
+    p.h_err.assign(err, err + n);
+    HIPCHK(e, hipMemcpyAsync(p.err, p.h_err.data(), n * 4, hipMemcpyHostToDevice, e->stream));
+    return AZG_OK;
+}
+
+int azg_selfplay_priorities_trained(azg_engine* e, const azg_trained_priority_config* c) {
+    if (!e) return AZG_E_INVALID;
+    if (!c) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities_trained: cfg must not be NULL");
+    if (int rc = ring_refusal(e, NEED_PRIORITIES | NEED_ERRORS)) return rc;
+    ReplayRing& r = e->ring;
+    ReplayRing::Priorities& p = r.prio;
+    if (c->struct_size != (int32_t)sizeof(azg_trained_priority_config)) return fail(e, AZG_E_INVALID, "azg_trained_priority_config size mismatch");
+    if (c->unseen != AZG_UNSEEN_MAX && c->unseen != AZG_UNSEEN_VALUE_GAP && c->unseen != AZG_UNSEEN_CONSTANT)
+        return fail(e, AZG_E_INVALID, "azg_selfplay_priorities_trained: unknown unseen");
+    if (c->unseen == AZG_UNSEEN_VALUE_GAP && !r.tr.on)
+        return fail(e, AZG_E_STATE, "azg_selfplay_priorities_trained: AZG_UNSEEN_VALUE_GAP needs azg_selfplay_keep_transitions: the stored steps' search values were not kept");
+    if (!(c->alpha >= 0.0f && std::isfinite(c->alpha))) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities_trained: alpha must be finite and >= 0");
+    if (!(c->eps > 0.0f && std::isfinite(c->eps))) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities_trained: eps must be finite and > 0");
+    if (c->unseen == AZG_UNSEEN_CONSTANT && !(c->unseen_d >= 0.0f && std::isfinite(c->unseen_d)))
+        return fail(e, AZG_E_INVALID, "azg_selfplay_priorities_trained: unseen_d must be finite and >= 0");
+    PrioErrMax pm;
+    if (int rc = ring_partition(e, "azg_selfplay_priorities_trained", &pm)) return rc;
+    const size_t n = r.stored_rows();
+    p.w_gen = -1;   // (weights computed from the priorities before these are no longer handed out)
+    if (n == 0) { p.gen = r.rows_gen; return AZG_OK; }
+    ON_DEVICE(e);
+    pm.err = p.err; pm.seg_max = p.err_max; pm.net_max = p.err_max + p.segs;
+    if (c->unseen == AZG_UNSEEN_MAX) {
+        hipLaunchKernelGGL(prio_errmax_segments_kernel, dim3(pm.nseg, e->n_nets), dim3(PR_THREADS), 0, e->stream, pm);
+        HIPCHK(e, hipGetLastError());
+        hipLaunchKernelGGL(prio_errmax_nets_kernel, dim3(e->n_nets), dim3(64), 0, e->stream, pm);
+        HIPCHK(e, hipGetLastError());
+    }
+    PrioritiesTrained pr;
+    pr.rows_n = (long long)n; pr.unseen = c->unseen;
+    pr.row_len = r.row; pr.vcol = r.row - 1; pr.B = pm.B; pr.T = pm.T;
+    pr.alpha = c->alpha; pr.eps = c->eps; pr.unseen_d = c->unseen_d;
+    pr.err = p.err; pr.net_max = pm.net_max; pr.value = r.tr.value; pr.rows = r.rows; pr.q = p.q;
+    hipLaunchKernelGGL(priorities_trained_kernel, dim3((unsigned)((n + PR_THREADS - 1) / PR_THREADS)), dim3(PR_THREADS), 0, e->stream, pr);
+    HIPCHK(e, hipGetLastError());
+    p.gen = r.rows_gen;
+    return AZG_OK;
 }
 
 // ---- search rollouts (include/azgym_search_rollout.h)

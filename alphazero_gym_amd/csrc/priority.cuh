@@ -3,7 +3,8 @@
 // segment of PR_SEG rows scanned by one workgroup, then the segment totals scanned by one wave per net); the row draws, each a binary
 // search over the segment totals and then within one segment; the slot draws, one thread per game column.  Every sum is an integer add
 // of uint64 values whose total stays below 2^63, so the sums are exact whatever the order and nothing here is atomic.  The
-// importance-sampling weights' kernels (at the end): a net's least q in the same two levels, then the weight of every stored row.
+// importance-sampling weights' kernels: a net's least q in the same two levels, then the weight of every stored row.  The priorities
+// fed back from the trainer's value errors (at the end): a net's largest seen error in those two levels, then q of every stored row.
 #pragma once
 #include "../../include/azg_math.h"
 #include "../../include/azgym_priority.h"
@@ -251,4 +252,95 @@ __global__ __launch_bounds__(PR_THREADS) void is_weights_kernel(IsWeights iw) {
     if (idx >= iw.rows_n) return;
     const int tree = (int)(idx % iw.B);
     iw.w[idx] = priority_is_weight(iw.q[idx], iw.net_min[tree / iw.T], iw.beta);
+}
+
+// ------------------------------------------------------------------------------------------------ priorities from the trainer's errors
+
+#define PR_ERR_UNSEEN (-1.0f)           // the sentinel of an entry never trained on since it was stored ...
+#define PR_ERR_UNSEEN_BITS 0xBF800000   // ... and its bit pattern, for the 32-bit fills
+
+// The largest seen error of every net, in the minimum's two levels and over the same segments.  Only entries >= 0 count (the sentinel
+// and NaN do not): non-negative floats order like their bit patterns read as int32 (-0.0f counts as +0.0f), and -1 stands for "none",
+// so this is an integer maximum, exact in any order.
+struct PrioErrMax {
+    int B, T;
+    int N, nseg;
+    const float* err;    // [capacity_steps][B]
+    int* seg_max;        // [n_nets][nseg]: the bits of a segment's largest seen error, or -1
+    int* net_max;        // [n_nets]
+};
+__device__ __forceinline__ int wave_max_i32(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int other = __shfl_xor(v, o, 64);
+        v = other > v ? other : v;
+    }
+    return v;
+}
+
+// grid (nseg, n_nets): one workgroup folds one segment (a row past N counts as none)
+__global__ __launch_bounds__(PR_THREADS) void prio_errmax_segments_kernel(PrioErrMax pm) {
+    __shared__ int wave_most[PR_THREADS / 64];
+    const int k = blockIdx.y, seg = blockIdx.x;
+    const int i = seg * PR_SEG + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int v = -1;
+    if (i < pm.N) {
+        const int slot = i / pm.T;
+        const float x = pm.err[(size_t)slot * pm.B + (size_t)k * pm.T + (i - slot * pm.T)];
+        if (x >= 0.0f) v = __float_as_int(fabsf(x));
+    }
+    v = wave_max_i32(v);
+    if (lane == 0) wave_most[wave] = v;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int w = 1; w < PR_THREADS / 64; ++w) v = wave_most[w] > v ? wave_most[w] : v;
+    pm.seg_max[(size_t)k * pm.nseg + seg] = v;
+}
+
+// grid (n_nets), one wave: lane l folds segments l, l + 64, ...; then the wave's largest
+__global__ __launch_bounds__(64) void prio_errmax_nets_kernel(PrioErrMax pm) {
+    const int* seg = pm.seg_max + (size_t)blockIdx.x * pm.nseg;
+    int v = -1;
+    for (int s = threadIdx.x; s < pm.nseg; s += 64) v = seg[s] > v ? seg[s] : v;
+    v = wave_max_i32(v);
+    if (threadIdx.x == 0) pm.net_max[blockIdx.x] = v;
+}
+
+// One thread per stored row, thread slot * B + tree, like priorities_kernel.  A seen entry (anything but the sentinel, NaN included) is
+// the row's d; an unseen one takes the largest seen error of its net (1.0f if the net has none), the value gap, or a constant.
+// q is priority_q's, except that a d that is NaN or +inf is decided here.
+struct PrioritiesTrained {
+    long long rows_n;         // stored rows: size_steps * n_trees
+    int unseen;               // AZG_UNSEEN_*
+    int row_len, vcol;        // a row's length and its V_target column
+    int B, T;
+    float alpha, eps, unseen_d;
+    const float* err;         // [capacity_steps][B]
+    const int* net_max;       // AZG_UNSEEN_MAX: [n_nets] (after both maximum kernels)
+    const double* value;      // AZG_UNSEEN_VALUE_GAP: the kept float64 values [capacity_steps][B]
+    const float* rows;        // ... and the replay ring [capacity_steps][B][row_len]
+    pr_u64* q;                // [capacity_steps][B]
+};
+__global__ __launch_bounds__(PR_THREADS) void priorities_trained_kernel(PrioritiesTrained pr) {
+    const long long idx = (long long)blockIdx.x * PR_THREADS + threadIdx.x;
+    if (idx >= pr.rows_n) return;
+    float d = pr.err[idx];
+    if (d == PR_ERR_UNSEEN) {
+        if (pr.unseen == AZG_UNSEEN_MAX) {
+            const int m = pr.net_max[(int)(idx % pr.B) / pr.T];
+            d = m < 0 ? 1.0f : __int_as_float(m);
+        } else if (pr.unseen == AZG_UNSEEN_VALUE_GAP) {
+            const double z = (double)pr.rows[(size_t)idx * pr.row_len + pr.vcol];
+            d = (float)fabs(pr.value[idx] - z);
+        } else {
+            d = pr.unseen_d;
+        }
+    }
+    // (a NaN or +inf d lies outside azg_logf's domain, which reads its argument's bits: p is taken as NaN / +inf by the header's rule)
+    pr_u64 q;
+    if (pr.alpha != 0.0f && !(d < __builtin_inff())) q = d != d ? 1ull : 1ull << 40;
+    else q = priority_q(d, pr.alpha, pr.eps);
+    pr.q[idx] = q;
 }

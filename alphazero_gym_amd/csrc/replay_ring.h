@@ -40,6 +40,11 @@ struct ReplayRingState {
         // never, or azg_selfplay_priorities has run since)
         float* w = nullptr; unsigned long long* w_min = nullptr;
         long long w_gen = -1;
+        // azg_selfplay_keep_errors: the trainer's value error of every stored row [cap][B] (-1.0f: not trained on since it was stored),
+        // the bits of the largest seen error per scan segment [segs] and per net [B], and the host side of an upload
+        int err_on = 0;
+        float* err = nullptr; int* err_max = nullptr;
+        std::vector<float> h_err;
     } prio;
 };
 

@@ -711,10 +711,16 @@ __global__ __launch_bounds__(64) void train_loss_sum_kernel(const float* table, 
 // own -- the three weighted terms and, fourth, the weight itself, whose sum S_w the tuned loss's alpha_loss needs:
 // alpha * (S_wH / n - target * (S_w / n)).  train_loss_kernel's text with those changes; weights of 1.0f give its bits (every product
 // with 1.0 is exact and S_w / n is 1).
+//
+// ERR (include/azgym_train_errors.h): the row's value error e = (float)fabs((double)raw[0] - (double)z), the first two operations of
+// tr_loss_row_t, also goes to errors[err_at[at]] -- err_at [n_nets][n_rows]: the element the epoch's gather staged beside the row -- or,
+// with err_at NULL, to the dense errors[at]; and NULL weights stand for weights of 1.0f.  ERR = false is the text as it was: the two
+// weighted kernels below compile to the code they had.
+template <bool ERR>
 __device__ __forceinline__ void tr_loss_weighted_body(const LossDims& c, const float* raw, const float* actions, const float* counts,
                                                       const float* values, const float* weights, int n_rows, float* log_alpha,
                                                       float* exp_avg, float* exp_avg_sq, float* d_raw, float* losses, double* rows,
-                                                      int stride) {
+                                                      int stride, const long long* err_at = nullptr, float* errors = nullptr) {
     const int net = blockIdx.x, tid = threadIdx.x, NO = 1 + c.nd;
     const bool tuned = c.kind == AZG_LOSS_A0C_TUNED;
     const float la = tuned ? log_alpha[net] : 0.0f;
@@ -722,7 +728,13 @@ __device__ __forceinline__ void tr_loss_weighted_body(const LossDims& c, const f
     double* rw = rows + (size_t)net * 4 * stride;
     for (int row = tid; row < n_rows; row += TR_LOSS_THREADS) {
         const size_t at = (size_t)net * n_rows + row;
-        const double w = (double)weights[at];
+        double w;
+        if constexpr (ERR) {
+            w = weights ? (double)weights[at] : 1.0;
+            errors[err_at ? (size_t)err_at[at] : at] = (float)fabs((double)raw[at * NO] - (double)values[at]);
+        } else {
+            w = (double)weights[at];
+        }
         double terms[3];
         tr_loss_row_t<true>(c, alpha, raw + at * NO, actions + at * c.A, counts + at * c.A, values[at], w, d_raw + at * NO, terms);
         rw[row] = w * terms[0]; rw[stride + row] = w * terms[1]; rw[2 * stride + row] = w * terms[2]; rw[3 * (size_t)stride + row] = w;
@@ -758,7 +770,7 @@ __global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_weighted_kernel(Lo
                                                                               const float* counts, const float* values, const float* weights,
                                                                               int n_rows, float* log_alpha, float* exp_avg, float* exp_avg_sq,
                                                                               float* d_raw, float* losses, double* rows, int stride) {
-    tr_loss_weighted_body(c, raw, actions, counts, values, weights, n_rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, rows, stride);
+    tr_loss_weighted_body<false>(c, raw, actions, counts, values, weights, n_rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, rows, stride);
 }
 
 // ... with the settings of net blockIdx.x from table[blockIdx.x] (the *_nets_weighted entry points)
@@ -768,7 +780,7 @@ __global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_nets_weighted_kern
                                                                                    float* log_alpha, float* exp_avg, float* exp_avg_sq,
                                                                                    float* d_raw, float* losses, double* rows, int stride) {
     const LossDims c = table[blockIdx.x];
-    tr_loss_weighted_body(c, raw, actions, counts, values, weights, n_rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, rows, stride);
+    tr_loss_weighted_body<false>(c, raw, actions, counts, values, weights, n_rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, rows, stride);
 }
 
 // train_gather_kernel, and the wave that copies row `at` also stages weights[at] -- the weight array is addressed like the rows with
@@ -793,5 +805,52 @@ __global__ __launch_bounds__(TR_GATHER_THREADS) void train_gather_weighted_kerne
         else values[out] = x;
     }
     if (lane == 0) wout[out] = weights[at];
+}
+
+// ------------------------------------------------------------------------------------------------ value errors out of the loss launch
+// include/azgym_train_errors.h: the weighted loss kernels' ERR = true forms (weights may be NULL), and the gather that stages each
+// row's element index `at` -- where its error goes in an array addressed like the rows with a row length of 1 -- beside the row.
+__global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_errors_kernel(LossDims c, const float* raw, const float* actions,
+                                                                            const float* counts, const float* values, const float* weights,
+                                                                            int n_rows, float* log_alpha, float* exp_avg, float* exp_avg_sq,
+                                                                            float* d_raw, float* losses, double* rows, int stride,
+                                                                            const long long* err_at, float* errors) {
+    tr_loss_weighted_body<true>(c, raw, actions, counts, values, weights, n_rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, rows, stride,
+                                err_at, errors);
+}
+
+__global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_nets_errors_kernel(const LossDims* __restrict__ table, const float* raw,
+                                                                                 const float* actions, const float* counts,
+                                                                                 const float* values, const float* weights, int n_rows,
+                                                                                 float* log_alpha, float* exp_avg, float* exp_avg_sq,
+                                                                                 float* d_raw, float* losses, double* rows, int stride,
+                                                                                 const long long* err_at, float* errors) {
+    const LossDims c = table[blockIdx.x];
+    tr_loss_weighted_body<true>(c, raw, actions, counts, values, weights, n_rows, log_alpha, exp_avg, exp_avg_sq, d_raw, losses, rows, stride,
+                                err_at, errors);
+}
+
+// train_gather_weighted_kernel, and the wave also stages `at` into at_out [nets][n_rows]; NULL weights stage 1.0f.
+__global__ __launch_bounds__(TR_GATHER_THREADS) void train_gather_errors_kernel(GatherDims g, const float* rows, const float* weights,
+                                                                                const int* order, int first, int n_rows, float* obs,
+                                                                                float* actions, float* counts, float* values, float* wout,
+                                                                                long long* at_out) {
+    const int net = blockIdx.y, lane = threadIdx.x & 63;
+    const int b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (TR_GATHER_THREADS / 64) + (threadIdx.x >> 6)));
+    if (b >= n_rows) return;
+    const int i = __builtin_amdgcn_readfirstlane(order[(size_t)net * g.n_order + first + b]);
+    const long long at = (long long)(i / g.group) * g.group_stride + (long long)net * g.net_stride + (long long)(i % g.group);
+    const float* src = rows + at * g.row_len;
+    const size_t out = (size_t)net * n_rows + b;
+    const int a0 = g.state_dim, c0 = a0 + g.A, q0 = c0 + g.A, v0 = g.row_len - 1;
+    for (int c = lane; c < g.row_len; c += 64) {
+        if (c >= q0 && c < v0) continue;
+        const float x = src[c];
+        if (c < a0) obs[out * g.state_dim + c] = x;
+        else if (c < c0) actions[out * g.A + (c - a0)] = x;
+        else if (c < q0) counts[out * g.A + (c - c0)] = x;
+        else values[out] = x;
+    }
+    if (lane == 0) { wout[out] = weights ? weights[at] : 1.0f; at_out[out] = at; }
 }
 #endif  // TR_NO_SHARED_KERNELS

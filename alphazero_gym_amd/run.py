@@ -338,7 +338,12 @@ class PopulationSelfPlay:
     every game the same way.  The draws are biased towards surprising rows; with ``"beta"`` in ``prioritized`` (optional; absent:
     no weight is ever computed) ``is_weights()`` computes the importance-sampling weight ``(q_min / q) ** beta`` of every stored
     row on the device, q_min the least priority of the row's net, and ``PopulationTrainer.train_epoch_ring(sp, order,
-    weights="priority")`` multiplies it into the row's losses."""
+    weights="priority")`` multiplies it into the row's losses.  With ``"feedback"`` in ``prioritized`` (optional; absent: every
+    call is what it was) the engine also keeps the trainer's value error of every stored row, ``|V - z|`` as
+    ``PopulationTrainer.train_epoch_ring(sp, order, errors=True)`` writes it from its loss launch, and ``priorities()`` takes a
+    row's d from it; a row not trained on since it was stored takes the largest trained error of its net (``"max"``; 1 while the
+    net has none), ``|search value - V_target|`` (``"value_gap"``) or a constant d >= 0 (a number).  ``errors()`` downloads the
+    kept errors, ``set_errors(array)`` uploads them (-1: not trained on)."""
 
     def __init__(self, policies, *, game: str, games_per_net: int, n_rollouts: int, c_uct: float, gamma: float = 1.0, epsilon: float = 0.0,
                  c_pw: float = 1.0, kappa: float = 0.5, V_target_policy: str = "off_policy", max_episode_length: int = 200,
@@ -351,9 +356,11 @@ class PopulationSelfPlay:
         if not policies or games_per_net < 1:
             raise ValueError(f"{type(self).__name__} needs at least one policy and games_per_net >= 1")
         if prioritized is not None:
-            if set(prioritized) - {"alpha", "eps", "beta"}:
-                raise ValueError(f"{type(self).__name__}: prioritized takes alpha, eps and beta, not "
-                                 f"{sorted(set(prioritized) - {'alpha', 'eps', 'beta'})}")
+            if set(prioritized) - {"alpha", "eps", "beta", "feedback"}:
+                raise ValueError(f"{type(self).__name__}: prioritized takes alpha, eps and beta, and feedback, not "
+                                 f"{sorted(set(prioritized) - {'alpha', 'eps', 'beta', 'feedback'})}")
+            if prioritized.get("feedback") is not None:
+                _capi.unseen_mode(prioritized["feedback"])   # (ValueError: neither "max", "value_gap" nor a number >= 0)
             if prioritized.get("beta") is not None:
                 if "alpha" not in prioritized:
                     raise ValueError(f"{type(self).__name__}: prioritized takes alpha and eps, and beta only beside alpha (the weights "
@@ -403,6 +410,9 @@ class PopulationSelfPlay:
         self._slot_sample_index = 0
         if self.prioritized is not None:
             self.engine.selfplay_keep_priorities(True)
+            if prioritized.get("feedback") is not None:
+                self.prioritized["feedback"] = prioritized["feedback"]
+                self.engine.selfplay_keep_errors(True)
 
     @staticmethod
     def _search(policies, games_per_net: int, **kw) -> PopulationMCTS:
@@ -439,10 +449,30 @@ class PopulationSelfPlay:
     def priorities(self, given=None) -> None:
         """Compute the priority of every stored row (``Engine.selfplay_priorities`` with the ``alpha`` and ``eps`` given at
         creation; asynchronous: one launch).  ``given`` None: from |kept search value - V_target|; else from ``given``, a float32
-        array with one entry >= 0 per stored row ordered like the ring ([size_steps, n_games]): a training loop's own TD errors."""
+        array with one entry >= 0 per stored row ordered like the ring ([size_steps, n_games]): a training loop's own TD errors.
+        Created with ``"feedback"`` and ``given`` None: from the kept errors of the trainer (``Engine.selfplay_priorities_trained``)."""
         if self.prioritized is None:
             raise RuntimeError(f"{type(self).__name__}.priorities needs a priority per stored row: create it with prioritized={{...}}")
+        if given is None and "feedback" in self.prioritized:
+            self.engine.selfplay_priorities_trained(self.prioritized["alpha"], self.prioritized["eps"], self.prioritized["feedback"])
+            return
         self.engine.selfplay_priorities(self.prioritized["alpha"], self.prioritized["eps"], given)
+
+    def _feedback_refusal(self, what: str) -> None:
+        if self.prioritized is None or "feedback" not in self.prioritized:
+            raise RuntimeError(f'{type(self).__name__}.{what} needs an error per stored row: create it with prioritized={{..., "feedback": ...}}')
+
+    def errors(self) -> np.ndarray:
+        """The kept value errors of the stored rows, float32 [size_steps * n_games] ordered like the ring; -1: not trained on since
+        the row was stored (``Engine.selfplay_error_values``; synchronises)."""
+        self._feedback_refusal("errors")
+        return self.engine.selfplay_error_values()
+
+    def set_errors(self, errors) -> None:
+        """Upload one error per stored row, ordered like the ring; every entry -1 (not trained on), NaN or >= 0
+        (``Engine.selfplay_set_error_values``): a caller's own errors, a restored checkpoint."""
+        self._feedback_refusal("set_errors")
+        self.engine.selfplay_set_error_values(errors)
 
     def sample_order(self, n_order: int, given=None) -> np.ndarray:
         """``n_order`` training rows per net drawn on the device in proportion to the rows' priorities, with replacement: int32

@@ -39,6 +39,10 @@ prioritized=..., sample_order); with --reanalyse-slots N the reanalysed position
 (the net's least priority / the row's priority)^B on the device (is_weights), and the population trainer multiplies it into the row's
 losses -- --trainer device-epoch reads the weights where they lie (train_epoch_ring(weights="priority")), --trainer device and
 device-fused pass the gathered weights to update.  It needs one of those three trainers.
+--prioritized-feedback {max,value_gap} closes the loop: with --trainer device-epoch every iteration runs priorities -> sample_order ->
+is_weights -> train_epoch_ring(errors=True), the epoch's loss launches write each trained row's |V - z| into the engine's ring and the
+next draw's priorities come from those errors; rows not trained on since they were stored take the net's largest trained error (max)
+or |search value - value target| (value_gap).
 The draw is with replacement and biased; the loss is not reweighted (no importance-sampling weights).
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
@@ -137,6 +141,11 @@ def parse_args(argv=None):
                     help="correct the prioritised draw's bias: multiply every drawn row's losses by its importance-sampling weight "
                          "(least priority of the net / the row's priority)^beta, computed on the device; needs --prioritized-alpha and a --trainer other than torch "
                          "(default: off, no weight is computed)")
+    ap.add_argument("--prioritized-feedback", choices=["max", "value_gap"], default=None,
+                    help="close the loop of prioritised replay: the priorities come from the learners' own value errors |V - z| on the "
+                         "rows they trained on, written by the training epoch's loss launches into the engine's ring; a row not trained "
+                         "on since it was stored takes the largest trained error of its net (max) or |search value - value target| "
+                         "(value_gap); needs --prioritized-alpha and --trainer device-epoch (default: off, nothing is kept)")
     a = ap.parse_args(argv)
     why = check_replay(a)
     if why:
@@ -212,6 +221,12 @@ def check_replay(a):
         if a.trainer == "torch":
             return ("--prioritized-beta: the weighted losses are the population trainer's: use --trainer device, device-fused or "
                     "device-epoch (the per-agent update loop of --trainer torch takes no weights)")
+    if getattr(a, "prioritized_feedback", None) is not None:
+        if getattr(a, "prioritized_alpha", None) is None:
+            return "--prioritized-feedback feeds the priorities of the prioritised draw: it needs --prioritized-alpha A"
+        if a.trainer != "device-epoch":
+            return ("--prioritized-feedback: the errors come out of the native epoch over the ring: use --trainer device-epoch (the "
+                    "per-agent update loop of --trainer torch and the update calls of device and device-fused write none)")
     if a.reanalyse_slots and not (a.replay_steps or a.trainer == "device-epoch"):
         return ("--reanalyse-slots rewrites rows that stay in the device ring: use it with --replay-steps R (the FIFO ring) or with "
                 "--trainer device-epoch; the other modes copy the rows out and clear the ring every iteration")
@@ -231,12 +246,15 @@ def check_population_shape(a):
 
 
 def prioritized(a):
-    """PopulationSelfPlay's ``prioritized`` for --prioritized-alpha / --prioritized-eps / --prioritized-beta (None: off)."""
+    """PopulationSelfPlay's ``prioritized`` for --prioritized-alpha / --prioritized-eps / --prioritized-beta / --prioritized-feedback
+    (None: off)."""
     if getattr(a, "prioritized_alpha", None) is None:
         return None
     out = {"alpha": a.prioritized_alpha, "eps": getattr(a, "prioritized_eps", 1e-3)}
     if getattr(a, "prioritized_beta", None) is not None:
         out["beta"] = a.prioritized_beta
+    if getattr(a, "prioritized_feedback", None) is not None:
+        out["feedback"] = a.prioritized_feedback
     return out
 
 
@@ -277,6 +295,7 @@ def train(a, log=print, on_rows=None, on_end=None):
     replay_steps, reanalyse_slots = getattr(a, "replay_steps", 0), getattr(a, "reanalyse_slots", 0)
     by_priority = sp.prioritized is not None
     weighted = by_priority and "beta" in sp.prioritized
+    feedback = by_priority and "feedback" in sp.prioritized
 
     def reanalyse():
         if by_priority:   # one search per "slot": every game re-searches the position drawn for it
@@ -330,7 +349,9 @@ def train(a, log=print, on_rows=None, on_end=None):
             for k, rng in enumerate(rngs):
                 pick = pick_rows(k, rng, n_ring)
                 order.append(pick[np.random.RandomState(int(rng.randint(2 ** 31 - 1))).permutation(len(pick))])
-            infos = trainer.train_epoch_ring(sp, np.stack(order), batch_size=a.batch_size, weights="priority" if weighted else None)
+            # (--prioritized-feedback: the epoch's loss launches write the rows' errors back, the next iteration's draw reads them)
+            infos = trainer.train_epoch_ring(sp, np.stack(order), batch_size=a.batch_size, weights="priority" if weighted else None,
+                                             **({"errors": True} if feedback else {}))
             if not replay_steps:
                 sp.engine.selfplay_clear()
             losses = [info["loss"] / max(1, len(order[0]) // a.batch_size) for info in infos]

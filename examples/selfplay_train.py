@@ -23,6 +23,10 @@ prioritized=..., sample_order); with --reanalyse-slots N the reanalysed position
 draw is with replacement and biased; --prioritized-beta B corrects for it: every drawn row's losses are multiplied by its
 importance-sampling weight (least priority / the row's priority)^B, computed on the device (DeviceSelfPlay.is_weights), and the
 optimiser steps go through a one-net PopulationTrainer(losses="device"), whose update takes the gathered weights.
+--prioritized-feedback {max,value_gap} closes the loop: every iteration runs priorities -> sample_order -> is_weights -> one native
+epoch over the ring (train_epoch_ring(errors=True)) whose loss launches write each trained row's |V - z| into the engine's ring, and the
+next draw's priorities come from those errors; rows not trained on since they were stored take the largest trained error (max) or
+|search value - value target| (value_gap).
 
 --eval-search-episodes E adds eval_search_return: after every iteration every game plays E whole episodes under MCTS with the greedy
 final-action rule, on the device in one call and on state of its own (DeviceSelfPlay.evaluate_search): the return of the agent as it
@@ -106,6 +110,11 @@ def parse_args(argv=None):
                     help="correct the prioritised draw's bias: multiply every drawn row's losses by its importance-sampling weight "
                          "(least priority of the net / the row's priority)^beta, computed on the device; needs --prioritized-alpha "
                          "(default: off, no weight is computed)")
+    ap.add_argument("--prioritized-feedback", choices=["max", "value_gap"], default=None,
+                    help="close the loop of prioritised replay: the priorities come from the learner's own value errors |V - z| on the "
+                         "rows it trained on, written by the training epoch's loss launches into the engine's ring; a row not trained "
+                         "on since it was stored takes the largest trained error (max) or |search value - value target| (value_gap); "
+                         "needs --prioritized-alpha (default: off, nothing is kept)")
     a = ap.parse_args(argv)
     if a.eval_search_episodes < 0:
         ap.error("--eval-search-episodes must be >= 0")
@@ -132,6 +141,8 @@ def parse_args(argv=None):
             ap.error("--prioritized-beta weighs rows drawn by priority: it needs --prioritized-alpha A")
         if not (a.prioritized_beta >= 0.0 and np.isfinite(a.prioritized_beta)):
             ap.error("--prioritized-beta must be finite and >= 0")
+    if a.prioritized_feedback is not None and a.prioritized_alpha is None:
+        ap.error("--prioritized-feedback feeds the priorities of the prioritised draw: it needs --prioritized-alpha A")
     return a
 
 
@@ -166,7 +177,10 @@ def train(a, log=print):
         prioritized = {"alpha": a.prioritized_alpha, "eps": getattr(a, "prioritized_eps", 1e-3)}
         if getattr(a, "prioritized_beta", None) is not None:
             prioritized["beta"] = a.prioritized_beta
+        if getattr(a, "prioritized_feedback", None) is not None:
+            prioritized["feedback"] = a.prioritized_feedback
     weighted = prioritized is not None and "beta" in prioritized
+    feedback = prioritized is not None and "feedback" in prioritized
     sp = run.DeviceSelfPlay(agent.nn, game=a.game, n_games=a.games, n_rollouts=a.n_rollouts, c_uct=m.c_uct, gamma=m.gamma,
                             epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0), kappa=getattr(m, "kappa", 0.5),
                             max_episode_length=a.max_episode_length, capacity_steps=replay_steps or a.steps_per_iter, fifo=bool(replay_steps),
@@ -176,7 +190,7 @@ def train(a, log=print):
     K = sp.engine.kmax if continuous else 2
     rng = np.random.RandomState(a.seed)
     trainer = None
-    if weighted:   # the weighted losses are the population trainer's: one net, the agent's own optimiser and clip
+    if weighted or feedback:   # the weighted losses and the errors are the population trainer's: one net, the agent's own optimiser and clip
         from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
         wide = len(a.hidden) > 3 or max(a.hidden) > 256
         trainer = PopulationTrainer([agent], max_batch=max(512, 2 * a.batch_size), losses="device", optimizers="agents",
@@ -208,7 +222,13 @@ def train(a, log=print):
             pick = sp.sample_order(min(a.train_rows, rows.shape[0]))[0].astype(np.int64)
         else:
             pick = rng.choice(rows.shape[0], size=min(a.train_rows, rows.shape[0]), replace=False)
-        if weighted:   # the weights of the priorities the draw was made from, in the ring's row numbering
+        if feedback:   # priorities -> sample_order -> is_weights -> one native epoch over the ring that writes the rows' errors back
+            if weighted:
+                sp.is_weights()
+            order = pick[np.random.RandomState(it).permutation(len(pick))][None, :]
+            info = trainer.train_epoch_ring(sp, order, batch_size=a.batch_size, weights="priority" if weighted else None, errors=True)[0]
+            sp.upload_flat(trainer.desc, trainer.flat)
+        elif weighted:   # the weights of the priorities the draw was made from, in the ring's row numbering
             sp.is_weights()
             w = torch.from_numpy(sp.engine.selfplay_is_weight_values()).to(rows.device)
             at = torch.from_numpy(pick).to(rows.device)

@@ -45,7 +45,24 @@
  *     otherwise  r = (float)((double)q_min_k / (double)q_i)  (both at most 2^40: the conversions are exact, the division is rounded once,
  *     then once more to float32) and w = azg_expf(beta * azg_logf(r)).
  * Every w lies in [0, 1] and is whatever azg_expf returns, an underflow for a large beta included.  Normalised by the ring's minimum,
- * not by a minibatch's maximum, a row's weight does not depend on what else was drawn. */
+ * not by a minibatch's maximum, a row's weight does not depend on what else was drawn.
+ *
+ * Priorities fed back from the trainer (azg_selfplay_keep_errors, azg_selfplay_priorities_trained).  The third source of a row's d is
+ * the learner's own value error on it: err [capacity_steps][n_trees] float32, slot-aligned with the rows, q and w.  An entry is the
+ * error a trainer wrote when it last trained on the row -- e = (float)fabs((double)V - (double)z), azgym_train_errors.h -- or the
+ * sentinel -1.0f: never trained on since the row was stored.  The switch-on fills the array with the sentinel and every
+ * azg_selfplay_step resets the block of the slot it stores into; a clear, a reanalysis and an n-step call leave it alone.  The row's d:
+ *   seen entry (err != -1.0f; NaN is seen):  d = err.
+ *   unseen entry, AZG_UNSEEN_MAX:  d = the largest seen error of the row's net (the rows the row draw sums over), taken over the
+ *       entries with err >= 0 only -- the sentinel and NaN do not count, +inf does.  Non-negative float32 values order like their bit
+ *       patterns read as integers (-0.0f counts as +0.0f), so the maximum is an integer maximum, exact in any order.  A net with no such
+ *       entry takes d = 1.0f.
+ *   unseen entry, AZG_UNSEEN_VALUE_GAP:  AZG_PRIO_VALUE_GAP's d = (float)fabs(v - (double)z).
+ *   unseen entry, AZG_UNSEEN_CONSTANT:  d = unseen_d.
+ * p and q follow from d, alpha and eps exactly as above for every finite d.  A d that is NaN or +inf lies outside azg_logf's domain
+ * (the function reads its argument's bits and would return a finite number near 89 for either), so with alpha != 0 the trained form
+ * decides them before it: a NaN d has p = NaN, hence q = 1; a +inf d has p = +inf, hence q = 2^40.  alpha == 0 gives p = 1, q = 2^20,
+ * for every row, these included. */
 #ifndef AZGYM_PRIORITY_H
 #define AZGYM_PRIORITY_H
 #include "azgym_nstep.h"
@@ -114,6 +131,51 @@ int azg_selfplay_is_weights_device(azg_engine* e, const float** w);
 /* The stored rows' weights as the array holds them, ordered like azg_selfplay_rows.  Returns the number of rows copied.  Synchronises
  * the engine's stream.  AZG_E_STATE without keep_priorities or before the first azg_selfplay_is_weights. */
 int azg_selfplay_is_weight_values(azg_engine* e, float* w, size_t max_rows);
+
+/* ---- priorities fed back from the trainer's value errors (the rule: the last paragraph of the head comment) */
+
+/* what an unseen row's d is */
+enum { AZG_UNSEEN_MAX = 0, AZG_UNSEEN_VALUE_GAP = 1, AZG_UNSEEN_CONSTANT = 2 };
+
+/* Keep a value error per stored row beside q: err [capacity_steps][n_trees] float32 and the scratch of the per-net maximum.  on = 1 /
+ * 0.  Needs azg_selfplay_keep_priorities (AZG_E_STATE otherwise, for on = 1) and is allowed at any ring size, like it; every switch-on
+ * fills the whole array with the sentinel -1.0f.  azg_selfplay_keep_priorities(0) switches it off too; the next begin drops it.  While
+ * it is on, azg_selfplay_step also sets the n_trees entries of the slot it stores into to the sentinel: one asynchronous 32-bit fill
+ * on the engine's stream, after the step's kernel launch, with no synchronisation, allocation or copy.  Off, a step's HIP calls are
+ * what they were. */
+int azg_selfplay_keep_errors(azg_engine* e, int32_t on);
+
+/* The mutable device pointer of err, for a trainer on the same GPU (azg_trainer_epoch_opt_errors over the ring: the array is addressed
+ * like the rows, with a row length of 1).  A switch-off and a new switch-on within one begin leave the array where it is (and refill it);
+ * the next begin frees it.  AZG_E_STATE without keep_errors.  The engine orders its own fills and reads on its stream; a trainer that
+ * writes from another stream finishes (its calls synchronise) before the next engine call that touches err. */
+int azg_selfplay_errors_device(azg_engine* e, float** err);
+
+/* The stored rows' errors as the array holds them, ordered like azg_selfplay_rows.  Returns the number of rows copied.  Synchronises
+ * the engine's stream.  AZG_E_STATE without keep_errors. */
+int azg_selfplay_error_values(azg_engine* e, float* err, size_t max_rows);
+
+/* Upload errors in the same order: a caller's own errors, a restored checkpoint.  n_rows must equal the stored rows and every entry
+ * must be -1.0f, NaN or >= 0: AZG_E_INVALID otherwise, with the array untouched.  AZG_E_STATE without keep_errors.  The array is
+ * copied before the call returns. */
+int azg_selfplay_set_error_values(azg_engine* e, const float* err, size_t n_rows);
+
+typedef struct azg_trained_priority_config {
+    int32_t struct_size;   /* sizeof(azg_trained_priority_config) */
+    int32_t unseen;        /* AZG_UNSEEN_* */
+    float alpha;           /* >= 0 and finite; 0: every row alike */
+    float eps;             /* > 0 and finite */
+    float unseen_d;        /* AZG_UNSEEN_CONSTANT: finite and >= 0; else not read */
+} azg_trained_priority_config;
+
+/* Write q for every stored row from err by the rule above, and nothing else; q counts as computed exactly as after
+ * azg_selfplay_priorities (the draws accept it, weights computed before it are no longer handed out).  Asynchronous: one kernel
+ * launch, after the per-net maximum's two under AZG_UNSEEN_MAX.  Refusals, before anything is launched and with q untouched: those of
+ * azg_selfplay_priorities with their codes (no begin or no keep_priorities: AZG_E_STATE; a wrong struct_size, alpha negative or not
+ * finite, eps not positive or not finite: AZG_E_INVALID), no keep_errors: AZG_E_STATE; an unknown unseen: AZG_E_INVALID;
+ * AZG_UNSEEN_VALUE_GAP without azg_selfplay_keep_transitions: AZG_E_STATE; AZG_UNSEEN_CONSTANT with unseen_d negative or not finite:
+ * AZG_E_INVALID.  An empty ring: AZG_OK, nothing is launched. */
+int azg_selfplay_priorities_trained(azg_engine* e, const azg_trained_priority_config* cfg);
 
 #ifdef __cplusplus
 }

@@ -11,8 +11,9 @@ Before the comparison comments are dropped, basic-block labels are renumbered in
 functions of the file) and the `.text` / `.section .text.<name>,...,comdat` line that follows a kernel is dropped (an instantiation
 lives in a comdat section).  With --renamed OLD=NEW (mangled names, repeatable) a kernel that was renamed is compared with its
 successor, the kernel's own name replaced by KERNEL on both sides.  With --added-ok a kernel that only the second file has is
-listed as added and is not a difference (a change that adds kernels beside the ones it must leave alone).  Exit status 1 on any
-difference."""
+listed as added and is not a difference (a change that adds kernels beside the ones it must leave alone); the last line counts
+them, and with --added=N the run also fails unless exactly N kernels were added (a new instantiation that was not meant shows).
+Exit status 1 on any difference."""
 import difflib
 import re
 import sys
@@ -48,10 +49,12 @@ def kernels(path):
 
 
 def main():
-    args, renamed, added_ok = [], {}, False
+    args, renamed, added_ok, want_added, added = [], {}, False, None, 0
     for arg in sys.argv[1:]:
         if arg == "--added-ok":
             added_ok = True
+        elif arg.startswith("--added="):
+            added_ok, want_added = True, int(arg[len("--added="):])
         elif arg.startswith("--renamed="):
             old, new = arg[len("--renamed="):].split("=")
             renamed[old] = new
@@ -79,11 +82,15 @@ def main():
     for name in kb:
         if name not in ka and name not in renamed.values():
             if added_ok:
+                added += 1
                 print(f"{name}\n    absent from the first file: added")
                 continue
             bad += 1
             print(f"{name}\n    absent from the first file: DIFFERENT")
-    print(f"{len(ka)} / {len(kb)} kernels, {bad} different")
+    if want_added is not None and added != want_added:
+        bad += 1
+        print(f"{added} kernels added where {want_added} were expected: DIFFERENT")
+    print(f"{len(ka)} / {len(kb)} kernels, {bad} different" + (f", {added} added" if added_ok else ""))
     return 1 if bad else 0
 
 
