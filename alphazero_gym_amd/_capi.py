@@ -128,6 +128,21 @@ UNSEEN_MAX, UNSEEN_VALUE_GAP, UNSEEN_CONSTANT = 0, 1, 2   # AZG_UNSEEN_*: the d 
 ERR_UNSEEN = np.float32(-1.0)                             # ... and its entry in the kept errors
 
 
+def trained_priority_config(alpha, eps, unseen="max"):
+    """azg_trained_priority_config of (alpha, eps) and an ``unseen`` setting (``unseen_mode``)."""
+    c = AzgTrainedPriorityConfig()
+    c.struct_size = C.sizeof(AzgTrainedPriorityConfig)
+    c.unseen, c.unseen_d = unseen_mode(unseen)
+    c.alpha, c.eps = float(alpha), float(eps)
+    return c
+
+
+class AzgOnlineEpoch(C.Structure):
+    """include/azgym_train_online.h: azg_online_epoch"""
+    _fields_ = [("struct_size", C.c_int32), ("n_minibatches", C.c_int32), ("batch_size", C.c_int32), ("sample_index", C.c_uint32),
+                ("beta", C.c_float), ("prio", AzgTrainedPriorityConfig), ("drawn", C.POINTER(C.c_int32))]
+
+
 def unseen_mode(feedback):
     """(AZG_UNSEEN_*, unseen_d) of a ``feedback`` setting: "max", "value_gap" or a finite number >= 0 (the constant d)."""
     if isinstance(feedback, str):
@@ -197,7 +212,8 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "trainer_backward_step_nets", "trainer_loss_nets", "trainer_step_nets", "trainer_epoch_nets",
                     "trainer_loss_weighted", "trainer_loss_nets_weighted", "trainer_step_opt_weighted", "trainer_step_nets_weighted",
                     "trainer_epoch_opt_weighted", "trainer_epoch_nets_weighted",
-                    "trainer_loss_errors", "trainer_loss_nets_errors", "trainer_epoch_opt_errors", "trainer_epoch_nets_errors"]
+                    "trainer_loss_errors", "trainer_loss_nets_errors", "trainer_epoch_opt_errors", "trainer_epoch_nets_errors",
+                    "trainer_epoch_online", "trainer_epoch_online_nets"]
 
 
 class AzgNetSearch(C.Structure):
@@ -434,6 +450,9 @@ def bind(lib, prefix):
             return args[:at] + [vp] + args[at:]
         f["trainer_loss_errors"].argtypes = f["trainer_loss_nets_errors"].argtypes = with_errors("trainer_loss_weighted", 6)
         f["trainer_epoch_opt_errors"].argtypes = f["trainer_epoch_nets_errors"].argtypes = with_errors("trainer_epoch_opt_weighted", 4)
+    if "trainer_epoch_online" in f:   # include/azgym_train_online.h
+        f["trainer_epoch_online"].argtypes = f["trainer_epoch_online_nets"].argtypes = [
+            vp, vp, vp, C.POINTER(AzgOnlineEpoch), C.POINTER(AzgLossCfg), C.POINTER(AzgAlphaState), C.POINTER(AzgOptim), vp]
     return f
 
 
@@ -1113,10 +1132,7 @@ def _selfplay_methods():
         """azg_selfplay_priorities_trained: the priority of every stored row from the kept errors, (d + eps)^alpha in fixed point with
         d the row's error; a row never trained on takes ``unseen``: "max" (the largest seen error of its net, 1 if none),
         "value_gap" (|kept search value - V_target|, needs selfplay_keep_transitions) or a constant d >= 0.  Asynchronous."""
-        c = AzgTrainedPriorityConfig()
-        c.struct_size = C.sizeof(AzgTrainedPriorityConfig)
-        c.unseen, c.unseen_d = unseen_mode(unseen)
-        c.alpha, c.eps = float(alpha), float(eps)
+        c = trained_priority_config(alpha, eps, unseen)
         self._check(self._optional("selfplay_priorities_trained")(self._h, C.byref(c)))
 
     for fn in (selfplay_keep_errors, selfplay_errors_device, selfplay_error_values, selfplay_set_error_values, selfplay_priorities_trained):
@@ -1464,6 +1480,41 @@ class Trainer:
         carr, oarr = self._entries("epoch_nets_errors", cfgs, AzgLossCfg), self._entries("epoch_nets_errors", opts, AzgOptim)
         return self._epoch("trainer_epoch_nets_errors", "epoch_nets_errors", params, rows, order, batch_size, carr, alpha, (oarr,),
                            loss_sums, (weights or None, errors or None))
+
+    # ---- the online epoch (include/azgym_train_online.h): every minibatch redrawn from the engine's refreshed priorities ----
+
+    def _epoch_online(self, symbol, engine, params, n_minibatches, batch_size, sample_index, beta, prio, cfg, alpha, opt, loss_sums,
+                      return_drawn):
+        fn = _require(self._f, symbol, "azg_trainer_epoch_online")
+        c = AzgOnlineEpoch()
+        c.struct_size = C.sizeof(AzgOnlineEpoch)
+        c.n_minibatches, c.batch_size = int(n_minibatches), int(batch_size)
+        c.sample_index, c.beta = int(sample_index) & 0xFFFFFFFF, float(beta)
+        c.prio = prio
+        drawn = None
+        if return_drawn:
+            drawn = np.empty((max(c.n_minibatches, 0), self.n_nets, max(c.batch_size, 0)), np.int32)
+            c.drawn = _ptr(drawn, C.c_int32)
+        self._check(fn(self._h, engine._h if engine is not None else None, params or None, C.byref(c), cfg, _ref(alpha), opt,
+                       loss_sums or None))
+        return drawn
+
+    def epoch_online(self, engine, params, n_minibatches, batch_size, sample_index, beta, prio, cfg, alpha, opt, loss_sums,
+                     return_drawn=False):
+        """azg_trainer_epoch_online: ``n_minibatches`` minibatches of ``batch_size`` rows per net over ``engine``'s replay ring, each
+        drawn under ``sample_index + m`` from priorities refreshed (``prio``: ``trained_priority_config``) with the errors of the
+        minibatches before it and weighted by (q_min / q)^beta; one synchronisation.  Equal, bit for bit, to the loop of
+        selfplay_priorities_trained, selfplay_sample_rows, selfplay_is_weights and epoch_opt_errors.  Returns the drawn rows, int32
+        [n_minibatches, n_nets, batch_size], when asked."""
+        return self._epoch_online("trainer_epoch_online", engine, params, n_minibatches, batch_size, sample_index, beta, prio, _ref(cfg),
+                                  alpha, _ref(opt), loss_sums, return_drawn)
+
+    def epoch_online_nets(self, engine, params, n_minibatches, batch_size, sample_index, beta, prio, cfgs, alpha, opts, loss_sums,
+                          return_drawn=False):
+        """azg_trainer_epoch_online_nets: ``epoch_online`` with one ``loss_cfg`` and one ``optim`` per net."""
+        carr, oarr = self._entries("epoch_online_nets", cfgs, AzgLossCfg), self._entries("epoch_online_nets", opts, AzgOptim)
+        return self._epoch_online("trainer_epoch_online_nets", engine, params, n_minibatches, batch_size, sample_index, beta, prio, carr,
+                                  alpha, oarr, loss_sums, return_drawn)
 
     def read_d_raw(self, n_rows, d_raw):
         """azg_trainer_read_d_raw: the last ``step``'s d_raw [n_nets, n_rows, 1 + n_dist] into the caller's device array."""

@@ -784,6 +784,56 @@ class PopulationTrainer:
         engine.sync()
         return self._epoch("train_epoch_ring", where, order.astype(np.int32), batch_size, w_ptr, e_ptr)
 
+    def train_online_ring(self, selfplay, n_minibatches: int, batch_size: int = 32, return_drawn: bool = False):
+        """Prioritised replay as published, in one native call (``azg_trainer_epoch_online``): ``n_minibatches`` minibatches of
+        ``batch_size`` rows per net over the self-play engine's ring, each one drawn from priorities refreshed with the value errors
+        of the minibatches before it, weighted by the importance-sampling weights of its rows, and writing its own errors back.
+        Bit for bit the loop, per minibatch, of ``selfplay.priorities()``, ``selfplay.sample_order(batch_size)``,
+        ``selfplay.is_weights()`` and ``train_epoch_ring(selfplay, order, batch_size, weights="priority", errors=True)`` -- with
+        3 launches (5 with feedback "max") in front of each step instead of 10, and one synchronisation for the whole call.
+
+        Needs ``losses="device"`` and a self-play object built with ``prioritized={..., "feedback": ...}``; ``alpha``, ``eps``, the
+        feedback mode and ``beta`` (absent: 0) are its.  Takes ``n_minibatches`` sample indices of the self-play object's counter
+        and as many optimiser (and alpha) steps.  Afterwards the engine's full weight array counts as not computed.  Returns the
+        per-net loss sums like ``train_epoch``; with ``return_drawn`` also the rows drawn, int32 [n_minibatches, K, batch_size]."""
+        _need_device_losses(self.losses, "train_online_ring")
+        prio = getattr(selfplay, "prioritized", None) or {}
+        if "feedback" not in prio:
+            raise ValueError('PopulationTrainer.train_online_ring needs a self-play engine built with prioritized={..., "feedback": ...}')
+        M, B = int(n_minibatches), int(batch_size)
+        if M < 1 or not 1 <= B <= self.max_batch:
+            raise ValueError(f"PopulationTrainer.train_online_ring: needs n_minibatches >= 1 and a batch_size of 1..{self.max_batch}")
+        engine = selfplay.engine
+        if int(engine.cfg.device_id) != (self.device.index or 0):
+            raise ValueError("PopulationTrainer.train_online_ring: the ring lies on another GPU than the trainer's nets")
+        if selfplay.n_nets != len(self.agents):
+            raise ValueError(f"PopulationTrainer.train_online_ring: the self-play engine has {selfplay.n_nets} nets, the trainer "
+                             f"{len(self.agents)}")
+        K = len(self.agents)
+        sums = torch.empty((K, len(_capi.LOSS_KEYS)), dtype=torch.float64, device=self.device)
+        tuned = self.log_alpha is not None
+        state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
+                                  self.alpha_exp_avg_sq.data_ptr()) if tuned else None
+        suffix, opt_args = self._form.suffix, self._form.opt_args()
+        if not suffix:   # (the azg_rmsprop family has no online form: the same RMSprop as an azg_optim, as ``_call`` does)
+            o = self.opt
+            opt_args = (_capi.optim("rmsprop", o.lr, self.square_avg.data_ptr(), eps=o.eps, weight_decay=o.weight_decay, alpha=o.alpha),)
+        call = self.trainer.epoch_online_nets if suffix == "_nets" else self.trainer.epoch_online
+        torch.cuda.current_stream(self.device).synchronize()
+        drawn = call(engine, self.flat.data_ptr(), M, B, selfplay._sample_index, prio.get("beta", 0.0),
+                     _capi.trained_priority_config(prio["alpha"], prio["eps"], prio["feedback"]), self._form.cfg(), state, opt_args[0],
+                     sums.data_ptr(), return_drawn=return_drawn)
+        selfplay._sample_index += M
+        if self._form.counts_steps:
+            self.opt_step += M
+        if tuned:
+            self.alpha_step += M
+        self.last_raw, self._last_d_raw = None, None   # (the minibatches' raw outputs stay in the native trainer)
+        table = sums.cpu().tolist()
+        slots = [(key, _capi.LOSS_KEYS.index(key)) for key in _capi.LOSS_KEYS_OF[self.loss_cfg.kind]]
+        out = [{key: row[i] for key, i in slots} for row in table]
+        return (out, drawn) if return_drawn else out
+
     def export_alpha(self) -> None:
         """Write every net's learned temperature and its Adam state (step, exp_avg, exp_avg_sq) back into its agent's loss object,
         so that ``agent.update`` or a checkpoint of ``agent.loss`` continues from where the trainer stands.  ``close()`` does this;

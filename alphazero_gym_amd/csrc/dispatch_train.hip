@@ -7,7 +7,8 @@
 // gradients first and norm, clip and update after the last layer; or that with every net's own entry of a device table), the state
 // pointers, and per minibatch the launch-ready TrainOptD and LossDims -- before the device scope is entered.  launch_forward,
 // launch_loss and launch_backward are the only places that choose between the forms and between train.cuh's kernels (plain,
-// LayerNorm) and dispatch_train_wide.hip's launches; a step is an epoch's minibatch body with one minibatch.
+// LayerNorm) and dispatch_train_wide.hip's launches; a step is an epoch's minibatch body with one minibatch.  The online epoch
+// (include/azgym_train_online.h) is an errors epoch whose gather is the engine's refresh, draw and gather (online_ring.h).
 #include <cmath>
 #include <cstdint>
 #include <memory>
@@ -17,7 +18,9 @@
 #include "../../include/azgym_train.h"
 #include "../../include/azgym_train_weighted.h"
 #include "../../include/azgym_train_errors.h"
+#include "../../include/azgym_train_online.h"
 #include "hip_host.h"
+#include "online_ring.h"
 #include "train.cuh"
 #include "train_wide_host.h"
 
@@ -748,6 +751,83 @@ static int epoch_impl(azg_trainer* t, const char* who, OptForm form, float* para
     return AZG_OK;
 }
 
+// include/azgym_train_online.h: an errors epoch of M whole minibatches over the engine's ring whose gather is the ring's refresh,
+// draw and gather (online_ring.h).  The checks are the loop's: the ring's, then epoch_impl's for M minibatches of batch_size rows.
+static int epoch_online_impl(azg_trainer* t, const char* who, OptForm form, azg_engine* e, float* params, const azg_online_epoch* cfg,
+                             const azg_loss_cfg* loss_cfg, const azg_alpha_state* alpha_state, const azg_optim* opt, double* loss_sums) {
+    if (!t) return AZG_E_INVALID;
+    const std::string w(who);
+    if (!e || !cfg) return tfail(t, AZG_E_INVALID, w + ": engine and cfg must not be NULL");
+    if (cfg->struct_size != (int32_t)sizeof(azg_online_epoch)) return tfail(t, AZG_E_INVALID, w + ": azg_online_epoch.struct_size mismatch");
+    if (cfg->n_minibatches < 1) return tfail(t, AZG_E_INVALID, w + ": n_minibatches must be at least 1");
+    if (cfg->batch_size < 1 || cfg->batch_size > t->max_batch) return tfail(t, AZG_E_INVALID, w + ": batch_size must be 1..max_batch");
+    if (!params || !loss_cfg || !opt || !loss_sums) return tfail(t, AZG_E_INVALID, w + ": NULL pointer");
+    OnlineRingShape ring;
+    if (int rc = online_ring_check(e, &cfg->prio, cfg->beta, &ring)) return tfail(t, rc, w + ": " + azg_last_error(e));
+    if (ring.device_id != t->device_id) return tfail(t, AZG_E_INVALID, w + ": the engine and the trainer are on different devices");
+    if (ring.n_nets != t->n_nets) return tfail(t, AZG_E_INVALID, w + ": the engine's n_nets is not the trainer's");
+    if (ring.obs_dim != t->net.in_dim) return tfail(t, AZG_E_INVALID, w + ": the engine's observation width must be the trainer's in_dim");
+    const int A = ring.n_actions, M = cfg->n_minibatches, B = cfg->batch_size;
+    if (A < 1 || A > TR_MAX_ACTIONS) return tfail(t, AZG_E_INVALID, w + ": the engine's action count must be 1..16");
+    // every refusal of azg_trainer_step, for every minibatch's Adam step (epoch_impl's)
+    TrainPlan plan(form);
+    plan.alpha = alpha_state;
+    plan.mb.assign((size_t)M, Minibatch{});
+    const bool stepped = alpha_state && loss_cfg->struct_size == (int32_t)sizeof(azg_loss_cfg) && loss_cfg->kind == AZG_LOSS_A0C_TUNED &&
+                         alpha_state->struct_size == (int32_t)sizeof(azg_alpha_state);
+    if (stepped && alpha_state->step > INT32_MAX - M) return tfail(t, AZG_E_INVALID, w + ": azg_alpha_state.step too large");
+    for (int m = 0; m < M; ++m) {
+        plan.mb[m].first = m * B; plan.mb[m].rows = B;
+        azg_alpha_state st{};
+        if (stepped) { st = *alpha_state; st.step += m; }
+        if (int rc = check_loss(t, who, B, A, loss_cfg, stepped ? &st : alpha_state, &plan.mb[m].c)) return rc;
+        if (int rc = check_optimiser(t, who, params, nullptr, nullptr, opt, &plan, m)) return rc;
+    }
+    if (form == OptForm::table) { if (int rc = plan_nets(t, who, params, opt, loss_cfg, stepped, A, &plan)) return rc; }
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    const RowWeights wt = with_errors(nullptr, ring.err);
+    const size_t K = (size_t)t->n_nets, mb = (size_t)t->max_batch, per = K * mb * t->net.NO, in_dim = (size_t)t->net.in_dim;
+    const size_t n_drawn = (size_t)M * K * (size_t)B;
+    if (int rc = ensure_loss_rows(t, wt)) return rc;
+    if (int rc = grow(t, t->stage_w, K * mb * sizeof(float))) return rc;
+    if (int rc = grow(t, t->stage_at, K * mb * sizeof(long long))) return rc;
+    if (int rc = ensure(t, t->d_raw_buf, per)) return rc;
+    if (int rc = ensure(t, t->raw_buf, per)) return rc;
+    if (int rc = grow(t, t->order_buf, n_drawn * sizeof(int32_t))) return rc;
+    if (int rc = grow(t, t->stage_buf, K * mb * (in_dim + 2 * (size_t)A + 1) * sizeof(float))) return rc;
+    if (int rc = grow(t, t->loss_table, (size_t)M * K * AZG_LOSS_SLOTS * sizeof(float))) return rc;
+    if (int rc = online_ring_enter(e)) return tfail(t, rc, w + ": " + azg_last_error(e));
+    float* loss_table = (float*)t->loss_table.p;
+    OnlineStage st;
+    st.n_rows = B;
+    st.obs = (float*)t->stage_buf.p;
+    st.actions = st.obs + K * mb * in_dim;
+    st.counts = st.actions + K * mb * (size_t)A;
+    st.values = st.counts + K * mb * (size_t)A;
+    st.w = (float*)t->stage_w.p;
+    st.at = (long long*)t->stage_at.p;
+    t->fwd_rows = 0;
+    t->step_rows = 0;
+    if (int rc = upload_nets(t, who, plan)) return rc;
+    for (int m = 0; m < M; ++m) {
+        st.drawn = (int*)t->order_buf.p + (size_t)m * K * B;
+        const hipError_t rc = online_ring_refresh(e, t->stream, cfg->prio, cfg->beta, cfg->sample_index + (uint32_t)m, st);
+        if (rc != hipSuccess) { (void)hipStreamSynchronize(t->stream); return tfail(t, AZG_E_DEVICE, w + ": " + hipGetErrorString(rc)); }
+        launch_minibatch(t, plan, m, params, st.obs, st.actions, st.counts, st.values, st.w, t->raw_buf, nullptr,
+                         loss_table + (size_t)m * K * AZG_LOSS_SLOTS, st.at, wt.errors);
+    }
+    const int n_sums = t->n_nets * AZG_LOSS_SLOTS;
+    hipLaunchKernelGGL(train_loss_sum_kernel, dim3((n_sums + 63) / 64), dim3(64), 0, t->stream, loss_table, M, n_sums, loss_sums);
+    if (cfg->drawn) {
+        const hipError_t down = hipMemcpyAsync(cfg->drawn, t->order_buf.p, n_drawn * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream);
+        if (down != hipSuccess) { (void)hipStreamSynchronize(t->stream); return tfail(t, AZG_E_DEVICE, w + ": " + hipGetErrorString(down)); }
+    }
+    if (int rc = finish(t, who)) return rc;
+    t->step_rows = B;
+    return AZG_OK;
+}
+
 extern "C" {
 
 int azg_trainer_forward(azg_trainer* t, const float* params, const float* obs, int32_t n_rows, float* raw) {
@@ -902,6 +982,19 @@ int azg_trainer_epoch_nets_errors(azg_trainer* t, float* params, const azg_epoch
                                   const azg_alpha_state* alpha_state, const azg_optim* opts, double* loss_sums, int32_t* n_minibatches) {
     return epoch_impl(t, "azg_trainer_epoch_nets_errors", OptForm::table, params, rows, with_errors(weights, errors), order, n_order, batch_size,
                       loss_cfgs, alpha_state, nullptr, nullptr, opts, loss_sums, n_minibatches);
+}
+
+// ---- the online epoch (include/azgym_train_online.h): an errors epoch whose every minibatch is redrawn from the engine's ring
+
+int azg_trainer_epoch_online(azg_trainer* t, azg_engine* e, float* params, const azg_online_epoch* cfg, const azg_loss_cfg* loss_cfg,
+                             const azg_alpha_state* alpha_state, const azg_optim* opt, double* loss_sums) {
+    return epoch_online_impl(t, "azg_trainer_epoch_online", OptForm::fused, e, params, cfg, loss_cfg, alpha_state, opt, loss_sums);
+}
+
+int azg_trainer_epoch_online_nets(azg_trainer* t, azg_engine* e, float* params, const azg_online_epoch* cfg,
+                                  const azg_loss_cfg* loss_cfgs, const azg_alpha_state* alpha_state, const azg_optim* opts,
+                                  double* loss_sums) {
+    return epoch_online_impl(t, "azg_trainer_epoch_online_nets", OptForm::table, e, params, cfg, loss_cfgs, alpha_state, opts, loss_sums);
 }
 
 int azg_trainer_read_d_raw(azg_trainer* t, int32_t n_rows, float* d_raw) {

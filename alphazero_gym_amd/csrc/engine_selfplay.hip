@@ -17,6 +17,8 @@
 #include "mlp.cuh"
 #include "aux_kernels.cuh"
 #include "priority.cuh"
+#include "priority_online.cuh"
+#include "online_ring.h"
 
 int launch_results(azg_engine* e) {
     if (!e->searched) return fail(e, AZG_E_STATE, "no search has run");
@@ -490,6 +492,19 @@ int azg_selfplay_sample_slots(azg_engine* e, uint32_t sample_index, int32_t* slo
 
 // ---- importance-sampling weights of the stored rows (include/azgym_priority.h)
 
+// the weights' memory, allocated by the first call that needs it (the engine's device is current)
+static int ensure_weights(azg_engine* e) {
+    ReplayRing& r = e->ring;
+    ReplayRing::Priorities& p = r.prio;
+    if (p.w) return AZG_OK;
+    // one block: the minima (uint64) in front of the weights, so a failure leaves nothing behind
+    const size_t n_min = p.segs + (size_t)e->cfg.n_trees, n_w = (size_t)r.cap * e->cfg.n_trees;
+    unsigned long long* block = nullptr;
+    if (dalloc(e, r.mem, &block, n_min + (n_w + 1) / 2)) return AZG_E_DEVICE;
+    p.w_min = block; p.w = reinterpret_cast<float*>(block + n_min);
+    return AZG_OK;
+}
+
 int azg_selfplay_is_weights(azg_engine* e, float beta) {
     if (int rc = sample_refusal(e, "azg_selfplay_is_weights")) return rc;
     if (!(beta >= 0.0f && std::isfinite(beta))) return fail(e, AZG_E_INVALID, "azg_selfplay_is_weights: beta must be finite and >= 0");
@@ -499,12 +514,7 @@ int azg_selfplay_is_weights(azg_engine* e, float beta) {
     PrioMin pm;
     if (int rc = ring_partition(e, "azg_selfplay_is_weights", &pm)) return rc;
     ON_DEVICE(e);
-    if (!p.w) {   // one block: the minima (uint64) in front of the weights, so a failure leaves nothing behind
-        const size_t n_min = p.segs + (size_t)e->cfg.n_trees, n_w = (size_t)r.cap * e->cfg.n_trees;
-        unsigned long long* block = nullptr;
-        if (dalloc(e, r.mem, &block, n_min + (n_w + 1) / 2)) return AZG_E_DEVICE;
-        p.w_min = block; p.w = reinterpret_cast<float*>(block + n_min);
-    }
+    if (int rc = ensure_weights(e)) return rc;
     pm.q = p.q; pm.seg_min = p.w_min; pm.net_min = p.w_min + p.segs;
     hipLaunchKernelGGL(prio_min_segments_kernel, dim3(pm.nseg, K), dim3(PR_THREADS), 0, e->stream, pm);
     HIPCHK(e, hipGetLastError());
@@ -586,12 +596,12 @@ int azg_selfplay_set_error_values(azg_engine* e, const float* err, size_t n_rows
     return AZG_OK;
 }
 
-int azg_selfplay_priorities_trained(azg_engine* e, const azg_trained_priority_config* c) {
+// What azg_selfplay_priorities_trained refuses, and the online epoch with it (online_ring_check)
+static int trained_priorities_refusal(azg_engine* e, const azg_trained_priority_config* c) {
     if (!e) return AZG_E_INVALID;
     if (!c) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities_trained: cfg must not be NULL");
     if (int rc = ring_refusal(e, NEED_PRIORITIES | NEED_ERRORS)) return rc;
-    ReplayRing& r = e->ring;
-    ReplayRing::Priorities& p = r.prio;
+    const ReplayRing& r = e->ring;
     if (c->struct_size != (int32_t)sizeof(azg_trained_priority_config)) return fail(e, AZG_E_INVALID, "azg_trained_priority_config size mismatch");
     if (c->unseen != AZG_UNSEEN_MAX && c->unseen != AZG_UNSEEN_VALUE_GAP && c->unseen != AZG_UNSEEN_CONSTANT)
         return fail(e, AZG_E_INVALID, "azg_selfplay_priorities_trained: unknown unseen");
@@ -601,24 +611,41 @@ int azg_selfplay_priorities_trained(azg_engine* e, const azg_trained_priority_co
     if (!(c->eps > 0.0f && std::isfinite(c->eps))) return fail(e, AZG_E_INVALID, "azg_selfplay_priorities_trained: eps must be finite and > 0");
     if (c->unseen == AZG_UNSEEN_CONSTANT && !(c->unseen_d >= 0.0f && std::isfinite(c->unseen_d)))
         return fail(e, AZG_E_INVALID, "azg_selfplay_priorities_trained: unseen_d must be finite and >= 0");
+    return AZG_OK;
+}
+
+// The two launches of a net's largest seen error, and the q kernel's arguments, from the partition both share
+static void launch_errmax(azg_engine* e, hipStream_t stream, PrioErrMax& pm) {
+    ReplayRing::Priorities& p = e->ring.prio;
+    pm.err = p.err; pm.seg_max = p.err_max; pm.net_max = p.err_max + p.segs;
+    hipLaunchKernelGGL(prio_errmax_segments_kernel, dim3(pm.nseg, e->n_nets), dim3(PR_THREADS), 0, stream, pm);
+    hipLaunchKernelGGL(prio_errmax_nets_kernel, dim3(e->n_nets), dim3(64), 0, stream, pm);
+}
+static PrioritiesTrained trained_args(azg_engine* e, const azg_trained_priority_config& c, int B, int T) {
+    const ReplayRing& r = e->ring;
+    PrioritiesTrained pr;
+    pr.rows_n = (long long)r.stored_rows(); pr.unseen = c.unseen;
+    pr.row_len = r.row; pr.vcol = r.row - 1; pr.B = B; pr.T = T;
+    pr.alpha = c.alpha; pr.eps = c.eps; pr.unseen_d = c.unseen_d;
+    pr.err = r.prio.err; pr.net_max = r.prio.err_max + r.prio.segs; pr.value = r.tr.value; pr.rows = r.rows; pr.q = r.prio.q;
+    return pr;
+}
+
+int azg_selfplay_priorities_trained(azg_engine* e, const azg_trained_priority_config* c) {
+    if (int rc = trained_priorities_refusal(e, c)) return rc;
+    ReplayRing& r = e->ring;
+    ReplayRing::Priorities& p = r.prio;
     PrioErrMax pm;
     if (int rc = ring_partition(e, "azg_selfplay_priorities_trained", &pm)) return rc;
     const size_t n = r.stored_rows();
     p.w_gen = -1;   // (weights computed from the priorities before these are no longer handed out)
     if (n == 0) { p.gen = r.rows_gen; return AZG_OK; }
     ON_DEVICE(e);
-    pm.err = p.err; pm.seg_max = p.err_max; pm.net_max = p.err_max + p.segs;
     if (c->unseen == AZG_UNSEEN_MAX) {
-        hipLaunchKernelGGL(prio_errmax_segments_kernel, dim3(pm.nseg, e->n_nets), dim3(PR_THREADS), 0, e->stream, pm);
-        HIPCHK(e, hipGetLastError());
-        hipLaunchKernelGGL(prio_errmax_nets_kernel, dim3(e->n_nets), dim3(64), 0, e->stream, pm);
+        launch_errmax(e, e->stream, pm);
         HIPCHK(e, hipGetLastError());
     }
-    PrioritiesTrained pr;
-    pr.rows_n = (long long)n; pr.unseen = c->unseen;
-    pr.row_len = r.row; pr.vcol = r.row - 1; pr.B = pm.B; pr.T = pm.T;
-    pr.alpha = c->alpha; pr.eps = c->eps; pr.unseen_d = c->unseen_d;
-    pr.err = p.err; pr.net_max = pm.net_max; pr.value = r.tr.value; pr.rows = r.rows; pr.q = p.q;
+    const PrioritiesTrained pr = trained_args(e, *c, pm.B, pm.T);
     hipLaunchKernelGGL(priorities_trained_kernel, dim3((unsigned)((n + PR_THREADS - 1) / PR_THREADS)), dim3(PR_THREADS), 0, e->stream, pr);
     HIPCHK(e, hipGetLastError());
     p.gen = r.rows_gen;
@@ -710,3 +737,53 @@ int azg_search_rollout(azg_engine* e, const azg_search_rollout_config* c, double
 }
 
 }  // extern "C"
+
+// ---- the online epoch's side of the ring (online_ring.h; include/azgym_train_online.h)
+
+int online_ring_check(azg_engine* e, const azg_trained_priority_config* prio, float beta, OnlineRingShape* shape) {
+    if (int rc = trained_priorities_refusal(e, prio)) return rc;
+    if (e->ring.steps == 0) return fail(e, AZG_E_STATE, "azg_trainer_epoch_online: the replay ring is empty");
+    if (!(beta >= 0.0f && std::isfinite(beta))) return fail(e, AZG_E_INVALID, "azg_selfplay_is_weights: beta must be finite and >= 0");
+    PrioScan ps;
+    if (int rc = ring_partition(e, "azg_trainer_epoch_online", &ps)) return rc;
+    shape->device_id = e->cfg.device_id; shape->n_nets = e->n_nets;
+    shape->obs_dim = e->S_obs; shape->n_actions = e->Kmax;
+    shape->err = e->ring.prio.err;
+    return AZG_OK;
+}
+
+int online_ring_enter(azg_engine* e) {
+    ON_DEVICE(e);
+    if (int rc = ensure_weights(e)) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->ring.prio.gen = e->ring.rows_gen;
+    e->ring.prio.w_gen = -1;
+    return AZG_OK;
+}
+
+hipError_t online_ring_refresh(azg_engine* e, hipStream_t stream, const azg_trained_priority_config& prio, float beta,
+                               uint32_t sample_index, const OnlineStage& stage) {
+    const ReplayRing& r = e->ring;
+    const ReplayRing::Priorities& p = r.prio;
+    const int K = e->n_nets;
+    PrioErrMax pm;
+    PrioScan ps;
+    if (ring_partition(e, "azg_trainer_epoch_online", &ps)) return hipErrorInvalidValue;   // (online_ring_check has passed it)
+    pm.B = ps.B; pm.T = ps.T; pm.N = ps.N; pm.nseg = ps.nseg;
+    if (prio.unseen == AZG_UNSEEN_MAX) launch_errmax(e, stream, pm);
+    ps.q = p.q; ps.within = p.within; ps.seg = p.seg;
+    OnlineRefresh on;
+    on.pr = trained_args(e, prio, ps.B, ps.T); on.ps = ps; on.seg_min = p.w_min;
+    hipLaunchKernelGGL(online_refresh_segments_kernel, dim3(ps.nseg, K), dim3(PR_THREADS), 0, stream, on);
+    unsigned long long* net_min = p.w_min + p.segs;
+    hipLaunchKernelGGL(online_refresh_nets_kernel, dim3(K), dim3(64), 0, stream, ps, (const pr_u64*)p.w_min, net_min);
+    OnlineDraw od;
+    od.ps = ps;
+    od.g.row_len = r.row; od.g.state_dim = e->S_obs; od.g.A = e->Kmax;
+    od.sample_index = sample_index; od.tree_base = (unsigned)e->cfg.tree_id_base; od.seed = e->cfg.seed;
+    od.beta = beta; od.n_rows = stage.n_rows; od.net_min = net_min; od.rows = r.rows;
+    od.obs = stage.obs; od.actions = stage.actions; od.counts = stage.counts; od.values = stage.values; od.wout = stage.w;
+    od.at_out = stage.at; od.drawn = stage.drawn;
+    hipLaunchKernelGGL(online_draw_gather_kernel, dim3((stage.n_rows + PR_THREADS / 64 - 1) / (PR_THREADS / 64), K), dim3(PR_THREADS), 0, stream, od);
+    return hipGetLastError();
+}

@@ -5,6 +5,8 @@
 // of uint64 values whose total stays below 2^63, so the sums are exact whatever the order and nothing here is atomic.  The
 // importance-sampling weights' kernels: a net's least q in the same two levels, then the weight of every stored row.  The priorities
 // fed back from the trainer's value errors (at the end): a net's largest seen error in those two levels, then q of every stored row.
+// The rules are device functions (priority_q, priority_trained_q, prio_scan_totals, prio_min_net, prio_draw_row, priority_is_weight):
+// priority_online.cuh's fused kernels call them too.
 #pragma once
 #include "../../include/azg_math.h"
 #include "../../include/azgym_priority.h"
@@ -102,9 +104,8 @@ __global__ __launch_bounds__(PR_THREADS) void prio_scan_segments_kernel(PrioScan
 
 // grid (n_nets), one wave: lane l folds the run of segments [l * per, l * per + per), the lanes' sums are scanned, then every lane
 // writes its run's inclusive prefix sums
-__global__ __launch_bounds__(64) void prio_scan_totals_kernel(PrioScan ps) {
-    pr_u64* seg = ps.seg + (size_t)blockIdx.x * ps.nseg;
-    const int lane = threadIdx.x;
+__device__ __forceinline__ void prio_scan_totals(const PrioScan& ps, int k, int lane) {
+    pr_u64* seg = ps.seg + (size_t)k * ps.nseg;
     const int per = (ps.nseg + 63) / 64;
     const int lo = lane * per < ps.nseg ? lane * per : ps.nseg;
     const int hi = lo + per < ps.nseg ? lo + per : ps.nseg;
@@ -113,6 +114,7 @@ __global__ __launch_bounds__(64) void prio_scan_totals_kernel(PrioScan ps) {
     pr_u64 acc = wave_scan_u64(sum, lane) - sum;   // the segments before this lane's run
     for (int s = lo; s < hi; ++s) { acc += seg[s]; seg[s] = acc; }
 }
+__global__ __launch_bounds__(64) void prio_scan_totals_kernel(PrioScan ps) { prio_scan_totals(ps, blockIdx.x, threadIdx.x); }
 
 // ------------------------------------------------------------------------------------------------ draws
 
@@ -131,6 +133,20 @@ __device__ __forceinline__ int prio_upper(const pr_u64* c, int n, pr_u64 target)
     return lo;
 }
 
+// Draw d of net k under sample_index (ps after both scans): the row number in the net's own numbering
+__device__ __forceinline__ int prio_draw_row(const PrioScan& ps, int k, unsigned long long seed, unsigned tree_base, unsigned sample_index,
+                                             int d) {
+    const pr_u64* seg = ps.seg + (size_t)k * ps.nseg;
+    const pr_u64* within = ps.within + (size_t)k * ps.N;
+    const azg_u32x4 w = azg_draw(seed, tree_base + (unsigned)(k * ps.T), sample_index, (unsigned)d, AZG_STREAM_SAMPLE);
+    const pr_u64 target = prio_target(w, seg[ps.nseg - 1]);
+    const int s = prio_upper(seg, ps.nseg, target);
+    const pr_u64 rest = target - (s ? seg[s - 1] : 0ull);
+    const int first = s * PR_SEG;
+    const int len = ps.N - first < PR_SEG ? ps.N - first : PR_SEG;
+    return first + prio_upper(within + first, len, rest);
+}
+
 // grid (ceil(n_order / PR_THREADS), n_nets): one thread per draw
 struct PrioRows {
     PrioScan ps;              // (after both scan kernels)
@@ -143,16 +159,7 @@ __global__ __launch_bounds__(PR_THREADS) void prio_draw_rows_kernel(PrioRows dr)
     const int k = blockIdx.y;
     const int d = blockIdx.x * PR_THREADS + threadIdx.x;
     if (d >= dr.n_order) return;
-    const PrioScan& ps = dr.ps;
-    const pr_u64* seg = ps.seg + (size_t)k * ps.nseg;
-    const pr_u64* within = ps.within + (size_t)k * ps.N;
-    const azg_u32x4 w = azg_draw(dr.seed, dr.tree_base + (unsigned)(k * ps.T), dr.sample_index, (unsigned)d, AZG_STREAM_SAMPLE);
-    const pr_u64 target = prio_target(w, seg[ps.nseg - 1]);
-    const int s = prio_upper(seg, ps.nseg, target);
-    const pr_u64 rest = target - (s ? seg[s - 1] : 0ull);
-    const int first = s * PR_SEG;
-    const int len = ps.N - first < PR_SEG ? ps.N - first : PR_SEG;
-    dr.order[(size_t)k * dr.n_order + d] = first + prio_upper(within + first, len, rest);
+    dr.order[(size_t)k * dr.n_order + d] = prio_draw_row(dr.ps, k, dr.seed, dr.tree_base, dr.sample_index, d);
 }
 
 // One thread per game column, walking its stored slots twice (the total, then the running sum); consecutive lanes are consecutive
@@ -229,11 +236,13 @@ __global__ __launch_bounds__(PR_THREADS) void prio_min_segments_kernel(PrioMin p
 }
 
 // grid (n_nets), one wave: lane l folds segments l, l + 64, ...; then the wave's least
-__global__ __launch_bounds__(64) void prio_min_nets_kernel(PrioMin pm) {
-    const pr_u64* seg = pm.seg_min + (size_t)blockIdx.x * pm.nseg;
+__device__ __forceinline__ pr_u64 prio_min_net(const pr_u64* seg, int nseg, int lane) {
     pr_u64 v = ~0ull;
-    for (int s = threadIdx.x; s < pm.nseg; s += 64) v = seg[s] < v ? seg[s] : v;
-    v = wave_min_u64(v);
+    for (int s = lane; s < nseg; s += 64) v = seg[s] < v ? seg[s] : v;
+    return wave_min_u64(v);
+}
+__global__ __launch_bounds__(64) void prio_min_nets_kernel(PrioMin pm) {
+    const pr_u64 v = prio_min_net(pm.seg_min + (size_t)blockIdx.x * pm.nseg, pm.nseg, threadIdx.x);
     if (threadIdx.x == 0) pm.net_min[blockIdx.x] = v;
 }
 
@@ -323,9 +332,8 @@ struct PrioritiesTrained {
     const float* rows;        // ... and the replay ring [capacity_steps][B][row_len]
     pr_u64* q;                // [capacity_steps][B]
 };
-__global__ __launch_bounds__(PR_THREADS) void priorities_trained_kernel(PrioritiesTrained pr) {
-    const long long idx = (long long)blockIdx.x * PR_THREADS + threadIdx.x;
-    if (idx >= pr.rows_n) return;
+// q of the stored row at element idx = slot * B + tree
+__device__ __forceinline__ pr_u64 priority_trained_q(const PrioritiesTrained& pr, long long idx) {
     float d = pr.err[idx];
     if (d == PR_ERR_UNSEEN) {
         if (pr.unseen == AZG_UNSEEN_MAX) {
@@ -342,5 +350,10 @@ __global__ __launch_bounds__(PR_THREADS) void priorities_trained_kernel(Prioriti
     pr_u64 q;
     if (pr.alpha != 0.0f && !(d < __builtin_inff())) q = d != d ? 1ull : 1ull << 40;
     else q = priority_q(d, pr.alpha, pr.eps);
-    pr.q[idx] = q;
+    return q;
+}
+__global__ __launch_bounds__(PR_THREADS) void priorities_trained_kernel(PrioritiesTrained pr) {
+    const long long idx = (long long)blockIdx.x * PR_THREADS + threadIdx.x;
+    if (idx >= pr.rows_n) return;
+    pr.q[idx] = priority_trained_q(pr, idx);
 }

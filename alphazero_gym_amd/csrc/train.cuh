@@ -29,6 +29,7 @@
 #include "../../include/azg_math.h"
 #include "../../include/azgym.h"
 #include "../../include/azgym_train.h"
+#include "gather_row.cuh"
 
 typedef float tr_f32x4 __attribute__((ext_vector_type(4)));
 
@@ -666,8 +667,7 @@ __global__ __launch_bounds__(TR_LOSS_THREADS) void train_loss_nets_kernel(const 
 // azg_trainer_epoch's two kernels: the minibatch gather in front of every step, and the sum of the steps' losses after the last.
 #define TR_GATHER_THREADS 256
 
-struct GatherDims {
-    int row_len, state_dim, A;      // floats of a replay row: obs[state_dim] | actions[A] | counts[A] | Q[A] | V
+struct GatherDims : GatherRow {     // (gather_row.cuh: the row's layout and its copy)
     int group, n_order;
     long long group_stride, net_stride;
 };
@@ -685,15 +685,7 @@ __global__ __launch_bounds__(TR_GATHER_THREADS) void train_gather_kernel(GatherD
     const long long at = (long long)(i / g.group) * g.group_stride + (long long)net * g.net_stride + (long long)(i % g.group);
     const float* src = rows + at * g.row_len;
     const size_t out = (size_t)net * n_rows + b;
-    const int a0 = g.state_dim, c0 = a0 + g.A, q0 = c0 + g.A, v0 = g.row_len - 1;
-    for (int c = lane; c < g.row_len; c += 64) {
-        if (c >= q0 && c < v0) continue;
-        const float x = src[c];
-        if (c < a0) obs[out * g.state_dim + c] = x;
-        else if (c < c0) actions[out * g.A + (c - a0)] = x;
-        else if (c < q0) counts[out * g.A + (c - c0)] = x;
-        else values[out] = x;
-    }
+    gather_row(g, src, out, lane, obs, actions, counts, values);
 }
 
 // One thread per (net, slot): table [n_minibatches][n_nets * AZG_LOSS_SLOTS] float32 -> sums [n_nets * AZG_LOSS_SLOTS] float64, the
@@ -795,15 +787,7 @@ __global__ __launch_bounds__(TR_GATHER_THREADS) void train_gather_weighted_kerne
     const long long at = (long long)(i / g.group) * g.group_stride + (long long)net * g.net_stride + (long long)(i % g.group);
     const float* src = rows + at * g.row_len;
     const size_t out = (size_t)net * n_rows + b;
-    const int a0 = g.state_dim, c0 = a0 + g.A, q0 = c0 + g.A, v0 = g.row_len - 1;
-    for (int c = lane; c < g.row_len; c += 64) {
-        if (c >= q0 && c < v0) continue;
-        const float x = src[c];
-        if (c < a0) obs[out * g.state_dim + c] = x;
-        else if (c < c0) actions[out * g.A + (c - a0)] = x;
-        else if (c < q0) counts[out * g.A + (c - c0)] = x;
-        else values[out] = x;
-    }
+    gather_row(g, src, out, lane, obs, actions, counts, values);
     if (lane == 0) wout[out] = weights[at];
 }
 
@@ -842,15 +826,7 @@ __global__ __launch_bounds__(TR_GATHER_THREADS) void train_gather_errors_kernel(
     const long long at = (long long)(i / g.group) * g.group_stride + (long long)net * g.net_stride + (long long)(i % g.group);
     const float* src = rows + at * g.row_len;
     const size_t out = (size_t)net * n_rows + b;
-    const int a0 = g.state_dim, c0 = a0 + g.A, q0 = c0 + g.A, v0 = g.row_len - 1;
-    for (int c = lane; c < g.row_len; c += 64) {
-        if (c >= q0 && c < v0) continue;
-        const float x = src[c];
-        if (c < a0) obs[out * g.state_dim + c] = x;
-        else if (c < c0) actions[out * g.A + (c - a0)] = x;
-        else if (c < q0) counts[out * g.A + (c - c0)] = x;
-        else values[out] = x;
-    }
+    gather_row(g, src, out, lane, obs, actions, counts, values);
     if (lane == 0) { wout[out] = weights ? weights[at] : 1.0f; at_out[out] = at; }
 }
 #endif  // TR_NO_SHARED_KERNELS

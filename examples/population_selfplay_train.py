@@ -42,7 +42,9 @@ device-fused pass the gathered weights to update.  It needs one of those three t
 --prioritized-feedback {max,value_gap} closes the loop: with --trainer device-epoch every iteration runs priorities -> sample_order ->
 is_weights -> train_epoch_ring(errors=True), the epoch's loss launches write each trained row's |V - z| into the engine's ring and the
 next draw's priorities come from those errors; rows not trained on since they were stored take the net's largest trained error (max)
-or |search value - value target| (value_gap).
+or |search value - value target| (value_gap).  --prioritized-online beside it is prioritised replay as published: the iteration's
+ceil(train-rows / batch-size) minibatches run in one native call (train_online_ring), each drawn from priorities refreshed with the
+errors of the minibatches before it.
 The draw is with replacement and biased; the loss is not reweighted (no importance-sampling weights).
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
@@ -146,6 +148,10 @@ def parse_args(argv=None):
                          "rows they trained on, written by the training epoch's loss launches into the engine's ring; a row not trained "
                          "on since it was stored takes the largest trained error of its net (max) or |search value - value target| "
                          "(value_gap); needs --prioritized-alpha and --trainer device-epoch (default: off, nothing is kept)")
+    ap.add_argument("--prioritized-online", action="store_true",
+                    help="prioritised replay as published: one native call per iteration (train_online_ring) trains "
+                         "ceil(train-rows / batch-size) minibatches, each drawn from priorities refreshed with the errors of the "
+                         "minibatches before it; needs --prioritized-feedback (default: off, one draw per iteration)")
     a = ap.parse_args(argv)
     why = check_replay(a)
     if why:
@@ -227,6 +233,8 @@ def check_replay(a):
         if a.trainer != "device-epoch":
             return ("--prioritized-feedback: the errors come out of the native epoch over the ring: use --trainer device-epoch (the "
                     "per-agent update loop of --trainer torch and the update calls of device and device-fused write none)")
+    if getattr(a, "prioritized_online", False) and getattr(a, "prioritized_feedback", None) is None:
+        return "--prioritized-online redraws from the learners' own errors: it needs --prioritized-feedback (and --trainer device-epoch)"
     if a.reanalyse_slots and not (a.replay_steps or a.trainer == "device-epoch"):
         return ("--reanalyse-slots rewrites rows that stay in the device ring: use it with --replay-steps R (the FIFO ring) or with "
                 "--trainer device-epoch; the other modes copy the rows out and clear the ring every iteration")
@@ -341,10 +349,15 @@ def train(a, log=print, on_rows=None, on_end=None):
                 on_rows(it, rows)
         losses = []
         # (net k's rows are numbered slot * T + game in the ring and in _split's copies alike)
-        prio_order = sp.sample_order(min(a.train_rows, n_ring)) if by_priority else None
-        if weighted:   # the weights of the priorities the draw was just made from
+        online = feedback and rows is None and getattr(a, "prioritized_online", False)
+        prio_order = sp.sample_order(min(a.train_rows, n_ring)) if by_priority and not online else None
+        if weighted and not online:   # the weights of the priorities the draw was just made from
             sp.is_weights()
-        if rows is None:   # the other trainers' picks and shuffles from the same streams, composed into one order per net
+        if online:   # every minibatch redrawn from the refreshed priorities, inside one native call
+            n_mb = -(-min(a.train_rows, n_ring) // a.batch_size)
+            infos = trainer.train_online_ring(sp, n_mb, batch_size=a.batch_size)
+            losses = [info["loss"] / n_mb for info in infos]
+        elif rows is None:   # the other trainers' picks and shuffles from the same streams, composed into one order per net
             order = []
             for k, rng in enumerate(rngs):
                 pick = pick_rows(k, rng, n_ring)

@@ -26,7 +26,9 @@ optimiser steps go through a one-net PopulationTrainer(losses="device"), whose u
 --prioritized-feedback {max,value_gap} closes the loop: every iteration runs priorities -> sample_order -> is_weights -> one native
 epoch over the ring (train_epoch_ring(errors=True)) whose loss launches write each trained row's |V - z| into the engine's ring, and the
 next draw's priorities come from those errors; rows not trained on since they were stored take the largest trained error (max) or
-|search value - value target| (value_gap).
+|search value - value target| (value_gap).  --prioritized-online beside it is prioritised replay as published: the iteration's
+ceil(train-rows / batch-size) minibatches run in one native call (PopulationTrainer.train_online_ring), each drawn from priorities
+refreshed with the errors of the minibatches before it.
 
 --eval-search-episodes E adds eval_search_return: after every iteration every game plays E whole episodes under MCTS with the greedy
 final-action rule, on the device in one call and on state of its own (DeviceSelfPlay.evaluate_search): the return of the agent as it
@@ -115,6 +117,10 @@ def parse_args(argv=None):
                          "rows it trained on, written by the training epoch's loss launches into the engine's ring; a row not trained "
                          "on since it was stored takes the largest trained error (max) or |search value - value target| (value_gap); "
                          "needs --prioritized-alpha (default: off, nothing is kept)")
+    ap.add_argument("--prioritized-online", action="store_true",
+                    help="prioritised replay as published: one native call per iteration (train_online_ring) trains "
+                         "ceil(train-rows / batch-size) minibatches, each drawn from priorities refreshed with the errors of the "
+                         "minibatches before it; needs --prioritized-feedback (default: off, one draw per iteration)")
     a = ap.parse_args(argv)
     if a.eval_search_episodes < 0:
         ap.error("--eval-search-episodes must be >= 0")
@@ -143,6 +149,8 @@ def parse_args(argv=None):
             ap.error("--prioritized-beta must be finite and >= 0")
     if a.prioritized_feedback is not None and a.prioritized_alpha is None:
         ap.error("--prioritized-feedback feeds the priorities of the prioritised draw: it needs --prioritized-alpha A")
+    if a.prioritized_online and a.prioritized_feedback is None:
+        ap.error("--prioritized-online redraws from the learner's own errors: it needs --prioritized-feedback")
     return a
 
 
@@ -218,11 +226,17 @@ def train(a, log=print):
             # and the world size are: the job as a whole plays a.games * world games)
             rows = D.gather_replay_rows(rows, counts=[rows.shape[0]] * world)
         info = {"loss": 0.0}
-        if prioritized:   # (the ring's rows in slot order are the engine's own numbering slot * games + game)
+        online = feedback and getattr(a, "prioritized_online", False)
+        if online:   # every minibatch redrawn from the refreshed priorities, inside one native call
+            pick = np.empty(-(-min(a.train_rows, rows.shape[0]) // a.batch_size) * a.batch_size, np.int64)
+        elif prioritized:   # (the ring's rows in slot order are the engine's own numbering slot * games + game)
             pick = sp.sample_order(min(a.train_rows, rows.shape[0]))[0].astype(np.int64)
         else:
             pick = rng.choice(rows.shape[0], size=min(a.train_rows, rows.shape[0]), replace=False)
-        if feedback:   # priorities -> sample_order -> is_weights -> one native epoch over the ring that writes the rows' errors back
+        if online:
+            info = trainer.train_online_ring(sp, len(pick) // a.batch_size, batch_size=a.batch_size)[0]
+            sp.upload_flat(trainer.desc, trainer.flat)
+        elif feedback:   # priorities -> sample_order -> is_weights -> one native epoch over the ring that writes the rows' errors back
             if weighted:
                 sp.is_weights()
             order = pick[np.random.RandomState(it).permutation(len(pick))][None, :]

@@ -25,7 +25,8 @@
  * the plain epoch when weights is NULL.  The caller vouches for the addresses.  The first call allocates the weighted path's scratch
  * and, for an epoch, the staged indices ([n_nets][max_batch] int64); the other paths' allocations do not change.
  *
- * Not provided: errors from azg_trainer_step_*; an epoch's priorities are fixed while it runs (no re-draw between its minibatches). */
+ * Not provided: errors from azg_trainer_step_*.  These epochs' priorities are fixed while they run; azgym_train_online.h redraws every
+ * minibatch from priorities refreshed with the errors of the minibatches before it. */
 #ifndef AZGYM_TRAIN_ERRORS_H
 #define AZGYM_TRAIN_ERRORS_H
 #include "azgym_train_weighted.h"
