@@ -101,6 +101,11 @@ class AzgNstepConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_step", C.c_int32), ("gamma", C.c_double), ("flags", C.c_int32)]
 
 
+class AzgReturnRule(C.Structure):
+    """include/azgym_lambda.h: azg_return_rule"""
+    _fields_ = [("struct_size", C.c_int32), ("n_step", C.c_int32), ("lambda_", C.c_double), ("gamma", C.c_double), ("flags", C.c_int32)]
+
+
 NSTEP_SEARCH_GAMMA = 1   # AZG_NSTEP_SEARCH_GAMMA: discount with the search's own gamma (the row's net's where a per-net table is set)
 END_NONE, END_TERMINAL, END_LENGTH = 0, 1, 2   # AZG_END_*: how a stored self-play step ended
 
@@ -199,6 +204,7 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "set_net_search_ex",
                     "population_selfplay_begin", "selfplay_keep_states", "selfplay_states", "selfplay_reanalyse",
                     "selfplay_keep_transitions", "selfplay_transitions", "selfplay_nstep_targets",
+                    "selfplay_lambda_targets", "selfplay_lambda_targets_nets",
                     "selfplay_keep_priorities", "selfplay_priorities", "selfplay_priority_values", "selfplay_sample_rows",
                     "selfplay_sample_slots", "selfplay_is_weights", "selfplay_is_weights_device", "selfplay_is_weight_values",
                     "selfplay_keep_errors", "selfplay_errors_device", "selfplay_error_values", "selfplay_set_error_values",
@@ -369,6 +375,9 @@ def bind(lib, prefix):
         f["selfplay_transitions"].argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                               C.c_size_t]
         f["selfplay_nstep_targets"].argtypes = [vp, C.POINTER(AzgNstepConfig)]
+    if "selfplay_lambda_targets" in f:   # include/azgym_lambda.h
+        f["selfplay_lambda_targets"].argtypes = [vp, C.POINTER(AzgReturnRule)]
+        f["selfplay_lambda_targets_nets"].argtypes = [vp, C.POINTER(AzgReturnRule)]
     if "selfplay_sample_rows" in f:   # include/azgym_priority.h
         f["selfplay_keep_priorities"].argtypes = [vp, C.c_int32]
         f["selfplay_priorities"].argtypes = [vp, C.POINTER(AzgPriorityConfig)]
@@ -640,6 +649,8 @@ class Engine:
         """azg_set_population: trees k*T .. k*T+T-1 (T = n_trees / n_nets) are searched with net k's weights.  Drops every weight
         when n_nets changes; 1 is the single-network engine."""
         self._check(self._optional("set_population")(self._h, int(n_nets)))
+        if int(n_nets) != getattr(self, "n_nets", 1):   # (the engine dropped its per-net search table with the old split)
+            self._net_search_gamma = None
         self.n_nets = int(n_nets)
 
     def set_net_search(self, settings, wide=False, n_sims=None):
@@ -657,6 +668,7 @@ class Engine:
             fn = self._optional("set_net_search")
         if settings is None:
             self._check(fn(self._h, None, 0))
+            self._net_search_gamma = None
             return
         settings = list(settings)
         if n_sims is not None:
@@ -670,6 +682,7 @@ class Engine:
             for key in NET_SEARCH_KEYS:
                 setattr(arr[k], key, float(st[key]))
         self._check(fn(self._h, arr, len(settings)))
+        self._net_search_gamma = [float(arr[k].gamma) for k in range(len(settings))]   # (selfplay_lambda_targets resolves a None among numbers from it)
 
     def set_net_weights(self, net, desc, blob):
         blob = np.ascontiguousarray(blob, dtype=np.float32)
@@ -1047,6 +1060,44 @@ def _selfplay_methods():
         c.flags = NSTEP_SEARCH_GAMMA if gamma is None else 0
         self._check(self._optional("selfplay_nstep_targets")(self._h, C.byref(c)))
 
+    def selfplay_lambda_targets(self, n_step, td_lambda, gamma=None):
+        """azg_selfplay_lambda_targets / _nets: rewrite every stored row's V_target column as the lambda-return of its game column
+        from the kept transitions -- selfplay_nstep_targets' window of ``n_step`` steps, inside which the returns of the windows 1 ..
+        n_step are mixed with weights (1 - lambda) lambda^(m-1), the longest taking the rest (include/azgym_lambda.h; asynchronous).
+        ``td_lambda`` 1 is the n-step return, 0 the 1-step return.  Each argument is a scalar or a sequence with one value per net;
+        any sequence selects the per-net call, in which net k's games follow entry k.  ``gamma`` None: the search's own gamma, the
+        row's net's where a per-net table is set; a sequence may hold None beside numbers (that net: its search's gamma)."""
+        K = int(getattr(self, "n_nets", 1))
+
+        def seq(x):
+            return x is not None and np.ndim(x) > 0
+
+        if not (seq(n_step) or seq(td_lambda) or seq(gamma)):
+            c = AzgReturnRule()
+            c.struct_size = C.sizeof(AzgReturnRule)
+            c.n_step, c.lambda_ = int(n_step), float(td_lambda)
+            c.gamma = 0.0 if gamma is None else float(gamma)
+            c.flags = NSTEP_SEARCH_GAMMA if gamma is None else 0
+            self._check(self._optional("selfplay_lambda_targets")(self._h, C.byref(c)))
+            return
+        cols = {}
+        for name, x in (("n_step", n_step), ("td_lambda", td_lambda), ("gamma", gamma)):
+            cols[name] = list(x) if seq(x) else [x] * K
+            if len(cols[name]) != K:
+                raise ValueError(f"selfplay_lambda_targets: {name} has {len(cols[name])} entries for {K} nets: a scalar or one per net")
+        gammas = cols["gamma"]
+        search = all(g is None for g in gammas)
+        if not search and any(g is None for g in gammas):   # (the flag is one for the call: resolve the search's gammas here)
+            own = getattr(self, "_net_search_gamma", None)
+            gammas = [(float(self.cfg.gamma) if own is None else own[k]) if g is None else g for k, g in enumerate(gammas)]
+        arr = (AzgReturnRule * K)()
+        for k in range(K):
+            arr[k].struct_size = C.sizeof(AzgReturnRule)
+            arr[k].n_step, arr[k].lambda_ = int(cols["n_step"][k]), float(cols["td_lambda"][k])
+            arr[k].gamma = 0.0 if search else float(gammas[k])
+            arr[k].flags = NSTEP_SEARCH_GAMMA if search else 0
+        self._check(self._optional("selfplay_lambda_targets_nets")(self._h, arr))
+
     def selfplay_keep_priorities(self, on=True):
         """azg_selfplay_keep_priorities: keep a fixed-point priority per stored row beside the replay ring, and the scratch of the
         proportional draws (include/azgym_priority.h).  After a begin, at any ring size; the next begin drops it."""
@@ -1140,7 +1191,7 @@ def _selfplay_methods():
 
     for fn in (selfplay_begin, population_selfplay_begin, selfplay_ring, selfplay_rows_device, selfplay_step, selfplay_rows, selfplay_clear, selfplay_stats,
                selfplay_keep_states, selfplay_states, selfplay_reanalyse, selfplay_keep_transitions, selfplay_transitions,
-               selfplay_nstep_targets, selfplay_keep_priorities, selfplay_priorities, selfplay_priority_values, selfplay_sample_rows,
+               selfplay_nstep_targets, selfplay_lambda_targets, selfplay_keep_priorities, selfplay_priorities, selfplay_priority_values, selfplay_sample_rows,
                selfplay_sample_slots, selfplay_is_weights, selfplay_is_weights_device, selfplay_is_weight_values):
         setattr(Engine, fn.__name__, fn)
 

@@ -9,6 +9,7 @@
 // end of this file (azgym_search_rollout.h): whole evaluation episodes under MCTS, the same step without a replay row.
 #pragma once
 #include "records.h"
+#include "replay_ring.h"
 #include "env.cuh"
 #include "tree.cuh"
 #include "results.cuh"
@@ -410,6 +411,50 @@ __global__ __launch_bounds__(NS_THREADS) void nstep_targets_kernel(NStep ns) {
     if (!terminal) { acc = ns.value[at(L)]; i = L - 1; }
     for (; i >= s; --i) acc = ns.reward[at(i)] + gamma * acc;
     ns.rows[at(s) * (size_t)ns.row_len + ns.vcol] = (float)acc;
+}
+
+// ------------------------------------------------------------------------------------------------ lambda-return targets
+
+// The same column by a rule per net (azg_selfplay_lambda_targets / _nets, include/azgym_lambda.h states the rule): net tree / T mixes
+// the returns of the windows 1 .. n_step with its own lambda and discounts with its own gamma.  The host resolves every net's rule
+// into one record of the table below (n_step clamped to the ring's size, gamma the search's where the flag asks for it, om = 1 - lambda).
+// One thread per stored row in nstep_targets_kernel's order, its scan for the window's far end, and its fold with one more load per
+// step: the kept value of the step after the one whose reward is added.
+struct LambdaTargets {
+    int B, T;                 // games; games per net
+    int size, oldest;         // stored steps; the ring slot of the oldest one
+    int row_len, vcol;        // a row's length and its V_target column
+    const ReturnRuleRec* rules;   // [n_nets] (replay_ring.h)
+    const double* reward; const double* value; const int* end;   // [capacity_steps][B]
+    float* rows;              // the replay ring [capacity_steps][B][row_len]
+};
+__global__ __launch_bounds__(NS_THREADS) void lambda_targets_kernel(LambdaTargets lt) {
+    const long long idx = (long long)blockIdx.x * NS_THREADS + threadIdx.x;
+    if (idx >= (long long)lt.size * lt.B) return;
+    const int s = (int)(idx / lt.B), tree = (int)(idx - (long long)s * lt.B);
+    const ReturnRuleRec rule = lt.rules[tree / lt.T];
+    const int last = lt.size - 1;
+    // element (position p, tree) of a [slot][tree] array (p <= last: the sum stays below 2 * size)
+    auto at = [&](int p) { int slot = lt.oldest + p; if (slot >= lt.size) slot -= lt.size; return (size_t)slot * lt.B + tree; };
+    // the window's far end: the first step in s .. s + n_step - 1 that ended its episode, else L = min(s + n_step, last)
+    int L = s + rule.n_step < last ? s + rule.n_step : last;
+    const int hi = s + rule.n_step - 1 < last ? s + rule.n_step - 1 : last;
+    bool terminal = false;
+    for (int i = s; i <= hi; ++i) {
+        const int end = lt.end[at(i)];
+        if (end != AZG_END_NONE) { L = i; terminal = end == AZG_END_TERMINAL; break; }
+    }
+    double acc = 0.0;
+    int i = L;
+    if (!terminal) { acc = lt.value[at(L)]; i = L - 1; }
+    // the first fold: the plain bootstrap from L's search value, or the terminal step's reward alone
+    if (i >= s) { acc = lt.reward[at(i)] + rule.gamma * acc; --i; }
+    // every nearer step mixes the search value of the step after it into what comes back from beyond
+    for (; i >= s; --i) {
+        const double mix = rule.om * lt.value[at(i + 1)] + rule.lambda * acc;
+        acc = lt.reward[at(i)] + rule.gamma * mix;
+    }
+    lt.rows[at(s) * (size_t)lt.row_len + lt.vcol] = (float)acc;
 }
 
 // ------------------------------------------------------------------------------------------------ search rollouts

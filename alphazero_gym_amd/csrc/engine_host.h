@@ -138,6 +138,7 @@ struct azg_engine : EngineQueue {
     DeviceAllocs net_search_mem; NetSearchTable net_search{};
     int net_search_wide = 0;
     int net_sims_max = 0;    // the table's largest per-net simulation budget (azg_net_search::n_sims): the per-layer launches' step count
+    std::vector<double> net_search_gamma;   // the table's gammas [n_nets] on the host (the lambda-return rules resolve theirs from it); empty: no table
     DeviceAllocs stamp_mem; size_t stamp_n = 0;   // rows of the diagnostic stamp buffer (P.stamps)
     uint32_t last_search_idx = 0;   // the search index the last search ran under (azg_dump_tree re-runs it with this one)
     float ms_kept = 0.0f; int ms_kept_valid = 0;   // kernel time of the last search, kept across azg_dump_tree's re-run of it

@@ -1,7 +1,7 @@
 // engine_selfplay.hip -- the C ABI's device-resident self-play (azg_selfplay_*, azg_population_selfplay_begin), the reanalysis of its
-// replay ring (azgym_reanalyse.h), the ring's n-step return targets (azgym_nstep.h), its prioritised sampling (azgym_priority.h), the
+// replay ring (azgym_reanalyse.h), the ring's n-step and lambda-return targets (azgym_nstep.h, azgym_lambda.h), its prioritised sampling (azgym_priority.h), the
 // search rollouts (azgym_search_rollout.h) and the launches of the small kernels after a search: results_kernel, the self-play step,
-// the reanalysis' gather and row kernels, the n-step target kernel, the priority, scan, draw and error-maximum kernels and the search rollouts' step
+// the reanalysis' gather and row kernels, the n-step and lambda target kernels, the priority, scan, draw and error-maximum kernels and the search rollouts' step
 // (aux_kernels.cuh and priority.cuh are compiled in this unit only).  The ring is the engine's one ReplayRing (replay_ring.h); what its
 // entry points share stands once, in front of them: their refusals, the row-aligned download, the keep_* calls' allocate-once, the
 // per-net partition, the launch after a search and the scoped swap of the engine's roots (reanalysis, search rollouts).
@@ -12,6 +12,7 @@
 #include "engine_host.h"
 #include "../../include/azgym_reanalyse.h"
 #include "../../include/azgym_nstep.h"
+#include "../../include/azgym_lambda.h"
 #include "../../include/azgym_priority.h"
 #include "../../include/azgym_search_rollout.h"
 #include "mlp.cuh"
@@ -388,6 +389,72 @@ int azg_selfplay_nstep_targets(azg_engine* e, const azg_nstep_config* c) {
     HIPCHK(e, hipGetLastError());
     return AZG_OK;
 }
+
+// ---- lambda-return targets (include/azgym_lambda.h)
+
+// Both calls: entry k of `rules` is net k's rule, or rules[0] every net's (one: azg_selfplay_lambda_targets).  Everything is refused
+// before the table's host side is touched; then one copy and one launch on the engine's stream.
+static int lambda_targets(azg_engine* e, const azg_return_rule* rules, bool one, const char* who_) {
+    if (!e) return AZG_E_INVALID;
+    const std::string who = who_;
+    if (!rules) return fail(e, AZG_E_INVALID, who + ": the rule must not be NULL");
+    if (int rc = ring_refusal(e, NEED_TRANSITIONS, ": the stored steps' rewards and ends were not kept")) return rc;
+    const int K = e->n_nets;
+    for (int k = 0; k < (one ? 1 : K); ++k) {
+        const azg_return_rule& c = rules[k];
+        const std::string net = one ? who + ": " : who + ": net " + std::to_string(k) + ": ";
+        if (k > 0 && c.struct_size != rules[0].struct_size)
+            return fail(e, AZG_E_INVALID, who + ": struct_size of net " + std::to_string(k) + " differs from net 0's (it must be equal in every entry)");
+        if (c.struct_size != (int32_t)sizeof(azg_return_rule)) return fail(e, AZG_E_INVALID, net + "azg_return_rule size mismatch");
+        if (k > 0 && c.flags != rules[0].flags)
+            return fail(e, AZG_E_INVALID, who + ": flags of net " + std::to_string(k) + " differs from net 0's (it must be equal in every entry)");
+        if (c.n_step < 0) return fail(e, AZG_E_INVALID, net + "n_step must be >= 0");
+        if (c.flags & ~(int32_t)AZG_NSTEP_SEARCH_GAMMA) return fail(e, AZG_E_INVALID, net + "unknown flag bits (AZG_NSTEP_SEARCH_GAMMA is the only flag)");
+        if (!(c.lambda >= 0.0 && c.lambda <= 1.0)) return fail(e, AZG_E_INVALID, net + "lambda must be in [0, 1]");
+        if (!(c.flags & AZG_NSTEP_SEARCH_GAMMA) && !(c.gamma >= 0.0 && std::isfinite(c.gamma)))
+            return fail(e, AZG_E_INVALID, net + "gamma must be finite and >= 0 (or set AZG_NSTEP_SEARCH_GAMMA)");
+    }
+    ReplayRing& r = e->ring;
+    if (r.steps == 0) return AZG_OK;
+    ON_DEVICE(e);
+    const bool search_gamma = (rules[0].flags & AZG_NSTEP_SEARCH_GAMMA) != 0;
+    // the search's gammas: per net where a table is set (the host keeps them beside it), azg_config's otherwise
+    const bool per_net = search_gamma && e->net_search.rec;
+    if (per_net && (int)e->net_search_gamma.size() != K) return fail(e, AZG_E_STATE, who + ": the per-net search table was not set completely (azg_set_net_search failed)");
+    ReplayRing::ReturnRules& t = r.rules;
+    if (t.n < K) {
+        ReturnRuleRec* d = nullptr;
+        if (dalloc(e, r.mem, &d, (size_t)K)) return AZG_E_DEVICE;
+        t.d = d; t.n = K;
+    }
+    if (!r.rules_copied) HIPCHK(e, hipEventCreateWithFlags(&r.rules_copied, hipEventDisableTiming));
+    else HIPCHK(e, hipEventSynchronize(r.rules_copied));   // (the last call's copy has read the host side: it may be rewritten)
+    t.h.resize(K);
+    for (int k = 0; k < K; ++k) {
+        const azg_return_rule& c = rules[one ? 0 : k];
+        ReturnRuleRec& rec = t.h[k];
+        rec.n_step = c.n_step < r.steps ? c.n_step : r.steps;   // (a longer window cannot reach further)
+        rec.pad = 0;
+        rec.lambda = c.lambda; rec.om = 1.0 - c.lambda;
+        rec.gamma = !search_gamma ? c.gamma : per_net ? e->net_search_gamma[k] : e->cfg.gamma;
+    }
+    HIPCHK(e, hipMemcpyAsync(t.d, t.h.data(), (size_t)K * sizeof(ReturnRuleRec), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipEventRecord(r.rules_copied, e->stream));
+    LambdaTargets lt;
+    lt.B = e->cfg.n_trees; lt.T = e->cfg.n_trees / K;
+    lt.size = r.steps; lt.oldest = r.insert;   // (as azg_selfplay_nstep_targets)
+    lt.row_len = r.row; lt.vcol = r.row - 1;
+    lt.rules = t.d;
+    lt.reward = r.tr.reward; lt.value = r.tr.value; lt.end = r.tr.end; lt.rows = r.rows;
+    const long long rows = (long long)lt.size * lt.B;
+    hipLaunchKernelGGL(lambda_targets_kernel, dim3((unsigned)((rows + NS_THREADS - 1) / NS_THREADS)), dim3(NS_THREADS), 0, e->stream, lt);
+    HIPCHK(e, hipGetLastError());
+    return AZG_OK;
+}
+
+int azg_selfplay_lambda_targets(azg_engine* e, const azg_return_rule* rule) { return lambda_targets(e, rule, true, "azg_selfplay_lambda_targets"); }
+
+int azg_selfplay_lambda_targets_nets(azg_engine* e, const azg_return_rule* rules) { return lambda_targets(e, rules, false, "azg_selfplay_lambda_targets_nets"); }
 
 // ---- prioritised sampling (include/azgym_priority.h)
 

@@ -334,6 +334,7 @@ int azg_set_population(azg_engine* e, int32_t n_nets) {
     e->net_search_mem.clear();
     e->net_search_wide = 0;
     e->net_sims_max = 0;
+    e->net_search_gamma.clear();
     e->n_nets = n_nets;
     e->net_have.assign(n_nets, 0);
     e->mlp_ready = 0; e->results_valid = 0; e->redo_ok = 0; e->searched = 0;
@@ -399,6 +400,7 @@ static int set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_n
         e->net_search_mem.clear();
         e->net_search_wide = 0;
         e->net_sims_max = 0;
+        e->net_search_gamma.clear();
         return AZG_OK;
     }
     if (!e->net_search.rec) {
@@ -414,6 +416,8 @@ static int set_net_search(azg_engine* e, const azg_net_search* nets, int32_t n_n
     HIPCHK(e, hipStreamSynchronize(e->stream));   // (the staging vectors go when this returns)
     e->net_search_wide = wide ? 1 : 0;
     e->net_sims_max = sims_max;
+    e->net_search_gamma.resize(n_nets);
+    for (int k = 0; k < n_nets; ++k) e->net_search_gamma[k] = rec[k].gamma;
     return AZG_OK;
 }
 

@@ -7,6 +7,14 @@
 
 #include "hip_host.h"
 
+// One net's rule of the lambda-return targets (azgym_lambda.h) as lambda_targets_kernel reads it: what the host resolved of the net's
+// azg_return_rule -- n_step clamped to the ring's size, om = 1.0 - lambda in float64, gamma the search's where the flag asks for it
+struct __attribute__((aligned(16))) ReturnRuleRec {
+    int n_step, pad;
+    double lambda, om, gamma;
+};
+static_assert(sizeof(ReturnRuleRec) == 32, "ReturnRuleRec must be 32 bytes");
+
 // Everything a begin starts over: value-initialised as a whole (ReplayRing::restart), so no member can outlive the memory it points into
 struct ReplayRingState {
     int on = 0;                      // azg_selfplay_begin has been called
@@ -28,6 +36,11 @@ struct ReplayRingState {
         int on = 0;
         double* reward = nullptr; double* value = nullptr; float* action = nullptr; int* end = nullptr;
     } tr;
+    struct ReturnRules {             // (azgym_lambda.h) the rule table of the last lambda-target call: d [n] on the device, allocated by
+        ReturnRuleRec* d = nullptr;  // the first call, and its host side, which the call's asynchronous copy reads (ReplayRing::
+        int n = 0;                   // rules_copied tells when it may be rewritten)
+        std::vector<ReturnRuleRec> h;
+    } rules;
     struct Priorities {              // (azgym_priority.h) a priority q per stored row [cap][B], the upload of a caller's d [cap][B], the
         int on = 0;                  // draws' prefix sums (within a segment [cap][B], segment totals [segs]) and the drawn slots [B]
         unsigned long long* q = nullptr; unsigned long long* within = nullptr; unsigned long long* seg = nullptr;
@@ -51,6 +64,13 @@ struct ReplayRingState {
 struct ReplayRing : ReplayRingState {
     DeviceAllocs mem;                // every device pointer of the state
     long long rows_gen = 0;          // counts the changes of the set of stored rows: a step, a clear, a begin (never reset)
+    // recorded behind every copy of rules.h to the device (created by the first one): a later call waits for it before it rewrites
+    // rules.h, so the staging outlives the copy that reads it
+    hipEvent_t rules_copied = nullptr;
+    ReplayRing() = default;
+    ReplayRing(const ReplayRing&) = delete;
+    ReplayRing& operator=(const ReplayRing&) = delete;
+    ~ReplayRing() { if (rules_copied) (void)hipEventDestroy(rules_copied); }
     // a begin: the memory goes, and every member of the state with it (the engine's stream is idle)
     void restart() { mem.clear(); static_cast<ReplayRingState&>(*this) = {}; rows_gen += 1; }
     // ReplayBuffer.store (buffers.py:75-82): the slot this step's block of B rows goes to

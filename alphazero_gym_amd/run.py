@@ -331,6 +331,13 @@ class PopulationSelfPlay:
     ``n_step`` steps plus the discounted search value after them (include/azgym_nstep.h: a terminal step closes the window with
     no bootstrap; a time-limit step and the newest stored step bootstrap from their own search value).  ``target_gamma`` None:
     the search's gamma, net k's own where ``net_settings`` gives it one.
+    ``td_lambda`` (a number in [0, 1]; None: off, every call made is the one above) turns them into lambda-returns
+    (include/azgym_lambda.h): inside the window of ``n_step`` steps the returns of the windows 1 .. ``n_step`` are mixed with weights
+    ``(1 - td_lambda) td_lambda**(m-1)``, the longest taking the rest -- 1 is the n-step return, 0 the 1-step return.  ``n_step``,
+    ``td_lambda`` and ``target_gamma`` may each be a list with one entry per net (a ``target_gamma`` entry None: that net's search
+    gamma): net k's rows then follow rule k, one launch for the population; a list for ``n_step`` or ``target_gamma`` with
+    ``td_lambda`` None means lambda 1.  ``play`` and ``reanalyse`` then end with ``lambda_targets()`` instead.  ``prioritized``
+    needs nothing else: the priority reads the V_target column, so it follows the lambda targets.
     ``prioritized`` (``{"alpha": 0.6, "eps": 1e-3}``; None: off, nothing is kept and behaviour is today's) keeps a priority per
     stored row beside the ring (include/azgym_priority.h): ``(|search value - V_target| + eps) ** alpha``, MuZero's, which needs
     ``n_step``.  ``sample_order(n)`` then draws training rows per net in proportion to it, on the device, in the form
@@ -350,11 +357,12 @@ class PopulationSelfPlay:
                  deterministic: bool = False, capacity_steps: int = 64, seed: int = 34, tree_id_base: int = 0, device_id: int = 0,
                  final_selection: str = "max_visit", temperature: float = 1.0, agent_epsilon: float = 0.0, fifo: bool = False,
                  net_settings: Optional[List[dict]] = None, net_settings_wide: Optional[bool] = None,
-                 net_rollouts: Optional[List[int]] = None, reanalyse: bool = False, n_step: Optional[int] = None,
-                 target_gamma: Optional[float] = None, prioritized: Optional[dict] = None):
+                 net_rollouts: Optional[List[int]] = None, reanalyse: bool = False, n_step=None,
+                 target_gamma=None, prioritized: Optional[dict] = None, td_lambda=None):
         policies = list(policies)
         if not policies or games_per_net < 1:
             raise ValueError(f"{type(self).__name__} needs at least one policy and games_per_net >= 1")
+        n_step, td_lambda, target_gamma, self._lambda_rule = self._return_rule(len(policies), n_step, td_lambda, target_gamma)
         if prioritized is not None:
             if set(prioritized) - {"alpha", "eps", "beta", "feedback"}:
                 raise ValueError(f"{type(self).__name__}: prioritized takes alpha, eps and beta, and feedback, not "
@@ -395,10 +403,9 @@ class PopulationSelfPlay:
         self._reanalyse_rng = np.random.default_rng(seed)
         if self.reanalysing:
             self.engine.selfplay_keep_states(True)
-        if n_step is not None and int(n_step) < 0:
+        if n_step is not None and not isinstance(n_step, list) and n_step < 0:
             raise ValueError(f"{type(self).__name__}: n_step must be >= 0 or None")
-        self.n_step = None if n_step is None else int(n_step)
-        self.target_gamma = None if target_gamma is None else float(target_gamma)
+        self.n_step, self.td_lambda, self.target_gamma = n_step, td_lambda, target_gamma
         if self.n_step is not None:
             self.engine.selfplay_keep_transitions(True)
         self.prioritized = None if prioritized is None else dict(alpha=float(prioritized.get("alpha", 0.6)),
@@ -413,6 +420,35 @@ class PopulationSelfPlay:
             if prioritized.get("feedback") is not None:
                 self.prioritized["feedback"] = prioritized["feedback"]
                 self.engine.selfplay_keep_errors(True)
+
+    @classmethod
+    def _return_rule(cls, K: int, n_step, td_lambda, target_gamma):
+        """The value-target settings as they are kept: (n_step, td_lambda, target_gamma, lambda rule in force).  A scalar stays a
+        scalar (an int / a float; None stays None), a sequence becomes a list with one entry per net.  The lambda rule is in force
+        when ``td_lambda`` is given or any setting is a list; ``td_lambda`` None is then lambda 1.  Raises ValueError for what no
+        engine call could accept."""
+        who = cls.__name__
+
+        def listed(name, x, conv):
+            if x is None or np.ndim(x) == 0:
+                return x if x is None else conv(x)
+            x = [conv(v) for v in x]
+            if len(x) != K:
+                raise ValueError(f"{who}: {name} has {len(x)} entries for {K} nets: a scalar or one per net")
+            return x
+
+        n_step = listed("n_step", n_step, int)
+        td_lambda = listed("td_lambda", td_lambda, float)
+        target_gamma = listed("target_gamma", target_gamma, lambda g: None if g is None else float(g))
+        in_force = td_lambda is not None or isinstance(n_step, list) or isinstance(target_gamma, list)
+        if in_force and n_step is None:
+            raise ValueError(f"{who}: td_lambda (and per-net target settings) need n_step: the window the returns are mixed in")
+        for lam in td_lambda if isinstance(td_lambda, list) else [] if td_lambda is None else [td_lambda]:
+            if not 0.0 <= lam <= 1.0:   # (NaN fails both)
+                raise ValueError(f"{who}: td_lambda must be in [0, 1], got {lam}")
+        if isinstance(n_step, list) and min(n_step) < 0:
+            raise ValueError(f"{who}: every n_step entry must be >= 0, got {n_step}")
+        return n_step, td_lambda, target_gamma, in_force
 
     @staticmethod
     def _search(policies, games_per_net: int, **kw) -> PopulationMCTS:
@@ -435,7 +471,15 @@ class PopulationSelfPlay:
         self.sync_weights()
         for _ in range(n_steps):
             self.engine.selfplay_step()
-        if self.n_step is not None:
+        self._value_targets()
+
+    def _value_targets(self) -> None:
+        """What ``play`` and ``reanalyse`` end with: the value targets asked for at creation, if any."""
+        if self.n_step is None:
+            return
+        if self._lambda_rule:
+            self.lambda_targets()
+        else:
             self.nstep_targets()
 
     def nstep_targets(self, n_step: Optional[int] = None, gamma: Optional[float] = None) -> None:
@@ -444,7 +488,23 @@ class PopulationSelfPlay:
         Idempotent: ``play`` and ``reanalyse`` already end with it."""
         if self.n_step is None:
             raise RuntimeError(f"{type(self).__name__}.nstep_targets needs the stored steps' rewards and ends: create it with n_step=...")
-        self.engine.selfplay_nstep_targets(self.n_step if n_step is None else int(n_step), self.target_gamma if gamma is None else float(gamma))
+        n_step = self.n_step if n_step is None else int(n_step)
+        gamma = self.target_gamma if gamma is None else float(gamma)
+        if isinstance(n_step, list) or isinstance(gamma, list):
+            raise ValueError(f"{type(self).__name__}.nstep_targets takes one n_step and one gamma: per-net settings go through lambda_targets()")
+        self.engine.selfplay_nstep_targets(n_step, gamma)
+
+    def lambda_targets(self, n_step=None, td_lambda=None, gamma=None) -> None:
+        """Rewrite the V_target column of every stored row as its lambda-return (``Engine.selfplay_lambda_targets``; asynchronous:
+        one small copy and one launch).  Each argument is a scalar or a list with one entry per net; None: the one given at
+        creation (``td_lambda`` None there: 1, the n-step return; ``target_gamma`` None: the search's gamma).  Idempotent: created
+        with ``td_lambda`` or a list, ``play`` and ``reanalyse`` already end with it."""
+        if self.n_step is None:
+            raise RuntimeError(f"{type(self).__name__}.lambda_targets needs the stored steps' rewards and ends: create it with n_step=...")
+        n_step, td_lambda, gamma, _ = self._return_rule(self.n_nets, self.n_step if n_step is None else n_step,
+                                                        self.td_lambda if td_lambda is None else td_lambda,
+                                                        self.target_gamma if gamma is None else gamma)
+        self.engine.selfplay_lambda_targets(n_step, 1.0 if td_lambda is None else td_lambda, gamma)
 
     def priorities(self, given=None) -> None:
         """Compute the priority of every stored row (``Engine.selfplay_priorities`` with the ``alpha`` and ``eps`` given at
@@ -532,8 +592,7 @@ class PopulationSelfPlay:
         for s in used:
             self.engine.selfplay_reanalyse(s, search_index=self._reanalyse_index)
             self._reanalyse_index += 1
-        if self.n_step is not None:   # (the reanalysed rows hold plain search values again: back to n-step returns, from the fresh values)
-            self.nstep_targets()
+        self._value_targets()   # (the reanalysed rows hold plain search values again: back to the returns, from the fresh values)
         return used
 
     def play_device(self, n_steps: int):

@@ -31,6 +31,9 @@ where rows stay in the ring -- --replay-steps, or --trainer device-epoch -- and 
 --n-step N trains the value heads on n-step returns instead of the search's root value: the discounted rewards of the next N steps
 plus the discounted search value after them, computed on the device from the transitions kept beside the ring (PopulationSelfPlay
 n_step=N; an episode's terminal step closes the window, a time limit and the newest stored step bootstrap from their own search value).
+--td-lambda L beside it mixes the returns of the windows 1 .. N into a lambda-return (PopulationSelfPlay td_lambda=L; 1: the n-step
+return).  --n-steps N0 N1 ... and --td-lambdas L0 L1 ... give every seed its own window and lambda: one engine, one launch, rule k for
+seed k's rows (--n-steps in place of --n-step; --td-lambdas beside either).
 
 --prioritized-alpha A [--prioritized-eps E], with --replay-steps and --n-step, replaces the uniform pick of training rows by a draw
 in proportion to (|search value - value target| + E)^A, made on the device from priorities kept beside the ring (PopulationSelfPlay
@@ -134,6 +137,14 @@ def parse_args(argv=None):
     ap.add_argument("--n-step", type=int, default=None,
                     help="value targets are n-step returns over the stored steps (discounted with each net's search gamma) instead of "
                          "the search's root value; 0 keeps the root value (default: off, nothing is kept)")
+    ap.add_argument("--n-steps", type=int, nargs="+", default=None,
+                    help="a sweep of --n-step, one window per --seeds entry (in place of --n-step): seed k's value targets follow its "
+                         "own window, all seeds still in one launch")
+    ap.add_argument("--td-lambda", type=float, default=None,
+                    help="with --n-step / --n-steps: value targets are lambda-returns, the returns of the windows 1 .. N mixed with "
+                         "weights (1 - L) L^(m-1) and the longest taking the rest; 1 is the n-step return, 0 the 1-step return (default: off)")
+    ap.add_argument("--td-lambdas", type=float, nargs="+", default=None,
+                    help="a sweep of --td-lambda, one value per --seeds entry (in place of --td-lambda)")
     ap.add_argument("--prioritized-alpha", type=float, default=None,
                     help="draw the training rows (and with --reanalyse-slots the reanalysed positions) in proportion to "
                          "(|search value - value target| + eps)^alpha on the device instead of uniformly; needs --replay-steps and "
@@ -208,6 +219,22 @@ def check_replay(a):
         return "--replay-steps and --reanalyse-slots must be >= 0"
     if getattr(a, "n_step", None) is not None and a.n_step < 0:
         return "--n-step must be >= 0"
+    n_steps, lambdas = getattr(a, "n_steps", None), getattr(a, "td_lambdas", None)
+    if n_steps is not None:
+        if getattr(a, "n_step", None) is not None:
+            return "--n-steps gives every seed its own window: use it in place of --n-step"
+        if len(n_steps) != len(a.seeds) or min(n_steps) < 0:
+            return f"--n-steps needs one value >= 0 per --seeds entry ({len(a.seeds)}), got {n_steps}"
+    if lambdas is not None:
+        if getattr(a, "td_lambda", None) is not None:
+            return "--td-lambdas gives every seed its own lambda: use it in place of --td-lambda"
+        if len(lambdas) != len(a.seeds):
+            return f"--td-lambdas needs one value per --seeds entry ({len(a.seeds)}), got {len(lambdas)}"
+    given = lambdas if lambdas is not None else [] if getattr(a, "td_lambda", None) is None else [a.td_lambda]
+    if given and target_rule(a)["n_step"] is None:
+        return "--td-lambda / --td-lambdas need --n-step N or --n-steps: the window the returns are mixed in"
+    if not all(0.0 <= lam <= 1.0 for lam in given):
+        return "--td-lambda / --td-lambdas must be in [0, 1]"
     if a.replay_steps and a.replay_steps < a.steps_per_iter:
         return f"--replay-steps ({a.replay_steps}) must hold at least one iteration's steps (--steps-per-iter {a.steps_per_iter})"
     if a.replay_steps and not a.device.startswith("cuda"):
@@ -215,7 +242,7 @@ def check_replay(a):
     if getattr(a, "prioritized_alpha", None) is not None:
         if not a.replay_steps:
             return "--prioritized-alpha draws from the rows kept in the FIFO ring: use it with --replay-steps R"
-        if getattr(a, "n_step", None) is None:
+        if target_rule(a)["n_step"] is None:
             return "--prioritized-alpha needs --n-step N: the priority is |search value - n-step target|, and both are kept only then"
         if not (a.prioritized_alpha >= 0.0 and a.prioritized_eps > 0.0):
             return "--prioritized-alpha must be >= 0 and --prioritized-eps > 0"
@@ -239,6 +266,13 @@ def check_replay(a):
         return ("--reanalyse-slots rewrites rows that stay in the device ring: use it with --replay-steps R (the FIFO ring) or with "
                 "--trainer device-epoch; the other modes copy the rows out and clear the ring every iteration")
     return None
+
+
+def target_rule(a):
+    """PopulationSelfPlay's ``n_step`` and ``td_lambda`` for --n-step / --n-steps and --td-lambda / --td-lambdas (None: off)."""
+    n_steps, lambdas = getattr(a, "n_steps", None), getattr(a, "td_lambdas", None)
+    return {"n_step": list(n_steps) if n_steps is not None else getattr(a, "n_step", None),
+            "td_lambda": list(lambdas) if lambdas is not None else getattr(a, "td_lambda", None)}
 
 
 def check_population_shape(a):
@@ -279,7 +313,7 @@ def build_population(a):
                                 c_uct=m.c_uct, gamma=m.gamma, epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0),
                                 kappa=getattr(m, "kappa", 0.5), max_episode_length=a.max_episode_length,
                                 capacity_steps=getattr(a, "replay_steps", 0) or a.steps_per_iter, fifo=bool(getattr(a, "replay_steps", 0)),
-                                reanalyse=getattr(a, "reanalyse_slots", 0) > 0, n_step=getattr(a, "n_step", None), prioritized=prioritized(a),
+                                reanalyse=getattr(a, "reanalyse_slots", 0) > 0, prioritized=prioritized(a), **target_rule(a),
                                 seed=a.engine_seed, device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0, **search_kwargs(a))
     return agents, state_dim, sp
 

@@ -16,6 +16,7 @@ before each iteration's training and overwrites their targets (DeviceSelfPlay.re
 --n-step N trains the value head on n-step returns instead of the search's root value: the discounted rewards of the next N steps plus
 the discounted search value after them, computed on the device from the transitions kept beside the ring (DeviceSelfPlay n_step=N;
 an episode's terminal step closes the window, a time limit and the newest stored step bootstrap from their own search value).
+--td-lambda L beside it mixes the returns of the windows 1 .. N into a lambda-return (DeviceSelfPlay td_lambda=L; 1: the n-step return).
 
 --prioritized-alpha A [--prioritized-eps E], with --replay-steps and --n-step, replaces the uniform pick of training rows by a draw in
 proportion to (|search value - value target| + E)^A, made on the device from priorities kept beside the ring (DeviceSelfPlay
@@ -103,6 +104,9 @@ def parse_args(argv=None):
     ap.add_argument("--n-step", type=int, default=None,
                     help="value targets are n-step returns over the stored steps (discounted with the search's gamma) instead of the "
                          "search's root value; 0 keeps the root value (default: off, nothing is kept)")
+    ap.add_argument("--td-lambda", type=float, default=None,
+                    help="with --n-step N: value targets are lambda-returns, the returns of the windows 1 .. N mixed with weights "
+                         "(1 - L) L^(m-1) and the longest taking the rest; 1 is the n-step return, 0 the 1-step return (default: off)")
     ap.add_argument("--prioritized-alpha", type=float, default=None,
                     help="draw the training rows (and with --reanalyse-slots the reanalysed positions) in proportion to "
                          "(|search value - value target| + eps)^alpha on the device instead of uniformly; needs --replay-steps and "
@@ -128,6 +132,11 @@ def parse_args(argv=None):
         ap.error("--replay-steps and --reanalyse-slots must be >= 0")
     if a.n_step is not None and a.n_step < 0:
         ap.error("--n-step must be >= 0")
+    if a.td_lambda is not None:
+        if a.n_step is None:
+            ap.error("--td-lambda needs --n-step N: the window the returns are mixed in")
+        if not 0.0 <= a.td_lambda <= 1.0:
+            ap.error("--td-lambda must be in [0, 1]")
     if a.replay_steps and a.replay_steps < a.steps_per_iter:
         ap.error(f"--replay-steps ({a.replay_steps}) must hold at least one iteration's steps (--steps-per-iter {a.steps_per_iter})")
     if a.replay_steps and (not a.device.startswith("cuda") or int(os.environ.get("WORLD_SIZE", "1")) > 1):
@@ -193,7 +202,7 @@ def train(a, log=print):
                             epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0), kappa=getattr(m, "kappa", 0.5),
                             max_episode_length=a.max_episode_length, capacity_steps=replay_steps or a.steps_per_iter, fifo=bool(replay_steps),
                             reanalyse=reanalyse_slots > 0, n_step=getattr(a, "n_step", None), prioritized=prioritized,
-                            seed=a.seed, rank=rank,
+                            td_lambda=getattr(a, "td_lambda", None), seed=a.seed, rank=rank,
                             device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0)
     K = sp.engine.kmax if continuous else 2
     rng = np.random.RandomState(a.seed)

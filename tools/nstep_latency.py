@@ -12,7 +12,16 @@ Every round starts one child process per library (AZG_HIP_LIB), parent and this 
     nstep       selfplay_nstep_targets(n_step, the search's gamma) over the full ring, n_step 5 and 1000 (this build)
 each as the host clock around 20 calls and ONE stream synchronisation after them, repeated; ms per call.  The table gives medians over
 all rounds and repeats, the parent step's spread (max - min of its per-round medians, relative), and the ratios to the parent's step.
-Nothing is gated: the figures are a record."""
+Nothing is gated: the figures are a record.
+
+    python tools/nstep_latency.py --lambda-call --parent-lib <parent build's libazgym_hip.so> [--out profiles/lambda_latency.txt]
+measures the lambda-return call (include/azgym_lambda.h) instead, on a CartPole 2x128 ReLU population of 8 nets x 512 games whose
+full ring holds 64 steps x 4096 games, per library in the same alternating child processes:
+    nstep       selfplay_nstep_targets(n_step) at n_step 5 and 1000 (both libraries; the parent's is the yardstick)
+    lambda      selfplay_lambda_targets(n_step, 0.9): one rule for every net (this build)
+    lambda nets the same with 8 per-net rules, lambda 0.3 .. 1 (this build)
+    copy        the call's host-to-device copy alone: 32 bytes per net on the engine's stream (this build)
+and writes the ratios lambda / parent nstep and the copy's share of the lambda call."""
 import argparse
 import json
 import os
@@ -72,13 +81,93 @@ def child(repeats):
     print("RESULT " + json.dumps(res), flush=True)
 
 
-def _run_child(lib, repeats):
+LAMBDA_NETS, LAMBDA_GAMES = 8, 512
+LAMBDA_KW = dict(env_id=0, mode=0, n_trees=LAMBDA_NETS * LAMBDA_GAMES, n_sims=50, c_uct=1.5, gamma=0.99, num_actions=2, seed=34)
+
+
+def lambda_child(repeats):
+    """One library: a JSON line {variant: [ms per call, ...]} over the full ring of the 8-net population."""
+    import numpy as np
+    import torch
+    from alphazero_gym_amd import _capi, _native
+    from alphazero_gym_amd.synthetic import make_weights
+    e = _native.HipEngine(**LAMBDA_KW)
+    e.set_population(LAMBDA_NETS)
+    desc = _capi.make_desc(4, [128, 128], 2, "relu")
+    for k in range(LAMBDA_NETS):
+        e.set_net_weights(k, desc, make_weights(34 + k, 4, [128, 128], 2))
+    e.population_selfplay_begin(200, False, capacity_steps=CAPACITY, fifo=True)
+    e.selfplay_keep_transitions(True)
+    for _ in range(CAPACITY):
+        e.selfplay_step()
+    r = {"rows": e.selfplay_ring()[0] * LAMBDA_KW["n_trees"]}
+    have = "selfplay_lambda_targets" in _native.fns()
+    lams = list(np.linspace(0.3, 1.0, LAMBDA_NETS))
+    for n in N_STEPS:
+        e.selfplay_nstep_targets(n)
+        r[f"nstep{n}"] = _timed(e, lambda i: e.selfplay_nstep_targets(n), repeats)
+        if have:
+            e.selfplay_lambda_targets(n, 0.9)
+            r[f"lambda{n}"] = _timed(e, lambda i: e.selfplay_lambda_targets(n, 0.9), repeats)
+            e.selfplay_lambda_targets(n, lams)
+            r[f"lambda_nets{n}"] = _timed(e, lambda i: e.selfplay_lambda_targets(n, lams), repeats)
+    if have:   # the rule table's copy alone: the same bytes from pageable host memory, on a stream of its own kind
+        src = torch.zeros(LAMBDA_NETS * 32, dtype=torch.uint8)
+        dst = torch.zeros(LAMBDA_NETS * 32, dtype=torch.uint8, device="cuda")
+        stream = torch.cuda.Stream()
+        out = []
+        with torch.cuda.stream(stream):
+            for _ in range(repeats + 1):
+                stream.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(CALLS):
+                    dst.copy_(src, non_blocking=True)
+                stream.synchronize()
+                out.append((time.perf_counter() - t0) * 1e3 / CALLS)
+        r["copy"] = out[1:]
+    e.close()
+    print("RESULT " + json.dumps(r), flush=True)
+
+
+def lambda_main(a):
+    parent, new = [], []
+    for _ in range(a.rounds):
+        parent.append(_run_child(os.path.abspath(a.parent_lib), a.repeats, "--lambda-child"))
+        new.append(_run_child(None, a.repeats, "--lambda-child"))
+    med = statistics.median
+
+    def m(runs, key):
+        return med([x for r in runs for x in r[key]])
+
+    def rounds(runs, key):
+        return ", ".join(f"{med(r[key]):.4f}" for r in runs)
+
+    lines = [f"lambda_latency: ms per call, host clock around {CALLS} calls + one stream synchronisation; {a.rounds} rounds x {a.repeats} repeats per library,",
+             f"parent-commit library and this build in alternating child processes of one run on one MI355X; CartPole 2x128 ReLU, {LAMBDA_NETS} nets x",
+             f"{LAMBDA_GAMES} games, FIFO ring of {CAPACITY} steps, full ({new[0]['rows']} stored rows)", ""]
+    copy = m(new, "copy")
+    for n in N_STEPS:
+        p, own = m(parent, f"nstep{n}"), m(new, f"nstep{n}")
+        one, nets = m(new, f"lambda{n}"), m(new, f"lambda_nets{n}")
+        lines += [f"n_step {n}",
+                  f"  parent nstep_targets          {p:9.4f} ms   per-round medians {rounds(parent, f'nstep{n}')}",
+                  f"  nstep_targets (this build)    {own:9.4f} ms   ratio to parent {own / p:.3f}",
+                  f"  lambda_targets, one rule      {one:9.4f} ms   ratio to parent nstep {one / p:.3f}   per-round medians {rounds(new, f'lambda{n}')}",
+                  f"  lambda_targets, 8 net rules   {nets:9.4f} ms   ratio to parent nstep {nets / p:.3f}   per-round medians {rounds(new, f'lambda_nets{n}')}",
+                  f"  the 256-byte copy alone       {copy:9.4f} ms   share of the one-rule call {copy / one:.2f}", ""]
+    text = "\n".join(lines)
+    print(text)
+    with open(a.out, "w") as f:
+        f.write(text)
+
+
+def _run_child(lib, repeats, mode="--child"):
     env = dict(os.environ)
     if lib:
         env["AZG_HIP_LIB"] = lib
     else:
         env.pop("AZG_HIP_LIB", None)
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--repeats", str(repeats)], env=env, check=True, capture_output=True,
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), mode, "--repeats", str(repeats)], env=env, check=True, capture_output=True,
                          text=True, timeout=600).stdout
     return json.loads([ln for ln in out.splitlines() if ln.startswith("RESULT ")][-1][len("RESULT "):])
 
@@ -86,15 +175,23 @@ def _run_child(lib, repeats):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--lambda-child", action="store_true")
+    ap.add_argument("--lambda-call", action="store_true", help="measure the lambda-return call (default --out: profiles/lambda_latency.txt)")
     ap.add_argument("--parent-lib")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "nstep_latency.txt"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "lambda_latency.txt" if a.lambda_call else "nstep_latency.txt")
     if a.child:
         return child(a.repeats)
+    if a.lambda_child:
+        return lambda_child(a.repeats)
     if not a.parent_lib or not os.path.exists(a.parent_lib):
         sys.exit("--parent-lib: the libazgym_hip.so of a build of the parent commit (the yardstick is measured in the same run)")
+    if a.lambda_call:
+        return lambda_main(a)
     parent, new = [], []
     for _ in range(a.rounds):
         parent.append(_run_child(os.path.abspath(a.parent_lib), a.repeats))
