@@ -22,6 +22,7 @@ import torch.nn.functional as F
 
 from .. import _capi
 from ..network.policies import DiagonalGMMPolicy, DiagonalNormalPolicy, DiscretePolicy
+from ..pbt import check_src
 from .losses import A0CLoss, A0CLossTuned, AlphaZeroLoss
 
 
@@ -313,7 +314,8 @@ class PopulationTrainer:
     learning-rate sweep in one trainer.  Optimiser class, loss class, reduction, network shape and step counts are still shared.
     Every call then goes through the ``*_nets`` entry points, which read one settings entry per net; agents with equal settings
     get the bits of ``per_net=False``.  ``reload_settings()`` reads the agents' settings again, e.g. after a schedule or an
-    exploit/explore step changed ``optimizer.param_groups[0]["lr"]``."""
+    exploit/explore step changed ``optimizer.param_groups[0]["lr"]``.  ``copy_nets(src)`` is that step's exploit half: net k
+    becomes a faithful clone of net ``src[k]`` (``alphazero_gym_amd.pbt.PopulationBasedTraining`` drives the whole step)."""
 
     def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False, losses: str = "torch",
                  optimizers: str = "rmsprop", layernorm: bool = False, wide: bool = False, wide_layernorm: bool = False,
@@ -592,6 +594,52 @@ class PopulationTrainer:
                                                                      self.loss_cfg.action_bound) for c in cfgs):
                 raise ValueError("PopulationTrainer.reload_settings: loss class, head and reduction cannot change")
         self._set_net_entries(settings, clips, cfgs)
+
+    def copy_nets(self, src) -> None:
+        """The exploit half of population-based training (``alphazero_gym_amd.pbt``): row k of every per-net piece of state becomes
+        row ``src[k]`` -- ``flat`` and the optimiser's moments (``square_avg``, or ``exp_avg`` and ``exp_avg_sq``: the agents'
+        modules, ``state_dict()`` and torch optimisers are views of those rows and see the copy), and with ``A0CLossTuned`` the
+        learned temperature with its Adam moments (``losses="device"``: ``log_alpha``, ``alpha_exp_avg``, ``alpha_exp_avg_sq``;
+        ``losses="torch"``: ``log_alpha.data`` and the ``alpha_optimizer``'s state).  With ``per_net=True`` agent k also takes agent
+        ``src[k]``'s numeric optimiser settings, ``clip`` and numeric loss settings, and ``reload_settings()`` runs; without it the
+        settings are shared.  ``opt_step`` and ``alpha_step`` are shared by all nets and stay.  ``src``: K ints in range with
+        ``src[src[k]] == src[k]`` (``pbt.check_src``; ``ValueError`` before anything is written).  The copies are row copies on the
+        trainer's stream; hand the result to the search with ``upload_flat`` (a copy into views bumps no ``_version``)."""
+        src = check_src(src, len(self.agents))
+        replaced = [k for k in range(len(self.agents)) if int(src[k]) != k]
+        if not replaced:
+            return
+        to = torch.as_tensor(replaced, dtype=torch.int64, device=self.device)
+        frm = torch.as_tensor([int(src[k]) for k in replaced], dtype=torch.int64, device=self.device)
+        tables = [self.flat, self.square_avg, self.exp_avg, self.exp_avg_sq, self.alpha_exp_avg, self.alpha_exp_avg_sq]
+        if self.log_alpha is not None:
+            tables.append(self.log_alpha.data)
+        if self.alpha_optimizer is not None:
+            st = self.alpha_optimizer.state.get(self.log_alpha, {})
+            tables += [st.get("exp_avg"), st.get("exp_avg_sq")]
+        with torch.no_grad():
+            for t in tables:
+                if t is not None:
+                    t[to] = t[frm]   # (sources are never replaced: the gather is complete before the scatter writes)
+        if not self.per_net:
+            return
+        for k in replaced:
+            a, s = self.agents[k], self.agents[int(src[k])]
+            ga, gs = a.optimizer.param_groups[0], s.optimizer.param_groups[0]
+            for key in ("lr", "eps", "weight_decay", "alpha", "betas"):
+                if key in gs:
+                    ga[key] = gs[key]
+            a.clip = s.clip
+            for key in ("tau", "policy_coeff", "value_coeff", "target_entropy", "clip"):
+                if hasattr(s.loss, key):
+                    setattr(a.loss, key, getattr(s.loss, key))
+            if type(s.loss) is A0CLoss:
+                a.loss.alpha = s.loss.alpha
+            elif type(s.loss) is A0CLossTuned:
+                la, ls = a.loss.optimizer.param_groups[0], s.loss.optimizer.param_groups[0]
+                for key in ("lr", "betas", "eps", "weight_decay"):
+                    la[key] = ls[key]
+        self.reload_settings()
 
     def _set_net_entries(self, settings: List[tuple], clips: List[float], cfgs: Optional[list]) -> None:
         """``per_net=True``: the arrays the ``*_nets`` calls read, built once per set of settings -- one azg_optim per net (its

@@ -24,6 +24,7 @@ from .agent.buffers import DeviceReplay, ReplayBuffer
 from .agent.population import AgentPopulation
 from .envs import VecCartPole, VecMountainCarContinuous, VecPendulum, make_game
 from .helpers import check_space, stable_normalizer
+from .pbt import check_src
 from .search.mcts import BatchedMCTS, PopulationMCTS
 
 LOSS_TUNED = dict(_target_="alphazero_gym_amd.agent.losses.A0CLossTuned", action_dim=1, alpha_init=1.0, lr=0.001, tau=0.1,
@@ -464,6 +465,56 @@ class PopulationSelfPlay:
     def upload_flat(self, desc, flat) -> None:
         """``PopulationMCTS.upload_flat``: the hand-off of parameters trained in place by ``PopulationTrainer``."""
         self.mcts.upload_flat(desc, flat)
+
+    def copy_nets(self, src, reset_errors: bool = True, explored: Optional[Dict[int, dict]] = None) -> None:
+        """The engine side of population-based training's exploit step (``alphazero_gym_amd.pbt``): net k's settings become those of
+        net ``src[k]`` -- its entry in ``mcts.net_settings``, in ``mcts.net_rollouts`` and in the per-net ``n_step``, ``td_lambda``
+        and ``target_gamma`` lists, each where that table or list exists.  Net k keeps its own games, carried subtrees, ring rows,
+        kept states and transitions, priorities and counters: weights and hyper-parameters move, experience does not
+        (``reanalyse()`` refreshes those rows' targets with the new weights).  The weights themselves arrive through
+        ``upload_flat``.  ``src``: K ints in range with ``src[src[k]] == src[k]`` (``pbt.check_src``).
+
+        ``reset_errors``: with ``prioritized={"feedback": ...}`` the kept trainer errors of the replaced nets' rows are set to -1
+        ("not trained on"): they were another net's errors.
+        ``explored`` ({net: {name: value}}, names among the search settings, ``n_rollouts`` and the target rules): values written
+        over net k's copied ones, the explore half of the same step (``pbt.PopulationBasedTraining``).
+        Every check -- this method's, ``PopulationMCTS.set_net_table``'s and the target rule's -- runs before the first write, and
+        the search table is pushed once: a refusal leaves the engine and this object as they were."""
+        src = check_src(src, self.n_nets)
+        explored = {int(k): dict(v) for k, v in (explored or {}).items()}
+        replaced = [k for k in range(self.n_nets) if int(src[k]) != k]
+        if not replaced and not explored:
+            return
+        who = f"{type(self).__name__}.copy_nets"
+        m = self.mcts
+        settings = None if m.net_settings is None else [dict(m.net_settings[int(s)]) for s in src]
+        rollouts = None if m.net_rollouts is None else [int(m.net_rollouts[int(s)]) for s in src]
+        rule = {name: [getattr(self, name)[int(s)] for s in src] if isinstance(getattr(self, name), list) else getattr(self, name)
+                for name in ("n_step", "td_lambda", "target_gamma")}
+        for k, values in explored.items():
+            if not 0 <= k < self.n_nets:
+                raise ValueError(f"{who}: explored names net {k} of {self.n_nets}")
+            for name, value in values.items():
+                if name in _capi.NET_SEARCH_KEYS and settings is not None:
+                    settings[k][name] = float(value)
+                elif name == "n_rollouts" and rollouts is not None:
+                    rollouts[k] = value
+                elif name in rule and isinstance(rule[name], list):
+                    rule[name][k] = value
+                else:
+                    raise ValueError(f"{who}: explored[{k}][{name!r}] has no per-net table or list in this engine to be written to")
+        self._return_rule(self.n_nets, rule["n_step"], rule["td_lambda"], rule["target_gamma"])   # (its refusals, before any write)
+        if settings is not None or rollouts is not None:
+            m.set_net_table(settings, rollouts)
+        self.n_step, self.td_lambda, self.target_gamma, _ = self._return_rule(self.n_nets, rule["n_step"], rule["td_lambda"],
+                                                                              rule["target_gamma"])
+        if reset_errors and replaced and self.prioritized is not None and "feedback" in self.prioritized \
+                and self.engine.selfplay_ring()[0]:
+            errors = self.errors().reshape(-1, self.n_games).copy()
+            T = self.games_per_net
+            for k in replaced:
+                errors[:, k * T:(k + 1) * T] = -1.0
+            self.set_errors(errors.reshape(-1))
 
     def play(self, n_steps: int) -> None:
         """n_steps self-play steps of every game of every net (asynchronous: launches only); rows accumulate in the device ring."""

@@ -198,6 +198,19 @@ class PopulationMCTS:
             return
         self._push_net_settings(self.net_settings, self.net_settings_wide, self._net_budgets(net_rollouts, self.net_settings_wide))
 
+    def set_net_table(self, net_settings: Optional[Sequence[dict]], net_rollouts: Optional[Sequence[int]]) -> None:
+        """``set_net_settings`` and ``set_net_rollouts`` in one: both setters' checks run first, then the table goes to the engine
+        once, so a refusal -- a budget above ``n_rollouts``, a widening beyond azg_max_children -- leaves both as they were (an
+        exploit/explore step changes settings and budgets together).  None for either: that part returns to the shared values."""
+        if net_settings is None and net_rollouts is None:
+            self.engine.set_net_search(None)
+            self.net_settings, self.net_rollouts = None, None
+            return
+        wide = self.net_settings_wide
+        entries = None if net_settings is None else self._net_entries(net_settings, wide)
+        rollouts = None if net_rollouts is None else self._net_budgets(net_rollouts, wide)
+        self._push_net_settings(entries, wide, rollouts)
+
     def sync_weights(self, force: bool = False) -> None:
         """Upload the weights of every model that changed since its last upload (net k = models[k]; after every optimiser step).
         ``last_weight_sync`` says how: "device" when every parameter lives on the engine's GPU (flattened there; K > 1: one gather

@@ -50,6 +50,14 @@ ceil(train-rows / batch-size) minibatches run in one native call (train_online_r
 errors of the minibatches before it.
 The draw is with replacement and biased; the loss is not reweighted (no importance-sampling weights).
 
+--pbt-every N turns the sweep into population-based training (alphazero_gym_amd.pbt): after every N-th iteration the seeds are ranked
+by --pbt-score (selfplay: the mean return of the episodes finished since the last such step; eval / eval-search: that iteration's
+--eval-episodes / --eval-search-episodes returns), the worst --pbt-fraction of them take the weights, optimiser state, learned
+temperature and settings of seeds drawn from the best fraction, and every --pbt-explore NAME[:f1,f2[:min:max]] hyper-parameter they
+inherited is multiplied by one of its factors (default 0.8,1.25) and clipped.  It needs a device trainer and at least two seeds.
+--pbt-explore lr builds the trainer with per_net=True; c_uct / gamma / epsilon / c_pw / kappa and n_rollouts give the engine its per-seed
+table from iteration 0, filled with the shared values; n_step / td_lambda / target_gamma turn --n-step / --td-lambda into per-seed lists.
+
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
 Seed k sets net k's initial weights (torch.manual_seed), and its own np.random.RandomState picks the training rows and the
@@ -163,8 +171,20 @@ def parse_args(argv=None):
                     help="prioritised replay as published: one native call per iteration (train_online_ring) trains "
                          "ceil(train-rows / batch-size) minibatches, each drawn from priorities refreshed with the errors of the "
                          "minibatches before it; needs --prioritized-feedback (default: off, one draw per iteration)")
+    ap.add_argument("--pbt-every", type=int, default=0,
+                    help="population-based training: after every N-th iteration the worst seeds copy the best ones and perturb what "
+                         "--pbt-explore names (0: off, the run is a plain sweep); needs a --trainer other than torch and two seeds or more")
+    ap.add_argument("--pbt-fraction", type=float, default=0.25,
+                    help="the share of the seeds replaced at a PBT step, floor(seeds * F) of them, drawn from as many of the best; in (0, 0.5]")
+    ap.add_argument("--pbt-explore", nargs="+", default=None, metavar="NAME[:f1,f2[:min:max]]",
+                    help="hyper-parameters a replaced seed perturbs after inheriting them: one of " + ", ".join(PBT_DEFAULTS) + "; "
+                         "the value is multiplied by one of the factors (default 0.8,1.25) and clipped to min .. max (default: per name)")
+    ap.add_argument("--pbt-score", choices=["selfplay", "eval", "eval-search"], default="selfplay",
+                    help="what ranks the seeds: selfplay, the mean return of the episodes finished since the last PBT step (a seed with "
+                         "none takes the lowest score); eval, --eval-episodes' eval_return; eval-search, --eval-search-episodes' "
+                         "eval_search_return")
     a = ap.parse_args(argv)
-    why = check_replay(a)
+    why = check_replay(a) or check_pbt(a)
     if why:
         ap.error(why)
     if a.eval_search_episodes < 0:
@@ -203,14 +223,112 @@ def search_kwargs(a):
     """PopulationSelfPlay's keywords for the sweeps given: ``net_settings``, ``net_rollouts`` (--n-rollouts-per-seed), and with --wide
     the opt-in that lets nets of width >= 512 search with them (``net_settings_wide=True``).  No sweep: the shared settings, no keyword."""
     kw = {}
+    explored = pbt_names(a)
     settings = net_settings(a)
+    if settings is None and any(n in PBT_SEARCH_NAMES for n in explored):   # the table a PBT step writes to, filled with the shared values
+        settings = [{} for _ in a.seeds]
     if settings is not None:
         kw["net_settings"] = settings
     if getattr(a, "n_rollouts_per_seed", None) is not None:
         kw["net_rollouts"] = list(a.n_rollouts_per_seed)
+    elif "n_rollouts" in explored:
+        kw["net_rollouts"] = [a.n_rollouts] * len(a.seeds)
     if kw and a.wide:
         kw["net_settings_wide"] = True
     return kw
+
+
+# --pbt-explore's names: (min, max) where no min:max is given; None: taken from the run (pbt_explore)
+PBT_DEFAULTS = {"lr": (1e-6, 1.0), "weight_decay": (0.0, 1.0), "grad_clip": (0.0, 100.0), "tau": (0.0, 10.0), "policy_coeff": (0.0, 100.0),
+                "value_coeff": (0.0, 100.0), "alpha": (0.0, 10.0), "c_uct": (0.0, 100.0), "gamma": (0.0, 1.0), "epsilon": (0.0, 1.0),
+                "c_pw": None, "kappa": None, "n_rollouts": None, "n_step": None, "td_lambda": (0.0, 1.0), "target_gamma": (0.0, 1.0)}
+PBT_FACTORS = (0.8, 1.25)
+PBT_TRAINER_NAMES = ("lr", "weight_decay", "grad_clip", "tau", "policy_coeff", "value_coeff", "alpha")
+PBT_LOSS_NAMES = ("tau", "policy_coeff", "value_coeff", "alpha")
+PBT_SEARCH_NAMES = ("c_uct", "gamma", "epsilon", "c_pw", "kappa")
+
+
+def pbt_explore(a):
+    """PopulationBasedTraining's ``explore`` for --pbt-explore, in the order given ({}: nothing is perturbed).  Raises ValueError
+    saying why an entry cannot be read.  Where no min:max is given: PBT_DEFAULTS, and for the settings the engine's size bounds --
+    n_rollouts 1 .. --n-rollouts, c_pw and kappa up to the widest the engine is created for, n_step 0 .. the ring's steps."""
+    out = {}
+    for item in getattr(a, "pbt_explore", None) or []:
+        parts = item.split(":")
+        name = parts[0]
+        if name not in PBT_DEFAULTS:
+            raise ValueError(f"--pbt-explore: {name!r} is not a hyper-parameter it can perturb ({', '.join(PBT_DEFAULTS)})")
+        if name in out:
+            raise ValueError(f"--pbt-explore names {name!r} twice: once per hyper-parameter")
+        if len(parts) not in (1, 2, 4):
+            raise ValueError(f"--pbt-explore {item!r}: the forms are NAME, NAME:f1,f2,... and NAME:f1,f2,...:min:max")
+        try:
+            factors = [float(f) for f in parts[1].split(",")] if len(parts) > 1 else list(PBT_FACTORS)
+        except ValueError:
+            factors = []
+        if not factors or not all(np.isfinite(f) and f > 0 for f in factors):
+            raise ValueError(f"--pbt-explore {item!r}: the factors are positive numbers separated by commas")
+        if len(parts) == 4:
+            try:
+                lo, hi = float(parts[2]), float(parts[3])
+            except ValueError:
+                lo, hi = 1.0, 0.0
+            if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 <= lo <= hi):
+                raise ValueError(f"--pbt-explore {item!r}: min and max are numbers with 0 <= min <= max")
+        elif PBT_DEFAULTS[name] is not None:
+            lo, hi = PBT_DEFAULTS[name]
+        elif name == "n_rollouts":
+            lo, hi = 1, a.n_rollouts
+        elif name == "n_step":
+            lo, hi = 0, getattr(a, "replay_steps", 0) or a.steps_per_iter
+        else:   # c_pw, kappa: not beyond the widening the engine is created for (the shared default, or the widest of a sweep)
+            given = getattr(a, "c_pws" if name == "c_pw" else "kappas", None)
+            lo, hi = 0.05, max(given) if given else (1.0 if name == "c_pw" else 0.5)
+        out[name] = {"factors": factors, "min": lo, "max": hi}
+        if name in ("n_rollouts", "n_step"):
+            out[name]["integer"] = True
+    return out
+
+
+def check_pbt(a):
+    """Why the --pbt-* flags cannot be honoured as given (None: they can)."""
+    every = getattr(a, "pbt_every", 0)
+    if every < 0:
+        return "--pbt-every must be >= 0"
+    if not every:
+        if getattr(a, "pbt_explore", None) is not None:
+            return "--pbt-explore perturbs what a PBT step copied: it needs --pbt-every N"
+        return None
+    if a.trainer == "torch":
+        return ("--pbt-every clones nets inside the population trainer: use --trainer device, device-fused or device-epoch (the "
+                "per-agent update loop of --trainer torch has no trainer to copy rows in)")
+    if len(a.seeds) < 2:
+        return f"--pbt-every ranks the seeds against each other: it needs two --seeds entries or more, got {len(a.seeds)}"
+    if not 0.0 < a.pbt_fraction <= 0.5:
+        return "--pbt-fraction must lie in (0, 0.5]: the replaced seeds and their sources are different seeds"
+    try:
+        explore = pbt_explore(a)
+    except ValueError as e:
+        return str(e)
+    lossy = [n for n in explore if n in PBT_LOSS_NAMES]
+    if lossy and a.trainer == "device":
+        return (f"--pbt-explore {lossy[0]}: per-seed loss settings need the losses on the device: use --trainer device-fused or "
+                "device-epoch")
+    rule = target_rule(a)
+    if ("n_step" in explore or "target_gamma" in explore) and rule["n_step"] is None:
+        return "--pbt-explore n_step / target_gamma perturbs the value-target rule: it needs --n-step N or --n-steps"
+    if "td_lambda" in explore and rule["td_lambda"] is None:
+        return "--pbt-explore td_lambda perturbs the lambda-return's lambda: it needs --td-lambda L or --td-lambdas"
+    if a.pbt_score == "eval" and a.eval_episodes <= 0:
+        return "--pbt-score eval ranks the seeds by eval_return: it needs --eval-episodes N"
+    if a.pbt_score == "eval-search" and a.eval_search_episodes <= 0:
+        return "--pbt-score eval-search ranks the seeds by eval_search_return: it needs --eval-search-episodes E"
+    return None
+
+
+def pbt_names(a):
+    """The names --pbt-explore perturbs, in order ([] without --pbt-every)."""
+    return list(pbt_explore(a)) if getattr(a, "pbt_every", 0) else []
 
 
 def check_replay(a):
@@ -275,6 +393,18 @@ def target_rule(a):
             "td_lambda": list(lambdas) if lambdas is not None else getattr(a, "td_lambda", None)}
 
 
+def pbt_target_rule(a):
+    """``target_rule`` with what --pbt-explore perturbs of it as per-seed lists (a PBT step writes list entries): a scalar --n-step /
+    --td-lambda repeated for every seed, and ``target_gamma`` as one None (the seed's search gamma) per seed.  No such name: the same."""
+    rule, K = target_rule(a), len(a.seeds)
+    for name in pbt_names(a):
+        if name in ("n_step", "td_lambda") and not isinstance(rule[name], list):
+            rule[name] = [rule[name]] * K
+        elif name == "target_gamma":
+            rule["target_gamma"] = [None] * K
+    return rule
+
+
 def check_population_shape(a):
     """Why the search engine would refuse this population (None: it takes it): several nets that it searches as teams of 32 trees
     need a multiple of 32 games each (_capi.lockstep_shaped).  Asked before anything is built."""
@@ -313,7 +443,7 @@ def build_population(a):
                                 c_uct=m.c_uct, gamma=m.gamma, epsilon=m.epsilon, c_pw=getattr(m, "c_pw", 1.0),
                                 kappa=getattr(m, "kappa", 0.5), max_episode_length=a.max_episode_length,
                                 capacity_steps=getattr(a, "replay_steps", 0) or a.steps_per_iter, fifo=bool(getattr(a, "replay_steps", 0)),
-                                reanalyse=getattr(a, "reanalyse_slots", 0) > 0, prioritized=prioritized(a), **target_rule(a),
+                                reanalyse=getattr(a, "reanalyse_slots", 0) > 0, prioritized=prioritized(a), **pbt_target_rule(a),
                                 seed=a.engine_seed, device_id=torch.cuda.current_device() if a.device.startswith("cuda") else 0, **search_kwargs(a))
     return agents, state_dim, sp
 
@@ -327,11 +457,13 @@ def train(a, log=print, on_rows=None, on_end=None):
     on_gpu = a.device.startswith("cuda")
     fs0, fc0 = np.zeros(len(a.seeds)), np.zeros(len(a.seeds), np.int64)
     trainer = None
+    pbt_every = getattr(a, "pbt_every", 0)
+    per_net = a.lrs is not None or any(n in PBT_TRAINER_NAMES for n in pbt_names(a))   # (a PBT step writes per-seed trainer settings)
     if a.trainer != "torch":
         from alphazero_gym_amd.agent.population_trainer import PopulationTrainer
         trainer = PopulationTrainer(agents, max_batch=max(512, 2 * a.batch_size), losses="torch" if a.trainer == "device" else "device",
-                                    optimizers="agents" if (a.optimizer != "rmsprop" or a.grad_clip or a.lrs is not None) else "rmsprop",
-                                    per_net=a.lrs is not None,
+                                    optimizers="agents" if (a.optimizer != "rmsprop" or a.grad_clip or per_net) else "rmsprop",
+                                    per_net=per_net,
                                     layernorm=a.layernorm and not a.wide, wide=a.wide and not a.layernorm,
                                     wide_layernorm=a.wide and a.layernorm)
     replay_steps, reanalyse_slots = getattr(a, "replay_steps", 0), getattr(a, "reanalyse_slots", 0)
@@ -352,6 +484,11 @@ def train(a, log=print, on_rows=None, on_end=None):
             return prio_order[k].astype(np.int64)
         return rng.choice(n, size=min(a.train_rows, n), replace=False)
 
+    pbt = None
+    if pbt_every:
+        from alphazero_gym_amd.pbt import PopulationBasedTraining
+        pbt = PopulationBasedTraining(sp, trainer, pbt_explore(a), fraction=a.pbt_fraction, seed=a.engine_seed)
+        pbt_fs, pbt_fc = fs0.copy(), fc0.copy()   # finished_returns() at the last PBT step
     ring_view = None
     t0 = time.time()
     history = []
@@ -439,9 +576,23 @@ def train(a, log=print, on_rows=None, on_end=None):
         if a.eval_episodes > 0:   # the nets as just trained and uploaded, each by itself, over the same start states
             ev = sp.evaluate(a.eval_episodes, rule=a.eval_rule)
             history[-1]["eval_return"] = [round(float(x), 2) for x in ev["mean_return"]]
+            ev_raw = ev
         if getattr(a, "eval_search_episodes", 0) > 0:   # the same nets acting with their search, over those same start states
             ev = sp.evaluate_search(a.eval_search_episodes)
             history[-1]["eval_search_return"] = [round(float(x), 2) for x in ev["mean_return"]]
+            ev_search = ev
+        if pbt is not None and (it + 1) % pbt_every == 0:   # exploit / explore on the nets as just trained, then uploaded again
+            if a.pbt_score == "selfplay":
+                done = fc - pbt_fc
+                scores = (fs - pbt_fs) / np.maximum(done, 1)
+                if (done > 0).any():   # (a seed that finished no episode since the last step ranks with the worst)
+                    scores[done == 0] = scores[done > 0].min()
+                pbt_fs, pbt_fc = fs, fc
+            else:
+                scores = (ev_raw if a.pbt_score == "eval" else ev_search)["mean_return"]
+            rec = pbt.step(scores)
+            history[-1]["pbt"] = {"src": rec["src"], "scores": [round(float(x), 4) for x in scores],
+                                  "explored": {str(k): v for k, v in rec["explored"].items()}}
         if log:
             log(json.dumps(history[-1]), flush=True)
         fs0, fc0 = fs, fc
