@@ -1572,6 +1572,25 @@ class Trainer:
         self._check(self._f["trainer_read_d_raw"](self._h, int(n_rows), d_raw or None))
 
 
+# Which ``Trainer`` method serves a (family, variant) call of a trainer whose optimiser arguments have the form "rmsprop" (an
+# azg_rmsprop and square_avg), "opt" (one azg_optim) or "nets" (an array of azg_optim, and of azg_loss_cfg), and the form in which
+# that method takes them.  azg_rmsprop has no weighted, errors or online entry point: those calls of its trainer go to the *_opt ones.
+_T = Trainer
+TRAINER_CALLS = {
+    "opt": {("backward_step", "plain"): (_T.backward_step_opt, "opt"), ("step", "plain"): (_T.step_opt, "opt"),
+            ("step", "weighted"): (_T.step_opt_weighted, "opt"), ("epoch", "plain"): (_T.epoch_opt, "opt"),
+            ("epoch", "weighted"): (_T.epoch_opt_weighted, "opt"), ("epoch", "errors"): (_T.epoch_opt_errors, "opt"),
+            ("epoch", "online"): (_T.epoch_online, "opt")},
+    "nets": {("backward_step", "plain"): (_T.backward_step_nets, "nets"), ("step", "plain"): (_T.step_nets, "nets"),
+             ("step", "weighted"): (_T.step_nets_weighted, "nets"), ("epoch", "plain"): (_T.epoch_nets, "nets"),
+             ("epoch", "weighted"): (_T.epoch_nets_weighted, "nets"), ("epoch", "errors"): (_T.epoch_nets_errors, "nets"),
+             ("epoch", "online"): (_T.epoch_online_nets, "nets")},
+}
+TRAINER_CALLS["rmsprop"] = {**TRAINER_CALLS["opt"], ("backward_step", "plain"): (_T.backward_step, "rmsprop"),
+                            ("step", "plain"): (_T.step, "rmsprop"), ("epoch", "plain"): (_T.epoch, "rmsprop")}
+del _T
+
+
 def pw_table(c_pw, kappa, n):
     """NodeContinuous.check_pw's threshold (alphazero/search/states.py:271-273) for visit counts 0..n-1."""
     return [math.ceil(c_pw * ((i + 1) ** kappa)) for i in range(n)]

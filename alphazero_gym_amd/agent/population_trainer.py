@@ -11,8 +11,13 @@ the same losses, their ``d_raw`` and the tuned alpha's Adam step are one more ke
 launches, one synchronisation, one copy of ``losses[K, 5]`` to the host).  ``train_epoch`` / ``train_epoch_ring`` take the loop
 around that step to the device as well (``azg_trainer_epoch``): the minibatches are gathered by a kernel from the rows where they
 lie, the self-play ring included, and a whole epoch costs one synchronisation.  The single-agent path (``Agent.update``) is untouched.
+
+Every native call of a trainer goes through ``PopulationTrainer._call``: the form of the trainer's optimiser arguments, chosen once
+in ``__init__``, names a row of ``_capi.TRAINER_CALLS``, which says what ``_capi.Trainer`` method serves each call and how that
+method takes the optimiser; ``_call`` adds the loss settings and the learned temperature's state and keeps the step counts.
 """
 import ctypes as C
+import operator
 from collections import namedtuple
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -265,10 +270,115 @@ def _need_device_losses(losses: str, who: str) -> None:
                          "epoch runs on the device from the gather to the loss sums")
 
 
-# How a trainer makes its native calls, chosen once in ``__init__``: the suffix of the ``_capi.Trainer`` methods, what to pass them
-# as the optimiser's arguments and as the loss settings (callables: the step count and ``reload_settings`` change them), and whether
-# the trainer counts the optimiser's steps.
-_CallForm = namedtuple("_CallForm", "suffix opt_args cfg counts_steps")
+def _check_selfplay(who: str, selfplay, device, n_nets: int) -> None:
+    """The self-play engine sits on the trainer's GPU and has the trainer's number of nets."""
+    if int(selfplay.engine.cfg.device_id) != (device.index or 0):
+        raise ValueError(f"PopulationTrainer.{who}: the ring lies on another GPU than the trainer's nets")
+    if selfplay.n_nets != n_nets:
+        raise ValueError(f"PopulationTrainer.{who}: the self-play engine has {selfplay.n_nets} nets, the trainer {n_nets}")
+
+
+def _check_device_tensor(who: str, name: str, t, device, shape: tuple, shape_text: str) -> None:
+    """``t`` is a contiguous float32 tensor of ``shape`` on the trainer's GPU: one the native call reads or writes where it lies."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != device or not t.is_contiguous() or \
+            tuple(t.shape) != shape:
+        raise ValueError(f"PopulationTrainer.{who}: {name} must be a contiguous float32 tensor {shape_text} on the trainer's GPU")
+
+
+def _agents_optim(agents, shared: bool) -> Tuple[List[tuple], List[float]]:
+    """``optimizers="agents"``: every agent's (class, settings) and grad_clip after the checks -- grad_clip >= 0 and a supported
+    optimiser of one class for all; ``shared`` (``per_net=False``): with one grad_clip and one set of settings."""
+    clips = [float(a.clip or 0.0) for a in agents]
+    if any(c < 0 for c in clips):
+        raise ValueError("PopulationTrainer: grad_clip must be >= 0")
+    if shared and len(set(clips)) != 1:
+        raise ValueError("PopulationTrainer: every agent must have the same grad_clip")
+    settings = [_optimizer_settings(a.optimizer) for a in agents]
+    if len({st[0] for st in settings}) != 1:
+        raise ValueError("PopulationTrainer: every agent must have the same optimiser class")
+    if shared and len(set(settings)) != 1:
+        raise ValueError(f"PopulationTrainer: every agent must have the same {settings[0][0].__name__} settings")
+    return settings, clips
+
+
+def _check_losses(agents, per_net: bool, losses: str) -> None:
+    """The loss objects share everything (``population_loss`` is written for one set of settings) -- with ``per_net=True`` and
+    ``losses="device"`` only what they must (``_loss_shared``)."""
+    if len({(_loss_shared if per_net and losses == "device" else _loss_settings)(a.loss) for a in agents}) != 1:
+        raise ValueError("PopulationTrainer: every agent must have the same loss class and hyper-parameters"
+                         + (' (per-net loss settings need losses="device")' if per_net and losses != "device" else ""))
+
+
+def _same_steps(states: List[dict], whose: str) -> int:
+    """The step count of Adam ``states`` (one dictionary per parameter, empty before the first step) that must agree on it."""
+    if not any(states):
+        return 0
+    if not all(states) or len({float(st["step"]) for st in states}) != 1:
+        raise ValueError(f"PopulationTrainer: the agents' {whose} must have taken the same number of steps")
+    return int(float(states[0]["step"]))
+
+
+# What the constructor's checks hand to its later steps: the nets' descriptor and device, every agent's optimiser settings
+# (``_optimizer_settings``; with ``optimizers="rmsprop"``, ``_rmsprop_settings``) and grad_clip, Adam's step count, the alpha optimisers'
+# states (A0CLossTuned) and step count, and with ``losses="device"`` the azg_loss_cfg (``per_net``: one per net too).
+_Checked = namedtuple("_Checked", "desc device settings clips opt_step alpha_states alpha_step loss_cfg net_cfgs")
+
+
+def _check(agents, losses: str, optimizers: str, per_net: bool, layernorm: bool, wide: bool, wide_layernorm: bool) -> _Checked:
+    """Every refusal of the constructor, the arguments' and then the agents', in the order the tests know; changes nothing."""
+    if losses not in ("torch", "device"):
+        raise ValueError("losses must be 'torch' or 'device'")
+    if optimizers not in ("rmsprop", "agents"):
+        raise ValueError("optimizers must be 'rmsprop' or 'agents'")
+    if per_net and optimizers != "agents":
+        raise ValueError('PopulationTrainer: per_net=True requires optimizers="agents"')
+    if not agents:
+        raise ValueError("PopulationTrainer needs at least one agent")
+    a0 = agents[0]
+    if len({type(a.nn) for a in agents}) != 1:
+        raise ValueError("PopulationTrainer: every agent must have the same policy class")
+    if not isinstance(a0.nn, (DiscretePolicy, DiagonalNormalPolicy, DiagonalGMMPolicy)):
+        raise ValueError(f"PopulationTrainer: policy {type(a0.nn).__name__} is not supported")
+    if wide_layernorm and layernorm:
+        raise ValueError("PopulationTrainer: wide_layernorm=True and layernorm=True ask for two different trainers")
+    if wide and not wide_layernorm and (layernorm or any(a.nn.layernorm for a in agents)):
+        raise ValueError("PopulationTrainer: wide=True does not train LayerNorm trunks on the device")
+    if not layernorm and not wide_layernorm and any(a.nn.layernorm for a in agents):
+        raise ValueError("PopulationTrainer: LayerNorm trunks are not trained on the device")
+    opt_step = 0
+    if optimizers == "agents":
+        settings, clips = _agents_optim(agents, shared=not per_net)
+        if settings[0][0] is torch.optim.Adam:
+            opt_step = _same_steps([a.optimizer.state.get(p, {}) for a in agents for p in a.nn.parameters()], "Adam optimisers")
+    else:
+        if any(a.clip for a in agents):
+            raise ValueError("PopulationTrainer: grad_clip != 0 is not supported (a per-net global norm needs a pass of its own)")
+        settings, clips = [_rmsprop_settings(a.optimizer) for a in agents], [0.0] * len(agents)
+        if len(set(settings)) != 1:
+            raise ValueError("PopulationTrainer: every agent must have the same RMSprop settings")
+    _check_losses(agents, per_net, losses)
+    max_layers, max_width = (8, 1024) if (wide or wide_layernorm) else (3, 256)
+    unsupported = (f"PopulationTrainer: supported nets have 1-{max_layers} hidden layers of widths 16, 32, ... {max_width}, at most "
+                   "8 inputs and 16 distribution outputs")
+    if any(len(list(a.nn.hidden_dimensions)) > _capi.MAX_HIDDEN for a in agents):   # (more than a descriptor holds)
+        raise ValueError(unsupported)
+    descs = [_capi.policy_tensors(a.nn) for a in agents]
+    if any([tuple(t.shape) for t in ts] != [tuple(t.shape) for t in descs[0][1]] or bytes(d) != bytes(descs[0][0]) for d, ts in descs):
+        raise ValueError("PopulationTrainer: every agent must have the same network shape, activation and head settings")
+    d0 = descs[0][0]
+    hidden = [d0.hidden[i] for i in range(d0.n_hidden)]
+    if not (1 <= d0.n_hidden <= max_layers and all(h % 16 == 0 and 16 <= h <= max_width for h in hidden) and d0.in_dim <= 8
+            and d0.n_dist <= 16):
+        raise ValueError(unsupported)
+    pars = [p for a in agents for p in a.nn.parameters()]
+    device = pars[0].device
+    if device.type != "cuda" or any(p.device != device for p in pars):
+        raise ValueError("PopulationTrainer: every parameter must live on one GPU (there is no CPU form of the trainer's kernels)")
+    alpha_states = [a.loss.optimizer.state.get(a.loss.log_alpha, {}) for a in agents] if type(a0.loss) is A0CLossTuned else []
+    alpha_step = _same_steps(alpha_states, "alpha optimisers")
+    loss_cfg = _capi.loss_cfg(a0.nn, a0.loss) if losses == "device" else None
+    net_cfgs = [_capi.loss_cfg(a.nn, a.loss) for a in agents] if (per_net and losses == "device") else None
+    return _Checked(d0, device, settings, clips, opt_step, alpha_states, alpha_step, loss_cfg, net_cfgs)
 
 
 class PopulationTrainer:
@@ -287,10 +397,11 @@ class PopulationTrainer:
     the same step (``_capi.Trainer.step``).  Then ``log_alpha`` and its Adam state (``alpha_exp_avg``, ``alpha_exp_avg_sq``,
     ``alpha_step``) are plain tensors of the trainer that the kernel steps in place, and there is no ``alpha_optimizer``.
 
-    ``optimizers``: "rmsprop" (the default) takes plain RMSprop without gradient clipping and steps it inside the backward kernel.
-    "agents" takes what the agents carry -- plain RMSprop or ``torch.optim.Adam`` (no amsgrad), and their ``grad_clip`` -- through
-    the ``*_opt`` entry points: the backward launch writes the gradients first, then computes every net's global norm, clips and
-    steps.  Every agent must have the same optimiser class, settings and ``grad_clip``, and, with Adam, have taken the same number
+    ``optimizers``: "rmsprop" (the default) takes plain RMSprop without gradient clipping and steps it inside the backward kernel
+    (its weighted, errors and online calls, for which azg_rmsprop has no entry points, take the ``*_opt`` ones with the same
+    RMSprop as an azg_optim, ``_optim``: the same bits; ``opt_step`` stays 0).  "agents" takes what the agents carry -- plain RMSprop
+    or ``torch.optim.Adam`` (no amsgrad), and their ``grad_clip`` -- through the ``*_opt`` entry points: the backward launch writes
+    the gradients first, then computes every net's global norm, clips and steps.  Every agent must have the same optimiser class, settings and ``grad_clip``, and, with Adam, have taken the same number
     of steps.  Adam's ``exp_avg`` / ``exp_avg_sq`` become ``self.exp_avg`` / ``self.exp_avg_sq`` [K, P] with the agents' optimiser
     state as views of their rows; ``self.opt_step`` counts the steps and ``export_alpha()`` / ``close()`` write it to every
     ``state[p]["step"]``.  ``self.last_grad_norms`` [K] holds every net's gradient norm (before clipping) of the last step.
@@ -320,103 +431,47 @@ class PopulationTrainer:
     def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False, losses: str = "torch",
                  optimizers: str = "rmsprop", layernorm: bool = False, wide: bool = False, wide_layernorm: bool = False,
                  per_net: bool = False):
-        if losses not in ("torch", "device"):
-            raise ValueError("losses must be 'torch' or 'device'")
-        if optimizers not in ("rmsprop", "agents"):
-            raise ValueError("optimizers must be 'rmsprop' or 'agents'")
-        if per_net and optimizers != "agents":
-            raise ValueError('PopulationTrainer: per_net=True requires optimizers="agents"')
-        self.per_net = bool(per_net)
-        self.losses = losses
-        self.optimizers = optimizers
+        # 1. checks that touch nothing: the arguments, then the agents
         self.agents = list(agents)
-        if not self.agents:
-            raise ValueError("PopulationTrainer needs at least one agent")
-        a0 = self.agents[0]
-        K = len(self.agents)
-        if len({type(a.nn) for a in self.agents}) != 1:
-            raise ValueError("PopulationTrainer: every agent must have the same policy class")
-        if not isinstance(a0.nn, (DiscretePolicy, DiagonalNormalPolicy, DiagonalGMMPolicy)):
-            raise ValueError(f"PopulationTrainer: policy {type(a0.nn).__name__} is not supported")
-        self.layernorm = bool(layernorm)
-        self.wide = bool(wide)
-        self.wide_layernorm = bool(wide_layernorm)
-        if self.wide_layernorm and self.layernorm:
-            raise ValueError("PopulationTrainer: wide_layernorm=True and layernorm=True ask for two different trainers")
-        if self.wide and not self.wide_layernorm and (self.layernorm or any(a.nn.layernorm for a in self.agents)):
-            raise ValueError("PopulationTrainer: wide=True does not train LayerNorm trunks on the device")
-        if not self.layernorm and not self.wide_layernorm and any(a.nn.layernorm for a in self.agents):
-            raise ValueError("PopulationTrainer: LayerNorm trunks are not trained on the device")
-        opt_states: List[List[dict]] = []
-        if optimizers == "agents":
-            settings, net_clips = self._agents_optim(shared=not self.per_net)
-            if settings[0][0] is torch.optim.Adam:
-                opt_states = [[a.optimizer.state.get(p, {}) for p in a.nn.parameters()] for a in self.agents]
-                flat_states = [st for sts in opt_states for st in sts]
-                if any(flat_states) and (not all(flat_states) or len({float(st["step"]) for st in flat_states}) != 1):
-                    raise ValueError("PopulationTrainer: the agents' Adam optimisers must have taken the same number of steps")
-        else:
-            if any(a.clip for a in self.agents):
-                raise ValueError("PopulationTrainer: grad_clip != 0 is not supported (a per-net global norm needs a pass of its own)")
-            if len({_rmsprop_settings(a.optimizer) for a in self.agents}) != 1:
-                raise ValueError("PopulationTrainer: every agent must have the same RMSprop settings")
-        if self.per_net:
-            self._per_net_loss()
-        elif len({_loss_settings(a.loss) for a in self.agents}) != 1:
-            raise ValueError("PopulationTrainer: every agent must have the same loss class and hyper-parameters")
-        max_layers, max_width = (8, 1024) if (self.wide or self.wide_layernorm) else (3, 256)
-        unsupported = (f"PopulationTrainer: supported nets have 1-{max_layers} hidden layers of widths 16, 32, ... {max_width}, at most "
-                       "8 inputs and 16 distribution outputs")
-        if any(len(list(a.nn.hidden_dimensions)) > _capi.MAX_HIDDEN for a in self.agents):   # (more than a descriptor holds)
-            raise ValueError(unsupported)
-        descs = [_capi.policy_tensors(a.nn) for a in self.agents]
-        if any([tuple(t.shape) for t in ts] != [tuple(t.shape) for t in descs[0][1]] or bytes(d) != bytes(descs[0][0]) for d, ts in descs):
-            raise ValueError("PopulationTrainer: every agent must have the same network shape, activation and head settings")
-        d0 = descs[0][0]
-        hidden = [d0.hidden[i] for i in range(d0.n_hidden)]
-        if not (1 <= d0.n_hidden <= max_layers and all(h % 16 == 0 and 16 <= h <= max_width for h in hidden) and d0.in_dim <= 8
-                and d0.n_dist <= 16):
-            raise ValueError(unsupported)
-        pars = [p for a in self.agents for p in a.nn.parameters()]
-        device = pars[0].device
-        if device.type != "cuda" or any(p.device != device for p in pars):
-            raise ValueError("PopulationTrainer: every parameter must live on one GPU (there is no CPU form of the trainer's kernels)")
-        alpha_states = []
-        if type(a0.loss) is A0CLossTuned:
-            alpha_states = [a.loss.optimizer.state.get(a.loss.log_alpha, {}) for a in self.agents]
-            if any(alpha_states) and (not all(alpha_states) or len({float(s["step"]) for s in alpha_states}) != 1):
-                raise ValueError("PopulationTrainer: the agents' alpha optimisers must have taken the same number of steps")
-        self.loss_cfg = _capi.loss_cfg(a0.nn, a0.loss) if losses == "device" else None
-        net_cfgs = [_capi.loss_cfg(a.nn, a.loss) for a in self.agents] if (self.per_net and losses == "device") else None
-        self.loss_cfgs = None   # (per_net=True, losses="device": one azg_loss_cfg per net)
+        self.per_net, self.losses, self.optimizers = bool(per_net), losses, optimizers
+        self.layernorm, self.wide, self.wide_layernorm = bool(layernorm), bool(wide), bool(wide_layernorm)
+        c = _check(self.agents, losses, optimizers, self.per_net, self.layernorm, self.wide, self.wide_layernorm)
+        # 2. the native trainer: if it cannot be created, the agents are left as they were
         from .. import _native   # raises if libazgym_hip.so is missing
-
-        # the native trainer first: if it cannot be created, the agents are left as they were
+        K = len(self.agents)
         self.max_batch = int(max_batch)
         kind = "wide_layernorm" if self.wide_layernorm else "wide" if self.wide else "layernorm" if self.layernorm else None
-        self.trainer = _native.HipTrainer(d0, K, self.max_batch, device_id=device.index or 0, **({kind: True} if kind else {}))
-        self.policy, self.loss = a0.nn, a0.loss
-        self.device = device
-        self.desc, self.flat = bind_flat([a.nn for a in self.agents])
-        self.square_avg, self.exp_avg, self.exp_avg_sq, self.opt_step = None, None, None, 0
-        self.opt, self.last_grad_norms = None, None
-        adam = optimizers == "agents" and type(a0.optimizer) is torch.optim.Adam
+        self.trainer = _native.HipTrainer(c.desc, K, self.max_batch, device_id=c.device.index or 0, **({kind: True} if kind else {}))
+        self.policy, self.loss, self.device = self.agents[0].nn, self.agents[0].loss, c.device
+        self.loss_cfg, self.loss_cfgs = c.loss_cfg, None   # (loss_cfgs: per_net=True, losses="device": one azg_loss_cfg per net)
+        # the form of the trainer's calls: the row of _capi.TRAINER_CALLS and the optimiser settings its methods are given
+        self.opt, self.last_grad_norms, self.opt_step = None, None, c.opt_step
         if optimizers == "agents":
-            self._opt_settings = _optimizer_settings(a0.optimizer)
-            self.grad_clip = float(a0.clip or 0.0)
-            self.last_grad_norms = torch.zeros(K, dtype=torch.float32, device=device)
-            if self.per_net:
-                self._form = _CallForm("_nets", lambda: (self._optims(),), lambda: self.loss_cfgs, True)
-            else:
-                self._form = _CallForm("_opt", lambda: (self._optim(),), lambda: self.loss_cfg, True)
+            self._calls = _capi.TRAINER_CALLS["nets" if self.per_net else "opt"]
+            self._opt_settings, self.grad_clip = c.settings[0], c.clips[0]
+            self.last_grad_norms = torch.zeros(K, dtype=torch.float32, device=c.device)
         else:
-            lr, alpha, eps, wd = _rmsprop_settings(a0.optimizer)
+            self._calls = _capi.TRAINER_CALLS["rmsprop"]
+            lr, alpha, eps, wd = c.settings[0]
             self.opt = _capi.rmsprop_opt(lr=lr, alpha=alpha, eps=eps, weight_decay=wd)
-            self._form = _CallForm("", lambda: (self.opt, self.square_avg.data_ptr()), lambda: self.loss_cfg, False)
+            self._opt_settings = (torch.optim.RMSprop, lr, alpha, eps, wd)
+        # 3. binding: the parameters, the optimiser's moments, the learned temperature
+        self.desc, self.flat = bind_flat([a.nn for a in self.agents])
+        self._bind_moments(adam=self._opt_settings[0] is torch.optim.Adam)
+        self.grads = torch.zeros_like(self.flat) if keep_grads else None
+        self._bind_alpha(c.alpha_states, c.alpha_step)
+        self.last_raw: Optional[torch.Tensor] = None
+        self._last_d_raw: Optional[torch.Tensor] = None
+        # 4. the per-net arrays
+        if self.per_net:
+            self._set_net_entries(c.settings, c.clips, c.net_cfgs)
+
+    def _bind_moments(self, adam: bool) -> None:
+        """The optimiser's moments as [K, P] tensors of the trainer (``square_avg``, or Adam's ``exp_avg`` and ``exp_avg_sq``), every
+        agent's ``optimizer.state`` entries re-pointed at views of its row; state an agent already has is taken over."""
+        self.square_avg, self.exp_avg, self.exp_avg_sq = None, None, None
         if adam:
             self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-            if opt_states and opt_states[0] and opt_states[0][0]:
-                self.opt_step = int(float(opt_states[0][0]["step"]))
             bound = (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq))
         else:
             self.square_avg = torch.zeros_like(self.flat)
@@ -434,30 +489,32 @@ class PopulationTrainer:
                         view.copy_(st[name])
                     st[name] = view
                 off += p.numel()
-        self.grads = torch.zeros_like(self.flat) if keep_grads else None
+
+    def _bind_alpha(self, states: List[dict], step: int) -> None:
+        """A0CLossTuned: the K learned temperatures as ``log_alpha`` [K] with the agents' alpha optimisers' ``states`` taken over --
+        ``losses="device"``: plain float32 tensors that the loss kernel steps, ``alpha_step`` counting; ``losses="torch"``: a leaf
+        under one torch Adam, ``alpha_optimizer``, which counts its own steps."""
         self.log_alpha, self.alpha_optimizer = None, None
         self.alpha_exp_avg, self.alpha_exp_avg_sq, self.alpha_step = None, None, 0
-        if type(self.loss) is A0CLossTuned and losses == "device":
+        if type(self.loss) is not A0CLossTuned:
+            return
+        device = self.device
+        if self.losses == "device":
             self.log_alpha = torch.stack([a.loss.log_alpha.detach().to(device, dtype=torch.float32) for a in self.agents]).contiguous()
             self.alpha_exp_avg, self.alpha_exp_avg_sq = torch.zeros_like(self.log_alpha), torch.zeros_like(self.log_alpha)
-            if any(alpha_states):
-                self.alpha_step = int(float(alpha_states[0]["step"]))
-                self.alpha_exp_avg = torch.stack([s["exp_avg"].to(device, dtype=torch.float32) for s in alpha_states]).contiguous()
-                self.alpha_exp_avg_sq = torch.stack([s["exp_avg_sq"].to(device, dtype=torch.float32) for s in alpha_states]).contiguous()
-        elif type(self.loss) is A0CLossTuned:
-            self.log_alpha = torch.stack([a.loss.log_alpha.detach().to(device) for a in self.agents]).requires_grad_(True)
-            g = a0.loss.optimizer.param_groups[0]
-            self.alpha_optimizer = torch.optim.Adam([self.log_alpha], lr=g["lr"], betas=g["betas"], eps=g["eps"],
-                                                    weight_decay=g["weight_decay"])
-            if any(alpha_states):
-                self.alpha_optimizer.state[self.log_alpha] = {
-                    "step": torch.tensor(float(alpha_states[0]["step"])),
-                    "exp_avg": torch.stack([s["exp_avg"].to(device) for s in alpha_states]),
-                    "exp_avg_sq": torch.stack([s["exp_avg_sq"].to(device) for s in alpha_states])}
-        self.last_raw: Optional[torch.Tensor] = None
-        self._last_d_raw: Optional[torch.Tensor] = None
-        if self.per_net:
-            self._set_net_entries(settings, net_clips, net_cfgs)
+            if any(states):
+                self.alpha_step = step
+                self.alpha_exp_avg = torch.stack([s["exp_avg"].to(device, dtype=torch.float32) for s in states]).contiguous()
+                self.alpha_exp_avg_sq = torch.stack([s["exp_avg_sq"].to(device, dtype=torch.float32) for s in states]).contiguous()
+            return
+        self.log_alpha = torch.stack([a.loss.log_alpha.detach().to(device) for a in self.agents]).requires_grad_(True)
+        g = self.loss.optimizer.param_groups[0]
+        self.alpha_optimizer = torch.optim.Adam([self.log_alpha], lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"])
+        if any(states):
+            self.alpha_optimizer.state[self.log_alpha] = {
+                "step": torch.tensor(float(step)),
+                "exp_avg": torch.stack([s["exp_avg"].to(device) for s in states]),
+                "exp_avg_sq": torch.stack([s["exp_avg_sq"].to(device) for s in states])}
 
     @property
     def last_d_raw(self) -> Optional[torch.Tensor]:
@@ -510,71 +567,60 @@ class PopulationTrainer:
             raise ValueError(f"PopulationTrainer.update: needs [K = {K}, 1..{self.max_batch} rows, ...] minibatches")
         states = states.reshape(K, B, -1)
         raw = torch.empty((K, B, self.trainer.n_raw), dtype=torch.float32, device=self.device)
-        stream = torch.cuda.current_stream(self.device)
         if weights is not None:
             weights = self._row_weights("update", weights, K, B)
-        if self.losses == "device":
-            return self._update_device(states, actions, counts, values, raw, stream, weights)
-        stream.synchronize()
-        self.trainer.forward(self.flat.data_ptr(), states.data_ptr(), B, raw.data_ptr())
-        self.last_raw = raw
-        raw.requires_grad_(True)
-        if weights is None:
-            losses = population_loss(self.policy, self.loss, raw, actions, counts, values, self.log_alpha, self.alpha_optimizer)
-        else:
-            losses = population_loss(self.policy, self.loss, raw, actions, counts, values, self.log_alpha, self.alpha_optimizer,
-                                     weights=weights)
-        losses["loss"].sum().backward()
-        d_raw = self._last_d_raw = raw.grad.contiguous()
-        out = per_net(losses)   # (the copy to the host also completes d_raw)
-        stream.synchronize()
         grads = self.grads.data_ptr() if self.grads is not None else None
+        if self.losses == "device":   # one native call (three launches), one copy of losses[K, 5] to the host
+            actions, counts = actions.reshape(K, B, -1), counts.reshape(K, B, -1)
+            variant, w = ("plain", ()) if weights is None else ("weighted", (weights.data_ptr(),))
+            return self._call("step", variant, (self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(),
+                                                values.data_ptr(), *w, B, actions.shape[2]), (grads, raw.data_ptr()), raw=raw)[1]
+        torch.cuda.current_stream(self.device).synchronize()
+        self.trainer.forward(self.flat.data_ptr(), states.data_ptr(), B, raw.data_ptr())
+        raw.requires_grad_(True)
+        losses = population_loss(self.policy, self.loss, raw, actions, counts, values, self.log_alpha, self.alpha_optimizer, weights=weights)
+        losses["loss"].sum().backward()
+        d_raw = raw.grad.contiguous()
+        out = per_net(losses)   # (the copy to the host also completes d_raw)
         # (a clip happens inside: PyTorch never sees the parameter gradients)
-        self._call("backward_step", (self.flat.data_ptr(), d_raw.data_ptr(), B), (grads,))
+        self._call("backward_step", "plain", (self.flat.data_ptr(), d_raw.data_ptr(), B), (grads,), raw=raw, d_raw=d_raw)
         return out
 
-    def _call(self, family: str, head: tuple, tail: tuple, weighted: bool = False, errors: bool = False):
-        """The trainer's ``family`` call in this trainer's form: ``head``, the optimiser's arguments, ``tail``.  Counts the steps it
-        took (an epoch returns their number).  ``weighted``: the ``*_weighted`` method of the form (``head`` carries the weights);
-        the azg_rmsprop family has none, and its trainer calls ``*_opt_weighted`` with the same RMSprop and no clip: the same bits.
-        ``errors``: the ``*_errors`` method likewise (``head`` carries the weights, or None, and the errors)."""
-        if weighted or errors:
-            suffix, opt_args = self._form.suffix, self._form.opt_args()
-            if not suffix:
-                o = self.opt
-                suffix, opt_args = "_opt", (_capi.optim("rmsprop", o.lr, self.square_avg.data_ptr(), eps=o.eps,
-                                                        weight_decay=o.weight_decay, alpha=o.alpha),)
-            n_steps = getattr(self.trainer, family + suffix + ("_errors" if errors else "_weighted"))(*head, *opt_args, *tail)
-        else:
-            n_steps = getattr(self.trainer, family + self._form.suffix)(*head, *self._form.opt_args(), *tail)
-        if self._form.counts_steps:
-            self.opt_step += 1 if n_steps is None else n_steps
-        return n_steps
-
-    def _agents_optim(self, shared: bool) -> Tuple[List[tuple], List[float]]:
-        """``optimizers="agents"``: every agent's (class, settings) and grad_clip after the checks -- grad_clip >= 0 and a supported
-        optimiser of one class for all; ``shared`` (``per_net=False``): with one grad_clip and one set of settings."""
-        clips = [float(a.clip or 0.0) for a in self.agents]
-        if any(c < 0 for c in clips):
-            raise ValueError("PopulationTrainer: grad_clip must be >= 0")
-        if shared and len(set(clips)) != 1:
-            raise ValueError("PopulationTrainer: every agent must have the same grad_clip")
-        settings = [_optimizer_settings(a.optimizer) for a in self.agents]
-        if len({st[0] for st in settings}) != 1:
-            raise ValueError("PopulationTrainer: every agent must have the same optimiser class")
-        if shared and len(set(settings)) != 1:
-            raise ValueError(f"PopulationTrainer: every agent must have the same {settings[0][0].__name__} settings")
-        return settings, clips
-
-    def _per_net_loss(self) -> None:
-        """``per_net=True``: the loss objects share what they must (``losses="device"``), or everything (``losses="torch"``:
-        ``population_loss`` is written for one set of settings)."""
-        if self.losses == "device":
-            if len({_loss_shared(a.loss) for a in self.agents}) != 1:
-                raise ValueError("PopulationTrainer: every agent must have the same loss class and hyper-parameters")
-        elif len({_loss_settings(a.loss) for a in self.agents}) != 1:
-            raise ValueError("PopulationTrainer: every agent must have the same loss class and hyper-parameters "
-                             '(per-net loss settings need losses="device")')
+    def _call(self, family: str, variant: str, head: tuple, tail: tuple = (), raw=None, d_raw=None, steps: Optional[int] = None, **kw):
+        """Every native call that steps the nets, and the bookkeeping after it: (what the method returned, the K loss dictionaries).
+        ``family`` ("backward_step", "step", "epoch") and ``variant`` ("plain", "weighted", "errors", "online") name the entry of
+        ``self._calls``: the ``_capi.Trainer`` method and the form in which it takes the optimiser.  The method gets ``head``, the
+        loss settings and the learned temperature's state, the optimiser's arguments, ``tail`` and the [K, 5] table it writes the
+        losses to (float32 for a step, float64 for an epoch's sums) -- "backward_step", with no loss in it, only ``head``, the
+        optimiser and ``tail``.  The work queued on the current stream is complete before it.  Afterwards the steps taken
+        (``steps``; else what the method returns, an epoch's number of minibatches; else 1) are counted in ``opt_step``, which stays
+        0 for ``optimizers="rmsprop"``, and in ``alpha_step`` where the call stepped a learned temperature; ``last_raw`` /
+        ``last_d_raw`` become ``raw`` / ``d_raw`` (None: the raw outputs stay in the native trainer)."""
+        method, opt_form = self._calls[family, variant]
+        with_loss = family != "backward_step"
+        tuned = with_loss and self.log_alpha is not None
+        if with_loss:
+            state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
+                                      self.alpha_exp_avg_sq.data_ptr()) if tuned else None
+            head += (self.loss_cfgs if self.per_net else self.loss_cfg, state)
+            table = torch.empty((len(self.agents), len(_capi.LOSS_KEYS)), dtype=torch.float32 if family == "step" else torch.float64,
+                                device=self.device)
+            tail += (table.data_ptr(),)
+        if opt_form == "nets":   # (per_net=True: the array of azg_optim, the step count written into all)
+            self._net_steps[:] = self.opt_step
+        opt = (self._net_opts,) if opt_form == "nets" else (self._optim(),) if opt_form == "opt" else (self.opt, self.square_avg.data_ptr())
+        torch.cuda.current_stream(self.device).synchronize()
+        out = method(self.trainer, *head, *opt, *tail, **kw)
+        n_steps = steps if steps is not None else 1 if out is None else out
+        if self.optimizers == "agents":
+            self.opt_step += n_steps
+        if tuned:
+            self.alpha_step += n_steps
+        self.last_raw, self._last_d_raw = raw, d_raw
+        if not with_loss:
+            return out, None
+        slots = [(key, _capi.LOSS_KEYS.index(key)) for key in _capi.LOSS_KEYS_OF[self.loss_cfg.kind]]
+        return out, [{key: row[i] for key, i in slots} for row in table.cpu().tolist()]
 
     def reload_settings(self) -> None:
         """Read every agent's ``optimizer.param_groups[0]``, ``clip`` and loss object again (``per_net=True`` only), with the
@@ -583,15 +629,15 @@ class PopulationTrainer:
         not touched."""
         if not self.per_net:
             raise ValueError("PopulationTrainer.reload_settings needs a trainer built with per_net=True")
-        settings, clips = self._agents_optim(shared=False)
+        settings, clips = _agents_optim(self.agents, shared=False)
         if settings[0][0] is not self._opt_settings[0]:
             raise ValueError("PopulationTrainer.reload_settings: the optimiser class cannot change")
-        self._per_net_loss()
+        _check_losses(self.agents, True, self.losses)
         cfgs = None
         if self.losses == "device":
             cfgs = [_capi.loss_cfg(a.nn, a.loss) for a in self.agents]
-            if any((c.kind, c.head, c.reduction, c.action_bound) != (self.loss_cfg.kind, self.loss_cfg.head, self.loss_cfg.reduction,
-                                                                     self.loss_cfg.action_bound) for c in cfgs):
+            fixed = operator.attrgetter("kind", "head", "reduction", "action_bound")
+            if any(fixed(c) != fixed(self.loss_cfg) for c in cfgs):
                 raise ValueError("PopulationTrainer.reload_settings: loss class, head and reduction cannot change")
         self._set_net_entries(settings, clips, cfgs)
 
@@ -643,7 +689,7 @@ class PopulationTrainer:
 
     def _set_net_entries(self, settings: List[tuple], clips: List[float], cfgs: Optional[list]) -> None:
         """``per_net=True``: the arrays the ``*_nets`` calls read, built once per set of settings -- one azg_optim per net (its
-        agent's settings over the shared state tensors; ``_optims`` writes the step count into all of them) and, with
+        agent's settings over the shared state tensors; ``_call`` writes the step count into all of them) and, with
         ``losses="device"``, one azg_loss_cfg per net."""
         out = [self._azg_optim(st, clip) for st, clip in zip(settings, clips)]
         opts = (_capi.AzgOptim * len(out))(*out)
@@ -653,14 +699,10 @@ class PopulationTrainer:
         self._net_opts, self._net_steps = opts, steps
         self.loss_cfgs = (_capi.AzgLossCfg * len(cfgs))(*cfgs) if cfgs is not None else None
 
-    def _optims(self):
-        """``per_net=True``: the azg_optim array of the next step."""
-        self._net_steps[:] = self.opt_step
-        return self._net_opts
-
     def _azg_optim(self, st: tuple, clip: float):
         """azg_optim of an ``_optimizer_settings`` tuple and a grad_clip over the trainer's state tensors and step count."""
-        common = dict(grad_clip=clip, step=self.opt_step, grad_norms=self.last_grad_norms.data_ptr())
+        norms = self.last_grad_norms
+        common = dict(grad_clip=clip, step=self.opt_step, grad_norms=norms.data_ptr() if norms is not None else None)
         if st[0] is torch.optim.Adam:
             _, lr, betas, eps, wd = st
             return _capi.optim("adam", lr, self.exp_avg_sq.data_ptr(), self.exp_avg.data_ptr(), eps=eps, weight_decay=wd, betas=betas,
@@ -669,29 +711,10 @@ class PopulationTrainer:
         return _capi.optim("rmsprop", lr, self.square_avg.data_ptr(), eps=eps, weight_decay=wd, alpha=alpha, **common)
 
     def _optim(self):
-        """azg_optim of the next step (``optimizers="agents"``): the agents' settings, the trainer's state tensors and step count."""
-        return self._azg_optim(self._opt_settings, self.grad_clip)
-
-    def _update_device(self, states, actions, counts, values, raw, stream, weights=None) -> List[Dict[str, float]]:
-        """``update`` with the losses on the device: one native call (three launches), one copy of losses[K, 5] to the host."""
-        K, B = raw.shape[0], raw.shape[1]
-        actions, counts = actions.reshape(K, B, -1), counts.reshape(K, B, -1)
-        table = torch.empty((K, len(_capi.LOSS_KEYS)), dtype=torch.float32, device=self.device)
-        tuned = self.log_alpha is not None
-        state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
-                                  self.alpha_exp_avg_sq.data_ptr()) if tuned else None
-        stream.synchronize()
-        grads = self.grads.data_ptr() if self.grads is not None else None
-        w = () if weights is None else (weights.data_ptr(),)
-        self._call("step", (self.flat.data_ptr(), states.data_ptr(), actions.data_ptr(), counts.data_ptr(), values.data_ptr(), *w, B,
-                              actions.shape[2], self._form.cfg(), state), (grads, raw.data_ptr(), table.data_ptr()),
-                   weighted=weights is not None)
-        if tuned:
-            self.alpha_step += 1
-        self.last_raw, self._last_d_raw = raw, None
-        rows = table.cpu().tolist()
-        slots = [(key, _capi.LOSS_KEYS.index(key)) for key in _capi.LOSS_KEYS_OF[self.loss_cfg.kind]]
-        return [{key: row[i] for key, i in slots} for row in rows]
+        """azg_optim of the next step over the trainer's state tensors and step count.  ``optimizers="agents"``: the agents' settings
+        and grad_clip.  ``optimizers="rmsprop"``: the trainer's RMSprop restated for the ``*_opt`` entry points that serve its
+        weighted, errors and online calls (azg_rmsprop has none): no clip, no grad_norms, step 0 -- the same bits."""
+        return self._azg_optim(self._opt_settings, self.grad_clip if self.optimizers == "agents" else 0.0)
 
     def train_on_rows(self, rows_per_net, state_dim: int, K: int, batch_size: int = 32,
                       shuffle_seeds: Optional[Sequence[int]] = None, weights=None) -> List[Dict[str, float]]:
@@ -710,17 +733,14 @@ class PopulationTrainer:
         order = torch.from_numpy(np.stack([np.random.RandomState(int(s)).permutation(n) for s in seeds])).to(self.device)
         net = torch.arange(N, device=self.device)[:, None]
         sums: List[Dict[str, float]] = [{} for _ in range(N)]
-        i = 0
-        while i < n:
-            j = n if i + 2 * batch_size > n else i + batch_size
+        for i, j in minibatch_bounds(n, batch_size):
             b = rows[net, order[:, i:j]]
             batch = (b[..., :state_dim], b[..., state_dim:state_dim + K], b[..., state_dim + K:state_dim + 2 * K],
                      b[..., state_dim + 2 * K:state_dim + 3 * K], b[..., -1])
-            infos = self.update(batch) if weights is None else self.update(batch, weights=weights[net, order[:, i:j]])
+            infos = self.update(batch, weights=None if weights is None else weights[net, order[:, i:j]])
             for s, info in zip(sums, infos):
                 for key, val in info.items():
                     s[key] = s.get(key, 0.0) + val
-            i = j
         return sums
 
     def _epoch(self, who: str, where, order: np.ndarray, batch_size: int, weights: Optional[int] = None,
@@ -728,27 +748,13 @@ class PopulationTrainer:
         """azg_trainer_epoch on rows described by ``where`` (``_capi.epoch_rows``), their producers complete; the per-net sums.
         ``weights``: the device address of a float32 array addressed like the rows (None: the unweighted epoch).  ``errors``: the
         device address of a float32 array addressed like them that receives the trained rows' value errors (None: none)."""
-        K = len(self.agents)
         bounds = minibatch_bounds(order.shape[1], int(batch_size))
         if not bounds or max(j - i for i, j in bounds) > self.max_batch:
             raise ValueError(f"PopulationTrainer.{who}: needs minibatches of 1..{self.max_batch} rows")
-        sums = torch.empty((K, len(_capi.LOSS_KEYS)), dtype=torch.float64, device=self.device)
-        tuned = self.log_alpha is not None
-        state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
-                                  self.alpha_exp_avg_sq.data_ptr()) if tuned else None
-        torch.cuda.current_stream(self.device).synchronize()
-        w = () if weights is None else (weights,)
-        if errors is not None:
-            w = (weights, errors)
-        n_steps = self._call("epoch", (self.flat.data_ptr(), where, *w, order, int(batch_size), self._form.cfg(), state),
-                             (sums.data_ptr(),), weighted=weights is not None, errors=errors is not None)
+        variant, w = ("errors", (weights, errors)) if errors is not None else ("weighted", (weights,)) if weights is not None else ("plain", ())
+        n_steps, sums = self._call("epoch", variant, (self.flat.data_ptr(), where, *w, order, int(batch_size)))
         assert n_steps == len(bounds)
-        if tuned:
-            self.alpha_step += n_steps
-        self.last_raw, self._last_d_raw = None, None   # (the minibatches' raw outputs stay in the native trainer)
-        table = sums.cpu().tolist()
-        slots = [(key, _capi.LOSS_KEYS.index(key)) for key in _capi.LOSS_KEYS_OF[self.loss_cfg.kind]]
-        return [{key: row[i] for key, i in slots} for row in table]
+        return sums
 
     def train_epoch(self, rows_per_net, state_dim: int, K: int, batch_size: int = 32,
                     shuffle_seeds: Optional[Sequence[int]] = None, weights=None, errors=None) -> List[Dict[str, float]]:
@@ -772,9 +778,7 @@ class PopulationTrainer:
         if weights is not None:
             weights = self._row_weights("train_epoch", weights, N, n)
         if errors is not None:
-            if not isinstance(errors, torch.Tensor) or errors.dtype != torch.float32 or errors.device != self.device or \
-                    not errors.is_contiguous() or tuple(errors.shape) != (N, n):
-                raise ValueError(f"PopulationTrainer.train_epoch: errors must be a contiguous float32 tensor [{N}, {n}] on the trainer's GPU")
+            _check_device_tensor("train_epoch", "errors", errors, self.device, (N, n), f"[{N}, {n}]")
         return self._epoch("train_epoch", _capi.epoch_rows(rows.data_ptr(), state_dim, K, n), order, batch_size,
                            None if weights is None else weights.data_ptr(), None if errors is None else errors.data_ptr())
 
@@ -801,12 +805,8 @@ class PopulationTrainer:
             if getattr(selfplay, "prioritized", None) is None:
                 raise ValueError('PopulationTrainer.train_epoch_ring: weights="priority" needs a self-play engine built with '
                                  "prioritized=")
+        _check_selfplay("train_epoch_ring", selfplay, self.device, len(self.agents))
         engine = selfplay.engine
-        if int(engine.cfg.device_id) != (self.device.index or 0):
-            raise ValueError("PopulationTrainer.train_epoch_ring: the ring lies on another GPU than the trainer's nets")
-        if selfplay.n_nets != len(self.agents):
-            raise ValueError(f"PopulationTrainer.train_epoch_ring: the self-play engine has {selfplay.n_nets} nets, the trainer "
-                             f"{len(self.agents)}")
         order = np.asarray(order)
         if order.ndim != 2 or order.shape[0] != len(self.agents) or order.shape[1] < 1 or order.dtype.kind not in "iu":
             raise ValueError("PopulationTrainer.train_epoch_ring: order must be an int array [K, n_order >= 1]")
@@ -823,10 +823,8 @@ class PopulationTrainer:
         if isinstance(weights, str):
             w_ptr = engine.selfplay_is_weights_device()
         elif weights is not None:
-            if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.device != self.device or \
-                    not weights.is_contiguous() or tuple(weights.shape) != (int(selfplay.capacity), int(selfplay.n_games)):
-                raise ValueError("PopulationTrainer.train_epoch_ring: weights must be a contiguous float32 tensor "
-                                 "[capacity_steps, n_games] on the trainer's GPU")
+            _check_device_tensor("train_epoch_ring", "weights", weights, self.device, (int(selfplay.capacity), int(selfplay.n_games)),
+                                 "[capacity_steps, n_games]")
             w_ptr = weights.data_ptr()
         e_ptr = engine.selfplay_errors_device() if errors else None
         engine.sync()
@@ -851,35 +849,11 @@ class PopulationTrainer:
         M, B = int(n_minibatches), int(batch_size)
         if M < 1 or not 1 <= B <= self.max_batch:
             raise ValueError(f"PopulationTrainer.train_online_ring: needs n_minibatches >= 1 and a batch_size of 1..{self.max_batch}")
-        engine = selfplay.engine
-        if int(engine.cfg.device_id) != (self.device.index or 0):
-            raise ValueError("PopulationTrainer.train_online_ring: the ring lies on another GPU than the trainer's nets")
-        if selfplay.n_nets != len(self.agents):
-            raise ValueError(f"PopulationTrainer.train_online_ring: the self-play engine has {selfplay.n_nets} nets, the trainer "
-                             f"{len(self.agents)}")
-        K = len(self.agents)
-        sums = torch.empty((K, len(_capi.LOSS_KEYS)), dtype=torch.float64, device=self.device)
-        tuned = self.log_alpha is not None
-        state = _capi.alpha_state(self.alpha_step, self.log_alpha.data_ptr(), self.alpha_exp_avg.data_ptr(),
-                                  self.alpha_exp_avg_sq.data_ptr()) if tuned else None
-        suffix, opt_args = self._form.suffix, self._form.opt_args()
-        if not suffix:   # (the azg_rmsprop family has no online form: the same RMSprop as an azg_optim, as ``_call`` does)
-            o = self.opt
-            opt_args = (_capi.optim("rmsprop", o.lr, self.square_avg.data_ptr(), eps=o.eps, weight_decay=o.weight_decay, alpha=o.alpha),)
-        call = self.trainer.epoch_online_nets if suffix == "_nets" else self.trainer.epoch_online
-        torch.cuda.current_stream(self.device).synchronize()
-        drawn = call(engine, self.flat.data_ptr(), M, B, selfplay._sample_index, prio.get("beta", 0.0),
-                     _capi.trained_priority_config(prio["alpha"], prio["eps"], prio["feedback"]), self._form.cfg(), state, opt_args[0],
-                     sums.data_ptr(), return_drawn=return_drawn)
+        _check_selfplay("train_online_ring", selfplay, self.device, len(self.agents))
+        head = (selfplay.engine, self.flat.data_ptr(), M, B, selfplay._sample_index, prio.get("beta", 0.0),
+                _capi.trained_priority_config(prio["alpha"], prio["eps"], prio["feedback"]))
+        drawn, out = self._call("epoch", "online", head, steps=M, return_drawn=return_drawn)
         selfplay._sample_index += M
-        if self._form.counts_steps:
-            self.opt_step += M
-        if tuned:
-            self.alpha_step += M
-        self.last_raw, self._last_d_raw = None, None   # (the minibatches' raw outputs stay in the native trainer)
-        table = sums.cpu().tolist()
-        slots = [(key, _capi.LOSS_KEYS.index(key)) for key in _capi.LOSS_KEYS_OF[self.loss_cfg.kind]]
-        out = [{key: row[i] for key, i in slots} for row in table]
         return (out, drawn) if return_drawn else out
 
     def export_alpha(self) -> None:
