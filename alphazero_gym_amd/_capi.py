@@ -219,7 +219,8 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "trainer_loss_weighted", "trainer_loss_nets_weighted", "trainer_step_opt_weighted", "trainer_step_nets_weighted",
                     "trainer_epoch_opt_weighted", "trainer_epoch_nets_weighted",
                     "trainer_loss_errors", "trainer_loss_nets_errors", "trainer_epoch_opt_errors", "trainer_epoch_nets_errors",
-                    "trainer_epoch_online", "trainer_epoch_online_nets"]
+                    "trainer_epoch_online", "trainer_epoch_online_nets",
+                    "trainer_set_ema", "trainer_ema_info", "use_weights", "weights_info"]
 
 
 class AzgNetSearch(C.Structure):
@@ -307,6 +308,15 @@ class AzgEpochRows(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("row_len", C.c_int32), ("state_dim", C.c_int32), ("n_actions", C.c_int32),
                 ("rows_per_net", C.c_int32), ("group", C.c_int32), ("group_stride", C.c_int64), ("net_stride", C.c_int64),
                 ("rows", C.c_void_p)]
+
+
+class AzgEmaCfg(C.Structure):
+    """include/azgym_train_ema.h: azg_ema_cfg"""
+    _fields_ = [("struct_size", C.c_int32), ("n_decay", C.c_int32), ("every", C.c_int32), ("reserved", C.c_int32),
+                ("ema", C.c_void_p), ("decay", C.POINTER(C.c_double))]
+
+
+WEIGHTS_LIVE, WEIGHTS_TARGET = 0, 1   # include/azgym_target.h: AZG_WEIGHTS_*
 
 
 def bind(lib, prefix):
@@ -462,6 +472,12 @@ def bind(lib, prefix):
     if "trainer_epoch_online" in f:   # include/azgym_train_online.h
         f["trainer_epoch_online"].argtypes = f["trainer_epoch_online_nets"].argtypes = [
             vp, vp, vp, C.POINTER(AzgOnlineEpoch), C.POINTER(AzgLossCfg), C.POINTER(AzgAlphaState), C.POINTER(AzgOptim), vp]
+    if "trainer_set_ema" in f:   # include/azgym_train_ema.h
+        f["trainer_set_ema"].argtypes = [vp, C.POINTER(AzgEmaCfg)]
+        f["trainer_ema_info"].argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    if "use_weights" in f:   # include/azgym_target.h
+        f["use_weights"].argtypes = [vp, C.c_int32]
+        f["weights_info"].argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     return f
 
 
@@ -718,6 +734,18 @@ class Engine:
         for k, pol in enumerate(policies):
             self.set_net_policy(k, pol)
         return "host"
+
+    def use_weights(self, which):
+        """azg_use_weights: ``which`` "live" or "target" (or AZG_WEIGHTS_*) becomes the weight set every upload writes and every
+        network evaluation reads (include/azgym_target.h)."""
+        which = {"live": WEIGHTS_LIVE, "target": WEIGHTS_TARGET}.get(which, which)
+        self._check(self._optional("use_weights")(self._h, int(which)))
+
+    def weights_info(self):
+        """azg_weights_info: {"in_use": "live" | "target", "target_ready": bool}."""
+        in_use, ready = C.c_int32(0), C.c_int32(0)
+        self._check(self._optional("weights_info")(self._h, C.byref(in_use), C.byref(ready)))
+        return {"in_use": "target" if in_use.value == WEIGHTS_TARGET else "live", "target_ready": bool(ready.value)}
 
     def results_resident(self):
         """azg_results_resident: launch return_results into the engine's device buffers; their addresses as a dict of ints."""
@@ -1570,6 +1598,27 @@ class Trainer:
     def read_d_raw(self, n_rows, d_raw):
         """azg_trainer_read_d_raw: the last ``step``'s d_raw [n_nets, n_rows, 1 + n_dist] into the caller's device array."""
         self._check(self._f["trainer_read_d_raw"](self._h, int(n_rows), d_raw or None))
+
+    # ---- the moving average of the parameters (include/azgym_train_ema.h) ----
+
+    def set_ema(self, ema, decay=None, every=1):
+        """azg_trainer_set_ema: from now on every ``every``-th optimiser step is followed by ema += (1 - decay) * (params - ema) on
+        the device.  ``ema``: the device address of the caller's float32 [n_nets, P] array, which must stay alive; ``decay``: one
+        number or one per net, each in [0, 1).  ``ema`` None detaches."""
+        fn = _require(self._f, "trainer_set_ema")
+        if ema is None:
+            self._check(fn(self._h, None))
+            return
+        decays = [float(d) for d in (decay if np.ndim(decay) else [decay])]
+        arr = (C.c_double * max(len(decays), 1))(*decays)
+        cfg = AzgEmaCfg(C.sizeof(AzgEmaCfg), len(decays), int(every), 0, ema or None, arr)
+        self._check(fn(self._h, C.byref(cfg)))
+
+    def ema_info(self):
+        """azg_trainer_ema_info: (optimiser steps seen, launches of the average's kernel) since the last attach."""
+        steps, updates = C.c_int64(0), C.c_int64(0)
+        self._check(_require(self._f, "trainer_ema_info")(self._h, C.byref(steps), C.byref(updates)))
+        return steps.value, updates.value
 
 
 # Which ``Trainer`` method serves a (family, variant) call of a trainer whose optimiser arguments have the form "rmsprop" (an

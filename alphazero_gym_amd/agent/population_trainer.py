@@ -309,6 +309,29 @@ def _check_losses(agents, per_net: bool, losses: str) -> None:
                          + (' (per-net loss settings need losses="device")' if per_net and losses != "device" else ""))
 
 
+def _ema_settings(ema, K: int) -> Tuple[Any, int]:
+    """``PopulationTrainer(ema=...)`` as (decay, every): a decay, a list of K decays, or ``{"decay": either, "every": N}`` (``every``
+    absent: 1).  Every decay is finite and in [0, 1), ``every`` an int >= 1: ``ValueError`` otherwise, before anything is touched."""
+    every = 1
+    if isinstance(ema, dict):
+        unknown = sorted(set(ema) - {"decay", "every"})
+        if unknown or "decay" not in ema:
+            raise ValueError(f"PopulationTrainer: ema takes decay and every, not {unknown}" if unknown else
+                             "PopulationTrainer: ema needs a decay")
+        every, ema = ema.get("every", 1), ema["decay"]
+    if isinstance(every, bool) or int(every) != every or int(every) < 1:
+        raise ValueError(f"PopulationTrainer: ema every must be an int >= 1, got {every!r}")
+    if np.ndim(ema) > 1 or isinstance(ema, str):
+        raise ValueError("PopulationTrainer: ema decay must be a number or one number per net")
+    decay = [float(d) for d in ema] if np.ndim(ema) == 1 else float(ema)
+    if isinstance(decay, list) and len(decay) != K:
+        raise ValueError(f"PopulationTrainer: ema decay has {len(decay)} entries for {K} nets: a number or one per net")
+    for d in decay if isinstance(decay, list) else [decay]:
+        if not (np.isfinite(d) and 0.0 <= d < 1.0):
+            raise ValueError(f"PopulationTrainer: every ema decay must be finite and in [0, 1), got {d}")
+    return decay, int(every)
+
+
 def _same_steps(states: List[dict], whose: str) -> int:
     """The step count of Adam ``states`` (one dictionary per parameter, empty before the first step) that must agree on it."""
     if not any(states):
@@ -426,13 +449,23 @@ class PopulationTrainer:
     Every call then goes through the ``*_nets`` entry points, which read one settings entry per net; agents with equal settings
     get the bits of ``per_net=False``.  ``reload_settings()`` reads the agents' settings again, e.g. after a schedule or an
     exploit/explore step changed ``optimizer.param_groups[0]["lr"]``.  ``copy_nets(src)`` is that step's exploit half: net k
-    becomes a faithful clone of net ``src[k]`` (``alphazero_gym_amd.pbt.PopulationBasedTraining`` drives the whole step)."""
+    becomes a faithful clone of net ``src[k]`` (``alphazero_gym_amd.pbt.PopulationBasedTraining`` drives the whole step).
+
+    ``ema`` (None: off, every call launches what it always did): a decay in [0, 1), a list of K decays, or ``{"decay": ..., "every":
+    N}`` keeps ``self.ema`` [K, P], a slowly moving copy of ``flat`` (include/azgym_train_ema.h): a copy of it to begin with, and after
+    every N-th optimiser step -- of ``update`` with either ``losses``, and of every minibatch inside ``train_epoch``,
+    ``train_epoch_ring`` and ``train_online_ring`` -- ``ema += (1 - decay_k) * (flat - ema)`` in float32, one more launch behind the
+    step's, no synchronisation.  The count of steps carries over from call to call.  ``ema_decay`` / ``ema_every`` are the settings in
+    force (``ema_decay`` None: detached), ``ema_updates`` the times it moved; ``set_ema`` re-attaches with other settings or detaches,
+    ``reset_ema(nets)`` copies rows of ``flat`` again, ``copy_nets`` clones the row (with a list of decays also the decay) and
+    ``close()`` detaches.  Hand it to the search as its target set: ``PopulationSelfPlay.upload_target_flat(trainer.desc, trainer.ema)``."""
 
     def __init__(self, agents: Sequence[Any], max_batch: int = 512, keep_grads: bool = False, losses: str = "torch",
                  optimizers: str = "rmsprop", layernorm: bool = False, wide: bool = False, wide_layernorm: bool = False,
-                 per_net: bool = False):
+                 per_net: bool = False, ema=None):
         # 1. checks that touch nothing: the arguments, then the agents
         self.agents = list(agents)
+        ema_settings = None if ema is None else _ema_settings(ema, len(self.agents))
         self.per_net, self.losses, self.optimizers = bool(per_net), losses, optimizers
         self.layernorm, self.wide, self.wide_layernorm = bool(layernorm), bool(wide), bool(wide_layernorm)
         c = _check(self.agents, losses, optimizers, self.per_net, self.layernorm, self.wide, self.wide_layernorm)
@@ -465,6 +498,54 @@ class PopulationTrainer:
         # 4. the per-net arrays
         if self.per_net:
             self._set_net_entries(c.settings, c.clips, c.net_cfgs)
+        # 5. the moving average of the parameters, a copy of them to begin with
+        self.ema: Optional[torch.Tensor] = None
+        self.ema_decay, self.ema_every = None, 1
+        if ema_settings is not None:
+            self.ema = self.flat.clone()
+            self._attach_ema(*ema_settings)
+
+    def _attach_ema(self, decay, every: int) -> None:
+        """azg_trainer_set_ema over ``self.ema`` with checked settings (``_ema_settings``); the native step count starts again."""
+        torch.cuda.current_stream(self.device).synchronize()   # (the copies that filled ``ema`` are complete)
+        self.trainer.set_ema(self.ema.data_ptr(), decay, every)
+        self.ema_decay, self.ema_every = decay, every
+
+    @property
+    def ema_updates(self) -> int:
+        """How often the average has moved since it was last attached (the constructor, ``set_ema``, ``copy_nets`` with a list of
+        decays): one launch per ``every`` optimiser steps.  0 without an average."""
+        return self.trainer.ema_info()[1] if self.ema is not None and self.ema_decay is not None else 0
+
+    def set_ema(self, decay=None, every: Optional[int] = None) -> None:
+        """Re-attach the average with new settings (None: the one in force); ``set_ema(None)`` with nothing else detaches it: the
+        steps after it leave ``ema`` as it stands (the tensor stays readable).  A trainer built without ``ema=`` has no average to
+        re-attach: ``ValueError``."""
+        if self.ema is None:
+            raise ValueError("PopulationTrainer.set_ema needs a trainer built with ema=...")
+        if decay is None and every is None:
+            self.trainer.set_ema(None)
+            self.ema_decay = None
+            return
+        if decay is None and self.ema_decay is None:
+            raise ValueError("PopulationTrainer.set_ema: the average is detached: give a decay")
+        self._attach_ema(*_ema_settings({"decay": self.ema_decay if decay is None else decay,
+                                         "every": self.ema_every if every is None else every}, len(self.agents)))
+
+    def reset_ema(self, nets=None) -> None:
+        """Copy the rows ``nets`` (None: all) of ``flat`` into ``ema`` again: those nets' averages start afresh from where the nets
+        stand.  Row copies on the current stream; the step count and the settings stay."""
+        if self.ema is None:
+            raise ValueError("PopulationTrainer.reset_ema needs a trainer built with ema=...")
+        with torch.no_grad():
+            if nets is None:
+                self.ema.copy_(self.flat)
+                return
+            rows = [int(k) for k in nets]
+            if any(not 0 <= k < len(self.agents) for k in rows):
+                raise ValueError(f"PopulationTrainer.reset_ema: nets must be in 0 .. {len(self.agents) - 1}")
+            idx = torch.as_tensor(rows, dtype=torch.int64, device=self.device)
+            self.ema[idx] = self.flat[idx]
 
     def _bind_moments(self, adam: bool) -> None:
         """The optimiser's moments as [K, P] tensors of the trainer (``square_avg``, or Adam's ``exp_avg`` and ``exp_avg_sq``), every
@@ -657,7 +738,7 @@ class PopulationTrainer:
             return
         to = torch.as_tensor(replaced, dtype=torch.int64, device=self.device)
         frm = torch.as_tensor([int(src[k]) for k in replaced], dtype=torch.int64, device=self.device)
-        tables = [self.flat, self.square_avg, self.exp_avg, self.exp_avg_sq, self.alpha_exp_avg, self.alpha_exp_avg_sq]
+        tables = [self.flat, self.square_avg, self.exp_avg, self.exp_avg_sq, self.alpha_exp_avg, self.alpha_exp_avg_sq, self.ema]
         if self.log_alpha is not None:
             tables.append(self.log_alpha.data)
         if self.alpha_optimizer is not None:
@@ -667,6 +748,8 @@ class PopulationTrainer:
             for t in tables:
                 if t is not None:
                     t[to] = t[frm]   # (sources are never replaced: the gather is complete before the scatter writes)
+        if isinstance(self.ema_decay, list):   # (a clone averages at its source's pace; the native step count starts again)
+            self._attach_ema([self.ema_decay[int(s)] for s in src], self.ema_every)
         if not self.per_net:
             return
         for k in replaced:
@@ -888,4 +971,7 @@ class PopulationTrainer:
         ``square_avg`` (or ``exp_avg`` / ``exp_avg_sq``)."""
         if self.trainer._h:
             self.export_alpha()
+            if self.ema is not None and self.ema_decay is not None:   # (the tensor outlives the native trainer's pointer to it)
+                self.trainer.set_ema(None)
+                self.ema_decay = None
         self.trainer.close()

@@ -9,6 +9,8 @@
 // launch_loss and launch_backward are the only places that choose between the forms and between train.cuh's kernels (plain,
 // LayerNorm) and dispatch_train_wide.hip's launches; a step is an epoch's minibatch body with one minibatch.  The online epoch
 // (include/azgym_train_online.h) is an errors epoch whose gather is the engine's refresh, draw and gather (online_ring.h).
+// An attached moving average of the parameters (include/azgym_train_ema.h, train_ema.cuh) follows launch_backward, the one place every
+// optimiser step leaves through.
 #include <cmath>
 #include <cstdint>
 #include <memory>
@@ -19,9 +21,11 @@
 #include "../../include/azgym_train_weighted.h"
 #include "../../include/azgym_train_errors.h"
 #include "../../include/azgym_train_online.h"
+#include "../../include/azgym_train_ema.h"
 #include "hip_host.h"
 #include "online_ring.h"
 #include "train.cuh"
+#include "train_ema.cuh"
 #include "train_wide_host.h"
 
 struct azg_trainer {
@@ -52,6 +56,12 @@ struct azg_trainer {
     // part the call has no entries for is empty), filled on the host for the whole call and uploaded in one copy; grown on demand
     std::vector<unsigned char> nets_host;
     DeviceBuffer nets_dev;
+    // azg_trainer_set_ema: the caller's average [n_nets][P] (NULL: none attached), the device table om[n_nets] = 1 - decay (allocated
+    // by the first attach), and the optimiser steps and kernel launches since the attach
+    float* ema = nullptr;
+    float* ema_om = nullptr;
+    int ema_every = 1;
+    int64_t ema_steps = 0, ema_updates = 0;
     hipStream_t stream = nullptr;
     std::string err;
 };
@@ -545,6 +555,20 @@ static void launch_loss(azg_trainer* t, const TrainPlan& plan, int m, const floa
     }
 }
 
+// The attached average after one more optimiser step: its kernel on the trainer's stream when the step's number is a multiple of `every`
+static void launch_ema(azg_trainer* t, const float* params) {
+    if (++t->ema_steps % t->ema_every) return;
+    const unsigned P = (unsigned)t->net.P;
+    const size_t N = (size_t)t->n_nets * P;
+    const bool aligned = (((uintptr_t)params | (uintptr_t)t->ema) & 15) == 0 && P >= 4;
+    const size_t n4 = aligned ? N / 4 : 0;
+    const size_t work = n4 ? n4 : N;
+    size_t blocks = (work + TR_EMA_THREADS - 1) / TR_EMA_THREADS;
+    if (blocks > TR_EMA_MAX_BLOCKS) blocks = TR_EMA_MAX_BLOCKS;
+    hipLaunchKernelGGL(train_ema_kernel, dim3((unsigned)blocks), dim3(TR_EMA_THREADS), 0, t->stream, params, t->ema, t->ema_om, P, n4, N);
+    ++t->ema_updates;
+}
+
 // minibatch m's backward pass and optimiser step, in the plan's form (a deferred form without the caller's grads keeps them in grad_buf)
 static void launch_backward(azg_trainer* t, const TrainPlan& plan, int m, float* params, const float* d_raw, float* grads) {
     const Minibatch& mb = plan.mb[m];
@@ -574,6 +598,7 @@ static void launch_backward(azg_trainer* t, const TrainPlan& plan, int m, float*
         break;
     }
     }
+    if (t->ema) launch_ema(t, params);
 }
 
 // one minibatch: forward, losses (d_raw to d_raw_buf), backward and step
@@ -995,6 +1020,48 @@ int azg_trainer_epoch_online_nets(azg_trainer* t, azg_engine* e, float* params, 
                                   const azg_loss_cfg* loss_cfgs, const azg_alpha_state* alpha_state, const azg_optim* opts,
                                   double* loss_sums) {
     return epoch_online_impl(t, "azg_trainer_epoch_online_nets", OptForm::table, e, params, cfg, loss_cfgs, alpha_state, opts, loss_sums);
+}
+
+// ---- the moving average of the parameters (include/azgym_train_ema.h)
+
+int azg_trainer_set_ema(azg_trainer* t, const azg_ema_cfg* cfg) {
+    if (!t) return AZG_E_INVALID;
+    const std::string w("azg_trainer_set_ema");
+    if (!cfg) {   // (the table stays with the handle; the stream is idle between calls)
+        t->ema = nullptr;
+        t->ema_every = 1;
+        t->ema_steps = t->ema_updates = 0;
+        return AZG_OK;
+    }
+    if (cfg->struct_size != (int32_t)sizeof(azg_ema_cfg)) return tfail(t, AZG_E_INVALID, w + ": azg_ema_cfg.struct_size mismatch");
+    if (!cfg->ema || !cfg->decay) return tfail(t, AZG_E_INVALID, w + ": NULL pointer in azg_ema_cfg");
+    if (cfg->n_decay != 1 && cfg->n_decay != t->n_nets) return tfail(t, AZG_E_INVALID, w + ": n_decay must be 1 or the trainer's n_nets");
+    if (cfg->every < 1) return tfail(t, AZG_E_INVALID, w + ": every must be at least 1");
+    std::vector<float> om((size_t)t->n_nets);
+    for (int k = 0; k < t->n_nets; ++k) {
+        const double d = cfg->decay[cfg->n_decay == 1 ? 0 : k];
+        if (!std::isfinite(d) || d < 0.0 || !(d < 1.0))
+            return tfail(t, AZG_E_INVALID, w + ": decay of net " + std::to_string(k) + " must be finite and in [0, 1)");
+        om[k] = (float)(1.0 - d);
+    }
+    DeviceScope scope(t->device_id);
+    if (!scope.ok) return tfail(t, AZG_E_DEVICE, "hipSetDevice failed");
+    if (int rc = ensure(t, t->ema_om, (size_t)t->n_nets)) return rc;
+    // (no launch of an earlier attach is in flight: every entry point ends with the stream's synchronisation)
+    hipError_t rc = hipMemcpyAsync(t->ema_om, om.data(), om.size() * sizeof(float), hipMemcpyHostToDevice, t->stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(t->stream);
+    if (rc != hipSuccess) return tfail(t, AZG_E_DEVICE, w + ": " + hipGetErrorString(rc));
+    t->ema = cfg->ema;
+    t->ema_every = cfg->every;
+    t->ema_steps = t->ema_updates = 0;
+    return AZG_OK;
+}
+
+int azg_trainer_ema_info(const azg_trainer* t, int64_t* steps_seen, int64_t* updates_made) {
+    if (!t) return AZG_E_INVALID;
+    if (steps_seen) *steps_seen = t->ema_steps;
+    if (updates_made) *updates_made = t->ema_updates;
+    return AZG_OK;
 }
 
 int azg_trainer_read_d_raw(azg_trainer* t, int32_t n_rows, float* d_raw) {

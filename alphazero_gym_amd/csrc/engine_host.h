@@ -16,6 +16,7 @@
 #include "records.h"
 #include "replay_ring.h"
 #include "../../include/azgym_population.h"
+#include "../../include/azgym_target.h"
 
 // diagnostic switches (environment variables, read once when the engine is created): force the other code paths in tests
 struct EngineOptions {
@@ -60,6 +61,16 @@ struct WeightMap {
     int HP = 0;
     std::vector<unsigned> src;   // per output float: 1 + index into the caller's blob, 0 = padding zero
     size_t oW0, oW0b, ob0, oW0u, ob0u, oWl[MAX_STREAM_LAYERS], obl[MAX_STREAM_LAYERS], oWh, obh, olg[MAX_STREAM_LAYERS], olb[MAX_STREAM_LAYERS];
+};
+
+// The weight set that is not in use (include/azgym_target.h): the engine's d_wblob, w_floats, net_have and mlp_ready of that set
+struct IdleWeights {
+    DeviceAllocs mem;
+    float* blob = nullptr;
+    size_t floats = 0;
+    std::vector<char> have;
+    int ready = 0;
+    void drop() { mem.clear(); blob = nullptr; floats = 0; have.clear(); ready = 0; }   // (its owner's device current, no reader in flight)
 };
 
 // return_results' five arrays in ONE device block (float64 parts first) with a pinned host mirror: byte offsets for B trees of at most K
@@ -133,6 +144,10 @@ struct azg_engine : EngineQueue {
     int redo_ok = 0;         // roots, carried counts and weights are still the ones the last search ran on: azg_dump_tree may re-run it
     int n_nets = 1;          // azg_set_population: the trees split into n_nets nets of n_trees / n_nets trees (1: one network)
     std::vector<char> net_have = std::vector<char>(1, 0);   // net k has weights (azg_set_net_weights); d_wblob holds n_nets blocks of w_floats
+    // include/azgym_target.h: which of the two weight sets d_wblob / w_floats / net_have / mlp_ready describe (AZG_WEIGHTS_*), and the
+    // other one, parked; both follow wmap.  Nothing is allocated for the parked set until an upload writes it while it is in use
+    int w_in_use = 0;
+    IdleWeights w_idle;
     // azg_set_net_search: per-net MCTS settings.  net_search.rec != nullptr: the engine carries a table and searches with the kernels that
     // take it.  net_search_wide: the table came with AZG_NET_SEARCH_WIDE (azg_set_net_search_ex) and may be searched at widths >= 512
     DeviceAllocs net_search_mem; NetSearchTable net_search{};

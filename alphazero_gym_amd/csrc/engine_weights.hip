@@ -244,6 +244,10 @@ static int set_weights_impl(azg_engine* e, const azg_mlp_desc* d, const float* b
     e->results_valid = 0;
     e->redo_ok = 0;
     WeightMap& m = e->wmap;
+    // the two weight sets (azgym_target.h) share the descriptor: one that differs in anything empties the set that is not in use
+    if (!m.valid || m.HP != HP || !same_desc(m.desc, *d) || d->activation != m.desc.activation || d->num_components != m.desc.num_components ||
+        d->log_std_min != m.desc.log_std_min || d->log_std_max != m.desc.log_std_max)
+        e->w_idle.drop();
     if (!m.valid || m.HP != HP || !same_desc(m.desc, *d)) {
         m.valid = false;
         build_weight_map(d, HP, m);
@@ -329,6 +333,7 @@ int azg_set_population(azg_engine* e, int32_t n_nets) {
     // every weight goes: the next search needs the weights of every net again
     e->wblob_mem.clear();
     e->d_wblob = nullptr; e->w_floats = 0;
+    e->w_idle.drop();   // (the set that is not in use, azgym_target.h, was laid out for the old split too)
     // ... and so do per-net search settings: their table has one entry per net of the old split
     e->net_search = NetSearchTable{};
     e->net_search_mem.clear();
@@ -430,6 +435,38 @@ int azg_set_net_search_ex(azg_engine* e, const azg_net_search* nets, int32_t n_n
     if (!e) return AZG_E_INVALID;
     if (flags & ~(uint32_t)AZG_NET_SEARCH_WIDE) return fail(e, AZG_E_INVALID, "azg_set_net_search_ex: unknown flag bits (AZG_NET_SEARCH_WIDE is the only flag)");
     return set_net_search(e, nets, n_nets, (flags & AZG_NET_SEARCH_WIDE) != 0);
+}
+
+// ---- the second weight set (include/azgym_target.h).  The set in use is what d_wblob / w_floats / net_have / mlp_ready describe, so
+// every upload above writes it and bind_weights points the kernels at it; selecting the other set swaps those with the parked ones.
+int azg_use_weights(azg_engine* e, int32_t which) {
+    if (!e) return AZG_E_INVALID;
+    if (which != AZG_WEIGHTS_LIVE && which != AZG_WEIGHTS_TARGET)
+        return fail(e, AZG_E_INVALID, "azg_use_weights: which must be AZG_WEIGHTS_LIVE or AZG_WEIGHTS_TARGET");
+    if (which == e->w_in_use) return AZG_OK;
+    ON_DEVICE(e);
+    { int trc = settle_team(e); if (trc) return trc; }   // an abandoned team search is redone with the weights it was started with
+    IdleWeights& o = e->w_idle;
+    if (o.have.size() != (size_t)e->n_nets) o.have.assign(e->n_nets, 0);   // (a set nothing was uploaded to since it was emptied)
+    e->wblob_mem.ptrs.swap(o.mem.ptrs);
+    std::swap(e->d_wblob, o.blob);
+    std::swap(e->w_floats, o.floats);
+    e->net_have.swap(o.have);
+    std::swap(e->mlp_ready, o.ready);
+    e->w_in_use = which;
+    // launches already made hold their weight pointers by value: no synchronisation.  What is cached about the last search goes, as
+    // after an upload
+    e->results_valid = 0;
+    e->redo_ok = 0;
+    if (e->d_wblob) bind_weights(e, e->wmap, &e->wmap.desc);
+    return AZG_OK;
+}
+
+int azg_weights_info(const azg_engine* e, int32_t* in_use, int32_t* target_ready) {
+    if (!e) return AZG_E_INVALID;
+    if (in_use) *in_use = e->w_in_use;
+    if (target_ready) *target_ready = e->w_in_use == AZG_WEIGHTS_TARGET ? e->mlp_ready : e->w_idle.ready;
+    return AZG_OK;
 }
 
 int azg_set_net_weights(azg_engine* e, int32_t net, const azg_mlp_desc* d, const float* blob, size_t n_floats) {

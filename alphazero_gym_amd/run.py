@@ -12,7 +12,9 @@ Default hyper-parameters are the reference's (config/*.yaml, SURVEY.md section 5
 one squashed-Normal component (num_components: 1) instead of the 2-component GMM.
 """
 import argparse
+import contextlib
 import copy
+import functools
 from typing import Callable, Dict, List, Optional
 
 import numpy as np
@@ -311,6 +313,22 @@ REANALYSE_INDEX_BASE = 1 << 31
 EVAL_SEARCH_INDEX_BASE = 3 << 30
 
 
+def _nets_keyword(method):
+    """Gives a ``PopulationSelfPlay`` method the keyword ``nets``: "live" (the default) is the call as it always was; "target" runs it
+    with the engine's TARGET weight set (``upload_target_flat``).  The method keeps its own parameters and signature; where it applies
+    pending weight uploads it enters ``self._with_nets(...)``, which reads what was asked for here."""
+    @functools.wraps(method)
+    def call(self, *args, nets: str = "live", **kw):
+        if nets not in ("live", "target"):
+            raise ValueError(f"{method.__name__}: nets must be 'live' or 'target', not {nets!r}")
+        self._nets = nets
+        try:
+            return method(self, *args, **kw)
+        finally:
+            self._nets = "live"
+    return call
+
+
 class PopulationSelfPlay:
     """Self-play with everything but the optimiser on the GPU (azg_selfplay_* in include/azgym.h), for K policies in ONE engine:
     games, final action rule, env step, episode resets and the replay ring live on the device; the host only downloads rows to
@@ -466,6 +484,24 @@ class PopulationSelfPlay:
         """``PopulationMCTS.upload_flat``: the hand-off of parameters trained in place by ``PopulationTrainer``."""
         self.mcts.upload_flat(desc, flat)
 
+    def upload_target_flat(self, desc, flat) -> None:
+        """``PopulationMCTS.upload_target_flat``: the engine's TARGET weight set from a ``[K, P]`` tensor such as
+        ``PopulationTrainer.ema``; the games go on with the live weights.  ``reanalyse``, ``evaluate`` and ``evaluate_search`` take
+        ``nets="target"`` to run with it."""
+        self.mcts.upload_target_flat(desc, flat)
+
+    _nets = "live"   # what the call in progress was asked to run with (_nets_keyword)
+
+    def _with_nets(self, who: str):
+        """The context the network launches of a ``_nets_keyword`` method run under, pending live uploads applied first: nothing for
+        "live" (the path as it always was), ``mcts.target_weights()`` for "target"."""
+        self.sync_weights()
+        if self._nets == "live":
+            return contextlib.nullcontext()
+        if not self.engine.weights_info()["target_ready"]:
+            raise RuntimeError(f"{type(self).__name__}.{who}(nets='target'): no target weights yet: upload_target_flat(desc, flat) first")
+        return self.mcts.target_weights()
+
     def copy_nets(self, src, reset_errors: bool = True, explored: Optional[Dict[int, dict]] = None) -> None:
         """The engine side of population-based training's exploit step (``alphazero_gym_amd.pbt``): net k's settings become those of
         net ``src[k]`` -- its entry in ``mcts.net_settings``, in ``mcts.net_rollouts`` and in the per-net ``n_step``, ``td_lambda``
@@ -610,6 +646,7 @@ class PopulationSelfPlay:
             raise ValueError(f"{type(self).__name__}.is_weights: beta must be finite and >= 0")
         self.engine.selfplay_is_weights(float(beta))
 
+    @_nets_keyword
     def reanalyse(self, slots=None, n: int = 1, rng: Optional[np.random.Generator] = None, by: str = "uniform") -> list:
         """MuZero's Reanalyse on the device ring: search stored positions again with the CURRENT weights (pending uploads are
         applied first, as ``play`` does) and overwrite their rows' actions | counts | Q | V_target; observations, the live games
@@ -620,12 +657,20 @@ class PopulationSelfPlay:
         ``REANALYSE_INDEX_BASE``.  Returns the slots used (the per-game array: a one-element list holding it).
         ``by="priority"`` (with ``prioritized`` and ``slots`` None): one search in which game t re-searches the slot drawn for it
         on the device in proportion to the priorities of its column (recomputed first); the draws take the next index of a second
-        counter that starts at 0.  ``by="uniform"`` is the rest of this description."""
+        counter that starts at 0.  ``by="uniform"`` is the rest of this description.
+        ``nets="target"``: the searches run with the engine's TARGET weight set (``upload_target_flat``; MuZero's target network)
+        instead of the live weights, which are in use again when the call returns; "live" is the call as it always was."""
         if by not in ("uniform", "priority"):
             raise ValueError(f"reanalyse: by must be 'uniform' or 'priority', not {by!r}")
         if not self.reanalysing:
             raise RuntimeError(f"{type(self).__name__}.reanalyse needs the stored positions' env states: create it with reanalyse=True")
-        self.sync_weights()
+        with self._with_nets("reanalyse"):
+            used = self._reanalyse_searches(slots, n, rng, by)
+        self._value_targets()   # (the reanalysed rows hold plain search values again: back to the returns, from the fresh values)
+        return used
+
+    def _reanalyse_searches(self, slots, n: int, rng, by: str) -> list:
+        """``reanalyse``'s choice of slots and its searches, with the weight set in use; the slots used."""
         if by == "priority":
             if slots is not None:
                 raise ValueError("reanalyse: by='priority' draws the slots itself")
@@ -643,7 +688,6 @@ class PopulationSelfPlay:
         for s in used:
             self.engine.selfplay_reanalyse(s, search_index=self._reanalyse_index)
             self._reanalyse_index += 1
-        self._value_targets()   # (the reanalysed rows hold plain search values again: back to the returns, from the fresh values)
         return used
 
     def play_device(self, n_steps: int):
@@ -706,6 +750,7 @@ class PopulationSelfPlay:
             c += fcnt[:, j]
         return s, c
 
+    @_nets_keyword
     def evaluate(self, episodes_per_net: int, rule: str = "mode", max_episode_length: Optional[int] = None, episode: int = 0,
                  game_id_base: Optional[int] = None) -> Dict[str, np.ndarray]:
         """How good each net is by itself: ``episodes_per_net`` whole episodes per net played by the raw policy, no search, on the
@@ -715,7 +760,8 @@ class PopulationSelfPlay:
         ``max_episode_length`` None: the self-play's own limit; ``game_id_base`` None: ``EVAL_GAME_ID_BASE``, or the first id
         above this engine's self-play games where those reach it.  Pending weight uploads are applied first, as ``play`` does;
         self-play, searches and their results are left untouched.  Returns [n_nets, episodes_per_net] arrays "returns",
-        "lengths", "terminated", "first_value" (the value head at the start state) and "mean_return" [n_nets]."""
+        "lengths", "terminated", "first_value" (the value head at the start state) and "mean_return" [n_nets].
+        ``nets="target"``: the engine's TARGET weight set (``upload_target_flat``) plays instead of the live weights."""
         if rule not in _capi.ROLLOUT_RULE:
             raise ValueError(f"evaluate: rule must be one of {sorted(_capi.ROLLOUT_RULE)}, not {rule!r}")
         if int(episodes_per_net) < 1:
@@ -726,12 +772,13 @@ class PopulationSelfPlay:
             raise ValueError("evaluate: max_episode_length must be >= 1")
         if game_id_base is None:
             game_id_base = max(EVAL_GAME_ID_BASE, self.tree_id_base + self.n_games)
-        self.sync_weights()
-        out = self.engine.policy_rollout(int(episodes_per_net), int(max_episode_length), rule=rule, game_id_base=int(game_id_base),
-                                         episode=int(episode))
+        with self._with_nets("evaluate"):
+            out = self.engine.policy_rollout(int(episodes_per_net), int(max_episode_length), rule=rule, game_id_base=int(game_id_base),
+                                             episode=int(episode))
         out["mean_return"] = out["returns"].mean(axis=1)
         return out
 
+    @_nets_keyword
     def evaluate_search(self, episodes_per_game: int = 1, final_selection: str = "max_visit", deterministic: bool = True,
                         temperature: float = 1.0, agent_epsilon: float = 0.0, max_episode_length: Optional[int] = None, episode: int = 0,
                         game_id_base: Optional[int] = None, index_base: int = EVAL_SEARCH_INDEX_BASE,
@@ -745,7 +792,8 @@ class PopulationSelfPlay:
         ``max_episode_length`` None: the self-play's own limit; ``game_id_base`` None: as ``evaluate``.  Pending weight uploads are
         applied first, as ``play`` does; the self-play's games, ring and search index are left untouched.  Returns
         [n_nets, games_per_net, episodes_per_game] arrays "returns", "lengths", "terminated", plus "mean_return" [n_nets] and
-        "steps" (the searches run)."""
+        "steps" (the searches run).  ``nets="target"``: the engine's TARGET weight set (``upload_target_flat``) searches and acts
+        instead of the live weights."""
         if final_selection not in _capi.FINAL_SELECTION:
             raise ValueError(f"evaluate_search: final_selection must be one of {sorted(_capi.FINAL_SELECTION)}, not {final_selection!r}")
         if int(episodes_per_game) < 1:
@@ -764,11 +812,11 @@ class PopulationSelfPlay:
             raise ValueError("evaluate_search: index_base and episode must fit 32 bits")
         if game_id_base is None:
             game_id_base = max(EVAL_GAME_ID_BASE, self.tree_id_base + self.n_games)
-        self.sync_weights()
-        out = self.engine.search_rollout(int(episodes_per_game), int(max_episode_length), final_selection=final_selection,
-                                         deterministic=bool(deterministic), temperature=float(temperature),
-                                         agent_epsilon=float(agent_epsilon), game_id_base=int(game_id_base), episode=int(episode),
-                                         index_base=int(index_base), poll_steps=int(poll_steps))
+        with self._with_nets("evaluate_search"):
+            out = self.engine.search_rollout(int(episodes_per_game), int(max_episode_length), final_selection=final_selection,
+                                             deterministic=bool(deterministic), temperature=float(temperature),
+                                             agent_epsilon=float(agent_epsilon), game_id_base=int(game_id_base), episode=int(episode),
+                                             index_base=int(index_base), poll_steps=int(poll_steps))
         shape = (self.n_nets, self.games_per_net, int(episodes_per_game))
         res = {k: out[k].reshape(shape) for k in ("returns", "lengths", "terminated")}
         res["mean_return"] = res["returns"].reshape(self.n_nets, -1).mean(axis=1)

@@ -9,6 +9,7 @@ weights the engine evaluates on the GPU.  One ``search`` call is ONE kernel laun
 for the two classes above).  ``PopulationMCTS`` searches the trees of K models, each with its own weights, in one launch.
 There is no CPU fallback; constructing an engine without the HIP library or a GPU raises.
 """
+import contextlib
 import warnings
 from typing import Any, List, Optional, Sequence, Tuple
 
@@ -125,6 +126,7 @@ class PopulationMCTS:
         if self.n_models > 1:   # (one model: the plain engine, which the tests' CPU oracle -- no population entry points -- also is)
             self.engine.set_population(self.n_models)
         self._versions: List[Any] = [None] * self.n_models
+        self._in_target = False   # inside target_weights(): the engine's TARGET weight set is in use
         self._cliff_warned = False
         self.last_weight_sync: Optional[str] = None
         if net_settings is not None or rollouts is not None:
@@ -215,6 +217,8 @@ class PopulationMCTS:
         """Upload the weights of every model that changed since its last upload (net k = models[k]; after every optimiser step).
         ``last_weight_sync`` says how: "device" when every parameter lives on the engine's GPU (flattened there; K > 1: one gather
         launch for all nets), "host" (K > 1: one host upload per changed net), None when nothing changed."""
+        if self._in_target:   # (the models are the live set's: inside ``target_weights()`` nothing of theirs is written)
+            return
         versions = [_weights_version(m) for m in self.models]
         changed = [k for k in range(self.n_models) if force or versions[k] != self._versions[k]]
         self.last_weight_sync = None
@@ -241,12 +245,51 @@ class PopulationMCTS:
         if not flat.is_cuda or flat.device.index != self.engine.cfg.device_id:
             raise ValueError("upload_flat: flat must live on the engine's GPU")
         torch.cuda.current_stream(flat.device).synchronize()
+        self._set_flat(desc, flat)
+        self._versions = [_weights_version(m) for m in self.models]
+        self.last_weight_sync = "device"
+
+    def _set_flat(self, desc, flat) -> None:
+        """One gather launch from ``flat`` [n_models, P] (checked, complete) into the weight set in use."""
         if self.n_models == 1:
             self.engine.set_weights_device(desc, flat.data_ptr(), flat.shape[1])
         else:
             self.engine.set_population_weights_device(desc, flat.data_ptr(), flat.shape[1], self.n_models)
-        self._versions = [_weights_version(m) for m in self.models]
-        self.last_weight_sync = "device"
+
+    def upload_target_flat(self, desc, flat) -> None:
+        """Upload every net of the engine's TARGET weight set (include/azgym_target.h) from ``flat`` [n_models, P] -- a
+        ``PopulationTrainer``'s ``ema``, say -- with ``upload_flat``'s checks and its one gather launch; the live weights, which the
+        games are played with, are not touched and are in use again when this returns.  ``target_weights()`` then runs anything with
+        the target set.  A ``desc`` that differs from the live set's empties the live set (the sets share one descriptor)."""
+        import torch
+        if tuple(flat.shape[:1]) != (self.n_models,) or flat.dim() != 2 or not flat.is_contiguous() or flat.dtype != torch.float32:
+            raise ValueError("upload_target_flat: flat must be a contiguous float32 [n_models, P] tensor")
+        if not flat.is_cuda or flat.device.index != self.engine.cfg.device_id:
+            raise ValueError("upload_target_flat: flat must live on the engine's GPU")
+        torch.cuda.current_stream(flat.device).synchronize()
+        self.engine.use_weights("target")
+        try:
+            self._set_flat(desc, flat)
+        finally:
+            self.engine.use_weights("live")
+
+    @contextlib.contextmanager
+    def target_weights(self):
+        """Everything inside runs with the engine's TARGET weight set (``upload_target_flat`` first: ``RuntimeError`` otherwise);
+        LIVE is in use again on exit, exceptions included.  Pending uploads of the models' own (live) weights are not applied
+        inside -- ``sync_weights()`` does nothing there -- so apply them before."""
+        if self._in_target:
+            raise RuntimeError("target_weights: already inside target_weights()")
+        if not self.engine.weights_info()["target_ready"]:
+            raise RuntimeError("target_weights: the engine has no target weights: upload_target_flat(desc, flat) first (an upload of "
+                               "another network descriptor empties them)")
+        self.engine.use_weights("target")
+        self._in_target = True
+        try:
+            yield self
+        finally:
+            self._in_target = False
+            self.engine.use_weights("live")
 
     def search(self, root_states: np.ndarray, root_n_carry: Optional[np.ndarray] = None) -> None:
         """root_states [n_trees, S] (or [n_models, trees_per_model, S]); tree k*T + j belongs to models[k]."""

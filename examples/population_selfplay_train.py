@@ -60,6 +60,12 @@ table from iteration 0, filled with the shared values; n_step / td_lambda / targ
 
     python examples/population_selfplay_train.py --game CartPole-v0 --seeds 0 1 2 3 4 5 6 7 --games-per-seed 64 --iters 30
 
+--ema-decay D keeps a slowly moving copy of every net on the device (PopulationTrainer ema=D: after every --ema-every-th optimiser
+step, one more launch behind it, ema += (1 - D) (weights - ema)); it needs a device trainer.  --reanalyse-target and --eval-target
+hand that copy to the engine as its second, target weight set after each training phase (PopulationSelfPlay.upload_target_flat) and
+run --reanalyse-slots' searches (MuZero's target network), respectively --eval-episodes' and --eval-search-episodes' evaluations,
+with it (nets="target"), while the games go on with the weights as last trained.
+
 Seed k sets net k's initial weights (torch.manual_seed), and its own np.random.RandomState picks the training rows and the
 minibatch shuffles.  Prints one JSON line per iteration: per-seed mean return of the episodes finished in it and mean loss, and
 the time spent in self-play, training and weight sync.  --eval-episodes N adds eval_return: each seed's raw policy (no search) over
@@ -171,6 +177,16 @@ def parse_args(argv=None):
                     help="prioritised replay as published: one native call per iteration (train_online_ring) trains "
                          "ceil(train-rows / batch-size) minibatches, each drawn from priorities refreshed with the errors of the "
                          "minibatches before it; needs --prioritized-feedback (default: off, one draw per iteration)")
+    ap.add_argument("--ema-decay", type=float, default=None,
+                    help="keep an exponential moving average of every net's weights on the device, updated behind the optimiser steps "
+                         "(PopulationTrainer ema=D, D in [0, 1)); needs a --trainer other than torch (default: off)")
+    ap.add_argument("--ema-every", type=int, default=1, help="with --ema-decay: the average moves after every N-th optimiser step")
+    ap.add_argument("--reanalyse-target", action="store_true",
+                    help="--reanalyse-slots' searches run with the averaged weights, the engine's target set, instead of the weights as "
+                         "last trained; needs --ema-decay and --reanalyse-slots")
+    ap.add_argument("--eval-target", action="store_true",
+                    help="--eval-episodes / --eval-search-episodes score the averaged weights, the engine's target set; needs "
+                         "--ema-decay and one of the two")
     ap.add_argument("--pbt-every", type=int, default=0,
                     help="population-based training: after every N-th iteration the worst seeds copy the best ones and perturb what "
                          "--pbt-explore names (0: off, the run is a plain sweep); needs a --trainer other than torch and two seeds or more")
@@ -184,7 +200,7 @@ def parse_args(argv=None):
                          "none takes the lowest score); eval, --eval-episodes' eval_return; eval-search, --eval-search-episodes' "
                          "eval_search_return")
     a = ap.parse_args(argv)
-    why = check_replay(a) or check_pbt(a)
+    why = check_replay(a) or check_pbt(a) or check_ema(a)
     if why:
         ap.error(why)
     if a.eval_search_episodes < 0:
@@ -323,6 +339,27 @@ def check_pbt(a):
         return "--pbt-score eval ranks the seeds by eval_return: it needs --eval-episodes N"
     if a.pbt_score == "eval-search" and a.eval_search_episodes <= 0:
         return "--pbt-score eval-search ranks the seeds by eval_search_return: it needs --eval-search-episodes E"
+    return None
+
+
+def check_ema(a):
+    """Why the --ema-* / --*-target flags cannot be honoured as given (None: they can)."""
+    decay, every = getattr(a, "ema_decay", None), getattr(a, "ema_every", 1)
+    if decay is None:
+        for flag, on in (("--ema-every", every != 1), ("--reanalyse-target", getattr(a, "reanalyse_target", False)),
+                         ("--eval-target", getattr(a, "eval_target", False))):
+            if on:
+                return f"{flag} is about the averaged weights: it needs --ema-decay D"
+        return None
+    if not (np.isfinite(decay) and 0.0 <= decay < 1.0) or every < 1:
+        return "--ema-decay must lie in [0, 1) and --ema-every be >= 1"
+    if a.trainer == "torch":
+        return ("--ema-decay: the average is kept by the population trainer behind its optimiser steps: use --trainer device, "
+                "device-fused or device-epoch")
+    if getattr(a, "reanalyse_target", False) and not a.reanalyse_slots:
+        return "--reanalyse-target chooses the weights of --reanalyse-slots' searches: it needs --reanalyse-slots N"
+    if getattr(a, "eval_target", False) and a.eval_episodes <= 0 and getattr(a, "eval_search_episodes", 0) <= 0:
+        return "--eval-target chooses the weights of the evaluations: it needs --eval-episodes N or --eval-search-episodes E"
     return None
 
 
@@ -465,18 +502,30 @@ def train(a, log=print, on_rows=None, on_end=None):
                                     optimizers="agents" if (a.optimizer != "rmsprop" or a.grad_clip or per_net) else "rmsprop",
                                     per_net=per_net,
                                     layernorm=a.layernorm and not a.wide, wide=a.wide and not a.layernorm,
-                                    wide_layernorm=a.wide and a.layernorm)
+                                    wide_layernorm=a.wide and a.layernorm,
+                                    **({"ema": {"decay": a.ema_decay, "every": getattr(a, "ema_every", 1)}}
+                                       if getattr(a, "ema_decay", None) is not None else {}))
     replay_steps, reanalyse_slots = getattr(a, "replay_steps", 0), getattr(a, "reanalyse_slots", 0)
     by_priority = sp.prioritized is not None
     weighted = by_priority and "beta" in sp.prioritized
     feedback = by_priority and "feedback" in sp.prioritized
 
+    # the averaged weights as the engine's target set: what --reanalyse-target's searches and --eval-target's evaluations run with
+    reanalyse_nets = {"nets": "target"} if getattr(a, "reanalyse_target", False) else {}
+    eval_nets = {"nets": "target"} if getattr(a, "eval_target", False) else {}
+
+    def upload_target():
+        if reanalyse_nets or eval_nets:
+            sp.upload_target_flat(trainer.desc, trainer.ema)
+
+    upload_target()   # (the average starts as a copy of the weights)
+
     def reanalyse():
         if by_priority:   # one search per "slot": every game re-searches the position drawn for it
             for _ in range(reanalyse_slots):
-                sp.reanalyse(by="priority")
+                sp.reanalyse(by="priority", **reanalyse_nets)
         else:
-            sp.reanalyse(n=reanalyse_slots)
+            sp.reanalyse(n=reanalyse_slots, **reanalyse_nets)
 
     def pick_rows(k, rng, n):
         """Net k's training rows of this iteration: the device's prioritised draw, else the seed's own uniform pick."""
@@ -565,6 +614,7 @@ def train(a, log=print, on_rows=None, on_end=None):
             sp.sync_weights()
         else:
             sp.upload_flat(trainer.desc, trainer.flat)
+            upload_target()
         t4 = time.time()
         fs, fc = sp.finished_returns()
         mean_ret = (fs - fs0) / np.maximum(fc - fc0, 1)
@@ -574,11 +624,11 @@ def train(a, log=print, on_rows=None, on_end=None):
                         "weight_sync": sp.last_weight_sync,
                         "env_steps": (it + 1) * a.steps_per_iter * sp.n_games, "elapsed_s": round(time.time() - t0, 2)})
         if a.eval_episodes > 0:   # the nets as just trained and uploaded, each by itself, over the same start states
-            ev = sp.evaluate(a.eval_episodes, rule=a.eval_rule)
+            ev = sp.evaluate(a.eval_episodes, rule=a.eval_rule, **eval_nets)
             history[-1]["eval_return"] = [round(float(x), 2) for x in ev["mean_return"]]
             ev_raw = ev
         if getattr(a, "eval_search_episodes", 0) > 0:   # the same nets acting with their search, over those same start states
-            ev = sp.evaluate_search(a.eval_search_episodes)
+            ev = sp.evaluate_search(a.eval_search_episodes, **eval_nets)
             history[-1]["eval_search_return"] = [round(float(x), 2) for x in ev["mean_return"]]
             ev_search = ev
         if pbt is not None and (it + 1) % pbt_every == 0:   # exploit / explore on the nets as just trained, then uploaded again
@@ -593,6 +643,7 @@ def train(a, log=print, on_rows=None, on_end=None):
             rec = pbt.step(scores)
             history[-1]["pbt"] = {"src": rec["src"], "scores": [round(float(x), 4) for x in scores],
                                   "explored": {str(k): v for k, v in rec["explored"].items()}}
+            upload_target()   # (a replaced seed's average is its source's)
         if log:
             log(json.dumps(history[-1]), flush=True)
         fs0, fc0 = fs, fc

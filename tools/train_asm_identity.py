@@ -21,7 +21,7 @@ import sys
 def functions(path):
     out, cur = {}, None
     for line in open(path):
-        m = re.match(r"^(_Z\w+):", line)
+        m = re.match(r"^([A-Za-z_]\w*):", line)   # (mangled names, and the extern "C" kernels' plain ones)
         if m:
             cur = m.group(1)
             out[cur] = []
