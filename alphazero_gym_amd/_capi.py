@@ -220,7 +220,7 @@ OPTIONAL_SYMBOLS = ["set_population", "set_net_weights", "set_net_weights_device
                     "trainer_epoch_opt_weighted", "trainer_epoch_nets_weighted",
                     "trainer_loss_errors", "trainer_loss_nets_errors", "trainer_epoch_opt_errors", "trainer_epoch_nets_errors",
                     "trainer_epoch_online", "trainer_epoch_online_nets",
-                    "trainer_set_ema", "trainer_ema_info", "use_weights", "weights_info"]
+                    "trainer_set_ema", "trainer_ema_info", "use_weights", "weights_info", "selfplay_refresh_values"]
 
 
 class AzgNetSearch(C.Structure):
@@ -385,6 +385,8 @@ def bind(lib, prefix):
         f["selfplay_transitions"].argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                               C.c_size_t]
         f["selfplay_nstep_targets"].argtypes = [vp, C.POINTER(AzgNstepConfig)]
+    if "selfplay_refresh_values" in f:   # include/azgym_refresh.h
+        f["selfplay_refresh_values"].argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
     if "selfplay_lambda_targets" in f:   # include/azgym_lambda.h
         f["selfplay_lambda_targets"].argtypes = [vp, C.POINTER(AzgReturnRule)]
         f["selfplay_lambda_targets_nets"].argtypes = [vp, C.POINTER(AzgReturnRule)]
@@ -1088,6 +1090,19 @@ def _selfplay_methods():
         c.flags = NSTEP_SEARCH_GAMMA if gamma is None else 0
         self._check(self._optional("selfplay_nstep_targets")(self._h, C.byref(c)))
 
+    def selfplay_refresh_values(self, slots=None):
+        """azg_selfplay_refresh_values (include/azgym_refresh.h): overwrite the kept float64 value of every row of the ring slots
+        ``slots`` (an iterable of ints; None: every stored slot) with the value head's output for the row's stored observation --
+        net k's weights of the weight set in use on net k's rows, mlp_eval's float32 value widened (asynchronous: one small copy
+        and one launch).  Nothing else is written: selfplay_nstep_targets / selfplay_lambda_targets turn the values into targets."""
+        fn = self._optional("selfplay_refresh_values")
+        if slots is None:
+            self._check(fn(self._h, None, 0))
+            return
+        arr = np.ascontiguousarray([int(s) for s in slots], dtype=np.int32).reshape(-1)
+        buf = arr if arr.size else np.zeros(1, np.int32)   # (an empty list is a list: never the NULL that means every slot)
+        self._check(fn(self._h, _ptr(buf, C.c_int32), arr.shape[0]))
+
     def selfplay_lambda_targets(self, n_step, td_lambda, gamma=None):
         """azg_selfplay_lambda_targets / _nets: rewrite every stored row's V_target column as the lambda-return of its game column
         from the kept transitions -- selfplay_nstep_targets' window of ``n_step`` steps, inside which the returns of the windows 1 ..
@@ -1219,7 +1234,7 @@ def _selfplay_methods():
 
     for fn in (selfplay_begin, population_selfplay_begin, selfplay_ring, selfplay_rows_device, selfplay_step, selfplay_rows, selfplay_clear, selfplay_stats,
                selfplay_keep_states, selfplay_states, selfplay_reanalyse, selfplay_keep_transitions, selfplay_transitions,
-               selfplay_nstep_targets, selfplay_lambda_targets, selfplay_keep_priorities, selfplay_priorities, selfplay_priority_values, selfplay_sample_rows,
+               selfplay_nstep_targets, selfplay_refresh_values, selfplay_lambda_targets, selfplay_keep_priorities, selfplay_priorities, selfplay_priority_values, selfplay_sample_rows,
                selfplay_sample_slots, selfplay_is_weights, selfplay_is_weights_device, selfplay_is_weight_values):
         setattr(Engine, fn.__name__, fn)
 

@@ -36,6 +36,11 @@ struct ReplayRingState {
         int on = 0;
         double* reward = nullptr; double* value = nullptr; float* action = nullptr; int* end = nullptr;
     } tr;
+    struct ValueRefresh {            // (azgym_refresh.h) the slot list of the last azg_selfplay_refresh_values call: d [cap] on the
+        int* d = nullptr;            // device (grow-only within a begin) and its host side, which the call's asynchronous copy reads
+        size_t cap = 0;              // (ReplayRing::slots_copied tells when it may be rewritten)
+        std::vector<int32_t> h;
+    } refresh;
     struct ReturnRules {             // (azgym_lambda.h) the rule table of the last lambda-target call: d [n] on the device, allocated by
         ReturnRuleRec* d = nullptr;  // the first call, and its host side, which the call's asynchronous copy reads (ReplayRing::
         int n = 0;                   // rules_copied tells when it may be rewritten)
@@ -67,10 +72,14 @@ struct ReplayRing : ReplayRingState {
     // recorded behind every copy of rules.h to the device (created by the first one): a later call waits for it before it rewrites
     // rules.h, so the staging outlives the copy that reads it
     hipEvent_t rules_copied = nullptr;
+    hipEvent_t slots_copied = nullptr;   // the same for refresh.h (azg_selfplay_refresh_values)
     ReplayRing() = default;
     ReplayRing(const ReplayRing&) = delete;
     ReplayRing& operator=(const ReplayRing&) = delete;
-    ~ReplayRing() { if (rules_copied) (void)hipEventDestroy(rules_copied); }
+    ~ReplayRing() {
+        if (rules_copied) (void)hipEventDestroy(rules_copied);
+        if (slots_copied) (void)hipEventDestroy(slots_copied);
+    }
     // a begin: the memory goes, and every member of the state with it (the engine's stream is idle)
     void restart() { mem.clear(); static_cast<ReplayRingState&>(*this) = {}; rows_gen += 1; }
     // ReplayBuffer.store (buffers.py:75-82): the slot this step's block of B rows goes to

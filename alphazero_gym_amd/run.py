@@ -486,8 +486,8 @@ class PopulationSelfPlay:
 
     def upload_target_flat(self, desc, flat) -> None:
         """``PopulationMCTS.upload_target_flat``: the engine's TARGET weight set from a ``[K, P]`` tensor such as
-        ``PopulationTrainer.ema``; the games go on with the live weights.  ``reanalyse``, ``evaluate`` and ``evaluate_search`` take
-        ``nets="target"`` to run with it."""
+        ``PopulationTrainer.ema``; the games go on with the live weights.  ``reanalyse``, ``refresh_values``, ``evaluate`` and ``evaluate_search``
+        take ``nets="target"`` to run with it."""
         self.mcts.upload_target_flat(desc, flat)
 
     _nets = "live"   # what the call in progress was asked to run with (_nets_keyword)
@@ -667,6 +667,25 @@ class PopulationSelfPlay:
         with self._with_nets("reanalyse"):
             used = self._reanalyse_searches(slots, n, rng, by)
         self._value_targets()   # (the reanalysed rows hold plain search values again: back to the returns, from the fresh values)
+        return used
+
+    @_nets_keyword
+    def refresh_values(self, slots=None) -> list:
+        """Refresh the bootstrap values of stored steps from the value head (``Engine.selfplay_refresh_values``,
+        include/azgym_refresh.h): the kept value of every row of the ring slots ``slots`` (an iterable of ints; None: every stored
+        slot) becomes net k's value of the row's stored observation -- one forward pass per row where ``reanalyse`` runs a whole
+        search, one launch for the population (asynchronous; pending uploads are applied first, as ``play`` does) -- and the value
+        targets asked for at creation are computed again from the fresh values.  The rows' policy targets, the live games and the
+        ring's books stay as they are.  A window that bootstraps from its own row (the newest stored step, a time-limit step,
+        ``n_step=0``) then has the net's own value as its target.  Returns the slots used.
+        ``nets="target"``: the values come from the engine's TARGET weight set (``upload_target_flat``; MuZero Reanalyse's value
+        targets), and the live weights are in use again when the call returns; "live" runs the live weights."""
+        if self.n_step is None:
+            raise RuntimeError(f"{type(self).__name__}.refresh_values needs the stored steps' kept values: create it with n_step=...")
+        used = list(range(self.engine.selfplay_ring()[0])) if slots is None else [int(s) for s in slots]
+        with self._with_nets("refresh_values"):
+            self.engine.selfplay_refresh_values(None if slots is None else used)
+        self._value_targets()
         return used
 
     def _reanalyse_searches(self, slots, n: int, rng, by: str) -> list:

@@ -66,6 +66,11 @@ hand that copy to the engine as its second, target weight set after each trainin
 run --reanalyse-slots' searches (MuZero's target network), respectively --eval-episodes' and --eval-search-episodes' evaluations,
 with it (nets="target"), while the games go on with the weights as last trained.
 
+--refresh-values-every N (with --n-step / --n-steps and --replay-steps or --trainer device-epoch) refreshes, after every N-th
+iteration's self-play, the value every stored step's n-step target bootstraps from: one forward pass of the value head per stored row,
+one launch for all seeds (PopulationSelfPlay.refresh_values), instead of the value its search left there; --refresh-target takes the
+averaged weights for it (MuZero Reanalyse's value targets; needs --ema-decay).
+
 Seed k sets net k's initial weights (torch.manual_seed), and its own np.random.RandomState picks the training rows and the
 minibatch shuffles.  Prints one JSON line per iteration: per-seed mean return of the episodes finished in it and mean loss, and
 the time spent in self-play, training and weight sync.  --eval-episodes N adds eval_return: each seed's raw policy (no search) over
@@ -148,6 +153,10 @@ def parse_args(argv=None):
     ap.add_argument("--reanalyse-slots", type=int, default=0,
                     help="before each iteration's training, search this many random stored steps again with the current weights and "
                          "overwrite their targets (0: off); with --replay-steps or --trainer device-epoch")
+    ap.add_argument("--refresh-values-every", type=int, default=0,
+                    help="after every N-th iteration's self-play, refresh the bootstrap value of every stored step from the value head "
+                         "(one forward pass per row, one launch: PopulationSelfPlay.refresh_values) and compute the value targets again "
+                         "(0: off); needs --n-step / --n-steps, with --replay-steps or --trainer device-epoch")
     ap.add_argument("--n-step", type=int, default=None,
                     help="value targets are n-step returns over the stored steps (discounted with each net's search gamma) instead of "
                          "the search's root value; 0 keeps the root value (default: off, nothing is kept)")
@@ -184,6 +193,9 @@ def parse_args(argv=None):
     ap.add_argument("--reanalyse-target", action="store_true",
                     help="--reanalyse-slots' searches run with the averaged weights, the engine's target set, instead of the weights as "
                          "last trained; needs --ema-decay and --reanalyse-slots")
+    ap.add_argument("--refresh-target", action="store_true",
+                    help="--refresh-values-every's values come from the averaged weights, the engine's target set (MuZero Reanalyse's "
+                         "value targets); needs --ema-decay and --refresh-values-every")
     ap.add_argument("--eval-target", action="store_true",
                     help="--eval-episodes / --eval-search-episodes score the averaged weights, the engine's target set; needs "
                          "--ema-decay and one of the two")
@@ -347,7 +359,7 @@ def check_ema(a):
     decay, every = getattr(a, "ema_decay", None), getattr(a, "ema_every", 1)
     if decay is None:
         for flag, on in (("--ema-every", every != 1), ("--reanalyse-target", getattr(a, "reanalyse_target", False)),
-                         ("--eval-target", getattr(a, "eval_target", False))):
+                         ("--refresh-target", getattr(a, "refresh_target", False)), ("--eval-target", getattr(a, "eval_target", False))):
             if on:
                 return f"{flag} is about the averaged weights: it needs --ema-decay D"
         return None
@@ -358,6 +370,8 @@ def check_ema(a):
                 "device-fused or device-epoch")
     if getattr(a, "reanalyse_target", False) and not a.reanalyse_slots:
         return "--reanalyse-target chooses the weights of --reanalyse-slots' searches: it needs --reanalyse-slots N"
+    if getattr(a, "refresh_target", False) and not getattr(a, "refresh_values_every", 0):
+        return "--refresh-target chooses the weights of --refresh-values-every's values: it needs --refresh-values-every N"
     if getattr(a, "eval_target", False) and a.eval_episodes <= 0 and getattr(a, "eval_search_episodes", 0) <= 0:
         return "--eval-target chooses the weights of the evaluations: it needs --eval-episodes N or --eval-search-episodes E"
     return None
@@ -417,6 +431,14 @@ def check_replay(a):
                     "per-agent update loop of --trainer torch and the update calls of device and device-fused write none)")
     if getattr(a, "prioritized_online", False) and getattr(a, "prioritized_feedback", None) is None:
         return "--prioritized-online redraws from the learners' own errors: it needs --prioritized-feedback (and --trainer device-epoch)"
+    if getattr(a, "refresh_values_every", 0) < 0:
+        return "--refresh-values-every must be >= 0"
+    if getattr(a, "refresh_values_every", 0):
+        if target_rule(a)["n_step"] is None:
+            return "--refresh-values-every refreshes the values the n-step targets bootstrap from: it needs --n-step N or --n-steps"
+        if not (a.replay_steps or a.trainer == "device-epoch"):
+            return ("--refresh-values-every rewrites values that stay beside the device ring: use it with --replay-steps R (the FIFO "
+                    "ring) or with --trainer device-epoch")
     if a.reanalyse_slots and not (a.replay_steps or a.trainer == "device-epoch"):
         return ("--reanalyse-slots rewrites rows that stay in the device ring: use it with --replay-steps R (the FIFO ring) or with "
                 "--trainer device-epoch; the other modes copy the rows out and clear the ring every iteration")
@@ -513,9 +535,11 @@ def train(a, log=print, on_rows=None, on_end=None):
     # the averaged weights as the engine's target set: what --reanalyse-target's searches and --eval-target's evaluations run with
     reanalyse_nets = {"nets": "target"} if getattr(a, "reanalyse_target", False) else {}
     eval_nets = {"nets": "target"} if getattr(a, "eval_target", False) else {}
+    refresh_every = getattr(a, "refresh_values_every", 0)
+    refresh_nets = {"nets": "target"} if getattr(a, "refresh_target", False) else {}
 
     def upload_target():
-        if reanalyse_nets or eval_nets:
+        if reanalyse_nets or eval_nets or refresh_nets:
             sp.upload_target_flat(trainer.desc, trainer.ema)
 
     upload_target()   # (the average starts as a copy of the weights)
@@ -526,6 +550,10 @@ def train(a, log=print, on_rows=None, on_end=None):
                 sp.reanalyse(by="priority", **reanalyse_nets)
         else:
             sp.reanalyse(n=reanalyse_slots, **reanalyse_nets)
+
+    def refresh(it):   # every stored step's bootstrap value from the value head, then the value targets again
+        if refresh_every and (it + 1) % refresh_every == 0:
+            sp.refresh_values(**refresh_nets)
 
     def pick_rows(k, rng, n):
         """Net k's training rows of this iteration: the device's prioritised draw, else the seed's own uniform pick."""
@@ -546,6 +574,7 @@ def train(a, log=print, on_rows=None, on_end=None):
         if a.trainer == "device-epoch":   # the rows stay in the ring
             rows = None
             n_ring = sp.play_device(a.steps_per_iter)[0] * sp.games_per_net
+            refresh(it)
             if reanalyse_slots:   # stored steps searched again with the weights as last trained: fresh targets, same observations
                 reanalyse()
             sp.engine.sync()
@@ -554,6 +583,7 @@ def train(a, log=print, on_rows=None, on_end=None):
                 from alphazero_gym_amd.agent.buffers import DeviceReplay
                 ring_view = DeviceReplay(sp.engine, 1)
             size = sp.play_device(a.steps_per_iter)[0]
+            refresh(it)
             if reanalyse_slots:
                 reanalyse()
             rows = sp._split(ring_view.rows(), size)

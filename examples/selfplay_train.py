@@ -17,6 +17,9 @@ before each iteration's training and overwrites their targets (DeviceSelfPlay.re
 the discounted search value after them, computed on the device from the transitions kept beside the ring (DeviceSelfPlay n_step=N;
 an episode's terminal step closes the window, a time limit and the newest stored step bootstrap from their own search value).
 --td-lambda L beside it mixes the returns of the windows 1 .. N into a lambda-return (DeviceSelfPlay td_lambda=L; 1: the n-step return).
+--refresh-values-every M (with --n-step and --replay-steps) refreshes, after every M-th iteration's self-play, the value every stored
+step's target bootstraps from: one forward pass of the value head per stored row, one launch (DeviceSelfPlay.refresh_values), instead of
+the value its search left there.
 
 --prioritized-alpha A [--prioritized-eps E], with --replay-steps and --n-step, replaces the uniform pick of training rows by a draw in
 proportion to (|search value - value target| + E)^A, made on the device from priorities kept beside the ring (DeviceSelfPlay
@@ -107,6 +110,10 @@ def parse_args(argv=None):
     ap.add_argument("--td-lambda", type=float, default=None,
                     help="with --n-step N: value targets are lambda-returns, the returns of the windows 1 .. N mixed with weights "
                          "(1 - L) L^(m-1) and the longest taking the rest; 1 is the n-step return, 0 the 1-step return (default: off)")
+    ap.add_argument("--refresh-values-every", type=int, default=0,
+                    help="after every M-th iteration's self-play, refresh the bootstrap value of every stored step from the value head "
+                         "(one forward pass per row, one launch: DeviceSelfPlay.refresh_values) and compute the value targets again "
+                         "(0: off); needs --n-step and --replay-steps")
     ap.add_argument("--prioritized-alpha", type=float, default=None,
                     help="draw the training rows (and with --reanalyse-slots the reanalysed positions) in proportion to "
                          "(|search value - value target| + eps)^alpha on the device instead of uniformly; needs --replay-steps and "
@@ -144,6 +151,11 @@ def parse_args(argv=None):
     if a.reanalyse_slots and not a.replay_steps:
         ap.error("--reanalyse-slots rewrites rows that stay in the device ring: use it with --replay-steps R (the FIFO ring); without it "
                  "every iteration copies its rows out and clears the ring")
+    if a.refresh_values_every < 0:
+        ap.error("--refresh-values-every must be >= 0")
+    if a.refresh_values_every and (a.n_step is None or not a.replay_steps):
+        ap.error("--refresh-values-every refreshes the values the n-step targets bootstrap from, beside the device ring: it needs "
+                 "--n-step N and --replay-steps R")
     if a.prioritized_alpha is not None:
         if not a.replay_steps:
             ap.error("--prioritized-alpha draws from the rows kept in the FIFO ring: use it with --replay-steps R")
@@ -222,6 +234,9 @@ def train(a, log=print):
     for it in range(a.iters):
         if replay_steps:   # the FIFO ring: the newest replay_steps steps stay where they lie, all of them are this iteration's rows
             sp.play(a.steps_per_iter)
+            refresh_every = getattr(a, "refresh_values_every", 0)
+            if refresh_every and (it + 1) % refresh_every == 0:   # every stored step's bootstrap value from the value head
+                sp.refresh_values()
             if reanalyse_slots and prioritized:   # one search per "slot": every game re-searches the position drawn for it
                 for _ in range(reanalyse_slots):
                     sp.reanalyse(by="priority")
